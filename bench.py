@@ -11,7 +11,7 @@ per-branch sufficient statistics J/D reduced after each of the 50 batch sweeps.
 Inputs are resident in HBM before the timed region; file IO, upload/download and the
 O(8) host M-step are outside it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 runs the product's C++ EM driver, epv::SingleSiteSampler (epievo_amd/csrc/host/epv_sampler.cpp,
 the class the epievo_* CLIs use) through libepv_driver.so.  The genome of N * n sites is cut into
 contiguous shards with wide halos that each GPU updates redundantly (the RNG is keyed by the
@@ -23,6 +23,10 @@ rehearses four slots on one GPU through the loopback transport); under
 communicator with ncclCommInitRank (torch.distributed/gloo only carries the id, the barriers and
 the max over ranks).  N = 1: n = 1e6 (BASELINE config 3, the metric's); N > 1: 1.25e6 per GPU,
 i.e. BASELINE config 4's n = 1e7 at N = 8.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes, after the timed steps, what the last of them handed its caller as
+DIR/<name>.npy (see dump_outputs); the inputs depend only on the arguments, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +44,9 @@ SEED = 42
 # HIP events around every 7th colour-phase launch of each context (coprime with the three colours, so
 # all of them are sampled): events around EVERY launch cost 4 % of the step they are meant to measure
 TIMING_EVERY = 7
+# --dump-outputs: the paths of at most this many sites (a fixed, seeded sample), all files within DUMP_BYTES
+DUMP_SITES = 65536
+DUMP_BYTES = 64 << 20
 
 
 def algorithmic_bytes_per_resample(kbar, n_branches):
@@ -125,6 +132,37 @@ def cpu_baseline(model, tree, fp, budget_s=20.0):
     return out
 
 
+def dump_outputs(outdir, result, fp):
+    """DIR/<name>.npy of one step's outputs: J.npy and D.npy, the per-branch sufficient statistics of the
+    batch (float64, as run_mcmc returns them), acceptance_rate.npy, and the sampled paths the next EM
+    iteration starts from, on a seeded sample of this process's sites: paths_sites.npy (site index),
+    paths_init.npy and paths_njumps.npy ([branch, sampled site]: start state, number of jumps) and
+    paths_jumps.npy (their jump times, branch by branch, site by site)."""
+    import numpy as np
+    J, D, acc = result
+    n, B = fp.n_sites, fp.n_nodes - 1
+    pick = np.random.RandomState(SEED).permutation(n)[:DUMP_SITES]
+    counts = np.diff(fp.offsets).astype(np.int64).reshape(B, n)
+    k = len(pick)
+    while True:
+        sites = np.sort(pick[:k])
+        edges = (np.arange(B)[:, None] * n + sites[None, :]).reshape(-1)
+        cnt = counts.reshape(-1)[edges]
+        if k == 1 or 8 * (len(J) + len(D) + 1 + len(sites) + int(cnt.sum())) + 8 * len(edges) <= DUMP_BYTES:
+            break
+        k //= 2
+    starts = fp.offsets[:-1][edges].astype(np.int64)
+    take = np.repeat(starts - np.concatenate(([0], np.cumsum(cnt)[:-1])), cnt) + np.arange(int(cnt.sum()))
+    out = {"J": np.asarray(J, np.float64), "D": np.asarray(D, np.float64),
+           "acceptance_rate": np.array([acc], np.float64), "paths_sites": sites.astype(np.float64),
+           "paths_init": fp.init[edges].astype(np.float32).reshape(B, len(sites)),
+           "paths_njumps": cnt.astype(np.float32).reshape(B, len(sites)),
+           "paths_jumps": np.asarray(fp.jumps, np.float64)[take]}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 class CppEngine:
     """the product's C++ EM driver (epv::SingleSiteSampler through libepv_driver.so): every GPU of
     the run in this process (ncclCommInitAll), or -- under torch.distributed.run -- this rank's GPU
@@ -166,6 +204,9 @@ class CppEngine:
     def step(self, i):
         self.s.reset(self.model)
         return self.s.run_mcmc(SEED, i)
+
+    def paths(self):
+        return self.s.paths()
 
     def set_timing(self, every):
         self.s.set_timing(every)
@@ -210,6 +251,9 @@ class TorchEngine:
         self.ss.reset()
         return self.ss.run_mcmc(BURN_IN, BATCH, SEED, sweep_base=i * (BURN_IN + BATCH))
 
+    def paths(self):
+        return self.ss.owned_paths()
+
     def set_timing(self, every):
         self.ss.dev.set_timing(every)
 
@@ -242,6 +286,9 @@ def main():
                     help="cpp: the product's C++ EM driver epv::SingleSiteSampler (what the epievo_* CLIs run), every "
                          "GPU in this process when launched plainly, one rank per GPU under torch.distributed.run; "
                          "torch: the Python driver over torch.distributed (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (J, D, acceptance rate, a "
+                         "seeded sample of the paths) as DIR/<name>.npy; rank 0 only")
     ap.add_argument("--shards-per-gpu", type=int, default=0,
                     help="contexts per GPU: their launches fill each other's tails; results are bit-identical "
                          "to 1.  0 = by tree size: 3 on small trees (fused colour phase), 2 on large ones")
@@ -249,6 +296,8 @@ def main():
                     help="--driver torch only: nccl (= RCCL) or gloo (lets several ranks share one GPU to "
                          "rehearse the N>1 code path on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -340,10 +389,12 @@ def main():
     eng.set_timing(TIMING_EVERY)  # HIP events around every TIMING_EVERY-th colour-phase launch of each context
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     barrier()
     el = time.perf_counter() - t0
     eng.set_timing(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, eng.paths())   # before the reference leg moves the paths on
     avg_ms, n_launch = eng.kernel_time_ms()
 
     def rank_max(x):

@@ -2,14 +2,27 @@
 include/epievo_mi355x.h declares; the product has no CPU fallback, so creating a context
 here must fail cleanly rather than route elsewhere."""
 import ctypes
+import functools
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 
 from epievo_amd import _build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu_present():
+    """whether torch sees a GPU, asked in a child process: torch brings its own HIP runtime, and
+    initialising it in this process before the product's libraries open the device leaves every
+    later context of the suite without one"""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"],
+                       capture_output=True, text=True, check=True)
+    return r.stdout.split()[-1] == "1"
 
 
 def _declared(header="epievo_mi355x.h"):
@@ -38,16 +51,14 @@ def test_exchange_library_exports_every_declared_symbol():
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
     # no device here: setting up ranks fails cleanly (no fallback transport for a missing GPU)
-    import torch
-    if not torch.cuda.is_available():
+    if not _gpu_present():
         comms = (ctypes.c_void_p * 2)()
         devs = (ctypes.c_int * 2)(0, 0)
         assert L.epv_comm_init_all(2, devs, comms) != 0
 
 
 def test_no_cpu_fallback():
-    import torch
-    if torch.cuda.is_available():
+    if _gpu_present():
         pytest.skip("a GPU is present")
     from epievo_amd.sampler import DeviceSampler
     with pytest.raises(RuntimeError, match="no usable HIP device"):

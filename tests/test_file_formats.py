@@ -10,8 +10,8 @@ own writers and readers, not against round trips through the product's code:
   Newick        PhyloTree operator>> + Newick_format (PhyloTree.cpp:110-122,189-203), TreeHelper
   param         EpiEvoModel::format_for_param_file (EpiEvoModel.cpp:192-200) -- see test_host_model.py
 
-Two layers: live against oracle/_ref where it exists (this container and the GPU box, which
-receives the built .so), and against tests/golden/text/* -- files WRITTEN BY THE REFERENCE
+Two layers: live against oracle/_ref where it exists (its outputs stored in tests/golden/ref/ stand in
+for it elsewhere, tests/refvec.py), and against tests/golden/text/* -- files WRITTEN BY THE REFERENCE
 (tests/golden/make_golden.py) -- everywhere."""
 import ctypes as C
 import os
@@ -20,11 +20,11 @@ import numpy as np
 import pytest
 
 import orc
+import refvec
 from common import GOLDEN, simulate, config, ref_test_model, TREE_NWK_TEXT, EXTRA_TREES
 from epievo_amd import host
 
 TEXT = os.path.join(GOLDEN, "text")
-need_ref = pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 dp, u8p, u32p, u64p = (C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64))
 
 
@@ -70,19 +70,30 @@ def ref_read_paths(path):
     return host.FlatPaths(n, nn.value, init, off, jumps[:tot.value]), names.value.decode().split("\n"), tt
 
 
-@need_ref
 @pytest.mark.parametrize("cfg,n", [("tree", 257), ("pair", 100), ("cat6", 50)])
 def test_local_paths_writer_and_reader_against_the_reference(tmp_path, cfg, n):
     tree, fp = awkward_paths(cfg, n)
     tt = tree.branches * 1.0000000000000002 + 1e-17        # values that need all 17 digits
     d = str(tmp_path)
-    ref_write_paths(d + "/ref.paths", tree, tt, fp)
     host.write_paths(d + "/own.paths", tree.node_names, tt, fp)
-    assert open(d + "/own.paths", "rb").read() == open(d + "/ref.paths", "rb").read()
+    own_bytes = open(d + "/own.paths", "rb").read()
+
+    def reference():
+        ref_write_paths(d + "/ref.paths", tree, tt, fp)
+        ref, names2, t2 = ref_read_paths(d + "/own.paths")
+        return dict(written=refvec.pack_text(open(d + "/ref.paths", "rb").read()), read_from=refvec.pack_text(own_bytes),
+                    names=refvec.pack_text("\n".join(names2)), tot_times=t2, **refvec.pack_paths("read", ref))
+
+    r = refvec.reference_outputs("local_paths_%s_n%d" % (cfg, n), reference)
+    ref_bytes = bytes(r["written"])
+    assert own_bytes == ref_bytes
     # each reader on the OTHER side's file: the same values, bit for bit
+    open(d + "/ref.paths", "wb").write(ref_bytes)
     own, names, t1 = host.read_paths(d + "/ref.paths")
     assert names == tree.node_names and np.array_equal(t1[1:], tt[1:]) and orc.paths_equal(own, fp)
-    ref, names2, t2 = ref_read_paths(d + "/own.paths")
+    # (the stored reading is of the product's file as written now)
+    assert bytes(r["read_from"]) == own_bytes
+    ref, names2, t2 = refvec.unpack_paths("read", r), refvec.unpack_text(r["names"]).split("\n"), r["tot_times"]
     assert names2 == tree.node_names and np.array_equal(t2[1:], tt[1:]) and orc.paths_equal(ref, fp)
 
 
@@ -128,35 +139,45 @@ def own_read_global(path):
     return root, off, tt[:tot.value], pp[:tot.value], names.value.decode().split("\n")
 
 
-@need_ref
 def test_global_jumps_writer_and_reader_against_the_reference(tmp_path):
     tree, n = config("tree"), 300
     seqs, off, tt, pp = _fwd(11, tree, n)
     d = str(tmp_path)
     own_write_global(d + "/own.jumps", tree, n, seqs, off, tt, pp)
-    L = orc.ref_lib()
-    L.ref_write_global_jumps.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_uint64, u8p, u64p, dp, u64p]
+    own_bytes = open(d + "/own.jumps", "rb").read()
     root = np.ascontiguousarray(seqs[:n])
-    assert L.ref_write_global_jumps((d + "/ref.jumps").encode(), tree.n_nodes, "\n".join(tree.node_names).encode(),
-                                    n, orc._p(root, C.c_uint8), orc._p(off, C.c_uint64), orc._p(tt, C.c_double),
-                                    orc._p(pp, C.c_uint64)) == 0
-    assert open(d + "/own.jumps", "rb").read() == open(d + "/ref.jumps", "rb").read()
+
+    def reference():
+        L = orc.ref_lib()
+        L.ref_write_global_jumps.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_uint64, u8p, u64p, dp, u64p]
+        assert L.ref_write_global_jumps((d + "/ref.jumps").encode(), tree.n_nodes,
+                                        "\n".join(tree.node_names).encode(), n, orc._p(root, C.c_uint8),
+                                        orc._p(off, C.c_uint64), orc._p(tt, C.c_double), orc._p(pp, C.c_uint64)) == 0
+        # the reference's reader on the product's file
+        L.ref_read_global_jumps.argtypes = [C.c_char_p, C.POINTER(C.c_int), u64p, u64p]
+        L.ref_global_jumps_copy.argtypes = [u8p, u64p, dp, u64p, C.c_char_p, C.c_uint64]
+        nn, ns, tot = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        assert L.ref_read_global_jumps((d + "/own.jumps").encode(), C.byref(nn), C.byref(ns), C.byref(tot)) == 0
+        r3, o3 = np.zeros(ns.value, np.uint8), np.zeros(nn.value + 1, np.uint64)
+        t3, p3 = np.zeros(max(tot.value, 1)), np.zeros(max(tot.value, 1), np.uint64)
+        nb = C.create_string_buffer(1 << 16)
+        assert L.ref_global_jumps_copy(orc._p(r3, C.c_uint8), orc._p(o3, C.c_uint64), orc._p(t3, C.c_double),
+                                       orc._p(p3, C.c_uint64), nb, len(nb)) == 0
+        return dict(written=refvec.pack_text(open(d + "/ref.jumps", "rb").read()), read_from=refvec.pack_text(own_bytes),
+                    sizes=np.array([nn.value, ns.value, tot.value], np.uint64), root=r3, off=o3,
+                    t=t3[:tot.value], p=p3[:tot.value], names=refvec.pack_text(nb.value))
+
+    r = refvec.reference_outputs("global_jumps_tree_n300_s11", reference)
+    assert own_bytes == bytes(r["written"])
+    open(d + "/ref.jumps", "wb").write(bytes(r["written"]))
     r2, o2, t2, p2, names = own_read_global(d + "/ref.jumps")
     assert np.array_equal(r2, root) and np.array_equal(o2, off) and np.array_equal(t2, tt) and np.array_equal(p2, pp)
     assert names == tree.node_names
-    # the reference's reader on the product's file
-    L.ref_read_global_jumps.argtypes = [C.c_char_p, C.POINTER(C.c_int), u64p, u64p]
-    L.ref_global_jumps_copy.argtypes = [u8p, u64p, dp, u64p, C.c_char_p, C.c_uint64]
-    nn, ns, tot = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
-    assert L.ref_read_global_jumps((d + "/own.jumps").encode(), C.byref(nn), C.byref(ns), C.byref(tot)) == 0
-    assert (nn.value, ns.value, tot.value) == (tree.n_nodes, n, len(tt))
-    r3, o3 = np.zeros(n, np.uint8), np.zeros(nn.value + 1, np.uint64)
-    t3, p3 = np.zeros(max(tot.value, 1)), np.zeros(max(tot.value, 1), np.uint64)
-    nb = C.create_string_buffer(1 << 16)
-    assert L.ref_global_jumps_copy(orc._p(r3, C.c_uint8), orc._p(o3, C.c_uint64), orc._p(t3, C.c_double),
-                                   orc._p(p3, C.c_uint64), nb, len(nb)) == 0
-    assert np.array_equal(r3, root) and np.array_equal(o3, off) and np.array_equal(t3[:tot.value], tt)
-    assert np.array_equal(p3[:tot.value], pp) and nb.value.decode().split("\n") == tree.node_names
+    # the reference's reader on the product's file (as written now)
+    assert bytes(r["read_from"]) == own_bytes
+    assert tuple(int(x) for x in r["sizes"]) == (tree.n_nodes, n, len(tt))
+    assert np.array_equal(r["root"], root) and np.array_equal(r["off"], off) and np.array_equal(r["t"], tt)
+    assert np.array_equal(r["p"], pp) and refvec.unpack_text(r["names"]).split("\n") == tree.node_names
 
 
 def test_global_jumps_against_reference_written_fixture(tmp_path):
@@ -169,7 +190,6 @@ def test_global_jumps_against_reference_written_fixture(tmp_path):
     assert open(str(tmp_path / "w.jumps"), "rb").read() == open(os.path.join(TEXT, "tree_n60.jumps"), "rb").read()
 
 
-@need_ref
 @pytest.mark.parametrize("only_leaves", [0, 1])
 def test_states_file_is_read_by_the_reference(tmp_path, only_leaves):
     tree, n = config("tree"), 123
@@ -180,18 +200,26 @@ def test_states_file_is_read_by_the_reference(tmp_path, only_leaves):
     flat = np.ascontiguousarray(seqs.reshape(-1))
     assert L.epvh_write_states(path.encode(), only_leaves, tree.n_nodes, orc._p(tree.subtree_sizes, C.c_uint32),
                                "\n".join(tree.node_names).encode(), n, orc._p(flat, C.c_uint8)) == 0
-    R = orc.ref_lib()
-    R.ref_read_states.argtypes = [C.c_char_p, C.POINTER(C.c_int), u64p]
-    R.ref_states_copy.argtypes = [u8p, C.c_char_p, C.c_uint64]
-    ns, nsites = C.c_int(0), C.c_uint64(0)
-    assert R.ref_read_states(path.encode(), C.byref(ns), C.byref(nsites)) == 0
+    own_bytes = open(path, "rb").read()
+
+    def reference():
+        R = orc.ref_lib()
+        R.ref_read_states.argtypes = [C.c_char_p, C.POINTER(C.c_int), u64p]
+        R.ref_states_copy.argtypes = [u8p, C.c_char_p, C.c_uint64]
+        ns, nsites = C.c_int(0), C.c_uint64(0)
+        assert R.ref_read_states(path.encode(), C.byref(ns), C.byref(nsites)) == 0
+        out = np.zeros(ns.value * nsites.value, np.uint8)
+        nb = C.create_string_buffer(1 << 12)
+        assert R.ref_states_copy(orc._p(out, C.c_uint8), nb, len(nb)) == 0
+        return dict(read_from=refvec.pack_text(own_bytes), sizes=np.array([ns.value, nsites.value], np.uint64),
+                    states=out, names=refvec.pack_text(nb.value))
+
+    r = refvec.reference_outputs("states_tree_n123_leaves%d" % only_leaves, reference)
+    assert bytes(r["read_from"]) == own_bytes     # the stored reading is of the file written now
     keep = [i for i in range(tree.n_nodes) if not only_leaves or tree.subtree_sizes[i] == 1]
-    assert (ns.value, nsites.value) == (len(keep), n)
-    out = np.zeros(len(keep) * n, np.uint8)
-    nb = C.create_string_buffer(1 << 12)
-    assert R.ref_states_copy(orc._p(out, C.c_uint8), nb, len(nb)) == 0
-    assert np.array_equal(out.reshape(len(keep), n), seqs[keep])
-    assert nb.value.decode().split("\n") == [tree.node_names[i] for i in keep]
+    assert tuple(int(x) for x in r["sizes"]) == (len(keep), n)
+    assert np.array_equal(r["states"].reshape(len(keep), n), seqs[keep])
+    assert refvec.unpack_text(r["names"]).split("\n") == [tree.node_names[i] for i in keep]
 
 
 NEWICKS = [TREE_NWK_TEXT] + list(EXTRA_TREES.values()) + [
@@ -200,30 +228,36 @@ NEWICKS = [TREE_NWK_TEXT] + list(EXTRA_TREES.values()) + [
 ]
 
 
-@need_ref
 @pytest.mark.parametrize("text", NEWICKS)
 def test_newick_parse_and_print_against_the_reference(tmp_path, text):
-    R = orc.ref_lib()
-    R.ref_newick_roundtrip.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int), u32p, u32p, dp,
-                                       C.c_char_p, C.c_uint64]
-    out, names = C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 14)
-    nn = C.c_int(0)
-    pa, st, br = np.zeros(256, np.uint32), np.zeros(256, np.uint32), np.zeros(256)
-    assert R.ref_newick_roundtrip(text.encode(), out, len(out), C.byref(nn), orc._p(pa, C.c_uint32),
-                                  orc._p(st, C.c_uint32), orc._p(br, C.c_double), names, len(names)) == 0
+    def reference():
+        R = orc.ref_lib()
+        R.ref_newick_roundtrip.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_int), u32p, u32p, dp,
+                                           C.c_char_p, C.c_uint64]
+        out, names = C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 14)
+        nn = C.c_int(0)
+        pa, st, br = np.zeros(256, np.uint32), np.zeros(256, np.uint32), np.zeros(256)
+        assert R.ref_newick_roundtrip(text.encode(), out, len(out), C.byref(nn), orc._p(pa, C.c_uint32),
+                                      orc._p(st, C.c_uint32), orc._p(br, C.c_double), names, len(names)) == 0
+        N = nn.value
+        return dict(text=refvec.pack_text(text), parent=pa[:N], subtree=st[:N], branches=br[:N],
+                    names=refvec.pack_text(names.value), printed=refvec.pack_text(out.value))
+
+    r = refvec.reference_outputs("newick_%d" % NEWICKS.index(text), reference)
+    assert refvec.unpack_text(r["text"]) == text
     p = str(tmp_path / "t.nwk")
     open(p, "w").write(text)
     t = host.Tree.read(p)
-    N = nn.value
+    N = len(r["parent"])
     assert t.n_nodes == N
-    assert np.array_equal(t.parent_ids, pa[:N]) and np.array_equal(t.subtree_sizes, st[:N])
-    assert np.array_equal(t.branches, br[:N])
-    assert t.node_names == names.value.decode().split("\n")
+    assert np.array_equal(t.parent_ids, r["parent"]) and np.array_equal(t.subtree_sizes, r["subtree"])
+    assert np.array_equal(t.branches, r["branches"])
+    assert t.node_names == refvec.unpack_text(r["names"]).split("\n")
     L = host.lib()
     L.epvh_tree_newick.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     own = C.create_string_buffer(1 << 14)
     assert L.epvh_tree_newick(p.encode(), own, len(own)) == 0
-    assert own.value == out.value
+    assert own.value == bytes(r["printed"])
 
 
 def test_local_paths_io_on_several_threads_is_the_sequential_io(tmp_path, monkeypatch):

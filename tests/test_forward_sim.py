@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import orc
+import refvec
 from common import GOLDEN, config, ref_test_model, TEST_PARAM_TEXT, TREE_NWK_TEXT
 from epievo_amd import _build, host
 
@@ -36,13 +37,16 @@ def test_forward_sim_matches_golden():
         assert np.array_equal(tt, g["fwd_%s_t" % cfg]) and np.array_equal(pp, g["fwd_%s_p" % cfg])
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("cfg,n,seed", [("tree", 5000, 1), ("pair", 3000, 7), ("bal16", 800, 3), ("tree", 3, 5)])
 def test_forward_sim_matches_linked_triplet_sampler(cfg, n, seed):
+    """(against the reference's stored outputs, tests/golden/ref/, where oracle/_ref is absent)"""
     m, tree = ref_test_model(), config(cfg)
     a = _run(host.lib().epvh_forward_sim, seed, m, tree, n)
-    b = _run(orc.ref_lib().ref_forward_sim, seed, m, tree, n)
-    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    keys = ("seqs", "off", "t", "p")
+    g = refvec.reference_outputs("forward_sim_%s_n%d_s%d" % (cfg, n, seed), lambda: dict(
+        zip(keys, _run(orc.ref_lib().ref_forward_sim, seed, m, tree, n))))
+    b = [g[k] for k in keys]
+    assert all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
 
 
 def test_sim_and_convert_clis(tmp_path):

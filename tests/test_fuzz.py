@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import orc
+import refvec
 from common import _tmp
 from epievo_amd import host
 
@@ -41,20 +42,26 @@ def _random_case(case):
     return tree, model, fp, cap, seed
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("case", range(12))
 def test_random_case_rung_a_vs_linked_reference(case):
-    """the same random inputs, reference-schedule rung against the LINKED reference, live"""
+    """the same random inputs, reference-schedule rung against the LINKED reference, live
+    (against its stored outputs, tests/golden/ref/, where oracle/_ref is absent)"""
     tree, model, fp, cap, seed = _random_case(case)
+
+    def reference():
+        R = orc.Reference(tree, model, fp, seed=seed & 0xffffffff)
+        R.reset(1, 2)
+        llh0 = R.tri_llh()
+        Jr, Dr, accr = R.run_mcmc()
+        return dict(llh0=llh0, J=Jr, D=Dr, acc=np.float64(accr), **refvec.pack_paths("paths", R.paths()))
+
+    r = refvec.reference_outputs("fuzz_case%d" % case, reference)
     o = orc.Oracle(tree, model, fp, "A", seed=seed & 0xffffffff)
-    R = orc.Reference(tree, model, fp, seed=seed & 0xffffffff)
     o.reset()
-    R.reset(1, 2)
-    assert np.array_equal(o.tri_llh(), R.tri_llh())
+    assert np.array_equal(o.tri_llh(), r["llh0"])
     Jo, Do, nacc, acc = o.run_mcmc(1, 2)
-    Jr, Dr, accr = R.run_mcmc()
-    assert np.array_equal(Jo, Jr) and np.array_equal(Do, Dr) and acc == accr
-    assert orc.paths_equal(o.paths(), R.paths())
+    assert np.array_equal(Jo, r["J"]) and np.array_equal(Do, r["D"]) and acc == float(r["acc"])
+    assert orc.paths_equal(o.paths(), refvec.unpack_paths("paths", r))
 
 
 @pytest.mark.gpu

@@ -97,22 +97,32 @@ def _states_from_paths(tree, fp):
 def test_indep_m_steps_match_linked_reference():
     """estimate_rates_indep / estimate_rates_and_branches_indep (IndepSite.cpp:299-360)"""
     import orc
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built")
+    import refvec
     from common import simulate
     for cfg in ("tree", "bal16"):
         model, tree, fp = simulate(cfg, 800, seed=3)
-        R = orc.Reference(tree, model, fp)
-        J, D = R.indep_suffstats()
+
+        def reference():
+            R = orc.Reference(tree, model, fp)
+            out = {}
+            out["J"], out["D"] = R.indep_suffstats()
+            for opt in (False, True):
+                R2 = orc.Reference(tree, model, fp)
+                out["r%d" % opt], out["br%d" % opt] = R2.indep_m_step(opt, out["J"], out["D"], np.array([0.4, 0.9]),
+                                                                      tree.n_nodes)
+                if opt:
+                    out.update(refvec.pack_paths("paths", R2.paths()))
+            return out
+
+        g = refvec.reference_outputs("indep_m_step_%s_n800_s3" % cfg, reference)
+        J, D = g["J"], g["D"]
         for opt in (False, True):
-            R2 = orc.Reference(tree, model, fp)
-            r_ref, br_ref = R2.indep_m_step(opt, J, D, np.array([0.4, 0.9]), tree.n_nodes)
             r, br = host.indep_m_step(np.array([0.4, 0.9]), tree.branches, J, D, optimize_branches=opt)
-            assert np.array_equal(r, r_ref) and np.array_equal(br, br_ref)
+            assert np.array_equal(r, g["r%d" % opt]) and np.array_equal(br, g["br%d" % opt])
             if opt:   # the reference also rescaled its paths: the same as scale_jump_times
                 o = orc.Oracle(tree, model, fp, "A")
                 o.scale_jump_times(br)
-                assert orc.paths_equal(o.paths(), R2.paths())
+                assert orc.paths_equal(o.paths(), refvec.unpack_paths("paths", g))
 
 
 def test_heuristic_initial_paths_invariants():

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import orc
+import refvec
 from common import GOLDEN
 from epievo_amd import host
 
@@ -95,26 +96,31 @@ def test_kat_ctmc_segments_suffstats_rng():
         assert np.array_equal(d, g["mt_%d" % seed])
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("cfg,n,seed", [("tree", 3000, 7), ("pair", 2500, 9), ("bal16", 600, 3),
                                         ("tree", 3, 1), ("tree", 4, 1), ("pair", 5, 2)])
 def test_rung_a_vs_linked_reference_live(cfg, n, seed):
-    """beyond the stored vectors: fresh inputs, compared live against the linked reference"""
+    """beyond the stored vectors: fresh inputs, compared live against the linked reference
+    (against its stored outputs, tests/golden/ref/, where oracle/_ref is absent)"""
     from common import simulate
     model, tree, fp = simulate(cfg, n, seed=seed)
+
+    def reference():
+        R = orc.Reference(tree, model, fp, seed=seed)
+        R.reset(2, 3)
+        llh0 = R.tri_llh()
+        Jr, Dr, accr = R.run_mcmc()
+        return dict(llh0=llh0, J=Jr, D=Dr, acc=np.float64(accr), llh=R.tri_llh(), **refvec.pack_paths("paths", R.paths()))
+
+    r = refvec.reference_outputs("rung_a_live_%s_n%d_s%d" % (cfg, n, seed), reference)
     o = orc.Oracle(tree, model, fp, "A", seed=seed)
-    R = orc.Reference(tree, model, fp, seed=seed)
     o.reset()
-    R.reset(2, 3)
-    assert np.array_equal(o.tri_llh(), R.tri_llh())
+    assert np.array_equal(o.tri_llh(), r["llh0"])
     Jo, Do, nacc, acc = o.run_mcmc(2, 3)
-    Jr, Dr, accr = R.run_mcmc()
-    assert np.array_equal(Jo, Jr) and np.array_equal(Do, Dr) and acc == accr
-    assert orc.paths_equal(o.paths(), R.paths())
-    assert np.array_equal(o.tri_llh(), R.tri_llh())
+    assert np.array_equal(Jo, r["J"]) and np.array_equal(Do, r["D"]) and acc == float(r["acc"])
+    assert orc.paths_equal(o.paths(), refvec.unpack_paths("paths", r))
+    assert np.array_equal(o.tri_llh(), r["llh"])
 
 
-@pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("n,seed", [(2000, 1), (37, 5), (3, 2)])
 def test_init_paths_indep_rung_a_vs_linked_reference(n, seed):
     """initialize_paths_indep (epievo_sim_pairwise.cpp:62-110): the oracle in
@@ -124,8 +130,9 @@ def test_init_paths_indep_rung_a_vs_linked_reference(n, seed):
     root = fp.init
     leaf = fp.init ^ (fp.counts() & 1).astype(np.uint8)
     a = orc.init_paths_indep("orc", seed, model.rates, root, leaf, 1.0, "A")
-    r = orc.init_paths_indep("ref", seed, model.rates, root, leaf, 1.0)
-    assert orc.paths_equal(a, r)
+    r = refvec.reference_outputs("init_paths_indep_n%d_s%d" % (n, seed), lambda: refvec.pack_paths(
+        "paths", orc.init_paths_indep("ref", seed, model.rates, root, leaf, 1.0)))
+    assert orc.paths_equal(a, refvec.unpack_paths("paths", r))
 
 
 def test_end_cond_samplers_match_linked_reference():

@@ -7,35 +7,43 @@ import numpy as np
 import pytest
 
 import orc
+import refvec
 from common import simulate
 
-need_ref = pytest.mark.skipif(not orc.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
 
-
-@need_ref
 @pytest.mark.parametrize("cfg,n,seed", [("tree", 400, 3), ("pair", 300, 5), ("cat6", 120, 7)])
 def test_rung_a_with_sample_root_equals_the_linked_reference(cfg, n, seed):
+    """(against the reference's stored outputs, tests/golden/ref/, where oracle/_ref is absent)"""
     model, tree, fp = simulate(cfg, n, seed=seed)
-    orc.ref_lib().ref_set_sample_root(1)
-    try:
-        r = orc.Reference(tree, model, fp, seed=seed)
-        r.reset(1, 2)
-        o = orc.Oracle(tree, model, fp, "A", seed=seed)
-        o.set_sample_root(True)
-        o.reset()
-        for k in range(3):
-            assert r.sweeps(1) == o.sweep(k)
-            assert orc.paths_equal(r.paths(), o.paths())
-        assert np.array_equal(r.tri_llh()[1:-1], o.tri_llh()[1:-1]) or True   # (the reference caches privately)
-        Jr, Dr, acc_r = r.run_mcmc()
-        Jo, Do, nacc, acc_o = o.run_mcmc(1, 2)
-        assert np.array_equal(Jr, Jo) and np.array_equal(Dr, Do) and acc_r == acc_o
-        # root states did change somewhere (that is the point of the option)
-        B = tree.n_nodes - 1
-        root_child = [b for b in range(B) if tree.parent_ids[b + 1] == 0][0]
-        assert (o.paths().init.reshape(B, n)[root_child] != fp.init.reshape(B, n)[root_child]).sum() > 0
-    finally:
-        orc.ref_lib().ref_set_sample_root(0)
+
+    def reference():
+        orc.ref_lib().ref_set_sample_root(1)
+        try:
+            r = orc.Reference(tree, model, fp, seed=seed)
+            r.reset(1, 2)
+            out = {}
+            for k in range(3):
+                out["acc%d" % k] = np.int64(r.sweeps(1))
+                out.update(refvec.pack_paths("paths%d" % k, r.paths()))
+            out["J"], out["D"], acc_r = r.run_mcmc()
+            out["acc"] = np.float64(acc_r)
+            return out
+        finally:
+            orc.ref_lib().ref_set_sample_root(0)
+
+    r = refvec.reference_outputs("sample_root_%s_n%d_s%d" % (cfg, n, seed), reference)
+    o = orc.Oracle(tree, model, fp, "A", seed=seed)
+    o.set_sample_root(True)
+    o.reset()
+    for k in range(3):
+        assert int(r["acc%d" % k]) == o.sweep(k)
+        assert orc.paths_equal(refvec.unpack_paths("paths%d" % k, r), o.paths())
+    Jo, Do, nacc, acc_o = o.run_mcmc(1, 2)
+    assert np.array_equal(r["J"], Jo) and np.array_equal(r["D"], Do) and float(r["acc"]) == acc_o
+    # root states did change somewhere (that is the point of the option)
+    B = tree.n_nodes - 1
+    root_child = [b for b in range(B) if tree.parent_ids[b + 1] == 0][0]
+    assert (o.paths().init.reshape(B, n)[root_child] != fp.init.reshape(B, n)[root_child]).sum() > 0
 
 
 def test_rung_b_sample_root_keeps_the_process_consistent():
