@@ -19,6 +19,7 @@
 
 #include "epv_kernels.h"  // all __global__ kernels (single translation unit, no -fgpu-rdc)
 #include "epv_math.h"
+#include "epv_pavg.h"
 
 struct epv_ctx {
   int device = 0;
@@ -105,6 +106,16 @@ struct epv_ctx {
   size_t ev_used = 0;
   double timed_ms = 0.0;
   uint64_t timed_launches = 0;
+  // average history of the sampled paths (epv_pavg.h), off while pa_P == 0
+  uint32_t pa_P = 0;
+  int32_t *d_pa = nullptr;         // [B][P][pa_cnt] counts over local sites pa_lo .. pa_lo + pa_cnt - 1
+  uint64_t pa_lo = 0, pa_cnt = 0, pa_n = 0, pa_g0 = 0;   // the site range d_pa was laid out for
+  uint32_t pa_B = 0;
+  uint64_t pa_samples = 0;
+  double *d_pa_grid = nullptr;     // [B][P] grid times
+  std::vector<double> pa_grid_blen;  // the branch lengths d_pa_grid was built from
+  uint32_t *d_pa_out = nullptr;    // read-out staging
+  uint64_t pa_out_cap = 0;         // bytes
 };
 
 namespace {
@@ -543,6 +554,89 @@ int launch_suffstats(epv_ctx *c, uint64_t slot) {
   return reduce_blocks_to_tot(c, c->d_partial[0], nb, 1u, slot);
 }
 
+// ---- path average (epv_pavg.h).  A context counts its owned sites, and the genome's two end sites
+// when it holds them (the sampler never changes those, so owned_range leaves them out): over all
+// contexts and GPUs every site is counted once.
+void pavg_range(const epv_ctx *c, uint64_t *lo, uint64_t *cnt) {
+  uint64_t a = 0, b = 0;
+  owned_range(c, &a, &b);
+  if (a == 1u && c->S.g0 == 0u) a = 0u;
+  if (b + 2u == c->S.n && c->S.g0 + c->S.n == c->S.n_global) b = c->S.n - 1u;
+  *lo = a;
+  *cnt = b >= a ? b - a + 1u : 0u;
+}
+// (re)lay out the counts for the current site range; zeroes them
+int pavg_alloc(epv_ctx *c) {
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_pa);
+  c->pa_cnt = 0;
+  const double need = 4.0 * (double)c->S.B * (double)cnt * (double)c->pa_P;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (a margin for the read-out and the kernels' own needs)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "path average of %u points needs %.3g GB of device memory (4 B x %u branches x "
+                  "%llu sites x %u points); %.3g GB are free: use fewer points or more GPUs (averaging is off)",
+                  c->pa_P, need / 1e9, c->S.B, (unsigned long long)cnt, c->pa_P, (double)free_b / 1e9);
+    c->pa_P = 0;
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t bytes = (size_t)4u * c->S.B * cnt * c->pa_P;
+  if (bytes) {
+    HIP_TRY(c, hipMalloc(&c->d_pa, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->d_pa, 0, bytes, c->stream));
+  }
+  c->pa_lo = lo;
+  c->pa_cnt = cnt;
+  c->pa_n = c->S.n;
+  c->pa_g0 = c->S.g0;
+  c->pa_B = c->S.B;
+  c->pa_samples = 0;
+  c->pa_grid_blen.clear();
+  return EPV_OK;
+}
+// the counts match the current site range, the grid the current branch lengths
+int ensure_pavg(epv_ctx *c) {
+  if (!c->pa_P) return EPV_OK;
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  if (lo != c->pa_lo || cnt != c->pa_cnt || c->S.n != c->pa_n || c->S.g0 != c->pa_g0 || c->S.B != c->pa_B) {
+    if (c->pa_samples)
+      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the path average took samples: "
+                                    "epv_set_path_average again");
+    int rc = pavg_alloc(c);
+    if (rc) return rc;
+  }
+  if (c->pa_grid_blen == c->blen) return EPV_OK;
+  const uint32_t P = c->pa_P, B = c->S.B;
+  std::vector<double> g((size_t)B * P);
+  for (uint32_t b = 0; b < B; ++b) {   // average_paths.cpp:33-42: t_1 = bin, t_{i+1} = t_i + bin
+    const double bin = c->blen[b + 1u] / (double)(P - 1u);
+    double t = bin;
+    g[(size_t)b * P] = 0.0;
+    for (uint32_t i = 1; i < P; ++i, t += bin) g[(size_t)b * P + i] = t;
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->pa_grid_blen.empty()) {   // (pavg_alloc: new layout)
+    dfree(c->d_pa_grid);
+    HIP_TRY(c, hipMalloc(&c->d_pa_grid, g.size() * sizeof(double)));
+  }
+  HIP_TRY(c, hipMemcpy(c->d_pa_grid, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->pa_grid_blen = c->blen;
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_pavg first)
+int launch_pavg(epv_ctx *c) {
+  if (c->pa_cnt)
+    hipLaunchKernelGGL(epv_pavg_accum_kernel, dim3((unsigned)((c->pa_cnt + 255u) / 256u), c->S.B), dim3(256), 0,
+                       c->stream, c->S, c->pa_lo, c->pa_cnt, (const double *)c->d_pa_grid, c->pa_P, c->d_pa);
+  ++c->pa_samples;
+  HIP_TRY(c, hipGetLastError());
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -823,6 +917,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   free_paths(c);
   dfree(c->d_model); dfree(c->d_parent); dfree(c->d_subtree); dfree(c->d_blen);
   dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_rows); dfree(c->d_gpool2); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
+  dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1472,6 +1567,7 @@ EPV_API int epv_run_mcmc_sums(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint
   if (rc) return rc;
   if (!J || !D || batch == 0) return fail(c, EPV_ERR_ARG, "bad run_mcmc arguments");
   HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_pavg(c))) return rc;
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -1486,6 +1582,7 @@ EPV_API int epv_run_mcmc_sums(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint
       if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
     ++c->n_sweeps;
     if ((rc = launch_suffstats(c, w))) return rc;
+    if (c->pa_P && (rc = launch_pavg(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   rc = finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
@@ -1541,6 +1638,7 @@ EPV_API int epv_run_mcmc_blocks(epv_ctx *c, uint64_t burn_in, uint64_t batch, ui
     return fail(c, EPV_ERR_ARG, "owned blocks exceed the group's block buffer");
   if ((c->S.g0 & 255u) != 0u) return fail(c, EPV_ERR_ARG, "the shard must start on a 256-site block of the genome");
   if ((rc = ensure_stat_scale(c))) return rc;
+  if ((rc = ensure_pavg(c))) return rc;
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -1567,6 +1665,7 @@ EPV_API int epv_run_mcmc_blocks(epv_ctx *c, uint64_t burn_in, uint64_t batch, ui
     else
       hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
                          dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows0 + w * nb_total * V);
+    if (c->pa_P && (rc = launch_pavg(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
@@ -1911,5 +2010,95 @@ EPV_API int epv_kernel_time_ms(epv_ctx *c, double *avg_ms, uint64_t *n_launches)
   *avg_ms = c->timed_launches ? c->timed_ms / (double)c->timed_launches : 0.0;
   c->timed_ms = 0.0;
   c->timed_launches = 0;
+  return EPV_OK;
+}
+
+// ---- average history of the sampled paths (epv_pavg.h)
+EPV_API int epv_set_path_average(epv_ctx *c, uint32_t n_points) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n_points == 0) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
+    c->pa_P = 0;
+    c->pa_cnt = c->pa_samples = c->pa_out_cap = 0;
+    c->pa_grid_blen.clear();
+    return EPV_OK;
+  }
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (n_points < 2) return fail(c, EPV_ERR_ARG, "a path average needs at least 2 points");
+  c->pa_P = n_points;
+  if ((rc = pavg_alloc(c))) return rc;
+  if ((rc = ensure_pavg(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_reset_path_average(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_pa)
+    HIP_TRY(c, hipMemsetAsync(c->d_pa, 0, (size_t)4u * c->pa_B * c->pa_cnt * c->pa_P, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->pa_samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_path_average(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_pavg(c)) || (rc = launch_pavg(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_path_average_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->pa_P ? c->pa_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_path_average_layout(epv_ctx *c, uint32_t *n_points, uint64_t *first, uint64_t *count) {
+  if (!c || !n_points || !first || !count) return EPV_ERR_ARG;
+  *n_points = 0;
+  *first = *count = 0;
+  if (!c->pa_P) return EPV_OK;
+  if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_pavg(c);
+    if (rc && c->pa_samples == 0) return rc;
+  }
+  *n_points = c->pa_P;
+  *first = c->pa_lo;
+  *count = c->pa_cnt;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_path_average(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *counts) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
+  if (!counts) return fail(c, EPV_ERR_ARG, "null output");
+  if (first < c->pa_lo || first + count > c->pa_lo + c->pa_cnt)
+    return fail(c, EPV_ERR_ARG, "site range outside the sites this context averages");
+  if (count == 0) return EPV_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t bytes = (uint64_t)4u * c->pa_B * count * c->pa_P;
+  if (bytes > c->pa_out_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_pa_out);
+    c->pa_out_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->d_pa_out, bytes));
+    c->pa_out_cap = bytes;
+  }
+  hipLaunchKernelGGL(epv_pavg_read_kernel, dim3((unsigned)((count + EPV_PAVG_RD - 1u) / EPV_PAVG_RD), c->pa_B),
+                     dim3(EPV_PAVG_RD), 0, c->stream, (const int32_t *)c->d_pa, c->pa_P, c->pa_cnt,
+                     first - c->pa_lo, count, c->d_pa_out);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(counts, c->d_pa_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }

@@ -1,0 +1,114 @@
+// epievo_est_histories -- the reference's E-step program (src/prog/epievo_est_histories.cpp, which
+// does not build there: SURVEY.md section 0.7) on the GPU: one run_mcmc (EM iteration 0) on the input
+// paths, the final paths written in local_paths format.  Same flags as the reference
+// (-B -L -s -o -T -v) plus -g as in epievo_est_params_histories; input loading and the tot_time
+// rescale are that program's (epv::load_paths_and_tree).
+// New: -a/--average FILE with -n/--npoints (default 100, as average_paths): the average history of
+// the B batch sweeps, counted on the device (epv_set_path_average), in average_paths' output format
+// (average_paths.cpp:49-63), without writing the samples to files.
+#include <cstdlib>
+#include <iostream>
+#include <limits>
+#include <random>
+#include <stdexcept>
+
+#include "epv_io.hpp"
+#include "epv_model.hpp"
+#include "epv_options.hpp"
+#include "epv_sampler.hpp"
+
+using std::cerr;
+using std::endl;
+using std::string;
+using std::vector;
+
+static string strip_path(const string &full) {
+  const size_t p = full.find_last_of('/');
+  return p == string::npos ? full : full.substr(p + 1);
+}
+
+int main(int argc, const char **argv) {
+  try {
+    bool VERBOSE = false, single_branch = false;
+    string outfile, tree_file, gpu_list, average_file;
+    size_t batch = 10, burnin = 10, n_points = 100;
+    size_t rng_seed = std::numeric_limits<size_t>::max();
+
+    epv::OptionParser opt_parse(strip_path(argv[0]), "estimate evolutionary histories",
+                                "<param> (<treefile>) <path_file>");
+    opt_parse.add_opt("batch", 'B', "number of MCMC iteration", false, batch);
+    opt_parse.add_opt("burnin", 'L', "MCMC burn-in length", false, burnin);
+    opt_parse.add_opt("seed", 's', "rng seed", false, rng_seed);
+    opt_parse.add_opt("outfile", 'o', "output file of local paths", true, outfile);
+    opt_parse.add_opt("single_branch", 'T', "pairwise process (assumes no tree)", false, single_branch);
+    opt_parse.add_opt("verbose", 'v', "print more run info", false, VERBOSE);
+    opt_parse.add_opt("gpus", 'g', "GPUs to shard the sites over: all | 0,1,.. (default: EPV_DEVICES or 0)", false,
+                      gpu_list);
+    opt_parse.add_opt("average", 'a', "output file of the average history of the batch sweeps", false, average_file);
+    opt_parse.add_opt("npoints", 'n', "number of time points per branch of the average", false, n_points);
+    vector<string> leftover_args;
+    opt_parse.parse(argc, argv, leftover_args);
+    if (argc == 1 || opt_parse.help_requested()) {
+      cerr << opt_parse.help_message() << endl << opt_parse.about_message() << endl;
+      return EXIT_SUCCESS;
+    }
+    if (opt_parse.option_missing()) {
+      cerr << opt_parse.option_missing_message() << endl;
+      return EXIT_SUCCESS;
+    }
+    if (leftover_args.size() == 2) {
+      if (!single_branch) { cerr << opt_parse.help_message() << endl; return EXIT_SUCCESS; }
+    } else if (leftover_args.size() != 3) {
+      cerr << opt_parse.help_message() << endl;
+      return EXIT_SUCCESS;
+    } else {
+      tree_file = leftover_args[1];
+    }
+    if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
+      throw std::runtime_error("-n: the number of points must be at least 2");
+    if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
+    const string param_file(leftover_args.front()), input_file(leftover_args.back());
+
+    if (VERBOSE) cerr << "[READING PARAMETERS: " << param_file << "]" << endl;
+    epv::Model the_model = epv::Model::read(param_file);
+    the_model.scale_triplet_rates();
+    vector<string> node_names;
+    epv::FlatPaths paths;
+    epv::Tree th;
+    epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
+
+    if (rng_seed == std::numeric_limits<size_t>::max()) {
+      std::random_device rd;
+      rng_seed = rd();
+    }
+    if (VERBOSE) cerr << "rng seed: " << rng_seed << endl;
+
+    epv::SingleSiteSampler mcmc(burnin, batch,
+                                gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
+    mcmc.reset(the_model, th, paths);
+    if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
+    if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);
+    double acceptance_rate = 0.0;
+    vector<vector<double>> J, D;
+    mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
+    if (VERBOSE) cerr << "[ACCEPTANCE RATE: " << acceptance_rate << "]" << endl;
+
+    epv::FlatPaths out;
+    mcmc.download(out);
+    if (VERBOSE) cerr << "[WRITING PATHS: " << outfile << "]" << endl;
+    epv::write_local_paths(outfile, th.node_names, th.n_nodes(), out.n_sites, th.branches.data(), out.init.data(),
+                           out.offsets.data(), out.jumps.data());
+    if (!average_file.empty()) {
+      vector<uint32_t> counts;
+      uint64_t n_samples = 0;
+      mcmc.download_path_average(counts, n_samples);
+      if (VERBOSE) cerr << "[WRITING AVERAGE OF " << n_samples << " SAMPLES: " << average_file << "]" << endl;
+      epv::write_path_average(average_file, th.node_names, th.n_nodes(), out.n_sites, (uint32_t)n_points,
+                              th.branches.data(), counts.data(), n_samples);
+    }
+  } catch (const std::exception &e) {
+    cerr << e.what() << endl;
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}

@@ -84,39 +84,10 @@ int main(int argc, const char **argv) {
     epv::Model the_model = epv::Model::read(param_file);
     the_model.scale_triplet_rates();
 
-    if (VERBOSE) cerr << "[READING PATHS FILE: " << input_file << "]" << endl;
     vector<string> node_names;
-    vector<double> tot_times;
-    epv::FlatPaths paths = epv::read_local_paths(input_file, node_names, tot_times);
-
+    epv::FlatPaths paths;
     epv::Tree th;
-    if (single_branch) {
-      if (VERBOSE) cerr << "[INITIALIZING TWO NODE TREE WITH TIME: " << tot_times.back() << "]" << endl;
-      th = epv::Tree::single_branch(tot_times.back());
-    } else {
-      if (VERBOSE) cerr << "[READING TREE: " << tree_file << "]" << endl;
-      th = epv::Tree::read(tree_file);
-    }
-    if (th.n_nodes() != paths.n_nodes)
-      throw std::runtime_error("tree and paths file have different numbers of nodes");
-    // The reference compares nothing here: branch lengths come from the tree, each Path keeps the
-    // tot_time of the file, and scale_jump_times (ParamEstimation.cpp:369-380) brings the two
-    // together at the end of the first iteration.  epievo_initialization without -b writes
-    // rate-scaled tot_times next to an unscaled tree, so a mismatch is an ordinary input.  The
-    // device keeps one length per branch, hence the same rescaling is applied at load time.
-    for (int b = 1; b < th.n_nodes(); ++b)
-      if (tot_times[b] != th.branches[b]) {
-        if (!(tot_times[b] > 0.0) || !std::isfinite(tot_times[b]))
-          throw std::runtime_error("paths of node " + th.node_names[b] + ": tot_time must be positive and finite");
-        const double scale = th.branches[b] / tot_times[b];
-        const uint64_t n = paths.n_sites;
-        for (uint64_t k = paths.offsets[(uint64_t)(b - 1) * n]; k < paths.offsets[(uint64_t)b * n]; ++k)
-          paths.jumps[k] *= scale;
-        // always reported: first-iteration statistics of such an input differ from the reference's,
-        // which keeps the file's tot_time until scale_jump_times ("tot_time")
-        cerr << "[RESCALING PATHS OF NODE " << th.node_names[b] << ": tot_time " << tot_times[b]
-             << " -> branch length " << th.branches[b] << "]" << endl;
-      }
+    epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
       std::random_device rd;

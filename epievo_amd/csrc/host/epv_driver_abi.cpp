@@ -17,6 +17,8 @@ struct epvd_sampler {
   bool rank_mode = false;
   std::string err;
   epv::FlatPaths staged;   // between epvd_download_sizes and epvd_download
+  std::vector<uint32_t> staged_avg;   // between epvd_path_average_sizes and epvd_download_path_average
+  bool have_staged_avg = false;
 };
 
 namespace {
@@ -149,3 +151,25 @@ EPVD_API int epvd_kernel_time_ms(epvd_sampler *h, double *avg_ms, uint64_t *n_la
   return guarded(h, [&] { h->s->kernel_time_ms(*avg_ms, *n_launches); });
 }
 EPVD_API int epvd_phase_mode(epvd_sampler *h, uint32_t *mode) { return guarded(h, [&] { *mode = h->s->phase_mode(); }); }
+
+EPVD_API int epvd_set_path_average(epvd_sampler *h, uint32_t n_points) {
+  return guarded(h, [&] { h->s->set_path_average(n_points); });
+}
+EPVD_API int epvd_path_average_sizes(epvd_sampler *h, uint64_t *n_values, uint32_t *n_points, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t ns = 0;
+    h->s->download_path_average(h->staged_avg, ns);
+    h->have_staged_avg = true;
+    *n_values = h->staged_avg.size();
+    *n_points = h->s->path_average_points();
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_path_average(epvd_sampler *h, uint32_t *counts) {
+  return guarded(h, [&] {
+    if (!h->have_staged_avg) throw std::runtime_error("epvd_path_average_sizes first");
+    std::copy(h->staged_avg.begin(), h->staged_avg.end(), counts);
+    h->staged_avg.clear();
+    h->have_staged_avg = false;
+  });
+}

@@ -13,6 +13,8 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
+#include <iostream>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -471,6 +473,93 @@ void read_states_file(const std::string &states_file, std::vector<std::string> &
     while (k < names.size() && ls >> v) states[k++].push_back(v == '1');
     if (k != names.size()) throw std::runtime_error("bad line in states file");
   }
+}
+
+}  // namespace epv
+
+namespace epv {
+
+void add_path_counts(const FlatPaths &paths, const double *tot_times, uint32_t n_points,
+                     std::vector<uint32_t> &counts) {
+  const uint64_t n = paths.n_sites, B = paths.n_nodes > 0 ? (uint64_t)paths.n_nodes - 1u : 0u;
+  if (n_points < 2) throw std::runtime_error("the number of points must be at least 2");
+  counts.resize(B * n * n_points, 0u);
+  std::vector<double> t(n_points);
+  for (uint64_t b = 0; b < B; ++b) {
+    const double bin = tot_times[b + 1] / (n_points - 1);
+    double curr_time = bin;
+    t[0] = 0.0;
+    for (uint32_t i = 1; i < n_points; ++i, curr_time += bin) t[i] = curr_time;
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t e = b * n + s;
+      const double *j0 = paths.jumps.data() + paths.offsets[e], *j1 = paths.jumps.data() + paths.offsets[e + 1];
+      const uint32_t init = paths.init[e];
+      uint32_t *c = counts.data() + e * n_points;
+      c[0] += init;
+      for (uint32_t i = 1; i < n_points; ++i) {
+        const size_t idx = std::lower_bound(j0, j1, t[i]) - j0;
+        c[i] += (idx % 2 == 0) ? init : 1u - init;
+      }
+    }
+  }
+}
+
+void write_path_average(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                        uint64_t n_sites, uint32_t n_points, const double *branch_len, const uint32_t *counts,
+                        uint64_t n_samples) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  const double ns = (double)n_samples;
+  out << "NODE:" << node_names[0] << std::endl;
+  for (int b = 1; b < n_nodes; ++b) {
+    out << "NODE:" << node_names[b] << "\t" << branch_len[b] << std::endl;
+    for (uint64_t s = 0; s < n_sites; ++s) {
+      const uint32_t *c = counts + ((uint64_t)(b - 1) * n_sites + s) * n_points;
+      out << (double)c[0] / ns;
+      for (uint32_t i = 1; i < n_points; ++i) out << "\t" << (double)c[i] / ns;
+      out << '\n';
+    }
+  }
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+}  // namespace epv
+
+namespace epv {
+
+void load_paths_and_tree(const std::string &paths_file, const std::string &tree_file, bool single_branch, bool verbose,
+                         FlatPaths &paths, std::vector<std::string> &node_names, Tree &th) {
+  if (verbose) std::cerr << "[READING PATHS FILE: " << paths_file << "]" << std::endl;
+  std::vector<double> tot_times;
+  paths = read_local_paths(paths_file, node_names, tot_times);
+
+  if (single_branch) {
+    if (verbose) std::cerr << "[INITIALIZING TWO NODE TREE WITH TIME: " << tot_times.back() << "]" << std::endl;
+    th = Tree::single_branch(tot_times.back());
+  } else {
+    if (verbose) std::cerr << "[READING TREE: " << tree_file << "]" << std::endl;
+    th = Tree::read(tree_file);
+  }
+  if (th.n_nodes() != paths.n_nodes)
+    throw std::runtime_error("tree and paths file have different numbers of nodes");
+  // The reference compares nothing here: branch lengths come from the tree, each Path keeps the
+  // tot_time of the file, and scale_jump_times (ParamEstimation.cpp:369-380) brings the two
+  // together at the end of the first iteration.  epievo_initialization without -b writes
+  // rate-scaled tot_times next to an unscaled tree, so a mismatch is an ordinary input.  The
+  // device keeps one length per branch, hence the same rescaling is applied at load time.
+  for (int b = 1; b < th.n_nodes(); ++b)
+    if (tot_times[b] != th.branches[b]) {
+      if (!(tot_times[b] > 0.0) || !std::isfinite(tot_times[b]))
+        throw std::runtime_error("paths of node " + th.node_names[b] + ": tot_time must be positive and finite");
+      const double scale = th.branches[b] / tot_times[b];
+      const uint64_t n = paths.n_sites;
+      for (uint64_t k = paths.offsets[(uint64_t)(b - 1) * n]; k < paths.offsets[(uint64_t)b * n]; ++k)
+        paths.jumps[k] *= scale;
+      // always reported: first-iteration statistics of such an input differ from the reference's,
+      // which keeps the file's tot_time until scale_jump_times ("tot_time")
+      std::cerr << "[RESCALING PATHS OF NODE " << th.node_names[b] << ": tot_time " << tot_times[b]
+           << " -> branch length " << th.branches[b] << "]" << std::endl;
+    }
 }
 
 }  // namespace epv

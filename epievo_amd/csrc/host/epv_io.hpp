@@ -44,6 +44,26 @@ void write_local_paths(const std::string &path_file, const std::vector<std::stri
                        int n_nodes, uint64_t n_sites, const double *tot_times,
                        const uint8_t *init, const uint64_t *offsets, const double *jumps);
 
+// average_paths (src/prog/average_paths.cpp:31-45), one sample: for every node b >= 1, site s
+// and point i of the grid t_0 = 0, t_1 = bin, t_{i+1} = t_i + bin (bin = tot_times[b] / (P - 1)),
+// counts[((b-1) * n_sites + s) * P + i] += the path's init state at i = 0, state_at_time(t_i)
+// (Path.cpp:106-111) at i >= 1.  The reference reads node 1's path for i >= 1 of every node
+// (average_paths.cpp:39); this reads node b's own.
+void add_path_counts(const FlatPaths &paths, const double *tot_times, uint32_t n_points,
+                     std::vector<uint32_t> &counts);
+// write_output of average_paths.cpp:49-63: "NODE:<root>", then per node "NODE:<name>\t<branch_len>"
+// and one line of P tab-separated averages counts / n_samples per site, default ostream formatting
+void write_path_average(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                        uint64_t n_sites, uint32_t n_points, const double *branch_len, const uint32_t *counts,
+                        uint64_t n_samples);
+
+// the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
+// then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The
+// device keeps one length per branch, so paths whose tot_time differs from the tree's branch length
+// are rescaled to it here (reported on stderr; INTEGRATION.md, "tot_time")
+void load_paths_and_tree(const std::string &paths_file, const std::string &tree_file, bool single_branch, bool verbose,
+                         FlatPaths &paths, std::vector<std::string> &node_names, Tree &th);
+
 // read_states_file (src/libepievo/epievo_utils.cpp:90-125): states[seq][site]
 void read_states_file(const std::string &states_file, std::vector<std::string> &names,
                       std::vector<std::vector<uint8_t>> &states);

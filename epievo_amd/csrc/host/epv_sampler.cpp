@@ -361,12 +361,51 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (rank_mode_) throw std::runtime_error("one slot per process: reset(model, tree, owned columns, n_global)");
   build(th, paths, paths.n_sites, false);
   reset(m);
+  if (pa_points_) set_path_average(pa_points_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
   if (!rank_mode_) throw std::runtime_error("reset(..., n_global) belongs to the one-slot-per-process constructor");
   build(th, owned, n_global, true);
   reset(m);
+  if (pa_points_) set_path_average(pa_points_);
+}
+
+void SingleSiteSampler::set_path_average(uint32_t n_points) {
+  // before the first reset(model, tree, paths) there are no paths to lay the counts out for: the
+  // setting is applied to the contexts that reset builds
+  if (n_sites_ || n_points == 0)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_path_average(c, n_points), "epv_set_path_average");
+  pa_points_ = n_points;
+}
+
+void SingleSiteSampler::download_path_average(std::vector<uint32_t> &counts, uint64_t &n_samples) {
+  if (!pa_points_) throw std::runtime_error("path average is off: set_path_average first");
+  const std::vector<epv_ctx *> cs = contexts();
+  const uint64_t B = (uint64_t)n_nodes_ - 1u, P = pa_points_;
+  std::vector<uint64_t> first(cs.size()), count(cs.size());
+  uint64_t total = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t p = 0;
+    check_on(cs[i], epv_path_average_layout(cs[i], &p, &first[i], &count[i]), "epv_path_average_layout");
+    if (p != P) throw std::runtime_error("a context's path average is off");
+    uint64_t ns = 0;
+    check_on(cs[i], epv_path_average_samples(cs[i], &ns), "epv_path_average_samples");
+    if (i == 0) n_samples = ns;
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of path-average samples");
+    total += count[i];
+  }
+  counts.assign(B * total * P, 0u);
+  std::vector<uint32_t> part;
+  uint64_t at = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {   // contexts in genome order, each one's sites contiguous
+    part.assign(B * count[i] * P, 0u);
+    if (count[i]) check_on(cs[i], epv_get_path_average(cs[i], first[i], count[i], part.data()), "epv_get_path_average");
+    for (uint64_t b = 0; b < B; ++b)
+      std::copy(part.begin() + b * count[i] * P, part.begin() + (b + 1) * count[i] * P,
+                counts.begin() + (b * total + at) * P);
+    at += count[i];
+  }
 }
 
 void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n, bool rank_mode) {

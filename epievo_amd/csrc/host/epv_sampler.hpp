@@ -101,6 +101,14 @@ public:
 
   // the resident paths (one slot per process: the owned columns of this slot)
   void download(FlatPaths &paths);
+  // average history of the sampled paths (epv_set_path_average) on every context: one sample per
+  // batch sweep of run_mcmc.  n_points = 0 turns it off; the setting carries over to the contexts of a
+  // later reset(model, tree, paths), which starts the counts from zero.  download_path_average:
+  // counts[((b-1) * sites + site) * n_points + i] over the sites of this process in genome order (the
+  // whole genome unless one slot per process), and the number of samples
+  void set_path_average(uint32_t n_points);
+  void download_path_average(std::vector<uint32_t> &counts, uint64_t &n_samples);
+  uint32_t path_average_points() const { return pa_points_; }
   // EPV_OPT_* of include/epievo_mi355x.h on every context; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
   void set_timing(int every);
@@ -177,6 +185,7 @@ private:
   uint64_t max_rows_ = 0, stat_batch_ = 0;
   std::vector<uint64_t> rows_of_slot_;   // statistics rows of every slot of the run
   uint32_t capacity_;
+  uint32_t pa_points_ = 0;    // set_path_average
   int n_nodes_ = 0;
   uint64_t n_sites_ = 0;      // genome length (all slots)
   size_t world_ = 1;          // slots of the run (== slots_.size() unless one slot per process)

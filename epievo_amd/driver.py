@@ -15,7 +15,7 @@ vp, dp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8
 DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_destroy", "epvd_last_error", "epvd_shard_cuts",
                   "epvd_reset", "epvd_reset_model", "epvd_run_mcmc", "epvd_scale_jump_times", "epvd_download_sizes",
                   "epvd_download", "epvd_layout", "epvd_set_options", "epvd_set_timing", "epvd_kernel_time_ms",
-                  "epvd_phase_mode"]
+                  "epvd_phase_mode", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average"]
 
 
 def lib():
@@ -44,6 +44,9 @@ def lib():
         L.epvd_set_timing.argtypes = [vp, C.c_int]
         L.epvd_kernel_time_ms.argtypes = [vp, dp, u64p]
         L.epvd_phase_mode.argtypes = [vp, u32p]
+        L.epvd_set_path_average.argtypes = [vp, C.c_uint32]
+        L.epvd_path_average_sizes.argtypes = [vp, u64p, u32p, u64p]
+        L.epvd_download_path_average.argtypes = [vp, u32p]
         _lib = L
     return _lib
 
@@ -149,3 +152,17 @@ class CppSampler:
         m = C.c_uint32(0)
         self._ck(self.L.epvd_phase_mode(self.h, C.byref(m)))
         return m.value
+
+    def enable_path_average(self, n_points):
+        """the average history of the sampled paths on every context (0 = off); kept across reset()"""
+        self._ck(self.L.epvd_set_path_average(self.h, int(n_points)))
+
+    def path_average(self, counts=False):
+        """-> (samples, [N-1, sites, P]) over the sites of this process: float64 averages or uint32 counts"""
+        nv, P, ns = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_path_average_sizes(self.h, C.byref(nv), C.byref(P), C.byref(ns)))
+        out = np.zeros(max(nv.value, 1), np.uint32)
+        self._ck(self.L.epvd_download_path_average(self.h, _p(out, C.c_uint32)))
+        out = out[:nv.value].reshape(self.B, -1, P.value)
+        ns = int(ns.value)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))

@@ -297,6 +297,43 @@ class ShardedSampler:
     def scale_jump_times(self, new_branches):
         self.dev.scale_jump_times(new_branches)
 
+    # ---- average history of the sampled paths: every rank counts its owned columns
+    def enable_path_average(self, n_points):
+        self.dev.enable_path_average(n_points)
+
+    def reset_path_average(self):
+        self.dev.reset_path_average()
+
+    def accumulate_path_average(self):
+        self.dev.accumulate_path_average()
+
+    def path_average(self, counts=False):
+        """-> (samples, [N-1, n_global, P]) of the whole genome, identical on every rank: the ranks'
+        counts are all-gathered (one collective) and concatenated in genome order"""
+        ns, own = self.dev.path_average(counts=True)
+        if self.comm.world > 1:
+            B, P = own.shape[0], own.shape[2]
+            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
+            if own.shape[1] != sizes[self.comm.rank]:
+                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[1], sizes[self.comm.rank]))
+            words = B * max(sizes) * P + 2                   # counts, then the sample count (two words)
+            mine = np.zeros(words, np.uint32)
+            mine[:B * max(sizes) * P].reshape(B, max(sizes), P)[:, :own.shape[1]] = own
+            mine[-2:] = [ns & 0xffffffff, ns >> 32]
+            piece, gathered = self.dev.alloc(4 * words), self.dev.alloc(4 * words * self.comm.world)
+            try:
+                self.dev.write(piece, 0, mine)
+                self.comm.all_gather(self.dev, piece, gathered)
+                allw = self.dev.read(gathered, 0, words * self.comm.world, np.uint32).reshape(self.comm.world, words)
+            finally:
+                piece.free()
+                gathered.free()
+            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of path-average samples")
+            own = np.concatenate([allw[r, :-2].reshape(B, max(sizes), P)[:, :sizes[r]] for r in range(self.comm.world)],
+                                 axis=1)
+        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -563,6 +600,31 @@ class LocalGroup:
     def set_capacity(self, capacity):
         for s in self.subs:
             s.set_capacity(capacity)
+
+    # ---- average history of the sampled paths: every shard counts the sites it owns
+    def enable_path_average(self, n_points):
+        self._each(lambda j, s: s.enable_path_average(n_points))
+
+    def reset_path_average(self):
+        self._each(lambda j, s: s.reset_path_average())
+
+    def accumulate_path_average(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a path-average sample")
+        self._each(lambda j, s: s.accumulate_path_average())
+
+    def path_average_samples(self):
+        return self.subs[0].path_average_samples()
+
+    def path_average(self, counts=False):
+        """-> (samples, [N-1, sites, P]) over the group's owned sites, shards in genome order"""
+        parts = self._each(lambda j, s: s.path_average(counts=True))
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of path-average samples")
+        out = np.concatenate([p[1] for p in parts], axis=1)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
 
     def counters(self):
         out = {}

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_blocks_to_rows", "epv_reduce_rows", "epv_reduce_gathered_rows", "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
+    "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
+    "epv_get_path_average", "epv_path_average_layout",
 ]
 
 
@@ -119,6 +121,12 @@ def lib():
         L.epv_get_counters.argtypes = [vp, C.POINTER(_Counters)]
         L.epv_kernel_time_ms.argtypes = [vp, dp, u64p]
         L.epv_set_timing.argtypes = [vp, C.c_int]
+        L.epv_set_path_average.argtypes = [vp, C.c_uint32]
+        L.epv_reset_path_average.argtypes = [vp]
+        L.epv_accumulate_path_average.argtypes = [vp]
+        L.epv_path_average_samples.argtypes = [vp, u64p]
+        L.epv_get_path_average.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
+        L.epv_path_average_layout.argtypes = [vp, u32p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -449,6 +457,46 @@ class DeviceSampler:
         self._ck(self.L.epv_kernel_time_ms(self.h, C.byref(ms), C.byref(n)))
         return ms.value, int(n.value)
 
+    # ---- average history of the sampled paths (epv_set_path_average)
+    def enable_path_average(self, n_points):
+        """count the resident paths on a grid of n_points per branch after every batch sweep of
+        run_mcmc (0 = off)"""
+        self._ck(self.L.epv_set_path_average(self.h, int(n_points)))
+
+    def reset_path_average(self):
+        self._ck(self.L.epv_reset_path_average(self.h))
+
+    def accumulate_path_average(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_path_average(self.h))
+
+    def path_average_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_path_average_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def path_average_layout(self):
+        """(points, first local site, number of sites) of the counts; points = 0: averaging is off.
+        A context counts its owned sites plus the genome's end sites when it holds them"""
+        P, a, k = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_path_average_layout(self.h, C.byref(P), C.byref(a), C.byref(k)))
+        return int(P.value), int(a.value), int(k.value)
+
+    def path_average(self, counts=False, chunk_bytes=256 << 20):
+        """-> (samples, array [N-1, sites, P]): float64 averages, or the uint32 counts"""
+        P, first, cnt = self.path_average_layout()
+        if not P:
+            raise EpvError(EPV_ERR_STATE, "path average is off: enable_path_average first")
+        out = np.zeros((self.B, cnt, P), np.uint32)
+        step = max(1, chunk_bytes // max(1, 4 * self.B * P))
+        for a in range(0, cnt, step):
+            k = min(step, cnt - a)
+            buf = np.zeros((self.B, k, P), np.uint32)
+            self._ck(self.L.epv_get_path_average(self.h, first + a, k, _p(buf, C.c_uint32)))
+            out[:, a:a + k] = buf
+        ns = self.path_average_samples()
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
 
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
@@ -504,3 +552,16 @@ class SingleSiteSampler:
 
     def paths(self):
         return self.dev.paths()
+
+    # average history of the sampled paths (DeviceSampler.enable_path_average)
+    def enable_path_average(self, n_points):
+        self.dev.enable_path_average(n_points)
+
+    def reset_path_average(self):
+        self.dev.reset_path_average()
+
+    def accumulate_path_average(self):
+        self.dev.accumulate_path_average()
+
+    def path_average(self, counts=False):
+        return self.dev.path_average(counts)

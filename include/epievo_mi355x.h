@@ -306,6 +306,31 @@ int epv_reduce_gathered_rows(epv_ctx *ctx, const double *d_gathered, uint32_t wo
 
 int epv_get_counters(epv_ctx *ctx, epv_counters *out);
 
+/* ---- average history of the sampled paths (new; the reference's average_paths program,
+ * average_paths.cpp:31-45, over files of sampled paths).  For P = n_points grid points
+ * t_0 = 0, t_1 = bin, t_{i+1} = t_i + bin (bin = branch length / (P - 1), repeated fp64 addition)
+ * a sample adds, per branch b, site s and point i, the state of the path at t_i: its init state at
+ * point 0, Path::state_at_time(t_i) (init XOR the parity of the jumps < t_i) at i >= 1.  A sample is
+ * the resident paths after each batch sweep of epv_run_mcmc / epv_run_mcmc_sums /
+ * epv_run_mcmc_blocks (not the burn-in), or one epv_accumulate_path_average call.  The counts are
+ * exact integers kept on the device (4 (N-1) P bytes per site), so they do not depend on the
+ * kernels, contexts or GPUs.  A context counts its owned sites plus the genome's end sites when it
+ * holds them: over all contexts every site once.  Off (the default) costs nothing.
+ * epv_set_path_average: n_points >= 2 allocates (checked against the free device memory first;
+ *   the message gives the figure) and zeroes the counts; 0 turns averaging off and frees them.
+ * epv_get_path_average: counts[(b-1)][s - first][i] (uint32) of local sites first .. first+count-1,
+ *   the convention of epv_get_columns; the average is counts / samples. */
+int epv_set_path_average(epv_ctx *ctx, uint32_t n_points);
+int epv_reset_path_average(epv_ctx *ctx);
+int epv_accumulate_path_average(epv_ctx *ctx);
+int epv_path_average_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_get_path_average(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *counts);
+/* the points (0 = averaging off) and the local sites first .. first+count-1 the counts cover.  Before
+ * the first sample the counts are laid out again for the sites the context counts at this moment
+ * (an owned range changed by epv_set_halo / epv_set_update_range); afterwards a change of those
+ * sites makes the next sample fail until epv_set_path_average is called again. */
+int epv_path_average_layout(epv_ctx *ctx, uint32_t *n_points, uint64_t *first, uint64_t *count);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

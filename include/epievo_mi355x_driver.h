@@ -55,6 +55,14 @@ int epvd_set_timing(epvd_sampler *s, int every);                 /* epv_set_timi
 int epvd_kernel_time_ms(epvd_sampler *s, double *avg_ms, uint64_t *n_launches);
 int epvd_phase_mode(epvd_sampler *s, uint32_t *mode);
 
+/* the average history of the sampled paths (epv_set_path_average on every context; 0 = off; kept
+ * across epvd_reset, which starts the counts from zero), and its counts over the sites of this process
+ * in genome order: sizes first (n_values = (n_nodes - 1) * sites * n_points), then the copy of
+ * counts[((b-1) * sites + site) * n_points + i]; the average is counts / n_samples */
+int epvd_set_path_average(epvd_sampler *s, uint32_t n_points);
+int epvd_path_average_sizes(epvd_sampler *s, uint64_t *n_values, uint32_t *n_points, uint64_t *n_samples);
+int epvd_download_path_average(epvd_sampler *s, uint32_t *counts);
+
 #ifdef __cplusplus
 }
 #endif
