@@ -91,6 +91,9 @@ struct epv_ctx {
   uint32_t fused_max_waves = 3072;   // measured on tree.nwk: +46 % at 520 waves, +20 % at 1700, +5 % at 2600, -4..-14 % at 5200 (tools/fused_scan.sh)
   bool fused = false;            // decided by plan_p2 for the uploaded paths
   uint32_t fused_lanes = 64;     // sites per wave of the fused phase (64 / 32 / 16: EPV_FUSED_LANES, else by launch size)
+  // the fused phase's small-tree body (epv_propose2.h, NN = node count) for trees of at most
+  // EPV_P2_SMALL_MAX nodes: 1 = wherever the tree fits (default), EPV_P2_SMALL_TREE=0 = the generic body
+  int use_small = 1;
   EpvFused F{};                  // per-wave lists, allocated on first use
   uint64_t fused_waves = 0;      // waves the lists are allocated for
   uint32_t tasks_per_wave = 0;   // epv_mh_jumps_kernel: lanes of a wave that own a task (0 = by workload)
@@ -212,6 +215,19 @@ int plan_mh(epv_ctx *c) {
 // table and a pool of doubles shared by the Felsenstein records (2 doubles) and the heavy-segment
 // records (EPV_HREC doubles).  The pool covers the typical demand of 64 lanes with a margin (a wave that
 // needs more runs in rounds) and always one lane's worst case.
+// the fused phase's kernel for a tree of nn nodes: the small-tree body for 2 <= nn <= EPV_P2_SMALL_MAX,
+// else (and for nn = 0) the generic one
+using fused_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                                uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused);
+fused_kernel_t fused_kernel(uint32_t nn) {
+  switch (nn) {
+    case 2: return epv_mh_propose2_kernel<false, true, true, 2>;
+    case 3: return epv_mh_propose2_kernel<false, true, true, 3>;
+    case 4: return epv_mh_propose2_kernel<false, true, true, 4>;
+    case 5: return epv_mh_propose2_kernel<false, true, true, 5>;
+    default: return epv_mh_propose2_kernel<false, true, true>;
+  }
+}
 bool seg_jumps_on(const epv_ctx *c) { return c->use_seg < 0 ? c->kbar >= 0.25 : c->use_seg != 0; }
 double p2_margin() {
   if (const char *e = std::getenv("EPV_P2_MARGIN")) { const double v = std::atof(e); if (v >= 1.0 && v <= 4.0) return v; }
@@ -702,7 +718,8 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     F.lanes = c->fused_lanes;
     static const int grouped = std::getenv("EPV_FUSED_GROUPED_ROUNDS") ? std::atoi(std::getenv("EPV_FUSED_GROUPED_ROUNDS")) : 4;
     F.grouped_rounds = (uint32_t)std::max(0, grouped);
-    hipLaunchKernelGGL((epv_mh_propose2_kernel<false, true, true>), dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S,
+    const auto kf = fused_kernel(c->use_small ? c->S.N : 0u);
+    hipLaunchKernelGGL(kf, dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,
                        c->p2_pool, c->p2_list_cap, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
     if (c->timing) HIP_TRY(c, hipEventRecord(e1, c->stream));
@@ -869,6 +886,7 @@ EPV_API epv_ctx *epv_create(int device_id) {
   if (const char *e = std::getenv("EPV_PROPOSE_V3")) c->use_p3 = std::atoi(e) != 0 ? 1 : 0;
   if (const char *e = std::getenv("EPV_SEG_JUMPS")) c->use_seg = std::atoi(e) != 0 ? 1 : 0;
   if (const char *e = std::getenv("EPV_FUSED_PHASE")) c->use_fused = std::atoi(e) != 0 ? 1 : 0;
+  if (const char *e = std::getenv("EPV_P2_SMALL_TREE")) c->use_small = std::atoi(e) != 0 ? 1 : 0;
   if (const char *e = std::getenv("EPV_FUSED_MAX_WAVES")) { const long v = std::atol(e); if (v >= 0) c->fused_max_waves = (uint32_t)v; }
   if (const char *e = std::getenv("EPV_TASKS_PER_WAVE")) {  // tuning knob
     const int v = std::atoi(e);
@@ -893,8 +911,9 @@ EPV_API epv_ctx *epv_create(int device_id) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, true, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn)),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, false, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, true, false>),

@@ -230,14 +230,15 @@ __device__ __forceinline__ double triple_llh(const EpvDev &S, const double *s_mo
 // col = the column's index in the caller's cache): the accept kernel fetches the 5 B words a
 // site needs in ONE batch of independent loads instead of paying a dependent global round trip
 // per branch and triple (it is bound by memory latency: SQ_WAIT_ANY was 70 % of its wave cycles)
-template <class ACC>
+// NB > 0: the branch count as a compile-time constant (the small-tree fused phase)
+template <int NB = 0, class ACC>
 __device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const double *s_model,
                                                     const double *s_blen, const epv_meta_t *mc, uint32_t stride,
                                                     uint32_t cl, uint32_t bl, uint64_t sl, uint32_t cm, uint32_t bm,
                                                     uint64_t sm, uint32_t cr, uint32_t br, uint64_t sr, ACC &A) {
   acc_clear(A);
   uint32_t rl = 0, rm = 0, rr = 0;
-  const uint32_t B = S.B;
+  const uint32_t B = NB ? (uint32_t)NB : S.B;
   for (uint32_t b = 0; b < B; ++b) {
     const uint32_t ml = mc[(cl * B + b) * stride], mm = mc[(cm * B + b) * stride], mr = mc[(cr * B + b) * stride];
     PathRef L, M, R;

@@ -160,12 +160,26 @@ struct EpvFused {
   uint32_t grouped_rounds;     // rounds of the grouped search of short segment lists (0 = off)
 };
 
-template <bool GPOOL, bool SEG, bool FUSED>
+// NN > 0 (fused phase only): the node count as a compile-time constant, for trees of at most
+// EPV_P2_SMALL_MAX nodes (5: from 6 nodes on, the unrolled body spills to scratch at 168 VGPRs).  The
+// node loops of the downward pass, the hand-over and the emission listing unroll; the lane's row of the
+// node table and one packed word per branch (meta word, K, matrix-table column) live in registers
+// indexed by constants, and the topology is one scalar word read at the kernel's head.  The LDS copies
+// stay for what other lanes read (heavy-pair merges, the emission pass, the acceptance stage).  Same
+// operations in the same order: the results are the generic body's bit for bit.  NN = 0: S.N nodes.
+#define EPV_P2_SMALL_MAX 5
+template <bool GPOOL, bool SEG, bool FUSED, int NN = 0>
 __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,
     uint64_t last, uint64_t own_first, uint64_t own_last, uint32_t pool_dbl, uint32_t list_cap,
     uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab, EpvFused F) {
   static_assert(!FUSED || (SEG && !GPOOL), "the fused phase emits segments and keeps its pool in LDS");
+  constexpr bool SMALL = NN > 0;
+  static_assert(!SMALL || (FUSED && EPV_FUSED_DENSE_EMIT && NN >= 2 && NN <= EPV_P2_SMALL_MAX),
+                "the small-tree body is the fused phase's, with the dense emission pass");
+  constexpr int NNA = SMALL ? NN : 1;      // register array extents (1: unused by the generic body)
+  constexpr int NBA = SMALL ? NN - 1 : 1;
+  const uint32_t NNODE = SMALL ? (uint32_t)NN : S.N;
   // SEG: true = dirty SEGMENTS go to the segment-parallel jump kernels (epv_jumps2.h); 0 = dirty
   // branches go to epv_mh_jumps_kernel's bucketed lists
   // pool_dbl: LDS pool -- doubles per wave; GPOOL -- record ROWS per lane (list_cap heavy records
@@ -176,13 +190,14 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   unsigned long long t_acc_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_prev_ = __builtin_readcyclecounter();
 #endif
-  const uint32_t const_dbl = (20u + S.N + 1u) & ~1u;
-  const uint32_t tab_dbl = S.B * 4u * EPV_SEGTAB_DBL;
-  const uint32_t regA_dbl = ((S.N * 64u + 1u) / 2u + 1u) & ~1u;
+  const uint32_t B = SMALL ? (uint32_t)NN - 1u : S.B;
+  const uint32_t const_dbl = (20u + NNODE + 1u) & ~1u;
+  const uint32_t tab_dbl = B * 4u * EPV_SEGTAB_DBL;
+  const uint32_t regA_dbl = ((NNODE * 64u + 1u) / 2u + 1u) & ~1u;
   // meta words of the three columns of every lane, + the column two sites left of lane 0 and two
   // sites right of the last lane (the acceptance stage's outer triples; the other lanes' outer
   // columns ARE their neighbour lanes' inner ones: lane l + 1 sits three sites further)
-  const uint32_t mc_dbl = ((3u * 64u + 2u) * S.B * (uint32_t)sizeof(epv_meta_t) + 15u) / 16u * 2u;
+  const uint32_t mc_dbl = ((3u * 64u + 2u) * B * (uint32_t)sizeof(epv_meta_t) + 15u) / 16u * 2u;
   // a block holds blockDim.x / 64 waves: constants and the matrix table once, then per wave the
   // node table, the meta cache and the pool
   const uint32_t wave_id = threadIdx.x >> 6;
@@ -197,7 +212,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   // batch of independent loads; the four passes below then read LDS instead of paying a global
   // round trip per branch (the kernel is bound by memory latency, not by issue)
   epv_meta_t *s_meta = reinterpret_cast<epv_meta_t *>(s_wave + regA_dbl);
-  epv_meta_t *s_edge = s_meta + 3u * S.B * 64u;     // [0 .. B): left of lane 0, [B .. 2B): right of the last valid lane
+  epv_meta_t *s_edge = s_meta + 3u * B * 64u;     // [0 .. B): left of lane 0, [B .. 2B): right of the last valid lane
   const int lane = epv_lane();
   // GPOOL: rows of 64 interleaved records (row r of lane l at (r * 64 + l) * 2 doubles), then
   // the flat heavy list; LDS: records packed by a wave prefix sum, the heavy list behind them
@@ -214,7 +229,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   const uint64_t site = s0 + 3u * tid;
   const bool valid = site <= last && (threadIdx.x & 63u) < lpw;
   const uint64_t n = S.n;
-  const uint32_t B = S.B;
   const uint32_t gsite = (uint32_t)(S.g0 + site);
   const uint32_t gsite_lane0 = gsite - 3u * (uint32_t)lane;
 
@@ -241,7 +255,38 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   const uint64_t mbaseM = (selM ? Bn : 0ull) + site;
   const uint64_t jbaseL = (selL ? Bn * S.C : 0ull) + (site - 1), jbaseR = (selR ? Bn * S.C : 0ull) + (site + 1);
   uint32_t need_rec = 0, heavy = 0;
-  if (valid) {
+  // SMALL: the topology in ONE scalar register (bit node: a leaf; bits 8 + 3 node ..: the parent); per branch ONE register of what this lane's own passes
+  // read: this site's meta word (bits 0..15), the segment count K <= 2C + 1 <= 64 (bits 16..23) and
+  // the start states of the left / right neighbour (bits 25 / 24: the matrix table's column)
+  uint32_t topo = 0u, r_w[NBA];
+#define EPV_TOPO_LEAF(node) ((topo >> (node)) & 1u)
+#define EPV_TOPO_PARENT(node) ((topo >> (8 + 3 * (node))) & 7u)
+#define EPV_RW_META(w) ((w) & 0xffffu)
+#define EPV_RW_K(w) (((w) >> 16) & 0xffu)
+#define EPV_RW_TAB(w) ((w) >> 24)
+  if constexpr (SMALL) {
+#pragma unroll
+    for (int node = 1; node < NN; ++node)
+      topo |= (S.subtree[node] == 1u ? 1u << node : 0u) | (S.parent[node] << (8 + 3 * node));
+    topo = __builtin_amdgcn_readfirstlane(topo);
+#pragma unroll
+    for (int b = 0; b < NN - 1; ++b) r_w[b] = 1u << 16;
+  }
+  if (SMALL && valid) {
+#pragma unroll
+    for (int b = 0; b < NBA; ++b) {
+      const uint32_t mL = S.meta[mbaseL + (uint64_t)b * n];
+      const uint32_t mR = S.meta[mbaseR + (uint64_t)b * n];
+      const uint32_t mM = S.meta[mbaseM + (uint64_t)b * n];
+      s_meta[(0u * B + b) * 64u + lane] = (epv_meta_t)mL;
+      s_meta[(1u * B + b) * 64u + lane] = (epv_meta_t)mR;
+      s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM;
+      const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
+      r_w[b] = (uint32_t)(epv_meta_t)mM | (K << 16) | ((2u * (mL >> EPV_INIT_SHIFT) + (mR >> EPV_INIT_SHIFT)) << 24);
+      need_rec += K + (EPV_TOPO_LEAF(b + 1) ? 0u : 1u);
+      if (K >= 2u) heavy += K;
+    }
+  } else if (!SMALL && valid) {
 #pragma unroll 4
     for (uint32_t b = 0; b < B; ++b) {
       const uint32_t mL = S.meta[mbaseL + (uint64_t)b * n];
@@ -261,7 +306,8 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   const int last_lane = vmask ? 63 - __clzll((long long)vmask) : 0;
   if (FUSED && valid && (lane == 0 || lane == last_lane)) {
     const bool hasLL = S.g0 + site > 1u, hasRR = S.g0 + site < S.n_global - 2u;
-    for (uint32_t b = 0; b < B; ++b) {
+    // (S.B, not B: unrolled for a small tree, this two-lane loop alone cost the NN = 5 body 8 bytes of scratch)
+    for (uint32_t b = 0; b < S.B; ++b) {
       if (lane == 0) s_edge[b] = hasLL ? S.meta[(selLL ? Bn : 0ull) + (uint64_t)b * n + (site - 2)] : (epv_meta_t)0;
       if (lane == last_lane) s_edge[B + b] = hasRR ? S.meta[(selRR ? Bn : 0ull) + (uint64_t)b * n + (site + 2)] : (epv_meta_t)0;
     }
@@ -272,6 +318,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   bool f_listed = false;
   const uint64_t f_wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave_id;
   bool pending = valid;
+  // SMALL: this lane's row of the node table (the generic body's regA[node][lane])
+  uint32_t r_node[NNA];
+#pragma unroll
+  for (int node = 0; node < NNA; ++node) r_node[node] = 0u;
   while (__any(pending)) {
     const uint32_t wantR = pending ? need_rec : 0u, wantH = pending ? heavy : 0u;
     const uint32_t inclR = wave_incl_scan_u32(wantR), inclH = wave_incl_scan_u32(wantH);
@@ -320,14 +370,25 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     if (!GPOOL && EPV_P2_DENSE_LIST && B > 1u) {      // (a single branch: every lane is its own pair)
       // 1a. pair words lane | node << 6 | first record << 18 (an LDS pool holds fewer than 2^14 records)
       uint32_t n_pairs = 0u;
-      if (run && heavy)
+      if constexpr (SMALL) {
+        if (run && heavy)
+#pragma unroll
+          for (int b = 0; b < NBA; ++b) n_pairs += EPV_RW_K(r_w[b]) >= 2u ? 1u : 0u;   // (a jump on either side)
+      } else if (run && heavy)
         for (uint32_t b = 0; b < B; ++b)
           n_pairs += ((s_meta[(0u * B + b) * 64u + lane] | s_meta[(1u * B + b) * 64u + lane]) & EPV_NJ_MASK) ? 1u : 0u;
       const uint32_t inclP = wave_incl_scan_u32(n_pairs);
       const uint32_t totP = epv_bcast(inclP, 63);
-      if (n_pairs) {
+      if (SMALL && n_pairs) {
         uint32_t hcur = hbase, at = inclP - n_pairs;
-        for (uint32_t node = 1u; node < S.N; ++node) {
+#pragma unroll
+        for (int node = 1; node < NNA; ++node) {
+          const uint32_t K = EPV_RW_K(r_w[node - 1]);
+          if (K >= 2u) { regA[at++] = (uint32_t)lane | ((uint32_t)node << 6) | (hcur << 18); hcur += K; }
+        }
+      } else if (n_pairs) {
+        uint32_t hcur = hbase, at = inclP - n_pairs;
+        for (uint32_t node = 1u; node < NNODE; ++node) {
           const uint32_t b = node - 1u;
           const uint32_t K = (s_meta[(0u * B + b) * 64u + lane] & EPV_NJ_MASK) + (s_meta[(1u * B + b) * 64u + lane] & EPV_NJ_MASK) + 1u;
           if (K < 2u) continue;
@@ -350,7 +411,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       __builtin_amdgcn_wave_barrier();     // regA goes back to pruning
     } else if (run && heavy) {
       uint32_t hcur = hbase;
-      for (uint32_t node = 1u; node < S.N; ++node) {
+      for (uint32_t node = 1u; node < NNODE; ++node) {
         const uint32_t b = node - 1u;
         const uint32_t K = (s_meta[(0u * B + b) * 64u + lane] & EPV_NJ_MASK) + (s_meta[(1u * B + b) * 64u + lane] & EPV_NJ_MASK) + 1u;
         if (K < 2u) continue;
@@ -385,7 +446,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     if (run) {
       // ---- 3. pruning, reverse pre-order (SingleSiteSampler.cpp:116-157)
       uint32_t off = need_rec, hcur = hbase + heavy;
-      for (uint32_t node = S.N - 1u; node >= 1u; --node) {
+      // (small tree: kept rolled -- unrolled, the scheduler hoisted every node's loads and the kernel
+      // spilled to scratch from NN = 3 on)
+#pragma unroll 1
+      for (uint32_t node = NNODE - 1u; node >= 1u; --node) {
         const uint32_t b = node - 1u;
         const uint32_t mL = s_meta[(0u * B + b) * 64u + lane], mR = s_meta[(1u * B + b) * 64u + lane];
         const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
@@ -437,6 +501,72 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     unsigned long long dirty = 0ull, multi = 0ull, deep = 0ull;
     const uint32_t root_state = run ? (uint32_t)(s_meta[(2u * B) * 64u + lane] >> EPV_INIT_SHIFT) : 0u;
     uint32_t hcur = hbase;
+    if constexpr (SMALL) {
+      // (small tree: the fused phase's dense emission; nothing in this loop is wave-wide)
+      if (run) {
+        // the node table's row of this lane, one batch of independent LDS reads
+#pragma unroll
+        for (int node = 1; node < NNA; ++node) r_node[node] = regA[(uint32_t)node * 64u + lane];
+#pragma unroll
+        for (int node = 1; node < NNA; ++node) {
+          const int b = node - 1;
+          const uint32_t K = EPV_RW_K(r_w[b]);
+          const uint32_t off = r_node[node];
+          uint32_t start_state = root_state;
+#pragma unroll
+          for (int p = 1; p < node; ++p)
+            if (EPV_TOPO_PARENT(node) == (uint32_t)p) start_state = r_node[p] >> 31;
+          const bool leaf = EPV_TOPO_LEAF(node);
+          const uint32_t mM = EPV_RW_META(r_w[b]);
+          uint32_t prev = start_state;
+          bool clean = true;
+          unsigned long long word = 0ull, w64 = 0ull;
+          double pk0 = my[(size_t)off * RS], pk1 = my[(size_t)off * RS + 1u];
+          for (uint32_t k = 0; k < K; ++k) {
+            const bool last_seg = (k + 1u == K);
+            double nxt0, nxt1;
+            if (last_seg && leaf) {          // q of a leaf: the observed state
+              const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
+              nxt0 = leaf_state ? 0.0 : 1.0;
+              nxt1 = leaf_state ? 1.0 : 0.0;
+            } else {
+              nxt0 = my[(size_t)(off + k + 1u) * RS];      // p[k+1], or the node's q
+              nxt1 = my[(size_t)(off + k + 1u) * RS + 1u];
+            }
+            double PT0, nb, u_end, u_first;
+            if (K == 1u) {
+              const double *t = s_tab + ((uint32_t)b * 4u + EPV_RW_TAB(r_w[b])) * EPV_SEGTAB_DBL;
+              PT0 = prev ? t[3] : t[2];
+              nb = prev ? t[5] : t[4];
+              const epv_block2 blk = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, (uint32_t)node, 0u, 0u, 0u);
+              u_end = blk.d0; u_first = blk.d1;
+            } else {
+              const double *hr = list + (size_t)(hcur + k) * HREC;
+              PT0 = prev ? hr[3] : hr[2];
+              nb = prev ? hr[5] : hr[4];
+              u_end = hr[6]; u_first = hr[7];
+            }
+            const double p0 = PT0 * nxt0 / (prev ? pk1 : pk0);
+            const uint32_t sampled = (u_end > p0) ? 1u : 0u;
+            const bool seg_clean = (sampled == prev) && (1.0 - u_first < nb);
+            clean = clean && seg_clean;
+            word |= (unsigned long long)sampled << (k & 63u);
+            if (k < 64u) w64 = word;
+            prev = sampled;
+            pk0 = nxt0; pk1 = nxt1;
+          }
+          const uint32_t hrec0 = hcur;
+          if (K >= 2u) hcur += K;
+          // node table row for the children and the emission pass (see the generic body below); the
+          // emission pass reads other lanes' rows, so the row goes to LDS as well
+          r_node[node] = off | (prev << 31) | (clean ? 0u : 1u << 30) | (K >= 2u ? hrec0 << 14 : 0u);
+          regA[node * 64u + lane] = r_node[node];
+          if (!clean && K >= 2u) list[(size_t)hrec0 * HREC + 6u] = epv_u2d(w64);
+          s_meta[(2u * B + (uint32_t)b) * 64u + lane] = (epv_meta_t)(start_state << EPV_INIT_SHIFT);
+          ident = ident && clean && mM == (start_state << EPV_INIT_SHIFT);
+        }
+      }
+    } else
     for (uint32_t node = 1u; node < S.N; ++node) {
       const uint32_t b = node - 1u;
       // what the wave-wide hand-over below needs from this lane's branch
@@ -606,7 +736,17 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     //         Everything else: start states of the proposal's branches into the other buffer,
     //         and the site onto the accept list of this block's shard.
     const bool to_list = run && !ident;
-    if (to_list) {
+    if (SMALL && to_list) {
+#pragma unroll
+      for (int node = 1; node < NNA; ++node) {
+        uint32_t st = root_state;
+#pragma unroll
+        for (int p = 1; p < node; ++p)
+          if (EPV_TOPO_PARENT(node) == (uint32_t)p) st = r_node[p] >> 31;
+        S.meta[(selM ? 0ull : Bn) + (uint64_t)(node - 1) * n + site] = (epv_meta_t)(st << EPV_INIT_SHIFT);
+      }
+      S.prop_flag[tid] = 0u;
+    } else if (!SMALL && to_list) {
       for (uint32_t node = 1u; node < S.N; ++node) {
         const uint32_t par = S.parent[node];
         const uint32_t st = (par == 0u) ? root_state : (regA[par * 64u + lane] >> 31);
@@ -641,13 +781,22 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       //      staged meta words and the heavy records.
       uint32_t *plist = reinterpret_cast<uint32_t *>(pool);
       uint32_t npair = 0u;
-      if (run)
+      if constexpr (SMALL) {
+        if (run)
+#pragma unroll
+          for (int node = 1; node < NNA; ++node) npair += (r_node[node] >> 30) & 1u;
+      } else if (run)
         for (uint32_t node = 1u; node < S.N; ++node) npair += (regA[node * 64u + lane] >> 30) & 1u;
       const uint32_t inclP = wave_incl_scan_u32(npair);
       const uint32_t totP = epv_bcast(inclP, 63);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (npair) {
+      if (SMALL && npair) {
+        uint32_t at = inclP - npair;
+#pragma unroll
+        for (int node = 1; node < NNA; ++node)
+          if ((r_node[node] >> 30) & 1u) plist[at++] = (uint32_t)lane | ((uint32_t)node << 6);
+      } else if (npair) {
         uint32_t at = inclP - npair;
         for (uint32_t node = 1u; node < S.N; ++node)
           if ((regA[node * 64u + lane] >> 30) & 1u) plist[at++] = (uint32_t)lane | (node << 6);
@@ -812,7 +961,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           const uint32_t bl = (ow >> (8u + w)) & 1u, bm = (ow >> (9u + w)) & 1u, br = (ow >> (10u + w)) & 1u;
 #ifdef EPV_ACC_GLOBAL_META
           if (F.meta_cache) {
-            const uint32_t B2 = S.B;
+            const uint32_t B2 = B;
 #pragma unroll 4
             for (uint32_t b = 0; b < B2; ++b) {
               const epv_meta_t m0 = S.meta[meta_idx(S, bl, b, c - 1u)];
@@ -827,7 +976,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
             // the meta words of the triple's columns without a global round trip: the neighbours'
             // current paths were staged at the head of the kernel (they belong to other colours and
             // do not change in this phase), the proposal's sit where the site's own column was
-            const uint32_t B2 = S.B;
+            const uint32_t B2 = B;
 #pragma unroll 4
             for (uint32_t b = 0; b < B2; ++b) {
               const epv_meta_t mP = s_meta[(2u * B2 + b) * 64u + o];
@@ -841,7 +990,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               mc[(2u * B2 + b) * 64u] = m2;
             }
 #endif
-            v = triple_llh_cached(S, s_const, s_blen, mc, 64u, 0u, bl, c - 1u, 1u, bm, c, 2u, br, c + 1u, A);
+            v = triple_llh_cached<NN ? NN - 1 : 0>(S, s_const, s_blen, mc, 64u, 0u, bl, c - 1u, 1u, bm, c, 2u, br, c + 1u, A);
           } else {
             v = triple_llh(S, s_const, s_blen, bl, c - 1u, bm, c, br, c + 1u, A);
           }
