@@ -318,7 +318,7 @@ int plan_p3(epv_ctx *c) {
     if (kids[node] > 2u) return EPV_OK;                  // two child fields per node word
     if (c->subtree[node] != 1u) qrow[node] = qrows++;
   }
-  if (qrows > 63u) return EPV_OK;                        // (six bits in the node word)
+  if (qrows > 63u) return EPV_OK;                        // (six bits in the node word; at N <= 128 only unary nodes reach it)
   // tables: node words [N] | internal nodes deepest first [n_up] | their level starts [D + 2] |
   //         all nodes but the root by depth [N - 1] | their level starts [D + 2]
   std::vector<uint32_t> tab;
@@ -369,23 +369,26 @@ int plan_p3(epv_ctx *c) {
   // 160 slabs per XCD.  Used when the launch has more blocks than the pool has slabs (EPV_P3_SLAB_POOL=2: always)
   static const int pool_env = std::getenv("EPV_P3_SLAB_POOL") ? std::atoi(std::getenv("EPV_P3_SLAB_POOL")) : 1;
   const uint64_t launch_waves = ((c->S.phase_cap + 255u) / 256u) * 4u;
-  c->p3_slots = (pool_env == 2 || (pool_env && launch_waves > 8u * 160u * 4u)) ? 160u : 0u;
-  const uint64_t waves = c->p3_slots ? 8ull * c->p3_slots * 4u : launch_waves;
+  const uint32_t slots = (pool_env == 2 || (pool_env && launch_waves > 8u * 160u * 4u)) ? 160u : 0u;
+  const uint64_t waves = slots ? 8ull * slots * 4u : launch_waves;
   const uint64_t need = waves * ((uint64_t)qrows * 128u + list_cap * EPV_HREC_SHORT);
   if (need * sizeof(double) > (24ull << 30)) return EPV_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  c->gpool3_need = need;
   if (tab.size() > 2048u) return EPV_OK;
+  const size_t shared = const_lds_bytes(N) + (size_t)B * 4u * EPV_SEGTAB_DBL * 8u + (tab.size() + 1u) / 2u * 8u;
+  const size_t per_wave = ((size_t)EPV_P3_PCAP * 3u + EPV_P3_PCAP / 8u + (max_depth * 64u * 2u + 7u) / 8u + (max_depth + 3u) / 2u) * 8u;   // pair list, pair results, group offsets
+  const size_t lds = shared + 4u * per_wave;
+  if (lds > 120u * 1024u) return EPV_OK;      // (a very deep tree's group offsets: keep the first kernels)
+  // (every refusal above leaves the context as it was: from here on the plan is taken)
+  HIP_TRY(c, hipSetDevice(c->device));
   if (!c->d_nodetab) HIP_TRY(c, hipMalloc(&c->d_nodetab, 2048u * sizeof(uint32_t)));
   if (!c->d_slabflags) {
     HIP_TRY(c, hipMalloc(&c->d_slabflags, 8u * 256u * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_slabflags, 0, 8u * 256u * sizeof(uint32_t)));
   }
   HIP_TRY(c, hipMemcpy(c->d_nodetab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const size_t shared = const_lds_bytes(N) + (size_t)B * 4u * EPV_SEGTAB_DBL * 8u + (tab.size() + 1u) / 2u * 8u;
-  const size_t per_wave = ((size_t)EPV_P3_PCAP * 3u + EPV_P3_PCAP / 8u + (max_depth * 64u * 2u + 7u) / 8u + (max_depth + 3u) / 2u) * 8u;   // pair list, pair results, group offsets
-  c->p3_lds = shared + 4u * per_wave;
-  if (c->p3_lds > 120u * 1024u) return EPV_OK;      // (a very deep tree's group offsets: keep the first kernels)
+  c->p3_slots = slots;
+  c->gpool3_need = need;
+  c->p3_lds = lds;
   c->p3_list_cap = (uint32_t)list_cap;
   c->p3_qrows = qrows;
   c->p3_nup = n_up;
@@ -666,6 +669,72 @@ int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
   return EPV_OK;
 }
 
+// the kernel variants of a colour phase (EPV_PLAN_* fields of include/epievo_mi355x.h): launch_phase
+// launches what this says, epv_phase_plan and epv_phase_mode report it
+struct PhasePlan {
+  uint32_t propose;      // EPV_PLAN_V1 / V2 / V3 / FUSED
+  bool gpool;            // V1, V2: the record pool in global memory
+  bool refq;             // the proposal ratio is evaluated (V1 takes the reference template)
+  uint32_t small_nn;     // fused: the small-tree body's node count, 0 = generic body
+  uint32_t p3_words;     // V3: words per node mask
+  bool p3_slab_pool;     // V3: slabs from the per-XCD pool
+  uint32_t jumps;        // EPV_PLAN_JUMPS_*
+  uint32_t accept;       // EPV_PLAN_ACCEPT_*
+  bool listed;           // the accept stage reads the listed sites
+  bool meta_cache;       // (accept and fused kernels) the LDS meta cache
+  uint32_t word() const {
+    return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
+           p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16;
+  }
+};
+PhasePlan phase_plan(const epv_ctx *c) {
+  PhasePlan P{};
+  // (root resampling changes the proposal's normalising constant with the path: the ratio must be evaluated)
+  P.refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
+  // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
+  // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
+  // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us, DESIGN.md section 4.1);
+  // EPV_PROPOSE_V2_GLOBAL=1 forces it for A/B runs (the third kernel, where the plan allows it, still wins)
+  static const bool p2_global = std::getenv("EPV_PROPOSE_V2_GLOBAL") != nullptr;
+  const bool p3 = c->p3 && !P.refq;
+  const bool p2 = !p3 && c->use_p2 && !P.refq && (!c->p2_gpool || p2_global);
+  static const bool no_cache = std::getenv("EPV_ACCEPT_NO_CACHE") != nullptr;
+  P.meta_cache = c->S.B <= 8u && !no_cache;
+  if (p2 && c->fused) {
+    P.propose = EPV_PLAN_FUSED;
+    P.small_nn = c->use_small && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
+    P.jumps = EPV_PLAN_JUMPS_FUSED;
+    P.accept = EPV_PLAN_ACCEPT_FUSED;
+    return P;
+  }
+  if (p3) {
+    P.propose = EPV_PLAN_V3;
+    P.p3_words = c->S.N > 64u ? 2u : 1u;
+    P.p3_slab_pool = c->p3_slots != 0u;
+  } else if (p2) {
+    P.propose = EPV_PLAN_V2;
+    P.gpool = c->p2_gpool;
+  } else {
+    P.propose = EPV_PLAN_V1;
+    P.gpool = c->mh_gpool;
+  }
+  // segment-parallel jumps pay on long branches (single branch T = 1: +17 %, every segment is
+  // dirty and needs several trials) and cost on short ones (tree.nwk: -12 %, one dirty segment in
+  // fourteen branches does not repay the extra hand-over): profiles/r02_ab_seg_jumps.txt
+  // The one-segment tasks (the first bucket: ~95 % on short branches) otherwise go to their own lean
+  // kernel, epv_mh_jumps_all_kernel.  (Forward-rejection mode keeps the general kernel for
+  // everything: a flip there can need 1e5 trials, which only the wave-wide search takes in reasonable time.)
+  static const int j1_env = std::getenv("EPV_JUMPS1") ? std::atoi(std::getenv("EPV_JUMPS1")) : 1;
+  P.jumps = p2 && seg_jumps_on(c) ? EPV_PLAN_JUMPS_SEGMENTS
+          : j1_env != 0 && !(c->S.flags & EPV_FLAG_FORWARD_REJECTION) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
+  // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
+  static const int acc_v3 = std::getenv("EPV_ACCEPT_V3") ? std::atoi(std::getenv("EPV_ACCEPT_V3")) : -1;
+  P.accept = (acc_v3 >= 0 ? acc_v3 != 0 : !P.meta_cache) ? EPV_PLAN_ACCEPT_V3
+           : P.meta_cache ? EPV_PLAN_ACCEPT_CACHE : EPV_PLAN_ACCEPT_NO_CACHE;
+  P.listed = p2 || p3;
+  return P;
+}
+
 int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
   uint64_t first = 0, last = 0, own_lo = 0, own_hi = 0;
   int prc = phase_range(c, &first, &last);
@@ -691,22 +760,10 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     ++c->ev_used;
     HIP_TRY(c, hipEventRecord(e0, c->stream));
   }
-  // (root resampling changes the proposal's normalising constant with the path: the ratio must be evaluated)
-  const bool refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
-  // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
-  // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
-  // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us, DESIGN.md section 4.1);
-  // EPV_PROPOSE_V2_GLOBAL=1 forces it for A/B runs
-  static const bool p2_global = std::getenv("EPV_PROPOSE_V2_GLOBAL") != nullptr;
-  const bool p3 = c->p3 && !refq;
-  const bool p2 = !p3 && c->use_p2 && !refq && (!c->p2_gpool || p2_global);
+  const PhasePlan P = phase_plan(c);
+  const uint32_t meta_cache = P.meta_cache ? 1u : 0u;
   uint32_t list_mode = 0;
-  // segment-parallel jumps pay on long branches (single branch T = 1: +17 %, every segment is
-  // dirty and needs several trials) and cost on short ones (tree.nwk: -12 %, one dirty segment in
-  // fourteen branches does not repay the extra hand-over): profiles/r02_ab_seg_jumps.txt
-  static const bool no_cache = std::getenv("EPV_ACCEPT_NO_CACHE") != nullptr;
-  const uint32_t meta_cache = (c->S.B <= 8u && !no_cache) ? 1u : 0u;
-  if (p2 && c->fused) {
+  if (P.propose == EPV_PLAN_FUSED) {
     // the whole phase in one kernel, one wave per 64 sites (see epv_propose2.h)
     const int frc = ensure_fused_buffers(c);
     if (frc) return frc;
@@ -718,7 +775,7 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     F.lanes = c->fused_lanes;
     static const int grouped = std::getenv("EPV_FUSED_GROUPED_ROUNDS") ? std::atoi(std::getenv("EPV_FUSED_GROUPED_ROUNDS")) : 4;
     F.grouped_rounds = (uint32_t)std::max(0, grouped);
-    const auto kf = fused_kernel(c->use_small ? c->S.N : 0u);
+    const auto kf = fused_kernel(P.small_nn);
     hipLaunchKernelGGL(kf, dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,
                        c->p2_pool, c->p2_list_cap, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
@@ -727,37 +784,37 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     if (c->halo_mode) ++c->phases_used;
     return EPV_OK;
   }
-  const uint32_t seg_mode = (p2 && seg_jumps_on(c)) ? 1u : 0u;
+  const bool seg_mode = P.jumps == EPV_PLAN_JUMPS_SEGMENTS;
   if (seg_mode) { const int src = ensure_seg_buffers(c); if (src) return src; }
-  if (p3) {
+  if (P.propose == EPV_PLAN_V3) {
     // large tree: a 16-bit word per (node, lane) in LDS, q rows and heavy records in a slab (epv_propose3.h)
     list_mode = 1u + (c->phase_parity & 1u);
     const unsigned pb = (unsigned)((threads + 255u) / 256u);
     { const int rc3 = ensure_slab(c, &c->d_gpool3, &c->gpool3_cap, c->gpool3_need); if (rc3) return rc3; }
-    auto k3 = c->S.N > 64u ? epv_mh_propose3_kernel<2> : epv_mh_propose3_kernel<1>;
+    auto k3 = P.p3_words == 2u ? epv_mh_propose3_kernel<2> : epv_mh_propose3_kernel<1>;
     hipLaunchKernelGGL(k3, dim3(pb), dim3(256), c->p3_lds, c->stream, c->S, (uint32_t)colour,
                        (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p3_list_cap,
                        c->p3_qrows, c->p3_nup, c->p3_depth, c->phase_parity & 1u, c->d_counters, c->d_gpool3, c->d_segtab,
                        c->d_nodetab, c->d_slabflags, c->p3_slots);
     ++c->phase_parity;
-  } else if (p2) {
+  } else if (P.propose == EPV_PLAN_V2) {
     list_mode = 1u + (c->phase_parity & 1u);
     const unsigned pt = 64u * c->p2_waves, pb = (unsigned)((threads + pt - 1u) / pt);
-    if (c->p2_gpool) { const int rc2 = ensure_slab(c, &c->d_gpool2, &c->gpool2_cap, c->gpool2_need); if (rc2) return rc2; }
-    auto kern = c->p2_gpool ? (seg_mode ? epv_mh_propose2_kernel<true, true, false> : epv_mh_propose2_kernel<true, false, false>)
-                            : (seg_mode ? epv_mh_propose2_kernel<false, true, false> : epv_mh_propose2_kernel<false, false, false>);
+    if (P.gpool) { const int rc2 = ensure_slab(c, &c->d_gpool2, &c->gpool2_cap, c->gpool2_need); if (rc2) return rc2; }
+    auto kern = P.gpool ? (seg_mode ? epv_mh_propose2_kernel<true, true, false> : epv_mh_propose2_kernel<true, false, false>)
+                        : (seg_mode ? epv_mh_propose2_kernel<false, true, false> : epv_mh_propose2_kernel<false, false, false>);
     hipLaunchKernelGGL(kern, dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S, (uint32_t)colour, (uint32_t)seed,
                        (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p2_pool, c->p2_list_cap,
-                       c->phase_parity & 1u, c->d_counters, c->p2_gpool ? c->d_gpool2 : (double *)nullptr, c->d_segtab,
+                       c->phase_parity & 1u, c->d_counters, P.gpool ? c->d_gpool2 : (double *)nullptr, c->d_segtab,
                        EpvFused{});
     ++c->phase_parity;
   } else {
-    if (c->mh_gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
-    auto kern = c->mh_gpool ? (refq ? epv_mh_propose_kernel<true, true> : epv_mh_propose_kernel<true, false>)
-                            : (refq ? epv_mh_propose_kernel<false, true> : epv_mh_propose_kernel<false, false>);
+    if (P.gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
+    auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true> : epv_mh_propose_kernel<true, false>)
+                        : (P.refq ? epv_mh_propose_kernel<false, true> : epv_mh_propose_kernel<false, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
-                       c->pool_entries, c->d_counters, c->mh_gpool ? c->d_gpool : (double *)nullptr);
+                       c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr);
   }
   if (seg_mode) {
     // dirty segments one lane each, then their branches one lane each; both lists are sized on
@@ -784,13 +841,9 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
       const double est = (double)threads * c->S.B * std::min(1.0, 0.1 + c->kbar) / 2048.0;
       tpw = est >= 64.0 ? 64u : est >= 32.0 ? 32u : est >= 16.0 ? 16u : 8u;
     }
-    // the one-segment tasks (the first bucket: ~95 % on short branches) in their own lean kernel; the general
-    // one then takes the rest with a grid sized for it.  (Forward-rejection mode keeps the general kernel for
-    // everything: a flip there can need 1e5 trials, which only the wave-wide search takes in reasonable time.)
-    static const int j1_env = std::getenv("EPV_JUMPS1") ? std::atoi(std::getenv("EPV_JUMPS1")) : 1;
-    const bool j1 = j1_env != 0 && !(c->S.flags & EPV_FLAG_FORWARD_REJECTION);
-    // a block (4 waves) takes 4*tpw tasks per pass; size the grid for ~1/4 of the worst case
-    if (j1) {
+    // the one-segment tasks in their own lean kernel (phase_plan), the general one then takes the rest
+    // with a grid sized for it; a block (4 waves) takes 4*tpw tasks per pass; size the grid for ~1/4 of the worst case
+    if (P.jumps == EPV_PLAN_JUMPS_ALL) {
       const uint64_t j1b = std::min<uint64_t>((max_tasks / 4u + 255u) / 256u + 1u, 256u);
       const uint64_t jgb = std::min<uint64_t>((max_tasks / 16u + 4u * tpw - 1u) / (4u * tpw) + 1u, 64u);
       hipLaunchKernelGGL(epv_mh_jumps_all_kernel, dim3(EPV_SHARDS, (unsigned)(jgb + j1b)), dim3(256), const_lds_bytes(c->S.N),
@@ -814,8 +867,7 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     const bool full = acc_full >= 0 ? acc_full != 0 : c->S.B > 8u;
     const unsigned ax = (unsigned)std::max<uint64_t>(1u, ((full ? per_shard : per_shard / 2u) + 255u) / 256u);
     // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
-    static const int acc_v3 = std::getenv("EPV_ACCEPT_V3") ? std::atoi(std::getenv("EPV_ACCEPT_V3")) : -1;
-    if (acc_v3 >= 0 ? acc_v3 != 0 : !meta_cache) {
+    if (P.accept == EPV_PLAN_ACCEPT_V3) {
       const unsigned ax3 = (unsigned)std::max<uint64_t>(1u, (per_shard + 4u * EPV_ACC3_SITES - 1u) / (4u * EPV_ACC3_SITES));
       hipLaunchKernelGGL(epv_mh_accept3_kernel, dim3(ax3, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
                          c->S, (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo,
@@ -824,8 +876,7 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     hipLaunchKernelGGL(epv_mh_accept_kernel, dim3(ax, EPV_SHARDS), dim3(256), acc_lds, c->stream,
                        c->S, (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo,
                        own_hi, c->d_counters, list_mode, meta_cache);
-  } else if (static const int acc_v3b = std::getenv("EPV_ACCEPT_V3") ? std::atoi(std::getenv("EPV_ACCEPT_V3")) : -1;
-             acc_v3b >= 0 ? acc_v3b != 0 : !meta_cache) {
+  } else if (P.accept == EPV_PLAN_ACCEPT_V3) {
     // every site of the colour (reference proposal arithmetic on a large tree), a lane per (site, triple)
     const unsigned ax3 = (unsigned)std::max<uint64_t>(1u, (threads + 4u * EPV_ACC3_SITES - 1u) / (4u * EPV_ACC3_SITES));
     hipLaunchKernelGGL(epv_mh_accept3_kernel, dim3(ax3, 1), dim3(256), const_lds_bytes(c->S.N), c->stream,
@@ -1192,11 +1243,15 @@ EPV_API int epv_get_options(epv_ctx *c, uint32_t *flags) {
 
 EPV_API int epv_phase_mode(epv_ctx *c, uint32_t *mode) {
   if (!c || !mode || !c->have_paths) return EPV_ERR_ARG;
-  const bool refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
-  static const bool p2_global = std::getenv("EPV_PROPOSE_V2_GLOBAL") != nullptr;
-  const bool p2 = c->use_p2 && !refq && (!c->p2_gpool || p2_global);
-  if (c->p3 && !refq) { *mode = EPV_PHASE_V3; return EPV_OK; }
-  *mode = !p2 ? EPV_PHASE_V1 : c->fused ? EPV_PHASE_FUSED : seg_jumps_on(c) ? EPV_PHASE_V2_SEGMENTS : EPV_PHASE_V2;
+  const PhasePlan P = phase_plan(c);
+  *mode = P.propose == EPV_PLAN_V3 ? EPV_PHASE_V3 : P.propose == EPV_PLAN_FUSED ? EPV_PHASE_FUSED
+        : P.propose == EPV_PLAN_V1 ? EPV_PHASE_V1 : P.jumps == EPV_PLAN_JUMPS_SEGMENTS ? EPV_PHASE_V2_SEGMENTS : EPV_PHASE_V2;
+  return EPV_OK;
+}
+
+EPV_API int epv_phase_plan(epv_ctx *c, uint32_t *word) {
+  if (!c || !word || !c->have_paths) return EPV_ERR_ARG;
+  *word = phase_plan(c).word();
   return EPV_OK;
 }
 

@@ -171,6 +171,7 @@ std::vector<epv_ctx *> SingleSiteSampler::contexts() const {
 void SingleSiteSampler::set_options(uint32_t flags) {
   SAMPLE_ROOT = (flags & (uint32_t)EPV_OPT_SAMPLE_ROOT) != 0;
   for (epv_ctx *c : contexts()) check_on(c, epv_set_options(c, flags), "epv_set_options");
+  options_ = flags;
 }
 void SingleSiteSampler::set_timing(int every) {
   for (epv_ctx *c : contexts()) check_on(c, epv_set_timing(c, every), "epv_set_timing");
@@ -324,13 +325,15 @@ void SingleSiteSampler::refresh_parts() {
 
 // SAMPLE_ROOT (a public field of the reference class, hard-wired false at SingleSiteSampler.cpp:441 and
 // set by none of its programs): the proposal also draws the root state (:167-176, :246-249).  The
-// field is forwarded to every context as EPV_OPT_SAMPLE_ROOT before each call that runs updates.
+// field is forwarded to every context as EPV_OPT_SAMPLE_ROOT before each call that runs updates, together
+// with the other options of set_options: every context runs with the same word.
 void SingleSiteSampler::apply_sample_root() {
+  const uint32_t bit = (uint32_t)EPV_OPT_SAMPLE_ROOT;
+  options_ = SAMPLE_ROOT ? (options_ | bit) : (options_ & ~bit);
   for (epv_ctx *c : contexts()) {
     uint32_t flags = 0;
     check_on(c, epv_get_options(c, &flags), "epv_get_options");
-    const uint32_t want = SAMPLE_ROOT ? (flags | (uint32_t)EPV_OPT_SAMPLE_ROOT) : (flags & ~(uint32_t)EPV_OPT_SAMPLE_ROOT);
-    if (want != flags) check_on(c, epv_set_options(c, want), "epv_set_options");
+    if (flags != options_) check_on(c, epv_set_options(c, options_), "epv_set_options");
   }
 }
 
@@ -497,6 +500,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
     epv_ctx *c = q.ctx;
     check_on(c, epv_set_tree(c, th.n_nodes(), th.parent_ids.data(), th.subtree_sizes.data(), th.branches.data()),
              "epv_set_tree");
+    check_on(c, epv_set_options(c, options_), "epv_set_options");   // (a context made here starts with none)
     const FlatPaths part = slice_sites_padded(paths, held_first, q.lo, q.hi);
     const double dummy = 0.0;
     check_on(c, epv_upload_paths(c, part.n_sites, part.init.data(), part.offsets.data(),

@@ -109,7 +109,8 @@ public:
   void set_path_average(uint32_t n_points);
   void download_path_average(std::vector<uint32_t> &counts, uint64_t &n_samples);
   uint32_t path_average_points() const { return pa_points_; }
-  // EPV_OPT_* of include/epievo_mi355x.h on every context; HIP-event timing of the colour phases
+  // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
+  // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
   void set_timing(int every);
   void kernel_time_ms(double &avg_ms, uint64_t &n_launches);
@@ -186,6 +187,7 @@ private:
   std::vector<uint64_t> rows_of_slot_;   // statistics rows of every slot of the run
   uint32_t capacity_;
   uint32_t pa_points_ = 0;    // set_path_average
+  uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   int n_nodes_ = 0;
   uint64_t n_sites_ = 0;      // genome length (all slots)
   size_t world_ = 1;          // slots of the run (== slots_.size() unless one slot per process)

@@ -137,8 +137,10 @@ class CppSampler:
         return {"text": buf.value.decode(), "slots_here": ns.value, "parts_here": npart.value,
                 "rccl": bool(rccl.value), "halo": halo.value}
 
-    def set_options(self, reference_proposal_ratio=False, forward_rejection=False):
-        self._ck(self.L.epvd_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0)))
+    def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
+        """EPV_OPT_* of include/epievo_mi355x.h on every context, those of later resets included"""
+        self._ck(self.L.epvd_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
+                                         (4 if sample_root else 0)))
 
     def set_timing(self, every):
         self._ck(self.L.epvd_set_timing(self.h, int(every)))

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_blocks", "epv_reduce_blocks", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_blocks_to_rows", "epv_reduce_rows", "epv_reduce_gathered_rows", "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
+    "epv_phase_plan",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -116,6 +117,7 @@ def lib():
         L.epv_forward_last_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.epv_get_options.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_dev_write.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_dev_read.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_get_counters.argtypes = [vp, C.POINTER(_Counters)]
@@ -219,6 +221,19 @@ class DeviceSampler:
         v = C.c_uint32(0)
         self._ck(self.L.epv_phase_mode(self.h, C.byref(v)))
         return int(v.value)
+
+    PLAN_PROPOSE = ("V1", "V2", "V3", "fused")
+    PLAN_JUMPS = ("fused", "segments", "jumps_all", "jumps")
+    PLAN_ACCEPT = ("fused", "accept3", "accept_cache", "accept_no_cache")
+
+    def phase_plan(self):
+        """the kernel variants of a colour phase (epv_phase_plan, EPV_PLAN_* of include/epievo_mi355x.h)"""
+        v = C.c_uint32(0)
+        self._ck(self.L.epv_phase_plan(self.h, C.byref(v)))
+        w = int(v.value)
+        return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
+                    small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
+                    jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1))
 
     def capacity(self):
         v = C.c_uint32(0)

@@ -18,6 +18,12 @@ EXTRA_TREES = {
     "multi": "((A:0.1,B:0.1,C:0.2)X:0.1,(D:0.3,E:0.05)Y:0.2,F:0.8)R:0.0;\n",
     "cat6": "(((((A:0.05,B:0.07)U:0.04,C:0.1)V:0.03,D:0.15)W:0.06,E:0.2)Z:0.02,F:0.25)R:0.0;\n",
 }
+# stars of 3, 4 and 6 nodes: around the node counts the fused phase's small-tree bodies are made for
+SMALL_TREES = {
+    "cherry": "(A:0.3,B:0.2)R:0.0;\n",
+    "star3": "(A:0.1,B:0.3,C:0.2)R:0.0;\n",
+    "star5": "(A:0.1,B:0.2,C:0.05,D:0.3,E:0.15)R:0.0;\n",
+}
 
 
 def _tmp(name, text):
@@ -47,7 +53,7 @@ def tree_nwk():
 
 def config(name):
     """the tree of the named configuration: tree (4-leaf test/tree.nwk), pair (one branch,
-    T = 1), bal16 / bal32 (balanced), cat20 (caterpillar), or one of EXTRA_TREES"""
+    T = 1), bal16 / bal32 (balanced), cat20 (caterpillar), or one of EXTRA_TREES and SMALL_TREES"""
     if name == "tree":
         return tree_nwk()
     if name == "pair":
@@ -67,6 +73,8 @@ def config(name):
         return host.Tree.read(_tmp("cat20.nwk", text.rsplit(":", 1)[0] + ":0.0;\n"))
     if name in EXTRA_TREES:
         return host.Tree.read(_tmp(name + ".nwk", EXTRA_TREES[name]))
+    if name in SMALL_TREES:
+        return host.Tree.read(_tmp(name + ".nwk", SMALL_TREES[name]))
     raise KeyError(name)
 
 

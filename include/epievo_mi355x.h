@@ -127,6 +127,27 @@ int epv_get_options(epv_ctx *ctx, uint32_t *flags);
 enum { EPV_PHASE_V1 = 0, EPV_PHASE_V2 = 1, EPV_PHASE_V2_SEGMENTS = 2, EPV_PHASE_FUSED = 3, EPV_PHASE_V3 = 4 };
 int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
 
+/* The exact kernel variants a colour phase of the resident paths launches, as one word (the launch
+ * code reads the same plan; for tests and profiles).  Fields that do not apply to the chosen
+ * proposal kernel are 0.
+ *   bits 0-1   proposal kernel: EPV_PLAN_V1 (epv_mh_propose_kernel), EPV_PLAN_V2 (epv_mh_propose2_kernel),
+ *              EPV_PLAN_V3 (epv_mh_propose3_kernel), EPV_PLAN_FUSED (epv_mh_propose2_kernel, fused phase)
+ *   bit  2     record pool in global memory (V1: its slab, V2: its slab; 0 = LDS)
+ *   bit  3     V1: the reference proposal-ratio template (EPV_OPT_REFERENCE_PROPOSAL_RATIO, EPV_OPT_SAMPLE_ROOT)
+ *   bits 4-7   fused: the small-tree body's node count NN (2 .. 5), 0 = the generic body
+ *   bits 8-9   V3: 64-bit words per node mask (1 for trees of at most 64 nodes, else 2)
+ *   bit  10    V3: slabs from the per-XCD pool (1) or one per block of the launch (0)
+ *   bits 12-13 jump stage: EPV_PLAN_JUMPS_FUSED (inside the fused kernel), _SEGMENTS (epv_seg_search_kernel +
+ *              epv_seg_assemble_kernel + epv_mh_jumps_kernel), _ALL (epv_mh_jumps_all_kernel), _GENERAL
+ *              (epv_mh_jumps_kernel alone)
+ *   bits 14-15 accept stage: EPV_PLAN_ACCEPT_FUSED (inside the fused kernel), _V3 (epv_mh_accept3_kernel),
+ *              _CACHE (epv_mh_accept_kernel with its LDS meta cache), _NO_CACHE (epv_mh_accept_kernel without)
+ *   bit  16    the accept stage reads the listed sites (proposal kernels V2 and V3; 0 = every site of the colour) */
+enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
+enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
+enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
+int epv_phase_plan(epv_ctx *ctx, uint32_t *word);
+
 /* initialize_paths_indep (src/prog/epievo_sim_pairwise.cpp:62-110) on the device, for the
  * two-node tree of one branch (epv_set_tree with n_nodes = 2 and epv_set_model first):
  * every interior site gets an independent end-conditioned path root[i] -> leaf[i] by

@@ -50,7 +50,7 @@ int epvd_download(epvd_sampler *s, uint8_t *init_state, uint64_t *offsets, doubl
 /* how the genome is laid out (tests, bench lines) */
 int epvd_layout(epvd_sampler *s, char *buf, int len, int *n_slots_here, int *n_parts_here, int *uses_rccl,
                 uint64_t *halo_columns);
-int epvd_set_options(epvd_sampler *s, uint32_t flags);           /* EPV_OPT_* on every context */
+int epvd_set_options(epvd_sampler *s, uint32_t flags);           /* EPV_OPT_* on every context, also those of later resets */
 int epvd_set_timing(epvd_sampler *s, int every);                 /* epv_set_timing on every context */
 int epvd_kernel_time_ms(epvd_sampler *s, double *avg_ms, uint64_t *n_launches);
 int epvd_phase_mode(epvd_sampler *s, uint32_t *mode);

@@ -132,3 +132,60 @@ def test_cpp_driver_slots_agree_on_a_grown_capacity(monkeypatch):
     p = s.paths()
     assert p.n_sites == fp.n_sites and p.counts().max() <= 2047
     s.close()
+
+
+def _oracle_mode(model, tree, fp, burn, batch, seed, cap=16, **opts):
+    o = orc.Oracle(tree, model, fp, "B", cap=cap, seed=seed)
+    o.set_sampler(bool(opts.get("forward_rejection")))
+    o.set_proposal_mode(bool(opts.get("reference_proposal_ratio")))
+    o.set_sample_root(bool(opts.get("sample_root")))
+    o.reset()
+    J, D, nacc, acc = o.run_mcmc(burn, batch)
+    return J, D, nacc, acc, o.paths()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["options-before-first-reset", "options-kept-across-full-reset"])
+def test_cpp_driver_options_reach_every_context(case, monkeypatch):
+    """epv::SingleSiteSampler keeps its option word and gives it to every context it makes: options set
+    before the first reset(model, tree, paths), and options kept across a second full reset (which makes
+    the contexts after the first again), must reach every part -- one part on other kernels or another
+    jump sampler walks another chain.  Forward rejection changes the chain (the reference ratio alone
+    does not: test_proposal_ratio.py), so both cases carry it."""
+    from epievo_amd import driver
+    monkeypatch.setenv("EPV_ROW_BLOCKS", "4")
+    monkeypatch.setenv("EPV_CONTEXTS_PER_GPU", "2")
+    model, tree, fp = simulate("tree", 40000, seed=12)
+    s = driver.CppSampler(1, 2, devices=[0, 0], capacity=16)
+    if case == "options-before-first-reset":
+        opts = dict(forward_rejection=True)
+        s.set_options(**opts)
+        s.reset(model, tree, fp)
+    else:
+        opts = dict(reference_proposal_ratio=True, forward_rejection=True)
+        s.reset(model, tree, fp)
+        s.set_options(**opts)
+        s.reset(model, tree, fp)
+    assert s.layout()["parts_here"] > 1
+    J, D, acc = s.run_mcmc(99, 0)
+    Jo, Do, _, acc_o, po = _oracle_mode(model, tree, fp, 1, 2, 99, **opts)
+    assert acc == acc_o and np.array_equal(J, Jo) and np.array_equal(D, Do)
+    assert orc.paths_equal(s.paths(), po)
+    s.close()
+
+
+@pytest.mark.gpu
+def test_local_group_options_reach_every_shard():
+    """the Python counterpart: options set on a LocalGroup of three shards before set_tree"""
+    from epievo_amd.parallel import LocalGroup
+    model, tree, fp = simulate("tree", 40000, seed=12)
+    g = LocalGroup(0, 3)
+    g.set_options(forward_rejection=True)
+    g.set_tree(tree); g.set_model(model); g.upload_paths(fp, 16)
+    assert len(g.subs) == 3
+    g.reset()
+    J, D, nacc = g.run_mcmc(1, 2, 99)
+    Jo, Do, nacc_o, _, po = _oracle_mode(model, tree, fp, 1, 2, 99, forward_rejection=True)
+    assert nacc == nacc_o and np.array_equal(J, Jo) and np.array_equal(D, Do)
+    assert orc.paths_equal(g.paths(), po)
+    g.close()

@@ -1,5 +1,6 @@
 """The fused colour phase's small-tree body (epv_propose2.h, NN = node count, EPV_P2_SMALL_TREE) must
-compute what the generic body computes, bit for bit, and both what the oracle's parallel rung computes:
+compute what the generic body computes, bit for bit, and both what the oracle's parallel rung computes
+(trees of 2, 3, 4 and 5 nodes, each asserted to run the body it names):
 paths, buffer selectors, cached triple likelihoods, J, D and the accept and overflow counters."""
 import os
 import subprocess
@@ -26,6 +27,8 @@ def run(knob):
     os.environ["EPV_P2_SMALL_TREE"] = knob       # read when a context is created
     d = DeviceSampler(0); d.set_tree(tree); d.set_model(model); d.upload_paths(fp, cap); d.reset()
     assert d.phase_mode() == 3
+    plan = d.phase_plan()       # the body that runs: NN = the node count, or 0 for the generic body
+    assert plan["propose"] == "fused" and plan["small_nn"] == (tree.n_nodes if knob == "1" else 0), plan
     if %(tiny)r:
         for w in range(3):
             try:
@@ -68,6 +71,12 @@ print("ok")
     ("star4", 3001, False, {}),
     ("star4", 3000, False, {"EPV_FUSED_LANES": "16"}),
     ("star4", 3000, True, {}),
+    ("cherry", 3001, False, {}),                     # 3 nodes
+    ("cherry", 3000, False, {"EPV_FUSED_LANES": "16"}),
+    ("cherry", 12001, True, {}),
+    ("star3", 3001, False, {}),                      # 4 nodes
+    ("star3", 3000, False, {"EPV_FUSED_LANES": "16"}),
+    ("star3", 20000, True, {}),
 ])
 def test_small_tree_body_equals_generic_and_oracle(cfg, n, tiny, env):
     code = _CODE % dict(root=_ROOT, tests=_TESTS, cfg=cfg, n=n, tiny=tiny)

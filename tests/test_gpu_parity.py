@@ -248,38 +248,62 @@ def test_long_branch_beyond_127_jumps(T, n):
 
 
 _SEPARATE = {"EPV_FUSED_PHASE": "0"}      # small launches take the fused phase kernel by default
-@pytest.mark.parametrize("cfg,n,env", [("tree", 20011, dict(_SEPARATE, EPV_SEG_JUMPS="1")),
-                                       ("tree", 20011, dict(_SEPARATE, EPV_SEG_JUMPS="0")),
-                                       ("pair", 9000, dict(_SEPARATE, EPV_SEG_JUMPS="0")),
-                                       ("pair", 9000, dict(_SEPARATE, EPV_SEG_JUMPS="1")),
-                                       ("cat6", 3000, dict(_SEPARATE, EPV_SEG_JUMPS="1")),
-                                       ("tree", 20011, dict(_SEPARATE, EPV_PROPOSE_V1="1")),
-                                       ("pair", 9000, dict(_SEPARATE, EPV_PROPOSE_V1="1")),
-                                       ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V2_GLOBAL="1", EPV_FORCE_GLOBAL_POOL="1")),
-                                       ("tree", 5000, dict(_SEPARATE, EPV_FORCE_GLOBAL_POOL="1", EPV_PROPOSE_V2_GLOBAL="1",
-                                                           EPV_SEG_JUMPS="1")),
-                                       ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="0")),
-                                       ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1")),
-                                       ("bal16", 9000, dict(_SEPARATE, EPV_P3_SLAB_POOL="2")),
-                                       ("bal32", 1500, dict(_SEPARATE, EPV_PROPOSE_V3="1")), ("bal64", 1200, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("bal64", 1200, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1", EPV_P3_SLAB_POOL="2")), ("cat20", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("cat20", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1", EPV_P3_SLAB_POOL="2")),
-                                       ("tree", 20011, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("bal16", 2000, dict(_SEPARATE, EPV_ACCEPT_V3="0")),
-                                       ("tree", 20011, dict(_SEPARATE, EPV_ACCEPT_V3="1")),
-                                       ("cat6", 3000, dict(_SEPARATE, EPV_ACCEPT_V3="1", EPV_SEG_JUMPS="1")),
-                                       ("pair", 9000, dict(_SEPARATE, EPV_ACCEPT_V3="1")),
-                                       ("cat6", 3000, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("star4", 3000, dict(_SEPARATE, EPV_PROPOSE_V3="1")),
-                                       ("pair", 9000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1")),
-                                       ("tree", 20011, {"EPV_FUSED_PHASE": "1"}), ("pair", 9000, {"EPV_FUSED_PHASE": "1"}),
-                                       ("cat6", 3000, {"EPV_FUSED_PHASE": "1"}),
-                                       ("tree", 20011, {"EPV_FUSED_PHASE": "1", "EPV_ACCEPT_NO_CACHE": "1"})])
-def test_every_kernel_path_is_bit_exact(cfg, n, env):
+_V2_GLOBAL = dict(_SEPARATE, EPV_FORCE_GLOBAL_POOL="1", EPV_PROPOSE_V2_GLOBAL="1", EPV_PROPOSE_V3="0")
+
+
+def _v2(gpool=False, **kw):
+    return dict(propose="V2", gpool=gpool, listed=True, **kw)
+
+
+def _v3(words, slab=False, **kw):
+    return dict(propose="V3", p3_words=words, p3_slab_pool=slab, listed=True, **kw)
+
+
+def _fused(nn):
+    return dict(propose="fused", small_nn=nn, jumps="fused", accept="fused")
+
+
+# (tree, n, knobs, the plan fields (DeviceSampler.phase_plan) the knobs are there to select)
+_PATHS = [
+    ("tree", 20011, dict(_SEPARATE, EPV_SEG_JUMPS="1"), _v2(jumps="segments")),
+    ("tree", 20011, dict(_SEPARATE, EPV_SEG_JUMPS="0"), _v2(jumps="jumps_all")),
+    ("pair", 9000, dict(_SEPARATE, EPV_SEG_JUMPS="0"), _v2(jumps="jumps_all")),
+    ("pair", 9000, dict(_SEPARATE, EPV_SEG_JUMPS="1"), _v2(jumps="segments")),
+    # (cat6: its record pool does not fit LDS by default, and the large-tree kernel would take it)
+    ("cat6", 3000, dict(_SEPARATE, EPV_SEG_JUMPS="1", EPV_FORCE_LDS_POOL="1"), _v2(jumps="segments")),
+    ("tree", 20011, dict(_SEPARATE, EPV_PROPOSE_V1="1"), dict(propose="V1", gpool=False, refq=False, listed=False)),
+    ("pair", 9000, dict(_SEPARATE, EPV_PROPOSE_V1="1"), dict(propose="V1", gpool=False, refq=False, listed=False)),
+    ("bal16", 2000, _V2_GLOBAL, _v2(gpool=True)),
+    ("tree", 5000, dict(_V2_GLOBAL, EPV_SEG_JUMPS="1"), _v2(gpool=True, jumps="segments")),
+    ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="0"), dict(propose="V1", gpool=True, accept="accept3")),
+    ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1)),
+    ("bal16", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1"), _v3(1)),
+    ("bal16", 9000, dict(_SEPARATE, EPV_P3_SLAB_POOL="2"), _v3(1, True)),
+    ("bal32", 1500, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1)),
+    ("bal64", 1200, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(2)),
+    ("bal64", 1200, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1", EPV_P3_SLAB_POOL="2"), _v3(2, True)),
+    ("cat20", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1)),
+    ("cat20", 2000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1", EPV_P3_SLAB_POOL="2"), _v3(1, True)),
+    ("tree", 20011, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1, accept="accept_cache")),
+    ("bal16", 2000, dict(_SEPARATE, EPV_ACCEPT_V3="0"), _v3(1, accept="accept_no_cache")),
+    ("tree", 20011, dict(_SEPARATE, EPV_ACCEPT_V3="1"), _v2(accept="accept3")),
+    ("cat6", 3000, dict(_SEPARATE, EPV_ACCEPT_V3="1", EPV_SEG_JUMPS="1", EPV_FORCE_LDS_POOL="1"),
+     _v2(jumps="segments", accept="accept3")),
+    ("pair", 9000, dict(_SEPARATE, EPV_ACCEPT_V3="1"), _v2(accept="accept3")),
+    ("cat6", 3000, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1)),
+    ("star4", 3000, dict(_SEPARATE, EPV_PROPOSE_V3="1"), _v3(1)),
+    ("pair", 9000, dict(_SEPARATE, EPV_PROPOSE_V3="1", EPV_P3_MIN_LIST="1"), _v3(1)),
+    ("tree", 20011, {"EPV_FUSED_PHASE": "1"}, _fused(5)), ("pair", 9000, {"EPV_FUSED_PHASE": "1"}, _fused(2)),
+    ("cat6", 3000, {"EPV_FUSED_PHASE": "1", "EPV_FORCE_LDS_POOL": "1"}, _fused(0)),
+    ("tree", 20011, {"EPV_FUSED_PHASE": "1", "EPV_ACCEPT_NO_CACHE": "1"}, _fused(5))]
+
+
+@pytest.mark.parametrize("cfg,n,env,expect", _PATHS, ids=["%s-%d-env%d" % (r[0], r[1], i) for i, r in enumerate(_PATHS)])
+def test_every_kernel_path_is_bit_exact(cfg, n, env, expect):
     """the library picks its kernels by workload (proposal kernel generation, where its record
     pool lives, sequential or segment-parallel jump sampling); every combination must give the
-    oracle's bits, so each is forced here on a workload that would not select it by itself"""
+    oracle's bits, so each is forced here on a workload that would not select it by itself, and the plan
+    the library reports must be the one the row names"""
     import os
     import subprocess
     import sys
@@ -293,6 +317,9 @@ from epievo_amd.sampler import DeviceSampler
 model, tree, fp = simulate(%r, %d, seed=6)
 cap = int(max(16, 2 * fp.counts().max() + 8))
 d = DeviceSampler(0); d.set_tree(tree); d.set_model(model); d.upload_paths(fp, cap); d.reset()
+plan, expect = d.phase_plan(), %r
+bad = dict((k, (v, plan[k])) for k, v in expect.items() if plan[k] != v)
+assert not bad, "plan differs (expected, got): %%r; plan %%r" %% (bad, plan)
 o = orc.Oracle(tree, model, fp, "B", cap=cap, seed=19); o.reset()
 Jd, Dd, nd = d.run_mcmc(2, 3, 19, sweep_base=4)
 Jo, Do, no, _ = o.run_mcmc(2, 3, sweep_base=4)
@@ -310,8 +337,10 @@ for w in range(2):
     nb = o2.sweep(w)
     assert orc.paths_equal(d2.paths(), o2.paths())
 assert d2.counters()["overflow"] == o2.counters()["overflow"]
+assert d.phase_plan() == plan
 print("ok")
-''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), cfg, n)
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)), cfg, n,
+       expect)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
 
@@ -352,7 +381,7 @@ def test_fused_phase_with_many_heavy_branches_and_several_rounds(scale, n, monke
     depend on those rows.  Fused phase forced; bit-exact against rung B"""
     from common import tree_nwk
     from epievo_amd import host
-    from epievo_amd.sampler import DeviceSampler
+    from epievo_amd.sampler import CapacityError, DeviceSampler
     monkeypatch.setenv("EPV_FUSED_PHASE", "1")
     model = simulate("tree", 100, seed=1)[0]
     t0 = tree_nwk()
