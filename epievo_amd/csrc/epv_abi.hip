@@ -21,8 +21,45 @@
 #include "epv_math.h"
 #include "epv_pavg.h"
 
+// The library's knobs: environment variables that a context reads once, when epv_create makes it.
+// Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
+// brackets, the tests that set it: P test_gpu_parity, M test_kernel_matrix, F test_fused_small_tree,
+// A test_path_average_gpu.
+//   EPV_PROPOSE_V1=1        the first proposal kernel everywhere [P M]
+//   EPV_PROPOSE_V3=0/1      the large-tree proposal kernel never / wherever the plan allows it; default:
+//                           where the second kernel's record pool does not fit LDS [P M]
+//   EPV_SEG_JUMPS=0/1       segment-parallel jump kernels off / on; default: kbar >= 0.25 [P M A]
+//   EPV_FUSED_PHASE=0/1     the fused colour phase off / on; default: phases of <= 3072 waves [P M F A]
+//   EPV_P2_SMALL_TREE=0     the fused phase's generic body also on trees of <= EPV_P2_SMALL_MAX nodes [F]
+//   EPV_FUSED_LANES=4/8/16/32/64   sites per wave of the fused phase (any other value: 64); default:
+//                           by launch size [F]
+//   EPV_FORCE_LDS_POOL      (set) the record pool in LDS wherever one lane's worst case fits [P M]
+//   EPV_FORCE_GLOBAL_POOL   (set) no LDS record pool: the first kernel's goes to global memory, and
+//                           the second kernel is not planned [M]
+//   EPV_P3_MIN_LIST         (set) the large-tree kernel's heavy list holds one lane's worst case only,
+//                           so that busy waves run in several rounds [P]
+//   EPV_P3_SLAB_POOL=0/1/2  the large-tree kernel's slabs: one per block / from a per-XCD pool when the
+//                           launch has more blocks than the pool has slabs (default) / always pooled [P M]
+//   EPV_ACCEPT_V3=0/1       the accept stage: the (no-)cache kernel / epv_mh_accept3_kernel; default:
+//                           accept3 where there is no meta cache [P]
+//   EPV_ACCEPT_NO_CACHE     (set) no LDS meta cache in the accept stage [P]
+struct EpvKnobs {
+  bool propose_v1 = false;
+  int propose_v3 = -1;         // -1: by the plan
+  int seg_jumps = -1;          // -1: by workload
+  int fused_phase = -1;        // -1: by launch size
+  bool small_tree = true;
+  uint32_t fused_lanes = 0;    // 0: by launch size
+  bool force_lds_pool = false, force_global_pool = false;
+  bool p3_min_list = false;
+  int p3_slab_pool = 1;
+  int accept_v3 = -1;          // -1: by the meta cache
+  bool accept_no_cache = false;
+};
+
 struct epv_ctx {
   int device = 0;
+  EpvKnobs knobs;
   hipStream_t stream = nullptr;
   std::string err;
   EpvDev S{};
@@ -63,20 +100,15 @@ struct epv_ctx {
   bool mh_gpool = false;        // record pool of the propose kernel in global memory (large trees)
   double *d_gpool = nullptr;
   uint64_t gpool_cap = 0;       // doubles allocated
-  uint64_t gpool_need = 0, gpool2_need = 0, gpool3_need = 0;   // what the plans ask for; allocated when a launch first uses the slab
-  // second-generation proposal kernel (epv_propose2.h)
-  bool use_p2 = true;            // EPV_PROPOSE_V1=1 falls back to the first kernel (A/B runs)
-  uint32_t p2_pool = 0, p2_list_cap = 0;   // LDS: doubles per wave; global slab: rows per lane + heavy records
-  uint32_t p2_waves = 1;                   // waves per block
-  bool p2_gpool = false;
+  uint64_t gpool_need = 0, gpool3_need = 0;   // what the plans ask for; allocated when a launch first uses the slab
+  // second-generation proposal kernel (epv_propose2.h), one wave per block
+  uint32_t p2_pool = 0;          // LDS doubles per wave
+  bool p2_gpool = false;         // the pool does not fit LDS: the kernel is not planned
   size_t p2_lds = 0;
-  double *d_gpool2 = nullptr;
-  uint64_t gpool2_cap = 0;
   double *d_gpool3 = nullptr;
   uint64_t gpool3_cap = 0;
   double *d_segtab = nullptr;    // [B][4][6] single-segment matrices, refreshed by epv_reset
   // third proposal kernel (epv_propose3.h): large trees, where the record pool does not fit LDS
-  int use_p3 = -1;               // -1 = whenever the plan allows it, EPV_PROPOSE_V3=0/1 forces
   bool p3 = false;               // decided by plan_p3 for the uploaded tree and paths
   uint32_t p3_list_cap = 0, p3_qrows = 0, p3_nup = 0, p3_depth = 0;
   uint32_t p3_slots = 0;         // slabs per XCD handed out to resident blocks (0 = a slab per block of the launch)
@@ -84,19 +116,11 @@ struct epv_ctx {
   size_t p3_lds = 0;
   uint32_t *d_nodetab = nullptr; // node words and level lists of epv_mh_propose3_kernel (EPV_P3_*)
   uint32_t phase_parity = 0;     // accept lists are double-buffered by phase parity
-  int use_seg = -1;              // segment-parallel jump kernels (epv_jumps2.h): -1 = by workload
-                                 // (long branches, kbar >= 0.25), EPV_SEG_JUMPS=0/1 forces
   // fused colour phase (epv_propose2.h, FUSED): one kernel per phase for launches of few waves
-  int use_fused = -1;            // -1 = by launch size (EPV_FUSED_MAX_WAVES), EPV_FUSED_PHASE=0/1 forces
-  uint32_t fused_max_waves = 3072;   // measured on tree.nwk: +46 % at 520 waves, +20 % at 1700, +5 % at 2600, -4..-14 % at 5200 (tools/fused_scan.sh)
   bool fused = false;            // decided by plan_p2 for the uploaded paths
-  uint32_t fused_lanes = 64;     // sites per wave of the fused phase (64 / 32 / 16: EPV_FUSED_LANES, else by launch size)
-  // the fused phase's small-tree body (epv_propose2.h, NN = node count) for trees of at most
-  // EPV_P2_SMALL_MAX nodes: 1 = wherever the tree fits (default), EPV_P2_SMALL_TREE=0 = the generic body
-  int use_small = 1;
+  uint32_t fused_lanes = 64;     // sites per wave of the fused phase (64 / 32 / 16 by launch size)
   EpvFused F{};                  // per-wave lists, allocated on first use
   uint64_t fused_waves = 0;      // waves the lists are allocated for
-  uint32_t tasks_per_wave = 0;   // epv_mh_jumps_kernel: lanes of a wave that own a task (0 = by workload)
   double kbar = 0.0;  // mean jumps per (site, branch) of the uploaded paths
   double fwd_alloc_ms = 0.0, fwd_sim_ms = 0.0;   // epv_forward_simulate: device memory management / the simulation itself
   size_t mh_lds = 0;
@@ -122,6 +146,30 @@ struct epv_ctx {
 };
 
 namespace {
+
+// the knobs as the environment holds them now (epv_create)
+EpvKnobs read_knobs() {
+  EpvKnobs k;
+  auto has = [](const char *name) { return std::getenv(name) != nullptr; };
+  auto num = [](const char *name, int unset) { const char *e = std::getenv(name); return e ? std::atoi(e) : unset; };
+  k.propose_v1 = num("EPV_PROPOSE_V1", 0) != 0;
+  if (has("EPV_PROPOSE_V3")) k.propose_v3 = num("EPV_PROPOSE_V3", 0) != 0 ? 1 : 0;
+  if (has("EPV_SEG_JUMPS")) k.seg_jumps = num("EPV_SEG_JUMPS", 0) != 0 ? 1 : 0;
+  if (has("EPV_FUSED_PHASE")) k.fused_phase = num("EPV_FUSED_PHASE", 0) != 0 ? 1 : 0;
+  k.small_tree = num("EPV_P2_SMALL_TREE", 1) != 0;
+  if (has("EPV_FUSED_LANES")) {
+    const int v = num("EPV_FUSED_LANES", 0);
+    k.fused_lanes = (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) ? (uint32_t)v : 64u;
+  }
+  k.force_lds_pool = has("EPV_FORCE_LDS_POOL");
+  k.force_global_pool = has("EPV_FORCE_GLOBAL_POOL");
+  k.p3_min_list = has("EPV_P3_MIN_LIST");
+  k.p3_slab_pool = num("EPV_P3_SLAB_POOL", 1);
+  k.accept_v3 = num("EPV_ACCEPT_V3", -1);
+  k.accept_no_cache = has("EPV_ACCEPT_NO_CACHE");
+  return k;
+}
+
 
 int fail(epv_ctx *c, int code, const std::string &msg) {
   if (c) c->err = msg;
@@ -189,9 +237,7 @@ int plan_mh(epv_ctx *c) {
   // LDS pool while it leaves >= 8 waves per CU (2 per SIMD); otherwise a global-memory slab
   // per block (the working set of the resident waves stays in L2 / Infinity Cache)
   const bool lds_ok = want <= max_fit && (fixed + std::min(want, max_fit) * 16u) * 8u <= 160u * 1024u;
-  // tuning knobs (tools/ab_env.py): EPV_FORCE_LDS_POOL / EPV_FORCE_GLOBAL_POOL
-  const bool use_lds = std::getenv("EPV_FORCE_GLOBAL_POOL") ? false
-                       : std::getenv("EPV_FORCE_LDS_POOL") ? want <= max_fit : lds_ok;
+  const bool use_lds = c->knobs.force_global_pool ? false : c->knobs.force_lds_pool ? want <= max_fit : lds_ok;
   if (use_lds) {
     const uint64_t pool = std::min(want, max_fit);
     c->mh_gpool = false;
@@ -221,18 +267,20 @@ using fused_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, 
                                 uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused);
 fused_kernel_t fused_kernel(uint32_t nn) {
   switch (nn) {
-    case 2: return epv_mh_propose2_kernel<false, true, true, 2>;
-    case 3: return epv_mh_propose2_kernel<false, true, true, 3>;
-    case 4: return epv_mh_propose2_kernel<false, true, true, 4>;
-    case 5: return epv_mh_propose2_kernel<false, true, true, 5>;
-    default: return epv_mh_propose2_kernel<false, true, true>;
+    case 2: return epv_mh_propose2_kernel<true, true, 2>;
+    case 3: return epv_mh_propose2_kernel<true, true, 3>;
+    case 4: return epv_mh_propose2_kernel<true, true, 4>;
+    case 5: return epv_mh_propose2_kernel<true, true, 5>;
+    default: return epv_mh_propose2_kernel<true, true>;
   }
 }
-bool seg_jumps_on(const epv_ctx *c) { return c->use_seg < 0 ? c->kbar >= 0.25 : c->use_seg != 0; }
-double p2_margin() {
-  if (const char *e = std::getenv("EPV_P2_MARGIN")) { const double v = std::atof(e); if (v >= 1.0 && v <= 4.0) return v; }
-  return 1.15;     // 1.25 -> 1.15 with the 8-double records: one more wave per CU, ~4 % of the waves take a second round
-}
+bool seg_jumps_on(const epv_ctx *c) { return c->knobs.seg_jumps < 0 ? c->kbar >= 0.25 : c->knobs.seg_jumps != 0; }
+// LDS pool of the second kernel relative to the typical demand: 1.25 -> 1.15 with the 8-double records
+// gave one more wave per CU, ~4 % of the waves take a second round
+constexpr double P2_MARGIN = 1.15;
+// the fused phase pays while a phase has at most this many waves: measured on tree.nwk, +46 % at 520
+// waves, +20 % at 1700, +5 % at 2600, -4..-14 % at 5200 (tools/fused_scan.sh)
+constexpr uint64_t FUSED_MAX_WAVES = 3072u;
 int plan_p2(epv_ctx *c) {
   const uint32_t B = c->S.B, C = c->S.C, N = c->S.N;
   const size_t shared = const_lds_bytes(N) + (size_t)B * 4u * 6u * 8u;     // constants, matrix table: once per block
@@ -245,14 +293,14 @@ int plan_p2(epv_ctx *c) {
   // three to five), at most 64 segments per branch (the hand-over's bit word), lists for the worst
   // case of every wave within 4 GB
   // sites per wave: halve while every SIMD could still get two waves
-  uint32_t f_lanes = 64u;
-  if (const char *e = std::getenv("EPV_FUSED_LANES")) { const int v = std::atoi(e); if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) f_lanes = (uint32_t)v; }
-  else while (f_lanes > 16u && (c->S.phase_cap + f_lanes / 2u - 1u) / (f_lanes / 2u) <= 2048u) f_lanes /= 2u;
+  uint32_t f_lanes = c->knobs.fused_lanes ? c->knobs.fused_lanes : 64u;
+  if (!c->knobs.fused_lanes)
+    while (f_lanes > 16u && (c->S.phase_cap + f_lanes / 2u - 1u) / (f_lanes / 2u) <= 2048u) f_lanes /= 2u;
   const uint64_t phase_waves = (c->S.phase_cap + 63u) / 64u;
   const uint64_t f_seg_cap = 64ull * B * (2u * C + 1u), f_bt_cap = 64ull * B;
   const uint64_t f_bytes = (c->S.phase_cap + f_lanes - 1u) / f_lanes * (f_seg_cap * (sizeof(EpvSegTask) + sizeof(EpvSegOut)) + f_bt_cap * 12u);
-  bool fused = c->use_p2 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
-               (c->use_fused < 0 ? phase_waves <= c->fused_max_waves : c->use_fused != 0);
+  bool fused = !c->knobs.propose_v1 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
+               (c->knobs.fused_phase < 0 ? phase_waves <= FUSED_MAX_WAVES : c->knobs.fused_phase != 0);
   // heavy-segment records: 8 doubles, 10 when the segment-parallel jump kernels read them back
   const uint64_t hrec = (fused || seg_jumps_on(c)) ? EPV_HREC : EPV_HREC_SHORT;
   const uint64_t worst_dbl = 2u * worst_rec + hrec * worst_heavy;
@@ -262,36 +310,20 @@ int plan_p2(epv_ctx *c) {
   uint32_t n_internal = 0;
   for (uint32_t node = 1; node < N; ++node) n_internal += c->subtree[node] != 1u;
   const double rec_per_lane = B * (1.0 + lam) + n_internal;     // K per branch, +1 for an internal node's q
-  const uint64_t typical_dbl = (uint64_t)(64.0 * (2.0 * rec_per_lane + (double)hrec * B * heavy_per_branch) * p2_margin()) + 64u;
+  const uint64_t typical_dbl = (uint64_t)(64.0 * (2.0 * rec_per_lane + (double)hrec * B * heavy_per_branch) * P2_MARGIN) + 64u;
   const uint64_t max_fit = fixed + 64u < 160u * 1024u ? (160u * 1024u - fixed) / 8u : 0u;
   uint64_t want = std::max(worst_dbl, typical_dbl);
   // the fused phase reuses the pool for the search's cooperative area and then for the accept
   // stage's task table, results, accumulators (992 doubles) and meta words (3 B columns of 64)
   if (fused) want = std::max<uint64_t>(want, std::max<uint64_t>(EPV_COOP_BYTES / 8u, 992u + 48u * (uint64_t)B));
   const bool lds_ok = want <= max_fit && (fixed + want * 8u) * 5u <= 160u * 1024u;   // >= 5 waves per CU
-  const bool use_lds = std::getenv("EPV_FORCE_GLOBAL_POOL") ? false
-                       : std::getenv("EPV_FORCE_LDS_POOL") ? want <= max_fit : lds_ok;
+  const bool use_lds = c->knobs.force_global_pool ? false : c->knobs.force_lds_pool ? want <= max_fit : lds_ok;
   if (fixed > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the 160 KiB LDS node table");
-  c->p2_waves = 1;
-  if (const char *e = std::getenv("EPV_P2_WAVES_PER_BLOCK")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) c->p2_waves = (uint32_t)v; }
   c->fused = fused && use_lds;
   c->fused_lanes = f_lanes;
-  if (use_lds) {
-    c->p2_gpool = false;
-    c->p2_pool = (uint32_t)((want + 1u) & ~(uint64_t)1u);
-    c->p2_list_cap = 0;
-    c->p2_lds = shared + c->p2_waves * (per_wave_fixed + (size_t)c->p2_pool * 8u);
-    return EPV_OK;
-  }
-  // global slab per wave: worst_rec rows of 64 interleaved records + a heavy list for the wave
-  const uint64_t rows = worst_rec;
-  const uint64_t list_cap = std::max<uint64_t>(worst_heavy, (uint64_t)(64.0 * B * heavy_per_branch * 2.0) + 64u);
-  const uint64_t blocks = (c->S.phase_cap + 63u) / 64u;
-  c->gpool2_need = blocks * (rows * 128u + list_cap * EPV_HREC);
-  c->p2_gpool = true;
-  c->p2_pool = (uint32_t)rows;
-  c->p2_list_cap = (uint32_t)list_cap;
-  c->p2_lds = shared + c->p2_waves * per_wave_fixed;
+  c->p2_gpool = !use_lds;
+  c->p2_pool = use_lds ? (uint32_t)((want + 1u) & ~(uint64_t)1u) : 0u;
+  c->p2_lds = shared + per_wave_fixed + (size_t)c->p2_pool * 8u;
   return EPV_OK;
 }
 
@@ -301,8 +333,8 @@ int plan_p2(epv_ctx *c) {
 int plan_p3(epv_ctx *c) {
   c->p3 = false;
   const uint32_t B = c->S.B, C = c->S.C, N = c->S.N;
-  if (c->use_p3 == 0 || !c->use_p2 || N > 128u || N < 2u) return EPV_OK;     // (node masks of one or two 64-bit words)
-  if (c->use_p3 < 0 && !c->p2_gpool) return EPV_OK;     // the LDS pool is the better place while it fits
+  if (c->knobs.propose_v3 == 0 || c->knobs.propose_v1 || N > 128u || N < 2u) return EPV_OK;     // (node masks of one or two 64-bit words)
+  if (c->knobs.propose_v3 < 0 && !c->p2_gpool) return EPV_OK;     // the LDS pool is the better place while it fits
   // per node: parent, children, depth; q rows for the internal nodes below the root
   std::vector<uint32_t> depth(N, 0u), c1(N, 0u), c2(N, 0u), kids(N, 0u), qrow(N, 0u);
   uint32_t qrows = 0, max_depth = 0;
@@ -361,13 +393,12 @@ int plan_p3(epv_ctx *c) {
   const double heavy_per_branch = (1.0 + lam) - std::exp(-lam);
   const uint64_t worst_heavy = (uint64_t)B * (2u * C + 1u);
   // EPV_P3_MIN_LIST=1 (tests): one lane's worst case only, so that busy waves run in several rounds
-  static const bool min_list = std::getenv("EPV_P3_MIN_LIST") != nullptr;
-  const uint64_t list_cap = min_list ? worst_heavy : std::max<uint64_t>(worst_heavy, (uint64_t)(64.0 * B * heavy_per_branch * 1.5) + 64u);
+  const uint64_t list_cap = c->knobs.p3_min_list ? worst_heavy : std::max<uint64_t>(worst_heavy, (uint64_t)(64.0 * B * heavy_per_branch * 1.5) + 64u);
   if (list_cap >= (1ull << 20)) return EPV_OK;             // the pair word's record field
   // a pool of slabs per XCD, claimed by resident blocks (EPV_P3_SLAB_POOL=0: one per block of the launch):
   // 4 blocks of this kernel fit a CU (LDS) and an XCD of the MI355X has 32 CUs: 128 resident blocks at most,
   // 160 slabs per XCD.  Used when the launch has more blocks than the pool has slabs (EPV_P3_SLAB_POOL=2: always)
-  static const int pool_env = std::getenv("EPV_P3_SLAB_POOL") ? std::atoi(std::getenv("EPV_P3_SLAB_POOL")) : 1;
+  const int pool_env = c->knobs.p3_slab_pool;
   const uint64_t launch_waves = ((c->S.phase_cap + 255u) / 256u) * 4u;
   const uint32_t slots = (pool_env == 2 || (pool_env && launch_waves > 8u * 160u * 4u)) ? 160u : 0u;
   const uint64_t waves = slots ? 8ull * slots * 4u : launch_waves;
@@ -395,6 +426,13 @@ int plan_p3(epv_ctx *c) {
   c->p3_depth = max_depth;
   c->p3 = true;
   return EPV_OK;
+}
+
+// the launch shapes of every proposal kernel, for the current tree, paths and capacity
+int plan_kernels(epv_ctx *c) {
+  int rc = plan_mh(c);
+  if (!rc) rc = plan_p2(c);
+  return rc ? rc : plan_p3(c);
 }
 
 // per-wave lists of the fused phase, on first use
@@ -673,7 +711,7 @@ int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
 // launches what this says, epv_phase_plan and epv_phase_mode report it
 struct PhasePlan {
   uint32_t propose;      // EPV_PLAN_V1 / V2 / V3 / FUSED
-  bool gpool;            // V1, V2: the record pool in global memory
+  bool gpool;            // V1: the record pool in global memory
   bool refq;             // the proposal ratio is evaluated (V1 takes the reference template)
   uint32_t small_nn;     // fused: the small-tree body's node count, 0 = generic body
   uint32_t p3_words;     // V3: words per node mask
@@ -693,16 +731,13 @@ PhasePlan phase_plan(const epv_ctx *c) {
   P.refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
   // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
   // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
-  // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us);
-  // EPV_PROPOSE_V2_GLOBAL=1 forces it for A/B runs (the third kernel, where the plan allows it, still wins)
-  static const bool p2_global = std::getenv("EPV_PROPOSE_V2_GLOBAL") != nullptr;
+  // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us)
   const bool p3 = c->p3 && !P.refq;
-  const bool p2 = !p3 && c->use_p2 && !P.refq && (!c->p2_gpool || p2_global);
-  static const bool no_cache = std::getenv("EPV_ACCEPT_NO_CACHE") != nullptr;
-  P.meta_cache = c->S.B <= 8u && !no_cache;
+  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !c->p2_gpool;
+  P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
   if (p2 && c->fused) {
     P.propose = EPV_PLAN_FUSED;
-    P.small_nn = c->use_small && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
+    P.small_nn = c->knobs.small_tree && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
     P.jumps = EPV_PLAN_JUMPS_FUSED;
     P.accept = EPV_PLAN_ACCEPT_FUSED;
     return P;
@@ -713,7 +748,6 @@ PhasePlan phase_plan(const epv_ctx *c) {
     P.p3_slab_pool = c->p3_slots != 0u;
   } else if (p2) {
     P.propose = EPV_PLAN_V2;
-    P.gpool = c->p2_gpool;
   } else {
     P.propose = EPV_PLAN_V1;
     P.gpool = c->mh_gpool;
@@ -724,11 +758,10 @@ PhasePlan phase_plan(const epv_ctx *c) {
   // The one-segment tasks (the first bucket: ~95 % on short branches) otherwise go to their own lean
   // kernel, epv_mh_jumps_all_kernel.  (Forward-rejection mode keeps the general kernel for
   // everything: a flip there can need 1e5 trials, which only the wave-wide search takes in reasonable time.)
-  static const int j1_env = std::getenv("EPV_JUMPS1") ? std::atoi(std::getenv("EPV_JUMPS1")) : 1;
   P.jumps = p2 && seg_jumps_on(c) ? EPV_PLAN_JUMPS_SEGMENTS
-          : j1_env != 0 && !(c->S.flags & EPV_FLAG_FORWARD_REJECTION) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
+          : !(c->S.flags & EPV_FLAG_FORWARD_REJECTION) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
   // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
-  static const int acc_v3 = std::getenv("EPV_ACCEPT_V3") ? std::atoi(std::getenv("EPV_ACCEPT_V3")) : -1;
+  const int acc_v3 = c->knobs.accept_v3;
   P.accept = (acc_v3 >= 0 ? acc_v3 != 0 : !P.meta_cache) ? EPV_PLAN_ACCEPT_V3
            : P.meta_cache ? EPV_PLAN_ACCEPT_CACHE : EPV_PLAN_ACCEPT_NO_CACHE;
   P.listed = p2 || p3;
@@ -767,18 +800,16 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     // the whole phase in one kernel, one wave per 64 sites (see epv_propose2.h)
     const int frc = ensure_fused_buffers(c);
     if (frc) return frc;
-    const unsigned pt = 64u * c->p2_waves, per_block = c->fused_lanes * c->p2_waves;
-    const unsigned pb = (unsigned)((threads + per_block - 1u) / per_block);
-    if ((uint64_t)pb * c->p2_waves > c->fused_waves) return fail(c, EPV_ERR_STATE, "fused phase: launch larger than its lists");
+    const unsigned pb = (unsigned)((threads + c->fused_lanes - 1u) / c->fused_lanes);
+    if (pb > c->fused_waves) return fail(c, EPV_ERR_STATE, "fused phase: launch larger than its lists");
     EpvFused F = c->F;
     F.meta_cache = meta_cache;
     F.lanes = c->fused_lanes;
-    static const int grouped = std::getenv("EPV_FUSED_GROUPED_ROUNDS") ? std::atoi(std::getenv("EPV_FUSED_GROUPED_ROUNDS")) : 4;
-    F.grouped_rounds = (uint32_t)std::max(0, grouped);
+    F.grouped_rounds = 4u;     // rounds of the grouped search of a short segment list
     const auto kf = fused_kernel(P.small_nn);
-    hipLaunchKernelGGL(kf, dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S,
+    hipLaunchKernelGGL(kf, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,
-                       c->p2_pool, c->p2_list_cap, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
+                       c->p2_pool, 0u, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
     if (c->timing) HIP_TRY(c, hipEventRecord(e1, c->stream));
     HIP_TRY(c, hipGetLastError());
     if (c->halo_mode) ++c->phases_used;
@@ -799,14 +830,11 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     ++c->phase_parity;
   } else if (P.propose == EPV_PLAN_V2) {
     list_mode = 1u + (c->phase_parity & 1u);
-    const unsigned pt = 64u * c->p2_waves, pb = (unsigned)((threads + pt - 1u) / pt);
-    if (P.gpool) { const int rc2 = ensure_slab(c, &c->d_gpool2, &c->gpool2_cap, c->gpool2_need); if (rc2) return rc2; }
-    auto kern = P.gpool ? (seg_mode ? epv_mh_propose2_kernel<true, true, false> : epv_mh_propose2_kernel<true, false, false>)
-                        : (seg_mode ? epv_mh_propose2_kernel<false, true, false> : epv_mh_propose2_kernel<false, false, false>);
-    hipLaunchKernelGGL(kern, dim3(pb), dim3(pt), c->p2_lds, c->stream, c->S, (uint32_t)colour, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p2_pool, c->p2_list_cap,
-                       c->phase_parity & 1u, c->d_counters, P.gpool ? c->d_gpool2 : (double *)nullptr, c->d_segtab,
-                       EpvFused{});
+    const unsigned pb = (unsigned)((threads + 63u) / 64u);
+    auto kern = seg_mode ? epv_mh_propose2_kernel<true, false> : epv_mh_propose2_kernel<false, false>;
+    hipLaunchKernelGGL(kern, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S, (uint32_t)colour, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p2_pool, 0u,
+                       c->phase_parity & 1u, c->d_counters, (double *)nullptr, c->d_segtab, EpvFused{});
     ++c->phase_parity;
   } else {
     if (P.gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
@@ -835,12 +863,9 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     const uint64_t max_tasks = blocks / EPV_SHARDS * 64u * c->S.B + 64u * c->S.B;  // per shard
     // lanes of a wave that own a task (the others only help in the cooperative search): full
     // waves when there is work for every SIMD, fewer tasks per wave -- a shorter critical path --
-    // on a small genome (measured: tools/ab_envbench.py EPV_TASKS_PER_WAVE)
-    uint32_t tpw = c->tasks_per_wave;
-    if (tpw == 0) {
-      const double est = (double)threads * c->S.B * std::min(1.0, 0.1 + c->kbar) / 2048.0;
-      tpw = est >= 64.0 ? 64u : est >= 32.0 ? 32u : est >= 16.0 ? 16u : 8u;
-    }
+    // on a small genome (measured: DESIGN.md section 4.1)
+    const double est = (double)threads * c->S.B * std::min(1.0, 0.1 + c->kbar) / 2048.0;
+    const uint32_t tpw = est >= 64.0 ? 64u : est >= 32.0 ? 32u : est >= 16.0 ? 16u : 8u;
     // the one-segment tasks in their own lean kernel (phase_plan), the general one then takes the rest
     // with a grid sized for it; a block (4 waves) takes 4*tpw tasks per pass; size the grid for ~1/4 of the worst case
     if (P.jumps == EPV_PLAN_JUMPS_ALL) {
@@ -863,8 +888,7 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     // (on a large tree nearly every site is listed -- one clean proposal in thirty branches is rare --
     // and a block that strides twice runs two of the kernel's long dependent chains back to back)
     const uint64_t per_shard = (threads + EPV_SHARDS - 1u) / EPV_SHARDS;
-    static const int acc_full = std::getenv("EPV_ACCEPT_FULL_GRID") ? std::atoi(std::getenv("EPV_ACCEPT_FULL_GRID")) : -1;
-    const bool full = acc_full >= 0 ? acc_full != 0 : c->S.B > 8u;
+    const bool full = c->S.B > 8u;
     const unsigned ax = (unsigned)std::max<uint64_t>(1u, ((full ? per_shard : per_shard / 2u) + 255u) / 256u);
     // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
     if (P.accept == EPV_PLAN_ACCEPT_V3) {
@@ -933,16 +957,7 @@ EPV_API epv_ctx *epv_create(int device_id) {
   if (hipSetDevice(device_id) != hipSuccess) return nullptr;
   epv_ctx *c = new epv_ctx();
   c->device = device_id;
-  if (const char *e = std::getenv("EPV_PROPOSE_V1")) c->use_p2 = std::atoi(e) == 0;
-  if (const char *e = std::getenv("EPV_PROPOSE_V3")) c->use_p3 = std::atoi(e) != 0 ? 1 : 0;
-  if (const char *e = std::getenv("EPV_SEG_JUMPS")) c->use_seg = std::atoi(e) != 0 ? 1 : 0;
-  if (const char *e = std::getenv("EPV_FUSED_PHASE")) c->use_fused = std::atoi(e) != 0 ? 1 : 0;
-  if (const char *e = std::getenv("EPV_P2_SMALL_TREE")) c->use_small = std::atoi(e) != 0 ? 1 : 0;
-  if (const char *e = std::getenv("EPV_FUSED_MAX_WAVES")) { const long v = std::atol(e); if (v >= 0) c->fused_max_waves = (uint32_t)v; }
-  if (const char *e = std::getenv("EPV_TASKS_PER_WAVE")) {  // tuning knob
-    const int v = std::atoi(e);
-    if (v >= 1 && v <= 64) c->tasks_per_wave = (uint32_t)v;
-  }
+  c->knobs = read_knobs();
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_model, sizeof(EpvModelConst)) != hipSuccess ||
       hipMalloc(&c->d_counters, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess ||
@@ -958,17 +973,13 @@ EPV_API epv_ctx *epv_create(int device_id) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);   // (it has static LDS too)
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose3_kernel<2>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, false, false>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, true, false>),
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn)),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false>),
@@ -986,7 +997,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   free_paths(c);
   dfree(c->d_model); dfree(c->d_parent); dfree(c->d_subtree); dfree(c->d_blen);
-  dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_rows); dfree(c->d_gpool2); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
+  dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_rows); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
@@ -1031,7 +1042,7 @@ EPV_API int epv_set_tree(epv_ctx *c, int n_nodes, const uint32_t *parent_ids,
   c->S.blen = c->d_blen;
   c->have_tree = true;
   c->have_reset = false;
-  if (c->have_paths) { int rc = plan_mh(c); if (!rc) rc = plan_p2(c); return rc ? rc : plan_p3(c); }
+  if (c->have_paths) return plan_kernels(c);
   return EPV_OK;
 }
 
@@ -1129,7 +1140,7 @@ EPV_API int epv_upload_paths(epv_ctx *c, uint64_t n_sites, const uint8_t *init_s
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->have_paths = true;
   c->have_reset = false;
-  { int rc = plan_mh(c); if (!rc) rc = plan_p2(c); return rc ? rc : plan_p3(c); }
+  return plan_kernels(c);
 }
 
 // epievo_sim's forward simulation on the device (epv_forward.h): root sequence (given, or
@@ -1213,7 +1224,7 @@ EPV_API int epv_forward_simulate(epv_ctx *c, uint64_t n_sites, const uint8_t *ro
   const auto t_end = std::chrono::steady_clock::now();
   c->fwd_alloc_ms = std::chrono::duration<double, std::milli>(t_alloc - t_begin).count();
   c->fwd_sim_ms = std::chrono::duration<double, std::milli>(t_end - t_alloc).count();
-  { int prc = plan_mh(c); if (!prc) prc = plan_p2(c); return prc ? prc : plan_p3(c); }
+  return plan_kernels(c);
 }
 
 EPV_API int epv_forward_last_ms(epv_ctx *c, double *alloc_ms, double *simulate_ms) {
@@ -1299,7 +1310,7 @@ EPV_API int epv_set_capacity(epv_ctx *c, uint32_t capacity) {
   c->S.prop_states = ns.release();
   c->S.C = capacity;
   c->S.W = W;
-  { int rc2 = plan_mh(c); if (!rc2) rc2 = plan_p2(c); return rc2 ? rc2 : plan_p3(c); }
+  return plan_kernels(c);
 }
 
 EPV_API int epv_init_paths_indep(epv_ctx *c, uint64_t n_sites, const uint8_t *root_states,
@@ -1327,7 +1338,7 @@ EPV_API int epv_init_paths_indep(epv_ctx *c, uint64_t n_sites, const uint8_t *ro
     hipLaunchKernelGGL(epv_init_tasks_kernel, dim3((unsigned)((threads + 63u) / 64u)), dim3(64), 0, c->stream,
                        c->S, colour, first, last, d_leaf, c->d_counters);
     const uint64_t per_shard = threads / EPV_SHARDS + 256u;
-    const uint32_t tpw = c->tasks_per_wave ? c->tasks_per_wave : 32u;
+    const uint32_t tpw = 32u;
     const uint64_t jb = std::min<uint64_t>((per_shard + 4u * tpw - 1u) / (4u * tpw), 256u);
     hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
                        c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), EPV_INIT_SWEEP,
@@ -1480,7 +1491,7 @@ EPV_API int epv_indep_update_paths(epv_ctx *c, const double *rates, uint64_t see
                        c->d_indep, rates[0], rates[1], colour, first, last, (uint32_t)seed,
                        (uint32_t)(seed >> 32), sweep, c->d_counters);
     const uint64_t max_tasks = blocks / EPV_SHARDS * 64u * c->S.B + 64u * c->S.B;
-    const uint32_t tpw = c->tasks_per_wave ? c->tasks_per_wave : 32u;
+    const uint32_t tpw = 32u;
     const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);
     hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
                        c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, rates[0],
@@ -1722,23 +1733,17 @@ EPV_API int epv_run_mcmc_blocks(epv_ctx *c, uint64_t burn_in, uint64_t batch, ui
   if ((rc = snapshot_counters(c))) return rc;
   // the statistics of a context that shares its GPU with others run as one-wave blocks (they fit
   // into the LDS the colour phases leave free); the waves of a 256-site block add into its row, so
-  // this context's rows start from zero.  EPV_STAT_BLOCKS=1: the 256-lane kernel (A/B runs)
-  static const bool stat_blocks = std::getenv("EPV_STAT_BLOCKS") != nullptr;
+  // this context's rows start from zero
   unsigned long long *rows0 = (unsigned long long *)d_blocks + (uint64_t)(block_offset + (int64_t)blk_lo) * V;
   const uint64_t n_own = blk_hi - blk_lo + 1u;
-  if (!stat_blocks)
-    HIP_TRY(c, hipMemset2DAsync(rows0, nb_total * V * sizeof(unsigned long long), 0, n_own * V * sizeof(unsigned long long),
-                                batch, c->stream));
+  HIP_TRY(c, hipMemset2DAsync(rows0, nb_total * V * sizeof(unsigned long long), 0, n_own * V * sizeof(unsigned long long),
+                              batch, c->stream));
   for (uint64_t w = 0; w < batch; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
       if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
     ++c->n_sweeps;
-    if (stat_blocks)
-      hipLaunchKernelGGL(epv_suffstat_kernel, dim3((unsigned)n_own, (c->S.B + EPV_STAT_BCH - 1u) / EPV_STAT_BCH),
-                         dim3(256), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows0 + w * nb_total * V);
-    else
-      hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
-                         dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows0 + w * nb_total * V);
+    hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
+                       dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows0 + w * nb_total * V);
     if (c->pa_P && (rc = launch_pavg(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());

@@ -43,7 +43,6 @@ __device__ __forceinline__ uint32_t epv_bcast(uint32_t v, int src) {
 // 1 and 3 (row_bcast:15, row mask 0b1010) and lane 31 into rows 2 and 3 (row_bcast:31, 0b1100):
 // six v_add_u32_dpp instead of six ds_bpermute with index arithmetic and predicated adds
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-#ifndef EPV_SCAN_BPERMUTE
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
@@ -51,15 +50,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31
   return v;
-#else
-  const int lane = epv_lane();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-#endif
 }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
@@ -786,11 +776,7 @@ __device__ __forceinline__ void epv_jumps_body(const EpvDev &S, uint32_t seed_lo
   // Work is handed out in chunks, one per wave and pass.  The DEEP tasks (K >= 3 segments: the
   // long loops) come first and in small chunks -- a quarter of tasks_per_wave -- so that the
   // longest chains start early and stall fewer neighbours; the shallow ones (K <= 2) follow.
-#ifdef EPV_JUMPS_UNIFORM_CHUNKS
-  const uint32_t tpw_deep = tasks_per_wave;
-#else
   const uint32_t tpw_deep = tasks_per_wave >= 32u ? tasks_per_wave / 4u : tasks_per_wave;
-#endif
   const unsigned long long n_deep = n_tasks - n1;
   // skip_single: the one-segment tasks (the first bucket) have been done by epv_mh_jumps1_kernel
   const unsigned long long first_task = skip_single ? n0 : 0ull;

@@ -44,40 +44,26 @@ __device__ __forceinline__ epv_block2 epv_keyed_block(uint32_t seed_lo, uint32_t
   uint32_t k0 = seed_lo, k1 = seed_hi;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
-#if !defined(EPV_PHILOX_MUL_HI_LO)
     // one v_mad_u64_u32 per 32 x 32 -> 64 product instead of the v_mul_hi_u32 + v_mul_lo_u32 the
     // compiler picks (all three are quarter-rate on CDNA: 20 instead of 40 slow multiplies per
     // block; +2..4 % end to end, tools/ab_bench.py; the same bits)
     unsigned long long p0, p1;
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "s"(EPV_PHILOX_M0), "v"(c0) : "vcc");
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "s"(EPV_PHILOX_M1), "v"(c2) : "vcc");
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "s"(EPV_PHILOX_M0), "v"(c0) : "vcc");   // p0 = (uint64_t)EPV_PHILOX_M0 * c0
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "s"(EPV_PHILOX_M1), "v"(c2) : "vcc");   // p1 = (uint64_t)EPV_PHILOX_M1 * c2
     const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-#else
-    const uint32_t hi0 = __umulhi(EPV_PHILOX_M0, c0);
-    const uint32_t lo0 = EPV_PHILOX_M0 * c0;
-    const uint32_t hi1 = __umulhi(EPV_PHILOX_M1, c2);
-    const uint32_t lo1 = EPV_PHILOX_M1 * c2;
-#endif
-#if !defined(EPV_PHILOX_XOR2)
     // a ^ b ^ key in ONE instruction: gfx950's three-input boolean op with the XOR3 truth table (0x96);
     // the compiler emits two v_xor_b32 (40 instead of 20 per block).  The key is wave-uniform (kernel
     // arguments plus round constants), hence the scalar operand.
     uint32_t n0, n2;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n0) : "v"(hi1), "v"(c1), "s"(k0));
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n2) : "v"(hi0), "v"(c3), "s"(k1));
-#else
-    const uint32_t n0 = hi1 ^ c1 ^ k0;
-    const uint32_t n2 = hi0 ^ c3 ^ k1;
-#endif
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n0) : "v"(hi1), "v"(c1), "s"(k0));   // n0 = hi1 ^ c1 ^ k0
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(n2) : "v"(hi0), "v"(c3), "s"(k1));   // n2 = hi0 ^ c3 ^ k1
     c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
     k0 += EPV_PHILOX_W0;
     k1 += EPV_PHILOX_W1;
-#ifndef EPV_PHILOX_HOISTKEYS
     // keep the key schedule a chain of scalar adds next to its use: hoisted out of the kernels' loops the
     // twenty round keys live in SGPRs from the first block to the last and push other values into spills
     // (fused phase: 108 -> 91 spilled SGPRs, +1..2 % on tree.nwk; the large-tree kernels: +-0)
     asm volatile("" : "+s"(k0), "+s"(k1));
-#endif
   }
   const uint64_t a = ((uint64_t)c1 << 32) | c0;
   const uint64_t c = ((uint64_t)c3 << 32) | c2;

@@ -28,8 +28,7 @@
 // LDS per wave: constants, the matrix table, the node table regA[N][64] (record offset of the
 // branch above the node | proposal end state << 31) and a pool of doubles holding, for the
 // lanes that run in this round, their Felsenstein records {p0, p1} (K per branch, +1 for the
-// q of an internal node) followed by the wave's heavy-segment records.  GPOOL = true keeps the
-// pool in a per-wave slab of global memory (large trees), records interleaved by lane.
+// q of an internal node) followed by the wave's heavy-segment records.
 
 struct EpvSegRec {      // one segment, everything the recursions need
   double P00, P11;      // continuous_time_trans_prob_mat (pruning form: h = 1 / exp(len (r0 + r1)))
@@ -120,16 +119,8 @@ __device__ __forceinline__ void epv_flush_tasks(const EpvDev &S, unsigned long l
   }
 }
 
-#ifndef EPV_P2_DENSE_LIST
-#define EPV_P2_DENSE_LIST 1
-#endif
 #ifndef EPV_PROPOSE2_WAVES
 #define EPV_PROPOSE2_WAVES 3
-#endif
-// the fused phase emits its segment / branch tasks in one dense pass behind the node loop (1) or, as the
-// separate kernels do, node by node inside it (0; A/B runs)
-#ifndef EPV_FUSED_DENSE_EMIT
-#define EPV_FUSED_DENSE_EMIT 1
 #endif
 
 // -DEPV_P2_PROFILE: wave-time per section of the kernel, read back by tools/p2_profile.py
@@ -168,22 +159,20 @@ struct EpvFused {
 // stay for what other lanes read (heavy-pair merges, the emission pass, the acceptance stage).  Same
 // operations in the same order: the results are the generic body's bit for bit.  NN = 0: S.N nodes.
 #define EPV_P2_SMALL_MAX 5
-template <bool GPOOL, bool SEG, bool FUSED, int NN = 0>
+template <bool SEG, bool FUSED, int NN = 0>
 __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,
     uint64_t last, uint64_t own_first, uint64_t own_last, uint32_t pool_dbl, uint32_t list_cap,
     uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab, EpvFused F) {
-  static_assert(!FUSED || (SEG && !GPOOL), "the fused phase emits segments and keeps its pool in LDS");
+  static_assert(!FUSED || SEG, "the fused phase emits segments");
   constexpr bool SMALL = NN > 0;
-  static_assert(!SMALL || (FUSED && EPV_FUSED_DENSE_EMIT && NN >= 2 && NN <= EPV_P2_SMALL_MAX),
-                "the small-tree body is the fused phase's, with the dense emission pass");
+  static_assert(!SMALL || (FUSED && NN >= 2 && NN <= EPV_P2_SMALL_MAX), "the small-tree body is the fused phase's");
   constexpr int NNA = SMALL ? NN : 1;      // register array extents (1: unused by the generic body)
   constexpr int NBA = SMALL ? NN - 1 : 1;
   const uint32_t NNODE = SMALL ? (uint32_t)NN : S.N;
   // SEG: true = dirty SEGMENTS go to the segment-parallel jump kernels (epv_jumps2.h); 0 = dirty
   // branches go to epv_mh_jumps_kernel's bucketed lists
-  // pool_dbl: LDS pool -- doubles per wave; GPOOL -- record ROWS per lane (list_cap heavy records
-  // behind them; unused for the LDS pool, where records and list share pool_dbl)
+  // pool_dbl: the LDS pool, doubles per wave (records and heavy list share it); list_cap and gpool are unused
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   constexpr uint32_t HREC = SEG ? EPV_HREC : EPV_HREC_SHORT, LEN_AT = HREC - 2u, INFO_AT = HREC - 1u;
 #ifdef EPV_P2_PROFILE
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   const uint32_t wave_id = threadIdx.x >> 6;
   // the counter shard and list regions are per WAVE (as if every wave were its own block)
   const uint32_t my_shard = (blockIdx.x * (blockDim.x >> 6) + wave_id) & (EPV_SHARDS - 1u);
-  const uint32_t wave_dbl = regA_dbl + mc_dbl + (GPOOL ? 0u : ((pool_dbl + 1u) & ~1u));
+  const uint32_t wave_dbl = regA_dbl + mc_dbl + ((pool_dbl + 1u) & ~1u);
   double *s_const = s_mem;
   double *s_tab = s_mem + const_dbl;
   double *s_wave = s_mem + const_dbl + tab_dbl + (size_t)wave_id * wave_dbl;
@@ -214,11 +203,8 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   epv_meta_t *s_meta = reinterpret_cast<epv_meta_t *>(s_wave + regA_dbl);
   epv_meta_t *s_edge = s_meta + 3u * B * 64u;     // [0 .. B): left of lane 0, [B .. 2B): right of the last valid lane
   const int lane = epv_lane();
-  // GPOOL: rows of 64 interleaved records (row r of lane l at (r * 64 + l) * 2 doubles), then
-  // the flat heavy list; LDS: records packed by a wave prefix sum, the heavy list behind them
-  double *pool = GPOOL ? gpool + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave_id) *
-                                     ((size_t)pool_dbl * 128u + (size_t)list_cap * EPV_HREC)
-                       : s_wave + regA_dbl + mc_dbl;
+  // records packed by a wave prefix sum, the heavy list behind them
+  double *pool = s_wave + regA_dbl + mc_dbl;
   const uint64_t gfirst = S.g0 + first;
   const uint64_t s0 = first + ((colour + 3u - (uint32_t)(gfirst % 3u)) % 3u);
   // FUSED: F.lanes (64, 32 or 16) sites per wave -- fewer sites, hence fewer search rounds, per wave
@@ -326,21 +312,20 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     const uint32_t wantR = pending ? need_rec : 0u, wantH = pending ? heavy : 0u;
     const uint32_t inclR = wave_incl_scan_u32(wantR), inclH = wave_incl_scan_u32(wantH);
     // non-decreasing in the lane index, so the lanes that run are a prefix of the pending ones
-    const bool run = pending && (GPOOL ? (need_rec <= pool_dbl && inclH <= list_cap)
-                                       : (2u * inclR + HREC * inclH <= pool_dbl));
+    const bool run = pending && 2u * inclR + HREC * inclH <= pool_dbl;
     const unsigned long long rmask = __ballot(run);
     const int hi_lane = rmask ? 63 - __clzll((long long)rmask) : 0;
     const uint32_t totR = rmask ? epv_bcast(inclR, hi_lane) : 0u, totH = rmask ? epv_bcast(inclH, hi_lane) : 0u;
-    constexpr size_t RS = GPOOL ? 128u : 2u;   // doubles between consecutive records of a lane
-    double *my = GPOOL ? pool + (size_t)lane * 2u : pool + (size_t)(inclR - wantR) * 2u;
-    double *list = GPOOL ? pool + (size_t)pool_dbl * 128u : pool + (size_t)totR * 2u;
+    constexpr size_t RS = 2u;   // doubles between consecutive records of a lane
+    double *my = pool + (size_t)(inclR - wantR) * 2u;
+    double *list = pool + (size_t)totR * 2u;
     const uint32_t hbase = inclH - wantH;
 
     P2_MARK(1);
     // ---- 1. list the heavy segments: forward merge of the neighbours' jumps (Segment.cpp:35-79).
     //      The merges of different branches are independent, and a lane has a heavy branch at
     //      about every eighth (lane, node) pair of a short tree: walking the nodes with whichever
-    //      lanes are heavy there kept an eighth of the wave busy.  LDS pool: the heavy (lane, node)
+    //      lanes are heavy there kept an eighth of the wave busy.  So the heavy (lane, node)
     //      pairs are listed first (in the node table, which pruning fills only afterwards) and
     //      then merged one pair per LANE.
     auto merge_branch = [&](uint32_t owner, uint32_t node, uint32_t hcur, uint64_t jl, uint64_t jr) __attribute__((always_inline)) {
@@ -367,7 +352,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         }
       }
     };
-    if (!GPOOL && EPV_P2_DENSE_LIST && B > 1u) {      // (a single branch: every lane is its own pair)
+    if (B > 1u) {      // (a single branch: every lane is its own pair)
       // 1a. pair words lane | node << 6 | first record << 18 (an LDS pool holds fewer than 2^14 records)
       uint32_t n_pairs = 0u;
       if constexpr (SMALL) {
@@ -626,7 +611,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         hrec0 = hcur;
         if (K >= 2u) hcur += K;
         if (!FUSED && (K & 63u) && !clean) states[(K - 1u) >> 6] = word;   // only a dirty branch is read back
-#if EPV_FUSED_DENSE_EMIT
         // FUSED: proposal end state for the children (bit 31); "dirty" (bit 30) and the branch's first
         // heavy record (bits 14..27) for the emission pass behind this loop, which gives every dirty
         // (site, branch) pair its own lane; the sampled end states of a heavy branch wait in the
@@ -635,8 +619,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           regA[node * 64u + lane] = off | (prev << 31) | (clean ? 0u : 1u << 30) | (K >= 2u ? hrec0 << 14 : 0u);
           if (!clean && K >= 2u) list[(size_t)hrec0 * HREC + 6u] = epv_u2d(w64);
         } else
-#endif
-        regA[node * 64u + lane] = off | (prev << 31);  // proposal end state for the children
+          regA[node * 64u + lane] = off | (prev << 31);  // proposal end state for the children
         // the proposal's meta word (start state, no jumps yet; the fused phase's assembly adds the
         // count) takes the place of the current path's, which this lane has just read for the last
         // time: the acceptance stage finds it there.  (NOT in the node table: a later round of this
@@ -649,7 +632,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         trip_b = 4u * (mL >> EPV_INIT_SHIFT) + (mR >> EPV_INIT_SHIFT);
       }
       bool old_list = dirty_b;
-      if (SEG && !(FUSED && EPV_FUSED_DENSE_EMIT)) {
+      if (SEG && !FUSED) {
         // ---- dirty SEGMENTS onto the segment list (one lane each in epv_seg_search_kernel) and the
         //      branch onto the assemble list: one atomic per wave and node reserves both ranges.
         //      A branch with more than 64 segments, or one that finds the lists full, takes the
@@ -771,7 +754,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       if (am && lane == 0)
         atomicAdd(&counters[EPV_CNT_IDX(EPV_CNT_ACCEPT, shard)], (unsigned long long)__popcll(am));
     }
-#if EPV_FUSED_DENSE_EMIT
     if (FUSED) {
       // ---- 6. the dirty (site, branch) pairs of this round, ONE LANE EACH: their dirty segments
       //      onto the wave's segment list, the branch onto its assemble list.  (Doing this inside the
@@ -875,7 +857,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();     // the pool goes to the next round's records
     }
-#endif
     pending = pending && !run;
     P2_MARK(6);
   }
@@ -890,12 +871,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     // one writes back and invalidates the XCD's L2, ~30 us each here
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    // -DEPV_DBG_SKIP=1 / 2 / 3 leaves out the acceptance / + assembly / + search (instruction counts
-    // per stage: tools/inst_count.sh; the chain then never moves, nothing reads what is missing)
-#ifndef EPV_DBG_SKIP
-#define EPV_DBG_SKIP 0
-#endif
-    if (f_nseg && EPV_DBG_SKIP < 3) {
+    if (f_nseg) {
       EpvCoop W;
       W.len = pool; W.r0 = pool + 64; W.r1 = pool + 128; W.trunc = pool + 192; W.tj = pool + 256;
       uint32_t *u = reinterpret_cast<uint32_t *>(pool + 384);
@@ -911,7 +887,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
       P2_MARK(7);
-      for (uint32_t i = (uint32_t)lane; i < (EPV_DBG_SKIP < 2 ? f_nbt : 0u); i += 64u)
+      for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
         epv_seg_assemble_one(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
                              seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -931,7 +907,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       A.d = pool + 224 + lane; A.stride = 64u;
       A.j = reinterpret_cast<uint32_t *>(pool + 736) + lane;
       epv_meta_t *mc = reinterpret_cast<epv_meta_t *>(pool + 992) + lane;
-      const unsigned long long lmask = EPV_DBG_SKIP >= 1 ? 0ull : __ballot(f_listed);
+      const unsigned long long lmask = __ballot(f_listed);
       const uint32_t n_listed = (uint32_t)__popcll(lmask);
       const uint32_t my_rank = (uint32_t)__popcll(lmask & ((1ull << lane) - 1ull));
       // the owner publishes what its three task lanes need -- the five columns' buffers (known
@@ -959,19 +935,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           const uint64_t c = osite - 1u + (uint64_t)w;            // centre column of this triple
           // buffers of the three columns (bits 8.. of the owner's word: LL, L, proposal, R, RR)
           const uint32_t bl = (ow >> (8u + w)) & 1u, bm = (ow >> (9u + w)) & 1u, br = (ow >> (10u + w)) & 1u;
-#ifdef EPV_ACC_GLOBAL_META
-          if (F.meta_cache) {
-            const uint32_t B2 = B;
-#pragma unroll 4
-            for (uint32_t b = 0; b < B2; ++b) {
-              const epv_meta_t m0 = S.meta[meta_idx(S, bl, b, c - 1u)];
-              const epv_meta_t m1 = S.meta[meta_idx(S, bm, b, c)];
-              const epv_meta_t m2 = S.meta[meta_idx(S, br, b, c + 1u)];
-              mc[(0u * B2 + b) * 64u] = m0;
-              mc[(1u * B2 + b) * 64u] = m1;
-              mc[(2u * B2 + b) * 64u] = m2;
-            }
-#else
           if (F.meta_cache) {
             // the meta words of the triple's columns without a global round trip: the neighbours'
             // current paths were staged at the head of the kernel (they belong to other colours and
@@ -989,7 +952,6 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               mc[(1u * B2 + b) * 64u] = m1;
               mc[(2u * B2 + b) * 64u] = m2;
             }
-#endif
             v = triple_llh_cached<NN ? NN - 1 : 0>(S, s_const, s_blen, mc, 64u, 0u, bl, c - 1u, 1u, bm, c, 2u, br, c + 1u, A);
           } else {
             v = triple_llh(S, s_const, s_blen, bl, c - 1u, bm, c, br, c + 1u, A);
@@ -999,7 +961,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (f_listed && EPV_DBG_SKIP < 1) {
+      if (f_listed) {
         // the owner: Metropolis_Hastings_site :510-533 with the three values (the arithmetic of
         // epv_accept_site, term by term)
         double llr = (S.flags & EPV_FLAG_REFERENCE_PROPOSAL_RATIO) ? S.prop_llr[tid] : 0.0;

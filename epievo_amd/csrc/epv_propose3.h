@@ -1,7 +1,7 @@
 #ifndef EPV_PROPOSE3_H
 #define EPV_PROPOSE3_H
 // epv_propose3.h -- the proposal kernel of a colour phase for LARGE trees (included by
-// epv_kernels.h behind epv_propose2.h).  Same contract as epv_mh_propose2_kernel<true, false, false>
+// epv_kernels.h behind epv_propose2.h).  Same contract as epv_mh_propose2_kernel<false, false>
 // -- pruning (SingleSiteSampler.cpp:116-157) and downward sampling of the segment end states
 // (:180-255) of one site per lane, bit for bit the numbers of the oracle's parallel rung; dirty
 // (site, branch) pairs onto the bucketed lists of epv_mh_jumps_kernel, sites whose proposal differs

@@ -132,7 +132,7 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  * proposal kernel are 0.
  *   bits 0-1   proposal kernel: EPV_PLAN_V1 (epv_mh_propose_kernel), EPV_PLAN_V2 (epv_mh_propose2_kernel),
  *              EPV_PLAN_V3 (epv_mh_propose3_kernel), EPV_PLAN_FUSED (epv_mh_propose2_kernel, fused phase)
- *   bit  2     record pool in global memory (V1: its slab, V2: its slab; 0 = LDS)
+ *   bit  2     V1: the record pool in global memory (0 = LDS)
  *   bit  3     V1: the reference proposal-ratio template (EPV_OPT_REFERENCE_PROPOSAL_RATIO, EPV_OPT_SAMPLE_ROOT)
  *   bits 4-7   fused: the small-tree body's node count NN (2 .. 5), 0 = the generic body
  *   bits 8-9   V3: 64-bit words per node mask (1 for trees of at most 64 nodes, else 2)

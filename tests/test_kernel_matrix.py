@@ -2,10 +2,10 @@
 
 Each row names a tree, a genome length, the EPV_* knobs that steer the plan, the options (EPV_OPT_*) and
 the plan fields it expects (DeviceSampler.phase_plan, epv_phase_plan of include/epievo_mi355x.h).  The
-row runs in a fresh process (several knobs are read once per process): the plan is asserted after
-reset(), then run_mcmc is compared with the oracle's parallel rung B in the same mode -- J, D, the
-accept count, the paths and the cached triple likelihoods bit for bit.  Rows with the default options
-also run two sweeps at a capacity that overflows.
+row runs in a fresh process with its knobs in the environment (a context reads them when it is
+created): the plan is asserted after reset(), then run_mcmc is compared with the oracle's parallel
+rung B in the same mode -- J, D, the accept count, the paths and the cached triple likelihoods bit
+for bit.  Rows with the default options also run two sweeps at a capacity that overflows.
 
 Coverage (variant x options -> rows):
   fused small-tree body NN = 2 / 3 / 4 / 5    forward rejection: fr-pair, fr-cherry, fr-star3, fr-tree;
@@ -13,7 +13,6 @@ Coverage (variant x options -> rows):
   fused generic body                         forward rejection: fr-star5, fr-cat6; default: star5 (6 nodes)
   V2, LDS pool, jumps_all / jumps           forward rejection: fr-v2-lds
   V2, LDS pool, segment jumps                forward rejection: fr-v2-lds-seg
-  V2, global pool                            forward rejection: fr-v2-global, fr-v2-global-seg
   V3, one-word masks / two-word / slab pool  forward rejection: fr-bal16-v3, fr-bal64-v3, fr-bal16-v3-slab;
                                              default: n64, n65, n128, cat64, unary-q63
   V1, LDS pool                               forward rejection: fr-v1-lds; reference ratio, forward
@@ -196,10 +195,6 @@ ROWS = [
     ("fr-cat6", "cat6", 11, 1500, {"EPV_FUSED_PHASE": "1", "EPV_FORCE_LDS_POOL": "1"}, FR, fused(0)),
     ("fr-v2-lds", "tree", 5, 2000, dict(_SEP, EPV_SEG_JUMPS="0"), FR, v2(False, "jumps")),
     ("fr-v2-lds-seg", "tree", 5, 2000, dict(_SEP, EPV_SEG_JUMPS="1"), FR, v2(False, "segments")),
-    ("fr-v2-global", "tree", 5, 2000, dict(_SEP, EPV_FORCE_GLOBAL_POOL="1", EPV_PROPOSE_V2_GLOBAL="1",
-                                             EPV_PROPOSE_V3="0", EPV_SEG_JUMPS="0"), FR, v2(True, "jumps")),
-    ("fr-v2-global-seg", "tree", 5, 2000, dict(_SEP, EPV_FORCE_GLOBAL_POOL="1", EPV_PROPOSE_V2_GLOBAL="1",
-                                                 EPV_PROPOSE_V3="0", EPV_SEG_JUMPS="1"), FR, v2(True, "segments")),
     ("fr-bal16-v3", "bal16", 31, 600, dict(_SEP, EPV_PROPOSE_V3="1"), FR, v3(1, False, "jumps")),
     ("fr-bal64-v3", "bal64", 127, 400, dict(_SEP, EPV_PROPOSE_V3="1"), FR, v3(2, False, "jumps")),
     ("fr-bal16-v3-slab", "bal16", 31, 600, dict(_SEP, EPV_PROPOSE_V3="1", EPV_P3_SLAB_POOL="2"), FR,
@@ -249,7 +244,7 @@ def test_rows_cover_the_matrix():
     for key in [("fused", 2, False, "fused", None, None), ("fused", 3, False, "fused", None, None),
                 ("fused", 4, False, "fused", None, None), ("fused", 5, False, "fused", None, None),
                 ("fused", 0, False, "fused", None, None), ("V2", 0, False, "jumps", 0, None),
-                ("V2", 0, False, "segments", 0, None), ("V2", 0, True, "jumps", 0, None),
+                ("V2", 0, False, "segments", 0, None),
                 ("V3", None, False, "jumps", 1, False), ("V3", None, False, "jumps", 2, False),
                 ("V3", None, False, "jumps", 1, True), ("V1", None, False, "jumps", 0, None),
                 ("V1", None, True, "jumps", 0, None)]:

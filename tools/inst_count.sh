@@ -1,7 +1,6 @@
 #!/bin/bash
 # VALU wave-instructions per launch of the MH kernels for library variants (tools/ab_defs.py build):
 #   bash tools/inst_count.sh <tag> NAME ...     (one context, fused phase forced)
-# per stage of the fused phase: python tools/ab_defs.py build "s0=" "s1=-DEPV_DBG_SKIP=1" "s2=-DEPV_DBG_SKIP=2" "s3=-DEPV_DBG_SKIP=3"
 tag=$1; shift
 export TMPDIR=/tmp
 export EPV_FUSED_PHASE=1
