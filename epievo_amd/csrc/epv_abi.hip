@@ -80,17 +80,15 @@ struct epv_ctx {
   unsigned long long *h_counters = nullptr;  // pinned staging for the sharded counters
   unsigned long long *d_cnt_snap = nullptr;  // the counters as they stood when the batch sweeps began (stream-ordered copy:
   unsigned long long *h_cnt_snap = nullptr;  // the host does not wait for the burn-in to read the accept base)
-  double *d_partial[2] = {nullptr, nullptr};  // tree-reduction ping-pong
+  double *d_partial[2] = {nullptr, nullptr};  // per-block statistics, tree-reduction ping-pong
   uint64_t partial_cap[2] = {0, 0};   // doubles allocated in d_partial[0], [1]
   unsigned long long *d_sweep_tot = nullptr;  // [sweep][B*16] integer statistics of the batch sweeps
   uint64_t sweep_tot_cap = 0;                 // sweeps allocated
   double *d_statscale = nullptr;              // [N] 2^k_b of the fixed-point dwell times (epv_suffstat_kernel)
   std::vector<double> statscale;              // host copy; refreshed when the tree or the genome length changes
   double *d_scale = nullptr;
-  double *d_lvl = nullptr;      // level outputs of epv_reduce_blocks (all batch sweeps at once)
+  double *d_lvl = nullptr;      // level outputs of reduce_blocks_to_tot (all batch sweeps at once)
   uint64_t lvl_cap = 0;
-  double *d_rows = nullptr;     // compacted statistic rows of the whole genome (epv_reduce_gathered_rows)
-  uint64_t rows_cap = 0;
   uint8_t *d_stage = nullptr;   // packed-column staging for the halo exchange (grown on demand)
   uint64_t stage_cap = 0;
   hipEvent_t ev_copy[2] = {nullptr, nullptr};   // epv_copy_columns_async: "slot s of my staging buffer is packed"
@@ -573,15 +571,18 @@ int reduce_blocks_to_tot(epv_ctx *c, const void *d_blocks, uint64_t nb_total, ui
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
-// the integer totals of `batch` sweeps (d_sweep_tot[0 .. batch)) -> J, D as run_mcmc returns them
-// (SingleSiteSampler.cpp:576-594): every sweep's statistics become doubles -- J = the count,
-// D = the integer * 2^-k_b, exact but for the one rounding of int64 -> double -- and are added up
-// sweep by sweep in fp64 like J_all_sites += J_one_site, then divided by the batch size
-int finish_stats(epv_ctx *c, uint64_t batch, int average, double *J, double *D) {
-  const uint32_t V = c->S.B * 16u;
-  std::vector<long long> tot(batch * V);
-  HIP_TRY(c, hipMemcpyAsync(tot.data(), c->d_sweep_tot, batch * V * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+// the integer totals of `batch` sweeps (d_sweep_tot[0 .. batch)) -> tot[batch][B*16] on the host
+int read_sweep_tot(epv_ctx *c, uint64_t batch, int64_t *tot) {
+  HIP_TRY(c, hipMemcpyAsync(tot, c->d_sweep_tot, batch * c->S.B * 16u * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+// integer totals tot[batch][B*16] -> J, D as run_mcmc returns them (SingleSiteSampler.cpp:576-594):
+// every sweep's statistics become doubles -- J = the count, D = the integer * 2^-k_b, exact but for
+// the one rounding of int64 -> double -- and are added up sweep by sweep in fp64 like
+// J_all_sites += J_one_site, then divided by the batch size
+void counts_to_stats(const epv_ctx *c, const int64_t *tot, uint64_t batch, int average, double *J, double *D) {
+  const uint32_t V = c->S.B * 16u;
   const double nb = average ? (double)batch : 1.0;
   for (uint32_t b = 0; b < c->S.B; ++b) {
     const double inv = 1.0 / c->statscale[b + 1u];     // a power of two: exact
@@ -595,6 +596,12 @@ int finish_stats(epv_ctx *c, uint64_t batch, int average, double *J, double *D) 
       D[b * 8 + k] = ad / nb;
     }
   }
+}
+int finish_stats(epv_ctx *c, uint64_t batch, int average, double *J, double *D) {
+  std::vector<int64_t> tot(batch * c->S.B * 16u);
+  const int rc = read_sweep_tot(c, batch, tot.data());
+  if (rc) return rc;
+  counts_to_stats(c, tot.data(), batch, average, J, D);
   return EPV_OK;
 }
 
@@ -997,7 +1004,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   free_paths(c);
   dfree(c->d_model); dfree(c->d_parent); dfree(c->d_subtree); dfree(c->d_blen);
-  dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_rows); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
+  dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
@@ -1645,6 +1652,31 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
+// burn_in sweeps, then batch x {sweep; stat(w); path-average sample}: the chain of epv_run_mcmc_sums
+// and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
+// snapshot where the batch sweeps begin (finish_mcmc_snapshot)
+template <class Stat>
+static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base, Stat stat) {
+  int rc = ensure_pavg(c);
+  if (rc) return rc;
+  uint32_t sweep = sweep_base;
+  for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
+    for (int colour = 0; colour < 3; ++colour)
+      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
+    ++c->n_sweeps;
+  }
+  if ((rc = snapshot_counters(c))) return rc;
+  for (uint64_t w = 0; w < batch; ++w, ++sweep) {
+    for (int colour = 0; colour < 3; ++colour)
+      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
+    ++c->n_sweeps;
+    if ((rc = stat(w))) return rc;
+    if (c->pa_P && (rc = launch_pavg(c))) return rc;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return EPV_OK;
+}
+
 EPV_API int epv_run_mcmc_sums(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed,
                               uint32_t sweep_base, int average, double *J, double *D,
                               uint64_t *n_accepted) {
@@ -1652,32 +1684,59 @@ EPV_API int epv_run_mcmc_sums(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint
   if (rc) return rc;
   if (!J || !D || batch == 0) return fail(c, EPV_ERR_ARG, "bad run_mcmc arguments");
   HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_pavg(c))) return rc;
-  uint32_t sweep = sweep_base;
-  for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
-    for (int colour = 0; colour < 3; ++colour)
-      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
-    ++c->n_sweeps;
-  }
   if ((rc = ensure_sweep_tot(c, batch))) return rc;
-  if ((rc = ensure_partials(c))) return rc;      // (allocations synchronise: before the snapshot)
-  if ((rc = snapshot_counters(c))) return rc;
-  for (uint64_t w = 0; w < batch; ++w, ++sweep) {
-    for (int colour = 0; colour < 3; ++colour)
-      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
-    ++c->n_sweeps;
-    if ((rc = launch_suffstats(c, w))) return rc;
-    if (c->pa_P && (rc = launch_pavg(c))) return rc;
-  }
-  HIP_TRY(c, hipGetLastError());
+  if ((rc = ensure_partials(c))) return rc;      // (allocations synchronise: before the chain)
+  rc = run_chain(c, burn_in, batch, seed, sweep_base, [c](uint64_t w) { return launch_suffstats(c, w); });
+  if (rc) return rc;
   rc = finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
   const int src = finish_stats(c, batch, average, J, D);
   return rc ? rc : src;
 }
 
-// ---- several shards on ONE GPU (epievo_amd.parallel.LocalGroup): each shard writes the
-// level-0 block partials of its owned 256-site blocks, per batch sweep, into a buffer shared
-// by the group; one reduction afterwards gives exactly the sums of the unsharded run
+// ---- a context that shares its GPU with others (the sharded drivers).  Its statistics run as
+// one-wave blocks (they fit into the LDS the colour phases leave free); the waves of a 256-site block
+// add into its row of d_partial[0] ([w][owned block][16 B], zeroed first), and one reduction after the
+// last sweep leaves the per-sweep totals in d_sweep_tot
+EPV_API int epv_run_mcmc_counts(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base,
+                                int64_t *counts, uint64_t *n_accepted) {
+  int rc = check_ready(c, true);
+  if (rc) return rc;
+  if (!counts || batch == 0) return fail(c, EPV_ERR_ARG, "bad run_mcmc_counts arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t V = c->S.B * 16u;
+  uint64_t own_lo = 0, own_hi = 0;
+  owned_range(c, &own_lo, &own_hi);
+  const uint64_t blk_lo = own_lo / 256u, n_own = own_hi / 256u - blk_lo + 1u;
+  if ((rc = ensure_stat_scale(c))) return rc;
+  if ((rc = ensure_sweep_tot(c, batch))) return rc;
+  if ((rc = ensure_partials(c, batch * n_own))) return rc;
+  unsigned long long *rows = (unsigned long long *)c->d_partial[0];
+  HIP_TRY(c, hipMemsetAsync(rows, 0, batch * n_own * V * sizeof(unsigned long long), c->stream));
+  rc = run_chain(c, burn_in, batch, seed, sweep_base, [&](uint64_t w) {
+    hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
+                       dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows + w * n_own * V);
+    return EPV_OK;
+  });
+  if (rc) return rc;
+  if ((rc = reduce_blocks_to_tot(c, rows, n_own, batch, 0u))) return rc;
+  rc = finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
+  const int src = read_sweep_tot(c, batch, counts);
+  return rc ? rc : src;
+}
+
+EPV_API int epv_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64_t batch, int average, double *J, double *D) {
+  if (!c || !counts || !J || !D || !batch) return EPV_ERR_ARG;
+  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int rc = ensure_stat_scale(c);     // k_b depends on the genome length and the branch lengths
+  if (rc) return rc;
+  counts_to_stats(c, counts, batch, average, J, D);
+  return EPV_OK;
+}
+
+// device buffers on the context's GPU for the sharded drivers: the halo columns and the all-gather
+// pieces they hand to RCCL, and small host <-> device copies into and out of them (e.g. the
+// statistics piece with its tail, so that ONE all-gather carries everything)
 EPV_API int epv_dev_alloc(epv_ctx *c, uint64_t bytes, void **p) {
   if (!c || !p || !bytes) return EPV_ERR_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1686,8 +1745,6 @@ EPV_API int epv_dev_alloc(epv_ctx *c, uint64_t bytes, void **p) {
   HIP_TRY(c, hipDeviceSynchronize());   // the contexts' streams do not wait for the null stream
   return EPV_OK;
 }
-// small host <-> device copies into / out of such buffers (e.g. the accept count a shard appends
-// to its statistic rows so that ONE all-gather carries everything)
 EPV_API int epv_dev_write(epv_ctx *c, void *d_dst, const void *src, uint64_t bytes) {
   if (!c || !d_dst || !src) return EPV_ERR_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1705,130 +1762,6 @@ EPV_API int epv_dev_free(epv_ctx *c, void *p) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (p) HIP_TRY(c, hipFree(p));
   return EPV_OK;
-}
-
-EPV_API int epv_run_mcmc_blocks(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed,
-                                uint32_t sweep_base, double *d_blocks, uint64_t nb_total,
-                                int64_t block_offset, uint64_t *n_accepted) {
-  int rc = check_ready(c, true);
-  if (rc) return rc;
-  if (!d_blocks || batch == 0) return fail(c, EPV_ERR_ARG, "bad run_mcmc_blocks arguments");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t V = c->S.B * 16u;
-  uint64_t own_lo = 0, own_hi = 0;
-  owned_range(c, &own_lo, &own_hi);
-  const uint64_t blk_lo = own_lo / 256u, blk_hi = own_hi / 256u;
-  // local block 0 may lie left of the buffer (a halo in front of the owned columns); the OWNED blocks must be inside
-  if (block_offset + (int64_t)blk_lo < 0 || block_offset + (int64_t)blk_hi >= (int64_t)nb_total)
-    return fail(c, EPV_ERR_ARG, "owned blocks exceed the group's block buffer");
-  if ((c->S.g0 & 255u) != 0u) return fail(c, EPV_ERR_ARG, "the shard must start on a 256-site block of the genome");
-  if ((rc = ensure_stat_scale(c))) return rc;
-  if ((rc = ensure_pavg(c))) return rc;
-  uint32_t sweep = sweep_base;
-  for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
-    for (int colour = 0; colour < 3; ++colour)
-      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
-    ++c->n_sweeps;
-  }
-  if ((rc = snapshot_counters(c))) return rc;
-  // the statistics of a context that shares its GPU with others run as one-wave blocks (they fit
-  // into the LDS the colour phases leave free); the waves of a 256-site block add into its row, so
-  // this context's rows start from zero
-  unsigned long long *rows0 = (unsigned long long *)d_blocks + (uint64_t)(block_offset + (int64_t)blk_lo) * V;
-  const uint64_t n_own = blk_hi - blk_lo + 1u;
-  HIP_TRY(c, hipMemset2DAsync(rows0, nb_total * V * sizeof(unsigned long long), 0, n_own * V * sizeof(unsigned long long),
-                              batch, c->stream));
-  for (uint64_t w = 0; w < batch; ++w, ++sweep) {
-    for (int colour = 0; colour < 3; ++colour)
-      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
-    ++c->n_sweeps;
-    hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
-                       dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows0 + w * nb_total * V);
-    if (c->pa_P && (rc = launch_pavg(c))) return rc;
-  }
-  HIP_TRY(c, hipGetLastError());
-  return finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
-}
-
-EPV_API int epv_reduce_blocks(epv_ctx *c, const double *d_blocks, uint64_t nb_total, uint64_t batch,
-                              int average, double *J, double *D) {
-  if (!c || !d_blocks || !J || !D || !nb_total || !batch) return EPV_ERR_ARG;
-  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int rc = ensure_stat_scale(c);
-  if (rc) return rc;
-  if ((rc = reduce_blocks_to_tot(c, d_blocks, nb_total, batch, 0u))) return rc;
-  return finish_stats(c, batch, average, J, D);
-}
-
-// ---- statistics of a genome sharded over several GPUs: every GPU turns the level-0 partials
-// of its blocks into ROWS of row_blocks (a power of two) blocks, the rows of all GPUs are
-// all-gathered (RCCL; the caller's business), and the last stage sums the rows of the whole
-// genome -- the same balanced tree as the one-context reduction, so J and D keep their bits
-EPV_API int epv_blocks_to_rows(epv_ctx *c, const double *d_blocks, uint64_t nb_total, uint64_t batch,
-                               uint32_t row_blocks, double *d_rows) {
-  if (!c || !d_blocks || !d_rows || !nb_total || !batch) return EPV_ERR_ARG;
-  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  if (row_blocks == 0 || (row_blocks & (row_blocks - 1u))) return fail(c, EPV_ERR_ARG, "row_blocks must be a power of two");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t V = c->S.B * 16u;
-  const uint64_t n_rows = (nb_total + row_blocks - 1u) / row_blocks;
-  if (n_rows > 65535u || batch > 65535u) return fail(c, EPV_ERR_ARG, "too many rows or batch sweeps for one launch");
-  // in: [w][block][V]   out: [row][w][V] (a GPU's rows are one contiguous piece of the gathered buffer)
-  launch_isum(c, d_blocks, nb_total, (uint64_t)row_blocks, (uint64_t)V, nb_total * V, d_rows, batch * V, (uint64_t)V,
-              n_rows, batch);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
-
-EPV_API int epv_reduce_rows(epv_ctx *c, const double *d_rows, uint64_t n_rows, uint64_t batch, int average,
-                            double *J, double *D) {
-  if (!c || !d_rows || !J || !D || !n_rows || !batch) return EPV_ERR_ARG;
-  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  if (batch > 65535u) return fail(c, EPV_ERR_ARG, "too many batch sweeps for one launch");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint32_t V = c->S.B * 16u;
-  int rc = ensure_stat_scale(c);
-  if (rc) return rc;
-  if ((rc = ensure_sweep_tot(c, batch))) return rc;
-  // per batch sweep the integer total over all rows ([row][sweep][V]), then the host's accumulation
-  launch_isum(c, d_rows, n_rows, 0u, batch * V, (uint64_t)V, c->d_sweep_tot, 0u, (uint64_t)V, 1u, batch);
-  HIP_TRY(c, hipGetLastError());
-  return finish_stats(c, batch, average, J, D);
-}
-
-// the same on the buffer an all-gather of equally sized pieces leaves behind:
-// d_gathered[rank][max_rows][batch][V], of which the first rows_per_rank[rank] rows count
-EPV_API int epv_reduce_gathered_rows(epv_ctx *c, const double *d_gathered, uint32_t world, uint64_t max_rows,
-                                     uint64_t piece_doubles, const uint64_t *rows_per_rank, uint64_t batch,
-                                     int average, double *J, double *D) {
-  if (!c || !d_gathered || !world || !max_rows || !rows_per_rank || !batch) return EPV_ERR_ARG;
-  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t V = (uint64_t)c->S.B * 16u, row = batch * V;
-  if (piece_doubles == 0) piece_doubles = max_rows * row;
-  if (piece_doubles < max_rows * row) return fail(c, EPV_ERR_ARG, "piece_doubles smaller than max_rows rows");
-  uint64_t total = 0;
-  for (uint32_t r = 0; r < world; ++r) {
-    if (rows_per_rank[r] > max_rows) return fail(c, EPV_ERR_ARG, "rows_per_rank exceeds max_rows");
-    total += rows_per_rank[r];
-  }
-  if (!total) return fail(c, EPV_ERR_ARG, "no rows");
-  if (total * row > c->rows_cap) {
-    dfree(c->d_rows);
-    c->rows_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_rows, total * row * sizeof(double)));
-    c->rows_cap = total * row;
-  }
-  uint64_t at = 0;
-  for (uint32_t r = 0; r < world; ++r) {
-    if (rows_per_rank[r])
-      HIP_TRY(c, hipMemcpyAsync(c->d_rows + at * row, d_gathered + (uint64_t)r * piece_doubles,
-                                rows_per_rank[r] * row * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    at += rows_per_rank[r];
-  }
-  return epv_reduce_rows(c, c->d_rows, total, batch, average, J, D);
 }
 
 EPV_API int epv_run_mcmc(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed,

@@ -1735,8 +1735,8 @@ __global__ __launch_bounds__(64) void epv_suffstat_wave_kernel(EpvDev S, uint64_
 // Sums of rows of 64-bit integers: out(r, z, c) = the sum of the G consecutive input rows
 // r*G .. r*G+G-1 (rows >= m do not exist; G = 0: all m rows) of column c in slice z.  A block takes 16
 // columns and walks the rows 16 at a time (a wave reads four 128-byte pieces per load).  Integer sums
-// need no fixed order: any chain of such stages (256-site blocks -> rows of 2^g blocks -> all-gather
-// over the GPUs -> total) gives the same bits.
+// need no fixed order: any chain of such stages (256-site blocks -> groups of blocks -> total) gives
+// the same bits.
 __global__ __launch_bounds__(256) void epv_isum_kernel(const unsigned long long *in, uint64_t m, uint32_t V, uint64_t G,
                                                        uint64_t in_row_stride, uint64_t in_z_stride,
                                                        unsigned long long *out, uint64_t out_row_stride,
@@ -1772,7 +1772,7 @@ __global__ __launch_bounds__(256) void epv_tree_reduce_kernel(const double *in, 
                                                               uint64_t in_stride = 0, uint64_t out_stride = 0) {
   __shared__ double s_part[4][16];
   in += (uint64_t)blockIdx.z * in_stride;     // blockIdx.z: one of several independent reductions
-  out += (uint64_t)blockIdx.z * out_stride;   // (the batch sweeps of epv_reduce_blocks)
+  out += (uint64_t)blockIdx.z * out_stride;
   const int lane = epv_lane();
   const uint32_t wave = threadIdx.x >> 6;
   const uint64_t idx_in = (uint64_t)blockIdx.x * 256u + threadIdx.x;

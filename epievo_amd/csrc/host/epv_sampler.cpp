@@ -14,7 +14,7 @@
 namespace epv {
 
 namespace {
-const uint64_t kBlock = 256;   // sites per level-0 block of the statistics tree
+const uint64_t kBlock = 256;   // sites per block: the unit of part cuts and halo widths
 const uint32_t kMaxCap = 2047;   // EPV_MAX_CAP: 2 C + 1 segments must fit the 12-bit segment field of the Philox address
 
 // worker threads that are joined on every exit path: if starting thread i + 1 throws
@@ -198,10 +198,9 @@ uint32_t SingleSiteSampler::phase_mode() {
 void SingleSiteSampler::free_stat_buffers() {
   for (Slot &s : slots_) {
     epv_ctx *c = parts_[s.part0].ctx;
-    if (s.d_blocks) epv_dev_free(c, s.d_blocks);
-    if (s.d_rows) epv_dev_free(c, s.d_rows);
+    if (s.d_piece) epv_dev_free(c, s.d_piece);
     if (s.d_gather) epv_dev_free(c, s.d_gather);
-    s.d_blocks = s.d_rows = s.d_gather = nullptr;
+    s.d_piece = s.d_gather = nullptr;
   }
   stat_batch_ = 0;
 }
@@ -230,9 +229,7 @@ std::string SingleSiteSampler::layout() const {
   if (rank_mode_) o << " (this process: slot " << rank_.rank << ")";
   o << " x up to " << contexts_per_gpu() << " context(s) = " << parts_.size() << " parts"
     << (rank_mode_ ? " here" : "") << ", halo " << halo_ << " columns";
-  if (slots_[0].comm)
-    o << ", statistics rows of " << kBlock * row_blocks_ << " sites, exchange over "
-      << (uses_rccl() ? "RCCL" : "the loopback transport");
+  if (slots_[0].comm) o << ", exchange over " << (uses_rccl() ? "RCCL" : "the loopback transport");
   o << "; devices";
   for (const Slot &s : slots_) o << " " << s.device;
   return o.str();
@@ -417,7 +414,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
   drop_parts();
   const uint64_t H = halo_for(burn_in, batch);
   const uint64_t min_part = 2 * H + 2 * kBlock;
-  // slots: as many of the requested GPUs as the genome can feed, cut on whole statistics rows
+  // slots: as many of the requested GPUs as the genome can feed, cut on multiples of 256 * row_blocks_ sites
   const std::vector<uint64_t> cut = shard_cuts(n, rank_mode ? world_ : devices_.size(), burn_in, batch, row_blocks_);
   const size_t G = cut.size() - 1;
   if (rank_mode && G != world_)
@@ -471,14 +468,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
     sl.gidx = g;
     sl.first = cut[g];
     sl.last = cut[g + 1];
-    sl.n_blocks = (cut[g + 1] - cut[g] + kBlock - 1) / kBlock;
-    sl.n_rows = (sl.n_blocks + row_blocks_ - 1) / row_blocks_;
   }
-  max_rows_ = 0;   // the same on every process: all slots of the run
-  for (size_t g = 0; g < G; ++g)
-    max_rows_ = std::max<uint64_t>(max_rows_, ((cut[g + 1] - cut[g] + kBlock - 1) / kBlock + row_blocks_ - 1) / row_blocks_);
-  rows_of_slot_.assign(G, 0);
-  for (size_t g = 0; g < G; ++g) rows_of_slot_[g] = ((cut[g + 1] - cut[g] + kBlock - 1) / kBlock + row_blocks_ - 1) / row_blocks_;
   const size_t P = pieces.size();
   for (size_t p = 0; p < P; ++p) {
     Part q;
@@ -554,21 +544,18 @@ void SingleSiteSampler::reset(const Model &m) {
   for (Part &p : parts_) check_on(p.ctx, epv_reset_async(p.ctx), "epv_reset_async");
 }
 
-// words appended to a slot's rows in the all-gather: its accept count
-static const uint64_t kTail = 8;
+// a slot's piece of the statistics all-gather: its counts [batch][16 B], then this tail
+// {accepted proposals, widest jump capacity of its contexts}
+static const uint64_t kTail = 2;
 
 void SingleSiteSampler::ensure_stat_buffers() {
-  if (stat_batch_ >= batch && slots_[0].d_blocks) return;
+  if (!slots_[0].comm || (stat_batch_ == batch && slots_[0].d_piece)) return;
   free_stat_buffers();
-  const uint64_t V = ((uint64_t)n_nodes_ - 1) * 16;
+  const uint64_t bytes = (batch * ((uint64_t)n_nodes_ - 1) * 16 + kTail) * sizeof(int64_t);
   for (Slot &s : slots_) {
     epv_ctx *c = parts_[s.part0].ctx;
-    check_on(c, epv_dev_alloc(c, batch * s.n_blocks * V * sizeof(double), &s.d_blocks), "epv_dev_alloc");
-    if (s.comm) {
-      const uint64_t piece = max_rows_ * batch * V + kTail;
-      check_on(c, epv_dev_alloc(c, piece * sizeof(double), &s.d_rows), "epv_dev_alloc");
-      check_on(c, epv_dev_alloc(c, world_ * piece * sizeof(double), &s.d_gather), "epv_dev_alloc");
-    }
+    check_on(c, epv_dev_alloc(c, bytes, &s.d_piece), "epv_dev_alloc");
+    check_on(c, epv_dev_alloc(c, world_ * bytes, &s.d_gather), "epv_dev_alloc");
   }
   stat_batch_ = batch;
 }
@@ -588,15 +575,14 @@ void SingleSiteSampler::run_mcmc(uint64_t seed, uint64_t em_iteration,
     // one host thread per part: their colour phases run concurrently, each GPU on its own,
     // the contexts of one GPU on their own streams
     const size_t P = parts_.size();
+    const uint64_t words = batch * B * 16, piece = words + kTail;
     std::vector<int> rcs(P, EPV_OK);
     std::vector<uint64_t> acc(P, 0);
+    std::vector<std::vector<int64_t>> counts(P, std::vector<int64_t>(words));
     ThreadGroup th;
     for (size_t p = 0; p < P; ++p)
       th.spawn([&, p] {
-        const Part &q = parts_[p];
-        const Slot &s = slots_[q.slot];
-        rcs[p] = epv_run_mcmc_blocks(q.ctx, burn_in, batch, seed, base, static_cast<double *>(s.d_blocks),
-                                     s.n_blocks, ((int64_t)q.lo - (int64_t)s.first) / (int64_t)kBlock, &acc[p]);
+        rcs[p] = epv_run_mcmc_counts(parts_[p].ctx, burn_in, batch, seed, base, counts[p].data(), &acc[p]);
       });
     th.join();
     for (size_t p = 0; p < P; ++p) {
@@ -604,61 +590,57 @@ void SingleSiteSampler::run_mcmc(uint64_t seed, uint64_t em_iteration,
       if (rcs[p] == EPV_ERR_CAPACITY) {   // absorbed as in check_mcmc; refresh_parts() evens the widths out
         uint32_t cap = 0;
         if (epv_get_capacity(c, &cap) == EPV_OK && cap < kMaxCap) {
-          capacity_events.push_back(std::string("epv_run_mcmc_blocks: ") + epv_last_error(c));
+          capacity_events.push_back(std::string("epv_run_mcmc_counts: ") + epv_last_error(c));
           check_on(c, epv_set_capacity(c, std::min(kMaxCap, cap * 2u)), "epv_set_capacity");
           rcs[p] = EPV_OK;
         }
       }
-      check_on(c, rcs[p], "epv_run_mcmc_blocks");
-      n_acc += acc[p];
+      check_on(c, rcs[p], "epv_run_mcmc_counts");
     }
-    if (!slots_[0].comm) {
-      const Slot &s = slots_[0];
-      check(epv_reduce_blocks(ctx_, static_cast<const double *>(s.d_blocks), s.n_blocks, batch, 1, Jf.data(), Df.data()),
-            "epv_reduce_blocks");
-    } else {
-      // the one collective of an EM iteration: every GPU's rows of integer statistics, its accept
-      // count riding in the tail of its piece
-      const uint64_t row_words = batch * B * 16, piece = max_rows_ * row_words + kTail;
-      for (Slot &s : slots_) {
-        epv_ctx *c = parts_[s.part0].ctx;
-        check_on(c, epv_blocks_to_rows(c, static_cast<const double *>(s.d_blocks), s.n_blocks, batch, row_blocks_,
-                                       static_cast<double *>(s.d_rows)), "epv_blocks_to_rows");
-        // the tail of the piece: the slot's accept count, and the jump capacity of its contexts
-        // (a slot that absorbed an overflow widened its slots: every slot of the run must follow
-        // before the next halo exchange, whose column size depends on it)
-        uint64_t tail[2] = {0, 0};
-        for (size_t p = s.part0; p < s.part1; ++p) {
-          tail[0] += acc[p];
-          uint32_t cap = 0;
-          check_on(parts_[p].ctx, epv_get_capacity(parts_[p].ctx, &cap), "epv_get_capacity");
-          tail[1] = std::max<uint64_t>(tail[1], cap);
-        }
-        check_on(c, epv_dev_write(c, static_cast<double *>(s.d_rows) + max_rows_ * row_words, tail, sizeof tail),
+    // the piece of every slot that lives here: its parts' counts added as integers, and the tail
+    // (a slot that absorbed an overflow widened its slots: every slot of the run must follow
+    // before the next halo exchange, whose column size depends on it)
+    std::vector<int64_t> pieces(slots_.size() * piece, 0);
+    for (size_t i = 0; i < slots_.size(); ++i) {
+      int64_t *mine = pieces.data() + i * piece;
+      for (size_t p = slots_[i].part0; p < slots_[i].part1; ++p) {
+        for (uint64_t k = 0; k < words; ++k) mine[k] += counts[p][k];
+        mine[words] += (int64_t)acc[p];
+        uint32_t cap = 0;
+        check_on(parts_[p].ctx, epv_get_capacity(parts_[p].ctx, &cap), "epv_get_capacity");
+        mine[words + 1] = std::max<int64_t>(mine[words + 1], cap);
+      }
+    }
+    if (slots_[0].comm) {
+      // the one collective of an EM iteration: every slot's piece to every slot
+      for (size_t i = 0; i < slots_.size(); ++i) {
+        epv_ctx *c = parts_[slots_[i].part0].ctx;
+        check_on(c, epv_dev_write(c, slots_[i].d_piece, pieces.data() + i * piece, piece * sizeof(int64_t)),
                  "epv_dev_write");
       }
       if (epv_comm_group_start() != EPV_OK) throw std::runtime_error("epv_comm_group_start failed");
       for (Slot &s : slots_)
-        check_comm(s.comm, epv_comm_all_gather(s.comm, s.d_rows, s.d_gather, piece * sizeof(double)), "epv_comm_all_gather");
+        check_comm(s.comm, epv_comm_all_gather(s.comm, s.d_piece, s.d_gather, piece * sizeof(int64_t)),
+                   "epv_comm_all_gather");
       if (epv_comm_group_end() != EPV_OK) throw std::runtime_error("epv_comm_group_end failed (statistics all-gather)");
       for (Slot &s : slots_) check_comm(s.comm, epv_comm_sync(s.comm), "epv_comm_sync");
-      // every GPU now holds the same rows; the host M-step needs one copy of the totals
-      check(epv_reduce_gathered_rows(ctx_, static_cast<const double *>(slots_[0].d_gather), (uint32_t)world_, max_rows_, piece,
-                                     rows_of_slot_.data(), batch, 1, Jf.data(), Df.data()), "epv_reduce_gathered_rows");
-      n_acc = 0;
-      uint64_t cap_all = 0;
-      for (size_t g = 0; g < world_; ++g) {
-        uint64_t v[2] = {0, 0};
-        check(epv_dev_read(ctx_, v, static_cast<const double *>(slots_[0].d_gather) + g * piece + max_rows_ * row_words, sizeof v),
-              "epv_dev_read");
-        n_acc += v[0];
-        cap_all = std::max(cap_all, v[1]);
-      }
-      for (Part &q : parts_) {     // (slots in other processes may have grown)
-        uint32_t cap = 0;
-        check_on(q.ctx, epv_get_capacity(q.ctx, &cap), "epv_get_capacity");
-        if (cap < cap_all) check_on(q.ctx, epv_set_capacity(q.ctx, (uint32_t)cap_all), "epv_set_capacity");
-      }
+      // every GPU now holds the pieces of all slots; the host M-step needs one copy
+      pieces.assign(world_ * piece, 0);
+      check(epv_dev_read(ctx_, pieces.data(), slots_[0].d_gather, pieces.size() * sizeof(int64_t)), "epv_dev_read");
+    }
+    std::vector<int64_t> total(words, 0);
+    int64_t cap_all = 0;
+    for (size_t g = 0; g * piece < pieces.size(); ++g) {
+      const int64_t *pc = pieces.data() + g * piece;
+      for (uint64_t k = 0; k < words; ++k) total[k] += pc[k];
+      n_acc += (uint64_t)pc[words];
+      cap_all = std::max(cap_all, pc[words + 1]);
+    }
+    check(epv_counts_to_stats(ctx_, total.data(), batch, 1, Jf.data(), Df.data()), "epv_counts_to_stats");
+    for (Part &q : parts_) {     // (slots in other processes may have grown)
+      uint32_t cap = 0;
+      check_on(q.ctx, epv_get_capacity(q.ctx, &cap), "epv_get_capacity");
+      if (cap < cap_all) check_on(q.ctx, epv_set_capacity(q.ctx, (uint32_t)cap_all), "epv_set_capacity");
     }
   }
   J.assign(n_nodes_, {});

@@ -18,13 +18,12 @@
 // blocks plus redundant halo columns wide enough for a whole run_mcmc; the RNG and the colouring
 // are keyed by the global site index, so the parts need no communication inside the E-step.
 // Per EM iteration the slots exchange, device to device through RCCL,
-//   (1) the edge columns of neighbouring parts before reset()   (epv_comm_exchange), and
-//   (2) their rows of the J/D reduction tree after run_mcmc()   (epv_comm_all_gather);
-// slots are cut on whole rows, every stage sums aligned subtrees of ONE balanced binary tree
-// over the site index, and so paths, J, D and the acceptance rate are bit-identical to the
-// one-context run for any G and k.  A device list with repeats
-// (EPV_DEVICES=0,0,0,0) rehearses an N-GPU run on a smaller box through the loopback transport
-// of the exchange layer.
+//   (1) the edge columns of neighbouring parts before reset()          (epv_comm_exchange), and
+//   (2) their integer J/D totals per batch sweep after run_mcmc()      (epv_comm_all_gather);
+// integer sums do not depend on how they are grouped, so paths, J, D and the acceptance rate are
+// bit-identical to the one-context run for any G and k.  A device list with
+// repeats (EPV_DEVICES=0,0,0,0) rehearses an N-GPU run on a smaller box through the loopback
+// transport of the exchange layer.
 //
 // Two ways to place the GPU slots (include/epievo_mi355x_comm.h):
 //   * every slot in THIS process (the CLIs, `bench.py --gpus N` called plainly): the constructor's
@@ -67,9 +66,9 @@ public:
   SingleSiteSampler(size_t n_burn_in, size_t n_batch, int device = 0, uint32_t capacity = 0);
   SingleSiteSampler(size_t n_burn_in, size_t n_batch, const std::vector<int> &devices, uint32_t capacity = 0);
   SingleSiteSampler(size_t n_burn_in, size_t n_batch, const RankSpec &rank, uint32_t capacity = 0);
-  // cut points of `world` contiguous slots of an n-site genome (whole statistics rows of
-  // 256 * row_blocks sites; every slot must be able to hold its halos): world + 1 entries, or fewer
-  // when the genome cannot feed that many slots
+  // cut points of `world` contiguous slots of an n-site genome (multiples of 256 * row_blocks
+  // sites; every slot must be able to hold its halos): world + 1 entries, or fewer when the genome
+  // cannot feed that many slots
   static std::vector<uint64_t> shard_cuts(uint64_t n_sites, size_t world, size_t n_burn_in, size_t n_batch,
                                           uint32_t row_blocks = 64);
   ~SingleSiteSampler();
@@ -155,10 +154,8 @@ private:
     epv_comm *comm = nullptr;
     uint64_t first = 0, last = 0;        // owned columns [first, last) of the genome
     size_t part0 = 0, part1 = 0;         // its parts [part0, part1)
-    uint64_t n_blocks = 0, n_rows = 0;
-    void *d_blocks = nullptr;            // [batch][n_blocks][V] level-0 partials of the slot
-    void *d_rows = nullptr;              // [max_rows][batch][V] rows of the slot (zero padded)
-    void *d_gather = nullptr;            // [slots][max_rows][batch][V]
+    void *d_piece = nullptr;             // its piece of the statistics all-gather (kTail of epv_sampler.cpp)
+    void *d_gather = nullptr;            // [slots] pieces
     void *d_halo[4] = {nullptr, nullptr, nullptr, nullptr};  // send prev, recv prev, send next, recv next
     uint64_t halo_bytes = 0;
   };
@@ -178,13 +175,12 @@ private:
   epv_ctx *ctx_;              // the context of the unsharded paths (== parts_[0].ctx when sharded)
   std::vector<int> devices_;
   int contexts_wanted_ = 0;      // contexts per GPU; 0 = by tree size (3 up to 8 branches: fused colour phase; else 2)
-  uint32_t row_blocks_ = 64;  // 256-site blocks per row of the cross-GPU statistics stage
+  uint32_t row_blocks_ = 64;  // GPU slots are cut on multiples of 256 * row_blocks_ sites (EPV_ROW_BLOCKS)
   bool force_comm_ = false;   // EPV_FORCE_COMM=1: the exchange layer even for one slot (tests)
   std::vector<Part> parts_;
   std::vector<Slot> slots_;
   uint64_t halo_ = 0;         // halo columns at every inner edge (multiple of 256)
-  uint64_t max_rows_ = 0, stat_batch_ = 0;
-  std::vector<uint64_t> rows_of_slot_;   // statistics rows of every slot of the run
+  uint64_t stat_batch_ = 0;   // batch the statistics pieces are sized for
   uint32_t capacity_;
   uint32_t pa_points_ = 0;    // set_path_average
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)

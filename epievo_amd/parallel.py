@@ -4,7 +4,7 @@ bench.py, the multi-process tests); the C++ EM driver shards inside one process 
 primitives and the same layout rules.
 
 Contiguous shards of the genome with WIDE halos that are updated redundantly, refreshed once
-per run_mcmc, and ONE all-gather of the per-branch J/D rows (+ accept count) per run_mcmc.
+per run_mcmc, and ONE all-gather of the per-branch J/D totals (+ accept count) per run_mcmc.
 
 Why it is correct: one MH update of site i reads the paths of sites
 i-2..i+2 and the cached triple log-likelihoods tri[i-1], tri[i+1]; it writes path i and
@@ -17,12 +17,12 @@ run_mcmc needs NO communication inside it: the halos are refreshed once before
 reset(), and the statistics are combined once after it -- instead of 3 exchanges per
 sweep.  The redundant work is 2H/n of a shard (0.1 % at n = 1e6, -L 10 -B 50).
 
-Statistics.  Shards are cut on multiples of ROW = 256 * row_blocks sites.  Every rank reduces
-its 256-site block partials to rows of ROW sites on its GPU, the rows of all ranks are
-all-gathered (device buffers handed to RCCL as they are), and every rank sums all rows of
-the genome.  Each stage adds aligned subtrees of ONE balanced binary tree over the global
-site index, so a sharded run reproduces the unsharded one bit-for-bit on paths, states, J
-AND D, for any number of ranks.
+Statistics.  J and D are exact 64-bit integers until the very end: J counts, every dwell time
+of branch b is rint(dt * 2^k_b).  Every rank's run_mcmc returns the integer totals of its owned
+sites per batch sweep; the ranks all-gather them in one fixed-size piece (with the accept count
+in its tail), and every rank adds all pieces as integers and turns the sum into J, D once.
+Integer sums do not depend on how they are grouped, so a sharded run reproduces the unsharded
+one bit-for-bit on paths, states, J AND D, for any number of ranks and any cut points.
 
 The reference has no parallelism at all (single-threaded); this
 module is new capability, not a translation.
@@ -31,8 +31,8 @@ import numpy as np
 
 from .host import FlatPaths
 
-BLOCK = 256      # sites per level-0 block of the statistics tree
-TAIL = 8         # doubles appended to a rank's rows in the all-gather (accept count)
+BLOCK = 256      # sites per block: halo widths and shard_cuts' cut points are whole blocks
+TAIL = 1         # int64 words after a rank's counts in the all-gather: its accept count
 
 
 def halo_width(sweeps_per_refresh):
@@ -41,11 +41,11 @@ def halo_width(sweeps_per_refresh):
 
 
 def shard_cuts(n_global, world, row_blocks=64):
-    """cut points of `world` near-equal contiguous shards on whole statistics rows"""
+    """cut points of `world` near-equal contiguous shards on multiples of 256 * row_blocks sites"""
     row = BLOCK * row_blocks
     cuts = [0] + [int(r * n_global / float(world) / row + 0.5) * row for r in range(1, world)] + [n_global]
     if any(b <= a for a, b in zip(cuts[:-1], cuts[1:])):
-        raise ValueError("a genome of %d sites is too short for %d shards on %d-site rows" % (n_global, world, row))
+        raise ValueError("a genome of %d sites is too short for %d shards cut on %d sites" % (n_global, world, row))
     return cuts
 
 
@@ -82,7 +82,7 @@ class TorchComm:
     """torch.distributed (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU
     tests).  The buffers are the device's own (DevBuf: device memory seen by torch through the
     CUDA array interface; the CPU double hands out numpy arrays), so nothing is staged: RCCL
-    reads the packed columns and the statistic rows where the kernels wrote them."""
+    reads the packed columns where the kernels wrote them."""
 
     def __init__(self, dist, device=None):
         import torch
@@ -166,21 +166,18 @@ class ShardedSampler:
         return self.n_own - (1 if self.comm.rank == 0 else 0) - \
             (1 if self.comm.rank == self.comm.world - 1 else 0)
 
-    def setup(self, model, tree, fp_own, cuts, capacity=16, sweeps_per_refresh=60, row_blocks=64):
+    def setup(self, model, tree, fp_own, cuts, capacity=16, sweeps_per_refresh=60):
         """fp_own: this rank's owned columns, sites [cuts[rank], cuts[rank+1]) of the genome
-        (cuts from shard_cuts: whole statistics rows).  The halo is sized for
-        `sweeps_per_refresh` sweeps between refreshes."""
+        (cuts as shard_cuts makes them, or any others whose shards hold their halos).  The halo
+        is sized for `sweeps_per_refresh` sweeps between refreshes."""
         c = self.comm
         cuts = [int(x) for x in cuts]
         if len(cuts) != c.world + 1 or cuts[0] != 0:
             raise ValueError("cuts must list world + 1 cut points starting at 0")
-        row = BLOCK * row_blocks
-        if any(x % row for x in cuts[1:-1]):
-            raise ValueError("inner cut points must be multiples of %d sites" % row)
         n_own, n_global = cuts[c.rank + 1] - cuts[c.rank], cuts[-1]
         if fp_own.n_sites != n_own:
             raise ValueError("fp_own has %d sites, the cuts give this rank %d" % (fp_own.n_sites, n_own))
-        self.cuts, self.row_blocks = cuts, row_blocks
+        self.cuts = cuts
         self.n_own, self.n_global, self.B = n_own, n_global, tree.n_nodes - 1
         H = halo_width(sweeps_per_refresh) if c.world > 1 else 0
         if H > min(b - a for a, b in zip(cuts[:-1], cuts[1:])):
@@ -198,9 +195,6 @@ class ShardedSampler:
         self.n_loc = fp_loc.n_sites
         self.left, self.right = left, right
         self.g0 = cuts[c.rank] - left
-        # statistics rows of every rank (all ranks compute the same table)
-        self.rows_per_rank = [(-(-(b - a) // BLOCK) + row_blocks - 1) // row_blocks for a, b in zip(cuts[:-1], cuts[1:])]
-        self.max_rows = max(self.rows_per_rank)
         self.dev.set_tree(tree)
         self.dev.set_model(model)
         self.dev.upload_paths(fp_loc, capacity, self.g0, n_global)
@@ -274,25 +268,23 @@ class ShardedSampler:
         if self.comm.world > 1 and self.dev.halo_phases_left() < 3 * (burn_in + batch):
             raise RuntimeError("halo too narrow for %d sweeps: call reset() first or set up with "
                                "a larger sweeps_per_refresh" % (burn_in + batch))
-        V = self.B * 16
-        piece_doubles = self.max_rows * batch * V + TAIL
+        words = batch * self.B * 16 + TAIL
         if self._piece is None or self._piece_batch != batch:
             for b in {id(x): x for x in (self._piece, self._gathered) if x is not None}.values():
                 b.free()
-            self._piece = self.dev.alloc(piece_doubles * 8)
-            self._gathered = self.dev.alloc(piece_doubles * 8 * self.comm.world) if self.comm.world > 1 \
+            self._piece = self.dev.alloc(words * 8)
+            self._gathered = self.dev.alloc(words * 8 * self.comm.world) if self.comm.world > 1 \
                 else self._piece
             self._piece_batch = batch
-        # this rank's rows of the statistics tree stay on the device; the accept count rides in
-        # the tail of the same piece, so ONE collective per EM iteration carries everything
-        nacc = self.dev.run_mcmc_rows(burn_in, batch, seed, sweep_base, self.row_blocks, self._piece)
-        self.dev.write(self._piece, (piece_doubles - TAIL) * 8, np.array([float(nacc)]))
+        # this rank's integer totals with its accept count in the tail of the same piece, so ONE
+        # collective per EM iteration carries everything
+        counts, nacc = self.dev.run_mcmc_counts(burn_in, batch, seed, sweep_base)
+        self.dev.write(self._piece, 0, np.append(counts.reshape(-1), np.int64(nacc)))
         self.comm.all_gather(self.dev, self._piece, self._gathered)
-        J, D = self.dev.reduce_gathered_rows(self._gathered, self.max_rows, piece_doubles, self.rows_per_rank,
-                                             batch, True)
-        nacc = sum(float(self.dev.read(self._gathered, ((r + 1) * piece_doubles - TAIL) * 8, 1)[0])
-                   for r in range(self.comm.world))
-        return J, D, nacc / float(batch * (self.n_global - 2))
+        pieces = self.dev.read(self._gathered, 0, words * self.comm.world, np.int64).reshape(self.comm.world, words)
+        total = pieces.sum(axis=0, dtype=np.int64)
+        J, D = self.dev.counts_to_stats(total[:-TAIL].reshape(batch, -1), batch, True)
+        return J, D, float(total[-TAIL]) / float(batch * (self.n_global - 2))
 
     def scale_jump_times(self, new_branches):
         self.dev.scale_jump_times(new_branches)
@@ -345,11 +337,9 @@ class LocalGroup:
     pays its own ramp and tail.  Two contexts on the same device, each owning half of the
     (local) genome plus redundant halos exactly like shards on different GPUs, run on their own
     streams from their own host threads and fill each other's gaps: +17 % on one MI355X
-    (tools/probe_streams.py).  Unlike shards on different GPUs, the group reproduces the
-    single-context run bit-for-bit INCLUDING D: the shards own whole 256-site blocks of the
-    canonical reduction tree (cut points and the internal halo width are multiples of 256)
-    and write their level-0 block partials into one shared buffer that is reduced once
-    (epv_run_mcmc_blocks / epv_reduce_blocks).  Drop-in for DeviceSampler inside
+    (tools/probe_streams.py).  The group reproduces the single-context run bit-for-bit
+    INCLUDING D: every shard returns the integer totals of its owned sites and the group adds
+    them (epv_run_mcmc_counts / epv_counts_to_stats).  Drop-in for DeviceSampler inside
     ShardedSampler, so it composes with the multi-GPU sharding."""
 
     BLOCK = 256
@@ -364,7 +354,6 @@ class LocalGroup:
         self.n_sites = self.n_nodes = self.B = 0
         self.capacity_events = []
         self._auto_grow = False
-        self._blocks, self._blocks_shape = None, None
         self.outer = (0, 0)
         self.halo_mode = False
 
@@ -383,14 +372,9 @@ class LocalGroup:
         if getattr(self, "_closed", False):
             return
         self._closed = True
-        try:
-            if self._blocks is not None and self.subs and self.subs[0].h:
-                self._blocks.free()
-        finally:
-            self._blocks = None
-            for s in self.subs:
-                s.close()
-            self.pool.shutdown(wait=True)
+        for s in self.subs:
+            s.close()
+        self.pool.shutdown(wait=True)
 
     def __del__(self):
         try:
@@ -433,19 +417,11 @@ class LocalGroup:
                            global_site_offset + self.lo[j], n_global)
         self.n_sites = n
         self.halo_mode = False
-        self.outer = (0, 0)
-        self._drop_blocks()     # the halos are set by set_halo() (ShardedSampler) or by reset()
-
-    def _drop_blocks(self):
-        if self._blocks is not None:
-            self._blocks.free()
-        self._blocks, self._blocks_shape = None, None
+        self.outer = (0, 0)     # the halos are set by set_halo() (ShardedSampler) or by reset()
 
     # ---- halos
     def set_halo(self, left, right):
         """outer halo blocks of the whole group (multi-GPU); the internal ones are managed here"""
-        if (left, right) != self.outer:
-            self._drop_blocks()          # ownership of the edge blocks changed
         self.outer, self.halo_mode = (left, right), True
         k, H = len(self.subs), self.H_INT
         for j, s in enumerate(self.subs):
@@ -534,47 +510,26 @@ class LocalGroup:
             return nacc
         return self._sweep_all(n_sweeps, seed, sweep_base)
 
-    def owned_blocks(self):
-        """(first local 256-site block with owned columns, number of such blocks)"""
-        left, right = self.outer
-        b0 = left // self.BLOCK
-        return b0, (self.n_sites - right + self.BLOCK - 1) // self.BLOCK - b0
-
-    def _run_blocks(self, burn_in, batch, seed, sweep_base):
-        """all shards' run_mcmc with the level-0 partials of the group's owned blocks in ONE
-        device buffer [batch][n_blocks][16 B] -> (accepted, n_blocks)"""
+    def run_mcmc_counts(self, burn_in, batch, seed, sweep_base=0):
+        """as DeviceSampler.run_mcmc_counts over the group's owned sites: the shards' totals added"""
         if self.halo_phases_left() < 3 * (burn_in + batch) and len(self.subs) > 1:
             raise RuntimeError("internal halo of %d columns is too narrow for %d sweeps without a "
                                "reset()" % (self.H_INT, burn_in + batch))
-        if self.outer[0] % self.BLOCK:
-            raise ValueError("the group's left halo must be a whole number of 256-site blocks")
-        b0, nb = self.owned_blocks()
-        shape = (batch, nb, self.B)
-        if self._blocks is None or self._blocks_shape != shape:
-            self._drop_blocks()
-            self._blocks, self._blocks_shape = self.subs[0].alloc(batch * nb * self.B * 16 * 8), shape
-        nacc = sum(self._each(lambda j, s: s.run_mcmc_blocks(burn_in, batch, seed, sweep_base, self._blocks.p,
-                                                             nb, self.lo[j] // self.BLOCK - b0)))
+        res = self._each(lambda j, s: s.run_mcmc_counts(burn_in, batch, seed, sweep_base))
         for s in self.subs:
             self.capacity_events += s.capacity_events
             s.capacity_events = []
-        return nacc, nb
+        return sum(c for c, _ in res), sum(n for _, n in res)
+
+    def counts_to_stats(self, counts, batch, average=True):
+        return self.subs[0].counts_to_stats(counts, batch, average)
 
     def run_mcmc(self, burn_in, batch, seed, sweep_base=0, average=True):
         if len(self.subs) == 1 and not self.halo_mode:
             return self.subs[0].run_mcmc(burn_in, batch, seed, sweep_base, average)
-        nacc, nb = self._run_blocks(burn_in, batch, seed, sweep_base)
-        J, D = self.subs[0].reduce_blocks(self._blocks.p, nb, batch, average)
+        counts, nacc = self.run_mcmc_counts(burn_in, batch, seed, sweep_base)
+        J, D = self.counts_to_stats(counts, batch, average)
         return J, D, nacc
-
-    def run_mcmc_rows(self, burn_in, batch, seed, sweep_base, row_blocks, rows_buf):
-        """as DeviceSampler.run_mcmc_rows, the group's shards writing one block buffer"""
-        nacc, nb = self._run_blocks(burn_in, batch, seed, sweep_base)
-        self.subs[0].blocks_to_rows(self._blocks.p, nb, batch, row_blocks, rows_buf.ptr)
-        return nacc
-
-    def reduce_gathered_rows(self, gathered_buf, max_rows, piece_doubles, rows_per_rank, batch, average=True):
-        return self.subs[0].reduce_gathered_rows(gathered_buf, max_rows, piece_doubles, rows_per_rank, batch, average)
 
     def scale_jump_times(self, new_branches):
         for s in self.subs:

@@ -43,9 +43,9 @@ ABI_SYMBOLS = [
     "epv_sweep_phase", "epv_run_mcmc", "epv_run_mcmc_sums", "epv_get_sufficient_statistics", "epv_scale_jump_times",
     "epv_paths_total_jumps", "epv_download_paths", "epv_get_tri_llh", "epv_column_bytes",
     "epv_get_columns", "epv_put_columns", "epv_copy_columns", "epv_dev_alloc", "epv_dev_free",
-    "epv_run_mcmc_blocks", "epv_reduce_blocks", "epv_get_counters", "epv_kernel_time_ms",
+    "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
-    "epv_blocks_to_rows", "epv_reduce_rows", "epv_reduce_gathered_rows", "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
+    "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
     "epv_phase_plan",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
@@ -101,16 +101,12 @@ def lib():
         L.epv_copy_columns.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
         L.epv_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
         L.epv_dev_free.argtypes = [vp, vp]
-        L.epv_run_mcmc_blocks.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64,
-                                          C.c_int64, u64p]
-        L.epv_reduce_blocks.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, dp, dp]
+        L.epv_run_mcmc_counts.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          C.POINTER(C.c_int64), u64p]
+        L.epv_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_int, dp, dp]
         L.epv_pack_columns_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
         L.epv_unpack_columns_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
         L.epv_device_of.argtypes = [vp]
-        L.epv_blocks_to_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp]
-        L.epv_reduce_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, dp, dp]
-        L.epv_reduce_gathered_rows.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint64, C.c_int,
-                                               dp, dp]
         L.epv_set_options.argtypes = [vp, C.c_uint32]
         L.epv_forward_simulate.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
                                            C.POINTER(C.c_uint64)]
@@ -139,8 +135,8 @@ def _p(a, t):
 
 class DevBuf:
     """Zero-filled device memory on a context's GPU.  torch (and anything else that speaks the
-    CUDA array interface) sees it without a copy, so the halo columns and statistic rows a
-    sharded run hands to RCCL never pass through the host."""
+    CUDA array interface) sees it without a copy, so the halo columns a sharded run hands to
+    RCCL never pass through the host."""
 
     def __init__(self, dev, nbytes):
         self.dev, self.nbytes = dev, int(nbytes)
@@ -171,13 +167,9 @@ class DeviceSampler:
         self.auto_grow = False     # True: widen the jump slots after an overflow and carry on
         self.capacity_events = []  # messages of the overflows that were absorbed
         self.halo = (0, 0)
-        self._blocks, self._blocks_shape = None, None
 
     def close(self):
         if getattr(self, "h", None):
-            if getattr(self, "_blocks", None) is not None:
-                self._blocks.free()
-                self._blocks = None
             self.L.epv_destroy(self.h)
             self.h = None
 
@@ -388,19 +380,24 @@ class DeviceSampler:
     def dev_free(self, p):
         self._ck(self.L.epv_dev_free(self.h, p))
 
-    def run_mcmc_blocks(self, burn_in, batch, seed, sweep_base, d_blocks, n_blocks_total, block_offset):
+    def run_mcmc_counts(self, burn_in, batch, seed, sweep_base=0):
+        """run_mcmc of a shard: -> (the integer totals of its owned sites per batch sweep, int64
+        [batch, 16 B]: J[8] then fixed-point D[8] per branch; accepted proposals).  Shards add
+        their totals as integers; counts_to_stats turns the sum into J, D"""
+        counts = np.zeros((batch, self.B * 16), np.int64)
         nacc = C.c_uint64(0)
-        self._ck_mcmc(self.L.epv_run_mcmc_blocks(self.h, burn_in, batch, seed, sweep_base, d_blocks,
-                                                 n_blocks_total, block_offset, C.byref(nacc)))
-        return int(nacc.value)
+        self._ck_mcmc(self.L.epv_run_mcmc_counts(self.h, burn_in, batch, seed, sweep_base,
+                                                 _p(counts, C.c_int64), C.byref(nacc)))
+        return counts, int(nacc.value)
 
-    def reduce_blocks(self, d_blocks, n_blocks_total, batch, average=True):
+    def counts_to_stats(self, counts, batch, average=True):
+        c = np.ascontiguousarray(counts, np.int64)
         J, D = np.zeros(self.B * 8), np.zeros(self.B * 8)
-        self._ck(self.L.epv_reduce_blocks(self.h, d_blocks, n_blocks_total, batch, int(average),
-                                          _p(J, C.c_double), _p(D, C.c_double)))
+        self._ck(self.L.epv_counts_to_stats(self.h, _p(c, C.c_int64), batch, int(average),
+                                            _p(J, C.c_double), _p(D, C.c_double)))
         return J, D
 
-    # ---- a genome sharded over several GPUs: device-resident halo columns and statistic rows
+    # ---- a genome sharded over several GPUs: device-resident halo columns and all-gather pieces
     # (buffers: DevBuf, or anything with .ptr = a device address on this context's GPU)
     def alloc(self, nbytes):
         return DevBuf(self, nbytes)
@@ -411,37 +408,6 @@ class DeviceSampler:
     def unpack_columns(self, first, count, buf):
         self._ck(self.L.epv_unpack_columns_dev(self.h, first, count, C.c_void_p(buf.ptr)))
 
-    def owned_blocks(self):
-        """(first local 256-site block with owned columns, number of such blocks)"""
-        left, right = self.halo
-        b0 = left // 256
-        return b0, (self.n_sites - right + 255) // 256 - b0
-
-    def run_mcmc_rows(self, burn_in, batch, seed, sweep_base, row_blocks, rows_buf):
-        """run_mcmc whose statistics stay on the device as rows of the reduction tree:
-        rows_buf[row][w][16 B] doubles, row = row_blocks consecutive blocks of the owned
-        columns (the shard starts on a whole row of the genome).  -> accepted proposals"""
-        if self.halo[0] % 256:
-            raise EpvError(EPV_ERR_ARG, "the left halo must be a whole number of 256-site blocks")
-        b0, nb = self.owned_blocks()
-        shape = (batch, nb, self.B)
-        if self._blocks is None or self._blocks_shape != shape:
-            if self._blocks is not None:
-                self._blocks.free()
-            self._blocks, self._blocks_shape = DevBuf(self, batch * nb * self.B * 16 * 8), shape
-        nacc = self.run_mcmc_blocks(burn_in, batch, seed, sweep_base, self._blocks.p, nb, -b0)
-        self.blocks_to_rows(self._blocks.p, nb, batch, row_blocks, rows_buf.ptr)
-        return nacc
-
-    def blocks_to_rows(self, d_blocks, n_blocks_total, batch, row_blocks, d_rows):
-        self._ck(self.L.epv_blocks_to_rows(self.h, d_blocks, n_blocks_total, batch, row_blocks, C.c_void_p(d_rows)))
-
-    def reduce_rows(self, d_rows, n_rows, batch, average=True):
-        J, D = np.zeros(self.B * 8), np.zeros(self.B * 8)
-        self._ck(self.L.epv_reduce_rows(self.h, C.c_void_p(d_rows), n_rows, batch, int(average),
-                                        _p(J, C.c_double), _p(D, C.c_double)))
-        return J, D
-
     def write(self, buf, offset, arr):
         a = np.ascontiguousarray(arr)
         self._ck(self.L.epv_dev_write(self.h, C.c_void_p(buf.ptr + offset), a.ctypes.data_as(C.c_void_p), a.nbytes))
@@ -450,14 +416,6 @@ class DeviceSampler:
         out = np.zeros(count, dtype)
         self._ck(self.L.epv_dev_read(self.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(buf.ptr + offset), out.nbytes))
         return out
-
-    def reduce_gathered_rows(self, gathered_buf, max_rows, piece_doubles, rows_per_rank, batch, average=True):
-        J, D = np.zeros(self.B * 8), np.zeros(self.B * 8)
-        rpr = np.ascontiguousarray(rows_per_rank, np.uint64)
-        self._ck(self.L.epv_reduce_gathered_rows(self.h, C.c_void_p(gathered_buf.ptr), len(rpr), max_rows, piece_doubles,
-                                                 _p(rpr, C.c_uint64), batch, int(average),
-                                                 _p(J, C.c_double), _p(D, C.c_double)))
-        return J, D
 
     def counters(self):
         c = _Counters()

@@ -285,45 +285,26 @@ int epv_copy_columns(epv_ctx *src, uint64_t src_first, uint64_t count, epv_ctx *
 int epv_copy_columns_async(epv_ctx *src, uint64_t src_first, uint64_t count, epv_ctx *dst, uint64_t dst_first,
                            int slot);
 
-/* ---- several shards on one GPU (new; the reference is single-process).  Two or three
- * contexts on one device, each owning a contiguous range of 256-aligned site blocks plus
- * redundant halos, run their colour phases on their own streams so that the ramps and tails
- * of the dependent kernels overlap (+17 % on one MI355X).  Every shard writes the integer
- * partial sums (see epv_get_sufficient_statistics) of its OWNED 256-site blocks, per batch sweep,
- * into one buffer shared by the group (epv_run_mcmc_blocks; d_blocks[w][block][16 (N-1)] 64-bit
- * words -- int64 behind the double pointer, J counts then fixed-point D; block_offset = index of
- * the shard's local block 0 in the group -- negative when a halo precedes the first owned block of
- * the buffer; the shard's global_site_offset must be a multiple of 256), and one reduction
- * (epv_reduce_blocks, on any context of the group) adds them up.  Integer sums are exact, so J AND
- * D equal the one-context run bit for bit however the genome is cut.
- * epv_dev_alloc returns zero-filled device memory (blocks nobody owns must read as 0). */
+/* ---- sharded runs (new; the reference is single-process).  Contexts that split a genome -- two or
+ * three on one GPU, whose colour phases overlap on their own streams (+17 % on one MI355X), and
+ * those of other GPUs -- each own a contiguous range of sites plus redundant halos.
+ * epv_run_mcmc_counts is epv_run_mcmc on such a context: it writes the integer totals (see
+ * epv_get_sufficient_statistics) of the context's OWNED sites per batch sweep to the host array
+ * counts[w][b][16] (int64, w < batch, b < n_nodes-1: J[8] as counts, then D[8] as fixed-point
+ * integers of scale 2^k_b).  A driver adds the arrays of all contexts as integers -- exact, in any
+ * grouping -- and epv_counts_to_stats turns the sum into J, D (average = 1: batch averages) as
+ * epv_run_mcmc_sums does, so J AND D equal the one-context run bit for bit however the genome is
+ * cut.  A capacity overflow (EPV_ERR_CAPACITY) still fills counts and n_accepted.
+ * epv_dev_alloc returns zero-filled device memory on the context's GPU, the buffers a driver hands
+ * to RCCL (halo columns, the statistics piece of the all-gather); epv_dev_write / epv_dev_read copy
+ * host memory into and out of them. */
+int epv_run_mcmc_counts(epv_ctx *ctx, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base,
+                        int64_t *counts, uint64_t *n_accepted);
+int epv_counts_to_stats(epv_ctx *ctx, const int64_t *counts, uint64_t batch, int average, double *J, double *D);
 int epv_dev_alloc(epv_ctx *ctx, uint64_t bytes, void **device_ptr);
 int epv_dev_free(epv_ctx *ctx, void *device_ptr);
 int epv_dev_write(epv_ctx *ctx, void *d_dst, const void *src, uint64_t bytes);
 int epv_dev_read(epv_ctx *ctx, void *dst, const void *d_src, uint64_t bytes);
-int epv_run_mcmc_blocks(epv_ctx *ctx, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base,
-                        double *d_blocks, uint64_t n_blocks_total, int64_t block_offset,
-                        uint64_t *n_accepted);
-int epv_reduce_blocks(epv_ctx *ctx, const double *d_blocks, uint64_t n_blocks_total, uint64_t batch,
-                      int average, double *J, double *D);
-
-/* ---- statistics of a genome sharded over several GPUs (new).  Shards are cut on multiples of
- * 256 * row_blocks sites (row_blocks a power of two).  Every GPU reduces the level-0 partials of
- * ITS blocks (d_blocks as written by epv_run_mcmc_blocks, nb_total blocks) to rows of row_blocks
- * blocks, d_rows[row][w][16 (N-1)]; the rows of all GPUs, concatenated in genome order (one RCCL
- * all-gather per EM iteration), go through epv_reduce_rows.  Every stage adds 64-bit integers, so
- * J AND D equal the one-context results bit for bit, whatever the number of GPUs and rows. */
-int epv_blocks_to_rows(epv_ctx *ctx, const double *d_blocks, uint64_t n_blocks_total, uint64_t batch,
-                       uint32_t row_blocks, double *d_rows);
-int epv_reduce_rows(epv_ctx *ctx, const double *d_rows, uint64_t n_rows, uint64_t batch, int average,
-                    double *J, double *D);
-/* the same straight on the output of an all-gather of equally sized pieces:
- * rank r's piece starts at d_gathered + r * piece_doubles (0 = max_rows * batch * 16 (N-1); larger
- * when the pieces carry a tail, e.g. the shard's accept count) and is laid out
- * [max_rows][batch][16 (N-1)], of which the first rows_per_rank[r] rows count */
-int epv_reduce_gathered_rows(epv_ctx *ctx, const double *d_gathered, uint32_t world, uint64_t max_rows,
-                             uint64_t piece_doubles, const uint64_t *rows_per_rank, uint64_t batch, int average,
-                             double *J, double *D);
 
 int epv_get_counters(epv_ctx *ctx, epv_counters *out);
 
@@ -333,7 +314,7 @@ int epv_get_counters(epv_ctx *ctx, epv_counters *out);
  * a sample adds, per branch b, site s and point i, the state of the path at t_i: its init state at
  * point 0, Path::state_at_time(t_i) (init XOR the parity of the jumps < t_i) at i >= 1.  A sample is
  * the resident paths after each batch sweep of epv_run_mcmc / epv_run_mcmc_sums /
- * epv_run_mcmc_blocks (not the burn-in), or one epv_accumulate_path_average call.  The counts are
+ * epv_run_mcmc_counts (not the burn-in), or one epv_accumulate_path_average call.  The counts are
  * exact integers kept on the device (4 (N-1) P bytes per site), so they do not depend on the
  * kernels, contexts or GPUs.  A context counts its owned sites plus the genome's end sites when it
  * holds them: over all contexts every site once.  Off (the default) costs nothing.

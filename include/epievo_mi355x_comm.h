@@ -6,9 +6,9 @@
  * the sites of the genome: per EM iteration the shards exchange
  *   1. their edge columns with the two genome neighbours (halo refresh before reset(),
  *      /root/reference/src/prog/epievo_est_params_histories.cpp:236-241 is the loop it sits in), and
- *   2. the rows of the sufficient statistics J/D (one all-gather after run_mcmc(), :248).
- * Buffers are DEVICE memory on the rank's GPU (epv_pack_columns_dev / epv_blocks_to_rows of
- * include/epievo_mi355x.h write them); nothing is staged through the host.
+ *   2. their integer totals of the sufficient statistics J/D (one all-gather after run_mcmc(), :248).
+ * Buffers are DEVICE memory on the rank's GPU (epv_pack_columns_dev / epv_dev_write of
+ * include/epievo_mi355x.h fill them).
  *
  * Two ways to make the ranks:
  *   epv_comm_init_all   every rank lives in THIS process (the C++ EM driver: one context and

@@ -1,6 +1,7 @@
 """Worker for the world_size>1 tests: runs ShardedSampler on a slice of a genome and
 writes its owned paths + J/D so the parent test can compare with the unsharded run.
-  python dist_worker.py <backend: oracle|hip|hipgroup> <cfg> <n_global> <burn> <batch> <em_iters> <outdir> [row_blocks]
+  python dist_worker.py <backend: oracle|hip|hipgroup> <cfg> <n_global> <burn> <batch> <em_iters> <outdir> <cuts>
+(cuts: the world + 1 cut points, comma-separated)
 Rendezvous via env (RANK/WORLD_SIZE/MASTER_ADDR/MASTER_PORT); comm backend is gloo."""
 import os
 import sys
@@ -15,10 +16,10 @@ sys.path.insert(0, os.path.dirname(HERE))
 def main():
     backend, cfg, n_global, burn, batch, iters, outdir = sys.argv[1:8]
     n_global, burn, batch, iters = int(n_global), int(burn), int(batch), int(iters)
-    row_blocks = int(sys.argv[8]) if len(sys.argv) > 8 else 1
+    cuts = [int(x) for x in sys.argv[8].split(",")]
     import torch.distributed as dist
     from common import simulate
-    from epievo_amd.parallel import ShardedSampler, TorchComm, shard_cuts
+    from epievo_amd.parallel import ShardedSampler, TorchComm
     dist.init_process_group("gloo")
     if backend == "oracle":
         comm = TorchComm(dist)
@@ -26,7 +27,6 @@ def main():
         import torch
         comm = TorchComm(dist, torch.device("cuda", 0))
     model, tree, fp = simulate(cfg, n_global, seed=17)
-    cuts = shard_cuts(n_global, comm.world, row_blocks)
     own = fp.slice_sites(cuts[comm.rank], cuts[comm.rank + 1])
     if backend == "oracle":
         from fake_device import OracleDevice
@@ -36,7 +36,7 @@ def main():
         ss = ShardedSampler(comm, device=0, device_factory=lambda dev: LocalGroup(dev, 2, burn + batch))
     else:
         ss = ShardedSampler(comm, device=0)
-    ss.setup(model, tree, own, cuts, capacity=16, sweeps_per_refresh=burn + batch, row_blocks=row_blocks)
+    ss.setup(model, tree, own, cuts, capacity=16, sweeps_per_refresh=burn + batch)
     out = {}
     for it in range(iters):
         ss.reset()

@@ -20,12 +20,6 @@ class HostBuf:
         pass
 
 
-def rows_total(rows):
-    """integer sum over axis 0 (the statistics are exact int64 sums: any order gives the same
-    bits; numpy restatement of the last stage of the device reduction)"""
-    return rows.sum(axis=0, dtype=np.int64)
-
-
 class OracleDevice:
     def __init__(self, device=0):
         self.o = None
@@ -159,40 +153,31 @@ class OracleDevice:
             self.o.L.orc_set_site(self.o.h, first + s, orc._p(i8, C.c_uint8),
                                   orc._p(c32, C.c_uint32), orc._p(js, C.c_double))
 
-    # ---- statistics rows (the product: epv_run_mcmc_blocks + epv_blocks_to_rows)
-    def run_mcmc_rows(self, burn_in, batch, seed, sweep_base, row_blocks, rows_buf):
-        assert self.left % 256 == 0
+    # ---- per-sweep integer totals (the product: epv_run_mcmc_counts + epv_counts_to_stats)
+    def run_mcmc_counts(self, burn_in, batch, seed, sweep_base=0):
         w = sweep_base
         for _ in range(burn_in):
             self._sweep(seed, w)
             w += 1
         lo, hi = self._owned()
-        nb = (self.n - self.right + 255) // 256 - self.left // 256
-        n_rows = (nb + row_blocks - 1) // row_blocks
-        V = self.B * 16
-        rows = rows_buf.np[:n_rows * batch * V * 8].view(np.int64).reshape(n_rows, batch, V)
-        one = np.zeros((n_rows, V), np.int64)
+        counts = np.zeros((batch, self.B * 16), np.int64)
         nacc = 0
         for i in range(batch):
             nacc += self._sweep(seed, w)
             w += 1
-            self.o.L.orc_suffstats_rows(self.o.h, self.left, 256 * row_blocks, n_rows, lo, hi,
-                                        orc._p(one, C.c_int64))
-            rows[:, i, :] = one
-        return nacc
+            one = np.zeros(self.B * 16, np.int64)    # one row over the owned sites
+            self.o.L.orc_suffstats_rows(self.o.h, 0, self.n, 1, lo, hi, orc._p(one, C.c_int64))
+            counts[i] = one
+        return counts, nacc
 
-    def reduce_gathered_rows(self, gathered_buf, max_rows, piece_doubles, rows_per_rank, batch, average=True):
-        V = self.B * 16
-        g = gathered_buf.np.view(np.int64)
-        rows = np.concatenate([g[r * piece_doubles:r * piece_doubles + k * batch * V].reshape(k, batch, V)
-                               for r, k in enumerate(rows_per_rank)], axis=0)
-        tot = rows_total(rows).reshape(batch, self.B, 16)            # [batch][B][16] integers
+    def counts_to_stats(self, counts, batch, average=True):
+        tot = np.asarray(counts, np.int64).reshape(batch, self.B, 16)
         scale = np.zeros(self.B + 1)
         self.o.L.orc_stat_scales(self.o.h, orc._p(scale, C.c_double))
         one = tot.astype(np.float64)       # int64 -> double rounds to nearest even, as C does
         one[:, :, 8:] *= (1.0 / scale[1:])[None, :, None]            # 2^-k: exact
-        one = one.reshape(batch, V)
-        acc = np.zeros(V)
+        one = one.reshape(batch, self.B * 16)
+        acc = np.zeros(self.B * 16)
         for i in range(batch):             # the sequential accumulation of run_mcmc
             acc = acc + one[i]
         if average:

@@ -1,6 +1,6 @@
 """The N>1 path: site shards with wide halos (epievo_amd/parallel.py) must reproduce the
-unsharded run bit-for-bit on paths, J, D and the acceptance rate (shards are cut on whole rows of
-the statistics tree, so every rank sums the same balanced tree as one context does).
+unsharded run bit-for-bit on paths, J, D and the acceptance rate (the ranks add exact integer
+statistics, so the result does not depend on where the genome is cut).
 CPU: 2 and 3 gloo ranks over the oracle-backed device double.  GPU: 2 gloo ranks sharing
 the one MI355X through the real HIP path."""
 import os
@@ -26,7 +26,7 @@ def _free_port():
         return sk.getsockname()[1]
 
 
-def _run_ranks(world, backend, cfg, n_global, burn, batch, iters, row_blocks=1):
+def _run_ranks(world, backend, cfg, n_global, burn, batch, iters, cuts):
     port = _free_port()      # a fixed port can still be in TIME_WAIT from the previous run
     out = tempfile.mkdtemp(prefix="epv_shard_")
     procs = []
@@ -35,7 +35,7 @@ def _run_ranks(world, backend, cfg, n_global, burn, batch, iters, row_blocks=1):
                    MASTER_PORT=str(port), LOCAL_RANK=str(r), OMP_NUM_THREADS="1")
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(HERE, "dist_worker.py"), backend, cfg, str(n_global),
-             str(burn), str(batch), str(iters), out, str(row_blocks)], env=env))
+             str(burn), str(batch), str(iters), out, ",".join(str(c) for c in cuts)], env=env))
     for p in procs:
         assert p.wait(timeout=600) == 0
     return [np.load(os.path.join(out, "rank%d.npz" % r)) for r in range(world)]
@@ -80,17 +80,20 @@ def _check(ranks, ref_res, ref_paths, n_nodes, cuts):
     for it, (J, D, acc) in enumerate(ref_res):
         for r in ranks:
             assert np.array_equal(r["J%d" % it], J)
-            assert np.array_equal(r["D%d" % it], D)       # same balanced tree, same bits
+            assert np.array_equal(r["D%d" % it], D)       # integer sums: same bits
             assert float(r["acc%d" % it]) == acc
 
 
-# shards of unequal length (the cut points sit on whole rows), 1- and 4-block rows
-@pytest.mark.parametrize("world,cfg,n,row_blocks", [(2, "tree", 1500, 1), (3, "pair", 2300, 1), (2, "tree", 4000, 4)])
-def test_sharded_oracle_gloo(world, cfg, n, row_blocks):
+# shards of unequal length: shard_cuts with 1- and 4-block rows (an int), or explicit cut points
+# off the 256-site grid
+@pytest.mark.parametrize("world,cfg,n,cuts", [(2, "tree", 1500, 1), (3, "pair", 2300, 1), (2, "tree", 4000, 4),
+                                              pytest.param(2, "tree", 1500, (0, 701, 1500), id="2-tree-1500-offgrid")])
+def test_sharded_oracle_gloo(world, cfg, n, cuts):
     burn, batch, iters = 1, 3, 2
-    ranks = _run_ranks(world, "oracle", cfg, n, burn, batch, iters, row_blocks)
+    cuts = shard_cuts(n, world, cuts) if isinstance(cuts, int) else list(cuts)
+    ranks = _run_ranks(world, "oracle", cfg, n, burn, batch, iters, cuts)
     ref_res, ref_paths, tree = _unsharded(_OracleEngine, cfg, n, burn, batch, iters)
-    _check(ranks, ref_res, ref_paths, tree.n_nodes, shard_cuts(n, world, row_blocks))
+    _check(ranks, ref_res, ref_paths, tree.n_nodes, cuts)
 
 
 def test_shard_cuts_and_halo_width():
@@ -126,11 +129,11 @@ def test_sharded_hip_two_ranks_one_gpu():
         def paths(self):
             return self.d.paths()
 
-    burn, batch, iters, n, rb = 2, 3, 2, 10000, 4
-    ranks = _run_ranks(2, "hip", "tree", n, burn, batch, iters, rb)
+    burn, batch, iters, n = 2, 3, 2, 10000
+    cuts = shard_cuts(n, 2, 4)
+    ranks = _run_ranks(2, "hip", "tree", n, burn, batch, iters, cuts)
     ref_res, ref_paths, tree = _unsharded(_HipEngine, "tree", n, burn, batch, iters)
-    cuts = shard_cuts(n, 2, rb)
     _check(ranks, ref_res, ref_paths, tree.n_nodes, cuts)
     # the same with two concurrent contexts per rank (LocalGroup inside each rank's shard)
-    ranks = _run_ranks(2, "hipgroup", "tree", n, burn, batch, iters, rb)
+    ranks = _run_ranks(2, "hipgroup", "tree", n, burn, batch, iters, cuts)
     _check(ranks, ref_res, ref_paths, tree.n_nodes, cuts)

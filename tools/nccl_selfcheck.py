@@ -5,7 +5,7 @@ Checks, with the nccl (= RCCL) process group of torch.distributed in the same pr
 library's own streams, every leg of the one-process-per-GPU path that one rank can exercise:
   * torch sees the library's device buffers (DevBuf) through the CUDA array interface without a
     copy, and RCCL moves them: an in-place all-gather and a send/receive pair to the own rank;
-  * ShardedSampler over TorchComm (statistics rows + accept count in ONE all-gather) gives the
+  * ShardedSampler over TorchComm (integer statistics + accept count in ONE all-gather) gives the
     numbers of the plain DeviceSampler.run_mcmc, bit for bit."""
 import os
 import sys
