@@ -141,6 +141,10 @@ struct epv_ctx {
   std::vector<double> pa_grid_blen;  // the branch lengths d_pa_grid was built from
   uint32_t *d_pa_out = nullptr;    // read-out staging
   uint64_t pa_out_cap = 0;         // bytes
+  // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
+  // the layout of epv_unobserved (epv_kernels.h)
+  uint32_t *d_unobs = nullptr;
+  uint64_t unobs_cells = 0;
 };
 
 namespace {
@@ -205,6 +209,8 @@ void free_paths(epv_ctx *c) {
   c->fused_waves = 0;
   dfree(c->d_partial[0]); dfree(c->d_partial[1]);
   c->partial_cap[0] = c->partial_cap[1] = 0;
+  dfree(c->d_unobs);   // new paths are new data
+  c->unobs_cells = 0;
   c->have_paths = c->have_reset = false;
 }
 
@@ -727,20 +733,24 @@ struct PhasePlan {
   uint32_t accept;       // EPV_PLAN_ACCEPT_*
   bool listed;           // the accept stage reads the listed sites
   bool meta_cache;       // (accept and fused kernels) the LDS meta cache
+  bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
   uint32_t word() const {
     return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
-           p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16;
+           p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16 |
+           (unobs ? 1u : 0u) << 17;
   }
 };
 PhasePlan phase_plan(const epv_ctx *c) {
   PhasePlan P{};
   // (root resampling changes the proposal's normalising constant with the path: the ratio must be evaluated)
   P.refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
+  // unobserved leaf cells: only the first kernel marginalises them
+  P.unobs = c->unobs_cells != 0u;
   // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
   // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
   // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us)
-  const bool p3 = c->p3 && !P.refq;
-  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !c->p2_gpool;
+  const bool p3 = c->p3 && !P.refq && !P.unobs;
+  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !c->p2_gpool;
   P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
   if (p2 && c->fused) {
     P.propose = EPV_PLAN_FUSED;
@@ -845,11 +855,20 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     ++c->phase_parity;
   } else {
     if (P.gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
-    auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true> : epv_mh_propose_kernel<true, false>)
-                        : (P.refq ? epv_mh_propose_kernel<false, true> : epv_mh_propose_kernel<false, false>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
-                       (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
-                       c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr);
+    if (P.unobs) {
+      using M = const uint32_t *;
+      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, true, M> : epv_mh_propose_kernel<true, false, true, M>)
+                          : (P.refq ? epv_mh_propose_kernel<false, true, true, M> : epv_mh_propose_kernel<false, false, true, M>);
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
+                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
+                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr, (M)c->d_unobs);
+    } else {
+      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, false> : epv_mh_propose_kernel<true, false, false>)
+                          : (P.refq ? epv_mh_propose_kernel<false, true, false> : epv_mh_propose_kernel<false, false, false>);
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
+                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
+                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr);
+    }
   }
   if (seg_mode) {
     // dirty segments one lane each, then their branches one lane each; both lists are sized on
@@ -987,14 +1006,16 @@ EPV_API epv_ctx *epv_create(int device_id) {
   for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn)),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const void *v1[] = {
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, false>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, false>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, false>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, false>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, true, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, true, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, true, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, true, const uint32_t *>)};
+  for (const void *k : v1) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return c;
 }
 
@@ -1029,6 +1050,12 @@ EPV_API int epv_set_tree(epv_ctx *c, int n_nodes, const uint32_t *parent_ids,
         !(branches[i] > 0.0))
       return fail(c, EPV_ERR_ARG, "tree arrays are not a valid pre-order tree with positive branches");
   HIP_TRY(c, hipSetDevice(c->device));
+  // the mask of unobserved cells holds rows for the leaves of the tree it was set on
+  if (c->d_unobs && !std::equal(c->subtree.begin(), c->subtree.end(), subtree_sizes)) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_unobs);
+    c->unobs_cells = 0;
+  }
   c->parent.assign(parent_ids, parent_ids + n_nodes);
   c->subtree.assign(subtree_sizes, subtree_sizes + n_nodes);
   c->blen.assign(branches, branches + n_nodes);
@@ -1270,6 +1297,58 @@ EPV_API int epv_phase_mode(epv_ctx *c, uint32_t *mode) {
 EPV_API int epv_phase_plan(epv_ctx *c, uint32_t *word) {
   if (!c || !word || !c->have_paths) return EPV_ERR_ARG;
   *word = phase_plan(c).word();
+  return EPV_OK;
+}
+
+EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_unobserved");
+  const uint32_t N = c->S.N;
+  const uint64_t n = c->S.n;
+  uint64_t cells = 0;
+  uint32_t leaves = 0;
+  for (uint32_t node = 1; node < N; ++node) {
+    const bool leaf = c->subtree[node] == 1u;
+    leaves += leaf ? 1u : 0u;
+    if (!unobserved) continue;
+    const uint8_t *row = unobserved + (uint64_t)(node - 1u) * n;
+    uint64_t k = 0;
+    for (uint64_t s = 0; s < n; ++s) k += row[s] != 0u;
+    if (k && !leaf)
+      return fail(c, EPV_ERR_ARG, "unobserved cells on branch " + std::to_string(node) +
+                                      ", which does not end in a leaf (internal nodes are latent already)");
+    cells += k;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (a queued phase may still read the old mask)
+  dfree(c->d_unobs);
+  c->unobs_cells = 0;
+  if (!cells) return EPV_OK;   // nothing unobserved: today's kernels, no allocation
+  // the layout of epv_unobserved: N words of row offsets, then one row of ceil(n / 32) words per leaf
+  const uint64_t row = (n + 31u) / 32u;
+  const uint64_t words = N + (uint64_t)leaves * row;
+  if (words > 0xffffffffull) return fail(c, EPV_ERR_ARG, "mask of unobserved cells too large for 32-bit row offsets");
+  std::vector<uint32_t> h(words, 0u);
+  uint64_t at = N;
+  for (uint32_t node = 1; node < N; ++node) {
+    if (c->subtree[node] != 1u) continue;
+    h[node] = (uint32_t)at;
+    const uint8_t *src = unobserved + (uint64_t)(node - 1u) * n;
+    for (uint64_t s = 0; s < n; ++s)
+      if (src[s]) h[at + (s >> 5)] |= 1u << (s & 31u);
+    at += row;
+  }
+  DevTmp<uint32_t> d;
+  HIP_TRY(c, d.alloc(words));
+  HIP_TRY(c, hipMemcpy(d.p, h.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->d_unobs = d.release();
+  c->unobs_cells = cells;
+  return EPV_OK;
+}
+
+EPV_API int epv_unobserved_cells(epv_ctx *c, uint64_t *n_cells) {
+  if (!c || !n_cells) return EPV_ERR_ARG;
+  *n_cells = c->unobs_cells;
   return EPV_OK;
 }
 

@@ -419,6 +419,13 @@ __device__ __forceinline__ double gtp(double r0, double r1, double h, double den
 // its lanes.
 #define EPV_MH_THREADS 256
 
+// the mask of unobserved leaf cells as epv_set_unobserved lays it out on the device (u32 words):
+// word `node` (< N) holds the offset of the node's bit row, rows follow the N-word header, one per
+// leaf, and bit (s & 31) of row word s >> 5 flags local site s
+__device__ __forceinline__ bool epv_unobserved(const uint32_t *mask, uint32_t node, uint64_t site) {
+  return (mask[(uint64_t)mask[node] + (site >> 5)] >> (site & 31u)) & 1u;
+}
+
 // GPOOL = false: the record pool lives in LDS (short trees: ~13 KB per wave, 12 waves/CU).
 // GPOOL = true : the pool is a per-block slab in global memory with the very same indexing.
 //   On a large tree the pool alone (64 lanes x (N-1) branches x ~2 records x 16 B = 84 KB for
@@ -438,11 +445,19 @@ __device__ __forceinline__ double gtp(double r0, double r1, double h, double den
 //   (<= 2e-12 over millions of updates, tests/test_proposal_ratio.py), and both modes produce
 //   the same paths.  The default; the kernel then needs no log, no current-path walk and no
 //   prop_llr hand-over.
-template <bool GPOOL, bool REFQ>
+// UNOBS = true: leaf cells flagged in the context's mask of unobserved cells (epv_set_unobserved:
+//   missing leaf data) are marginalised: the leaf's q is (1, 1) instead of the indicator of its end
+//   state, so the downward pass draws that end state from its conditional law like any other.  The
+//   proposal is still f_mid(path) / Z with Z a function of the neighbours and the OBSERVED data, so
+//   the telescoping argument above and both REFQ modes hold unchanged.  The mask (epv_unobserved) is
+//   the one trailing argument only these instantiations take: the others keep their argument layout
+//   and so their instruction stream.
+template <bool GPOOL, bool REFQ, bool UNOBS, class... Unobs>
 __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
     uint64_t first, uint64_t last, uint32_t pool_entries, unsigned long long *counters,
-    double *gpool) {
+    double *gpool, Unobs... unobs) {
+  static_assert(sizeof...(Unobs) == (UNOBS ? 1u : 0u), "the mask of unobserved cells comes with UNOBS");
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   double *s_const = s_mem;                     // 20 + N doubles (padded to even)
   const uint32_t const_dbl = (20u + S.N + 1u) & ~1u;
@@ -507,6 +522,9 @@ __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
           const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
           q0 = leaf_state ? 0.0 : 1.0;
           q1 = leaf_state ? 1.0 : 0.0;
+          if constexpr (UNOBS) {
+            if (epv_unobserved(unobs..., node, site)) { q0 = 1.0; q1 = 1.0; }
+          }
         } else {
           for (uint32_t ch = 1u; ch < sub; ch += S.subtree[node + ch]) {
             const double *a = my + (size_t)(regA[(node + ch) * 64u + lane] & 0x7fffffffu) * RS;

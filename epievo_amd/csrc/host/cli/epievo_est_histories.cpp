@@ -6,6 +6,8 @@
 // New: -a/--average FILE with -n/--npoints (default 100, as average_paths): the average history of
 // the B batch sweeps, counted on the device (epv_set_path_average), in average_paths' output format
 // (average_paths.cpp:49-63), without writing the samples to files.
+// New: -m/--missing STATES_FILE: leaf cells marked N there are unobserved (SingleSiteSampler::set_unobserved):
+// the MCMC resamples their end states instead of pinning them; the other cells must agree with the paths.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -30,7 +32,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     size_t rng_seed = std::numeric_limits<size_t>::max();
 
@@ -46,6 +48,8 @@ int main(int argc, const char **argv) {
                       gpu_list);
     opt_parse.add_opt("average", 'a', "output file of the average history of the batch sweeps", false, average_file);
     opt_parse.add_opt("npoints", 'n', "number of time points per branch of the average", false, n_points);
+    opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data: resampled, not pinned", false,
+                      missing_file);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -76,6 +80,13 @@ int main(int argc, const char **argv) {
     epv::FlatPaths paths;
     epv::Tree th;
     epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
+    // missing leaf data, checked against the paths before any GPU call
+    vector<uint8_t> unobserved;
+    if (!missing_file.empty()) {
+      uint64_t n_unobserved = 0, n_leaf_cells = 0;
+      unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
+      if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+    }
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
       std::random_device rd;
@@ -85,6 +96,7 @@ int main(int argc, const char **argv) {
 
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
+    if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     mcmc.reset(the_model, th, paths);
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);

@@ -7,6 +7,8 @@
 // the node to shard the sites over -- "all", or HIP device ids "0,1,2,3" -- with RCCL between
 // them (epv_sampler.hpp); results do not depend on the list.  A list with repeats ("0,0,0,0")
 // rehearses a multi-GPU run on fewer GPUs.
+// Another: -m/--missing STATES_FILE -- leaf cells marked N there are missing data, resampled in every
+// E-step instead of pinned (SingleSiteSampler::set_unobserved; kept across the iterations).
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -35,7 +37,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false, optimize_branches = false;
-    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list;
+    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file;
     size_t iteration = 10, batch = 10, burnin = 10, paths_every = 1;
     size_t rng_seed = std::numeric_limits<size_t>::max();
     static const double param_tol = 1e-10;
@@ -57,6 +59,8 @@ int main(int argc, const char **argv) {
     // extension: the reference rewrites the whole paths file after EVERY iteration (:280-283; the file
     // doubles as a checkpoint).  -e k keeps that for every k-th iteration and the last one: the final
     // file is the same bytes, the ones in between are not written
+    opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data: resampled, not pinned", false,
+                      missing_file);
     opt_parse.add_opt("paths-every", 'e', "write the paths file every k-th iteration and after the last (default 1: "
                       "every iteration, as the reference does)", false, paths_every);
     vector<string> leftover_args;
@@ -88,6 +92,13 @@ int main(int argc, const char **argv) {
     epv::FlatPaths paths;
     epv::Tree th;
     epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
+    // missing leaf data, checked against the paths before any GPU call
+    vector<uint8_t> unobserved;
+    if (!missing_file.empty()) {
+      uint64_t n_unobserved = 0, n_leaf_cells = 0;
+      unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
+      if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+    }
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
       std::random_device rd;
@@ -109,6 +120,7 @@ int main(int argc, const char **argv) {
     vector<double> out_branches;
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
+    if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     // declared AFTER everything the thread references (and after the sampler): on an exception the
     // join runs first, while out_paths, out_branches and writer_error are still alive, and the file
     // of the last completed iteration is written out in full, as the synchronous reference leaves it

@@ -151,6 +151,13 @@ EPVD_API int epvd_kernel_time_ms(epvd_sampler *h, double *avg_ms, uint64_t *n_la
   return guarded(h, [&] { h->s->kernel_time_ms(*avg_ms, *n_launches); });
 }
 EPVD_API int epvd_phase_mode(epvd_sampler *h, uint32_t *mode) { return guarded(h, [&] { *mode = h->s->phase_mode(); }); }
+EPVD_API int epvd_set_unobserved(epvd_sampler *h, uint64_t n_sites, int n_nodes, const uint8_t *unobserved) {
+  return guarded(h, [&] {
+    std::vector<uint8_t> m;
+    if (unobserved) m.assign(unobserved, unobserved + (uint64_t)(n_nodes - 1) * n_sites);
+    h->s->set_unobserved(std::move(m));
+  });
+}
 
 EPVD_API int epvd_set_path_average(epvd_sampler *h, uint32_t n_points) {
   return guarded(h, [&] { h->s->set_path_average(n_points); });

@@ -475,6 +475,67 @@ void read_states_file(const std::string &states_file, std::vector<std::string> &
   }
 }
 
+void read_states_file_missing(const std::string &states_file, std::vector<std::string> &names,
+                              std::vector<std::vector<uint8_t>> &states, std::vector<std::vector<uint8_t>> &missing) {
+  std::ifstream in(states_file);
+  if (!in) throw std::runtime_error("cannot read states file: " + states_file);
+  std::string line;
+  std::getline(in, line);
+  if (!line.empty() && line[0] == '#') line = line.substr(1);
+  std::istringstream hs(line);
+  std::string nm;
+  while (hs >> nm) names.push_back(nm);
+  states.assign(names.size(), {});
+  missing.assign(names.size(), {});
+  while (std::getline(in, line)) {
+    std::istringstream ls(line);
+    size_t site = 0;
+    ls >> site;
+    size_t k = 0;
+    char v = 0;
+    for (; k < names.size() && ls >> v; ++k) {
+      const bool miss = v == 'N' || v == 'n';
+      states[k].push_back(v == '1');
+      missing[k].push_back(miss ? 1u : 0u);
+    }
+    if (k != names.size()) throw std::runtime_error("bad line in states file");
+  }
+}
+
+std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const Tree &th, const FlatPaths &paths,
+                                           uint64_t &n_unobserved, uint64_t &n_leaf_cells) {
+  std::vector<std::string> names;
+  std::vector<std::vector<uint8_t>> states, missing;
+  read_states_file_missing(states_file, names, states, missing);
+  const uint64_t n = paths.n_sites, N = (uint64_t)th.n_nodes();
+  std::vector<uint8_t> mask((N - 1u) * n, 0u);
+  n_unobserved = n_leaf_cells = 0;
+  for (uint64_t node = 1; node < N; ++node) {
+    if (!th.is_leaf((int)node)) continue;   // (columns of internal nodes are not data: ignored)
+    const std::string &leaf = th.node_names[node];
+    const size_t k = std::find(names.begin(), names.end(), leaf) - names.begin();
+    if (k == names.size()) throw std::runtime_error("states file " + states_file + " has no column for leaf " + leaf);
+    if (states[k].size() != n)
+      throw std::runtime_error("states file " + states_file + " has " + std::to_string(states[k].size()) +
+                               " sites, the paths " + std::to_string(n));
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t e = (node - 1u) * n + s;
+      if (missing[k][s]) {
+        mask[e] = 1u;
+        ++n_unobserved;
+        continue;
+      }
+      const uint32_t end = paths.init[e] ^ (uint32_t)((paths.offsets[e + 1] - paths.offsets[e]) & 1u);
+      if (end != states[k][s])
+        throw std::runtime_error("states file " + states_file + ": leaf " + leaf + " at site " + std::to_string(s) +
+                                 " is " + std::to_string(states[k][s]) + ", the input paths end in " +
+                                 std::to_string(end));
+    }
+    n_leaf_cells += n;
+  }
+  return mask;
+}
+
 }  // namespace epv
 
 namespace epv {

@@ -67,6 +67,16 @@ void load_paths_and_tree(const std::string &paths_file, const std::string &tree_
 // read_states_file (src/libepievo/epievo_utils.cpp:90-125): states[seq][site]
 void read_states_file(const std::string &states_file, std::vector<std::string> &names,
                       std::vector<std::vector<uint8_t>> &states);
+// the same file with missing data: `N` or `n` marks a missing cell (missing[seq][site] = 1, its state 0);
+// every other character keeps read_states_file's meaning
+void read_states_file_missing(const std::string &states_file, std::vector<std::string> &names,
+                              std::vector<std::vector<uint8_t>> &states, std::vector<std::vector<uint8_t>> &missing);
+// -m/--missing of the E-step programs: the leaf cells a states file marks missing, as the whole-genome mask
+// of SingleSiteSampler::set_unobserved over `paths` ([(b-1) * n_sites + site]).  Columns are matched to the
+// leaves by name (every leaf needs one; columns of internal nodes are ignored) and the file needs one row per
+// site.  Throws, naming leaf and site, where an observed cell differs from the paths' leaf end state.
+std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const Tree &th, const FlatPaths &paths,
+                                           uint64_t &n_unobserved, uint64_t &n_leaf_cells);
 
 }  // namespace epv
 

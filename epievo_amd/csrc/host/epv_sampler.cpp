@@ -408,7 +408,38 @@ void SingleSiteSampler::download_path_average(std::vector<uint32_t> &counts, uin
   }
 }
 
+void SingleSiteSampler::set_unobserved(std::vector<uint8_t> whole_genome) {
+  bool any = false;
+  for (uint8_t v : whole_genome) any = any || v != 0u;
+  if (!any) whole_genome.clear();
+  if (n_sites_ && !whole_genome.empty() && whole_genome.size() != (uint64_t)(n_nodes_ - 1) * n_sites_)
+    throw std::runtime_error("mask of unobserved cells: " + std::to_string(whole_genome.size()) + " entries for " +
+                             std::to_string(n_nodes_ - 1) + " branches x " + std::to_string(n_sites_) + " sites");
+  unobs_ = std::move(whole_genome);
+  if (!n_sites_) return;   // no paths yet: the reset that uploads them applies it
+  if (!sharded()) {
+    apply_unobserved(ctx_, 0, n_sites_);
+    return;
+  }
+  for (const Part &p : parts_) apply_unobserved(p.ctx, p.lo, p.hi);
+}
+
+void SingleSiteSampler::apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi) {
+  if (unobs_.empty()) {
+    check_on(c, epv_set_unobserved(c, nullptr), "epv_set_unobserved");
+    return;
+  }
+  const uint64_t B = (uint64_t)n_nodes_ - 1u, w = hi - lo;
+  std::vector<uint8_t> win(B * w);
+  for (uint64_t b = 0; b < B; ++b)
+    std::copy(unobs_.begin() + b * n_sites_ + lo, unobs_.begin() + b * n_sites_ + hi, win.begin() + b * w);
+  check_on(c, epv_set_unobserved(c, win.data()), "epv_set_unobserved");
+}
+
 void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n, bool rank_mode) {
+  if (!unobs_.empty() && unobs_.size() != (uint64_t)(th.n_nodes() - 1) * n)
+    throw std::runtime_error("mask of unobserved cells: " + std::to_string(unobs_.size()) + " entries for " +
+                             std::to_string(th.n_nodes() - 1) + " branches x " + std::to_string(n) + " sites");
   n_nodes_ = th.n_nodes();
   n_sites_ = n;
   drop_parts();
@@ -443,6 +474,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
                        th.branches.data()), "epv_set_tree");
     check(epv_upload_paths(ctx_, paths.n_sites, paths.init.data(), paths.offsets.data(),
                            paths.jumps.data(), capacity_, 0), "epv_upload_paths");
+    if (!unobs_.empty()) apply_unobserved(ctx_, 0, n);
     return;
   }
   uint32_t cap = capacity_;
@@ -495,6 +527,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
     const double dummy = 0.0;
     check_on(c, epv_upload_paths(c, part.n_sites, part.init.data(), part.offsets.data(),
                                  part.jumps.empty() ? &dummy : part.jumps.data(), cap, q.lo), "epv_upload_paths");
+    if (!unobs_.empty()) apply_unobserved(c, q.lo, q.hi);   // (its window of the genome, halos included)
     check_on(c, epv_set_global_length(c, n), "epv_set_global_length");
   }
   if (rank_mode) {

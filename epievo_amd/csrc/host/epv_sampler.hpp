@@ -111,6 +111,12 @@ public:
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
+  // missing leaf data (epv_set_unobserved): whole_genome[(b-1) * n_sites + s] != 0 -> the leaf end state
+  // of branch b at genome site s is resampled with the history.  The whole genome also in one-slot-per-
+  // process mode (each process slices its own columns).  Kept in the sampler: applied to every context
+  // now if paths are resident, and to the window of every part a later reset(model, tree, paths) makes
+  // (which throws when the length does not match its genome); reset(model) keeps it.  Empty = clear.
+  void set_unobserved(std::vector<uint8_t> whole_genome);
   void set_timing(int every);
   void kernel_time_ms(double &avg_ms, uint64_t &n_launches);
   uint32_t phase_mode();
@@ -167,6 +173,7 @@ private:
   void drop_parts();          // back to the single context ctx_
   void refresh_parts();       // equal capacities, halo columns of every inner edge, fresh halo marks
   void apply_sample_root();
+  void apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi);   // unobs_ columns [lo, hi) of the genome
   void build(const Tree &th, const FlatPaths &paths, uint64_t n_global, bool rank_mode);
   std::vector<epv_ctx *> contexts() const;
   void equalize_capacity();
@@ -184,6 +191,7 @@ private:
   uint32_t capacity_;
   uint32_t pa_points_ = 0;    // set_path_average
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
+  std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   int n_nodes_ = 0;
   uint64_t n_sites_ = 0;      // genome length (all slots)
   size_t world_ = 1;          // slots of the run (== slots_.size() unless one slot per process)

@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan",
+    "epv_phase_plan", "epv_set_unobserved", "epv_unobserved_cells",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -114,6 +114,8 @@ def lib():
         L.epv_get_options.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.epv_set_unobserved.argtypes = [vp, u8p]
+        L.epv_unobserved_cells.argtypes = [vp, u64p]
         L.epv_dev_write.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_dev_read.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_get_counters.argtypes = [vp, C.POINTER(_Counters)]
@@ -225,7 +227,29 @@ class DeviceSampler:
         w = int(v.value)
         return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
                     small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
-                    jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1))
+                    jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
+                    unobs=bool(w >> 17 & 1))
+
+    def set_unobserved(self, mask):
+        """missing leaf data (epv_set_unobserved): mask[b-1, s] != 0 -> the leaf end state of branch b at
+        local site s is resampled with the history instead of pinned.  Shape (n_nodes - 1, n_sites) or
+        flat in that order, halo columns included; None clears.  Nonzero entries are allowed on leaf
+        branches only.  Uploading paths clears the mask."""
+        if mask is None:
+            self._ck(self.L.epv_set_unobserved(self.h, None))
+            return
+        m = np.ascontiguousarray(mask).reshape(-1)
+        if m.size != self.B * self.n_sites:
+            raise ValueError("mask of unobserved cells: %d entries for %d branches x %d sites"
+                             % (m.size, self.B, self.n_sites))
+        m = (m != 0).astype(np.uint8)
+        self._ck(self.L.epv_set_unobserved(self.h, _p(m, C.c_uint8)))
+
+    def unobserved_cells(self):
+        """the number of leaf cells flagged unobserved (epv_unobserved_cells)"""
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_unobserved_cells(self.h, C.byref(v)))
+        return int(v.value)
 
     def capacity(self):
         v = C.c_uint32(0)
@@ -490,6 +514,7 @@ class SingleSiteSampler:
         self.dev = DeviceSampler(device)
         self.dev.auto_grow = True     # paths grow on demand, as the reference's vectors do
         self._uploaded = False
+        self._unobserved = None       # the mask of unobserved leaf cells, re-applied after every upload
 
     def _apply_sample_root(self):
         flags = C.c_uint32(0)
@@ -504,10 +529,22 @@ class SingleSiteSampler:
         if paths is not None:
             self.dev.upload_paths(paths, self.capacity)
             self._uploaded = True
+            if self._unobserved is not None:
+                self.dev.set_unobserved(self._unobserved)
         if not self._uploaded:
             raise EpvError(EPV_ERR_STATE, "reset() needs paths the first time")
         self._apply_sample_root()
         self.dev.reset()
+
+    def set_unobserved(self, mask):
+        """missing leaf data (DeviceSampler.set_unobserved); kept across resets, re-applied to new paths.
+        None clears."""
+        if mask is None:
+            self._unobserved = None
+        else:
+            self._unobserved = (np.ascontiguousarray(mask).reshape(-1) != 0).astype(np.uint8)
+        if self._uploaded:
+            self.dev.set_unobserved(self._unobserved)
 
     def run_mcmc(self, seed, em_iter=0):
         self._apply_sample_root()

@@ -142,11 +142,28 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *              (epv_mh_jumps_kernel alone)
  *   bits 14-15 accept stage: EPV_PLAN_ACCEPT_FUSED (inside the fused kernel), _V3 (epv_mh_accept3_kernel),
  *              _CACHE (epv_mh_accept_kernel with its LDS meta cache), _NO_CACHE (epv_mh_accept_kernel without)
- *   bit  16    the accept stage reads the listed sites (proposal kernels V2 and V3; 0 = every site of the colour) */
+ *   bit  16    the accept stage reads the listed sites (proposal kernels V2 and V3; 0 = every site of the colour)
+ *   bit  17    V1: the template that marginalises unobserved leaf cells (epv_set_unobserved holds a cell;
+ *              it forces V1 like bit 3 does) */
 enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
 enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
 int epv_phase_plan(epv_ctx *ctx, uint32_t *word);
+
+/* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
+ * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
+ * instead of the indicator of the path's end state) instead of pinning it.  The node-major layout
+ * of epv_upload_paths' init_state over all local columns, halos included.  Cells of the genome's
+ * two end sites are never updated, so their flags have no effect.  NULL, or no nonzero entry,
+ * clears the mask: then the plan and the results are those of a context that never had one.  A
+ * nonzero entry on a branch that does not end in a leaf returns EPV_ERR_ARG (internal nodes are
+ * latent already); before paths are resident EPV_ERR_STATE.  The device holds one bit per (leaf,
+ * site), and only while a cell is flagged.  epv_upload_paths, epv_init_paths_indep and
+ * epv_forward_simulate clear the mask (new paths are new data); everything else keeps it.  While a
+ * cell is flagged a colour phase takes the first proposal kernel (epv_phase_mode 0, plan bit 17).
+ * epv_unobserved_cells: the number of flagged cells.  No reference counterpart. */
+int epv_set_unobserved(epv_ctx *ctx, const uint8_t *unobserved);
+int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
 
 /* initialize_paths_indep (src/prog/epievo_sim_pairwise.cpp:62-110) on the device, for the
  * two-node tree of one branch (epv_set_tree with n_nodes = 2 and epv_set_model first):

@@ -54,6 +54,11 @@ int epvd_set_options(epvd_sampler *s, uint32_t flags);           /* EPV_OPT_* on
 int epvd_set_timing(epvd_sampler *s, int every);                 /* epv_set_timing on every context */
 int epvd_kernel_time_ms(epvd_sampler *s, double *avg_ms, uint64_t *n_launches);
 int epvd_phase_mode(epvd_sampler *s, uint32_t *mode);
+/* missing leaf data: epv_set_unobserved over the whole genome, unobserved[(b-1)*n_sites + s] (all n_sites
+ * columns also under epvd_create_rank: each process takes its own window).  Kept across epvd_reset_model
+ * and applied to the contexts of every later epvd_reset, whose genome must have n_sites columns and
+ * n_nodes nodes; NULL clears */
+int epvd_set_unobserved(epvd_sampler *s, uint64_t n_sites, int n_nodes, const uint8_t *unobserved);
 
 /* the average history of the sampled paths (epv_set_path_average on every context; 0 = off; kept
  * across epvd_reset, which starts the counts from zero), and its counts over the sites of this process
