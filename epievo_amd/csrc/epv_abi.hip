@@ -145,6 +145,10 @@ struct epv_ctx {
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
   uint64_t unobs_cells = 0;
+  // leaf cells that carry evidence instead of data (epv_set_leaf_evidence), allocated while
+  // evidence_cells > 0: the layout of epv_leaf_evidence (epv_kernels.h)
+  uint32_t *d_evidence = nullptr;
+  uint64_t evidence_cells = 0;
 };
 
 namespace {
@@ -211,6 +215,8 @@ void free_paths(epv_ctx *c) {
   c->partial_cap[0] = c->partial_cap[1] = 0;
   dfree(c->d_unobs);   // new paths are new data
   c->unobs_cells = 0;
+  dfree(c->d_evidence);
+  c->evidence_cells = 0;
   c->have_paths = c->have_reset = false;
 }
 
@@ -734,10 +740,11 @@ struct PhasePlan {
   bool listed;           // the accept stage reads the listed sites
   bool meta_cache;       // (accept and fused kernels) the LDS meta cache
   bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
+  bool evidence;         // a leaf cell carries evidence: V1 takes the template that reads the table
   uint32_t word() const {
     return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
            p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16 |
-           (unobs ? 1u : 0u) << 17;
+           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18;
   }
 };
 PhasePlan phase_plan(const epv_ctx *c) {
@@ -746,11 +753,13 @@ PhasePlan phase_plan(const epv_ctx *c) {
   P.refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
   // unobserved leaf cells: only the first kernel marginalises them
   P.unobs = c->unobs_cells != 0u;
+  // leaf evidence: the same rule
+  P.evidence = c->evidence_cells != 0u;
   // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
   // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
   // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us)
-  const bool p3 = c->p3 && !P.refq && !P.unobs;
-  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !c->p2_gpool;
+  const bool p3 = c->p3 && !P.refq && !P.unobs && !P.evidence;
+  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !P.evidence && !c->p2_gpool;
   P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
   if (p2 && c->fused) {
     P.propose = EPV_PLAN_FUSED;
@@ -855,16 +864,27 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     ++c->phase_parity;
   } else {
     if (P.gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
-    if (P.unobs) {
-      using M = const uint32_t *;
-      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, true, M> : epv_mh_propose_kernel<true, false, true, M>)
-                          : (P.refq ? epv_mh_propose_kernel<false, true, true, M> : epv_mh_propose_kernel<false, false, true, M>);
+    using M = const uint32_t *;
+    if (P.evidence) {
+      // (the mask rides along where one is held: a cell without evidence follows it)
+      constexpr int E = EPV_LEAF_EVIDENCE;
+      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, E, M, M> : epv_mh_propose_kernel<true, false, E, M, M>)
+                          : (P.refq ? epv_mh_propose_kernel<false, true, E, M, M> : epv_mh_propose_kernel<false, false, E, M, M>);
+      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
+                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
+                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr, (M)c->d_evidence,
+                         (M)c->d_unobs);
+    } else if (P.unobs) {
+      constexpr int U = EPV_LEAF_MASK;
+      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, U, M> : epv_mh_propose_kernel<true, false, U, M>)
+                          : (P.refq ? epv_mh_propose_kernel<false, true, U, M> : epv_mh_propose_kernel<false, false, U, M>);
       hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
                          (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
                          c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr, (M)c->d_unobs);
     } else {
-      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, false> : epv_mh_propose_kernel<true, false, false>)
-                          : (P.refq ? epv_mh_propose_kernel<false, true, false> : epv_mh_propose_kernel<false, false, false>);
+      constexpr int D = EPV_LEAF_DATA;
+      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, D> : epv_mh_propose_kernel<true, false, D>)
+                          : (P.refq ? epv_mh_propose_kernel<false, true, D> : epv_mh_propose_kernel<false, false, D>);
       hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
                          (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
                          c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr);
@@ -1007,14 +1027,18 @@ EPV_API epv_ctx *epv_create(int device_id) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn)),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const void *v1[] = {
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, false>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, false>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, false>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, false>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, true, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, true, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, true, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, true, const uint32_t *>)};
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_DATA>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_DATA>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_DATA>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_DATA>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_MASK, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_MASK, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_MASK, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_MASK, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
+      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>)};
   for (const void *k : v1) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return c;
 }
@@ -1050,11 +1074,13 @@ EPV_API int epv_set_tree(epv_ctx *c, int n_nodes, const uint32_t *parent_ids,
         !(branches[i] > 0.0))
       return fail(c, EPV_ERR_ARG, "tree arrays are not a valid pre-order tree with positive branches");
   HIP_TRY(c, hipSetDevice(c->device));
-  // the mask of unobserved cells holds rows for the leaves of the tree it was set on
-  if (c->d_unobs && !std::equal(c->subtree.begin(), c->subtree.end(), subtree_sizes)) {
+  // the mask of unobserved cells and the evidence table hold rows for the leaves of the tree they were set on
+  if ((c->d_unobs || c->d_evidence) && !std::equal(c->subtree.begin(), c->subtree.end(), subtree_sizes)) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     dfree(c->d_unobs);
     c->unobs_cells = 0;
+    dfree(c->d_evidence);
+    c->evidence_cells = 0;
   }
   c->parent.assign(parent_ids, parent_ids + n_nodes);
   c->subtree.assign(subtree_sizes, subtree_sizes + n_nodes);
@@ -1349,6 +1375,60 @@ EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
 EPV_API int epv_unobserved_cells(epv_ctx *c, uint64_t *n_cells) {
   if (!c || !n_cells) return EPV_ERR_ARG;
   *n_cells = c->unobs_cells;
+  return EPV_OK;
+}
+
+EPV_API int epv_set_leaf_evidence(epv_ctx *c, const float *p_state1) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_leaf_evidence");
+  const uint32_t N = c->S.N;
+  const uint64_t n = c->S.n;
+  uint64_t cells = 0;
+  uint32_t leaves = 0;
+  for (uint32_t node = 1; node < N; ++node) {
+    const bool leaf = c->subtree[node] == 1u;
+    leaves += leaf ? 1u : 0u;
+    if (!p_state1) continue;
+    const float *row = p_state1 + (uint64_t)(node - 1u) * n;
+    for (uint64_t s = 0; s < n; ++s) {
+      const float r = row[s];
+      if (r != r) continue;   // NaN: no evidence
+      if (!leaf)
+        return fail(c, EPV_ERR_ARG, "leaf evidence on branch " + std::to_string(node) + " at site " + std::to_string(s) +
+                                        ": the branch does not end in a leaf (internal nodes are latent already)");
+      if (!(r >= 0.0f && r <= 1.0f))
+        return fail(c, EPV_ERR_ARG, "leaf evidence on branch " + std::to_string(node) + " at site " + std::to_string(s) +
+                                        " is " + std::to_string(r) + ": a probability in [0, 1] or NaN is needed");
+      ++cells;
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (a queued phase may still read the old table)
+  dfree(c->d_evidence);
+  c->evidence_cells = 0;
+  if (!cells) return EPV_OK;   // no evidence: today's kernels, no allocation
+  // the layout of epv_leaf_evidence: N words of row offsets, then one row of n float32 per leaf
+  const uint64_t words = N + (uint64_t)leaves * n;
+  if (words > 0xffffffffull) return fail(c, EPV_ERR_ARG, "table of leaf evidence too large for 32-bit row offsets");
+  std::vector<uint32_t> h(words, 0u);
+  uint64_t at = N;
+  for (uint32_t node = 1; node < N; ++node) {
+    if (c->subtree[node] != 1u) continue;
+    h[node] = (uint32_t)at;
+    std::memcpy(h.data() + at, p_state1 + (uint64_t)(node - 1u) * n, n * sizeof(float));
+    at += n;
+  }
+  DevTmp<uint32_t> d;
+  HIP_TRY(c, d.alloc(words));
+  HIP_TRY(c, hipMemcpy(d.p, h.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->d_evidence = d.release();
+  c->evidence_cells = cells;
+  return EPV_OK;
+}
+
+EPV_API int epv_leaf_evidence_cells(epv_ctx *c, uint64_t *n_cells) {
+  if (!c || !n_cells) return EPV_ERR_ARG;
+  *n_cells = c->evidence_cells;
   return EPV_OK;
 }
 

@@ -426,6 +426,21 @@ __device__ __forceinline__ bool epv_unobserved(const uint32_t *mask, uint32_t no
   return (mask[(uint64_t)mask[node] + (site >> 5)] >> (site & 31u)) & 1u;
 }
 
+// the table of leaf evidence as epv_set_leaf_evidence lays it out on the device (32-bit words): word
+// `node` (< N) holds the offset of the node's row, rows follow the N-word header, one per leaf, and
+// row word s is the float32 r of local site s: P(state 1 | the cell's own observation), NaN = none.
+// Offsets count words: the 64-leaf tree at n = 1e7 needs 6.4e8 of the 2^32 they reach.
+__device__ __forceinline__ float epv_leaf_evidence(const uint32_t *table, uint32_t node, uint64_t site) {
+  return __uint_as_float(table[(uint64_t)table[node] + site]);
+}
+
+// how epv_mh_propose_kernel sets a leaf's Felsenstein vector, and the trailing arguments of each mode
+#define EPV_LEAF_DATA 0       /* the indicator of the path's end state; none */
+#define EPV_LEAF_MASK 1       /* ... or (1, 1) where the mask flags the cell; (mask) */
+#define EPV_LEAF_EVIDENCE 2   /* ... or (1 - r, r) where the table holds r; (table, mask or nullptr) */
+template <class A, class... Rest> __device__ __forceinline__ A epv_first_arg(A a, Rest...) { return a; }
+template <class A, class Z> __device__ __forceinline__ Z epv_second_arg(A, Z z) { return z; }
+
 // GPOOL = false: the record pool lives in LDS (short trees: ~13 KB per wave, 12 waves/CU).
 // GPOOL = true : the pool is a per-block slab in global memory with the very same indexing.
 //   On a large tree the pool alone (64 lanes x (N-1) branches x ~2 records x 16 B = 84 KB for
@@ -445,19 +460,27 @@ __device__ __forceinline__ bool epv_unobserved(const uint32_t *mask, uint32_t no
 //   (<= 2e-12 over millions of updates, tests/test_proposal_ratio.py), and both modes produce
 //   the same paths.  The default; the kernel then needs no log, no current-path walk and no
 //   prop_llr hand-over.
-// UNOBS = true: leaf cells flagged in the context's mask of unobserved cells (epv_set_unobserved:
+// LEAF (EPV_LEAF_*) says what a leaf's q starts from; EPV_LEAF_DATA is the reference's indicator.
+// LEAF = EPV_LEAF_MASK (UNOBS below): leaf cells flagged in the context's mask of unobserved cells (epv_set_unobserved:
 //   missing leaf data) are marginalised: the leaf's q is (1, 1) instead of the indicator of its end
 //   state, so the downward pass draws that end state from its conditional law like any other.  The
 //   proposal is still f_mid(path) / Z with Z a function of the neighbours and the OBSERVED data, so
 //   the telescoping argument above and both REFQ modes hold unchanged.  The mask (epv_unobserved) is
 //   the one trailing argument only these instantiations take: the others keep their argument layout
 //   and so their instruction stream.
-template <bool GPOOL, bool REFQ, bool UNOBS, class... Unobs>
+// LEAF = EPV_LEAF_EVIDENCE: a leaf cell may carry r = P(state 1 | its own observation) under a flat prior
+//   (epv_set_leaf_evidence; NaN = none).  Its q is then (1 - r, r) in fp64, not normalised: r = 0 and
+//   r = 1 are the indicator bit for bit, r = 0.5 is the mask's (1, 1) times 2^-1, which cancels in every
+//   quotient below, and the larger entry is >= 0.5, so no partial underflows.  The argument is UNOBS's:
+//   Z depends on the neighbours and the evidence, not on the path.  A cell without r follows the mask,
+//   the second trailing argument (nullptr = no mask held), and is data otherwise.
+template <bool GPOOL, bool REFQ, int LEAF, class... Leaf>
 __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
     uint64_t first, uint64_t last, uint32_t pool_entries, unsigned long long *counters,
-    double *gpool, Unobs... unobs) {
-  static_assert(sizeof...(Unobs) == (UNOBS ? 1u : 0u), "the mask of unobserved cells comes with UNOBS");
+    double *gpool, Leaf... leaf_args) {
+  constexpr bool UNOBS = LEAF == EPV_LEAF_MASK;
+  static_assert(sizeof...(Leaf) == (size_t)LEAF, "the mask comes with EPV_LEAF_MASK, the table and the mask with EPV_LEAF_EVIDENCE");
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   double *s_const = s_mem;                     // 20 + N doubles (padded to even)
   const uint32_t const_dbl = (20u + S.N + 1u) & ~1u;
@@ -518,12 +541,24 @@ __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
         double q0 = 1.0, q1 = 1.0;
         const uint32_t sub = S.subtree[node];
         if (sub == 1u) {
+          [[maybe_unused]] float ev_r = 0.0f;
+          [[maybe_unused]] bool ev_unobs = false;
+          if constexpr (LEAF == EPV_LEAF_EVIDENCE) {
+            // (addresses of node and site only: in flight together with the meta load below)
+            ev_r = epv_leaf_evidence(epv_first_arg(leaf_args...), node, site);
+            const uint32_t *mask = epv_second_arg(leaf_args...);
+            if (mask) ev_unobs = epv_unobserved(mask, node, site);
+          }
           const uint32_t mM = S.meta[meta_idx(S, selM, b, site)];
           const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
           q0 = leaf_state ? 0.0 : 1.0;
           q1 = leaf_state ? 1.0 : 0.0;
           if constexpr (UNOBS) {
-            if (epv_unobserved(unobs..., node, site)) { q0 = 1.0; q1 = 1.0; }
+            if (epv_unobserved(leaf_args..., node, site)) { q0 = 1.0; q1 = 1.0; }
+          }
+          if constexpr (LEAF == EPV_LEAF_EVIDENCE) {
+            if (ev_r == ev_r) { q1 = (double)ev_r; q0 = 1.0 - (double)ev_r; }   // (not NaN)
+            else if (ev_unobs) { q0 = 1.0; q1 = 1.0; }
           }
         } else {
           for (uint32_t ch = 1u; ch < sub; ch += S.subtree[node + ch]) {

@@ -8,6 +8,9 @@
 // (average_paths.cpp:49-63), without writing the samples to files.
 // New: -m/--missing STATES_FILE: leaf cells marked N there are unobserved (SingleSiteSampler::set_unobserved):
 // the MCMC resamples their end states instead of pinning them; the other cells must agree with the paths.
+// New: -l/--leaf-probs FILE: a file of the same shape with P(state 1) per leaf cell (N = 0.5): cells with a
+// probability strictly between 0 and 1 carry evidence (SingleSiteSampler::set_leaf_evidence) and are resampled;
+// 0 and 1 are data and must agree with the paths.  Not together with -m.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -32,7 +35,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     size_t rng_seed = std::numeric_limits<size_t>::max();
 
@@ -50,6 +53,8 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("npoints", 'n', "number of time points per branch of the average", false, n_points);
     opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data: resampled, not pinned", false,
                       missing_file);
+    opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell (N = 0.5): evidence, resampled; 0 and 1 are data",
+                      false, leaf_probs_file);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -80,12 +85,21 @@ int main(int argc, const char **argv) {
     epv::FlatPaths paths;
     epv::Tree th;
     epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
+    if (!missing_file.empty() && !leaf_probs_file.empty())
+      throw std::runtime_error("-m/--missing and -l/--leaf-probs cannot be given together (N in a -l file is a missing cell)");
     // missing leaf data, checked against the paths before any GPU call
     vector<uint8_t> unobserved;
     if (!missing_file.empty()) {
       uint64_t n_unobserved = 0, n_leaf_cells = 0;
       unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
       if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+    }
+    // leaf evidence, likewise
+    vector<float> evidence;
+    if (!leaf_probs_file.empty()) {
+      uint64_t n_evidence = 0, n_leaf_cells = 0;
+      evidence = epv::leaf_evidence_cells(leaf_probs_file, th, paths, n_evidence, n_leaf_cells);
+      if (VERBOSE) cerr << "[LEAF CELLS WITH EVIDENCE: " << n_evidence << " of " << n_leaf_cells << "]" << endl;
     }
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
@@ -97,6 +111,7 @@ int main(int argc, const char **argv) {
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
+    if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
     mcmc.reset(the_model, th, paths);
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);

@@ -9,6 +9,8 @@
 // rehearses a multi-GPU run on fewer GPUs.
 // Another: -m/--missing STATES_FILE -- leaf cells marked N there are missing data, resampled in every
 // E-step instead of pinned (SingleSiteSampler::set_unobserved; kept across the iterations).
+// And: -l/--leaf-probs FILE -- P(state 1) per leaf cell in a file of the same shape (N = 0.5); cells strictly
+// between 0 and 1 carry evidence in every E-step (SingleSiteSampler::set_leaf_evidence).  Not together with -m.
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -37,7 +39,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false, optimize_branches = false;
-    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file;
+    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file, leaf_probs_file;
     size_t iteration = 10, batch = 10, burnin = 10, paths_every = 1;
     size_t rng_seed = std::numeric_limits<size_t>::max();
     static const double param_tol = 1e-10;
@@ -61,6 +63,8 @@ int main(int argc, const char **argv) {
     // file is the same bytes, the ones in between are not written
     opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data: resampled, not pinned", false,
                       missing_file);
+    opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell (N = 0.5): evidence, resampled; 0 and 1 are data",
+                      false, leaf_probs_file);
     opt_parse.add_opt("paths-every", 'e', "write the paths file every k-th iteration and after the last (default 1: "
                       "every iteration, as the reference does)", false, paths_every);
     vector<string> leftover_args;
@@ -92,12 +96,21 @@ int main(int argc, const char **argv) {
     epv::FlatPaths paths;
     epv::Tree th;
     epv::load_paths_and_tree(input_file, tree_file, single_branch, VERBOSE, paths, node_names, th);
+    if (!missing_file.empty() && !leaf_probs_file.empty())
+      throw std::runtime_error("-m/--missing and -l/--leaf-probs cannot be given together (N in a -l file is a missing cell)");
     // missing leaf data, checked against the paths before any GPU call
     vector<uint8_t> unobserved;
     if (!missing_file.empty()) {
       uint64_t n_unobserved = 0, n_leaf_cells = 0;
       unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
       if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+    }
+    // leaf evidence, likewise
+    vector<float> evidence;
+    if (!leaf_probs_file.empty()) {
+      uint64_t n_evidence = 0, n_leaf_cells = 0;
+      evidence = epv::leaf_evidence_cells(leaf_probs_file, th, paths, n_evidence, n_leaf_cells);
+      if (VERBOSE) cerr << "[LEAF CELLS WITH EVIDENCE: " << n_evidence << " of " << n_leaf_cells << "]" << endl;
     }
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
@@ -121,6 +134,7 @@ int main(int argc, const char **argv) {
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
+    if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
     // declared AFTER everything the thread references (and after the sampler): on an exception the
     // join runs first, while out_paths, out_branches and writer_error are still alive, and the file
     // of the last completed iteration is written out in full, as the synchronous reference leaves it

@@ -159,6 +159,14 @@ EPVD_API int epvd_set_unobserved(epvd_sampler *h, uint64_t n_sites, int n_nodes,
   });
 }
 
+EPVD_API int epvd_set_leaf_evidence(epvd_sampler *h, uint64_t n_sites, int n_nodes, const float *p_state1) {
+  return guarded(h, [&] {
+    std::vector<float> r;
+    if (p_state1) r.assign(p_state1, p_state1 + (uint64_t)(n_nodes - 1) * n_sites);
+    h->s->set_leaf_evidence(std::move(r));
+  });
+}
+
 EPVD_API int epvd_set_path_average(epvd_sampler *h, uint32_t n_points) {
   return guarded(h, [&] { h->s->set_path_average(n_points); });
 }

@@ -536,6 +536,78 @@ std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const
   return mask;
 }
 
+void read_leaf_probs_file(const std::string &probs_file, std::vector<std::string> &names,
+                          std::vector<std::vector<float>> &probs) {
+  std::ifstream in(probs_file);
+  if (!in) throw std::runtime_error("cannot read leaf probabilities file: " + probs_file);
+  std::string line;
+  std::getline(in, line);
+  if (!line.empty() && line[0] == '#') line = line.substr(1);
+  std::istringstream hs(line);
+  std::string nm;
+  while (hs >> nm) names.push_back(nm);
+  probs.assign(names.size(), {});
+  std::string tok;
+  while (std::getline(in, line)) {
+    std::istringstream ls(line);
+    size_t site = 0;
+    ls >> site;
+    size_t k = 0;
+    for (; k < names.size() && ls >> tok; ++k) {
+      float r = std::numeric_limits<float>::infinity();   // (what no valid token gives)
+      if (tok == "N" || tok == "n") {
+        r = 0.5f;
+      } else {
+        char *end = nullptr;
+        const double v = std::strtod(tok.c_str(), &end);
+        if (end != tok.c_str() && *end == '\0' && v >= 0.0 && v <= 1.0) r = (float)v;
+      }
+      probs[k].push_back(r);
+    }
+    if (k != names.size()) throw std::runtime_error("bad line in leaf probabilities file");
+  }
+}
+
+std::vector<float> leaf_evidence_cells(const std::string &probs_file, const Tree &th, const FlatPaths &paths,
+                                       uint64_t &n_evidence, uint64_t &n_leaf_cells) {
+  std::vector<std::string> names;
+  std::vector<std::vector<float>> probs;
+  read_leaf_probs_file(probs_file, names, probs);
+  const uint64_t n = paths.n_sites, N = (uint64_t)th.n_nodes();
+  std::vector<float> table((N - 1u) * n, std::numeric_limits<float>::quiet_NaN());
+  n_evidence = n_leaf_cells = 0;
+  for (uint64_t node = 1; node < N; ++node) {
+    if (!th.is_leaf((int)node)) continue;   // (columns of internal nodes are not data: ignored)
+    const std::string &leaf = th.node_names[node];
+    const size_t k = std::find(names.begin(), names.end(), leaf) - names.begin();
+    if (k == names.size())
+      throw std::runtime_error("leaf probabilities file " + probs_file + " has no column for leaf " + leaf);
+    if (probs[k].size() != n)
+      throw std::runtime_error("leaf probabilities file " + probs_file + " has " + std::to_string(probs[k].size()) +
+                               " sites, the paths " + std::to_string(n));
+    for (uint64_t s = 0; s < n; ++s) {
+      const uint64_t e = (node - 1u) * n + s;
+      const float r = probs[k][s];
+      if (!(r >= 0.0f && r <= 1.0f))
+        throw std::runtime_error("leaf probabilities file " + probs_file + ": leaf " + leaf + " at site " +
+                                 std::to_string(s) + " is neither a probability in [0, 1] nor N");
+      if (r != 0.0f && r != 1.0f) {
+        table[e] = r;
+        ++n_evidence;
+        continue;
+      }
+      // exactly 0 or 1 is data: it stays pinned (no table entry) and must be what the paths hold
+      const uint32_t end = paths.init[e] ^ (uint32_t)((paths.offsets[e + 1] - paths.offsets[e]) & 1u);
+      if (end != (r == 1.0f ? 1u : 0u))
+        throw std::runtime_error("leaf probabilities file " + probs_file + ": leaf " + leaf + " at site " +
+                                 std::to_string(s) + " is " + std::to_string(r == 1.0f ? 1 : 0) +
+                                 ", the input paths end in " + std::to_string(end));
+    }
+    n_leaf_cells += n;
+  }
+  return table;
+}
+
 }  // namespace epv
 
 namespace epv {

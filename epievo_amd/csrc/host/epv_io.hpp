@@ -77,6 +77,17 @@ void read_states_file_missing(const std::string &states_file, std::vector<std::s
 // site.  Throws, naming leaf and site, where an observed cell differs from the paths' leaf end state.
 std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const Tree &th, const FlatPaths &paths,
                                            uint64_t &n_unobserved, uint64_t &n_leaf_cells);
+// a file of the same shape whose tokens are probabilities of state 1: a real number in [0, 1], or `N`/`n` for
+// no information (0.5).  probs[seq][site]; any other token is stored as +infinity
+void read_leaf_probs_file(const std::string &probs_file, std::vector<std::string> &names,
+                          std::vector<std::vector<float>> &probs);
+// -l/--leaf-probs of the E-step programs: the whole-genome table of SingleSiteSampler::set_leaf_evidence over
+// `paths` ([(b-1) * n_sites + site], NaN = none).  Columns and rows are matched as unobserved_leaf_cells does.
+// A token that is exactly 0 or 1 as a float32 is data: it gets no entry (the cell stays pinned) and must agree
+// with the paths' leaf end state.  Throws, naming leaf and site, where it does not, or where a token of a leaf
+// column is not a probability.  n_evidence counts the entries set.
+std::vector<float> leaf_evidence_cells(const std::string &probs_file, const Tree &th, const FlatPaths &paths,
+                                       uint64_t &n_evidence, uint64_t &n_leaf_cells);
 
 }  // namespace epv
 

@@ -436,7 +436,38 @@ void SingleSiteSampler::apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi) {
   check_on(c, epv_set_unobserved(c, win.data()), "epv_set_unobserved");
 }
 
+void SingleSiteSampler::set_leaf_evidence(std::vector<float> whole_genome) {
+  bool any = false;
+  for (float r : whole_genome) any = any || r == r;
+  if (!any) whole_genome.clear();
+  if (n_sites_ && !whole_genome.empty() && whole_genome.size() != (uint64_t)(n_nodes_ - 1) * n_sites_)
+    throw std::runtime_error("table of leaf evidence: " + std::to_string(whole_genome.size()) + " entries for " +
+                             std::to_string(n_nodes_ - 1) + " branches x " + std::to_string(n_sites_) + " sites");
+  evidence_ = std::move(whole_genome);
+  if (!n_sites_) return;   // no paths yet: the reset that uploads them applies it
+  if (!sharded()) {
+    apply_leaf_evidence(ctx_, 0, n_sites_);
+    return;
+  }
+  for (const Part &p : parts_) apply_leaf_evidence(p.ctx, p.lo, p.hi);
+}
+
+void SingleSiteSampler::apply_leaf_evidence(epv_ctx *c, uint64_t lo, uint64_t hi) {
+  if (evidence_.empty()) {
+    check_on(c, epv_set_leaf_evidence(c, nullptr), "epv_set_leaf_evidence");
+    return;
+  }
+  const uint64_t B = (uint64_t)n_nodes_ - 1u, w = hi - lo;
+  std::vector<float> win(B * w);
+  for (uint64_t b = 0; b < B; ++b)
+    std::copy(evidence_.begin() + b * n_sites_ + lo, evidence_.begin() + b * n_sites_ + hi, win.begin() + b * w);
+  check_on(c, epv_set_leaf_evidence(c, win.data()), "epv_set_leaf_evidence");
+}
+
 void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n, bool rank_mode) {
+  if (!evidence_.empty() && evidence_.size() != (uint64_t)(th.n_nodes() - 1) * n)
+    throw std::runtime_error("table of leaf evidence: " + std::to_string(evidence_.size()) + " entries for " +
+                             std::to_string(th.n_nodes() - 1) + " branches x " + std::to_string(n) + " sites");
   if (!unobs_.empty() && unobs_.size() != (uint64_t)(th.n_nodes() - 1) * n)
     throw std::runtime_error("mask of unobserved cells: " + std::to_string(unobs_.size()) + " entries for " +
                              std::to_string(th.n_nodes() - 1) + " branches x " + std::to_string(n) + " sites");
@@ -475,6 +506,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
     check(epv_upload_paths(ctx_, paths.n_sites, paths.init.data(), paths.offsets.data(),
                            paths.jumps.data(), capacity_, 0), "epv_upload_paths");
     if (!unobs_.empty()) apply_unobserved(ctx_, 0, n);
+    if (!evidence_.empty()) apply_leaf_evidence(ctx_, 0, n);
     return;
   }
   uint32_t cap = capacity_;
@@ -528,6 +560,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
     check_on(c, epv_upload_paths(c, part.n_sites, part.init.data(), part.offsets.data(),
                                  part.jumps.empty() ? &dummy : part.jumps.data(), cap, q.lo), "epv_upload_paths");
     if (!unobs_.empty()) apply_unobserved(c, q.lo, q.hi);   // (its window of the genome, halos included)
+    if (!evidence_.empty()) apply_leaf_evidence(c, q.lo, q.hi);
     check_on(c, epv_set_global_length(c, n), "epv_set_global_length");
   }
   if (rank_mode) {

@@ -117,6 +117,10 @@ public:
   // now if paths are resident, and to the window of every part a later reset(model, tree, paths) makes
   // (which throws when the length does not match its genome); reset(model) keeps it.  Empty = clear.
   void set_unobserved(std::vector<uint8_t> whole_genome);
+  // leaf evidence (epv_set_leaf_evidence): whole_genome[(b-1) * n_sites + s] = P(leaf end state of branch b at
+  // genome site s is 1 | that cell's observation), NaN = none.  Stored, sliced, re-applied and length-checked
+  // exactly as set_unobserved's mask; empty or all NaN = clear.
+  void set_leaf_evidence(std::vector<float> whole_genome);
   void set_timing(int every);
   void kernel_time_ms(double &avg_ms, uint64_t &n_launches);
   uint32_t phase_mode();
@@ -174,6 +178,7 @@ private:
   void refresh_parts();       // equal capacities, halo columns of every inner edge, fresh halo marks
   void apply_sample_root();
   void apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi);   // unobs_ columns [lo, hi) of the genome
+  void apply_leaf_evidence(epv_ctx *c, uint64_t lo, uint64_t hi);   // evidence_ columns [lo, hi) of the genome
   void build(const Tree &th, const FlatPaths &paths, uint64_t n_global, bool rank_mode);
   std::vector<epv_ctx *> contexts() const;
   void equalize_capacity();
@@ -192,6 +197,7 @@ private:
   uint32_t pa_points_ = 0;    // set_path_average
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
+  std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none
   int n_nodes_ = 0;
   uint64_t n_sites_ = 0;      // genome length (all slots)
   size_t world_ = 1;          // slots of the run (== slots_.size() unless one slot per process)

@@ -15,7 +15,7 @@ vp, dp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8
 DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_destroy", "epvd_last_error", "epvd_shard_cuts",
                   "epvd_reset", "epvd_reset_model", "epvd_run_mcmc", "epvd_scale_jump_times", "epvd_download_sizes",
                   "epvd_download", "epvd_layout", "epvd_set_options", "epvd_set_timing", "epvd_kernel_time_ms",
-                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average"]
+                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average"]
 
 
 def lib():
@@ -45,6 +45,7 @@ def lib():
         L.epvd_kernel_time_ms.argtypes = [vp, dp, u64p]
         L.epvd_phase_mode.argtypes = [vp, u32p]
         L.epvd_set_unobserved.argtypes = [vp, C.c_uint64, C.c_int, u8p]
+        L.epvd_set_leaf_evidence.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_float)]
         L.epvd_set_path_average.argtypes = [vp, C.c_uint32]
         L.epvd_path_average_sizes.argtypes = [vp, u64p, u32p, u64p]
         L.epvd_download_path_average.argtypes = [vp, u32p]
@@ -171,6 +172,22 @@ class CppSampler:
             m = m.reshape(self.B, -1)
         m = np.ascontiguousarray(m != 0, np.uint8)
         self._ck(self.L.epvd_set_unobserved(self.h, m.shape[1], m.shape[0] + 1, _p(m, C.c_uint8)))
+
+    def set_leaf_evidence(self, p_state1):
+        """leaf evidence over the whole genome (epvd_set_leaf_evidence): p_state1[b-1, s] = P(the leaf end state
+        of branch b at site s is 1 | that cell's own observation), float32, NaN = none.  Shape
+        (n_nodes - 1, n_sites), or flat once reset() has set the tree; None clears.  Kept and applied as
+        set_unobserved's mask is."""
+        if p_state1 is None:
+            self._ck(self.L.epvd_set_leaf_evidence(self.h, 0, 0, None))
+            return
+        r = np.asarray(p_state1, np.float32)
+        if r.ndim == 1:
+            if not self.B:
+                raise ValueError("a flat table needs the tree: pass shape (n_nodes - 1, n_sites) before reset()")
+            r = r.reshape(self.B, -1)
+        r = np.ascontiguousarray(r)
+        self._ck(self.L.epvd_set_leaf_evidence(self.h, r.shape[1], r.shape[0] + 1, _p(r, C.c_float)))
 
     def enable_path_average(self, n_points):
         """the average history of the sampled paths on every context (0 = off); kept across reset()"""

@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan", "epv_set_unobserved", "epv_unobserved_cells",
+    "epv_phase_plan", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -116,6 +116,8 @@ def lib():
         L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_set_unobserved.argtypes = [vp, u8p]
         L.epv_unobserved_cells.argtypes = [vp, u64p]
+        L.epv_set_leaf_evidence.argtypes = [vp, C.POINTER(C.c_float)]
+        L.epv_leaf_evidence_cells.argtypes = [vp, u64p]
         L.epv_dev_write.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_dev_read.argtypes = [vp, vp, vp, C.c_uint64]
         L.epv_get_counters.argtypes = [vp, C.POINTER(_Counters)]
@@ -228,7 +230,7 @@ class DeviceSampler:
         return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
                     small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
                     jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
-                    unobs=bool(w >> 17 & 1))
+                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1))
 
     def set_unobserved(self, mask):
         """missing leaf data (epv_set_unobserved): mask[b-1, s] != 0 -> the leaf end state of branch b at
@@ -249,6 +251,27 @@ class DeviceSampler:
         """the number of leaf cells flagged unobserved (epv_unobserved_cells)"""
         v = C.c_uint64(0)
         self._ck(self.L.epv_unobserved_cells(self.h, C.byref(v)))
+        return int(v.value)
+
+    def set_leaf_evidence(self, p_state1):
+        """leaf evidence (epv_set_leaf_evidence): p_state1[b-1, s] = P(the leaf end state of branch b at local
+        site s is 1 | that cell's own observation), float32, NaN = none.  Such a cell is resampled with the
+        history from the leaf vector (1 - r, r); r = 0 or 1 is data, r = 0.5 an unobserved cell.  Shape
+        (n_nodes - 1, n_sites) or flat in that order, halo columns included; None clears.  Non-NaN entries
+        are allowed on leaf branches only; they win over the mask.  Uploading paths clears the table."""
+        if p_state1 is None:
+            self._ck(self.L.epv_set_leaf_evidence(self.h, None))
+            return
+        r = np.ascontiguousarray(p_state1, np.float32).reshape(-1)
+        if r.size != self.B * self.n_sites:
+            raise ValueError("table of leaf evidence: %d entries for %d branches x %d sites"
+                             % (r.size, self.B, self.n_sites))
+        self._ck(self.L.epv_set_leaf_evidence(self.h, _p(r, C.c_float)))
+
+    def leaf_evidence_cells(self):
+        """the number of leaf cells that hold evidence (epv_leaf_evidence_cells)"""
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_leaf_evidence_cells(self.h, C.byref(v)))
         return int(v.value)
 
     def capacity(self):
@@ -515,6 +538,7 @@ class SingleSiteSampler:
         self.dev.auto_grow = True     # paths grow on demand, as the reference's vectors do
         self._uploaded = False
         self._unobserved = None       # the mask of unobserved leaf cells, re-applied after every upload
+        self._leaf_evidence = None    # the table of leaf evidence, likewise
 
     def _apply_sample_root(self):
         flags = C.c_uint32(0)
@@ -531,6 +555,8 @@ class SingleSiteSampler:
             self._uploaded = True
             if self._unobserved is not None:
                 self.dev.set_unobserved(self._unobserved)
+            if self._leaf_evidence is not None:
+                self.dev.set_leaf_evidence(self._leaf_evidence)
         if not self._uploaded:
             raise EpvError(EPV_ERR_STATE, "reset() needs paths the first time")
         self._apply_sample_root()
@@ -545,6 +571,16 @@ class SingleSiteSampler:
             self._unobserved = (np.ascontiguousarray(mask).reshape(-1) != 0).astype(np.uint8)
         if self._uploaded:
             self.dev.set_unobserved(self._unobserved)
+
+    def set_leaf_evidence(self, p_state1):
+        """leaf evidence (DeviceSampler.set_leaf_evidence); kept across resets, re-applied to new paths.
+        None clears."""
+        if p_state1 is None:
+            self._leaf_evidence = None
+        else:
+            self._leaf_evidence = np.ascontiguousarray(p_state1, np.float32).reshape(-1).copy()
+        if self._uploaded:
+            self.dev.set_leaf_evidence(self._leaf_evidence)
 
     def run_mcmc(self, seed, em_iter=0):
         self._apply_sample_root()

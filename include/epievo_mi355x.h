@@ -144,7 +144,9 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *              _CACHE (epv_mh_accept_kernel with its LDS meta cache), _NO_CACHE (epv_mh_accept_kernel without)
  *   bit  16    the accept stage reads the listed sites (proposal kernels V2 and V3; 0 = every site of the colour)
  *   bit  17    V1: the template that marginalises unobserved leaf cells (epv_set_unobserved holds a cell;
- *              it forces V1 like bit 3 does) */
+ *              it forces V1 like bit 3 does)
+ *   bit  18    V1: the template that reads the table of leaf evidence (epv_set_leaf_evidence holds a cell;
+ *              it forces V1 too, and the mask of bit 17 rides along for the cells without evidence) */
 enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
 enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
@@ -164,6 +166,26 @@ int epv_phase_plan(epv_ctx *ctx, uint32_t *word);
  * epv_unobserved_cells: the number of flagged cells.  No reference counterpart. */
 int epv_set_unobserved(epv_ctx *ctx, const uint8_t *unobserved);
 int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
+
+/* Leaf evidence.  p_state1[(b-1)*n_sites + s] = r, a float32: the probability that the leaf end
+ * state of branch b at local site s is 1 given that cell's observation alone, under a flat prior;
+ * NaN = the cell has none.  The MCMC then starts Felsenstein pruning at that leaf from
+ * (q0, q1) = (1.0 - (double)r, (double)r), not normalised, and resamples the end state with the
+ * history.  r = 0 and r = 1 are data bit for bit; r = 0.5 gives the chain of an unobserved cell.
+ * A NaN cell is what it is without this call: data, or unobserved where epv_set_unobserved flags
+ * it; where both are given, a non-NaN r wins over the mask.  The node-major layout of
+ * epv_set_unobserved over all local columns, halos included; cells of the genome's two end sites
+ * are never updated, so their values have no effect.  NULL, or an array of NaN only, clears the
+ * table: then the plan and the results are those of a context that never had one.  A non-NaN value
+ * on a branch that does not end in a leaf, or one that is infinite or outside [0, 1], returns
+ * EPV_ERR_ARG naming branch and site; before paths are resident EPV_ERR_STATE.  The device holds
+ * one float32 per (leaf, site), and only while a cell is non-NaN.  What clears the mask clears the
+ * table (epv_upload_paths, epv_init_paths_indep, epv_forward_simulate, another tree); everything
+ * else keeps it.  While a cell holds evidence a colour phase takes the first proposal kernel
+ * (epv_phase_mode 0, plan bit 18).  epv_leaf_evidence_cells: the number of non-NaN cells.  No
+ * reference counterpart. */
+int epv_set_leaf_evidence(epv_ctx *ctx, const float *p_state1);
+int epv_leaf_evidence_cells(epv_ctx *ctx, uint64_t *n_cells);
 
 /* initialize_paths_indep (src/prog/epievo_sim_pairwise.cpp:62-110) on the device, for the
  * two-node tree of one branch (epv_set_tree with n_nodes = 2 and epv_set_model first):

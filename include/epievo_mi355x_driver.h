@@ -59,6 +59,9 @@ int epvd_phase_mode(epvd_sampler *s, uint32_t *mode);
  * and applied to the contexts of every later epvd_reset, whose genome must have n_sites columns and
  * n_nodes nodes; NULL clears */
 int epvd_set_unobserved(epvd_sampler *s, uint64_t n_sites, int n_nodes, const uint8_t *unobserved);
+/* leaf evidence: epv_set_leaf_evidence over the whole genome, p_state1[(b-1)*n_sites + s] (NaN = none), kept
+ * and applied exactly as epvd_set_unobserved's mask is; NULL clears */
+int epvd_set_leaf_evidence(epvd_sampler *s, uint64_t n_sites, int n_nodes, const float *p_state1);
 
 /* the average history of the sampled paths (epv_set_path_average on every context; 0 = off; kept
  * across epvd_reset, which starts the counts from zero), and its counts over the sites of this process
