@@ -709,6 +709,16 @@ __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
               seg_start = seg_end;
             }
           }
+          if constexpr (REFQ && LEAF == EPV_LEAF_EVIDENCE) {
+            // The target of the middle site carries the leaf's factor q[end state]; the cached
+            // likelihoods do not.  The sums above telescope to log q[end state] on either side, so
+            // q(old)/q(new) alone would divide the evidence out again (the chain would follow the
+            // mask's law): the target's share q[new end] / q[old end] joins the current path's sum
+            // here, where both end states and q (pk after the last segment) are at hand.  An exact 0
+            // for data, the mask and r = 0.5, and whenever the proposal keeps the leaf's state.
+            if (S.subtree[node] == 1u && prev != cs_end)
+              lp += epv_log(prev ? pk1 : pk0) - epv_log(cs_end ? pk1 : pk0);
+          }
           // only a dirty branch is ever read back (by epv_mh_jumps_kernel)
           if ((K & 63u) && !clean) states[(K - 1u) >> 6] = word;
           // proposal so far: no jumps; epv_mh_jumps_kernel fills dirty branches in

@@ -183,7 +183,23 @@ int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
  * table (epv_upload_paths, epv_init_paths_indep, epv_forward_simulate, another tree); everything
  * else keeps it.  While a cell holds evidence a colour phase takes the first proposal kernel
  * (epv_phase_mode 0, plan bit 18).  epv_leaf_evidence_cells: the number of non-NaN cells.  No
- * reference counterpart. */
+ * reference counterpart.
+ * The two ratio modes.  The target of a site carries the leaf factor q[end state].  The default mode
+ * needs nothing for it (the proposal carries the same factor and the ratio stays 1).  Under
+ * EPV_OPT_REFERENCE_PROPOSAL_RATIO and EPV_OPT_SAMPLE_ROOT the reference's two sums leave
+ * log q[end state] behind on either side, so the kernel adds the target's share
+ * log q[new end] - log q[old end] where a leaf with evidence changes state; with it both modes walk the
+ * same chain up to the rounding noise that mode always carries, ~1e-11 in the log ratio
+ * (tests/test_leaf_oracle.py).
+ * Precondition: a hard cell (r exactly 0 or 1) agrees with the end state of the resident path; the
+ * programs enforce it, this call does not look at the paths.  A cell that contradicts its path has
+ * target weight 0 where the chain stands.  Default mode: the ratio is taken as 1, the cell takes the
+ * evidence's state at its site's first accepted update and keeps it.  Reference-ratio mode: the sums are
+ * not finite there.  With r = 1 against state 0 the ratio is (-inf) + (+inf) = NaN and the site is never
+ * updated again; with r = 0 against state 1 the sum holds log(1 - p0) with p0 = 1 up to rounding, and the
+ * site is rejected (-inf, NaN) or accepted and repaired (+inf) as that rounding falls.  No NaN or
+ * infinity reaches the paths, tri_llh, J or D in either mode; the GPU decides bit for bit what the
+ * oracle's arithmetic decides (tests/test_leaf_matrix.py). */
 int epv_set_leaf_evidence(epv_ctx *ctx, const float *p_state1);
 int epv_leaf_evidence_cells(epv_ctx *ctx, uint64_t *n_cells);
 

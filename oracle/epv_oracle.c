@@ -36,6 +36,11 @@
  * the exp/log pair, the visiting order, the reduction order and that sampler
  * choice differ.
  *
+ * Without a reference counterpart: the leaf vector (leaf_vector below; orc_set_unobserved,
+ * orc_set_leaf_evidence).  A leaf cell may be unobserved or carry evidence r instead of data; both
+ * rungs start pruning() from the same vector, and with neither table held the code path is the
+ * reference's.  Held to the exact posterior in tests/test_leaf_oracle.py.
+ *
  * Path storage: node-major flat arrays, index (node*n_sites + site), node 0
  * (the root) unused -- as in the reference, where paths[site][0] is a dummy.
  */
@@ -118,6 +123,10 @@ typedef struct orc_state {
   int proposal_mode;       /* ORC_PROPOSAL_* */
   int sample_root;         /* SingleSiteSampler::SAMPLE_ROOT (hard-wired false in the reference, :441) */
   double max_qdiff;        /* max |proposal_prob(old) - proposal_prob(new)| seen (reference arithmetic) */
+  /* the leaf vector (orc_set_unobserved, orc_set_leaf_evidence): plain copies of the caller's arrays,
+   * [(node-1)*n_sites + site] over local sites; NULL = not held, and pruning() is then the reference's */
+  uint8_t *leaf_unobs;     /* != 0: the leaf cell is not data */
+  float *leaf_r;           /* P(state 1 | the cell's own observation); NaN = none */
 } orc_state;
 
 static double libm_exp(double x) { return exp(x); }
@@ -207,14 +216,38 @@ static inline double get_trans_prob(const orc_state *st, double r0, double r1, d
 }
 
 /* ------------------------------------------------------------- pruning */
+/* What Felsenstein pruning starts from at a leaf cell, (P(obs | state 0), P(obs | state 1)):
+ *   a cell with evidence r (not NaN)   (1 - r, r) in fp64, not normalised;
+ *   else a cell flagged unobserved     (1, 1);
+ *   else                               the indicator of the path's end state (SingleSiteSampler.cpp:121-125).
+ * The one place where the leaf tables are read: the downward pass and proposal_prob take q from the
+ * scratch pruning() fills. */
+static void leaf_vector(const orc_state *st, int node, size_t site, double *q0, double *q1) {
+  const size_t cell = (size_t)(node - 1) * st->n_sites + site;
+  if (st->leaf_r) {
+    const float r = st->leaf_r[cell];
+    if (r == r) { /* not NaN */
+      *q1 = (double)r;
+      *q0 = 1.0 - (double)r;
+      return;
+    }
+  }
+  if (st->leaf_unobs && st->leaf_unobs[cell]) {
+    *q0 = 1.0;
+    *q1 = 1.0;
+    return;
+  }
+  const int leaf_state = path_end_state(PATH(st, node, site));
+  *q0 = leaf_state ? 0.0 : 1.0;
+  *q1 = leaf_state ? 1.0 : 0.0;
+}
+
 /* SingleSiteSampler.cpp:80-157 */
 static void pruning(const orc_state *st, size_t site, orc_scratch *sc) {
   for (int node = st->n_nodes - 1; node >= 0; --node) {
     double q0 = 1.0, q1 = 1.0;
     if (is_leaf(st, node)) {
-      const int leaf_state = path_end_state(PATH(st, node, site));
-      q0 = leaf_state ? 0.0 : 1.0;
-      q1 = leaf_state ? 1.0 : 0.0;
+      leaf_vector(st, node, site, &q0, &q1);
     } else {
       /* children of `node` in pre-order: node+1, then skip subtrees */
       for (uint32_t ch = 1; ch < st->subtree[node]; ch += st->subtree[node + ch]) {
@@ -442,6 +475,18 @@ static double proposal_prob(const orc_state *st, size_t site, const orc_scratch 
       start_jump = end_jump;
       start_state = end_state;
     }
+    /* Leaf evidence: the target of the middle site carries the leaf's factor q[end state], which the
+     * cached likelihoods do not hold.  In the sums above it stays behind as log q[end state] (the terms
+     * telescope to it), so q(old)/q(new) alone would divide the evidence out again and the chain would
+     * follow the mask's law.  The target's share pi(new)/pi(old) = q[new end]/q[old end] is added here,
+     * where both end states are known; it is an exact 0 for data, for the mask and for r = 0.5, and
+     * whenever the proposal keeps the leaf's state.  (Called after downward_sampling: sc->prop is the
+     * proposal.) */
+    if (st->leaf_r && is_leaf(st, node)) {
+      const int new_end = path_end_state(&sc->prop[node]);
+      if (new_end != end_state)
+        lp += st->flog(new_end ? sc->q1[node] : sc->q0[node]) - st->flog(end_state ? sc->q1[node] : sc->q0[node]);
+    }
     log_prob += lp;
   }
   return log_prob;
@@ -636,7 +681,28 @@ ORC_API void orc_destroy(orc_state *st) {
   for (int t = 0; t < st->n_thr_scr; ++t) scratch_free(&st->thr_scr[t], st->n_nodes);
   free(st->thr_scr);
   free(st->paths); free(st->tri_llh); free(st->parent); free(st->subtree); free(st->blen);
+  free(st->leaf_unobs); free(st->leaf_r);
   free(st);
+}
+
+/* Unobserved leaf cells and leaf evidence, as epv_set_unobserved and epv_set_leaf_evidence take them:
+ * node-major [(node-1)*n_sites + site] over the local sites, rows of internal branches ignored.  The
+ * state keeps a copy; NULL drops it. */
+ORC_API void orc_set_unobserved(orc_state *st, const uint8_t *mask) {
+  const size_t cells = (size_t)(st->n_nodes - 1) * st->n_sites;
+  free(st->leaf_unobs);
+  st->leaf_unobs = NULL;
+  if (!mask) return;
+  st->leaf_unobs = (uint8_t *)malloc(cells);
+  memcpy(st->leaf_unobs, mask, cells);
+}
+ORC_API void orc_set_leaf_evidence(orc_state *st, const float *r) {
+  const size_t cells = (size_t)(st->n_nodes - 1) * st->n_sites;
+  free(st->leaf_r);
+  st->leaf_r = NULL;
+  if (!r) return;
+  st->leaf_r = (float *)malloc(cells * sizeof(float));
+  memcpy(st->leaf_r, r, cells * sizeof(float));
 }
 
 ORC_API void orc_set_modes(orc_state *st, int rng_mode, int math_mode, int schedule,

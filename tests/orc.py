@@ -58,6 +58,8 @@ def orc_lib():
         L.orc_set_proposal_mode.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_sample_root.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_sampler.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_unobserved.argtypes = [C.c_void_p, u8p]
+        L.orc_set_leaf_evidence.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.orc_get_max_qdiff.argtypes = [C.c_void_p]
         L.orc_get_max_qdiff.restype = C.c_double
         L.orc_set_shard.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
@@ -247,6 +249,24 @@ class Oracle(_Engine):
     def set_sampler(self, forward):
         """True: forward rejection for every segment; False: Nielsen for state changes"""
         self.L.orc_set_sampler(self.h, 0 if forward else 1)
+
+    def set_unobserved(self, mask):
+        """leaf cells that are not data, [N-1, n] (node-major, as DeviceSampler.set_unobserved); None clears"""
+        if mask is None:
+            self.L.orc_set_unobserved(self.h, None)
+            return
+        m = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert m.size == self.B * self.n_sites, m.size
+        self.L.orc_set_unobserved(self.h, _p(m, C.c_uint8))
+
+    def set_leaf_evidence(self, r):
+        """float32 r = P(state 1 | the cell's own observation) per leaf cell, NaN = none, [N-1, n]; None clears"""
+        if r is None:
+            self.L.orc_set_leaf_evidence(self.h, None)
+            return
+        r = np.ascontiguousarray(r, np.float32).reshape(-1)
+        assert r.size == self.B * self.n_sites, r.size
+        self.L.orc_set_leaf_evidence(self.h, _p(r, C.c_float))
 
     def max_qdiff(self):
         return float(self.L.orc_get_max_qdiff(self.h))

@@ -20,6 +20,8 @@ Coverage (variant x options -> rows):
                                              sr-tree
   V1, global pool (accept3 over all sites)   forward rejection: fr-v1-global; ref-tree-global, ref-bal16,
                                              frref-bal16, sr-bal16; default: n129, multi-no-v3, unary-q64
+  V1's LEAF template axis (mask, evidence)   test_leaf_matrix.py: all eight (pool, ratio, leaf mode)
+                                             instantiations against rung B with its own leaf vector
 """
 import json
 import os

@@ -13,7 +13,8 @@ from common import simulate, ref_test_model, TEST_PARAM_TEXT, TREE_NWK_TEXT
 from epievo_amd import _build, host
 from epievo_amd.sampler import DeviceSampler, EpvError
 from test_unobserved_leaves import leaf_ends, write_states, leaves
-from test_unobserved_leaves_gpu import _dev, _mask, _run, _same, MISSING, TRIALS
+from test_unobserved_leaves_gpu import _dev, _mask, _run, _same
+from leaf_law import MISSING, TRIALS, EVIDENCE, _exact_completions, _mixture, _sigma      # noqa: F401
 from test_leaf_evidence import write_probs
 import test_mcmc_posterior as post
 
@@ -139,50 +140,7 @@ def test_evidence_wins_over_the_mask(opts):
 # kept_c is what a fixed number of forward simulations keeps (the prior weight of the completion's data) and
 # e_c = prod (r_i or 1 - r_i) the evidence.  Standard errors come from the reference's counts alone: the Kish
 # effective count (sum k_c e_c)^2 / sum k_c e_c^2 stands where the number of kept draws does for one target.
-EVIDENCE = [np.float32(0.8), np.float32(0.02)]        # r of MISSING[0] = (D, 3) and MISSING[1] = (C, 6)
-
-
-def _exact_completions(model, tree, leaf):
-    L = orc.orc_lib()
-    u8p, u32p, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    L.orc_exact_posterior_tree.restype = C.c_uint64
-    L.orc_exact_posterior_tree.argtypes = [dp, C.c_uint64, C.c_int, u32p, u32p, dp, u8p, u8p, C.c_uint64, C.c_uint64,
-                                           C.c_uint64, dp, dp, dp, dp]
-    B = tree.n_nodes - 1
-    kept, mom = [], []
-    for c in range(1 << len(MISSING)):
-        lf = leaf.copy()
-        for i, (name, s) in enumerate(MISSING):
-            lf[tree.node_names.index(name), s] = c >> i & 1
-        Jm, Dm, J2, D2 = (np.zeros(B * 8) for _ in range(4))
-        flat = np.ascontiguousarray(lf.reshape(-1))
-        k = L.orc_exact_posterior_tree(orc._p(model.rates, C.c_double), lf.shape[1], tree.n_nodes,
-                                       orc._p(tree.parent_ids, C.c_uint32), orc._p(tree.subtree_sizes, C.c_uint32),
-                                       orc._p(tree.branches, C.c_double), orc._p(post.TROOT, C.c_uint8),
-                                       orc._p(flat, C.c_uint8), 7 + c, TRIALS, TRIALS, orc._p(Jm, C.c_double),
-                                       orc._p(Dm, C.c_double), orc._p(J2, C.c_double), orc._p(D2, C.c_double))
-        kept.append(k)
-        mom.append((Jm, Dm, J2, D2))
-    return np.array(kept, np.float64), mom
-
-
-def _mixture(kept, mom, evidence):
-    """(Jm, Dm, Jse, Dse), P(state 1) per cell, Kish effective count; evidence None = the plain mask"""
-    e = np.ones(len(kept))
-    if evidence is not None:
-        for c in range(len(kept)):
-            for i, r in enumerate(evidence):
-                e[c] *= float(r) if c >> i & 1 else 1.0 - float(r)
-    w = kept * e
-    tot = w.sum()
-    kish = tot ** 2 / (kept * e ** 2).sum()
-    Jm, Dm, J2, D2 = (sum(w[c] * mom[c][i] for c in range(len(w))) / tot for i in range(4))
-    p1 = [sum(w[c] for c in range(len(w)) if c >> i & 1) / tot for i in range(len(MISSING))]
-    return (Jm, Dm, np.sqrt(np.maximum(J2 - Jm ** 2, 1e-12) / kish), np.sqrt(np.maximum(D2 - Dm ** 2, 1e-12) / kish)), p1, kish
-
-
-def _sigma(p, kish):
-    return np.sqrt(max(p * (1 - p), 1e-4) * (1.0 / kish + 1.0 / 1200.0))
+# The target lives in leaf_law.py, which computes the completions once per process.
 
 
 @pytest.fixture(scope="module")
@@ -204,8 +162,11 @@ def test_the_evidence_moves_the_target_away_from_the_mask(exact_case):
         assert abs(p1[i] - p1_mask[i]) >= 10 * sig, (name, s, p1[i], p1_mask[i], sig)
 
 
-@pytest.mark.parametrize("seed,opts", [(21, {}), (22, {}), (23, {}), (24, {"forward_rejection": True})])
+@pytest.mark.parametrize("seed,opts", [(21, {}), (22, {}), (23, {}), (24, {"forward_rejection": True}),
+                                       (25, {"reference_proposal_ratio": True})])
 def test_chain_matches_the_exact_posterior_under_leaf_evidence(exact_case, seed, opts):
+    """(the reference-ratio case: without the target's leaf factor in the ratio that mode follows the mask's
+    law)"""
     model, tree, leaf, fp, (exact, p1, kish), _ = exact_case
     n = len(post.TROOT)
     r = np.full((tree.n_nodes - 1, n), NAN, np.float32)

@@ -13,6 +13,7 @@ from epievo_amd import _build, host
 from epievo_amd.sampler import DeviceSampler, EpvError
 from test_unobserved_leaves import leaf_ends, write_states, leaves
 import test_mcmc_posterior as post
+from leaf_law import MISSING, TRIALS, _exact_completions, _mixture      # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -125,44 +126,15 @@ def test_both_ratio_modes_give_the_same_chain_under_the_mask():
 # ------------------------------------------------------------------ the exact posterior
 # test_mcmc_posterior's 14-site tree case; two leaf cells unobserved: (D, 3) where leaf D flips, and
 # (C, 6) where nothing does.  The target mixes the exact posterior of each completion of the two cells,
-# weighted by how many of a fixed number of forward simulations each completion keeps.
-MISSING = [("D", 3), ("C", 6)]
-TRIALS = 20000000
-
-
-def _exact_mixture(model, tree, leaf):
-    L = orc.orc_lib()
-    u8p, u32p, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-    L.orc_exact_posterior_tree.restype = C.c_uint64
-    L.orc_exact_posterior_tree.argtypes = [dp, C.c_uint64, C.c_int, u32p, u32p, dp, u8p, u8p, C.c_uint64, C.c_uint64,
-                                           C.c_uint64, dp, dp, dp, dp]
-    B = tree.n_nodes - 1
-    kept, mom = [], []
-    for c in range(1 << len(MISSING)):
-        lf = leaf.copy()
-        for i, (name, s) in enumerate(MISSING):
-            lf[tree.node_names.index(name), s] = c >> i & 1
-        Jm, Dm, J2, D2 = (np.zeros(B * 8) for _ in range(4))
-        flat = np.ascontiguousarray(lf.reshape(-1))
-        k = L.orc_exact_posterior_tree(orc._p(model.rates, C.c_double), lf.shape[1], tree.n_nodes,
-                                       orc._p(tree.parent_ids, C.c_uint32), orc._p(tree.subtree_sizes, C.c_uint32),
-                                       orc._p(tree.branches, C.c_double), orc._p(post.TROOT, C.c_uint8),
-                                       orc._p(flat, C.c_uint8), 7 + c, TRIALS, TRIALS, orc._p(Jm, C.c_double),
-                                       orc._p(Dm, C.c_double), orc._p(J2, C.c_double), orc._p(D2, C.c_double))
-        kept.append(k)
-        mom.append((Jm, Dm, J2, D2))
-    w = np.array(kept, np.float64)
-    tot = w.sum()
-    Jm, Dm, J2, D2 = (sum(w[c] * mom[c][i] for c in range(len(w))) / tot for i in range(4))
-    p1 = [sum(w[c] for c in range(len(w)) if c >> i & 1) / tot for i in range(len(MISSING))]
-    return (Jm, Dm, np.sqrt(np.maximum(J2 - Jm ** 2, 1e-12) / tot), np.sqrt(np.maximum(D2 - Dm ** 2, 1e-12) / tot)), p1, tot
-
+# weighted by how many of a fixed number of forward simulations each completion keeps (leaf_law.py).
 
 @pytest.fixture(scope="module")
 def exact_case():
     model = ref_test_model()
     tree, leaf, fp = post._tree_case()
-    return model, tree, leaf, fp, _exact_mixture(model, tree, leaf)
+    kept, mom = _exact_completions(model, tree, leaf)
+    # (no evidence: every completion weighs what the simulations kept, and the effective count is their total)
+    return model, tree, leaf, fp, _mixture(kept, mom, None)
 
 
 @pytest.mark.parametrize("seed,opts", [(21, {}), (22, {}), (23, {}), (24, {"forward_rejection": True})])
