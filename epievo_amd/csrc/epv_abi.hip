@@ -1570,26 +1570,42 @@ int upload_indep_consts(epv_ctx *c, const double *rates) {
   return EPV_OK;
 }
 
+// launch shape of the kernels that keep a per-node table of 5 doubles per lane in LDS: 256-lane blocks when
+// it fits, 64-lane blocks for large trees
+void indep_stats_shape(const epv_ctx *c, uint32_t &threads, size_t &lds) {
+  threads = 256u;
+  lds = (size_t)c->S.N * threads * 5u * sizeof(double);
+  if (lds > 60u * 1024u) { threads = 64u; lds = (size_t)c->S.N * threads * 5u * sizeof(double); }
+}
+
 int indep_stats(epv_ctx *c, const double *rates, uint32_t what, double *J, double *D) {
   const uint32_t B = c->S.B, V16 = ((B * 4u + 15u) / 16u) * 16u;
-  // 256-lane blocks when the per-node LDS table fits, 64-lane blocks for large trees
-  uint32_t threads = 256u;
-  size_t lds = (size_t)c->S.N * threads * 5u * sizeof(double);
-  if (lds > 60u * 1024u) { threads = 64u; lds = (size_t)c->S.N * threads * 5u * sizeof(double); }
+  uint32_t threads = 0;
+  size_t lds = 0;
+  indep_stats_shape(c, threads, lds);
   const uint64_t nb = (c->S.n + threads - 1u) / threads;
   // the tree-reduction buffers are shared with the 8-context statistics but sized for THIS
   // launch shape: nb rows of V16 doubles at level 0, ceil(nb/256) rows at level 1
   int rc = ensure_partial_doubles(c, nb * V16, ((nb + 255u) / 256u) * V16);
   if (rc) return rc;
   if (lds > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the site-independent kernels");
+  // the leaf vector: the table instantiation only while the context holds a flagged
+  // or non-NaN cell and the call reads leaf data; otherwise the kernel a context without tables always ran
+  const bool tables = what == 0u && (c->d_evidence || c->d_unobs);
+  typedef const uint32_t *M;
   if (lds > 60u * 1024u &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(epv_indep_stats_kernel),
+      hipFuncSetAttribute(tables ? reinterpret_cast<const void *>(epv_indep_stats_kernel<EPV_LEAF_EVIDENCE, M, M>)
+                                 : reinterpret_cast<const void *>(epv_indep_stats_kernel<EPV_LEAF_DATA>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(c, EPV_ERR_HIP, "cannot raise the dynamic LDS limit");
   double pi_0 = 0.0;
   if (what == 0u) pi_0 = rates[1] / (rates[0] + rates[1]);
-  hipLaunchKernelGGL(epv_indep_stats_kernel, dim3((unsigned)nb), dim3(threads), lds, c->stream, c->S, c->d_indep,
-                     pi_0, what, V16, c->d_partial[0]);
+  if (tables)
+    hipLaunchKernelGGL((epv_indep_stats_kernel<EPV_LEAF_EVIDENCE, M, M>), dim3((unsigned)nb), dim3(threads), lds,
+                       c->stream, c->S, c->d_indep, pi_0, what, V16, c->d_partial[0], (M)c->d_evidence, (M)c->d_unobs);
+  else
+    hipLaunchKernelGGL((epv_indep_stats_kernel<EPV_LEAF_DATA>), dim3((unsigned)nb), dim3(threads), lds, c->stream,
+                       c->S, c->d_indep, pi_0, what, V16, c->d_partial[0]);
   uint64_t m = nb;
   int cur = 0;
   while (m > 1) {
@@ -1635,6 +1651,43 @@ EPV_API int epv_indep_sufficient_statistics(epv_ctx *c, double *J, double *D) {
   return EPV_OK;
 }
 
+EPV_API int epv_indep_node_posterior(epv_ctx *c, const double *rates, double *p_state1) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!rates || !p_state1) return fail(c, EPV_ERR_ARG, "null argument");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = upload_indep_consts(c, rates))) return rc;
+  uint32_t threads = 0;
+  size_t lds = 0;
+  indep_stats_shape(c, threads, lds);
+  if (lds > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the site-independent kernels");
+  if (lds > 60u * 1024u &&
+      hipFuncSetAttribute(reinterpret_cast<const void *>(epv_indep_posterior_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(c, EPV_ERR_HIP, "cannot raise the dynamic LDS limit");
+  // the read-out is staged on the device, [N][n] doubles
+  const uint64_t cells = (uint64_t)c->S.N * c->S.n;
+  const double need = 8.0 * (double)cells;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of epv_set_path_average)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "node posterior needs %.3g GB of device memory (8 B x %u nodes x %llu sites); "
+                  "%.3g GB are free", need / 1e9, c->S.N, (unsigned long long)c->S.n, (double)free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  DevTmp<double> out;
+  HIP_TRY(c, out.alloc(cells));
+  const uint64_t nb = (c->S.n + threads - 1u) / threads;
+  hipLaunchKernelGGL(epv_indep_posterior_kernel, dim3((unsigned)nb), dim3(threads), lds, c->stream, c->S, c->d_indep,
+                     rates[1] / (rates[0] + rates[1]), (const uint32_t *)c->d_evidence, (const uint32_t *)c->d_unobs,
+                     out.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(p_state1, out.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
 EPV_API int epv_indep_update_paths(epv_ctx *c, const double *rates, uint64_t seed, uint32_t sweep) {
   int rc = check_ready(c, false);
   if (rc) return rc;
@@ -1646,16 +1699,24 @@ EPV_API int epv_indep_update_paths(epv_ctx *c, const double *rates, uint64_t see
   const uint64_t threads = (last - first + 1u + 2u) / 3u;
   const size_t lds = (size_t)c->S.N * 64u * 4u * sizeof(double);
   if (lds > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the site-independent kernels");
+  const bool tables = c->d_evidence || c->d_unobs;   // the leaf vector: as in indep_stats
+  typedef const uint32_t *M;
   if (lds > 60u * 1024u &&
-      hipFuncSetAttribute(reinterpret_cast<const void *>(epv_indep_propose_kernel),
+      hipFuncSetAttribute(tables ? reinterpret_cast<const void *>(epv_indep_propose_kernel<EPV_LEAF_EVIDENCE, M, M>)
+                                 : reinterpret_cast<const void *>(epv_indep_propose_kernel<EPV_LEAF_DATA>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return fail(c, EPV_ERR_HIP, "cannot raise the dynamic LDS limit");
   for (uint32_t colour = 0; colour < 3; ++colour) {
     const uint64_t s0 = first + ((colour + 3u - (uint32_t)((c->S.g0 + first) % 3u)) % 3u);
     const uint64_t blocks = (threads + 63u) / 64u;
-    hipLaunchKernelGGL(epv_indep_propose_kernel, dim3((unsigned)blocks), dim3(64), lds, c->stream, c->S,
-                       c->d_indep, rates[0], rates[1], colour, first, last, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), sweep, c->d_counters);
+    if (tables)
+      hipLaunchKernelGGL((epv_indep_propose_kernel<EPV_LEAF_EVIDENCE, M, M>), dim3((unsigned)blocks), dim3(64), lds,
+                         c->stream, c->S, c->d_indep, rates[0], rates[1], colour, first, last, (uint32_t)seed,
+                         (uint32_t)(seed >> 32), sweep, c->d_counters, (M)c->d_evidence, (M)c->d_unobs);
+    else
+      hipLaunchKernelGGL((epv_indep_propose_kernel<EPV_LEAF_DATA>), dim3((unsigned)blocks), dim3(64), lds, c->stream,
+                         c->S, c->d_indep, rates[0], rates[1], colour, first, last, (uint32_t)seed,
+                         (uint32_t)(seed >> 32), sweep, c->d_counters);
     const uint64_t max_tasks = blocks / EPV_SHARDS * 64u * c->S.B + 64u * c->S.B;
     const uint32_t tpw = 32u;
     const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);

@@ -1330,18 +1330,40 @@ __global__ void epv_init_ends_kernel(EpvDev S, const uint8_t *leaf, uint32_t see
 //  site; per-node Felsenstein values {q0,q1,p0,p1} in LDS [node][lane]; the per-branch
 //  matrices come from EpvIndepConst, so there is no exp/log on this path.
 // =========================================================================
+// LEAF (EPV_LEAF_*, as in epv_mh_propose_kernel) says what a leaf's (q0, q1) starts from.  EPV_LEAF_DATA: the
+// indicator of the path's end state, no trailing argument.  EPV_LEAF_EVIDENCE, the one table mode here: (table,
+// mask) trail, either may be nullptr (the same for every lane); a non-NaN r of the table gives (1 - r, r) in fp64,
+// else a flagged cell of the mask gives (1, 1), else the cell is data.  Nothing above the leaf changes: every
+// quotient the callers form is homogeneous of degree 0 in a leaf's q, so r = 0.5 equals the mask bit for bit
+// (a factor 2^-1 cancels exactly) and r = 0 or 1 agreeing with the path equals data bit for bit.
+template <int LEAF, class... Leaf>
 __device__ __forceinline__ void indep_upward(const EpvDev &S, const EpvIndepConst *ic, uint32_t sel,
-                                             uint64_t site, double *fh /* [N][blockDim][4] */) {
+                                             uint64_t site, double *fh /* [N][blockDim][4] */, Leaf... leaf_args) {
+  static_assert(LEAF == EPV_LEAF_DATA || LEAF == EPV_LEAF_EVIDENCE, "data, or the table and the mask");
+  static_assert(sizeof...(Leaf) == (size_t)LEAF, "the table and the mask come with EPV_LEAF_EVIDENCE");
   // upward_process (IndepSite.cpp:53-96)
   const uint32_t T = blockDim.x, t = threadIdx.x;
   for (uint32_t node = S.N; node-- > 0u;) {
     double a = 1.0, b = 1.0;
     const uint32_t sub = S.subtree[node];
     if (sub == 1u) {
+      [[maybe_unused]] float ev_r = __uint_as_float(0x7fc00000u);   // NaN: no evidence
+      [[maybe_unused]] bool ev_unobs = false;
+      if constexpr (LEAF == EPV_LEAF_EVIDENCE) {
+        // (addresses of node and site only: in flight together with the meta load below)
+        const uint32_t *table = epv_first_arg(leaf_args...);
+        const uint32_t *mask = epv_second_arg(leaf_args...);
+        if (table) ev_r = epv_leaf_evidence(table, node, site);
+        if (mask) ev_unobs = epv_unobserved(mask, node, site);
+      }
       const uint32_t m = S.meta[meta_idx(S, sel, node - 1u, site)];
       const uint32_t leaf_state = (m >> EPV_INIT_SHIFT) ^ (m & 1u);
       a = leaf_state ? 0.0 : 1.0;
       b = leaf_state ? 1.0 : 0.0;
+      if constexpr (LEAF == EPV_LEAF_EVIDENCE) {
+        if (ev_r == ev_r) { b = (double)ev_r; a = 1.0 - (double)ev_r; }   // (not NaN: wins over the mask)
+        else if (ev_unobs) { a = 1.0; b = 1.0; }
+      }
     } else {
       for (uint32_t ch = 1u; ch < sub; ch += S.subtree[node + ch]) {
         const double *c = fh + ((size_t)(node + ch) * T + t) * 4u;
@@ -1363,9 +1385,11 @@ __device__ __forceinline__ void indep_upward(const EpvDev &S, const EpvIndepCons
 // partial layout [block][V16], column 4*(node-1) + {0,1,2,3}, zero padded to V16.
 // what = 0: conditional expectations; what = 1: counts of the current paths
 // (compute_sufficient_statistics, :266-297).
+// LEAF and its trailing arguments: see indep_upward.  The counting mode reads no leaf vector.
+template <int LEAF, class... Leaf>
 __global__ __launch_bounds__(256) void epv_indep_stats_kernel(EpvDev S, const EpvIndepConst *ic,
                                                               double pi_0, uint32_t what, uint32_t V16,
-                                                              double *partial) {
+                                                              double *partial, Leaf... leaf_args) {
   extern __shared__ __attribute__((aligned(16))) double fh[];
   __shared__ double s_part[2][4][16];
   const int lane = epv_lane();
@@ -1375,7 +1399,7 @@ __global__ __launch_bounds__(256) void epv_indep_stats_kernel(EpvDev S, const Ep
   const uint32_t sel = on ? S.sel[site] : 0u;
   double *pm = fh + (size_t)S.N * blockDim.x * 4u;   // [N][blockDim] marginal P(state 0)
   if (on && what == 0u) {
-    indep_upward(S, ic, sel, site, fh);
+    indep_upward<LEAF>(S, ic, sel, site, fh, leaf_args...);
     const double *root = fh + (size_t)threadIdx.x * 4u;
     const double a = pi_0 * root[0], b = (1 - pi_0) * root[1];
     pm[threadIdx.x] = a / (a + b);   // root_post_prob0 (:98-104)
@@ -1439,16 +1463,57 @@ __global__ __launch_bounds__(256) void epv_indep_stats_kernel(EpvDev S, const Ep
   }
 }
 
+// epv_indep_node_posterior: P(state 1 | all leaf data, mask and evidence) of every node at every site, out
+// [N][n] node-major.  The upward pass and the downward recursion of epv_indep_stats_kernel (root_post_prob0 and
+// joint_post, IndepSite.cpp:98-127) with the same per-node marginal P(state 0) in LDS; the read-out writes its
+// complement, one site per lane.  Its own kernel: the statistics kernels keep their instruction streams.
+__global__ __launch_bounds__(256) void epv_indep_posterior_kernel(EpvDev S, const EpvIndepConst *ic, double pi_0,
+                                                                  const uint32_t *table, const uint32_t *mask,
+                                                                  double *out) {
+  extern __shared__ __attribute__((aligned(16))) double fh[];
+  const uint64_t site = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (site >= S.n) return;   // (no barrier below: a lane reads the LDS columns it wrote)
+  double *pm = fh + (size_t)S.N * blockDim.x * 4u;   // [N][blockDim] marginal P(state 0)
+  indep_upward<EPV_LEAF_EVIDENCE>(S, ic, (uint32_t)S.sel[site], site, fh, table, mask);
+  {
+    const double *root = fh + (size_t)threadIdx.x * 4u;
+    const double a = pi_0 * root[0], b = (1 - pi_0) * root[1];
+    const double p0 = a / (a + b);
+    pm[threadIdx.x] = p0;
+    out[site] = 1 - p0;
+  }
+  for (uint32_t node = 1u; node < S.N; ++node) {   // pre-order: the parent's marginal is there
+    const double *me = fh + ((size_t)node * blockDim.x + threadIdx.x) * 4u;
+    const EpvIndepConst &k = ic[node];
+    const double p0u = pm[(size_t)S.parent[node] * blockDim.x + threadIdx.x];
+    double pj[4];
+    pj[0] = k.P[0] * me[0] * p0u / me[2];
+    pj[1] = k.P[1] * me[1] * p0u / me[2];
+    pj[2] = k.P[2] * me[0] * (1 - p0u) / me[3];
+    pj[3] = k.P[3] * me[1] * (1 - p0u) / me[3];
+    const double Z = pj[0] + pj[1] + pj[2] + pj[3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pj[i] /= Z;
+    const double p0 = pj[0] + pj[2];
+    pm[(size_t)node * blockDim.x + threadIdx.x] = p0;
+    out[(uint64_t)node * S.n + site] = 1 - p0;
+  }
+}
+
 // update_paths_indep (IndepSite.cpp:177-215, :241-259), part 1: end state of every
 // branch; clean branches (state kept, provably no jump in trial 1) are final, the rest
 // goes to epv_mh_jumps_kernel (run with the two context-free rates).  Processed in three
 // thirds of the sites so that the phase-sized hand-over arrays suffice.
+// LEAF and its trailing arguments: see indep_upward.  pr0 below is the general expression: a leaf whose q is
+// not an indicator draws its end state from its conditional law like an internal node, and the jumps kernel
+// takes that end state from prop_states.
+template <int LEAF, class... Leaf>
 __global__ __launch_bounds__(64) void epv_indep_propose_kernel(EpvDev S, const EpvIndepConst *ic,
                                                               double r0, double r1, uint32_t colour,
                                                               uint64_t first, uint64_t last,
                                                               uint32_t seed_lo, uint32_t seed_hi,
                                                               uint32_t sweep,
-                                                              unsigned long long *counters) {
+                                                              unsigned long long *counters, Leaf... leaf_args) {
   extern __shared__ __attribute__((aligned(16))) double fh[];
   const int lane = epv_lane();
   const uint64_t s0 = first + ((colour + 3u - (uint32_t)((S.g0 + first) % 3u)) % 3u);
@@ -1459,7 +1524,7 @@ __global__ __launch_bounds__(64) void epv_indep_propose_kernel(EpvDev S, const E
   uint32_t sel = 0, root_state = 0;
   if (valid) {
     sel = S.sel[site];
-    indep_upward(S, ic, sel, site, fh);
+    indep_upward<LEAF>(S, ic, sel, site, fh, leaf_args...);
     root_state = (uint32_t)(S.meta[meta_idx(S, sel, 0u, site)] >> EPV_INIT_SHIFT);
     S.prop_flag[tid] = 0u;
   }

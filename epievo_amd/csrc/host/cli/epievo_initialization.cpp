@@ -3,6 +3,12 @@
 // initial histories from it, and derive initial parameters of the context-dependent model --
 // i.e. produce the inputs of epievo_est_params_histories.  Same flags and positionals
 // (-v -s -i -B -p -t -T -o -b, (<tree-file>) <states-file>), same file formats.
+// Extensions: -m/--missing FILE, a states file whose N cells are missing leaf data, and -l/--leaf-probs FILE, a
+// file of P(state 1) per leaf cell (N = 0.5; exactly 0 and 1 are data), with the formats and readers of the E-step
+// programs.  FILE takes the place of the positional states file.  The site-independent EM marginalises those
+// cells (SingleSiteSampler::set_unobserved / set_leaf_evidence on the one context of this stage) instead of
+// fitting rates and branch lengths to invented calls, and the output paths carry the last resampled state in
+// them, so the same FILE passes the agreement check of epievo_est_params_histories -m / -l.
 // The O(n) parts (conditional expectations, path resampling, both kinds of sufficient
 // statistics, rescaling) run on the GPU; the O(nodes) M-steps and the one-pass heuristic
 // start run on the host.
@@ -33,7 +39,7 @@ int main(int argc, const char **argv) {
     double evolutionary_time = 0.0;
     size_t rng_seed = std::numeric_limits<size_t>::max();
     size_t iterations = 10, batch = 10;
-    string paramfile, pathfile, tree_file, treefile_updated;
+    string paramfile, pathfile, tree_file, treefile_updated, missing_file, leaf_probs_file;
 
     const string prog = string(argv[0]).substr(string(argv[0]).find_last_of('/') + 1);
     epv::OptionParser opt_parse(prog, "generate initial paths and parameters given states at leaves",
@@ -47,13 +53,30 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("evo-time", 'T', "evolutionary time (assumes no tree)", false, evolutionary_time);
     opt_parse.add_opt("path", 'o', "output file of local paths (default: stdout)", false, pathfile);
     opt_parse.add_opt("branch", 'b', "optimize branch lengths as well", false, optimize_branches);
+    opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data (in place of <states-file>)", false,
+                      missing_file);
+    opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell, N = 0.5; 0 and 1 are data (in place of "
+                      "<states-file>)", false, leaf_probs_file);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
       cerr << opt_parse.help_message() << endl << opt_parse.about_message() << endl;
       return EXIT_SUCCESS;
     }
-    if (leftover_args.size() == 1) {
+    if (!missing_file.empty() && !leaf_probs_file.empty())
+      throw std::runtime_error("-m/--missing and -l/--leaf-probs cannot be given together (N in a -l file is a missing cell)");
+    const bool soft = !missing_file.empty() || !leaf_probs_file.empty();
+    const string &soft_file = missing_file.empty() ? leaf_probs_file : missing_file;
+    if (soft) {
+      // FILE takes the place of the states file: the positionals are (<tree-file>) alone, or none with -T
+      const size_t want = evolutionary_time == 0.0 ? 1 : 0;
+      if (leftover_args.size() != want)
+        throw std::runtime_error(string(missing_file.empty() ? "-l/--leaf-probs" : "-m/--missing") +
+                                 " takes the place of <states-file>: the positional arguments are " +
+                                 (want ? "<tree-file> alone" : "none with -T") + ", got " +
+                                 std::to_string(leftover_args.size()));
+      if (want) tree_file = leftover_args.front();
+    } else if (leftover_args.size() == 1) {
       if (evolutionary_time == 0.0) { cerr << opt_parse.help_message() << endl; return EXIT_SUCCESS; }
     } else if (leftover_args.size() != 2) {
       cerr << opt_parse.help_message() << endl;
@@ -61,7 +84,7 @@ int main(int argc, const char **argv) {
     } else {
       tree_file = leftover_args.front();
     }
-    const string statesfile(leftover_args.back());
+    const string statesfile(soft ? soft_file : leftover_args.back());
 
     epv::Tree th;
     if (evolutionary_time > 0.0) {
@@ -72,7 +95,9 @@ int main(int argc, const char **argv) {
       th = epv::Tree::read(tree_file);
     }
     if (VERBOSE) cerr << "[READING STATES FILE: " << statesfile << "]" << endl;
-    vector<vector<uint8_t>> state_sequences = epv::read_states_for_tree(statesfile, th);
+    vector<vector<uint8_t>> state_sequences = !missing_file.empty() ? epv::start_states_missing(missing_file, th)
+                                              : !leaf_probs_file.empty() ? epv::start_states_leaf_probs(leaf_probs_file, th)
+                                                                         : epv::read_states_for_tree(statesfile, th);
 
     if (rng_seed == std::numeric_limits<size_t>::max()) { std::random_device rd; rng_seed = rd(); }
     if (VERBOSE) cerr << "rng seed: " << rng_seed << endl;
@@ -80,8 +105,26 @@ int main(int argc, const char **argv) {
     /* generate initial paths by heuristics (host) */
     epv::FlatPaths paths = epv::initialize_paths_heuristic(rng_seed, th, state_sequences);
 
+    // the cells of FILE that are not data, over the heuristic paths (whose leaves end in the start states); tokens
+    // that are exactly 0 or 1 stay data.  Host work: a bad FILE fails before any GPU call
+    vector<uint8_t> unobserved;
+    vector<float> evidence;
+    if (!missing_file.empty()) {
+      uint64_t n_unobserved = 0, n_leaf_cells = 0;
+      unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
+      if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+    }
+    if (!leaf_probs_file.empty()) {
+      uint64_t n_evidence = 0, n_leaf_cells = 0;
+      evidence = epv::leaf_evidence_cells(leaf_probs_file, th, paths, n_evidence, n_leaf_cells);
+      if (VERBOSE) cerr << "[LEAF CELLS WITH EVIDENCE: " << n_evidence << " of " << n_leaf_cells << "]" << endl;
+    }
+
     epv::SingleSiteSampler gpu(0, batch, 0, 32);
     gpu.upload(th, paths);
+    // before the first indep_* call; scale_jump_times (-b) keeps them
+    if (!unobserved.empty()) gpu.set_unobserved(std::move(unobserved));
+    if (!evidence.empty()) gpu.set_leaf_evidence(std::move(evidence));
 
     /* Run EM to learn a site-independent model */
     double rates[2] = {0.0, 0.0};

@@ -88,6 +88,51 @@ std::vector<std::vector<uint8_t>> read_states_for_tree(const std::string &states
   return states;
 }
 
+namespace {
+// columns of a states-like file, by name, onto the nodes of the tree: what read_states_for_tree does with its
+// own reader (a leaf without a column is an error, an internal node without one starts from 0)
+std::vector<std::vector<uint8_t>> start_states_onto_tree(const std::string &file, const std::vector<std::string> &names,
+                                                         const std::vector<std::vector<uint8_t>> &cols, const Tree &th) {
+  const int N = th.n_nodes();
+  const size_t n = cols.empty() ? 0 : cols.front().size();
+  if (n == 0) throw std::runtime_error("no sites read from states file: " + file);
+  std::vector<std::vector<uint8_t>> states(N);
+  for (int node = 0; node < N; ++node) {
+    const size_t k = std::find(names.begin(), names.end(), th.node_names[node]) - names.begin();
+    if (k < names.size()) states[node] = cols[k];
+    else if (th.is_leaf(node)) throw std::runtime_error("no data in leaf node: " + th.node_names[node]);
+    else states[node].assign(n, 0);
+  }
+  return states;
+}
+}  // namespace
+
+std::vector<std::vector<uint8_t>> start_states_missing(const std::string &states_file, const Tree &th) {
+  std::vector<std::string> names;
+  std::vector<std::vector<uint8_t>> states, missing;
+  read_states_file_missing(states_file, names, states, missing);   // (N reads as state 0)
+  return start_states_onto_tree(states_file, names, states, th);
+}
+
+std::vector<std::vector<uint8_t>> start_states_leaf_probs(const std::string &probs_file, const Tree &th) {
+  std::vector<std::string> names;
+  std::vector<std::vector<float>> probs;
+  read_leaf_probs_file(probs_file, names, probs);
+  std::vector<std::vector<uint8_t>> cols(names.size());
+  for (size_t k = 0; k < names.size(); ++k) {
+    const bool in_tree = std::find(th.node_names.begin(), th.node_names.end(), names[k]) != th.node_names.end();
+    cols[k].resize(probs[k].size());
+    for (size_t s = 0; s < probs[k].size(); ++s) {
+      const float r = probs[k][s];
+      if (in_tree && !(r >= 0.0f && r <= 1.0f))
+        throw std::runtime_error("leaf probabilities file " + probs_file + ": " + names[k] + " at site " +
+                                 std::to_string(s) + " is neither a probability in [0, 1] nor N");
+      cols[k][s] = r > 0.5f ? 1u : 0u;
+    }
+  }
+  return start_states_onto_tree(probs_file, names, cols, th);
+}
+
 FlatPaths initialize_paths_heuristic(uint64_t seed, const Tree &th,
                                      std::vector<std::vector<uint8_t>> &states) {
   const int N = th.n_nodes();

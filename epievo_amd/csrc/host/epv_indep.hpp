@@ -33,6 +33,14 @@ Model model_from_indep_rates(const double rates[2]);
 // Returns states[node][site].
 std::vector<std::vector<uint8_t>> read_states_for_tree(const std::string &states_file, const Tree &th);
 
+// -m/--missing and -l/--leaf-probs of epievo_initialization: the start states of the host heuristic from a
+// states file with N cells (read_states_file_missing: the token, N gives 0) or from a file of P(state 1) per cell
+// (read_leaf_probs_file: 1 if r > 0.5, else 0; N is 0.5).  Columns onto nodes as read_states_for_tree does.
+// Throws where a leaf has no column, the file has no rows, a row is short, or a token of a -l file is neither a
+// probability in [0, 1] nor N.
+std::vector<std::vector<uint8_t>> start_states_missing(const std::string &states_file, const Tree &th);
+std::vector<std::vector<uint8_t>> start_states_leaf_probs(const std::string &probs_file, const Tree &th);
+
 // initialize_paths (epievo_initialization.cpp:141-185): internal states are drawn from the
 // children's states (the root keeps the states file's column / zeros), and a branch whose
 // ends differ gets one uniformly placed jump.  Uses std::mt19937 exactly as the reference.

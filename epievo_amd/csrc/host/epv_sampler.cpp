@@ -784,6 +784,16 @@ void SingleSiteSampler::upload(const Tree &th, const FlatPaths &paths) {
   check(epv_upload_paths(ctx_, paths.n_sites, paths.init.data(), paths.offsets.data(),
                          paths.jumps.empty() ? &dummy : paths.jumps.data(), capacity_, 0),
         "epv_upload_paths");
+  // new paths cleared the context's tables: a mask or a table the sampler keeps goes back on, as in build()
+  const uint64_t cells = (uint64_t)(n_nodes_ - 1) * n_sites_;
+  if (!unobs_.empty() && unobs_.size() != cells)
+    throw std::runtime_error("mask of unobserved cells: " + std::to_string(unobs_.size()) + " entries for " +
+                             std::to_string(n_nodes_ - 1) + " branches x " + std::to_string(n_sites_) + " sites");
+  if (!evidence_.empty() && evidence_.size() != cells)
+    throw std::runtime_error("table of leaf evidence: " + std::to_string(evidence_.size()) + " entries for " +
+                             std::to_string(n_nodes_ - 1) + " branches x " + std::to_string(n_sites_) + " sites");
+  if (!unobs_.empty()) apply_unobserved(ctx_, 0, n_sites_);
+  if (!evidence_.empty()) apply_leaf_evidence(ctx_, 0, n_sites_);
 }
 
 void SingleSiteSampler::get_sufficient_statistics(std::vector<std::vector<double>> &J,
@@ -811,6 +821,12 @@ void SingleSiteSampler::indep_sufficient_statistics(std::vector<double> &J, std:
   J.assign(((size_t)n_nodes_ - 1) * 2, 0.0);
   D.assign(((size_t)n_nodes_ - 1) * 2, 0.0);
   check(epv_indep_sufficient_statistics(ctx_, J.data(), D.data()), "epv_indep_sufficient_statistics");
+}
+
+void SingleSiteSampler::indep_node_posterior(const double rates[2], std::vector<double> &p_state1) {
+  if (sharded()) throw std::runtime_error("indep_node_posterior: load the paths with upload() (one context)");
+  p_state1.assign((size_t)n_nodes_ * n_sites_, 0.0);
+  check(epv_indep_node_posterior(ctx_, rates, p_state1.data()), "epv_indep_node_posterior");
 }
 
 void SingleSiteSampler::indep_update_paths(const double rates[2], uint64_t seed, uint32_t sweep) {

@@ -126,7 +126,10 @@ public:
   uint32_t phase_mode();
   uint64_t halo_columns() const { return halo_; }
 
-  // upload paths without touching the model (the site-independent stage has no EpiEvoModel yet)
+  // upload paths without touching the model (the site-independent stage has no EpiEvoModel yet).  One context;
+  // set_unobserved and set_leaf_evidence work on it as after reset (a mask or table set before goes on the new
+  // paths), the three indep_* calls that read leaf data honour them (include/epievo_mi355x.h), and
+  // scale_jump_times keeps them
   void upload(const Tree &th, const FlatPaths &paths);
   // get_sufficient_statistics, per-branch overload (ParamEstimation.cpp:92-114), of the
   // resident paths: rows 1..n_nodes-1 of 8 contexts
@@ -135,6 +138,8 @@ public:
   void indep_expectation(const double rates[2], std::vector<double> &J, std::vector<double> &D);
   void indep_sufficient_statistics(std::vector<double> &J, std::vector<double> &D);
   void indep_update_paths(const double rates[2], uint64_t seed, uint32_t sweep);
+  // epv_indep_node_posterior: p_state1[node * n_sites + s] = P(state 1 | all leaf data, mask, evidence)
+  void indep_node_posterior(const double rates[2], std::vector<double> &p_state1);
 
   // MCMC parameter constants (public fields of the reference class)
   bool SAMPLE_ROOT;  // hard-wired false in the reference (SingleSiteSampler.cpp:441); true = EPV_OPT_SAMPLE_ROOT on

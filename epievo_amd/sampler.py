@@ -38,7 +38,7 @@ MAX_CAPACITY = 2047    # EPV_MAX_CAP: jump slots per (site, branch)
 ABI_SYMBOLS = [
     "epv_create", "epv_destroy", "epv_last_error", "epv_set_tree", "epv_set_model",
     "epv_upload_paths", "epv_set_capacity", "epv_get_capacity", "epv_init_paths_indep", "epv_indep_expectation",
-    "epv_indep_sufficient_statistics", "epv_indep_update_paths", "epv_set_global_length", "epv_set_update_range", "epv_set_halo",
+    "epv_indep_sufficient_statistics", "epv_indep_update_paths", "epv_indep_node_posterior", "epv_set_global_length", "epv_set_update_range", "epv_set_halo",
     "epv_halo_phases_left", "epv_reset", "epv_reset_async", "epv_sweep",
     "epv_sweep_phase", "epv_run_mcmc", "epv_run_mcmc_sums", "epv_get_sufficient_statistics", "epv_scale_jump_times",
     "epv_paths_total_jumps", "epv_download_paths", "epv_get_tri_llh", "epv_column_bytes",
@@ -80,6 +80,7 @@ def lib():
         L.epv_indep_expectation.argtypes = [vp, dp, dp, dp]
         L.epv_indep_sufficient_statistics.argtypes = [vp, dp, dp]
         L.epv_indep_update_paths.argtypes = [vp, dp, C.c_uint64, C.c_uint32]
+        L.epv_indep_node_posterior.argtypes = [vp, dp, dp]
         L.epv_set_global_length.argtypes = [vp, C.c_uint64]
         L.epv_set_update_range.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.epv_set_halo.argtypes = [vp, C.c_uint64, C.c_uint64]
@@ -346,6 +347,16 @@ class DeviceSampler:
     def indep_update_paths(self, rates, seed, sweep=0):
         r = np.ascontiguousarray(rates, np.float64)
         self._ck_mcmc(self.L.epv_indep_update_paths(self.h, _p(r, C.c_double), seed, sweep))
+
+    def indep_node_posterior(self, rates):
+        """-> (n_nodes, n_sites): P(state 1) at every node and site given all leaf data, the mask of
+        unobserved cells and the table of leaf evidence, under the site-independent two-rate model
+        (epv_indep_node_posterior): the imputed probability of every missing or soft leaf cell and the
+        marginal ancestral reconstruction"""
+        r = np.ascontiguousarray(rates, np.float64)
+        out = np.zeros((self.n_nodes, self.n_sites))
+        self._ck(self.L.epv_indep_node_posterior(self.h, _p(r, C.c_double), _p(out, C.c_double)))
+        return out
 
     def set_update_range(self, first, last):
         self._ck(self.L.epv_set_update_range(self.h, first, last))

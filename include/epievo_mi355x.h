@@ -241,10 +241,27 @@ int epv_forward_last_ms(epv_ctx *ctx, double *alloc_ms, double *simulate_ms);
  * epv_indep_sufficient_statistics  compute_sufficient_statistics (:266-297): per-branch
  *                                  averages of the resident paths
  * epv_indep_update_paths           update_paths_indep (:241-259): fresh end-conditioned paths
- *                                  for every site; `sweep` keys the random stream */
+ *                                  for every site; `sweep` keys the random stream
+ * epv_indep_node_posterior         p_state1[node * n_sites + s], node-major over all N nodes: the
+ *                                  probability of state 1 at that node and site given all leaf data;
+ *                                  the preconditions and error codes of epv_indep_expectation, and
+ *                                  EPV_ERR_ARG naming the figure when the device cannot stage the
+ *                                  8 * N * n_sites bytes.  No reference counterpart.
+ * Leaf masks and evidence.  epv_indep_expectation, epv_indep_update_paths and epv_indep_node_posterior
+ * honour the mask of epv_set_unobserved and the table of epv_set_leaf_evidence: a leaf starts the
+ * upward pass from (1.0 - (double)r, (double)r) where the table holds a non-NaN r, else from (1, 1)
+ * where the mask flags the cell, else from the indicator of the path's end state; a non-NaN r wins
+ * over the mask.  epv_indep_update_paths then draws the end state of such a cell from its conditional
+ * law with the rest of the history, and keeps every other leaf cell.  r = 0.5 equals the mask bit
+ * for bit, and r = 0 or 1 agreeing with the path equals data bit for bit (so does r = -0).
+ * These calls process EVERY site, the genome's two end sites included: a flag or a value at an
+ * end site has its effect here, although the MCMC never updates those sites.  A context that holds
+ * no flagged and no non-NaN cell runs the kernels it ran before masks existed.
+ * epv_indep_sufficient_statistics counts the resident paths and reads no leaf vector. */
 int epv_indep_expectation(epv_ctx *ctx, const double *rates, double *J, double *D);
 int epv_indep_sufficient_statistics(epv_ctx *ctx, double *J, double *D);
 int epv_indep_update_paths(epv_ctx *ctx, const double *rates, uint64_t seed, uint32_t sweep);
+int epv_indep_node_posterior(epv_ctx *ctx, const double *rates, double *p_state1);
 
 /* Site-sharded runs only: total genome length (default: global_site_offset + n_sites),
  * so that the two special cases at the genome ends (SingleSiteSampler.cpp:422,427) are
