@@ -20,6 +20,7 @@
 #include "epv_kernels.h"  // all __global__ kernels (single translation unit, no -fgpu-rdc)
 #include "epv_math.h"
 #include "epv_pavg.h"
+#include "epv_bevents.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
 // Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
@@ -141,6 +142,14 @@ struct epv_ctx {
   std::vector<double> pa_grid_blen;  // the branch lengths d_pa_grid was built from
   uint32_t *d_pa_out = nullptr;    // read-out staging
   uint64_t pa_out_cap = 0;         // bytes
+  // posterior branch-event maps (epv_bevents.h), off while !be_on
+  bool be_on = false;
+  uint32_t *d_be = nullptr;        // [6][B][be_cnt] counts over local sites be_lo .. be_lo + be_cnt - 1
+  uint64_t be_lo = 0, be_cnt = 0, be_n = 0, be_g0 = 0, be_ng = 0;   // the site range d_be was laid out for
+  uint32_t be_B = 0;
+  uint64_t be_samples = 0;
+  unsigned long long *d_be_out = nullptr;   // window read-out staging
+  uint64_t be_out_cap = 0;         // bytes
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -713,6 +722,66 @@ int launch_pavg(epv_ctx *c) {
   return EPV_OK;
 }
 
+// ---- posterior branch-event maps (epv_bevents.h): the sites of pavg_range, six uint32 planes
+// (re)lay out the planes for the current site range; zeroes them
+int bevents_alloc(epv_ctx *c) {
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_be);
+  c->be_cnt = 0;
+  const double need = 4.0 * EPV_BEV_PLANES * (double)c->S.B * (double)cnt;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "branch events need %.3g GB of device memory (24 B x %u branches x %llu sites); "
+                  "%.3g GB are free: use more GPUs (the counters are off)",
+                  need / 1e9, c->S.B, (unsigned long long)cnt, (double)free_b / 1e9);
+    c->be_on = false;
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t bytes = (size_t)4u * EPV_BEV_PLANES * c->S.B * cnt;
+  if (bytes) {
+    HIP_TRY(c, hipMalloc(&c->d_be, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->d_be, 0, bytes, c->stream));
+  }
+  c->be_lo = lo;
+  c->be_cnt = cnt;
+  c->be_n = c->S.n;
+  c->be_g0 = c->S.g0;
+  c->be_ng = c->S.n_global;
+  c->be_B = c->S.B;
+  c->be_samples = 0;
+  return EPV_OK;
+}
+// the planes match the current site range (there is no grid: branch lengths do not matter)
+int ensure_bevents(epv_ctx *c) {
+  if (!c->be_on) return EPV_OK;
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  if (lo != c->be_lo || cnt != c->be_cnt || c->S.n != c->be_n || c->S.g0 != c->be_g0 || c->S.n_global != c->be_ng ||
+      c->S.B != c->be_B) {
+    if (c->be_samples)
+      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the branch events took samples: "
+                                    "epv_set_branch_events again");
+    return bevents_alloc(c);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_bevents first)
+int launch_bevents(epv_ctx *c) {
+  if (c->be_samples >= EPV_BEV_MAX_SAMPLES)
+    return fail(c, EPV_ERR_STATE, "branch events hold 2^21 samples, the most their 32-bit counts take: "
+                                  "read them out and epv_reset_branch_events");
+  if (c->be_cnt)
+    hipLaunchKernelGGL(epv_bevents_accum_kernel, dim3((unsigned)((c->be_cnt + 255u) / 256u)), dim3(256), 0, c->stream,
+                       c->S, c->be_lo, c->be_cnt, c->d_be);
+  ++c->be_samples;
+  HIP_TRY(c, hipGetLastError());
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -1051,6 +1120,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_model); dfree(c->d_parent); dfree(c->d_subtree); dfree(c->d_blen);
   dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
+  dfree(c->d_be); dfree(c->d_be_out);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1872,13 +1942,17 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average sample}: the chain of epv_run_mcmc_sums
+// burn_in sweeps, then batch x {sweep; stat(w); path-average sample; branch-event sample}: the chain of epv_run_mcmc_sums
 // and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
 // snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
 static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base, Stat stat) {
   int rc = ensure_pavg(c);
   if (rc) return rc;
+  if ((rc = ensure_bevents(c))) return rc;
+  if (c->be_on && c->be_samples + batch > EPV_BEV_MAX_SAMPLES)   // (before any sweep: the chain is not cut short)
+    return fail(c, EPV_ERR_STATE, "branch events would pass 2^21 samples, the most their 32-bit counts take: "
+                                  "read them out and epv_reset_branch_events");
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -1892,6 +1966,7 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     ++c->n_sweeps;
     if ((rc = stat(w))) return rc;
     if (c->pa_P && (rc = launch_pavg(c))) return rc;
+    if (c->be_on && (rc = launch_bevents(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
@@ -2331,6 +2406,123 @@ EPV_API int epv_get_path_average(epv_ctx *c, uint64_t first, uint64_t count, uin
                      first - c->pa_lo, count, c->d_pa_out);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(counts, c->d_pa_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+// ---- posterior branch-event maps (epv_bevents.h)
+EPV_API int epv_set_branch_events(epv_ctx *c, int on) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_be); dfree(c->d_be_out);
+    c->be_on = false;
+    c->be_cnt = c->be_samples = c->be_out_cap = 0;
+    return EPV_OK;
+  }
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->be_on = true;
+  if ((rc = bevents_alloc(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_reset_branch_events(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_be)
+    HIP_TRY(c, hipMemsetAsync(c->d_be, 0, (size_t)4u * EPV_BEV_PLANES * c->be_B * c->be_cnt, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->be_samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_branch_events(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_bevents(c)) || (rc = launch_bevents(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_branch_events_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->be_on ? c->be_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_branch_events_set_samples(epv_ctx *c, uint64_t n) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  c->be_samples = n;
+  return EPV_OK;
+}
+
+EPV_API int epv_branch_events_layout(epv_ctx *c, uint64_t *first, uint64_t *count) {
+  if (!c || !first || !count) return EPV_ERR_ARG;
+  *first = *count = 0;
+  if (!c->be_on) return EPV_OK;
+  if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_bevents(c);
+    if (rc && c->be_samples == 0) return rc;
+  }
+  *first = c->be_lo;
+  *count = c->be_cnt;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_branch_events(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *planes) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  if (!planes) return fail(c, EPV_ERR_ARG, "null output");
+  if (first < c->be_lo || first + count > c->be_lo + c->be_cnt)
+    return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
+  if (count == 0) return EPV_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // rows of `count` sites out of rows of be_cnt: [6 B][be_cnt] -> [6 B][count]
+  HIP_TRY(c, hipMemcpy2D(planes, count * 4u, c->d_be + (first - c->be_lo), c->be_cnt * 4u, count * 4u,
+                         (size_t)EPV_BEV_PLANES * c->be_B, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+EPV_API int epv_get_branch_event_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                         uint64_t *sums) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  if (!sums) return fail(c, EPV_ERR_ARG, "null output");
+  if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
+  if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
+  if (n_windows == 0) return EPV_OK;
+  const uint64_t rows = (uint64_t)EPV_BEV_PLANES * c->be_B, bytes = rows * n_windows * 8u;
+  if (c->be_cnt == 0 || c->be_ng == 0) {   // this context counts no site
+    std::memset(sums, 0, bytes);
+    return EPV_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (bytes > c->be_out_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_be_out);
+    c->be_out_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->d_be_out, bytes));
+    c->be_out_cap = bytes;
+  }
+  if (W > c->be_ng) W = c->be_ng;   // one window holds the genome: the same sums, and w W cannot overflow
+  uint32_t Wp = 256u;
+  if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
+  const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
+  if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many windows in one call: read them out in pieces");
+  hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, c->stream,
+                     (const uint32_t *)c->d_be, c->be_B, c->be_cnt, c->be_g0 + c->be_lo, c->be_ng, W, Wp, first_window,
+                     n_windows, c->d_be_out);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(sums, c->d_be_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }

@@ -11,6 +11,9 @@
 // New: -l/--leaf-probs FILE: a file of the same shape with P(state 1) per leaf cell (N = 0.5): cells with a
 // probability strictly between 0 and 1 carry evidence (SingleSiteSampler::set_leaf_evidence) and are resampled;
 // 0 and 1 are data and must agree with the paths.  Not together with -m.
+// New: -c/--changes FILE with -w/--window W (default 1): the posterior branch-event maps of the B batch sweeps
+// (epv_set_branch_events: end state, net gain / loss, any change, gains, losses per branch and site), summed
+// over windows of W sites, as integers (epv::write_branch_events).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -35,8 +38,10 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file;
     size_t batch = 10, burnin = 10, n_points = 100;
+    const size_t no_window = std::numeric_limits<size_t>::max();
+    size_t window = no_window;
     size_t rng_seed = std::numeric_limits<size_t>::max();
 
     epv::OptionParser opt_parse(strip_path(argv[0]), "estimate evolutionary histories",
@@ -55,6 +60,9 @@ int main(int argc, const char **argv) {
                       missing_file);
     opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell (N = 0.5): evidence, resampled; 0 and 1 are data",
                       false, leaf_probs_file);
+    opt_parse.add_opt("changes", 'c', "output file of the branch-event maps of the batch sweeps (integer window sums)",
+                      false, changes_file);
+    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps (default 1)", false, window);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -75,6 +83,10 @@ int main(int argc, const char **argv) {
     }
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
+    if (window != no_window && changes_file.empty())
+      throw std::runtime_error("-w/--window belongs to -c/--changes: give the output file of the branch-event maps");
+    if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
+    if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
     const string param_file(leftover_args.front()), input_file(leftover_args.back());
 
@@ -115,6 +127,7 @@ int main(int argc, const char **argv) {
     mcmc.reset(the_model, th, paths);
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);
+    if (!changes_file.empty()) mcmc.set_branch_events(true);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -132,6 +145,14 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING AVERAGE OF " << n_samples << " SAMPLES: " << average_file << "]" << endl;
       epv::write_path_average(average_file, th.node_names, th.n_nodes(), out.n_sites, (uint32_t)n_points,
                               th.branches.data(), counts.data(), n_samples);
+    }
+    if (!changes_file.empty()) {
+      vector<uint64_t> sums;
+      uint64_t n_samples = 0;
+      mcmc.download_branch_event_windows(window, sums, n_samples);
+      if (VERBOSE) cerr << "[WRITING BRANCH EVENTS OF " << n_samples << " SAMPLES: " << changes_file << "]" << endl;
+      epv::write_branch_events(changes_file, th.node_names, th.n_nodes(), mcmc.branch_event_windows(window), window,
+                               th.branches.data(), sums.data(), n_samples);
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

@@ -19,6 +19,8 @@ struct epvd_sampler {
   epv::FlatPaths staged;   // between epvd_download_sizes and epvd_download
   std::vector<uint32_t> staged_avg;   // between epvd_path_average_sizes and epvd_download_path_average
   bool have_staged_avg = false;
+  std::vector<uint32_t> staged_events;   // between epvd_branch_events_sizes and epvd_download_branch_events
+  bool have_staged_events = false;
 };
 
 namespace {
@@ -186,5 +188,38 @@ EPVD_API int epvd_download_path_average(epvd_sampler *h, uint32_t *counts) {
     std::copy(h->staged_avg.begin(), h->staged_avg.end(), counts);
     h->staged_avg.clear();
     h->have_staged_avg = false;
+  });
+}
+
+EPVD_API int epvd_set_branch_events(epvd_sampler *h, int on) {
+  return guarded(h, [&] { h->s->set_branch_events(on != 0); });
+}
+EPVD_API int epvd_branch_events_sizes(epvd_sampler *h, uint64_t *n_values, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t ns = 0;
+    h->s->download_branch_events(h->staged_events, ns);
+    h->have_staged_events = true;
+    *n_values = h->staged_events.size();
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_branch_events(epvd_sampler *h, uint32_t *planes) {
+  return guarded(h, [&] {
+    if (!h->have_staged_events) throw std::runtime_error("epvd_branch_events_sizes first");
+    std::copy(h->staged_events.begin(), h->staged_events.end(), planes);
+    h->staged_events.clear();
+    h->have_staged_events = false;
+  });
+}
+EPVD_API int epvd_download_branch_event_windows(epvd_sampler *h, uint64_t W, uint64_t n_windows, uint64_t *sums,
+                                                uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> v;
+    uint64_t ns = 0;
+    if (n_windows != h->s->branch_event_windows(W))
+      throw std::runtime_error("epvd_download_branch_event_windows: n_windows must be ceil(genome length / W), W >= 1");
+    h->s->download_branch_event_windows(W, v, ns);
+    std::copy(v.begin(), v.end(), sums);
+    if (n_samples) *n_samples = ns;
   });
 }

@@ -656,6 +656,25 @@ void write_path_average(const std::string &file, const std::vector<std::string> 
   if (!out) throw std::runtime_error("error writing: " + file);
 }
 
+void write_branch_events(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                         uint64_t n_windows, uint64_t window, const double *branch_len, const uint64_t *sums,
+                         uint64_t n_samples) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#samples\t" << n_samples << "\twindow\t" << window << '\n';
+  const uint64_t B = (uint64_t)n_nodes - 1u;
+  for (int b = 1; b < n_nodes; ++b) {
+    out << "NODE:" << node_names[b] << "\t" << branch_len[b] << '\n';
+    for (uint64_t w = 0; w < n_windows; ++w) {
+      out << w * window;
+      for (uint64_t p = 0; p < 6u; ++p) out << "\t" << sums[(p * B + (uint64_t)(b - 1)) * n_windows + w];
+      out << '\n';
+    }
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
 }  // namespace epv
 
 namespace epv {

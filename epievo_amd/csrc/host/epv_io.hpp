@@ -57,6 +57,14 @@ void write_path_average(const std::string &file, const std::vector<std::string> 
                         uint64_t n_sites, uint32_t n_points, const double *branch_len, const uint32_t *counts,
                         uint64_t n_samples);
 
+// the window sums of the branch-event planes (epv_get_branch_event_windows), integers only so that files
+// compare exactly: "#samples\t<S>\twindow\t<W>", then per non-root node in pre-order
+// "NODE:<name>\t<branch_len>" (default ostream formatting) and one line per window: the window's first
+// global site and sums[(p * (n_nodes-1) + b-1) * n_windows + w] for the six planes p, tab-separated
+void write_branch_events(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                         uint64_t n_windows, uint64_t window, const double *branch_len, const uint64_t *sums,
+                         uint64_t n_samples);
+
 // the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
 // then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The
 // device keeps one length per branch, so paths whose tot_time differs from the tree's branch length

@@ -362,6 +362,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   build(th, paths, paths.n_sites, false);
   reset(m);
   if (pa_points_) set_path_average(pa_points_);
+  if (bevents_) set_branch_events(true);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -369,6 +370,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   build(th, owned, n_global, true);
   reset(m);
   if (pa_points_) set_path_average(pa_points_);
+  if (bevents_) set_branch_events(true);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -405,6 +407,61 @@ void SingleSiteSampler::download_path_average(std::vector<uint32_t> &counts, uin
       std::copy(part.begin() + b * count[i] * P, part.begin() + (b + 1) * count[i] * P,
                 counts.begin() + (b * total + at) * P);
     at += count[i];
+  }
+}
+
+void SingleSiteSampler::set_branch_events(bool on) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !on)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_branch_events(c, on ? 1 : 0), "epv_set_branch_events");
+  bevents_ = on;
+}
+
+static uint64_t branch_event_samples(const std::vector<epv_ctx *> &cs) {
+  uint64_t n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint64_t ns = 0;
+    if (epv_branch_events_samples(cs[i], &ns) != EPV_OK) throw std::runtime_error("epv_branch_events_samples failed");
+    if (i == 0) n_samples = ns;
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of branch-event samples");
+  }
+  return n_samples;
+}
+
+void SingleSiteSampler::download_branch_events(std::vector<uint32_t> &planes, uint64_t &n_samples) {
+  if (!bevents_) throw std::runtime_error("branch events are off: set_branch_events first");
+  const std::vector<epv_ctx *> cs = contexts();
+  const uint64_t R = 6u * ((uint64_t)n_nodes_ - 1u);
+  std::vector<uint64_t> first(cs.size()), count(cs.size());
+  uint64_t total = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    check_on(cs[i], epv_branch_events_layout(cs[i], &first[i], &count[i]), "epv_branch_events_layout");
+    total += count[i];
+  }
+  n_samples = branch_event_samples(cs);
+  planes.assign(R * total, 0u);
+  std::vector<uint32_t> part;
+  uint64_t at = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {   // contexts in genome order, each one's sites contiguous
+    part.assign(R * count[i], 0u);
+    if (count[i]) check_on(cs[i], epv_get_branch_events(cs[i], first[i], count[i], part.data()), "epv_get_branch_events");
+    for (uint64_t r = 0; r < R; ++r)
+      std::copy(part.begin() + r * count[i], part.begin() + (r + 1) * count[i], planes.begin() + r * total + at);
+    at += count[i];
+  }
+}
+
+void SingleSiteSampler::download_branch_event_windows(uint64_t W, std::vector<uint64_t> &sums, uint64_t &n_samples) {
+  if (!bevents_) throw std::runtime_error("branch events are off: set_branch_events first");
+  if (W == 0) throw std::runtime_error("a window holds at least one site");
+  const std::vector<epv_ctx *> cs = contexts();
+  const uint64_t R = 6u * ((uint64_t)n_nodes_ - 1u), nw = (n_sites_ + W - 1u) / W;
+  n_samples = branch_event_samples(cs);
+  sums.assign(R * nw, 0u);
+  std::vector<uint64_t> part(R * nw);
+  for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites
+    check_on(c, epv_get_branch_event_windows(c, W, 0u, nw, part.data()), "epv_get_branch_event_windows");
+    for (size_t k = 0; k < part.size(); ++k) sums[k] += part[k];
   }
 }
 

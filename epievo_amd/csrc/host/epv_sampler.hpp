@@ -108,6 +108,16 @@ public:
   void set_path_average(uint32_t n_points);
   void download_path_average(std::vector<uint32_t> &counts, uint64_t &n_samples);
   uint32_t path_average_points() const { return pa_points_; }
+  // posterior branch-event maps (epv_set_branch_events) on every context, with the path average's
+  // samples and lifecycle (the setting carries over to the contexts of a later reset(model, tree, paths),
+  // which starts the planes from zero).  download_branch_events: planes[(p * (n_nodes-1) + b-1) * sites +
+  // site] over the sites of this process in genome order; download_branch_event_windows: sums[(p *
+  // (n_nodes-1) + b-1) * n_windows + w] over windows of W global sites, all contexts of this process added
+  void set_branch_events(bool on);
+  bool branch_events_on() const { return bevents_; }
+  uint64_t branch_event_windows(uint64_t W) const { return W ? (n_sites_ + W - 1u) / W : 0u; }   // windows of the genome
+  void download_branch_events(std::vector<uint32_t> &planes, uint64_t &n_samples);
+  void download_branch_event_windows(uint64_t W, std::vector<uint64_t> &sums, uint64_t &n_samples);
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
@@ -200,6 +210,7 @@ private:
   uint64_t stat_batch_ = 0;   // batch the statistics pieces are sized for
   uint32_t capacity_;
   uint32_t pa_points_ = 0;    // set_path_average
+  bool bevents_ = false;      // set_branch_events
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

@@ -15,7 +15,9 @@ vp, dp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8
 DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_destroy", "epvd_last_error", "epvd_shard_cuts",
                   "epvd_reset", "epvd_reset_model", "epvd_run_mcmc", "epvd_scale_jump_times", "epvd_download_sizes",
                   "epvd_download", "epvd_layout", "epvd_set_options", "epvd_set_timing", "epvd_kernel_time_ms",
-                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average"]
+                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average",
+                  "epvd_set_branch_events", "epvd_branch_events_sizes", "epvd_download_branch_events",
+                  "epvd_download_branch_event_windows"]
 
 
 def lib():
@@ -49,6 +51,10 @@ def lib():
         L.epvd_set_path_average.argtypes = [vp, C.c_uint32]
         L.epvd_path_average_sizes.argtypes = [vp, u64p, u32p, u64p]
         L.epvd_download_path_average.argtypes = [vp, u32p]
+        L.epvd_set_branch_events.argtypes = [vp, C.c_int]
+        L.epvd_branch_events_sizes.argtypes = [vp, u64p, u64p]
+        L.epvd_download_branch_events.argtypes = [vp, u32p]
+        L.epvd_download_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, u64p]
         _lib = L
     return _lib
 
@@ -88,7 +94,7 @@ class CppSampler:
             self.h = self.L.epvd_create_rank(self.burn_in, self.batch, device, world, r, idb, capacity)
         if not self.h:
             raise DriverError(self.L.epvd_last_error(None).decode())
-        self.B = 0
+        self.B = self.n_global = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -109,6 +115,7 @@ class CppSampler:
             self._ck(self.L.epvd_reset_model(self.h, _p(rates, C.c_double), _p(T, C.c_double)))
             return
         self.B, self.n_nodes = tree.n_nodes - 1, tree.n_nodes
+        self.n_global = int(n_global) or fp.n_sites
         jumps = fp.jumps if len(fp.jumps) else np.zeros(1)
         self._ck(self.L.epvd_reset(self.h, _p(rates, C.c_double), _p(T, C.c_double), tree.n_nodes,
                                    _p(tree.parent_ids, C.c_uint32), _p(tree.subtree_sizes, C.c_uint32),
@@ -202,3 +209,28 @@ class CppSampler:
         out = out[:nv.value].reshape(self.B, -1, P.value)
         ns = int(ns.value)
         return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def enable_branch_events(self, on=True):
+        """posterior branch-event maps on every context (False = off); kept across reset()"""
+        self._ck(self.L.epvd_set_branch_events(self.h, 1 if on else 0))
+
+    def branch_events(self, counts=False):
+        """-> (samples, [6, N-1, sites]) over the sites of this process: float64 counts / samples or uint32 counts"""
+        nv, ns = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epvd_branch_events_sizes(self.h, C.byref(nv), C.byref(ns)))
+        out = np.zeros(max(nv.value, 1), np.uint32)
+        self._ck(self.L.epvd_download_branch_events(self.h, _p(out, C.c_uint32)))
+        out = out[:nv.value].reshape(6, self.B, -1)
+        ns = int(ns.value)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def branch_event_windows(self, W):
+        """-> (samples, uint64 [6, N-1, windows]): the planes summed over windows of W global sites (the
+        contexts of this process added)"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        nw = (self.n_global + W - 1) // W
+        out, ns = np.zeros((6, self.B, nw), np.uint64), C.c_uint64(0)
+        self._ck(self.L.epvd_download_branch_event_windows(self.h, W, nw, _p(out, C.c_uint64), C.byref(ns)))
+        return int(ns.value), out

@@ -326,6 +326,59 @@ class ShardedSampler:
                                  axis=1)
         return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
 
+    # ---- posterior branch-event maps: every rank counts its owned columns
+    def enable_branch_events(self, on=True):
+        self.dev.enable_branch_events(on)
+
+    def reset_branch_events(self):
+        self.dev.reset_branch_events()
+
+    def accumulate_branch_events(self):
+        self.dev.accumulate_branch_events()
+
+    def _gather_words(self, mine):
+        """all-gather equal-sized uint32 pieces -> [world, words]"""
+        words = len(mine)
+        piece, gathered = self.dev.alloc(4 * words), self.dev.alloc(4 * words * self.comm.world)
+        try:
+            self.dev.write(piece, 0, mine)
+            self.comm.all_gather(self.dev, piece, gathered)
+            return self.dev.read(gathered, 0, words * self.comm.world, np.uint32).reshape(self.comm.world, words)
+        finally:
+            piece.free()
+            gathered.free()
+
+    def branch_events(self, counts=False):
+        """-> (samples, [6, N-1, n_global]) of the whole genome, identical on every rank: the ranks'
+        planes are all-gathered (one collective) and concatenated in genome order"""
+        ns, own = self.dev.branch_events(counts=True)
+        if self.comm.world > 1:
+            R = own.shape[0] * own.shape[1]
+            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
+            if own.shape[2] != sizes[self.comm.rank]:
+                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[2], sizes[self.comm.rank]))
+            mine = np.zeros(R * max(sizes) + 2, np.uint32)       # planes, then the sample count (two words)
+            mine[:-2].reshape(R, max(sizes))[:, :own.shape[2]] = own.reshape(R, -1)
+            mine[-2:] = [ns & 0xffffffff, ns >> 32]
+            allw = self._gather_words(mine)
+            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of branch-event samples")
+            own = np.concatenate([allw[r, :-2].reshape(R, max(sizes))[:, :sizes[r]] for r in range(self.comm.world)],
+                                 axis=1).reshape(own.shape[0], own.shape[1], -1)
+        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
+
+    def branch_event_windows(self, W):
+        """-> (samples, uint64 [6, N-1, windows]) of the whole genome, identical on every rank: the ranks'
+        contributions (windows of global sites) are all-gathered and summed"""
+        ns, own = self.dev.branch_event_windows(W)
+        if self.comm.world > 1:
+            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
+            allw = self._gather_words(mine).view(np.uint64)
+            if any(int(w[-1]) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of branch-event samples")
+            own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
+        return ns, own
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -580,6 +633,43 @@ class LocalGroup:
             raise RuntimeError("the shards of the group hold different numbers of path-average samples")
         out = np.concatenate([p[1] for p in parts], axis=1)
         return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    # ---- posterior branch-event maps: every shard counts the sites it owns
+    def enable_branch_events(self, on=True):
+        self._each(lambda j, s: s.enable_branch_events(on))
+
+    def reset_branch_events(self):
+        self._each(lambda j, s: s.reset_branch_events())
+
+    def accumulate_branch_events(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a branch-event sample")
+        self._each(lambda j, s: s.accumulate_branch_events())
+
+    def branch_events_samples(self):
+        return self.subs[0].branch_events_samples()
+
+    def _same_samples(self, parts):
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of branch-event samples")
+        return ns
+
+    def branch_events(self, counts=False):
+        """-> (samples, [6, N-1, sites]) over the group's owned sites, shards in genome order"""
+        parts = self._each(lambda j, s: s.branch_events(counts=True))
+        ns = self._same_samples(parts)
+        out = np.concatenate([p[1] for p in parts], axis=2)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def branch_event_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [6, N-1, windows]): the shards' contributions to the windows of W global
+        sites, added"""
+        if n_windows is None:
+            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
+        parts = self._each(lambda j, s: s.branch_event_windows(W, first_window, n_windows))
+        return self._same_samples(parts), sum(p[1] for p in parts)
 
     def counters(self):
         out = {}

@@ -50,7 +50,13 @@ ABI_SYMBOLS = [
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
+    "epv_set_branch_events", "epv_reset_branch_events", "epv_accumulate_branch_events", "epv_branch_events_samples",
+    "epv_branch_events_set_samples", "epv_branch_events_layout", "epv_get_branch_events",
+    "epv_get_branch_event_windows",
 ]
+
+# planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
+BRANCH_EVENT_PLANES = ("end1", "net_gain", "net_loss", "changed", "gains", "losses")
 
 
 def lib():
@@ -130,6 +136,14 @@ def lib():
         L.epv_path_average_samples.argtypes = [vp, u64p]
         L.epv_get_path_average.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
         L.epv_path_average_layout.argtypes = [vp, u32p, u64p, u64p]
+        L.epv_set_branch_events.argtypes = [vp, C.c_int]
+        L.epv_reset_branch_events.argtypes = [vp]
+        L.epv_accumulate_branch_events.argtypes = [vp]
+        L.epv_branch_events_samples.argtypes = [vp, u64p]
+        L.epv_branch_events_set_samples.argtypes = [vp, C.c_uint64]
+        L.epv_branch_events_layout.argtypes = [vp, u64p, u64p]
+        L.epv_get_branch_events.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
+        L.epv_get_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -169,6 +183,7 @@ class DeviceSampler:
             raise RuntimeError("epv_create(%d) failed: no usable HIP device (this build has no "
                                "CPU fallback)" % device)
         self.n_sites = self.n_nodes = self.B = 0
+        self.n_global = 0             # genome length as upload_paths set it
         self.auto_grow = False     # True: widen the jump slots after an overflow and carry on
         self.capacity_events = []  # messages of the overflows that were absorbed
         self.halo = (0, 0)
@@ -300,6 +315,7 @@ class DeviceSampler:
                                          capacity, global_site_offset))
         if n_global is not None:
             self._ck(self.L.epv_set_global_length(self.h, n_global))
+        self.n_global = int(global_site_offset + fp.n_sites if n_global is None else n_global)
         self.halo = (0, 0)
 
     def init_paths_indep(self, root, leaf, seed, capacity=0):
@@ -528,6 +544,51 @@ class DeviceSampler:
         ns = self.path_average_samples()
         return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
 
+    # ---- posterior branch-event maps (epv_set_branch_events)
+    def enable_branch_events(self, on=True):
+        """count end states, net and total gains and losses per (branch, site) after every batch sweep
+        of run_mcmc (BRANCH_EVENT_PLANES; False = off)"""
+        self._ck(self.L.epv_set_branch_events(self.h, 1 if on else 0))
+
+    def reset_branch_events(self):
+        self._ck(self.L.epv_reset_branch_events(self.h))
+
+    def accumulate_branch_events(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_branch_events(self.h))
+
+    def branch_events_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_branch_events_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def branch_events_layout(self):
+        """(first local site, number of sites) of the planes: the sites of path_average_layout"""
+        a, k = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_branch_events_layout(self.h, C.byref(a), C.byref(k)))
+        return int(a.value), int(k.value)
+
+    def branch_events(self, counts=False):
+        """-> (samples, array [6, N-1, sites]): float64 counts / samples, or the uint32 counts"""
+        first, cnt = self.branch_events_layout()
+        out = np.zeros((len(BRANCH_EVENT_PLANES), self.B, cnt), np.uint32)
+        self._ck(self.L.epv_get_branch_events(self.h, first, cnt, _p(out, C.c_uint32)))
+        ns = self.branch_events_samples()
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def branch_event_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [6, N-1, windows]): the planes summed over windows of W consecutive global
+        sites, this context's contribution (zero where it counts no site); all windows of the genome
+        unless a range is given"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        if n_windows is None:
+            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
+        out = np.zeros((len(BRANCH_EVENT_PLANES), self.B, max(int(n_windows), 0)), np.uint64)
+        self._ck(self.L.epv_get_branch_event_windows(self.h, W, int(first_window), out.shape[2], _p(out, C.c_uint64)))
+        return self.branch_events_samples(), out
+
 
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
@@ -622,3 +683,19 @@ class SingleSiteSampler:
 
     def path_average(self, counts=False):
         return self.dev.path_average(counts)
+
+    # posterior branch-event maps (DeviceSampler.enable_branch_events)
+    def enable_branch_events(self, on=True):
+        self.dev.enable_branch_events(on)
+
+    def reset_branch_events(self):
+        self.dev.reset_branch_events()
+
+    def accumulate_branch_events(self):
+        self.dev.accumulate_branch_events()
+
+    def branch_events(self, counts=False):
+        return self.dev.branch_events(counts)
+
+    def branch_event_windows(self, W):
+        return self.dev.branch_event_windows(W)

@@ -405,6 +405,44 @@ int epv_get_path_average(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t 
  * sites makes the next sample fail until epv_set_path_average is called again. */
 int epv_path_average_layout(epv_ctx *ctx, uint32_t *n_points, uint64_t *first, uint64_t *count);
 
+/* ---- posterior branch-event maps (new): where in the genome, and on which branch, the state changed.
+ * A sample reads, per branch b and site s, the init state a and the number of jumps k of the resident
+ * path (no jump times) and adds to six uint32 planes, with e = a XOR (k & 1) the state at the child node,
+ * g = (k + (a == 0)) >> 1 the 0->1 jumps and l = k - g the 1->0 jumps:
+ *   0 end1 += e          1 net_gain += (a == 0 && e == 1)    2 net_loss += (a == 1 && e == 0)
+ *   3 changed += (k >= 1)    4 gains += g                    5 losses += l
+ * Divided by the sample count: P(state 1 at the child node) -- the imputed state of an open leaf cell --,
+ * P(0 -> 1 end to end), P(1 -> 0 end to end), P(any jump, reverted ones included), E[gains], E[losses].
+ * The start state needs no plane: start1 = end1 - net_gain + net_loss; the root's state is start1 of a
+ * branch below the root.  Samples, sites and lifecycle are the path average's: a sample after each batch
+ * sweep of epv_run_mcmc / _sums / _counts (not the burn-in) or one epv_accumulate_branch_events call;
+ * the owned sites plus the genome's end sites where the context holds them (over all contexts every site
+ * once); kept over epv_reset, epv_set_model, capacity growth, epv_scale_jump_times, masks, evidence and
+ * epv_sweep_phase; a site range that changes after samples were taken is EPV_ERR_STATE.  There is no
+ * grid, so branch lengths do not matter.  Exact integers: they depend on no kernel path, context or GPU.
+ * Either, both or neither of the two accumulators may be on; off (the default) allocates and launches
+ * nothing.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_branch_events: on != 0 allocates 24 (N-1) bytes per counted site (checked against the free
+ *   device memory first; the message gives the figure) and zeroes the planes; 0 frees them.
+ * A path holds at most 2047 jumps, so g <= 1024: the planes take 2^21 samples; a sample (or a run whose
+ *   batch would pass that) beyond is EPV_ERR_STATE.  epv_branch_events_set_samples overwrites the sample
+ *   count and nothing else (a hook for testing that cap).
+ * epv_branch_events_layout: the local sites first .. first+count-1 the planes cover (0, 0 when off).
+ * epv_get_branch_events: planes[p][b-1][s - first] (uint32) of local sites first .. first+count-1.
+ * epv_get_branch_event_windows: sums[p][b-1][w - first_window] (uint64) = the planes summed over window
+ *   w = GLOBAL sites [w W, (w+1) W), for n_windows windows from first_window; this context's contribution
+ *   only, zero where it counts no site, so the contributions of contexts, shards and GPUs add up to the
+ *   one-context result.  W = 1 gives the per-site planes, a W beyond the genome one window. */
+int epv_set_branch_events(epv_ctx *ctx, int on);
+int epv_reset_branch_events(epv_ctx *ctx);
+int epv_accumulate_branch_events(epv_ctx *ctx);
+int epv_branch_events_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_branch_events_set_samples(epv_ctx *ctx, uint64_t n_samples);
+int epv_branch_events_layout(epv_ctx *ctx, uint64_t *first, uint64_t *count);
+int epv_get_branch_events(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *planes);
+int epv_get_branch_event_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                 uint64_t *sums);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

@@ -71,6 +71,17 @@ int epvd_set_path_average(epvd_sampler *s, uint32_t n_points);
 int epvd_path_average_sizes(epvd_sampler *s, uint64_t *n_values, uint32_t *n_points, uint64_t *n_samples);
 int epvd_download_path_average(epvd_sampler *s, uint32_t *counts);
 
+/* posterior branch-event maps (epv_set_branch_events on every context; kept across epvd_reset, which starts
+ * the planes from zero), and the six planes over the sites of this process in genome order: sizes first
+ * (n_values = 6 * (n_nodes - 1) * sites), then the copy of planes[(p * (n_nodes-1) + b-1) * sites + site].
+ * epvd_download_branch_event_windows: sums[(p * (n_nodes-1) + b-1) * n_windows + w] over windows of W
+ * global sites, the contexts of this process added; n_windows must be ceil(genome length / W) */
+int epvd_set_branch_events(epvd_sampler *s, int on);
+int epvd_branch_events_sizes(epvd_sampler *s, uint64_t *n_values, uint64_t *n_samples);
+int epvd_download_branch_events(epvd_sampler *s, uint32_t *planes);
+int epvd_download_branch_event_windows(epvd_sampler *s, uint64_t W, uint64_t n_windows, uint64_t *sums,
+                                       uint64_t *n_samples);
+
 #ifdef __cplusplus
 }
 #endif
