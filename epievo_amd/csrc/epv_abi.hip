@@ -2283,7 +2283,7 @@ EPV_API int epv_get_counters(epv_ctx *c, epv_counters *out) {
   out->n_overflow = cnt[EPV_CNT_OVERFLOW];
   out->n_coop_tasks = cnt[EPV_CNT_COOP];
   out->n_sweeps = c->n_sweeps;
-  out->reserved = 0;
+  out->n_search_finished = cnt[EPV_CNT_SEARCH_FINISHED];
   return EPV_OK;
 }
 

@@ -38,7 +38,8 @@ struct EpvSegTask {      // one dirty segment of a proposal: sample its jump tim
   unsigned long long w0; // site | node << 40 | segment index << 52
   double len;            // segment length (< 0: blank entry)
   double start;          // time of the segment's start on the branch
-  unsigned long long w3; // start state | end state << 1 | trip0 << 2
+  unsigned long long w3; // start state | end state << 1 | trip0 << 2 | (fused phase) sole dirty segment of its
+                         // branch << 5 | the proposal's buffer << 6
 };
 struct EpvSegOut {       // what the search found
   uint32_t cnt;          // jumps of the winning trial
@@ -112,7 +113,8 @@ struct EpvIndepConst {
 enum { EPV_CNT_ACCEPT = 0, EPV_CNT_OVERFLOW = 1, EPV_CNT_COOP = 2, EPV_CNT_TASKS = 3, EPV_CNT_TASKS2 = 4,
        EPV_CNT_ALIST0 = 5, EPV_CNT_ALIST1 = 6,   // accept-list lengths, double-buffered by phase parity
        EPV_CNT_SEG = 7,                          // dirty segments (low word) and their branches (high word)
-       EPV_CNT_N = 8 };
+       EPV_CNT_SEARCH_FINISHED = 8,              // fused phase: branches finished by the grouped search (of EPV_CNT_COOP)
+       EPV_CNT_N = 9 };
 // Every counter is sharded 64 ways with a 128-byte stride (one device-scope atomic word
 // saturates near 90 ops/us; 5000 waves hitting ONE word would serialise for ~60 us).
 // A block uses shard (blockIdx.x & 63); the host sums the shards.

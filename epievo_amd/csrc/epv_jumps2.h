@@ -25,6 +25,10 @@
 //                            Times come from the search (<= 2 jumps) or from replaying trial t*
 //                            (random-access RNG) straight into the path.
 //
+// Who finishes a branch: epv_seg_assemble_one, except in the fused phase, where the grouped search
+// (epv_seg_search_grouped) finishes a branch whose sole dirty segment it has just settled; the
+// fused body skips the assembly for a wave all of whose branches were finished that way.
+//
 // Branches with more than 64 segments, or that find the lists full, stay with
 // epv_mh_jumps_kernel (launched behind these two with a small grid; it finds empty lists
 // otherwise).
@@ -166,9 +170,19 @@ __global__ __launch_bounds__(256, EPV_SEARCH_WAVES) void epv_seg_search_kernel(E
 // trial up to it, whoever evaluated them, so the results are those of epv_seg_search_wave.
 // Returns false when some segment is still open after `rounds` rounds (long tails belong to the
 // wave-wide cooperative search): the caller then runs epv_seg_search_wave over the whole list.
+//
+// A segment that is the SOLE dirty segment of its branch (task word w3 bit 5; bit 6 = the proposal's
+// buffer) is all the assembly would walk for that branch, and the group's winning lane holds all
+// of it: the jump count, the two times, M, and the segment's start state, which is the branch's
+// (every earlier segment is clean and keeps its state).  With at most two jumps and M within the
+// capacity the lane therefore FINISHES the branch -- the stores of epv_seg_assemble_one for
+// nds = 1: times into the proposal, the meta word to global memory and into the wave's LDS column
+// prop_meta[b * 64 + owner].  outs[seg] is written all the same, so an assembly that runs anyway
+// re-stores the same values.  n_finished (wave-uniform) counts the branches finished here.
 __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
                                                        EpvSegOut *outs, uint32_t n_seg, uint32_t G, uint32_t rounds,
-                                                       uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, bool nielsen) {
+                                                       uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, bool nielsen,
+                                                       epv_meta_t *prop_meta, uint64_t site_lane0, uint32_t &n_finished) {
   const int lane = epv_lane();
   const uint32_t seg = (uint32_t)lane / G, sub = (uint32_t)lane - seg * G, gbase = seg * G;
   EpvSegTask t;
@@ -177,8 +191,10 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
   const uint32_t gsite = (uint32_t)(S.g0 + (t.w0 & 0xffffffffffull));
   const uint32_t node = (uint32_t)(t.w0 >> 40) & 4095u, k = (uint32_t)(t.w0 >> 52);
   const uint32_t prev = (uint32_t)t.w3 & 1u, sampled = (uint32_t)(t.w3 >> 1) & 1u, trip0 = (uint32_t)(t.w3 >> 2) & 7u;
+  const bool sole = (t.w3 >> 5) & 1ull;
   const double len = t.len, r0 = s_rates[trip0], r1 = s_rates[trip0 | 2u];
   bool pend = seg < n_seg && t.len >= 0.0;
+  n_finished = 0u;
   double trunc = 0.0;
   if (pend && sampled != prev) trunc = 1.0 - epv_exp(-(prev ? r1 : r0) * len);
   uint32_t tcur = 1u + sub, hist = 0u;      // hist: most jumps of this lane's failed trials so far
@@ -199,18 +215,31 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
       const uint32_t v = __shfl(m, (int)((gbase + q) & 63u));
       m_all = v > m_all ? v : m_all;
     }
+    bool fin = false;
     if (pend && gh) {
       if (sub == wsub) {
         EpvSegOut o;
         o.cnt = cnt; o.tstar = tcur; o.maxm = m_all; o.pad = 0u;
         o.j0 = jt[0]; o.j1 = jt[1];
         outs[seg] = o;
+        fin = sole && cnt <= 2u && m_all <= S.C;
+        if (fin) {
+          const uint64_t site = t.w0 & 0xffffffffffull;
+          const uint32_t b = node - 1u, selP = (uint32_t)(t.w3 >> 6) & 1u;
+          double *dst = S.jumps + jump_idx(S, selP, b, site);
+          if (cnt >= 1u) dst[0] = jt[0];
+          if (cnt >= 2u) dst[S.n] = jt[1];
+          const epv_meta_t mw = (epv_meta_t)((prev << EPV_INIT_SHIFT) | cnt);
+          S.meta[meta_idx(S, selP, b, site)] = mw;
+          prop_meta[b * 64u + (uint32_t)(site - site_lane0) / 3u] = mw;
+        }
       }
       pend = false;
     } else {
       hist = m;
       tcur += G;
     }
+    n_finished += (uint32_t)__popcll(__ballot(fin));
   }
   return !__any(pend);
 }

@@ -140,6 +140,10 @@ __device__ unsigned long long epv_p2_prof[16 * EPV_P2_PROF_ROWS];
 // Every site of a colour is independent of the others, so nothing in a phase needs more than a
 // wave; what the separate kernels buy is dense lanes, and what they cost is one ~20 us wave chain
 // per kernel, which is all there is to pay when a launch has fewer waves than the chip has SIMDs.
+// Who finishes a branch (times and meta word of the proposal): the grouped search's winning lane, for
+// a branch whose sole dirty segment it has just settled with at most two jumps and room for them
+// (the segment task says so: w3 bits 5, 6); the assembly stage for every branch of the wave
+// otherwise -- it is skipped only when the search has finished ALL of the wave's branches.
 struct EpvFused {
   EpvSegTask *segs;            // [waves][seg_cap]
   EpvSegOut *outs;             // [waves][seg_cap]
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   }
   P2_MARK(0);
   // FUSED: lengths of the wave's private lists (wave-uniform), and which lanes' sites await acceptance
-  uint32_t f_nseg = 0u, f_nbt = 0u;
+  uint32_t f_nseg = 0u, f_nbt = 0u, f_nsole = 0u;    // f_nsole: branches with one dirty segment
   bool f_listed = false;
   const uint64_t f_wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave_id;
   bool pending = valid;
@@ -844,13 +848,16 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               t.w0 = osite | ((unsigned long long)node << 40) | ((unsigned long long)k << 52);
               t.len = len;
               t.start = tp;
-              t.w3 = prev | (sampled << 1) | (trip0 << 2);
+              // bit 5: the sole dirty segment of its branch, bit 6: the proposal's buffer -- the grouped
+              // search finishes such a branch itself (epv_jumps2.h)
+              t.w3 = prev | (sampled << 1) | (trip0 << 2) | (nds == 1u ? 32u | ((selM_o ^ 1u) << 6) : 0u);
               segs_w[at++] = t;
             }
             tp += len;
             prev = sampled;
           }
         }
+        f_nsole += (uint32_t)__popcll(__ballot(act && nds == 1u));
         f_nseg += totS;
         f_nbt += (totP - p0 < 64u) ? totP - p0 : 64u;
       }
@@ -871,6 +878,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     // one writes back and invalidates the XCD's L2, ~30 us each here
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
+    uint32_t f_nfin = 0u;      // branches the grouped search finished
     if (f_nseg) {
       EpvCoop W;
       W.len = pool; W.r0 = pool + 64; W.r1 = pool + 128; W.trunc = pool + 192; W.tj = pool + 256;
@@ -881,17 +889,23 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       bool done = false;
       if (f_nseg <= 32u && F.grouped_rounds) {
         const uint32_t G = 64u / f_nseg > 8u ? 8u : 64u / f_nseg;
-        done = epv_seg_search_grouped(S, s_rates, segs, outs, f_nseg, G, F.grouped_rounds, seed_lo, seed_hi, sweep, nielsen);
+        done = epv_seg_search_grouped(S, s_rates, segs, outs, f_nseg, G, F.grouped_rounds, seed_lo, seed_hi, sweep, nielsen,
+                                      s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane, f_nfin);
       }
       if (!done) epv_seg_search_wave(S, s_rates, W, segs, outs, f_nseg, 0u, 64u, seed_lo, seed_hi, sweep, nielsen);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
       P2_MARK(7);
-      for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
-        epv_seg_assemble_one(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
-                             seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane);
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      __builtin_amdgcn_wave_barrier();
+      // the grouped search has finished every branch (each had one dirty segment, <= 2 jumps, room):
+      // nothing is left to assemble.  In EVERY other case the assembly walks the whole branch list
+      // and stores the finished branches' values once more.
+      if (!(done && f_nsole == f_nbt && f_nfin == f_nbt)) {
+        for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
+          epv_seg_assemble_one(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
+                               seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+      }
       P2_MARK(8);
     }
     // ---- acceptance.  A site's ratio needs the three triples around it (log_accept_rate,
@@ -990,6 +1004,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       if (am) atomicAdd(&counters[EPV_CNT_IDX(EPV_CNT_ACCEPT, my_shard)], (unsigned long long)__popcll(am));
       if (om) atomicAdd(&counters[EPV_CNT_IDX(EPV_CNT_OVERFLOW, my_shard)], (unsigned long long)__popcll(om));
       if (f_nbt) atomicAdd(&counters[EPV_CNT_IDX(EPV_CNT_COOP, my_shard)], (unsigned long long)f_nbt);
+      if (f_nfin) atomicAdd(&counters[EPV_CNT_IDX(EPV_CNT_SEARCH_FINISHED, my_shard)], (unsigned long long)f_nfin);
     }
   }
 #ifdef EPV_P2_PROFILE

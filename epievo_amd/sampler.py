@@ -30,7 +30,7 @@ class CapacityError(EpvError):
 
 class _Counters(C.Structure):
     _fields_ = [("n_overflow", C.c_uint64), ("n_coop_tasks", C.c_uint64),
-                ("n_sweeps", C.c_uint64), ("reserved", C.c_uint64)]
+                ("n_sweeps", C.c_uint64), ("n_search_finished", C.c_uint64)]
 
 
 MAX_CAPACITY = 2047    # EPV_MAX_CAP: jump slots per (site, branch)
@@ -494,7 +494,8 @@ class DeviceSampler:
     def counters(self):
         c = _Counters()
         self._ck(self.L.epv_get_counters(self.h, C.byref(c)))
-        return {"overflow": c.n_overflow, "coop_tasks": c.n_coop_tasks, "sweeps": c.n_sweeps}
+        return {"overflow": c.n_overflow, "coop_tasks": c.n_coop_tasks, "sweeps": c.n_sweeps,
+                "search_finished": c.n_search_finished}
 
     def set_timing(self, on):
         self._ck(self.L.epv_set_timing(self.h, int(on)))

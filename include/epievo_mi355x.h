@@ -47,7 +47,7 @@ typedef struct {
   uint64_t n_overflow;   /* proposals rejected because a branch exceeded `capacity` jumps */
   uint64_t n_coop_tasks; /* rejection tasks resolved by the wave-cooperative search */
   uint64_t n_sweeps;     /* colour-complete sweeps executed since create */
-  uint64_t reserved;
+  uint64_t n_search_finished; /* of n_coop_tasks (fused phase): branches the segment search finished itself */
 } epv_counters;
 
 /* Run-time options of a context (epv_set_options; default 0).
