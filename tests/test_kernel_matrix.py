@@ -22,6 +22,13 @@ Coverage (variant x options -> rows):
                                              frref-bal16, sr-bal16; default: n129, multi-no-v3, unary-q64
   V1's LEAF template axis (mask, evidence)   test_leaf_matrix.py: all eight (pool, ratio, leaf mode)
                                              instantiations against rung B with its own leaf vector
+  dense histories (tens of jumps per path,   test_dense_histories_gpu.py: every row here draws its histories from
+  where the rows above have two or three)    test.param on branches of 0.02 - 0.8, which the reference model
+                                             forces (it accepts nothing on dense input); the rows there use two
+                                             other models (dense_cases.py) and cover more than 64 segments on a
+                                             branch, two and more words of proposal states, the fused phase at
+                                             C = 31 with every branch heavy, the statistics kernels' merge rings
+                                             and the accumulate kernels
 """
 import json
 import os
