@@ -21,6 +21,7 @@
 #include "epv_math.h"
 #include "epv_pavg.h"
 #include "epv_bevents.h"
+#include "epv_wstat.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
 // Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
@@ -150,6 +151,15 @@ struct epv_ctx {
   uint64_t be_samples = 0;
   unsigned long long *d_be_out = nullptr;   // window read-out staging
   uint64_t be_out_cap = 0;         // bytes
+  // regional sufficient statistics (epv_wstat.h), off while ws_W == 0
+  uint64_t ws_W = 0;               // sites per window, clamped to n_global
+  uint64_t ws_W_asked = 0;         // as epv_set_window_stats got it (a changed n_global clamps it again)
+  unsigned long long *d_ws = nullptr;   // [ws_nw][B][16] over the global windows ws_w0 .. ws_w0 + ws_nw - 1
+  uint64_t ws_w0 = 0, ws_nw = 0;
+  uint64_t ws_lo = 0, ws_hi = 0, ws_n = 0, ws_g0 = 0, ws_ng = 0;   // the site range d_ws was laid out for
+  uint32_t ws_B = 0;
+  uint64_t ws_samples = 0;
+  std::vector<double> ws_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -782,6 +792,128 @@ int launch_bevents(epv_ctx *c) {
   return EPV_OK;
 }
 
+// ---- regional sufficient statistics (epv_wstat.h): J and D per window of W global sites, over the
+// triples centred at the sites of owned_range (the statistics kernels' range, not pavg_range: the
+// genome's end sites centre no triple)
+// the statistics off: no accumulator, no layout, no samples
+void wstat_off(epv_ctx *c) {
+  dfree(c->d_ws);
+  c->ws_W = c->ws_W_asked = 0;
+  c->ws_w0 = c->ws_nw = 0;
+  c->ws_lo = c->ws_hi = c->ws_n = c->ws_g0 = c->ws_ng = 0;
+  c->ws_B = 0;
+  c->ws_samples = 0;
+  c->ws_scale.clear();
+}
+int wstat_alloc_try(epv_ctx *c) {
+  uint64_t lo = 0, hi = 0;
+  owned_range(c, &lo, &hi);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_ws);
+  c->ws_nw = 0;
+  c->ws_W = std::max<uint64_t>(1u, std::min<uint64_t>(c->ws_W_asked, c->S.n_global));
+  const bool any = hi >= lo && c->S.n >= 3u;
+  const uint64_t w0 = any ? (c->S.g0 + lo) / c->ws_W : 0u, nw = any ? (c->S.g0 + hi) / c->ws_W - w0 + 1u : 0u;
+  const double need = 128.0 * (double)c->S.B * (double)nw;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "window statistics need %.3g GB of device memory (128 B x %u branches x %llu windows "
+                  "of %llu sites); %.3g GB are free: use wider windows or more GPUs (the statistics are off)",
+                  need / 1e9, c->S.B, (unsigned long long)nw, (unsigned long long)c->ws_W, (double)free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t bytes = (size_t)128u * c->S.B * nw;
+  if (bytes) {
+    HIP_TRY(c, hipMalloc(&c->d_ws, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->d_ws, 0, bytes, c->stream));
+  }
+  c->ws_w0 = w0;
+  c->ws_nw = nw;
+  c->ws_lo = lo;
+  c->ws_hi = hi;
+  c->ws_n = c->S.n;
+  c->ws_g0 = c->S.g0;
+  c->ws_ng = c->S.n_global;
+  c->ws_B = c->S.B;
+  c->ws_samples = 0;
+  c->ws_scale.clear();
+  return EPV_OK;
+}
+// (re)lay out the accumulator for the current site range; zeroes it.  Whatever fails on the way (not enough
+// memory, a HIP error) leaves the statistics off: never a window size without its accumulator
+int wstat_alloc(epv_ctx *c) {
+  const int rc = wstat_alloc_try(c);
+  if (rc) wstat_off(c);
+  return rc;
+}
+// the accumulator matches the current site range, and the scales 2^k_b are the ones its integers were taken with
+int ensure_wstat(epv_ctx *c) {
+  if (!c->ws_W) return EPV_OK;
+  uint64_t lo = 0, hi = 0;
+  owned_range(c, &lo, &hi);
+  if (lo != c->ws_lo || hi != c->ws_hi || c->S.n != c->ws_n || c->S.g0 != c->ws_g0 || c->S.n_global != c->ws_ng ||
+      c->S.B != c->ws_B) {
+    if (c->ws_samples)
+      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the window statistics took samples: "
+                                    "epv_set_window_stats again");
+    const int rc = wstat_alloc(c);
+    if (rc) return rc;
+  }
+  const int rc = ensure_stat_scale(c);
+  if (rc) return rc;
+  if (c->ws_samples && c->ws_scale != c->statscale)
+    return fail(c, EPV_ERR_STATE, "the branch lengths or the genome length changed after the window statistics took "
+                                  "samples, so their fixed-point scales 2^k_b differ: read them out and "
+                                  "epv_reset_window_stats");
+  return EPV_OK;
+}
+// the most samples the 64-bit sums take: a site adds at most q_b = rint(T_b 2^k_b) + 3072 to a branch's D
+// per sample (half a quantum of rounding for each of at most 3 * 2047 + 1 intervals), a window holds at
+// most min(W, counted sites) sites: samples * sites * max_b q_b stays below 2^63
+uint64_t wstat_max_samples(const epv_ctx *c) {
+  uint64_t q = 0;   // (T_b 2^k_b < 2^50: exact in a double and in 64 bits)
+  for (uint32_t b = 1; b < c->S.N; ++b)
+    q = std::max<uint64_t>(q, (uint64_t)std::llrint(c->blen[b] * c->statscale[b]) + 3072u);
+  const uint64_t cnt = c->ws_hi >= c->ws_lo ? c->ws_hi - c->ws_lo + 1u : 0u;
+  const unsigned __int128 per = (unsigned __int128)std::min<uint64_t>(c->ws_W, cnt) * q;
+  if (!per) return UINT64_MAX;
+  return (uint64_t)((((unsigned __int128)1 << 63) - 1u) / per);   // the most m with m * per < 2^63
+}
+// `batch` more samples fit (ensure_wstat first)
+int wstat_check_cap(epv_ctx *c, uint64_t batch) {
+  const uint64_t most = wstat_max_samples(c);
+  if (c->ws_samples > most || batch > most - c->ws_samples) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "window statistics with windows of %llu sites take at most %llu samples in their "
+                  "64-bit sums and hold %llu: read them out and epv_reset_window_stats",
+                  (unsigned long long)c->ws_W, (unsigned long long)most, (unsigned long long)c->ws_samples);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_wstat first)
+int launch_wstat(epv_ctx *c) {
+  int rc = wstat_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->ws_nw) {
+    const uint64_t tiles = (c->ws_hi - c->ws_lo) / 64u + 1u;
+    if (tiles > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many sites in one context for the window statistics");
+    const dim3 grid((unsigned)tiles, (c->S.B + EPV_WSTAT_BCH - 1u) / EPV_WSTAT_BCH);
+    if (c->ws_W < 64u)
+      hipLaunchKernelGGL(epv_wstat_accum_kernel<true>, grid, dim3(64), 0, c->stream, c->S, c->ws_lo, c->ws_hi,
+                         c->d_statscale, c->ws_W, c->ws_w0, c->ws_nw, c->d_ws);
+    else
+      hipLaunchKernelGGL(epv_wstat_accum_kernel<false>, grid, dim3(64), 0, c->stream, c->S, c->ws_lo, c->ws_hi,
+                         c->d_statscale, c->ws_W, c->ws_w0, c->ws_nw, c->d_ws);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (!c->ws_samples) c->ws_scale = c->statscale;
+  ++c->ws_samples;
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -1121,6 +1253,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   dfree(c->d_be); dfree(c->d_be_out);
+  dfree(c->d_ws);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1942,7 +2075,7 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average sample; branch-event sample}: the chain of epv_run_mcmc_sums
+// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event and window-statistics sample}: the chain of epv_run_mcmc_sums
 // and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
 // snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
@@ -1953,6 +2086,8 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
   if (c->be_on && c->be_samples + batch > EPV_BEV_MAX_SAMPLES)   // (before any sweep: the chain is not cut short)
     return fail(c, EPV_ERR_STATE, "branch events would pass 2^21 samples, the most their 32-bit counts take: "
                                   "read them out and epv_reset_branch_events");
+  if ((rc = ensure_wstat(c))) return rc;
+  if (c->ws_W && (rc = wstat_check_cap(c, batch))) return rc;   // (before any sweep as well)
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -1967,6 +2102,7 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     if ((rc = stat(w))) return rc;
     if (c->pa_P && (rc = launch_pavg(c))) return rc;
     if (c->be_on && (rc = launch_bevents(c))) return rc;
+    if (c->ws_W && (rc = launch_wstat(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
@@ -2524,5 +2660,130 @@ EPV_API int epv_get_branch_event_windows(epv_ctx *c, uint64_t W, uint64_t first_
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(sums, c->d_be_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+// ---- regional sufficient statistics (epv_wstat.h)
+EPV_API int epv_set_window_stats(epv_ctx *c, uint64_t W) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!W) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    wstat_off(c);
+    return EPV_OK;
+  }
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->ws_W_asked = W;
+  if ((rc = wstat_alloc(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_reset_window_stats(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_ws) HIP_TRY(c, hipMemsetAsync(c->d_ws, 0, (size_t)128u * c->ws_B * c->ws_nw, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->ws_samples = 0;
+  c->ws_scale.clear();
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_window_stats(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_wstat(c)) || (rc = launch_wstat(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_window_stats_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->ws_W ? c->ws_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_window_stats_set_samples(epv_ctx *c, uint64_t n) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  if (n && c->ws_scale.empty()) {   // (as if the samples had been taken with the scales of now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_stat_scale(c);
+    if (rc) return rc;
+    c->ws_scale = c->statscale;
+  }
+  c->ws_samples = n;
+  if (!n) c->ws_scale.clear();
+  return EPV_OK;
+}
+
+EPV_API int epv_window_stats_scale_exps(epv_ctx *c, int *k) {
+  if (!c || !k) return EPV_ERR_ARG;
+  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
+  if (c->ws_scale.empty()) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_stat_scale(c);
+    if (rc) return rc;
+  }
+  const std::vector<double> &sc = c->ws_scale.empty() ? c->statscale : c->ws_scale;
+  for (uint32_t b = 1; b < c->S.N && b < sc.size(); ++b) k[b - 1u] = std::ilogb(sc[b]);   // (sc[b] = 2^k_b exactly)
+  return EPV_OK;
+}
+
+EPV_API int epv_window_stats_layout(epv_ctx *c, uint64_t *W, uint64_t *first_window, uint64_t *n_windows) {
+  if (!c || !W || !first_window || !n_windows) return EPV_ERR_ARG;
+  *W = *first_window = *n_windows = 0;
+  if (!c->ws_W) return EPV_OK;
+  if (c->have_tree && c->have_paths && c->ws_samples == 0) {   // lay out for the sites as they are now
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_wstat(c);
+    if (rc) return rc;
+  }
+  *W = c->ws_W;
+  *first_window = c->ws_w0;
+  *n_windows = c->ws_nw;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_window_stats(epv_ctx *c, uint64_t first_window, uint64_t n_windows, int64_t *counts) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  if (!counts) return fail(c, EPV_ERR_ARG, "null output");
+  if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
+  if (n_windows == 0) return EPV_OK;
+  const uint64_t V = (uint64_t)c->ws_B * 16u;
+  std::memset(counts, 0, n_windows * V * sizeof(int64_t));
+  const uint64_t a = std::max(first_window, c->ws_w0), e = std::min(first_window + n_windows, c->ws_w0 + c->ws_nw);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (a < e)
+    HIP_TRY(c, hipMemcpy(counts + (a - first_window) * V, c->d_ws + (a - c->ws_w0) * V, (e - a) * V * sizeof(int64_t),
+                         hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+EPV_API int epv_window_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64_t n_windows, uint64_t samples,
+                                       double *J, double *D) {
+  if (!c || !counts || !J || !D || !samples) return EPV_ERR_ARG;
+  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int rc = ensure_stat_scale(c);     // k_b depends on the genome length and the branch lengths
+  if (rc) return rc;
+  const uint32_t B = c->S.B;
+  const double ns = (double)samples;
+  for (uint64_t w = 0; w < n_windows; ++w)
+    for (uint32_t b = 0; b < B; ++b) {
+      const double inv = 1.0 / c->statscale[b + 1u];     // a power of two: exact
+      const int64_t *p = counts + (w * B + b) * 16u;
+      for (int k = 0; k < 8; ++k) {
+        J[(w * B + b) * 8u + k] = (double)p[k] / ns;
+        D[(w * B + b) * 8u + k] = (double)p[8 + k] * inv / ns;
+      }
+    }
   return EPV_OK;
 }

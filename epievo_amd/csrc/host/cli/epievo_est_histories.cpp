@@ -14,6 +14,10 @@
 // New: -c/--changes FILE with -w/--window W (default 1): the posterior branch-event maps of the B batch sweeps
 // (epv_set_branch_events: end state, net gain / loss, any change, gains, losses per branch and site), summed
 // over windows of W sites, as integers (epv::write_branch_events).  Changes nothing else the run writes.
+// New: -r/--regional FILE with the same -w/--window W: the regional sufficient statistics of the B batch sweeps
+// (epv_set_window_stats: J and D per branch and window of W sites as exact integers, then per window the sums
+// over the branches and the regional rate factor under the model of the run; epv::write_window_stats).
+// Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -38,7 +42,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
@@ -62,7 +66,10 @@ int main(int argc, const char **argv) {
                       false, leaf_probs_file);
     opt_parse.add_opt("changes", 'c', "output file of the branch-event maps of the batch sweeps (integer window sums)",
                       false, changes_file);
-    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps (default 1)", false, window);
+    opt_parse.add_opt("regional", 'r', "output file of J and D per window of the batch sweeps, with regional rate factors",
+                      false, regional_file);
+    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps and regional statistics (default 1)", false,
+                      window);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -83,8 +90,9 @@ int main(int argc, const char **argv) {
     }
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
-    if (window != no_window && changes_file.empty())
-      throw std::runtime_error("-w/--window belongs to -c/--changes: give the output file of the branch-event maps");
+    if (window != no_window && changes_file.empty() && regional_file.empty())
+      throw std::runtime_error("-w/--window belongs to -c/--changes and -r/--regional: give the output file of the "
+                               "branch-event maps or of the regional statistics");
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
@@ -128,6 +136,7 @@ int main(int argc, const char **argv) {
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);
     if (!changes_file.empty()) mcmc.set_branch_events(true);
+    if (!regional_file.empty()) mcmc.set_window_stats(window);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -153,6 +162,17 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING BRANCH EVENTS OF " << n_samples << " SAMPLES: " << changes_file << "]" << endl;
       epv::write_branch_events(changes_file, th.node_names, th.n_nodes(), mcmc.branch_event_windows(window), window,
                                th.branches.data(), sums.data(), n_samples);
+    }
+    if (!regional_file.empty()) {
+      vector<int64_t> counts;
+      vector<double> Jw, Dw;
+      uint64_t n_samples = 0, W = 0, n_windows = 0;
+      mcmc.download_window_stats(counts, W, n_windows, n_samples);
+      mcmc.window_counts_to_stats(counts, n_windows, n_samples, Jw, Dw);
+      const vector<int> scale_exp = mcmc.window_stats_scale_exps();   // the accumulator's own k_b
+      if (VERBOSE) cerr << "[WRITING REGIONAL STATISTICS OF " << n_samples << " SAMPLES: " << regional_file << "]" << endl;
+      epv::write_window_stats(regional_file, th.node_names, th.n_nodes(), n_windows, W, th.branches.data(),
+                              scale_exp.data(), counts.data(), n_samples, Jw.data(), Dw.data(), the_model.rates);
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

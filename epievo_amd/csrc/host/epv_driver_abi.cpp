@@ -21,6 +21,9 @@ struct epvd_sampler {
   bool have_staged_avg = false;
   std::vector<uint32_t> staged_events;   // between epvd_branch_events_sizes and epvd_download_branch_events
   bool have_staged_events = false;
+  std::vector<int64_t> staged_wstat;   // between epvd_window_stats_sizes and epvd_download_window_stats
+  uint64_t staged_wstat_nw = 0, staged_wstat_ns = 0;
+  bool have_staged_wstat = false;
 };
 
 namespace {
@@ -221,5 +224,35 @@ EPVD_API int epvd_download_branch_event_windows(epvd_sampler *h, uint64_t W, uin
     h->s->download_branch_event_windows(W, v, ns);
     std::copy(v.begin(), v.end(), sums);
     if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_window_stats(epvd_sampler *h, uint64_t W) {
+  return guarded(h, [&] { h->s->set_window_stats(W); });
+}
+EPVD_API int epvd_window_stats_sizes(epvd_sampler *h, uint64_t *W, uint64_t *n_windows, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t w = 0, nw = 0, ns = 0;
+    h->s->download_window_stats(h->staged_wstat, w, nw, ns);
+    h->have_staged_wstat = true;
+    h->staged_wstat_nw = nw;
+    h->staged_wstat_ns = ns;
+    *W = w;
+    *n_windows = nw;
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_window_stats(epvd_sampler *h, int64_t *counts, double *J, double *D) {
+  return guarded(h, [&] {
+    if (!h->have_staged_wstat) throw std::runtime_error("epvd_window_stats_sizes first");
+    if (counts) std::copy(h->staged_wstat.begin(), h->staged_wstat.end(), counts);
+    if (J && D && h->staged_wstat_ns) {
+      std::vector<double> j, d;
+      h->s->window_counts_to_stats(h->staged_wstat, h->staged_wstat_nw, h->staged_wstat_ns, j, d);
+      std::copy(j.begin(), j.end(), J);
+      std::copy(d.begin(), d.end(), D);
+    }
+    h->staged_wstat.clear();
+    h->have_staged_wstat = false;
   });
 }

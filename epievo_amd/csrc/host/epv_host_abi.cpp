@@ -2,8 +2,11 @@
 // Python tests / bench.py can drive the same C++ host code the CLI programs use.
 // No GPU code here; no exceptions cross the boundary (non-zero return = failure,
 // message via epvh_last_error).
+#include <algorithm>
 #include <cstring>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "epv_model.hpp"
 #include "epv_sim.hpp"
@@ -314,3 +317,71 @@ EPVH_API uint64_t epvh_forward_sim(uint64_t seed, const double *rates, const dou
   }
   return tot;
 }
+
+// ---- regional sufficient statistics: the rate factor per window, and the file of epievo_est_histories -r
+// J, D: [n_windows][n_nodes-1][8]; out[n_windows] (NaN for a window without dwell time)
+EPVH_API void epvh_regional_rate_factors(int n_nodes, uint64_t n_windows, const double *J, const double *D,
+                                         const double *rates, double *out) {
+  std::array<double, 8> r;
+  for (int i = 0; i < 8; ++i) r[i] = rates[i];
+  const uint64_t step = (uint64_t)(n_nodes - 1) * 8u;
+  for (uint64_t w = 0; w < n_windows; ++w) out[w] = epv::regional_rate_factor(n_nodes, J + w * step, D + w * step, r);
+}
+EPVH_API double epvh_collapsed_log_likelihood(int n_nodes, const double *J, const double *D, const double *rates) {
+  std::array<double, 8> r;
+  for (int i = 0; i < 8; ++i) r[i] = rates[i];
+  return epv::collapsed_log_likelihood(n_nodes, J, D, r);
+}
+// node_names: n_nodes names joined by '\n' (the root's first); branch_len, scale_exp: [n_nodes], index 0 = root
+EPVH_API int epvh_write_window_stats(const char *file, const char *node_names, int n_nodes, uint64_t n_windows,
+                                     uint64_t window, const double *branch_len, const int *scale_exp,
+                                     const int64_t *counts, uint64_t n_samples, const double *J, const double *D,
+                                     const double *rates) {
+  try {
+    std::vector<std::string> names;
+    std::string all(node_names), cur;
+    for (char ch : all) {
+      if (ch == '\n') { names.push_back(cur); cur.clear(); } else cur.push_back(ch);
+    }
+    names.push_back(cur);
+    if ((int)names.size() != n_nodes) throw std::runtime_error("epvh_write_window_stats: one name per node");
+    std::array<double, 8> r;
+    for (int i = 0; i < 8; ++i) r[i] = rates[i];
+    epv::write_window_stats(file, names, n_nodes, n_windows, window, branch_len, scale_exp, counts, n_samples, J, D, r);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_window_stats(const char *file) {
+  try {
+    return new epv::WindowStats(epv::read_window_stats(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+static std::string joined_names(const epv::WindowStats *ws) {
+  std::string joined;
+  for (size_t i = 0; i < ws->node_names.size(); ++i) joined += (i ? "\n" : "") + ws->node_names[i];
+  return joined;
+}
+// names_len: the bytes epvh_window_stats_copy needs for the names, the closing 0 included
+EPVH_API void epvh_window_stats_dims(void *h, uint64_t *n_samples, uint64_t *window, uint64_t *n_windows,
+                                     uint64_t *n_branches, uint64_t *names_len) {
+  const epv::WindowStats *ws = (const epv::WindowStats *)h;
+  *names_len = joined_names(ws).size() + 1u;
+  *n_samples = ws->n_samples;
+  *window = ws->window;
+  *n_windows = ws->n_windows;
+  *n_branches = ws->node_names.size();
+}
+// names: the non-root nodes' names joined by '\n'; branch_len, scale_exp: [B]; counts [nw][B][16]; all_J, all_D
+// [nw][8]; factor [nw]
+EPVH_API void epvh_window_stats_copy(void *h, char *names, int names_len, double *branch_len, int *scale_exp,
+                                     int64_t *counts, int64_t *all_J, double *all_D, double *factor) {
+  const epv::WindowStats *ws = (const epv::WindowStats *)h;
+  put_text(joined_names(ws), names, names_len);
+  std::copy(ws->branch_len.begin(), ws->branch_len.end(), branch_len);
+  std::copy(ws->scale_exp.begin(), ws->scale_exp.end(), scale_exp);
+  std::copy(ws->counts.begin(), ws->counts.end(), counts);
+  std::copy(ws->all_J.begin(), ws->all_J.end(), all_J);
+  std::copy(ws->all_D.begin(), ws->all_D.end(), all_D);
+  std::copy(ws->factor.begin(), ws->factor.end(), factor);
+}
+EPVH_API void epvh_window_stats_free(void *h) { delete (epv::WindowStats *)h; }

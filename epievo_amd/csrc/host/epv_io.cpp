@@ -1,5 +1,6 @@
 // epv_io.cpp -- see epv_io.hpp
 #include "epv_io.hpp"
+#include "epv_model.hpp"
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -673,6 +674,108 @@ void write_branch_events(const std::string &file, const std::vector<std::string>
   }
   out.flush();
   if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+void write_window_stats(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                        uint64_t n_windows, uint64_t window, const double *branch_len, const int *scale_exp,
+                        const int64_t *counts, uint64_t n_samples, const double *J, const double *D,
+                        const std::array<double, 8> &rates) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  char buf[64];
+  auto g17 = [&](double v) { std::snprintf(buf, sizeof buf, "%.17g", v); return buf; };
+  out << "#samples\t" << n_samples << "\twindow\t" << window << '\n';
+  const uint64_t B = (uint64_t)n_nodes - 1u;
+  for (int b = 1; b < n_nodes; ++b) {
+    out << "NODE:" << node_names[b] << "\t" << g17(branch_len[b]) << "\t" << scale_exp[b] << '\n';
+    for (uint64_t w = 0; w < n_windows; ++w) {
+      out << w * window;
+      for (uint64_t c = 0; c < 16u; ++c) out << "\t" << counts[(w * B + (uint64_t)(b - 1)) * 16u + c];
+      out << '\n';
+    }
+  }
+  out << "NODE:all\n";
+  for (uint64_t w = 0; w < n_windows; ++w) {
+    out << w * window;
+    for (uint64_t c = 0; c < 8u; ++c) {
+      int64_t j = 0;
+      for (uint64_t b = 0; b < B; ++b) j += counts[(w * B + b) * 16u + c];
+      out << "\t" << j;
+    }
+    for (uint64_t c = 0; c < 8u; ++c) {
+      double d = 0.0;
+      for (uint64_t b = 0; b < B; ++b) d += D[(w * B + b) * 8u + c];
+      out << "\t" << g17(d);
+    }
+    out << "\t" << g17(regional_rate_factor(n_nodes, J + w * B * 8u, D + w * B * 8u, rates)) << '\n';
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+WindowStats read_window_stats(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad window-statistics file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("window-statistics file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  WindowStats ws;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 4 || f[0] != "#samples" || f[2] != "window") throw bad("bad header: " + line);
+  ws.n_samples = std::stoull(f[1]);
+  ws.window = std::stoull(f[3]);
+  std::vector<std::vector<int64_t>> rows;   // the current node's windows
+  std::vector<std::vector<std::vector<int64_t>>> nodes;
+  bool in_all = false;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    f = fields(line);
+    if (line.compare(0, 5, "NODE:") == 0) {
+      if (in_all) throw bad("a node after NODE:all");
+      if (!ws.node_names.empty()) nodes.push_back(rows);
+      rows.clear();
+      if (line == "NODE:all") { in_all = true; continue; }
+      if (f.size() != 3) throw bad("bad node line: " + line);
+      ws.node_names.push_back(f[0].substr(5));
+      ws.branch_len.push_back(std::stod(f[1]));
+      ws.scale_exp.push_back(std::stoi(f[2]));
+    } else if (in_all) {
+      if (f.size() != 18) throw bad("bad line in NODE:all: " + line);
+      const uint64_t w = ws.factor.size();
+      if (std::stoull(f[0]) != w * ws.window) throw bad("windows out of order: " + line);
+      for (int c = 0; c < 8; ++c) ws.all_J.push_back(std::stoll(f[1 + c]));
+      for (int c = 0; c < 8; ++c) ws.all_D.push_back(std::stod(f[9 + c]));
+      ws.factor.push_back(std::strtod(f[17].c_str(), nullptr));   // (takes "nan")
+    } else {
+      if (ws.node_names.empty() || f.size() != 17) throw bad("bad window line: " + line);
+      if (std::stoull(f[0]) != rows.size() * ws.window) throw bad("windows out of order: " + line);
+      std::vector<int64_t> r(16);
+      for (int c = 0; c < 16; ++c) r[c] = std::stoll(f[1 + c]);
+      rows.push_back(r);
+    }
+  }
+  if (!in_all) throw bad("no NODE:all block");
+  const uint64_t B = ws.node_names.size();
+  ws.n_windows = ws.factor.size();
+  if (nodes.size() != B) throw bad("node blocks missing");
+  ws.counts.assign(ws.n_windows * B * 16u, 0);
+  for (uint64_t b = 0; b < B; ++b) {
+    if (nodes[b].size() != ws.n_windows) throw bad("node " + ws.node_names[b] + " has another number of windows");
+    for (uint64_t w = 0; w < ws.n_windows; ++w)
+      std::copy(nodes[b][w].begin(), nodes[b][w].end(), ws.counts.begin() + (w * B + b) * 16u);
+  }
+  return ws;
 }
 
 }  // namespace epv

@@ -3,6 +3,7 @@
 #ifndef EPV_IO_HPP
 #define EPV_IO_HPP
 
+#include <array>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -64,6 +65,30 @@ void write_path_average(const std::string &file, const std::vector<std::string> 
 void write_branch_events(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
                          uint64_t n_windows, uint64_t window, const double *branch_len, const uint64_t *sums,
                          uint64_t n_samples);
+
+// the regional sufficient statistics of epievo_est_histories -r (epv_get_window_stats):
+//   "#samples\t<S>\twindow\t<W>", then per non-root node in pre-order "NODE:<name>\t<branch length>\t<k_b>"
+//   (%.17g; D integers are in units of 2^-k_b) and one line per window: its first global site, J[0..7] and
+//   D[0..7] as the integer sums over the samples, tab-separated; after the last node one block "NODE:all"
+//   with a line per window: first global site, sum_b J[8] (integers), sum_b D[8] per sample in time units
+//   (%.17g) and the regional rate factor under `rates` (epv::regional_rate_factor; "nan" for an empty window).
+// counts: [w][b-1][16] int64; J, D: [w][b-1][8] per sample (epv_window_counts_to_stats); scale_exp: k_b per
+// node, index 0 = root (epv_window_stats_scale_exps: the accumulator's own).
+struct WindowStats {
+  uint64_t n_samples = 0, window = 0, n_windows = 0;
+  std::vector<std::string> node_names;   // non-root nodes
+  std::vector<double> branch_len;        // per non-root node
+  std::vector<int> scale_exp;            // k_b per non-root node
+  std::vector<int64_t> counts;           // [w][b][16]
+  std::vector<int64_t> all_J;            // [w][8]
+  std::vector<double> all_D;             // [w][8]
+  std::vector<double> factor;            // [w]
+};
+void write_window_stats(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
+                        uint64_t n_windows, uint64_t window, const double *branch_len, const int *scale_exp,
+                        const int64_t *counts, uint64_t n_samples, const double *J, const double *D,
+                        const std::array<double, 8> &rates);
+WindowStats read_window_stats(const std::string &file);
 
 // the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
 // then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The

@@ -249,4 +249,24 @@ double estimate_rates_and_branches(double param_tol, int n_nodes, const double *
   return log_likelihood(Jc, Dc, updated);
 }
 
+double collapsed_log_likelihood(int n_nodes, const double *J, const double *D, const std::array<double, 8> &rates) {
+  double Jc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, Dc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = 1; b < n_nodes; ++b)
+    for (int i = 0; i < 8; ++i) {
+      Jc[i] += J[(b - 1) * 8 + i];
+      Dc[i] += D[(b - 1) * 8 + i];
+    }
+  return log_likelihood(Jc, Dc, rates);
+}
+
+double regional_rate_factor(int n_nodes, const double *J, const double *D, const std::array<double, 8> &rates) {
+  double num = 0.0, den = 0.0;
+  for (int b = 1; b < n_nodes; ++b)
+    for (int i = 0; i < 8; ++i) {
+      num += J[(b - 1) * 8 + i];
+      den += D[(b - 1) * 8 + i] * rates[i];
+    }
+  return den == 0.0 ? std::numeric_limits<double>::quiet_NaN() : num / den;
+}
+
 }  // namespace epv

@@ -52,6 +52,17 @@ double estimate_rates_and_branches(double param_tol, int n_nodes, const double *
                                    const double *D, std::vector<double> &branches,
                                    Model &model);
 
+// log_likelihood of ParamEstimation.cpp:131-143 over the branches' sums: sum_c J_c log(rate_c) - D_c rate_c
+// with J_c, D_c added over the n_nodes - 1 branches (J, D: [n_nodes-1][8])
+double collapsed_log_likelihood(int n_nodes, const double *J, const double *D, const std::array<double, 8> &rates);
+
+// Regional rate factor of one window: the multiplier rho that maximises collapsed_log_likelihood(J, D,
+// rho * rates).  d/d rho [sum J (log rho + log r) - rho sum D r] = sum J / rho - sum D r = 0, so
+//   rho = sum_{b,c} J / sum_{b,c} D_c rate_c     (J, D: [n_nodes-1][8] of the window)
+// -- observed jumps over the jumps the fitted rates expect for the window's dwell times.  NaN where the
+// denominator is 0 (a window without a counted triple).
+double regional_rate_factor(int n_nodes, const double *J, const double *D, const std::array<double, 8> &rates);
+
 }  // namespace epv
 
 #endif

@@ -363,6 +363,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   reset(m);
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
+  if (wstat_W_) set_window_stats(wstat_W_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -371,6 +372,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   reset(m);
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
+  if (wstat_W_) set_window_stats(wstat_W_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -463,6 +465,55 @@ void SingleSiteSampler::download_branch_event_windows(uint64_t W, std::vector<ui
     check_on(c, epv_get_branch_event_windows(c, W, 0u, nw, part.data()), "epv_get_branch_event_windows");
     for (size_t k = 0; k < part.size(); ++k) sums[k] += part[k];
   }
+}
+
+void SingleSiteSampler::set_window_stats(uint64_t W) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !W)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_window_stats(c, W), "epv_set_window_stats");
+  wstat_W_ = W;
+}
+
+void SingleSiteSampler::download_window_stats(std::vector<int64_t> &counts, uint64_t &W, uint64_t &n_windows,
+                                              uint64_t &n_samples) {
+  if (!wstat_W_) throw std::runtime_error("window statistics are off: set_window_stats first");
+  const std::vector<epv_ctx *> cs = contexts();
+  W = window_stats_width();
+  n_windows = window_stats_windows();
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint64_t ns = 0;
+    if (epv_window_stats_samples(cs[i], &ns) != EPV_OK) throw std::runtime_error("epv_window_stats_samples failed");
+    if (i == 0) n_samples = ns;
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of window-statistics samples");
+  }
+  const uint64_t V = 16u * ((uint64_t)n_nodes_ - 1u);
+  counts.assign(V * n_windows, 0);
+  std::vector<int64_t> part(V * n_windows);
+  for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites, as integers
+    check_on(c, epv_get_window_stats(c, 0u, n_windows, part.data()), "epv_get_window_stats");
+    for (size_t k = 0; k < part.size(); ++k) counts[k] += part[k];
+  }
+}
+
+void SingleSiteSampler::window_counts_to_stats(const std::vector<int64_t> &counts, uint64_t n_windows, uint64_t n_samples,
+                                               std::vector<double> &J, std::vector<double> &D) {
+  const uint64_t B = (uint64_t)n_nodes_ - 1u;
+  if (counts.size() != n_windows * B * 16u) throw std::runtime_error("window_counts_to_stats: counts of the wrong size");
+  J.assign(n_windows * B * 8u, 0.0);
+  D.assign(n_windows * B * 8u, 0.0);
+  epv_ctx *c = contexts().at(0);
+  if (n_windows)
+    check_on(c, epv_window_counts_to_stats(c, counts.data(), n_windows, n_samples, J.data(), D.data()),
+             "epv_window_counts_to_stats");
+}
+
+std::vector<int> SingleSiteSampler::window_stats_scale_exps() {
+  if (!wstat_W_) throw std::runtime_error("window statistics are off: set_window_stats first");
+  std::vector<int> k((size_t)n_nodes_, 0);
+  epv_ctx *c = contexts().at(0);     // (every context of a genome has its tree and its n_global)
+  if (n_nodes_ > 1) check_on(c, epv_window_stats_scale_exps(c, k.data() + 1), "epv_window_stats_scale_exps");
+  return k;
 }
 
 void SingleSiteSampler::set_unobserved(std::vector<uint8_t> whole_genome) {

@@ -118,6 +118,19 @@ public:
   uint64_t branch_event_windows(uint64_t W) const { return W ? (n_sites_ + W - 1u) / W : 0u; }   // windows of the genome
   void download_branch_events(std::vector<uint32_t> &planes, uint64_t &n_samples);
   void download_branch_event_windows(uint64_t W, std::vector<uint64_t> &sums, uint64_t &n_samples);
+  // regional sufficient statistics (epv_set_window_stats) on every context: J and D per window of W global
+  // sites, with the branch events' samples and lifecycle (W = 0: off).  download_window_stats:
+  // counts[(w * (n_nodes-1) + b-1) * 16 + c] (J[8] then D[8] as integers) over all windows of the genome,
+  // all slots and contexts of this process added; window_counts_to_stats: J, D[(w * (n_nodes-1) + b-1) * 8 + c]
+  // per sample, D in time units; window_stats_scale_exps: k_b per node (index 0, the root: 0) of the
+  // accumulator's D integers, from the context itself (epv_window_stats_scale_exps)
+  void set_window_stats(uint64_t W);
+  uint64_t window_stats_width() const { return wstat_W_ && n_sites_ ? std::min<uint64_t>(wstat_W_, n_sites_) : wstat_W_; }
+  uint64_t window_stats_windows() const { const uint64_t W = window_stats_width(); return W ? (n_sites_ + W - 1u) / W : 0u; }
+  void download_window_stats(std::vector<int64_t> &counts, uint64_t &W, uint64_t &n_windows, uint64_t &n_samples);
+  void window_counts_to_stats(const std::vector<int64_t> &counts, uint64_t n_windows, uint64_t n_samples,
+                              std::vector<double> &J, std::vector<double> &D);
+  std::vector<int> window_stats_scale_exps();
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
@@ -211,6 +224,7 @@ private:
   uint32_t capacity_;
   uint32_t pa_points_ = 0;    // set_path_average
   bool bevents_ = false;      // set_branch_events
+  uint64_t wstat_W_ = 0;      // set_window_stats
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

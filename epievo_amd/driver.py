@@ -17,7 +17,8 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_download", "epvd_layout", "epvd_set_options", "epvd_set_timing", "epvd_kernel_time_ms",
                   "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average",
                   "epvd_set_branch_events", "epvd_branch_events_sizes", "epvd_download_branch_events",
-                  "epvd_download_branch_event_windows"]
+                  "epvd_download_branch_event_windows",
+                  "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats"]
 
 
 def lib():
@@ -55,6 +56,9 @@ def lib():
         L.epvd_branch_events_sizes.argtypes = [vp, u64p, u64p]
         L.epvd_download_branch_events.argtypes = [vp, u32p]
         L.epvd_download_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.epvd_set_window_stats.argtypes = [vp, C.c_uint64]
+        L.epvd_window_stats_sizes.argtypes = [vp, u64p, u64p, u64p]
+        L.epvd_download_window_stats.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
         _lib = L
     return _lib
 
@@ -234,3 +238,23 @@ class CppSampler:
         out, ns = np.zeros((6, self.B, nw), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_branch_event_windows(self.h, W, nw, _p(out, C.c_uint64), C.byref(ns)))
         return int(ns.value), out
+
+    def enable_window_stats(self, W):
+        """regional sufficient statistics on every context: J and D per window of W global sites (0 = off);
+        kept across reset()"""
+        self._ck(self.L.epvd_set_window_stats(self.h, int(W)))
+
+    def window_stats(self, counts=False):
+        """-> (samples, J, D [windows, N-1, 8]) per sample, or (samples, int64 [windows, N-1, 16]): the slots
+        and contexts of this process added as integers"""
+        W, nw, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epvd_window_stats_sizes(self.h, C.byref(W), C.byref(nw), C.byref(ns)))
+        cnt = np.zeros((nw.value, self.B, 16), np.int64)
+        J, D = np.zeros((nw.value, self.B, 8)), np.zeros((nw.value, self.B, 8))
+        self._ck(self.L.epvd_download_window_stats(self.h, _p(cnt, C.c_int64), _p(J, C.c_double), _p(D, C.c_double)))
+        ns = int(ns.value)
+        if counts:
+            return ns, cnt
+        if not ns:
+            raise DriverError("window statistics hold no sample")
+        return ns, J, D

@@ -41,6 +41,21 @@ def lib():
         L.epvh_model_from_indep_rates.argtypes = [dp, dp, dp, dp]
         L.epvh_initialize_paths_heuristic.argtypes = [C.c_uint64, C.c_int, u32p, u32p, dp, C.c_uint64, u8p]
         L.epvh_initialize_paths_heuristic.restype = C.c_void_p
+        i64p, ip = C.POINTER(C.c_int64), C.POINTER(C.c_int)
+        L.epvh_regional_rate_factors.argtypes = [C.c_int, C.c_uint64, dp, dp, dp, dp]
+        L.epvh_regional_rate_factors.restype = None
+        L.epvh_collapsed_log_likelihood.argtypes = [C.c_int, dp, dp, dp]
+        L.epvh_collapsed_log_likelihood.restype = C.c_double
+        L.epvh_write_window_stats.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, dp, ip, i64p,
+                                              C.c_uint64, dp, dp, dp]
+        L.epvh_read_window_stats.argtypes = [C.c_char_p]
+        L.epvh_read_window_stats.restype = C.c_void_p
+        L.epvh_window_stats_dims.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p]
+        L.epvh_window_stats_dims.restype = None
+        L.epvh_window_stats_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, dp, ip, i64p, i64p, dp, dp]
+        L.epvh_window_stats_copy.restype = None
+        L.epvh_window_stats_free.argtypes = [C.c_void_p]
+        L.epvh_window_stats_free.restype = None
         _lib = L
     return _lib
 
@@ -221,3 +236,65 @@ def initialize_paths_heuristic(seed, tree, states):
         raise RuntimeError(lib().epvh_last_error().decode())
     states[...] = st
     return FlatPaths._from_handle(h)
+
+
+# ---- regional sufficient statistics (J and D per genomic window)
+def regional_rate_factors(J, D, rates):
+    """J, D [windows, N-1, 8] -> rho[windows] = sum J / sum D_c rate_c: per window the multiplier of the
+    fitted rates that maximises log_likelihood(J, D, rho * rates); NaN where a window has no dwell time"""
+    J = np.ascontiguousarray(J, np.float64)
+    D = np.ascontiguousarray(D, np.float64)
+    r = np.ascontiguousarray(rates, np.float64)
+    if J.ndim != 3 or J.shape != D.shape or J.shape[2] != 8 or r.shape != (8,):
+        raise ValueError("J and D are [windows, N-1, 8], rates [8]")
+    out = np.zeros(J.shape[0])
+    lib().epvh_regional_rate_factors(J.shape[1] + 1, J.shape[0], _p(J, C.c_double), _p(D, C.c_double),
+                                     _p(r, C.c_double), _p(out, C.c_double))
+    return out
+
+
+def collapsed_log_likelihood(J, D, rates):
+    """J, D [N-1, 8]: sum_c Jc log(rate_c) - Dc rate_c over the branches' sums (the M-step's objective)"""
+    J = np.ascontiguousarray(J, np.float64)
+    D = np.ascontiguousarray(D, np.float64)
+    r = np.ascontiguousarray(rates, np.float64)
+    return float(lib().epvh_collapsed_log_likelihood(J.shape[0] + 1, _p(J, C.c_double), _p(D, C.c_double),
+                                                     _p(r, C.c_double)))
+
+
+def write_window_stats(path, node_names, branches, scale_exp, window, samples, counts, J, D, rates):
+    """the file of epievo_est_histories -r.  node_names, branches, scale_exp: per node, the root first;
+    counts int64 [windows, N-1, 16]; J, D [windows, N-1, 8] per sample"""
+    counts = np.ascontiguousarray(counts, np.int64)
+    J = np.ascontiguousarray(J, np.float64)
+    D = np.ascontiguousarray(D, np.float64)
+    br = np.ascontiguousarray(branches, np.float64)
+    k = np.ascontiguousarray(scale_exp, np.intc)
+    r = np.ascontiguousarray(rates, np.float64)
+    if lib().epvh_write_window_stats(path.encode(), "\n".join(node_names).encode(), len(br), counts.shape[0], int(window),
+                                     _p(br, C.c_double), _p(k, C.c_int), _p(counts, C.c_int64), int(samples),
+                                     _p(J, C.c_double), _p(D, C.c_double), _p(r, C.c_double)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_window_stats(path):
+    """-> dict(samples, window, node_names, branches, scale_exp (non-root nodes), counts [windows, N-1, 16],
+    all_J int64 [windows, 8], all_D [windows, 8], factor [windows])"""
+    L = lib()
+    h = L.epvh_read_window_stats(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, W, nw, B, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.epvh_window_stats_dims(h, C.byref(ns), C.byref(W), C.byref(nw), C.byref(B), C.byref(nl))
+        nw, B = int(nw.value), int(B.value)
+        buf = C.create_string_buffer(int(nl.value))        # the names as the file has them, however long
+        br, k = np.zeros(max(B, 1)), np.zeros(max(B, 1), np.intc)
+        counts = np.zeros((nw, B, 16), np.int64)
+        aJ, aD, f = np.zeros((nw, 8), np.int64), np.zeros((nw, 8)), np.zeros(nw)
+        L.epvh_window_stats_copy(h, buf, len(buf), _p(br, C.c_double), _p(k, C.c_int), _p(counts, C.c_int64),
+                                 _p(aJ, C.c_int64), _p(aD, C.c_double), _p(f, C.c_double))
+        return dict(samples=int(ns.value), window=int(W.value), node_names=buf.value.decode().split("\n"),
+                    branches=br[:B], scale_exp=k[:B], counts=counts, all_J=aJ, all_D=aD, factor=f)
+    finally:
+        L.epvh_window_stats_free(h)

@@ -379,6 +379,35 @@ class ShardedSampler:
             own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
         return ns, own
 
+    # ---- regional sufficient statistics: every rank adds the windows its owned columns meet
+    def enable_window_stats(self, W):
+        self.dev.enable_window_stats(W)
+
+    def reset_window_stats(self):
+        self.dev.reset_window_stats()
+
+    def accumulate_window_stats(self):
+        self.dev.accumulate_window_stats()
+
+    def window_stats_scale_exps(self):
+        return self.dev.window_stats_scale_exps()
+
+    def window_stats(self, counts=False):
+        """-> (samples, J, D [nw, N-1, 8]) of the whole genome (or the int64 [nw, N-1, 16]), identical on
+        every rank: the ranks' integer contributions are all-gathered and added, then converted once"""
+        ns, own = self.dev.window_counts()
+        if self.comm.world > 1:
+            mine = np.append(own.reshape(-1), np.int64(ns)).view(np.uint32)
+            allw = self._gather_words(mine).view(np.int64)
+            if any(int(w[-1]) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of window-statistics samples")
+            own = allw[:, :-1].sum(axis=0, dtype=np.int64).reshape(own.shape)
+        if counts:
+            return ns, own
+        if not ns:
+            raise RuntimeError("window statistics hold no sample")
+        return (ns,) + self.dev.window_counts_to_stats(own, ns)
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -670,6 +699,45 @@ class LocalGroup:
             n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
         parts = self._each(lambda j, s: s.branch_event_windows(W, first_window, n_windows))
         return self._same_samples(parts), sum(p[1] for p in parts)
+
+    # ---- regional sufficient statistics: every shard adds the windows its owned sites meet
+    def enable_window_stats(self, W):
+        self._each(lambda j, s: s.enable_window_stats(W))
+
+    def reset_window_stats(self):
+        self._each(lambda j, s: s.reset_window_stats())
+
+    def accumulate_window_stats(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            raise RuntimeError("reset() the group before taking a window-statistics sample")
+        self._each(lambda j, s: s.accumulate_window_stats())
+
+    def window_stats_samples(self):
+        return self.subs[0].window_stats_samples()
+
+    def window_counts(self, first_window=0, n_windows=None):
+        """-> (samples, int64 [windows, N-1, 16]): the shards' contributions, added as integers"""
+        parts = self._each(lambda j, s: s.window_counts(first_window, n_windows))
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of window-statistics samples")
+        return ns, sum(p[1] for p in parts)
+
+    def window_counts_to_stats(self, counts, samples):
+        return self.subs[0].window_counts_to_stats(counts, samples)
+
+    def window_stats_scale_exps(self):
+        return self.subs[0].window_stats_scale_exps()
+
+    def window_stats(self, counts=False):
+        """-> (samples, J, D [nw, N-1, 8]) or (samples, int64 [nw, N-1, 16]): added over the shards as
+        integers, then converted once"""
+        ns, cnt = self.window_counts()
+        if counts:
+            return ns, cnt
+        if not ns:
+            raise RuntimeError("window statistics hold no sample")
+        return (ns,) + self.window_counts_to_stats(cnt, ns)
 
     def counters(self):
         out = {}

@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "epv_set_branch_events", "epv_reset_branch_events", "epv_accumulate_branch_events", "epv_branch_events_samples",
     "epv_branch_events_set_samples", "epv_branch_events_layout", "epv_get_branch_events",
     "epv_get_branch_event_windows",
+    "epv_set_window_stats", "epv_reset_window_stats", "epv_accumulate_window_stats", "epv_window_stats_samples",
+    "epv_window_stats_set_samples", "epv_window_stats_scale_exps", "epv_window_stats_layout", "epv_get_window_stats", "epv_window_counts_to_stats",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
@@ -144,6 +146,15 @@ def lib():
         L.epv_branch_events_layout.argtypes = [vp, u64p, u64p]
         L.epv_get_branch_events.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
         L.epv_get_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        L.epv_set_window_stats.argtypes = [vp, C.c_uint64]
+        L.epv_reset_window_stats.argtypes = [vp]
+        L.epv_accumulate_window_stats.argtypes = [vp]
+        L.epv_window_stats_samples.argtypes = [vp, u64p]
+        L.epv_window_stats_set_samples.argtypes = [vp, C.c_uint64]
+        L.epv_window_stats_scale_exps.argtypes = [vp, C.POINTER(C.c_int)]
+        L.epv_window_stats_layout.argtypes = [vp, u64p, u64p, u64p]
+        L.epv_get_window_stats.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]
+        L.epv_window_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, dp, dp]
         _lib = L
     return _lib
 
@@ -590,6 +601,69 @@ class DeviceSampler:
         self._ck(self.L.epv_get_branch_event_windows(self.h, W, int(first_window), out.shape[2], _p(out, C.c_uint64)))
         return self.branch_events_samples(), out
 
+    # ---- regional sufficient statistics (epv_set_window_stats)
+    def enable_window_stats(self, W):
+        """add J and D per window of W global sites after every batch sweep of run_mcmc (0 = off)"""
+        W = int(W)
+        if W < 0:
+            raise ValueError("a window holds at least one site (0 turns the statistics off)")
+        self._ck(self.L.epv_set_window_stats(self.h, W))
+
+    def reset_window_stats(self):
+        self._ck(self.L.epv_reset_window_stats(self.h))
+
+    def accumulate_window_stats(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_window_stats(self.h))
+
+    def window_stats_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_window_stats_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def window_stats_layout(self):
+        """(W as clamped, first global window, number of windows) this context holds; (0, 0, 0) when off"""
+        w, a, k = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_window_stats_layout(self.h, C.byref(w), C.byref(a), C.byref(k)))
+        return int(w.value), int(a.value), int(k.value)
+
+    def window_stats_scale_exps(self):
+        """k_b of the non-root nodes: a D integer of the accumulator is a dwell time in units of 2^-k_b"""
+        k = np.zeros(max(self.B, 1), np.intc)
+        self._ck(self.L.epv_window_stats_scale_exps(self.h, _p(k, C.c_int)))
+        return k[:self.B]
+
+    def window_counts(self, first_window=0, n_windows=None):
+        """-> (samples, int64 [windows, N-1, 16]): this context's contribution (J[8] then D[8] as integers),
+        zero where it holds no site; all windows of the genome unless a range is given"""
+        W = self.window_stats_layout()[0]
+        if not W:
+            self._ck(self.L.epv_get_window_stats(self.h, 0, 0, None))     # off: EPV_ERR_STATE
+        if n_windows is None:
+            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
+        out = np.zeros((max(int(n_windows), 0), self.B, 16), np.int64)
+        self._ck(self.L.epv_get_window_stats(self.h, int(first_window), out.shape[0], _p(out, C.c_int64)))
+        return self.window_stats_samples(), out
+
+    def window_counts_to_stats(self, counts, samples):
+        """int64 [windows, N-1, 16] -> J, D [windows, N-1, 8] per sample (D in time units)"""
+        counts = np.ascontiguousarray(counts, np.int64)
+        J, D = np.zeros(counts.shape[:2] + (8,)), np.zeros(counts.shape[:2] + (8,))
+        if counts.shape[0]:
+            self._ck(self.L.epv_window_counts_to_stats(self.h, _p(counts, C.c_int64), counts.shape[0], int(samples),
+                                                       _p(J, C.c_double), _p(D, C.c_double)))
+        return J, D
+
+    def window_stats(self, counts=False):
+        """-> (samples, J[nw, N-1, 8], D[nw, N-1, 8]) averaged over the samples, or (samples, int64
+        [nw, N-1, 16]) with counts=True"""
+        ns, cnt = self.window_counts()
+        if counts:
+            return ns, cnt
+        if not ns:
+            raise RuntimeError("window statistics hold no sample")
+        return (ns,) + self.window_counts_to_stats(cnt, ns)
+
 
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
@@ -700,3 +774,16 @@ class SingleSiteSampler:
 
     def branch_event_windows(self, W):
         return self.dev.branch_event_windows(W)
+
+    # regional sufficient statistics (DeviceSampler.enable_window_stats)
+    def enable_window_stats(self, W):
+        self.dev.enable_window_stats(W)
+
+    def reset_window_stats(self):
+        self.dev.reset_window_stats()
+
+    def accumulate_window_stats(self):
+        self.dev.accumulate_window_stats()
+
+    def window_stats(self, counts=False):
+        return self.dev.window_stats(counts)

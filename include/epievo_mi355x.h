@@ -443,6 +443,50 @@ int epv_get_branch_events(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t
 int epv_get_branch_event_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                  uint64_t *sums);
 
+/* ---- regional sufficient statistics (new): J and D per genomic window, the numbers a regional rate is
+ * made of (jumps divided by dwell time, per neighbour context).  Window w = GLOBAL sites [w W, (w+1) W),
+ * n_win = ceil(n_global / W).  A sample adds, per window and branch, the 16 exact integers of the
+ * statistics -- J[8] as counts, D[8] as rint(dt 2^k_b) -- of the triples whose centre site lies in the
+ * window, is interior (global 1 .. n_global-2) and is owned by the context (the range of the statistics,
+ * not the path average's: the genome's end sites centre no triple).  The sums are 64-bit integers; added
+ * over all windows (and all contexts of a genome) they equal, bit for bit, the sum over the batch sweeps
+ * of the counts epv_run_mcmc_counts returns.  Samples and lifecycle are the branch events': a sample after
+ * each batch sweep of epv_run_mcmc / _sums / _counts (not the burn-in) or one epv_accumulate_window_stats
+ * call; kept over epv_reset, epv_set_model, capacity growth, masks, evidence and epv_sweep_phase; a site
+ * range that changes after samples were taken is EPV_ERR_STATE.  k_b depends on the branch lengths and on
+ * n_global: the accumulator remembers the scales of its first sample, and if they differ later (after
+ * epv_scale_jump_times, another tree or epv_set_global_length) a sample or run is EPV_ERR_STATE until
+ * epv_reset_window_stats.  Off (the default) allocates and launches nothing; J, D, accept counts, paths,
+ * tri_llh and the plan word do not depend on it.
+ * epv_set_window_stats: W >= 1 (clamped to n_global) allocates 128 (N-1) bytes per local window -- a
+ *   window that meets the owned sites -- checked against the free device memory first (the message gives
+ *   the figure), and zeroes them; W = 0 frees them.
+ * Cap: a site adds at most q_b = rint(T_b 2^k_b) + 3072 to a branch's D per sample, so a sample, or a run
+ *   whose batch would get there, is EPV_ERR_STATE when (samples + batch) min(W, owned sites) max_b q_b
+ *   >= 2^63 (a run is refused before its first sweep; the message names W and the most samples that
+ *   fit).  epv_window_stats_set_samples (a test hook) overwrites the sample count; the accumulator is left
+ *   as it is.  With it go the remembered scales: a count above 0 on an accumulator without samples
+ *   remembers the scales of now, as if the samples had been taken with them, and a count of 0 forgets them.
+ * epv_window_stats_scale_exps: k[b-1] = k_b of the accumulator's D integers for the N-1 non-root nodes: the
+ *   scales its first sample was taken with, or, while it holds no sample, the context's current ones.
+ * epv_window_stats_layout: W as clamped and the global windows first_window .. +n_windows-1 this context
+ *   holds (0, 0, 0 when off).
+ * epv_get_window_stats: counts[w - first_window][b-1][16] (int64, J then D) for n_windows windows from
+ *   first_window: this context's contribution, zero elsewhere, so contexts, shards and GPUs add up to
+ *   the one-context result.
+ * epv_window_counts_to_stats: J[w][b-1][8] = count / samples, D[w][b-1][8] = integer 2^-k_b / samples with
+ *   the context's current scales. */
+int epv_set_window_stats(epv_ctx *ctx, uint64_t W);
+int epv_reset_window_stats(epv_ctx *ctx);
+int epv_accumulate_window_stats(epv_ctx *ctx);
+int epv_window_stats_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_window_stats_set_samples(epv_ctx *ctx, uint64_t n_samples);
+int epv_window_stats_scale_exps(epv_ctx *ctx, int *k);
+int epv_window_stats_layout(epv_ctx *ctx, uint64_t *W, uint64_t *first_window, uint64_t *n_windows);
+int epv_get_window_stats(epv_ctx *ctx, uint64_t first_window, uint64_t n_windows, int64_t *counts);
+int epv_window_counts_to_stats(epv_ctx *ctx, const int64_t *counts, uint64_t n_windows, uint64_t samples,
+                               double *J, double *D);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

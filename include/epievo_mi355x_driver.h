@@ -82,6 +82,16 @@ int epvd_download_branch_events(epvd_sampler *s, uint32_t *planes);
 int epvd_download_branch_event_windows(epvd_sampler *s, uint64_t W, uint64_t n_windows, uint64_t *sums,
                                        uint64_t *n_samples);
 
+/* regional sufficient statistics (epv_set_window_stats on every context, W = 0: off; kept across epvd_reset,
+ * which starts the sums from zero).  Sizes first: W as clamped to the genome, n_windows = ceil(genome
+ * length / W) and the sample count; then the copy of counts[(w * (n_nodes-1) + b-1) * 16 + c] (int64, J[8]
+ * then D[8]), all slots and contexts of this process added as integers, and -- where J and D are not null
+ * and samples were taken -- J, D[(w * (n_nodes-1) + b-1) * 8 + c] per sample, D in time units.  counts may
+ * be null. */
+int epvd_set_window_stats(epvd_sampler *s, uint64_t W);
+int epvd_window_stats_sizes(epvd_sampler *s, uint64_t *W, uint64_t *n_windows, uint64_t *n_samples);
+int epvd_download_window_stats(epvd_sampler *s, int64_t *counts, double *J, double *D);
+
 #ifdef __cplusplus
 }
 #endif
