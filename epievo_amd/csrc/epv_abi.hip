@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <new>
 #include <vector>
 
 #include "epievo_mi355x.h"
@@ -22,6 +23,7 @@
 #include "epv_pavg.h"
 #include "epv_bevents.h"
 #include "epv_wstat.h"
+#include "epv_origin.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
 // Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
@@ -160,6 +162,21 @@ struct epv_ctx {
   uint32_t ws_B = 0;
   uint64_t ws_samples = 0;
   std::vector<double> ws_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
+  // lineage origin maps (epv_origin.h), off while !lo_on
+  bool lo_on = false;
+  uint32_t *d_lo = nullptr;               // origin [lo_R][lo_cnt] counts over local sites lo_lo .. lo_lo + lo_cnt - 1
+  unsigned long long *d_lo_age = nullptr;   // age [lo_L][lo_cnt]
+  uint64_t lo_lo = 0, lo_cnt = 0, lo_n = 0, lo_g0 = 0, lo_ng = 0;   // the site range they were laid out for
+  uint32_t lo_L = 0, lo_R = 0;            // leaves and rows of the tree they were laid out for
+  uint64_t lo_samples = 0;
+  std::vector<uint32_t> lo_parent;        // the tree of the tables below
+  std::vector<uint32_t> lo_first, lo_leaf, lo_rowb;   // first row per leaf [L + 1]; leaf and branch node per row [R]
+  std::vector<long long> lo_fixT;         // [N] llrint(ldexp(T_v, lo_k)): with lo_k what the accumulated ages mean
+  int lo_k = 0;
+  uint32_t *d_lo_first = nullptr, *d_lo_rowb = nullptr;
+  long long *d_lo_fixT = nullptr;
+  unsigned long long *d_lo_out = nullptr;   // window read-out staging
+  uint64_t lo_out_cap = 0;                // bytes
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -914,6 +931,137 @@ int launch_wstat(epv_ctx *c) {
   return EPV_OK;
 }
 
+// ---- lineage origin maps (epv_origin.h): the sites of pavg_range; origin uint32 [R][cnt], age uint64 [L][cnt]
+// the maps off: no accumulators, no tables, no samples
+void origins_off(epv_ctx *c) {
+  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
+  c->lo_on = false;
+  c->lo_lo = c->lo_cnt = c->lo_n = c->lo_g0 = c->lo_ng = 0;
+  c->lo_L = c->lo_R = 0;
+  c->lo_samples = c->lo_out_cap = 0;
+  c->lo_parent.clear(); c->lo_first.clear(); c->lo_leaf.clear(); c->lo_rowb.clear(); c->lo_fixT.clear();
+  c->lo_k = 0;
+}
+// k = 40 - e(H), H = the longest lineage (fp64 sums from the leaf upward), and fixT[v] = llrint(ldexp(T_v, k)):
+// an age term stays below 2^40, so 2^21 samples stay below 2^63
+void origins_scale(const epv_ctx *c, int *k, std::vector<long long> *fixT) {
+  double H = 0.0;
+  for (uint32_t v = 1; v < c->S.N; ++v) {
+    if (c->subtree[v] != 1u) continue;
+    double h = 0.0;
+    for (uint32_t u = v; u != 0u; u = c->parent[u]) h += c->blen[u];
+    if (!(h <= H)) H = h;   // (a NaN sum stays and gives k = 0)
+  }
+  *k = 0;
+  if (H > 0.0 && std::isfinite(H)) {
+    int e = 0;
+    (void)std::frexp(H, &e);
+    *k = std::max(-1000, std::min(1000, 40 - e));
+  }
+  fixT->assign(c->S.N, 0);
+  for (uint32_t v = 1; v < c->S.N; ++v) (*fixT)[v] = std::llrint(std::ldexp(c->blen[v], *k));
+}
+int origins_alloc_try(epv_ctx *c) {
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT);
+  c->lo_cnt = 0;
+  // the row table: per leaf in node order its lineage from the leaf upward, then the root row
+  std::vector<uint32_t> first, leaf, rowb;
+  for (uint32_t v = 1; v < c->S.N; ++v) {
+    if (c->subtree[v] != 1u) continue;
+    first.push_back((uint32_t)rowb.size());
+    for (uint32_t u = v; u != 0u; u = c->parent[u]) { leaf.push_back(v); rowb.push_back(u); }
+    leaf.push_back(v);
+    rowb.push_back(0u);
+  }
+  const uint32_t L = (uint32_t)first.size(), R = (uint32_t)rowb.size();
+  first.push_back(R);
+  const double need = (4.0 * R + 8.0 * L) * (double)cnt;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "lineage origins need %.3g GB of device memory ((4 B x %u rows + 8 B x %u leaves) x "
+                  "%llu sites); %.3g GB are free: use more GPUs (the maps are off)",
+                  need / 1e9, R, L, (unsigned long long)cnt, (double)free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  int k = 0;
+  std::vector<long long> fixT;
+  origins_scale(c, &k, &fixT);
+  HIP_TRY(c, hipMalloc(&c->d_lo_first, sizeof(uint32_t) * first.size()));
+  HIP_TRY(c, hipMalloc(&c->d_lo_rowb, sizeof(uint32_t) * rowb.size()));
+  HIP_TRY(c, hipMalloc(&c->d_lo_fixT, sizeof(long long) * fixT.size()));
+  HIP_TRY(c, hipMemcpy(c->d_lo_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_lo_rowb, rowb.data(), sizeof(uint32_t) * rowb.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_lo_fixT, fixT.data(), sizeof(long long) * fixT.size(), hipMemcpyHostToDevice));
+  if (cnt) {
+    HIP_TRY(c, hipMalloc(&c->d_lo, (size_t)4u * R * cnt));
+    HIP_TRY(c, hipMalloc(&c->d_lo_age, (size_t)8u * L * cnt));
+    HIP_TRY(c, hipMemsetAsync(c->d_lo, 0, (size_t)4u * R * cnt, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_lo_age, 0, (size_t)8u * L * cnt, c->stream));
+  }
+  c->lo_lo = lo;
+  c->lo_cnt = cnt;
+  c->lo_n = c->S.n;
+  c->lo_g0 = c->S.g0;
+  c->lo_ng = c->S.n_global;
+  c->lo_L = L;
+  c->lo_R = R;
+  c->lo_samples = 0;
+  c->lo_parent = c->parent;
+  c->lo_first.swap(first);
+  c->lo_leaf.swap(leaf);
+  c->lo_rowb.swap(rowb);
+  c->lo_fixT.swap(fixT);
+  c->lo_k = k;
+  return EPV_OK;
+}
+// (re)lay out the accumulators and tables for the current tree and site range; zeroes them.  Whatever fails on
+// the way leaves the maps off
+int origins_alloc(epv_ctx *c) {
+  const int rc = origins_alloc_try(c);
+  if (rc) origins_off(c);
+  return rc;
+}
+// the accumulators match the current site range, and the tree, k and fixT are the ones the samples were taken with
+int ensure_origins(epv_ctx *c) {
+  if (!c->lo_on) return EPV_OK;
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  const bool sites = lo != c->lo_lo || cnt != c->lo_cnt || c->S.n != c->lo_n || c->S.g0 != c->lo_g0 ||
+                     c->S.n_global != c->lo_ng;
+  int k = 0;
+  std::vector<long long> fixT;
+  origins_scale(c, &k, &fixT);
+  const bool tree = c->parent != c->lo_parent || k != c->lo_k || fixT != c->lo_fixT;
+  if (!sites && !tree) return EPV_OK;
+  if (c->lo_samples) {
+    if (sites)
+      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the lineage origins took samples: "
+                                    "epv_set_lineage_origins again");
+    return fail(c, EPV_ERR_STATE, "the tree or the branch lengths changed after the lineage origins took samples, so "
+                                  "their rows or fixed-point ages differ: read them out and epv_reset_lineage_origins");
+  }
+  return origins_alloc(c);
+}
+// the resident paths as one sample (ensure_origins first)
+int launch_origins(epv_ctx *c) {
+  if (c->lo_samples >= EPV_BEV_MAX_SAMPLES)
+    return fail(c, EPV_ERR_STATE, "lineage origins hold 2^21 samples, the most their 32-bit counts take: "
+                                  "read them out and epv_reset_lineage_origins");
+  if (c->lo_cnt && c->lo_L)
+    hipLaunchKernelGGL(epv_origin_accum_kernel, dim3((unsigned)((c->lo_cnt + 255u) / 256u), c->lo_L), dim3(256), 0,
+                       c->stream, c->S, c->lo_lo, c->lo_cnt, (const uint32_t *)c->d_lo_first,
+                       (const uint32_t *)c->d_lo_rowb, (const long long *)c->d_lo_fixT, std::ldexp(1.0, c->lo_k),
+                       c->d_lo, c->d_lo_age);
+  HIP_TRY(c, hipGetLastError());
+  ++c->lo_samples;
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -1254,6 +1402,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   dfree(c->d_be); dfree(c->d_be_out);
   dfree(c->d_ws);
+  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -2075,7 +2224,7 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event and window-statistics sample}: the chain of epv_run_mcmc_sums
+// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics and lineage-origin sample}: the chain of epv_run_mcmc_sums
 // and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
 // snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
@@ -2088,6 +2237,10 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
                                   "read them out and epv_reset_branch_events");
   if ((rc = ensure_wstat(c))) return rc;
   if (c->ws_W && (rc = wstat_check_cap(c, batch))) return rc;   // (before any sweep as well)
+  if ((rc = ensure_origins(c))) return rc;
+  if (c->lo_on && c->lo_samples + batch > EPV_BEV_MAX_SAMPLES)
+    return fail(c, EPV_ERR_STATE, "lineage origins would pass 2^21 samples, the most their 32-bit counts take: "
+                                  "read them out and epv_reset_lineage_origins");
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -2103,6 +2256,7 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     if (c->pa_P && (rc = launch_pavg(c))) return rc;
     if (c->be_on && (rc = launch_bevents(c))) return rc;
     if (c->ws_W && (rc = launch_wstat(c))) return rc;
+    if (c->lo_on && (rc = launch_origins(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
@@ -2764,6 +2918,187 @@ EPV_API int epv_get_window_stats(epv_ctx *c, uint64_t first_window, uint64_t n_w
   if (a < e)
     HIP_TRY(c, hipMemcpy(counts + (a - first_window) * V, c->d_ws + (a - c->ws_w0) * V, (e - a) * V * sizeof(int64_t),
                          hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+// ---- lineage origin maps (epv_origin.h)
+EPV_API int epv_set_lineage_origins(epv_ctx *c, int on) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!on) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    origins_off(c);
+    return EPV_OK;
+  }
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->lo_on = true;
+  if ((rc = origins_alloc(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+static const char *const kOriginsOff = "lineage origins are off: epv_set_lineage_origins first";
+
+EPV_API int epv_reset_lineage_origins(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_lo) HIP_TRY(c, hipMemsetAsync(c->d_lo, 0, (size_t)4u * c->lo_R * c->lo_cnt, c->stream));
+  if (c->d_lo_age) HIP_TRY(c, hipMemsetAsync(c->d_lo_age, 0, (size_t)8u * c->lo_L * c->lo_cnt, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->lo_samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_lineage_origins(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_origins(c)) || (rc = launch_origins(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_lineage_origins_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->lo_on ? c->lo_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_lineage_origins_set_samples(epv_ctx *c, uint64_t n) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  c->lo_samples = n;
+  return EPV_OK;
+}
+
+// (no samples yet: lay out for the tree and the sites as they are now)
+static int origins_current(epv_ctx *c) {
+  if (!c->have_tree || !c->have_paths || c->lo_samples) return EPV_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return ensure_origins(c);
+}
+
+EPV_API int epv_lineage_origins_layout(epv_ctx *c, uint32_t *n_leaves, uint32_t *n_rows, uint64_t *first,
+                                       uint64_t *count) {
+  if (!c || !n_leaves || !n_rows || !first || !count) return EPV_ERR_ARG;
+  *n_leaves = *n_rows = 0;
+  *first = *count = 0;
+  if (!c->lo_on) return EPV_OK;
+  const int rc = origins_current(c);
+  if (rc) return rc;
+  *n_leaves = c->lo_L;
+  *n_rows = c->lo_R;
+  *first = c->lo_lo;
+  *count = c->lo_cnt;
+  return EPV_OK;
+}
+
+EPV_API int epv_lineage_origin_rows(epv_ctx *c, uint32_t *leaf_node, uint32_t *branch_node) {
+  if (!c || !leaf_node || !branch_node) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  const int rc = origins_current(c);
+  if (rc) return rc;
+  std::copy(c->lo_leaf.begin(), c->lo_leaf.end(), leaf_node);
+  std::copy(c->lo_rowb.begin(), c->lo_rowb.end(), branch_node);
+  return EPV_OK;
+}
+
+EPV_API int epv_lineage_origins_scale_exp(epv_ctx *c, int *k) {
+  if (!c || !k) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  const int rc = origins_current(c);
+  if (rc) return rc;
+  *k = c->lo_k;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_lineage_origins(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *origin, uint64_t *age) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  if (!origin || !age) return fail(c, EPV_ERR_ARG, "null output");
+  if (first < c->lo_lo || first + count > c->lo_lo + c->lo_cnt)
+    return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
+  if (count == 0) return EPV_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // rows of `count` sites out of rows of lo_cnt
+  HIP_TRY(c, hipMemcpy2D(origin, count * 4u, c->d_lo + (first - c->lo_lo), c->lo_cnt * 4u, count * 4u, c->lo_R,
+                         hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy2D(age, count * 8u, c->d_lo_age + (first - c->lo_lo), c->lo_cnt * 8u, count * 8u, c->lo_L,
+                         hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                           uint64_t *out) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  if (!out) return fail(c, EPV_ERR_ARG, "null output");
+  if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
+  if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
+  if (n_windows == 0) return EPV_OK;
+  const uint64_t rows = c->lo_R, bytes = rows * n_windows * 8u;
+  std::memset(out, 0, ((uint64_t)c->lo_R + c->lo_L) * n_windows * 8u);
+  if (c->lo_cnt == 0 || c->lo_ng == 0 || rows == 0) return EPV_OK;   // this context counts no site
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (bytes > c->lo_out_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_lo_out);
+    c->lo_out_cap = 0;
+    HIP_TRY(c, hipMalloc(&c->d_lo_out, bytes));
+    c->lo_out_cap = bytes;
+  }
+  if (W > c->lo_ng) W = c->lo_ng;   // one window holds the genome: the same sums, and w W cannot overflow
+  uint32_t Wp = 256u;
+  if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
+  const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
+  if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many windows in one call: read them out in pieces");
+  // (the branch events' window kernel: generic uint32 rows x cnt, blockIdx.y = row; a deep tree has more rows
+  // than a grid's y dimension takes)
+  for (uint64_t r0 = 0; r0 < rows; r0 += 65535u) {
+    const uint64_t nr = std::min<uint64_t>(65535u, rows - r0);
+    hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)nr), dim3(256), 0, c->stream,
+                       (const uint32_t *)c->d_lo + r0 * c->lo_cnt, c->lo_R, c->lo_cnt, c->lo_g0 + c->lo_lo, c->lo_ng, W,
+                       Wp, first_window, n_windows, c->d_lo_out + r0 * n_windows);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipMemcpyAsync(out, c->d_lo_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // the ages are 64-bit cells, which the window kernel does not take: the counted sites that lie in the asked
+  // windows come to the host and are added there, in 128 bits so that a sum beyond 64 is refused, not wrapped
+  const uint64_t glo = c->lo_g0 + c->lo_lo, n_win = (c->lo_ng + W - 1u) / W;
+  const uint64_t w_end = std::min(first_window + n_windows, n_win);
+  if (first_window >= w_end) return EPV_OK;
+  const uint64_t a = std::max(first_window * W, glo), e = std::min(std::min(w_end * W, c->lo_ng), glo + c->lo_cnt);
+  if (a >= e) return EPV_OK;
+  // in pieces of sites (512 KB of cells on the host at a time, or 1024 sites of every leaf); a window that
+  // straddles two pieces gets both parts
+  const uint64_t piece = std::max<uint64_t>(1024u, (1ull << 16) / c->lo_L);
+  try {
+    std::vector<unsigned long long> cells((size_t)c->lo_L * std::min(piece, e - a));
+    for (uint64_t p0 = a; p0 < e; p0 += piece) {
+      const uint64_t p1 = std::min(p0 + piece, e), len = p1 - p0;
+      HIP_TRY(c, hipMemcpy2D(cells.data(), len * 8u, c->d_lo_age + (p0 - glo), c->lo_cnt * 8u, len * 8u, c->lo_L,
+                             hipMemcpyDeviceToHost));
+      for (uint32_t l = 0; l < c->lo_L; ++l) {
+        const unsigned long long *p = cells.data() + (size_t)l * len;
+        uint64_t *o = out + (rows + l) * n_windows;
+        for (uint64_t g = p0; g < p1;) {
+          const uint64_t w = g / W, stop = std::min((w + 1u) * W, p1);
+          unsigned __int128 sum = o[w - first_window];
+          for (; g < stop; ++g) sum += p[g - p0];
+          if (sum >> 64)
+            return fail(c, EPV_ERR_ARG, "the age sum of a window passes 64 bits: use narrower windows");
+          o[w - first_window] = (uint64_t)sum;
+        }
+      }
+    }
+  } catch (const std::bad_alloc &) {
+    return fail(c, EPV_ERR_ARG, "no host memory for a piece of the lineage origins' ages");
+  }
   return EPV_OK;
 }
 

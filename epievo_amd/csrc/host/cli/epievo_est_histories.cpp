@@ -18,6 +18,10 @@
 // (epv_set_window_stats: J and D per branch and window of W sites as exact integers, then per window the sums
 // over the branches and the regional rate factor under the model of the run; epv::write_window_stats).
 // Changes nothing else the run writes.
+// New: -O/--origins FILE with the same -w/--window W: the lineage origin maps of the B batch sweeps
+// (epv_set_lineage_origins: per leaf and site on which branch of the leaf's lineage the state last changed, and
+// the age of the leaf's state), summed over windows of W sites, as integers (epv::write_lineage_origins).
+// Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -42,7 +46,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
@@ -68,8 +72,10 @@ int main(int argc, const char **argv) {
                       false, changes_file);
     opt_parse.add_opt("regional", 'r', "output file of J and D per window of the batch sweeps, with regional rate factors",
                       false, regional_file);
-    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps and regional statistics (default 1)", false,
-                      window);
+    opt_parse.add_opt("origins", 'O', "output file of the lineage origin maps of the batch sweeps (integer window sums)",
+                      false, origins_file);
+    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics and origin maps "
+                      "(default 1)", false, window);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -90,9 +96,9 @@ int main(int argc, const char **argv) {
     }
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
-    if (window != no_window && changes_file.empty() && regional_file.empty())
-      throw std::runtime_error("-w/--window belongs to -c/--changes and -r/--regional: give the output file of the "
-                               "branch-event maps or of the regional statistics");
+    if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty())
+      throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional and -O/--origins: give the output "
+                               "file of the branch-event maps, of the regional statistics or of the origin maps");
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
@@ -137,6 +143,7 @@ int main(int argc, const char **argv) {
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);
     if (!changes_file.empty()) mcmc.set_branch_events(true);
     if (!regional_file.empty()) mcmc.set_window_stats(window);
+    if (!origins_file.empty()) mcmc.set_lineage_origins(true);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -173,6 +180,17 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING REGIONAL STATISTICS OF " << n_samples << " SAMPLES: " << regional_file << "]" << endl;
       epv::write_window_stats(regional_file, th.node_names, th.n_nodes(), n_windows, W, th.branches.data(),
                               scale_exp.data(), counts.data(), n_samples, Jw.data(), Dw.data(), the_model.rates);
+    }
+    if (!origins_file.empty()) {
+      vector<uint32_t> leaf_node, branch_node;
+      vector<uint64_t> origin, age;
+      uint64_t n_samples = 0;
+      int k = 0;
+      mcmc.lineage_origin_rows(leaf_node, branch_node);
+      mcmc.download_lineage_origin_windows(window, origin, age, k, n_samples);
+      if (VERBOSE) cerr << "[WRITING LINEAGE ORIGINS OF " << n_samples << " SAMPLES: " << origins_file << "]" << endl;
+      epv::write_lineage_origins(origins_file, th.node_names, leaf_node.size(), leaf_node.data(), branch_node.data(),
+                                 mcmc.branch_event_windows(window), window, k, origin.data(), age.data(), n_samples);
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

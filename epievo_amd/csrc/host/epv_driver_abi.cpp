@@ -24,6 +24,9 @@ struct epvd_sampler {
   std::vector<int64_t> staged_wstat;   // between epvd_window_stats_sizes and epvd_download_window_stats
   uint64_t staged_wstat_nw = 0, staged_wstat_ns = 0;
   bool have_staged_wstat = false;
+  std::vector<uint32_t> staged_origin;   // between epvd_lineage_origins_sizes and epvd_download_lineage_origins
+  std::vector<uint64_t> staged_age;
+  bool have_staged_origins = false;
 };
 
 namespace {
@@ -254,5 +257,68 @@ EPVD_API int epvd_download_window_stats(epvd_sampler *h, int64_t *counts, double
     }
     h->staged_wstat.clear();
     h->have_staged_wstat = false;
+  });
+}
+
+EPVD_API int epvd_set_lineage_origins(epvd_sampler *h, int on) {
+  return guarded(h, [&] { h->s->set_lineage_origins(on != 0); });
+}
+EPVD_API int epvd_reset_lineage_origins(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_lineage_origins(); });
+}
+EPVD_API int epvd_accumulate_lineage_origins(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_lineage_origins(); });
+}
+EPVD_API int epvd_lineage_origin_rows(epvd_sampler *h, uint32_t *n_leaves, uint32_t *n_rows, uint32_t *leaf_node,
+                                      uint32_t *branch_node) {
+  return guarded(h, [&] {
+    std::vector<uint32_t> leaf, node;
+    h->s->lineage_origin_rows(leaf, node);
+    uint32_t L = 0;
+    for (uint32_t v : node) L += v == 0u;   // one root row per leaf
+    *n_leaves = L;
+    *n_rows = (uint32_t)node.size();
+    if (leaf_node) std::copy(leaf.begin(), leaf.end(), leaf_node);
+    if (branch_node) std::copy(node.begin(), node.end(), branch_node);
+  });
+}
+EPVD_API int epvd_lineage_origins_scale_exp(epvd_sampler *h, int *k) {
+  return guarded(h, [&] { *k = h->s->lineage_origins_scale_exp(); });
+}
+EPVD_API int epvd_lineage_origins_sizes(epvd_sampler *h, uint64_t *n_origin, uint64_t *n_age, int *k, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t ns = 0;
+    int kk = 0;
+    h->s->download_lineage_origins(h->staged_origin, h->staged_age, kk, ns);
+    h->have_staged_origins = true;
+    *n_origin = h->staged_origin.size();
+    *n_age = h->staged_age.size();
+    *k = kk;
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_lineage_origins(epvd_sampler *h, uint32_t *origin, uint64_t *age) {
+  return guarded(h, [&] {
+    if (!h->have_staged_origins) throw std::runtime_error("epvd_lineage_origins_sizes first");
+    std::copy(h->staged_origin.begin(), h->staged_origin.end(), origin);
+    std::copy(h->staged_age.begin(), h->staged_age.end(), age);
+    h->staged_origin.clear();
+    h->staged_age.clear();
+    h->have_staged_origins = false;
+  });
+}
+EPVD_API int epvd_download_lineage_origin_windows(epvd_sampler *h, uint64_t W, uint64_t n_windows, uint64_t *origin,
+                                                  uint64_t *age, int *k, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> o, a;
+    uint64_t ns = 0;
+    int kk = 0;
+    if (n_windows != h->s->branch_event_windows(W))
+      throw std::runtime_error("epvd_download_lineage_origin_windows: n_windows must be ceil(genome length / W), W >= 1");
+    h->s->download_lineage_origin_windows(W, o, a, kk, ns);
+    std::copy(o.begin(), o.end(), origin);
+    std::copy(a.begin(), a.end(), age);
+    if (k) *k = kk;
+    if (n_samples) *n_samples = ns;
   });
 }

@@ -385,3 +385,56 @@ EPVH_API void epvh_window_stats_copy(void *h, char *names, int names_len, double
   std::copy(ws->factor.begin(), ws->factor.end(), factor);
 }
 EPVH_API void epvh_window_stats_free(void *h) { delete (epv::WindowStats *)h; }
+
+// ---- lineage origin maps: the file of epievo_est_histories -O
+static std::vector<std::string> split_names(const char *joined) {
+  std::vector<std::string> names;
+  std::string cur;
+  for (const char *p = joined; *p; ++p) {
+    if (*p == '\n') { names.push_back(cur); cur.clear(); } else cur.push_back(*p);
+  }
+  names.push_back(cur);
+  return names;
+}
+static std::string join_names(const std::vector<std::string> &names) {
+  std::string joined;
+  for (size_t i = 0; i < names.size(); ++i) joined += (i ? "\n" : "") + names[i];
+  return joined;
+}
+// node_names: every node's name joined by '\n' (the root's first); origin [n_rows][n_windows], age [leaves][n_windows]
+EPVH_API int epvh_write_lineage_origins(const char *file, const char *node_names, uint64_t n_rows,
+                                        const uint32_t *leaf_node, const uint32_t *branch_node, uint64_t n_windows,
+                                        uint64_t window, int scale_exp, const uint64_t *origin, const uint64_t *age,
+                                        uint64_t n_samples) {
+  try {
+    epv::write_lineage_origins(file, split_names(node_names), n_rows, leaf_node, branch_node, n_windows, window, scale_exp,
+                               origin, age, n_samples);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_lineage_origins(const char *file) {
+  try {
+    return new epv::LineageOrigins(epv::read_lineage_origins(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+// names_len: the bytes epvh_lineage_origins_copy needs for either list of names, the closing 0 included
+EPVH_API void epvh_lineage_origins_dims(void *h, uint64_t *n_samples, uint64_t *window, uint64_t *n_windows, int *scale_exp,
+                                        uint64_t *n_rows, uint64_t *n_leaves, uint64_t *names_len) {
+  const epv::LineageOrigins *lo = (const epv::LineageOrigins *)h;
+  *n_samples = lo->n_samples;
+  *window = lo->window;
+  *n_windows = lo->n_windows;
+  *scale_exp = lo->scale_exp;
+  *n_rows = lo->row_leaf.size();
+  *n_leaves = lo->n_windows ? lo->age.size() / lo->n_windows : 0u;
+  *names_len = std::max(join_names(lo->row_leaf).size(), join_names(lo->row_node).size()) + 1u;
+}
+EPVH_API void epvh_lineage_origins_copy(void *h, char *row_leaf, char *row_node, int names_len, uint64_t *origin,
+                                        uint64_t *age) {
+  const epv::LineageOrigins *lo = (const epv::LineageOrigins *)h;
+  put_text(join_names(lo->row_leaf), row_leaf, names_len);
+  put_text(join_names(lo->row_node), row_node, names_len);
+  std::copy(lo->origin.begin(), lo->origin.end(), origin);
+  std::copy(lo->age.begin(), lo->age.end(), age);
+}
+EPVH_API void epvh_lineage_origins_free(void *h) { delete (epv::LineageOrigins *)h; }

@@ -778,6 +778,94 @@ WindowStats read_window_stats(const std::string &file) {
   return ws;
 }
 
+void write_lineage_origins(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_rows,
+                           const uint32_t *leaf_node, const uint32_t *branch_node, uint64_t n_windows, uint64_t window,
+                           int scale_exp, const uint64_t *origin, const uint64_t *age, uint64_t n_samples) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#samples\t" << n_samples << "\twindow\t" << window << "\tscale_exp\t" << scale_exp << '\n';
+  for (uint64_t r = 0; r < n_rows; ++r)
+    out << "#row\t" << r << "\t" << node_names.at(leaf_node[r]) << "\t" << node_names.at(branch_node[r]) << '\n';
+  uint64_t leaf = 0;
+  for (uint64_t r0 = 0; r0 < n_rows; ++leaf) {
+    uint64_t r1 = r0;
+    while (r1 < n_rows && branch_node[r1] != 0u) ++r1;   // the root row ends a leaf's rows
+    if (r1 == n_rows) throw std::runtime_error("write_lineage_origins: the last row of a leaf must be its root row");
+    out << "LEAF:" << node_names.at(leaf_node[r0]) << "\t" << r1 - r0 + 1u << '\n';
+    for (uint64_t w = 0; w < n_windows; ++w) {
+      out << w * window;
+      for (uint64_t r = r0; r <= r1; ++r) out << "\t" << origin[r * n_windows + w];
+      out << "\t" << age[leaf * n_windows + w] << '\n';
+    }
+    r0 = r1 + 1u;
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+LineageOrigins read_lineage_origins(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad lineage-origins file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("lineage-origins file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  LineageOrigins lo;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 6 || f[0] != "#samples" || f[2] != "window" || f[4] != "scale_exp") throw bad("bad header: " + line);
+  lo.n_samples = std::stoull(f[1]);
+  lo.window = std::stoull(f[3]);
+  lo.scale_exp = std::stoi(f[5]);
+  std::vector<std::vector<std::vector<uint64_t>>> leaves;   // [leaf][window][rows + 1]
+  std::vector<uint64_t> leaf_rows;
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    f = fields(line);
+    if (f[0] == "#row") {
+      if (f.size() != 4 || std::stoull(f[1]) != lo.row_leaf.size() || !leaves.empty()) throw bad("bad row line: " + line);
+      lo.row_leaf.push_back(f[2]);
+      lo.row_node.push_back(f[3]);
+    } else if (line.compare(0, 5, "LEAF:") == 0) {
+      if (f.size() != 2) throw bad("bad leaf line: " + line);
+      leaf_rows.push_back(std::stoull(f[1]));
+      leaves.emplace_back();
+    } else {
+      if (leaves.empty() || f.size() != leaf_rows.back() + 2u) throw bad("bad window line: " + line);
+      if (std::stoull(f[0]) != leaves.back().size() * lo.window) throw bad("windows out of order: " + line);
+      std::vector<uint64_t> v(f.size() - 1u);
+      for (size_t i = 1; i < f.size(); ++i) v[i - 1u] = std::stoull(f[i]);
+      leaves.back().push_back(v);
+    }
+  }
+  const uint64_t R = lo.row_leaf.size(), L = leaves.size();
+  uint64_t rows = 0;
+  for (uint64_t n : leaf_rows) rows += n;
+  if (rows != R) throw bad("the leaf blocks hold another number of rows than the row table");
+  lo.n_windows = L ? leaves[0].size() : 0u;
+  lo.origin.assign(R * lo.n_windows, 0u);
+  lo.age.assign(L * lo.n_windows, 0u);
+  uint64_t r0 = 0;
+  for (uint64_t l = 0; l < L; ++l) {
+    if (leaves[l].size() != lo.n_windows) throw bad("a leaf has another number of windows");
+    for (uint64_t w = 0; w < lo.n_windows; ++w) {
+      for (uint64_t i = 0; i < leaf_rows[l]; ++i) lo.origin[(r0 + i) * lo.n_windows + w] = leaves[l][w][i];
+      lo.age[l * lo.n_windows + w] = leaves[l][w][leaf_rows[l]];
+    }
+    r0 += leaf_rows[l];
+  }
+  return lo;
+}
+
 }  // namespace epv
 
 namespace epv {

@@ -90,6 +90,25 @@ void write_window_stats(const std::string &file, const std::vector<std::string> 
                         const std::array<double, 8> &rates);
 WindowStats read_window_stats(const std::string &file);
 
+// the lineage origin maps of epievo_est_histories -O (epv_get_lineage_origin_windows), integers only:
+//   "#samples\t<S>\twindow\t<W>\tscale_exp\t<k>" (an age integer is a time in units of 2^-k), then the row
+//   table, one line "#row\t<r>\t<leaf name>\t<node name>" per row (the node whose branch the row belongs to;
+//   a leaf's last row, the root row, names the root), then per leaf in node order "LEAF:<name>\t<rows>" and
+//   one line per window: its first global site, the window sums of the leaf's origin rows from the leaf's own
+//   branch up to the root row, and the window's age sum, tab-separated.
+// origin: [r][w], age: [l][w] (uint64); leaf_node, branch_node: per row (epv_lineage_origin_rows)
+struct LineageOrigins {
+  uint64_t n_samples = 0, window = 0, n_windows = 0;
+  int scale_exp = 0;
+  std::vector<std::string> row_leaf, row_node;   // names per row
+  std::vector<uint64_t> origin;                  // [r][w]
+  std::vector<uint64_t> age;                     // [l][w]
+};
+void write_lineage_origins(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_rows,
+                           const uint32_t *leaf_node, const uint32_t *branch_node, uint64_t n_windows, uint64_t window,
+                           int scale_exp, const uint64_t *origin, const uint64_t *age, uint64_t n_samples);
+LineageOrigins read_lineage_origins(const std::string &file);
+
 // the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
 // then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The
 // device keeps one length per branch, so paths whose tot_time differs from the tree's branch length

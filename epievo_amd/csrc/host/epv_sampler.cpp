@@ -364,6 +364,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
+  if (origins_) set_lineage_origins(true);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -373,6 +374,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
+  if (origins_) set_lineage_origins(true);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -514,6 +516,110 @@ std::vector<int> SingleSiteSampler::window_stats_scale_exps() {
   epv_ctx *c = contexts().at(0);     // (every context of a genome has its tree and its n_global)
   if (n_nodes_ > 1) check_on(c, epv_window_stats_scale_exps(c, k.data() + 1), "epv_window_stats_scale_exps");
   return k;
+}
+
+void SingleSiteSampler::set_lineage_origins(bool on) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !on)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_lineage_origins(c, on ? 1 : 0), "epv_set_lineage_origins");
+  origins_ = on;
+}
+
+void SingleSiteSampler::reset_lineage_origins() {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_lineage_origins(c), "epv_reset_lineage_origins");
+}
+
+void SingleSiteSampler::accumulate_lineage_origins() {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_lineage_origins(c), "epv_accumulate_lineage_origins");
+}
+
+// the sample count and the scale exponent every context agrees on
+static uint64_t lineage_origin_samples(const std::vector<epv_ctx *> &cs, int &k) {
+  uint64_t n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint64_t ns = 0;
+    int ki = 0;
+    if (epv_lineage_origins_samples(cs[i], &ns) != EPV_OK) throw std::runtime_error("epv_lineage_origins_samples failed");
+    if (epv_lineage_origins_scale_exp(cs[i], &ki) != EPV_OK)
+      throw std::runtime_error(std::string("epv_lineage_origins_scale_exp: ") + epv_last_error(cs[i]));
+    if (i == 0) { n_samples = ns; k = ki; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of lineage-origin samples");
+    else if (ki != k) throw std::runtime_error("the contexts hold lineage-origin ages of different scales");
+  }
+  return n_samples;
+}
+
+void SingleSiteSampler::lineage_origin_rows(std::vector<uint32_t> &leaf_node, std::vector<uint32_t> &branch_node) {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  epv_ctx *c = contexts().at(0);     // (every context of a genome has its tree)
+  uint32_t L = 0, R = 0;
+  uint64_t first = 0, count = 0;
+  check_on(c, epv_lineage_origins_layout(c, &L, &R, &first, &count), "epv_lineage_origins_layout");
+  leaf_node.assign(R, 0u);
+  branch_node.assign(R, 0u);
+  if (R) check_on(c, epv_lineage_origin_rows(c, leaf_node.data(), branch_node.data()), "epv_lineage_origin_rows");
+}
+
+int SingleSiteSampler::lineage_origins_scale_exp() {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  int k = 0;
+  (void)lineage_origin_samples(contexts(), k);
+  return k;
+}
+
+void SingleSiteSampler::download_lineage_origins(std::vector<uint32_t> &origin, std::vector<uint64_t> &age, int &k,
+                                                 uint64_t &n_samples) {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  const std::vector<epv_ctx *> cs = contexts();
+  std::vector<uint64_t> first(cs.size()), count(cs.size());
+  uint64_t total = 0;
+  uint32_t L = 0, R = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    check_on(cs[i], epv_lineage_origins_layout(cs[i], &L, &R, &first[i], &count[i]), "epv_lineage_origins_layout");
+    total += count[i];
+  }
+  n_samples = lineage_origin_samples(cs, k);
+  origin.assign((uint64_t)R * total, 0u);
+  age.assign((uint64_t)L * total, 0u);
+  std::vector<uint32_t> po;
+  std::vector<uint64_t> pa;
+  uint64_t at = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {   // contexts in genome order, each one's sites contiguous
+    po.assign((uint64_t)R * count[i], 0u);
+    pa.assign((uint64_t)L * count[i], 0u);
+    if (count[i])
+      check_on(cs[i], epv_get_lineage_origins(cs[i], first[i], count[i], po.data(), pa.data()), "epv_get_lineage_origins");
+    for (uint64_t r = 0; r < R; ++r)
+      std::copy(po.begin() + r * count[i], po.begin() + (r + 1) * count[i], origin.begin() + r * total + at);
+    for (uint64_t l = 0; l < L; ++l)
+      std::copy(pa.begin() + l * count[i], pa.begin() + (l + 1) * count[i], age.begin() + l * total + at);
+    at += count[i];
+  }
+}
+
+void SingleSiteSampler::download_lineage_origin_windows(uint64_t W, std::vector<uint64_t> &origin,
+                                                        std::vector<uint64_t> &age, int &k, uint64_t &n_samples) {
+  if (!origins_) throw std::runtime_error("lineage origins are off: set_lineage_origins first");
+  if (W == 0) throw std::runtime_error("a window holds at least one site");
+  const std::vector<epv_ctx *> cs = contexts();
+  uint32_t L = 0, R = 0;
+  uint64_t first = 0, count = 0;
+  check_on(cs.at(0), epv_lineage_origins_layout(cs[0], &L, &R, &first, &count), "epv_lineage_origins_layout");
+  const uint64_t nw = (n_sites_ + W - 1u) / W;
+  n_samples = lineage_origin_samples(cs, k);
+  std::vector<uint64_t> sums(((uint64_t)R + L) * nw, 0u), part(((uint64_t)R + L) * nw);
+  for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites
+    check_on(c, epv_get_lineage_origin_windows(c, W, 0u, nw, part.data()), "epv_get_lineage_origin_windows");
+    for (size_t i = 0; i < part.size(); ++i) {
+      if (part[i] > UINT64_MAX - sums[i])   // (a context alone refuses such a sum: so does their total)
+        throw std::runtime_error("the age sum of a window passes 64 bits: use narrower windows");
+      sums[i] += part[i];
+    }
+  }
+  origin.assign(sums.begin(), sums.begin() + (uint64_t)R * nw);
+  age.assign(sums.begin() + (uint64_t)R * nw, sums.end());
 }
 
 void SingleSiteSampler::set_unobserved(std::vector<uint8_t> whole_genome) {

@@ -131,6 +131,21 @@ public:
   void window_counts_to_stats(const std::vector<int64_t> &counts, uint64_t n_windows, uint64_t n_samples,
                               std::vector<double> &J, std::vector<double> &D);
   std::vector<int> window_stats_scale_exps();
+  // lineage origin maps (epv_set_lineage_origins) on every context, with the branch events' samples and
+  // lifecycle.  lineage_origin_rows: per row the leaf node and the branch node (0 = a leaf's root row);
+  // download_lineage_origins: origin[r * sites + site] (R rows), age[l * sites + site] (L rows) over the sites
+  // of this process in genome order, k = the ages' scale exponent (an age integer is a time in units of
+  // 2^-k); download_lineage_origin_windows: origin[r * n_windows + w], age[l * n_windows + w] over windows of
+  // W global sites, all slots and contexts of this process added as integers
+  void set_lineage_origins(bool on);
+  bool lineage_origins_on() const { return origins_; }
+  void reset_lineage_origins();
+  void accumulate_lineage_origins();
+  void lineage_origin_rows(std::vector<uint32_t> &leaf_node, std::vector<uint32_t> &branch_node);
+  int lineage_origins_scale_exp();   // k, the same on every context
+  void download_lineage_origins(std::vector<uint32_t> &origin, std::vector<uint64_t> &age, int &k, uint64_t &n_samples);
+  void download_lineage_origin_windows(uint64_t W, std::vector<uint64_t> &origin, std::vector<uint64_t> &age, int &k,
+                                       uint64_t &n_samples);
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
@@ -225,6 +240,7 @@ private:
   uint32_t pa_points_ = 0;    // set_path_average
   bool bevents_ = false;      // set_branch_events
   uint64_t wstat_W_ = 0;      // set_window_stats
+  bool origins_ = false;      // set_lineage_origins
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

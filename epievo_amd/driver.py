@@ -18,7 +18,10 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average",
                   "epvd_set_branch_events", "epvd_branch_events_sizes", "epvd_download_branch_events",
                   "epvd_download_branch_event_windows",
-                  "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats"]
+                  "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats",
+                  "epvd_set_lineage_origins", "epvd_reset_lineage_origins", "epvd_accumulate_lineage_origins",
+                  "epvd_lineage_origin_rows", "epvd_lineage_origins_scale_exp", "epvd_lineage_origins_sizes", "epvd_download_lineage_origins",
+                  "epvd_download_lineage_origin_windows"]
 
 
 def lib():
@@ -59,6 +62,15 @@ def lib():
         L.epvd_set_window_stats.argtypes = [vp, C.c_uint64]
         L.epvd_window_stats_sizes.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_window_stats.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
+        ip = C.POINTER(C.c_int)
+        L.epvd_set_lineage_origins.argtypes = [vp, C.c_int]
+        L.epvd_reset_lineage_origins.argtypes = [vp]
+        L.epvd_accumulate_lineage_origins.argtypes = [vp]
+        L.epvd_lineage_origin_rows.argtypes = [vp, u32p, u32p, u32p, u32p]
+        L.epvd_lineage_origins_scale_exp.argtypes = [vp, ip]
+        L.epvd_lineage_origins_sizes.argtypes = [vp, u64p, u64p, ip, u64p]
+        L.epvd_download_lineage_origins.argtypes = [vp, u32p, u64p]
+        L.epvd_download_lineage_origin_windows.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, u64p, ip, u64p]
         _lib = L
     return _lib
 
@@ -258,3 +270,58 @@ class CppSampler:
         if not ns:
             raise DriverError("window statistics hold no sample")
         return ns, J, D
+
+    def enable_lineage_origins(self, on=True):
+        """lineage origin maps on every context (False = off); kept across reset()"""
+        self._ck(self.L.epvd_set_lineage_origins(self.h, 1 if on else 0))
+
+    def reset_lineage_origins(self):
+        self._ck(self.L.epvd_reset_lineage_origins(self.h))
+
+    def accumulate_lineage_origins(self):
+        self._ck(self.L.epvd_accumulate_lineage_origins(self.h))
+
+    def lineage_origin_rows(self):
+        """uint32 [R, 2]: per row the leaf node and the branch node (0 = the leaf's root row)"""
+        nl, nr = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self.L.epvd_lineage_origin_rows(self.h, C.byref(nl), C.byref(nr), None, None))
+        leaf, node = np.zeros(max(nr.value, 1), np.uint32), np.zeros(max(nr.value, 1), np.uint32)
+        self._ck(self.L.epvd_lineage_origin_rows(self.h, C.byref(nl), C.byref(nr), _p(leaf, C.c_uint32),
+                                                 _p(node, C.c_uint32)))
+        return np.stack([leaf[:nr.value], node[:nr.value]], axis=1)
+
+    def lineage_origins(self, counts=False):
+        """-> (samples, rows [R, 2], origin [R, sites], age [L, sites]) over the sites of this process: origin /
+        samples and age * 2^-k / samples, or the uint32 and uint64 sums"""
+        rows = self.lineage_origin_rows()
+        R, L = len(rows), int((rows[:, 1] == 0).sum())
+        no, na, k, ns = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+        self._ck(self.L.epvd_lineage_origins_sizes(self.h, C.byref(no), C.byref(na), C.byref(k), C.byref(ns)))
+        origin, age = np.zeros(max(no.value, 1), np.uint32), np.zeros(max(na.value, 1), np.uint64)
+        self._ck(self.L.epvd_download_lineage_origins(self.h, _p(origin, C.c_uint32), _p(age, C.c_uint64)))
+        origin, age, ns = origin[:no.value].reshape(R, -1), age[:na.value].reshape(L, -1), int(ns.value)
+        if counts:
+            return ns, rows, origin, age
+        d = float(ns) if ns else 1.0
+        return ns, rows, origin / d, np.ldexp(age.astype(np.float64), -k.value) / d
+
+    def lineage_origins_scale_exp(self):
+        """k: an age integer is a time in units of 2^-k"""
+        k = C.c_int(0)
+        self._ck(self.L.epvd_lineage_origins_scale_exp(self.h, C.byref(k)))
+        return int(k.value)
+
+    def lineage_origin_windows(self, W):
+        """-> (samples, uint64 [R, windows], uint64 [L, windows]): the origin rows and the ages summed over windows
+        of W global sites (the slots and contexts of this process added)"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        rows = self.lineage_origin_rows()
+        nw = (self.n_global + W - 1) // W
+        o = np.zeros((len(rows), nw), np.uint64)
+        a = np.zeros((int((rows[:, 1] == 0).sum()), nw), np.uint64)
+        ns = C.c_uint64(0)
+        self._ck(self.L.epvd_download_lineage_origin_windows(self.h, W, nw, _p(o, C.c_uint64), _p(a, C.c_uint64), None,
+                                                             C.byref(ns)))
+        return int(ns.value), o, a

@@ -56,6 +56,16 @@ def lib():
         L.epvh_window_stats_copy.restype = None
         L.epvh_window_stats_free.argtypes = [C.c_void_p]
         L.epvh_window_stats_free.restype = None
+        L.epvh_write_lineage_origins.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, u32p, u32p, C.c_uint64, C.c_uint64,
+                                                 C.c_int, u64p, u64p, C.c_uint64]
+        L.epvh_read_lineage_origins.argtypes = [C.c_char_p]
+        L.epvh_read_lineage_origins.restype = C.c_void_p
+        L.epvh_lineage_origins_dims.argtypes = [C.c_void_p, u64p, u64p, u64p, ip, u64p, u64p, u64p]
+        L.epvh_lineage_origins_dims.restype = None
+        L.epvh_lineage_origins_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, u64p, u64p]
+        L.epvh_lineage_origins_copy.restype = None
+        L.epvh_lineage_origins_free.argtypes = [C.c_void_p]
+        L.epvh_lineage_origins_free.restype = None
         _lib = L
     return _lib
 
@@ -298,3 +308,43 @@ def read_window_stats(path):
                     branches=br[:B], scale_exp=k[:B], counts=counts, all_J=aJ, all_D=aD, factor=f)
     finally:
         L.epvh_window_stats_free(h)
+
+
+# ---- lineage origin maps (where each leaf's state arose, and how old it is)
+def write_lineage_origins(path, node_names, rows, window, samples, scale_exp, origin, age):
+    """the file of epievo_est_histories -O.  node_names: per node, the root first; rows uint32 [R, 2] (leaf node,
+    branch node or 0); origin uint64 [R, windows] and age uint64 [L, windows]: integer window sums"""
+    rows = np.asarray(rows, np.uint32).reshape(-1, 2)
+    leaf, node = np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1])
+    origin = np.ascontiguousarray(origin, np.uint64)
+    age = np.ascontiguousarray(age, np.uint64)
+    if origin.ndim != 2 or age.ndim != 2 or origin.shape[0] != len(rows) or age.shape[1] != origin.shape[1] or \
+            age.shape[0] != int((node == 0).sum()):
+        raise ValueError("origin is [rows, windows], age [leaves, windows]")
+    if lib().epvh_write_lineage_origins(path.encode(), "\n".join(node_names).encode(), len(rows), _p(leaf, C.c_uint32),
+                                        _p(node, C.c_uint32), origin.shape[1], int(window), int(scale_exp),
+                                        _p(origin, C.c_uint64), _p(age, C.c_uint64), int(samples)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_lineage_origins(path):
+    """-> dict(samples, window, scale_exp, row_leaf, row_node (names per row; a root row names the root),
+    origin uint64 [R, windows], age uint64 [L, windows])"""
+    L = lib()
+    h = L.epvh_read_lineage_origins(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, W, nw, R, nl, ln = (C.c_uint64(0) for _ in range(6))
+        k = C.c_int(0)
+        L.epvh_lineage_origins_dims(h, C.byref(ns), C.byref(W), C.byref(nw), C.byref(k), C.byref(R), C.byref(nl), C.byref(ln))
+        R, nl, nw = int(R.value), int(nl.value), int(nw.value)
+        b1, b2 = C.create_string_buffer(int(ln.value)), C.create_string_buffer(int(ln.value))
+        origin, age = np.zeros((R, nw), np.uint64), np.zeros((nl, nw), np.uint64)
+        o, a = (origin, age) if R * nw else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+        L.epvh_lineage_origins_copy(h, b1, b2, len(b1), _p(o, C.c_uint64), _p(a, C.c_uint64))
+        return dict(samples=int(ns.value), window=int(W.value), scale_exp=int(k.value),
+                    row_leaf=b1.value.decode().split("\n") if R else [],
+                    row_node=b2.value.decode().split("\n") if R else [], origin=origin, age=age)
+    finally:
+        L.epvh_lineage_origins_free(h)

@@ -141,6 +141,18 @@ class TorchComm:
         self._sync()
 
 
+def add_uint64(parts):
+    """the sum of uint64 arrays of one shape; a sum that passes 64 bits is refused, not wrapped (the age sums of
+    the lineage origin maps over wide windows near the sample cap)"""
+    total = np.array(parts[0], np.uint64)
+    for p in parts[1:]:
+        t = total + np.asarray(p, np.uint64)
+        if (t < total).any():
+            raise OverflowError("a sum over contexts passes 64 bits: use narrower windows")
+        total = t
+    return total
+
+
 class ShardedSampler:
     """SingleSiteSampler over a site-sharded genome.  `device_factory(device)` builds the
     per-rank engine (the HIP DeviceSampler / LocalGroup in the product; the tests inject an
@@ -407,6 +419,71 @@ class ShardedSampler:
         if not ns:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.dev.window_counts_to_stats(own, ns)
+
+    # ---- lineage origin maps: every rank counts its owned columns
+    def enable_lineage_origins(self, on=True):
+        self.dev.enable_lineage_origins(on)
+
+    def reset_lineage_origins(self):
+        self.dev.reset_lineage_origins()
+
+    def accumulate_lineage_origins(self):
+        self.dev.accumulate_lineage_origins()
+
+    def lineage_origins_samples(self):
+        return self.dev.lineage_origins_samples()
+
+    def lineage_origins_layout(self):
+        """(leaves L, rows R, first local site, number of sites) of this rank's engine"""
+        return self.dev.lineage_origins_layout()
+
+    def lineage_origin_rows(self):
+        return self.dev.lineage_origin_rows()
+
+    def lineage_origins_scale_exp(self):
+        return self.dev.lineage_origins_scale_exp()
+
+    def lineage_origins(self, counts=False):
+        """-> (samples, rows [R, 2], origin [R, n_global], age [L, n_global]) of the whole genome, identical on
+        every rank: the ranks' cells are all-gathered (one collective) and concatenated in genome order"""
+        ns, rows, origin, age = self.dev.lineage_origins(counts=True)
+        k = self.dev.lineage_origins_scale_exp()
+        if self.comm.world > 1:
+            R, L = origin.shape[0], age.shape[0]
+            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
+            if origin.shape[1] != sizes[self.comm.rank]:
+                raise RuntimeError("this rank counts %d sites, it owns %d" % (origin.shape[1], sizes[self.comm.rank]))
+            m = max(sizes)
+            mine = np.zeros((R + 2 * L) * m + 3, np.uint32)   # origin rows, age rows (two words a cell), samples, k
+            mine[:R * m].reshape(R, m)[:, :origin.shape[1]] = origin
+            mine[R * m:-3].view(np.uint64).reshape(L, m)[:, :age.shape[1]] = age
+            mine[-3:] = [ns & 0xffffffff, ns >> 32, k & 0xffffffff]
+            allw = self._gather_words(mine)
+            if any(int(w[-3]) | (int(w[-2]) << 32) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of lineage-origin samples")
+            if any(int(w[-1]) != k & 0xffffffff for w in allw):
+                raise RuntimeError("the ranks hold lineage-origin ages of different scales")
+            origin = np.concatenate([allw[r, :R * m].reshape(R, m)[:, :sizes[r]] for r in range(self.comm.world)], axis=1)
+            age = np.concatenate([np.ascontiguousarray(allw[r, R * m:-3]).view(np.uint64).reshape(L, m)[:, :sizes[r]]
+                                  for r in range(self.comm.world)], axis=1)
+        if counts:
+            return ns, rows, origin, age
+        d = float(ns) if ns else 1.0
+        return ns, rows, origin / d, np.ldexp(age.astype(np.float64), -k) / d
+
+    def lineage_origin_windows(self, W):
+        """-> (samples, uint64 [R, windows], uint64 [L, windows]) of the whole genome, identical on every rank:
+        the ranks' contributions (windows of global sites) are all-gathered and added as integers"""
+        ns, ow, aw = self.dev.lineage_origin_windows(W)
+        if self.comm.world > 1:
+            R = ow.shape[0]
+            mine = np.concatenate([ow.reshape(-1), aw.reshape(-1), [np.uint64(ns)]]).astype(np.uint64).view(np.uint32)
+            allw = np.ascontiguousarray(self._gather_words(mine)).view(np.uint64)
+            if any(int(w[-1]) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of lineage-origin samples")
+            tot = add_uint64([w[:-1] for w in allw]).reshape(R + aw.shape[0], -1)
+            ow, aw = tot[:R], tot[R:]
+        return ns, ow, aw
 
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
@@ -738,6 +815,58 @@ class LocalGroup:
         if not ns:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.window_counts_to_stats(cnt, ns)
+
+    # ---- lineage origin maps: every shard counts the sites it owns
+    def enable_lineage_origins(self, on=True):
+        self._each(lambda j, s: s.enable_lineage_origins(on))
+
+    def reset_lineage_origins(self):
+        self._each(lambda j, s: s.reset_lineage_origins())
+
+    def accumulate_lineage_origins(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            raise RuntimeError("reset() the group before taking a lineage-origin sample")
+        self._each(lambda j, s: s.accumulate_lineage_origins())
+
+    def lineage_origins_samples(self):
+        return self.subs[0].lineage_origins_samples()
+
+    def lineage_origins_layout(self):
+        """(leaves L, rows R, first local site of the first shard, sites over all shards)"""
+        lay = self._each(lambda j, s: s.lineage_origins_layout())
+        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay)
+
+    def lineage_origin_rows(self):
+        return self.subs[0].lineage_origin_rows()
+
+    def lineage_origins_scale_exp(self):
+        return self.subs[0].lineage_origins_scale_exp()
+
+    def _same_origin_samples(self, parts):
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of lineage-origin samples")
+        return ns
+
+    def lineage_origins(self, counts=False):
+        """-> (samples, rows [R, 2], origin [R, sites], age [L, sites]) over the group's owned sites, shards in
+        genome order"""
+        parts = self._each(lambda j, s: s.lineage_origins(counts=True))
+        ns = self._same_origin_samples(parts)
+        origin = np.concatenate([p[2] for p in parts], axis=1)
+        age = np.concatenate([p[3] for p in parts], axis=1)
+        if counts:
+            return ns, parts[0][1], origin, age
+        k, d = self.lineage_origins_scale_exp(), float(ns) if ns else 1.0
+        return ns, parts[0][1], origin / d, np.ldexp(age.astype(np.float64), -k) / d
+
+    def lineage_origin_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [R, windows], uint64 [L, windows]): the shards' contributions to the windows of
+        W global sites, added as integers"""
+        if n_windows is None:
+            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
+        parts = self._each(lambda j, s: s.lineage_origin_windows(W, first_window, n_windows))
+        return self._same_origin_samples(parts), add_uint64([p[1] for p in parts]), add_uint64([p[2] for p in parts])
 
     def counters(self):
         out = {}

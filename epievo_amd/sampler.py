@@ -55,6 +55,10 @@ ABI_SYMBOLS = [
     "epv_get_branch_event_windows",
     "epv_set_window_stats", "epv_reset_window_stats", "epv_accumulate_window_stats", "epv_window_stats_samples",
     "epv_window_stats_set_samples", "epv_window_stats_scale_exps", "epv_window_stats_layout", "epv_get_window_stats", "epv_window_counts_to_stats",
+    "epv_set_lineage_origins", "epv_reset_lineage_origins", "epv_accumulate_lineage_origins",
+    "epv_lineage_origins_samples", "epv_lineage_origins_set_samples", "epv_lineage_origins_layout",
+    "epv_lineage_origin_rows", "epv_lineage_origins_scale_exp", "epv_get_lineage_origins",
+    "epv_get_lineage_origin_windows",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
@@ -155,6 +159,16 @@ def lib():
         L.epv_window_stats_layout.argtypes = [vp, u64p, u64p, u64p]
         L.epv_get_window_stats.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]
         L.epv_window_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, dp, dp]
+        L.epv_set_lineage_origins.argtypes = [vp, C.c_int]
+        L.epv_reset_lineage_origins.argtypes = [vp]
+        L.epv_accumulate_lineage_origins.argtypes = [vp]
+        L.epv_lineage_origins_samples.argtypes = [vp, u64p]
+        L.epv_lineage_origins_set_samples.argtypes = [vp, C.c_uint64]
+        L.epv_lineage_origins_layout.argtypes = [vp, u32p, u32p, u64p, u64p]
+        L.epv_lineage_origin_rows.argtypes = [vp, u32p, u32p]
+        L.epv_lineage_origins_scale_exp.argtypes = [vp, C.POINTER(C.c_int)]
+        L.epv_get_lineage_origins.argtypes = [vp, C.c_uint64, C.c_uint64, u32p, u64p]
+        L.epv_get_lineage_origin_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -664,6 +678,72 @@ class DeviceSampler:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.window_counts_to_stats(cnt, ns)
 
+    # ---- lineage origin maps (epv_set_lineage_origins)
+    def enable_lineage_origins(self, on=True):
+        """count, per leaf and site, on which branch of the leaf's lineage the sampled history last changed
+        state, and the age of the leaf's state, after every batch sweep of run_mcmc (False = off)"""
+        self._ck(self.L.epv_set_lineage_origins(self.h, 1 if on else 0))
+
+    def reset_lineage_origins(self):
+        self._ck(self.L.epv_reset_lineage_origins(self.h))
+
+    def accumulate_lineage_origins(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_lineage_origins(self.h))
+
+    def lineage_origins_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_lineage_origins_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def lineage_origins_layout(self):
+        """(leaves L, rows R, first local site, number of sites); zeros when off"""
+        nl, nr, a, k = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_lineage_origins_layout(self.h, C.byref(nl), C.byref(nr), C.byref(a), C.byref(k)))
+        return int(nl.value), int(nr.value), int(a.value), int(k.value)
+
+    def lineage_origin_rows(self):
+        """uint32 [R, 2]: per row the leaf node and the branch node (0 = the leaf's root row)"""
+        R = self.lineage_origins_layout()[1]
+        leaf, node = np.zeros(max(R, 1), np.uint32), np.zeros(max(R, 1), np.uint32)
+        self._ck(self.L.epv_lineage_origin_rows(self.h, _p(leaf, C.c_uint32), _p(node, C.c_uint32)))
+        return np.stack([leaf[:R], node[:R]], axis=1)
+
+    def lineage_origins_scale_exp(self):
+        """k: an age integer is a time in units of 2^-k"""
+        k = C.c_int(0)
+        self._ck(self.L.epv_lineage_origins_scale_exp(self.h, C.byref(k)))
+        return int(k.value)
+
+    def lineage_origins(self, counts=False):
+        """-> (samples, rows [R, 2], origin [R, sites], age [L, sites]): origin / samples = the posterior over the
+        origin branch per leaf and site, age * 2^-k / samples = the posterior mean age of the leaf's state
+        in branch-length units; counts=True gives the uint32 and uint64 sums"""
+        rows = self.lineage_origin_rows()
+        L, R, first, cnt = self.lineage_origins_layout()
+        origin, age = np.zeros((R, cnt), np.uint32), np.zeros((L, cnt), np.uint64)
+        self._ck(self.L.epv_get_lineage_origins(self.h, first, cnt, _p(origin, C.c_uint32), _p(age, C.c_uint64)))
+        ns = self.lineage_origins_samples()
+        if counts:
+            return ns, rows, origin, age
+        k = self.lineage_origins_scale_exp()
+        d = float(ns) if ns else 1.0
+        return ns, rows, origin / d, np.ldexp(age.astype(np.float64), -k) / d
+
+    def lineage_origin_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [R, windows], uint64 [L, windows]): the origin rows and the ages summed over
+        windows of W consecutive global sites, this context's contribution (zero where it counts no site);
+        all windows of the genome unless a range is given"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        if n_windows is None:
+            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
+        L, R = self.lineage_origins_layout()[:2]
+        out = np.zeros((R + L, max(int(n_windows), 0)), np.uint64)
+        self._ck(self.L.epv_get_lineage_origin_windows(self.h, W, int(first_window), out.shape[1], _p(out, C.c_uint64)))
+        return self.lineage_origins_samples(), out[:R], out[R:]
+
 
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
@@ -787,3 +867,31 @@ class SingleSiteSampler:
 
     def window_stats(self, counts=False):
         return self.dev.window_stats(counts)
+
+    # lineage origin maps (DeviceSampler.enable_lineage_origins)
+    def enable_lineage_origins(self, on=True):
+        self.dev.enable_lineage_origins(on)
+
+    def reset_lineage_origins(self):
+        self.dev.reset_lineage_origins()
+
+    def accumulate_lineage_origins(self):
+        self.dev.accumulate_lineage_origins()
+
+    def lineage_origins_samples(self):
+        return self.dev.lineage_origins_samples()
+
+    def lineage_origins_layout(self):
+        return self.dev.lineage_origins_layout()
+
+    def lineage_origin_rows(self):
+        return self.dev.lineage_origin_rows()
+
+    def lineage_origins(self, counts=False):
+        return self.dev.lineage_origins(counts)
+
+    def lineage_origins_scale_exp(self):
+        return self.dev.lineage_origins_scale_exp()
+
+    def lineage_origin_windows(self, W, first_window=0, n_windows=None):
+        return self.dev.lineage_origin_windows(W, first_window, n_windows)

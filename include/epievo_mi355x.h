@@ -487,6 +487,54 @@ int epv_get_window_stats(epv_ctx *ctx, uint64_t first_window, uint64_t n_windows
 int epv_window_counts_to_stats(epv_ctx *ctx, const int64_t *counts, uint64_t n_windows, uint64_t samples,
                                double *J, double *D);
 
+/* ---- lineage origin maps (new): on which branch the state a leaf shows at a site arose, and how long it
+ * has been held.  A joint property of the lineage from a leaf to the root, which the per-branch planes of
+ * the branch events cannot give.
+ * Leaves: the nodes v >= 1 with subtree_sizes[v] == 1, in node order.  The lineage of leaf l is v_0 = l,
+ * v_1 = parent(v_0), ..., v_{d-1} (the child of the root; d = the leaf's depth).  Leaf l owns d + 1 consecutive
+ * rows: rows 0 .. d-1 belong to the branches v_0 .. v_{d-1}, row d is the ROOT ROW (no jump on the lineage:
+ * the state is as old as the root, its age censored at the leaf's depth).  R = sum over leaves of (d + 1).
+ * One sample, per leaf l and counted site s: i* = the smallest i with a jump on branch v_i at s;
+ *   origin[row(l, i*)][s] += 1,  age[l][s] += sum_{i < i*} fixT[v_i] + fix(T_{v_i*} - t_last)
+ * (t_last = the last jump of branch v_i* at s), or without any jump origin[row(l, d)][s] += 1 and
+ * age[l][s] += sum_{i < d} fixT[v_i].  Fixed point: H = the largest fp64 sum T_{v_0} + T_{v_1} + ... over the
+ * leaves, k = 40 - e(H) (e = the frexp exponent; clamped to +-1000; 0 if H is not positive and finite),
+ * fixT[v] = llrint(ldexp(T_v, k)), fix(x) = x 2^k rounded to nearest even.  All sums are integers: they depend
+ * on no kernel path, context or GPU.  origin / samples is the posterior over the origin branch per leaf and
+ * site, age 2^-k / samples the posterior mean age of the leaf's state in branch-length units.
+ * Samples, sites and lifecycle are the branch events': a sample after each batch sweep of epv_run_mcmc /
+ * _sums / _counts or one epv_accumulate_lineage_origins call; kept over epv_reset, epv_set_model, capacity
+ * growth, masks, evidence and epv_sweep_phase; a changed site range lays the maps out again before the first
+ * sample and is EPV_ERR_STATE after it.  The maps remember the tree, k and fixT of their first sample: after
+ * epv_scale_jump_times or another epv_set_tree that changes any of them, a sample or a run is EPV_ERR_STATE
+ * until epv_reset_lineage_origins (before the first sample the tables just follow).  At most 2^21 samples
+ * (the branch events' cap, checked before any sweep of a run); a sample adds at most 2^40 + d to an age, so
+ * the ages then stay below 2^62.
+ * J, D, accept counts, paths, tri_llh and the plan word do not depend on the maps.
+ * epv_set_lineage_origins: on != 0 allocates 4 R + 8 L bytes per counted site (checked against the free
+ *   device memory first) and zeroes them; 0 frees everything.  A layout that fails leaves the maps off.
+ * epv_lineage_origins_set_samples overwrites the sample count and nothing else (a hook for testing the cap).
+ * epv_lineage_origins_layout: leaves L, rows R and the local sites first .. first+count-1 (zeros when off).
+ * epv_lineage_origin_rows: per row the leaf node and the branch node (0 for a root row), R entries each.
+ * epv_lineage_origins_scale_exp: k (of the first sample once there is one).
+ * epv_get_lineage_origins: origin[r][s - first] (uint32, R rows) and age[l][s - first] (uint64, L rows).
+ * epv_get_lineage_origin_windows: out[r][w - first_window] (uint64) for the R origin rows, then
+ *   out[R + l][w - first_window] for the L age rows, summed over window w = GLOBAL sites [w W, (w+1) W): this
+ *   context's contribution, zero where it counts no site, so contexts, shards and GPUs add up.  An age sum
+ *   that passes 64 bits is EPV_ERR_ARG (narrower windows); callers that add contexts must check their own sums
+ *   the same way (the ages come to the host in pieces of sites and are added there). */
+int epv_set_lineage_origins(epv_ctx *ctx, int on);
+int epv_reset_lineage_origins(epv_ctx *ctx);
+int epv_accumulate_lineage_origins(epv_ctx *ctx);
+int epv_lineage_origins_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_lineage_origins_set_samples(epv_ctx *ctx, uint64_t n_samples);
+int epv_lineage_origins_layout(epv_ctx *ctx, uint32_t *n_leaves, uint32_t *n_rows, uint64_t *first, uint64_t *count);
+int epv_lineage_origin_rows(epv_ctx *ctx, uint32_t *leaf_node, uint32_t *branch_node);
+int epv_lineage_origins_scale_exp(epv_ctx *ctx, int *k);
+int epv_get_lineage_origins(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *origin, uint64_t *age);
+int epv_get_lineage_origin_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                   uint64_t *out);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

@@ -92,6 +92,25 @@ int epvd_set_window_stats(epvd_sampler *s, uint64_t W);
 int epvd_window_stats_sizes(epvd_sampler *s, uint64_t *W, uint64_t *n_windows, uint64_t *n_samples);
 int epvd_download_window_stats(epvd_sampler *s, int64_t *counts, double *J, double *D);
 
+/* lineage origin maps (epv_set_lineage_origins on every context; kept across epvd_reset, which starts the maps
+ * from zero).  epvd_lineage_origin_rows: the leaves L, the rows R and, where the pointers are not null, per row
+ * the leaf node and the branch node (0 = a leaf's root row).  epvd_lineage_origins_scale_exp: k.  The maps over
+ * the sites of this process in genome order: sizes first (n_origin = R * sites, n_age = L * sites, k = the ages' scale exponent), then the copy of
+ * origin[r * sites + site] and age[l * sites + site].  epvd_download_lineage_origin_windows:
+ * origin[r * n_windows + w] and age[l * n_windows + w] over windows of W global sites, the slots and contexts of
+ * this process added as integers (a sum beyond 64 bits is an error, not wrapped); n_windows must be
+ * ceil(genome length / W) */
+int epvd_set_lineage_origins(epvd_sampler *s, int on);
+int epvd_reset_lineage_origins(epvd_sampler *s);
+int epvd_accumulate_lineage_origins(epvd_sampler *s);
+int epvd_lineage_origin_rows(epvd_sampler *s, uint32_t *n_leaves, uint32_t *n_rows, uint32_t *leaf_node,
+                             uint32_t *branch_node);
+int epvd_lineage_origins_scale_exp(epvd_sampler *s, int *k);
+int epvd_lineage_origins_sizes(epvd_sampler *s, uint64_t *n_origin, uint64_t *n_age, int *k, uint64_t *n_samples);
+int epvd_download_lineage_origins(epvd_sampler *s, uint32_t *origin, uint64_t *age);
+int epvd_download_lineage_origin_windows(epvd_sampler *s, uint64_t W, uint64_t n_windows, uint64_t *origin,
+                                         uint64_t *age, int *k, uint64_t *n_samples);
+
 #ifdef __cplusplus
 }
 #endif
