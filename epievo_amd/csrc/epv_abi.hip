@@ -1678,6 +1678,43 @@ EPV_API int epv_phase_plan(epv_ctx *c, uint32_t *word) {
   return EPV_OK;
 }
 
+// known-answer entry for the device's Philox blocks: every form a kernel may inline (epv_philox.h) at
+// call sites with run-time and with compile-time-zero counter fields
+__global__ void epv_philox_kat_kernel(uint32_t seed_lo, uint32_t seed_hi, uint32_t n, const uint32_t *ctr, double *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t site = ctr[6u * i], sweep = ctr[6u * i + 1u], b = ctr[6u * i + 2u], k = ctr[6u * i + 3u];
+  const uint32_t t = ctr[6u * i + 4u], blk = ctr[6u * i + 5u];
+  const epv_block2 a = epv_keyed_block<true>(seed_lo, seed_hi, site, sweep, b, k, t, blk);
+  epv_block2 p = epv_keyed_block<false>(seed_lo, seed_hi, site, sweep, b, k, t, blk);
+  epv_block2 f = p;       // the folded call sites, where the counter allows them
+  if (t == 0u && blk == 0u) f = epv_keyed_block<false>(seed_lo, seed_hi, site, sweep, b, k, 0u, 0u);
+  if (t == 0u && blk == 0u && k == 0u) p = epv_keyed_block<false>(seed_lo, seed_hi, site, sweep, b, 0u, 0u, 0u);
+  if (t == 0u && blk == 0u && k == 0u && b == 0u) f = epv_keyed_block<false>(seed_lo, seed_hi, site, sweep, 0u, 0u, 0u, 0u);
+  out[6u * i] = a.d0; out[6u * i + 1u] = a.d1;
+  out[6u * i + 2u] = p.d0; out[6u * i + 3u] = p.d1;
+  out[6u * i + 4u] = f.d0; out[6u * i + 5u] = f.d1;
+}
+
+EPV_API int epv_philox_kat(epv_ctx *c, uint64_t seed, uint32_t n, const uint32_t *counters, double *out) {
+  if (!c || !counters || !out || !n || n > (1u << 20)) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  uint32_t *d_ctr = nullptr;
+  double *d_out = nullptr;
+  HIP_TRY(c, hipMalloc(&d_ctr, (size_t)n * 6u * sizeof(uint32_t)));
+  if (hipMalloc(&d_out, (size_t)n * 6u * sizeof(double)) != hipSuccess) { dfree(d_ctr); return fail(c, EPV_ERR_HIP, "epv_philox_kat: allocation"); }
+  hipError_t e = hipMemcpyAsync(d_ctr, counters, (size_t)n * 6u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    epv_philox_kat_kernel<<<(n + 255u) / 256u, 256, 0, c->stream>>>((uint32_t)seed, (uint32_t)(seed >> 32), n, d_ctr, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 6u * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_ctr); dfree(d_out);
+  if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_philox_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
 EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
   if (!c) return EPV_ERR_ARG;
   if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_unobserved");

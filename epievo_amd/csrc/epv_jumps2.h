@@ -45,6 +45,7 @@ struct EpvCoop {
 #define EPV_COOP_BYTES (64u * (6u * 8u + 7u * 4u))
 
 // the wave's share of a segment list: entries base_first + lane, + stride, ... below n_seg
+template <bool ASM_MUL = true>
 __device__ __forceinline__ void epv_seg_search_wave(const EpvDev &S, const double *s_rates, const EpvCoop &W,
                                                     const EpvSegTask *segs, EpvSegOut *outs, uint64_t n_seg,
                                                     uint64_t base_first, uint64_t stride, uint32_t seed_lo,
@@ -71,7 +72,7 @@ __device__ __forceinline__ void epv_seg_search_wave(const EpvDev &S, const doubl
     bool pend = false;
     if (active) {
       // unlimited room: whether the path overflows is decided when the branch is assembled
-      const int oc = scan_trials(seed_lo, seed_hi, gsite, sweep, node, k, 1u, EPV_INLINE_TRIALS, prev, sampled, len,
+      const int oc = scan_trials<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 1u, EPV_INLINE_TRIALS, prev, sampled, len,
                                  r0, r1, trunc, 0xffffffffu, jt, 1u, 2u, t.start, tstar, cnt, nielsen, &maxm);
       pend = oc != TRIAL_OK;
     }
@@ -100,7 +101,7 @@ __device__ __forceinline__ void epv_seg_search_wave(const EpvDev &S, const doubl
         const uint32_t misc = c_misc[tj], nk = c_nk[tj];
         const uint32_t t0 = c_tbase[tj] + tr_ * EPV_COOP_WINDOW;
         uint32_t njt = 0, tw = 0u, mm = 0u;
-        oc = scan_trials(seed_lo, seed_hi, c_gsite[tj], sweep, nk >> 12, nk & 4095u, t0, EPV_COOP_WINDOW, misc & 1u,
+        oc = scan_trials<ASM_MUL>(seed_lo, seed_hi, c_gsite[tj], sweep, nk >> 12, nk & 4095u, t0, EPV_COOP_WINDOW, misc & 1u,
                          (misc >> 1) & 1u, c_len[tj], c_r0[tj], c_r1[tj], c_trunc[tj], 0xffffffffu,
                          c_tj + (size_t)lane * 2u, 1u, 2u, 0.0, tw, njt, nielsen, &mm);
         c_tw[lane] = tw;
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(256, EPV_SEARCH_WAVES) void epv_seg_search_kernel(E
 // nds = 1: times into the proposal, the meta word to global memory and into the wave's LDS column
 // prop_meta[b * 64 + owner].  outs[seg] is written all the same, so an assembly that runs anyway
 // re-stores the same values.  n_finished (wave-uniform) counts the branches finished here.
+template <bool ASM_MUL = true>
 __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
                                                        EpvSegOut *outs, uint32_t n_seg, uint32_t G, uint32_t rounds,
                                                        uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, bool nielsen,
@@ -203,7 +205,7 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
     uint32_t cnt = 0u, tw = 0u, mm = 0u;
     double jt[2] = {0.0, 0.0};
     if (pend)
-      oc = scan_trials(seed_lo, seed_hi, gsite, sweep, node, k, tcur, 1u, prev, sampled, len, r0, r1, trunc, 0xffffffffu,
+      oc = scan_trials<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, tcur, 1u, prev, sampled, len, r0, r1, trunc, 0xffffffffu,
                        jt, 1u, 2u, t.start, tw, cnt, nielsen, &mm);
     const unsigned long long hit = __ballot(pend && oc != TRIAL_FAIL);
     const uint32_t gh = (uint32_t)(hit >> gbase) & ((1u << G) - 1u);     // this group's hits (G <= 8)
@@ -248,6 +250,7 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
 // proposal; a capacity overflow flags the site (phase index tid).  The task word carries the
 // proposal's buffer and the branch's start state (bits 61, 60) so that the lane's chain does not
 // begin with two dependent loads (sel, then the meta word the proposal kernel wrote)
+template <bool ASM_MUL = true>
 __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
                                                      const EpvSegOut *outs, unsigned long long bt, uint64_t first,
                                                      uint64_t s0, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
@@ -278,9 +281,9 @@ __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const doub
       const double r0 = s_rates[trip0], r1 = s_rates[trip0 | 2u];
       double trunc = 0.0;
       if (sampled != prev) trunc = 1.0 - epv_exp(-(prev ? r1 : r0) * t.len);
-      const double u0 = first_draw(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar);
+      const double u0 = first_draw<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar);
       uint32_t nj2 = 0;
-      run_trial(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar, u0, prev, sampled, t.len, r0, r1, 0.0, 0.0, trunc,
+      run_trial<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar, u0, prev, sampled, t.len, r0, r1, 0.0, 0.0, trunc,
                 room, dst + (uint64_t)cnt * n, n, 0xffffffffu, t.start, nj2, nielsen);
     }
     cnt += o.cnt;

@@ -271,6 +271,7 @@ enum { TRIAL_FAIL = 0, TRIAL_OK = 1, TRIAL_OVERFLOW = 2 };
 // the fp64 rounding of the exact test -- so "1-u < nojump" PROVES the exact computation
 // -log(1-u)/rate >= T (>= the time left) without evaluating log or the division.
 // Everything else takes the exact path below, so the outcome is always the oracle's.
+template <bool ASM_MUL = true>
 __device__ __forceinline__ int run_trial(uint32_t seed_lo, uint32_t seed_hi, uint32_t gsite,
                                          uint32_t sweep, uint32_t node, uint32_t k, uint32_t t,
                                          double u0, uint32_t a0, uint32_t end, double T, double r0,
@@ -290,7 +291,7 @@ __device__ __forceinline__ int run_trial(uint32_t seed_lo, uint32_t seed_hi, uin
     a ^= 1u;
     if (max_store > 0u) dst[0] = tau + start_time;
     nj = 1u;
-    blk = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, t, 0u);
+    blk = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t, 0u);
     u = blk.d0;
     d = 1u;
     if (1.0 - u < (a ? nojump1 : nojump0)) { nj_out = 1u; return TRIAL_OK; }   // a == end now
@@ -305,7 +306,7 @@ __device__ __forceinline__ int run_trial(uint32_t seed_lo, uint32_t seed_hi, uin
     a ^= 1u;
     if (nj < max_store) dst[(uint64_t)nj * stride] = tau + start_time;
     ++nj;
-    if ((d & 1u) == 0u) blk = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, t, d >> 1);
+    if ((d & 1u) == 0u) blk = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t, d >> 1);
     u = (d & 1u) ? blk.d1 : blk.d0;
     ++d;
   }
@@ -320,10 +321,11 @@ __device__ __forceinline__ double nojump_bound(double x) {
 }
 
 // First draw of trial t of segment (node,k) -- see the address table in epv_philox.h
+template <bool ASM_MUL = true>
 __device__ __forceinline__ double first_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t gsite,
                                              uint32_t sweep, uint32_t node, uint32_t k, uint32_t t) {
-  if (t == 1u) return epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
-  const epv_block2 fb = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, t >> 1,
+  if (t == 1u) return epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
+  const epv_block2 fb = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t >> 1,
                                         EPV_FIRST_DRAW_BLOCK);
   return (t & 1u) ? fb.d1 : fb.d0;
 }
@@ -335,6 +337,7 @@ __device__ __forceinline__ double first_draw(uint32_t seed_lo, uint32_t seed_hi,
 // exact thanks to run_trial's guard band), and only a trial that does jump is evaluated
 // exactly.  On a short branch ~95 % of trials never leave the scan.  A segment that changes
 // state (Nielsen) evaluates each trial exactly; nearly every one succeeds.
+template <bool ASM_MUL = true>
 __device__ __forceinline__ int scan_trials(uint32_t seed_lo, uint32_t seed_hi, uint32_t gsite,
                                            uint32_t sweep, uint32_t node, uint32_t k, uint32_t t0,
                                            uint32_t W, uint32_t a0, uint32_t end, double T, double r0,
@@ -362,11 +365,11 @@ __device__ __forceinline__ int scan_trials(uint32_t seed_lo, uint32_t seed_hi, u
     bool cand = false;
     for (; t < t_end; ++t) {
       if (t == 1u) {
-        u = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
+        u = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
       } else {
         if ((t >> 1) != fb_pair) {
           fb_pair = t >> 1;
-          fb = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, k, fb_pair, EPV_FIRST_DRAW_BLOCK);
+          fb = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, fb_pair, EPV_FIRST_DRAW_BLOCK);
         }
         u = (t & 1u) ? fb.d1 : fb.d0;
       }
@@ -379,7 +382,7 @@ __device__ __forceinline__ int scan_trials(uint32_t seed_lo, uint32_t seed_hi, u
     }
     if (!cand) return TRIAL_FAIL;
     const double nb = flip ? bound : 0.0;
-    const int oc = run_trial(seed_lo, seed_hi, gsite, sweep, node, k, t, u, a0, end, T, r0, r1, nb, nb,
+    const int oc = run_trial<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t, u, a0, end, T, r0, r1, nb, nb,
                              trunc, room, dst, stride, max_store, start_time, nj_out, nielsen);
     if (maxm && nj_out > *maxm) *maxm = nj_out;
     if (oc != TRIAL_FAIL) { t_out = t; return oc; }

@@ -36,6 +36,18 @@ struct epv_block2 {
   double d0, d1;
 };
 
+// The two 32 x 32 -> 64 products of a round are one v_mad_u64_u32 each (quarter-rate on CDNA like
+// v_mul_hi_u32 and v_mul_lo_u32, so 20 instead of 40 slow multiplies per block), in one of two forms:
+//   ASM_MUL = false  plain C.  The compiler selects v_mad_u64_u32 itself (given the barrier in the last
+//                    round), schedules it without the s_nop it puts behind an inline-asm instruction it
+//                    cannot see into (11..13 per block), folds the first round's M1 * c2 where a call site
+//                    passes a constant t, and drops a product's unused half.  The fused colour phase
+//                    (epv_propose2.h) uses this form (counts: profiles/inst_diet_static.txt).
+//   ASM_MUL = true   inline asm, every other kernel: with the plain form the sequential jump kernels and
+//                    the one-kernel proposals gain 8..28 bytes of scratch and epv_seg_assemble_kernel
+//                    loses a wave per SIMD (tools/static_mix.sh prints both for any kernel).
+// The bits are the same either way.
+template <bool ASM_MUL = true>
 __device__ __forceinline__ epv_block2 epv_keyed_block(uint32_t seed_lo, uint32_t seed_hi,
                                                       uint32_t site, uint32_t sweep,
                                                       uint32_t b, uint32_t k, uint32_t t,
@@ -44,12 +56,17 @@ __device__ __forceinline__ epv_block2 epv_keyed_block(uint32_t seed_lo, uint32_t
   uint32_t k0 = seed_lo, k1 = seed_hi;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
-    // one v_mad_u64_u32 per 32 x 32 -> 64 product instead of the v_mul_hi_u32 + v_mul_lo_u32 the
-    // compiler picks (all three are quarter-rate on CDNA: 20 instead of 40 slow multiplies per
-    // block; +2..4 % end to end, tools/ab_bench.py; the same bits)
     unsigned long long p0, p1;
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "s"(EPV_PHILOX_M0), "v"(c0) : "vcc");   // p0 = (uint64_t)EPV_PHILOX_M0 * c0
-    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "s"(EPV_PHILOX_M1), "v"(c2) : "vcc");   // p1 = (uint64_t)EPV_PHILOX_M1 * c2
+    if constexpr (ASM_MUL) {
+      asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "s"(EPV_PHILOX_M0), "v"(c0) : "vcc");   // p0 = (uint64_t)EPV_PHILOX_M0 * c0
+      asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "s"(EPV_PHILOX_M1), "v"(c2) : "vcc");   // p1 = (uint64_t)EPV_PHILOX_M1 * c2
+    } else {
+      p0 = (unsigned long long)EPV_PHILOX_M0 * c0;
+      p1 = (unsigned long long)EPV_PHILOX_M1 * c2;
+      // the last round's low words go straight into the output's shifts, where the compiler would split
+      // the product into a v_mul_hi_u32 + v_mul_lo_u32 pair; an empty barrier keeps it one value
+      if (r == 9) asm("" : "+v"(p0), "+v"(p1));
+    }
     const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
     // a ^ b ^ key in ONE instruction: gfx950's three-input boolean op with the XOR3 truth table (0x96);
     // the compiler emits two v_xor_b32 (40 instead of 20 per block).  The key is wave-uniform (kernel
@@ -62,7 +79,8 @@ __device__ __forceinline__ epv_block2 epv_keyed_block(uint32_t seed_lo, uint32_t
     k1 += EPV_PHILOX_W1;
     // keep the key schedule a chain of scalar adds next to its use: hoisted out of the kernels' loops the
     // twenty round keys live in SGPRs from the first block to the last and push other values into spills
-    // (fused phase: 108 -> 91 spilled SGPRs, +1..2 % on tree.nwk; the large-tree kernels: +-0)
+    // (measured when the chain was introduced: fewer spilled SGPRs in the fused phase, +1..2 % on
+    // tree.nwk; the large-tree kernels +-0; today's counts: profiles/inst_diet_static.txt)
     asm volatile("" : "+s"(k0), "+s"(k1));
   }
   const uint64_t a = ((uint64_t)c1 << 32) | c0;

@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       const uint32_t node = (uint32_t)(info >> 9) & 4095u, k = (uint32_t)(info >> 21);
       double m[6];
       epv_seg_matrices(len, s_rates[trip0], s_rates[trip0 | 2u], m);
-      const epv_block2 blk = epv_keyed_block(seed_lo, seed_hi, gsite_lane0 + 3u * owner, sweep, node, k, 0u, 0u);
+      const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite_lane0 + 3u * owner, sweep, node, k, 0u, 0u);
 #pragma unroll
       for (int q = 0; q < 6; ++q) rec[q] = m[q];
       rec[6] = blk.d0;
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               const double *t = s_tab + ((uint32_t)b * 4u + EPV_RW_TAB(r_w[b])) * EPV_SEGTAB_DBL;
               PT0 = prev ? t[3] : t[2];
               nb = prev ? t[5] : t[4];
-              const epv_block2 blk = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, (uint32_t)node, 0u, 0u, 0u);
+              const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite, sweep, (uint32_t)node, 0u, 0u, 0u);
               u_end = blk.d0; u_first = blk.d1;
             } else {
               const double *hr = list + (size_t)(hcur + k) * HREC;
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
             const double *t = s_tab + (b * 4u + 2u * (mL >> EPV_INIT_SHIFT) + (mR >> EPV_INIT_SHIFT)) * EPV_SEGTAB_DBL;   // (32-bit index: an LDS address)
             PT0 = prev ? t[3] : t[2];
             nb = prev ? t[5] : t[4];
-            const epv_block2 blk = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, node, 0u, 0u, 0u);
+            const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite, sweep, node, 0u, 0u, 0u);
             u_end = blk.d0; u_first = blk.d1;
           } else {
             const double *hr = list + (size_t)(hcur + k) * HREC;
@@ -889,10 +889,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       bool done = false;
       if (f_nseg <= 32u && F.grouped_rounds) {
         const uint32_t G = 64u / f_nseg > 8u ? 8u : 64u / f_nseg;
-        done = epv_seg_search_grouped(S, s_rates, segs, outs, f_nseg, G, F.grouped_rounds, seed_lo, seed_hi, sweep, nielsen,
+        done = epv_seg_search_grouped<!FUSED>(S, s_rates, segs, outs, f_nseg, G, F.grouped_rounds, seed_lo, seed_hi, sweep, nielsen,
                                       s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane, f_nfin);
       }
-      if (!done) epv_seg_search_wave(S, s_rates, W, segs, outs, f_nseg, 0u, 64u, seed_lo, seed_hi, sweep, nielsen);
+      if (!done) epv_seg_search_wave<!FUSED>(S, s_rates, W, segs, outs, f_nseg, 0u, 64u, seed_lo, seed_hi, sweep, nielsen);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
       P2_MARK(7);
@@ -901,7 +901,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       // and stores the finished branches' values once more.
       if (!(done && f_nsole == f_nbt && f_nfin == f_nbt)) {
         for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
-          epv_seg_assemble_one(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
+          epv_seg_assemble_one<!FUSED>(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
                                seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -934,7 +934,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         llh_l = S.tri[site - 1]; llh_m = S.tri[site]; llh_r = S.tri[site + 1];
         s_own[my_rank] = (uint32_t)lane | (selLL << 8) | (selL << 9) | ((selM ^ 1u) << 10) | (selR << 11) | (selRR << 12) |
                          ((ovf ? 1u : 0u) << 13);
-        u_acc = epv_keyed_block(seed_lo, seed_hi, gsite, sweep, 0u, 0u, 0u, 0u).d0;
+        u_acc = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite, sweep, 0u, 0u, 0u, 0u).d0;
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -978,7 +978,9 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       if (f_listed) {
         // the owner: Metropolis_Hastings_site :510-533 with the three values (the arithmetic of
         // epv_accept_site, term by term)
-        double llr = (S.flags & EPV_FLAG_REFERENCE_PROPOSAL_RATIO) ? S.prop_llr[tid] : 0.0;
+        // (no proposal ratio: the phase plan never picks this kernel when the reference's ratio or a
+        // sampled root is asked for, so the term is zero by construction)
+        double llr = 0.0;
         const double llh_l_orig = llh_l, llh_r_orig = llh_r;
         if (!ovf) {
           const uint64_t g = S.g0 + site;

@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
+    "epv_phase_plan", "epv_philox_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -127,6 +127,7 @@ def lib():
         L.epv_get_options.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.epv_philox_kat.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, dp]
         L.epv_set_unobserved.argtypes = [vp, u8p]
         L.epv_unobserved_cells.argtypes = [vp, u64p]
         L.epv_set_leaf_evidence.argtypes = [vp, C.POINTER(C.c_float)]
@@ -272,6 +273,14 @@ class DeviceSampler:
                     small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
                     jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
                     unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1))
+
+    def philox_kat(self, seed, counters):
+        """the device's Philox blocks (epv_philox_kat): counters[i] = (site, sweep, branch, segment, trial,
+        block); returns [i, form, 2] doubles, form = inline-asm, plain, plain at a constant-folded call site"""
+        ctr = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 6)
+        out = np.zeros((ctr.shape[0], 3, 2))
+        self._ck(self.L.epv_philox_kat(self.h, int(seed), ctr.shape[0], _p(ctr, C.c_uint32), _p(out, C.c_double)))
+        return out
 
     def set_unobserved(self, mask):
         """missing leaf data (epv_set_unobserved): mask[b-1, s] != 0 -> the leaf end state of branch b at

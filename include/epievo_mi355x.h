@@ -152,6 +152,16 @@ enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
 int epv_phase_plan(epv_ctx *ctx, uint32_t *word);
 
+/* Known-answer entry for the random stream, for tests: evaluates on the device the Philox4x32-10
+ * block of each of n <= 2^20 counters, counters[6 i ..] = site, sweep, branch, segment, trial, block
+ * (the layout of epv_philox.h, key = seed).  out[6 i ..] = (d0, d1) three times: with the inline-asm
+ * multiplies, with the plain ones, and with the plain ones called with literal zeros for the fields
+ * of the counter that are zero (trial and block; segment; branch).  All three pairs equal the CPU
+ * oracle's block.  This checks the two source forms of the block in a kernel of its own; it does
+ * not show what the compiler makes of a call site inside the MCMC kernels -- their bit identity
+ * is what the comparisons of whole runs against the oracle's parallel rung establish. */
+int epv_philox_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *counters, double *out);
+
 /* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
  * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
  * instead of the indicator of the path's end state) instead of pinning it.  The node-major layout
