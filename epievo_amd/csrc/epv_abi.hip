@@ -24,6 +24,7 @@
 #include "epv_bevents.h"
 #include "epv_wstat.h"
 #include "epv_origin.h"
+#include "epv_domains.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
 // Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
@@ -177,6 +178,17 @@ struct epv_ctx {
   long long *d_lo_fixT = nullptr;
   unsigned long long *d_lo_out = nullptr;   // window read-out staging
   uint64_t lo_out_cap = 0;                // bytes
+  // domain size spectra (epv_domains.h), off while !dm_on
+  bool dm_on = false;
+  uint64_t dm_max = 0;                      // samples the edge records are allocated for
+  unsigned long long *d_dm_hist = nullptr;  // [dm_N][2][128] runs closed inside the counted stretch, over the samples
+  unsigned long long *d_dm_len = nullptr;   // [dm_N][2] their lengths
+  unsigned long long *d_dm_edge = nullptr;  // [dm_max][dm_N][2] the two runs a sample's stretch cannot close
+  unsigned long long *d_dm_bits = nullptr;  // [dm_N][dm_words] scratch: the node states of one sample, 64 sites a word
+  uint64_t dm_lo = 0, dm_cnt = 0, dm_n = 0, dm_g0 = 0, dm_ng = 0, dm_words = 0;   // the site range they were laid out for
+  uint32_t dm_N = 0, dm_child0 = 0;         // nodes, and the root's lowest-numbered child
+  uint64_t dm_samples = 0;
+  std::vector<uint32_t> dm_parent;          // the tree they were laid out for
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -1062,6 +1074,112 @@ int launch_origins(epv_ctx *c) {
   return EPV_OK;
 }
 
+// ---- domain size spectra (epv_domains.h): the sites of pavg_range; a context keeps its PART, unclosed
+void domains_off(epv_ctx *c) {
+  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
+  c->dm_on = false;
+  c->dm_max = c->dm_lo = c->dm_cnt = c->dm_n = c->dm_g0 = c->dm_ng = c->dm_words = c->dm_samples = 0;
+  c->dm_N = c->dm_child0 = 0;
+  c->dm_parent.clear();
+}
+int domains_alloc_try(epv_ctx *c) {
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
+  c->dm_cnt = c->dm_words = 0;
+  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^32 - 1 sites per context");
+  const uint32_t N = c->S.N;
+  const uint64_t words = (cnt + 63u) / 64u;
+  const double need = 8.0 * N * (2.0 * EPV_DOM_BINS + 2.0) + 8.0 * N * (double)words + 16.0 * N * (double)c->dm_max;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "domain statistics need %.3g GB of device memory (16 B x %u nodes x %llu samples of "
+                  "edge records, 8 B x %u nodes x %llu words of node states); %.3g GB are free: ask for fewer samples "
+                  "(the statistics are off)",
+                  need / 1e9, N, (unsigned long long)c->dm_max, N, (unsigned long long)words, (double)free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  uint32_t child0 = 0;
+  for (uint32_t v = 1; v < N && !child0; ++v) if (c->parent[v] == 0u) child0 = v;
+  const size_t hist_b = (size_t)16u * EPV_DOM_BINS * N, len_b = (size_t)16u * N, edge_b = (size_t)16u * N * c->dm_max;
+  HIP_TRY(c, hipMalloc(&c->d_dm_hist, hist_b));
+  HIP_TRY(c, hipMalloc(&c->d_dm_len, len_b));
+  HIP_TRY(c, hipMalloc(&c->d_dm_edge, edge_b));
+  if (words) HIP_TRY(c, hipMalloc(&c->d_dm_bits, (size_t)8u * N * words));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_hist, 0, hist_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_len, 0, len_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_edge, 0, edge_b, c->stream));
+  c->dm_lo = lo;
+  c->dm_cnt = cnt;
+  c->dm_words = words;
+  c->dm_n = c->S.n;
+  c->dm_g0 = c->S.g0;
+  c->dm_ng = c->S.n_global;
+  c->dm_N = N;
+  c->dm_child0 = child0;
+  c->dm_samples = 0;
+  c->dm_parent = c->parent;
+  return EPV_OK;
+}
+// (re)lay out the part for the current tree and site range; zeroes it.  Whatever fails on the way leaves the
+// statistics off
+int domains_alloc(epv_ctx *c) {
+  const int rc = domains_alloc_try(c);
+  if (rc) domains_off(c);
+  return rc;
+}
+// the part matches the current site range and tree (branch lengths do not matter: no jump time is read)
+int ensure_domains(epv_ctx *c) {
+  if (!c->dm_on) return EPV_OK;
+  uint64_t lo = 0, cnt = 0;
+  pavg_range(c, &lo, &cnt);
+  const bool sites = lo != c->dm_lo || cnt != c->dm_cnt || c->S.n != c->dm_n || c->S.g0 != c->dm_g0 ||
+                     c->S.n_global != c->dm_ng;
+  const bool tree = c->S.N != c->dm_N || c->parent != c->dm_parent;
+  if (!sites && !tree) return EPV_OK;
+  if (c->dm_samples) {
+    if (sites)
+      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the domain statistics took samples: "
+                                    "epv_set_domain_stats again");
+    return fail(c, EPV_ERR_STATE, "the tree changed after the domain statistics took samples: read them out and "
+                                  "epv_reset_domain_stats");
+  }
+  return domains_alloc(c);
+}
+int domains_check_cap(epv_ctx *c, uint64_t more) {
+  if (c->dm_samples + more > c->dm_max) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "domain statistics hold %llu of the %llu samples their edge records were allocated "
+                  "for, and %llu more were asked: read them out and epv_reset_domain_stats, or epv_set_domain_stats "
+                  "with more", (unsigned long long)c->dm_samples, (unsigned long long)c->dm_max, (unsigned long long)more);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_domains first): pack the node states, then count the runs
+int launch_domains(epv_ctx *c) {
+  int rc = domains_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->dm_cnt) {
+    const uint64_t words = c->dm_words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
+    hipLaunchKernelGGL(epv_dom_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->dm_lo,
+                       c->dm_cnt, words, c->dm_child0, c->d_dm_bits);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *edge = c->d_dm_edge + c->dm_samples * 2u * c->dm_N;
+    for (uint32_t v0 = 0; v0 < c->dm_N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
+      const uint32_t nv = std::min<uint32_t>(65535u, c->dm_N - v0);
+      hipLaunchKernelGGL(epv_dom_runs_kernel, dim3((unsigned)chunks, nv), dim3(256), 0, c->stream,
+                         (const unsigned long long *)c->d_dm_bits, words, c->dm_cnt, v0, c->d_dm_hist, c->d_dm_len, edge);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  ++c->dm_samples;
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -1403,6 +1521,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_be); dfree(c->d_be_out);
   dfree(c->d_ws);
   dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
+  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -2261,7 +2380,7 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics and lineage-origin sample}: the chain of epv_run_mcmc_sums
+// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics, lineage-origin and domain-statistics sample}: the chain of epv_run_mcmc_sums
 // and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
 // snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
@@ -2278,6 +2397,8 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
   if (c->lo_on && c->lo_samples + batch > EPV_BEV_MAX_SAMPLES)
     return fail(c, EPV_ERR_STATE, "lineage origins would pass 2^21 samples, the most their 32-bit counts take: "
                                   "read them out and epv_reset_lineage_origins");
+  if ((rc = ensure_domains(c))) return rc;
+  if (c->dm_on && (rc = domains_check_cap(c, batch))) return rc;   // (before any sweep as well)
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -2294,6 +2415,7 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     if (c->be_on && (rc = launch_bevents(c))) return rc;
     if (c->ws_W && (rc = launch_wstat(c))) return rc;
     if (c->lo_on && (rc = launch_origins(c))) return rc;
+    if (c->dm_on && (rc = launch_domains(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
@@ -3136,6 +3258,87 @@ EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t firs
   } catch (const std::bad_alloc &) {
     return fail(c, EPV_ERR_ARG, "no host memory for a piece of the lineage origins' ages");
   }
+  return EPV_OK;
+}
+
+// ---- domain size spectra (epv_domains.h)
+EPV_API int epv_set_domain_stats(epv_ctx *c, uint64_t max_samples) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!max_samples) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    domains_off(c);
+    return EPV_OK;
+  }
+  if (max_samples > EPV_DOM_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^21 samples");
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->dm_on = true;
+  c->dm_max = max_samples;
+  if ((rc = domains_alloc(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+static const char *const kDomainsOff = "domain statistics are off: epv_set_domain_stats first";
+
+EPV_API int epv_reset_domain_stats(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_hist, 0, (size_t)16u * EPV_DOM_BINS * c->dm_N, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_len, 0, (size_t)16u * c->dm_N, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_dm_edge, 0, (size_t)16u * c->dm_N * c->dm_max, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->dm_samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_domain_stats(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_domains(c)) || (rc = launch_domains(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_domain_stats_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->dm_on ? c->dm_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_domain_stats_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_bins, uint64_t *first, uint64_t *count,
+                                    uint64_t *chunk_sites) {
+  if (!c || !n_nodes || !n_bins || !first || !count || !chunk_sites) return EPV_ERR_ARG;
+  *n_nodes = *n_bins = 0;
+  *first = *count = *chunk_sites = 0;
+  if (!c->dm_on) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->dm_samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_domains(c);
+    if (rc) return rc;
+  }
+  *n_nodes = c->dm_N;
+  *n_bins = EPV_DOM_BINS;
+  *first = c->dm_lo;
+  *count = c->dm_cnt;
+  *chunk_sites = 64ull * EPV_DOM_CHUNK_WORDS;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_domain_stats(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
+  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(hist, c->d_dm_hist, (size_t)16u * EPV_DOM_BINS * c->dm_N, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(len_sum, c->d_dm_len, (size_t)16u * c->dm_N, hipMemcpyDeviceToHost));
+  if (c->dm_samples)
+    HIP_TRY(c, hipMemcpy(edges, c->d_dm_edge, (size_t)16u * c->dm_N * c->dm_samples, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 

@@ -22,6 +22,9 @@
 // (epv_set_lineage_origins: per leaf and site on which branch of the leaf's lineage the state last changed, and
 // the age of the leaf's state), summed over windows of W sites, as integers (epv::write_lineage_origins).
 // Changes nothing else the run writes.
+// New: -d/--domains FILE: the domain size spectra of the B batch sweeps (epv_set_domain_stats with max_samples = B:
+// per node and state the spectrum of run lengths of the node's state along the genome, closed over the whole
+// genome), as integers (epv::write_domain_stats).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -46,7 +49,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
@@ -74,6 +77,8 @@ int main(int argc, const char **argv) {
                       false, regional_file);
     opt_parse.add_opt("origins", 'O', "output file of the lineage origin maps of the batch sweeps (integer window sums)",
                       false, origins_file);
+    opt_parse.add_opt("domains", 'd', "output file of the domain size spectra of the batch sweeps (integer counts per bin)",
+                      false, domains_file);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics and origin maps "
                       "(default 1)", false, window);
     vector<string> leftover_args;
@@ -144,6 +149,7 @@ int main(int argc, const char **argv) {
     if (!changes_file.empty()) mcmc.set_branch_events(true);
     if (!regional_file.empty()) mcmc.set_window_stats(window);
     if (!origins_file.empty()) mcmc.set_lineage_origins(true);
+    if (!domains_file.empty()) mcmc.set_domain_stats(batch);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -191,6 +197,14 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING LINEAGE ORIGINS OF " << n_samples << " SAMPLES: " << origins_file << "]" << endl;
       epv::write_lineage_origins(origins_file, th.node_names, leaf_node.size(), leaf_node.data(), branch_node.data(),
                                  mcmc.branch_event_windows(window), window, k, origin.data(), age.data(), n_samples);
+    }
+    if (!domains_file.empty()) {
+      vector<uint64_t> hist, len_sum;
+      uint32_t n_nodes = 0;
+      uint64_t n_samples = 0;
+      mcmc.download_domain_stats(hist, len_sum, n_nodes, n_samples);
+      if (VERBOSE) cerr << "[WRITING DOMAIN SIZE SPECTRA OF " << n_samples << " SAMPLES: " << domains_file << "]" << endl;
+      epv::write_domain_stats(domains_file, th.node_names, n_samples, hist.data(), len_sum.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

@@ -27,6 +27,8 @@ struct epvd_sampler {
   std::vector<uint32_t> staged_origin;   // between epvd_lineage_origins_sizes and epvd_download_lineage_origins
   std::vector<uint64_t> staged_age;
   bool have_staged_origins = false;
+  std::vector<uint64_t> staged_dom_hist, staged_dom_len, staged_dom_edges;   // between epvd_domain_part_sizes and epvd_download_domain_part
+  bool have_staged_domains = false;
 };
 
 namespace {
@@ -319,6 +321,47 @@ EPVD_API int epvd_download_lineage_origin_windows(epvd_sampler *h, uint64_t W, u
     std::copy(o.begin(), o.end(), origin);
     std::copy(a.begin(), a.end(), age);
     if (k) *k = kk;
+    if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_domain_stats(epvd_sampler *h, uint64_t max_samples) {
+  return guarded(h, [&] { h->s->set_domain_stats(max_samples); });
+}
+EPVD_API int epvd_reset_domain_stats(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_domain_stats(); });
+}
+EPVD_API int epvd_accumulate_domain_stats(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_domain_stats(); });
+}
+EPVD_API int epvd_domain_part_sizes(epvd_sampler *h, uint32_t *n_nodes, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    h->s->download_domain_part(h->staged_dom_hist, h->staged_dom_len, h->staged_dom_edges, *n_nodes, *n_samples);
+    h->have_staged_domains = true;
+  });
+}
+EPVD_API int epvd_download_domain_part(epvd_sampler *h, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  return guarded(h, [&] {
+    if (!h->have_staged_domains) throw std::runtime_error("epvd_domain_part_sizes first");
+    std::copy(h->staged_dom_hist.begin(), h->staged_dom_hist.end(), hist);
+    std::copy(h->staged_dom_len.begin(), h->staged_dom_len.end(), len_sum);
+    std::copy(h->staged_dom_edges.begin(), h->staged_dom_edges.end(), edges);
+    h->staged_dom_hist.clear();
+    h->staged_dom_len.clear();
+    h->staged_dom_edges.clear();
+    h->have_staged_domains = false;
+  });
+}
+EPVD_API int epvd_download_domain_stats(epvd_sampler *h, uint32_t n_nodes, uint64_t *hist, uint64_t *len_sum,
+                                        uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> hh, ll;
+    uint32_t N = 0;
+    uint64_t ns = 0;
+    h->s->download_domain_stats(hh, ll, N, ns);
+    if (N != n_nodes) throw std::runtime_error("epvd_download_domain_stats: n_nodes must be the tree's number of nodes");
+    std::copy(hh.begin(), hh.end(), hist);
+    std::copy(ll.begin(), ll.end(), len_sum);
     if (n_samples) *n_samples = ns;
   });
 }

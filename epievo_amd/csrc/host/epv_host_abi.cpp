@@ -11,6 +11,7 @@
 #include "epv_model.hpp"
 #include "epv_sim.hpp"
 #include "epv_io.hpp"
+#include "epv_domains.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
 
@@ -438,3 +439,48 @@ EPVH_API void epvh_lineage_origins_copy(void *h, char *row_leaf, char *row_node,
   std::copy(lo->age.begin(), lo->age.end(), age);
 }
 EPVH_API void epvh_lineage_origins_free(void *h) { delete (epv::LineageOrigins *)h; }
+
+// ---- domain size spectra: bins, merge and close of parts (epv_domains.hpp), the file of epievo_est_histories -d
+EPVH_API uint32_t epvh_domain_bin(uint64_t l) { return epv_domain_bin(l); }
+EPVH_API void epvh_domain_bin_range(uint32_t b, uint64_t *lo, uint64_t *hi) { epv::domain_bin_range(b, lo, hi); }
+// hists, len_sums, edges: n_parts pointers each, parts in genome order ([N][2][128], [N][2], [samples][N][2])
+EPVH_API int epvh_domain_parts_merge(uint64_t n_parts, uint32_t N, uint64_t samples, const uint64_t *const *hists,
+                                     const uint64_t *const *len_sums, const uint64_t *const *edges, uint64_t *out_hist,
+                                     uint64_t *out_len_sum, uint64_t *out_edges) {
+  try {
+    epv::domain_parts_merge(n_parts, N, samples, hists, len_sums, edges, out_hist, out_len_sum, out_edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API int epvh_domain_part_close(uint32_t N, uint64_t samples, uint64_t *hist, uint64_t *len_sum, const uint64_t *edges) {
+  try {
+    epv::domain_part_close(N, samples, hist, len_sum, edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// node_names: every node's name joined by '\n' (the root's first); hist [N][2][128], len_sum [N][2]: the closed result
+EPVH_API int epvh_write_domain_stats(const char *file, const char *node_names, uint64_t n_samples, const uint64_t *hist,
+                                     const uint64_t *len_sum) {
+  try {
+    epv::write_domain_stats(file, split_names(node_names), n_samples, hist, len_sum);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_domain_stats(const char *file) {
+  try {
+    return new epv::DomainStats(epv::read_domain_stats(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+EPVH_API void epvh_domain_stats_dims(void *h, uint64_t *n_samples, uint64_t *n_nodes, uint64_t *names_len) {
+  const epv::DomainStats *ds = (const epv::DomainStats *)h;
+  *n_samples = ds->n_samples;
+  *n_nodes = ds->node_names.size();
+  *names_len = join_names(ds->node_names).size() + 1u;
+}
+EPVH_API void epvh_domain_stats_copy(void *h, char *names, int names_len, uint64_t *hist, uint64_t *len_sum) {
+  const epv::DomainStats *ds = (const epv::DomainStats *)h;
+  put_text(join_names(ds->node_names), names, names_len);
+  std::copy(ds->hist.begin(), ds->hist.end(), hist);
+  std::copy(ds->len_sum.begin(), ds->len_sum.end(), len_sum);
+}
+EPVH_API void epvh_domain_stats_free(void *h) { delete (epv::DomainStats *)h; }

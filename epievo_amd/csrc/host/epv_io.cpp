@@ -1,5 +1,6 @@
 // epv_io.cpp -- see epv_io.hpp
 #include "epv_io.hpp"
+#include "epv_domains.hpp"
 #include "epv_model.hpp"
 
 #include <fcntl.h>
@@ -864,6 +865,95 @@ LineageOrigins read_lineage_origins(const std::string &file) {
     r0 += leaf_rows[l];
   }
   return lo;
+}
+
+void write_domain_stats(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_samples,
+                        const uint64_t *hist, const uint64_t *len_sum) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#samples\t" << n_samples << "\tbins\t" << EPV_DOM_BINS << '\n';
+  for (size_t v = 0; v < node_names.size(); ++v) {
+    out << "NODE:" << node_names[v] << '\n';
+    for (uint64_t st = 0; st < 2u; ++st) {
+      const uint64_t *h = hist + (v * 2u + st) * EPV_DOM_BINS;
+      uint64_t runs = 0;
+      for (uint32_t b = 0; b < EPV_DOM_BINS; ++b) runs += h[b];
+      out << "state\t" << st << "\truns\t" << runs << "\tsites\t" << len_sum[v * 2u + st] << '\n';
+      for (uint32_t b = 0; b < EPV_DOM_BINS; ++b) {
+        if (!h[b]) continue;
+        uint64_t lo = 0, hi = 0;
+        domain_bin_range(b, &lo, &hi);
+        out << lo << "\t" << hi << "\t" << h[b] << '\n';
+      }
+    }
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+DomainStats read_domain_stats(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad domain-statistics file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("domain-statistics file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  DomainStats ds;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 4 || f[0] != "#samples" || f[2] != "bins" || std::stoull(f[3]) != EPV_DOM_BINS)
+    throw bad("bad header: " + line);
+  ds.n_samples = std::stoull(f[1]);
+  int state = -1;
+  uint64_t runs = 0, seen = 0;
+  auto end_state = [&] {
+    if (state >= 0 && seen != runs) throw bad("the bins of a state do not add up to its runs");
+  };
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    if (line.compare(0, 5, "NODE:") == 0) {
+      end_state();
+      if (state == 0 || (state < 0 && !ds.node_names.empty())) throw bad("a node without both states: " + line);
+      ds.node_names.push_back(line.substr(5));
+      ds.hist.resize(ds.node_names.size() * 2u * EPV_DOM_BINS, 0u);
+      ds.len_sum.resize(ds.node_names.size() * 2u, 0u);
+      state = -1;
+      continue;
+    }
+    f = fields(line);
+    if (ds.node_names.empty()) throw bad("a line before the first node: " + line);
+    if (f[0] == "state") {
+      end_state();
+      if (f.size() != 6 || f[2] != "runs" || f[4] != "sites" || std::stoi(f[1]) != state + 1)
+        throw bad("bad state line: " + line);
+      state = std::stoi(f[1]);
+      runs = std::stoull(f[3]);
+      seen = 0;
+      ds.len_sum[(ds.node_names.size() - 1u) * 2u + (size_t)state] = std::stoull(f[5]);
+    } else {
+      if (state < 0 || f.size() != 3) throw bad("bad bin line: " + line);
+      const uint64_t lo = std::stoull(f[0]), hi = std::stoull(f[1]);
+      const uint32_t b = epv_domain_bin(lo);
+      uint64_t blo = 0, bhi = 0;
+      domain_bin_range(b, &blo, &bhi);
+      if (!lo || lo != blo || hi != bhi) throw bad("not the range of a bin: " + line);
+      const uint64_t n = std::stoull(f[2]);
+      ds.hist[((ds.node_names.size() - 1u) * 2u + (size_t)state) * EPV_DOM_BINS + b] += n;
+      seen += n;
+    }
+  }
+  end_state();
+  if (state == 0 || (state < 0 && !ds.node_names.empty())) throw bad("the last node lacks a state");
+  return ds;
 }
 
 }  // namespace epv

@@ -109,6 +109,20 @@ void write_lineage_origins(const std::string &file, const std::vector<std::strin
                            int scale_exp, const uint64_t *origin, const uint64_t *age, uint64_t n_samples);
 LineageOrigins read_lineage_origins(const std::string &file);
 
+// the domain size spectra of epievo_est_histories -d (the closed result of epv_get_domain_stats), integers only:
+//   "#samples\t<S>\tbins\t128", then per node "NODE:<name>", per state a line
+//   "state\t<0|1>\truns\t<count>\tsites\t<len_sum>" and one line "lo\thi\tcount" per nonzero bin (lo .. hi: the run
+//   lengths of the bin).  Readers divide by the samples.  hist: [v][state][bin], len_sum: [v][state] (uint64)
+struct DomainStats {
+  uint64_t n_samples = 0;
+  std::vector<std::string> node_names;
+  std::vector<uint64_t> hist;      // [v][2][128]
+  std::vector<uint64_t> len_sum;   // [v][2]
+};
+void write_domain_stats(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_samples,
+                        const uint64_t *hist, const uint64_t *len_sum);
+DomainStats read_domain_stats(const std::string &file);
+
 // the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
 // then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The
 // device keeps one length per branch, so paths whose tot_time differs from the tree's branch length

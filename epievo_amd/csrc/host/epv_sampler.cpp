@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "epievo_mi355x.h"
+#include "epv_domains.hpp"
 #include "epievo_mi355x_comm.h"
 
 namespace epv {
@@ -365,6 +366,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
   if (origins_) set_lineage_origins(true);
+  if (domains_max_) set_domain_stats(domains_max_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -375,6 +377,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
   if (origins_) set_lineage_origins(true);
+  if (domains_max_) set_domain_stats(domains_max_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -620,6 +623,64 @@ void SingleSiteSampler::download_lineage_origin_windows(uint64_t W, std::vector<
   }
   origin.assign(sums.begin(), sums.begin() + (uint64_t)R * nw);
   age.assign(sums.begin() + (uint64_t)R * nw, sums.end());
+}
+
+void SingleSiteSampler::set_domain_stats(uint64_t max_samples) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !max_samples)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_domain_stats(c, max_samples), "epv_set_domain_stats");
+  domains_max_ = max_samples;
+}
+
+void SingleSiteSampler::reset_domain_stats() {
+  if (!domains_max_) throw std::runtime_error("domain statistics are off: set_domain_stats first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_domain_stats(c), "epv_reset_domain_stats");
+}
+
+void SingleSiteSampler::accumulate_domain_stats() {
+  if (!domains_max_) throw std::runtime_error("domain statistics are off: set_domain_stats first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_domain_stats(c), "epv_accumulate_domain_stats");
+}
+
+void SingleSiteSampler::download_domain_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                             std::vector<uint64_t> &edges, uint32_t &n_nodes, uint64_t &n_samples) {
+  if (!domains_max_) throw std::runtime_error("domain statistics are off: set_domain_stats first");
+  const std::vector<epv_ctx *> cs = contexts();   // in genome order
+  std::vector<std::vector<uint64_t>> h(cs.size()), l(cs.size()), e(cs.size());
+  std::vector<const uint64_t *> hp(cs.size()), lp(cs.size()), ep(cs.size());
+  n_nodes = 0;
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t N = 0, bins = 0;
+    uint64_t first = 0, count = 0, chunk = 0, ns = 0;
+    check_on(cs[i], epv_domain_stats_layout(cs[i], &N, &bins, &first, &count, &chunk), "epv_domain_stats_layout");
+    check_on(cs[i], epv_domain_stats_samples(cs[i], &ns), "epv_domain_stats_samples");
+    if (i == 0) { n_nodes = N; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of domain-statistics samples");
+    else if (N != n_nodes) throw std::runtime_error("the contexts hold domain statistics of different trees");
+    h[i].assign((size_t)N * 2u * EPV_DOM_BINS, 0u);
+    l[i].assign((size_t)N * 2u, 0u);
+    e[i].assign(std::max<size_t>((size_t)ns * N * 2u, 1u), 0u);
+    check_on(cs[i], epv_get_domain_stats(cs[i], h[i].data(), l[i].data(), e[i].data()), "epv_get_domain_stats");
+    hp[i] = h[i].data(); lp[i] = l[i].data(); ep[i] = e[i].data();
+  }
+  hist.assign((size_t)n_nodes * 2u * EPV_DOM_BINS, 0u);
+  len_sum.assign((size_t)n_nodes * 2u, 0u);
+  edges.assign((size_t)n_samples * n_nodes * 2u, 0u);
+  std::vector<uint64_t> none(1, 0u);
+  domain_parts_merge(cs.size(), n_nodes, n_samples, hp.data(), lp.data(), ep.data(), hist.data(), len_sum.data(),
+                     edges.empty() ? none.data() : edges.data());
+}
+
+void SingleSiteSampler::download_domain_stats(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                              uint32_t &n_nodes, uint64_t &n_samples) {
+  if (rank_mode_)
+    throw std::runtime_error("download_domain_stats: this process holds one slot's stretch of the genome, not the genome: "
+                             "merge the processes' download_domain_part in genome order (epv::domain_parts_merge, "
+                             "epvh_domain_parts_merge), then close the merged part");
+  std::vector<uint64_t> edges;
+  download_domain_part(hist, len_sum, edges, n_nodes, n_samples);
+  domain_part_close(n_nodes, n_samples, hist.data(), len_sum.data(), edges.data());
 }
 
 void SingleSiteSampler::set_unobserved(std::vector<uint8_t> whole_genome) {

@@ -146,6 +146,19 @@ public:
   void download_lineage_origins(std::vector<uint32_t> &origin, std::vector<uint64_t> &age, int &k, uint64_t &n_samples);
   void download_lineage_origin_windows(uint64_t W, std::vector<uint64_t> &origin, std::vector<uint64_t> &age, int &k,
                                        uint64_t &n_samples);
+  // domain size spectra (epv_set_domain_stats) on every context, with the branch events' samples and lifecycle;
+  // max_samples = 0 is off.  download_domain_part: the parts of all slots and contexts of this process merged in
+  // genome order (epv::domain_parts_merge), unclosed: hist [N][2][128], len_sum [N][2], edges [samples][N][2].
+  // download_domain_stats: that part closed (epv::domain_part_close).  One slot per process: it throws, because
+  // one process's stretch is not the genome; merge the processes' download_domain_part, then close
+  void set_domain_stats(uint64_t max_samples);
+  uint64_t domain_stats_max() const { return domains_max_; }
+  void reset_domain_stats();
+  void accumulate_domain_stats();
+  void download_domain_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, std::vector<uint64_t> &edges,
+                            uint32_t &n_nodes, uint64_t &n_samples);
+  void download_domain_stats(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_nodes,
+                             uint64_t &n_samples);
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
@@ -241,6 +254,7 @@ private:
   bool bevents_ = false;      // set_branch_events
   uint64_t wstat_W_ = 0;      // set_window_stats
   bool origins_ = false;      // set_lineage_origins
+  uint64_t domains_max_ = 0; // set_domain_stats
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

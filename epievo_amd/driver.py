@@ -21,7 +21,9 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats",
                   "epvd_set_lineage_origins", "epvd_reset_lineage_origins", "epvd_accumulate_lineage_origins",
                   "epvd_lineage_origin_rows", "epvd_lineage_origins_scale_exp", "epvd_lineage_origins_sizes", "epvd_download_lineage_origins",
-                  "epvd_download_lineage_origin_windows"]
+                  "epvd_download_lineage_origin_windows",
+                  "epvd_set_domain_stats", "epvd_reset_domain_stats", "epvd_accumulate_domain_stats",
+                  "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats"]
 
 
 def lib():
@@ -71,6 +73,12 @@ def lib():
         L.epvd_lineage_origins_sizes.argtypes = [vp, u64p, u64p, ip, u64p]
         L.epvd_download_lineage_origins.argtypes = [vp, u32p, u64p]
         L.epvd_download_lineage_origin_windows.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, u64p, ip, u64p]
+        L.epvd_set_domain_stats.argtypes = [vp, C.c_uint64]
+        L.epvd_reset_domain_stats.argtypes = [vp]
+        L.epvd_accumulate_domain_stats.argtypes = [vp]
+        L.epvd_domain_part_sizes.argtypes = [vp, u32p, u64p]
+        L.epvd_download_domain_part.argtypes = [vp, u64p, u64p, u64p]
+        L.epvd_download_domain_stats.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -325,3 +333,33 @@ class CppSampler:
         self._ck(self.L.epvd_download_lineage_origin_windows(self.h, W, nw, _p(o, C.c_uint64), _p(a, C.c_uint64), None,
                                                              C.byref(ns)))
         return int(ns.value), o, a
+
+    def enable_domain_stats(self, max_samples):
+        """domain size spectra on every context, for at most max_samples samples (0 = off); kept across reset()"""
+        self._ck(self.L.epvd_set_domain_stats(self.h, int(max_samples)))
+
+    def reset_domain_stats(self):
+        self._ck(self.L.epvd_reset_domain_stats(self.h))
+
+    def accumulate_domain_stats(self):
+        self._ck(self.L.epvd_accumulate_domain_stats(self.h))
+
+    def domain_stats_part(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2], edges [samples, N, 2]), uint64: the parts of the slots and
+        contexts of this process merged in genome order, unclosed"""
+        N, ns = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_domain_part_sizes(self.h, C.byref(N), C.byref(ns)))
+        N, ns = int(N.value), int(ns.value)
+        hist, len_sum = np.zeros((max(N, 1), 2, 128), np.uint64), np.zeros((max(N, 1), 2), np.uint64)
+        edges = np.zeros((max(ns, 1), max(N, 1), 2), np.uint64)
+        self._ck(self.L.epvd_download_domain_part(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64),
+                                                  _p(edges.reshape(-1)[:max(ns * N * 2, 1)], C.c_uint64)))
+        return ns, hist[:N], len_sum[:N], edges.reshape(-1)[:ns * N * 2].reshape(ns, N, 2)
+
+    def domain_stats(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2]): the closed result over the genome (one slot per process:
+        an error; merge the processes' domain_stats_part with host.domain_parts_merge, then host.domain_part_close)"""
+        N = self.B + 1
+        hist, len_sum, ns = np.zeros((N, 2, 128), np.uint64), np.zeros((N, 2), np.uint64), C.c_uint64(0)
+        self._ck(self.L.epvd_download_domain_stats(self.h, N, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
+        return int(ns.value), hist, len_sum

@@ -66,6 +66,22 @@ def lib():
         L.epvh_lineage_origins_copy.restype = None
         L.epvh_lineage_origins_free.argtypes = [C.c_void_p]
         L.epvh_lineage_origins_free.restype = None
+        u64pp = C.POINTER(u64p)
+        L.epvh_domain_bin.argtypes = [C.c_uint64]
+        L.epvh_domain_bin.restype = C.c_uint32
+        L.epvh_domain_bin_range.argtypes = [C.c_uint32, u64p, u64p]
+        L.epvh_domain_bin_range.restype = None
+        L.epvh_domain_parts_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u64pp, u64pp, u64pp, u64p, u64p, u64p]
+        L.epvh_domain_part_close.argtypes = [C.c_uint32, C.c_uint64, u64p, u64p, u64p]
+        L.epvh_write_domain_stats.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, u64p, u64p]
+        L.epvh_read_domain_stats.argtypes = [C.c_char_p]
+        L.epvh_read_domain_stats.restype = C.c_void_p
+        L.epvh_domain_stats_dims.argtypes = [C.c_void_p, u64p, u64p, u64p]
+        L.epvh_domain_stats_dims.restype = None
+        L.epvh_domain_stats_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, u64p, u64p]
+        L.epvh_domain_stats_copy.restype = None
+        L.epvh_domain_stats_free.argtypes = [C.c_void_p]
+        L.epvh_domain_stats_free.restype = None
         _lib = L
     return _lib
 
@@ -348,3 +364,103 @@ def read_lineage_origins(path):
                     row_node=b2.value.decode().split("\n") if R else [], origin=origin, age=age)
     finally:
         L.epvh_lineage_origins_free(h)
+
+
+# ---- domain size spectra (run lengths of every node's state along the genome)
+DOMAIN_BINS = 128
+
+
+def domain_bin(length):
+    """the bin of a run of `length` sites: the length itself below 16, then four bins per octave"""
+    return int(lib().epvh_domain_bin(int(length)))
+
+
+def domain_bin_range(b):
+    """(lo, hi): the run lengths bin b holds, both included; (0, 0) for bin 0, which is never used"""
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    lib().epvh_domain_bin_range(int(b), C.byref(lo), C.byref(hi))
+    return int(lo.value), int(hi.value)
+
+
+def domain_bin_edges():
+    """uint64 [128, 2]: per bin the smallest and the largest run length it holds"""
+    return np.array([domain_bin_range(b) for b in range(DOMAIN_BINS)], np.uint64)
+
+
+def _ptrs(arrays):
+    return (C.POINTER(C.c_uint64) * len(arrays))(*[_p(a, C.c_uint64) for a in arrays])
+
+
+def domain_parts_merge(parts):
+    """parts: [(hist [N, 2, 128], len_sum [N, 2], edges [samples, N, 2])] of adjacent stretches of sites in genome
+    order, of the same samples -> the part of their union (uint64 arrays of the same shapes)"""
+    if not parts:
+        raise ValueError("no parts")
+    hists = [np.ascontiguousarray(p[0], np.uint64) for p in parts]
+    sums = [np.ascontiguousarray(p[1], np.uint64) for p in parts]
+    edges = [np.ascontiguousarray(p[2], np.uint64) for p in parts]
+    N, ns = hists[0].shape[0], edges[0].shape[0]
+    for h, l, e in zip(hists, sums, edges):
+        if h.shape != (N, 2, DOMAIN_BINS) or l.shape != (N, 2) or e.shape != (ns, N, 2):
+            raise ValueError("a part is hist [N, 2, 128], len_sum [N, 2], edges [samples, N, 2] of the same N and samples")
+    hist, len_sum = np.zeros((N, 2, DOMAIN_BINS), np.uint64), np.zeros((N, 2), np.uint64)
+    out = np.zeros((ns, N, 2), np.uint64)
+    o = out if out.size else np.zeros(1, np.uint64)
+    if lib().epvh_domain_parts_merge(len(parts), N, ns, _ptrs(hists), _ptrs(sums),
+                                     _ptrs([e if e.size else np.zeros(1, np.uint64) for e in edges]),
+                                     _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(o, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum, out
+
+
+def domain_part_close(hist, len_sum, edges):
+    """a part -> the result (hist [N, 2, 128], len_sum [N, 2]): its first and last records are binned and added, a
+    whole record once.  The runs at the two ends count with the length the stretch leaves them"""
+    hist, len_sum = np.array(hist, np.uint64), np.array(len_sum, np.uint64)
+    edges = np.ascontiguousarray(edges, np.uint64)
+    N, ns = hist.shape[0], edges.shape[0]
+    if hist.shape != (N, 2, DOMAIN_BINS) or len_sum.shape != (N, 2) or edges.shape != (ns, N, 2):
+        raise ValueError("a part is hist [N, 2, 128], len_sum [N, 2], edges [samples, N, 2]")
+    e = edges if edges.size else np.zeros(1, np.uint64)
+    if lib().epvh_domain_part_close(N, ns, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(e, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum
+
+
+def domain_summary(samples, hist, len_sum):
+    """-> (runs per sample [N, 2], mean run length [N, 2]) per node and state of a closed result; nan where a state
+    has no run"""
+    runs = np.asarray(hist, np.uint64).sum(axis=2, dtype=np.uint64).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return runs / float(samples), np.asarray(len_sum, np.uint64).astype(np.float64) / runs
+
+
+def write_domain_stats(path, node_names, samples, hist, len_sum):
+    """the file of epievo_est_histories -d: the closed result, integers only"""
+    hist, len_sum = np.ascontiguousarray(hist, np.uint64), np.ascontiguousarray(len_sum, np.uint64)
+    N = len(node_names)
+    if hist.shape != (N, 2, DOMAIN_BINS) or len_sum.shape != (N, 2):
+        raise ValueError("hist is [nodes, 2, 128], len_sum [nodes, 2]")
+    if lib().epvh_write_domain_stats(path.encode(), "\n".join(node_names).encode(), int(samples), _p(hist, C.c_uint64),
+                                     _p(len_sum, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_domain_stats(path):
+    """-> dict(samples, node_names, hist uint64 [N, 2, 128], len_sum uint64 [N, 2])"""
+    L = lib()
+    h = L.epvh_read_domain_stats(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, N, ln = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.epvh_domain_stats_dims(h, C.byref(ns), C.byref(N), C.byref(ln))
+        N = int(N.value)
+        buf = C.create_string_buffer(int(ln.value))
+        hist, len_sum = np.zeros((N, 2, DOMAIN_BINS), np.uint64), np.zeros((N, 2), np.uint64)
+        a, b = (hist, len_sum) if N else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+        L.epvh_domain_stats_copy(h, buf, len(buf), _p(a, C.c_uint64), _p(b, C.c_uint64))
+        return dict(samples=int(ns.value), node_names=buf.value.decode().split("\n") if N else [], hist=hist,
+                    len_sum=len_sum)
+    finally:
+        L.epvh_domain_stats_free(h)

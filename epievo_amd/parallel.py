@@ -29,6 +29,7 @@ module is new capability, not a translation.
 """
 import numpy as np
 
+from . import host
 from .host import FlatPaths
 
 BLOCK = 256      # sites per block: halo widths and shard_cuts' cut points are whole blocks
@@ -485,6 +486,45 @@ class ShardedSampler:
             ow, aw = tot[:R], tot[R:]
         return ns, ow, aw
 
+    # ---- domain size spectra: every rank counts the part of its owned columns
+    def enable_domain_stats(self, max_samples):
+        self.dev.enable_domain_stats(max_samples)
+
+    def reset_domain_stats(self):
+        self.dev.reset_domain_stats()
+
+    def accumulate_domain_stats(self):
+        self.dev.accumulate_domain_stats()
+
+    def domain_stats_samples(self):
+        return self.dev.domain_stats_samples()
+
+    def domain_stats_layout(self):
+        """(nodes N, bins, first local site, sites, sites per block of the runs kernel) of this rank's engine"""
+        return self.dev.domain_stats_layout()
+
+    def domain_stats_part(self):
+        """-> (samples, hist, len_sum, edges): the part of the whole genome, identical on every rank: the sample
+        counts are compared first (a part's size depends on them), then the ranks' parts are all-gathered and
+        merged in genome order"""
+        ns, hist, len_sum, edges = self.dev.domain_stats_part()
+        if self.comm.world > 1:
+            N = hist.shape[0]
+            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
+            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
+                raise RuntimeError("the ranks hold different numbers of domain-statistics samples")
+            mine = np.concatenate([hist.reshape(-1), len_sum.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
+            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
+            nh, nl = hist.size, len_sum.size
+            hist, len_sum, edges = host.domain_parts_merge(
+                [(w[:nh].reshape(N, 2, -1), w[nh:nh + nl].reshape(N, 2), w[nh + nl:].reshape(ns, N, 2)) for w in allw])
+        return ns, hist, len_sum, edges
+
+    def domain_stats(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2]) of the whole genome, closed; every rank merges and closes"""
+        ns, hist, len_sum, edges = self.domain_stats_part()
+        return (ns,) + host.domain_part_close(hist, len_sum, edges)
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -867,6 +907,40 @@ class LocalGroup:
             n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
         parts = self._each(lambda j, s: s.lineage_origin_windows(W, first_window, n_windows))
         return self._same_origin_samples(parts), add_uint64([p[1] for p in parts]), add_uint64([p[2] for p in parts])
+
+    # ---- domain size spectra: every shard counts the part of the sites it owns
+    def enable_domain_stats(self, max_samples):
+        self._each(lambda j, s: s.enable_domain_stats(max_samples))
+
+    def reset_domain_stats(self):
+        self._each(lambda j, s: s.reset_domain_stats())
+
+    def accumulate_domain_stats(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a domain-statistics sample")
+        self._each(lambda j, s: s.accumulate_domain_stats())
+
+    def domain_stats_samples(self):
+        return self.subs[0].domain_stats_samples()
+
+    def domain_stats_layout(self):
+        """(nodes N, bins, first local site of the first shard, sites over all shards, sites per block)"""
+        lay = self._each(lambda j, s: s.domain_stats_layout())
+        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+
+    def domain_stats_part(self):
+        """-> (samples, hist, len_sum, edges): the shards' parts merged in genome order, unclosed"""
+        parts = self._each(lambda j, s: s.domain_stats_part())
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of domain-statistics samples")
+        return (ns,) + host.domain_parts_merge([p[1:] for p in parts])
+
+    def domain_stats(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2]) over the group's owned sites, closed"""
+        ns, hist, len_sum, edges = self.domain_stats_part()
+        return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
     def counters(self):
         out = {}

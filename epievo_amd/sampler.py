@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _build
+from . import host
 from .host import FlatPaths
 
 _lib = None
@@ -59,6 +60,8 @@ ABI_SYMBOLS = [
     "epv_lineage_origins_samples", "epv_lineage_origins_set_samples", "epv_lineage_origins_layout",
     "epv_lineage_origin_rows", "epv_lineage_origins_scale_exp", "epv_get_lineage_origins",
     "epv_get_lineage_origin_windows",
+    "epv_set_domain_stats", "epv_reset_domain_stats", "epv_accumulate_domain_stats", "epv_domain_stats_samples",
+    "epv_domain_stats_layout", "epv_get_domain_stats",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
@@ -170,6 +173,12 @@ def lib():
         L.epv_lineage_origins_scale_exp.argtypes = [vp, C.POINTER(C.c_int)]
         L.epv_get_lineage_origins.argtypes = [vp, C.c_uint64, C.c_uint64, u32p, u64p]
         L.epv_get_lineage_origin_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        L.epv_set_domain_stats.argtypes = [vp, C.c_uint64]
+        L.epv_reset_domain_stats.argtypes = [vp]
+        L.epv_accumulate_domain_stats.argtypes = [vp]
+        L.epv_domain_stats_samples.argtypes = [vp, u64p]
+        L.epv_domain_stats_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
+        L.epv_get_domain_stats.argtypes = [vp, u64p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -754,6 +763,48 @@ class DeviceSampler:
         return self.lineage_origins_samples(), out[:R], out[R:]
 
 
+    # ---- domain size spectra (epv_set_domain_stats)
+    def enable_domain_stats(self, max_samples):
+        """count the run lengths of every node's state along the genome after every batch sweep of run_mcmc, for
+        at most max_samples samples (0 = off)"""
+        self._ck(self.L.epv_set_domain_stats(self.h, int(max_samples)))
+
+    def reset_domain_stats(self):
+        self._ck(self.L.epv_reset_domain_stats(self.h))
+
+    def accumulate_domain_stats(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_domain_stats(self.h))
+
+    def domain_stats_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_domain_stats_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def domain_stats_layout(self):
+        """(nodes N, bins, first local site, number of sites, sites per block of the runs kernel); zeros when off"""
+        nn, nb, a, k, cs = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_domain_stats_layout(self.h, C.byref(nn), C.byref(nb), C.byref(a), C.byref(k), C.byref(cs)))
+        return int(nn.value), int(nb.value), int(a.value), int(k.value), int(cs.value)
+
+    def domain_stats_part(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2], edges [samples, N, 2]), uint64: what this context's
+        stretch of sites contributes, unclosed (host.domain_parts_merge, host.domain_part_close)"""
+        ns = self.domain_stats_samples()
+        N, nb = self.domain_stats_layout()[:2]
+        hist, len_sum = np.zeros((max(N, 1), 2, max(nb, 1)), np.uint64), np.zeros((max(N, 1), 2), np.uint64)
+        edges = np.zeros((max(ns, 1), max(N, 1), 2), np.uint64)
+        self._ck(self.L.epv_get_domain_stats(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(edges, C.c_uint64)))
+        return ns, hist[:N], len_sum[:N], edges[:ns, :N]
+
+    def domain_stats(self):
+        """-> (samples, hist [N, 2, 128], len_sum [N, 2]): the closed result over this context's sites.  hist /
+        samples is the posterior spectrum of run lengths per node and state; the runs at the two ends count with
+        the length the stretch leaves them"""
+        ns, hist, len_sum, edges = self.domain_stats_part()
+        return (ns,) + host.domain_part_close(hist, len_sum, edges)
+
+
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
 
@@ -904,3 +955,25 @@ class SingleSiteSampler:
 
     def lineage_origin_windows(self, W, first_window=0, n_windows=None):
         return self.dev.lineage_origin_windows(W, first_window, n_windows)
+
+    # domain size spectra (DeviceSampler.enable_domain_stats)
+    def enable_domain_stats(self, max_samples):
+        self.dev.enable_domain_stats(max_samples)
+
+    def reset_domain_stats(self):
+        self.dev.reset_domain_stats()
+
+    def accumulate_domain_stats(self):
+        self.dev.accumulate_domain_stats()
+
+    def domain_stats_samples(self):
+        return self.dev.domain_stats_samples()
+
+    def domain_stats_layout(self):
+        return self.dev.domain_stats_layout()
+
+    def domain_stats_part(self):
+        return self.dev.domain_stats_part()
+
+    def domain_stats(self):
+        return self.dev.domain_stats()

@@ -545,6 +545,47 @@ int epv_get_lineage_origins(epv_ctx *ctx, uint64_t first, uint64_t count, uint32
 int epv_get_lineage_origin_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                    uint64_t *out);
 
+/* ---- domain size spectra (new): the posterior spectrum of run lengths of every node's state along the
+ * genome, for all N nodes (root and leaves included) and both states.  The first accumulator that is joint
+ * along the genome: no per-site posterior can give it.  Counted as exact integers after every batch sweep; the
+ * result depends on no kernel path, context, shard or GPU.
+ * Node states of one sample: x_v[s] = a XOR (k & 1) for v >= 1 (a = init state, k = jumps of branch v at site s;
+ * the branch events' e), x_0[s] = the init state of the branch of the root's lowest-numbered child.  No jump
+ * time is read.
+ * Runs over a stretch of sites [lo, lo + cnt): an END is a position p with p + 1 < cnt and x[p] != x[p + 1]; the
+ * run that ends at p has length p - p' (p' = the previous end) and state x[p].
+ * Bins: EPV_DOM_BINS = 128.  bin(l) = l for l < 16; otherwise, e = floor(log2 l), bin(l) = 16 + 4 (e - 4) +
+ * ((l >> (e - 2)) & 3): exact up to 15, then four bins per octave; l < 2^32, the last bin is 127, bin 0 is never
+ * used.  Bin b >= 16 holds lo = (4 + q) << (e - 2) .. lo + (1 << (e - 2)) - 1, e = 4 + (b - 16) / 4, q = (b - 16) % 4.
+ * A context keeps a PART, what its stretch of counted sites contributes:
+ *   hist[N][2][128] uint64   runs that end at an end and start after an earlier end, summed over the samples
+ *   len_sum[N][2]   uint64   their lengths
+ *   edge[sample][N][2] uint64  the two runs the stretch cannot close: [0] from its first site to its first end,
+ *     [1] from its last end to its last site; bits 0-61 the length, bit 63 the state, bit 62 WHOLE (no end at
+ *     all: both records equal, the length is cnt).  A stretch of no sites has both records 0.
+ * Adjacent parts merge, in genome order, to the part of their union, and a part is closed to the result by
+ * binning its first and last records (a whole record once): epvh_domain_parts_merge and epvh_domain_part_close
+ * (libepv_host.so).  The runs at the genome's two ends count with the length the genome leaves them.
+ * Samples, sites and lifecycle are the branch events': a sample after each batch sweep of epv_run_mcmc /
+ * _sums / _counts or one epv_accumulate_domain_stats call; kept over epv_reset, epv_set_model, capacity growth,
+ * epv_scale_jump_times, masks, evidence and epv_sweep_phase; a changed site range or tree lays the part out
+ * again before the first sample and is EPV_ERR_STATE after it.  Off by default: nothing allocated, nothing
+ * launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_domain_stats: max_samples >= 1 (at most 2^21) allocates hist, len_sum, 8 N ceil(cnt / 64) bytes of
+ *   scratch and 16 N max_samples bytes of edge records (checked against the free device memory first) and zeroes
+ *   them; 0 frees everything.  A sample beyond max_samples is EPV_ERR_STATE, and so is a run whose batch would
+ *   pass it, refused before its first sweep.
+ * epv_domain_stats_layout: nodes N, bins, the local sites first .. first+count-1 and the sites one block of the
+ *   runs kernel covers (zeros when off).
+ * epv_get_domain_stats: the context's part, unclosed; edges holds [samples][N][2]. */
+int epv_set_domain_stats(epv_ctx *ctx, uint64_t max_samples);
+int epv_reset_domain_stats(epv_ctx *ctx);
+int epv_accumulate_domain_stats(epv_ctx *ctx);
+int epv_domain_stats_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_domain_stats_layout(epv_ctx *ctx, uint32_t *n_nodes, uint32_t *n_bins, uint64_t *first, uint64_t *count,
+                            uint64_t *chunk_sites);
+int epv_get_domain_stats(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

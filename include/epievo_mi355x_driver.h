@@ -111,6 +111,20 @@ int epvd_download_lineage_origins(epvd_sampler *s, uint32_t *origin, uint64_t *a
 int epvd_download_lineage_origin_windows(epvd_sampler *s, uint64_t W, uint64_t n_windows, uint64_t *origin,
                                          uint64_t *age, int *k, uint64_t *n_samples);
 
+/* domain size spectra (epv_set_domain_stats on every context; max_samples = 0 is off; kept across epvd_reset,
+ * which starts them from zero).  The part of this process: the parts of its slots and contexts merged in genome
+ * order, unclosed -- sizes first (nodes N and samples S), then the copy of hist[N][2][128], len_sum[N][2] and
+ * edges[S][N][2].  epvd_download_domain_stats: that part closed, into hist[n_nodes][2][128] and
+ * len_sum[n_nodes][2] (n_nodes = the tree's); one slot per process: an error that names the part and the merge
+ * function, because one process's stretch is not the genome */
+int epvd_set_domain_stats(epvd_sampler *s, uint64_t max_samples);
+int epvd_reset_domain_stats(epvd_sampler *s);
+int epvd_accumulate_domain_stats(epvd_sampler *s);
+int epvd_domain_part_sizes(epvd_sampler *s, uint32_t *n_nodes, uint64_t *n_samples);
+int epvd_download_domain_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+int epvd_download_domain_stats(epvd_sampler *s, uint32_t n_nodes, uint64_t *hist, uint64_t *len_sum,
+                               uint64_t *n_samples);
+
 #ifdef __cplusplus
 }
 #endif
