@@ -15,31 +15,6 @@
 //     registers (a later jump of a path -- rare -- is fetched inside the merge as before).
 // Two round trips per G branches instead of two per branch.
 
-template <class ACC>
-__device__ __forceinline__ void merge3_pre(const PathRef &L, const PathRef &M, const PathRef &R, double tl, double tm,
-                                           double tr, uint64_t n, double tot_time, ACC &A) {
-  // merge3 (Path.cpp:206-301) with the first jump of each path already loaded
-  int ctx = (int)(4u * L.init + 2u * M.init + R.init);
-  double prev = 0.0;
-  uint32_t i = 0, j = 0, k = 0;
-  while (i < L.nj || j < M.nj || k < R.nj) {
-    if (tl < (tm < tr ? tm : tr)) {
-      acc_add(A, ctx, tl - prev, false);
-      prev = tl; ctx ^= 4; ++i;
-      tl = i < L.nj ? L.j[(uint64_t)i * n] : EPV_INF;
-    } else if (tm < tr) {
-      acc_add(A, ctx, tm - prev, true);
-      prev = tm; ctx ^= 2; ++j;
-      tm = j < M.nj ? M.j[(uint64_t)j * n] : EPV_INF;
-    } else {
-      acc_add(A, ctx, tr - prev, false);
-      prev = tr; ctx ^= 1; ++k;
-      tr = k < R.nj ? R.j[(uint64_t)k * n] : EPV_INF;
-    }
-  }
-  acc_add(A, ctx, tot_time - prev, false);
-}
-
 #ifndef EPV_ACC3_GROUP
 #define EPV_ACC3_GROUP 4   /* branches per batch of loads (5 or 6: more registers than 4 waves per SIMD have, no faster) */
 #endif

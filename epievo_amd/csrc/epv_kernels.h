@@ -191,6 +191,33 @@ __device__ __forceinline__ void merge3(const PathRef &L, const PathRef &M, const
   acc_add(A, ctx, tot_time - prev, false);
 }
 
+// merge3 with the first jump of each path already loaded (+inf for a path without jumps): the caller
+// has issued those loads in one batch, for several branches at once; a later jump of a path is fetched
+// inside the merge as before
+template <class ACC>
+__device__ __forceinline__ void merge3_pre(const PathRef &L, const PathRef &M, const PathRef &R, double tl, double tm,
+                                           double tr, uint64_t n, double tot_time, ACC &A) {
+  int ctx = (int)(4u * L.init + 2u * M.init + R.init);
+  double prev = 0.0;
+  uint32_t i = 0, j = 0, k = 0;
+  while (i < L.nj || j < M.nj || k < R.nj) {
+    if (tl < (tm < tr ? tm : tr)) {
+      acc_add(A, ctx, tl - prev, false);
+      prev = tl; ctx ^= 4; ++i;
+      tl = i < L.nj ? L.j[(uint64_t)i * n] : EPV_INF;
+    } else if (tm < tr) {
+      acc_add(A, ctx, tm - prev, true);
+      prev = tm; ctx ^= 2; ++j;
+      tm = j < M.nj ? M.j[(uint64_t)j * n] : EPV_INF;
+    } else {
+      acc_add(A, ctx, tr - prev, false);
+      prev = tr; ctx ^= 1; ++k;
+      tr = k < R.nj ? R.j[(uint64_t)k * n] : EPV_INF;
+    }
+  }
+  acc_add(A, ctx, tot_time - prev, false);
+}
+
 // path_log_likelihood (SingleSiteSampler.cpp:374-391): un-logged root prior (reference
 // quirk) + sum_c J_c log(rate_c) - D_c rate_c over all branches of one triple.
 // (bl,sl),(bm,sm),(br,sr) = (buffer, site) of the left / middle / right column.
@@ -229,6 +256,37 @@ __device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const doubl
   acc_clear(A);
   uint32_t rl = 0, rm = 0, rr = 0;
   const uint32_t B = NB ? (uint32_t)NB : S.B;
+  if constexpr (NB > 0) {
+    // the counts of all 3 NB columns are in LDS and their addresses known: the first jump of every
+    // column that has one leaves in ONE batch of predicated loads, and the merges start from loaded
+    // values -- one round trip for the triple instead of one per branch (a wave of task lanes nearly
+    // always has a jump somewhere on every branch)
+    const uint64_t n = S.n, Cn = (uint64_t)S.C * n;
+    const double *jl = S.jumps + ((bl ? (uint64_t)B * Cn : 0ull) + sl);
+    const double *jm = S.jumps + ((bm ? (uint64_t)B * Cn : 0ull) + sm);
+    const double *jr = S.jumps + ((br ? (uint64_t)B * Cn : 0ull) + sr);
+    uint32_t wl[NB], wm[NB], wr[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      wl[b] = mc[(cl * B + b) * stride]; wm[b] = mc[(cm * B + b) * stride]; wr[b] = mc[(cr * B + b) * stride];
+    }
+    double tl[NB], tm[NB], tr[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      tl[b] = (wl[b] & EPV_NJ_MASK) ? jl[(uint64_t)b * Cn] : EPV_INF;
+      tm[b] = (wm[b] & EPV_NJ_MASK) ? jm[(uint64_t)b * Cn] : EPV_INF;
+      tr[b] = (wr[b] & EPV_NJ_MASK) ? jr[(uint64_t)b * Cn] : EPV_INF;
+    }
+    rl = wl[0] >> EPV_INIT_SHIFT; rm = wm[0] >> EPV_INIT_SHIFT; rr = wr[0] >> EPV_INIT_SHIFT;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      PathRef L, M, R;
+      L.j = jl + (uint64_t)b * Cn; L.nj = wl[b] & EPV_NJ_MASK; L.init = wl[b] >> EPV_INIT_SHIFT;
+      M.j = jm + (uint64_t)b * Cn; M.nj = wm[b] & EPV_NJ_MASK; M.init = wm[b] >> EPV_INIT_SHIFT;
+      R.j = jr + (uint64_t)b * Cn; R.nj = wr[b] & EPV_NJ_MASK; R.init = wr[b] >> EPV_INIT_SHIFT;
+      merge3_pre(L, M, R, tl[b], tm[b], tr[b], n, s_blen[b + 1], A);
+    }
+  } else
   for (uint32_t b = 0; b < B; ++b) {
     const uint32_t ml = mc[(cl * B + b) * stride], mm = mc[(cm * B + b) * stride], mr = mc[(cr * B + b) * stride];
     PathRef L, M, R;
