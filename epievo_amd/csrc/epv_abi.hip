@@ -1834,6 +1834,65 @@ EPV_API int epv_philox_kat(epv_ctx *c, uint64_t seed, uint32_t n, const uint32_t
   return EPV_OK;
 }
 
+// known-answer entry for the arithmetic under the MCMC kernels: one item = 4 doubles in, 6 out, evaluated
+// by the project's own functions -- in a kernel of its own (one lane per item) and in this library's host
+// pass of the same headers.  Ops 1 and 6 involve nojump_bound, which exists on the device only.
+#define EPV_KAT_OPS 7u
+EPV_DEV bool epv_math_kat_item(uint32_t op, const double *in, double *out) {
+  double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool ok = true;
+  switch (op) {
+    case 0u: o[0] = epv_exp(in[0]); o[1] = epv_log(in[0]); break;
+    case 2u: epv_seg_matrices(in[0], in[1], in[2], o); break;
+    case 3u: { const double u = in[0], r = in[1]; o[0] = -epv_log(1.0 - u) / r; break; }
+    case 4u: { const double u0 = in[0], trunc = in[1], r = in[2]; o[0] = -epv_log(1.0 - u0 * trunc) / r; break; }
+    case 5u: o[0] = epv_u2d(epv_stat_fix(in[0], in[1])); break;
+#if defined(__HIP_DEVICE_COMPILE__)
+    case 1u: o[0] = nojump_bound(in[0]); break;
+    case 6u: {
+      const double u = in[0], T = in[1], r = in[2];
+      o[0] = (1.0 - u < nojump_bound(T * r)) ? 1.0 : 0.0;
+      o[1] = !(-epv_log(1.0 - u) / r < T) ? 1.0 : 0.0;
+      break;
+    }
+#endif
+    default: ok = false;
+  }
+  for (int i = 0; i < 6; ++i) out[i] = o[i];
+  return ok;
+}
+
+__global__ void epv_math_kat_kernel(uint32_t op, uint32_t n, const double *in, double *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double x[4];
+  for (int j = 0; j < 4; ++j) x[j] = in[4u * (size_t)i + j];
+  epv_math_kat_item(op, x, out + 6u * (size_t)i);
+}
+
+EPV_API int epv_math_kat(epv_ctx *c, uint32_t op, uint32_t where, uint32_t n, const double *in, double *out) {
+  if (!c || !in || !out || !n || n > (1u << 20) || op >= EPV_KAT_OPS || where > 1u) return EPV_ERR_ARG;
+  if (where == 1u) {
+    if (op == 1u || op == 6u) return EPV_ERR_ARG;   // the float bound has no host form
+    for (uint32_t i = 0; i < n; ++i) epv_math_kat_item(op, in + 4u * (size_t)i, out + 6u * (size_t)i);
+    return EPV_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  double *d_in = nullptr, *d_out = nullptr;
+  HIP_TRY(c, hipMalloc(&d_in, (size_t)n * 4u * sizeof(double)));
+  if (hipMalloc(&d_out, (size_t)n * 6u * sizeof(double)) != hipSuccess) { dfree(d_in); return fail(c, EPV_ERR_HIP, "epv_math_kat: allocation"); }
+  hipError_t e = hipMemcpyAsync(d_in, in, (size_t)n * 4u * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    epv_math_kat_kernel<<<(n + 255u) / 256u, 256, 0, c->stream>>>(op, n, d_in, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 6u * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_in); dfree(d_out);
+  if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_math_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
 EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
   if (!c) return EPV_ERR_ARG;
   if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_unobserved");

@@ -9,7 +9,8 @@
 //
 // The reference calls glibc exp/log at ContinuousTimeMarkovModel.cpp:120,149 and
 // SingleSiteSampler.cpp:207,214,299,304,524; accuracy of these replacements is < 1 ulp
-// (tests/test_math.py, against mpmath).
+// (the oracle's restatement against mpmath: tests/test_math_rng.py and tests/test_device_math.py; this header's
+// device and host passes against the oracle, bit for bit, through epv_math_kat: tests/test_device_math.py).
 #ifndef EPV_MATH_H
 #define EPV_MATH_H
 

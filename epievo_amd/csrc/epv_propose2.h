@@ -43,7 +43,8 @@ struct EpvSegRec {      // one segment, everything the recursions need
 #define EPV_HREC_SHORT 8u   /* ... when nothing reads length and address word after the dense evaluation
                                (sequential jump kernel): they are parked in the slots of the two uniforms */
 
-__device__ __forceinline__ void epv_seg_matrices(double len, double r0, double r1, double out[6]) {
+// (host too, for epv_math_kat's host pass: the four matrix entries; the bounds are a device float exp)
+EPV_DEV void epv_seg_matrices(double len, double r0, double r1, double out[6]) {
   const double denom = r0 + r1;
   const double h = 1.0 / epv_exp(len * (r0 + r1));     // ContinuousTimeMarkovModel.cpp:143-161
   out[0] = (r0 * h + r1) / denom;
@@ -51,8 +52,13 @@ __device__ __forceinline__ void epv_seg_matrices(double len, double r0, double r
   const double h2 = epv_exp(-len * (r0 + r1));         // :116-125, shared by both start states
   out[2] = gtp(r0, r1, h2, denom, 0u, 0u);
   out[3] = gtp(r0, r1, h2, denom, 1u, 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
   out[4] = nojump_bound(len * r0);
   out[5] = nojump_bound(len * r1);
+#else
+  out[4] = 0.0;
+  out[5] = 0.0;
+#endif
 }
 
 // tab[(b * 4 + 2 * left_state + right_state) * 6 ..]: the single segment of branch b (length =

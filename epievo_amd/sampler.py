@@ -47,7 +47,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan", "epv_philox_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
+    "epv_phase_plan", "epv_philox_kat", "epv_math_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -131,6 +131,7 @@ def lib():
         L.epv_phase_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_philox_kat.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, dp]
+        L.epv_math_kat.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, dp]
         L.epv_set_unobserved.argtypes = [vp, u8p]
         L.epv_unobserved_cells.argtypes = [vp, u64p]
         L.epv_set_leaf_evidence.argtypes = [vp, C.POINTER(C.c_float)]
@@ -289,6 +290,18 @@ class DeviceSampler:
         ctr = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 6)
         out = np.zeros((ctr.shape[0], 3, 2))
         self._ck(self.L.epv_philox_kat(self.h, int(seed), ctr.shape[0], _p(ctr, C.c_uint32), _p(out, C.c_double)))
+        return out
+
+    def math_kat(self, op, items, where=0):
+        """the arithmetic under the kernels on known inputs (epv_math_kat): items[i] = up to four doubles, the
+        inputs of `op`; where = 0 a kernel of its own, 1 the library's host pass of the same headers.
+        Returns [i, 6] doubles (an op's outputs first, zeros after)."""
+        x = np.ascontiguousarray(items, dtype=np.float64)
+        x = x.reshape(-1, 1) if x.ndim == 1 else x
+        inp = np.zeros((x.shape[0], 4))
+        inp[:, :x.shape[1]] = x
+        out = np.zeros((x.shape[0], 6))
+        self._ck(self.L.epv_math_kat(self.h, int(op), int(where), x.shape[0], _p(inp, C.c_double), _p(out, C.c_double)))
         return out
 
     def set_unobserved(self, mask):

@@ -162,6 +162,27 @@ int epv_phase_plan(epv_ctx *ctx, uint32_t *word);
  * is what the comparisons of whole runs against the oracle's parallel rung establish. */
 int epv_philox_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *counters, double *out);
 
+/* Known-answer entry for the arithmetic, for tests: evaluates one operation on each of n <= 2^20 items,
+ * in[4 i ..] -> out[6 i ..], with the functions the kernels call (epv_math.h, epv_kernels.h,
+ * epv_propose2.h).  An op's results fill the first slots of the item's six doubles, the rest are 0.
+ *   where = 0  a kernel of its own, one launch, one lane per item;
+ *   where = 1  the host pass of the same headers inside this library (the one the ABI glue takes its
+ *              per-branch constants from).  Ops that exist on the device only return EPV_ERR_ARG.
+ *   op 0  x              -> epv_exp(x), epv_log(x)
+ *   op 1  x              -> nojump_bound(x)                                      (device only)
+ *   op 2  len, r0, r1    -> epv_seg_matrices: P00, P11, PT00, PT10, and the no-jump bounds of len r0 and
+ *                           len r1 (where = 1: the bounds are 0)
+ *   op 3  u, r           -> the hold time -epv_log(1 - u) / r
+ *   op 4  u, trunc, r    -> Nielsen's first jump -epv_log(1 - u trunc) / r
+ *   op 5  dt, scale      -> epv_stat_fix(dt, scale), the 64-bit integer in the bits of the double
+ *   op 6  u, T, r        -> 1.0 or 0.0 twice: the shortcut's test 1 - u < nojump_bound(T r), and the exact
+ *                           test !(-epv_log(1 - u) / r < T) it stands in for           (device only)
+ * Ops 0 and 2-5 equal the CPU oracle's parallel rung bit for bit; ops 1 and 6 are what the no-jump shortcut
+ * rests on (bound <= exp(-x) with room for the rounding of the exact test).  As with epv_philox_kat, this
+ * checks the functions in a kernel of their own; it does not show what the compiler makes of a call site
+ * inside the MCMC kernels -- that is what the comparisons of whole runs against the oracle establish. */
+int epv_math_kat(epv_ctx *ctx, uint32_t op, uint32_t where, uint32_t n, const double *in, double *out);
+
 /* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
  * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
  * instead of the indicator of the path's end state) instead of pinning it.  The node-major layout

@@ -323,6 +323,13 @@ static inline double rng_trial_canonical(orc_rng *g) {
 }
 
 /* ------------------------------------------------ end-conditioned sampling */
+/* the two transforms of a uniform draw (EndCondSampling.cpp:466-476 and :577-580, :606) */
+static inline double hold_time(const orc_state *st, double u, double rate) {
+  return -st->flog(1.0 - u) / rate;
+}
+static inline double trunc_exp_time(const orc_state *st, double u, double trunc, double rate) {
+  return -st->flog(1.0 - u * trunc) / rate;
+}
 /* EndCondSampling.cpp:466-509.  Returns 0 ok, 1 capacity overflow.
  * Appends accepted jump times (offset by start_time) to `out`. */
 static int forward_rejection(orc_state *st, orc_scratch *sc, orc_rng *g,
@@ -351,7 +358,7 @@ static int forward_rejection(orc_state *st, orc_scratch *sc, orc_rng *g,
 #ifndef _OPENMP
       ++st->n_draws;
 #endif
-      tau = -st->flog(1.0 - u * trunc) / rate_a;
+      tau = trunc_exp_time(st, u, trunc, rate_a);
       /* mathematically tau < T; a draw within rounding of 1 could land on T: redraw (the
        * reference has no such guard; the event has probability ~1e-13 per draw) */
       if (!(tau < T)) bad = 1;
@@ -370,7 +377,7 @@ static int forward_rejection(orc_state *st, orc_scratch *sc, orc_rng *g,
 #ifndef _OPENMP
       ++st->n_draws;
 #endif
-      tau += -st->flog(1.0 - u) / (a ? rate1 : rate0);
+      tau += hold_time(st, u, a ? rate1 : rate0);
       if (!(tau < T)) break;
       if (cap && nj >= room) { overflow = 1; break; }
       a ^= 1;
@@ -1436,6 +1443,31 @@ ORC_API double orc_kat_exp(double x) { return orc_exp(x); }
 ORC_API double orc_kat_log(double x) { return orc_log(x); }
 ORC_API void orc_kat_exp_log_array(const double *x, uint64_t n, double *e, double *l) {
   for (uint64_t i = 0; i < n; ++i) { e[i] = orc_exp(x[i]); l[i] = orc_log(x[i]); }
+}
+/* array forms for the device numerics tests: item i of every array.  seg[4 i ..] = P00, P11 of
+ * trans_prob_mat and get_trans_prob(0 -> 0), (1 -> 0): the four entries the kernels keep per segment */
+ORC_API void orc_kat_seg_matrices_array(int math_mode, uint64_t n, const double *len, const double *r0,
+                                        const double *r1, double *seg) {
+  orc_state st; st.math_mode = math_mode; set_math(&st);
+  for (uint64_t i = 0; i < n; ++i) {
+    double P[4];
+    trans_prob_mat(&st, r0[i], r1[i], len[i], P);
+    seg[4 * i] = P[0]; seg[4 * i + 1] = P[3];
+    seg[4 * i + 2] = get_trans_prob(&st, r0[i], r1[i], len[i], 0, 0);
+    seg[4 * i + 3] = get_trans_prob(&st, r0[i], r1[i], len[i], 1, 0);
+  }
+}
+ORC_API void orc_kat_hold_time_array(int math_mode, uint64_t n, const double *u, const double *rate, double *out) {
+  orc_state st; st.math_mode = math_mode; set_math(&st);
+  for (uint64_t i = 0; i < n; ++i) out[i] = hold_time(&st, u[i], rate[i]);
+}
+ORC_API void orc_kat_trunc_exp_time_array(int math_mode, uint64_t n, const double *u, const double *trunc,
+                                          const double *rate, double *out) {
+  orc_state st; st.math_mode = math_mode; set_math(&st);
+  for (uint64_t i = 0; i < n; ++i) out[i] = trunc_exp_time(&st, u[i], trunc[i], rate[i]);
+}
+ORC_API void orc_kat_stat_fix(uint64_t n, const double *dt, const double *scale, int64_t *out) {
+  for (uint64_t i = 0; i < n; ++i) out[i] = stat_fix(dt[i], scale[i]);
 }
 ORC_API void orc_kat_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {
   orc_philox4x32_10(ctr, key, out);

@@ -10,7 +10,7 @@
  * :149; SingleSiteSampler.cpp:207,214,299,304,524); "rung A" of the oracle
  * keeps libm so that it stays bit-identical to the reference.
  *
- * Accuracy (checked in tests/test_math.py against mpmath): < 1 ulp.
+ * Accuracy (checked in tests/test_math_rng.py and tests/test_device_math.py against mpmath): < 1 ulp.
  */
 #ifndef ORC_MATH_H
 #define ORC_MATH_H

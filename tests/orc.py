@@ -101,6 +101,10 @@ def orc_lib():
         L.orc_kat_log.restype = C.c_double
         L.orc_kat_exp_log_array.argtypes = [dp, C.c_uint64, dp, dp]
         L.orc_kat_philox.argtypes = [u32p, u32p, u32p]
+        L.orc_kat_seg_matrices_array.argtypes = [C.c_int, C.c_uint64, dp, dp, dp, dp]
+        L.orc_kat_hold_time_array.argtypes = [C.c_int, C.c_uint64, dp, dp, dp]
+        L.orc_kat_trunc_exp_time_array.argtypes = [C.c_int, C.c_uint64, dp, dp, dp, dp]
+        L.orc_kat_stat_fix.argtypes = [C.c_uint64, dp, dp, C.POINTER(C.c_int64)]
         L.orc_kat_keyed_block.argtypes = [C.c_uint64] + [C.c_uint32] * 6 + [dp]
         L.orc_kat_mt_canonical.argtypes = [C.c_uint64, C.c_uint64, dp]
         _orc = L
@@ -405,3 +409,49 @@ def forward_thinning(model, tree, n, seed, root=None):
         if tot != 2 ** 64 - 1:
             return FlatPaths(n, tree.n_nodes, init, off, jumps[:tot]), states
         cap *= 4
+
+
+def _f64(*arrays):
+    return [np.ascontiguousarray(a, np.float64) for a in arrays]
+
+
+def kat_exp_log(x):
+    """orc_exp, orc_log of every x"""
+    x, = _f64(x)
+    e, l = np.zeros_like(x), np.zeros_like(x)
+    orc_lib().orc_kat_exp_log_array(_p(x, C.c_double), len(x), _p(e, C.c_double), _p(l, C.c_double))
+    return e, l
+
+
+def kat_seg_matrices(length, r0, r1, math_mode=MATH_EPV):
+    """[i, 4] = P00, P11 of trans_prob_mat and get_trans_prob(0 -> 0), (1 -> 0) of every (length, r0, r1)"""
+    length, r0, r1 = _f64(length, r0, r1)
+    out = np.zeros((len(length), 4))
+    orc_lib().orc_kat_seg_matrices_array(math_mode, len(length), _p(length, C.c_double), _p(r0, C.c_double),
+                                         _p(r1, C.c_double), _p(out, C.c_double))
+    return out
+
+
+def kat_hold_time(u, rate, math_mode=MATH_EPV):
+    """forward sampling's hold time of every (u, rate)"""
+    u, rate = _f64(u, rate)
+    out = np.zeros_like(u)
+    orc_lib().orc_kat_hold_time_array(math_mode, len(u), _p(u, C.c_double), _p(rate, C.c_double), _p(out, C.c_double))
+    return out
+
+
+def kat_trunc_exp_time(u, trunc, rate, math_mode=MATH_EPV):
+    """Nielsen's first jump of every (u, trunc, rate)"""
+    u, trunc, rate = _f64(u, trunc, rate)
+    out = np.zeros_like(u)
+    orc_lib().orc_kat_trunc_exp_time_array(math_mode, len(u), _p(u, C.c_double), _p(trunc, C.c_double),
+                                           _p(rate, C.c_double), _p(out, C.c_double))
+    return out
+
+
+def kat_stat_fix(dt, scale):
+    """the fixed-point dwell time llrint(dt * scale) of every (dt, scale), int64"""
+    dt, scale = _f64(dt, scale)
+    out = np.zeros(len(dt), np.int64)
+    orc_lib().orc_kat_stat_fix(len(dt), _p(dt, C.c_double), _p(scale, C.c_double), _p(out, C.c_int64))
+    return out
