@@ -23,6 +23,7 @@
 #include "epv_pavg.h"
 #include "epv_bevents.h"
 #include "epv_wstat.h"
+#include "epv_epochs.h"
 #include "epv_origin.h"
 #include "epv_domains.h"
 
@@ -163,6 +164,14 @@ struct epv_ctx {
   uint32_t ws_B = 0;
   uint64_t ws_samples = 0;
   std::vector<double> ws_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
+  // epoch statistics (epv_epochs.h), off while ep_P == 0
+  uint32_t ep_P = 0;               // epochs per branch
+  unsigned long long *d_ep = nullptr;   // [ep_B][ep_P][32]: J[8], lo[8], hi[8], cov[8]
+  uint32_t ep_B = 0;
+  uint64_t ep_samples = 0;
+  uint64_t ep_addends = 0;         // blocks along the sites, added over the samples: the addends a global word has received
+  std::vector<double> ep_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
+  std::vector<uint64_t> ep_fixT;   // llrint(T_b 2^k_b) of the first sample: the edges its epochs were cut at
   // lineage origin maps (epv_origin.h), off while !lo_on
   bool lo_on = false;
   uint32_t *d_lo = nullptr;               // origin [lo_R][lo_cnt] counts over local sites lo_lo .. lo_lo + lo_cnt - 1
@@ -1180,6 +1189,115 @@ int launch_domains(epv_ctx *c) {
   return EPV_OK;
 }
 
+// ---- epoch statistics (epv_epochs.h): J and D per branch and epoch of the branch, over the triples centred
+// at the sites of owned_range.  The accumulator [B][P][32] does not depend on the site range
+// the statistics off: no accumulator, no samples
+void epoch_off(epv_ctx *c) {
+  dfree(c->d_ep);
+  c->ep_P = 0;
+  c->ep_B = 0;
+  c->ep_samples = 0;
+  c->ep_addends = 0;
+  c->ep_scale.clear();
+  c->ep_fixT.clear();
+}
+// (re)lay out the accumulator for the current tree; zeroes it.  A HIP error leaves the statistics off
+int epoch_alloc(epv_ctx *c, uint32_t P) {
+  auto body = [&]() -> int {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dfree(c->d_ep);
+    const size_t bytes = (size_t)256u * c->S.B * P;
+    if (bytes) {
+      HIP_TRY(c, hipMalloc(&c->d_ep, bytes));
+      HIP_TRY(c, hipMemsetAsync(c->d_ep, 0, bytes, c->stream));
+    }
+    c->ep_P = P;
+    c->ep_B = c->S.B;
+    c->ep_samples = 0;
+    c->ep_addends = 0;
+    c->ep_scale.clear();
+    c->ep_fixT.clear();
+    return EPV_OK;
+  };
+  const int rc = body();
+  if (rc) epoch_off(c);
+  return rc;
+}
+// the accumulator matches the current tree, and the scales 2^k_b are the ones its integers were taken with
+int ensure_epochs(epv_ctx *c) {
+  if (!c->ep_P) return EPV_OK;
+  if (c->S.B != c->ep_B) {
+    if (c->ep_samples)
+      return fail(c, EPV_ERR_STATE, "the tree of this context changed after the epoch statistics took samples: "
+                                    "epv_set_epoch_stats again");
+    const int rc = epoch_alloc(c, c->ep_P);
+    if (rc) return rc;
+  }
+  const int rc = ensure_stat_scale(c);
+  if (rc) return rc;
+  if (c->ep_samples && c->ep_scale != c->statscale)
+    return fail(c, EPV_ERR_STATE, "the branch lengths or the genome length changed after the epoch statistics took "
+                                  "samples, so their fixed-point scales 2^k_b differ: read them out and "
+                                  "epv_reset_epoch_stats");
+  return EPV_OK;
+}
+// 256-site tiles per block of epv_epoch_accum_kernel: about a thousand blocks where the sites allow it (a
+// block's flush costs up to 32 P atomics whatever it covered), at most EPV_EPOCH_MAX_TILES
+uint32_t epoch_tiles(const epv_ctx *c, uint64_t lo, uint64_t hi) {
+  if (hi < lo) return 1u;
+  const uint64_t tiles = (hi - lo) / 256u + 1u;
+  const uint64_t want = (tiles * std::max<uint32_t>(c->S.B, 1u) + 1023u) / 1024u;
+  return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(want, EPV_EPOCH_MAX_TILES));
+}
+// blocks along the sites of one launch over the current owned range
+uint64_t epoch_blocks(const epv_ctx *c) {
+  uint64_t lo = 0, hi = 0;
+  owned_range(c, &lo, &hi);
+  return hi >= lo ? (hi - lo) / (256ull * epoch_tiles(c, lo, hi)) + 1u : 0u;
+}
+// `batch` more samples fit (ensure_epochs first): a block adds at most one addend below 2^32 to a global
+// word per sample (the lo and hi halves of its 64-bit sum, its counts), so the 64-bit words hold while
+//   addends so far + batch * blocks along the sites < 2^32
+// (ep_addends counts the blocks of every sample taken, whatever the owned range was then)
+int epoch_check_cap(epv_ctx *c, uint64_t batch) {
+  const uint64_t blocks = epoch_blocks(c), room = (1ull << 32) - 1u;
+  if (!blocks) return EPV_OK;
+  const uint64_t left = c->ep_addends > room ? 0u : (room - c->ep_addends) / blocks;   // samples that still fit
+  if (c->ep_addends > room || batch > left) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "epoch statistics over %llu blocks of sites take at most %llu samples in their "
+                  "64-bit sums and hold %llu: read them out and epv_reset_epoch_stats",
+                  (unsigned long long)blocks, (unsigned long long)(c->ep_samples + left), (unsigned long long)c->ep_samples);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the scales and branch lengths of now become the ones the accumulator's integers mean
+void epoch_remember(epv_ctx *c) {
+  c->ep_scale = c->statscale;
+  c->ep_fixT.assign(c->S.N, 0u);
+  for (uint32_t b = 1; b < c->S.N; ++b) c->ep_fixT[b] = (uint64_t)std::llrint(c->blen[b] * c->statscale[b]);   // (< 2^50: exact)
+}
+// the resident paths as one sample (ensure_epochs first)
+int launch_epochs(epv_ctx *c) {
+  int rc = epoch_check_cap(c, 1u);
+  if (rc) return rc;
+  uint64_t lo = 0, hi = 0;
+  owned_range(c, &lo, &hi);
+  if (hi >= lo && c->S.n >= 3u && c->S.B) {
+    const uint32_t tiles = epoch_tiles(c, lo, hi);
+    const uint64_t blocks = (hi - lo) / (256ull * tiles) + 1u;
+    if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many sites in one context for the epoch statistics");
+    hipLaunchKernelGGL(epv_epoch_accum_kernel, dim3((unsigned)blocks, c->S.B), dim3(256), (size_t)136u * c->ep_P,
+                       c->stream, c->S, lo, hi, c->d_statscale, c->ep_P, tiles, c->d_ep);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (!c->ep_samples) epoch_remember(c);
+  ++c->ep_samples;
+  c->ep_addends += epoch_blocks(c);
+  return EPV_OK;
+}
+
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
 int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
@@ -1520,6 +1638,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
   dfree(c->d_be); dfree(c->d_be_out);
   dfree(c->d_ws);
+  dfree(c->d_ep);
   dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
   dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
@@ -2439,7 +2558,7 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics, lineage-origin and domain-statistics sample}: the chain of epv_run_mcmc_sums
+// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics, epoch-statistics, lineage-origin and domain-statistics sample}: the chain of epv_run_mcmc_sums
 // and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
 // snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
@@ -2452,6 +2571,8 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
                                   "read them out and epv_reset_branch_events");
   if ((rc = ensure_wstat(c))) return rc;
   if (c->ws_W && (rc = wstat_check_cap(c, batch))) return rc;   // (before any sweep as well)
+  if ((rc = ensure_epochs(c))) return rc;
+  if (c->ep_P && (rc = epoch_check_cap(c, batch))) return rc;   // (before any sweep as well)
   if ((rc = ensure_origins(c))) return rc;
   if (c->lo_on && c->lo_samples + batch > EPV_BEV_MAX_SAMPLES)
     return fail(c, EPV_ERR_STATE, "lineage origins would pass 2^21 samples, the most their 32-bit counts take: "
@@ -2473,6 +2594,7 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     if (c->pa_P && (rc = launch_pavg(c))) return rc;
     if (c->be_on && (rc = launch_bevents(c))) return rc;
     if (c->ws_W && (rc = launch_wstat(c))) return rc;
+    if (c->ep_P && (rc = launch_epochs(c))) return rc;
     if (c->lo_on && (rc = launch_origins(c))) return rc;
     if (c->dm_on && (rc = launch_domains(c))) return rc;
   }
@@ -3419,5 +3541,97 @@ EPV_API int epv_window_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64
         D[(w * B + b) * 8u + k] = (double)p[8 + k] * inv / ns;
       }
     }
+  return EPV_OK;
+}
+
+// ---- epoch statistics (epv_epochs.h)
+EPV_API int epv_set_epoch_stats(epv_ctx *c, uint32_t P) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!P) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    epoch_off(c);
+    return EPV_OK;
+  }
+  if (P > EPV_EPOCH_MAX_P) return fail(c, EPV_ERR_ARG, "epoch statistics take at most EPV_EPOCH_MAX_P = 256 epochs");
+  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
+  int rc = epoch_alloc(c, P);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_reset_epoch_stats(epv_ctx *c) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->d_ep) HIP_TRY(c, hipMemsetAsync(c->d_ep, 0, (size_t)256u * c->ep_B * c->ep_P, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->ep_samples = 0;
+  c->ep_addends = 0;
+  c->ep_scale.clear();
+  c->ep_fixT.clear();
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_epoch_stats(epv_ctx *c) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = ensure_epochs(c)) || (rc = launch_epochs(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_epoch_stats_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->ep_P ? c->ep_samples : 0u;
+  return EPV_OK;
+}
+
+EPV_API int epv_epoch_stats_set_samples(epv_ctx *c, uint64_t n) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
+  if (n && c->ep_scale.empty()) {   // (as if the samples had been taken with the scales of now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_stat_scale(c);
+    if (rc) return rc;
+    epoch_remember(c);
+  }
+  c->ep_samples = n;
+  c->ep_addends = n * epoch_blocks(c);   // (as if every one had been taken over the sites of now)
+  if (!n) { c->ep_scale.clear(); c->ep_fixT.clear(); }
+  return EPV_OK;
+}
+
+EPV_API int epv_epoch_stats_layout(epv_ctx *c, uint32_t *B, uint32_t *P, int *k, uint64_t *fixT) {
+  if (!c || !B || !P) return EPV_ERR_ARG;
+  *B = *P = 0;
+  if (!c->ep_P) return EPV_OK;
+  if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->ep_samples == 0) {   // lay out for the tree as it is now
+    const int rc = ensure_epochs(c);
+    if (rc) return rc;
+  }
+  const std::vector<double> &sc = c->ep_scale.empty() ? c->statscale : c->ep_scale;
+  *B = c->ep_B;
+  *P = c->ep_P;
+  for (uint32_t b = 1; b <= c->ep_B && b < sc.size(); ++b) {
+    if (k) k[b - 1u] = std::ilogb(sc[b]);                                   // (sc[b] = 2^k_b exactly)
+    if (fixT) fixT[b - 1u] = c->ep_fixT.empty() ? (uint64_t)std::llrint(c->blen[b] * sc[b]) : c->ep_fixT[b];
+  }
+  return EPV_OK;
+}
+
+EPV_API int epv_get_epoch_stats(epv_ctx *c, uint64_t *raw) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
+  if (!raw) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t bytes = (size_t)256u * c->ep_B * c->ep_P;
+  if (bytes) HIP_TRY(c, hipMemcpy(raw, c->d_ep, bytes, hipMemcpyDeviceToHost));
   return EPV_OK;
 }

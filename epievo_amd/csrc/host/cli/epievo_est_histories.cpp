@@ -25,12 +25,16 @@
 // New: -d/--domains FILE: the domain size spectra of the B batch sweeps (epv_set_domain_stats with max_samples = B:
 // per node and state the spectrum of run lengths of the node's state along the genome, closed over the whole
 // genome), as integers (epv::write_domain_stats).  Changes nothing else the run writes.
+// New: -E/--epochs FILE with -K/--nepochs P (default 10): the epoch statistics of the B batch sweeps
+// (epv_set_epoch_stats: J and D per branch and epoch of the branch as exact integers, with the epoch's rate factor
+// under the model of the run; epv::write_epoch_stats).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
 #include <random>
 #include <stdexcept>
 
+#include "epievo_mi355x.h"
 #include "epv_io.hpp"
 #include "epv_model.hpp"
 #include "epv_options.hpp"
@@ -49,8 +53,10 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file;
     size_t batch = 10, burnin = 10, n_points = 100;
+    const size_t no_epochs = std::numeric_limits<size_t>::max();
+    size_t n_epochs = no_epochs;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
     size_t rng_seed = std::numeric_limits<size_t>::max();
@@ -79,6 +85,9 @@ int main(int argc, const char **argv) {
                       false, origins_file);
     opt_parse.add_opt("domains", 'd', "output file of the domain size spectra of the batch sweeps (integer counts per bin)",
                       false, domains_file);
+    opt_parse.add_opt("epochs", 'E', "output file of J and D per branch and epoch of the batch sweeps, with rate factors",
+                      false, epochs_file);
+    opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics and origin maps "
                       "(default 1)", false, window);
     vector<string> leftover_args;
@@ -104,6 +113,10 @@ int main(int argc, const char **argv) {
     if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty())
       throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional and -O/--origins: give the output "
                                "file of the branch-event maps, of the regional statistics or of the origin maps");
+    if (n_epochs != no_epochs && epochs_file.empty())
+      throw std::runtime_error("-K/--nepochs belongs to -E/--epochs: give the output file of the epoch statistics");
+    if (n_epochs == no_epochs) n_epochs = 10;
+    if (n_epochs == 0 || n_epochs > EPV_EPOCH_MAX_P) throw std::runtime_error("-K: 1 to 256 epochs per branch");
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
@@ -150,6 +163,7 @@ int main(int argc, const char **argv) {
     if (!regional_file.empty()) mcmc.set_window_stats(window);
     if (!origins_file.empty()) mcmc.set_lineage_origins(true);
     if (!domains_file.empty()) mcmc.set_domain_stats(batch);
+    if (!epochs_file.empty()) mcmc.set_epoch_stats((uint32_t)n_epochs);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -205,6 +219,15 @@ int main(int argc, const char **argv) {
       mcmc.download_domain_stats(hist, len_sum, n_nodes, n_samples);
       if (VERBOSE) cerr << "[WRITING DOMAIN SIZE SPECTRA OF " << n_samples << " SAMPLES: " << domains_file << "]" << endl;
       epv::write_domain_stats(domains_file, th.node_names, n_samples, hist.data(), len_sum.data());
+    }
+    if (!epochs_file.empty()) {
+      vector<uint64_t> closed, fixT;
+      vector<int> scale_exp;
+      uint64_t n_samples = 0;
+      mcmc.download_epoch_stats(closed, scale_exp, fixT, n_samples);
+      if (VERBOSE) cerr << "[WRITING EPOCH STATISTICS OF " << n_samples << " SAMPLES: " << epochs_file << "]" << endl;
+      epv::write_epoch_stats(epochs_file, th.node_names, th.n_nodes(), (uint32_t)n_epochs, th.branches.data(),
+                             scale_exp.data(), fixT.data(), closed.data(), n_samples, the_model.rates);
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

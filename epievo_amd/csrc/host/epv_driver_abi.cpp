@@ -24,6 +24,11 @@ struct epvd_sampler {
   std::vector<int64_t> staged_wstat;   // between epvd_window_stats_sizes and epvd_download_window_stats
   uint64_t staged_wstat_nw = 0, staged_wstat_ns = 0;
   bool have_staged_wstat = false;
+  std::vector<uint64_t> staged_epoch;   // between epvd_epoch_stats_sizes and epvd_download_epoch_stats
+  std::vector<int> staged_epoch_k;
+  std::vector<uint64_t> staged_epoch_fixT;
+  uint64_t staged_epoch_ns = 0;
+  bool have_staged_epoch = false;
   std::vector<uint32_t> staged_origin;   // between epvd_lineage_origins_sizes and epvd_download_lineage_origins
   std::vector<uint64_t> staged_age;
   bool have_staged_origins = false;
@@ -363,5 +368,35 @@ EPVD_API int epvd_download_domain_stats(epvd_sampler *h, uint32_t n_nodes, uint6
     std::copy(hh.begin(), hh.end(), hist);
     std::copy(ll.begin(), ll.end(), len_sum);
     if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_epoch_stats(epvd_sampler *h, uint32_t P) {
+  return guarded(h, [&] { h->s->set_epoch_stats(P); });
+}
+EPVD_API int epvd_epoch_stats_sizes(epvd_sampler *h, uint32_t *P, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t ns = 0;
+    h->s->download_epoch_stats(h->staged_epoch, h->staged_epoch_k, h->staged_epoch_fixT, ns);
+    h->have_staged_epoch = true;
+    h->staged_epoch_ns = ns;
+    *P = h->s->epoch_stats_epochs();
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_epoch_stats(epvd_sampler *h, uint64_t *closed, int *k, uint64_t *fixT, double *J, double *D) {
+  return guarded(h, [&] {
+    if (!h->have_staged_epoch) throw std::runtime_error("epvd_epoch_stats_sizes first");
+    if (closed) std::copy(h->staged_epoch.begin(), h->staged_epoch.end(), closed);
+    if (k) std::copy(h->staged_epoch_k.begin() + 1, h->staged_epoch_k.end(), k);
+    if (fixT) std::copy(h->staged_epoch_fixT.begin() + 1, h->staged_epoch_fixT.end(), fixT);
+    if (J && D && h->staged_epoch_ns) {
+      std::vector<double> j, d;
+      h->s->epoch_counts_to_stats(h->staged_epoch, h->staged_epoch_k, h->staged_epoch_ns, j, d);
+      std::copy(j.begin(), j.end(), J);
+      std::copy(d.begin(), d.end(), D);
+    }
+    h->staged_epoch.clear();
+    h->have_staged_epoch = false;
   });
 }

@@ -12,6 +12,7 @@
 #include "epv_sim.hpp"
 #include "epv_io.hpp"
 #include "epv_domains.hpp"
+#include "epv_epochs.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
 
@@ -484,3 +485,69 @@ EPVH_API void epvh_domain_stats_copy(void *h, char *names, int names_len, uint64
   std::copy(ds->len_sum.begin(), ds->len_sum.end(), len_sum);
 }
 EPVH_API void epvh_domain_stats_free(void *h) { delete (epv::DomainStats *)h; }
+
+// ---- epoch statistics: closing the difference form (epv_epochs.hpp), and the file of epievo_est_histories -E
+EPVH_API void epvh_epoch_edges(uint64_t fixT, uint32_t P, uint64_t *out) { epv::epoch_edges(fixT, P, out); }
+EPVH_API int epvh_epoch_close(const uint64_t *raw, const uint64_t *fixT, uint32_t B, uint32_t P, uint64_t *closed) {
+  try {
+    epv::epoch_close(raw, fixT, B, P, closed);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// closed[B][P][24], k[B] -> J, D[B][P][8] per sample
+EPVH_API int epvh_epoch_counts_to_stats(const uint64_t *closed, const int *k, uint32_t B, uint32_t P, uint64_t samples,
+                                        double *J, double *D) {
+  try {
+    epv::epoch_counts_to_stats(closed, k, B, P, samples, J, D);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// node_names: n_nodes names joined by '\n' (the root's first); branch_len, scale_exp, fixT: [n_nodes], index 0 = root
+EPVH_API int epvh_write_epoch_stats(const char *file, const char *node_names, int n_nodes, uint32_t P,
+                                    const double *branch_len, const int *scale_exp, const uint64_t *fixT,
+                                    const uint64_t *closed, uint64_t n_samples, const double *rates) {
+  try {
+    std::vector<std::string> names;
+    std::string all(node_names), cur;
+    for (char ch : all) {
+      if (ch == '\n') { names.push_back(cur); cur.clear(); } else cur.push_back(ch);
+    }
+    names.push_back(cur);
+    if ((int)names.size() != n_nodes) throw std::runtime_error("epvh_write_epoch_stats: one name per node");
+    std::array<double, 8> r;
+    for (int i = 0; i < 8; ++i) r[i] = rates[i];
+    epv::write_epoch_stats(file, names, n_nodes, P, branch_len, scale_exp, fixT, closed, n_samples, r);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_epoch_stats(const char *file) {
+  try {
+    return new epv::EpochStats(epv::read_epoch_stats(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+static std::string joined_names(const epv::EpochStats *es) {
+  std::string joined;
+  for (size_t i = 0; i < es->node_names.size(); ++i) joined += (i ? "\n" : "") + es->node_names[i];
+  return joined;
+}
+// names_len: the bytes epvh_epoch_stats_copy needs for the names, the closing 0 included
+EPVH_API void epvh_epoch_stats_dims(void *h, uint64_t *n_samples, uint64_t *n_epochs, uint64_t *n_branches,
+                                    uint64_t *names_len) {
+  const epv::EpochStats *es = (const epv::EpochStats *)h;
+  *names_len = joined_names(es).size() + 1u;
+  *n_samples = es->n_samples;
+  *n_epochs = es->n_epochs;
+  *n_branches = es->node_names.size();
+}
+// names: the non-root nodes' names joined by '\n'; branch_len, scale_exp: [B]; closed [B][P][24]; start, factor [B][P]
+EPVH_API void epvh_epoch_stats_copy(void *h, char *names, int names_len, double *branch_len, int *scale_exp,
+                                    uint64_t *closed, double *start, double *factor) {
+  const epv::EpochStats *es = (const epv::EpochStats *)h;
+  put_text(joined_names(es), names, names_len);
+  std::copy(es->branch_len.begin(), es->branch_len.end(), branch_len);
+  std::copy(es->scale_exp.begin(), es->scale_exp.end(), scale_exp);
+  std::copy(es->closed.begin(), es->closed.end(), closed);
+  std::copy(es->start.begin(), es->start.end(), start);
+  std::copy(es->factor.begin(), es->factor.end(), factor);
+}
+EPVH_API void epvh_epoch_stats_free(void *h) { delete (epv::EpochStats *)h; }

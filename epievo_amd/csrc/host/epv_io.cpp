@@ -956,6 +956,106 @@ DomainStats read_domain_stats(const std::string &file) {
   return ds;
 }
 
+// a 128-bit integer (low, high word) in decimal, and back
+static std::string u128_str(uint64_t lo, uint64_t hi) {
+  unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;
+  if (!v) return "0";
+  std::string r;
+  while (v) { r.push_back((char)('0' + (int)(v % 10u))); v /= 10u; }
+  std::reverse(r.begin(), r.end());
+  return r;
+}
+static void u128_parse(const std::string &t, uint64_t *lo, uint64_t *hi) {
+  if (t.empty() || t.size() > 39) throw std::runtime_error("not a 128-bit integer: " + t);
+  unsigned __int128 v = 0;
+  for (char ch : t) {
+    if (ch < '0' || ch > '9') throw std::runtime_error("not a 128-bit integer: " + t);
+    v = v * 10u + (unsigned)(ch - '0');
+  }
+  *lo = (uint64_t)v;
+  *hi = (uint64_t)(v >> 64);
+}
+
+void write_epoch_stats(const std::string &file, const std::vector<std::string> &node_names, int n_nodes, uint32_t P,
+                       const double *branch_len, const int *scale_exp, const uint64_t *fixT, const uint64_t *closed,
+                       uint64_t n_samples, const std::array<double, 8> &rates) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  char buf[64];
+  auto g17 = [&](double v) { std::snprintf(buf, sizeof buf, "%.17g", v); return buf; };
+  out << "#samples\t" << n_samples << "\tepochs\t" << P << '\n';
+  for (int b = 1; b < n_nodes; ++b) {
+    out << "NODE:" << node_names[b] << "\t" << g17(branch_len[b]) << "\t" << scale_exp[b] << '\n';
+    const double inv = std::ldexp(1.0, -scale_exp[b]);
+    for (uint32_t p = 0; p < P; ++p) {
+      const uint64_t *o = closed + ((uint64_t)(b - 1) * P + p) * 24u;
+      const uint64_t e = (uint64_t)((unsigned __int128)p * fixT[b] / P);
+      out << g17(fixT[b] ? (double)e / (double)fixT[b] : 0.0);
+      double J[8], D[8];
+      for (int c = 0; c < 8; ++c) {
+        out << "\t" << (int64_t)o[c];
+        J[c] = (double)(int64_t)o[c];
+      }
+      for (int c = 0; c < 8; ++c) {
+        out << "\t" << u128_str(o[8 + c], o[16 + c]);
+        D[c] = (double)(((unsigned __int128)o[16 + c] << 64) | o[8 + c]) * inv;
+      }
+      out << "\t" << g17(regional_rate_factor(2, J, D, rates)) << '\n';   // (the sample count cancels)
+    }
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+EpochStats read_epoch_stats(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad epoch-statistics file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("epoch-statistics file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  EpochStats es;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 4 || f[0] != "#samples" || f[2] != "epochs") throw bad("bad header: " + line);
+  es.n_samples = std::stoull(f[1]);
+  es.n_epochs = (uint32_t)std::stoul(f[3]);
+  if (!es.n_epochs) throw bad("no epochs");
+  uint32_t row = es.n_epochs;   // rows read of the current node
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    f = fields(line);
+    if (line.compare(0, 5, "NODE:") == 0) {
+      if (row != es.n_epochs) throw bad("node " + es.node_names.back() + " has another number of epochs");
+      if (f.size() != 3) throw bad("bad node line: " + line);
+      es.node_names.push_back(f[0].substr(5));
+      es.branch_len.push_back(std::stod(f[1]));
+      es.scale_exp.push_back(std::stoi(f[2]));
+      es.closed.resize(es.node_names.size() * es.n_epochs * 24u, 0u);
+      row = 0;
+    } else {
+      if (es.node_names.empty() || f.size() != 18 || row >= es.n_epochs) throw bad("bad epoch line: " + line);
+      uint64_t *o = es.closed.data() + ((es.node_names.size() - 1u) * es.n_epochs + row) * 24u;
+      es.start.push_back(std::stod(f[0]));
+      for (int c = 0; c < 8; ++c) o[c] = (uint64_t)std::stoll(f[1 + c]);
+      for (int c = 0; c < 8; ++c) u128_parse(f[9 + c], &o[8 + c], &o[16 + c]);
+      es.factor.push_back(std::strtod(f[17].c_str(), nullptr));   // (takes "nan")
+      ++row;
+    }
+  }
+  if (row != es.n_epochs) throw bad("the last node has another number of epochs");
+  return es;
+}
+
 }  // namespace epv
 
 namespace epv {

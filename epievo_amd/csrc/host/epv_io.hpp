@@ -123,6 +123,28 @@ void write_domain_stats(const std::string &file, const std::vector<std::string> 
                         const uint64_t *hist, const uint64_t *len_sum);
 DomainStats read_domain_stats(const std::string &file);
 
+// the epoch statistics of epievo_est_histories -E (epv_get_epoch_stats closed by epv::epoch_close):
+//   "#samples\t<S>\tepochs\t<P>", then per non-root node in pre-order "NODE:<name>\t<branch length>\t<k_b>"
+//   (%.17g; D integers are in units of 2^-k_b) and one line per epoch: the epoch's start as a fraction of
+//   the branch (E_p / fixT_b, %.17g), J[0..7] and D[0..7] as the integer sums over the samples (D up to 128
+//   bits, in decimal) and the epoch's rate factor under `rates` (epv::regional_rate_factor of the one
+//   branch and epoch; "nan" without dwell time), tab-separated.
+// closed: [b-1][p][24] as epv::epoch_close writes it; scale_exp, fixT, branch_len: per node, index 0 = root.
+struct EpochStats {
+  uint64_t n_samples = 0;
+  uint32_t n_epochs = 0;
+  std::vector<std::string> node_names;   // non-root nodes
+  std::vector<double> branch_len;        // per non-root node
+  std::vector<int> scale_exp;            // k_b per non-root node
+  std::vector<uint64_t> closed;          // [b][p][24]: J[8], D low words [8], D high words [8]
+  std::vector<double> start;             // [b][p]
+  std::vector<double> factor;            // [b][p]
+};
+void write_epoch_stats(const std::string &file, const std::vector<std::string> &node_names, int n_nodes, uint32_t P,
+                       const double *branch_len, const int *scale_exp, const uint64_t *fixT, const uint64_t *closed,
+                       uint64_t n_samples, const std::array<double, 8> &rates);
+EpochStats read_epoch_stats(const std::string &file);
+
 // the inputs of the E-step programs (epievo_est_params_histories.cpp:166-200): the local_paths file,
 // then the Newick tree or, with single_branch, the two-node tree of the file's last tot_time.  The
 // device keeps one length per branch, so paths whose tot_time differs from the tree's branch length

@@ -1,5 +1,6 @@
 // epv_sampler.cpp -- see epv_sampler.hpp
 #include "epv_sampler.hpp"
+#include "epv_epochs.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -365,6 +366,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
+  if (epoch_P_) set_epoch_stats(epoch_P_);
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
 }
@@ -376,6 +378,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (pa_points_) set_path_average(pa_points_);
   if (bevents_) set_branch_events(true);
   if (wstat_W_) set_window_stats(wstat_W_);
+  if (epoch_P_) set_epoch_stats(epoch_P_);
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
 }
@@ -681,6 +684,60 @@ void SingleSiteSampler::download_domain_stats(std::vector<uint64_t> &hist, std::
   std::vector<uint64_t> edges;
   download_domain_part(hist, len_sum, edges, n_nodes, n_samples);
   domain_part_close(n_nodes, n_samples, hist.data(), len_sum.data(), edges.data());
+}
+
+void SingleSiteSampler::set_epoch_stats(uint32_t P) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !P)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_epoch_stats(c, P), "epv_set_epoch_stats");
+  epoch_P_ = P;
+}
+
+void SingleSiteSampler::download_epoch_stats(std::vector<uint64_t> &closed, std::vector<int> &k,
+                                             std::vector<uint64_t> &fixT, uint64_t &n_samples) {
+  if (!epoch_P_) throw std::runtime_error("epoch statistics are off: set_epoch_stats first");
+  const std::vector<epv_ctx *> cs = contexts();
+  const uint64_t B = (uint64_t)n_nodes_ - 1u, P = epoch_P_;
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint64_t ns = 0;
+    if (epv_epoch_stats_samples(cs[i], &ns) != EPV_OK) throw std::runtime_error("epv_epoch_stats_samples failed");
+    if (i == 0) n_samples = ns;
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of epoch-statistics samples");
+  }
+  k.assign((size_t)n_nodes_, 0);
+  fixT.assign((size_t)n_nodes_, 0u);
+  uint32_t gotB = 0, gotP = 0;
+  check_on(cs.at(0), epv_epoch_stats_layout(cs[0], &gotB, &gotP, k.data() + 1, fixT.data() + 1), "epv_epoch_stats_layout");
+  if (gotB != B || gotP != P) throw std::runtime_error("the epoch statistics of the context have another layout");
+  // every context's raw part, added as integers: part = lo + 2^32 hi is kept with lo < 2^32, so no word wraps
+  std::vector<uint64_t> raw(B * P * 32u, 0u), part(B * P * 32u);
+  for (epv_ctx *c : cs) {
+    check_on(c, epv_get_epoch_stats(c, part.data()), "epv_get_epoch_stats");
+    for (uint64_t cell = 0; cell < B * P; ++cell) {
+      uint64_t *r = raw.data() + cell * 32u;
+      const uint64_t *q = part.data() + cell * 32u;
+      for (int c8 = 0; c8 < 8; ++c8) {
+        r[c8] += q[c8];
+        r[24 + c8] += q[24 + c8];           // (two's complement)
+        const uint64_t lo = r[8 + c8] + (q[8 + c8] & 0xffffffffull);
+        r[16 + c8] += q[16 + c8] + (q[8 + c8] >> 32) + (lo >> 32);
+        r[8 + c8] = lo & 0xffffffffull;
+      }
+    }
+  }
+  closed.assign(B * P * 24u, 0u);
+  if (B) epoch_close(raw.data(), fixT.data() + 1, (uint32_t)B, (uint32_t)P, closed.data());
+}
+
+void SingleSiteSampler::epoch_counts_to_stats(const std::vector<uint64_t> &closed, const std::vector<int> &k,
+                                              uint64_t n_samples, std::vector<double> &J, std::vector<double> &D) const {
+  const uint64_t B = (uint64_t)n_nodes_ - 1u, P = epoch_P_;
+  if (closed.size() != B * P * 24u || k.size() != (size_t)n_nodes_)
+    throw std::runtime_error("epoch_counts_to_stats: counts of the wrong size");
+  J.assign(B * P * 8u, 0.0);
+  D.assign(B * P * 8u, 0.0);
+  if (B && P) epv::epoch_counts_to_stats(closed.data(), k.data() + 1, (uint32_t)B, (uint32_t)P, n_samples, J.data(), D.data());
 }
 
 void SingleSiteSampler::set_unobserved(std::vector<uint8_t> whole_genome) {

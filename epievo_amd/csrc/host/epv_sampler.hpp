@@ -159,6 +159,18 @@ public:
                             uint32_t &n_nodes, uint64_t &n_samples);
   void download_domain_stats(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_nodes,
                              uint64_t &n_samples);
+  // epoch statistics (epv_set_epoch_stats) on every context: J and D per branch and epoch, with the window
+  // statistics' samples and lifecycle (P = 0: off).  download_epoch_stats: the raw parts of all slots and
+  // contexts of this process added as integers and closed once (epv::epoch_close):
+  // closed[((b-1) * P + p) * 24 + ..] = J[8], D low words [8], D high words [8]; k and fixT per node (index 0,
+  // the root: 0) from the context itself (epv_epoch_stats_layout); epoch_counts_to_stats: J, D[((b-1) * P + p) * 8 + c]
+  // per sample, D in time units
+  void set_epoch_stats(uint32_t P);
+  uint32_t epoch_stats_epochs() const { return epoch_P_; }
+  void download_epoch_stats(std::vector<uint64_t> &closed, std::vector<int> &k, std::vector<uint64_t> &fixT,
+                            uint64_t &n_samples);
+  void epoch_counts_to_stats(const std::vector<uint64_t> &closed, const std::vector<int> &k, uint64_t n_samples,
+                             std::vector<double> &J, std::vector<double> &D) const;
   // EPV_OPT_* of include/epievo_mi355x.h on every context, also those a later reset(model, tree, paths)
   // makes; HIP-event timing of the colour phases
   void set_options(uint32_t flags);
@@ -253,6 +265,7 @@ private:
   uint32_t pa_points_ = 0;    // set_path_average
   bool bevents_ = false;      // set_branch_events
   uint64_t wstat_W_ = 0;      // set_window_stats
+  uint32_t epoch_P_ = 0;      // set_epoch_stats
   bool origins_ = false;      // set_lineage_origins
   uint64_t domains_max_ = 0; // set_domain_stats
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)

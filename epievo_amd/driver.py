@@ -19,6 +19,7 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_set_branch_events", "epvd_branch_events_sizes", "epvd_download_branch_events",
                   "epvd_download_branch_event_windows",
                   "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats",
+                  "epvd_set_epoch_stats", "epvd_epoch_stats_sizes", "epvd_download_epoch_stats",
                   "epvd_set_lineage_origins", "epvd_reset_lineage_origins", "epvd_accumulate_lineage_origins",
                   "epvd_lineage_origin_rows", "epvd_lineage_origins_scale_exp", "epvd_lineage_origins_sizes", "epvd_download_lineage_origins",
                   "epvd_download_lineage_origin_windows",
@@ -64,6 +65,9 @@ def lib():
         L.epvd_set_window_stats.argtypes = [vp, C.c_uint64]
         L.epvd_window_stats_sizes.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_window_stats.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
+        L.epvd_set_epoch_stats.argtypes = [vp, C.c_uint32]
+        L.epvd_epoch_stats_sizes.argtypes = [vp, C.POINTER(C.c_uint32), u64p]
+        L.epvd_download_epoch_stats.argtypes = [vp, u64p, C.POINTER(C.c_int), u64p, dp, dp]
         ip = C.POINTER(C.c_int)
         L.epvd_set_lineage_origins.argtypes = [vp, C.c_int]
         L.epvd_reset_lineage_origins.argtypes = [vp]
@@ -277,6 +281,29 @@ class CppSampler:
             return ns, cnt
         if not ns:
             raise DriverError("window statistics hold no sample")
+        return ns, J, D
+
+    def enable_epoch_stats(self, P):
+        """epoch statistics on every context: J and D per branch and epoch, P epochs per branch (0 = off);
+        kept across reset()"""
+        self._ck(self.L.epvd_set_epoch_stats(self.h, int(P)))
+
+    def epoch_stats(self, counts=False):
+        """-> (samples, J, D [N-1, P, 8]) per sample, or with counts=True the closed integers (samples, J int64,
+        D Python ints in an object array): the slots and contexts of this process added as integers"""
+        P, ns = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_epoch_stats_sizes(self.h, C.byref(P), C.byref(ns)))
+        closed = np.zeros((self.B, P.value, 24), np.uint64)
+        k, f = np.zeros(max(self.B, 1), np.intc), np.zeros(max(self.B, 1), np.uint64)
+        J, D = np.zeros((self.B, P.value, 8)), np.zeros((self.B, P.value, 8))
+        self._ck(self.L.epvd_download_epoch_stats(self.h, _p(closed, C.c_uint64), _p(k, C.c_int), _p(f, C.c_uint64),
+                                                  _p(J, C.c_double), _p(D, C.c_double)))
+        ns = int(ns.value)
+        if counts:
+            return ns, closed[..., :8].astype(np.int64), \
+                closed[..., 8:16].astype(object) + closed[..., 16:24].astype(object) * (1 << 64)
+        if not ns:
+            raise DriverError("epoch statistics hold no sample")
         return ns, J, D
 
     def enable_lineage_origins(self, on=True):

@@ -82,6 +82,21 @@ def lib():
         L.epvh_domain_stats_copy.restype = None
         L.epvh_domain_stats_free.argtypes = [C.c_void_p]
         L.epvh_domain_stats_free.restype = None
+        u64p_, u32 = C.POINTER(C.c_uint64), C.c_uint32
+        L.epvh_epoch_edges.argtypes = [C.c_uint64, u32, u64p_]
+        L.epvh_epoch_edges.restype = None
+        L.epvh_epoch_close.argtypes = [u64p_, u64p_, u32, u32, u64p_]
+        L.epvh_epoch_counts_to_stats.argtypes = [u64p_, C.POINTER(C.c_int), u32, u32, C.c_uint64, dp, dp]
+        L.epvh_write_epoch_stats.argtypes = [C.c_char_p, C.c_char_p, C.c_int, u32, dp, C.POINTER(C.c_int), u64p_, u64p_,
+                                             C.c_uint64, dp]
+        L.epvh_read_epoch_stats.argtypes = [C.c_char_p]
+        L.epvh_read_epoch_stats.restype = C.c_void_p
+        L.epvh_epoch_stats_dims.argtypes = [C.c_void_p, u64p_, u64p_, u64p_, u64p_]
+        L.epvh_epoch_stats_dims.restype = None
+        L.epvh_epoch_stats_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, dp, C.POINTER(C.c_int), u64p_, dp, dp]
+        L.epvh_epoch_stats_copy.restype = None
+        L.epvh_epoch_stats_free.argtypes = [C.c_void_p]
+        L.epvh_epoch_stats_free.restype = None
         _lib = L
     return _lib
 
@@ -464,3 +479,131 @@ def read_domain_stats(path):
                     len_sum=len_sum)
     finally:
         L.epvh_domain_stats_free(h)
+
+
+# ---- epoch statistics (J and D per branch and epoch of the branch)
+def epoch_edges(fixT, P):
+    """E_p = floor(p fixT / P), p = 0 .. P-1 (uint64[P]): the epoch edges on a branch's fixed-point clock;
+    the last epoch is open-ended"""
+    out = np.zeros(int(P), np.uint64)
+    lib().epvh_epoch_edges(int(fixT), int(P), _p(out, C.c_uint64))
+    return out
+
+
+def epoch_raw_add(parts):
+    """raw parts uint64 [N-1, P, 32] (J[8], lo[8], hi[8], cov[8]) of the contexts of one genome -> their sum,
+    with part = lo + 2^32 hi renormalised to lo < 2^32 so that no word wraps however many parts are added"""
+    m = np.uint64(0xffffffff)
+    tot = None
+    for raw in parts:
+        raw = np.array(raw, np.uint64)
+        raw[..., 16:24] += raw[..., 8:16] >> np.uint64(32)
+        raw[..., 8:16] &= m
+        if tot is None:
+            tot = raw
+            continue
+        if raw.shape != tot.shape:
+            raise ValueError("raw parts of different shapes")
+        tot = tot + raw          # (J and cov modulo 2^64: cov is two's complement)
+        tot[..., 16:24] += tot[..., 8:16] >> np.uint64(32)
+        tot[..., 8:16] &= m
+    if tot is None:
+        raise ValueError("no raw part")
+    return tot
+
+
+def epoch_close(raw, fixT):
+    """raw uint64 [N-1, P, 32], fixT [N-1] -> (J int64 [N-1, P, 8], D [N-1, P, 8] Python ints in an object
+    array): the closed counts, D[p] = part[p] + (E_p+1 - E_p) sum_{q <= p} cov[q]"""
+    raw = np.ascontiguousarray(raw, np.uint64)
+    f = np.ascontiguousarray(fixT, np.uint64)
+    if raw.ndim != 3 or raw.shape[2] != 32 or f.shape != (raw.shape[0],):
+        raise ValueError("raw is [N-1, P, 32], fixT [N-1]")
+    closed = _epoch_closed_words(raw, f)
+    D = closed[..., 8:16].astype(object) + closed[..., 16:24].astype(object) * (1 << 64)
+    return closed[..., :8].astype(np.int64), D
+
+
+def _epoch_closed_words(raw, f):
+    closed = np.zeros(raw.shape[:2] + (24,), np.uint64)
+    if raw.size and lib().epvh_epoch_close(_p(raw, C.c_uint64), _p(f, C.c_uint64), raw.shape[0], raw.shape[1],
+                                           _p(closed, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return closed
+
+
+def epoch_finish(raw, fixT, k, samples, counts=False):
+    """what every sampler's epoch_stats() returns from a genome's raw part: (samples, J, D) per sample, or
+    the closed integers with counts=True"""
+    raw = np.ascontiguousarray(raw, np.uint64)
+    f = np.ascontiguousarray(fixT, np.uint64)
+    if counts:
+        return (samples,) + epoch_close(raw, f)
+    if not samples:
+        raise RuntimeError("epoch statistics hold no sample")
+    closed = _epoch_closed_words(raw, f)
+    kk = np.ascontiguousarray(k, np.intc)
+    J, D = np.zeros(raw.shape[:2] + (8,)), np.zeros(raw.shape[:2] + (8,))
+    if raw.size and lib().epvh_epoch_counts_to_stats(_p(closed, C.c_uint64), _p(kk, C.c_int), raw.shape[0], raw.shape[1],
+                                                     int(samples), _p(J, C.c_double), _p(D, C.c_double)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return samples, J, D
+
+
+def epoch_rate_factors(J, D, rates):
+    """J, D [N-1, P, 8] -> rho[N-1, P] = sum_c J / sum_c D_c rate_c: per branch and epoch the multiplier of
+    the fitted rates that maximises the likelihood of that epoch's counts (regional_rate_factor over the
+    (branch, epoch) axes); NaN where an epoch has no dwell time"""
+    J = np.ascontiguousarray(J, np.float64)
+    D = np.ascontiguousarray(D, np.float64)
+    if J.ndim != 3 or J.shape != D.shape or J.shape[2] != 8:
+        raise ValueError("J and D are [N-1, P, 8], rates [8]")
+    return regional_rate_factors(J.reshape(-1, 1, 8), D.reshape(-1, 1, 8), rates).reshape(J.shape[:2])
+
+
+def _closed_words(J, D):
+    J = np.asarray(J)
+    closed = np.zeros(J.shape[:2] + (24,), np.uint64)
+    closed[..., :8] = J.astype(np.int64).view(np.uint64)
+    Do = np.asarray(D, object)
+    closed[..., 8:16] = (Do % (1 << 64)).astype(np.uint64)
+    closed[..., 16:24] = (Do // (1 << 64)).astype(np.uint64)
+    return closed
+
+
+def write_epoch_stats(path, node_names, branches, scale_exp, fixT, samples, J, D, rates):
+    """the file of epievo_est_histories -E.  node_names, branches, scale_exp, fixT: per node, the root first;
+    J int64 [N-1, P, 8] and D (Python ints) [N-1, P, 8]: the closed counts"""
+    closed = _closed_words(J, D)
+    br = np.ascontiguousarray(branches, np.float64)
+    k = np.ascontiguousarray(scale_exp, np.intc)
+    f = np.ascontiguousarray(fixT, np.uint64)
+    r = np.ascontiguousarray(rates, np.float64)
+    if lib().epvh_write_epoch_stats(path.encode(), "\n".join(node_names).encode(), len(br), closed.shape[1],
+                                    _p(br, C.c_double), _p(k, C.c_int), _p(f, C.c_uint64), _p(closed, C.c_uint64),
+                                    int(samples), _p(r, C.c_double)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_epoch_stats(path):
+    """-> dict(samples, epochs, node_names, branches, scale_exp (non-root nodes), J int64 [N-1, P, 8], D Python
+    ints [N-1, P, 8], start [N-1, P], factor [N-1, P])"""
+    L = lib()
+    h = L.epvh_read_epoch_stats(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, P, B, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.epvh_epoch_stats_dims(h, C.byref(ns), C.byref(P), C.byref(B), C.byref(nl))
+        P, B = int(P.value), int(B.value)
+        buf = C.create_string_buffer(int(nl.value))
+        br, k = np.zeros(max(B, 1)), np.zeros(max(B, 1), np.intc)
+        closed = np.zeros((B, P, 24), np.uint64)
+        st, f = np.zeros((B, P)), np.zeros((B, P))
+        L.epvh_epoch_stats_copy(h, buf, len(buf), _p(br, C.c_double), _p(k, C.c_int), _p(closed, C.c_uint64),
+                                _p(st, C.c_double), _p(f, C.c_double))
+        D = closed[..., 8:16].astype(object) + closed[..., 16:24].astype(object) * (1 << 64)
+        return dict(samples=int(ns.value), epochs=P, node_names=buf.value.decode().split("\n"), branches=br[:B],
+                    scale_exp=k[:B], J=closed[..., :8].astype(np.int64), D=D, start=st, factor=f)
+    finally:
+        L.epvh_epoch_stats_free(h)

@@ -421,6 +421,32 @@ class ShardedSampler:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.dev.window_counts_to_stats(own, ns)
 
+    # ---- epoch statistics: every rank adds the triples centred at its owned columns
+    def enable_epoch_stats(self, P):
+        self.dev.enable_epoch_stats(P)
+
+    def reset_epoch_stats(self):
+        self.dev.reset_epoch_stats()
+
+    def accumulate_epoch_stats(self):
+        self.dev.accumulate_epoch_stats()
+
+    def epoch_stats_samples(self):
+        return self.dev.epoch_stats_samples()
+
+    def epoch_stats(self, counts=False):
+        """-> (samples, J, D [N-1, P, 8]) of the whole genome (or the closed integers), identical on every
+        rank: the ranks' raw parts are all-gathered and added as integers, then closed once"""
+        ns, own = self.dev.epoch_raw()
+        if self.comm.world > 1:
+            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
+            allw = self._gather_words(mine).view(np.uint64)
+            if any(int(w[-1]) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of epoch-statistics samples")
+            own = host.epoch_raw_add([w[:-1].reshape(own.shape) for w in allw])
+        _, k, fixT = self.dev.epoch_stats_layout()
+        return host.epoch_finish(own, fixT, k, ns, counts)
+
     # ---- lineage origin maps: every rank counts its owned columns
     def enable_lineage_origins(self, on=True):
         self.dev.enable_lineage_origins(on)
@@ -941,6 +967,39 @@ class LocalGroup:
         """-> (samples, hist [N, 2, 128], len_sum [N, 2]) over the group's owned sites, closed"""
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
+
+    # ---- epoch statistics: every shard adds the triples centred at its owned sites
+    def enable_epoch_stats(self, P):
+        self._each(lambda j, s: s.enable_epoch_stats(P))
+
+    def reset_epoch_stats(self):
+        self._each(lambda j, s: s.reset_epoch_stats())
+
+    def accumulate_epoch_stats(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            raise RuntimeError("reset() the group before taking an epoch-statistics sample")
+        self._each(lambda j, s: s.accumulate_epoch_stats())
+
+    def epoch_stats_samples(self):
+        return self.subs[0].epoch_stats_samples()
+
+    def epoch_stats_layout(self):
+        return self.subs[0].epoch_stats_layout()
+
+    def epoch_raw(self):
+        """-> (samples, uint64 [N-1, P, 32]): the shards' raw parts, added as integers"""
+        parts = self._each(lambda j, s: s.epoch_raw())
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of epoch-statistics samples")
+        return ns, host.epoch_raw_add([p[1] for p in parts])
+
+    def epoch_stats(self, counts=False):
+        """-> (samples, J, D [N-1, P, 8]) or the closed integers: added over the shards as integers, then
+        closed once"""
+        ns, raw = self.epoch_raw()
+        _, k, fixT = self.epoch_stats_layout()
+        return host.epoch_finish(raw, fixT, k, ns, counts)
 
     def counters(self):
         out = {}

@@ -35,6 +35,7 @@ class _Counters(C.Structure):
 
 
 MAX_CAPACITY = 2047    # EPV_MAX_CAP: jump slots per (site, branch)
+EPOCH_MAX_P = 256      # EPV_EPOCH_MAX_P: epochs per branch of the epoch statistics
 
 ABI_SYMBOLS = [
     "epv_create", "epv_destroy", "epv_last_error", "epv_set_tree", "epv_set_model",
@@ -56,6 +57,8 @@ ABI_SYMBOLS = [
     "epv_get_branch_event_windows",
     "epv_set_window_stats", "epv_reset_window_stats", "epv_accumulate_window_stats", "epv_window_stats_samples",
     "epv_window_stats_set_samples", "epv_window_stats_scale_exps", "epv_window_stats_layout", "epv_get_window_stats", "epv_window_counts_to_stats",
+    "epv_set_epoch_stats", "epv_reset_epoch_stats", "epv_accumulate_epoch_stats", "epv_epoch_stats_samples",
+    "epv_epoch_stats_set_samples", "epv_epoch_stats_layout", "epv_get_epoch_stats",
     "epv_set_lineage_origins", "epv_reset_lineage_origins", "epv_accumulate_lineage_origins",
     "epv_lineage_origins_samples", "epv_lineage_origins_set_samples", "epv_lineage_origins_layout",
     "epv_lineage_origin_rows", "epv_lineage_origins_scale_exp", "epv_get_lineage_origins",
@@ -164,6 +167,13 @@ def lib():
         L.epv_window_stats_layout.argtypes = [vp, u64p, u64p, u64p]
         L.epv_get_window_stats.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]
         L.epv_window_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, dp, dp]
+        L.epv_set_epoch_stats.argtypes = [vp, C.c_uint32]
+        L.epv_reset_epoch_stats.argtypes = [vp]
+        L.epv_accumulate_epoch_stats.argtypes = [vp]
+        L.epv_epoch_stats_samples.argtypes = [vp, u64p]
+        L.epv_epoch_stats_set_samples.argtypes = [vp, C.c_uint64]
+        L.epv_epoch_stats_layout.argtypes = [vp, u32p, u32p, C.POINTER(C.c_int), u64p]
+        L.epv_get_epoch_stats.argtypes = [vp, u64p]
         L.epv_set_lineage_origins.argtypes = [vp, C.c_int]
         L.epv_reset_lineage_origins.argtypes = [vp]
         L.epv_accumulate_lineage_origins.argtypes = [vp]
@@ -817,6 +827,50 @@ class DeviceSampler:
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
+    # ---- epoch statistics (epv_set_epoch_stats)
+    def enable_epoch_stats(self, P):
+        """add J and D per branch and epoch (P epochs per branch) after every batch sweep of run_mcmc (0 = off)"""
+        P = int(P)
+        if P < 0 or P > EPOCH_MAX_P:
+            raise ValueError("1 .. %d epochs per branch (0 turns the statistics off)" % EPOCH_MAX_P)
+        self._ck(self.L.epv_set_epoch_stats(self.h, P))
+
+    def reset_epoch_stats(self):
+        self._ck(self.L.epv_reset_epoch_stats(self.h))
+
+    def accumulate_epoch_stats(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_epoch_stats(self.h))
+
+    def epoch_stats_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_epoch_stats_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def epoch_stats_layout(self):
+        """(P, k_b int[N-1], fixT_b uint64[N-1]) of the accumulator's samples; (0, [], []) when off"""
+        B, P = C.c_uint32(0), C.c_uint32(0)
+        k, f = np.zeros(max(self.B, 1), np.intc), np.zeros(max(self.B, 1), np.uint64)
+        self._ck(self.L.epv_epoch_stats_layout(self.h, C.byref(B), C.byref(P), _p(k, C.c_int), _p(f, C.c_uint64)))
+        return int(P.value), k[:int(B.value)], f[:int(B.value)]
+
+    def epoch_raw(self):
+        """-> (samples, uint64 [N-1, P, 32]): this context's raw part (J[8], lo[8], hi[8], cov[8]); raw parts
+        of the contexts of a genome add up (host.epoch_raw_add) and are closed once (host.epoch_close)"""
+        P = self.epoch_stats_layout()[0]
+        if not P:
+            self._ck(self.L.epv_get_epoch_stats(self.h, None))     # off: EPV_ERR_STATE
+        out = np.zeros((self.B, P, 32), np.uint64)
+        self._ck(self.L.epv_get_epoch_stats(self.h, _p(out, C.c_uint64)))
+        return self.epoch_stats_samples(), out
+
+    def epoch_stats(self, counts=False):
+        """-> (samples, J[N-1, P, 8], D[N-1, P, 8]) averaged over the samples (D in time units), or with
+        counts=True the closed integers: J int64, D Python ints (object array) in units of 2^-k_b"""
+        ns, raw = self.epoch_raw()
+        _, k, fixT = self.epoch_stats_layout()
+        return host.epoch_finish(raw, fixT, k, ns, counts)
+
 
 class SingleSiteSampler:
     """Mirror of the reference class (SingleSiteSampler.hpp:35-81).
@@ -990,3 +1044,19 @@ class SingleSiteSampler:
 
     def domain_stats(self):
         return self.dev.domain_stats()
+
+    # epoch statistics (DeviceSampler.enable_epoch_stats)
+    def enable_epoch_stats(self, P):
+        self.dev.enable_epoch_stats(P)
+
+    def reset_epoch_stats(self):
+        self.dev.reset_epoch_stats()
+
+    def accumulate_epoch_stats(self):
+        self.dev.accumulate_epoch_stats()
+
+    def epoch_stats_samples(self):
+        return self.dev.epoch_stats_samples()
+
+    def epoch_stats(self, counts=False):
+        return self.dev.epoch_stats(counts)

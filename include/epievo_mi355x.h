@@ -607,6 +607,48 @@ int epv_domain_stats_layout(epv_ctx *ctx, uint32_t *n_nodes, uint32_t *n_bins, u
                             uint64_t *chunk_sites);
 int epv_get_domain_stats(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
 
+/* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
+ * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
+ * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and
+ * D[8] for every branch b and epoch p = 0 .. P-1 over the triples the whole-genome statistics count (centre
+ * site interior and owned).  Everything is defined on the triple's own fixed-point clock, so the result is
+ * integers only:  with the branch's scale 2^k_b and fixT_b = llrint(T_b 2^k_b) (< 2^50) the epoch edges are
+ * E_p = floor(p fixT_b / P), E_P = +inf (the last epoch absorbs any overshoot), bin(c) = the largest
+ * p <= P-1 with E_p <= c.  A triple's events are walked in the order and with the tie rules of the
+ * whole-genome statistics, with an integer clock c from 0: an interval adds F = rint((t - prev) 2^k_b), the
+ * integer those statistics add for it, and occupies [c, c + F); D[b][p][ctx] receives its overlap with
+ * [E_p, E_p+1); then c += F, and a jump of the centre site at the interval's end adds 1 to
+ * J[b][bin(c)][ctx before the jump].  The clock differs from real time by at most 3072 quanta (about 1e-9 of
+ * a branch), and sum_p D[b][p][ctx] equals the whole-genome integer exactly: summed over the epochs the
+ * closed result equals, bit for bit, the sum over the batch sweeps of the counts epv_run_mcmc_counts
+ * returns.  Samples and lifecycle are the window statistics': a sample after each batch sweep of epv_run_mcmc
+ * / _sums / _counts (not the burn-in) or one epv_accumulate_epoch_stats call; kept over epv_reset,
+ * epv_set_model, capacity growth, masks, evidence and epv_sweep_phase; the scales of the first sample are
+ * remembered and a sample under other scales is EPV_ERR_STATE until epv_reset_epoch_stats; a failed launch
+ * counts no sample.  Off (the default) allocates and launches nothing; J, D, accept counts, paths, tri_llh
+ * and the plan word do not depend on it.
+ * The context keeps a RAW difference form that is linear -- contexts, shards and GPUs of a genome add their
+ * raw parts word by word as integers -- and is closed once on the host (epvh_epoch_close, libepv_host):
+ * raw[b][p][32] uint64 = J[8], lo[8], hi[8], cov[8]; part = lo + 2^32 hi holds the pieces of the two end
+ * bins of every interval, cov (two's complement) +1 where an interval starts to cover whole bins and -1
+ * where that ends; D[p] = part[p] + (E_p+1 - E_p) sum_{q <= p} cov[q].  256 bytes per branch and epoch.
+ * Cap: every raw word receives at most one addend below 2^32 per block of sites and sample, so a sample, or
+ *   a run whose batch would get there, is EPV_ERR_STATE when addends + batch x blocks >= 2^32 (blocks =
+ *   ceil(owned sites / sites per block), at least 256 sites per block; addends = the blocks of every sample
+ *   taken so far, samples x blocks while the owned range stays; a run is refused before its first sweep).  epv_epoch_stats_set_samples (a test hook) overwrites the sample count, with the remembered
+ *   scales as epv_window_stats_set_samples does.
+ * epv_epoch_stats_layout: B = N-1 and P (0, 0 when off); k[b-1] = k_b and fixT[b-1] = fixT_b of the
+ *   accumulator's samples (of the context's current scales while it holds none); k and fixT may be null.
+ * epv_get_epoch_stats: raw[B][P][32], this context's contribution. */
+#define EPV_EPOCH_MAX_P 256u
+int epv_set_epoch_stats(epv_ctx *ctx, uint32_t P);
+int epv_reset_epoch_stats(epv_ctx *ctx);
+int epv_accumulate_epoch_stats(epv_ctx *ctx);
+int epv_epoch_stats_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_epoch_stats_set_samples(epv_ctx *ctx, uint64_t n_samples);
+int epv_epoch_stats_layout(epv_ctx *ctx, uint32_t *B, uint32_t *P, int *k, uint64_t *fixT);
+int epv_get_epoch_stats(epv_ctx *ctx, uint64_t *raw);
+
 /* Timing hook for bench.py: average duration (ms) of the colour-phase kernel launches
  * issued since the last call, measured with HIP events on the context's stream, and
  * how many launches that covers.  epv_set_timing(ctx, N): 0 = off, N >= 1 = events around every

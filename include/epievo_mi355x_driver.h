@@ -125,6 +125,16 @@ int epvd_download_domain_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum
 int epvd_download_domain_stats(epvd_sampler *s, uint32_t n_nodes, uint64_t *hist, uint64_t *len_sum,
                                uint64_t *n_samples);
 
+/* epoch statistics (epv_set_epoch_stats on every context, P = 0: off; kept across epvd_reset, which starts
+ * the sums from zero).  Sizes first: P and the sample count; then the copy of the closed counts
+ * closed[((b-1) * P + p) * 24 + ..] (uint64: J[8], then D[8] as 128-bit integers, low words [8] and high words
+ * [8]) -- the raw parts of all slots and contexts of this process added as integers and closed once --, of
+ * k[b-1] = k_b and fixT[b-1] = fixT_b, and, where J and D are not null and samples were taken,
+ * J, D[((b-1) * P + p) * 8 + c] per sample, D in time units.  closed, k and fixT may be null. */
+int epvd_set_epoch_stats(epvd_sampler *s, uint32_t P);
+int epvd_epoch_stats_sizes(epvd_sampler *s, uint32_t *P, uint64_t *n_samples);
+int epvd_download_epoch_stats(epvd_sampler *s, uint64_t *closed, int *k, uint64_t *fixT, double *J, double *D);
+
 #ifdef __cplusplus
 }
 #endif
