@@ -2012,6 +2012,86 @@ EPV_API int epv_math_kat(epv_ctx *c, uint32_t op, uint32_t where, uint32_t n, co
   return EPV_OK;
 }
 
+// known-answer entry for the three-way merge of a triple's jumps: item i = three paths of up to 8 jumps on
+// one branch.  heads[i] = start states (bit 0 left, 1 middle, 2 right) | jump counts << 4, << 8, << 12;
+// times[25 i + 8 col + k] = jump k of column col, times[25 i + 24] = the branch length.  A first kernel lays
+// the times out as the jump store does (jump k of a path at j[k * n]); a second one runs merge3<Acc8> (the
+// untouched form) and merge3_sel<AccLds> (heads loaded in one predicated batch first, as
+// triple_llh_cached<NB > 0> does) on every item.  d_out / j_out[16 i + 8 form + ctx], form 0 = merge3.
+// Like the two entries above this checks the function in a kernel of its own (one lane per item), not a
+// call site inside the MCMC kernels.
+#define EPV_MERGE_KAT_CAP 8u
+__global__ void epv_merge_kat_layout_kernel(uint32_t n, const double *times, double *store) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  for (uint32_t q = 0; q < 3u * EPV_MERGE_KAT_CAP; ++q) store[(size_t)q * n + i] = times[25u * (size_t)i + q];
+}
+
+__global__ void __launch_bounds__(64) epv_merge_kat_kernel(uint32_t n, const uint32_t *heads, const double *times,
+                                                           const double *store, double *d_out, uint32_t *j_out) {
+  __shared__ double s_d[8 * 64];
+  __shared__ uint32_t s_j[8 * 64];
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t h = heads[i];
+  const double blen = times[25u * (size_t)i + 24u];
+  PathRef P[3];
+  for (uint32_t col = 0; col < 3u; ++col) {
+    P[col].j = store + (size_t)col * EPV_MERGE_KAT_CAP * n + i;
+    P[col].nj = (h >> (4u + 4u * col)) & 15u;
+    P[col].init = (h >> col) & 1u;
+  }
+  Acc8 A8;
+  acc_clear(A8);
+  merge3(P[0], P[1], P[2], (uint64_t)n, blen, A8);
+  AccLds AL;
+  AL.d = s_d + threadIdx.x; AL.j = s_j + threadIdx.x; AL.stride = 64u;
+  acc_clear(AL);
+  const double tl = P[0].nj ? P[0].j[0] : EPV_INF, tm = P[1].nj ? P[1].j[0] : EPV_INF, tr = P[2].nj ? P[2].j[0] : EPV_INF;
+  merge3_sel(P[0], P[1], P[2], tl, tm, tr, (uint64_t)n, blen, AL);
+  for (int c = 0; c < 8; ++c) {
+    d_out[16u * (size_t)i + c] = acc_d(A8, c); j_out[16u * (size_t)i + c] = acc_j(A8, c);
+    d_out[16u * (size_t)i + 8u + c] = acc_d(AL, c); j_out[16u * (size_t)i + 8u + c] = acc_j(AL, c);
+  }
+}
+
+EPV_API int epv_merge_kat(epv_ctx *c, uint32_t n, const uint32_t *heads, const double *times, double *d_out, uint32_t *j_out) {
+  if (!c || !heads || !times || !d_out || !j_out || !n || n > (1u << 20)) return EPV_ERR_ARG;
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t col = 0; col < 3u; ++col)
+    {
+      // (a finite time on every jump is what keeps a merge on paths that still have one: an item that
+      // breaks it would walk off its column)
+      const uint32_t nj = (heads[i] >> (4u + 4u * col)) & 15u;
+      if (nj > EPV_MERGE_KAT_CAP) return EPV_ERR_ARG;
+      for (uint32_t k = 0; k < nj; ++k)
+        if (!(std::fabs(times[25u * (size_t)i + 8u * col + k]) < EPV_INF)) return EPV_ERR_ARG;
+    }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one allocation: times [25 n] | store [24 n] | d_out [16 n] doubles, then heads [n] | j_out [16 n] words
+  const size_t nd = (size_t)n * (25u + 24u + 16u), nw = (size_t)n * 17u;
+  double *d_buf = nullptr;
+  HIP_TRY(c, hipMalloc(&d_buf, nd * sizeof(double) + nw * sizeof(uint32_t)));
+  double *d_times = d_buf, *d_store = d_buf + (size_t)n * 25u, *d_d = d_store + (size_t)n * 24u;
+  uint32_t *d_heads = reinterpret_cast<uint32_t *>(d_buf + nd), *d_j = d_heads + n;
+  hipError_t e = hipMemcpyAsync(d_times, times, (size_t)n * 25u * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_heads, heads, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    epv_merge_kat_layout_kernel<<<(n + 255u) / 256u, 256, 0, c->stream>>>(n, d_times, d_store);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    epv_merge_kat_kernel<<<(n + 63u) / 64u, 64, 0, c->stream>>>(n, d_heads, d_times, d_store, d_d, d_j);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_d, (size_t)n * 16u * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(j_out, d_j, (size_t)n * 16u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_buf);
+  if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_merge_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
 EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
   if (!c) return EPV_ERR_ARG;
   if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_unobserved");

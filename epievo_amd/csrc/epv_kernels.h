@@ -218,6 +218,49 @@ __device__ __forceinline__ void merge3_pre(const PathRef &L, const PathRef &M, c
   acc_add(A, ctx, tot_time - prev, false);
 }
 
+// merge3_pre with ONE body per event instead of three divergent arms (same contract, same events in the
+// same order under the same tie rules, the same acc_add calls).  A wave runs an iteration as long as any
+// lane has an event left, and on a branch's first iteration its lanes spread over all three arms: the
+// three-arm form then executes three LDS read-modify-writes, three loads and three waits one after the
+// other.  Here the advancing path is chosen by two compares; its time, context flip, remaining count and
+// address are selects; one acc_add and one predicated load (the path's next jump, +inf past its last)
+// follow, and selects write the three heads back.  The address runs ahead by n elements per step (no
+// i * n product: 64-bit multiplies are quarter-rate).
+// Written with if / else around the assignments the compiler splits the body into three arms again;
+// what keeps it whole is pure ternaries plus the two empty asm statements, which pin the advancing
+// path's remaining count and the loaded value in a register at that point.  (The pointer is NOT pinned:
+// that would lose its address space and turn the load into a flat one, which waits on the LDS counter.)
+template <class ACC>
+__device__ __forceinline__ void merge3_sel(const PathRef &L, const PathRef &M, const PathRef &R, double tl, double tm,
+                                           double tr, uint64_t n, double tot_time, ACC &A) {
+  int ctx = (int)(4u * L.init + 2u * M.init + R.init);
+  double prev = 0.0;
+  uint32_t nl = L.nj, nm = M.nj, nr = R.nj;          // jumps left on each path, its head included
+  const double *pl = L.j, *pm = M.j, *pr = R.j;      // address of each path's head
+  while (nl | nm | nr) {
+    const bool left = tl < (tm < tr ? tm : tr);
+    const bool mid = !left && tm < tr;
+    const double t = left ? tl : mid ? tm : tr;
+    const int flip = left ? 4 : mid ? 2 : 1;
+    uint32_t rem = (left ? nl : mid ? nm : nr) - 1u;
+    const double *p = (left ? pl : mid ? pm : pr) + n;
+    acc_add(A, ctx, t - prev, mid);
+    prev = t; ctx ^= flip;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(rem));
+#endif
+    double nx = EPV_INF;
+    if (rem) nx = *p;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(nx));
+#endif
+    tl = left ? nx : tl; nl = left ? rem : nl; pl = left ? p : pl;
+    tm = mid ? nx : tm; nm = mid ? rem : nm; pm = mid ? p : pm;
+    tr = (left || mid) ? tr : nx; nr = (left || mid) ? nr : rem; pr = (left || mid) ? pr : p;
+  }
+  acc_add(A, ctx, tot_time - prev, false);
+}
+
 // path_log_likelihood (SingleSiteSampler.cpp:374-391): un-logged root prior (reference
 // quirk) + sum_c J_c log(rate_c) - D_c rate_c over all branches of one triple.
 // (bl,sl),(bm,sm),(br,sr) = (buffer, site) of the left / middle / right column.
@@ -284,7 +327,7 @@ __device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const doubl
       L.j = jl + (uint64_t)b * Cn; L.nj = wl[b] & EPV_NJ_MASK; L.init = wl[b] >> EPV_INIT_SHIFT;
       M.j = jm + (uint64_t)b * Cn; M.nj = wm[b] & EPV_NJ_MASK; M.init = wm[b] >> EPV_INIT_SHIFT;
       R.j = jr + (uint64_t)b * Cn; R.nj = wr[b] & EPV_NJ_MASK; R.init = wr[b] >> EPV_INIT_SHIFT;
-      merge3_pre(L, M, R, tl[b], tm[b], tr[b], n, s_blen[b + 1], A);
+      merge3_sel(L, M, R, tl[b], tm[b], tr[b], n, s_blen[b + 1], A);
     }
   } else
   for (uint32_t b = 0; b < B; ++b) {

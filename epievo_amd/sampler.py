@@ -48,7 +48,7 @@ ABI_SYMBOLS = [
     "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
     "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
     "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan", "epv_philox_kat", "epv_math_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
+    "epv_phase_plan", "epv_philox_kat", "epv_math_kat", "epv_merge_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
     "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
     "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
     "epv_get_path_average", "epv_path_average_layout",
@@ -135,6 +135,7 @@ def lib():
         L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.epv_philox_kat.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, dp]
         L.epv_math_kat.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, dp]
+        L.epv_merge_kat.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), dp, dp, C.POINTER(C.c_uint32)]
         L.epv_set_unobserved.argtypes = [vp, u8p]
         L.epv_unobserved_cells.argtypes = [vp, u64p]
         L.epv_set_leaf_evidence.argtypes = [vp, C.POINTER(C.c_float)]
@@ -313,6 +314,30 @@ class DeviceSampler:
         out = np.zeros((x.shape[0], 6))
         self._ck(self.L.epv_math_kat(self.h, int(op), int(where), x.shape[0], _p(inp, C.c_double), _p(out, C.c_double)))
         return out
+
+    def merge_kat(self, items):
+        """the three-way merge of a triple's jumps on known inputs (epv_merge_kat): items[i] = (start states
+        (l, m, r), (left times, middle times, right times) with 0 .. 8 each, branch length).  Returns
+        (D [i, form, 8] doubles, J [i, form, 8] uint32), form 0 = merge3 with register accumulators,
+        1 = merge3_sel with LDS accumulators behind the batched first-jump load."""
+        n = len(items)
+        heads = np.zeros(n, np.uint32)
+        times = np.zeros((n, 25))
+        for i, (init, cols, blen) in enumerate(items):
+            h = 0
+            for c in range(3):
+                k = len(cols[c])
+                if k > 8:
+                    raise ValueError("merge_kat: at most 8 jumps per column")
+                h |= (int(init[c]) & 1) << c | k << (4 + 4 * c)
+                times[i, 8 * c:8 * c + k] = cols[c]
+            heads[i] = h
+            times[i, 24] = blen
+        D = np.zeros((n, 2, 8))
+        J = np.zeros((n, 2, 8), np.uint32)
+        self._ck(self.L.epv_merge_kat(self.h, n, _p(heads, C.c_uint32), _p(times, C.c_double), _p(D, C.c_double),
+                                      _p(J, C.c_uint32)))
+        return D, J
 
     def set_unobserved(self, mask):
         """missing leaf data (epv_set_unobserved): mask[b-1, s] != 0 -> the leaf end state of branch b at

@@ -183,6 +183,22 @@ int epv_philox_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *coun
  * inside the MCMC kernels -- that is what the comparisons of whole runs against the oracle establish. */
 int epv_math_kat(epv_ctx *ctx, uint32_t op, uint32_t where, uint32_t n, const double *in, double *out);
 
+/* Known-answer entry for the three-way merge of a triple's jumps on one branch (the sufficient statistics
+ * D[8], J[8] of the acceptance stage), for tests: n <= 2^20 items, item i = three paths of 0 .. 8 jumps.
+ *   heads[i]               start states (bit 0 left, bit 1 middle, bit 2 right) | left count << 4 |
+ *                          middle count << 8 | right count << 12
+ *   times[25 i + 8 c + k]  jump k of column c (0 left, 1 middle, 2 right), finite; times[25 i + 24] the
+ *                          branch length
+ * The device lays the times out with a stride as the jump store does and runs, one lane per item,
+ *   form 0  merge3 with register accumulators (what the statistics and the generic acceptance call), and
+ *   form 1  merge3_sel with accumulators in LDS, the heads loaded in one predicated batch before it
+ *           (what the fused small-tree acceptance calls);
+ * d_out[16 i + 8 form + ctx] and j_out[16 i + 8 form + ctx] are the two results.  As with the two entries
+ * above, this checks the functions in a kernel of their own; it does not show what the compiler makes of
+ * a call site inside the MCMC kernels -- that is what the comparisons of whole runs against the oracle
+ * establish. */
+int epv_merge_kat(epv_ctx *ctx, uint32_t n, const uint32_t *heads, const double *times, double *d_out, uint32_t *j_out);
+
 /* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
  * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
  * instead of the indicator of the path's end state) instead of pinning it.  The node-major layout
