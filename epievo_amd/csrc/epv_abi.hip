@@ -80,6 +80,11 @@ struct epv_ctx {
   uint64_t phases_used = 0;              // colour phases run since the halos were fresh
   // device allocations
   EpvModelConst *d_model = nullptr;
+  // epv_set_model is stream-ordered: the constants leave from one of two pinned slots, taken in turn; a slot is
+  // written again only after the copy that last read it has passed (its event)
+  EpvModelConst *h_model = nullptr;          // [2], pinned
+  hipEvent_t ev_model[2] = {nullptr, nullptr};
+  uint32_t model_slot = 0;
   uint32_t *d_parent = nullptr, *d_subtree = nullptr;
   double *d_blen = nullptr;
   unsigned long long *d_counters = nullptr;
@@ -90,6 +95,8 @@ struct epv_ctx {
   uint64_t partial_cap[2] = {0, 0};   // doubles allocated in d_partial[0], [1]
   unsigned long long *d_sweep_tot = nullptr;  // [sweep][B*16] integer statistics of the batch sweeps
   uint64_t sweep_tot_cap = 0;                 // sweeps allocated
+  long long *h_tot = nullptr;                 // pinned staging of epv_run_mcmc_counts' totals (one wait for all it reads)
+  uint64_t h_tot_cap = 0;                     // words
   double *d_statscale = nullptr;              // [N] 2^k_b of the fixed-point dwell times (epv_suffstat_kernel)
   std::vector<double> statscale;              // host copy; refreshed when the tree or the genome length changes
   double *d_scale = nullptr;
@@ -1643,6 +1650,9 @@ EPV_API void epv_destroy(epv_ctx *c) {
   dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
+  if (c->h_tot) (void)hipHostFree(c->h_tot);
+  if (c->h_model) (void)hipHostFree(c->h_model);
+  for (hipEvent_t &e : c->ev_model) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t &e : c->ev_copy) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   dfree(c->d_cnt_snap);
   for (auto &p : c->ev_pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
@@ -1706,8 +1716,17 @@ EPV_API int epv_set_model(epv_ctx *c, const double *triplet_rates, const double 
   }
   for (int i = 0; i < 4; ++i) c->model.T[i] = T[i];
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (a kernel of epv_reset_async may still read the old constants)
-  HIP_TRY(c, hipMemcpy(c->d_model, &c->model, sizeof(EpvModelConst), hipMemcpyHostToDevice));
+  // stream-ordered: the kernels already queued read the old constants, those launched after this call the new
+  // ones, and the host waits for neither.  The copy leaves from a pinned slot; the two slots take turns, and a
+  // slot is written only after the copy that last read it has passed.
+  if (!c->h_model) HIP_TRY(c, hipHostMalloc(&c->h_model, 2u * sizeof(EpvModelConst)));
+  const uint32_t slot = c->model_slot;
+  if (!c->ev_model[slot]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_model[slot], hipEventDisableTiming));
+  else HIP_TRY(c, hipEventSynchronize(c->ev_model[slot]));
+  c->h_model[slot] = c->model;
+  HIP_TRY(c, hipMemcpyAsync(c->d_model, &c->h_model[slot], sizeof(EpvModelConst), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->ev_model[slot], c->stream));
+  c->model_slot = slot ^ 1u;
   c->S.model = c->d_model;
   c->have_model = true;
   c->have_reset = false;
@@ -2698,10 +2717,35 @@ EPV_API int epv_run_mcmc_sums(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint
   return rc ? rc : src;
 }
 
+// what epv_run_mcmc_counts hands back, fetched with ONE wait: the accept counters as they stood when the batch
+// sweeps began, the final counters and the sweep totals leave as three stream-ordered copies into pinned memory
+static int finish_counts(epv_ctx *c, uint64_t batch, int64_t *counts, uint64_t *n_accepted) {
+  const uint64_t words = batch * c->S.B * 16u;
+  if (words > c->h_tot_cap) {
+    if (c->h_tot) HIP_TRY(c, hipHostFree(c->h_tot));
+    c->h_tot = nullptr;
+    c->h_tot_cap = 0;
+    HIP_TRY(c, hipHostMalloc(&c->h_tot, words * sizeof(long long)));
+    c->h_tot_cap = words;
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->h_cnt_snap, c->d_cnt_snap, sizeof(unsigned long long) * EPV_CNT_WORDS,
+                            hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_tot, c->d_sweep_tot, words * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  uint64_t total = 0;
+  const int rc = finish_mcmc(c, &total, 0);      // the final counters; synchronises the stream
+  if (rc && rc != EPV_ERR_CAPACITY) return rc;   // (an overflow leaves complete outputs)
+  uint64_t base = 0;
+  for (uint32_t sh = 0; sh < EPV_SHARDS; ++sh) base += c->h_cnt_snap[EPV_CNT_IDX(EPV_CNT_ACCEPT, sh)];
+  if (n_accepted) *n_accepted = total - base;
+  std::memcpy(counts, c->h_tot, words * sizeof(long long));
+  return rc;
+}
+
 // ---- a context that shares its GPU with others (the sharded drivers).  Its statistics run as
-// one-wave blocks (they fit into the LDS the colour phases leave free); the waves of a 256-site block
-// add into its row of d_partial[0] ([w][owned block][16 B], zeroed first), and one reduction after the
-// last sweep leaves the per-sweep totals in d_sweep_tot
+// one-wave blocks (they fit into the LDS the colour phases leave free); the waves add into EPV_STATW_ROWS
+// rows per sweep of d_partial[0] ([w][row][16 B], zeroed first; a 256-site block adds into row block % rows,
+// so a word takes a few dozen adds per launch, not thousands), and one reduction after the last sweep leaves
+// the per-sweep totals in d_sweep_tot
 EPV_API int epv_run_mcmc_counts(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base,
                                 int64_t *counts, uint64_t *n_accepted) {
   int rc = check_ready(c, true);
@@ -2714,19 +2758,18 @@ EPV_API int epv_run_mcmc_counts(epv_ctx *c, uint64_t burn_in, uint64_t batch, ui
   const uint64_t blk_lo = own_lo / 256u, n_own = own_hi / 256u - blk_lo + 1u;
   if ((rc = ensure_stat_scale(c))) return rc;
   if ((rc = ensure_sweep_tot(c, batch))) return rc;
-  if ((rc = ensure_partials(c, batch * n_own))) return rc;
+  const uint32_t n_rows = (uint32_t)std::min<uint64_t>(n_own, EPV_STATW_ROWS);
+  if ((rc = ensure_partials(c, batch * n_rows))) return rc;
   unsigned long long *rows = (unsigned long long *)c->d_partial[0];
-  HIP_TRY(c, hipMemsetAsync(rows, 0, batch * n_own * V * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(rows, 0, batch * n_rows * V * sizeof(unsigned long long), c->stream));
   rc = run_chain(c, burn_in, batch, seed, sweep_base, [&](uint64_t w) {
     hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
-                       dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows + w * n_own * V);
+                       dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows + w * n_rows * V, n_rows);
     return EPV_OK;
   });
   if (rc) return rc;
-  if ((rc = reduce_blocks_to_tot(c, rows, n_own, batch, 0u))) return rc;
-  rc = finish_mcmc_snapshot(c, n_accepted);  // synchronises the stream
-  const int src = read_sweep_tot(c, batch, counts);
-  return rc ? rc : src;
+  if ((rc = reduce_blocks_to_tot(c, rows, n_rows, batch, 0u))) return rc;   // (at most 1024 rows: one stage)
+  return finish_counts(c, batch, counts, n_accepted);
 }
 
 EPV_API int epv_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64_t batch, int average, double *J, double *D) {

@@ -1860,10 +1860,15 @@ __global__ __launch_bounds__(256) void epv_suffstat_kernel(EpvDev S, uint64_t fi
 // out, while a one-wave block slips into the gap.  64 sites and up to EPV_STATW_BCH branches per
 // block; neighbours' meta words through LDS, no block barrier; the four waves of a 256-site block add
 // their sums into the block's row of `partial` with 64-bit atomics (the row must be zero: integer sums
-// commute, so the result is the one of epv_suffstat_kernel).
+// commute, so the result is the one of epv_suffstat_kernel).  `partial` has n_rows rows, block i adds into
+// row i % n_rows: with EPV_STATW_ROWS rows a launch of 5 000 waves puts about 80 adds on a word, spread over
+// its run time (no-return atomics, nobody waits for them), and the rows of a whole batch stay small enough
+// to be zeroed and summed in passing (50 sweeps x 64 rows x 16 B words: 1.3 MB at B = 4).
 #define EPV_STATW_BCH 8u
+#define EPV_STATW_ROWS 64u
 __global__ __launch_bounds__(64) void epv_suffstat_wave_kernel(EpvDev S, uint64_t first, uint64_t last, uint64_t block0,
-                                                               const double *statscale, unsigned long long *partial) {
+                                                               const double *statscale, unsigned long long *partial,
+                                                               uint32_t n_rows) {
   __shared__ unsigned long long s_acc[EPV_STATW_BCH * 16u];
   __shared__ uint32_t s_cnt[EPV_STATW_BCH * 8u];
   __shared__ epv_meta_t s_meta[66];
@@ -1956,7 +1961,7 @@ __global__ __launch_bounds__(64) void epv_suffstat_wave_kernel(EpvDev S, uint64_
   if (t < tail - head) merge_item((head + t) & 127u);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  const uint64_t row = (site0 - block0 * 256u) / 256u;      // the 256-site block this wave belongs to
+  const uint64_t row = ((site0 - block0 * 256u) / 256u) % n_rows;      // the 256-site block this wave belongs to, folded
   for (uint32_t i = t; i < (b_hi - b_lo) * 16u; i += 64u) {
     const uint32_t bl = i >> 4, c = i & 15u, b = b_lo + bl;
     unsigned long long v = s_acc[i];

@@ -3,7 +3,10 @@
 #include "epv_epochs.hpp"
 
 #include <algorithm>
+#include <condition_variable>
 #include <cstdlib>
+#include <exception>
+#include <mutex>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -18,16 +21,6 @@ namespace epv {
 namespace {
 const uint64_t kBlock = 256;   // sites per block: the unit of part cuts and halo widths
 const uint32_t kMaxCap = 2047;   // EPV_MAX_CAP: 2 C + 1 segments must fit the 12-bit segment field of the Philox address
-
-// worker threads that are joined on every exit path: if starting thread i + 1 throws
-// (std::system_error on thread exhaustion), the i threads already running are joined before the
-// exception leaves the scope instead of taking the process down through std::terminate
-struct ThreadGroup {
-  std::vector<std::thread> th;
-  template <class F> void spawn(F &&f) { th.emplace_back(std::forward<F>(f)); }
-  void join() { for (std::thread &t : th) if (t.joinable()) t.join(); }
-  ~ThreadGroup() { join(); }
-};
 
 uint64_t round_to(double x, uint64_t unit) { return (uint64_t)(x / (double)unit + 0.5) * unit; }
 
@@ -97,6 +90,78 @@ FlatPaths concat_sites(const std::vector<FlatPaths> &parts) {
   return q;
 }
 }  // namespace
+
+// One persistent host thread per part, started when a call first needs it and kept until the sampler goes:
+// run(P, f) hands f(p) to worker p for p < P and returns when all of them are back -- what a spawn and a join
+// of P fresh threads did on every run_mcmc, sweeps and download, without the thread start-up between the end of
+// one E-step and the first launch of the next.  A part stays with its thread (a HIP thread keeps its device).
+// An exception that leaves f(p) is carried over and rethrown by run (the first by part index) after every
+// worker has finished; if a thread cannot be started, run throws before any work was handed out.
+class SingleSiteSampler::Workers {
+public:
+  ~Workers() {
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      stop_ = true;
+    }
+    work_.notify_all();
+    for (std::thread &t : th_) t.join();
+  }
+  void run(size_t P, const std::function<void(size_t)> &f) {
+    if (P == 0) return;
+    std::unique_lock<std::mutex> lk(m_);
+    while (th_.size() < P) {
+      const size_t i = th_.size();
+      const uint64_t g0 = gen_;
+      th_.emplace_back([this, i, g0] { loop(i, g0); });
+    }
+    errs_.assign(P, nullptr);
+    f_ = &f;
+    n_ = P;
+    pending_ = P;
+    ++gen_;
+    work_.notify_all();
+    done_.wait(lk, [this] { return pending_ == 0; });
+    f_ = nullptr;
+    n_ = 0;
+    for (std::exception_ptr &e : errs_)
+      if (e) std::rethrow_exception(e);
+  }
+
+private:
+  void loop(size_t i, uint64_t seen) {
+    std::unique_lock<std::mutex> lk(m_);
+    for (;;) {
+      work_.wait(lk, [&] { return stop_ || (gen_ != seen && i < n_); });
+      if (stop_) return;
+      seen = gen_;
+      const std::function<void(size_t)> *f = f_;
+      lk.unlock();
+      std::exception_ptr e;
+      try {
+        (*f)(i);
+      } catch (...) {
+        e = std::current_exception();
+      }
+      lk.lock();
+      errs_[i] = e;
+      if (--pending_ == 0) done_.notify_one();
+    }
+  }
+  std::mutex m_;
+  std::condition_variable work_, done_;
+  std::vector<std::thread> th_;
+  std::vector<std::exception_ptr> errs_;
+  const std::function<void(size_t)> *f_ = nullptr;
+  size_t n_ = 0, pending_ = 0;
+  uint64_t gen_ = 0;
+  bool stop_ = false;
+};
+
+void SingleSiteSampler::on_parts(const std::function<void(size_t)> &f) {
+  if (!workers_) workers_.reset(new Workers());
+  workers_->run(parts_.size(), f);
+}
 
 std::vector<int> parse_device_list(const std::string &spec) {
   std::vector<int> out;
@@ -970,19 +1035,16 @@ void SingleSiteSampler::run_mcmc(uint64_t seed, uint64_t em_iteration,
     check_mcmc(epv_run_mcmc(ctx_, burn_in, batch, seed, base, Jf.data(), Df.data(), &n_acc), "epv_run_mcmc");
   } else {
     ensure_stat_buffers();
-    // one host thread per part: their colour phases run concurrently, each GPU on its own,
-    // the contexts of one GPU on their own streams
+    // one host thread per part (the persistent workers): their colour phases run concurrently, each GPU on
+    // its own, the contexts of one GPU on their own streams
     const size_t P = parts_.size();
     const uint64_t words = batch * B * 16, piece = words + kTail;
     std::vector<int> rcs(P, EPV_OK);
     std::vector<uint64_t> acc(P, 0);
     std::vector<std::vector<int64_t>> counts(P, std::vector<int64_t>(words));
-    ThreadGroup th;
-    for (size_t p = 0; p < P; ++p)
-      th.spawn([&, p] {
-        rcs[p] = epv_run_mcmc_counts(parts_[p].ctx, burn_in, batch, seed, base, counts[p].data(), &acc[p]);
-      });
-    th.join();
+    on_parts([&](size_t p) {
+      rcs[p] = epv_run_mcmc_counts(parts_[p].ctx, burn_in, batch, seed, base, counts[p].data(), &acc[p]);
+    });
     for (size_t p = 0; p < P; ++p) {
       epv_ctx *c = parts_[p].ctx;
       if (rcs[p] == EPV_ERR_CAPACITY) {   // absorbed as in check_mcmc; refresh_parts() evens the widths out
@@ -1071,10 +1133,7 @@ size_t SingleSiteSampler::sweeps(size_t n, uint64_t seed, uint32_t sweep_base) {
     const size_t P = parts_.size();
     std::vector<int> rcs(P, EPV_OK);
     std::vector<uint64_t> acc(P, 0);
-    ThreadGroup th;
-    for (size_t p = 0; p < P; ++p)
-      th.spawn([&, p] { rcs[p] = epv_sweep(parts_[p].ctx, kk, seed, sweep_base + (uint32_t)done, &acc[p]); });
-    th.join();
+    on_parts([&](size_t p) { rcs[p] = epv_sweep(parts_[p].ctx, kk, seed, sweep_base + (uint32_t)done, &acc[p]); });
     bool grew = false;
     for (size_t p = 0; p < P; ++p) {
       epv_ctx *c = parts_[p].ctx;
@@ -1170,9 +1229,7 @@ void SingleSiteSampler::download(FlatPaths &paths) {
     // every part on its own host thread (its context has its own stream): gather, copy, trim halos
     std::vector<FlatPaths> owned(parts_.size());
     std::vector<std::string> errors(parts_.size());
-    ThreadGroup workers;
-    for (size_t i = 0; i < parts_.size(); ++i)
-      workers.spawn([this, i, &owned, &errors] {
+    on_parts([this, &owned, &errors](size_t i) {
         try {
           Part &q = parts_[i];
           epv_ctx *c = q.ctx;
@@ -1190,7 +1247,6 @@ void SingleSiteSampler::download(FlatPaths &paths) {
           owned[i] = slice_sites(p, q.a - q.lo, q.b - q.lo);
         } catch (const std::exception &e) { errors[i] = e.what(); }
       });
-    workers.join();
     for (const std::string &e : errors) if (!e.empty()) throw std::runtime_error(e);
     paths = concat_sites(owned);
     return;

@@ -38,6 +38,8 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -252,6 +254,9 @@ private:
   void equalize_capacity();
   void ensure_stat_buffers();
   void free_stat_buffers();
+  class Workers;              // one persistent host thread per part (epv_sampler.cpp)
+  void on_parts(const std::function<void(size_t)> &f);   // f(p) for every part p, each on its part's thread; waits
+  std::unique_ptr<Workers> workers_;
   epv_ctx *ctx_;              // the context of the unsharded paths (== parts_[0].ctx when sharded)
   std::vector<int> devices_;
   int contexts_wanted_ = 0;      // contexts per GPU; 0 = by tree size (3 up to 8 branches: fused colour phase; else 2)

@@ -90,7 +90,8 @@ int epv_set_tree(epv_ctx *ctx, int n_nodes, const uint32_t *parent_ids,
 /* Model = the two members of EpiEvoModel the sampler reads (EpiEvoModel.hpp:37-41):
  * triplet_rates[8] and the horizontal transition matrix T (row-major 2x2).
  * log(rate) is taken here on the host with libm, as reset() does
- * (SingleSiteSampler.cpp:464-468). */
+ * (SingleSiteSampler.cpp:464-468).  The call is ordered on the context's stream and does not wait for
+ * the device: work queued before it reads the old constants, work queued after it the new ones. */
 int epv_set_model(epv_ctx *ctx, const double *triplet_rates, const double *T);
 
 /* Upload all paths (replaces handing `vector<vector<Path>>&` to reset()).
