@@ -63,6 +63,92 @@ struct EpvKnobs {
   bool accept_no_cache = false;
 };
 
+// ---- the state of the posterior summaries ("layers") of run_mcmc, one struct each.  Every member has a default:
+// a layer goes off by freeing its device buffers and taking a default-constructed struct (the *_off functions).
+// The sites a layer was laid out for: a layer whose current sites differ is laid out again, or, once it holds
+// samples, refused (sites_changed).  A member a layer does not depend on stays zero on both sides of the comparison
+struct SiteLayout {
+  uint64_t lo = 0;       // first local site
+  uint64_t cnt = 0;      // sites counted (the layers of pavg_range)
+  uint64_t hi = 0;       // last local site (the layers of owned_range; hi < lo: none)
+  uint64_t n = 0, g0 = 0, ng = 0;   // S.n, S.g0, S.n_global
+  uint32_t B = 0;
+  bool operator==(const SiteLayout &o) const {
+    return lo == o.lo && cnt == o.cnt && hi == o.hi && n == o.n && g0 == o.g0 && ng == o.ng && B == o.B;
+  }
+};
+// average history of the sampled paths (epv_pavg.h), off while P == 0
+struct PavgState {
+  uint32_t P = 0;
+  int32_t *d = nullptr;            // [B][P][at.cnt] counts over local sites at.lo .. at.lo + at.cnt - 1
+  SiteLayout at;                   // (without ng: the path average never depended on the genome's length)
+  uint64_t samples = 0;
+  double *d_grid = nullptr;        // [B][P] grid times
+  std::vector<double> grid_blen;   // the branch lengths d_grid was built from
+  uint32_t *d_out = nullptr;       // read-out staging
+  uint64_t out_cap = 0;            // bytes
+};
+// posterior branch-event maps (epv_bevents.h), off while !on
+struct BeventsState {
+  bool on = false;
+  uint32_t *d = nullptr;           // [6][B][at.cnt] counts over local sites at.lo .. at.lo + at.cnt - 1
+  SiteLayout at;
+  uint64_t samples = 0;
+  unsigned long long *d_out = nullptr;   // window read-out staging
+  uint64_t out_cap = 0;            // bytes
+};
+// regional sufficient statistics (epv_wstat.h), off while W == 0
+struct WstatState {
+  uint64_t W = 0;                  // sites per window, clamped to n_global
+  uint64_t W_asked = 0;            // as epv_set_window_stats got it (a changed n_global clamps it again)
+  unsigned long long *d = nullptr;   // [nw][B][16] over the global windows w0 .. w0 + nw - 1
+  uint64_t w0 = 0, nw = 0;
+  SiteLayout at;
+  uint64_t samples = 0;
+  std::vector<double> scale;       // 2^k_b of the first sample: the integers of later ones must mean the same
+};
+// epoch statistics (epv_epochs.h), off while P == 0.  No SiteLayout: the accumulator depends on B alone
+struct EpochState {
+  uint32_t P = 0;                  // epochs per branch
+  unsigned long long *d = nullptr;   // [B][P][32]: J[8], lo[8], hi[8], cov[8]
+  uint32_t B = 0;
+  uint64_t samples = 0;
+  uint64_t addends = 0;            // blocks along the sites, added over the samples: the addends a global word has received
+  std::vector<double> scale;       // 2^k_b of the first sample: the integers of later ones must mean the same
+  std::vector<uint64_t> fixT;      // llrint(T_b 2^k_b) of the first sample: the edges its epochs were cut at
+};
+// lineage origin maps (epv_origin.h), off while !on
+struct OriginsState {
+  bool on = false;
+  uint32_t *d = nullptr;                  // origin [R][at.cnt] counts over local sites at.lo .. at.lo + at.cnt - 1
+  unsigned long long *d_age = nullptr;    // age [L][at.cnt]
+  SiteLayout at;                          // (without B: the tree is compared itself)
+  uint32_t L = 0, R = 0;                  // leaves and rows of the tree they were laid out for
+  uint64_t samples = 0;
+  std::vector<uint32_t> parent;           // the tree of the tables below
+  std::vector<uint32_t> first, leaf, rowb;   // first row per leaf [L + 1]; leaf and branch node per row [R]
+  std::vector<long long> fixT;            // [N] llrint(ldexp(T_v, k)): with k what the accumulated ages mean
+  int k = 0;
+  uint32_t *d_first = nullptr, *d_rowb = nullptr;
+  long long *d_fixT = nullptr;
+  unsigned long long *d_out = nullptr;    // window read-out staging
+  uint64_t out_cap = 0;                   // bytes
+};
+// domain size spectra (epv_domains.h), off while !on
+struct DomainsState {
+  bool on = false;
+  uint64_t max = 0;                       // samples the edge records are allocated for
+  unsigned long long *d_hist = nullptr;   // [N][2][128] runs closed inside the counted stretch, over the samples
+  unsigned long long *d_len = nullptr;    // [N][2] their lengths
+  unsigned long long *d_edge = nullptr;   // [max][N][2] the two runs a sample's stretch cannot close
+  unsigned long long *d_bits = nullptr;   // [N][words] scratch: the node states of one sample, 64 sites a word
+  SiteLayout at;                          // (without B: the tree is compared itself)
+  uint64_t words = 0;
+  uint32_t N = 0, child0 = 0;             // nodes, and the root's lowest-numbered child
+  uint64_t samples = 0;
+  std::vector<uint32_t> parent;           // the tree they were laid out for
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -144,67 +230,13 @@ struct epv_ctx {
   size_t ev_used = 0;
   double timed_ms = 0.0;
   uint64_t timed_launches = 0;
-  // average history of the sampled paths (epv_pavg.h), off while pa_P == 0
-  uint32_t pa_P = 0;
-  int32_t *d_pa = nullptr;         // [B][P][pa_cnt] counts over local sites pa_lo .. pa_lo + pa_cnt - 1
-  uint64_t pa_lo = 0, pa_cnt = 0, pa_n = 0, pa_g0 = 0;   // the site range d_pa was laid out for
-  uint32_t pa_B = 0;
-  uint64_t pa_samples = 0;
-  double *d_pa_grid = nullptr;     // [B][P] grid times
-  std::vector<double> pa_grid_blen;  // the branch lengths d_pa_grid was built from
-  uint32_t *d_pa_out = nullptr;    // read-out staging
-  uint64_t pa_out_cap = 0;         // bytes
-  // posterior branch-event maps (epv_bevents.h), off while !be_on
-  bool be_on = false;
-  uint32_t *d_be = nullptr;        // [6][B][be_cnt] counts over local sites be_lo .. be_lo + be_cnt - 1
-  uint64_t be_lo = 0, be_cnt = 0, be_n = 0, be_g0 = 0, be_ng = 0;   // the site range d_be was laid out for
-  uint32_t be_B = 0;
-  uint64_t be_samples = 0;
-  unsigned long long *d_be_out = nullptr;   // window read-out staging
-  uint64_t be_out_cap = 0;         // bytes
-  // regional sufficient statistics (epv_wstat.h), off while ws_W == 0
-  uint64_t ws_W = 0;               // sites per window, clamped to n_global
-  uint64_t ws_W_asked = 0;         // as epv_set_window_stats got it (a changed n_global clamps it again)
-  unsigned long long *d_ws = nullptr;   // [ws_nw][B][16] over the global windows ws_w0 .. ws_w0 + ws_nw - 1
-  uint64_t ws_w0 = 0, ws_nw = 0;
-  uint64_t ws_lo = 0, ws_hi = 0, ws_n = 0, ws_g0 = 0, ws_ng = 0;   // the site range d_ws was laid out for
-  uint32_t ws_B = 0;
-  uint64_t ws_samples = 0;
-  std::vector<double> ws_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
-  // epoch statistics (epv_epochs.h), off while ep_P == 0
-  uint32_t ep_P = 0;               // epochs per branch
-  unsigned long long *d_ep = nullptr;   // [ep_B][ep_P][32]: J[8], lo[8], hi[8], cov[8]
-  uint32_t ep_B = 0;
-  uint64_t ep_samples = 0;
-  uint64_t ep_addends = 0;         // blocks along the sites, added over the samples: the addends a global word has received
-  std::vector<double> ep_scale;    // 2^k_b of the first sample: the integers of later ones must mean the same
-  std::vector<uint64_t> ep_fixT;   // llrint(T_b 2^k_b) of the first sample: the edges its epochs were cut at
-  // lineage origin maps (epv_origin.h), off while !lo_on
-  bool lo_on = false;
-  uint32_t *d_lo = nullptr;               // origin [lo_R][lo_cnt] counts over local sites lo_lo .. lo_lo + lo_cnt - 1
-  unsigned long long *d_lo_age = nullptr;   // age [lo_L][lo_cnt]
-  uint64_t lo_lo = 0, lo_cnt = 0, lo_n = 0, lo_g0 = 0, lo_ng = 0;   // the site range they were laid out for
-  uint32_t lo_L = 0, lo_R = 0;            // leaves and rows of the tree they were laid out for
-  uint64_t lo_samples = 0;
-  std::vector<uint32_t> lo_parent;        // the tree of the tables below
-  std::vector<uint32_t> lo_first, lo_leaf, lo_rowb;   // first row per leaf [L + 1]; leaf and branch node per row [R]
-  std::vector<long long> lo_fixT;         // [N] llrint(ldexp(T_v, lo_k)): with lo_k what the accumulated ages mean
-  int lo_k = 0;
-  uint32_t *d_lo_first = nullptr, *d_lo_rowb = nullptr;
-  long long *d_lo_fixT = nullptr;
-  unsigned long long *d_lo_out = nullptr;   // window read-out staging
-  uint64_t lo_out_cap = 0;                // bytes
-  // domain size spectra (epv_domains.h), off while !dm_on
-  bool dm_on = false;
-  uint64_t dm_max = 0;                      // samples the edge records are allocated for
-  unsigned long long *d_dm_hist = nullptr;  // [dm_N][2][128] runs closed inside the counted stretch, over the samples
-  unsigned long long *d_dm_len = nullptr;   // [dm_N][2] their lengths
-  unsigned long long *d_dm_edge = nullptr;  // [dm_max][dm_N][2] the two runs a sample's stretch cannot close
-  unsigned long long *d_dm_bits = nullptr;  // [dm_N][dm_words] scratch: the node states of one sample, 64 sites a word
-  uint64_t dm_lo = 0, dm_cnt = 0, dm_n = 0, dm_g0 = 0, dm_ng = 0, dm_words = 0;   // the site range they were laid out for
-  uint32_t dm_N = 0, dm_child0 = 0;         // nodes, and the root's lowest-numbered child
-  uint64_t dm_samples = 0;
-  std::vector<uint32_t> dm_parent;          // the tree they were laid out for
+  // the posterior summaries of run_mcmc (the structs above), in the order of the chain (kLayers)
+  PavgState pa;
+  BeventsState be;
+  WstatState ws;
+  EpochState ep;
+  OriginsState lo;
+  DomainsState dm;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -694,9 +726,61 @@ int launch_suffstats(epv_ctx *c, uint64_t slot) {
   return reduce_blocks_to_tot(c, c->d_partial[0], nb, 1u, slot);
 }
 
-// ---- path average (epv_pavg.h).  A context counts its owned sites, and the genome's two end sites
-// when it holds them (the sampler never changes those, so owned_range leaves them out): over all
-// contexts and GPUs every site is counted once.
+// ---- the posterior summaries of run_mcmc ("layers").  What the chain, the destructor and
+// the entry points need of a layer, whichever it is; its range, sizes, cap rule, launch and read-out stay its own
+struct Layer {
+  bool (*on)(const epv_ctx *);
+  int (*ensure)(epv_ctx *);                    // (on) the layout fits the sites, tree and scales of now
+  int (*check_cap)(epv_ctx *, uint64_t more);  // (on, ensured) `more` further samples fit
+  int (*launch)(epv_ctx *);                    // (on, ensured) the resident paths as one sample
+  void (*off)(epv_ctx *);                      // no buffers, no layout, no samples
+  const char *off_msg;                         // what an entry point that needs the layer says while it is off
+  const char *name;                            // as the sites-changed failure calls it
+};
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains;   // (each behind its functions)
+
+int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
+  return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
+                                setter + " again");
+}
+// (re)lay a layer out with its alloc function.  Whatever fails on the way (not enough memory, a HIP error) leaves
+// the layer off: never a layer that is on without its accumulator
+int relayout(epv_ctx *c, const Layer &L, int (*alloc)(epv_ctx *)) {
+  const int rc = alloc(c);
+  if (rc) L.off(c);
+  return rc;
+}
+// the free device memory, and whether `need` bytes fit it with a margin for the read-outs and the kernels' own needs
+int device_room(epv_ctx *c, double need, bool *fits, double *free_bytes) {
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+  *fits = !(need + 256.0 * 1024 * 1024 > (double)free_b);
+  *free_bytes = (double)free_b;
+  return EPV_OK;
+}
+// `more` further samples fit 32-bit counts that hold `samples` (the branch events and the lineage origins: a site
+// adds at most 1024 per sample).  One more that does not fit (a launch) and a batch that would pass the cap
+// (refused before the chain) have their own texts
+int check_cap32(epv_ctx *c, uint64_t samples, uint64_t more, const char *who, const char *reset) {
+  if (samples <= EPV_BEV_MAX_SAMPLES && more <= EPV_BEV_MAX_SAMPLES - samples) return EPV_OK;
+  return fail(c, EPV_ERR_STATE, std::string(who) + (more == 1u ? " hold" : " would pass") +
+                                " 2^21 samples, the most their 32-bit counts take: read them out and " + reset);
+}
+// read-out staging of at least `bytes`
+template <class T>
+int grow_staging(epv_ctx *c, T **buf, uint64_t *cap, uint64_t bytes) {
+  if (bytes <= *cap) return EPV_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(*buf);
+  *cap = 0;
+  HIP_TRY(c, hipMalloc(buf, bytes));
+  *cap = bytes;
+  return EPV_OK;
+}
+
+// The two site ranges a layer counts.  owned_range: the centres of the triples the statistics kernels take.
+// pavg_range: a context's owned sites, and the genome's two end sites when it holds them (the sampler never
+// changes those, so owned_range leaves them out): over all contexts and GPUs every site is counted once.
 void pavg_range(const epv_ctx *c, uint64_t *lo, uint64_t *cnt) {
   uint64_t a = 0, b = 0;
   owned_range(c, &a, &b);
@@ -705,52 +789,68 @@ void pavg_range(const epv_ctx *c, uint64_t *lo, uint64_t *cnt) {
   *lo = a;
   *cnt = b >= a ? b - a + 1u : 0u;
 }
+// the current layout of either range; the genome's length and B only for a layer that depends on them
+SiteLayout owned_layout(const epv_ctx *c) {
+  SiteLayout s;
+  owned_range(c, &s.lo, &s.hi);
+  s.n = c->S.n;
+  s.g0 = c->S.g0;
+  s.ng = c->S.n_global;
+  s.B = c->S.B;
+  return s;
+}
+SiteLayout pavg_layout(const epv_ctx *c, bool with_ng, bool with_B) {
+  SiteLayout s;
+  pavg_range(c, &s.lo, &s.cnt);
+  s.n = c->S.n;
+  s.g0 = c->S.g0;
+  if (with_ng) s.ng = c->S.n_global;
+  if (with_B) s.B = c->S.B;
+  return s;
+}
+
+// ---- path average (epv_pavg.h): the sites of pavg_range
+bool pavg_on(const epv_ctx *c) { return c->pa.P != 0u; }
+void pavg_off(epv_ctx *c) {
+  dfree(c->pa.d); dfree(c->pa.d_grid); dfree(c->pa.d_out);
+  c->pa = PavgState{};
+}
 // (re)lay out the counts for the current site range; zeroes them
 int pavg_alloc(epv_ctx *c) {
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
+  const SiteLayout at = pavg_layout(c, false, true);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_pa);
-  c->pa_cnt = 0;
-  const double need = 4.0 * (double)c->S.B * (double)cnt * (double)c->pa_P;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (a margin for the read-out and the kernels' own needs)
+  dfree(c->pa.d);
+  const double need = 4.0 * (double)c->S.B * (double)at.cnt * (double)c->pa.P;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "path average of %u points needs %.3g GB of device memory (4 B x %u branches x "
                   "%llu sites x %u points); %.3g GB are free: use fewer points or more GPUs (averaging is off)",
-                  c->pa_P, need / 1e9, c->S.B, (unsigned long long)cnt, c->pa_P, (double)free_b / 1e9);
-    c->pa_P = 0;
+                  c->pa.P, need / 1e9, c->S.B, (unsigned long long)at.cnt, c->pa.P, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
-  const size_t bytes = (size_t)4u * c->S.B * cnt * c->pa_P;
+  const size_t bytes = (size_t)4u * c->S.B * at.cnt * c->pa.P;
   if (bytes) {
-    HIP_TRY(c, hipMalloc(&c->d_pa, bytes));
-    HIP_TRY(c, hipMemsetAsync(c->d_pa, 0, bytes, c->stream));
+    HIP_TRY(c, hipMalloc(&c->pa.d, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->pa.d, 0, bytes, c->stream));
   }
-  c->pa_lo = lo;
-  c->pa_cnt = cnt;
-  c->pa_n = c->S.n;
-  c->pa_g0 = c->S.g0;
-  c->pa_B = c->S.B;
-  c->pa_samples = 0;
-  c->pa_grid_blen.clear();
+  c->pa.at = at;
+  c->pa.samples = 0;
+  c->pa.grid_blen.clear();
   return EPV_OK;
 }
 // the counts match the current site range, the grid the current branch lengths
 int ensure_pavg(epv_ctx *c) {
-  if (!c->pa_P) return EPV_OK;
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
-  if (lo != c->pa_lo || cnt != c->pa_cnt || c->S.n != c->pa_n || c->S.g0 != c->pa_g0 || c->S.B != c->pa_B) {
-    if (c->pa_samples)
-      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the path average took samples: "
-                                    "epv_set_path_average again");
-    int rc = pavg_alloc(c);
+  if (!(pavg_layout(c, false, true) == c->pa.at)) {
+    if (c->pa.samples) return sites_changed(c, kPavg, "epv_set_path_average");
+    const int rc = relayout(c, kPavg, pavg_alloc);
     if (rc) return rc;
   }
-  if (c->pa_grid_blen == c->blen) return EPV_OK;
-  const uint32_t P = c->pa_P, B = c->S.B;
+  if (c->pa.grid_blen == c->blen) return EPV_OK;
+  const uint32_t P = c->pa.P, B = c->S.B;
   std::vector<double> g((size_t)B * P);
   for (uint32_t b = 0; b < B; ++b) {   // average_paths.cpp:33-42: t_1 = bin, t_{i+1} = t_i + bin
     const double bin = c->blen[b + 1u] / (double)(P - 1u);
@@ -759,156 +859,132 @@ int ensure_pavg(epv_ctx *c) {
     for (uint32_t i = 1; i < P; ++i, t += bin) g[(size_t)b * P + i] = t;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->pa_grid_blen.empty()) {   // (pavg_alloc: new layout)
-    dfree(c->d_pa_grid);
-    HIP_TRY(c, hipMalloc(&c->d_pa_grid, g.size() * sizeof(double)));
+  if (c->pa.grid_blen.empty()) {   // (pavg_alloc: new layout)
+    dfree(c->pa.d_grid);
+    HIP_TRY(c, hipMalloc(&c->pa.d_grid, g.size() * sizeof(double)));
   }
-  HIP_TRY(c, hipMemcpy(c->d_pa_grid, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->pa_grid_blen = c->blen;
+  HIP_TRY(c, hipMemcpy(c->pa.d_grid, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->pa.grid_blen = c->blen;
   return EPV_OK;
 }
+int pavg_check_cap(epv_ctx *, uint64_t) { return EPV_OK; }   // (no cap is kept: a count takes at most one per sample)
 // the resident paths as one sample (ensure_pavg first)
 int launch_pavg(epv_ctx *c) {
-  if (c->pa_cnt)
-    hipLaunchKernelGGL(epv_pavg_accum_kernel, dim3((unsigned)((c->pa_cnt + 255u) / 256u), c->S.B), dim3(256), 0,
-                       c->stream, c->S, c->pa_lo, c->pa_cnt, (const double *)c->d_pa_grid, c->pa_P, c->d_pa);
-  ++c->pa_samples;
+  if (c->pa.at.cnt)
+    hipLaunchKernelGGL(epv_pavg_accum_kernel, dim3((unsigned)((c->pa.at.cnt + 255u) / 256u), c->S.B), dim3(256), 0,
+                       c->stream, c->S, c->pa.at.lo, c->pa.at.cnt, (const double *)c->pa.d_grid, c->pa.P, c->pa.d);
+  ++c->pa.samples;
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
+const Layer kPavg = {pavg_on, ensure_pavg, pavg_check_cap, launch_pavg, pavg_off,
+                     "path average is off: epv_set_path_average first", "the path average"};
 
 // ---- posterior branch-event maps (epv_bevents.h): the sites of pavg_range, six uint32 planes
+bool bevents_on(const epv_ctx *c) { return c->be.on; }
+void bevents_off(epv_ctx *c) {
+  dfree(c->be.d); dfree(c->be.d_out);
+  c->be = BeventsState{};
+}
 // (re)lay out the planes for the current site range; zeroes them
 int bevents_alloc(epv_ctx *c) {
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
+  const SiteLayout at = pavg_layout(c, true, true);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_be);
-  c->be_cnt = 0;
-  const double need = 4.0 * EPV_BEV_PLANES * (double)c->S.B * (double)cnt;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+  dfree(c->be.d);
+  const double need = 4.0 * EPV_BEV_PLANES * (double)c->S.B * (double)at.cnt;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "branch events need %.3g GB of device memory (24 B x %u branches x %llu sites); "
                   "%.3g GB are free: use more GPUs (the counters are off)",
-                  need / 1e9, c->S.B, (unsigned long long)cnt, (double)free_b / 1e9);
-    c->be_on = false;
+                  need / 1e9, c->S.B, (unsigned long long)at.cnt, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
-  const size_t bytes = (size_t)4u * EPV_BEV_PLANES * c->S.B * cnt;
+  const size_t bytes = (size_t)4u * EPV_BEV_PLANES * c->S.B * at.cnt;
   if (bytes) {
-    HIP_TRY(c, hipMalloc(&c->d_be, bytes));
-    HIP_TRY(c, hipMemsetAsync(c->d_be, 0, bytes, c->stream));
+    HIP_TRY(c, hipMalloc(&c->be.d, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->be.d, 0, bytes, c->stream));
   }
-  c->be_lo = lo;
-  c->be_cnt = cnt;
-  c->be_n = c->S.n;
-  c->be_g0 = c->S.g0;
-  c->be_ng = c->S.n_global;
-  c->be_B = c->S.B;
-  c->be_samples = 0;
+  c->be.at = at;
+  c->be.samples = 0;
   return EPV_OK;
 }
 // the planes match the current site range (there is no grid: branch lengths do not matter)
 int ensure_bevents(epv_ctx *c) {
-  if (!c->be_on) return EPV_OK;
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
-  if (lo != c->be_lo || cnt != c->be_cnt || c->S.n != c->be_n || c->S.g0 != c->be_g0 || c->S.n_global != c->be_ng ||
-      c->S.B != c->be_B) {
-    if (c->be_samples)
-      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the branch events took samples: "
-                                    "epv_set_branch_events again");
-    return bevents_alloc(c);
-  }
-  return EPV_OK;
+  if (pavg_layout(c, true, true) == c->be.at) return EPV_OK;
+  if (c->be.samples) return sites_changed(c, kBevents, "epv_set_branch_events");
+  return relayout(c, kBevents, bevents_alloc);
+}
+int bevents_check_cap(epv_ctx *c, uint64_t more) {
+  return check_cap32(c, c->be.samples, more, "branch events", "epv_reset_branch_events");
 }
 // the resident paths as one sample (ensure_bevents first)
 int launch_bevents(epv_ctx *c) {
-  if (c->be_samples >= EPV_BEV_MAX_SAMPLES)
-    return fail(c, EPV_ERR_STATE, "branch events hold 2^21 samples, the most their 32-bit counts take: "
-                                  "read them out and epv_reset_branch_events");
-  if (c->be_cnt)
-    hipLaunchKernelGGL(epv_bevents_accum_kernel, dim3((unsigned)((c->be_cnt + 255u) / 256u)), dim3(256), 0, c->stream,
-                       c->S, c->be_lo, c->be_cnt, c->d_be);
-  ++c->be_samples;
+  const int rc = bevents_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->be.at.cnt)
+    hipLaunchKernelGGL(epv_bevents_accum_kernel, dim3((unsigned)((c->be.at.cnt + 255u) / 256u)), dim3(256), 0, c->stream,
+                       c->S, c->be.at.lo, c->be.at.cnt, c->be.d);
+  ++c->be.samples;
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
+const Layer kBevents = {bevents_on, ensure_bevents, bevents_check_cap, launch_bevents, bevents_off,
+                        "branch events are off: epv_set_branch_events first", "the branch events"};
 
 // ---- regional sufficient statistics (epv_wstat.h): J and D per window of W global sites, over the
 // triples centred at the sites of owned_range (the statistics kernels' range, not pavg_range: the
 // genome's end sites centre no triple)
-// the statistics off: no accumulator, no layout, no samples
+bool wstat_on(const epv_ctx *c) { return c->ws.W != 0u; }
 void wstat_off(epv_ctx *c) {
-  dfree(c->d_ws);
-  c->ws_W = c->ws_W_asked = 0;
-  c->ws_w0 = c->ws_nw = 0;
-  c->ws_lo = c->ws_hi = c->ws_n = c->ws_g0 = c->ws_ng = 0;
-  c->ws_B = 0;
-  c->ws_samples = 0;
-  c->ws_scale.clear();
+  dfree(c->ws.d);
+  c->ws = WstatState{};
 }
-int wstat_alloc_try(epv_ctx *c) {
-  uint64_t lo = 0, hi = 0;
-  owned_range(c, &lo, &hi);
+// (re)lay out the accumulator for the current site range; zeroes it
+int wstat_alloc(epv_ctx *c) {
+  const SiteLayout at = owned_layout(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_ws);
-  c->ws_nw = 0;
-  c->ws_W = std::max<uint64_t>(1u, std::min<uint64_t>(c->ws_W_asked, c->S.n_global));
-  const bool any = hi >= lo && c->S.n >= 3u;
-  const uint64_t w0 = any ? (c->S.g0 + lo) / c->ws_W : 0u, nw = any ? (c->S.g0 + hi) / c->ws_W - w0 + 1u : 0u;
+  dfree(c->ws.d);
+  c->ws.W = std::max<uint64_t>(1u, std::min<uint64_t>(c->ws.W_asked, c->S.n_global));
+  const bool any = at.hi >= at.lo && c->S.n >= 3u;
+  const uint64_t w0 = any ? (c->S.g0 + at.lo) / c->ws.W : 0u, nw = any ? (c->S.g0 + at.hi) / c->ws.W - w0 + 1u : 0u;
   const double need = 128.0 * (double)c->S.B * (double)nw;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "window statistics need %.3g GB of device memory (128 B x %u branches x %llu windows "
                   "of %llu sites); %.3g GB are free: use wider windows or more GPUs (the statistics are off)",
-                  need / 1e9, c->S.B, (unsigned long long)nw, (unsigned long long)c->ws_W, (double)free_b / 1e9);
+                  need / 1e9, c->S.B, (unsigned long long)nw, (unsigned long long)c->ws.W, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
   const size_t bytes = (size_t)128u * c->S.B * nw;
   if (bytes) {
-    HIP_TRY(c, hipMalloc(&c->d_ws, bytes));
-    HIP_TRY(c, hipMemsetAsync(c->d_ws, 0, bytes, c->stream));
+    HIP_TRY(c, hipMalloc(&c->ws.d, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->ws.d, 0, bytes, c->stream));
   }
-  c->ws_w0 = w0;
-  c->ws_nw = nw;
-  c->ws_lo = lo;
-  c->ws_hi = hi;
-  c->ws_n = c->S.n;
-  c->ws_g0 = c->S.g0;
-  c->ws_ng = c->S.n_global;
-  c->ws_B = c->S.B;
-  c->ws_samples = 0;
-  c->ws_scale.clear();
+  c->ws.w0 = w0;
+  c->ws.nw = nw;
+  c->ws.at = at;
+  c->ws.samples = 0;
+  c->ws.scale.clear();
   return EPV_OK;
-}
-// (re)lay out the accumulator for the current site range; zeroes it.  Whatever fails on the way (not enough
-// memory, a HIP error) leaves the statistics off: never a window size without its accumulator
-int wstat_alloc(epv_ctx *c) {
-  const int rc = wstat_alloc_try(c);
-  if (rc) wstat_off(c);
-  return rc;
 }
 // the accumulator matches the current site range, and the scales 2^k_b are the ones its integers were taken with
 int ensure_wstat(epv_ctx *c) {
-  if (!c->ws_W) return EPV_OK;
-  uint64_t lo = 0, hi = 0;
-  owned_range(c, &lo, &hi);
-  if (lo != c->ws_lo || hi != c->ws_hi || c->S.n != c->ws_n || c->S.g0 != c->ws_g0 || c->S.n_global != c->ws_ng ||
-      c->S.B != c->ws_B) {
-    if (c->ws_samples)
-      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the window statistics took samples: "
-                                    "epv_set_window_stats again");
-    const int rc = wstat_alloc(c);
+  if (!(owned_layout(c) == c->ws.at)) {
+    if (c->ws.samples) return sites_changed(c, kWstat, "epv_set_window_stats");
+    const int rc = relayout(c, kWstat, wstat_alloc);
     if (rc) return rc;
   }
   const int rc = ensure_stat_scale(c);
   if (rc) return rc;
-  if (c->ws_samples && c->ws_scale != c->statscale)
+  if (c->ws.samples && c->ws.scale != c->statscale)
     return fail(c, EPV_ERR_STATE, "the branch lengths or the genome length changed after the window statistics took "
                                   "samples, so their fixed-point scales 2^k_b differ: read them out and "
                                   "epv_reset_window_stats");
@@ -921,19 +997,19 @@ uint64_t wstat_max_samples(const epv_ctx *c) {
   uint64_t q = 0;   // (T_b 2^k_b < 2^50: exact in a double and in 64 bits)
   for (uint32_t b = 1; b < c->S.N; ++b)
     q = std::max<uint64_t>(q, (uint64_t)std::llrint(c->blen[b] * c->statscale[b]) + 3072u);
-  const uint64_t cnt = c->ws_hi >= c->ws_lo ? c->ws_hi - c->ws_lo + 1u : 0u;
-  const unsigned __int128 per = (unsigned __int128)std::min<uint64_t>(c->ws_W, cnt) * q;
+  const uint64_t cnt = c->ws.at.hi >= c->ws.at.lo ? c->ws.at.hi - c->ws.at.lo + 1u : 0u;
+  const unsigned __int128 per = (unsigned __int128)std::min<uint64_t>(c->ws.W, cnt) * q;
   if (!per) return UINT64_MAX;
   return (uint64_t)((((unsigned __int128)1 << 63) - 1u) / per);   // the most m with m * per < 2^63
 }
 // `batch` more samples fit (ensure_wstat first)
 int wstat_check_cap(epv_ctx *c, uint64_t batch) {
   const uint64_t most = wstat_max_samples(c);
-  if (c->ws_samples > most || batch > most - c->ws_samples) {
+  if (c->ws.samples > most || batch > most - c->ws.samples) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "window statistics with windows of %llu sites take at most %llu samples in their "
                   "64-bit sums and hold %llu: read them out and epv_reset_window_stats",
-                  (unsigned long long)c->ws_W, (unsigned long long)most, (unsigned long long)c->ws_samples);
+                  (unsigned long long)c->ws.W, (unsigned long long)most, (unsigned long long)c->ws.samples);
     return fail(c, EPV_ERR_STATE, buf);
   }
   return EPV_OK;
@@ -942,33 +1018,30 @@ int wstat_check_cap(epv_ctx *c, uint64_t batch) {
 int launch_wstat(epv_ctx *c) {
   int rc = wstat_check_cap(c, 1u);
   if (rc) return rc;
-  if (c->ws_nw) {
-    const uint64_t tiles = (c->ws_hi - c->ws_lo) / 64u + 1u;
+  if (c->ws.nw) {
+    const uint64_t tiles = (c->ws.at.hi - c->ws.at.lo) / 64u + 1u;
     if (tiles > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many sites in one context for the window statistics");
     const dim3 grid((unsigned)tiles, (c->S.B + EPV_WSTAT_BCH - 1u) / EPV_WSTAT_BCH);
-    if (c->ws_W < 64u)
-      hipLaunchKernelGGL(epv_wstat_accum_kernel<true>, grid, dim3(64), 0, c->stream, c->S, c->ws_lo, c->ws_hi,
-                         c->d_statscale, c->ws_W, c->ws_w0, c->ws_nw, c->d_ws);
+    if (c->ws.W < 64u)
+      hipLaunchKernelGGL(epv_wstat_accum_kernel<true>, grid, dim3(64), 0, c->stream, c->S, c->ws.at.lo, c->ws.at.hi,
+                         c->d_statscale, c->ws.W, c->ws.w0, c->ws.nw, c->ws.d);
     else
-      hipLaunchKernelGGL(epv_wstat_accum_kernel<false>, grid, dim3(64), 0, c->stream, c->S, c->ws_lo, c->ws_hi,
-                         c->d_statscale, c->ws_W, c->ws_w0, c->ws_nw, c->d_ws);
+      hipLaunchKernelGGL(epv_wstat_accum_kernel<false>, grid, dim3(64), 0, c->stream, c->S, c->ws.at.lo, c->ws.at.hi,
+                         c->d_statscale, c->ws.W, c->ws.w0, c->ws.nw, c->ws.d);
   }
   HIP_TRY(c, hipGetLastError());
-  if (!c->ws_samples) c->ws_scale = c->statscale;
-  ++c->ws_samples;
+  if (!c->ws.samples) c->ws.scale = c->statscale;
+  ++c->ws.samples;
   return EPV_OK;
 }
+const Layer kWstat = {wstat_on, ensure_wstat, wstat_check_cap, launch_wstat, wstat_off,
+                      "window statistics are off: epv_set_window_stats first", "the window statistics"};
 
 // ---- lineage origin maps (epv_origin.h): the sites of pavg_range; origin uint32 [R][cnt], age uint64 [L][cnt]
-// the maps off: no accumulators, no tables, no samples
+bool origins_on(const epv_ctx *c) { return c->lo.on; }
 void origins_off(epv_ctx *c) {
-  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
-  c->lo_on = false;
-  c->lo_lo = c->lo_cnt = c->lo_n = c->lo_g0 = c->lo_ng = 0;
-  c->lo_L = c->lo_R = 0;
-  c->lo_samples = c->lo_out_cap = 0;
-  c->lo_parent.clear(); c->lo_first.clear(); c->lo_leaf.clear(); c->lo_rowb.clear(); c->lo_fixT.clear();
-  c->lo_k = 0;
+  dfree(c->lo.d); dfree(c->lo.d_age); dfree(c->lo.d_first); dfree(c->lo.d_rowb); dfree(c->lo.d_fixT); dfree(c->lo.d_out);
+  c->lo = OriginsState{};
 }
 // k = 40 - e(H), H = the longest lineage (fp64 sums from the leaf upward), and fixT[v] = llrint(ldexp(T_v, k)):
 // an age term stays below 2^40, so 2^21 samples stay below 2^63
@@ -989,12 +1062,12 @@ void origins_scale(const epv_ctx *c, int *k, std::vector<long long> *fixT) {
   fixT->assign(c->S.N, 0);
   for (uint32_t v = 1; v < c->S.N; ++v) (*fixT)[v] = std::llrint(std::ldexp(c->blen[v], *k));
 }
-int origins_alloc_try(epv_ctx *c) {
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
+// (re)lay out the accumulators and tables for the current tree and site range; zeroes them
+int origins_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, false);
+  const uint64_t cnt = at.cnt;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT);
-  c->lo_cnt = 0;
+  dfree(c->lo.d); dfree(c->lo.d_age); dfree(c->lo.d_first); dfree(c->lo.d_rowb); dfree(c->lo.d_fixT);
   // the row table: per leaf in node order its lineage from the leaf upward, then the root row
   std::vector<uint32_t> first, leaf, rowb;
   for (uint32_t v = 1; v < c->S.N; ++v) {
@@ -1007,170 +1080,142 @@ int origins_alloc_try(epv_ctx *c) {
   const uint32_t L = (uint32_t)first.size(), R = (uint32_t)rowb.size();
   first.push_back(R);
   const double need = (4.0 * R + 8.0 * L) * (double)cnt;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "lineage origins need %.3g GB of device memory ((4 B x %u rows + 8 B x %u leaves) x "
                   "%llu sites); %.3g GB are free: use more GPUs (the maps are off)",
-                  need / 1e9, R, L, (unsigned long long)cnt, (double)free_b / 1e9);
+                  need / 1e9, R, L, (unsigned long long)cnt, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
   int k = 0;
   std::vector<long long> fixT;
   origins_scale(c, &k, &fixT);
-  HIP_TRY(c, hipMalloc(&c->d_lo_first, sizeof(uint32_t) * first.size()));
-  HIP_TRY(c, hipMalloc(&c->d_lo_rowb, sizeof(uint32_t) * rowb.size()));
-  HIP_TRY(c, hipMalloc(&c->d_lo_fixT, sizeof(long long) * fixT.size()));
-  HIP_TRY(c, hipMemcpy(c->d_lo_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_lo_rowb, rowb.data(), sizeof(uint32_t) * rowb.size(), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_lo_fixT, fixT.data(), sizeof(long long) * fixT.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMalloc(&c->lo.d_first, sizeof(uint32_t) * first.size()));
+  HIP_TRY(c, hipMalloc(&c->lo.d_rowb, sizeof(uint32_t) * rowb.size()));
+  HIP_TRY(c, hipMalloc(&c->lo.d_fixT, sizeof(long long) * fixT.size()));
+  HIP_TRY(c, hipMemcpy(c->lo.d_first, first.data(), sizeof(uint32_t) * first.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->lo.d_rowb, rowb.data(), sizeof(uint32_t) * rowb.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->lo.d_fixT, fixT.data(), sizeof(long long) * fixT.size(), hipMemcpyHostToDevice));
   if (cnt) {
-    HIP_TRY(c, hipMalloc(&c->d_lo, (size_t)4u * R * cnt));
-    HIP_TRY(c, hipMalloc(&c->d_lo_age, (size_t)8u * L * cnt));
-    HIP_TRY(c, hipMemsetAsync(c->d_lo, 0, (size_t)4u * R * cnt, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_lo_age, 0, (size_t)8u * L * cnt, c->stream));
+    HIP_TRY(c, hipMalloc(&c->lo.d, (size_t)4u * R * cnt));
+    HIP_TRY(c, hipMalloc(&c->lo.d_age, (size_t)8u * L * cnt));
+    HIP_TRY(c, hipMemsetAsync(c->lo.d, 0, (size_t)4u * R * cnt, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->lo.d_age, 0, (size_t)8u * L * cnt, c->stream));
   }
-  c->lo_lo = lo;
-  c->lo_cnt = cnt;
-  c->lo_n = c->S.n;
-  c->lo_g0 = c->S.g0;
-  c->lo_ng = c->S.n_global;
-  c->lo_L = L;
-  c->lo_R = R;
-  c->lo_samples = 0;
-  c->lo_parent = c->parent;
-  c->lo_first.swap(first);
-  c->lo_leaf.swap(leaf);
-  c->lo_rowb.swap(rowb);
-  c->lo_fixT.swap(fixT);
-  c->lo_k = k;
+  c->lo.at = at;
+  c->lo.L = L;
+  c->lo.R = R;
+  c->lo.samples = 0;
+  c->lo.parent = c->parent;
+  c->lo.first.swap(first);
+  c->lo.leaf.swap(leaf);
+  c->lo.rowb.swap(rowb);
+  c->lo.fixT.swap(fixT);
+  c->lo.k = k;
   return EPV_OK;
-}
-// (re)lay out the accumulators and tables for the current tree and site range; zeroes them.  Whatever fails on
-// the way leaves the maps off
-int origins_alloc(epv_ctx *c) {
-  const int rc = origins_alloc_try(c);
-  if (rc) origins_off(c);
-  return rc;
 }
 // the accumulators match the current site range, and the tree, k and fixT are the ones the samples were taken with
 int ensure_origins(epv_ctx *c) {
-  if (!c->lo_on) return EPV_OK;
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
-  const bool sites = lo != c->lo_lo || cnt != c->lo_cnt || c->S.n != c->lo_n || c->S.g0 != c->lo_g0 ||
-                     c->S.n_global != c->lo_ng;
+  const bool sites = !(pavg_layout(c, true, false) == c->lo.at);
   int k = 0;
   std::vector<long long> fixT;
   origins_scale(c, &k, &fixT);
-  const bool tree = c->parent != c->lo_parent || k != c->lo_k || fixT != c->lo_fixT;
+  const bool tree = c->parent != c->lo.parent || k != c->lo.k || fixT != c->lo.fixT;
   if (!sites && !tree) return EPV_OK;
-  if (c->lo_samples) {
-    if (sites)
-      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the lineage origins took samples: "
-                                    "epv_set_lineage_origins again");
+  if (c->lo.samples) {
+    if (sites) return sites_changed(c, kOrigins, "epv_set_lineage_origins");
     return fail(c, EPV_ERR_STATE, "the tree or the branch lengths changed after the lineage origins took samples, so "
                                   "their rows or fixed-point ages differ: read them out and epv_reset_lineage_origins");
   }
-  return origins_alloc(c);
+  return relayout(c, kOrigins, origins_alloc);
+}
+int origins_check_cap(epv_ctx *c, uint64_t more) {
+  return check_cap32(c, c->lo.samples, more, "lineage origins", "epv_reset_lineage_origins");
 }
 // the resident paths as one sample (ensure_origins first)
 int launch_origins(epv_ctx *c) {
-  if (c->lo_samples >= EPV_BEV_MAX_SAMPLES)
-    return fail(c, EPV_ERR_STATE, "lineage origins hold 2^21 samples, the most their 32-bit counts take: "
-                                  "read them out and epv_reset_lineage_origins");
-  if (c->lo_cnt && c->lo_L)
-    hipLaunchKernelGGL(epv_origin_accum_kernel, dim3((unsigned)((c->lo_cnt + 255u) / 256u), c->lo_L), dim3(256), 0,
-                       c->stream, c->S, c->lo_lo, c->lo_cnt, (const uint32_t *)c->d_lo_first,
-                       (const uint32_t *)c->d_lo_rowb, (const long long *)c->d_lo_fixT, std::ldexp(1.0, c->lo_k),
-                       c->d_lo, c->d_lo_age);
+  const int rc = origins_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->lo.at.cnt && c->lo.L)
+    hipLaunchKernelGGL(epv_origin_accum_kernel, dim3((unsigned)((c->lo.at.cnt + 255u) / 256u), c->lo.L), dim3(256), 0,
+                       c->stream, c->S, c->lo.at.lo, c->lo.at.cnt, (const uint32_t *)c->lo.d_first,
+                       (const uint32_t *)c->lo.d_rowb, (const long long *)c->lo.d_fixT, std::ldexp(1.0, c->lo.k),
+                       c->lo.d, c->lo.d_age);
   HIP_TRY(c, hipGetLastError());
-  ++c->lo_samples;
+  ++c->lo.samples;
   return EPV_OK;
 }
+const Layer kOrigins = {origins_on, ensure_origins, origins_check_cap, launch_origins, origins_off,
+                        "lineage origins are off: epv_set_lineage_origins first", "the lineage origins"};
 
 // ---- domain size spectra (epv_domains.h): the sites of pavg_range; a context keeps its PART, unclosed
+bool domains_on(const epv_ctx *c) { return c->dm.on; }
 void domains_off(epv_ctx *c) {
-  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
-  c->dm_on = false;
-  c->dm_max = c->dm_lo = c->dm_cnt = c->dm_n = c->dm_g0 = c->dm_ng = c->dm_words = c->dm_samples = 0;
-  c->dm_N = c->dm_child0 = 0;
-  c->dm_parent.clear();
+  dfree(c->dm.d_hist); dfree(c->dm.d_len); dfree(c->dm.d_edge); dfree(c->dm.d_bits);
+  c->dm = DomainsState{};
 }
-int domains_alloc_try(epv_ctx *c) {
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
+// (re)lay out the part for the current tree and site range; zeroes it
+int domains_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, false);
+  const uint64_t cnt = at.cnt;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
-  c->dm_cnt = c->dm_words = 0;
+  dfree(c->dm.d_hist); dfree(c->dm.d_len); dfree(c->dm.d_edge); dfree(c->dm.d_bits);
   if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^32 - 1 sites per context");
   const uint32_t N = c->S.N;
   const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 8.0 * N * (2.0 * EPV_DOM_BINS + 2.0) + 8.0 * N * (double)words + 16.0 * N * (double)c->dm_max;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of pavg_alloc)
+  const double need = 8.0 * N * (2.0 * EPV_DOM_BINS + 2.0) + 8.0 * N * (double)words + 16.0 * N * (double)c->dm.max;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "domain statistics need %.3g GB of device memory (16 B x %u nodes x %llu samples of "
                   "edge records, 8 B x %u nodes x %llu words of node states); %.3g GB are free: ask for fewer samples "
                   "(the statistics are off)",
-                  need / 1e9, N, (unsigned long long)c->dm_max, N, (unsigned long long)words, (double)free_b / 1e9);
+                  need / 1e9, N, (unsigned long long)c->dm.max, N, (unsigned long long)words, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
   uint32_t child0 = 0;
   for (uint32_t v = 1; v < N && !child0; ++v) if (c->parent[v] == 0u) child0 = v;
-  const size_t hist_b = (size_t)16u * EPV_DOM_BINS * N, len_b = (size_t)16u * N, edge_b = (size_t)16u * N * c->dm_max;
-  HIP_TRY(c, hipMalloc(&c->d_dm_hist, hist_b));
-  HIP_TRY(c, hipMalloc(&c->d_dm_len, len_b));
-  HIP_TRY(c, hipMalloc(&c->d_dm_edge, edge_b));
-  if (words) HIP_TRY(c, hipMalloc(&c->d_dm_bits, (size_t)8u * N * words));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_hist, 0, hist_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_len, 0, len_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_edge, 0, edge_b, c->stream));
-  c->dm_lo = lo;
-  c->dm_cnt = cnt;
-  c->dm_words = words;
-  c->dm_n = c->S.n;
-  c->dm_g0 = c->S.g0;
-  c->dm_ng = c->S.n_global;
-  c->dm_N = N;
-  c->dm_child0 = child0;
-  c->dm_samples = 0;
-  c->dm_parent = c->parent;
+  const size_t hist_b = (size_t)16u * EPV_DOM_BINS * N, len_b = (size_t)16u * N, edge_b = (size_t)16u * N * c->dm.max;
+  HIP_TRY(c, hipMalloc(&c->dm.d_hist, hist_b));
+  HIP_TRY(c, hipMalloc(&c->dm.d_len, len_b));
+  HIP_TRY(c, hipMalloc(&c->dm.d_edge, edge_b));
+  if (words) HIP_TRY(c, hipMalloc(&c->dm.d_bits, (size_t)8u * N * words));
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_hist, 0, hist_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_len, 0, len_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_edge, 0, edge_b, c->stream));
+  c->dm.at = at;
+  c->dm.words = words;
+  c->dm.N = N;
+  c->dm.child0 = child0;
+  c->dm.samples = 0;
+  c->dm.parent = c->parent;
   return EPV_OK;
-}
-// (re)lay out the part for the current tree and site range; zeroes it.  Whatever fails on the way leaves the
-// statistics off
-int domains_alloc(epv_ctx *c) {
-  const int rc = domains_alloc_try(c);
-  if (rc) domains_off(c);
-  return rc;
 }
 // the part matches the current site range and tree (branch lengths do not matter: no jump time is read)
 int ensure_domains(epv_ctx *c) {
-  if (!c->dm_on) return EPV_OK;
-  uint64_t lo = 0, cnt = 0;
-  pavg_range(c, &lo, &cnt);
-  const bool sites = lo != c->dm_lo || cnt != c->dm_cnt || c->S.n != c->dm_n || c->S.g0 != c->dm_g0 ||
-                     c->S.n_global != c->dm_ng;
-  const bool tree = c->S.N != c->dm_N || c->parent != c->dm_parent;
+  const bool sites = !(pavg_layout(c, true, false) == c->dm.at);
+  const bool tree = c->S.N != c->dm.N || c->parent != c->dm.parent;
   if (!sites && !tree) return EPV_OK;
-  if (c->dm_samples) {
-    if (sites)
-      return fail(c, EPV_ERR_STATE, "the sites of this context changed after the domain statistics took samples: "
-                                    "epv_set_domain_stats again");
+  if (c->dm.samples) {
+    if (sites) return sites_changed(c, kDomains, "epv_set_domain_stats");
     return fail(c, EPV_ERR_STATE, "the tree changed after the domain statistics took samples: read them out and "
                                   "epv_reset_domain_stats");
   }
-  return domains_alloc(c);
+  return relayout(c, kDomains, domains_alloc);
 }
 int domains_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->dm_samples + more > c->dm_max) {
+  if (c->dm.samples + more > c->dm.max) {
     char buf[256];
     std::snprintf(buf, sizeof buf, "domain statistics hold %llu of the %llu samples their edge records were allocated "
                   "for, and %llu more were asked: read them out and epv_reset_domain_stats, or epv_set_domain_stats "
-                  "with more", (unsigned long long)c->dm_samples, (unsigned long long)c->dm_max, (unsigned long long)more);
+                  "with more", (unsigned long long)c->dm.samples, (unsigned long long)c->dm.max, (unsigned long long)more);
     return fail(c, EPV_ERR_STATE, buf);
   }
   return EPV_OK;
@@ -1179,70 +1224,60 @@ int domains_check_cap(epv_ctx *c, uint64_t more) {
 int launch_domains(epv_ctx *c) {
   int rc = domains_check_cap(c, 1u);
   if (rc) return rc;
-  if (c->dm_cnt) {
-    const uint64_t words = c->dm_words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
-    hipLaunchKernelGGL(epv_dom_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->dm_lo,
-                       c->dm_cnt, words, c->dm_child0, c->d_dm_bits);
+  if (c->dm.at.cnt) {
+    const uint64_t words = c->dm.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
+    hipLaunchKernelGGL(epv_dom_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->dm.at.lo,
+                       c->dm.at.cnt, words, c->dm.child0, c->dm.d_bits);
     HIP_TRY(c, hipGetLastError());
-    unsigned long long *edge = c->d_dm_edge + c->dm_samples * 2u * c->dm_N;
-    for (uint32_t v0 = 0; v0 < c->dm_N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
-      const uint32_t nv = std::min<uint32_t>(65535u, c->dm_N - v0);
+    unsigned long long *edge = c->dm.d_edge + c->dm.samples * 2u * c->dm.N;
+    for (uint32_t v0 = 0; v0 < c->dm.N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
+      const uint32_t nv = std::min<uint32_t>(65535u, c->dm.N - v0);
       hipLaunchKernelGGL(epv_dom_runs_kernel, dim3((unsigned)chunks, nv), dim3(256), 0, c->stream,
-                         (const unsigned long long *)c->d_dm_bits, words, c->dm_cnt, v0, c->d_dm_hist, c->d_dm_len, edge);
+                         (const unsigned long long *)c->dm.d_bits, words, c->dm.at.cnt, v0, c->dm.d_hist, c->dm.d_len, edge);
       HIP_TRY(c, hipGetLastError());
     }
   }
-  ++c->dm_samples;
+  ++c->dm.samples;
   return EPV_OK;
 }
+const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off,
+                        "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
 
 // ---- epoch statistics (epv_epochs.h): J and D per branch and epoch of the branch, over the triples centred
 // at the sites of owned_range.  The accumulator [B][P][32] does not depend on the site range
-// the statistics off: no accumulator, no samples
+bool epoch_on(const epv_ctx *c) { return c->ep.P != 0u; }
 void epoch_off(epv_ctx *c) {
-  dfree(c->d_ep);
-  c->ep_P = 0;
-  c->ep_B = 0;
-  c->ep_samples = 0;
-  c->ep_addends = 0;
-  c->ep_scale.clear();
-  c->ep_fixT.clear();
+  dfree(c->ep.d);
+  c->ep = EpochState{};
 }
-// (re)lay out the accumulator for the current tree; zeroes it.  A HIP error leaves the statistics off
-int epoch_alloc(epv_ctx *c, uint32_t P) {
-  auto body = [&]() -> int {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_ep);
-    const size_t bytes = (size_t)256u * c->S.B * P;
-    if (bytes) {
-      HIP_TRY(c, hipMalloc(&c->d_ep, bytes));
-      HIP_TRY(c, hipMemsetAsync(c->d_ep, 0, bytes, c->stream));
-    }
-    c->ep_P = P;
-    c->ep_B = c->S.B;
-    c->ep_samples = 0;
-    c->ep_addends = 0;
-    c->ep_scale.clear();
-    c->ep_fixT.clear();
-    return EPV_OK;
-  };
-  const int rc = body();
-  if (rc) epoch_off(c);
-  return rc;
+// (re)lay out the accumulator of ep.P epochs for the current tree; zeroes it
+int epoch_alloc(epv_ctx *c) {
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->ep.d);
+  const size_t bytes = (size_t)256u * c->S.B * c->ep.P;
+  if (bytes) {
+    HIP_TRY(c, hipMalloc(&c->ep.d, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->ep.d, 0, bytes, c->stream));
+  }
+  c->ep.B = c->S.B;
+  c->ep.samples = 0;
+  c->ep.addends = 0;
+  c->ep.scale.clear();
+  c->ep.fixT.clear();
+  return EPV_OK;
 }
 // the accumulator matches the current tree, and the scales 2^k_b are the ones its integers were taken with
 int ensure_epochs(epv_ctx *c) {
-  if (!c->ep_P) return EPV_OK;
-  if (c->S.B != c->ep_B) {
-    if (c->ep_samples)
+  if (c->S.B != c->ep.B) {
+    if (c->ep.samples)
       return fail(c, EPV_ERR_STATE, "the tree of this context changed after the epoch statistics took samples: "
                                     "epv_set_epoch_stats again");
-    const int rc = epoch_alloc(c, c->ep_P);
+    const int rc = relayout(c, kEpochs, epoch_alloc);
     if (rc) return rc;
   }
   const int rc = ensure_stat_scale(c);
   if (rc) return rc;
-  if (c->ep_samples && c->ep_scale != c->statscale)
+  if (c->ep.samples && c->ep.scale != c->statscale)
     return fail(c, EPV_ERR_STATE, "the branch lengths or the genome length changed after the epoch statistics took "
                                   "samples, so their fixed-point scales 2^k_b differ: read them out and "
                                   "epv_reset_epoch_stats");
@@ -1265,25 +1300,25 @@ uint64_t epoch_blocks(const epv_ctx *c) {
 // `batch` more samples fit (ensure_epochs first): a block adds at most one addend below 2^32 to a global
 // word per sample (the lo and hi halves of its 64-bit sum, its counts), so the 64-bit words hold while
 //   addends so far + batch * blocks along the sites < 2^32
-// (ep_addends counts the blocks of every sample taken, whatever the owned range was then)
+// (ep.addends counts the blocks of every sample taken, whatever the owned range was then)
 int epoch_check_cap(epv_ctx *c, uint64_t batch) {
   const uint64_t blocks = epoch_blocks(c), room = (1ull << 32) - 1u;
   if (!blocks) return EPV_OK;
-  const uint64_t left = c->ep_addends > room ? 0u : (room - c->ep_addends) / blocks;   // samples that still fit
-  if (c->ep_addends > room || batch > left) {
+  const uint64_t left = c->ep.addends > room ? 0u : (room - c->ep.addends) / blocks;   // samples that still fit
+  if (c->ep.addends > room || batch > left) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "epoch statistics over %llu blocks of sites take at most %llu samples in their "
                   "64-bit sums and hold %llu: read them out and epv_reset_epoch_stats",
-                  (unsigned long long)blocks, (unsigned long long)(c->ep_samples + left), (unsigned long long)c->ep_samples);
+                  (unsigned long long)blocks, (unsigned long long)(c->ep.samples + left), (unsigned long long)c->ep.samples);
     return fail(c, EPV_ERR_STATE, buf);
   }
   return EPV_OK;
 }
 // the scales and branch lengths of now become the ones the accumulator's integers mean
 void epoch_remember(epv_ctx *c) {
-  c->ep_scale = c->statscale;
-  c->ep_fixT.assign(c->S.N, 0u);
-  for (uint32_t b = 1; b < c->S.N; ++b) c->ep_fixT[b] = (uint64_t)std::llrint(c->blen[b] * c->statscale[b]);   // (< 2^50: exact)
+  c->ep.scale = c->statscale;
+  c->ep.fixT.assign(c->S.N, 0u);
+  for (uint32_t b = 1; b < c->S.N; ++b) c->ep.fixT[b] = (uint64_t)std::llrint(c->blen[b] * c->statscale[b]);   // (< 2^50: exact)
 }
 // the resident paths as one sample (ensure_epochs first)
 int launch_epochs(epv_ctx *c) {
@@ -1295,15 +1330,21 @@ int launch_epochs(epv_ctx *c) {
     const uint32_t tiles = epoch_tiles(c, lo, hi);
     const uint64_t blocks = (hi - lo) / (256ull * tiles) + 1u;
     if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many sites in one context for the epoch statistics");
-    hipLaunchKernelGGL(epv_epoch_accum_kernel, dim3((unsigned)blocks, c->S.B), dim3(256), (size_t)136u * c->ep_P,
-                       c->stream, c->S, lo, hi, c->d_statscale, c->ep_P, tiles, c->d_ep);
+    hipLaunchKernelGGL(epv_epoch_accum_kernel, dim3((unsigned)blocks, c->S.B), dim3(256), (size_t)136u * c->ep.P,
+                       c->stream, c->S, lo, hi, c->d_statscale, c->ep.P, tiles, c->ep.d);
   }
   HIP_TRY(c, hipGetLastError());
-  if (!c->ep_samples) epoch_remember(c);
-  ++c->ep_samples;
-  c->ep_addends += epoch_blocks(c);
+  if (!c->ep.samples) epoch_remember(c);
+  ++c->ep.samples;
+  c->ep.addends += epoch_blocks(c);
   return EPV_OK;
 }
+const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, epoch_off,
+                       "epoch statistics are off: epv_set_epoch_stats first", "the epoch statistics"};
+
+// the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
+// that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
+const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -1587,6 +1628,41 @@ int check_ready(epv_ctx *c, bool need_reset) {
   return EPV_OK;
 }
 
+// ---- what the entry points of every summary layer begin with
+// an entry point that needs the layer on: a context, the layer on (or its message), the context's device current
+int layer_entry(epv_ctx *c, const Layer &L) {
+  if (!c) return EPV_ERR_ARG;
+  if (!L.on(c)) return fail(c, EPV_ERR_STATE, L.off_msg);
+  HIP_TRY(c, hipSetDevice(c->device));
+  return EPV_OK;
+}
+// a setter told to switch its layer off
+int layer_set_off(epv_ctx *c, const Layer &L) {
+  if (!c) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  L.off(c);
+  return EPV_OK;
+}
+// a setter that has taken its arguments into the layer's state: lay out for the context as it is now
+int layer_set_on(epv_ctx *c, const Layer &L, int (*alloc)(epv_ctx *)) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int rc = relayout(c, L, alloc);
+  if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+// epv_accumulate_*: the resident paths as one sample of the layer
+int layer_accumulate(epv_ctx *c, const Layer &L) {
+  int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (!L.on(c)) return fail(c, EPV_ERR_STATE, L.off_msg);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = L.ensure(c)) || (rc = L.launch(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
 }  // namespace
 
 EPV_API epv_ctx *epv_create(int device_id) {
@@ -1642,12 +1718,7 @@ EPV_API void epv_destroy(epv_ctx *c) {
   free_paths(c);
   dfree(c->d_model); dfree(c->d_parent); dfree(c->d_subtree); dfree(c->d_blen);
   dfree(c->d_counters); dfree(c->d_sweep_tot); dfree(c->d_statscale); dfree(c->d_scale); dfree(c->d_indep); dfree(c->d_gpool); dfree(c->d_stage); dfree(c->d_lvl); dfree(c->d_gpool3); dfree(c->d_segtab); dfree(c->d_nodetab); dfree(c->d_slabflags);
-  dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
-  dfree(c->d_be); dfree(c->d_be_out);
-  dfree(c->d_ws);
-  dfree(c->d_ep);
-  dfree(c->d_lo); dfree(c->d_lo_age); dfree(c->d_lo_first); dfree(c->d_lo_rowb); dfree(c->d_lo_fixT); dfree(c->d_lo_out);
-  dfree(c->d_dm_hist); dfree(c->d_dm_len); dfree(c->d_dm_edge); dfree(c->d_dm_bits);
+  for (const Layer *L : kLayers) L->off(c);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_cnt_snap) (void)hipHostFree(c->h_cnt_snap);
   if (c->h_tot) (void)hipHostFree(c->h_tot);
@@ -2453,12 +2524,13 @@ EPV_API int epv_indep_node_posterior(epv_ctx *c, const double *rates, double *p_
   // the read-out is staged on the device, [N][n] doubles
   const uint64_t cells = (uint64_t)c->S.N * c->S.n;
   const double need = 8.0 * (double)cells;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
-  if (need + 256.0 * 1024 * 1024 > (double)free_b) {   // (the margin of epv_set_path_average)
+  bool fits = false;
+  double free_b = 0.0;
+  if ((rc = device_room(c, need, &fits, &free_b))) return rc;
+  if (!fits) {
     char buf[320];
     std::snprintf(buf, sizeof buf, "node posterior needs %.3g GB of device memory (8 B x %u nodes x %llu sites); "
-                  "%.3g GB are free", need / 1e9, c->S.N, (unsigned long long)c->S.n, (double)free_b / 1e9);
+                  "%.3g GB are free", need / 1e9, c->S.N, (unsigned long long)c->S.n, free_b / 1e9);
     return fail(c, EPV_ERR_ARG, buf);
   }
   DevTmp<double> out;
@@ -2657,27 +2729,14 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
   return finish_mcmc(c, n_accepted, base);
 }
 
-// burn_in sweeps, then batch x {sweep; stat(w); path-average, branch-event, window-statistics, epoch-statistics, lineage-origin and domain-statistics sample}: the chain of epv_run_mcmc_sums
-// and epv_run_mcmc_counts.  stat(w) launches the statistics of batch sweep w; the accept counters are
-// snapshot where the batch sweeps begin (finish_mcmc_snapshot)
+// burn_in sweeps, then batch x {sweep; stat(w); one sample of every summary layer that is on, in the order of
+// kLayers}: the chain of epv_run_mcmc_sums and epv_run_mcmc_counts.  stat(w) launches the statistics of batch
+// sweep w; the accept counters are snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
 static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base, Stat stat) {
-  int rc = ensure_pavg(c);
-  if (rc) return rc;
-  if ((rc = ensure_bevents(c))) return rc;
-  if (c->be_on && c->be_samples + batch > EPV_BEV_MAX_SAMPLES)   // (before any sweep: the chain is not cut short)
-    return fail(c, EPV_ERR_STATE, "branch events would pass 2^21 samples, the most their 32-bit counts take: "
-                                  "read them out and epv_reset_branch_events");
-  if ((rc = ensure_wstat(c))) return rc;
-  if (c->ws_W && (rc = wstat_check_cap(c, batch))) return rc;   // (before any sweep as well)
-  if ((rc = ensure_epochs(c))) return rc;
-  if (c->ep_P && (rc = epoch_check_cap(c, batch))) return rc;   // (before any sweep as well)
-  if ((rc = ensure_origins(c))) return rc;
-  if (c->lo_on && c->lo_samples + batch > EPV_BEV_MAX_SAMPLES)
-    return fail(c, EPV_ERR_STATE, "lineage origins would pass 2^21 samples, the most their 32-bit counts take: "
-                                  "read them out and epv_reset_lineage_origins");
-  if ((rc = ensure_domains(c))) return rc;
-  if (c->dm_on && (rc = domains_check_cap(c, batch))) return rc;   // (before any sweep as well)
+  int rc = EPV_OK;
+  for (const Layer *L : kLayers)   // (the caps before any sweep: the chain is not cut short)
+    if (L->on(c) && ((rc = L->ensure(c)) || (rc = L->check_cap(c, batch)))) return rc;
   uint32_t sweep = sweep_base;
   for (uint64_t w = 0; w < burn_in; ++w, ++sweep) {
     for (int colour = 0; colour < 3; ++colour)
@@ -2690,12 +2749,8 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
       if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
     ++c->n_sweeps;
     if ((rc = stat(w))) return rc;
-    if (c->pa_P && (rc = launch_pavg(c))) return rc;
-    if (c->be_on && (rc = launch_bevents(c))) return rc;
-    if (c->ws_W && (rc = launch_wstat(c))) return rc;
-    if (c->ep_P && (rc = launch_epochs(c))) return rc;
-    if (c->lo_on && (rc = launch_origins(c))) return rc;
-    if (c->dm_on && (rc = launch_domains(c))) return rc;
+    for (const Layer *L : kLayers)
+      if (L->on(c) && (rc = L->launch(c))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
@@ -3075,50 +3130,32 @@ EPV_API int epv_kernel_time_ms(epv_ctx *c, double *avg_ms, uint64_t *n_launches)
 
 // ---- average history of the sampled paths (epv_pavg.h)
 EPV_API int epv_set_path_average(epv_ctx *c, uint32_t n_points) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (n_points == 0) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_pa); dfree(c->d_pa_grid); dfree(c->d_pa_out);
-    c->pa_P = 0;
-    c->pa_cnt = c->pa_samples = c->pa_out_cap = 0;
-    c->pa_grid_blen.clear();
-    return EPV_OK;
-  }
+  if (n_points == 0) return layer_set_off(c, kPavg);
   int rc = check_ready(c, false);
   if (rc) return rc;
   if (n_points < 2) return fail(c, EPV_ERR_ARG, "a path average needs at least 2 points");
-  c->pa_P = n_points;
-  if ((rc = pavg_alloc(c))) return rc;
-  if ((rc = ensure_pavg(c))) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->pa.P = n_points;
+  if ((rc = relayout(c, kPavg, pavg_alloc)) || (rc = ensure_pavg(c))) return rc;   // (the grid as well)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }
 
 EPV_API int epv_reset_path_average(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_pa)
-    HIP_TRY(c, hipMemsetAsync(c->d_pa, 0, (size_t)4u * c->pa_B * c->pa_cnt * c->pa_P, c->stream));
+  const int rc = layer_entry(c, kPavg);
+  if (rc) return rc;
+  if (c->pa.d)
+    HIP_TRY(c, hipMemsetAsync(c->pa.d, 0, (size_t)4u * c->pa.at.B * c->pa.at.cnt * c->pa.P, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->pa_samples = 0;
+  c->pa.samples = 0;
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_path_average(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_pavg(c)) || (rc = launch_pavg(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_path_average(epv_ctx *c) { return layer_accumulate(c, kPavg); }
 
 EPV_API int epv_path_average_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->pa_P ? c->pa_samples : 0u;
+  *n = c->pa.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
@@ -3126,228 +3163,172 @@ EPV_API int epv_path_average_layout(epv_ctx *c, uint32_t *n_points, uint64_t *fi
   if (!c || !n_points || !first || !count) return EPV_ERR_ARG;
   *n_points = 0;
   *first = *count = 0;
-  if (!c->pa_P) return EPV_OK;
+  if (!c->pa.P) return EPV_OK;
   if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the sites as they are now)
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = ensure_pavg(c);
-    if (rc && c->pa_samples == 0) return rc;
+    if (rc && c->pa.samples == 0) return rc;
   }
-  *n_points = c->pa_P;
-  *first = c->pa_lo;
-  *count = c->pa_cnt;
+  *n_points = c->pa.P;
+  *first = c->pa.at.lo;
+  *count = c->pa.at.cnt;
   return EPV_OK;
 }
 
 EPV_API int epv_get_path_average(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *counts) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->pa_P) return fail(c, EPV_ERR_STATE, "path average is off: epv_set_path_average first");
+  int rc = layer_entry(c, kPavg);
+  if (rc) return rc;
   if (!counts) return fail(c, EPV_ERR_ARG, "null output");
-  if (first < c->pa_lo || first + count > c->pa_lo + c->pa_cnt)
+  if (first < c->pa.at.lo || first + count > c->pa.at.lo + c->pa.at.cnt)
     return fail(c, EPV_ERR_ARG, "site range outside the sites this context averages");
   if (count == 0) return EPV_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const uint64_t bytes = (uint64_t)4u * c->pa_B * count * c->pa_P;
-  if (bytes > c->pa_out_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_pa_out);
-    c->pa_out_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_pa_out, bytes));
-    c->pa_out_cap = bytes;
-  }
-  hipLaunchKernelGGL(epv_pavg_read_kernel, dim3((unsigned)((count + EPV_PAVG_RD - 1u) / EPV_PAVG_RD), c->pa_B),
-                     dim3(EPV_PAVG_RD), 0, c->stream, (const int32_t *)c->d_pa, c->pa_P, c->pa_cnt,
-                     first - c->pa_lo, count, c->d_pa_out);
+  const uint64_t bytes = (uint64_t)4u * c->pa.at.B * count * c->pa.P;
+  if ((rc = grow_staging(c, &c->pa.d_out, &c->pa.out_cap, bytes))) return rc;
+  hipLaunchKernelGGL(epv_pavg_read_kernel, dim3((unsigned)((count + EPV_PAVG_RD - 1u) / EPV_PAVG_RD), c->pa.at.B),
+                     dim3(EPV_PAVG_RD), 0, c->stream, (const int32_t *)c->pa.d, c->pa.P, c->pa.at.cnt,
+                     first - c->pa.at.lo, count, c->pa.d_out);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(counts, c->d_pa_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(counts, c->pa.d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }
 
 // ---- posterior branch-event maps (epv_bevents.h)
 EPV_API int epv_set_branch_events(epv_ctx *c, int on) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_be); dfree(c->d_be_out);
-    c->be_on = false;
-    c->be_cnt = c->be_samples = c->be_out_cap = 0;
-    return EPV_OK;
-  }
-  int rc = check_ready(c, false);
+  if (!on) return layer_set_off(c, kBevents);
+  const int rc = check_ready(c, false);
   if (rc) return rc;
-  c->be_on = true;
-  if ((rc = bevents_alloc(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
+  c->be.on = true;
+  return layer_set_on(c, kBevents, bevents_alloc);
 }
 
 EPV_API int epv_reset_branch_events(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_be)
-    HIP_TRY(c, hipMemsetAsync(c->d_be, 0, (size_t)4u * EPV_BEV_PLANES * c->be_B * c->be_cnt, c->stream));
+  const int rc = layer_entry(c, kBevents);
+  if (rc) return rc;
+  if (c->be.d)
+    HIP_TRY(c, hipMemsetAsync(c->be.d, 0, (size_t)4u * EPV_BEV_PLANES * c->be.at.B * c->be.at.cnt, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->be_samples = 0;
+  c->be.samples = 0;
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_branch_events(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_bevents(c)) || (rc = launch_bevents(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_branch_events(epv_ctx *c) { return layer_accumulate(c, kBevents); }
 
 EPV_API int epv_branch_events_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->be_on ? c->be_samples : 0u;
+  *n = c->be.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
 EPV_API int epv_branch_events_set_samples(epv_ctx *c, uint64_t n) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
-  c->be_samples = n;
+  const int rc = layer_entry(c, kBevents);
+  if (rc) return rc;
+  c->be.samples = n;
   return EPV_OK;
 }
 
 EPV_API int epv_branch_events_layout(epv_ctx *c, uint64_t *first, uint64_t *count) {
   if (!c || !first || !count) return EPV_ERR_ARG;
   *first = *count = 0;
-  if (!c->be_on) return EPV_OK;
+  if (!c->be.on) return EPV_OK;
   if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the sites as they are now)
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = ensure_bevents(c);
-    if (rc && c->be_samples == 0) return rc;
+    if (rc && c->be.samples == 0) return rc;
   }
-  *first = c->be_lo;
-  *count = c->be_cnt;
+  *first = c->be.at.lo;
+  *count = c->be.at.cnt;
   return EPV_OK;
 }
 
 EPV_API int epv_get_branch_events(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *planes) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  const int rc = layer_entry(c, kBevents);
+  if (rc) return rc;
   if (!planes) return fail(c, EPV_ERR_ARG, "null output");
-  if (first < c->be_lo || first + count > c->be_lo + c->be_cnt)
+  if (first < c->be.at.lo || first + count > c->be.at.lo + c->be.at.cnt)
     return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
   if (count == 0) return EPV_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // rows of `count` sites out of rows of be_cnt: [6 B][be_cnt] -> [6 B][count]
-  HIP_TRY(c, hipMemcpy2D(planes, count * 4u, c->d_be + (first - c->be_lo), c->be_cnt * 4u, count * 4u,
-                         (size_t)EPV_BEV_PLANES * c->be_B, hipMemcpyDeviceToHost));
+  // rows of `count` sites out of rows of at.cnt: [6 B][at.cnt] -> [6 B][count]
+  HIP_TRY(c, hipMemcpy2D(planes, count * 4u, c->be.d + (first - c->be.at.lo), c->be.at.cnt * 4u, count * 4u,
+                         (size_t)EPV_BEV_PLANES * c->be.at.B, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 
 EPV_API int epv_get_branch_event_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                          uint64_t *sums) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->be_on) return fail(c, EPV_ERR_STATE, "branch events are off: epv_set_branch_events first");
+  int rc = layer_entry(c, kBevents);
+  if (rc) return rc;
   if (!sums) return fail(c, EPV_ERR_ARG, "null output");
   if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
   if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
   if (n_windows == 0) return EPV_OK;
-  const uint64_t rows = (uint64_t)EPV_BEV_PLANES * c->be_B, bytes = rows * n_windows * 8u;
-  if (c->be_cnt == 0 || c->be_ng == 0) {   // this context counts no site
+  const uint64_t rows = (uint64_t)EPV_BEV_PLANES * c->be.at.B, bytes = rows * n_windows * 8u;
+  if (c->be.at.cnt == 0 || c->be.at.ng == 0) {   // this context counts no site
     std::memset(sums, 0, bytes);
     return EPV_OK;
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (bytes > c->be_out_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_be_out);
-    c->be_out_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_be_out, bytes));
-    c->be_out_cap = bytes;
-  }
-  if (W > c->be_ng) W = c->be_ng;   // one window holds the genome: the same sums, and w W cannot overflow
+  if ((rc = grow_staging(c, &c->be.d_out, &c->be.out_cap, bytes))) return rc;
+  if (W > c->be.at.ng) W = c->be.at.ng;   // one window holds the genome: the same sums, and w W cannot overflow
   uint32_t Wp = 256u;
   if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
   const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
   if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many windows in one call: read them out in pieces");
   hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, c->stream,
-                     (const uint32_t *)c->d_be, c->be_B, c->be_cnt, c->be_g0 + c->be_lo, c->be_ng, W, Wp, first_window,
-                     n_windows, c->d_be_out);
+                     (const uint32_t *)c->be.d, c->be.at.B, c->be.at.cnt, c->be.at.g0 + c->be.at.lo, c->be.at.ng, W, Wp, first_window,
+                     n_windows, c->be.d_out);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(sums, c->d_be_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(sums, c->be.d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }
 
 // ---- regional sufficient statistics (epv_wstat.h)
 EPV_API int epv_set_window_stats(epv_ctx *c, uint64_t W) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!W) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    wstat_off(c);
-    return EPV_OK;
-  }
-  int rc = check_ready(c, false);
+  if (!W) return layer_set_off(c, kWstat);
+  const int rc = check_ready(c, false);
   if (rc) return rc;
-  c->ws_W_asked = W;
-  if ((rc = wstat_alloc(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
+  c->ws.W_asked = W;
+  return layer_set_on(c, kWstat, wstat_alloc);
 }
 
 EPV_API int epv_reset_window_stats(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_ws) HIP_TRY(c, hipMemsetAsync(c->d_ws, 0, (size_t)128u * c->ws_B * c->ws_nw, c->stream));
+  const int rc = layer_entry(c, kWstat);
+  if (rc) return rc;
+  if (c->ws.d) HIP_TRY(c, hipMemsetAsync(c->ws.d, 0, (size_t)128u * c->ws.at.B * c->ws.nw, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->ws_samples = 0;
-  c->ws_scale.clear();
+  c->ws.samples = 0;
+  c->ws.scale.clear();
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_window_stats(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_wstat(c)) || (rc = launch_wstat(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_window_stats(epv_ctx *c) { return layer_accumulate(c, kWstat); }
 
 EPV_API int epv_window_stats_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->ws_W ? c->ws_samples : 0u;
+  *n = c->ws.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
 EPV_API int epv_window_stats_set_samples(epv_ctx *c, uint64_t n) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
-  if (n && c->ws_scale.empty()) {   // (as if the samples had been taken with the scales of now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_stat_scale(c);
-    if (rc) return rc;
-    c->ws_scale = c->statscale;
+  int rc = layer_entry(c, kWstat);
+  if (rc) return rc;
+  if (n && c->ws.scale.empty()) {   // (as if the samples had been taken with the scales of now)
+    if ((rc = ensure_stat_scale(c))) return rc;
+    c->ws.scale = c->statscale;
   }
-  c->ws_samples = n;
-  if (!n) c->ws_scale.clear();
+  c->ws.samples = n;
+  if (!n) c->ws.scale.clear();
   return EPV_OK;
 }
 
 EPV_API int epv_window_stats_scale_exps(epv_ctx *c, int *k) {
-  if (!c || !k) return EPV_ERR_ARG;
-  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  if (!k) return EPV_ERR_ARG;
+  int rc = layer_entry(c, kWstat);
+  if (rc) return rc;
   if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  if (c->ws_scale.empty()) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_stat_scale(c);
-    if (rc) return rc;
-  }
-  const std::vector<double> &sc = c->ws_scale.empty() ? c->statscale : c->ws_scale;
+  if (c->ws.scale.empty() && (rc = ensure_stat_scale(c))) return rc;
+  const std::vector<double> &sc = c->ws.scale.empty() ? c->statscale : c->ws.scale;
   for (uint32_t b = 1; b < c->S.N && b < sc.size(); ++b) k[b - 1u] = std::ilogb(sc[b]);   // (sc[b] = 2^k_b exactly)
   return EPV_OK;
 }
@@ -3355,91 +3336,71 @@ EPV_API int epv_window_stats_scale_exps(epv_ctx *c, int *k) {
 EPV_API int epv_window_stats_layout(epv_ctx *c, uint64_t *W, uint64_t *first_window, uint64_t *n_windows) {
   if (!c || !W || !first_window || !n_windows) return EPV_ERR_ARG;
   *W = *first_window = *n_windows = 0;
-  if (!c->ws_W) return EPV_OK;
-  if (c->have_tree && c->have_paths && c->ws_samples == 0) {   // lay out for the sites as they are now
+  if (!c->ws.W) return EPV_OK;
+  if (c->have_tree && c->have_paths && c->ws.samples == 0) {   // lay out for the sites as they are now
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_wstat(c);
     if (rc) return rc;
   }
-  *W = c->ws_W;
-  *first_window = c->ws_w0;
-  *n_windows = c->ws_nw;
+  *W = c->ws.W;
+  *first_window = c->ws.w0;
+  *n_windows = c->ws.nw;
   return EPV_OK;
 }
 
 EPV_API int epv_get_window_stats(epv_ctx *c, uint64_t first_window, uint64_t n_windows, int64_t *counts) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ws_W) return fail(c, EPV_ERR_STATE, "window statistics are off: epv_set_window_stats first");
+  const int rc = layer_entry(c, kWstat);
+  if (rc) return rc;
   if (!counts) return fail(c, EPV_ERR_ARG, "null output");
   if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
   if (n_windows == 0) return EPV_OK;
-  const uint64_t V = (uint64_t)c->ws_B * 16u;
+  const uint64_t V = (uint64_t)c->ws.at.B * 16u;
   std::memset(counts, 0, n_windows * V * sizeof(int64_t));
-  const uint64_t a = std::max(first_window, c->ws_w0), e = std::min(first_window + n_windows, c->ws_w0 + c->ws_nw);
-  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t a = std::max(first_window, c->ws.w0), e = std::min(first_window + n_windows, c->ws.w0 + c->ws.nw);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (a < e)
-    HIP_TRY(c, hipMemcpy(counts + (a - first_window) * V, c->d_ws + (a - c->ws_w0) * V, (e - a) * V * sizeof(int64_t),
+    HIP_TRY(c, hipMemcpy(counts + (a - first_window) * V, c->ws.d + (a - c->ws.w0) * V, (e - a) * V * sizeof(int64_t),
                          hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 
 // ---- lineage origin maps (epv_origin.h)
 EPV_API int epv_set_lineage_origins(epv_ctx *c, int on) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!on) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    origins_off(c);
-    return EPV_OK;
-  }
-  int rc = check_ready(c, false);
+  if (!on) return layer_set_off(c, kOrigins);
+  const int rc = check_ready(c, false);
   if (rc) return rc;
-  c->lo_on = true;
-  if ((rc = origins_alloc(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
+  c->lo.on = true;
+  return layer_set_on(c, kOrigins, origins_alloc);
 }
-
-static const char *const kOriginsOff = "lineage origins are off: epv_set_lineage_origins first";
 
 EPV_API int epv_reset_lineage_origins(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_lo) HIP_TRY(c, hipMemsetAsync(c->d_lo, 0, (size_t)4u * c->lo_R * c->lo_cnt, c->stream));
-  if (c->d_lo_age) HIP_TRY(c, hipMemsetAsync(c->d_lo_age, 0, (size_t)8u * c->lo_L * c->lo_cnt, c->stream));
+  const int rc = layer_entry(c, kOrigins);
+  if (rc) return rc;
+  if (c->lo.d) HIP_TRY(c, hipMemsetAsync(c->lo.d, 0, (size_t)4u * c->lo.R * c->lo.at.cnt, c->stream));
+  if (c->lo.d_age) HIP_TRY(c, hipMemsetAsync(c->lo.d_age, 0, (size_t)8u * c->lo.L * c->lo.at.cnt, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->lo_samples = 0;
+  c->lo.samples = 0;
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_lineage_origins(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_origins(c)) || (rc = launch_origins(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_lineage_origins(epv_ctx *c) { return layer_accumulate(c, kOrigins); }
 
 EPV_API int epv_lineage_origins_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->lo_on ? c->lo_samples : 0u;
+  *n = c->lo.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
 EPV_API int epv_lineage_origins_set_samples(epv_ctx *c, uint64_t n) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
-  c->lo_samples = n;
+  const int rc = layer_entry(c, kOrigins);
+  if (rc) return rc;
+  c->lo.samples = n;
   return EPV_OK;
 }
 
 // (no samples yet: lay out for the tree and the sites as they are now)
 static int origins_current(epv_ctx *c) {
-  if (!c->have_tree || !c->have_paths || c->lo_samples) return EPV_OK;
+  if (!c->have_tree || !c->have_paths || c->lo.samples) return EPV_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   return ensure_origins(c);
 }
@@ -3449,72 +3410,62 @@ EPV_API int epv_lineage_origins_layout(epv_ctx *c, uint32_t *n_leaves, uint32_t 
   if (!c || !n_leaves || !n_rows || !first || !count) return EPV_ERR_ARG;
   *n_leaves = *n_rows = 0;
   *first = *count = 0;
-  if (!c->lo_on) return EPV_OK;
+  if (!c->lo.on) return EPV_OK;
   const int rc = origins_current(c);
   if (rc) return rc;
-  *n_leaves = c->lo_L;
-  *n_rows = c->lo_R;
-  *first = c->lo_lo;
-  *count = c->lo_cnt;
+  *n_leaves = c->lo.L;
+  *n_rows = c->lo.R;
+  *first = c->lo.at.lo;
+  *count = c->lo.at.cnt;
   return EPV_OK;
 }
 
 EPV_API int epv_lineage_origin_rows(epv_ctx *c, uint32_t *leaf_node, uint32_t *branch_node) {
-  if (!c || !leaf_node || !branch_node) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
-  const int rc = origins_current(c);
-  if (rc) return rc;
-  std::copy(c->lo_leaf.begin(), c->lo_leaf.end(), leaf_node);
-  std::copy(c->lo_rowb.begin(), c->lo_rowb.end(), branch_node);
+  if (!leaf_node || !branch_node) return EPV_ERR_ARG;
+  int rc = layer_entry(c, kOrigins);
+  if (rc || (rc = origins_current(c))) return rc;
+  std::copy(c->lo.leaf.begin(), c->lo.leaf.end(), leaf_node);
+  std::copy(c->lo.rowb.begin(), c->lo.rowb.end(), branch_node);
   return EPV_OK;
 }
 
 EPV_API int epv_lineage_origins_scale_exp(epv_ctx *c, int *k) {
-  if (!c || !k) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
-  const int rc = origins_current(c);
-  if (rc) return rc;
-  *k = c->lo_k;
+  if (!k) return EPV_ERR_ARG;
+  int rc = layer_entry(c, kOrigins);
+  if (rc || (rc = origins_current(c))) return rc;
+  *k = c->lo.k;
   return EPV_OK;
 }
 
 EPV_API int epv_get_lineage_origins(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *origin, uint64_t *age) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  const int rc = layer_entry(c, kOrigins);
+  if (rc) return rc;
   if (!origin || !age) return fail(c, EPV_ERR_ARG, "null output");
-  if (first < c->lo_lo || first + count > c->lo_lo + c->lo_cnt)
+  if (first < c->lo.at.lo || first + count > c->lo.at.lo + c->lo.at.cnt)
     return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
   if (count == 0) return EPV_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // rows of `count` sites out of rows of lo_cnt
-  HIP_TRY(c, hipMemcpy2D(origin, count * 4u, c->d_lo + (first - c->lo_lo), c->lo_cnt * 4u, count * 4u, c->lo_R,
+  // rows of `count` sites out of rows of at.cnt
+  HIP_TRY(c, hipMemcpy2D(origin, count * 4u, c->lo.d + (first - c->lo.at.lo), c->lo.at.cnt * 4u, count * 4u, c->lo.R,
                          hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy2D(age, count * 8u, c->d_lo_age + (first - c->lo_lo), c->lo_cnt * 8u, count * 8u, c->lo_L,
+  HIP_TRY(c, hipMemcpy2D(age, count * 8u, c->lo.d_age + (first - c->lo.at.lo), c->lo.at.cnt * 8u, count * 8u, c->lo.L,
                          hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 
 EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                            uint64_t *out) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->lo_on) return fail(c, EPV_ERR_STATE, kOriginsOff);
+  int rc = layer_entry(c, kOrigins);
+  if (rc) return rc;
   if (!out) return fail(c, EPV_ERR_ARG, "null output");
   if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
   if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
   if (n_windows == 0) return EPV_OK;
-  const uint64_t rows = c->lo_R, bytes = rows * n_windows * 8u;
-  std::memset(out, 0, ((uint64_t)c->lo_R + c->lo_L) * n_windows * 8u);
-  if (c->lo_cnt == 0 || c->lo_ng == 0 || rows == 0) return EPV_OK;   // this context counts no site
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (bytes > c->lo_out_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_lo_out);
-    c->lo_out_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_lo_out, bytes));
-    c->lo_out_cap = bytes;
-  }
-  if (W > c->lo_ng) W = c->lo_ng;   // one window holds the genome: the same sums, and w W cannot overflow
+  const uint64_t rows = c->lo.R, bytes = rows * n_windows * 8u;
+  std::memset(out, 0, ((uint64_t)c->lo.R + c->lo.L) * n_windows * 8u);
+  if (c->lo.at.cnt == 0 || c->lo.at.ng == 0 || rows == 0) return EPV_OK;   // this context counts no site
+  if ((rc = grow_staging(c, &c->lo.d_out, &c->lo.out_cap, bytes))) return rc;
+  if (W > c->lo.at.ng) W = c->lo.at.ng;   // one window holds the genome: the same sums, and w W cannot overflow
   uint32_t Wp = 256u;
   if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
   const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
@@ -3524,29 +3475,29 @@ EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t firs
   for (uint64_t r0 = 0; r0 < rows; r0 += 65535u) {
     const uint64_t nr = std::min<uint64_t>(65535u, rows - r0);
     hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)nr), dim3(256), 0, c->stream,
-                       (const uint32_t *)c->d_lo + r0 * c->lo_cnt, c->lo_R, c->lo_cnt, c->lo_g0 + c->lo_lo, c->lo_ng, W,
-                       Wp, first_window, n_windows, c->d_lo_out + r0 * n_windows);
+                       (const uint32_t *)c->lo.d + r0 * c->lo.at.cnt, c->lo.R, c->lo.at.cnt, c->lo.at.g0 + c->lo.at.lo, c->lo.at.ng, W,
+                       Wp, first_window, n_windows, c->lo.d_out + r0 * n_windows);
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipMemcpyAsync(out, c->d_lo_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out, c->lo.d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // the ages are 64-bit cells, which the window kernel does not take: the counted sites that lie in the asked
   // windows come to the host and are added there, in 128 bits so that a sum beyond 64 is refused, not wrapped
-  const uint64_t glo = c->lo_g0 + c->lo_lo, n_win = (c->lo_ng + W - 1u) / W;
+  const uint64_t glo = c->lo.at.g0 + c->lo.at.lo, n_win = (c->lo.at.ng + W - 1u) / W;
   const uint64_t w_end = std::min(first_window + n_windows, n_win);
   if (first_window >= w_end) return EPV_OK;
-  const uint64_t a = std::max(first_window * W, glo), e = std::min(std::min(w_end * W, c->lo_ng), glo + c->lo_cnt);
+  const uint64_t a = std::max(first_window * W, glo), e = std::min(std::min(w_end * W, c->lo.at.ng), glo + c->lo.at.cnt);
   if (a >= e) return EPV_OK;
   // in pieces of sites (512 KB of cells on the host at a time, or 1024 sites of every leaf); a window that
   // straddles two pieces gets both parts
-  const uint64_t piece = std::max<uint64_t>(1024u, (1ull << 16) / c->lo_L);
+  const uint64_t piece = std::max<uint64_t>(1024u, (1ull << 16) / c->lo.L);
   try {
-    std::vector<unsigned long long> cells((size_t)c->lo_L * std::min(piece, e - a));
+    std::vector<unsigned long long> cells((size_t)c->lo.L * std::min(piece, e - a));
     for (uint64_t p0 = a; p0 < e; p0 += piece) {
       const uint64_t p1 = std::min(p0 + piece, e), len = p1 - p0;
-      HIP_TRY(c, hipMemcpy2D(cells.data(), len * 8u, c->d_lo_age + (p0 - glo), c->lo_cnt * 8u, len * 8u, c->lo_L,
+      HIP_TRY(c, hipMemcpy2D(cells.data(), len * 8u, c->lo.d_age + (p0 - glo), c->lo.at.cnt * 8u, len * 8u, c->lo.L,
                              hipMemcpyDeviceToHost));
-      for (uint32_t l = 0; l < c->lo_L; ++l) {
+      for (uint32_t l = 0; l < c->lo.L; ++l) {
         const unsigned long long *p = cells.data() + (size_t)l * len;
         uint64_t *o = out + (rows + l) * n_windows;
         for (uint64_t g = p0; g < p1;) {
@@ -3567,50 +3518,31 @@ EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t firs
 
 // ---- domain size spectra (epv_domains.h)
 EPV_API int epv_set_domain_stats(epv_ctx *c, uint64_t max_samples) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!max_samples) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    domains_off(c);
-    return EPV_OK;
-  }
+  if (!max_samples) return layer_set_off(c, kDomains);
   if (max_samples > EPV_DOM_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^21 samples");
-  int rc = check_ready(c, false);
+  const int rc = check_ready(c, false);
   if (rc) return rc;
-  c->dm_on = true;
-  c->dm_max = max_samples;
-  if ((rc = domains_alloc(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
+  c->dm.on = true;
+  c->dm.max = max_samples;
+  return layer_set_on(c, kDomains, domains_alloc);
 }
-
-static const char *const kDomainsOff = "domain statistics are off: epv_set_domain_stats first";
 
 EPV_API int epv_reset_domain_stats(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_hist, 0, (size_t)16u * EPV_DOM_BINS * c->dm_N, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_len, 0, (size_t)16u * c->dm_N, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->d_dm_edge, 0, (size_t)16u * c->dm_N * c->dm_max, c->stream));
+  const int rc = layer_entry(c, kDomains);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_hist, 0, (size_t)16u * EPV_DOM_BINS * c->dm.N, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_len, 0, (size_t)16u * c->dm.N, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->dm.d_edge, 0, (size_t)16u * c->dm.N * c->dm.max, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->dm_samples = 0;
+  c->dm.samples = 0;
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_domain_stats(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_domains(c)) || (rc = launch_domains(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_domain_stats(epv_ctx *c) { return layer_accumulate(c, kDomains); }
 
 EPV_API int epv_domain_stats_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->dm_on ? c->dm_samples : 0u;
+  *n = c->dm.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
@@ -3619,30 +3551,29 @@ EPV_API int epv_domain_stats_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_b
   if (!c || !n_nodes || !n_bins || !first || !count || !chunk_sites) return EPV_ERR_ARG;
   *n_nodes = *n_bins = 0;
   *first = *count = *chunk_sites = 0;
-  if (!c->dm_on) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->dm_samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+  if (!c->dm.on) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->dm.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_domains(c);
     if (rc) return rc;
   }
-  *n_nodes = c->dm_N;
+  *n_nodes = c->dm.N;
   *n_bins = EPV_DOM_BINS;
-  *first = c->dm_lo;
-  *count = c->dm_cnt;
+  *first = c->dm.at.lo;
+  *count = c->dm.at.cnt;
   *chunk_sites = 64ull * EPV_DOM_CHUNK_WORDS;
   return EPV_OK;
 }
 
 EPV_API int epv_get_domain_stats(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->dm_on) return fail(c, EPV_ERR_STATE, kDomainsOff);
+  const int rc = layer_entry(c, kDomains);
+  if (rc) return rc;
   if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(hist, c->d_dm_hist, (size_t)16u * EPV_DOM_BINS * c->dm_N, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(len_sum, c->d_dm_len, (size_t)16u * c->dm_N, hipMemcpyDeviceToHost));
-  if (c->dm_samples)
-    HIP_TRY(c, hipMemcpy(edges, c->d_dm_edge, (size_t)16u * c->dm_N * c->dm_samples, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(hist, c->dm.d_hist, (size_t)16u * EPV_DOM_BINS * c->dm.N, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(len_sum, c->dm.d_len, (size_t)16u * c->dm.N, hipMemcpyDeviceToHost));
+  if (c->dm.samples)
+    HIP_TRY(c, hipMemcpy(edges, c->dm.d_edge, (size_t)16u * c->dm.N * c->dm.samples, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 
@@ -3669,92 +3600,73 @@ EPV_API int epv_window_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64
 
 // ---- epoch statistics (epv_epochs.h)
 EPV_API int epv_set_epoch_stats(epv_ctx *c, uint32_t P) {
-  if (!c) return EPV_ERR_ARG;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!P) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    epoch_off(c);
-    return EPV_OK;
-  }
+  if (!P) return layer_set_off(c, kEpochs);
   if (P > EPV_EPOCH_MAX_P) return fail(c, EPV_ERR_ARG, "epoch statistics take at most EPV_EPOCH_MAX_P = 256 epochs");
+  if (!c) return EPV_ERR_ARG;
   if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
-  int rc = epoch_alloc(c, P);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
+  c->ep.P = P;
+  return layer_set_on(c, kEpochs, epoch_alloc);
 }
 
 EPV_API int epv_reset_epoch_stats(epv_ctx *c) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_ep) HIP_TRY(c, hipMemsetAsync(c->d_ep, 0, (size_t)256u * c->ep_B * c->ep_P, c->stream));
+  const int rc = layer_entry(c, kEpochs);
+  if (rc) return rc;
+  if (c->ep.d) HIP_TRY(c, hipMemsetAsync(c->ep.d, 0, (size_t)256u * c->ep.B * c->ep.P, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->ep_samples = 0;
-  c->ep_addends = 0;
-  c->ep_scale.clear();
-  c->ep_fixT.clear();
+  c->ep.samples = 0;
+  c->ep.addends = 0;
+  c->ep.scale.clear();
+  c->ep.fixT.clear();
   return EPV_OK;
 }
 
-EPV_API int epv_accumulate_epoch_stats(epv_ctx *c) {
-  int rc = check_ready(c, false);
-  if (rc) return rc;
-  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = ensure_epochs(c)) || (rc = launch_epochs(c))) return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return EPV_OK;
-}
+EPV_API int epv_accumulate_epoch_stats(epv_ctx *c) { return layer_accumulate(c, kEpochs); }
 
 EPV_API int epv_epoch_stats_samples(epv_ctx *c, uint64_t *n) {
   if (!c || !n) return EPV_ERR_ARG;
-  *n = c->ep_P ? c->ep_samples : 0u;
+  *n = c->ep.samples;   // (0 while the layer is off)
   return EPV_OK;
 }
 
 EPV_API int epv_epoch_stats_set_samples(epv_ctx *c, uint64_t n) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
-  if (n && c->ep_scale.empty()) {   // (as if the samples had been taken with the scales of now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_stat_scale(c);
-    if (rc) return rc;
+  int rc = layer_entry(c, kEpochs);
+  if (rc) return rc;
+  if (n && c->ep.scale.empty()) {   // (as if the samples had been taken with the scales of now)
+    if ((rc = ensure_stat_scale(c))) return rc;
     epoch_remember(c);
   }
-  c->ep_samples = n;
-  c->ep_addends = n * epoch_blocks(c);   // (as if every one had been taken over the sites of now)
-  if (!n) { c->ep_scale.clear(); c->ep_fixT.clear(); }
+  c->ep.samples = n;
+  c->ep.addends = n * epoch_blocks(c);   // (as if every one had been taken over the sites of now)
+  if (!n) { c->ep.scale.clear(); c->ep.fixT.clear(); }
   return EPV_OK;
 }
 
 EPV_API int epv_epoch_stats_layout(epv_ctx *c, uint32_t *B, uint32_t *P, int *k, uint64_t *fixT) {
   if (!c || !B || !P) return EPV_ERR_ARG;
   *B = *P = 0;
-  if (!c->ep_P) return EPV_OK;
+  if (!c->ep.P) return EPV_OK;
   if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");
   HIP_TRY(c, hipSetDevice(c->device));
-  if (c->ep_samples == 0) {   // lay out for the tree as it is now
+  if (c->ep.samples == 0) {   // lay out for the tree as it is now
     const int rc = ensure_epochs(c);
     if (rc) return rc;
   }
-  const std::vector<double> &sc = c->ep_scale.empty() ? c->statscale : c->ep_scale;
-  *B = c->ep_B;
-  *P = c->ep_P;
-  for (uint32_t b = 1; b <= c->ep_B && b < sc.size(); ++b) {
+  const std::vector<double> &sc = c->ep.scale.empty() ? c->statscale : c->ep.scale;
+  *B = c->ep.B;
+  *P = c->ep.P;
+  for (uint32_t b = 1; b <= c->ep.B && b < sc.size(); ++b) {
     if (k) k[b - 1u] = std::ilogb(sc[b]);                                   // (sc[b] = 2^k_b exactly)
-    if (fixT) fixT[b - 1u] = c->ep_fixT.empty() ? (uint64_t)std::llrint(c->blen[b] * sc[b]) : c->ep_fixT[b];
+    if (fixT) fixT[b - 1u] = c->ep.fixT.empty() ? (uint64_t)std::llrint(c->blen[b] * sc[b]) : c->ep.fixT[b];
   }
   return EPV_OK;
 }
 
 EPV_API int epv_get_epoch_stats(epv_ctx *c, uint64_t *raw) {
-  if (!c) return EPV_ERR_ARG;
-  if (!c->ep_P) return fail(c, EPV_ERR_STATE, "epoch statistics are off: epv_set_epoch_stats first");
+  const int rc = layer_entry(c, kEpochs);
+  if (rc) return rc;
   if (!raw) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const size_t bytes = (size_t)256u * c->ep_B * c->ep_P;
-  if (bytes) HIP_TRY(c, hipMemcpy(raw, c->d_ep, bytes, hipMemcpyDeviceToHost));
+  const size_t bytes = (size_t)256u * c->ep.B * c->ep.P;
+  if (bytes) HIP_TRY(c, hipMemcpy(raw, c->ep.d, bytes, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
