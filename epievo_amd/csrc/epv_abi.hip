@@ -26,6 +26,7 @@
 #include "epv_epochs.h"
 #include "epv_origin.h"
 #include "epv_domains.h"
+#include "epv_patterns.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
 // Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
@@ -149,6 +150,18 @@ struct DomainsState {
   std::vector<uint32_t> parent;           // the tree they were laid out for
 };
 
+// change patterns (epv_patterns.h), off while !on
+struct PatternsState {
+  bool on = false;
+  uint32_t *d = nullptr;                  // [R][at.cnt] counts over local sites at.lo .. at.lo + at.cnt - 1
+  SiteLayout at;
+  uint32_t I = 0, R = 0;                  // clade rows and all rows of the tree they were laid out for
+  uint64_t samples = 0;
+  std::vector<uint32_t> subtree;          // the tree's pre-order subtree sizes: what the row layout depends on
+  unsigned long long *d_out = nullptr;    // window read-out staging
+  uint64_t out_cap = 0;                   // bytes
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -237,6 +250,7 @@ struct epv_ctx {
   EpochState ep;
   OriginsState lo;
   DomainsState dm;
+  PatternsState pt;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -737,7 +751,7 @@ struct Layer {
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -1243,6 +1257,68 @@ int launch_domains(epv_ctx *c) {
 const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off,
                         "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
 
+// ---- change patterns (epv_patterns.h): the sites of pavg_range, R = 12 + 2 B + I uint32 rows
+bool patterns_on(const epv_ctx *c) { return c->pt.on; }
+void patterns_off(epv_ctx *c) {
+  dfree(c->pt.d); dfree(c->pt.d_out);
+  c->pt = PatternsState{};
+}
+// (re)lay out the rows for the current tree and site range; zeroes them
+int patterns_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, true);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->pt.d);
+  uint32_t I = 0;
+  for (uint32_t v = 1; v < c->S.N; ++v) I += c->subtree[v] > 1u;
+  const uint32_t R = EPV_PAT_FIXED + 2u * c->S.B + I;
+  const double need = 4.0 * (double)R * (double)at.cnt;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "change patterns need %.3g GB of device memory (4 B x %u rows x %llu sites); "
+                  "%.3g GB are free: use more GPUs (the counters are off)",
+                  need / 1e9, R, (unsigned long long)at.cnt, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t bytes = (size_t)4u * R * at.cnt;
+  if (bytes) {
+    HIP_TRY(c, hipMalloc(&c->pt.d, bytes));
+    HIP_TRY(c, hipMemsetAsync(c->pt.d, 0, bytes, c->stream));
+  }
+  c->pt.at = at;
+  c->pt.I = I;
+  c->pt.R = R;
+  c->pt.samples = 0;
+  c->pt.subtree = c->subtree;
+  return EPV_OK;
+}
+// the rows match the current site range and tree (branch lengths do not matter: no jump time is read)
+int ensure_patterns(epv_ctx *c) {
+  const bool sites = !(pavg_layout(c, true, true) == c->pt.at);
+  if (!sites && c->subtree == c->pt.subtree) return EPV_OK;
+  if (c->pt.samples) {
+    if (sites) return sites_changed(c, kPatterns, "epv_set_change_patterns");
+    return fail(c, EPV_ERR_STATE, "the tree changed after the change patterns took samples: read them out and "
+                                  "epv_reset_change_patterns");
+  }
+  return relayout(c, kPatterns, patterns_alloc);
+}
+int patterns_check_cap(epv_ctx *, uint64_t) { return EPV_OK; }   // (no cap is kept: a count takes at most one per sample)
+// the resident paths as one sample (ensure_patterns first)
+int launch_patterns(epv_ctx *c) {
+  if (c->pt.at.cnt)
+    hipLaunchKernelGGL(epv_patterns_accum_kernel, dim3((unsigned)((c->pt.at.cnt + 255u) / 256u)), dim3(256), 0, c->stream,
+                       c->S, c->pt.at.lo, c->pt.at.cnt, c->pt.I, c->pt.d);
+  ++c->pt.samples;
+  HIP_TRY(c, hipGetLastError());
+  return EPV_OK;
+}
+const Layer kPatterns = {patterns_on, ensure_patterns, patterns_check_cap, launch_patterns, patterns_off,
+                         "change patterns are off: epv_set_change_patterns first", "the change patterns"};
+
 // ---- epoch statistics (epv_epochs.h): J and D per branch and epoch of the branch, over the triples centred
 // at the sites of owned_range.  The accumulator [B][P][32] does not depend on the site range
 bool epoch_on(const epv_ctx *c) { return c->ep.P != 0u; }
@@ -1344,7 +1420,7 @@ const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, 
 
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
-const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains};
+const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -1659,6 +1735,34 @@ int layer_accumulate(epv_ctx *c, const Layer &L) {
   if (!L.on(c)) return fail(c, EPV_ERR_STATE, L.off_msg);
   HIP_TRY(c, hipSetDevice(c->device));
   if ((rc = L.ensure(c)) || (rc = L.launch(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+// window sums of `rows` uint32 rows [rows][at.cnt] over the sites of pavg_range (the branch events, the change
+// patterns): sums[row][w - first_window] through epv_bevents_window_kernel, this context's contribution
+int row_window_sums(epv_ctx *c, const uint32_t *acc, uint64_t rows, const SiteLayout &at, unsigned long long **d_out,
+                    uint64_t *out_cap, uint64_t W, uint64_t first_window, uint64_t n_windows, uint64_t *sums) {
+  if (!sums) return fail(c, EPV_ERR_ARG, "null output");
+  if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
+  if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
+  if (n_windows == 0) return EPV_OK;
+  const uint64_t bytes = rows * n_windows * 8u;
+  if (at.cnt == 0 || at.ng == 0) {   // this context counts no site
+    std::memset(sums, 0, bytes);
+    return EPV_OK;
+  }
+  const int rc = grow_staging(c, d_out, out_cap, bytes);
+  if (rc) return rc;
+  if (W > at.ng) W = at.ng;   // one window holds the genome: the same sums, and w W cannot overflow
+  uint32_t Wp = 256u;
+  if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
+  const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
+  if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many windows in one call: read them out in pieces");
+  hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, c->stream, acc,
+                     at.B, at.cnt, at.g0 + at.lo, at.ng, W, Wp, first_window, n_windows, *d_out);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(sums, *d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return EPV_OK;
 }
@@ -3257,30 +3361,78 @@ EPV_API int epv_get_branch_events(epv_ctx *c, uint64_t first, uint64_t count, ui
 
 EPV_API int epv_get_branch_event_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                          uint64_t *sums) {
-  int rc = layer_entry(c, kBevents);
+  const int rc = layer_entry(c, kBevents);
   if (rc) return rc;
-  if (!sums) return fail(c, EPV_ERR_ARG, "null output");
-  if (W == 0) return fail(c, EPV_ERR_ARG, "a window holds at least one site");
-  if (first_window + n_windows < first_window) return fail(c, EPV_ERR_ARG, "window range overflows");
-  if (n_windows == 0) return EPV_OK;
-  const uint64_t rows = (uint64_t)EPV_BEV_PLANES * c->be.at.B, bytes = rows * n_windows * 8u;
-  if (c->be.at.cnt == 0 || c->be.at.ng == 0) {   // this context counts no site
-    std::memset(sums, 0, bytes);
-    return EPV_OK;
-  }
-  if ((rc = grow_staging(c, &c->be.d_out, &c->be.out_cap, bytes))) return rc;
-  if (W > c->be.at.ng) W = c->be.at.ng;   // one window holds the genome: the same sums, and w W cannot overflow
-  uint32_t Wp = 256u;
-  if (W <= 64u) for (Wp = 1u; Wp < W; Wp <<= 1) {}
-  const uint64_t per_block = 256u / Wp, blocks = (n_windows + per_block - 1u) / per_block;
-  if (blocks > 0x7fffffffull) return fail(c, EPV_ERR_ARG, "too many windows in one call: read them out in pieces");
-  hipLaunchKernelGGL(epv_bevents_window_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, c->stream,
-                     (const uint32_t *)c->be.d, c->be.at.B, c->be.at.cnt, c->be.at.g0 + c->be.at.lo, c->be.at.ng, W, Wp, first_window,
-                     n_windows, c->be.d_out);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(sums, c->be.d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  return row_window_sums(c, c->be.d, (uint64_t)EPV_BEV_PLANES * c->be.at.B, c->be.at, &c->be.d_out, &c->be.out_cap, W,
+                         first_window, n_windows, sums);
+}
+
+// ---- change patterns (epv_patterns.h)
+EPV_API int epv_set_change_patterns(epv_ctx *c, int on) {
+  if (!on) return layer_set_off(c, kPatterns);
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->pt.on = true;
+  return layer_set_on(c, kPatterns, patterns_alloc);
+}
+
+EPV_API int epv_reset_change_patterns(epv_ctx *c) {
+  const int rc = layer_entry(c, kPatterns);
+  if (rc) return rc;
+  if (c->pt.d) HIP_TRY(c, hipMemsetAsync(c->pt.d, 0, (size_t)4u * c->pt.R * c->pt.at.cnt, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->pt.samples = 0;
   return EPV_OK;
+}
+
+EPV_API int epv_accumulate_change_patterns(epv_ctx *c) { return layer_accumulate(c, kPatterns); }
+
+EPV_API int epv_change_patterns_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->pt.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_change_patterns_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *n_clades, uint32_t *clade_node,
+                                       uint64_t *first, uint64_t *count) {
+  if (!c || !n_rows || !n_clades || !first || !count) return EPV_ERR_ARG;
+  *n_rows = *n_clades = 0;
+  *first = *count = 0;
+  if (!c->pt.on) return EPV_OK;
+  if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_patterns(c);
+    if (rc && c->pt.samples == 0) return rc;
+  }
+  *n_rows = c->pt.R;
+  *n_clades = c->pt.I;
+  *first = c->pt.at.lo;
+  *count = c->pt.at.cnt;
+  if (clade_node)
+    for (uint32_t v = 1, j = 0; v < c->pt.subtree.size(); ++v)
+      if (c->pt.subtree[v] > 1u) clade_node[j++] = v;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_change_patterns(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *rows) {
+  const int rc = layer_entry(c, kPatterns);
+  if (rc) return rc;
+  if (!rows) return fail(c, EPV_ERR_ARG, "null output");
+  if (first < c->pt.at.lo || first + count > c->pt.at.lo + c->pt.at.cnt)
+    return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
+  if (count == 0) return EPV_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // rows of `count` sites out of rows of at.cnt: [R][at.cnt] -> [R][count]
+  HIP_TRY(c, hipMemcpy2D(rows, count * 4u, c->pt.d + (first - c->pt.at.lo), c->pt.at.cnt * 4u, count * 4u, c->pt.R,
+                         hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+EPV_API int epv_get_change_pattern_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                           uint64_t *sums) {
+  const int rc = layer_entry(c, kPatterns);
+  if (rc) return rc;
+  return row_window_sums(c, c->pt.d, c->pt.R, c->pt.at, &c->pt.d_out, &c->pt.out_cap, W, first_window, n_windows, sums);
 }
 
 // ---- regional sufficient statistics (epv_wstat.h)

@@ -28,6 +28,10 @@
 // New: -E/--epochs FILE with -K/--nepochs P (default 10): the epoch statistics of the B batch sweeps
 // (epv_set_epoch_stats: J and D per branch and epoch of the branch as exact integers, with the epoch's rate factor
 // under the model of the run; epv::write_epoch_stats).  Changes nothing else the run writes.
+// New: -P/--patterns FILE with the same -w/--window W: the change patterns of the B batch sweeps
+// (epv_set_change_patterns: per site what happened across the branches of the tree -- the jump spectrum, one-branch,
+// parallel and reverted changes, sole gains and losses per branch, changed clades), summed over windows of W sites,
+// as integers (epv::write_change_patterns).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -53,7 +57,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
@@ -87,9 +91,11 @@ int main(int argc, const char **argv) {
                       false, domains_file);
     opt_parse.add_opt("epochs", 'E', "output file of J and D per branch and epoch of the batch sweeps, with rate factors",
                       false, epochs_file);
+    opt_parse.add_opt("patterns", 'P', "output file of the change patterns of the batch sweeps (integer window sums)",
+                      false, patterns_file);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
-    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics and origin maps "
-                      "(default 1)", false, window);
+    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps and "
+                      "change patterns (default 1)", false, window);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -110,9 +116,11 @@ int main(int argc, const char **argv) {
     }
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
-    if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty())
-      throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional and -O/--origins: give the output "
-                               "file of the branch-event maps, of the regional statistics or of the origin maps");
+    if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty() &&
+        patterns_file.empty())
+      throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional, -O/--origins and -P/--patterns: "
+                               "give the output file of the branch-event maps, of the regional statistics, of the "
+                               "origin maps or of the change patterns");
     if (n_epochs != no_epochs && epochs_file.empty())
       throw std::runtime_error("-K/--nepochs belongs to -E/--epochs: give the output file of the epoch statistics");
     if (n_epochs == no_epochs) n_epochs = 10;
@@ -164,6 +172,7 @@ int main(int argc, const char **argv) {
     if (!origins_file.empty()) mcmc.set_lineage_origins(true);
     if (!domains_file.empty()) mcmc.set_domain_stats(batch);
     if (!epochs_file.empty()) mcmc.set_epoch_stats((uint32_t)n_epochs);
+    if (!patterns_file.empty()) mcmc.set_change_patterns(true);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -228,6 +237,15 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING EPOCH STATISTICS OF " << n_samples << " SAMPLES: " << epochs_file << "]" << endl;
       epv::write_epoch_stats(epochs_file, th.node_names, th.n_nodes(), (uint32_t)n_epochs, th.branches.data(),
                              scale_exp.data(), fixT.data(), closed.data(), n_samples, the_model.rates);
+    }
+    if (!patterns_file.empty()) {
+      vector<uint64_t> sums;
+      uint32_t n_rows = 0;
+      uint64_t n_samples = 0;
+      mcmc.download_change_pattern_windows(window, sums, n_rows, n_samples);
+      if (VERBOSE) cerr << "[WRITING CHANGE PATTERNS OF " << n_samples << " SAMPLES: " << patterns_file << "]" << endl;
+      epv::write_change_patterns(patterns_file, th.node_names, th.subtree_sizes, n_rows, out.n_sites,
+                                 mcmc.branch_event_windows(window), window, sums.data(), n_samples);
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

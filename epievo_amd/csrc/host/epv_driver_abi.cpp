@@ -21,6 +21,8 @@ struct epvd_sampler {
   bool have_staged_avg = false;
   std::vector<uint32_t> staged_events;   // between epvd_branch_events_sizes and epvd_download_branch_events
   bool have_staged_events = false;
+  std::vector<uint32_t> staged_patterns;   // between epvd_change_patterns_sizes and epvd_download_change_patterns
+  bool have_staged_patterns = false;
   std::vector<int64_t> staged_wstat;   // between epvd_window_stats_sizes and epvd_download_window_stats
   uint64_t staged_wstat_nw = 0, staged_wstat_ns = 0;
   bool have_staged_wstat = false;
@@ -232,6 +234,43 @@ EPVD_API int epvd_download_branch_event_windows(epvd_sampler *h, uint64_t W, uin
     if (n_windows != h->s->branch_event_windows(W))
       throw std::runtime_error("epvd_download_branch_event_windows: n_windows must be ceil(genome length / W), W >= 1");
     h->s->download_branch_event_windows(W, v, ns);
+    std::copy(v.begin(), v.end(), sums);
+    if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_change_patterns(epvd_sampler *h, int on) {
+  return guarded(h, [&] { h->s->set_change_patterns(on != 0); });
+}
+EPVD_API int epvd_change_patterns_sizes(epvd_sampler *h, uint64_t *n_values, uint32_t *n_rows, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    uint64_t ns = 0;
+    uint32_t R = 0;
+    h->s->download_change_patterns(h->staged_patterns, R, ns);
+    h->have_staged_patterns = true;
+    *n_values = h->staged_patterns.size();
+    *n_rows = R;
+    *n_samples = ns;
+  });
+}
+EPVD_API int epvd_download_change_patterns(epvd_sampler *h, uint32_t *rows) {
+  return guarded(h, [&] {
+    if (!h->have_staged_patterns) throw std::runtime_error("epvd_change_patterns_sizes first");
+    std::copy(h->staged_patterns.begin(), h->staged_patterns.end(), rows);
+    h->staged_patterns.clear();
+    h->have_staged_patterns = false;
+  });
+}
+EPVD_API int epvd_download_change_pattern_windows(epvd_sampler *h, uint64_t W, uint32_t n_rows, uint64_t n_windows,
+                                                  uint64_t *sums, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> v;
+    uint64_t ns = 0;
+    uint32_t R = 0;
+    if (n_windows != h->s->branch_event_windows(W))
+      throw std::runtime_error("epvd_download_change_pattern_windows: n_windows must be ceil(genome length / W), W >= 1");
+    h->s->download_change_pattern_windows(W, v, R, ns);
+    if (R != n_rows) throw std::runtime_error("epvd_download_change_pattern_windows: n_rows must be the rows of epvd_change_patterns_sizes");
     std::copy(v.begin(), v.end(), sums);
     if (n_samples) *n_samples = ns;
   });

@@ -677,6 +677,31 @@ void write_branch_events(const std::string &file, const std::vector<std::string>
   if (!out) throw std::runtime_error("error writing: " + file);
 }
 
+void write_change_patterns(const std::string &file, const std::vector<std::string> &node_names,
+                           const std::vector<uint32_t> &subtree_sizes, uint32_t n_rows, uint64_t n_sites,
+                           uint64_t n_windows, uint64_t window, const uint64_t *sums, uint64_t n_samples) {
+  const size_t N = subtree_sizes.size();
+  std::vector<std::string> names = {"jumps_1", "jumps_2", "jumps_3", "jumps_4", "jumps_5", "jumps_6", "jumps_7plus",
+                                    "one_branch", "parallel_gain", "parallel_loss", "gain_and_loss", "reverted_only"};
+  for (size_t v = 1; v < N; ++v) names.push_back("sole_gain:" + node_names[v]);
+  for (size_t v = 1; v < N; ++v) names.push_back("sole_loss:" + node_names[v]);
+  for (size_t v = 1; v < N; ++v) if (subtree_sizes[v] > 1u) names.push_back("clade_changed:" + node_names[v]);
+  if (names.size() != n_rows) throw std::runtime_error("change patterns: the rows do not belong to this tree");
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#samples\t" << n_samples << "\twindow\t" << window << "\tsites\t" << n_sites << '\n';
+  out << "#rows";
+  for (const std::string &s : names) out << "\t" << s;
+  out << '\n';
+  for (uint64_t w = 0; w < n_windows; ++w) {
+    out << w * window;
+    for (uint64_t r = 0; r < n_rows; ++r) out << "\t" << sums[r * n_windows + w];
+    out << '\n';
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
 void write_window_stats(const std::string &file, const std::vector<std::string> &node_names, int n_nodes,
                         uint64_t n_windows, uint64_t window, const double *branch_len, const int *scale_exp,
                         const int64_t *counts, uint64_t n_samples, const double *J, const double *D,

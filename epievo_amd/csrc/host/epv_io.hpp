@@ -66,6 +66,15 @@ void write_branch_events(const std::string &file, const std::vector<std::string>
                          uint64_t n_windows, uint64_t window, const double *branch_len, const uint64_t *sums,
                          uint64_t n_samples);
 
+// the window sums of the change-pattern rows (epv_get_change_pattern_windows), integers only:
+// "#samples\t<S>\twindow\t<W>\tsites\t<n>", a line "#rows" with the name of every row (jumps_1 .. jumps_6,
+// jumps_7plus, one_branch, parallel_gain, parallel_loss, gain_and_loss, reverted_only, sole_gain:<node> and
+// sole_loss:<node> per non-root node, clade_changed:<node> per internal non-root node, from subtree_sizes), then one
+// line per window: the window's first global site and sums[r * n_windows + w] for the rows r, tab-separated
+void write_change_patterns(const std::string &file, const std::vector<std::string> &node_names,
+                           const std::vector<uint32_t> &subtree_sizes, uint32_t n_rows, uint64_t n_sites,
+                           uint64_t n_windows, uint64_t window, const uint64_t *sums, uint64_t n_samples);
+
 // the regional sufficient statistics of epievo_est_histories -r (epv_get_window_stats):
 //   "#samples\t<S>\twindow\t<W>", then per non-root node in pre-order "NODE:<name>\t<branch length>\t<k_b>"
 //   (%.17g; D integers are in units of 2^-k_b) and one line per window: its first global site, J[0..7] and

@@ -434,6 +434,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (epoch_P_) set_epoch_stats(epoch_P_);
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
+  if (patterns_) set_change_patterns(true);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -446,6 +447,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (epoch_P_) set_epoch_stats(epoch_P_);
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
+  if (patterns_) set_change_patterns(true);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -536,6 +538,66 @@ void SingleSiteSampler::download_branch_event_windows(uint64_t W, std::vector<ui
   std::vector<uint64_t> part(R * nw);
   for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites
     check_on(c, epv_get_branch_event_windows(c, W, 0u, nw, part.data()), "epv_get_branch_event_windows");
+    for (size_t k = 0; k < part.size(); ++k) sums[k] += part[k];
+  }
+}
+
+void SingleSiteSampler::set_change_patterns(bool on) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !on)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_change_patterns(c, on ? 1 : 0), "epv_set_change_patterns");
+  patterns_ = on;
+}
+
+// the sample count and the row count, the same on every context; first and count per context when asked for
+void SingleSiteSampler::change_pattern_layouts(const std::vector<epv_ctx *> &cs, uint32_t &n_rows, uint64_t &n_samples,
+                                               std::vector<uint64_t> *first, std::vector<uint64_t> *count) {
+  n_rows = 0;
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t R = 0, I = 0;
+    uint64_t a = 0, k = 0, ns = 0;
+    check_on(cs[i], epv_change_patterns_layout(cs[i], &R, &I, nullptr, &a, &k), "epv_change_patterns_layout");
+    check_on(cs[i], epv_change_patterns_samples(cs[i], &ns), "epv_change_patterns_samples");
+    if (i == 0) { n_rows = R; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of change-pattern samples");
+    else if (R != n_rows) throw std::runtime_error("the contexts hold different numbers of change-pattern rows");
+    if (first) (*first)[i] = a;
+    if (count) (*count)[i] = k;
+  }
+}
+
+void SingleSiteSampler::download_change_patterns(std::vector<uint32_t> &rows, uint32_t &n_rows, uint64_t &n_samples) {
+  if (!patterns_) throw std::runtime_error("change patterns are off: set_change_patterns first");
+  const std::vector<epv_ctx *> cs = contexts();
+  std::vector<uint64_t> first(cs.size()), count(cs.size());
+  change_pattern_layouts(cs, n_rows, n_samples, &first, &count);
+  const uint64_t R = n_rows;
+  uint64_t total = 0;
+  for (uint64_t k : count) total += k;
+  rows.assign(R * total, 0u);
+  std::vector<uint32_t> part;
+  uint64_t at = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {   // contexts in genome order, each one's sites contiguous
+    part.assign(R * count[i], 0u);
+    if (count[i]) check_on(cs[i], epv_get_change_patterns(cs[i], first[i], count[i], part.data()), "epv_get_change_patterns");
+    for (uint64_t r = 0; r < R; ++r)
+      std::copy(part.begin() + r * count[i], part.begin() + (r + 1) * count[i], rows.begin() + r * total + at);
+    at += count[i];
+  }
+}
+
+void SingleSiteSampler::download_change_pattern_windows(uint64_t W, std::vector<uint64_t> &sums, uint32_t &n_rows,
+                                                        uint64_t &n_samples) {
+  if (!patterns_) throw std::runtime_error("change patterns are off: set_change_patterns first");
+  if (W == 0) throw std::runtime_error("a window holds at least one site");
+  const std::vector<epv_ctx *> cs = contexts();
+  change_pattern_layouts(cs, n_rows, n_samples, nullptr, nullptr);
+  const uint64_t nw = (n_sites_ + W - 1u) / W;
+  sums.assign((uint64_t)n_rows * nw, 0u);
+  std::vector<uint64_t> part(sums.size());
+  for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites
+    check_on(c, epv_get_change_pattern_windows(c, W, 0u, nw, part.data()), "epv_get_change_pattern_windows");
     for (size_t k = 0; k < part.size(); ++k) sums[k] += part[k];
   }
 }

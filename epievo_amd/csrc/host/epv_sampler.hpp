@@ -161,6 +161,14 @@ public:
                             uint32_t &n_nodes, uint64_t &n_samples);
   void download_domain_stats(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_nodes,
                              uint64_t &n_samples);
+  // change patterns (epv_set_change_patterns) on every context, with the branch events' samples and lifecycle.
+  // n_rows = 12 + 2 (n_nodes-1) + internal non-root nodes.  download_change_patterns: rows[r * sites + site] over
+  // the sites of this process in genome order; download_change_pattern_windows: sums[r * n_windows + w] over
+  // windows of W global sites, all slots and contexts of this process added
+  void set_change_patterns(bool on);
+  bool change_patterns_on() const { return patterns_; }
+  void download_change_patterns(std::vector<uint32_t> &rows, uint32_t &n_rows, uint64_t &n_samples);
+  void download_change_pattern_windows(uint64_t W, std::vector<uint64_t> &sums, uint32_t &n_rows, uint64_t &n_samples);
   // epoch statistics (epv_set_epoch_stats) on every context: J and D per branch and epoch, with the window
   // statistics' samples and lifecycle (P = 0: off).  download_epoch_stats: the raw parts of all slots and
   // contexts of this process added as integers and closed once (epv::epoch_close):
@@ -242,6 +250,8 @@ private:
   void check(int rc, const char *what);
   void check_mcmc(int rc, const char *what);
   void check_on(epv_ctx *c, int rc, const char *what);
+  void change_pattern_layouts(const std::vector<epv_ctx *> &cs, uint32_t &n_rows, uint64_t &n_samples,
+                              std::vector<uint64_t> *first, std::vector<uint64_t> *count);
   void check_comm(epv_comm *c, int rc, const char *what);
   bool sharded() const { return !parts_.empty(); }
   void drop_parts();          // back to the single context ctx_
@@ -273,6 +283,7 @@ private:
   uint32_t epoch_P_ = 0;      // set_epoch_stats
   bool origins_ = false;      // set_lineage_origins
   uint64_t domains_max_ = 0; // set_domain_stats
+  bool patterns_ = false;     // set_change_patterns
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

@@ -24,7 +24,9 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_lineage_origin_rows", "epvd_lineage_origins_scale_exp", "epvd_lineage_origins_sizes", "epvd_download_lineage_origins",
                   "epvd_download_lineage_origin_windows",
                   "epvd_set_domain_stats", "epvd_reset_domain_stats", "epvd_accumulate_domain_stats",
-                  "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats"]
+                  "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats",
+                  "epvd_set_change_patterns", "epvd_change_patterns_sizes", "epvd_download_change_patterns",
+                  "epvd_download_change_pattern_windows"]
 
 
 def lib():
@@ -62,6 +64,10 @@ def lib():
         L.epvd_branch_events_sizes.argtypes = [vp, u64p, u64p]
         L.epvd_download_branch_events.argtypes = [vp, u32p]
         L.epvd_download_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, u64p]
+        L.epvd_set_change_patterns.argtypes = [vp, C.c_int]
+        L.epvd_change_patterns_sizes.argtypes = [vp, u64p, u32p, u64p]
+        L.epvd_download_change_patterns.argtypes = [vp, u32p]
+        L.epvd_download_change_pattern_windows.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p, u64p]
         L.epvd_set_window_stats.argtypes = [vp, C.c_uint64]
         L.epvd_window_stats_sizes.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_window_stats.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
@@ -122,7 +128,7 @@ class CppSampler:
             self.h = self.L.epvd_create_rank(self.burn_in, self.batch, device, world, r, idb, capacity)
         if not self.h:
             raise DriverError(self.L.epvd_last_error(None).decode())
-        self.B = self.n_global = 0
+        self.B = self.n_global = self.pattern_rows = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -144,6 +150,8 @@ class CppSampler:
             return
         self.B, self.n_nodes = tree.n_nodes - 1, tree.n_nodes
         self.n_global = int(n_global) or fp.n_sites
+        # rows of the change patterns: 12 + 2 (N-1) + internal non-root nodes
+        self.pattern_rows = 12 + 2 * self.B + int((np.asarray(tree.subtree_sizes)[1:] > 1).sum())
         jumps = fp.jumps if len(fp.jumps) else np.zeros(1)
         self._ck(self.L.epvd_reset(self.h, _p(rates, C.c_double), _p(T, C.c_double), tree.n_nodes,
                                    _p(tree.parent_ids, C.c_uint32), _p(tree.subtree_sizes, C.c_uint32),
@@ -261,6 +269,32 @@ class CppSampler:
         nw = (self.n_global + W - 1) // W
         out, ns = np.zeros((6, self.B, nw), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_branch_event_windows(self.h, W, nw, _p(out, C.c_uint64), C.byref(ns)))
+        return int(ns.value), out
+
+    def enable_change_patterns(self, on=True):
+        """change patterns on every context (False = off); kept across reset()"""
+        self._ck(self.L.epvd_set_change_patterns(self.h, 1 if on else 0))
+
+    def change_patterns(self, counts=False):
+        """-> (samples, [R, sites]) over the sites of this process: float64 counts / samples or uint32 counts"""
+        nv, R, ns = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_change_patterns_sizes(self.h, C.byref(nv), C.byref(R), C.byref(ns)))
+        out = np.zeros(max(nv.value, 1), np.uint32)
+        self._ck(self.L.epvd_download_change_patterns(self.h, _p(out, C.c_uint32)))
+        out = out[:nv.value].reshape(R.value, -1)
+        ns = int(ns.value)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def change_pattern_windows(self, W):
+        """-> (samples, uint64 [R, windows]): the rows summed over windows of W global sites (the slots and
+        contexts of this process added)"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        nw = (self.n_global + W - 1) // W
+        out, ns = np.zeros((self.pattern_rows, nw), np.uint64), C.c_uint64(0)
+        self._ck(self.L.epvd_download_change_pattern_windows(self.h, W, self.pattern_rows, nw, _p(out, C.c_uint64),
+                                                             C.byref(ns)))
         return int(ns.value), out
 
     def enable_window_stats(self, W):

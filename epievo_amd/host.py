@@ -481,6 +481,40 @@ def read_domain_stats(path):
         L.epvh_domain_stats_free(h)
 
 
+# ---- change patterns (what happened across the branches of the tree at one site)
+CHANGE_PATTERN_CLASSES = ("one_branch", "parallel_gain", "parallel_loss", "gain_and_loss", "reverted_only")
+
+
+def change_pattern_row_names(tree):
+    """the names of the R = 12 + 2 (N-1) + I rows, in order: the -P file's #rows line"""
+    names = ["jumps_%d" % h for h in range(1, 7)] + ["jumps_7plus"] + list(CHANGE_PATTERN_CLASSES)
+    nodes = range(1, tree.n_nodes)
+    names += ["sole_gain:" + tree.node_names[v] for v in nodes] + ["sole_loss:" + tree.node_names[v] for v in nodes]
+    return names + ["clade_changed:" + tree.node_names[v] for v in nodes if tree.subtree_sizes[v] > 1]
+
+
+def change_pattern_summary(samples, rows, tree):
+    """rows [R, ...] (per site, or window sums divided by the window's sites) -> dict of probabilities per sample:
+    conserved (by descent: no jump on the tree), jump_spectrum [8, ...] (K = 0, 1 .. 6, >= 7), the five classes of
+    CHANGE_PATTERN_CLASSES, sole_gain / sole_loss [N-1, ...] per branch, clade_nodes [I] and
+    clade_identical_by_descent [I, ...] (no jump strictly below the internal non-root node)"""
+    rows = np.asarray(rows)
+    B = tree.n_nodes - 1
+    clade_nodes = np.array([v for v in range(1, tree.n_nodes) if tree.subtree_sizes[v] > 1], np.uint32)
+    if rows.shape[0] != 12 + 2 * B + len(clade_nodes):
+        raise ValueError("rows holds %d rows, the tree has 12 + 2 x %d + %d" % (rows.shape[0], B, len(clade_nodes)))
+    if samples < 1:
+        raise ValueError("the change patterns hold no sample")
+    p = rows.astype(np.float64) / float(samples)
+    conserved = 1.0 - rows[:7].sum(axis=0, dtype=np.uint64).astype(np.float64) / float(samples)
+    out = dict(conserved=conserved, jump_spectrum=np.concatenate([conserved[None], p[:7]]),
+               sole_gain=p[12:12 + B], sole_loss=p[12 + B:12 + 2 * B], clade_nodes=clade_nodes,
+               clade_identical_by_descent=1.0 - p[12 + 2 * B:])
+    for i, name in enumerate(CHANGE_PATTERN_CLASSES):
+        out[name] = p[7 + i]
+    return out
+
+
 # ---- epoch statistics (J and D per branch and epoch of the branch)
 def epoch_edges(fixT, P):
     """E_p = floor(p fixT / P), p = 0 .. P-1 (uint64[P]): the epoch edges on a branch's fixed-point clock;

@@ -392,6 +392,50 @@ class ShardedSampler:
             own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
         return ns, own
 
+    # ---- change patterns: every rank counts its owned columns
+    def enable_change_patterns(self, on=True):
+        self.dev.enable_change_patterns(on)
+
+    def reset_change_patterns(self):
+        self.dev.reset_change_patterns()
+
+    def accumulate_change_patterns(self):
+        self.dev.accumulate_change_patterns()
+
+    def change_patterns_samples(self):
+        return self.dev.change_patterns_samples()
+
+    def change_patterns(self, counts=False):
+        """-> (samples, [R, n_global]) of the whole genome, identical on every rank: the ranks' rows are
+        all-gathered (one collective) and concatenated in genome order"""
+        ns, own = self.dev.change_patterns(counts=True)
+        if self.comm.world > 1:
+            R = own.shape[0]
+            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
+            if own.shape[1] != sizes[self.comm.rank]:
+                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[1], sizes[self.comm.rank]))
+            mine = np.zeros(R * max(sizes) + 2, np.uint32)       # rows, then the sample count (two words)
+            mine[:-2].reshape(R, max(sizes))[:, :own.shape[1]] = own
+            mine[-2:] = [ns & 0xffffffff, ns >> 32]
+            allw = self._gather_words(mine)
+            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of change-pattern samples")
+            own = np.concatenate([allw[r, :-2].reshape(R, max(sizes))[:, :sizes[r]] for r in range(self.comm.world)],
+                                 axis=1)
+        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
+
+    def change_pattern_windows(self, W):
+        """-> (samples, uint64 [R, windows]) of the whole genome, identical on every rank: the ranks'
+        contributions (windows of global sites) are all-gathered and summed"""
+        ns, own = self.dev.change_pattern_windows(W)
+        if self.comm.world > 1:
+            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
+            allw = self._gather_words(mine).view(np.uint64)
+            if any(int(w[-1]) != ns for w in allw):
+                raise RuntimeError("the ranks hold different numbers of change-pattern samples")
+            own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
+        return ns, own
+
     # ---- regional sufficient statistics: every rank adds the windows its owned columns meet
     def enable_window_stats(self, W):
         self.dev.enable_window_stats(W)
@@ -842,6 +886,43 @@ class LocalGroup:
             n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
         parts = self._each(lambda j, s: s.branch_event_windows(W, first_window, n_windows))
         return self._same_samples(parts), sum(p[1] for p in parts)
+
+    # ---- change patterns: every shard counts the sites it owns
+    def enable_change_patterns(self, on=True):
+        self._each(lambda j, s: s.enable_change_patterns(on))
+
+    def reset_change_patterns(self):
+        self._each(lambda j, s: s.reset_change_patterns())
+
+    def accumulate_change_patterns(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a change-pattern sample")
+        self._each(lambda j, s: s.accumulate_change_patterns())
+
+    def change_patterns_samples(self):
+        return self.subs[0].change_patterns_samples()
+
+    def _same_pattern_samples(self, parts):
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of change-pattern samples")
+        return ns
+
+    def change_patterns(self, counts=False):
+        """-> (samples, [R, sites]) over the group's owned sites, shards in genome order"""
+        parts = self._each(lambda j, s: s.change_patterns(counts=True))
+        ns = self._same_pattern_samples(parts)
+        out = np.concatenate([p[1] for p in parts], axis=1)
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def change_pattern_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [R, windows]): the shards' contributions to the windows of W global sites,
+        added"""
+        if n_windows is None:
+            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
+        parts = self._each(lambda j, s: s.change_pattern_windows(W, first_window, n_windows))
+        return self._same_pattern_samples(parts), sum(p[1] for p in parts)
 
     # ---- regional sufficient statistics: every shard adds the windows its owned sites meet
     def enable_window_stats(self, W):

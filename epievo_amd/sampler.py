@@ -65,10 +65,17 @@ ABI_SYMBOLS = [
     "epv_get_lineage_origin_windows",
     "epv_set_domain_stats", "epv_reset_domain_stats", "epv_accumulate_domain_stats", "epv_domain_stats_samples",
     "epv_domain_stats_layout", "epv_get_domain_stats",
+    "epv_set_change_patterns", "epv_reset_change_patterns", "epv_accumulate_change_patterns",
+    "epv_change_patterns_samples", "epv_change_patterns_layout", "epv_get_change_patterns",
+    "epv_get_change_pattern_windows",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
 BRANCH_EVENT_PLANES = ("end1", "net_gain", "net_loss", "changed", "gains", "losses")
+# the first rows of the change patterns (include/epievo_mi355x.h), in order; then sole_gain[b], sole_loss[b]
+# per branch and clade_changed[j] per internal non-root node
+CHANGE_PATTERN_ROWS = ("jumps_1", "jumps_2", "jumps_3", "jumps_4", "jumps_5", "jumps_6", "jumps_7plus", "one_branch",
+                       "parallel_gain", "parallel_loss", "gain_and_loss", "reverted_only")
 
 
 def lib():
@@ -191,6 +198,13 @@ def lib():
         L.epv_domain_stats_samples.argtypes = [vp, u64p]
         L.epv_domain_stats_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
         L.epv_get_domain_stats.argtypes = [vp, u64p, u64p, u64p]
+        L.epv_set_change_patterns.argtypes = [vp, C.c_int]
+        L.epv_reset_change_patterns.argtypes = [vp]
+        L.epv_accumulate_change_patterns.argtypes = [vp]
+        L.epv_change_patterns_samples.argtypes = [vp, u64p]
+        L.epv_change_patterns_layout.argtypes = [vp, u32p, u32p, u32p, u64p, u64p]
+        L.epv_get_change_patterns.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
+        L.epv_get_change_pattern_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
         _lib = L
     return _lib
 
@@ -681,6 +695,54 @@ class DeviceSampler:
         self._ck(self.L.epv_get_branch_event_windows(self.h, W, int(first_window), out.shape[2], _p(out, C.c_uint64)))
         return self.branch_events_samples(), out
 
+    # ---- change patterns (epv_set_change_patterns)
+    def enable_change_patterns(self, on=True):
+        """count, per site, what happened across the branches of the tree -- the jump spectrum, one-branch,
+        parallel and reverted changes, sole gains and losses per branch, changed clades -- after every batch
+        sweep of run_mcmc (CHANGE_PATTERN_ROWS; False = off)"""
+        self._ck(self.L.epv_set_change_patterns(self.h, 1 if on else 0))
+
+    def reset_change_patterns(self):
+        self._ck(self.L.epv_reset_change_patterns(self.h))
+
+    def accumulate_change_patterns(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_change_patterns(self.h))
+
+    def change_patterns_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_change_patterns_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def change_patterns_layout(self):
+        """(rows R, clade nodes [I], first local site, number of sites): R = 12 + 2 (N-1) + I, the clade nodes
+        are the internal non-root nodes in pre-order; (0, [], 0, 0) when off"""
+        R, I, a, k = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        nodes = np.zeros(max(self.B, 1), np.uint32)
+        self._ck(self.L.epv_change_patterns_layout(self.h, C.byref(R), C.byref(I), _p(nodes, C.c_uint32), C.byref(a),
+                                                   C.byref(k)))
+        return int(R.value), nodes[:I.value].copy(), int(a.value), int(k.value)
+
+    def change_patterns(self, counts=False):
+        """-> (samples, array [R, sites]): float64 counts / samples, or the uint32 counts"""
+        R, _, first, cnt = self.change_patterns_layout()
+        out = np.zeros((R, cnt), np.uint32)
+        self._ck(self.L.epv_get_change_patterns(self.h, first, cnt, _p(out, C.c_uint32)))
+        ns = self.change_patterns_samples()
+        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+
+    def change_pattern_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, uint64 [R, windows]): the rows summed over windows of W consecutive global sites, this
+        context's contribution (zero where it counts no site); all windows of the genome unless a range is given"""
+        W = int(W)
+        if W < 1:
+            raise ValueError("a window holds at least one site")
+        if n_windows is None:
+            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
+        out = np.zeros((self.change_patterns_layout()[0], max(int(n_windows), 0)), np.uint64)
+        self._ck(self.L.epv_get_change_pattern_windows(self.h, W, int(first_window), out.shape[1], _p(out, C.c_uint64)))
+        return self.change_patterns_samples(), out
+
     # ---- regional sufficient statistics (epv_set_window_stats)
     def enable_window_stats(self, W):
         """add J and D per window of W global sites after every batch sweep of run_mcmc (0 = off)"""
@@ -1069,6 +1131,28 @@ class SingleSiteSampler:
 
     def domain_stats(self):
         return self.dev.domain_stats()
+
+    # change patterns (DeviceSampler.enable_change_patterns)
+    def enable_change_patterns(self, on=True):
+        self.dev.enable_change_patterns(on)
+
+    def reset_change_patterns(self):
+        self.dev.reset_change_patterns()
+
+    def accumulate_change_patterns(self):
+        self.dev.accumulate_change_patterns()
+
+    def change_patterns_samples(self):
+        return self.dev.change_patterns_samples()
+
+    def change_patterns_layout(self):
+        return self.dev.change_patterns_layout()
+
+    def change_patterns(self, counts=False):
+        return self.dev.change_patterns(counts)
+
+    def change_pattern_windows(self, W):
+        return self.dev.change_pattern_windows(W)
 
     # epoch statistics (DeviceSampler.enable_epoch_stats)
     def enable_epoch_stats(self, P):

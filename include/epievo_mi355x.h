@@ -624,6 +624,53 @@ int epv_domain_stats_layout(epv_ctx *ctx, uint32_t *n_nodes, uint32_t *n_bins, u
                             uint64_t *chunk_sites);
 int epv_get_domain_stats(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
 
+/* ---- change patterns (new): what happened ACROSS the branches of the tree at one site -- conserved by descent,
+ * one clean change on one branch, the same change on several branches, a clade untouched while the rest of the
+ * tree moved.  Joint over the branches of one sampled history, which the per-branch planes of the branch events
+ * cannot give.  A sample reads, per site s and branch b (child node v = b + 1 in pre-order), the init state a_b
+ * and the number of jumps k_b of the resident path (no jump times), and the tree's subtree_sizes.  Per site:
+ *   c  = branches with k_b >= 1                      K  = sum of k_b
+ *   ng = branches with a_b == 0 and k_b odd (a net gain)   nl = branches with a_b == 1 and k_b odd (a net loss)
+ *   S_v = sum of k over the branches strictly below v (nodes v+1 .. v+subtree_sizes[v]-1) for every internal
+ *         non-root node v (subtree_sizes[v] > 1, v >= 1); I = the number of such nodes
+ * and the sample adds at most 1 to each of R = 12 + 2 (N-1) + I uint32 rows [R][sites]:
+ *   0..5  jumps_1 .. jumps_6   K == h                  6  jumps_7plus    K >= 7
+ *   7  one_branch      c == 1                          8  parallel_gain  ng >= 2
+ *   9  parallel_loss   nl >= 2                         10 gain_and_loss  ng >= 1 and nl >= 1
+ *   11 reverted_only   c >= 1 and ng == nl == 0 (every node shows the root's state, yet not by descent)
+ *   12 + (b-1)          sole_gain[b]    c == 1, the changed branch is b, and it nets a gain
+ *   12 + (N-1) + (b-1)  sole_loss[b]    the same for a net loss
+ *   12 + 2 (N-1) + j    clade_changed[j]   S_v >= 1, v the j-th internal non-root node in pre-order
+ * There is no dense row: P(conserved by descent) = 1 - (rows 0..6) / samples, P(the clade below v identical by
+ * descent to v) = 1 - clade_changed / samples; a site without a jump on the tree writes nothing.  Which state a
+ * conserved site holds is the branch events' end1.
+ * Samples, sites and lifecycle are the branch events': a sample after each batch sweep of epv_run_mcmc / _sums /
+ * _counts (not the burn-in) or one epv_accumulate_change_patterns call; the owned sites plus the genome's end
+ * sites where the context holds them (over all contexts every site once); kept over epv_reset, epv_set_model,
+ * capacity growth, epv_scale_jump_times, masks, evidence and epv_sweep_phase; a changed site range or tree lays
+ * the rows out again before the first sample and is EPV_ERR_STATE after it.  An increment is at most 1 per
+ * sample, so, as for the path average, no cap is kept.  Exact integers: they depend on no kernel path, context
+ * or GPU.  Off (the default) allocates and launches nothing; J, D, accept counts, paths, tri_llh and the plan
+ * word do not depend on it.
+ * epv_set_change_patterns: on != 0 allocates 4 R bytes per counted site (checked against the free device memory
+ *   first; the message gives the figure) and zeroes the rows; 0 frees them.
+ * epv_change_patterns_layout: rows R, clades I, clade_node[j] = the node v of clade row j (I <= N-2 entries; may
+ *   be null) and the local sites first .. first+count-1 the rows cover (zeros when off).
+ * epv_get_change_patterns: rows[r][s - first] (uint32) of local sites first .. first+count-1.
+ * epv_get_change_pattern_windows: sums[r][w - first_window] (uint64) = the rows summed over window w = GLOBAL
+ *   sites [w W, (w+1) W), for n_windows windows from first_window; this context's contribution only, zero where
+ *   it counts no site, so contexts, shards and GPUs add up to the one-context result.  W = 1 gives the per-site
+ *   rows, a W beyond the genome one window. */
+int epv_set_change_patterns(epv_ctx *ctx, int on);
+int epv_reset_change_patterns(epv_ctx *ctx);
+int epv_accumulate_change_patterns(epv_ctx *ctx);
+int epv_change_patterns_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_change_patterns_layout(epv_ctx *ctx, uint32_t *n_rows, uint32_t *n_clades, uint32_t *clade_node,
+                               uint64_t *first, uint64_t *count);
+int epv_get_change_patterns(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *rows);
+int epv_get_change_pattern_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
+                                   uint64_t *sums);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

@@ -125,6 +125,17 @@ int epvd_download_domain_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum
 int epvd_download_domain_stats(epvd_sampler *s, uint32_t n_nodes, uint64_t *hist, uint64_t *len_sum,
                                uint64_t *n_samples);
 
+/* change patterns (epv_set_change_patterns on every context; kept across epvd_reset, which starts the rows from
+ * zero), and the rows over the sites of this process in genome order: sizes first (n_rows = 12 + 2 (n_nodes-1) +
+ * internal non-root nodes, n_values = n_rows * sites), then the copy of rows[r * sites + site].
+ * epvd_download_change_pattern_windows: sums[r * n_windows + w] over windows of W global sites, the slots and
+ * contexts of this process added; n_rows as the sizes gave it, n_windows must be ceil(genome length / W) */
+int epvd_set_change_patterns(epvd_sampler *s, int on);
+int epvd_change_patterns_sizes(epvd_sampler *s, uint64_t *n_values, uint32_t *n_rows, uint64_t *n_samples);
+int epvd_download_change_patterns(epvd_sampler *s, uint32_t *rows);
+int epvd_download_change_pattern_windows(epvd_sampler *s, uint64_t W, uint32_t n_rows, uint64_t n_windows,
+                                         uint64_t *sums, uint64_t *n_samples);
+
 /* epoch statistics (epv_set_epoch_stats on every context, P = 0: off; kept across epvd_reset, which starts
  * the sums from zero).  Sizes first: P and the sample count; then the copy of the closed counts
  * closed[((b-1) * P + p) * 24 + ..] (uint64: J[8], then D[8] as 128-bit integers, low words [8] and high words
