@@ -26,6 +26,7 @@
 #include "epv_epochs.h"
 #include "epv_origin.h"
 #include "epv_domains.h"
+#include "epv_turnover.h"
 #include "epv_patterns.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
@@ -162,6 +163,20 @@ struct PatternsState {
   uint64_t out_cap = 0;                   // bytes
 };
 
+// domain turnover (epv_turnover.h), off while !on
+struct TurnoverState {
+  bool on = false;
+  uint64_t max = 0;                       // samples the edge records are allocated for
+  unsigned long long *d_hist = nullptr;   // [R][2][2][128] runs closed inside the counted stretch, over the samples
+  unsigned long long *d_len = nullptr;    // [R][2][2] their lengths
+  unsigned long long *d_edge = nullptr;   // [max][R][2] the two runs a sample's stretch cannot close
+  unsigned long long *d_bits = nullptr;   // [R][words] scratch: the rows of one sample, 64 sites a word
+  SiteLayout at;                          // (with B: the rows depend on nothing else of the tree)
+  uint64_t words = 0;
+  uint32_t R = 0;                         // rows: two per branch
+  uint64_t samples = 0;
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -251,6 +266,7 @@ struct epv_ctx {
   OriginsState lo;
   DomainsState dm;
   PatternsState pt;
+  TurnoverState to;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -751,7 +767,7 @@ struct Layer {
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -1257,6 +1273,89 @@ int launch_domains(epv_ctx *c) {
 const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off,
                         "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
 
+// ---- domain turnover (epv_turnover.h): the sites of pavg_range, R = 2 B rows; a context keeps its PART, unclosed
+bool turnover_on(const epv_ctx *c) { return c->to.on; }
+void turnover_off(epv_ctx *c) {
+  dfree(c->to.d_hist); dfree(c->to.d_len); dfree(c->to.d_edge); dfree(c->to.d_bits);
+  c->to = TurnoverState{};
+}
+// (re)lay out the part for the current branches and site range; zeroes it
+int turnover_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, true);
+  const uint64_t cnt = at.cnt;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->to.d_hist); dfree(c->to.d_len); dfree(c->to.d_edge); dfree(c->to.d_bits);
+  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain turnover takes at most 2^32 - 1 sites per context");
+  const uint32_t R = 2u * c->S.B;
+  const uint64_t words = (cnt + 63u) / 64u;
+  const double need = 8.0 * R * (4.0 * EPV_DOM_BINS + 4.0) + 8.0 * R * (double)words + 16.0 * R * (double)c->to.max;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "domain turnover needs %.3g GB of device memory (16 B x %u rows x %llu samples of "
+                  "edge records, 8 B x %u rows x %llu words of row states); %.3g GB are free: ask for fewer samples "
+                  "(the turnover is off)",
+                  need / 1e9, R, (unsigned long long)c->to.max, R, (unsigned long long)words, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t hist_b = (size_t)32u * EPV_DOM_BINS * R, len_b = (size_t)32u * R, edge_b = (size_t)16u * R * c->to.max;
+  HIP_TRY(c, hipMalloc(&c->to.d_hist, hist_b));
+  HIP_TRY(c, hipMalloc(&c->to.d_len, len_b));
+  HIP_TRY(c, hipMalloc(&c->to.d_edge, edge_b));
+  if (words) HIP_TRY(c, hipMalloc(&c->to.d_bits, (size_t)8u * R * words));
+  HIP_TRY(c, hipMemsetAsync(c->to.d_hist, 0, hist_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->to.d_len, 0, len_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->to.d_edge, 0, edge_b, c->stream));
+  c->to.at = at;
+  c->to.words = words;
+  c->to.R = R;
+  c->to.samples = 0;
+  return EPV_OK;
+}
+// the part matches the current site range and number of branches (neither the tree's shape nor its branch lengths
+// matter: a row is one branch's meta words)
+int ensure_turnover(epv_ctx *c) {
+  if (pavg_layout(c, true, true) == c->to.at) return EPV_OK;
+  if (c->to.samples) return sites_changed(c, kTurnover, "epv_set_domain_turnover");
+  return relayout(c, kTurnover, turnover_alloc);
+}
+int turnover_check_cap(epv_ctx *c, uint64_t more) {
+  if (c->to.samples + more > c->to.max) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "domain turnover holds %llu of the %llu samples its edge records were allocated "
+                  "for, and %llu more were asked: read them out and epv_reset_domain_turnover, or "
+                  "epv_set_domain_turnover with more", (unsigned long long)c->to.samples, (unsigned long long)c->to.max,
+                  (unsigned long long)more);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_turnover first): pack the rows, then count the runs
+int launch_turnover(epv_ctx *c) {
+  int rc = turnover_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->to.at.cnt && c->to.R) {
+    const uint64_t words = c->to.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
+    hipLaunchKernelGGL(epv_turn_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->to.at.lo,
+                       c->to.at.cnt, words, c->to.d_bits);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *edge = c->to.d_edge + c->to.samples * 2u * c->to.R;
+    for (uint32_t r0 = 0; r0 < c->to.R; r0 += 65534u) {   // (a grid's y dimension takes 65535 rows)
+      const uint32_t nr = std::min<uint32_t>(65534u, c->to.R - r0);
+      hipLaunchKernelGGL(epv_turn_runs_kernel, dim3((unsigned)chunks, nr), dim3(256), 0, c->stream,
+                         (const unsigned long long *)c->to.d_bits, words, c->to.at.cnt, r0, c->to.d_hist, c->to.d_len, edge);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  ++c->to.samples;
+  return EPV_OK;
+}
+const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off,
+                         "domain turnover is off: epv_set_domain_turnover first", "the domain turnover"};
+
 // ---- change patterns (epv_patterns.h): the sites of pavg_range, R = 12 + 2 B + I uint32 rows
 bool patterns_on(const epv_ctx *c) { return c->pt.on; }
 void patterns_off(epv_ctx *c) {
@@ -1420,7 +1519,7 @@ const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, 
 
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
-const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns};
+const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -3726,6 +3825,67 @@ EPV_API int epv_get_domain_stats(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, 
   HIP_TRY(c, hipMemcpy(len_sum, c->dm.d_len, (size_t)16u * c->dm.N, hipMemcpyDeviceToHost));
   if (c->dm.samples)
     HIP_TRY(c, hipMemcpy(edges, c->dm.d_edge, (size_t)16u * c->dm.N * c->dm.samples, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+// ---- domain turnover (epv_turnover.h)
+EPV_API int epv_set_domain_turnover(epv_ctx *c, uint64_t max_samples) {
+  if (!max_samples) return layer_set_off(c, kTurnover);
+  if (max_samples > EPV_TURN_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain turnover takes at most 2^21 samples");
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->to.on = true;
+  c->to.max = max_samples;
+  return layer_set_on(c, kTurnover, turnover_alloc);
+}
+
+EPV_API int epv_reset_domain_turnover(epv_ctx *c) {
+  const int rc = layer_entry(c, kTurnover);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->to.d_hist, 0, (size_t)32u * EPV_DOM_BINS * c->to.R, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->to.d_len, 0, (size_t)32u * c->to.R, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->to.d_edge, 0, (size_t)16u * c->to.R * c->to.max, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->to.samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_domain_turnover(epv_ctx *c) { return layer_accumulate(c, kTurnover); }
+
+EPV_API int epv_domain_turnover_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->to.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_domain_turnover_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *n_bins, uint64_t *first, uint64_t *count,
+                                       uint64_t *chunk_sites) {
+  if (!c || !n_rows || !n_bins || !first || !count || !chunk_sites) return EPV_ERR_ARG;
+  *n_rows = *n_bins = 0;
+  *first = *count = *chunk_sites = 0;
+  if (!c->to.on) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->to.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_turnover(c);
+    if (rc) return rc;
+  }
+  *n_rows = c->to.R;
+  *n_bins = EPV_DOM_BINS;
+  *first = c->to.at.lo;
+  *count = c->to.at.cnt;
+  *chunk_sites = 64ull * EPV_DOM_CHUNK_WORDS;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_domain_turnover(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  const int rc = layer_entry(c, kTurnover);
+  if (rc) return rc;
+  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(hist, c->to.d_hist, (size_t)32u * EPV_DOM_BINS * c->to.R, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(len_sum, c->to.d_len, (size_t)32u * c->to.R, hipMemcpyDeviceToHost));
+  if (c->to.samples)
+    HIP_TRY(c, hipMemcpy(edges, c->to.d_edge, (size_t)16u * c->to.R * c->to.samples, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 

@@ -32,6 +32,10 @@
 // (epv_set_change_patterns: per site what happened across the branches of the tree -- the jump spectrum, one-branch,
 // parallel and reverted changes, sole gains and losses per branch, changed clades), summed over windows of W sites,
 // as integers (epv::write_change_patterns).  Changes nothing else the run writes.
+// New: -R/--turnover FILE: the domain turnover of the B batch sweeps (epv_set_domain_turnover with max_samples = B:
+// per branch the runs of the state at its start and at its end, each kept or turned over -- domains born and died,
+// gaps filled and opened -- closed over the whole genome), as integers (epv::write_domain_turnover).  Changes
+// nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -57,7 +61,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
@@ -93,6 +97,8 @@ int main(int argc, const char **argv) {
                       false, epochs_file);
     opt_parse.add_opt("patterns", 'P', "output file of the change patterns of the batch sweeps (integer window sums)",
                       false, patterns_file);
+    opt_parse.add_opt("turnover", 'R', "output file of the domain turnover of the batch sweeps (integer counts per bin)",
+                      false, turnover_file);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps and "
                       "change patterns (default 1)", false, window);
@@ -128,6 +134,8 @@ int main(int argc, const char **argv) {
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
+    if (!turnover_file.empty() && batch > (1ull << 21))
+      throw std::runtime_error("-R/--turnover: the domain turnover takes at most 2^21 batch sweeps (-B)");
     const string param_file(leftover_args.front()), input_file(leftover_args.back());
 
     if (VERBOSE) cerr << "[READING PARAMETERS: " << param_file << "]" << endl;
@@ -173,6 +181,7 @@ int main(int argc, const char **argv) {
     if (!domains_file.empty()) mcmc.set_domain_stats(batch);
     if (!epochs_file.empty()) mcmc.set_epoch_stats((uint32_t)n_epochs);
     if (!patterns_file.empty()) mcmc.set_change_patterns(true);
+    if (!turnover_file.empty()) mcmc.set_domain_turnover(batch);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -246,6 +255,15 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING CHANGE PATTERNS OF " << n_samples << " SAMPLES: " << patterns_file << "]" << endl;
       epv::write_change_patterns(patterns_file, th.node_names, th.subtree_sizes, n_rows, out.n_sites,
                                  mcmc.branch_event_windows(window), window, sums.data(), n_samples);
+    }
+    if (!turnover_file.empty()) {
+      vector<uint64_t> hist, len_sum;
+      uint32_t n_rows = 0;
+      uint64_t n_samples = 0;
+      mcmc.download_domain_turnover(hist, len_sum, n_rows, n_samples);
+      if (VERBOSE) cerr << "[WRITING DOMAIN TURNOVER OF " << n_samples << " SAMPLES: " << turnover_file << "]" << endl;
+      const vector<string> branch_names(th.node_names.begin() + 1, th.node_names.end());
+      epv::write_domain_turnover(turnover_file, branch_names, n_samples, hist.data(), len_sum.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

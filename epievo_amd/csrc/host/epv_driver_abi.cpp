@@ -36,6 +36,8 @@ struct epvd_sampler {
   bool have_staged_origins = false;
   std::vector<uint64_t> staged_dom_hist, staged_dom_len, staged_dom_edges;   // between epvd_domain_part_sizes and epvd_download_domain_part
   bool have_staged_domains = false;
+  std::vector<uint64_t> staged_turn_hist, staged_turn_len, staged_turn_edges;   // between epvd_turnover_part_sizes and epvd_download_turnover_part
+  bool have_staged_turnover = false;
 };
 
 namespace {
@@ -404,6 +406,47 @@ EPVD_API int epvd_download_domain_stats(epvd_sampler *h, uint32_t n_nodes, uint6
     uint64_t ns = 0;
     h->s->download_domain_stats(hh, ll, N, ns);
     if (N != n_nodes) throw std::runtime_error("epvd_download_domain_stats: n_nodes must be the tree's number of nodes");
+    std::copy(hh.begin(), hh.end(), hist);
+    std::copy(ll.begin(), ll.end(), len_sum);
+    if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_turnover(epvd_sampler *h, uint64_t max_samples) {
+  return guarded(h, [&] { h->s->set_domain_turnover(max_samples); });
+}
+EPVD_API int epvd_reset_turnover(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_domain_turnover(); });
+}
+EPVD_API int epvd_accumulate_turnover(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_domain_turnover(); });
+}
+EPVD_API int epvd_turnover_part_sizes(epvd_sampler *h, uint32_t *n_rows, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    h->s->download_domain_turnover_part(h->staged_turn_hist, h->staged_turn_len, h->staged_turn_edges, *n_rows, *n_samples);
+    h->have_staged_turnover = true;
+  });
+}
+EPVD_API int epvd_download_turnover_part(epvd_sampler *h, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  return guarded(h, [&] {
+    if (!h->have_staged_turnover) throw std::runtime_error("epvd_turnover_part_sizes first");
+    std::copy(h->staged_turn_hist.begin(), h->staged_turn_hist.end(), hist);
+    std::copy(h->staged_turn_len.begin(), h->staged_turn_len.end(), len_sum);
+    std::copy(h->staged_turn_edges.begin(), h->staged_turn_edges.end(), edges);
+    h->staged_turn_hist.clear();
+    h->staged_turn_len.clear();
+    h->staged_turn_edges.clear();
+    h->have_staged_turnover = false;
+  });
+}
+EPVD_API int epvd_download_turnover(epvd_sampler *h, uint32_t n_rows, uint64_t *hist, uint64_t *len_sum,
+                                    uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> hh, ll;
+    uint32_t R = 0;
+    uint64_t ns = 0;
+    h->s->download_domain_turnover(hh, ll, R, ns);
+    if (R != n_rows) throw std::runtime_error("epvd_download_turnover: n_rows must be twice the tree's number of branches");
     std::copy(hh.begin(), hh.end(), hist);
     std::copy(ll.begin(), ll.end(), len_sum);
     if (n_samples) *n_samples = ns;

@@ -12,6 +12,7 @@
 #include "epv_sim.hpp"
 #include "epv_io.hpp"
 #include "epv_domains.hpp"
+#include "epv_turnover.hpp"
 #include "epv_epochs.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
@@ -485,6 +486,49 @@ EPVH_API void epvh_domain_stats_copy(void *h, char *names, int names_len, uint64
   std::copy(ds->len_sum.begin(), ds->len_sum.end(), len_sum);
 }
 EPVH_API void epvh_domain_stats_free(void *h) { delete (epv::DomainStats *)h; }
+
+// ---- domain turnover: merge and close of parts (epv_turnover.hpp), the file of epievo_est_histories -R
+// hists, len_sums, edges: n_parts pointers each, parts in genome order ([R][2][2][128], [R][2][2], [samples][R][2])
+EPVH_API int epvh_turnover_parts_merge(uint64_t n_parts, uint32_t R, uint64_t samples, const uint64_t *const *hists,
+                                       const uint64_t *const *len_sums, const uint64_t *const *edges, uint64_t *out_hist,
+                                       uint64_t *out_len_sum, uint64_t *out_edges) {
+  try {
+    epv::turnover_parts_merge(n_parts, R, samples, hists, len_sums, edges, out_hist, out_len_sum, out_edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API int epvh_turnover_part_close(uint32_t R, uint64_t samples, uint64_t *hist, uint64_t *len_sum, const uint64_t *edges) {
+  try {
+    epv::turnover_part_close(R, samples, hist, len_sum, edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// branch_names: the child node's name of every branch joined by '\n'; hist [2 B][2][2][128], len_sum [2 B][2][2]: closed
+EPVH_API int epvh_write_domain_turnover(const char *file, const char *branch_names, uint64_t n_samples, const uint64_t *hist,
+                                        const uint64_t *len_sum) {
+  try {
+    epv::write_domain_turnover(file, split_names(branch_names), n_samples, hist, len_sum);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_domain_turnover(const char *file) {
+  try {
+    return new epv::DomainTurnover(epv::read_domain_turnover(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+EPVH_API void epvh_domain_turnover_dims(void *h, uint64_t *n_samples, uint64_t *n_branches, uint64_t *names_len) {
+  const epv::DomainTurnover *dt = (const epv::DomainTurnover *)h;
+  *n_samples = dt->n_samples;
+  *n_branches = dt->branch_names.size();
+  *names_len = join_names(dt->branch_names).size() + 1u;
+}
+EPVH_API void epvh_domain_turnover_copy(void *h, char *names, int names_len, uint64_t *hist, uint64_t *len_sum) {
+  const epv::DomainTurnover *dt = (const epv::DomainTurnover *)h;
+  put_text(join_names(dt->branch_names), names, names_len);
+  std::copy(dt->hist.begin(), dt->hist.end(), hist);
+  std::copy(dt->len_sum.begin(), dt->len_sum.end(), len_sum);
+}
+EPVH_API void epvh_domain_turnover_free(void *h) { delete (epv::DomainTurnover *)h; }
 
 // ---- epoch statistics: closing the difference form (epv_epochs.hpp), and the file of epievo_est_histories -E
 EPVH_API void epvh_epoch_edges(uint64_t fixT, uint32_t P, uint64_t *out) { epv::epoch_edges(fixT, P, out); }

@@ -981,6 +981,99 @@ DomainStats read_domain_stats(const std::string &file) {
   return ds;
 }
 
+void write_domain_turnover(const std::string &file, const std::vector<std::string> &branch_names, uint64_t n_samples,
+                           const uint64_t *hist, const uint64_t *len_sum) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#samples\t" << n_samples << "\tbins\t" << EPV_DOM_BINS << '\n';
+  for (size_t b = 0; b < branch_names.size(); ++b) {
+    out << "BRANCH:" << branch_names[b] << '\n';
+    for (uint64_t cls = 0; cls < 8u; ++cls) {   // (row, state, kept)
+      const uint64_t *h = hist + (b * 8u + cls) * EPV_DOM_BINS;
+      uint64_t runs = 0;
+      for (uint32_t i = 0; i < EPV_DOM_BINS; ++i) runs += h[i];
+      out << (cls & 4u ? "end" : "start") << "\tstate\t" << ((cls >> 1) & 1u) << "\tkept\t" << (cls & 1u) << "\truns\t"
+          << runs << "\tsites\t" << len_sum[b * 8u + cls] << '\n';
+      for (uint32_t i = 0; i < EPV_DOM_BINS; ++i) {
+        if (!h[i]) continue;
+        uint64_t lo = 0, hi = 0;
+        domain_bin_range(i, &lo, &hi);
+        out << lo << "\t" << hi << "\t" << h[i] << '\n';
+      }
+    }
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+DomainTurnover read_domain_turnover(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad domain-turnover file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("domain-turnover file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  DomainTurnover dt;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 4 || f[0] != "#samples" || f[2] != "bins" || std::stoull(f[3]) != EPV_DOM_BINS)
+    throw bad("bad header: " + line);
+  dt.n_samples = std::stoull(f[1]);
+  int cls = 7;   // the class of the last class line of the current branch (7: the branch is complete)
+  uint64_t runs = 0, seen = 0;
+  auto end_class = [&] {
+    if (!dt.branch_names.empty() && cls >= 0 && seen != runs) throw bad("the bins of a class do not add up to its runs");
+  };
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    if (line.compare(0, 7, "BRANCH:") == 0) {
+      end_class();
+      if (cls != 7) throw bad("a branch without all eight classes: " + line);
+      dt.branch_names.push_back(line.substr(7));
+      dt.hist.resize(dt.branch_names.size() * 8u * EPV_DOM_BINS, 0u);
+      dt.len_sum.resize(dt.branch_names.size() * 8u, 0u);
+      cls = -1;
+      runs = seen = 0;
+      continue;
+    }
+    f = fields(line);
+    if (dt.branch_names.empty()) throw bad("a line before the first branch: " + line);
+    if (f[0] == "start" || f[0] == "end") {
+      end_class();
+      if (f.size() != 9 || f[1] != "state" || f[3] != "kept" || f[5] != "runs" || f[7] != "sites")
+        throw bad("bad class line: " + line);
+      const int c = (f[0] == "end" ? 4 : 0) + 2 * std::stoi(f[2]) + std::stoi(f[4]);
+      if (c != cls + 1 || (f[2] != "0" && f[2] != "1") || (f[4] != "0" && f[4] != "1")) throw bad("bad class line: " + line);
+      cls = c;
+      runs = std::stoull(f[6]);
+      seen = 0;
+      dt.len_sum[(dt.branch_names.size() - 1u) * 8u + (size_t)cls] = std::stoull(f[8]);
+    } else {
+      if (cls < 0 || f.size() != 3) throw bad("bad bin line: " + line);
+      const uint64_t lo = std::stoull(f[0]), hi = std::stoull(f[1]);
+      const uint32_t b = epv_domain_bin(lo);
+      uint64_t blo = 0, bhi = 0;
+      domain_bin_range(b, &blo, &bhi);
+      if (!lo || lo != blo || hi != bhi) throw bad("not the range of a bin: " + line);
+      const uint64_t n = std::stoull(f[2]);
+      dt.hist[((dt.branch_names.size() - 1u) * 8u + (size_t)cls) * EPV_DOM_BINS + b] += n;
+      seen += n;
+    }
+  }
+  end_class();
+  if (cls != 7) throw bad("the last branch lacks a class");
+  return dt;
+}
+
 // a 128-bit integer (low, high word) in decimal, and back
 static std::string u128_str(uint64_t lo, uint64_t hi) {
   unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;

@@ -132,6 +132,20 @@ void write_domain_stats(const std::string &file, const std::vector<std::string> 
                         const uint64_t *hist, const uint64_t *len_sum);
 DomainStats read_domain_stats(const std::string &file);
 
+// the domain turnover of epievo_est_histories -R (the closed result of epv_get_domain_turnover), integers only:
+//   "#samples\t<S>\tbins\t128", then per branch "BRANCH:<child node name>", per row (start, end), state and kept
+//   a line "<start|end>\tstate\t<0|1>\tkept\t<0|1>\truns\t<count>\tsites\t<len_sum>" and one line "lo\thi\tcount"
+//   per nonzero bin.  hist: [2 b + row][state][kept][bin], len_sum: [2 b + row][state][kept] (uint64)
+struct DomainTurnover {
+  uint64_t n_samples = 0;
+  std::vector<std::string> branch_names;
+  std::vector<uint64_t> hist;      // [2 B][2][2][128]
+  std::vector<uint64_t> len_sum;   // [2 B][2][2]
+};
+void write_domain_turnover(const std::string &file, const std::vector<std::string> &branch_names, uint64_t n_samples,
+                           const uint64_t *hist, const uint64_t *len_sum);
+DomainTurnover read_domain_turnover(const std::string &file);
+
 // the epoch statistics of epievo_est_histories -E (epv_get_epoch_stats closed by epv::epoch_close):
 //   "#samples\t<S>\tepochs\t<P>", then per non-root node in pre-order "NODE:<name>\t<branch length>\t<k_b>"
 //   (%.17g; D integers are in units of 2^-k_b) and one line per epoch: the epoch's start as a fraction of

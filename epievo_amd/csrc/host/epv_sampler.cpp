@@ -14,6 +14,7 @@
 
 #include "epievo_mi355x.h"
 #include "epv_domains.hpp"
+#include "epv_turnover.hpp"
 #include "epievo_mi355x_comm.h"
 
 namespace epv {
@@ -435,6 +436,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
   if (patterns_) set_change_patterns(true);
+  if (turnover_max_) set_domain_turnover(turnover_max_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -448,6 +450,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (origins_) set_lineage_origins(true);
   if (domains_max_) set_domain_stats(domains_max_);
   if (patterns_) set_change_patterns(true);
+  if (turnover_max_) set_domain_turnover(turnover_max_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -811,6 +814,65 @@ void SingleSiteSampler::download_domain_stats(std::vector<uint64_t> &hist, std::
   std::vector<uint64_t> edges;
   download_domain_part(hist, len_sum, edges, n_nodes, n_samples);
   domain_part_close(n_nodes, n_samples, hist.data(), len_sum.data(), edges.data());
+}
+
+void SingleSiteSampler::set_domain_turnover(uint64_t max_samples) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !max_samples)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_domain_turnover(c, max_samples), "epv_set_domain_turnover");
+  turnover_max_ = max_samples;
+}
+
+void SingleSiteSampler::reset_domain_turnover() {
+  if (!turnover_max_) throw std::runtime_error("domain turnover is off: set_domain_turnover first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_domain_turnover(c), "epv_reset_domain_turnover");
+}
+
+void SingleSiteSampler::accumulate_domain_turnover() {
+  if (!turnover_max_) throw std::runtime_error("domain turnover is off: set_domain_turnover first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_domain_turnover(c), "epv_accumulate_domain_turnover");
+}
+
+void SingleSiteSampler::download_domain_turnover_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                                      std::vector<uint64_t> &edges, uint32_t &n_rows,
+                                                      uint64_t &n_samples) {
+  if (!turnover_max_) throw std::runtime_error("domain turnover is off: set_domain_turnover first");
+  const std::vector<epv_ctx *> cs = contexts();   // in genome order
+  std::vector<std::vector<uint64_t>> h(cs.size()), l(cs.size()), e(cs.size());
+  std::vector<const uint64_t *> hp(cs.size()), lp(cs.size()), ep(cs.size());
+  n_rows = 0;
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t R = 0, bins = 0;
+    uint64_t first = 0, count = 0, chunk = 0, ns = 0;
+    check_on(cs[i], epv_domain_turnover_layout(cs[i], &R, &bins, &first, &count, &chunk), "epv_domain_turnover_layout");
+    check_on(cs[i], epv_domain_turnover_samples(cs[i], &ns), "epv_domain_turnover_samples");
+    if (i == 0) { n_rows = R; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of domain-turnover samples");
+    else if (R != n_rows) throw std::runtime_error("the contexts hold domain turnover of different trees");
+    h[i].assign((size_t)R * 4u * EPV_DOM_BINS, 0u);
+    l[i].assign((size_t)R * 4u, 0u);
+    e[i].assign(std::max<size_t>((size_t)ns * R * 2u, 1u), 0u);
+    check_on(cs[i], epv_get_domain_turnover(cs[i], h[i].data(), l[i].data(), e[i].data()), "epv_get_domain_turnover");
+    hp[i] = h[i].data(); lp[i] = l[i].data(); ep[i] = e[i].data();
+  }
+  hist.assign((size_t)n_rows * 4u * EPV_DOM_BINS, 0u);
+  len_sum.assign((size_t)n_rows * 4u, 0u);
+  edges.assign((size_t)n_samples * n_rows * 2u, 0u);
+  std::vector<uint64_t> none(1, 0u);
+  turnover_parts_merge(cs.size(), n_rows, n_samples, hp.data(), lp.data(), ep.data(), hist.data(), len_sum.data(),
+                       edges.empty() ? none.data() : edges.data());
+}
+
+void SingleSiteSampler::download_domain_turnover(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                                 uint32_t &n_rows, uint64_t &n_samples) {
+  if (rank_mode_)
+    throw std::runtime_error("download_domain_turnover: this process holds one slot's stretch of the genome, not the "
+                             "genome: merge the processes' download_domain_turnover_part in genome order "
+                             "(epv::turnover_parts_merge, epvh_turnover_parts_merge), then close the merged part");
+  std::vector<uint64_t> edges;
+  download_domain_turnover_part(hist, len_sum, edges, n_rows, n_samples);
+  turnover_part_close(n_rows, n_samples, hist.data(), len_sum.data(), edges.data());
 }
 
 void SingleSiteSampler::set_epoch_stats(uint32_t P) {

@@ -161,6 +161,19 @@ public:
                             uint32_t &n_nodes, uint64_t &n_samples);
   void download_domain_stats(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_nodes,
                              uint64_t &n_samples);
+  // domain turnover (epv_set_domain_turnover) on every context, with the domain size spectra's samples and
+  // lifecycle; max_samples = 0 is off.  n_rows = 2 (n_nodes-1).  download_domain_turnover_part: the parts of all
+  // slots and contexts of this process merged in genome order (epv::turnover_parts_merge), unclosed: hist
+  // [R][2][2][128], len_sum [R][2][2], edges [samples][R][2].  download_domain_turnover: that part closed
+  // (epv::turnover_part_close).  One slot per process: it throws, as download_domain_stats does
+  void set_domain_turnover(uint64_t max_samples);
+  uint64_t domain_turnover_max() const { return turnover_max_; }
+  void reset_domain_turnover();
+  void accumulate_domain_turnover();
+  void download_domain_turnover_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                     std::vector<uint64_t> &edges, uint32_t &n_rows, uint64_t &n_samples);
+  void download_domain_turnover(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_rows,
+                                uint64_t &n_samples);
   // change patterns (epv_set_change_patterns) on every context, with the branch events' samples and lifecycle.
   // n_rows = 12 + 2 (n_nodes-1) + internal non-root nodes.  download_change_patterns: rows[r * sites + site] over
   // the sites of this process in genome order; download_change_pattern_windows: sums[r * n_windows + w] over
@@ -283,6 +296,7 @@ private:
   uint32_t epoch_P_ = 0;      // set_epoch_stats
   bool origins_ = false;      // set_lineage_origins
   uint64_t domains_max_ = 0; // set_domain_stats
+  uint64_t turnover_max_ = 0; // set_domain_turnover
   bool patterns_ = false;     // set_change_patterns
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none

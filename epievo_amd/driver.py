@@ -25,6 +25,8 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_download_lineage_origin_windows",
                   "epvd_set_domain_stats", "epvd_reset_domain_stats", "epvd_accumulate_domain_stats",
                   "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats",
+                  "epvd_set_turnover", "epvd_reset_turnover", "epvd_accumulate_turnover",
+                  "epvd_turnover_part_sizes", "epvd_download_turnover_part", "epvd_download_turnover",
                   "epvd_set_change_patterns", "epvd_change_patterns_sizes", "epvd_download_change_patterns",
                   "epvd_download_change_pattern_windows"]
 
@@ -89,6 +91,12 @@ def lib():
         L.epvd_domain_part_sizes.argtypes = [vp, u32p, u64p]
         L.epvd_download_domain_part.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_domain_stats.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
+        L.epvd_set_turnover.argtypes = [vp, C.c_uint64]
+        L.epvd_reset_turnover.argtypes = [vp]
+        L.epvd_accumulate_turnover.argtypes = [vp]
+        L.epvd_turnover_part_sizes.argtypes = [vp, u32p, u64p]
+        L.epvd_download_turnover_part.argtypes = [vp, u64p, u64p, u64p]
+        L.epvd_download_turnover.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -423,4 +431,35 @@ class CppSampler:
         N = self.B + 1
         hist, len_sum, ns = np.zeros((N, 2, 128), np.uint64), np.zeros((N, 2), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_domain_stats(self.h, N, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
+        return int(ns.value), hist, len_sum
+
+    def enable_domain_turnover(self, max_samples):
+        """domain turnover on every context, for at most max_samples samples (0 = off); kept across reset()"""
+        self._ck(self.L.epvd_set_turnover(self.h, int(max_samples)))
+
+    def reset_domain_turnover(self):
+        self._ck(self.L.epvd_reset_turnover(self.h))
+
+    def accumulate_domain_turnover(self):
+        self._ck(self.L.epvd_accumulate_turnover(self.h))
+
+    def domain_turnover_part(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2], edges [samples, R, 2]), uint64: the parts of the slots
+        and contexts of this process merged in genome order, unclosed"""
+        R, ns = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_turnover_part_sizes(self.h, C.byref(R), C.byref(ns)))
+        R, ns = int(R.value), int(ns.value)
+        hist, len_sum = np.zeros((max(R, 1), 2, 2, 128), np.uint64), np.zeros((max(R, 1), 2, 2), np.uint64)
+        edges = np.zeros((max(ns, 1), max(R, 1), 2), np.uint64)
+        self._ck(self.L.epvd_download_turnover_part(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64),
+                                                    _p(edges.reshape(-1)[:max(ns * R * 2, 1)], C.c_uint64)))
+        return ns, hist[:R], len_sum[:R], edges.reshape(-1)[:ns * R * 2].reshape(ns, R, 2)
+
+    def domain_turnover(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]): the closed result over the genome (one slot per
+        process: an error; merge the processes' domain_turnover_part with host.turnover_parts_merge, then
+        host.turnover_part_close)"""
+        R = 2 * self.B
+        hist, len_sum, ns = np.zeros((R, 2, 2, 128), np.uint64), np.zeros((R, 2, 2), np.uint64), C.c_uint64(0)
+        self._ck(self.L.epvd_download_turnover(self.h, R, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
         return int(ns.value), hist, len_sum

@@ -82,6 +82,17 @@ def lib():
         L.epvh_domain_stats_copy.restype = None
         L.epvh_domain_stats_free.argtypes = [C.c_void_p]
         L.epvh_domain_stats_free.restype = None
+        L.epvh_turnover_parts_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u64pp, u64pp, u64pp, u64p, u64p, u64p]
+        L.epvh_turnover_part_close.argtypes = [C.c_uint32, C.c_uint64, u64p, u64p, u64p]
+        L.epvh_write_domain_turnover.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, u64p, u64p]
+        L.epvh_read_domain_turnover.argtypes = [C.c_char_p]
+        L.epvh_read_domain_turnover.restype = C.c_void_p
+        L.epvh_domain_turnover_dims.argtypes = [C.c_void_p, u64p, u64p, u64p]
+        L.epvh_domain_turnover_dims.restype = None
+        L.epvh_domain_turnover_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, u64p, u64p]
+        L.epvh_domain_turnover_copy.restype = None
+        L.epvh_domain_turnover_free.argtypes = [C.c_void_p]
+        L.epvh_domain_turnover_free.restype = None
         u64p_, u32 = C.POINTER(C.c_uint64), C.c_uint32
         L.epvh_epoch_edges.argtypes = [C.c_uint64, u32, u64p_]
         L.epvh_epoch_edges.restype = None
@@ -479,6 +490,99 @@ def read_domain_stats(path):
                     len_sum=len_sum)
     finally:
         L.epvh_domain_stats_free(h)
+
+
+# ---- domain turnover (per branch, the runs of its start and end rows, kept or turned over)
+def turnover_parts_merge(parts):
+    """parts: [(hist [R, 2, 2, 128], len_sum [R, 2, 2], edges [samples, R, 2])] of adjacent stretches of sites in
+    genome order, of the same samples -> the part of their union (uint64 arrays of the same shapes)"""
+    if not parts:
+        raise ValueError("no parts")
+    hists = [np.ascontiguousarray(p[0], np.uint64) for p in parts]
+    sums = [np.ascontiguousarray(p[1], np.uint64) for p in parts]
+    edges = [np.ascontiguousarray(p[2], np.uint64) for p in parts]
+    R, ns = hists[0].shape[0], edges[0].shape[0]
+    for h, l, e in zip(hists, sums, edges):
+        if h.shape != (R, 2, 2, DOMAIN_BINS) or l.shape != (R, 2, 2) or e.shape != (ns, R, 2):
+            raise ValueError("a part is hist [R, 2, 2, 128], len_sum [R, 2, 2], edges [samples, R, 2] of the same R "
+                             "and samples")
+    hist, len_sum = np.zeros((R, 2, 2, DOMAIN_BINS), np.uint64), np.zeros((R, 2, 2), np.uint64)
+    out = np.zeros((ns, R, 2), np.uint64)
+    o = out if out.size else np.zeros(1, np.uint64)
+    if lib().epvh_turnover_parts_merge(len(parts), R, ns, _ptrs(hists), _ptrs(sums),
+                                       _ptrs([e if e.size else np.zeros(1, np.uint64) for e in edges]),
+                                       _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(o, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum, out
+
+
+def turnover_part_close(hist, len_sum, edges):
+    """a part -> the result (hist [R, 2, 2, 128], len_sum [R, 2, 2]): its first and last records are binned and
+    added, a whole record once.  The runs at the two ends count with the length the stretch leaves them"""
+    hist, len_sum = np.array(hist, np.uint64), np.array(len_sum, np.uint64)
+    edges = np.ascontiguousarray(edges, np.uint64)
+    R, ns = hist.shape[0], edges.shape[0]
+    if hist.shape != (R, 2, 2, DOMAIN_BINS) or len_sum.shape != (R, 2, 2) or edges.shape != (ns, R, 2):
+        raise ValueError("a part is hist [R, 2, 2, 128], len_sum [R, 2, 2], edges [samples, R, 2]")
+    e = edges if edges.size else np.zeros(1, np.uint64)
+    h, l = (hist, len_sum) if R else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+    if lib().epvh_turnover_part_close(R, ns, _p(h, C.c_uint64), _p(l, C.c_uint64), _p(e, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum
+
+
+def domain_turnover_summary(samples, hist, len_sum, tree):
+    """a closed result -> dict of float64 [B] arrays, per branch b (child node b + 1): born, died, merged (parent
+    gaps filled) and split (gaps opened) = turned-over runs per sample; born_size, died_size, merged_size,
+    split_size = their mean lengths (nan where a class has no run); parent_domains and child_domains = the
+    state-1 runs of the start and the end row per sample, kept or not"""
+    hist, len_sum = np.asarray(hist, np.uint64), np.asarray(len_sum, np.uint64)
+    B = tree.n_nodes - 1
+    if hist.shape != (2 * B, 2, 2, DOMAIN_BINS) or len_sum.shape != (2 * B, 2, 2):
+        raise ValueError("hist is [2 B, 2, 2, 128], len_sum [2 B, 2, 2] of the tree's B branches")
+    runs = hist.sum(axis=3, dtype=np.uint64).astype(np.float64).reshape(B, 2, 2, 2)   # [b, row, state, kept]
+    sites = len_sum.astype(np.float64).reshape(B, 2, 2, 2)
+    ns = float(samples)
+    out = {}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for name, row, state in (("born", 1, 1), ("died", 0, 1), ("merged", 0, 0), ("split", 1, 0)):
+            out[name] = runs[:, row, state, 0] / ns
+            out[name + "_size"] = sites[:, row, state, 0] / runs[:, row, state, 0]
+        out["parent_domains"] = runs[:, 0, 1, :].sum(axis=1) / ns
+        out["child_domains"] = runs[:, 1, 1, :].sum(axis=1) / ns
+    return out
+
+
+def write_domain_turnover(path, branch_names, samples, hist, len_sum):
+    """the file of epievo_est_histories -R: the closed result, integers only; branch_names = the child node's name
+    of every branch"""
+    hist, len_sum = np.ascontiguousarray(hist, np.uint64), np.ascontiguousarray(len_sum, np.uint64)
+    B = len(branch_names)
+    if hist.shape != (2 * B, 2, 2, DOMAIN_BINS) or len_sum.shape != (2 * B, 2, 2):
+        raise ValueError("hist is [2 branches, 2, 2, 128], len_sum [2 branches, 2, 2]")
+    if lib().epvh_write_domain_turnover(path.encode(), "\n".join(branch_names).encode(), int(samples),
+                                        _p(hist, C.c_uint64), _p(len_sum, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_domain_turnover(path):
+    """-> dict(samples, branch_names, hist uint64 [2 B, 2, 2, 128], len_sum uint64 [2 B, 2, 2])"""
+    L = lib()
+    h = L.epvh_read_domain_turnover(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, B, ln = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.epvh_domain_turnover_dims(h, C.byref(ns), C.byref(B), C.byref(ln))
+        B = int(B.value)
+        buf = C.create_string_buffer(int(ln.value))
+        hist, len_sum = np.zeros((2 * B, 2, 2, DOMAIN_BINS), np.uint64), np.zeros((2 * B, 2, 2), np.uint64)
+        a, b = (hist, len_sum) if B else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+        L.epvh_domain_turnover_copy(h, buf, len(buf), _p(a, C.c_uint64), _p(b, C.c_uint64))
+        return dict(samples=int(ns.value), branch_names=buf.value.decode().split("\n") if B else [], hist=hist,
+                    len_sum=len_sum)
+    finally:
+        L.epvh_domain_turnover_free(h)
 
 
 # ---- change patterns (what happened across the branches of the tree at one site)

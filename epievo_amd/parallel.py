@@ -595,6 +595,47 @@ class ShardedSampler:
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
+    # ---- domain turnover: every rank counts the part of its owned columns
+    def enable_domain_turnover(self, max_samples):
+        self.dev.enable_domain_turnover(max_samples)
+
+    def reset_domain_turnover(self):
+        self.dev.reset_domain_turnover()
+
+    def accumulate_domain_turnover(self):
+        self.dev.accumulate_domain_turnover()
+
+    def domain_turnover_samples(self):
+        return self.dev.domain_turnover_samples()
+
+    def domain_turnover_layout(self):
+        """(rows R, bins, first local site, sites, sites per block of the runs kernel) of this rank's engine"""
+        return self.dev.domain_turnover_layout()
+
+    def domain_turnover_part(self):
+        """-> (samples, hist, len_sum, edges): the part of the whole genome, identical on every rank: the sample
+        counts are compared first (a part's size depends on them), then the ranks' parts are all-gathered and
+        merged in genome order"""
+        ns, hist, len_sum, edges = self.dev.domain_turnover_part()
+        if self.comm.world > 1:
+            R = hist.shape[0]
+            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
+            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
+                raise RuntimeError("the ranks hold different numbers of domain-turnover samples")
+            mine = np.concatenate([hist.reshape(-1), len_sum.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
+            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
+            nh, nl = hist.size, len_sum.size
+            hist, len_sum, edges = host.turnover_parts_merge(
+                [(w[:nh].reshape(R, 2, 2, -1), w[nh:nh + nl].reshape(R, 2, 2), w[nh + nl:].reshape(ns, R, 2))
+                 for w in allw])
+        return ns, hist, len_sum, edges
+
+    def domain_turnover(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]) of the whole genome, closed; every rank merges and
+        closes"""
+        ns, hist, len_sum, edges = self.domain_turnover_part()
+        return (ns,) + host.turnover_part_close(hist, len_sum, edges)
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -1048,6 +1089,40 @@ class LocalGroup:
         """-> (samples, hist [N, 2, 128], len_sum [N, 2]) over the group's owned sites, closed"""
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
+
+    # ---- domain turnover: every shard counts the part of the sites it owns
+    def enable_domain_turnover(self, max_samples):
+        self._each(lambda j, s: s.enable_domain_turnover(max_samples))
+
+    def reset_domain_turnover(self):
+        self._each(lambda j, s: s.reset_domain_turnover())
+
+    def accumulate_domain_turnover(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a domain-turnover sample")
+        self._each(lambda j, s: s.accumulate_domain_turnover())
+
+    def domain_turnover_samples(self):
+        return self.subs[0].domain_turnover_samples()
+
+    def domain_turnover_layout(self):
+        """(rows R, bins, first local site of the first shard, sites over all shards, sites per block)"""
+        lay = self._each(lambda j, s: s.domain_turnover_layout())
+        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+
+    def domain_turnover_part(self):
+        """-> (samples, hist, len_sum, edges): the shards' parts merged in genome order, unclosed"""
+        parts = self._each(lambda j, s: s.domain_turnover_part())
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of domain-turnover samples")
+        return (ns,) + host.turnover_parts_merge([p[1:] for p in parts])
+
+    def domain_turnover(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]) over the group's owned sites, closed"""
+        ns, hist, len_sum, edges = self.domain_turnover_part()
+        return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
     # ---- epoch statistics: every shard adds the triples centred at its owned sites
     def enable_epoch_stats(self, P):

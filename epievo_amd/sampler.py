@@ -68,6 +68,8 @@ ABI_SYMBOLS = [
     "epv_set_change_patterns", "epv_reset_change_patterns", "epv_accumulate_change_patterns",
     "epv_change_patterns_samples", "epv_change_patterns_layout", "epv_get_change_patterns",
     "epv_get_change_pattern_windows",
+    "epv_set_domain_turnover", "epv_reset_domain_turnover", "epv_accumulate_domain_turnover",
+    "epv_domain_turnover_samples", "epv_domain_turnover_layout", "epv_get_domain_turnover",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
@@ -198,6 +200,12 @@ def lib():
         L.epv_domain_stats_samples.argtypes = [vp, u64p]
         L.epv_domain_stats_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
         L.epv_get_domain_stats.argtypes = [vp, u64p, u64p, u64p]
+        L.epv_set_domain_turnover.argtypes = [vp, C.c_uint64]
+        L.epv_reset_domain_turnover.argtypes = [vp]
+        L.epv_accumulate_domain_turnover.argtypes = [vp]
+        L.epv_domain_turnover_samples.argtypes = [vp, u64p]
+        L.epv_domain_turnover_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
+        L.epv_get_domain_turnover.argtypes = [vp, u64p, u64p, u64p]
         L.epv_set_change_patterns.argtypes = [vp, C.c_int]
         L.epv_reset_change_patterns.argtypes = [vp]
         L.epv_accumulate_change_patterns.argtypes = [vp]
@@ -914,6 +922,48 @@ class DeviceSampler:
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
+    # ---- domain turnover (epv_set_domain_turnover)
+    def enable_domain_turnover(self, max_samples):
+        """count, per branch, the runs of the state at its start and at its end along the genome, each kept or
+        turned over, after every batch sweep of run_mcmc, for at most max_samples samples (0 = off)"""
+        self._ck(self.L.epv_set_domain_turnover(self.h, int(max_samples)))
+
+    def reset_domain_turnover(self):
+        self._ck(self.L.epv_reset_domain_turnover(self.h))
+
+    def accumulate_domain_turnover(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_domain_turnover(self.h))
+
+    def domain_turnover_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_domain_turnover_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def domain_turnover_layout(self):
+        """(rows R = 2 B, bins, first local site, number of sites, sites per block of the runs kernel); zeros when off"""
+        nr, nb, a, k, cs = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_domain_turnover_layout(self.h, C.byref(nr), C.byref(nb), C.byref(a), C.byref(k), C.byref(cs)))
+        return int(nr.value), int(nb.value), int(a.value), int(k.value), int(cs.value)
+
+    def domain_turnover_part(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2], edges [samples, R, 2]), uint64: what this context's
+        stretch of sites contributes, unclosed (host.turnover_parts_merge, host.turnover_part_close)"""
+        ns = self.domain_turnover_samples()
+        R, nb = self.domain_turnover_layout()[:2]
+        hist = np.zeros((max(R, 1), 2, 2, max(nb, 1)), np.uint64)
+        len_sum = np.zeros((max(R, 1), 2, 2), np.uint64)
+        edges = np.zeros((max(ns, 1), max(R, 1), 2), np.uint64)
+        self._ck(self.L.epv_get_domain_turnover(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64),
+                                                _p(edges, C.c_uint64)))
+        return ns, hist[:R], len_sum[:R], edges[:ns, :R]
+
+    def domain_turnover(self):
+        """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]): the closed result over this context's sites; row
+        2 b is the start of branch b, row 2 b + 1 its end; axes state and kept (host.domain_turnover_summary)"""
+        ns, hist, len_sum, edges = self.domain_turnover_part()
+        return (ns,) + host.turnover_part_close(hist, len_sum, edges)
+
     # ---- epoch statistics (epv_set_epoch_stats)
     def enable_epoch_stats(self, P):
         """add J and D per branch and epoch (P epochs per branch) after every batch sweep of run_mcmc (0 = off)"""
@@ -1131,6 +1181,28 @@ class SingleSiteSampler:
 
     def domain_stats(self):
         return self.dev.domain_stats()
+
+    # domain turnover (DeviceSampler.enable_domain_turnover)
+    def enable_domain_turnover(self, max_samples):
+        self.dev.enable_domain_turnover(max_samples)
+
+    def reset_domain_turnover(self):
+        self.dev.reset_domain_turnover()
+
+    def accumulate_domain_turnover(self):
+        self.dev.accumulate_domain_turnover()
+
+    def domain_turnover_samples(self):
+        return self.dev.domain_turnover_samples()
+
+    def domain_turnover_layout(self):
+        return self.dev.domain_turnover_layout()
+
+    def domain_turnover_part(self):
+        return self.dev.domain_turnover_part()
+
+    def domain_turnover(self):
+        return self.dev.domain_turnover()
 
     # change patterns (DeviceSampler.enable_change_patterns)
     def enable_change_patterns(self, on=True):

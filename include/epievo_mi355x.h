@@ -671,6 +671,47 @@ int epv_get_change_patterns(epv_ctx *ctx, uint64_t first, uint64_t count, uint32
 int epv_get_change_pattern_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows,
                                    uint64_t *sums);
 
+/* ---- domain turnover (new): which domains (runs of consecutive sites in state 1) arose or died on which
+ * branch, how large they were, and where two domains merged or one split.  Joint along the genome and across the
+ * two ends of a branch: neither the domain size spectra (no link from a child's domains to its parent's), the
+ * branch events (per site) nor the change patterns (one site) can give it.
+ * One sample reads, per branch b (child node v = b + 1) and site s, the init state a and the jump count k of the
+ * resident path (no jump time): e = a XOR (k & 1) is the state at the child node, c = k & 1 the net change.
+ * Rows: R = 2 B.  Row 2 b is the START row, X = a (the parent's state as this branch sees it); row 2 b + 1 is the
+ * END row, X = e.  Runs over a stretch [lo, lo + cnt) are those of the domain size spectra: an END is a position
+ * p with p + 1 < cnt and X[p] != X[p + 1]; the run that ends at p has length p - p' and state X[p].
+ * A run is KEPT (flag 1) iff at least one of its sites has c == 0, and TURNED OVER (flag 0) iff every site of it
+ * has a net change on the branch.  Turned over: end row, state 1 = a domain BORN on the branch; start row, state
+ * 1 = a parent domain that DIED; start row, state 0 = a parent gap FILLED (its flanking domains merged); end row,
+ * state 0 = a gap OPENED (a domain split or was hollowed).  Kept runs are the domains and gaps that hold at
+ * least one inherited site.
+ * Bins: those of the domain size spectra (EPV_DOM_BINS = 128).  A context keeps a PART:
+ *   hist[R][2 state][2 kept][128] uint64, len_sum[R][2][2] uint64   the runs closed inside the stretch
+ *   edge[sample][R][2] uint64  the two runs the stretch cannot close: bits 0-60 the length, bit 61 KEPT, bit 62
+ *     WHOLE, bit 63 the state.  A stretch of no sites has both records 0.
+ * Merge and close are the domain size spectra's with one addition: a run joined from pieces is kept iff any piece
+ * is kept (epvh_turnover_parts_merge, epvh_turnover_part_close in libepv_host.so).  After close, len_sum over
+ * state and kept adds up to samples x sites for every row.  Where every child starts in its parent's end state
+ * (the sampler's paths), the end row of b summed over kept is the domain part of node v, the start row that of
+ * node parent(v), and the edge records match after clearing bit 61.
+ * Samples, sites and lifecycle are the domain size spectra's; a changed site range or number of branches lays
+ * the part out again before the first sample and is EPV_ERR_STATE after it.  Off by default: nothing allocated,
+ * nothing launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_domain_turnover: max_samples >= 1 (at most 2^21) allocates hist, len_sum, 8 R ceil(cnt / 64) bytes of
+ *   scratch and 16 R max_samples bytes of edge records (checked against the free device memory first; the message
+ *   gives the figure) and zeroes them; 0 frees everything.  A sample beyond max_samples is EPV_ERR_STATE, and so
+ *   is a run whose batch would pass it, refused before its first sweep.  At most 2^32 - 1 sites per context.
+ * epv_domain_turnover_layout: rows R, bins, the local sites first .. first+count-1 and the sites one block of the
+ *   runs kernel covers (zeros when off).
+ * epv_get_domain_turnover: the context's part, unclosed; edges holds [samples][R][2]. */
+int epv_set_domain_turnover(epv_ctx *ctx, uint64_t max_samples);
+int epv_reset_domain_turnover(epv_ctx *ctx);
+int epv_accumulate_domain_turnover(epv_ctx *ctx);
+int epv_domain_turnover_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_domain_turnover_layout(epv_ctx *ctx, uint32_t *n_rows, uint32_t *n_bins, uint64_t *first, uint64_t *count,
+                               uint64_t *chunk_sites);
+int epv_get_domain_turnover(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

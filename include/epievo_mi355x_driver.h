@@ -125,6 +125,19 @@ int epvd_download_domain_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum
 int epvd_download_domain_stats(epvd_sampler *s, uint32_t n_nodes, uint64_t *hist, uint64_t *len_sum,
                                uint64_t *n_samples);
 
+/* the turnover of domains per branch (epv_set_domain_turnover on every context; max_samples = 0 is off; kept across
+ * epvd_reset, which starts it from zero).  The part of this process: the parts of its slots and contexts merged in
+ * genome order, unclosed -- sizes first (rows R = 2 B and samples S), then the copy of hist[R][2][2][128],
+ * len_sum[R][2][2] and edges[S][R][2].  epvd_download_turnover: that part closed, into hist[n_rows][2][2][128] and
+ * len_sum[n_rows][2][2] (n_rows = twice the tree's branches); one slot per process: an error that names the part
+ * and the merge function, because one process's stretch is not the genome */
+int epvd_set_turnover(epvd_sampler *s, uint64_t max_samples);
+int epvd_reset_turnover(epvd_sampler *s);
+int epvd_accumulate_turnover(epvd_sampler *s);
+int epvd_turnover_part_sizes(epvd_sampler *s, uint32_t *n_rows, uint64_t *n_samples);
+int epvd_download_turnover_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+int epvd_download_turnover(epvd_sampler *s, uint32_t n_rows, uint64_t *hist, uint64_t *len_sum, uint64_t *n_samples);
+
 /* change patterns (epv_set_change_patterns on every context; kept across epvd_reset, which starts the rows from
  * zero), and the rows over the sites of this process in genome order: sizes first (n_rows = 12 + 2 (n_nodes-1) +
  * internal non-root nodes, n_values = n_rows * sites), then the copy of rows[r * sites + site].
