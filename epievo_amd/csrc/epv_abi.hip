@@ -27,6 +27,7 @@
 #include "epv_origin.h"
 #include "epv_domains.h"
 #include "epv_turnover.h"
+#include "epv_corr.h"
 #include "epv_patterns.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
@@ -177,6 +178,20 @@ struct TurnoverState {
   uint64_t samples = 0;
 };
 
+// spatial correlations (epv_corr.h), off while L == 0
+struct CorrState {
+  uint32_t L = 0;                         // max_lag
+  uint64_t max = 0;                       // samples the edge records are allocated for
+  unsigned long long *d_n11 = nullptr;    // [R][L + 1] pairs of ones inside the counted stretch, over the samples
+  unsigned long long *d_edge = nullptr;   // [max][R][2][LW] the first and the last L bits of every sample's rows
+  unsigned long long *d_bits = nullptr;   // [R][words] scratch: the rows of one sample, 64 sites a word
+  SiteLayout at;                          // (with B)
+  uint64_t words = 0;
+  uint32_t R = 0, LW = 0;                 // rows N + B, words of an edge record
+  uint32_t N = 0, child0 = 0;             // nodes, and the root's lowest-numbered child: what row 0 depends on
+  uint64_t samples = 0;
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -267,6 +282,7 @@ struct epv_ctx {
   DomainsState dm;
   PatternsState pt;
   TurnoverState to;
+  CorrState co;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -767,7 +783,7 @@ struct Layer {
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -1356,6 +1372,107 @@ int launch_turnover(epv_ctx *c) {
 const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off,
                          "domain turnover is off: epv_set_domain_turnover first", "the domain turnover"};
 
+// ---- spatial correlations (epv_corr.h): the sites of pavg_range, R = N + B rows; a context keeps its PART, unclosed
+bool corr_on(const epv_ctx *c) { return c->co.L != 0u; }
+void corr_off(epv_ctx *c) {
+  dfree(c->co.d_n11); dfree(c->co.d_edge); dfree(c->co.d_bits);
+  c->co = CorrState{};
+}
+uint32_t corr_child0(const epv_ctx *c) {
+  for (uint32_t v = 1; v < c->S.N; ++v) if (c->parent[v] == 0u) return v;
+  return 0u;
+}
+// (re)lay out the part for the current tree and site range; zeroes it
+int corr_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, true);
+  const uint64_t cnt = at.cnt;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->co.d_n11); dfree(c->co.d_edge); dfree(c->co.d_bits);
+  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "spatial correlations take at most 2^32 - 1 sites per context");
+  const uint32_t L = c->co.L;
+  if (cnt < L) {   // (a pair may span two parts, never three)
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "spatial correlations: this context counts %llu sites, fewer than max_lag = %u: "
+                  "a context's stretch holds at least max_lag sites (the correlations are off)",
+                  (unsigned long long)cnt, L);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const uint32_t N = c->S.N, R = N + c->S.B, LW = (L + 63u) / 64u;
+  const uint64_t words = (cnt + 63u) / 64u;
+  const double need = 8.0 * R * (L + 1.0) + 8.0 * R * (double)words + 16.0 * R * LW * (double)c->co.max;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[360];
+    std::snprintf(buf, sizeof buf, "spatial correlations need %.3g GB of device memory (16 B x %u rows x %u words x %llu "
+                  "samples of edge records, 8 B x %u rows x %llu words of row states, 8 B x %u rows x %u lags of "
+                  "counts); %.3g GB are free: ask for fewer samples (the correlations are off)",
+                  need / 1e9, R, LW, (unsigned long long)c->co.max, R, (unsigned long long)words, R, L + 1u, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t n11_b = (size_t)8u * R * (L + 1u), edge_b = (size_t)16u * R * LW * c->co.max;
+  HIP_TRY(c, hipMalloc(&c->co.d_n11, n11_b));
+  HIP_TRY(c, hipMalloc(&c->co.d_edge, edge_b));
+  HIP_TRY(c, hipMalloc(&c->co.d_bits, (size_t)8u * R * words));
+  HIP_TRY(c, hipMemsetAsync(c->co.d_n11, 0, n11_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->co.d_edge, 0, edge_b, c->stream));
+  c->co.at = at;
+  c->co.words = words;
+  c->co.R = R;
+  c->co.LW = LW;
+  c->co.N = N;
+  c->co.child0 = corr_child0(c);
+  c->co.samples = 0;
+  return EPV_OK;
+}
+// the part matches the current site range, number of nodes and branches and the root's first child (nothing else
+// of the tree matters: a row is one branch's meta words, and no jump time is read)
+int ensure_corr(epv_ctx *c) {
+  const bool sites = !(pavg_layout(c, true, true) == c->co.at);
+  const bool tree = c->S.N != c->co.N || corr_child0(c) != c->co.child0;
+  if (!sites && !tree) return EPV_OK;
+  if (c->co.samples) {
+    if (sites) return sites_changed(c, kCorr, "epv_set_spatial_correlation");
+    return fail(c, EPV_ERR_STATE, "the tree changed after the spatial correlations took samples: read them out and "
+                                  "epv_reset_spatial_correlation");
+  }
+  return relayout(c, kCorr, corr_alloc);
+}
+int corr_check_cap(epv_ctx *c, uint64_t more) {
+  if (c->co.samples + more > c->co.max) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "spatial correlations hold %llu of the %llu samples their edge records were "
+                  "allocated for, and %llu more were asked: read them out and epv_reset_spatial_correlation, or "
+                  "epv_set_spatial_correlation with more", (unsigned long long)c->co.samples,
+                  (unsigned long long)c->co.max, (unsigned long long)more);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_corr first): pack the rows, then count the pairs of every lag
+int launch_corr(epv_ctx *c) {
+  int rc = corr_check_cap(c, 1u);
+  if (rc) return rc;
+  const uint64_t words = c->co.words, chunks = (words + EPV_CORR_CHUNK_WORDS - 1u) / EPV_CORR_CHUNK_WORDS;
+  hipLaunchKernelGGL(epv_corr_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->co.at.lo,
+                     c->co.at.cnt, words, c->co.child0, c->co.d_bits);
+  HIP_TRY(c, hipGetLastError());
+  unsigned long long *edge = c->co.d_edge + c->co.samples * 2u * c->co.R * c->co.LW;
+  const unsigned threads = std::min<unsigned>(256u, (c->co.L + 1u + 63u) / 64u * 64u);   // (a thread owns lags)
+  for (uint32_t r0 = 0; r0 < c->co.R; r0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
+    const uint32_t nr = std::min<uint32_t>(65535u, c->co.R - r0);
+    hipLaunchKernelGGL(epv_corr_count_kernel, dim3((unsigned)chunks, nr), dim3(threads), 0, c->stream,
+                       (const unsigned long long *)c->co.d_bits, words, c->co.at.cnt, r0, c->co.L, c->co.d_n11, edge);
+    HIP_TRY(c, hipGetLastError());
+  }
+  ++c->co.samples;
+  return EPV_OK;
+}
+const Layer kCorr = {corr_on, ensure_corr, corr_check_cap, launch_corr, corr_off,
+                     "spatial correlations are off: epv_set_spatial_correlation first", "the spatial correlations"};
+
 // ---- change patterns (epv_patterns.h): the sites of pavg_range, R = 12 + 2 B + I uint32 rows
 bool patterns_on(const epv_ctx *c) { return c->pt.on; }
 void patterns_off(epv_ctx *c) {
@@ -1519,7 +1636,7 @@ const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, 
 
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
-const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover};
+const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover, &kCorr};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -3886,6 +4003,68 @@ EPV_API int epv_get_domain_turnover(epv_ctx *c, uint64_t *hist, uint64_t *len_su
   HIP_TRY(c, hipMemcpy(len_sum, c->to.d_len, (size_t)32u * c->to.R, hipMemcpyDeviceToHost));
   if (c->to.samples)
     HIP_TRY(c, hipMemcpy(edges, c->to.d_edge, (size_t)16u * c->to.R * c->to.samples, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+// ---- spatial correlations (epv_corr.h)
+EPV_API int epv_set_spatial_correlation(epv_ctx *c, uint32_t max_lag, uint64_t max_samples) {
+  if (!max_lag) return layer_set_off(c, kCorr);
+  if (!c) return EPV_ERR_ARG;
+  if (max_lag > EPV_CORR_MAX_LAG) return fail(c, EPV_ERR_ARG, "spatial correlations take lags up to 1024");
+  if (!max_samples) return fail(c, EPV_ERR_ARG, "spatial correlations: max_samples is at least 1");
+  if (max_samples > EPV_CORR_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "spatial correlations take at most 2^21 samples");
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->co.L = max_lag;
+  c->co.max = max_samples;
+  return layer_set_on(c, kCorr, corr_alloc);
+}
+
+EPV_API int epv_reset_spatial_correlation(epv_ctx *c) {
+  const int rc = layer_entry(c, kCorr);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->co.d_n11, 0, (size_t)8u * c->co.R * (c->co.L + 1u), c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->co.d_edge, 0, (size_t)16u * c->co.R * c->co.LW * c->co.max, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->co.samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_spatial_correlation(epv_ctx *c) { return layer_accumulate(c, kCorr); }
+
+EPV_API int epv_spatial_correlation_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->co.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_spatial_correlation_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *max_lag, uint64_t *first,
+                                           uint64_t *count, uint64_t *chunk_sites) {
+  if (!c || !n_rows || !max_lag || !first || !count || !chunk_sites) return EPV_ERR_ARG;
+  *n_rows = *max_lag = 0;
+  *first = *count = *chunk_sites = 0;
+  if (!corr_on(c)) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->co.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_corr(c);
+    if (rc) return rc;
+  }
+  *n_rows = c->co.R;
+  *max_lag = c->co.L;
+  *first = c->co.at.lo;
+  *count = c->co.at.cnt;
+  *chunk_sites = 64ull * EPV_CORR_CHUNK_WORDS;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_spatial_correlation(epv_ctx *c, uint64_t *n11, uint64_t *edges) {
+  const int rc = layer_entry(c, kCorr);
+  if (rc) return rc;
+  if (!n11 || !edges) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(n11, c->co.d_n11, (size_t)8u * c->co.R * (c->co.L + 1u), hipMemcpyDeviceToHost));
+  if (c->co.samples)
+    HIP_TRY(c, hipMemcpy(edges, c->co.d_edge, (size_t)16u * c->co.R * c->co.LW * c->co.samples, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 

@@ -36,6 +36,10 @@
 // per branch the runs of the state at its start and at its end, each kept or turned over -- domains born and died,
 // gaps filled and opened -- closed over the whole genome), as integers (epv::write_domain_turnover).  Changes
 // nothing else the run writes.
+// New: -C/--correlation FILE with -M/--maxlag L (default 64, at most 1024): the spatial correlations of the B batch
+// sweeps (epv_set_spatial_correlation with max_samples = B: per node state row and branch change row the pairs of
+// ones at every lag 1 .. L, closed over the whole genome), as integers (epv::write_spatial_correlation).  Changes
+// nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -61,10 +65,12 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
+    const size_t no_lag = std::numeric_limits<size_t>::max();
+    size_t max_lag = no_lag;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
     size_t rng_seed = std::numeric_limits<size_t>::max();
@@ -99,6 +105,9 @@ int main(int argc, const char **argv) {
                       false, patterns_file);
     opt_parse.add_opt("turnover", 'R', "output file of the domain turnover of the batch sweeps (integer counts per bin)",
                       false, turnover_file);
+    opt_parse.add_opt("correlation", 'C', "output file of the spatial correlations of the batch sweeps (integer pair counts "
+                      "per lag)", false, corr_file);
+    opt_parse.add_opt("maxlag", 'M', "largest lag of the spatial correlations (default 64, at most 1024)", false, max_lag);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps and "
                       "change patterns (default 1)", false, window);
@@ -131,11 +140,17 @@ int main(int argc, const char **argv) {
       throw std::runtime_error("-K/--nepochs belongs to -E/--epochs: give the output file of the epoch statistics");
     if (n_epochs == no_epochs) n_epochs = 10;
     if (n_epochs == 0 || n_epochs > EPV_EPOCH_MAX_P) throw std::runtime_error("-K: 1 to 256 epochs per branch");
+    if (max_lag != no_lag && corr_file.empty())
+      throw std::runtime_error("-M/--maxlag belongs to -C/--correlation: give the output file of the spatial correlations");
+    if (max_lag == no_lag) max_lag = 64;
+    if (max_lag == 0 || max_lag > 1024) throw std::runtime_error("-M: a largest lag of 1 to 1024 sites");
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
     if (!turnover_file.empty() && batch > (1ull << 21))
       throw std::runtime_error("-R/--turnover: the domain turnover takes at most 2^21 batch sweeps (-B)");
+    if (!corr_file.empty() && batch > (1ull << 21))
+      throw std::runtime_error("-C/--correlation: the spatial correlations take at most 2^21 batch sweeps (-B)");
     const string param_file(leftover_args.front()), input_file(leftover_args.back());
 
     if (VERBOSE) cerr << "[READING PARAMETERS: " << param_file << "]" << endl;
@@ -182,6 +197,7 @@ int main(int argc, const char **argv) {
     if (!epochs_file.empty()) mcmc.set_epoch_stats((uint32_t)n_epochs);
     if (!patterns_file.empty()) mcmc.set_change_patterns(true);
     if (!turnover_file.empty()) mcmc.set_domain_turnover(batch);
+    if (!corr_file.empty()) mcmc.set_spatial_correlation((uint32_t)max_lag, batch);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -264,6 +280,15 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING DOMAIN TURNOVER OF " << n_samples << " SAMPLES: " << turnover_file << "]" << endl;
       const vector<string> branch_names(th.node_names.begin() + 1, th.node_names.end());
       epv::write_domain_turnover(turnover_file, branch_names, n_samples, hist.data(), len_sum.data());
+    }
+    if (!corr_file.empty()) {
+      vector<uint64_t> n11, left1, right1;
+      uint32_t n_rows = 0, L = 0;
+      uint64_t n_samples = 0;
+      mcmc.download_spatial_correlation(n11, left1, right1, n_rows, L, n_samples);
+      if (VERBOSE) cerr << "[WRITING SPATIAL CORRELATIONS OF " << n_samples << " SAMPLES: " << corr_file << "]" << endl;
+      epv::write_spatial_correlation(corr_file, th.node_names, n_samples, out.n_sites, L, n11.data(), left1.data(),
+                                     right1.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

@@ -38,6 +38,8 @@ struct epvd_sampler {
   bool have_staged_domains = false;
   std::vector<uint64_t> staged_turn_hist, staged_turn_len, staged_turn_edges;   // between epvd_turnover_part_sizes and epvd_download_turnover_part
   bool have_staged_turnover = false;
+  std::vector<uint64_t> staged_corr_n11, staged_corr_edges;   // between epvd_corr_part_sizes and epvd_download_corr_part
+  bool have_staged_corr = false;
 };
 
 namespace {
@@ -449,6 +451,49 @@ EPVD_API int epvd_download_turnover(epvd_sampler *h, uint32_t n_rows, uint64_t *
     if (R != n_rows) throw std::runtime_error("epvd_download_turnover: n_rows must be twice the tree's number of branches");
     std::copy(hh.begin(), hh.end(), hist);
     std::copy(ll.begin(), ll.end(), len_sum);
+    if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_corr(epvd_sampler *h, uint32_t max_lag, uint64_t max_samples) {
+  return guarded(h, [&] { h->s->set_spatial_correlation(max_lag, max_samples); });
+}
+EPVD_API int epvd_reset_corr(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_spatial_correlation(); });
+}
+EPVD_API int epvd_accumulate_corr(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_spatial_correlation(); });
+}
+EPVD_API int epvd_corr_part_sizes(epvd_sampler *h, uint32_t *n_rows, uint32_t *max_lag, uint64_t *n_samples,
+                                  uint64_t *n_sites) {
+  return guarded(h, [&] {
+    h->s->download_spatial_correlation_part(h->staged_corr_n11, h->staged_corr_edges, *n_rows, *max_lag, *n_samples,
+                                            *n_sites);
+    h->have_staged_corr = true;
+  });
+}
+EPVD_API int epvd_download_corr_part(epvd_sampler *h, uint64_t *n11, uint64_t *edges) {
+  return guarded(h, [&] {
+    if (!h->have_staged_corr) throw std::runtime_error("epvd_corr_part_sizes first");
+    std::copy(h->staged_corr_n11.begin(), h->staged_corr_n11.end(), n11);
+    std::copy(h->staged_corr_edges.begin(), h->staged_corr_edges.end(), edges);
+    h->staged_corr_n11.clear();
+    h->staged_corr_edges.clear();
+    h->have_staged_corr = false;
+  });
+}
+EPVD_API int epvd_download_corr(epvd_sampler *h, uint32_t n_rows, uint32_t max_lag, uint64_t *n11, uint64_t *left1,
+                                uint64_t *right1, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> a, l, r;
+    uint32_t R = 0, L = 0;
+    uint64_t ns = 0;
+    h->s->download_spatial_correlation(a, l, r, R, L, ns);
+    if (R != n_rows || L != max_lag)
+      throw std::runtime_error("epvd_download_corr: n_rows must be the tree's nodes plus branches and max_lag the one set");
+    std::copy(a.begin(), a.end(), n11);
+    std::copy(l.begin(), l.end(), left1);
+    std::copy(r.begin(), r.end(), right1);
     if (n_samples) *n_samples = ns;
   });
 }

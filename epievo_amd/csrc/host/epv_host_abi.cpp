@@ -13,6 +13,7 @@
 #include "epv_io.hpp"
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
+#include "epv_corr.hpp"
 #include "epv_epochs.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
@@ -529,6 +530,58 @@ EPVH_API void epvh_domain_turnover_copy(void *h, char *names, int names_len, uin
   std::copy(dt->len_sum.begin(), dt->len_sum.end(), len_sum);
 }
 EPVH_API void epvh_domain_turnover_free(void *h) { delete (epv::DomainTurnover *)h; }
+
+// ---- spatial correlations: merge and close of parts (epv_corr.hpp), the file of epievo_est_histories -C
+// cnts, n11s, edges: n_parts entries each, parts in genome order ([R][L + 1], [samples][R][2][LW]); out_cnt: the
+// sites of the union
+EPVH_API int epvh_corr_parts_merge(uint64_t n_parts, uint32_t R, uint32_t L, uint64_t samples, const uint64_t *cnts,
+                                   const uint64_t *const *n11s, const uint64_t *const *edges, uint64_t *out_n11,
+                                   uint64_t *out_edges, uint64_t *out_cnt) {
+  try {
+    const uint64_t n = epv::corr_parts_merge(n_parts, R, L, samples, cnts, n11s, edges, out_n11, out_edges);
+    if (out_cnt) *out_cnt = n;
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API int epvh_corr_part_close(uint32_t R, uint32_t L, uint64_t samples, uint64_t n, const uint64_t *n11,
+                                  const uint64_t *edges, uint64_t *left1, uint64_t *right1) {
+  try {
+    epv::corr_part_close(R, L, samples, n, n11, edges, left1, right1);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// node_names: the N node names joined by '\n'; n11, left1, right1 [2 N - 1][L + 1]: closed
+EPVH_API int epvh_write_spatial_correlation(const char *file, const char *node_names, uint64_t n_samples, uint64_t n_sites,
+                                            uint32_t max_lag, const uint64_t *n11, const uint64_t *left1,
+                                            const uint64_t *right1) {
+  try {
+    epv::write_spatial_correlation(file, split_names(node_names), n_samples, n_sites, max_lag, n11, left1, right1);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_spatial_correlation(const char *file) {
+  try {
+    return new epv::SpatialCorrelation(epv::read_spatial_correlation(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+EPVH_API void epvh_spatial_correlation_dims(void *h, uint64_t *n_samples, uint64_t *n_sites, uint64_t *max_lag,
+                                            uint64_t *n_rows, uint64_t *names_len) {
+  const epv::SpatialCorrelation *sc = (const epv::SpatialCorrelation *)h;
+  *n_samples = sc->n_samples;
+  *n_sites = sc->n_sites;
+  *max_lag = sc->max_lag;
+  *n_rows = sc->row_names.size();
+  *names_len = join_names(sc->row_names).size() + 1u;
+}
+EPVH_API void epvh_spatial_correlation_copy(void *h, char *names, int names_len, uint64_t *n11, uint64_t *left1,
+                                            uint64_t *right1) {
+  const epv::SpatialCorrelation *sc = (const epv::SpatialCorrelation *)h;
+  put_text(join_names(sc->row_names), names, names_len);
+  std::copy(sc->n11.begin(), sc->n11.end(), n11);
+  std::copy(sc->left1.begin(), sc->left1.end(), left1);
+  std::copy(sc->right1.begin(), sc->right1.end(), right1);
+}
+EPVH_API void epvh_spatial_correlation_free(void *h) { delete (epv::SpatialCorrelation *)h; }
 
 // ---- epoch statistics: closing the difference form (epv_epochs.hpp), and the file of epievo_est_histories -E
 EPVH_API void epvh_epoch_edges(uint64_t fixT, uint32_t P, uint64_t *out) { epv::epoch_edges(fixT, P, out); }

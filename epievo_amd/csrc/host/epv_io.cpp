@@ -1074,6 +1074,80 @@ DomainTurnover read_domain_turnover(const std::string &file) {
   return dt;
 }
 
+void write_spatial_correlation(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_samples,
+                               uint64_t n_sites, uint32_t max_lag, const uint64_t *n11, const uint64_t *left1,
+                               const uint64_t *right1) {
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  const size_t N = node_names.size(), R = N ? 2u * N - 1u : 0u, W = (size_t)max_lag + 1u;
+  out << "#samples\t" << n_samples << "\tsites\t" << n_sites << "\tmax_lag\t" << max_lag << '\n';
+  for (size_t r = 0; r < R; ++r) {
+    if (r < N) out << "NODE:" << node_names[r] << '\n';
+    else out << "BRANCH:" << node_names[r - N + 1u] << '\n';
+    out << "ones\t" << n11[r * W] << '\n';
+    for (size_t d = 1; d < W; ++d)
+      out << d << '\t' << n11[r * W + d] << '\t' << left1[r * W + d] << '\t' << right1[r * W + d] << '\n';
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
+SpatialCorrelation read_spatial_correlation(const std::string &file) {
+  std::ifstream in(file);
+  if (!in) throw std::runtime_error("bad spatial-correlation file: " + file);
+  auto bad = [&](const std::string &what) { return std::runtime_error("spatial-correlation file " + file + ": " + what); };
+  auto fields = [](const std::string &line) {
+    std::vector<std::string> f;
+    size_t a = 0;
+    for (;;) {
+      const size_t t = line.find('\t', a);
+      f.push_back(line.substr(a, t == std::string::npos ? t : t - a));
+      if (t == std::string::npos) break;
+      a = t + 1;
+    }
+    return f;
+  };
+  SpatialCorrelation sc;
+  std::string line;
+  if (!std::getline(in, line)) throw bad("empty");
+  std::vector<std::string> f = fields(line);
+  if (f.size() != 6 || f[0] != "#samples" || f[2] != "sites" || f[4] != "max_lag") throw bad("bad header: " + line);
+  sc.n_samples = std::stoull(f[1]);
+  sc.n_sites = std::stoull(f[3]);
+  const uint64_t L = std::stoull(f[5]);
+  if (L == 0u || L > 1024u) throw bad("max_lag is 1 .. 1024: " + line);
+  sc.max_lag = (uint32_t)L;
+  const size_t W = (size_t)L + 1u;
+  uint64_t next = W;   // the lag the next line of the current row holds (W: the row is complete)
+  while (std::getline(in, line)) {
+    if (line.empty()) continue;
+    if (line.compare(0, 5, "NODE:") == 0 || line.compare(0, 7, "BRANCH:") == 0) {
+      if (next != W) throw bad("a row without all its lags before: " + line);
+      sc.row_names.push_back(line);
+      sc.n11.resize(sc.row_names.size() * W, 0u);
+      sc.left1.resize(sc.row_names.size() * W, 0u);
+      sc.right1.resize(sc.row_names.size() * W, 0u);
+      next = 0;
+      continue;
+    }
+    if (sc.row_names.empty()) throw bad("a line before the first row: " + line);
+    f = fields(line);
+    const size_t at = (sc.row_names.size() - 1u) * W + (size_t)next;
+    if (next == 0u) {
+      if (f.size() != 2 || f[0] != "ones") throw bad("bad ones line: " + line);
+      sc.n11[at] = sc.left1[at] = sc.right1[at] = std::stoull(f[1]);
+    } else {
+      if (next >= W || f.size() != 4 || std::stoull(f[0]) != next) throw bad("bad lag line: " + line);
+      sc.n11[at] = std::stoull(f[1]);
+      sc.left1[at] = std::stoull(f[2]);
+      sc.right1[at] = std::stoull(f[3]);
+    }
+    ++next;
+  }
+  if (next != W) throw bad("the last row lacks a lag");
+  return sc;
+}
+
 // a 128-bit integer (low, high word) in decimal, and back
 static std::string u128_str(uint64_t lo, uint64_t hi) {
   unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;

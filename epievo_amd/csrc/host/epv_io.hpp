@@ -146,6 +146,21 @@ void write_domain_turnover(const std::string &file, const std::vector<std::strin
                            const uint64_t *hist, const uint64_t *len_sum);
 DomainTurnover read_domain_turnover(const std::string &file);
 
+// the spatial correlations of epievo_est_histories -C (the closed result of epv_get_spatial_correlation), integers
+// only: "#samples\t<S>\tsites\t<n>\tmax_lag\t<L>", then per row "NODE:<name>" (the N nodes) or "BRANCH:<child node
+//   name>" (the B branches), a line "ones\t<n11[0]>" and one line "d\tn11\tleft1\tright1" per lag 1 .. L.
+//   n11, left1, right1: [N + B][L + 1] (uint64)
+struct SpatialCorrelation {
+  uint64_t n_samples = 0, n_sites = 0;
+  uint32_t max_lag = 0;
+  std::vector<std::string> row_names;   // "NODE:<name>" or "BRANCH:<name>"
+  std::vector<uint64_t> n11, left1, right1;   // [R][L + 1]
+};
+void write_spatial_correlation(const std::string &file, const std::vector<std::string> &node_names, uint64_t n_samples,
+                               uint64_t n_sites, uint32_t max_lag, const uint64_t *n11, const uint64_t *left1,
+                               const uint64_t *right1);
+SpatialCorrelation read_spatial_correlation(const std::string &file);
+
 // the epoch statistics of epievo_est_histories -E (epv_get_epoch_stats closed by epv::epoch_close):
 //   "#samples\t<S>\tepochs\t<P>", then per non-root node in pre-order "NODE:<name>\t<branch length>\t<k_b>"
 //   (%.17g; D integers are in units of 2^-k_b) and one line per epoch: the epoch's start as a fraction of

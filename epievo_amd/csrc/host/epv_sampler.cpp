@@ -15,6 +15,7 @@
 #include "epievo_mi355x.h"
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
+#include "epv_corr.hpp"
 #include "epievo_mi355x_comm.h"
 
 namespace epv {
@@ -437,6 +438,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (domains_max_) set_domain_stats(domains_max_);
   if (patterns_) set_change_patterns(true);
   if (turnover_max_) set_domain_turnover(turnover_max_);
+  if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -451,6 +453,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (domains_max_) set_domain_stats(domains_max_);
   if (patterns_) set_change_patterns(true);
   if (turnover_max_) set_domain_turnover(turnover_max_);
+  if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -873,6 +876,76 @@ void SingleSiteSampler::download_domain_turnover(std::vector<uint64_t> &hist, st
   std::vector<uint64_t> edges;
   download_domain_turnover_part(hist, len_sum, edges, n_rows, n_samples);
   turnover_part_close(n_rows, n_samples, hist.data(), len_sum.data(), edges.data());
+}
+
+void SingleSiteSampler::set_spatial_correlation(uint32_t max_lag, uint64_t max_samples) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !max_lag)
+    for (epv_ctx *c : contexts())
+      check_on(c, epv_set_spatial_correlation(c, max_lag, max_samples), "epv_set_spatial_correlation");
+  corr_lag_ = max_lag;
+  corr_max_ = max_lag ? max_samples : 0u;
+}
+
+void SingleSiteSampler::reset_spatial_correlation() {
+  if (!corr_lag_) throw std::runtime_error("spatial correlations are off: set_spatial_correlation first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_spatial_correlation(c), "epv_reset_spatial_correlation");
+}
+
+void SingleSiteSampler::accumulate_spatial_correlation() {
+  if (!corr_lag_) throw std::runtime_error("spatial correlations are off: set_spatial_correlation first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_spatial_correlation(c), "epv_accumulate_spatial_correlation");
+}
+
+void SingleSiteSampler::download_spatial_correlation_part(std::vector<uint64_t> &n11, std::vector<uint64_t> &edges,
+                                                          uint32_t &n_rows, uint32_t &max_lag, uint64_t &n_samples,
+                                                          uint64_t &n_sites) {
+  if (!corr_lag_) throw std::runtime_error("spatial correlations are off: set_spatial_correlation first");
+  const std::vector<epv_ctx *> cs = contexts();   // in genome order
+  std::vector<std::vector<uint64_t>> a(cs.size()), e(cs.size());
+  std::vector<const uint64_t *> ap(cs.size()), ep(cs.size());
+  std::vector<uint64_t> cnts(cs.size(), 0u);
+  n_rows = 0;
+  max_lag = corr_lag_;
+  n_samples = 0;
+  const uint32_t LW = corr_edge_words(corr_lag_);
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t R = 0, L = 0;
+    uint64_t first = 0, count = 0, chunk = 0, ns = 0;
+    check_on(cs[i], epv_spatial_correlation_layout(cs[i], &R, &L, &first, &count, &chunk), "epv_spatial_correlation_layout");
+    check_on(cs[i], epv_spatial_correlation_samples(cs[i], &ns), "epv_spatial_correlation_samples");
+    if (L != corr_lag_) throw std::runtime_error("a context holds spatial correlations of another max_lag");
+    if (i == 0) { n_rows = R; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of spatial-correlation samples");
+    else if (R != n_rows) throw std::runtime_error("the contexts hold spatial correlations of different trees");
+    cnts[i] = count;
+    a[i].assign((size_t)R * (L + 1u), 0u);
+    e[i].assign(std::max<size_t>((size_t)ns * R * 2u * LW, 1u), 0u);
+    check_on(cs[i], epv_get_spatial_correlation(cs[i], a[i].data(), e[i].data()), "epv_get_spatial_correlation");
+    ap[i] = a[i].data(); ep[i] = e[i].data();
+  }
+  n11.assign((size_t)n_rows * (max_lag + 1u), 0u);
+  edges.assign(std::max<size_t>((size_t)n_samples * n_rows * 2u * LW, 1u), 0u);
+  n_sites = corr_parts_merge(cs.size(), n_rows, max_lag, n_samples, cnts.data(), ap.data(), ep.data(), n11.data(),
+                             edges.data());
+  edges.resize((size_t)n_samples * n_rows * 2u * LW);
+}
+
+void SingleSiteSampler::download_spatial_correlation(std::vector<uint64_t> &n11, std::vector<uint64_t> &left1,
+                                                     std::vector<uint64_t> &right1, uint32_t &n_rows,
+                                                     uint32_t &max_lag, uint64_t &n_samples) {
+  if (rank_mode_)
+    throw std::runtime_error("download_spatial_correlation: this process holds one slot's stretch of the genome, not "
+                             "the genome: merge the processes' download_spatial_correlation_part in genome order "
+                             "(epv::corr_parts_merge, epvh_corr_parts_merge), then close the merged part");
+  std::vector<uint64_t> edges;
+  uint64_t n_sites = 0;
+  download_spatial_correlation_part(n11, edges, n_rows, max_lag, n_samples, n_sites);
+  left1.assign(n11.size(), 0u);
+  right1.assign(n11.size(), 0u);
+  std::vector<uint64_t> none(1, 0u);
+  corr_part_close(n_rows, max_lag, n_samples, n_sites, n11.data(), edges.empty() ? none.data() : edges.data(),
+                  left1.data(), right1.data());
 }
 
 void SingleSiteSampler::set_epoch_stats(uint32_t P) {

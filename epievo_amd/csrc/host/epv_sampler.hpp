@@ -174,6 +174,21 @@ public:
                                      std::vector<uint64_t> &edges, uint32_t &n_rows, uint64_t &n_samples);
   void download_domain_turnover(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_rows,
                                 uint64_t &n_samples);
+  // spatial correlations (epv_set_spatial_correlation) on every context, with the domain turnover's samples and
+  // lifecycle; max_lag = 0 is off.  n_rows = 2 n_nodes - 1.  download_spatial_correlation_part: the parts of all
+  // slots and contexts of this process merged in genome order (epv::corr_parts_merge), unclosed: n11 [R][L + 1],
+  // edges [samples][R][2][ceil(L / 64)], over n_sites sites.  download_spatial_correlation: that part closed
+  // (epv::corr_part_close) into left1 and right1 [R][L + 1].  One slot per process: it throws, as
+  // download_domain_turnover does
+  void set_spatial_correlation(uint32_t max_lag, uint64_t max_samples);
+  uint32_t spatial_correlation_max_lag() const { return corr_lag_; }
+  void reset_spatial_correlation();
+  void accumulate_spatial_correlation();
+  void download_spatial_correlation_part(std::vector<uint64_t> &n11, std::vector<uint64_t> &edges, uint32_t &n_rows,
+                                         uint32_t &max_lag, uint64_t &n_samples, uint64_t &n_sites);
+  void download_spatial_correlation(std::vector<uint64_t> &n11, std::vector<uint64_t> &left1,
+                                    std::vector<uint64_t> &right1, uint32_t &n_rows, uint32_t &max_lag,
+                                    uint64_t &n_samples);
   // change patterns (epv_set_change_patterns) on every context, with the branch events' samples and lifecycle.
   // n_rows = 12 + 2 (n_nodes-1) + internal non-root nodes.  download_change_patterns: rows[r * sites + site] over
   // the sites of this process in genome order; download_change_pattern_windows: sums[r * n_windows + w] over
@@ -297,6 +312,8 @@ private:
   bool origins_ = false;      // set_lineage_origins
   uint64_t domains_max_ = 0; // set_domain_stats
   uint64_t turnover_max_ = 0; // set_domain_turnover
+  uint32_t corr_lag_ = 0;     // set_spatial_correlation
+  uint64_t corr_max_ = 0;
   bool patterns_ = false;     // set_change_patterns
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none

@@ -27,6 +27,8 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats",
                   "epvd_set_turnover", "epvd_reset_turnover", "epvd_accumulate_turnover",
                   "epvd_turnover_part_sizes", "epvd_download_turnover_part", "epvd_download_turnover",
+                  "epvd_set_corr", "epvd_reset_corr", "epvd_accumulate_corr",
+                  "epvd_corr_part_sizes", "epvd_download_corr_part", "epvd_download_corr",
                   "epvd_set_change_patterns", "epvd_change_patterns_sizes", "epvd_download_change_patterns",
                   "epvd_download_change_pattern_windows"]
 
@@ -97,6 +99,12 @@ def lib():
         L.epvd_turnover_part_sizes.argtypes = [vp, u32p, u64p]
         L.epvd_download_turnover_part.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_turnover.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
+        L.epvd_set_corr.argtypes = [vp, C.c_uint32, C.c_uint64]
+        L.epvd_reset_corr.argtypes = [vp]
+        L.epvd_accumulate_corr.argtypes = [vp]
+        L.epvd_corr_part_sizes.argtypes = [vp, u32p, u32p, u64p, u64p]
+        L.epvd_download_corr_part.argtypes = [vp, u64p, u64p]
+        L.epvd_download_corr.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p]
         _lib = L
     return _lib
 
@@ -463,3 +471,38 @@ class CppSampler:
         hist, len_sum, ns = np.zeros((R, 2, 2, 128), np.uint64), np.zeros((R, 2, 2), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_turnover(self.h, R, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
         return int(ns.value), hist, len_sum
+
+    def enable_spatial_correlation(self, max_lag, max_samples):
+        """spatial correlations on every context, lags 0 .. max_lag, for at most max_samples samples (max_lag = 0:
+        off); kept across reset()"""
+        self._ck(self.L.epvd_set_corr(self.h, int(max_lag), int(max_samples)))
+        self._corr_lag = int(max_lag)
+
+    def reset_spatial_correlation(self):
+        self._ck(self.L.epvd_reset_corr(self.h))
+
+    def accumulate_spatial_correlation(self):
+        self._ck(self.L.epvd_accumulate_corr(self.h))
+
+    def spatial_correlation_part(self):
+        """-> (samples, sites, n11 [R, L + 1], edges [samples, R, 2, ceil(L / 64)]), uint64: the parts of the slots
+        and contexts of this process merged in genome order, unclosed"""
+        R, L, ns, cnt = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epvd_corr_part_sizes(self.h, C.byref(R), C.byref(L), C.byref(ns), C.byref(cnt)))
+        R, L, ns = int(R.value), int(L.value), int(ns.value)
+        LW = (L + 63) // 64
+        n11 = np.zeros(max(R * (L + 1), 1), np.uint64)
+        edges = np.zeros(max(ns * R * 2 * LW, 1), np.uint64)
+        self._ck(self.L.epvd_download_corr_part(self.h, _p(n11, C.c_uint64), _p(edges, C.c_uint64)))
+        return ns, int(cnt.value), n11[:R * (L + 1)].reshape(R, L + 1), edges[:ns * R * 2 * LW].reshape(ns, R, 2, LW)
+
+    def spatial_correlation(self):
+        """-> (samples, n11, left1, right1), each [R, L + 1]: the closed result over the genome (one slot per process:
+        an error; merge the processes' spatial_correlation_part with host.corr_parts_merge, then
+        host.corr_part_close)"""
+        R, L = 2 * self.B + 1, getattr(self, "_corr_lag", 0)
+        n11, left1, right1 = (np.zeros((R, L + 1), np.uint64) for _ in range(3))
+        ns = C.c_uint64(0)
+        self._ck(self.L.epvd_download_corr(self.h, R, L, _p(n11, C.c_uint64), _p(left1, C.c_uint64),
+                                           _p(right1, C.c_uint64), C.byref(ns)))
+        return int(ns.value), n11, left1, right1

@@ -93,6 +93,19 @@ def lib():
         L.epvh_domain_turnover_copy.restype = None
         L.epvh_domain_turnover_free.argtypes = [C.c_void_p]
         L.epvh_domain_turnover_free.restype = None
+        L.epvh_corr_parts_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64pp, u64pp, u64p, u64p,
+                                            u64p]
+        L.epvh_corr_part_close.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p]
+        L.epvh_write_spatial_correlation.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint32, u64p, u64p,
+                                                     u64p]
+        L.epvh_read_spatial_correlation.argtypes = [C.c_char_p]
+        L.epvh_read_spatial_correlation.restype = C.c_void_p
+        L.epvh_spatial_correlation_dims.argtypes = [C.c_void_p, u64p, u64p, u64p, u64p, u64p]
+        L.epvh_spatial_correlation_dims.restype = None
+        L.epvh_spatial_correlation_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, u64p, u64p, u64p]
+        L.epvh_spatial_correlation_copy.restype = None
+        L.epvh_spatial_correlation_free.argtypes = [C.c_void_p]
+        L.epvh_spatial_correlation_free.restype = None
         u64p_, u32 = C.POINTER(C.c_uint64), C.c_uint32
         L.epvh_epoch_edges.argtypes = [C.c_uint64, u32, u64p_]
         L.epvh_epoch_edges.restype = None
@@ -583,6 +596,108 @@ def read_domain_turnover(path):
                     len_sum=len_sum)
     finally:
         L.epvh_domain_turnover_free(h)
+
+
+# ---- spatial correlations (two-point counts of node states and branch changes along the genome)
+def _corr_dims(n11, edges):
+    bad = ValueError("a part is n11 [R, L + 1] with 1 <= L <= 1024 and edges [samples, R, 2, ceil(L / 64)]")
+    if n11.ndim != 2 or edges.ndim != 4:
+        raise bad
+    R, L = n11.shape[0], n11.shape[1] - 1
+    if L < 1 or L > 1024 or edges.shape[1:] != (R, 2, (L + 63) // 64):
+        raise bad
+    return R, L, edges.shape[0]
+
+
+def corr_parts_merge(parts):
+    """parts: [(sites, n11 [R, L + 1], edges [samples, R, 2, LW])] of adjacent stretches of sites in genome order, of
+    the same samples, each of at least L sites -> the part of their union, (sites, n11, edges)"""
+    if not parts:
+        raise ValueError("no parts")
+    cnts = np.array([int(p[0]) for p in parts], np.uint64)
+    n11s = [np.ascontiguousarray(p[1], np.uint64) for p in parts]
+    edges = [np.ascontiguousarray(p[2], np.uint64) for p in parts]
+    R, L, ns = _corr_dims(n11s[0], edges[0])
+    for a, e in zip(n11s, edges):
+        if a.shape != n11s[0].shape or e.shape != edges[0].shape:
+            raise ValueError("the parts differ in rows, max_lag or samples")
+    n11, out = np.zeros((R, L + 1), np.uint64), np.zeros(edges[0].shape, np.uint64)
+    o = out if out.size else np.zeros(1, np.uint64)
+    total = C.c_uint64(0)
+    if lib().epvh_corr_parts_merge(len(parts), R, L, ns, _p(cnts, C.c_uint64), _ptrs(n11s),
+                                   _ptrs([e if e.size else np.zeros(1, np.uint64) for e in edges]),
+                                   _p(n11 if n11.size else np.zeros(1, np.uint64), C.c_uint64), _p(o, C.c_uint64),
+                                   C.byref(total)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return int(total.value), n11, out
+
+
+def corr_part_close(sites, n11, edges):
+    """a part over the whole genome of `sites` sites -> (n11, left1, right1), each [R, L + 1]: left1[r][d] (right1)
+    are the ones at the left (right) site of the samples x (sites - d) pairs of lag d"""
+    n11, edges = np.ascontiguousarray(n11, np.uint64), np.ascontiguousarray(edges, np.uint64)
+    R, L, ns = _corr_dims(n11, edges)
+    left1, right1 = np.zeros((R, L + 1), np.uint64), np.zeros((R, L + 1), np.uint64)
+    one = np.zeros(1, np.uint64)
+    if lib().epvh_corr_part_close(R, L, ns, int(sites), _p(n11 if R else one, C.c_uint64),
+                                  _p(edges if edges.size else one, C.c_uint64), _p(left1 if R else one, C.c_uint64),
+                                  _p(right1 if R else np.zeros(1, np.uint64), C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return n11.copy(), left1, right1
+
+
+def spatial_correlation_summary(samples, n_sites, n11, left1, right1, tree):
+    """a closed result -> dict: p11, p10, p01, p00 (float64 [R, L + 1], the joint frequencies of (X[p], X[p + d]) over
+    the samples x (n_sites - d) pairs of lag d), corr (their Pearson correlation, nan where a margin is 0 or 1) and
+    decay (per row the first lag >= 1 at which corr falls below 1/e, or None)"""
+    n11, left1, right1 = (np.asarray(a, np.uint64).astype(np.float64) for a in (n11, left1, right1))
+    R = 2 * tree.n_nodes - 1
+    if n11.ndim != 2 or n11.shape[0] != R or left1.shape != n11.shape or right1.shape != n11.shape:
+        raise ValueError("n11, left1 and right1 are [N + B, L + 1] of the tree's N nodes and B branches")
+    L = n11.shape[1] - 1
+    pairs = float(samples) * (float(n_sites) - np.arange(L + 1, dtype=np.float64))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p11, pl, pr = n11 / pairs, left1 / pairs, right1 / pairs
+        var = pl * (1.0 - pl) * pr * (1.0 - pr)
+        corr = np.where(var > 0.0, (p11 - pl * pr) / np.sqrt(var), np.nan)
+    decay = []
+    for r in range(R):
+        below = np.nonzero(corr[r, 1:] < np.exp(-1.0))[0]
+        decay.append(int(below[0]) + 1 if len(below) else None)
+    return dict(p11=p11, p10=pl - p11, p01=pr - p11, p00=1.0 - pl - pr + p11, corr=corr, decay=decay)
+
+
+def write_spatial_correlation(path, node_names, samples, n_sites, n11, left1, right1):
+    """the file of epievo_est_histories -C: the closed result, integers only; node_names = the N node names"""
+    n11, left1, right1 = (np.ascontiguousarray(a, np.uint64) for a in (n11, left1, right1))
+    R = 2 * len(node_names) - 1
+    if n11.ndim != 2 or n11.shape[0] != R or n11.shape[1] < 2 or left1.shape != n11.shape or right1.shape != n11.shape:
+        raise ValueError("n11, left1 and right1 are [2 nodes - 1, L + 1]")
+    if lib().epvh_write_spatial_correlation(path.encode(), "\n".join(node_names).encode(), int(samples), int(n_sites),
+                                            n11.shape[1] - 1, _p(n11, C.c_uint64), _p(left1, C.c_uint64),
+                                            _p(right1, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_spatial_correlation(path):
+    """-> dict(samples, sites, max_lag, row_names ("NODE:<name>" / "BRANCH:<name>"), n11, left1, right1 uint64
+    [R, L + 1])"""
+    L_ = lib()
+    h = L_.epvh_read_spatial_correlation(path.encode())
+    if not h:
+        raise RuntimeError(L_.epvh_last_error().decode())
+    try:
+        ns, n, ml, R, ln = (C.c_uint64(0) for _ in range(5))
+        L_.epvh_spatial_correlation_dims(h, C.byref(ns), C.byref(n), C.byref(ml), C.byref(R), C.byref(ln))
+        R, ml = int(R.value), int(ml.value)
+        buf = C.create_string_buffer(int(ln.value))
+        arrs = [np.zeros((R, ml + 1), np.uint64) for _ in range(3)]
+        ptrs = [_p(a if a.size else np.zeros(1, np.uint64), C.c_uint64) for a in arrs]
+        L_.epvh_spatial_correlation_copy(h, buf, len(buf), *ptrs)
+        return dict(samples=int(ns.value), sites=int(n.value), max_lag=ml,
+                    row_names=buf.value.decode().split("\n") if R else [], n11=arrs[0], left1=arrs[1], right1=arrs[2])
+    finally:
+        L_.epvh_spatial_correlation_free(h)
 
 
 # ---- change patterns (what happened across the branches of the tree at one site)

@@ -636,6 +636,45 @@ class ShardedSampler:
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
+    # ---- spatial correlations: every rank counts the part of its owned columns
+    def enable_spatial_correlation(self, max_lag, max_samples):
+        self.dev.enable_spatial_correlation(max_lag, max_samples)
+
+    def reset_spatial_correlation(self):
+        self.dev.reset_spatial_correlation()
+
+    def accumulate_spatial_correlation(self):
+        self.dev.accumulate_spatial_correlation()
+
+    def spatial_correlation_samples(self):
+        return self.dev.spatial_correlation_samples()
+
+    def spatial_correlation_layout(self):
+        """(rows R, max_lag, first local site, sites, sites per block of the count kernel) of this rank's engine"""
+        return self.dev.spatial_correlation_layout()
+
+    def spatial_correlation_part(self):
+        """-> (samples, sites, n11, edges): the part of the whole genome, identical on every rank: the sample counts
+        are compared first (a part's size depends on them), then the ranks' parts are all-gathered and merged in
+        genome order"""
+        ns, cnt, n11, edges = self.dev.spatial_correlation_part()
+        if self.comm.world > 1:
+            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
+            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
+                raise RuntimeError("the ranks hold different numbers of spatial-correlation samples")
+            mine = np.concatenate([np.array([cnt], np.uint64), n11.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
+            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
+            na = n11.size
+            cnt, n11, edges = host.corr_parts_merge(
+                [(int(w[0]), w[1:1 + na].reshape(n11.shape), w[1 + na:].reshape(edges.shape)) for w in allw])
+        return ns, cnt, n11, edges
+
+    def spatial_correlation(self):
+        """-> (samples, n11, left1, right1), each [R, L + 1], of the whole genome, closed; every rank merges and
+        closes"""
+        ns, cnt, n11, edges = self.spatial_correlation_part()
+        return (ns,) + host.corr_part_close(cnt, n11, edges)
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -825,6 +864,9 @@ class LocalGroup:
         if self.halo_phases_left() < 3 * (burn_in + batch) and len(self.subs) > 1:
             raise RuntimeError("internal halo of %d columns is too narrow for %d sweeps without a "
                                "reset()" % (self.H_INT, burn_in + batch))
+        if getattr(self, "_corr_lag", 0):
+            # a shard that owns fewer than max_lag sites refuses here, before any shard's first sweep
+            self._each(lambda j, s: s.spatial_correlation_layout())
         res = self._each(lambda j, s: s.run_mcmc_counts(burn_in, batch, seed, sweep_base))
         for s in self.subs:
             self.capacity_events += s.capacity_events
@@ -1123,6 +1165,41 @@ class LocalGroup:
         """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]) over the group's owned sites, closed"""
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
+
+    # ---- spatial correlations: every shard counts the part of the sites it owns
+    def enable_spatial_correlation(self, max_lag, max_samples):
+        self._corr_lag = int(max_lag)
+        self._each(lambda j, s: s.enable_spatial_correlation(max_lag, max_samples))
+
+    def reset_spatial_correlation(self):
+        self._each(lambda j, s: s.reset_spatial_correlation())
+
+    def accumulate_spatial_correlation(self):
+        if len(self.subs) > 1 and not self.halo_mode:
+            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
+            raise RuntimeError("reset() the group before taking a spatial-correlation sample")
+        self._each(lambda j, s: s.accumulate_spatial_correlation())
+
+    def spatial_correlation_samples(self):
+        return self.subs[0].spatial_correlation_samples()
+
+    def spatial_correlation_layout(self):
+        """(rows R, max_lag, first local site of the first shard, sites over all shards, sites per block)"""
+        lay = self._each(lambda j, s: s.spatial_correlation_layout())
+        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+
+    def spatial_correlation_part(self):
+        """-> (samples, sites, n11, edges): the shards' parts merged in genome order, unclosed"""
+        parts = self._each(lambda j, s: s.spatial_correlation_part())
+        ns = parts[0][0]
+        if any(p[0] != ns for p in parts):
+            raise RuntimeError("the shards of the group hold different numbers of spatial-correlation samples")
+        return (ns,) + host.corr_parts_merge([p[1:] for p in parts])
+
+    def spatial_correlation(self):
+        """-> (samples, n11, left1, right1), each [R, L + 1], over the group's owned sites, closed"""
+        ns, cnt, n11, edges = self.spatial_correlation_part()
+        return (ns,) + host.corr_part_close(cnt, n11, edges)
 
     # ---- epoch statistics: every shard adds the triples centred at its owned sites
     def enable_epoch_stats(self, P):

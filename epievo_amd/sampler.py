@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "epv_get_change_pattern_windows",
     "epv_set_domain_turnover", "epv_reset_domain_turnover", "epv_accumulate_domain_turnover",
     "epv_domain_turnover_samples", "epv_domain_turnover_layout", "epv_get_domain_turnover",
+    "epv_set_spatial_correlation", "epv_reset_spatial_correlation", "epv_accumulate_spatial_correlation",
+    "epv_spatial_correlation_samples", "epv_spatial_correlation_layout", "epv_get_spatial_correlation",
 ]
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
@@ -206,6 +208,12 @@ def lib():
         L.epv_domain_turnover_samples.argtypes = [vp, u64p]
         L.epv_domain_turnover_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
         L.epv_get_domain_turnover.argtypes = [vp, u64p, u64p, u64p]
+        L.epv_set_spatial_correlation.argtypes = [vp, C.c_uint32, C.c_uint64]
+        L.epv_reset_spatial_correlation.argtypes = [vp]
+        L.epv_accumulate_spatial_correlation.argtypes = [vp]
+        L.epv_spatial_correlation_samples.argtypes = [vp, u64p]
+        L.epv_spatial_correlation_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
+        L.epv_get_spatial_correlation.argtypes = [vp, u64p, u64p]
         L.epv_set_change_patterns.argtypes = [vp, C.c_int]
         L.epv_reset_change_patterns.argtypes = [vp]
         L.epv_accumulate_change_patterns.argtypes = [vp]
@@ -964,6 +972,50 @@ class DeviceSampler:
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
+    # ---- spatial correlations (epv_set_spatial_correlation)
+    def enable_spatial_correlation(self, max_lag, max_samples):
+        """count, per node state row and branch change row, the site pairs (p, p + d) that are both 1 for every lag
+        d = 0 .. max_lag (at most 1024) after every batch sweep of run_mcmc, for at most max_samples samples
+        (max_lag = 0: off)"""
+        self._ck(self.L.epv_set_spatial_correlation(self.h, int(max_lag), int(max_samples)))
+
+    def reset_spatial_correlation(self):
+        self._ck(self.L.epv_reset_spatial_correlation(self.h))
+
+    def accumulate_spatial_correlation(self):
+        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
+        self._ck(self.L.epv_accumulate_spatial_correlation(self.h))
+
+    def spatial_correlation_samples(self):
+        v = C.c_uint64(0)
+        self._ck(self.L.epv_spatial_correlation_samples(self.h, C.byref(v)))
+        return int(v.value)
+
+    def spatial_correlation_layout(self):
+        """(rows R = N + B, max_lag, first local site, number of sites, sites per block of the count kernel); zeros
+        when off"""
+        nr, ml, a, k, cs = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_spatial_correlation_layout(self.h, C.byref(nr), C.byref(ml), C.byref(a), C.byref(k),
+                                                       C.byref(cs)))
+        return int(nr.value), int(ml.value), int(a.value), int(k.value), int(cs.value)
+
+    def spatial_correlation_part(self):
+        """-> (samples, sites, n11 [R, L + 1], edges [samples, R, 2, ceil(L / 64)]), uint64: what this context's
+        stretch of sites contributes, unclosed (host.corr_parts_merge, host.corr_part_close)"""
+        ns = self.spatial_correlation_samples()
+        R, L, _, cnt, _ = self.spatial_correlation_layout()
+        LW = (L + 63) // 64
+        n11 = np.zeros((max(R, 1), L + 1), np.uint64)
+        edges = np.zeros(max(ns * R * 2 * LW, 1), np.uint64)
+        self._ck(self.L.epv_get_spatial_correlation(self.h, _p(n11, C.c_uint64), _p(edges, C.c_uint64)))
+        return ns, cnt, n11[:R], edges[:ns * R * 2 * LW].reshape(ns, R, 2, LW)
+
+    def spatial_correlation(self):
+        """-> (samples, n11, left1, right1), each [R, L + 1]: the closed result over this context's sites; rows 0 ..
+        N - 1 the node states, rows N .. N + B - 1 the net changes of the branches (host.spatial_correlation_summary)"""
+        ns, cnt, n11, edges = self.spatial_correlation_part()
+        return (ns,) + host.corr_part_close(cnt, n11, edges)
+
     # ---- epoch statistics (epv_set_epoch_stats)
     def enable_epoch_stats(self, P):
         """add J and D per branch and epoch (P epochs per branch) after every batch sweep of run_mcmc (0 = off)"""
@@ -1203,6 +1255,28 @@ class SingleSiteSampler:
 
     def domain_turnover(self):
         return self.dev.domain_turnover()
+
+    # spatial correlations (DeviceSampler.enable_spatial_correlation)
+    def enable_spatial_correlation(self, max_lag, max_samples):
+        self.dev.enable_spatial_correlation(max_lag, max_samples)
+
+    def reset_spatial_correlation(self):
+        self.dev.reset_spatial_correlation()
+
+    def accumulate_spatial_correlation(self):
+        self.dev.accumulate_spatial_correlation()
+
+    def spatial_correlation_samples(self):
+        return self.dev.spatial_correlation_samples()
+
+    def spatial_correlation_layout(self):
+        return self.dev.spatial_correlation_layout()
+
+    def spatial_correlation_part(self):
+        return self.dev.spatial_correlation_part()
+
+    def spatial_correlation(self):
+        return self.dev.spatial_correlation()
 
     # change patterns (DeviceSampler.enable_change_patterns)
     def enable_change_patterns(self, on=True):

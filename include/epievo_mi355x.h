@@ -712,6 +712,47 @@ int epv_domain_turnover_layout(epv_ctx *ctx, uint32_t *n_rows, uint32_t *n_bins,
                                uint64_t *chunk_sites);
 int epv_get_domain_turnover(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
 
+/* ---- spatial correlations (new): two-point counts of node states and branch changes along the genome.  For a
+ * 0/1 row X over a stretch of sites and a lag d, n11[d] is the number of site pairs (p, p + d) inside the stretch
+ * with X[p] = X[p + d] = 1: whether sites 5, 50 or 500 apart still agree more often than chance, and whether the
+ * changes on a branch arrive in clusters.  Neither the domain layers (a run ends at the first disagreement) nor
+ * the per-site layers can give it.
+ * One sample reads, per branch b (child node v = b + 1) and site, the init state a and the jump count k of the
+ * resident path (no jump time).  Rows: R = N + B.  Row v < N is the state of node v as the domain size spectra
+ * define it (x_0 = a of the branch of the root's lowest-numbered child, x_v = a XOR (k & 1)); row N + b is the net
+ * change on branch b, k & 1.
+ * With L = max_lag, 1 <= L <= min(1024, cnt), a context keeps a PART over its cnt sites (those of the path
+ * average):
+ *   n11[R][L + 1] uint64   summed over the samples; n11[r][0] counts the ones of the row
+ *   edge[sample][R][2][LW] uint64, LW = ceil(L / 64)   record 0 (head): bit j = X_r[j]; record 1 (tail): bit j =
+ *     X_r[cnt - L + j]; j < L, the bits beyond L in the last word are zero
+ * Merge of a part A left of a part B (same samples, L and R, both of at least L sites): n11 = A.n11 + B.n11 + the
+ * pairs that cross, cross[r][d] = #{k < d : tailA[L - d + k] = headB[k] = 1} summed over the samples; the head is
+ * A's, the tail B's.  Close, for a part over the whole genome of n sites: left1[r][d] = n11[r][0] - the ones among
+ * the last d sites (the ones at the left site of a pair), right1[r][d] = n11[r][0] - the ones among the first d
+ * sites, pairs[d] = samples (n - d); the 2 x 2 table of (X[p], X[p + d]) follows (epvh_corr_parts_merge,
+ * epvh_corr_part_close in libepv_host.so).
+ * A context that counts fewer than max_lag sites is EPV_ERR_ARG (the message gives both figures), when the layer is
+ * set or, for a range that changed since, before the first sweep of a run: a pair never spans three parts.
+ * Samples, sites and lifecycle are the domain turnover's; a changed site range, number of nodes or first child of
+ * the root lays the part out again before the first sample and is EPV_ERR_STATE after it.  Off by default:
+ * nothing allocated, nothing launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_spatial_correlation: max_lag >= 1 (at most 1024) and max_samples >= 1 (at most 2^21) allocate
+ *   8 R (L + 1) bytes of counts, 8 R ceil(cnt / 64) bytes of scratch and 16 R LW max_samples bytes of edge records
+ *   (checked against the free device memory first; the message gives the figure) and zero them; max_lag = 0 frees
+ *   everything.  A sample beyond max_samples is EPV_ERR_STATE, and so is a run whose batch would pass it, refused
+ *   before its first sweep.  At most 2^32 - 1 sites per context.
+ * epv_spatial_correlation_layout: rows R, max_lag, the local sites first .. first+count-1 and the sites one block
+ *   of the count kernel covers (zeros when off).
+ * epv_get_spatial_correlation: the context's part, unclosed; edges holds [samples][R][2][LW]. */
+int epv_set_spatial_correlation(epv_ctx *ctx, uint32_t max_lag, uint64_t max_samples);
+int epv_reset_spatial_correlation(epv_ctx *ctx);
+int epv_accumulate_spatial_correlation(epv_ctx *ctx);
+int epv_spatial_correlation_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_spatial_correlation_layout(epv_ctx *ctx, uint32_t *n_rows, uint32_t *max_lag, uint64_t *first, uint64_t *count,
+                                   uint64_t *chunk_sites);
+int epv_get_spatial_correlation(epv_ctx *ctx, uint64_t *n11, uint64_t *edges);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

@@ -138,6 +138,20 @@ int epvd_turnover_part_sizes(epvd_sampler *s, uint32_t *n_rows, uint64_t *n_samp
 int epvd_download_turnover_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
 int epvd_download_turnover(epvd_sampler *s, uint32_t n_rows, uint64_t *hist, uint64_t *len_sum, uint64_t *n_samples);
 
+/* spatial correlations (epv_set_spatial_correlation on every context; max_lag = 0 is off; kept across epvd_reset,
+ * which starts them from zero).  The part of this process: the parts of its slots and contexts merged in genome
+ * order, unclosed -- sizes first (rows R = N + B, max_lag L, samples S and the sites the part covers), then the copy
+ * of n11[R][L + 1] and edges[S][R][2][ceil(L / 64)].  epvd_download_corr: that part closed, into n11, left1 and
+ * right1 [n_rows][max_lag + 1]; one slot per process: an error that names the part and the merge function, because
+ * one process's stretch is not the genome */
+int epvd_set_corr(epvd_sampler *s, uint32_t max_lag, uint64_t max_samples);
+int epvd_reset_corr(epvd_sampler *s);
+int epvd_accumulate_corr(epvd_sampler *s);
+int epvd_corr_part_sizes(epvd_sampler *s, uint32_t *n_rows, uint32_t *max_lag, uint64_t *n_samples, uint64_t *n_sites);
+int epvd_download_corr_part(epvd_sampler *s, uint64_t *n11, uint64_t *edges);
+int epvd_download_corr(epvd_sampler *s, uint32_t n_rows, uint32_t max_lag, uint64_t *n11, uint64_t *left1,
+                       uint64_t *right1, uint64_t *n_samples);
+
 /* change patterns (epv_set_change_patterns on every context; kept across epvd_reset, which starts the rows from
  * zero), and the rows over the sites of this process in genome order: sizes first (n_rows = 12 + 2 (n_nodes-1) +
  * internal non-root nodes, n_values = n_rows * sites), then the copy of rows[r * sites + site].
