@@ -1666,10 +1666,11 @@ struct PhasePlan {
   bool meta_cache;       // (accept and fused kernels) the LDS meta cache
   bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
   bool evidence;         // a leaf cell carries evidence: V1 takes the template that reads the table
+  uint32_t lanes_log2;   // fused: log2 of the sites per wave (2 .. 6)
   uint32_t word() const {
     return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
            p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16 |
-           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18;
+           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18 | lanes_log2 << 20;
   }
 };
 PhasePlan phase_plan(const epv_ctx *c) {
@@ -1691,6 +1692,7 @@ PhasePlan phase_plan(const epv_ctx *c) {
     P.small_nn = c->knobs.small_tree && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
     P.jumps = EPV_PLAN_JUMPS_FUSED;
     P.accept = EPV_PLAN_ACCEPT_FUSED;
+    for (uint32_t l = c->fused_lanes; l > 1u; l >>= 1) ++P.lanes_log2;
     return P;
   }
   if (p3) {

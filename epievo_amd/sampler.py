@@ -323,7 +323,8 @@ class DeviceSampler:
         return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
                     small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
                     jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
-                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1))
+                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1),
+                    fused_lanes=(1 << (w >> 20 & 7)) if (w & 3) == 3 else 0)
 
     def philox_kat(self, seed, counters):
         """the device's Philox blocks (epv_philox_kat): counters[i] = (site, sweep, branch, segment, trial,

@@ -147,7 +147,9 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *   bit  17    V1: the template that marginalises unobserved leaf cells (epv_set_unobserved holds a cell;
  *              it forces V1 like bit 3 does)
  *   bit  18    V1: the template that reads the table of leaf evidence (epv_set_leaf_evidence holds a cell;
- *              it forces V1 too, and the mask of bit 17 rides along for the cells without evidence) */
+ *              it forces V1 too, and the mask of bit 17 rides along for the cells without evidence)
+ *   bits 20-22 fused: log2 of the sites per wave (2 .. 6 for 4, 8, 16, 32 or 64 sites: EPV_FUSED_LANES, or by
+ *              launch size -- with (n + 2) / 3 + 1 lanes 64 above 65536, 32 above 32768, else 16) */
 enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
 enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };

@@ -23,8 +23,14 @@ more than 64 segments and the fused generic body are reached by inputs that are 
 homogeneous inputs is kept and asserts the plan it takes.
 
 The fused phase's two exits.  The grouped search, which finishes a branch whose sole dirty segment it has settled,
-takes a wave's segment list only when it has at most 32 entries; a wave of 16 or 64 dense sites lists hundreds.
+takes a wave's segment list only when it has at most 32 entries; a wave of 16, 32 or 64 dense sites lists hundreds.
 The rows that assert 0 < search_finished < coop_tasks therefore run four sites a wave (EPV_FUSED_LANES=4).
+
+Sites per wave.  These inputs have 400 or 600 sites, where a context chooses 16 sites per wave by itself (plan_p2:
+32 and 64 only above 98301 and 196605 sites), so the fused rows without EPV_FUSED_LANES run 16.  The rows named
+-lanes32 and -lanes64 set the knob: four times the demand on the record pool, several rounds of the proposal loop
+per wave, private lists four times as long, up to 192 (site, triple) tasks in the acceptance.  Every fused row
+asserts its fused_lanes (test_fused_lanes.py runs the widths on sparse inputs at the launch tails).
 
 Observed on the MI355X (acceptance, K max; search_finished / coop_tasks at 4 and at 16 sites a wave):
   pair x 4 0.753, 18 (47 and 1 / 2983)    cherry x 12 0.720, 16       star3 x 15 0.641, 22
@@ -73,7 +79,7 @@ def check_plan(d):
 
 def result(plan, cap, nacc, sweeps, cnt):
     print("result", json.dumps(dict(workload=name, cap=cap, W=dc.words(cap), propose=plan["propose"], gpool=plan["gpool"],
-          small_nn=plan["small_nn"], jumps=plan["jumps"], accept=plan["accept"], acceptance=round(nacc / float(sweeps * (fp.n_sites - 2)), 3),
+          small_nn=plan["small_nn"], fused_lanes=plan["fused_lanes"], jumps=plan["jumps"], accept=plan["accept"], acceptance=round(nacc / float(sweeps * (fp.n_sites - 2)), 3),
           kmax=dens["kmax"], over64=round(dens["over64"], 3), overflow=cnt["overflow"], search_finished=cnt["search_finished"],
           coop_tasks=cnt["coop_tasks"])), flush=True)
 '''
@@ -207,45 +213,59 @@ FR, REF, SR = {"forward_rejection": True}, {"reference_proposal_ratio": True}, {
 FRREF = {"forward_rejection": True, "reference_proposal_ratio": True}
 
 
-def fused(nn):
-    return dict(propose="fused", small_nn=nn, jumps="fused", accept="fused", gpool=False, listed=False)
+def fused(nn, lanes=16):
+    return dict(propose="fused", small_nn=nn, jumps="fused", accept="fused", gpool=False, listed=False,
+                fused_lanes=lanes)
 
 
 def v2(jumps, accept="accept_cache"):
-    return dict(propose="V2", gpool=False, jumps=jumps, accept=accept, listed=True, small_nn=0, p3_words=0)
+    return dict(propose="V2", gpool=False, jumps=jumps, accept=accept, listed=True, small_nn=0, p3_words=0,
+                fused_lanes=0)
 
 
 def v3(words, jumps="jumps_all", accept="accept3", slab=False):
     return dict(propose="V3", p3_words=words, p3_slab_pool=slab, jumps=jumps, accept=accept, listed=True, gpool=False,
-                small_nn=0)
+                small_nn=0, fused_lanes=0)
 
 
 def v1(gpool, refq, jumps, accept="accept_cache"):
-    return dict(propose="V1", gpool=gpool, refq=refq, jumps=jumps, accept=accept, listed=False, p3_words=0)
+    return dict(propose="V1", gpool=gpool, refq=refq, jumps=jumps, accept=accept, listed=False, p3_words=0,
+                fused_lanes=0)
 
 
 LANES4 = dict(FUSED_LDS, EPV_FUSED_LANES="4")
+LANES32, LANES64 = dict(FUSED_LDS, EPV_FUSED_LANES="32"), dict(FUSED_LDS, EPV_FUSED_LANES="64")
 
 # (id, workload, capacity, env, options, expected plan fields, both fused exits ran).  The plans are the observed
 # ones (MI355X); a comment says where a row was written for another.
 PARITY = [
-    # ---- the fused phase at C = 31, every branch heavy: the small-tree bodies NN = 2 .. 5.  With 64 or 16 sites
+    # ---- the fused phase at C = 31, every branch heavy: the small-tree bodies NN = 2 .. 5.  With 16 sites and more
     # a wave its segment list is hundreds long and the wave-wide search and the assembly do everything; the
     # grouped search, whose own finish is the other exit, takes lists of at most 32 segments, so the rows that
-    # assert both exits run four sites a wave
-    ("fused-pair4", "weak-pair4", "roomy", LANES4, {}, fused(2), True),
-    ("fused-tree40", "weak-tree40", "roomy", LANES4, {}, fused(5), True),
+    # assert both exits run four sites a wave.  The -wide rows run the width the context chooses at 600 sites, 16
+    # (wide next to the four of the rows above them; the 64 of a large genome are the -lanes64 rows)
+    ("fused-pair4", "weak-pair4", "roomy", LANES4, {}, fused(2, 4), True),
+    ("fused-tree40", "weak-tree40", "roomy", LANES4, {}, fused(5, 4), True),
     ("fused-pair4-wide", "weak-pair4", "roomy", FUSED_LDS, {}, fused(2), False),
     ("fused-cherry12", "weak-cherry12", "roomy", FUSED_LDS, {}, fused(3), False),
     ("fused-star3x15", "weak-star3x15", "roomy", FUSED_LDS, {}, fused(4), False),
     ("fused-tree40-wide", "weak-tree40", "roomy", FUSED_LDS, {}, fused(5), False),
     ("fused-tree40-overflow", "weak-tree40", "tight", FUSED_LDS, {}, fused(5), False),
-    ("fused-tree40-overflow-lanes4", "weak-tree40", "tight", LANES4, {}, fused(5), False),
+    ("fused-tree40-overflow-lanes4", "weak-tree40", "tight", LANES4, {}, fused(5, 4), False),
+    # ... and at 64 and 32 sites a wave, the widths of genomes above 196605 and 98301 sites
+    ("fused-pair4-lanes64", "weak-pair4", "roomy", LANES64, {}, fused(2, 64), False),
+    ("fused-cherry12-lanes64", "weak-cherry12", "roomy", LANES64, {}, fused(3, 64), False),
+    ("fused-star3x15-lanes64", "weak-star3x15", "roomy", LANES64, {}, fused(4, 64), False),
+    ("fused-tree40-lanes64", "weak-tree40", "roomy", LANES64, {}, fused(5, 64), False),
+    ("fused-tree40-overflow-lanes64", "weak-tree40", "tight", LANES64, {}, fused(5, 64), False),
+    ("fused-tree40-lanes32", "weak-tree40", "roomy", LANES32, {}, fused(5, 32), False),
     # the generic body: star5 x 20 and cat6 x 25 are too dense for the fused phase under any knob (large-tree
     # kernel); star5 x 20 thinned outside a window takes it
     ("fused-star5x20", "weak-star5x20", "roomy", FUSED_LDS, {}, v3(1, accept="accept_cache"), False),
     ("fused-cat6x25", "weak-cat6x25", "roomy", FUSED_LDS, {}, v3(1), False),
     ("fused-mixed-star5x20", "mixed-star5x20", "roomy", FUSED_LDS, {}, fused(0), False),
+    ("fused-mixed-star5x20-lanes64", "mixed-star5x20", "roomy", LANES64, {}, fused(0, 64), False),
+    ("fused-mixed-star5x20-lanes32", "mixed-star5x20", "roomy", LANES32, {}, fused(0, 32), False),
     ("fused-mixed-tree40", "mixed-tree40", "roomy", FUSED_LDS, {}, fused(5), False),
     # the same inputs without a knob: the plan the context chooses for them
     ("default-pair4", "weak-pair4", "roomy", {}, {}, v3(1, accept="accept_cache"), False),
@@ -271,6 +291,7 @@ PARITY = [
     # which the thinned input reaches (C = 25, K max 44)
     ("fused-tree150-overflow", "weak-tree150", "tight", FUSED_LDS, {}, v3(1, accept="accept_cache"), False),
     ("fused-mixed-tree150-overflow", "mixed-tree150", "tight", FUSED_LDS, {}, fused(5), False),
+    ("fused-mixed-tree150-overflow-lanes64", "mixed-tree150", "tight", LANES64, {}, fused(5, 64), False),
     ("w3-multi30", "weak-multi30", "roomy", {}, {}, v1(True, False, "jumps_all"), False),
     # ---- more than 64 segments on a branch.  The homogeneous inputs go to the large-tree kernel, which keeps such a
     # branch's proposal states out of the two-word hand-over (epv_propose3.h, K <= 64)

@@ -22,6 +22,10 @@ Coverage (variant x options -> rows):
                                              frref-bal16, sr-bal16; default: n129, multi-no-v3, unary-q64
   V1's LEAF template axis (mask, evidence)   test_leaf_matrix.py: all eight (pool, ratio, leaf mode)
                                              instantiations against rung B with its own leaf vector
+  fused, 32 and 64 sites per wave            forward rejection: fr-pair-lanes64, fr-tree-lanes64, fr-star5-lanes64; every
+  (every other fused row here runs 16,       other option, the launch tails, update ranges, the halo mode and the
+  the width a context chooses below          width a context chooses by itself: test_fused_lanes.py; dense histories
+  98302 sites)                               at 32 and 64: the -lanes rows of test_dense_histories_gpu.py
   dense histories (tens of jumps per path,   test_dense_histories_gpu.py: every row here draws its histories from
   where the rows above have two or three)    test.param on branches of 0.02 - 0.8, which the reference model
                                              forces (it accepts nothing on dense input); the rows there use two
@@ -172,12 +176,14 @@ print("ok", json.dumps(plan))
 '''
 
 _SEP = {"EPV_FUSED_PHASE": "0"}              # the separate kernels (small launches take the fused phase)
+_L64 = {"EPV_FUSED_PHASE": "1", "EPV_FUSED_LANES": "64"}     # the sites per wave of a genome above 196605 sites
 FR, REF, SR = {"forward_rejection": True}, {"reference_proposal_ratio": True}, {"sample_root": True}
 FRREF = {"forward_rejection": True, "reference_proposal_ratio": True}
 
 
-def fused(nn):
-    return dict(propose="fused", small_nn=nn, jumps="fused", accept="fused", gpool=False, listed=False)
+def fused(nn, lanes=16):
+    return dict(propose="fused", small_nn=nn, jumps="fused", accept="fused", gpool=False, listed=False,
+                fused_lanes=lanes)
 
 
 def v2(gpool, jumps, accept="accept_cache"):
@@ -201,6 +207,9 @@ ROWS = [
     ("fr-star3", "star3", 4, 1500, {}, FR, fused(4)),
     ("fr-tree", "tree", 5, 1500, {}, FR, fused(5)),
     ("fr-star5", "star5", 6, 1500, {}, FR, fused(0)),
+    ("fr-pair-lanes64", "pair", 2, 1500, _L64, FR, fused(2, 64)),
+    ("fr-tree-lanes64", "tree", 5, 1500, _L64, FR, fused(5, 64)),
+    ("fr-star5-lanes64", "star5", 6, 1500, _L64, FR, fused(0, 64)),
     ("fr-cat6", "cat6", 11, 1500, {"EPV_FUSED_PHASE": "1", "EPV_FORCE_LDS_POOL": "1"}, FR, fused(0)),
     ("fr-v2-lds", "tree", 5, 2000, dict(_SEP, EPV_SEG_JUMPS="0"), FR, v2(False, "jumps")),
     ("fr-v2-lds-seg", "tree", 5, 2000, dict(_SEP, EPV_SEG_JUMPS="1"), FR, v2(False, "segments")),
@@ -243,21 +252,26 @@ def test_kernel_variant_matches_rung_b(tree, nodes, n, env, opts, expect):
     code = _CODE % dict(root=_ROOT, tests=_TESTS, spec=spec)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True,
                        timeout=900)
+    print(r.stdout[-2000:])         # the plan that ran, fused_lanes included
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-3000:]
 
 
 def test_rows_cover_the_matrix():
-    """no GPU: the table names every variant under forward rejection and the trees it claims"""
+    """no GPU: the table names every variant under forward rejection -- the fused bodies by their sites per wave --
+    and the trees it claims"""
     seen = set((r[6]["propose"], r[6].get("small_nn"), r[6].get("gpool"), r[6].get("jumps"), r[6].get("p3_words"),
-                r[6].get("p3_slab_pool")) for r in ROWS if r[5] == FR)
-    for key in [("fused", 2, False, "fused", None, None), ("fused", 3, False, "fused", None, None),
-                ("fused", 4, False, "fused", None, None), ("fused", 5, False, "fused", None, None),
-                ("fused", 0, False, "fused", None, None), ("V2", 0, False, "jumps", 0, None),
-                ("V2", 0, False, "segments", 0, None),
-                ("V3", None, False, "jumps", 1, False), ("V3", None, False, "jumps", 2, False),
-                ("V3", None, False, "jumps", 1, True), ("V1", None, False, "jumps", 0, None),
-                ("V1", None, True, "jumps", 0, None)]:
+                r[6].get("p3_slab_pool"), r[6].get("fused_lanes")) for r in ROWS if r[5] == FR)
+    for key in [("fused", 2, False, "fused", None, None, 16), ("fused", 3, False, "fused", None, None, 16),
+                ("fused", 4, False, "fused", None, None, 16), ("fused", 5, False, "fused", None, None, 16),
+                ("fused", 0, False, "fused", None, None, 16), ("fused", 2, False, "fused", None, None, 64),
+                ("fused", 5, False, "fused", None, None, 64), ("fused", 0, False, "fused", None, None, 64),
+                ("V2", 0, False, "jumps", 0, None, None),
+                ("V2", 0, False, "segments", 0, None, None),
+                ("V3", None, False, "jumps", 1, False, None), ("V3", None, False, "jumps", 2, False, None),
+                ("V3", None, False, "jumps", 1, True, None), ("V1", None, False, "jumps", 0, None, None),
+                ("V1", None, True, "jumps", 0, None, None)]:
         assert key in seen, key
+    assert all(r[6]["fused_lanes"] == int(r[4].get("EPV_FUSED_LANES", 16)) for r in ROWS if r[6]["propose"] == "fused")
     assert len(set(r[0] for r in ROWS)) == len(ROWS)
     for r in ROWS:
         t = make_tree(r[1])
