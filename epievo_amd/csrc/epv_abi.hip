@@ -1759,6 +1759,9 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     F.meta_cache = meta_cache;
     F.lanes = c->fused_lanes;
     F.grouped_rounds = 4u;     // rounds of the grouped search of a short segment list
+    F.topo = 0u;               // small-tree body: bit node = a leaf, bits 8 + 3 node .. = the parent
+    for (uint32_t node = 1; node < P.small_nn; ++node)
+      F.topo |= (c->subtree[node] == 1u ? 1u << node : 0u) | (c->parent[node] << (8u + 3u * node));
     const auto kf = fused_kernel(P.small_nn);
     hipLaunchKernelGGL(kf, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,

@@ -159,6 +159,7 @@ struct EpvFused {
   uint32_t meta_cache;         // accept stage: meta words of the five columns in LDS (B <= 8)
   uint32_t lanes;              // sites per wave
   uint32_t grouped_rounds;     // rounds of the grouped search of short segment lists (0 = off)
+  uint32_t topo;               // small-tree body: the topology word (bit node: a leaf; bits 8 + 3 node ..: the parent)
 };
 
 // NN > 0 (fused phase only): the node count as a compile-time constant, for trees of at most
@@ -228,19 +229,53 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   const uint32_t gsite = (uint32_t)(S.g0 + site);
   const uint32_t gsite_lane0 = gsite - 3u * (uint32_t)lane;
 
-  // the head of the kernel's dependent chain (sel -> meta -> jumps) starts before the constants are
-  // staged, so that the two round trips overlap
+  // the head of the kernel's dependent chain (sel -> meta -> jumps) leaves together with the loads of
+  // the staging, so that the round trips overlap (fused phase: profiles/head_batch_static.txt shows
+  // what the compiler makes of it; the separate kernels keep the plain form)
   uint32_t selL = 0, selM = 0, selR = 0;
-  if (valid) { selL = S.sel[site - 1]; selM = S.sel[site]; selR = S.sel[site + 1]; }
   // FUSED: the buffers of the columns two sites away, for the acceptance stage's outer triples (they
   // belong to other colours and do not change in this phase), in the same batch of loads
   uint32_t selLL = 0, selRR = 0;
-  if (FUSED && valid) {
-    if (S.g0 + site > 1u) selLL = S.sel[site - 2];
-    if (S.g0 + site < S.n_global - 2u) selRR = S.sel[site + 2];
+  const bool hasLL = FUSED && valid && S.g0 + site > 1u, hasRR = FUSED && valid && S.g0 + site < S.n_global - 2u;
+  if constexpr (FUSED) {
+    // ONE batch of loads, one wait: everything whose address is known at entry.  A load under a
+    // condition compiles to a branch and a wait of its own, so every load here is unconditional,
+    // its address clamped to one that is always in range (`first` is a site of this launch), and
+    // the condition selects the value afterwards.  This lane's share of the matrix table and of the
+    // constants waits in registers; the LDS writes follow the batch.
+    constexpr int TK = SMALL ? (NBA * 4 * (int)EPV_SEGTAB_DBL + 63) / 64 : 6;   // table doubles per lane (generic: B <= 16 at 64 lanes)
+    const uint8_t *psel = S.sel + (valid ? site : first);
+    const uint32_t rL = psel[-1], rM = psel[0], rR = psel[1];
+    const uint32_t rLL = *(hasLL ? psel - 2 : psel), rRR = *(hasRR ? psel + 2 : psel);
+    double r_tab[TK];
+#pragma unroll
+    for (int k = 0; k < TK; ++k) {
+      const uint32_t i = threadIdx.x + (uint32_t)k * blockDim.x;
+      r_tab[k] = segtab[i < tab_dbl ? i : 0u];
+    }
+    const uint32_t ci = threadIdx.x < 20u + NNODE ? threadIdx.x : 0u;
+    const double *cbase = ci < 20u ? reinterpret_cast<const double *>(S.model) : S.blen;
+    const double r_c = cbase[ci < 20u ? ci : ci - 20u];
+    // (the writes are unconditional too -- under a condition the compiler sinks the load into the
+    // branch and waits there: a lane beyond the end writes entry 0 with entry 0's value once more)
+#pragma unroll
+    for (int k = 0; k < TK; ++k) {
+      const uint32_t i = threadIdx.x + (uint32_t)k * blockDim.x;
+      s_tab[i < tab_dbl ? i : 0u] = r_tab[k];
+    }
+    s_const[ci] = r_c;
+    if constexpr (!SMALL) {     // (a tree beyond the registers' share: the rest as stage_constants does it)
+      for (uint32_t i = threadIdx.x + (uint32_t)TK * blockDim.x; i < tab_dbl; i += blockDim.x) s_tab[i] = segtab[i];
+      for (uint32_t i = threadIdx.x + blockDim.x; i < 20u + NNODE; i += blockDim.x) s_const[i] = S.blen[i - 20u];
+    }
+    __syncthreads();
+    selL = valid ? rL : 0u; selM = valid ? rM : 0u; selR = valid ? rR : 0u;
+    selLL = hasLL ? rLL : 0u; selRR = hasRR ? rRR : 0u;
+  } else {
+    if (valid) { selL = S.sel[site - 1]; selM = S.sel[site]; selR = S.sel[site + 1]; }
+    for (uint32_t i = threadIdx.x; i < tab_dbl; i += blockDim.x) s_tab[i] = segtab[i];
+    stage_constants(S, s_const);
   }
-  for (uint32_t i = threadIdx.x; i < tab_dbl; i += blockDim.x) s_tab[i] = segtab[i];
-  stage_constants(S, s_const);
   const double *s_rates = s_const;
   const double *s_blen = s_const + 20;
 
@@ -261,24 +296,47 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
 #define EPV_RW_K(w) (((w) >> 16) & 0xffu)
 #define EPV_RW_TAB(w) ((w) >> 24)
   if constexpr (SMALL) {
-#pragma unroll
-    for (int node = 1; node < NN; ++node)
-      topo |= (S.subtree[node] == 1u ? 1u << node : 0u) | (S.parent[node] << (8 + 3 * node));
-    topo = __builtin_amdgcn_readfirstlane(topo);
+    topo = F.topo;     // (the host packs it: a kernel argument, no load)
 #pragma unroll
     for (int b = 0; b < NN - 1; ++b) r_w[b] = 1u << 16;
   }
+  // FUSED: the two outer columns no neighbour lane holds (s_edge) travel in the batch of the meta
+  // words: lane 0 fetches the column two sites to its left, the last valid lane the one two sites
+  // to its right (one lane may be both), zero where the genome ends.  No condition on loads or
+  // writes here either: every lane loads two words per branch and writes them, a lane without that
+  // outer column its own site's word once more, into the slot that word has anyway.
+  const unsigned long long vmask = __ballot(valid);
+  const int last_lane = vmask ? 63 - __clzll((long long)vmask) : 0;
+  const bool edgeL = lane == 0, edgeR = lane == last_lane;
+  const uint64_t ebaseL = edgeL && hasLL ? (selLL ? Bn : 0ull) + (site - 2) : mbaseM;
+  const uint64_t ebaseR = edgeR && hasRR ? (selRR ? Bn : 0ull) + (site + 2) : mbaseM;
+  // slot of branch b in s_meta: at + b * step (s_edge = s_meta + 3 B 64)
+  const uint32_t own_at = 2u * B * 64u + (uint32_t)lane;
+  const uint32_t eatL = edgeL ? 3u * B * 64u : own_at, estepL = edgeL ? 1u : 64u;
+  const uint32_t eatR = edgeR ? 3u * B * 64u + B : own_at, estepR = edgeR ? 1u : 64u;
+  const bool ezeroL = edgeL && !hasLL, ezeroR = edgeR && !hasRR;
   if (SMALL && valid) {
+    uint32_t mL[NBA], mR[NBA], mM[NBA], eL[NBA], eR[NBA];
 #pragma unroll
     for (int b = 0; b < NBA; ++b) {
-      const uint32_t mL = S.meta[mbaseL + (uint64_t)b * n];
-      const uint32_t mR = S.meta[mbaseR + (uint64_t)b * n];
-      const uint32_t mM = S.meta[mbaseM + (uint64_t)b * n];
-      s_meta[(0u * B + b) * 64u + lane] = (epv_meta_t)mL;
-      s_meta[(1u * B + b) * 64u + lane] = (epv_meta_t)mR;
-      s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM;
-      const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
-      r_w[b] = (uint32_t)(epv_meta_t)mM | (K << 16) | ((2u * (mL >> EPV_INIT_SHIFT) + (mR >> EPV_INIT_SHIFT)) << 24);
+      mL[b] = S.meta[mbaseL + (uint64_t)b * n];
+      mR[b] = S.meta[mbaseR + (uint64_t)b * n];
+      mM[b] = S.meta[mbaseM + (uint64_t)b * n];
+      eL[b] = S.meta[ebaseL + (uint64_t)b * n];
+      eR[b] = S.meta[ebaseR + (uint64_t)b * n];
+    }
+#pragma unroll
+    for (int b = 0; b < NBA; ++b) {
+      s_meta[eatL + (uint32_t)b * estepL] = ezeroL ? (epv_meta_t)0 : (epv_meta_t)eL[b];
+      s_meta[eatR + (uint32_t)b * estepR] = ezeroR ? (epv_meta_t)0 : (epv_meta_t)eR[b];
+    }
+#pragma unroll
+    for (int b = 0; b < NBA; ++b) {
+      s_meta[(0u * B + b) * 64u + lane] = (epv_meta_t)mL[b];
+      s_meta[(1u * B + b) * 64u + lane] = (epv_meta_t)mR[b];
+      s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM[b];
+      const uint32_t K = (mL[b] & EPV_NJ_MASK) + (mR[b] & EPV_NJ_MASK) + 1u;
+      r_w[b] = (uint32_t)(epv_meta_t)mM[b] | (K << 16) | ((2u * (mL[b] >> EPV_INIT_SHIFT) + (mR[b] >> EPV_INIT_SHIFT)) << 24);
       need_rec += K + (EPV_TOPO_LEAF(b + 1) ? 0u : 1u);
       if (K >= 2u) heavy += K;
     }
@@ -288,24 +346,18 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       const uint32_t mL = S.meta[mbaseL + (uint64_t)b * n];
       const uint32_t mR = S.meta[mbaseR + (uint64_t)b * n];
       const uint32_t mM = S.meta[mbaseM + (uint64_t)b * n];
+      if constexpr (FUSED) {
+        const uint32_t eL = S.meta[ebaseL + (uint64_t)b * n];
+        const uint32_t eR = S.meta[ebaseR + (uint64_t)b * n];
+        s_meta[eatL + b * estepL] = ezeroL ? (epv_meta_t)0 : (epv_meta_t)eL;
+        s_meta[eatR + b * estepR] = ezeroR ? (epv_meta_t)0 : (epv_meta_t)eR;
+      }
       s_meta[(0u * B + b) * 64u + lane] = (epv_meta_t)mL;
       s_meta[(1u * B + b) * 64u + lane] = (epv_meta_t)mR;
       s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM;
       const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
       need_rec += K + (S.subtree[b + 1u] != 1u ? 1u : 0u);
       if (K >= 2u) heavy += K;
-    }
-  }
-
-  // FUSED: the two outer columns no neighbour lane holds
-  const unsigned long long vmask = __ballot(valid);
-  const int last_lane = vmask ? 63 - __clzll((long long)vmask) : 0;
-  if (FUSED && valid && (lane == 0 || lane == last_lane)) {
-    const bool hasLL = S.g0 + site > 1u, hasRR = S.g0 + site < S.n_global - 2u;
-    // (S.B, not B: unrolled for a small tree, this two-lane loop alone cost the NN = 5 body 8 bytes of scratch)
-    for (uint32_t b = 0; b < S.B; ++b) {
-      if (lane == 0) s_edge[b] = hasLL ? S.meta[(selLL ? Bn : 0ull) + (uint64_t)b * n + (site - 2)] : (epv_meta_t)0;
-      if (lane == last_lane) s_edge[B + b] = hasRR ? S.meta[(selRR ? Bn : 0ull) + (uint64_t)b * n + (site + 2)] : (epv_meta_t)0;
     }
   }
   P2_MARK(0);
