@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _build
 from .host import FlatPaths
+from .summaries import _per_sample
 
 _lib = None
 vp, dp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -260,7 +261,7 @@ class CppSampler:
         self._ck(self.L.epvd_download_path_average(self.h, _p(out, C.c_uint32)))
         out = out[:nv.value].reshape(self.B, -1, P.value)
         ns = int(ns.value)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     def enable_branch_events(self, on=True):
         """posterior branch-event maps on every context (False = off); kept across reset()"""
@@ -274,7 +275,7 @@ class CppSampler:
         self._ck(self.L.epvd_download_branch_events(self.h, _p(out, C.c_uint32)))
         out = out[:nv.value].reshape(6, self.B, -1)
         ns = int(ns.value)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     def branch_event_windows(self, W):
         """-> (samples, uint64 [6, N-1, windows]): the planes summed over windows of W global sites (the
@@ -299,7 +300,7 @@ class CppSampler:
         self._ck(self.L.epvd_download_change_patterns(self.h, _p(out, C.c_uint32)))
         out = out[:nv.value].reshape(R.value, -1)
         ns = int(ns.value)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     def change_pattern_windows(self, W):
         """-> (samples, uint64 [R, windows]): the rows summed over windows of W global sites (the slots and

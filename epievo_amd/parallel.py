@@ -27,10 +27,14 @@ one bit-for-bit on paths, states, J AND D, for any number of ranks and any cut p
 The reference has no parallelism at all (single-threaded); this
 module is new capability, not a translation.
 """
+import functools
+
 import numpy as np
 
 from . import host
 from .host import FlatPaths
+from .sampler import DeviceSampler, forward_to_dev
+from .summaries import LIFECYCLE, NOUN, SUMMARIES, _per_sample, _window_range, summary_method
 
 BLOCK = 256      # sites per block: halo widths and shard_cuts' cut points are whole blocks
 TAIL = 1         # int64 words after a rank's counts in the all-gather: its accept count
@@ -162,7 +166,6 @@ class ShardedSampler:
     def __init__(self, comm, device=0, device_factory=None):
         self.comm = comm
         if device_factory is None:
-            from .sampler import DeviceSampler
             device_factory = DeviceSampler
         self.dev = device_factory(device)
         # a capacity overflow widens this shard's jump slots and the run carries on (as the
@@ -252,9 +255,6 @@ class ShardedSampler:
         self.dev.set_halo(self.left, self.right)     # marks the halos fresh
 
     # ---- SingleSiteSampler interface
-    def set_model(self, model):
-        self.dev.set_model(model)
-
     def reset(self):
         """refresh the halos (they are stale after the previous run_mcmc), then cache the
         triple log-likelihoods as SingleSiteSampler::reset does"""
@@ -299,56 +299,9 @@ class ShardedSampler:
         J, D = self.dev.counts_to_stats(total[:-TAIL].reshape(batch, -1), batch, True)
         return J, D, float(total[-TAIL]) / float(batch * (self.n_global - 2))
 
-    def scale_jump_times(self, new_branches):
-        self.dev.scale_jump_times(new_branches)
-
-    # ---- average history of the sampled paths: every rank counts its owned columns
-    def enable_path_average(self, n_points):
-        self.dev.enable_path_average(n_points)
-
-    def reset_path_average(self):
-        self.dev.reset_path_average()
-
-    def accumulate_path_average(self):
-        self.dev.accumulate_path_average()
-
-    def path_average(self, counts=False):
-        """-> (samples, [N-1, n_global, P]) of the whole genome, identical on every rank: the ranks'
-        counts are all-gathered (one collective) and concatenated in genome order"""
-        ns, own = self.dev.path_average(counts=True)
-        if self.comm.world > 1:
-            B, P = own.shape[0], own.shape[2]
-            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
-            if own.shape[1] != sizes[self.comm.rank]:
-                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[1], sizes[self.comm.rank]))
-            words = B * max(sizes) * P + 2                   # counts, then the sample count (two words)
-            mine = np.zeros(words, np.uint32)
-            mine[:B * max(sizes) * P].reshape(B, max(sizes), P)[:, :own.shape[1]] = own
-            mine[-2:] = [ns & 0xffffffff, ns >> 32]
-            piece, gathered = self.dev.alloc(4 * words), self.dev.alloc(4 * words * self.comm.world)
-            try:
-                self.dev.write(piece, 0, mine)
-                self.comm.all_gather(self.dev, piece, gathered)
-                allw = self.dev.read(gathered, 0, words * self.comm.world, np.uint32).reshape(self.comm.world, words)
-            finally:
-                piece.free()
-                gathered.free()
-            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of path-average samples")
-            own = np.concatenate([allw[r, :-2].reshape(B, max(sizes), P)[:, :sizes[r]] for r in range(self.comm.world)],
-                                 axis=1)
-        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
-
-    # ---- posterior branch-event maps: every rank counts its owned columns
-    def enable_branch_events(self, on=True):
-        self.dev.enable_branch_events(on)
-
-    def reset_branch_events(self):
-        self.dev.reset_branch_events()
-
-    def accumulate_branch_events(self):
-        self.dev.accumulate_branch_events()
-
+    # ---- the posterior summaries: every rank counts its owned columns, and a read-out of
+    # the whole genome, identical on every rank, has one of three shapes across ranks: _gather_sites, _gather_sums,
+    # _gather_parts.  At one rank none of them makes a collective
     def _gather_words(self, mine):
         """all-gather equal-sized uint32 pieces -> [world, words]"""
         words = len(mine)
@@ -361,182 +314,132 @@ class ShardedSampler:
             piece.free()
             gathered.free()
 
+    def _gather_sites(self, ns, blocks, noun, extra=()):
+        """rows concatenated by site in genome order, ONE collective.  blocks: this rank's uint32 arrays [rows, its
+        sites, words per cell] -> (the same over the whole genome, the ranks' `extra` words [world, len(extra)]).  A
+        rank's piece: its blocks, each padded to the sites of the widest rank, then the sample count (two words),
+        then `extra`"""
+        world = self.comm.world
+        if world == 1:
+            return blocks, np.array([extra], np.uint32)
+        sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
+        m, cnt = max(sizes), blocks[0].shape[1]
+        if cnt != sizes[self.comm.rank]:
+            raise RuntimeError("this rank counts %d sites, it owns %d" % (cnt, sizes[self.comm.rank]))
+        tail = np.array([ns & 0xffffffff, ns >> 32] + list(extra), np.uint32)
+        mine = []
+        for b in blocks:
+            padded = np.zeros((b.shape[0], m, b.shape[2]), np.uint32)
+            padded[:, :cnt] = b
+            mine.append(padded.reshape(-1))
+        allw = self._gather_words(np.concatenate(mine + [tail]))
+        at = allw.shape[1] - len(tail)
+        if any(int(w[at]) | (int(w[at + 1]) << 32) != ns for w in allw):
+            raise RuntimeError("the ranks hold different numbers of %s samples" % noun)
+        out, lo = [], 0
+        for b in blocks:
+            hi = lo + b.shape[0] * m * b.shape[2]
+            out.append(np.concatenate([allw[r, lo:hi].reshape(b.shape[0], m, b.shape[2])[:, :sizes[r]]
+                                       for r in range(world)], axis=1))
+            lo = hi
+        return out, allw[:, at + 2:]
+
+    def _gather_sums(self, ns, arrays, noun, add=None):
+        """integer totals added, ONE collective.  arrays: this rank's contributions, 64-bit integers of one dtype and
+        of the same shapes on every rank -> their sums over the ranks (`add` of the ranks' arrays, in rank order; plain
+        wrapping addition unless given).  A rank's piece: the arrays, then the sample count"""
+        if self.comm.world == 1:
+            return arrays
+        dt = arrays[0].dtype
+        mine = np.concatenate([np.asarray(a, dt).reshape(-1) for a in arrays] + [np.array([ns], dt)])
+        allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(dt)
+        if any(int(w[-1]) != ns for w in allw):
+            raise RuntimeError("the ranks hold different numbers of %s samples" % noun)
+        out, lo = [], 0
+        for a in arrays:
+            parts = [w[lo:lo + a.size].reshape(a.shape) for w in allw]
+            out.append(add(parts) if add else np.sum(parts, axis=0, dtype=dt))
+            lo += a.size
+        return out
+
+    def _gather_parts(self, ns, arrays, noun, merge):
+        """parts merged in genome order, TWO collectives: the sample counts are compared first (a part's size depends
+        on them), then the ranks' parts, uint64 arrays of the same shapes on every rank, are all-gathered and
+        merge([(arrays of rank 0), (arrays of rank 1), ...]) is the part of the whole genome"""
+        if self.comm.world == 1:
+            return tuple(arrays)
+        counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
+        if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
+            raise RuntimeError("the ranks hold different numbers of %s samples" % noun)
+        mine = np.concatenate([a.reshape(-1) for a in arrays]).astype(np.uint64)
+        allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
+        ends = np.cumsum([a.size for a in arrays])
+        return merge([tuple(w[e - a.size:e].reshape(a.shape) for a, e in zip(arrays, ends)) for w in allw])
+
+    def path_average(self, counts=False):
+        """-> (samples, [N-1, n_global, P]) of the whole genome, identical on every rank: the ranks'
+        counts are all-gathered (one collective) and concatenated in genome order"""
+        ns, own = self.dev.path_average(counts=True)
+        (own,), _ = self._gather_sites(ns, [own], NOUN["path_average"])
+        return ns, _per_sample(own, ns, counts)
+
     def branch_events(self, counts=False):
         """-> (samples, [6, N-1, n_global]) of the whole genome, identical on every rank: the ranks'
         planes are all-gathered (one collective) and concatenated in genome order"""
         ns, own = self.dev.branch_events(counts=True)
-        if self.comm.world > 1:
-            R = own.shape[0] * own.shape[1]
-            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
-            if own.shape[2] != sizes[self.comm.rank]:
-                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[2], sizes[self.comm.rank]))
-            mine = np.zeros(R * max(sizes) + 2, np.uint32)       # planes, then the sample count (two words)
-            mine[:-2].reshape(R, max(sizes))[:, :own.shape[2]] = own.reshape(R, -1)
-            mine[-2:] = [ns & 0xffffffff, ns >> 32]
-            allw = self._gather_words(mine)
-            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of branch-event samples")
-            own = np.concatenate([allw[r, :-2].reshape(R, max(sizes))[:, :sizes[r]] for r in range(self.comm.world)],
-                                 axis=1).reshape(own.shape[0], own.shape[1], -1)
-        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
+        (rows,), _ = self._gather_sites(ns, [own.reshape(-1, own.shape[2], 1)], NOUN["branch_events"])
+        return ns, _per_sample(rows.reshape(own.shape[0], own.shape[1], -1), ns, counts)
 
     def branch_event_windows(self, W):
         """-> (samples, uint64 [6, N-1, windows]) of the whole genome, identical on every rank: the ranks'
         contributions (windows of global sites) are all-gathered and summed"""
         ns, own = self.dev.branch_event_windows(W)
-        if self.comm.world > 1:
-            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
-            allw = self._gather_words(mine).view(np.uint64)
-            if any(int(w[-1]) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of branch-event samples")
-            own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
-        return ns, own
-
-    # ---- change patterns: every rank counts its owned columns
-    def enable_change_patterns(self, on=True):
-        self.dev.enable_change_patterns(on)
-
-    def reset_change_patterns(self):
-        self.dev.reset_change_patterns()
-
-    def accumulate_change_patterns(self):
-        self.dev.accumulate_change_patterns()
-
-    def change_patterns_samples(self):
-        return self.dev.change_patterns_samples()
+        return ns, self._gather_sums(ns, [own], NOUN["branch_events"])[0]
 
     def change_patterns(self, counts=False):
         """-> (samples, [R, n_global]) of the whole genome, identical on every rank: the ranks' rows are
         all-gathered (one collective) and concatenated in genome order"""
         ns, own = self.dev.change_patterns(counts=True)
-        if self.comm.world > 1:
-            R = own.shape[0]
-            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
-            if own.shape[1] != sizes[self.comm.rank]:
-                raise RuntimeError("this rank counts %d sites, it owns %d" % (own.shape[1], sizes[self.comm.rank]))
-            mine = np.zeros(R * max(sizes) + 2, np.uint32)       # rows, then the sample count (two words)
-            mine[:-2].reshape(R, max(sizes))[:, :own.shape[1]] = own
-            mine[-2:] = [ns & 0xffffffff, ns >> 32]
-            allw = self._gather_words(mine)
-            if any(int(w[-2]) | (int(w[-1]) << 32) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of change-pattern samples")
-            own = np.concatenate([allw[r, :-2].reshape(R, max(sizes))[:, :sizes[r]] for r in range(self.comm.world)],
-                                 axis=1)
-        return ns, (own if counts else own / float(ns) if ns else own.astype(np.float64))
+        (rows,), _ = self._gather_sites(ns, [own[:, :, None]], NOUN["change_patterns"])
+        return ns, _per_sample(rows[:, :, 0], ns, counts)
 
     def change_pattern_windows(self, W):
         """-> (samples, uint64 [R, windows]) of the whole genome, identical on every rank: the ranks'
         contributions (windows of global sites) are all-gathered and summed"""
         ns, own = self.dev.change_pattern_windows(W)
-        if self.comm.world > 1:
-            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
-            allw = self._gather_words(mine).view(np.uint64)
-            if any(int(w[-1]) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of change-pattern samples")
-            own = allw[:, :-1].sum(axis=0, dtype=np.uint64).reshape(own.shape)
-        return ns, own
-
-    # ---- regional sufficient statistics: every rank adds the windows its owned columns meet
-    def enable_window_stats(self, W):
-        self.dev.enable_window_stats(W)
-
-    def reset_window_stats(self):
-        self.dev.reset_window_stats()
-
-    def accumulate_window_stats(self):
-        self.dev.accumulate_window_stats()
-
-    def window_stats_scale_exps(self):
-        return self.dev.window_stats_scale_exps()
+        return ns, self._gather_sums(ns, [own], NOUN["change_patterns"])[0]
 
     def window_stats(self, counts=False):
         """-> (samples, J, D [nw, N-1, 8]) of the whole genome (or the int64 [nw, N-1, 16]), identical on
         every rank: the ranks' integer contributions are all-gathered and added, then converted once"""
         ns, own = self.dev.window_counts()
-        if self.comm.world > 1:
-            mine = np.append(own.reshape(-1), np.int64(ns)).view(np.uint32)
-            allw = self._gather_words(mine).view(np.int64)
-            if any(int(w[-1]) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of window-statistics samples")
-            own = allw[:, :-1].sum(axis=0, dtype=np.int64).reshape(own.shape)
+        own, = self._gather_sums(ns, [own], NOUN["window_stats"])
         if counts:
             return ns, own
         if not ns:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.dev.window_counts_to_stats(own, ns)
 
-    # ---- epoch statistics: every rank adds the triples centred at its owned columns
-    def enable_epoch_stats(self, P):
-        self.dev.enable_epoch_stats(P)
-
-    def reset_epoch_stats(self):
-        self.dev.reset_epoch_stats()
-
-    def accumulate_epoch_stats(self):
-        self.dev.accumulate_epoch_stats()
-
-    def epoch_stats_samples(self):
-        return self.dev.epoch_stats_samples()
-
     def epoch_stats(self, counts=False):
         """-> (samples, J, D [N-1, P, 8]) of the whole genome (or the closed integers), identical on every
         rank: the ranks' raw parts are all-gathered and added as integers, then closed once"""
         ns, own = self.dev.epoch_raw()
-        if self.comm.world > 1:
-            mine = np.append(own.reshape(-1), np.uint64(ns)).view(np.uint32)
-            allw = self._gather_words(mine).view(np.uint64)
-            if any(int(w[-1]) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of epoch-statistics samples")
-            own = host.epoch_raw_add([w[:-1].reshape(own.shape) for w in allw])
+        own, = self._gather_sums(ns, [own], NOUN["epoch_stats"], host.epoch_raw_add)
         _, k, fixT = self.dev.epoch_stats_layout()
         return host.epoch_finish(own, fixT, k, ns, counts)
 
-    # ---- lineage origin maps: every rank counts its owned columns
-    def enable_lineage_origins(self, on=True):
-        self.dev.enable_lineage_origins(on)
-
-    def reset_lineage_origins(self):
-        self.dev.reset_lineage_origins()
-
-    def accumulate_lineage_origins(self):
-        self.dev.accumulate_lineage_origins()
-
-    def lineage_origins_samples(self):
-        return self.dev.lineage_origins_samples()
-
-    def lineage_origins_layout(self):
-        """(leaves L, rows R, first local site, number of sites) of this rank's engine"""
-        return self.dev.lineage_origins_layout()
-
-    def lineage_origin_rows(self):
-        return self.dev.lineage_origin_rows()
-
-    def lineage_origins_scale_exp(self):
-        return self.dev.lineage_origins_scale_exp()
-
     def lineage_origins(self, counts=False):
         """-> (samples, rows [R, 2], origin [R, n_global], age [L, n_global]) of the whole genome, identical on
-        every rank: the ranks' cells are all-gathered (one collective) and concatenated in genome order"""
+        every rank: the ranks' cells are all-gathered (one collective) and concatenated in genome order; an age cell
+        travels as two words, and the scale exponent after the sample count"""
         ns, rows, origin, age = self.dev.lineage_origins(counts=True)
         k = self.dev.lineage_origins_scale_exp()
-        if self.comm.world > 1:
-            R, L = origin.shape[0], age.shape[0]
-            sizes = [b - a for a, b in zip(self.cuts[:-1], self.cuts[1:])]
-            if origin.shape[1] != sizes[self.comm.rank]:
-                raise RuntimeError("this rank counts %d sites, it owns %d" % (origin.shape[1], sizes[self.comm.rank]))
-            m = max(sizes)
-            mine = np.zeros((R + 2 * L) * m + 3, np.uint32)   # origin rows, age rows (two words a cell), samples, k
-            mine[:R * m].reshape(R, m)[:, :origin.shape[1]] = origin
-            mine[R * m:-3].view(np.uint64).reshape(L, m)[:, :age.shape[1]] = age
-            mine[-3:] = [ns & 0xffffffff, ns >> 32, k & 0xffffffff]
-            allw = self._gather_words(mine)
-            if any(int(w[-3]) | (int(w[-2]) << 32) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of lineage-origin samples")
-            if any(int(w[-1]) != k & 0xffffffff for w in allw):
-                raise RuntimeError("the ranks hold lineage-origin ages of different scales")
-            origin = np.concatenate([allw[r, :R * m].reshape(R, m)[:, :sizes[r]] for r in range(self.comm.world)], axis=1)
-            age = np.concatenate([np.ascontiguousarray(allw[r, R * m:-3]).view(np.uint64).reshape(L, m)[:, :sizes[r]]
-                                  for r in range(self.comm.world)], axis=1)
+        age_words = np.ascontiguousarray(age, np.uint64).view(np.uint32).reshape(age.shape[0], -1, 2)
+        (origin, age_words), ks = self._gather_sites(ns, [origin[:, :, None], age_words], NOUN["lineage_origins"],
+                                                     extra=[k & 0xffffffff])
+        if any(int(w[0]) != k & 0xffffffff for w in ks):
+            raise RuntimeError("the ranks hold lineage-origin ages of different scales")
+        origin, age = origin[:, :, 0], np.ascontiguousarray(age_words).view(np.uint64)[:, :, 0]
         if counts:
             return ns, rows, origin, age
         d = float(ns) if ns else 1.0
@@ -546,89 +449,27 @@ class ShardedSampler:
         """-> (samples, uint64 [R, windows], uint64 [L, windows]) of the whole genome, identical on every rank:
         the ranks' contributions (windows of global sites) are all-gathered and added as integers"""
         ns, ow, aw = self.dev.lineage_origin_windows(W)
-        if self.comm.world > 1:
-            R = ow.shape[0]
-            mine = np.concatenate([ow.reshape(-1), aw.reshape(-1), [np.uint64(ns)]]).astype(np.uint64).view(np.uint32)
-            allw = np.ascontiguousarray(self._gather_words(mine)).view(np.uint64)
-            if any(int(w[-1]) != ns for w in allw):
-                raise RuntimeError("the ranks hold different numbers of lineage-origin samples")
-            tot = add_uint64([w[:-1] for w in allw]).reshape(R + aw.shape[0], -1)
-            ow, aw = tot[:R], tot[R:]
+        ow, aw = self._gather_sums(ns, [ow, aw], NOUN["lineage_origins"], add_uint64)
         return ns, ow, aw
-
-    # ---- domain size spectra: every rank counts the part of its owned columns
-    def enable_domain_stats(self, max_samples):
-        self.dev.enable_domain_stats(max_samples)
-
-    def reset_domain_stats(self):
-        self.dev.reset_domain_stats()
-
-    def accumulate_domain_stats(self):
-        self.dev.accumulate_domain_stats()
-
-    def domain_stats_samples(self):
-        return self.dev.domain_stats_samples()
-
-    def domain_stats_layout(self):
-        """(nodes N, bins, first local site, sites, sites per block of the runs kernel) of this rank's engine"""
-        return self.dev.domain_stats_layout()
 
     def domain_stats_part(self):
         """-> (samples, hist, len_sum, edges): the part of the whole genome, identical on every rank: the sample
         counts are compared first (a part's size depends on them), then the ranks' parts are all-gathered and
         merged in genome order"""
-        ns, hist, len_sum, edges = self.dev.domain_stats_part()
-        if self.comm.world > 1:
-            N = hist.shape[0]
-            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
-            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
-                raise RuntimeError("the ranks hold different numbers of domain-statistics samples")
-            mine = np.concatenate([hist.reshape(-1), len_sum.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
-            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
-            nh, nl = hist.size, len_sum.size
-            hist, len_sum, edges = host.domain_parts_merge(
-                [(w[:nh].reshape(N, 2, -1), w[nh:nh + nl].reshape(N, 2), w[nh + nl:].reshape(ns, N, 2)) for w in allw])
-        return ns, hist, len_sum, edges
+        ns, *part = self.dev.domain_stats_part()
+        return (ns,) + self._gather_parts(ns, part, NOUN["domain_stats"], host.domain_parts_merge)
 
     def domain_stats(self):
         """-> (samples, hist [N, 2, 128], len_sum [N, 2]) of the whole genome, closed; every rank merges and closes"""
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
-    # ---- domain turnover: every rank counts the part of its owned columns
-    def enable_domain_turnover(self, max_samples):
-        self.dev.enable_domain_turnover(max_samples)
-
-    def reset_domain_turnover(self):
-        self.dev.reset_domain_turnover()
-
-    def accumulate_domain_turnover(self):
-        self.dev.accumulate_domain_turnover()
-
-    def domain_turnover_samples(self):
-        return self.dev.domain_turnover_samples()
-
-    def domain_turnover_layout(self):
-        """(rows R, bins, first local site, sites, sites per block of the runs kernel) of this rank's engine"""
-        return self.dev.domain_turnover_layout()
-
     def domain_turnover_part(self):
         """-> (samples, hist, len_sum, edges): the part of the whole genome, identical on every rank: the sample
         counts are compared first (a part's size depends on them), then the ranks' parts are all-gathered and
         merged in genome order"""
-        ns, hist, len_sum, edges = self.dev.domain_turnover_part()
-        if self.comm.world > 1:
-            R = hist.shape[0]
-            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
-            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
-                raise RuntimeError("the ranks hold different numbers of domain-turnover samples")
-            mine = np.concatenate([hist.reshape(-1), len_sum.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
-            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
-            nh, nl = hist.size, len_sum.size
-            hist, len_sum, edges = host.turnover_parts_merge(
-                [(w[:nh].reshape(R, 2, 2, -1), w[nh:nh + nl].reshape(R, 2, 2), w[nh + nl:].reshape(ns, R, 2))
-                 for w in allw])
-        return ns, hist, len_sum, edges
+        ns, *part = self.dev.domain_turnover_part()
+        return (ns,) + self._gather_parts(ns, part, NOUN["domain_turnover"], host.turnover_parts_merge)
 
     def domain_turnover(self):
         """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]) of the whole genome, closed; every rank merges and
@@ -636,38 +477,16 @@ class ShardedSampler:
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
-    # ---- spatial correlations: every rank counts the part of its owned columns
-    def enable_spatial_correlation(self, max_lag, max_samples):
-        self.dev.enable_spatial_correlation(max_lag, max_samples)
-
-    def reset_spatial_correlation(self):
-        self.dev.reset_spatial_correlation()
-
-    def accumulate_spatial_correlation(self):
-        self.dev.accumulate_spatial_correlation()
-
-    def spatial_correlation_samples(self):
-        return self.dev.spatial_correlation_samples()
-
-    def spatial_correlation_layout(self):
-        """(rows R, max_lag, first local site, sites, sites per block of the count kernel) of this rank's engine"""
-        return self.dev.spatial_correlation_layout()
-
     def spatial_correlation_part(self):
         """-> (samples, sites, n11, edges): the part of the whole genome, identical on every rank: the sample counts
-        are compared first (a part's size depends on them), then the ranks' parts are all-gathered and merged in
-        genome order"""
+        are compared first (a part's size depends on them), then the ranks' parts, each behind its number of sites,
+        are all-gathered and merged in genome order"""
         ns, cnt, n11, edges = self.dev.spatial_correlation_part()
-        if self.comm.world > 1:
-            counts = self._gather_words(np.array([ns & 0xffffffff, ns >> 32], np.uint32))
-            if any(int(w[0]) | (int(w[1]) << 32) != ns for w in counts):
-                raise RuntimeError("the ranks hold different numbers of spatial-correlation samples")
-            mine = np.concatenate([np.array([cnt], np.uint64), n11.reshape(-1), edges.reshape(-1)]).astype(np.uint64)
-            allw = np.ascontiguousarray(self._gather_words(mine.view(np.uint32))).view(np.uint64)
-            na = n11.size
-            cnt, n11, edges = host.corr_parts_merge(
-                [(int(w[0]), w[1:1 + na].reshape(n11.shape), w[1 + na:].reshape(edges.shape)) for w in allw])
-        return ns, cnt, n11, edges
+        if self.comm.world == 1:
+            return ns, cnt, n11, edges
+        return (ns,) + self._gather_parts(
+            ns, [np.array([cnt], np.uint64), n11, edges], NOUN["spatial_correlation"],
+            lambda parts: host.corr_parts_merge([(int(c[0]), a, e) for c, a, e in parts]))
 
     def spatial_correlation(self):
         """-> (samples, n11, left1, right1), each [R, L + 1], of the whole genome, closed; every rank merges and
@@ -677,6 +496,12 @@ class ShardedSampler:
 
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
+
+
+# what needs nothing from the other ranks is the engine's own
+forward_to_dev(ShardedSampler, LIFECYCLE + [
+    "set_model", "scale_jump_times", "window_stats_scale_exps", "lineage_origins_layout", "lineage_origin_rows",
+    "lineage_origins_scale_exp", "domain_stats_layout", "domain_turnover_layout", "spatial_correlation_layout"])
 
 
 class LocalGroup:
@@ -695,7 +520,6 @@ class LocalGroup:
 
     def __init__(self, device=0, shards=2, sweeps_per_refresh=60):
         from concurrent.futures import ThreadPoolExecutor
-        from .sampler import DeviceSampler
         self.device, self.k_req = device, max(1, int(shards))
         self.H_INT = halo_width(sweeps_per_refresh)   # internal halo columns (whole blocks)
         self.subs = [DeviceSampler(device) for _ in range(self.k_req)]
@@ -908,127 +732,94 @@ class LocalGroup:
         for s in self.subs:
             s.set_capacity(capacity)
 
-    # ---- average history of the sampled paths: every shard counts the sites it owns
-    def enable_path_average(self, n_points):
-        self._each(lambda j, s: s.enable_path_average(n_points))
+    # ---- the posterior summaries: every shard counts the sites it owns.  enable_<stem>,
+    # reset_<stem>, accumulate_<stem> and <stem>_samples of every row of SUMMARIES are made below the class of the
+    # three helpers here (enable_spatial_correlation is written out: it keeps the lag).  A read-out takes every
+    # shard's, wants the same number of samples of all, and concatenates along sites, adds integers or merges parts
+    def _each_call(self, name, *args, **kwargs):
+        """every shard's method `name`, from the shard's own host thread; results in shard (= genome) order"""
+        return self._each(lambda j, s: getattr(s, name)(*args, **kwargs))
 
-    def reset_path_average(self):
-        self._each(lambda j, s: s.reset_path_average())
+    def _reset_summary(self, s):
+        self._each_call("reset_" + s.stem)
 
-    def accumulate_path_average(self):
+    def _accumulate_summary(self, s):
         if len(self.subs) > 1 and not self.halo_mode:
             # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a path-average sample")
-        self._each(lambda j, s: s.accumulate_path_average())
+            raise RuntimeError("reset() the group before taking %s %s sample" % (s.article, s.noun))
+        self._each_call("accumulate_" + s.stem)
 
-    def path_average_samples(self):
-        return self.subs[0].path_average_samples()
+    def _summary_samples(self, s):
+        return getattr(self.subs[0], s.stem + "_samples")()
 
-    def path_average(self, counts=False):
-        """-> (samples, [N-1, sites, P]) over the group's owned sites, shards in genome order"""
-        parts = self._each(lambda j, s: s.path_average(counts=True))
+    def _same_samples(self, parts, noun):
         ns = parts[0][0]
         if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of path-average samples")
-        out = np.concatenate([p[1] for p in parts], axis=1)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
-
-    # ---- posterior branch-event maps: every shard counts the sites it owns
-    def enable_branch_events(self, on=True):
-        self._each(lambda j, s: s.enable_branch_events(on))
-
-    def reset_branch_events(self):
-        self._each(lambda j, s: s.reset_branch_events())
-
-    def accumulate_branch_events(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a branch-event sample")
-        self._each(lambda j, s: s.accumulate_branch_events())
-
-    def branch_events_samples(self):
-        return self.subs[0].branch_events_samples()
-
-    def _same_samples(self, parts):
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of branch-event samples")
+            raise RuntimeError("the shards of the group hold different numbers of %s samples" % noun)
         return ns
 
+    def _parts(self, stem, name, *args, **kwargs):
+        """-> (the number of samples all shards agree on, every shard's read-out `name` of the summary `stem`)"""
+        parts = self._each_call(name, *args, **kwargs)
+        return self._same_samples(parts, NOUN[stem]), parts
+
+    @staticmethod
+    def _along_sites(parts, field, axis=1):
+        return np.concatenate([p[field] for p in parts], axis=axis)
+
+    @staticmethod
+    def _added(parts, field, add=sum):
+        return add([p[field] for p in parts])
+
+    @staticmethod
+    def _merged(parts, merge):
+        return merge([p[1:] for p in parts])
+
+    def _layout_over_shards(self, name):
+        """a layout (.., .., first local site, sites, ..): of the first shard, with the sites of all shards"""
+        lay = self._each_call(name)
+        return lay[0][:3] + (sum(v[3] for v in lay),) + lay[0][4:]
+
+    def _windows(self, W, first_window, n_windows):
+        return _window_range(W, self.subs[0].n_global, first_window, n_windows)
+
+    # average history of the sampled paths
+    def path_average(self, counts=False):
+        """-> (samples, [N-1, sites, P]) over the group's owned sites, shards in genome order"""
+        ns, parts = self._parts("path_average", "path_average", counts=True)
+        return ns, _per_sample(self._along_sites(parts, 1), ns, counts)
+
+    # posterior branch-event maps
     def branch_events(self, counts=False):
         """-> (samples, [6, N-1, sites]) over the group's owned sites, shards in genome order"""
-        parts = self._each(lambda j, s: s.branch_events(counts=True))
-        ns = self._same_samples(parts)
-        out = np.concatenate([p[1] for p in parts], axis=2)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        ns, parts = self._parts("branch_events", "branch_events", counts=True)
+        return ns, _per_sample(self._along_sites(parts, 1, axis=2), ns, counts)
 
     def branch_event_windows(self, W, first_window=0, n_windows=None):
         """-> (samples, uint64 [6, N-1, windows]): the shards' contributions to the windows of W global
         sites, added"""
-        if n_windows is None:
-            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
-        parts = self._each(lambda j, s: s.branch_event_windows(W, first_window, n_windows))
-        return self._same_samples(parts), sum(p[1] for p in parts)
+        W, n_windows = self._windows(W, first_window, n_windows)
+        ns, parts = self._parts("branch_events", "branch_event_windows", W, first_window, n_windows)
+        return ns, self._added(parts, 1)
 
-    # ---- change patterns: every shard counts the sites it owns
-    def enable_change_patterns(self, on=True):
-        self._each(lambda j, s: s.enable_change_patterns(on))
-
-    def reset_change_patterns(self):
-        self._each(lambda j, s: s.reset_change_patterns())
-
-    def accumulate_change_patterns(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a change-pattern sample")
-        self._each(lambda j, s: s.accumulate_change_patterns())
-
-    def change_patterns_samples(self):
-        return self.subs[0].change_patterns_samples()
-
-    def _same_pattern_samples(self, parts):
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of change-pattern samples")
-        return ns
-
+    # change patterns
     def change_patterns(self, counts=False):
         """-> (samples, [R, sites]) over the group's owned sites, shards in genome order"""
-        parts = self._each(lambda j, s: s.change_patterns(counts=True))
-        ns = self._same_pattern_samples(parts)
-        out = np.concatenate([p[1] for p in parts], axis=1)
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        ns, parts = self._parts("change_patterns", "change_patterns", counts=True)
+        return ns, _per_sample(self._along_sites(parts, 1), ns, counts)
 
     def change_pattern_windows(self, W, first_window=0, n_windows=None):
         """-> (samples, uint64 [R, windows]): the shards' contributions to the windows of W global sites,
         added"""
-        if n_windows is None:
-            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
-        parts = self._each(lambda j, s: s.change_pattern_windows(W, first_window, n_windows))
-        return self._same_pattern_samples(parts), sum(p[1] for p in parts)
+        W, n_windows = self._windows(W, first_window, n_windows)
+        ns, parts = self._parts("change_patterns", "change_pattern_windows", W, first_window, n_windows)
+        return ns, self._added(parts, 1)
 
-    # ---- regional sufficient statistics: every shard adds the windows its owned sites meet
-    def enable_window_stats(self, W):
-        self._each(lambda j, s: s.enable_window_stats(W))
-
-    def reset_window_stats(self):
-        self._each(lambda j, s: s.reset_window_stats())
-
-    def accumulate_window_stats(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            raise RuntimeError("reset() the group before taking a window-statistics sample")
-        self._each(lambda j, s: s.accumulate_window_stats())
-
-    def window_stats_samples(self):
-        return self.subs[0].window_stats_samples()
-
+    # regional sufficient statistics: every shard adds the windows its owned sites meet
     def window_counts(self, first_window=0, n_windows=None):
         """-> (samples, int64 [windows, N-1, 16]): the shards' contributions, added as integers"""
-        parts = self._each(lambda j, s: s.window_counts(first_window, n_windows))
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of window-statistics samples")
-        return ns, sum(p[1] for p in parts)
+        ns, parts = self._parts("window_stats", "window_counts", first_window, n_windows)
+        return ns, self._added(parts, 1)
 
     def window_counts_to_stats(self, counts, samples):
         return self.subs[0].window_counts_to_stats(counts, samples)
@@ -1046,25 +837,10 @@ class LocalGroup:
             raise RuntimeError("window statistics hold no sample")
         return (ns,) + self.window_counts_to_stats(cnt, ns)
 
-    # ---- lineage origin maps: every shard counts the sites it owns
-    def enable_lineage_origins(self, on=True):
-        self._each(lambda j, s: s.enable_lineage_origins(on))
-
-    def reset_lineage_origins(self):
-        self._each(lambda j, s: s.reset_lineage_origins())
-
-    def accumulate_lineage_origins(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            raise RuntimeError("reset() the group before taking a lineage-origin sample")
-        self._each(lambda j, s: s.accumulate_lineage_origins())
-
-    def lineage_origins_samples(self):
-        return self.subs[0].lineage_origins_samples()
-
+    # lineage origin maps
     def lineage_origins_layout(self):
         """(leaves L, rows R, first local site of the first shard, sites over all shards)"""
-        lay = self._each(lambda j, s: s.lineage_origins_layout())
-        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay)
+        return self._layout_over_shards("lineage_origins_layout")
 
     def lineage_origin_rows(self):
         return self.subs[0].lineage_origin_rows()
@@ -1072,19 +848,11 @@ class LocalGroup:
     def lineage_origins_scale_exp(self):
         return self.subs[0].lineage_origins_scale_exp()
 
-    def _same_origin_samples(self, parts):
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of lineage-origin samples")
-        return ns
-
     def lineage_origins(self, counts=False):
         """-> (samples, rows [R, 2], origin [R, sites], age [L, sites]) over the group's owned sites, shards in
         genome order"""
-        parts = self._each(lambda j, s: s.lineage_origins(counts=True))
-        ns = self._same_origin_samples(parts)
-        origin = np.concatenate([p[2] for p in parts], axis=1)
-        age = np.concatenate([p[3] for p in parts], axis=1)
+        ns, parts = self._parts("lineage_origins", "lineage_origins", counts=True)
+        origin, age = self._along_sites(parts, 2), self._along_sites(parts, 3)
         if counts:
             return ns, parts[0][1], origin, age
         k, d = self.lineage_origins_scale_exp(), float(ns) if ns else 1.0
@@ -1093,139 +861,67 @@ class LocalGroup:
     def lineage_origin_windows(self, W, first_window=0, n_windows=None):
         """-> (samples, uint64 [R, windows], uint64 [L, windows]): the shards' contributions to the windows of
         W global sites, added as integers"""
-        if n_windows is None:
-            n_windows = (self.subs[0].n_global + int(W) - 1) // int(W) - first_window
-        parts = self._each(lambda j, s: s.lineage_origin_windows(W, first_window, n_windows))
-        return self._same_origin_samples(parts), add_uint64([p[1] for p in parts]), add_uint64([p[2] for p in parts])
+        W, n_windows = self._windows(W, first_window, n_windows)
+        ns, parts = self._parts("lineage_origins", "lineage_origin_windows", W, first_window, n_windows)
+        return ns, self._added(parts, 1, add_uint64), self._added(parts, 2, add_uint64)
 
-    # ---- domain size spectra: every shard counts the part of the sites it owns
-    def enable_domain_stats(self, max_samples):
-        self._each(lambda j, s: s.enable_domain_stats(max_samples))
-
-    def reset_domain_stats(self):
-        self._each(lambda j, s: s.reset_domain_stats())
-
-    def accumulate_domain_stats(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a domain-statistics sample")
-        self._each(lambda j, s: s.accumulate_domain_stats())
-
-    def domain_stats_samples(self):
-        return self.subs[0].domain_stats_samples()
-
+    # domain size spectra: a shard's part is that of the sites it owns
     def domain_stats_layout(self):
         """(nodes N, bins, first local site of the first shard, sites over all shards, sites per block)"""
-        lay = self._each(lambda j, s: s.domain_stats_layout())
-        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+        return self._layout_over_shards("domain_stats_layout")
 
     def domain_stats_part(self):
         """-> (samples, hist, len_sum, edges): the shards' parts merged in genome order, unclosed"""
-        parts = self._each(lambda j, s: s.domain_stats_part())
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of domain-statistics samples")
-        return (ns,) + host.domain_parts_merge([p[1:] for p in parts])
+        ns, parts = self._parts("domain_stats", "domain_stats_part")
+        return (ns,) + self._merged(parts, host.domain_parts_merge)
 
     def domain_stats(self):
         """-> (samples, hist [N, 2, 128], len_sum [N, 2]) over the group's owned sites, closed"""
         ns, hist, len_sum, edges = self.domain_stats_part()
         return (ns,) + host.domain_part_close(hist, len_sum, edges)
 
-    # ---- domain turnover: every shard counts the part of the sites it owns
-    def enable_domain_turnover(self, max_samples):
-        self._each(lambda j, s: s.enable_domain_turnover(max_samples))
-
-    def reset_domain_turnover(self):
-        self._each(lambda j, s: s.reset_domain_turnover())
-
-    def accumulate_domain_turnover(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a domain-turnover sample")
-        self._each(lambda j, s: s.accumulate_domain_turnover())
-
-    def domain_turnover_samples(self):
-        return self.subs[0].domain_turnover_samples()
-
+    # domain turnover: likewise
     def domain_turnover_layout(self):
         """(rows R, bins, first local site of the first shard, sites over all shards, sites per block)"""
-        lay = self._each(lambda j, s: s.domain_turnover_layout())
-        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+        return self._layout_over_shards("domain_turnover_layout")
 
     def domain_turnover_part(self):
         """-> (samples, hist, len_sum, edges): the shards' parts merged in genome order, unclosed"""
-        parts = self._each(lambda j, s: s.domain_turnover_part())
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of domain-turnover samples")
-        return (ns,) + host.turnover_parts_merge([p[1:] for p in parts])
+        ns, parts = self._parts("domain_turnover", "domain_turnover_part")
+        return (ns,) + self._merged(parts, host.turnover_parts_merge)
 
     def domain_turnover(self):
         """-> (samples, hist [R, 2, 2, 128], len_sum [R, 2, 2]) over the group's owned sites, closed"""
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
-    # ---- spatial correlations: every shard counts the part of the sites it owns
+    # spatial correlations: likewise
     def enable_spatial_correlation(self, max_lag, max_samples):
         self._corr_lag = int(max_lag)
-        self._each(lambda j, s: s.enable_spatial_correlation(max_lag, max_samples))
-
-    def reset_spatial_correlation(self):
-        self._each(lambda j, s: s.reset_spatial_correlation())
-
-    def accumulate_spatial_correlation(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            # before the first reset() the shards' ranges overlap (their halos are not marked yet)
-            raise RuntimeError("reset() the group before taking a spatial-correlation sample")
-        self._each(lambda j, s: s.accumulate_spatial_correlation())
-
-    def spatial_correlation_samples(self):
-        return self.subs[0].spatial_correlation_samples()
+        self._each_call("enable_spatial_correlation", max_lag, max_samples)
 
     def spatial_correlation_layout(self):
         """(rows R, max_lag, first local site of the first shard, sites over all shards, sites per block)"""
-        lay = self._each(lambda j, s: s.spatial_correlation_layout())
-        return lay[0][0], lay[0][1], lay[0][2], sum(v[3] for v in lay), lay[0][4]
+        return self._layout_over_shards("spatial_correlation_layout")
 
     def spatial_correlation_part(self):
         """-> (samples, sites, n11, edges): the shards' parts merged in genome order, unclosed"""
-        parts = self._each(lambda j, s: s.spatial_correlation_part())
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of spatial-correlation samples")
-        return (ns,) + host.corr_parts_merge([p[1:] for p in parts])
+        ns, parts = self._parts("spatial_correlation", "spatial_correlation_part")
+        return (ns,) + self._merged(parts, host.corr_parts_merge)
 
     def spatial_correlation(self):
         """-> (samples, n11, left1, right1), each [R, L + 1], over the group's owned sites, closed"""
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
 
-    # ---- epoch statistics: every shard adds the triples centred at its owned sites
-    def enable_epoch_stats(self, P):
-        self._each(lambda j, s: s.enable_epoch_stats(P))
-
-    def reset_epoch_stats(self):
-        self._each(lambda j, s: s.reset_epoch_stats())
-
-    def accumulate_epoch_stats(self):
-        if len(self.subs) > 1 and not self.halo_mode:
-            raise RuntimeError("reset() the group before taking an epoch-statistics sample")
-        self._each(lambda j, s: s.accumulate_epoch_stats())
-
-    def epoch_stats_samples(self):
-        return self.subs[0].epoch_stats_samples()
-
+    # epoch statistics: every shard adds the triples centred at its owned sites
     def epoch_stats_layout(self):
         return self.subs[0].epoch_stats_layout()
 
     def epoch_raw(self):
         """-> (samples, uint64 [N-1, P, 32]): the shards' raw parts, added as integers"""
-        parts = self._each(lambda j, s: s.epoch_raw())
-        ns = parts[0][0]
-        if any(p[0] != ns for p in parts):
-            raise RuntimeError("the shards of the group hold different numbers of epoch-statistics samples")
-        return ns, host.epoch_raw_add([p[1] for p in parts])
+        ns, parts = self._parts("epoch_stats", "epoch_raw")
+        return ns, self._added(parts, 1, host.epoch_raw_add)
 
     def epoch_stats(self, counts=False):
         """-> (samples, J, D [N-1, P, 8]) or the closed integers: added over the shards as integers, then
@@ -1262,3 +958,20 @@ class LocalGroup:
             tot += ms * nl
             n += nl
         return (tot / n if n else 0.0), n
+
+
+def _enable_on_every_shard(name):
+    """LocalGroup's enable_<stem>: DeviceSampler's, with its arguments, on every shard"""
+    @functools.wraps(getattr(DeviceSampler, name))
+    def method(self, *args, **kwargs):
+        self._each_call(name, *args, **kwargs)
+    return method
+
+
+for _s in SUMMARIES:
+    if "enable_" + _s.stem not in vars(LocalGroup):
+        setattr(LocalGroup, "enable_" + _s.stem, _enable_on_every_shard("enable_" + _s.stem))
+    setattr(LocalGroup, "reset_" + _s.stem, summary_method(LocalGroup._reset_summary, _s, "reset_" + _s.stem))
+    setattr(LocalGroup, "accumulate_" + _s.stem,
+            summary_method(LocalGroup._accumulate_summary, _s, "accumulate_" + _s.stem))
+    setattr(LocalGroup, _s.stem + "_samples", summary_method(LocalGroup._summary_samples, _s, _s.stem + "_samples"))

@@ -6,6 +6,7 @@ reset(model, paths), run_mcmc(...) -> J, D, acc_rate).
 There is no CPU fallback: if the HIP library is missing or no GPU can be opened,
 construction raises."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -13,6 +14,7 @@ import numpy as np
 from . import _build
 from . import host
 from .host import FlatPaths
+from .summaries import LIFECYCLE, SUMMARIES, _per_sample, _window_range, summary_method
 
 _lib = None
 
@@ -37,42 +39,78 @@ class _Counters(C.Structure):
 MAX_CAPACITY = 2047    # EPV_MAX_CAP: jump slots per (site, branch)
 EPOCH_MAX_P = 256      # EPV_EPOCH_MAX_P: epochs per branch of the epoch statistics
 
-ABI_SYMBOLS = [
-    "epv_create", "epv_destroy", "epv_last_error", "epv_set_tree", "epv_set_model",
-    "epv_upload_paths", "epv_set_capacity", "epv_get_capacity", "epv_init_paths_indep", "epv_indep_expectation",
-    "epv_indep_sufficient_statistics", "epv_indep_update_paths", "epv_indep_node_posterior", "epv_set_global_length", "epv_set_update_range", "epv_set_halo",
-    "epv_halo_phases_left", "epv_reset", "epv_reset_async", "epv_sweep",
-    "epv_sweep_phase", "epv_run_mcmc", "epv_run_mcmc_sums", "epv_get_sufficient_statistics", "epv_scale_jump_times",
-    "epv_paths_total_jumps", "epv_download_paths", "epv_get_tri_llh", "epv_column_bytes",
-    "epv_get_columns", "epv_put_columns", "epv_copy_columns", "epv_dev_alloc", "epv_dev_free",
-    "epv_run_mcmc_counts", "epv_counts_to_stats", "epv_get_counters", "epv_kernel_time_ms",
-    "epv_set_timing", "epv_pack_columns_dev", "epv_unpack_columns_dev", "epv_device_of",
-    "epv_dev_write", "epv_dev_read", "epv_set_options", "epv_get_options", "epv_phase_mode",
-    "epv_phase_plan", "epv_philox_kat", "epv_math_kat", "epv_merge_kat", "epv_set_unobserved", "epv_unobserved_cells", "epv_set_leaf_evidence", "epv_leaf_evidence_cells",
-    "epv_forward_simulate", "epv_forward_last_ms", "epv_copy_columns_async",
-    "epv_set_path_average", "epv_reset_path_average", "epv_accumulate_path_average", "epv_path_average_samples",
-    "epv_get_path_average", "epv_path_average_layout",
-    "epv_set_branch_events", "epv_reset_branch_events", "epv_accumulate_branch_events", "epv_branch_events_samples",
-    "epv_branch_events_set_samples", "epv_branch_events_layout", "epv_get_branch_events",
-    "epv_get_branch_event_windows",
-    "epv_set_window_stats", "epv_reset_window_stats", "epv_accumulate_window_stats", "epv_window_stats_samples",
-    "epv_window_stats_set_samples", "epv_window_stats_scale_exps", "epv_window_stats_layout", "epv_get_window_stats", "epv_window_counts_to_stats",
-    "epv_set_epoch_stats", "epv_reset_epoch_stats", "epv_accumulate_epoch_stats", "epv_epoch_stats_samples",
-    "epv_epoch_stats_set_samples", "epv_epoch_stats_layout", "epv_get_epoch_stats",
-    "epv_set_lineage_origins", "epv_reset_lineage_origins", "epv_accumulate_lineage_origins",
-    "epv_lineage_origins_samples", "epv_lineage_origins_set_samples", "epv_lineage_origins_layout",
-    "epv_lineage_origin_rows", "epv_lineage_origins_scale_exp", "epv_get_lineage_origins",
-    "epv_get_lineage_origin_windows",
-    "epv_set_domain_stats", "epv_reset_domain_stats", "epv_accumulate_domain_stats", "epv_domain_stats_samples",
-    "epv_domain_stats_layout", "epv_get_domain_stats",
-    "epv_set_change_patterns", "epv_reset_change_patterns", "epv_accumulate_change_patterns",
-    "epv_change_patterns_samples", "epv_change_patterns_layout", "epv_get_change_patterns",
-    "epv_get_change_pattern_windows",
-    "epv_set_domain_turnover", "epv_reset_domain_turnover", "epv_accumulate_domain_turnover",
-    "epv_domain_turnover_samples", "epv_domain_turnover_layout", "epv_get_domain_turnover",
-    "epv_set_spatial_correlation", "epv_reset_spatial_correlation", "epv_accumulate_spatial_correlation",
-    "epv_spatial_correlation_samples", "epv_spatial_correlation_layout", "epv_get_spatial_correlation",
-]
+
+def _abi():
+    """the C ABI of include/epievo_mi355x.h, declared once: name -> (argtypes, restype)"""
+    i, u32, u64, vp = C.c_int, C.c_uint32, C.c_uint64, C.c_void_p
+    ip, dp, fp, u8p, u32p, u64p, i64p = (C.POINTER(t) for t in (C.c_int, C.c_double, C.c_float, C.c_uint8, C.c_uint32,
+                                                                C.c_uint64, C.c_int64))
+    args = {   # every entry point returns an EPV_* code (int) but those of `other` below
+        "epv_create": [i], "epv_destroy": [vp], "epv_last_error": [vp],
+        "epv_set_tree": [vp, i, u32p, u32p, dp], "epv_set_model": [vp, dp, dp],
+        "epv_upload_paths": [vp, u64, u8p, u64p, dp, u32, u64],
+        "epv_set_capacity": [vp, u32], "epv_get_capacity": [vp, u32p],
+        "epv_init_paths_indep": [vp, u64, u8p, u8p, u64, u32],
+        "epv_indep_expectation": [vp, dp, dp, dp], "epv_indep_sufficient_statistics": [vp, dp, dp],
+        "epv_indep_update_paths": [vp, dp, u64, u32], "epv_indep_node_posterior": [vp, dp, dp],
+        "epv_set_global_length": [vp, u64], "epv_set_update_range": [vp, u64, u64], "epv_set_halo": [vp, u64, u64],
+        "epv_halo_phases_left": [vp, u64p],
+        "epv_reset": [vp], "epv_reset_async": [vp],
+        "epv_sweep": [vp, u64, u64, u32, u64p], "epv_sweep_phase": [vp, i, u64, u32, u64p],
+        "epv_run_mcmc": [vp, u64, u64, u64, u32, dp, dp, u64p],
+        "epv_run_mcmc_sums": [vp, u64, u64, u64, u32, i, dp, dp, u64p],
+        "epv_get_sufficient_statistics": [vp, dp, dp], "epv_scale_jump_times": [vp, dp],
+        "epv_paths_total_jumps": [vp, u64p], "epv_download_paths": [vp, u8p, u64p, dp], "epv_get_tri_llh": [vp, dp],
+        "epv_column_bytes": [vp],
+        "epv_get_columns": [vp, u64, u64, vp], "epv_put_columns": [vp, u64, u64, vp],
+        "epv_copy_columns": [vp, u64, u64, vp, u64], "epv_copy_columns_async": [vp, u64, u64, vp, u64, i],
+        "epv_dev_alloc": [vp, u64, C.POINTER(vp)], "epv_dev_free": [vp, vp],
+        "epv_run_mcmc_counts": [vp, u64, u64, u64, u32, i64p, u64p], "epv_counts_to_stats": [vp, i64p, u64, i, dp, dp],
+        "epv_get_counters": [vp, C.POINTER(_Counters)], "epv_kernel_time_ms": [vp, dp, u64p], "epv_set_timing": [vp, i],
+        "epv_pack_columns_dev": [vp, u64, u64, vp], "epv_unpack_columns_dev": [vp, u64, u64, vp],
+        "epv_device_of": [vp], "epv_dev_write": [vp, vp, vp, u64], "epv_dev_read": [vp, vp, vp, u64],
+        "epv_set_options": [vp, u32], "epv_get_options": [vp, u32p],
+        "epv_phase_mode": [vp, u32p], "epv_phase_plan": [vp, u32p],
+        "epv_philox_kat": [vp, u64, u32, u32p, dp], "epv_math_kat": [vp, u32, u32, u32, dp, dp],
+        "epv_merge_kat": [vp, u32, u32p, dp, dp, u32p],
+        "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
+        "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
+        "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
+        # the summaries: what is particular to each (the four lifecycle entry points of each follow from SUMMARIES)
+        "epv_get_path_average": [vp, u64, u64, u32p], "epv_path_average_layout": [vp, u32p, u64p, u64p],
+        "epv_branch_events_set_samples": [vp, u64], "epv_branch_events_layout": [vp, u64p, u64p],
+        "epv_get_branch_events": [vp, u64, u64, u32p], "epv_get_branch_event_windows": [vp, u64, u64, u64, u64p],
+        "epv_window_stats_set_samples": [vp, u64], "epv_window_stats_scale_exps": [vp, ip],
+        "epv_window_stats_layout": [vp, u64p, u64p, u64p], "epv_get_window_stats": [vp, u64, u64, i64p],
+        "epv_window_counts_to_stats": [vp, i64p, u64, u64, dp, dp],
+        "epv_epoch_stats_set_samples": [vp, u64], "epv_epoch_stats_layout": [vp, u32p, u32p, ip, u64p],
+        "epv_get_epoch_stats": [vp, u64p],
+        "epv_lineage_origins_set_samples": [vp, u64], "epv_lineage_origins_layout": [vp, u32p, u32p, u64p, u64p],
+        "epv_lineage_origin_rows": [vp, u32p, u32p], "epv_lineage_origins_scale_exp": [vp, ip],
+        "epv_get_lineage_origins": [vp, u64, u64, u32p, u64p],
+        "epv_get_lineage_origin_windows": [vp, u64, u64, u64, u64p],
+        "epv_domain_stats_layout": [vp, u32p, u32p, u64p, u64p, u64p], "epv_get_domain_stats": [vp, u64p, u64p, u64p],
+        "epv_change_patterns_layout": [vp, u32p, u32p, u32p, u64p, u64p], "epv_get_change_patterns": [vp, u64, u64, u32p],
+        "epv_get_change_pattern_windows": [vp, u64, u64, u64, u64p],
+        "epv_domain_turnover_layout": [vp, u32p, u32p, u64p, u64p, u64p],
+        "epv_get_domain_turnover": [vp, u64p, u64p, u64p],
+        "epv_spatial_correlation_layout": [vp, u32p, u32p, u64p, u64p, u64p],
+        "epv_get_spatial_correlation": [vp, u64p, u64p],
+    }
+    # epv_set_<stem>: what switches the summary on, after the context
+    set_args = {"path_average": [u32], "branch_events": [i], "window_stats": [u64], "epoch_stats": [u32],
+                "lineage_origins": [i], "domain_stats": [u64], "change_patterns": [i], "domain_turnover": [u64],
+                "spatial_correlation": [u32, u64]}
+    for s in SUMMARIES:
+        args["epv_set_" + s.stem] = [vp] + set_args[s.stem]
+        args["epv_reset_" + s.stem] = args["epv_accumulate_" + s.stem] = [vp]
+        args["epv_%s_samples" % s.stem] = [vp, u64p]
+    other = {"epv_create": vp, "epv_destroy": None, "epv_last_error": C.c_char_p, "epv_column_bytes": u64}
+    return {name: (a, other.get(name, i)) for name, a in args.items()}
+
+
+ABI = _abi()
+ABI_SYMBOLS = list(ABI)
 
 # planes of the posterior branch-event maps (include/epievo_mi355x.h), in order
 BRANCH_EVENT_PLANES = ("end1", "net_gain", "net_loss", "changed", "gains", "losses")
@@ -92,135 +130,9 @@ def lib():
             raise RuntimeError("%s is missing: run `python -c 'import __graft_entry__ as g; "
                                "g.build()'` (hipcc --offload-arch=gfx950)" % path)
         L = C.CDLL(path)
-        dp, u8p, u32p, u64p, vp = (C.POINTER(C.c_double), C.POINTER(C.c_uint8),
-                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p)
-        L.epv_create.argtypes = [C.c_int]
-        L.epv_create.restype = vp
-        L.epv_destroy.argtypes = [vp]
-        L.epv_destroy.restype = None
-        L.epv_last_error.argtypes = [vp]
-        L.epv_last_error.restype = C.c_char_p
-        L.epv_set_tree.argtypes = [vp, C.c_int, u32p, u32p, dp]
-        L.epv_set_model.argtypes = [vp, dp, dp]
-        L.epv_upload_paths.argtypes = [vp, C.c_uint64, u8p, u64p, dp, C.c_uint32, C.c_uint64]
-        L.epv_set_capacity.argtypes = [vp, C.c_uint32]
-        L.epv_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32)]
-        L.epv_init_paths_indep.argtypes = [vp, C.c_uint64, u8p, u8p, C.c_uint64, C.c_uint32]
-        L.epv_indep_expectation.argtypes = [vp, dp, dp, dp]
-        L.epv_indep_sufficient_statistics.argtypes = [vp, dp, dp]
-        L.epv_indep_update_paths.argtypes = [vp, dp, C.c_uint64, C.c_uint32]
-        L.epv_indep_node_posterior.argtypes = [vp, dp, dp]
-        L.epv_set_global_length.argtypes = [vp, C.c_uint64]
-        L.epv_set_update_range.argtypes = [vp, C.c_uint64, C.c_uint64]
-        L.epv_set_halo.argtypes = [vp, C.c_uint64, C.c_uint64]
-        L.epv_halo_phases_left.argtypes = [vp, u64p]
-        L.epv_reset.argtypes = [vp]
-        L.epv_sweep.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, u64p]
-        L.epv_sweep_phase.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint32, u64p]
-        L.epv_run_mcmc.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, dp, dp, u64p]
-        L.epv_run_mcmc_sums.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, dp, dp, u64p]
-        L.epv_get_sufficient_statistics.argtypes = [vp, dp, dp]
-        L.epv_scale_jump_times.argtypes = [vp, dp]
-        L.epv_paths_total_jumps.argtypes = [vp, u64p]
-        L.epv_download_paths.argtypes = [vp, u8p, u64p, dp]
-        L.epv_get_tri_llh.argtypes = [vp, dp]
-        L.epv_column_bytes.argtypes = [vp]
-        L.epv_column_bytes.restype = C.c_uint64
-        L.epv_get_columns.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
-        L.epv_put_columns.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
-        L.epv_copy_columns.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64]
-        L.epv_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-        L.epv_dev_free.argtypes = [vp, vp]
-        L.epv_run_mcmc_counts.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
-                                          C.POINTER(C.c_int64), u64p]
-        L.epv_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_int, dp, dp]
-        L.epv_pack_columns_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
-        L.epv_unpack_columns_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
-        L.epv_device_of.argtypes = [vp]
-        L.epv_set_options.argtypes = [vp, C.c_uint32]
-        L.epv_forward_simulate.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint32,
-                                           C.POINTER(C.c_uint64)]
-        L.epv_forward_last_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.epv_get_options.argtypes = [vp, C.POINTER(C.c_uint32)]
-        L.epv_phase_mode.argtypes = [vp, C.POINTER(C.c_uint32)]
-        L.epv_phase_plan.argtypes = [vp, C.POINTER(C.c_uint32)]
-        L.epv_philox_kat.argtypes = [vp, C.c_uint64, C.c_uint32, u32p, dp]
-        L.epv_math_kat.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, dp, dp]
-        L.epv_merge_kat.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), dp, dp, C.POINTER(C.c_uint32)]
-        L.epv_set_unobserved.argtypes = [vp, u8p]
-        L.epv_unobserved_cells.argtypes = [vp, u64p]
-        L.epv_set_leaf_evidence.argtypes = [vp, C.POINTER(C.c_float)]
-        L.epv_leaf_evidence_cells.argtypes = [vp, u64p]
-        L.epv_dev_write.argtypes = [vp, vp, vp, C.c_uint64]
-        L.epv_dev_read.argtypes = [vp, vp, vp, C.c_uint64]
-        L.epv_get_counters.argtypes = [vp, C.POINTER(_Counters)]
-        L.epv_kernel_time_ms.argtypes = [vp, dp, u64p]
-        L.epv_set_timing.argtypes = [vp, C.c_int]
-        L.epv_set_path_average.argtypes = [vp, C.c_uint32]
-        L.epv_reset_path_average.argtypes = [vp]
-        L.epv_accumulate_path_average.argtypes = [vp]
-        L.epv_path_average_samples.argtypes = [vp, u64p]
-        L.epv_get_path_average.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
-        L.epv_path_average_layout.argtypes = [vp, u32p, u64p, u64p]
-        L.epv_set_branch_events.argtypes = [vp, C.c_int]
-        L.epv_reset_branch_events.argtypes = [vp]
-        L.epv_accumulate_branch_events.argtypes = [vp]
-        L.epv_branch_events_samples.argtypes = [vp, u64p]
-        L.epv_branch_events_set_samples.argtypes = [vp, C.c_uint64]
-        L.epv_branch_events_layout.argtypes = [vp, u64p, u64p]
-        L.epv_get_branch_events.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
-        L.epv_get_branch_event_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
-        L.epv_set_window_stats.argtypes = [vp, C.c_uint64]
-        L.epv_reset_window_stats.argtypes = [vp]
-        L.epv_accumulate_window_stats.argtypes = [vp]
-        L.epv_window_stats_samples.argtypes = [vp, u64p]
-        L.epv_window_stats_set_samples.argtypes = [vp, C.c_uint64]
-        L.epv_window_stats_scale_exps.argtypes = [vp, C.POINTER(C.c_int)]
-        L.epv_window_stats_layout.argtypes = [vp, u64p, u64p, u64p]
-        L.epv_get_window_stats.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64)]
-        L.epv_window_counts_to_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, dp, dp]
-        L.epv_set_epoch_stats.argtypes = [vp, C.c_uint32]
-        L.epv_reset_epoch_stats.argtypes = [vp]
-        L.epv_accumulate_epoch_stats.argtypes = [vp]
-        L.epv_epoch_stats_samples.argtypes = [vp, u64p]
-        L.epv_epoch_stats_set_samples.argtypes = [vp, C.c_uint64]
-        L.epv_epoch_stats_layout.argtypes = [vp, u32p, u32p, C.POINTER(C.c_int), u64p]
-        L.epv_get_epoch_stats.argtypes = [vp, u64p]
-        L.epv_set_lineage_origins.argtypes = [vp, C.c_int]
-        L.epv_reset_lineage_origins.argtypes = [vp]
-        L.epv_accumulate_lineage_origins.argtypes = [vp]
-        L.epv_lineage_origins_samples.argtypes = [vp, u64p]
-        L.epv_lineage_origins_set_samples.argtypes = [vp, C.c_uint64]
-        L.epv_lineage_origins_layout.argtypes = [vp, u32p, u32p, u64p, u64p]
-        L.epv_lineage_origin_rows.argtypes = [vp, u32p, u32p]
-        L.epv_lineage_origins_scale_exp.argtypes = [vp, C.POINTER(C.c_int)]
-        L.epv_get_lineage_origins.argtypes = [vp, C.c_uint64, C.c_uint64, u32p, u64p]
-        L.epv_get_lineage_origin_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
-        L.epv_set_domain_stats.argtypes = [vp, C.c_uint64]
-        L.epv_reset_domain_stats.argtypes = [vp]
-        L.epv_accumulate_domain_stats.argtypes = [vp]
-        L.epv_domain_stats_samples.argtypes = [vp, u64p]
-        L.epv_domain_stats_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
-        L.epv_get_domain_stats.argtypes = [vp, u64p, u64p, u64p]
-        L.epv_set_domain_turnover.argtypes = [vp, C.c_uint64]
-        L.epv_reset_domain_turnover.argtypes = [vp]
-        L.epv_accumulate_domain_turnover.argtypes = [vp]
-        L.epv_domain_turnover_samples.argtypes = [vp, u64p]
-        L.epv_domain_turnover_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
-        L.epv_get_domain_turnover.argtypes = [vp, u64p, u64p, u64p]
-        L.epv_set_spatial_correlation.argtypes = [vp, C.c_uint32, C.c_uint64]
-        L.epv_reset_spatial_correlation.argtypes = [vp]
-        L.epv_accumulate_spatial_correlation.argtypes = [vp]
-        L.epv_spatial_correlation_samples.argtypes = [vp, u64p]
-        L.epv_spatial_correlation_layout.argtypes = [vp, u32p, u32p, u64p, u64p, u64p]
-        L.epv_get_spatial_correlation.argtypes = [vp, u64p, u64p]
-        L.epv_set_change_patterns.argtypes = [vp, C.c_int]
-        L.epv_reset_change_patterns.argtypes = [vp]
-        L.epv_accumulate_change_patterns.argtypes = [vp]
-        L.epv_change_patterns_samples.argtypes = [vp, u64p]
-        L.epv_change_patterns_layout.argtypes = [vp, u32p, u32p, u32p, u64p, u64p]
-        L.epv_get_change_patterns.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
-        L.epv_get_change_pattern_windows.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+        for name, (argtypes, restype) in ABI.items():
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = argtypes, restype
         _lib = L
     return _lib
 
@@ -291,6 +203,27 @@ class DeviceSampler:
                 self.capacity_events.append(msg)
                 return
         self._ck(rc)
+
+    def _u64(self, fn):
+        """an entry point whose one result is a uint64 out-parameter"""
+        v = C.c_uint64(0)
+        self._ck(fn(self.h, C.byref(v)))
+        return int(v.value)
+
+    def _window_range(self, W, first_window, n_windows):
+        """(W, number of windows) of a read-out per window: all windows of the genome unless a range is given"""
+        return _window_range(W, max(self.n_global, self.n_sites), first_window, n_windows)
+
+    # what every summary has besides enable_<stem>, its layout and its read-outs: reset_<stem>, accumulate_<stem>
+    # and <stem>_samples are made of these three, one set per row of SUMMARIES (below the class)
+    def _reset_summary(self, s):
+        self._ck(getattr(self.L, "epv_reset_" + s.stem)(self.h))
+
+    def _accumulate_summary(self, s):
+        self._ck(getattr(self.L, "epv_accumulate_" + s.stem)(self.h))
+
+    def _summary_samples(self, s):
+        return self._u64(getattr(self.L, "epv_%s_samples" % s.stem))
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
         """see EPV_OPT_* in include/epievo_mi355x.h"""
@@ -387,9 +320,7 @@ class DeviceSampler:
 
     def unobserved_cells(self):
         """the number of leaf cells flagged unobserved (epv_unobserved_cells)"""
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_unobserved_cells(self.h, C.byref(v)))
-        return int(v.value)
+        return self._u64(self.L.epv_unobserved_cells)
 
     def set_leaf_evidence(self, p_state1):
         """leaf evidence (epv_set_leaf_evidence): p_state1[b-1, s] = P(the leaf end state of branch b at local
@@ -408,9 +339,7 @@ class DeviceSampler:
 
     def leaf_evidence_cells(self):
         """the number of leaf cells that hold evidence (epv_leaf_evidence_cells)"""
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_leaf_evidence_cells(self.h, C.byref(v)))
-        return int(v.value)
+        return self._u64(self.L.epv_leaf_evidence_cells)
 
     def capacity(self):
         v = C.c_uint32(0)
@@ -504,9 +433,7 @@ class DeviceSampler:
         self.halo = (int(left), int(right))
 
     def halo_phases_left(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_halo_phases_left(self.h, C.byref(v)))
-        return int(v.value)
+        return self._u64(self.L.epv_halo_phases_left)
 
     def reset(self):
         self._ck(self.L.epv_reset(self.h))
@@ -633,18 +560,6 @@ class DeviceSampler:
         run_mcmc (0 = off)"""
         self._ck(self.L.epv_set_path_average(self.h, int(n_points)))
 
-    def reset_path_average(self):
-        self._ck(self.L.epv_reset_path_average(self.h))
-
-    def accumulate_path_average(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_path_average(self.h))
-
-    def path_average_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_path_average_samples(self.h, C.byref(v)))
-        return int(v.value)
-
     def path_average_layout(self):
         """(points, first local site, number of sites) of the counts; points = 0: averaging is off.
         A context counts its owned sites plus the genome's end sites when it holds them"""
@@ -665,25 +580,13 @@ class DeviceSampler:
             self._ck(self.L.epv_get_path_average(self.h, first + a, k, _p(buf, C.c_uint32)))
             out[:, a:a + k] = buf
         ns = self.path_average_samples()
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     # ---- posterior branch-event maps (epv_set_branch_events)
     def enable_branch_events(self, on=True):
         """count end states, net and total gains and losses per (branch, site) after every batch sweep
         of run_mcmc (BRANCH_EVENT_PLANES; False = off)"""
         self._ck(self.L.epv_set_branch_events(self.h, 1 if on else 0))
-
-    def reset_branch_events(self):
-        self._ck(self.L.epv_reset_branch_events(self.h))
-
-    def accumulate_branch_events(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_branch_events(self.h))
-
-    def branch_events_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_branch_events_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def branch_events_layout(self):
         """(first local site, number of sites) of the planes: the sites of path_average_layout"""
@@ -697,18 +600,14 @@ class DeviceSampler:
         out = np.zeros((len(BRANCH_EVENT_PLANES), self.B, cnt), np.uint32)
         self._ck(self.L.epv_get_branch_events(self.h, first, cnt, _p(out, C.c_uint32)))
         ns = self.branch_events_samples()
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     def branch_event_windows(self, W, first_window=0, n_windows=None):
         """-> (samples, uint64 [6, N-1, windows]): the planes summed over windows of W consecutive global
         sites, this context's contribution (zero where it counts no site); all windows of the genome
         unless a range is given"""
-        W = int(W)
-        if W < 1:
-            raise ValueError("a window holds at least one site")
-        if n_windows is None:
-            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
-        out = np.zeros((len(BRANCH_EVENT_PLANES), self.B, max(int(n_windows), 0)), np.uint64)
+        W, n_windows = self._window_range(W, first_window, n_windows)
+        out = np.zeros((len(BRANCH_EVENT_PLANES), self.B, n_windows), np.uint64)
         self._ck(self.L.epv_get_branch_event_windows(self.h, W, int(first_window), out.shape[2], _p(out, C.c_uint64)))
         return self.branch_events_samples(), out
 
@@ -718,18 +617,6 @@ class DeviceSampler:
         parallel and reverted changes, sole gains and losses per branch, changed clades -- after every batch
         sweep of run_mcmc (CHANGE_PATTERN_ROWS; False = off)"""
         self._ck(self.L.epv_set_change_patterns(self.h, 1 if on else 0))
-
-    def reset_change_patterns(self):
-        self._ck(self.L.epv_reset_change_patterns(self.h))
-
-    def accumulate_change_patterns(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_change_patterns(self.h))
-
-    def change_patterns_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_change_patterns_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def change_patterns_layout(self):
         """(rows R, clade nodes [I], first local site, number of sites): R = 12 + 2 (N-1) + I, the clade nodes
@@ -746,17 +633,13 @@ class DeviceSampler:
         out = np.zeros((R, cnt), np.uint32)
         self._ck(self.L.epv_get_change_patterns(self.h, first, cnt, _p(out, C.c_uint32)))
         ns = self.change_patterns_samples()
-        return ns, (out if counts else out / float(ns) if ns else out.astype(np.float64))
+        return ns, _per_sample(out, ns, counts)
 
     def change_pattern_windows(self, W, first_window=0, n_windows=None):
         """-> (samples, uint64 [R, windows]): the rows summed over windows of W consecutive global sites, this
         context's contribution (zero where it counts no site); all windows of the genome unless a range is given"""
-        W = int(W)
-        if W < 1:
-            raise ValueError("a window holds at least one site")
-        if n_windows is None:
-            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
-        out = np.zeros((self.change_patterns_layout()[0], max(int(n_windows), 0)), np.uint64)
+        W, n_windows = self._window_range(W, first_window, n_windows)
+        out = np.zeros((self.change_patterns_layout()[0], n_windows), np.uint64)
         self._ck(self.L.epv_get_change_pattern_windows(self.h, W, int(first_window), out.shape[1], _p(out, C.c_uint64)))
         return self.change_patterns_samples(), out
 
@@ -767,18 +650,6 @@ class DeviceSampler:
         if W < 0:
             raise ValueError("a window holds at least one site (0 turns the statistics off)")
         self._ck(self.L.epv_set_window_stats(self.h, W))
-
-    def reset_window_stats(self):
-        self._ck(self.L.epv_reset_window_stats(self.h))
-
-    def accumulate_window_stats(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_window_stats(self.h))
-
-    def window_stats_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_window_stats_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def window_stats_layout(self):
         """(W as clamped, first global window, number of windows) this context holds; (0, 0, 0) when off"""
@@ -798,9 +669,7 @@ class DeviceSampler:
         W = self.window_stats_layout()[0]
         if not W:
             self._ck(self.L.epv_get_window_stats(self.h, 0, 0, None))     # off: EPV_ERR_STATE
-        if n_windows is None:
-            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
-        out = np.zeros((max(int(n_windows), 0), self.B, 16), np.int64)
+        out = np.zeros((self._window_range(W, first_window, n_windows)[1], self.B, 16), np.int64)
         self._ck(self.L.epv_get_window_stats(self.h, int(first_window), out.shape[0], _p(out, C.c_int64)))
         return self.window_stats_samples(), out
 
@@ -828,18 +697,6 @@ class DeviceSampler:
         """count, per leaf and site, on which branch of the leaf's lineage the sampled history last changed
         state, and the age of the leaf's state, after every batch sweep of run_mcmc (False = off)"""
         self._ck(self.L.epv_set_lineage_origins(self.h, 1 if on else 0))
-
-    def reset_lineage_origins(self):
-        self._ck(self.L.epv_reset_lineage_origins(self.h))
-
-    def accumulate_lineage_origins(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_lineage_origins(self.h))
-
-    def lineage_origins_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_lineage_origins_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def lineage_origins_layout(self):
         """(leaves L, rows R, first local site, number of sites); zeros when off"""
@@ -879,13 +736,9 @@ class DeviceSampler:
         """-> (samples, uint64 [R, windows], uint64 [L, windows]): the origin rows and the ages summed over
         windows of W consecutive global sites, this context's contribution (zero where it counts no site);
         all windows of the genome unless a range is given"""
-        W = int(W)
-        if W < 1:
-            raise ValueError("a window holds at least one site")
-        if n_windows is None:
-            n_windows = (max(self.n_global, self.n_sites) + W - 1) // W - first_window
+        W, n_windows = self._window_range(W, first_window, n_windows)
         L, R = self.lineage_origins_layout()[:2]
-        out = np.zeros((R + L, max(int(n_windows), 0)), np.uint64)
+        out = np.zeros((R + L, n_windows), np.uint64)
         self._ck(self.L.epv_get_lineage_origin_windows(self.h, W, int(first_window), out.shape[1], _p(out, C.c_uint64)))
         return self.lineage_origins_samples(), out[:R], out[R:]
 
@@ -895,18 +748,6 @@ class DeviceSampler:
         """count the run lengths of every node's state along the genome after every batch sweep of run_mcmc, for
         at most max_samples samples (0 = off)"""
         self._ck(self.L.epv_set_domain_stats(self.h, int(max_samples)))
-
-    def reset_domain_stats(self):
-        self._ck(self.L.epv_reset_domain_stats(self.h))
-
-    def accumulate_domain_stats(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_domain_stats(self.h))
-
-    def domain_stats_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_domain_stats_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def domain_stats_layout(self):
         """(nodes N, bins, first local site, number of sites, sites per block of the runs kernel); zeros when off"""
@@ -936,18 +777,6 @@ class DeviceSampler:
         """count, per branch, the runs of the state at its start and at its end along the genome, each kept or
         turned over, after every batch sweep of run_mcmc, for at most max_samples samples (0 = off)"""
         self._ck(self.L.epv_set_domain_turnover(self.h, int(max_samples)))
-
-    def reset_domain_turnover(self):
-        self._ck(self.L.epv_reset_domain_turnover(self.h))
-
-    def accumulate_domain_turnover(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_domain_turnover(self.h))
-
-    def domain_turnover_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_domain_turnover_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def domain_turnover_layout(self):
         """(rows R = 2 B, bins, first local site, number of sites, sites per block of the runs kernel); zeros when off"""
@@ -979,18 +808,6 @@ class DeviceSampler:
         d = 0 .. max_lag (at most 1024) after every batch sweep of run_mcmc, for at most max_samples samples
         (max_lag = 0: off)"""
         self._ck(self.L.epv_set_spatial_correlation(self.h, int(max_lag), int(max_samples)))
-
-    def reset_spatial_correlation(self):
-        self._ck(self.L.epv_reset_spatial_correlation(self.h))
-
-    def accumulate_spatial_correlation(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_spatial_correlation(self.h))
-
-    def spatial_correlation_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_spatial_correlation_samples(self.h, C.byref(v)))
-        return int(v.value)
 
     def spatial_correlation_layout(self):
         """(rows R = N + B, max_lag, first local site, number of sites, sites per block of the count kernel); zeros
@@ -1025,18 +842,6 @@ class DeviceSampler:
             raise ValueError("1 .. %d epochs per branch (0 turns the statistics off)" % EPOCH_MAX_P)
         self._ck(self.L.epv_set_epoch_stats(self.h, P))
 
-    def reset_epoch_stats(self):
-        self._ck(self.L.epv_reset_epoch_stats(self.h))
-
-    def accumulate_epoch_stats(self):
-        """the resident paths as one more sample (for callers that drive sweep() themselves)"""
-        self._ck(self.L.epv_accumulate_epoch_stats(self.h))
-
-    def epoch_stats_samples(self):
-        v = C.c_uint64(0)
-        self._ck(self.L.epv_epoch_stats_samples(self.h, C.byref(v)))
-        return int(v.value)
-
     def epoch_stats_layout(self):
         """(P, k_b int[N-1], fixT_b uint64[N-1]) of the accumulator's samples; (0, [], []) when off"""
         B, P = C.c_uint32(0), C.c_uint32(0)
@@ -1060,6 +865,27 @@ class DeviceSampler:
         ns, raw = self.epoch_raw()
         _, k, fixT = self.epoch_stats_layout()
         return host.epoch_finish(raw, fixT, k, ns, counts)
+
+
+for _s in SUMMARIES:
+    setattr(DeviceSampler, "reset_" + _s.stem, summary_method(DeviceSampler._reset_summary, _s, "reset_" + _s.stem))
+    setattr(DeviceSampler, "accumulate_" + _s.stem,
+            summary_method(DeviceSampler._accumulate_summary, _s, "accumulate_" + _s.stem,
+                           "the resident paths as one more sample (for callers that drive sweep() themselves)"))
+    setattr(DeviceSampler, _s.stem + "_samples",
+            summary_method(DeviceSampler._summary_samples, _s, _s.stem + "_samples"))
+
+
+def forward_to_dev(cls, names):
+    """give cls the methods `names` of DeviceSampler, each forwarding to self.dev (resolved by name at call time: a
+    LocalGroup or a test's stand-in serves as well) under DeviceSampler's signature and docstring"""
+    def make(name):
+        @functools.wraps(getattr(DeviceSampler, name))
+        def method(self, *args, **kwargs):
+            return getattr(self.dev, name)(*args, **kwargs)
+        return method
+    for name in names:
+        setattr(cls, name, make(name))
 
 
 class SingleSiteSampler:
@@ -1137,182 +963,11 @@ class SingleSiteSampler:
         self._apply_sample_root()
         return self.dev.sweep(n, seed, sweep_base)
 
-    def scale_jump_times(self, new_branches):
-        self.dev.scale_jump_times(new_branches)
 
-    def paths(self):
-        return self.dev.paths()
-
-    # average history of the sampled paths (DeviceSampler.enable_path_average)
-    def enable_path_average(self, n_points):
-        self.dev.enable_path_average(n_points)
-
-    def reset_path_average(self):
-        self.dev.reset_path_average()
-
-    def accumulate_path_average(self):
-        self.dev.accumulate_path_average()
-
-    def path_average(self, counts=False):
-        return self.dev.path_average(counts)
-
-    # posterior branch-event maps (DeviceSampler.enable_branch_events)
-    def enable_branch_events(self, on=True):
-        self.dev.enable_branch_events(on)
-
-    def reset_branch_events(self):
-        self.dev.reset_branch_events()
-
-    def accumulate_branch_events(self):
-        self.dev.accumulate_branch_events()
-
-    def branch_events(self, counts=False):
-        return self.dev.branch_events(counts)
-
-    def branch_event_windows(self, W):
-        return self.dev.branch_event_windows(W)
-
-    # regional sufficient statistics (DeviceSampler.enable_window_stats)
-    def enable_window_stats(self, W):
-        self.dev.enable_window_stats(W)
-
-    def reset_window_stats(self):
-        self.dev.reset_window_stats()
-
-    def accumulate_window_stats(self):
-        self.dev.accumulate_window_stats()
-
-    def window_stats(self, counts=False):
-        return self.dev.window_stats(counts)
-
-    # lineage origin maps (DeviceSampler.enable_lineage_origins)
-    def enable_lineage_origins(self, on=True):
-        self.dev.enable_lineage_origins(on)
-
-    def reset_lineage_origins(self):
-        self.dev.reset_lineage_origins()
-
-    def accumulate_lineage_origins(self):
-        self.dev.accumulate_lineage_origins()
-
-    def lineage_origins_samples(self):
-        return self.dev.lineage_origins_samples()
-
-    def lineage_origins_layout(self):
-        return self.dev.lineage_origins_layout()
-
-    def lineage_origin_rows(self):
-        return self.dev.lineage_origin_rows()
-
-    def lineage_origins(self, counts=False):
-        return self.dev.lineage_origins(counts)
-
-    def lineage_origins_scale_exp(self):
-        return self.dev.lineage_origins_scale_exp()
-
-    def lineage_origin_windows(self, W, first_window=0, n_windows=None):
-        return self.dev.lineage_origin_windows(W, first_window, n_windows)
-
-    # domain size spectra (DeviceSampler.enable_domain_stats)
-    def enable_domain_stats(self, max_samples):
-        self.dev.enable_domain_stats(max_samples)
-
-    def reset_domain_stats(self):
-        self.dev.reset_domain_stats()
-
-    def accumulate_domain_stats(self):
-        self.dev.accumulate_domain_stats()
-
-    def domain_stats_samples(self):
-        return self.dev.domain_stats_samples()
-
-    def domain_stats_layout(self):
-        return self.dev.domain_stats_layout()
-
-    def domain_stats_part(self):
-        return self.dev.domain_stats_part()
-
-    def domain_stats(self):
-        return self.dev.domain_stats()
-
-    # domain turnover (DeviceSampler.enable_domain_turnover)
-    def enable_domain_turnover(self, max_samples):
-        self.dev.enable_domain_turnover(max_samples)
-
-    def reset_domain_turnover(self):
-        self.dev.reset_domain_turnover()
-
-    def accumulate_domain_turnover(self):
-        self.dev.accumulate_domain_turnover()
-
-    def domain_turnover_samples(self):
-        return self.dev.domain_turnover_samples()
-
-    def domain_turnover_layout(self):
-        return self.dev.domain_turnover_layout()
-
-    def domain_turnover_part(self):
-        return self.dev.domain_turnover_part()
-
-    def domain_turnover(self):
-        return self.dev.domain_turnover()
-
-    # spatial correlations (DeviceSampler.enable_spatial_correlation)
-    def enable_spatial_correlation(self, max_lag, max_samples):
-        self.dev.enable_spatial_correlation(max_lag, max_samples)
-
-    def reset_spatial_correlation(self):
-        self.dev.reset_spatial_correlation()
-
-    def accumulate_spatial_correlation(self):
-        self.dev.accumulate_spatial_correlation()
-
-    def spatial_correlation_samples(self):
-        return self.dev.spatial_correlation_samples()
-
-    def spatial_correlation_layout(self):
-        return self.dev.spatial_correlation_layout()
-
-    def spatial_correlation_part(self):
-        return self.dev.spatial_correlation_part()
-
-    def spatial_correlation(self):
-        return self.dev.spatial_correlation()
-
-    # change patterns (DeviceSampler.enable_change_patterns)
-    def enable_change_patterns(self, on=True):
-        self.dev.enable_change_patterns(on)
-
-    def reset_change_patterns(self):
-        self.dev.reset_change_patterns()
-
-    def accumulate_change_patterns(self):
-        self.dev.accumulate_change_patterns()
-
-    def change_patterns_samples(self):
-        return self.dev.change_patterns_samples()
-
-    def change_patterns_layout(self):
-        return self.dev.change_patterns_layout()
-
-    def change_patterns(self, counts=False):
-        return self.dev.change_patterns(counts)
-
-    def change_pattern_windows(self, W):
-        return self.dev.change_pattern_windows(W)
-
-    # epoch statistics (DeviceSampler.enable_epoch_stats)
-    def enable_epoch_stats(self, P):
-        self.dev.enable_epoch_stats(P)
-
-    def reset_epoch_stats(self):
-        self.dev.reset_epoch_stats()
-
-    def accumulate_epoch_stats(self):
-        self.dev.accumulate_epoch_stats()
-
-    def epoch_stats_samples(self):
-        return self.dev.epoch_stats_samples()
-
-    def epoch_stats(self, counts=False):
-        return self.dev.epoch_stats(counts)
+# everything else is DeviceSampler's: the four lifecycle methods of every summary, and
+forward_to_dev(SingleSiteSampler, LIFECYCLE + [
+    "scale_jump_times", "paths", "path_average", "branch_events", "branch_event_windows", "window_stats", "epoch_stats",
+    "lineage_origins_layout", "lineage_origin_rows", "lineage_origins_scale_exp", "lineage_origins",
+    "lineage_origin_windows", "domain_stats_layout", "domain_stats_part", "domain_stats", "change_patterns_layout",
+    "change_patterns", "change_pattern_windows", "domain_turnover_layout", "domain_turnover_part", "domain_turnover",
+    "spatial_correlation_layout", "spatial_correlation_part", "spatial_correlation"])
