@@ -254,9 +254,11 @@ template <bool ASM_MUL = true>
 __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
                                                      const EpvSegOut *outs, unsigned long long bt, uint64_t first,
                                                      uint64_t s0, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
-                                                     bool nielsen, epv_meta_t *prop_meta = nullptr, uint64_t site_lane0 = 0) {
+                                                     bool nielsen, epv_meta_t *prop_meta = nullptr, uint64_t site_lane0 = 0,
+                                                     uint32_t *flag_lds = nullptr) {
   // prop_meta (fused phase): the wave's LDS column [branch][lane] of proposal meta words; the
   // assembled branch's word goes to its owner's entry, where the acceptance stage picks it up
+  // flag_lds (fused small-tree bodies): the wave's overflow flags, one LDS word per lane, instead of S.prop_flag
   const uint64_t n = S.n;
   const uint32_t B = S.B, C = S.C;
   const uint64_t site = bt & 0xffffffffffull;
@@ -290,7 +292,8 @@ __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const doub
   }
   if (ovf) {
     cnt = (start_state ^ end_state) & 1u;         // keep the end-state parity; the proposal is rejected
-    S.prop_flag[(site - s0) / 3u] = 1u;
+    if (flag_lds) flag_lds[(uint32_t)((site - site_lane0) / 3u)] = 1u;
+    else S.prop_flag[(site - s0) / 3u] = 1u;
   }
   *meta = (epv_meta_t)((start_state << EPV_INIT_SHIFT) | cnt);
   if (prop_meta) prop_meta[b * 64u + (uint32_t)((site - site_lane0) / 3u)] = (epv_meta_t)((start_state << EPV_INIT_SHIFT) | cnt);

@@ -290,46 +290,14 @@ __device__ __forceinline__ double triple_llh(const EpvDev &S, const double *s_mo
 // col = the column's index in the caller's cache): the accept kernel fetches the 5 B words a
 // site needs in ONE batch of independent loads instead of paying a dependent global round trip
 // per branch and triple (it is bound by memory latency: SQ_WAIT_ANY was 70 % of its wave cycles)
-// NB > 0: the branch count as a compile-time constant (the small-tree fused phase)
-template <int NB = 0, class ACC>
+template <class ACC>
 __device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const double *s_model,
                                                     const double *s_blen, const epv_meta_t *mc, uint32_t stride,
                                                     uint32_t cl, uint32_t bl, uint64_t sl, uint32_t cm, uint32_t bm,
                                                     uint64_t sm, uint32_t cr, uint32_t br, uint64_t sr, ACC &A) {
   acc_clear(A);
   uint32_t rl = 0, rm = 0, rr = 0;
-  const uint32_t B = NB ? (uint32_t)NB : S.B;
-  if constexpr (NB > 0) {
-    // the counts of all 3 NB columns are in LDS and their addresses known: the first jump of every
-    // column that has one leaves in ONE batch of predicated loads, and the merges start from loaded
-    // values -- one round trip for the triple instead of one per branch (a wave of task lanes nearly
-    // always has a jump somewhere on every branch)
-    const uint64_t n = S.n, Cn = (uint64_t)S.C * n;
-    const double *jl = S.jumps + ((bl ? (uint64_t)B * Cn : 0ull) + sl);
-    const double *jm = S.jumps + ((bm ? (uint64_t)B * Cn : 0ull) + sm);
-    const double *jr = S.jumps + ((br ? (uint64_t)B * Cn : 0ull) + sr);
-    uint32_t wl[NB], wm[NB], wr[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      wl[b] = mc[(cl * B + b) * stride]; wm[b] = mc[(cm * B + b) * stride]; wr[b] = mc[(cr * B + b) * stride];
-    }
-    double tl[NB], tm[NB], tr[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      tl[b] = (wl[b] & EPV_NJ_MASK) ? jl[(uint64_t)b * Cn] : EPV_INF;
-      tm[b] = (wm[b] & EPV_NJ_MASK) ? jm[(uint64_t)b * Cn] : EPV_INF;
-      tr[b] = (wr[b] & EPV_NJ_MASK) ? jr[(uint64_t)b * Cn] : EPV_INF;
-    }
-    rl = wl[0] >> EPV_INIT_SHIFT; rm = wm[0] >> EPV_INIT_SHIFT; rr = wr[0] >> EPV_INIT_SHIFT;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      PathRef L, M, R;
-      L.j = jl + (uint64_t)b * Cn; L.nj = wl[b] & EPV_NJ_MASK; L.init = wl[b] >> EPV_INIT_SHIFT;
-      M.j = jm + (uint64_t)b * Cn; M.nj = wm[b] & EPV_NJ_MASK; M.init = wm[b] >> EPV_INIT_SHIFT;
-      R.j = jr + (uint64_t)b * Cn; R.nj = wr[b] & EPV_NJ_MASK; R.init = wr[b] >> EPV_INIT_SHIFT;
-      merge3_sel(L, M, R, tl[b], tm[b], tr[b], n, s_blen[b + 1], A);
-    }
-  } else
+  const uint32_t B = S.B;
   for (uint32_t b = 0; b < B; ++b) {
     const uint32_t ml = mc[(cl * B + b) * stride], mm = mc[(cm * B + b) * stride], mr = mc[(cr * B + b) * stride];
     PathRef L, M, R;
@@ -338,6 +306,57 @@ __device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const doubl
     R.j = S.jumps + jump_idx(S, br, b, sr); R.nj = mr & EPV_NJ_MASK; R.init = mr >> EPV_INIT_SHIFT;
     if (b == 0) { rl = L.init; rm = M.init; rr = R.init; }
     merge3(L, M, R, S.n, s_blen[b + 1], A);
+  }
+  const double *rates = s_model, *lrates = s_model + 8, *T = s_model + 16;
+  double llh = T[2 * rl + rm] * T[2 * rm + rr];
+  double s = 0.0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) s += (double)acc_j(A, c) * lrates[c] - acc_d(A, c) * rates[c];
+  llh += s;
+  return llh;
+}
+
+// triple_llh_cached<NB > 0>: the branch count as a compile-time constant (the small-tree fused phase), and
+// the words read IN PLACE: the word of branch b of the left / middle / right column is lds[il + b stl],
+// lds[im + b stm], lds[ir + b str] -- whatever rows of the caller's LDS hold the three columns, no copy into
+// a cache of the lane's own first.
+template <int NB, class ACC>
+__device__ __forceinline__ double triple_llh_cached(const EpvDev &S, const double *s_model,
+                                                    const double *s_blen, const epv_meta_t *lds,
+                                                    uint32_t il, uint32_t stl, uint32_t bl, uint64_t sl,
+                                                    uint32_t im, uint32_t stm, uint32_t bm, uint64_t sm,
+                                                    uint32_t ir, uint32_t str, uint32_t br, uint64_t sr, ACC &A) {
+  static_assert(NB > 0, "the branch count of a small-tree body");
+  acc_clear(A);
+  constexpr uint32_t B = (uint32_t)NB;
+  // the counts of all 3 NB columns are in LDS and their addresses known: the first jump of every
+  // column that has one leaves in ONE batch of predicated loads, and the merges start from loaded
+  // values -- one round trip for the triple instead of one per branch (a wave of task lanes nearly
+  // always has a jump somewhere on every branch)
+  const uint64_t n = S.n, Cn = (uint64_t)S.C * n;
+  const double *jl = S.jumps + ((bl ? (uint64_t)B * Cn : 0ull) + sl);
+  const double *jm = S.jumps + ((bm ? (uint64_t)B * Cn : 0ull) + sm);
+  const double *jr = S.jumps + ((br ? (uint64_t)B * Cn : 0ull) + sr);
+  uint32_t wl[NB], wm[NB], wr[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    wl[b] = lds[il + (uint32_t)b * stl]; wm[b] = lds[im + (uint32_t)b * stm]; wr[b] = lds[ir + (uint32_t)b * str];
+  }
+  double tl[NB], tm[NB], tr[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    tl[b] = (wl[b] & EPV_NJ_MASK) ? jl[(uint64_t)b * Cn] : EPV_INF;
+    tm[b] = (wm[b] & EPV_NJ_MASK) ? jm[(uint64_t)b * Cn] : EPV_INF;
+    tr[b] = (wr[b] & EPV_NJ_MASK) ? jr[(uint64_t)b * Cn] : EPV_INF;
+  }
+  const uint32_t rl = wl[0] >> EPV_INIT_SHIFT, rm = wm[0] >> EPV_INIT_SHIFT, rr = wr[0] >> EPV_INIT_SHIFT;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    PathRef L, M, R;
+    L.j = jl + (uint64_t)b * Cn; L.nj = wl[b] & EPV_NJ_MASK; L.init = wl[b] >> EPV_INIT_SHIFT;
+    M.j = jm + (uint64_t)b * Cn; M.nj = wm[b] & EPV_NJ_MASK; M.init = wm[b] >> EPV_INIT_SHIFT;
+    R.j = jr + (uint64_t)b * Cn; R.nj = wr[b] & EPV_NJ_MASK; R.init = wr[b] >> EPV_INIT_SHIFT;
+    merge3_sel(L, M, R, tl[b], tm[b], tr[b], n, s_blen[b + 1], A);
   }
   const double *rates = s_model, *lrates = s_model + 8, *T = s_model + 16;
   double llh = T[2 * rl + rm] * T[2 * rm + rr];

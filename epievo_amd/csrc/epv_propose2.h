@@ -500,7 +500,9 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         const uint32_t b = node - 1u;
         const uint32_t mL = s_meta[(0u * B + b) * 64u + lane], mR = s_meta[(1u * B + b) * 64u + lane];
         const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
-        const uint32_t sub = S.subtree[node];
+        // SMALL: the tree's shape from the topology word -- no load on the chain.  (S.subtree[] is
+        // wave-uniform, yet the compiler fetched it with a vector load and a full wait per node and child.)
+        const uint32_t sub = SMALL ? 2u - EPV_TOPO_LEAF(node) : S.subtree[node];     // (SMALL: 1 = a leaf, that is all it says)
         off -= K + (sub != 1u ? 1u : 0u);
         double n0 = 1.0, n1 = 1.0;
         if (sub == 1u) {
@@ -509,6 +511,16 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           n0 = leaf_state ? 0.0 : 1.0;
           n1 = leaf_state ? 1.0 : 0.0;
         } else {
+          if constexpr (SMALL) {
+            // the children are the later nodes whose parent this is, in ascending order: the order of
+            // the stride walk below, so the products take their factors in the same order
+            for (uint32_t c = node + 1u; c < NNODE; ++c) {
+              if (EPV_TOPO_PARENT(c) != node) continue;
+              const double *a = my + (size_t)(regA[c * 64u + lane] & 0x3fffffffu) * RS;
+              n0 *= a[0];
+              n1 *= a[1];
+            }
+          } else
           for (uint32_t ch = 1u; ch < sub; ch += S.subtree[node + ch]) {
             const double *a = my + (size_t)(regA[(node + ch) * 64u + lane] & 0x3fffffffu) * RS;
             n0 *= a[0];   // p.front() of the child's branch
@@ -790,7 +802,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           if (EPV_TOPO_PARENT(node) == (uint32_t)p) st = r_node[p] >> 31;
         S.meta[(selM ? 0ull : Bn) + (uint64_t)(node - 1) * n + site] = (epv_meta_t)(st << EPV_INIT_SHIFT);
       }
-      S.prop_flag[tid] = 0u;
+      // (the overflow flag of a small-tree body stays in the wave: cleared behind the rounds, below)
     } else if (!SMALL && to_list) {
       for (uint32_t node = 1u; node < S.N; ++node) {
         const uint32_t par = S.parent[node];
@@ -931,6 +943,13 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     const bool nielsen = !(S.flags & EPV_FLAG_FORWARD_REJECTION);
     const EpvSegTask *segs = F.segs + f_wave * F.seg_cap;
     EpvSegOut *outs = F.outs + f_wave * F.seg_cap;
+    // SMALL: the sites' overflow flags, one word per lane in row 0 of the node table, which is dead
+    // from here on (inside the rounds it is not: a later round lists its heavy pairs over it, so the
+    // flags are cleared here and not in a round's hand-over).  The assembly raises a flag, the
+    // site's owner reads it: S.prop_flag, a global round trip in front of the whole acceptance for a
+    // byte the wave wrote itself, is left to the separate kernels and the generic body.
+    uint32_t *s_flag = regA;
+    if constexpr (SMALL) s_flag[lane] = 0u;
     // lists, start states and flags pass between the lanes of THIS wave through global memory: a
     // workgroup-scope fence (wait for the stores; one CU, one vector L1) is enough -- an agent-scope
     // one writes back and invalidates the XCD's L2, ~30 us each here
@@ -960,7 +979,8 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       if (!(done && f_nsole == f_nbt && f_nfin == f_nbt)) {
         for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
           epv_seg_assemble_one<!FUSED>(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i], s0,
-                               seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane);
+                               seed_lo, seed_hi, sweep, nielsen, s_meta + 2u * B * 64u, site - 3u * (uint64_t)lane,
+                               SMALL ? s_flag : nullptr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
       }
@@ -988,7 +1008,8 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       bool ovf = false;
       double llh_l = 0.0, llh_m = 0.0, llh_r = 0.0, u_acc = 0.0;
       if (f_listed) {
-        ovf = S.prop_flag[tid] != 0;
+        if constexpr (SMALL) ovf = s_flag[lane] != 0u;
+        else ovf = S.prop_flag[tid] != 0;
         llh_l = S.tri[site - 1]; llh_m = S.tri[site]; llh_r = S.tri[site + 1];
         s_own[my_rank] = (uint32_t)lane | (selLL << 8) | (selL << 9) | ((selM ^ 1u) << 10) | (selR << 11) | (selRR << 12) |
                          ((ovf ? 1u : 0u) << 13);
@@ -1011,6 +1032,19 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
             // the meta words of the triple's columns without a global round trip: the neighbours'
             // current paths were staged at the head of the kernel (they belong to other colours and
             // do not change in this phase), the proposal's sit where the site's own column was
+            if constexpr (SMALL) {
+              // read where they are.  A column is a row of s_meta (branch stride 64) or, for the outer
+              // column of lane 0 / the last valid lane, a run of s_edge = s_meta + 3 B 64 (branch
+              // stride 1): three (index, stride) pairs chosen by selects
+              const uint32_t oL = 0u * B * 64u + o, oR = 1u * B * 64u + o, oP = 2u * B * 64u + o;
+              const bool outL = w == 0u && o == 0u, outR = w == 2u && !(o < (uint32_t)last_lane);
+              const uint32_t i0 = w == 0u ? (outL ? 3u * B * 64u : oR - 1u) : w == 1u ? oL : oP;
+              const uint32_t i1 = w == 0u ? oL : w == 1u ? oP : oR;
+              const uint32_t i2 = w == 0u ? oP : w == 1u ? oR : (outR ? 3u * B * 64u + B : oL + 1u);
+              v = triple_llh_cached<NBA>(S, s_const, s_blen, s_meta, i0, outL ? 1u : 64u, bl, c - 1u, i1, 64u, bm, c,
+                                         i2, outR ? 1u : 64u, br, c + 1u, A);
+            } else {
+            // (generic body: the three columns copied into the lane's private area mc first)
             const uint32_t B2 = B;
 #pragma unroll 4
             for (uint32_t b = 0; b < B2; ++b) {
@@ -1024,7 +1058,8 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               mc[(1u * B2 + b) * 64u] = m1;
               mc[(2u * B2 + b) * 64u] = m2;
             }
-            v = triple_llh_cached<NN ? NN - 1 : 0>(S, s_const, s_blen, mc, 64u, 0u, bl, c - 1u, 1u, bm, c, 2u, br, c + 1u, A);
+            v = triple_llh_cached(S, s_const, s_blen, mc, 64u, 0u, bl, c - 1u, 1u, bm, c, 2u, br, c + 1u, A);
+            }
           } else {
             v = triple_llh(S, s_const, s_blen, bl, c - 1u, bm, c, br, c + 1u, A);
           }
