@@ -22,6 +22,7 @@
 #include "epv_math.h"
 #include "epv_pavg.h"
 #include "epv_bevents.h"
+#include "epv_mixing.h"
 #include "epv_wstat.h"
 #include "epv_epochs.h"
 #include "epv_origin.h"
@@ -192,6 +193,25 @@ struct CorrState {
   uint64_t samples = 0;
 };
 
+// chain mixing diagnostics (epv_mixing.h), off while K == 0.  The one layer that is joint across samples: it keeps
+// a run, the samples linked each to its predecessor
+struct MixingState {
+  uint32_t K = 0;                         // max_lag
+  unsigned long long *d_fp = nullptr;     // [at.cnt] fingerprint of the site's history at the last sample
+  uint32_t *d_moved = nullptr;            // [at.cnt] linked pairs whose histories differ
+  unsigned long long *d_sums = nullptr;   // [2 + K][at.cnt] S1, S2, C_1 .. C_K
+  uint32_t *d_ring = nullptr;             // [K][at.cnt] the last K values of x of the run
+  SiteLayout at;                          // (with B)
+  uint32_t C = 0;                         // the capacity the cap was last evaluated for
+  uint64_t samples = 0, moved_pairs = 0;
+  uint64_t pairs[EPV_MIX_MAX_LAG + 1u] = {};   // [k] linked pairs at lag k = 1 .. K
+  bool run_open = false;                  // a fingerprint of the state one sweep back may be on the device
+  uint64_t run_len = 0;                   // samples of the open run
+  uint64_t run_sweep = 0;                 // n_sweeps at the run's last sample (or its opening state)
+  unsigned long long *d_out = nullptr;    // window read-out staging
+  uint64_t out_cap = 0;                   // bytes
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -283,6 +303,7 @@ struct epv_ctx {
   PatternsState pt;
   TurnoverState to;
   CorrState co;
+  MixingState mx;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -780,10 +801,12 @@ struct Layer {
   int (*check_cap)(epv_ctx *, uint64_t more);  // (on, ensured) `more` further samples fit
   int (*launch)(epv_ctx *);                    // (on, ensured) the resident paths as one sample
   void (*off)(epv_ctx *);                      // no buffers, no layout, no samples
+  int (*begin)(epv_ctx *);                     // (on, ensured; may be null) the state after burn-in, before the first
+                                               // batch sweep of run_mcmc: for a layer that is joint across samples
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr, kMixing;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -923,7 +946,7 @@ int launch_pavg(epv_ctx *c) {
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
-const Layer kPavg = {pavg_on, ensure_pavg, pavg_check_cap, launch_pavg, pavg_off,
+const Layer kPavg = {pavg_on, ensure_pavg, pavg_check_cap, launch_pavg, pavg_off, nullptr,
                      "path average is off: epv_set_path_average first", "the path average"};
 
 // ---- posterior branch-event maps (epv_bevents.h): the sites of pavg_range, six uint32 planes
@@ -978,7 +1001,7 @@ int launch_bevents(epv_ctx *c) {
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
-const Layer kBevents = {bevents_on, ensure_bevents, bevents_check_cap, launch_bevents, bevents_off,
+const Layer kBevents = {bevents_on, ensure_bevents, bevents_check_cap, launch_bevents, bevents_off, nullptr,
                         "branch events are off: epv_set_branch_events first", "the branch events"};
 
 // ---- regional sufficient statistics (epv_wstat.h): J and D per window of W global sites, over the
@@ -1080,7 +1103,7 @@ int launch_wstat(epv_ctx *c) {
   ++c->ws.samples;
   return EPV_OK;
 }
-const Layer kWstat = {wstat_on, ensure_wstat, wstat_check_cap, launch_wstat, wstat_off,
+const Layer kWstat = {wstat_on, ensure_wstat, wstat_check_cap, launch_wstat, wstat_off, nullptr,
                       "window statistics are off: epv_set_window_stats first", "the window statistics"};
 
 // ---- lineage origin maps (epv_origin.h): the sites of pavg_range; origin uint32 [R][cnt], age uint64 [L][cnt]
@@ -1195,7 +1218,7 @@ int launch_origins(epv_ctx *c) {
   ++c->lo.samples;
   return EPV_OK;
 }
-const Layer kOrigins = {origins_on, ensure_origins, origins_check_cap, launch_origins, origins_off,
+const Layer kOrigins = {origins_on, ensure_origins, origins_check_cap, launch_origins, origins_off, nullptr,
                         "lineage origins are off: epv_set_lineage_origins first", "the lineage origins"};
 
 // ---- domain size spectra (epv_domains.h): the sites of pavg_range; a context keeps its PART, unclosed
@@ -1286,7 +1309,7 @@ int launch_domains(epv_ctx *c) {
   ++c->dm.samples;
   return EPV_OK;
 }
-const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off,
+const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off, nullptr,
                         "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
 
 // ---- domain turnover (epv_turnover.h): the sites of pavg_range, R = 2 B rows; a context keeps its PART, unclosed
@@ -1369,7 +1392,7 @@ int launch_turnover(epv_ctx *c) {
   ++c->to.samples;
   return EPV_OK;
 }
-const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off,
+const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off, nullptr,
                          "domain turnover is off: epv_set_domain_turnover first", "the domain turnover"};
 
 // ---- spatial correlations (epv_corr.h): the sites of pavg_range, R = N + B rows; a context keeps its PART, unclosed
@@ -1470,7 +1493,7 @@ int launch_corr(epv_ctx *c) {
   ++c->co.samples;
   return EPV_OK;
 }
-const Layer kCorr = {corr_on, ensure_corr, corr_check_cap, launch_corr, corr_off,
+const Layer kCorr = {corr_on, ensure_corr, corr_check_cap, launch_corr, corr_off, nullptr,
                      "spatial correlations are off: epv_set_spatial_correlation first", "the spatial correlations"};
 
 // ---- change patterns (epv_patterns.h): the sites of pavg_range, R = 12 + 2 B + I uint32 rows
@@ -1532,7 +1555,7 @@ int launch_patterns(epv_ctx *c) {
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
-const Layer kPatterns = {patterns_on, ensure_patterns, patterns_check_cap, launch_patterns, patterns_off,
+const Layer kPatterns = {patterns_on, ensure_patterns, patterns_check_cap, launch_patterns, patterns_off, nullptr,
                          "change patterns are off: epv_set_change_patterns first", "the change patterns"};
 
 // ---- epoch statistics (epv_epochs.h): J and D per branch and epoch of the branch, over the triples centred
@@ -1631,12 +1654,127 @@ int launch_epochs(epv_ctx *c) {
   c->ep.addends += epoch_blocks(c);
   return EPV_OK;
 }
-const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, epoch_off,
+const Layer kEpochs = {epoch_on, ensure_epochs, epoch_check_cap, launch_epochs, epoch_off, nullptr,
                        "epoch statistics are off: epv_set_epoch_stats first", "the epoch statistics"};
+
+// ---- chain mixing diagnostics (epv_mixing.h): the sites of pavg_range; per site a fingerprint, a move count,
+// 2 + K sums and a ring of K jump counts.  The host keeps the run: which sample is linked to which
+bool mixing_on(const epv_ctx *c) { return c->mx.K != 0u; }
+void mixing_off(epv_ctx *c) {
+  dfree(c->mx.d_fp); dfree(c->mx.d_moved); dfree(c->mx.d_sums); dfree(c->mx.d_ring); dfree(c->mx.d_out);
+  c->mx = MixingState{};
+}
+// no sample is linked to the one before it until a run opens again
+void mixing_close_run(epv_ctx *c) {
+  c->mx.run_open = false;
+  c->mx.run_len = 0;
+}
+// no samples, no run: the accumulators zeroed (the fingerprints and the ring are written before they are read)
+int mixing_zero(epv_ctx *c) {
+  const uint64_t cnt = c->mx.at.cnt, K = c->mx.K;
+  if (cnt) {
+    HIP_TRY(c, hipMemsetAsync(c->mx.d_fp, 0, 8u * cnt, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->mx.d_moved, 0, 4u * cnt, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->mx.d_sums, 0, 8u * (2u + K) * cnt, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->mx.d_ring, 0, 4u * K * cnt, c->stream));
+  }
+  c->mx.samples = c->mx.moved_pairs = 0;
+  for (uint64_t &p : c->mx.pairs) p = 0;
+  mixing_close_run(c);
+  return EPV_OK;
+}
+// (re)lay out the buffers for the current site range; zeroes them
+int mixing_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, true);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->mx.d_fp); dfree(c->mx.d_moved); dfree(c->mx.d_sums); dfree(c->mx.d_ring);
+  const uint32_t K = c->mx.K, per_site = 28u + 12u * K;
+  const double need = (double)per_site * (double)at.cnt;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "mixing diagnostics of max_lag %u need %.3g GB of device memory (%u B x %llu sites); "
+                  "%.3g GB are free: use a smaller max_lag or more GPUs (the diagnostics are off)",
+                  K, need / 1e9, per_site, (unsigned long long)at.cnt, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  if (at.cnt) {
+    HIP_TRY(c, hipMalloc(&c->mx.d_fp, (size_t)8u * at.cnt));
+    HIP_TRY(c, hipMalloc(&c->mx.d_moved, (size_t)4u * at.cnt));
+    HIP_TRY(c, hipMalloc(&c->mx.d_sums, (size_t)8u * (2u + K) * at.cnt));
+    HIP_TRY(c, hipMalloc(&c->mx.d_ring, (size_t)4u * K * at.cnt));
+  }
+  c->mx.at = at;
+  c->mx.C = c->S.C;
+  return mixing_zero(c);
+}
+// `more` further samples fit: a site's x is at most B C, so S2 and C_k stay below 2^64 while
+//   samples <= (2^64 - 1) / (B C)^2, and moved (32 bits) while samples <= 2^21.  With the capacity of now
+int mixing_check_cap(epv_ctx *c, uint64_t more) {
+  const uint64_t xmax = (uint64_t)c->S.B * c->S.C;   // (< 2^23: B < 2^12, C <= EPV_MAX_CAP)
+  const uint64_t cap = xmax ? std::min<uint64_t>(EPV_MIX_MAX_SAMPLES, ~0ull / (xmax * xmax)) : EPV_MIX_MAX_SAMPLES;
+  if (c->mx.samples <= cap && more <= cap - c->mx.samples) return EPV_OK;
+  char buf[320];
+  std::snprintf(buf, sizeof buf, "mixing diagnostics %s %llu samples, the most their sums take at %u branches of "
+                "capacity %u: read them out and epv_reset_mixing", more == 1u ? "hold" : "would pass",
+                (unsigned long long)cap, c->S.B, c->S.C);
+  return fail(c, EPV_ERR_STATE, buf);
+}
+// the buffers match the current site range, and the samples held fit the cap of the capacity of now
+int ensure_mixing(epv_ctx *c) {
+  if (!(pavg_layout(c, true, true) == c->mx.at)) {
+    if (c->mx.samples) return sites_changed(c, kMixing, "epv_set_mixing");
+    return relayout(c, kMixing, mixing_alloc);
+  }
+  if (c->S.C == c->mx.C) return EPV_OK;
+  c->mx.C = c->S.C;
+  return mixing_check_cap(c, 0u);
+}
+int mixing_launch_mode(epv_ctx *c, uint32_t mode, uint32_t slot, uint32_t lags) {
+  if (c->mx.at.cnt)
+    hipLaunchKernelGGL(epv_mixing_accum_kernel, dim3((unsigned)((c->mx.at.cnt + 255u) / 256u)), dim3(256), 0, c->stream,
+                       c->S, c->mx.at.lo, c->mx.at.cnt, c->mx.K, mode, slot, lags, c->mx.d_fp, c->mx.d_moved,
+                       c->mx.d_sums, c->mx.d_ring);
+  HIP_TRY(c, hipGetLastError());
+  return EPV_OK;
+}
+// the state after burn-in opens a run: its fingerprint is kept, it is no sample (ensure_mixing first)
+int begin_mixing(epv_ctx *c) {
+  const int rc = mixing_launch_mode(c, EPV_MIX_OPEN, 0u, 0u);
+  if (rc) return rc;
+  c->mx.run_open = true;
+  c->mx.run_len = 0;
+  c->mx.run_sweep = c->n_sweeps;
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_mixing first): linked to the sample (or opening state) before it when
+// the run is open and exactly one sweep has passed since, else the first of a new run
+int launch_mixing(epv_ctx *c) {
+  int rc = mixing_check_cap(c, 1u);
+  if (rc) return rc;
+  MixingState &m = c->mx;
+  const bool linked = m.run_open && c->n_sweeps == m.run_sweep + 1u;
+  if (!linked) m.run_len = 0;
+  const uint32_t lags = (uint32_t)std::min<uint64_t>(m.run_len, m.K);
+  if ((rc = mixing_launch_mode(c, linked ? EPV_MIX_LINKED : EPV_MIX_FIRST, (uint32_t)(m.run_len % m.K), lags))) return rc;
+  ++m.samples;
+  if (linked) ++m.moved_pairs;
+  for (uint32_t k = 1; k <= lags; ++k) ++m.pairs[k];
+  m.run_open = true;
+  ++m.run_len;
+  m.run_sweep = c->n_sweeps;
+  return EPV_OK;
+}
+const Layer kMixing = {mixing_on, ensure_mixing, mixing_check_cap, launch_mixing, mixing_off, begin_mixing,
+                       "mixing diagnostics are off: epv_set_mixing first", "the mixing diagnostics"};
 
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
-const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover, &kCorr};
+const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover, &kCorr,
+                                &kMixing};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -2135,6 +2273,7 @@ static int alloc_paths(epv_ctx *c, uint64_t n_sites, uint32_t capacity, uint64_t
   const uint64_t B = c->S.B, E = B * n_sites;
   HIP_TRY(c, hipSetDevice(c->device));
   free_paths(c);
+  mixing_close_run(c);   // (other paths: no sample is linked to them)
   c->S.n = n_sites;
   c->S.g0 = global_site_offset;
   c->S.n_global = global_site_offset + n_sites;
@@ -3055,7 +3194,8 @@ EPV_API int epv_sweep(epv_ctx *c, uint64_t n_sweeps, uint64_t seed, uint32_t swe
 }
 
 // burn_in sweeps, then batch x {sweep; stat(w); one sample of every summary layer that is on, in the order of
-// kLayers}: the chain of epv_run_mcmc_sums and epv_run_mcmc_counts.  stat(w) launches the statistics of batch
+// kLayers}: the chain of epv_run_mcmc_sums and epv_run_mcmc_counts.  A layer with a begin() sees the state after
+// burn-in first.  stat(w) launches the statistics of batch
 // sweep w; the accept counters are snapshot where the batch sweeps begin (finish_mcmc_snapshot)
 template <class Stat>
 static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed, uint32_t sweep_base, Stat stat) {
@@ -3069,14 +3209,18 @@ static int run_chain(epv_ctx *c, uint64_t burn_in, uint64_t batch, uint64_t seed
     ++c->n_sweeps;
   }
   if ((rc = snapshot_counters(c))) return rc;
-  for (uint64_t w = 0; w < batch; ++w, ++sweep) {
-    for (int colour = 0; colour < 3; ++colour)
-      if ((rc = launch_phase(c, colour, seed, sweep))) return rc;
+  for (const Layer *L : kLayers)   // (the opening state of what is joint across samples)
+    if (L->begin && L->on(c) && (rc = L->begin(c))) return rc;
+  for (uint64_t w = 0; w < batch && !rc; ++w, ++sweep) {
+    for (int colour = 0; colour < 3 && !rc; ++colour) rc = launch_phase(c, colour, seed, sweep);
+    if (rc) break;
     ++c->n_sweeps;
-    if ((rc = stat(w))) return rc;
+    if ((rc = stat(w))) break;
     for (const Layer *L : kLayers)
-      if (L->on(c) && (rc = L->launch(c))) return rc;
+      if (L->on(c) && (rc = L->launch(c))) break;
   }
+  mixing_close_run(c);   // nothing links across two calls: parameters and branch lengths may change between them
+  if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   return EPV_OK;
 }
@@ -3217,6 +3361,7 @@ EPV_API int epv_scale_jump_times(epv_ctx *c, const double *new_branches) {
   HIP_TRY(c, hipMemcpyAsync(c->d_scale, scale.data(), sizeof(double) * c->S.N, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(epv_scale_kernel, dim3((unsigned)((c->S.n + 255u) / 256u)), dim3(256), 0,
                      c->stream, c->S, c->d_scale);
+  mixing_close_run(c);   // (every jump time changed: not a move of the chain)
   HIP_TRY(c, hipGetLastError());
   for (uint32_t b = 1; b < c->S.N; ++b) c->blen[b] = new_branches[b];
   HIP_TRY(c, hipMemcpyAsync(c->d_blen, c->blen.data(), sizeof(double) * c->S.N, hipMemcpyHostToDevice, c->stream));
@@ -3586,6 +3731,80 @@ EPV_API int epv_get_branch_event_windows(epv_ctx *c, uint64_t W, uint64_t first_
   if (rc) return rc;
   return row_window_sums(c, c->be.d, (uint64_t)EPV_BEV_PLANES * c->be.at.B, c->be.at, &c->be.d_out, &c->be.out_cap, W,
                          first_window, n_windows, sums);
+}
+
+// ---- chain mixing diagnostics (epv_mixing.h)
+EPV_API int epv_set_mixing(epv_ctx *c, uint32_t max_lag) {
+  if (!max_lag) return layer_set_off(c, kMixing);
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  if (max_lag > EPV_MIX_MAX_LAG) return fail(c, EPV_ERR_ARG, "max_lag of the mixing diagnostics: 1 .. 16 (0 turns them off)");
+  c->mx.K = max_lag;
+  return layer_set_on(c, kMixing, mixing_alloc);
+}
+
+EPV_API int epv_reset_mixing(epv_ctx *c) {
+  int rc = layer_entry(c, kMixing);
+  if (rc) return rc;
+  if ((rc = mixing_zero(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_mixing(epv_ctx *c) { return layer_accumulate(c, kMixing); }
+
+EPV_API int epv_mixing_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->mx.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_mixing_layout(epv_ctx *c, uint64_t *first, uint64_t *count, uint32_t *max_lag) {
+  if (!c || !first || !count || !max_lag) return EPV_ERR_ARG;
+  *first = *count = 0;
+  *max_lag = 0;
+  if (!c->mx.K) return EPV_OK;
+  if (c->have_tree && c->have_paths) {   // (no samples yet: lay out for the sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_mixing(c);
+    if (rc && c->mx.samples == 0) return rc;
+  }
+  *first = c->mx.at.lo;
+  *count = c->mx.at.cnt;
+  *max_lag = c->mx.K;
+  return EPV_OK;
+}
+
+EPV_API int epv_mixing_pairs(epv_ctx *c, uint64_t *words) {
+  const int rc = layer_entry(c, kMixing);
+  if (rc) return rc;
+  if (!words) return fail(c, EPV_ERR_ARG, "null output");
+  words[0] = c->mx.samples;
+  words[1] = c->mx.moved_pairs;
+  for (uint32_t k = 1; k <= c->mx.K; ++k) words[1u + k] = c->mx.pairs[k];
+  return EPV_OK;
+}
+
+EPV_API int epv_mixing_counts(epv_ctx *c, uint64_t first, uint64_t count, uint32_t *moved, uint64_t *sums) {
+  const int rc = layer_entry(c, kMixing);
+  if (rc) return rc;
+  if (!moved || !sums) return fail(c, EPV_ERR_ARG, "null output");
+  if (first < c->mx.at.lo || first + count > c->mx.at.lo + c->mx.at.cnt)
+    return fail(c, EPV_ERR_ARG, "site range outside the sites this context counts");
+  if (count == 0) return EPV_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint64_t off = first - c->mx.at.lo;
+  HIP_TRY(c, hipMemcpy(moved, c->mx.d_moved + off, count * 4u, hipMemcpyDeviceToHost));
+  // rows of `count` sites out of rows of at.cnt: [2 + K][at.cnt] -> [2 + K][count]
+  HIP_TRY(c, hipMemcpy2D(sums, count * 8u, c->mx.d_sums + off, c->mx.at.cnt * 8u, count * 8u, 2u + c->mx.K,
+                         hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+EPV_API int epv_mixing_windows(epv_ctx *c, uint64_t W, uint64_t first_window, uint64_t n_windows, uint64_t *sums) {
+  const int rc = layer_entry(c, kMixing);
+  if (rc) return rc;
+  return row_window_sums(c, c->mx.d_moved, 1u, c->mx.at, &c->mx.d_out, &c->mx.out_cap, W, first_window, n_windows, sums);
 }
 
 // ---- change patterns (epv_patterns.h)

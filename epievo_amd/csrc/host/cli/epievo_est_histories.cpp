@@ -40,6 +40,11 @@
 // sweeps (epv_set_spatial_correlation with max_samples = B: per node state row and branch change row the pairs of
 // ones at every lag 1 .. L, closed over the whole genome), as integers (epv::write_spatial_correlation).  Changes
 // nothing else the run writes.
+// New: -x/--mixing FILE with -A/--acflags K (default 8, at most 16) and the same -w/--window W: the chain mixing
+// diagnostics of the B batch sweeps (epv_set_mixing: per site the linked sample pairs whose history differs, and the
+// sums of the site's jump count and of its lagged products up to lag K), per window of W sites: the integer sum of
+// the moves, the move rate, the pooled autocorrelations and their integrated autocorrelation time
+// (epv::write_mixing).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -65,12 +70,12 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
     const size_t no_lag = std::numeric_limits<size_t>::max();
-    size_t max_lag = no_lag;
+    size_t max_lag = no_lag, mixing_lag = no_lag;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
     size_t rng_seed = std::numeric_limits<size_t>::max();
@@ -108,6 +113,9 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("correlation", 'C', "output file of the spatial correlations of the batch sweeps (integer pair counts "
                       "per lag)", false, corr_file);
     opt_parse.add_opt("maxlag", 'M', "largest lag of the spatial correlations (default 64, at most 1024)", false, max_lag);
+    opt_parse.add_opt("mixing", 'x', "output file of the chain mixing diagnostics of the batch sweeps per window (moves, "
+                      "move rate, autocorrelations of the jump count)", false, mixing_file);
+    opt_parse.add_opt("acflags", 'A', "largest lag of the mixing diagnostics (default 8, at most 16)", false, mixing_lag);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps and "
                       "change patterns (default 1)", false, window);
@@ -132,7 +140,7 @@ int main(int argc, const char **argv) {
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
     if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty() &&
-        patterns_file.empty())
+        patterns_file.empty() && mixing_file.empty())
       throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional, -O/--origins and -P/--patterns: "
                                "give the output file of the branch-event maps, of the regional statistics, of the "
                                "origin maps or of the change patterns");
@@ -144,6 +152,10 @@ int main(int argc, const char **argv) {
       throw std::runtime_error("-M/--maxlag belongs to -C/--correlation: give the output file of the spatial correlations");
     if (max_lag == no_lag) max_lag = 64;
     if (max_lag == 0 || max_lag > 1024) throw std::runtime_error("-M: a largest lag of 1 to 1024 sites");
+    if (mixing_lag != no_lag && mixing_file.empty())
+      throw std::runtime_error("-A/--acflags belongs to -x/--mixing: give the output file of the mixing diagnostics");
+    if (mixing_lag == no_lag) mixing_lag = 8;
+    if (mixing_lag == 0 || mixing_lag > 16) throw std::runtime_error("-A: a largest lag of 1 to 16 samples");
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
@@ -198,6 +210,7 @@ int main(int argc, const char **argv) {
     if (!patterns_file.empty()) mcmc.set_change_patterns(true);
     if (!turnover_file.empty()) mcmc.set_domain_turnover(batch);
     if (!corr_file.empty()) mcmc.set_spatial_correlation((uint32_t)max_lag, batch);
+    if (!mixing_file.empty()) mcmc.enable_mixing((uint32_t)mixing_lag);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -289,6 +302,13 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[WRITING SPATIAL CORRELATIONS OF " << n_samples << " SAMPLES: " << corr_file << "]" << endl;
       epv::write_spatial_correlation(corr_file, th.node_names, n_samples, out.n_sites, L, n11.data(), left1.data(),
                                      right1.data());
+    }
+    if (!mixing_file.empty()) {
+      vector<uint64_t> words, sums;
+      vector<uint32_t> moved;
+      mcmc.download_mixing(words, moved, sums);
+      if (VERBOSE) cerr << "[WRITING MIXING DIAGNOSTICS OF " << words[0] << " SAMPLES: " << mixing_file << "]" << endl;
+      epv::write_mixing(mixing_file, (uint32_t)mixing_lag, words.data(), moved.size(), window, moved.data(), sums.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

@@ -40,6 +40,9 @@ struct epvd_sampler {
   bool have_staged_turnover = false;
   std::vector<uint64_t> staged_corr_n11, staged_corr_edges;   // between epvd_corr_part_sizes and epvd_download_corr_part
   bool have_staged_corr = false;
+  std::vector<uint64_t> staged_mix_words, staged_mix_sums;   // between epvd_mixing_sizes and epvd_download_mixing
+  std::vector<uint32_t> staged_mix_moved;
+  bool have_staged_mixing = false;
 };
 
 namespace {
@@ -240,6 +243,28 @@ EPVD_API int epvd_download_branch_event_windows(epvd_sampler *h, uint64_t W, uin
     h->s->download_branch_event_windows(W, v, ns);
     std::copy(v.begin(), v.end(), sums);
     if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_mixing(epvd_sampler *h, uint32_t max_lag) {
+  return guarded(h, [&] { h->s->enable_mixing(max_lag); });
+}
+EPVD_API int epvd_mixing_sizes(epvd_sampler *h, uint64_t *n_sites, uint32_t *max_lag) {
+  return guarded(h, [&] {
+    h->s->download_mixing(h->staged_mix_words, h->staged_mix_moved, h->staged_mix_sums);
+    h->have_staged_mixing = true;
+    *n_sites = h->staged_mix_moved.size();
+    *max_lag = h->s->mixing_max_lag();
+  });
+}
+EPVD_API int epvd_download_mixing(epvd_sampler *h, uint64_t *words, uint32_t *moved, uint64_t *sums) {
+  return guarded(h, [&] {
+    if (!h->have_staged_mixing) throw std::runtime_error("epvd_mixing_sizes first");
+    std::copy(h->staged_mix_words.begin(), h->staged_mix_words.end(), words);
+    std::copy(h->staged_mix_moved.begin(), h->staged_mix_moved.end(), moved);
+    std::copy(h->staged_mix_sums.begin(), h->staged_mix_sums.end(), sums);
+    h->staged_mix_words.clear(); h->staged_mix_moved.clear(); h->staged_mix_sums.clear();
+    h->have_staged_mixing = false;
   });
 }
 

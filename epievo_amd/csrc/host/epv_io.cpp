@@ -677,6 +677,58 @@ void write_branch_events(const std::string &file, const std::vector<std::string>
   if (!out) throw std::runtime_error("error writing: " + file);
 }
 
+void write_mixing(const std::string &file, uint32_t max_lag, const uint64_t *words, uint64_t n_sites, uint64_t window,
+                  const uint32_t *moved, const uint64_t *sums) {
+  const uint32_t K = max_lag;
+  const uint64_t samples = words[0], moved_pairs = words[1];
+  if (!samples) throw std::runtime_error("the mixing diagnostics hold no sample");
+  if (!window) throw std::runtime_error("a window holds at least one site");
+  std::ofstream out(file);
+  if (!out) throw std::runtime_error("bad output file: " + file);
+  out << "#epievo-mixing 1\nsamples " << samples << "\nmoved_pairs " << moved_pairs << "\nmax_lag " << K << "\npairs";
+  for (uint32_t k = 1; k <= K; ++k) out << ' ' << words[1u + k];
+  out << "\nwindow " << window << "\nfirst_window 0\n#window sites moved move_rate";
+  for (uint32_t k = 1; k <= K; ++k) out << " rho_" << k;
+  out << " tau\n";
+  const double nan = std::numeric_limits<double>::quiet_NaN(), ns = (double)samples;
+  auto num = [&out](double v) {
+    char buf[40];
+    std::snprintf(buf, sizeof buf, " %.17g", v);
+    out << buf;
+  };
+  std::vector<double> csum(K + 1u), rho(K + 1u);
+  for (uint64_t w = 0, lo = 0; lo < n_sites; ++w, lo += window) {
+    const uint64_t hi = n_sites - lo < window ? n_sites : lo + window;
+    uint64_t msum = 0;
+    double vsum = 0.0;
+    std::fill(csum.begin(), csum.end(), 0.0);
+    for (uint64_t p = lo; p < hi; ++p) {
+      msum += moved[p];
+      const double mean = (double)sums[p] / ns, var = (double)sums[n_sites + p] / ns - mean * mean;
+      vsum += var;
+      for (uint32_t k = 1; k <= K; ++k)
+        csum[k] += words[1u + k] ? (double)sums[(uint64_t)(1u + k) * n_sites + p] / (double)words[1u + k] - mean * mean : nan;
+    }
+    rho[0] = vsum > 0.0 ? 1.0 : nan;
+    for (uint32_t k = 1; k <= K; ++k) rho[k] = vsum > 0.0 ? csum[k] / vsum : nan;
+    // Geyer's initial positive sequence: G_m = rho[2 m] + rho[2 m + 1], G_0 always, then while G_m > 0
+    double tau = -1.0;
+    for (uint32_t m = 0; 2u * m + 1u <= K; ++m) {
+      const double G = rho[2u * m] + rho[2u * m + 1u];
+      if (m && !(G > 0.0)) break;
+      tau += 2.0 * G;
+    }
+    if (!(vsum > 0.0)) tau = nan;
+    out << w << ' ' << hi - lo << ' ' << msum;
+    num(moved_pairs ? (double)msum / ((double)moved_pairs * (double)(hi - lo)) : nan);
+    for (uint32_t k = 1; k <= K; ++k) num(rho[k]);
+    num(tau);
+    out << '\n';
+  }
+  out.flush();
+  if (!out) throw std::runtime_error("error writing: " + file);
+}
+
 void write_change_patterns(const std::string &file, const std::vector<std::string> &node_names,
                            const std::vector<uint32_t> &subtree_sizes, uint32_t n_rows, uint64_t n_sites,
                            uint64_t n_windows, uint64_t window, const uint64_t *sums, uint64_t n_samples) {

@@ -66,6 +66,15 @@ void write_branch_events(const std::string &file, const std::vector<std::string>
                          uint64_t n_windows, uint64_t window, const double *branch_len, const uint64_t *sums,
                          uint64_t n_samples);
 
+// the chain mixing diagnostics per window of `window` sites (the file host.read_mixing of the Python package reads):
+// "#epievo-mixing 1", the lines "samples S", "moved_pairs M", "max_lag K", "pairs p_1 .. p_K", "window W",
+// "first_window 0", a comment line, then per window: its index, its sites, the integer sum of moved, and as
+// floating point (%.17g, nan where undefined) the move rate moved / (M sites), the pooled rho_k = sum_p cov_k(p) /
+// sum_p var(p) for k = 1 .. K and tau of it (Geyer's initial positive sequence).  words[K + 2] = S, M, p_1 .. p_K;
+// moved[site]; sums[r * n_sites + site], rows S1, S2, C_1 .. C_K
+void write_mixing(const std::string &file, uint32_t max_lag, const uint64_t *words, uint64_t n_sites, uint64_t window,
+                  const uint32_t *moved, const uint64_t *sums);
+
 // the window sums of the change-pattern rows (epv_get_change_pattern_windows), integers only:
 // "#samples\t<S>\twindow\t<W>\tsites\t<n>", a line "#rows" with the name of every row (jumps_1 .. jumps_6,
 // jumps_7plus, one_branch, parallel_gain, parallel_loss, gain_and_loss, reverted_only, sole_gain:<node> and

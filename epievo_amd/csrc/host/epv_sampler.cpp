@@ -439,6 +439,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (patterns_) set_change_patterns(true);
   if (turnover_max_) set_domain_turnover(turnover_max_);
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
+  if (mixing_lag_) enable_mixing(mixing_lag_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -454,6 +455,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (patterns_) set_change_patterns(true);
   if (turnover_max_) set_domain_turnover(turnover_max_);
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
+  if (mixing_lag_) enable_mixing(mixing_lag_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -545,6 +547,53 @@ void SingleSiteSampler::download_branch_event_windows(uint64_t W, std::vector<ui
   for (epv_ctx *c : cs) {   // every context's contribution to the windows of global sites
     check_on(c, epv_get_branch_event_windows(c, W, 0u, nw, part.data()), "epv_get_branch_event_windows");
     for (size_t k = 0; k < part.size(); ++k) sums[k] += part[k];
+  }
+}
+
+void SingleSiteSampler::enable_mixing(uint32_t max_lag) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (max_lag > 16u) throw std::runtime_error("max_lag of the mixing diagnostics: 1 .. 16 (0 turns them off)");
+  if (n_sites_ || !max_lag)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_mixing(c, max_lag), "epv_set_mixing");
+  mixing_lag_ = max_lag;
+}
+
+// samples, moved_pairs, pairs[1 .. K]: the contexts ran the same runs
+static void mixing_words(const std::vector<epv_ctx *> &cs, uint32_t K, std::vector<uint64_t> &words) {
+  std::vector<uint64_t> w(K + 2u);
+  for (size_t i = 0; i < cs.size(); ++i) {
+    if (epv_mixing_pairs(cs[i], w.data()) != EPV_OK) throw std::runtime_error(std::string("epv_mixing_pairs: ") + epv_last_error(cs[i]));
+    if (i == 0) words = w;
+    else if (w[0] != words[0]) throw std::runtime_error("the contexts hold different numbers of mixing samples");
+    else if (w != words) throw std::runtime_error("the contexts hold mixing samples of different runs (their pair counts differ)");
+  }
+}
+
+void SingleSiteSampler::download_mixing(std::vector<uint64_t> &words, std::vector<uint32_t> &moved,
+                                        std::vector<uint64_t> &sums) {
+  if (!mixing_lag_) throw std::runtime_error("mixing diagnostics are off: enable_mixing first");
+  const std::vector<epv_ctx *> cs = contexts();
+  const uint64_t R = 2u + mixing_lag_;
+  std::vector<uint64_t> first(cs.size()), count(cs.size());
+  uint64_t total = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t K = 0;
+    check_on(cs[i], epv_mixing_layout(cs[i], &first[i], &count[i], &K), "epv_mixing_layout");
+    if (K != mixing_lag_) throw std::runtime_error("a context's mixing diagnostics are off");
+    total += count[i];
+  }
+  mixing_words(cs, mixing_lag_, words);
+  moved.assign(total, 0u);
+  sums.assign(R * total, 0u);
+  std::vector<uint64_t> part;
+  uint64_t at = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {   // contexts in genome order, each one's sites contiguous
+    part.assign(R * count[i], 0u);
+    if (count[i])
+      check_on(cs[i], epv_mixing_counts(cs[i], first[i], count[i], moved.data() + at, part.data()), "epv_mixing_counts");
+    for (uint64_t r = 0; r < R; ++r)
+      std::copy(part.begin() + r * count[i], part.begin() + (r + 1) * count[i], sums.begin() + r * total + at);
+    at += count[i];
   }
 }
 

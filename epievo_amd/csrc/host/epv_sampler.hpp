@@ -120,6 +120,13 @@ public:
   uint64_t branch_event_windows(uint64_t W) const { return W ? (n_sites_ + W - 1u) / W : 0u; }   // windows of the genome
   void download_branch_events(std::vector<uint32_t> &planes, uint64_t &n_samples);
   void download_branch_event_windows(uint64_t W, std::vector<uint64_t> &sums, uint64_t &n_samples);
+  // chain mixing diagnostics (epv_set_mixing) on every context, with the branch events' lifecycle (max_lag = 0:
+  // off).  download_mixing: words[K + 2] = samples, moved_pairs, pairs[1 .. K] (the same on every context, else it
+  // throws), moved[site] and sums[r * sites + site] (rows S1, S2, C_1 .. C_K) over the sites of this process in
+  // genome order
+  void enable_mixing(uint32_t max_lag);
+  uint32_t mixing_max_lag() const { return mixing_lag_; }
+  void download_mixing(std::vector<uint64_t> &words, std::vector<uint32_t> &moved, std::vector<uint64_t> &sums);
   // regional sufficient statistics (epv_set_window_stats) on every context: J and D per window of W global
   // sites, with the branch events' samples and lifecycle (W = 0: off).  download_window_stats:
   // counts[(w * (n_nodes-1) + b-1) * 16 + c] (J[8] then D[8] as integers) over all windows of the genome,
@@ -315,6 +322,7 @@ private:
   uint32_t corr_lag_ = 0;     // set_spatial_correlation
   uint64_t corr_max_ = 0;
   bool patterns_ = false;     // set_change_patterns
+  uint32_t mixing_lag_ = 0;   // enable_mixing
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none

@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _build
 from .host import FlatPaths
+from . import host
 from .summaries import _per_sample
 
 _lib = None
@@ -31,7 +32,8 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_set_corr", "epvd_reset_corr", "epvd_accumulate_corr",
                   "epvd_corr_part_sizes", "epvd_download_corr_part", "epvd_download_corr",
                   "epvd_set_change_patterns", "epvd_change_patterns_sizes", "epvd_download_change_patterns",
-                  "epvd_download_change_pattern_windows"]
+                  "epvd_download_change_pattern_windows",
+                  "epvd_set_mixing", "epvd_mixing_sizes", "epvd_download_mixing"]
 
 
 def lib():
@@ -73,6 +75,9 @@ def lib():
         L.epvd_change_patterns_sizes.argtypes = [vp, u64p, u32p, u64p]
         L.epvd_download_change_patterns.argtypes = [vp, u32p]
         L.epvd_download_change_pattern_windows.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p, u64p]
+        L.epvd_set_mixing.argtypes = [vp, C.c_uint32]
+        L.epvd_mixing_sizes.argtypes = [vp, u64p, u32p]
+        L.epvd_download_mixing.argtypes = [vp, u64p, u32p, u64p]
         L.epvd_set_window_stats.argtypes = [vp, C.c_uint64]
         L.epvd_window_stats_sizes.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_window_stats.argtypes = [vp, C.POINTER(C.c_int64), dp, dp]
@@ -287,6 +292,23 @@ class CppSampler:
         out, ns = np.zeros((6, self.B, nw), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_branch_event_windows(self.h, W, nw, _p(out, C.c_uint64), C.byref(ns)))
         return int(ns.value), out
+
+    def enable_mixing(self, max_lag=8):
+        """chain mixing diagnostics on every context (0 = off); kept across reset()"""
+        self._ck(self.L.epvd_set_mixing(self.h, int(max_lag)))
+
+    def mixing(self, counts=False):
+        """-> DeviceSampler.mixing over the sites of this process: the counts, or host.mixing_summary of them"""
+        n, K = C.c_uint64(0), C.c_uint32(0)
+        self._ck(self.L.epvd_mixing_sizes(self.h, C.byref(n), C.byref(K)))
+        n, K = int(n.value), int(K.value)
+        words, moved = np.zeros(K + 2, np.uint64), np.zeros(max(n, 1), np.uint32)
+        sums = np.zeros(max((2 + K) * n, 1), np.uint64)
+        self._ck(self.L.epvd_download_mixing(self.h, _p(words, C.c_uint64), _p(moved, C.c_uint32), _p(sums, C.c_uint64)))
+        sums = sums[:(2 + K) * n].reshape(2 + K, n)
+        pairs = np.concatenate([np.zeros(1, np.uint64), words[2:]])
+        out = (int(words[0]), int(words[1]), pairs, moved[:n], sums[0], sums[1], sums[2:])
+        return out if counts else host.mixing_summary(*out)
 
     def enable_change_patterns(self, on=True):
         """change patterns on every context (False = off); kept across reset()"""

@@ -700,8 +700,144 @@ def read_spatial_correlation(path):
         L_.epvh_spatial_correlation_free(h)
 
 
+# ---- chain mixing diagnostics (does a site's history move, and how long does its jump count remember itself)
+def _mixing_moments(samples, pairs, S1, S2, Ck):
+    """-> (mean [n], var [n], cov [K + 1, n]) of a site's jump count x over the samples: the plain estimators, the
+    mean and the variance over all samples, cov[k] = C_k / pairs[k] - mean^2 (cov[0] = var; nan where pairs[k] = 0)"""
+    S1, S2, Ck = (np.asarray(a, np.uint64).astype(np.float64) for a in (S1, S2, Ck))
+    pairs = np.asarray(pairs, np.uint64).astype(np.float64)
+    if Ck.ndim != 2 or pairs.shape != (Ck.shape[0] + 1,) or S1.shape != Ck.shape[1:] or S2.shape != S1.shape:
+        raise ValueError("pairs is [K + 1], S1 and S2 are [sites], C is [K, sites]")
+    if samples < 1:
+        raise ValueError("the mixing diagnostics hold no sample")
+    mean = S1 / float(samples)
+    var = S2 / float(samples) - mean * mean
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cov = np.concatenate([var[None], Ck / pairs[1:, None] - mean * mean])
+    cov[1:][pairs[1:] == 0] = np.nan
+    return mean, var, cov
+
+
+def _geyer_tau(rho):
+    """integrated autocorrelation time of rho [K + 1, ...] (rho[0] = 1) by Geyer's initial positive sequence:
+    tau = -1 + 2 sum of G_m = rho[2 m] + rho[2 m + 1] over m = 0, 1, .. while G_m > 0 (G_0 always; a lag without
+    its partner, K even, is left out).  -> (tau, censored): censored where every G_m up to K was positive, so
+    that the sum was cut by max_lag and tau is a lower bound"""
+    G = rho[0:rho.shape[0] // 2 * 2:2] + rho[1::2]
+    with np.errstate(invalid="ignore"):
+        alive = np.logical_and.accumulate(np.concatenate([np.ones((1,) + G.shape[1:], bool), G[1:] > 0.0]), axis=0)
+    tau = -1.0 + 2.0 * np.where(alive, G, 0.0).sum(axis=0)
+    return tau, alive[-1] & (G[-1] > 0.0)
+
+
+def mixing_summary(samples, moved_pairs, pairs, moved, S1, S2, Ck):
+    """the counts of DeviceSampler.mixing(counts=True) -> dict, per site: move_rate = moved / moved_pairs (nan
+    without a linked pair), mean and var of the site's jump count x over the samples, rho [K + 1, sites] with
+    rho[k] = (C_k / pairs[k] - mean^2) / var, tau (Geyer's initial positive sequence over rho[1 .. K]),
+    tau_censored (the sequence was still positive at max_lag: tau is a lower bound) and ess = samples / tau clipped
+    to [1, samples]; also samples, moved_pairs, pairs.  Where var == 0 (x never changed) rho, tau and ess are nan:
+    the move rate is what speaks there.
+    rho is the plain estimator: both members of a pair are centred at the mean of ALL samples and scaled by the
+    variance of all samples, and the pairs that a run boundary cuts are missing from C_k but not from the mean.  Its
+    bias is of the order 1 / (length of a run): for an independent chain of runs of length B, E rho[k] is about
+    -1 / B, and rho[k] at k close to B rests on few pairs.  Read tau of short runs (B = 50) per window
+    (mixing_window_summary), not per site."""
+    moved = np.asarray(moved, np.uint32).astype(np.float64)
+    mean, var, cov = _mixing_moments(samples, pairs, S1, S2, Ck)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = np.where(var > 0.0, cov / var, np.nan)
+        tau, censored = _geyer_tau(rho)
+        tau = np.where(var > 0.0, tau, np.nan)
+        ess = np.where(tau > 0.0, float(samples) / tau, float(samples))
+        ess = np.where(var > 0.0, np.clip(ess, 1.0, float(samples)), np.nan)
+        rate = moved / float(moved_pairs) if moved_pairs else np.full(moved.shape, np.nan)
+    return dict(samples=int(samples), moved_pairs=int(moved_pairs), pairs=np.asarray(pairs, np.uint64),
+                move_rate=rate, mean=mean, var=var, rho=rho, tau=tau, tau_censored=censored & (var > 0.0), ess=ess)
+
+
+def mixing_window_summary(W, samples, moved_pairs, pairs, moved, S1, S2, Ck, first_site=0):
+    """the same counts, pooled over windows of W consecutive global sites (the rows start at global site first_site;
+    a window is [w W, (w + 1) W)) -> dict per window from window first_site // W on: sites, moved (uint64 sums),
+    move_rate = moved / (moved_pairs x sites), rho [K + 1, windows] with rho[k] = sum_p cov_k(p) / sum_p var(p) over
+    the window's sites (usable at 50 samples, where a single site's rho is not; nan where no site of the window
+    varies), tau and tau_censored of it, and first_window"""
+    W = int(W)
+    if W < 1:
+        raise ValueError("a window holds at least one site")
+    moved = np.asarray(moved, np.uint32).astype(np.uint64)
+    _, var, cov = _mixing_moments(samples, pairs, S1, S2, Ck)
+    n = moved.shape[0]
+    g = first_site + np.arange(n, dtype=np.int64)
+    w0 = first_site // W
+    cuts = np.nonzero(np.concatenate([[True], g[1:] // W != g[:-1] // W]))[0] if n else np.zeros(0, np.int64)
+    nw = int(g[-1] // W - w0 + 1) if n else 0
+    if len(cuts) != nw:
+        raise AssertionError("windows of consecutive sites")
+    sites = np.diff(np.concatenate([cuts, [n]])) if n else np.zeros(0, np.int64)
+    msum = np.add.reduceat(moved, cuts) if n else moved
+    vsum = np.add.reduceat(var, cuts) if n else var
+    csum = np.add.reduceat(cov, cuts, axis=1) if n else cov
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rho = np.where(vsum > 0.0, csum / vsum, np.nan)
+        tau, censored = _geyer_tau(rho)
+        tau = np.where(vsum > 0.0, tau, np.nan)
+        rate = msum / (float(moved_pairs) * sites) if moved_pairs else np.full(nw, np.nan)
+    return dict(window=W, first_window=int(w0), sites=sites.astype(np.int64), moved=msum, move_rate=rate, rho=rho,
+                tau=tau, tau_censored=censored & (vsum > 0.0))
+
+
+def write_mixing(path, samples, moved_pairs, pairs, summary):
+    """the file of mixing diagnostics per window: the header (samples, moved_pairs, max_lag, pairs[1 .. K], window,
+    first_window), then a line per window: index, sites, moved (the integer window sum), move_rate, rho[1 .. K], tau.
+    summary = what mixing_window_summary returned; floats are written so that they read back bit for bit"""
+    rho = np.asarray(summary["rho"], np.float64)
+    K = rho.shape[0] - 1
+    pairs = np.asarray(pairs, np.uint64)
+    if pairs.shape != (K + 1,):
+        raise ValueError("pairs is [K + 1]")
+    with open(path, "w") as f:
+        f.write("#epievo-mixing 1\n")
+        f.write("samples %d\nmoved_pairs %d\nmax_lag %d\n" % (samples, moved_pairs, K))
+        f.write("pairs %s\n" % " ".join(str(int(p)) for p in pairs[1:]))
+        f.write("window %d\nfirst_window %d\n" % (summary["window"], summary["first_window"]))
+        f.write("#window sites moved move_rate %s tau\n" % " ".join("rho_%d" % k for k in range(1, K + 1)))
+        for i in range(len(summary["sites"])):
+            vals = [summary["move_rate"][i]] + list(rho[1:, i]) + [summary["tau"][i]]
+            f.write("%d %d %d %s\n" % (summary["first_window"] + i, summary["sites"][i], int(summary["moved"][i]),
+                                       " ".join(repr(float(v)) for v in vals)))
+
+
+def read_mixing(path):
+    """-> dict(samples, moved_pairs, max_lag, pairs uint64[K + 1], window, first_window, sites int64[windows], moved
+    uint64[windows], move_rate, rho [K + 1, windows] (rho[0] = 1 where any rho of the window is a number), tau)"""
+    with open(path) as f:
+        lines = [ln.split() for ln in f.read().splitlines()]
+    if not lines or lines[0][:1] != ["#epievo-mixing"]:
+        raise RuntimeError("%s is not a file of mixing diagnostics" % path)
+    head = {ln[0]: ln[1:] for ln in lines[1:7]}
+    try:
+        K = int(head["max_lag"][0])
+        out = dict(samples=int(head["samples"][0]), moved_pairs=int(head["moved_pairs"][0]), max_lag=K,
+                   pairs=np.array([0] + [int(v) for v in head["pairs"]], np.uint64), window=int(head["window"][0]),
+                   first_window=int(head["first_window"][0]))
+        rows = [ln for ln in lines[7:] if ln and not ln[0].startswith("#")]
+        if len(out["pairs"]) != K + 1 or any(len(r) != K + 5 for r in rows):
+            raise ValueError("a line of the wrong length")
+        if [int(r[0]) for r in rows] != list(range(out["first_window"], out["first_window"] + len(rows))):
+            raise ValueError("windows out of order")
+        out["sites"] = np.array([int(r[1]) for r in rows], np.int64)
+        out["moved"] = np.array([int(r[2]) for r in rows], np.uint64)
+        fl = np.array([[float(v) for v in r[3:]] for r in rows], np.float64).reshape(len(rows), K + 2)
+    except (KeyError, IndexError, ValueError) as e:
+        raise RuntimeError("%s: malformed file of mixing diagnostics (%s)" % (path, e))
+    out["move_rate"], out["tau"] = fl[:, 0].copy(), fl[:, K + 1].copy()
+    first = np.where(np.isnan(fl[:, 1:K + 1]).all(axis=1), np.nan, 1.0)
+    out["rho"] = np.concatenate([first[None], fl[:, 1:K + 1].T])
+    return out
+
+
 # ---- change patterns (what happened across the branches of the tree at one site)
-CHANGE_PATTERN_CLASSES = ("one_branch", "parallel_gain", "parallel_loss", "gain_and_loss", "reverted_only")
+CHANGE_PATTERN_CLASSES =("one_branch", "parallel_gain", "parallel_loss", "gain_and_loss", "reverted_only")
 
 
 def change_pattern_row_names(tree):

@@ -34,7 +34,7 @@ import numpy as np
 from . import host
 from .host import FlatPaths
 from .sampler import DeviceSampler, forward_to_dev
-from .summaries import LIFECYCLE, NOUN, SUMMARIES, _per_sample, _window_range, summary_method
+from .summaries import LAYERS, LIFECYCLE, NOUN, _per_sample, _window_range, summary_method
 
 BLOCK = 256      # sites per block: halo widths and shard_cuts' cut points are whole blocks
 TAIL = 1         # int64 words after a rank's counts in the all-gather: its accept count
@@ -494,6 +494,27 @@ class ShardedSampler:
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
 
+    def mixing(self, counts=False):
+        """-> DeviceSampler.mixing of the whole genome, identical on every rank: the ranks' rows are all-gathered
+        (one collective) and concatenated in genome order (a 64-bit cell travels as two words); the ranks' pair
+        counts travel behind the sample count and must agree"""
+        ns, mp, pairs, moved, S1, S2, Ck = self.dev.mixing(counts=True)
+        wide = np.ascontiguousarray(np.concatenate([S1[None], S2[None], Ck]), np.uint64)
+        tail = np.concatenate([[mp], pairs]).astype(np.uint64).view(np.uint32)
+        (moved, wide), tails = self._gather_sites(
+            ns, [moved[None, :, None], wide.view(np.uint32).reshape(wide.shape[0], -1, 2)], NOUN["mixing"], extra=list(tail))
+        if any(not np.array_equal(w, tail) for w in tails):
+            raise RuntimeError("the ranks hold mixing samples of different runs (their pair counts differ)")
+        wide = np.ascontiguousarray(wide).view(np.uint64)[:, :, 0]
+        out = (ns, mp, pairs, np.ascontiguousarray(moved[0, :, 0]), wide[0], wide[1], wide[2:])
+        return out if counts else host.mixing_summary(*out)
+
+    def mixing_windows(self, W):
+        """-> (samples, moved_pairs, uint64 [windows]) of the whole genome, identical on every rank: the ranks'
+        contributions (windows of global sites) are all-gathered and summed"""
+        ns, mp, own = self.dev.mixing_windows(W)
+        return ns, mp, self._gather_sums(ns, [own], NOUN["mixing"])[0]
+
     def owned_paths(self):
         return self.dev.paths().slice_sites(self.left, self.n_loc - self.right)
 
@@ -501,7 +522,8 @@ class ShardedSampler:
 # what needs nothing from the other ranks is the engine's own
 forward_to_dev(ShardedSampler, LIFECYCLE + [
     "set_model", "scale_jump_times", "window_stats_scale_exps", "lineage_origins_layout", "lineage_origin_rows",
-    "lineage_origins_scale_exp", "domain_stats_layout", "domain_turnover_layout", "spatial_correlation_layout"])
+    "lineage_origins_scale_exp", "domain_stats_layout", "domain_turnover_layout", "spatial_correlation_layout",
+    "mixing_layout"])
 
 
 class LocalGroup:
@@ -733,7 +755,7 @@ class LocalGroup:
             s.set_capacity(capacity)
 
     # ---- the posterior summaries: every shard counts the sites it owns.  enable_<stem>,
-    # reset_<stem>, accumulate_<stem> and <stem>_samples of every row of SUMMARIES are made below the class of the
+    # reset_<stem>, accumulate_<stem> and <stem>_samples of every row of SUMMARIES and DIAGNOSTICS are made below the class of the
     # three helpers here (enable_spatial_correlation is written out: it keeps the lag).  A read-out takes every
     # shard's, wants the same number of samples of all, and concatenates along sites, adds integers or merges parts
     def _each_call(self, name, *args, **kwargs):
@@ -914,6 +936,33 @@ class LocalGroup:
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
 
+    # chain mixing diagnostics: rows by site; the shards ran the same runs, so their pair counts agree
+    def mixing_layout(self):
+        """(first local site of the first shard, sites over all shards, max_lag)"""
+        lay = self._each_call("mixing_layout")
+        return lay[0][0], sum(v[1] for v in lay), lay[0][2]
+
+    def _mixing_parts(self, name, *args):
+        ns, parts = self._parts("mixing", name, *args)
+        if any(p[1] != parts[0][1] for p in parts) or (
+                name == "mixing" and any(not np.array_equal(p[2], parts[0][2]) for p in parts)):
+            raise RuntimeError("the shards of the group hold mixing samples of different runs (their pair counts differ)")
+        return ns, parts
+
+    def mixing(self, counts=False):
+        """-> DeviceSampler.mixing over the group's owned sites, shards in genome order"""
+        ns, parts = self._mixing_parts("mixing", True)
+        out = (ns, parts[0][1], parts[0][2], self._along_sites(parts, 3, axis=0), self._along_sites(parts, 4, axis=0),
+               self._along_sites(parts, 5, axis=0), self._along_sites(parts, 6, axis=1))
+        return out if counts else host.mixing_summary(*out)
+
+    def mixing_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, moved_pairs, uint64 [windows]): the shards' contributions to the windows of W global sites,
+        added"""
+        W, n_windows = self._windows(W, first_window, n_windows)
+        ns, parts = self._mixing_parts("mixing_windows", W, first_window, n_windows)
+        return ns, parts[0][1], self._added(parts, 2)
+
     # epoch statistics: every shard adds the triples centred at its owned sites
     def epoch_stats_layout(self):
         return self.subs[0].epoch_stats_layout()
@@ -968,7 +1017,7 @@ def _enable_on_every_shard(name):
     return method
 
 
-for _s in SUMMARIES:
+for _s in LAYERS:
     if "enable_" + _s.stem not in vars(LocalGroup):
         setattr(LocalGroup, "enable_" + _s.stem, _enable_on_every_shard("enable_" + _s.stem))
     setattr(LocalGroup, "reset_" + _s.stem, summary_method(LocalGroup._reset_summary, _s, "reset_" + _s.stem))

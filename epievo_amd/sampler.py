@@ -14,7 +14,7 @@ import numpy as np
 from . import _build
 from . import host
 from .host import FlatPaths
-from .summaries import LIFECYCLE, SUMMARIES, _per_sample, _window_range, summary_method
+from .summaries import LAYERS, LIFECYCLE, _per_sample, _window_range, summary_method
 
 _lib = None
 
@@ -38,6 +38,7 @@ class _Counters(C.Structure):
 
 MAX_CAPACITY = 2047    # EPV_MAX_CAP: jump slots per (site, branch)
 EPOCH_MAX_P = 256      # EPV_EPOCH_MAX_P: epochs per branch of the epoch statistics
+MIXING_MAX_LAG = 16    # EPV_MIX_MAX_LAG: lags of the mixing diagnostics
 
 
 def _abi():
@@ -76,7 +77,7 @@ def _abi():
         "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
         "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
         "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
-        # the summaries: what is particular to each (the four lifecycle entry points of each follow from SUMMARIES)
+        # the summaries: what is particular to each (the four lifecycle entry points of each follow from LAYERS)
         "epv_get_path_average": [vp, u64, u64, u32p], "epv_path_average_layout": [vp, u32p, u64p, u64p],
         "epv_branch_events_set_samples": [vp, u64], "epv_branch_events_layout": [vp, u64p, u64p],
         "epv_get_branch_events": [vp, u64, u64, u32p], "epv_get_branch_event_windows": [vp, u64, u64, u64, u64p],
@@ -96,12 +97,14 @@ def _abi():
         "epv_get_domain_turnover": [vp, u64p, u64p, u64p],
         "epv_spatial_correlation_layout": [vp, u32p, u32p, u64p, u64p, u64p],
         "epv_get_spatial_correlation": [vp, u64p, u64p],
+        "epv_mixing_layout": [vp, u64p, u64p, u32p], "epv_mixing_pairs": [vp, u64p],
+        "epv_mixing_counts": [vp, u64, u64, u32p, u64p], "epv_mixing_windows": [vp, u64, u64, u64, u64p],
     }
     # epv_set_<stem>: what switches the summary on, after the context
     set_args = {"path_average": [u32], "branch_events": [i], "window_stats": [u64], "epoch_stats": [u32],
                 "lineage_origins": [i], "domain_stats": [u64], "change_patterns": [i], "domain_turnover": [u64],
-                "spatial_correlation": [u32, u64]}
-    for s in SUMMARIES:
+                "spatial_correlation": [u32, u64], "mixing": [u32]}
+    for s in LAYERS:
         args["epv_set_" + s.stem] = [vp] + set_args[s.stem]
         args["epv_reset_" + s.stem] = args["epv_accumulate_" + s.stem] = [vp]
         args["epv_%s_samples" % s.stem] = [vp, u64p]
@@ -215,7 +218,7 @@ class DeviceSampler:
         return _window_range(W, max(self.n_global, self.n_sites), first_window, n_windows)
 
     # what every summary has besides enable_<stem>, its layout and its read-outs: reset_<stem>, accumulate_<stem>
-    # and <stem>_samples are made of these three, one set per row of SUMMARIES (below the class)
+    # and <stem>_samples are made of these three, one set per row of SUMMARIES and DIAGNOSTICS (below the class)
     def _reset_summary(self, s):
         self._ck(getattr(self.L, "epv_reset_" + s.stem)(self.h))
 
@@ -866,8 +869,44 @@ class DeviceSampler:
         _, k, fixT = self.epoch_stats_layout()
         return host.epoch_finish(raw, fixT, k, ns, counts)
 
+    # ---- chain mixing diagnostics (epv_set_mixing)
+    def enable_mixing(self, max_lag=8):
+        """count, per site, the linked sample pairs whose history differs, and the sums of the site's jump count x
+        and of its lagged products up to max_lag (1 .. MIXING_MAX_LAG) after every batch sweep of run_mcmc, the state
+        after burn-in as the opening state of the run (0 = off)"""
+        self._ck(self.L.epv_set_mixing(self.h, int(max_lag)))
 
-for _s in SUMMARIES:
+    def mixing_layout(self):
+        """(first local site, number of sites, max_lag): the sites of path_average_layout; zeros when off"""
+        a, k, ml = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._ck(self.L.epv_mixing_layout(self.h, C.byref(a), C.byref(k), C.byref(ml)))
+        return int(a.value), int(k.value), int(ml.value)
+
+    def mixing(self, counts=False):
+        """counts=True -> (samples, moved_pairs, pairs uint64[K + 1] (pairs[k] at lag k, pairs[0] = 0), moved
+        uint32[sites], S1 uint64[sites], S2 uint64[sites], C uint64[K, sites]); otherwise the dict
+        host.mixing_summary makes of them"""
+        first, cnt, K = self.mixing_layout()
+        words = np.zeros(MIXING_MAX_LAG + 2, np.uint64)
+        self._ck(self.L.epv_mixing_pairs(self.h, _p(words, C.c_uint64)))
+        moved, sums = np.zeros(cnt, np.uint32), np.zeros((2 + K, cnt), np.uint64)
+        self._ck(self.L.epv_mixing_counts(self.h, first, cnt, _p(moved, C.c_uint32), _p(sums, C.c_uint64)))
+        pairs = np.concatenate([np.zeros(1, np.uint64), words[2:2 + K]])
+        out = (int(words[0]), int(words[1]), pairs, moved, sums[0], sums[1], sums[2:])
+        return out if counts else host.mixing_summary(*out)
+
+    def mixing_windows(self, W, first_window=0, n_windows=None):
+        """-> (samples, moved_pairs, uint64 [windows]): moved summed over windows of W consecutive global sites, this
+        context's contribution (zero where it counts no site); all windows of the genome unless a range is given"""
+        W, n_windows = self._window_range(W, first_window, n_windows)
+        out = np.zeros(n_windows, np.uint64)
+        words = np.zeros(MIXING_MAX_LAG + 2, np.uint64)
+        self._ck(self.L.epv_mixing_pairs(self.h, _p(words, C.c_uint64)))
+        self._ck(self.L.epv_mixing_windows(self.h, W, int(first_window), n_windows, _p(out, C.c_uint64)))
+        return int(words[0]), int(words[1]), out
+
+
+for _s in LAYERS:
     setattr(DeviceSampler, "reset_" + _s.stem, summary_method(DeviceSampler._reset_summary, _s, "reset_" + _s.stem))
     setattr(DeviceSampler, "accumulate_" + _s.stem,
             summary_method(DeviceSampler._accumulate_summary, _s, "accumulate_" + _s.stem,
@@ -970,4 +1009,5 @@ forward_to_dev(SingleSiteSampler, LIFECYCLE + [
     "lineage_origins_layout", "lineage_origin_rows", "lineage_origins_scale_exp", "lineage_origins",
     "lineage_origin_windows", "domain_stats_layout", "domain_stats_part", "domain_stats", "change_patterns_layout",
     "change_patterns", "change_pattern_windows", "domain_turnover_layout", "domain_turnover_part", "domain_turnover",
-    "spatial_correlation_layout", "spatial_correlation_part", "spatial_correlation"])
+    "spatial_correlation_layout", "spatial_correlation_part", "spatial_correlation", "mixing_layout", "mixing",
+    "mixing_windows"])

@@ -19,9 +19,15 @@ SUMMARIES = (
     Summary("domain_turnover", "a", "domain-turnover"),
     Summary("spatial_correlation", "a", "spatial-correlation"),
 )
-NOUN = {s.stem: s.noun for s in SUMMARIES}
-# the four methods every sampler has for every summary
-LIFECYCLE = [fmt % s.stem for s in SUMMARIES for fmt in ("enable_%s", "reset_%s", "accumulate_%s", "%s_samples")]
+# what run_mcmc can take besides: diagnostics of the chain itself, the same record and the same lifecycle.  After
+# SUMMARIES in kLayers
+DIAGNOSTICS = (
+    Summary("mixing", "a", "mixing"),
+)
+LAYERS = SUMMARIES + DIAGNOSTICS
+NOUN = {s.stem: s.noun for s in LAYERS}
+# the four methods every sampler has for every summary and diagnostic
+LIFECYCLE = [fmt % s.stem for s in LAYERS for fmt in ("enable_%s", "reset_%s", "accumulate_%s", "%s_samples")]
 
 
 def summary_method(helper, row, name, doc=None):

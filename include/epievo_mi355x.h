@@ -755,6 +755,41 @@ int epv_spatial_correlation_layout(epv_ctx *ctx, uint32_t *n_rows, uint32_t *max
                                    uint64_t *chunk_sites);
 int epv_get_spatial_correlation(epv_ctx *ctx, uint64_t *n11, uint64_t *edges);
 
+/* ---- chain mixing diagnostics (new): whether the means above can be trusted.  Per site of the sites the path
+ * average counts, over the samples: moved = linked sample pairs (t - 1, t) whose whole history on the tree differs
+ * (every branch's init state, jump count and the bit pattern of every jump time; content, not the buffer flag, so
+ * an accepted proposal identical to the path is no move); with x_t the site's jumps over all branches, S1 = sum
+ * x_t, S2 = sum x_t^2 and C_k = sum x_t x_{t-k} over linked pairs at lag k = 1 .. K = max_lag <= 16.  All exact
+ * integers, independent of context, shard, GPU and kernel path.  Histories are compared through a 64-bit
+ * fingerprint per site: a collision (2^-64) undercounts one move.
+ * A RUN is a sequence of samples each linked to its predecessor.  epv_run_mcmc*: the state after burn-in opens a
+ * run (its fingerprint is kept; it is no sample and enters no sum), each of the batch samples is linked to the one
+ * before it, and the run closes when the call ends: a call adds batch to samples and to moved_pairs and
+ * max(0, batch - k) to pairs[k].  epv_accumulate_mixing: the sample is linked if and only if a run is open and
+ * exactly one sweep has run since its last sample; otherwise it opens a new run (counted in samples, S1 and S2,
+ * linked to nothing).  epv_upload_paths (and whatever else replaces the paths), epv_scale_jump_times and
+ * epv_reset_mixing close the run.
+ * epv_set_mixing: max_lag 1 .. 16 allocates 28 + 12 max_lag bytes per counted site (checked against the free
+ *   device memory first) and zeroes them; 0 frees everything; more than 16 is EPV_ERR_ARG.  samples never pass
+ *   min(2^21, floor((2^64 - 1) / (B C)^2)) with C the capacity of now (no sum wraps): a further sample is
+ *   EPV_ERR_STATE, and so is a run whose batch would pass it, refused before its first sweep.  A changed site range
+ *   lays out again before the first sample and is EPV_ERR_STATE after it.  Off by default: nothing allocated,
+ *   nothing launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_mixing_layout: the local sites first .. first+count-1 and max_lag (zeros when off).
+ * epv_mixing_pairs: words[K + 2] = samples, moved_pairs, pairs[1 .. K].
+ * epv_mixing_counts: moved[count] uint32 and sums[2 + K][count] uint64 (rows S1, S2, C_1 .. C_K) of the local
+ *   sites first .. first+count-1.
+ * epv_mixing_windows: moved summed over windows of W global sites, sums[n_windows], this context's contribution
+ *   (as epv_get_branch_event_windows). */
+int epv_set_mixing(epv_ctx *ctx, uint32_t max_lag);
+int epv_reset_mixing(epv_ctx *ctx);
+int epv_accumulate_mixing(epv_ctx *ctx);
+int epv_mixing_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_mixing_layout(epv_ctx *ctx, uint64_t *first, uint64_t *count, uint32_t *max_lag);
+int epv_mixing_pairs(epv_ctx *ctx, uint64_t *words);
+int epv_mixing_counts(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *moved, uint64_t *sums);
+int epv_mixing_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows, uint64_t *sums);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

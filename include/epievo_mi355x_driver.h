@@ -82,6 +82,14 @@ int epvd_download_branch_events(epvd_sampler *s, uint32_t *planes);
 int epvd_download_branch_event_windows(epvd_sampler *s, uint64_t W, uint64_t n_windows, uint64_t *sums,
                                        uint64_t *n_samples);
 
+/* chain mixing diagnostics (epv_set_mixing on every context, max_lag = 0: off; kept across epvd_reset, which starts
+ * the counts from zero).  Sizes first: the sites of this process and max_lag K; then the copy of words[K + 2]
+ * (samples, moved_pairs, pairs[1 .. K]: the same on every context, else an error), moved[site] and
+ * sums[r * sites + site] (rows S1, S2, C_1 .. C_K) in genome order */
+int epvd_set_mixing(epvd_sampler *s, uint32_t max_lag);
+int epvd_mixing_sizes(epvd_sampler *s, uint64_t *n_sites, uint32_t *max_lag);
+int epvd_download_mixing(epvd_sampler *s, uint64_t *words, uint32_t *moved, uint64_t *sums);
+
 /* regional sufficient statistics (epv_set_window_stats on every context, W = 0: off; kept across epvd_reset,
  * which starts the sums from zero).  Sizes first: W as clamped to the genome, n_windows = ceil(genome
  * length / W) and the sample count; then the copy of counts[(w * (n_nodes-1) + b-1) * 16 + c] (int64, J[8]
