@@ -29,6 +29,7 @@
 #include "epv_domains.h"
 #include "epv_turnover.h"
 #include "epv_corr.h"
+#include "epv_dmaps.h"
 #include "epv_patterns.h"
 
 // The library's knobs: environment variables that a context reads once, when epv_create makes it.
@@ -212,6 +213,20 @@ struct MixingState {
   uint64_t out_cap = 0;                   // bytes
 };
 
+// domain maps (epv_dmaps.h), off while Z.K == 0
+struct DmapsState {
+  EpvDmapSizes Z{};                       // the sizes
+  uint32_t state = 1;                     // the state whose runs are located
+  uint64_t max = 0;                       // samples the edge records are allocated for
+  uint32_t *d_counts = nullptr;           // [N][K][at.cnt] memberships inside the counted stretch, over the samples
+  unsigned long long *d_edge = nullptr;   // [max][N][2][EW] the first and the last E bits of every sample's rows
+  unsigned long long *d_bits = nullptr;   // [N][words] scratch: the rows of one sample, 64 sites a word
+  SiteLayout at;                          // (without B: the tree is compared itself)
+  uint64_t words = 0;
+  uint32_t N = 0, child0 = 0, EW = 0;     // nodes, the root's lowest-numbered child, words of an edge record
+  uint64_t samples = 0;
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -304,6 +319,7 @@ struct epv_ctx {
   TurnoverState to;
   CorrState co;
   MixingState mx;
+  DmapsState dp;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -806,7 +822,7 @@ struct Layer {
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr, kMixing;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr, kMixing, kDmaps;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -1771,10 +1787,111 @@ int launch_mixing(epv_ctx *c) {
 const Layer kMixing = {mixing_on, ensure_mixing, mixing_check_cap, launch_mixing, mixing_off, begin_mixing,
                        "mixing diagnostics are off: epv_set_mixing first", "the mixing diagnostics"};
 
+// ---- domain maps (epv_dmaps.h): the sites of pavg_range, N rows; a context keeps its PART
+bool dmaps_on(const epv_ctx *c) { return c->dp.Z.K != 0u; }
+void dmaps_off(epv_ctx *c) {
+  dfree(c->dp.d_counts); dfree(c->dp.d_edge); dfree(c->dp.d_bits);
+  c->dp = DmapsState{};
+}
+// (re)lay out the part for the current tree and site range; zeroes it
+int dmaps_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, false);
+  const uint64_t cnt = at.cnt;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->dp.d_counts); dfree(c->dp.d_edge); dfree(c->dp.d_bits);
+  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain maps take at most 2^32 - 1 sites per context");
+  const uint32_t K = c->dp.Z.K, LK = c->dp.Z.L[K - 1u], E = 2u * (LK - 1u), EW = (E + 63u) / 64u;
+  if (cnt < E) {   // (a run's membership is decided inside two adjacent parts, never three)
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "domain maps: this context counts %llu sites, fewer than the %u of an edge record "
+                  "(twice the largest size %u less one): a context's stretch holds at least those (the maps are off)",
+                  (unsigned long long)cnt, E, LK);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const uint32_t N = c->S.N;
+  const uint64_t words = (cnt + 63u) / 64u;
+  const double need = 4.0 * N * K * (double)cnt + 8.0 * N * (double)words + 16.0 * N * EW * (double)c->dp.max;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[400];
+    std::snprintf(buf, sizeof buf, "domain maps need %.3g GB of device memory (4 B x %u nodes x %u sizes x %llu sites of "
+                  "counts, 16 B x %u nodes x %u words x %llu samples of edge records, 8 B x %u nodes x %llu words of node "
+                  "states); %.3g GB are free: ask for fewer sizes or samples, or use more GPUs (the maps are off)",
+                  need / 1e9, N, K, (unsigned long long)cnt, N, EW, (unsigned long long)c->dp.max, N,
+                  (unsigned long long)words, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t counts_b = (size_t)4u * N * K * cnt, edge_b = (size_t)16u * N * EW * c->dp.max;
+  if (counts_b) {
+    HIP_TRY(c, hipMalloc(&c->dp.d_counts, counts_b));
+    HIP_TRY(c, hipMemsetAsync(c->dp.d_counts, 0, counts_b, c->stream));
+    HIP_TRY(c, hipMalloc(&c->dp.d_bits, (size_t)8u * N * words));
+  }
+  if (edge_b) {
+    HIP_TRY(c, hipMalloc(&c->dp.d_edge, edge_b));
+    HIP_TRY(c, hipMemsetAsync(c->dp.d_edge, 0, edge_b, c->stream));
+  }
+  c->dp.at = at;
+  c->dp.words = words;
+  c->dp.N = N;
+  c->dp.child0 = corr_child0(c);
+  c->dp.EW = EW;
+  c->dp.samples = 0;
+  return EPV_OK;
+}
+// the part matches the current site range, number of nodes and the root's first child (nothing else of the tree
+// matters: a row is one branch's meta words, and no jump time is read)
+int ensure_dmaps(epv_ctx *c) {
+  const bool sites = !(pavg_layout(c, true, false) == c->dp.at);
+  const bool tree = c->S.N != c->dp.N || corr_child0(c) != c->dp.child0;
+  if (!sites && !tree) return EPV_OK;
+  if (c->dp.samples) {
+    if (sites) return sites_changed(c, kDmaps, "epv_set_domain_maps");
+    return fail(c, EPV_ERR_STATE, "the tree changed after the domain maps took samples: read them out and "
+                                  "epv_reset_domain_maps");
+  }
+  return relayout(c, kDmaps, dmaps_alloc);
+}
+int dmaps_check_cap(epv_ctx *c, uint64_t more) {
+  if (c->dp.samples + more > c->dp.max) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "domain maps hold %llu of the %llu samples their edge records were allocated for, "
+                  "and %llu more were asked: read them out and epv_reset_domain_maps, or epv_set_domain_maps with more",
+                  (unsigned long long)c->dp.samples, (unsigned long long)c->dp.max, (unsigned long long)more);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return check_cap32(c, c->dp.samples, more, "domain maps", "epv_reset_domain_maps");
+}
+// the resident paths as one sample (ensure_dmaps first): pack the rows, then add every site's memberships
+int launch_dmaps(epv_ctx *c) {
+  int rc = dmaps_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->dp.at.cnt) {
+    const uint64_t words = c->dp.words, chunks = (words + EPV_DMAPS_CHUNK_WORDS - 1u) / EPV_DMAPS_CHUNK_WORDS;
+    hipLaunchKernelGGL(epv_dmaps_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S,
+                       c->dp.at.lo, c->dp.at.cnt, words, c->dp.child0, c->dp.state, c->dp.d_bits);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *edge = c->dp.d_edge + c->dp.samples * 2u * c->dp.N * c->dp.EW;   // (never read while EW == 0)
+    for (uint32_t v0 = 0; v0 < c->dp.N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
+      const uint32_t nv = std::min<uint32_t>(65535u, c->dp.N - v0);
+      hipLaunchKernelGGL(epv_dmaps_member_kernel, dim3((unsigned)chunks, nv), dim3(256), 0, c->stream,
+                         (const unsigned long long *)c->dp.d_bits, words, c->dp.at.cnt, v0, c->dp.Z, c->dp.d_counts, edge);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  ++c->dp.samples;
+  return EPV_OK;
+}
+const Layer kDmaps = {dmaps_on, ensure_dmaps, dmaps_check_cap, launch_dmaps, dmaps_off, nullptr,
+                      "domain maps are off: epv_set_domain_maps first", "the domain maps"};
+
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
 const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover, &kCorr,
-                                &kMixing};
+                                &kMixing, &kDmaps};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -4289,6 +4406,82 @@ EPV_API int epv_get_spatial_correlation(epv_ctx *c, uint64_t *n11, uint64_t *edg
   HIP_TRY(c, hipMemcpy(n11, c->co.d_n11, (size_t)8u * c->co.R * (c->co.L + 1u), hipMemcpyDeviceToHost));
   if (c->co.samples)
     HIP_TRY(c, hipMemcpy(edges, c->co.d_edge, (size_t)16u * c->co.R * c->co.LW * c->co.samples, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+// ---- domain maps (epv_dmaps.h)
+EPV_API int epv_set_domain_maps(epv_ctx *c, uint32_t n_sizes, const uint32_t *sizes, uint32_t state, uint64_t max_samples) {
+  if (!n_sizes) return layer_set_off(c, kDmaps);
+  if (!c) return EPV_ERR_ARG;
+  if (!sizes) return fail(c, EPV_ERR_ARG, "null sizes");
+  if (n_sizes > EPV_DMAPS_MAX_SIZES) return fail(c, EPV_ERR_ARG, "domain maps take at most 4 sizes");
+  for (uint32_t k = 0; k < n_sizes; ++k) {
+    if (sizes[k] < 1u || sizes[k] > EPV_DMAPS_MAX_SIZE) return fail(c, EPV_ERR_ARG, "domain maps take sizes 1 .. 1024");
+    if (k && sizes[k] <= sizes[k - 1u]) return fail(c, EPV_ERR_ARG, "domain maps take strictly increasing sizes");
+  }
+  if (state > 1u) return fail(c, EPV_ERR_ARG, "domain maps: the state is 0 or 1");
+  if (!max_samples) return fail(c, EPV_ERR_ARG, "domain maps: max_samples is at least 1");
+  if (max_samples > EPV_DMAPS_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain maps take at most 2^21 samples");
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->dp.Z = EpvDmapSizes{};
+  c->dp.Z.K = n_sizes;
+  for (uint32_t k = 0; k < n_sizes; ++k) c->dp.Z.L[k] = sizes[k];
+  c->dp.state = state;
+  c->dp.max = max_samples;
+  return layer_set_on(c, kDmaps, dmaps_alloc);
+}
+
+EPV_API int epv_reset_domain_maps(epv_ctx *c) {
+  const int rc = layer_entry(c, kDmaps);
+  if (rc) return rc;
+  const size_t counts_b = (size_t)4u * c->dp.N * c->dp.Z.K * c->dp.at.cnt, edge_b = (size_t)16u * c->dp.N * c->dp.EW * c->dp.max;
+  if (counts_b) HIP_TRY(c, hipMemsetAsync(c->dp.d_counts, 0, counts_b, c->stream));
+  if (edge_b) HIP_TRY(c, hipMemsetAsync(c->dp.d_edge, 0, edge_b, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->dp.samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_domain_maps(epv_ctx *c) { return layer_accumulate(c, kDmaps); }
+
+EPV_API int epv_domain_maps_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->dp.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_domain_maps_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_sizes, uint32_t *sizes, uint32_t *state,
+                                   uint64_t *first, uint64_t *count, uint64_t *chunk_sites) {
+  if (!c || !n_nodes || !n_sizes || !sizes || !state || !first || !count || !chunk_sites) return EPV_ERR_ARG;
+  *n_nodes = *n_sizes = *state = 0;
+  for (uint32_t k = 0; k < EPV_DMAPS_MAX_SIZES; ++k) sizes[k] = 0;
+  *first = *count = *chunk_sites = 0;
+  if (!dmaps_on(c)) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->dp.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_dmaps(c);
+    if (rc) return rc;
+  }
+  *n_nodes = c->dp.N;
+  *n_sizes = c->dp.Z.K;
+  for (uint32_t k = 0; k < c->dp.Z.K; ++k) sizes[k] = c->dp.Z.L[k];
+  *state = c->dp.state;
+  *first = c->dp.at.lo;
+  *count = c->dp.at.cnt;
+  *chunk_sites = 64ull * EPV_DMAPS_CHUNK_WORDS;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_domain_maps(epv_ctx *c, uint32_t *counts, uint64_t *edges) {
+  const int rc = layer_entry(c, kDmaps);
+  if (rc) return rc;
+  if (!counts || !edges) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t counts_b = (size_t)4u * c->dp.N * c->dp.Z.K * c->dp.at.cnt;
+  const size_t edge_b = (size_t)16u * c->dp.N * c->dp.EW * c->dp.samples;
+  if (counts_b) HIP_TRY(c, hipMemcpy(counts, c->dp.d_counts, counts_b, hipMemcpyDeviceToHost));
+  if (edge_b) HIP_TRY(c, hipMemcpy(edges, c->dp.d_edge, edge_b, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 

@@ -45,6 +45,10 @@
 // sums of the site's jump count and of its lagged products up to lag K), per window of W sites: the integer sum of
 // the moves, the move rate, the pooled autocorrelations and their integrated autocorrelation time
 // (epv::write_mixing).  Changes nothing else the run writes.
+// New: -D/--maps FILE with -z/--sizes L1,L2,.. (default 5,20; 1 to 4 increasing sizes of 1 .. 1024), -S/--state s
+// (default 1) and the same -w/--window W: the domain maps of the B batch sweeps (epv_set_domain_maps with max_samples =
+// B: per node, size and site the samples in which the site lies in a run of state s of at least that size), summed
+// over windows of W sites, as integers (epv::write_domain_maps).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -52,6 +56,7 @@
 #include <stdexcept>
 
 #include "epievo_mi355x.h"
+#include "epv_dmaps.hpp"
 #include "epv_io.hpp"
 #include "epv_model.hpp"
 #include "epv_options.hpp"
@@ -70,12 +75,12 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
     const size_t no_lag = std::numeric_limits<size_t>::max();
-    size_t max_lag = no_lag, mixing_lag = no_lag;
+    size_t max_lag = no_lag, mixing_lag = no_lag, maps_state = no_lag;
     const size_t no_window = std::numeric_limits<size_t>::max();
     size_t window = no_window;
     size_t rng_seed = std::numeric_limits<size_t>::max();
@@ -116,9 +121,14 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("mixing", 'x', "output file of the chain mixing diagnostics of the batch sweeps per window (moves, "
                       "move rate, autocorrelations of the jump count)", false, mixing_file);
     opt_parse.add_opt("acflags", 'A', "largest lag of the mixing diagnostics (default 8, at most 16)", false, mixing_lag);
+    opt_parse.add_opt("maps", 'D', "output file of the domain maps of the batch sweeps (integer window sums)", false,
+                      maps_file);
+    opt_parse.add_opt("sizes", 'z', "sizes of the domain maps: 1 to 4 increasing numbers of sites, at most 1024 (default "
+                      "5,20)", false, maps_sizes);
+    opt_parse.add_opt("state", 'S', "state whose domains the maps locate: 0 or 1 (default 1)", false, maps_state);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
-    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps and "
-                      "change patterns (default 1)", false, window);
+    opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps, "
+                      "change patterns, mixing diagnostics and domain maps (default 1)", false, window);
     vector<string> leftover_args;
     opt_parse.parse(argc, argv, leftover_args);
     if (argc == 1 || opt_parse.help_requested()) {
@@ -140,10 +150,11 @@ int main(int argc, const char **argv) {
     if (!average_file.empty() && (n_points < 2 || n_points > 0xffffffffu))
       throw std::runtime_error("-n: the number of points must be at least 2");
     if (window != no_window && changes_file.empty() && regional_file.empty() && origins_file.empty() &&
-        patterns_file.empty() && mixing_file.empty())
-      throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional, -O/--origins and -P/--patterns: "
-                               "give the output file of the branch-event maps, of the regional statistics, of the "
-                               "origin maps or of the change patterns");
+        patterns_file.empty() && mixing_file.empty() && maps_file.empty())
+      throw std::runtime_error("-w/--window belongs to -c/--changes, -r/--regional, -O/--origins, -P/--patterns, "
+                               "-x/--mixing and -D/--maps: give the output file of the branch-event maps, of the "
+                               "regional statistics, of the origin maps, of the change patterns, of the mixing "
+                               "diagnostics or of the domain maps");
     if (n_epochs != no_epochs && epochs_file.empty())
       throw std::runtime_error("-K/--nepochs belongs to -E/--epochs: give the output file of the epoch statistics");
     if (n_epochs == no_epochs) n_epochs = 10;
@@ -156,6 +167,24 @@ int main(int argc, const char **argv) {
       throw std::runtime_error("-A/--acflags belongs to -x/--mixing: give the output file of the mixing diagnostics");
     if (mixing_lag == no_lag) mixing_lag = 8;
     if (mixing_lag == 0 || mixing_lag > 16) throw std::runtime_error("-A: a largest lag of 1 to 16 samples");
+    if ((!maps_sizes.empty() || maps_state != no_lag) && maps_file.empty())
+      throw std::runtime_error("-z/--sizes and -S/--state belong to -D/--maps: give the output file of the domain maps");
+    if (maps_state == no_lag) maps_state = 1;
+    if (maps_state > 1) throw std::runtime_error("-S: the state is 0 or 1");
+    vector<uint32_t> map_sizes;
+    if (!maps_file.empty()) {
+      const string text = maps_sizes.empty() ? "5,20" : maps_sizes;
+      for (size_t a = 0; a <= text.size();) {
+        const size_t b = std::min(text.find(',', a), text.size());
+        const string item = text.substr(a, b - a);
+        if (item.empty() || item.size() > 4 || item.find_first_not_of("0123456789") != string::npos)
+          throw std::runtime_error("-z: sizes are numbers of sites separated by commas, as in 5,20");
+        map_sizes.push_back((uint32_t)std::stoul(item));
+        a = b + 1;
+      }
+      epv::check_domain_map_sizes((uint32_t)map_sizes.size(), map_sizes.data(), "-z");
+      if (batch > (1ull << 21)) throw std::runtime_error("-D/--maps: the domain maps take at most 2^21 batch sweeps (-B)");
+    }
     if (window == 0) throw std::runtime_error("-w: a window holds at least one site");
     if (window == no_window) window = 1;
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
@@ -211,6 +240,7 @@ int main(int argc, const char **argv) {
     if (!turnover_file.empty()) mcmc.set_domain_turnover(batch);
     if (!corr_file.empty()) mcmc.set_spatial_correlation((uint32_t)max_lag, batch);
     if (!mixing_file.empty()) mcmc.enable_mixing((uint32_t)mixing_lag);
+    if (!maps_file.empty()) mcmc.set_domain_maps(map_sizes, (uint32_t)maps_state, batch);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -309,6 +339,18 @@ int main(int argc, const char **argv) {
       mcmc.download_mixing(words, moved, sums);
       if (VERBOSE) cerr << "[WRITING MIXING DIAGNOSTICS OF " << words[0] << " SAMPLES: " << mixing_file << "]" << endl;
       epv::write_mixing(mixing_file, (uint32_t)mixing_lag, words.data(), moved.size(), window, moved.data(), sums.data());
+    }
+    if (!maps_file.empty()) {
+      vector<uint32_t> counts;
+      vector<uint64_t> edges;
+      uint32_t n_nodes = 0;
+      uint64_t n_samples = 0, n_sites = 0;
+      mcmc.download_domain_maps(counts, edges, n_nodes, n_samples, n_sites);
+      if (VERBOSE) cerr << "[WRITING DOMAIN MAPS OF " << n_samples << " SAMPLES: " << maps_file << "]" << endl;
+      vector<uint64_t> sums((size_t)n_nodes * map_sizes.size() * ((n_sites + window - 1u) / window), 0u);
+      epv::domain_map_windows(n_nodes, (uint32_t)map_sizes.size(), n_sites, counts.data(), window, sums.data());
+      epv::write_domain_maps(maps_file, th.node_names, n_samples, (uint32_t)maps_state, map_sizes, n_sites, window,
+                             sums.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

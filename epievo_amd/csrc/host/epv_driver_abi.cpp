@@ -40,6 +40,9 @@ struct epvd_sampler {
   bool have_staged_turnover = false;
   std::vector<uint64_t> staged_corr_n11, staged_corr_edges;   // between epvd_corr_part_sizes and epvd_download_corr_part
   bool have_staged_corr = false;
+  std::vector<uint32_t> staged_dmaps_counts;   // between epvd_dmaps_sizes and epvd_download_dmaps
+  std::vector<uint64_t> staged_dmaps_edges;
+  bool have_staged_dmaps = false;
   std::vector<uint64_t> staged_mix_words, staged_mix_sums;   // between epvd_mixing_sizes and epvd_download_mixing
   std::vector<uint32_t> staged_mix_moved;
   bool have_staged_mixing = false;
@@ -505,6 +508,36 @@ EPVD_API int epvd_download_corr_part(epvd_sampler *h, uint64_t *n11, uint64_t *e
     h->staged_corr_n11.clear();
     h->staged_corr_edges.clear();
     h->have_staged_corr = false;
+  });
+}
+EPVD_API int epvd_set_dmaps(epvd_sampler *h, uint32_t n_sizes, const uint32_t *sizes, uint32_t state,
+                                  uint64_t max_samples) {
+  return guarded(h, [&] {
+    h->s->set_domain_maps(n_sizes ? std::vector<uint32_t>(sizes, sizes + n_sizes) : std::vector<uint32_t>(), state, max_samples);
+  });
+}
+EPVD_API int epvd_reset_dmaps(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_domain_maps(); });
+}
+EPVD_API int epvd_accumulate_dmaps(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_domain_maps(); });
+}
+EPVD_API int epvd_dmaps_sizes(epvd_sampler *h, uint32_t *n_nodes, uint32_t *n_sizes, uint64_t *n_samples,
+                                    uint64_t *n_sites) {
+  return guarded(h, [&] {
+    h->s->download_domain_maps(h->staged_dmaps_counts, h->staged_dmaps_edges, *n_nodes, *n_samples, *n_sites);
+    *n_sizes = (uint32_t)h->s->domain_map_sizes().size();
+    h->have_staged_dmaps = true;
+  });
+}
+EPVD_API int epvd_download_dmaps(epvd_sampler *h, uint32_t *counts, uint64_t *edges) {
+  return guarded(h, [&] {
+    if (!h->have_staged_dmaps) throw std::runtime_error("epvd_dmaps_sizes first");
+    std::copy(h->staged_dmaps_counts.begin(), h->staged_dmaps_counts.end(), counts);
+    std::copy(h->staged_dmaps_edges.begin(), h->staged_dmaps_edges.end(), edges);
+    h->staged_dmaps_counts.clear();
+    h->staged_dmaps_edges.clear();
+    h->have_staged_dmaps = false;
   });
 }
 EPVD_API int epvd_download_corr(epvd_sampler *h, uint32_t n_rows, uint32_t max_lag, uint64_t *n11, uint64_t *left1,

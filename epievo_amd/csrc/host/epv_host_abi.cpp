@@ -14,6 +14,7 @@
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
 #include "epv_corr.hpp"
+#include "epv_dmaps.hpp"
 #include "epv_epochs.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
@@ -582,6 +583,66 @@ EPVH_API void epvh_spatial_correlation_copy(void *h, char *names, int names_len,
   std::copy(sc->right1.begin(), sc->right1.end(), right1);
 }
 EPVH_API void epvh_spatial_correlation_free(void *h) { delete (epv::SpatialCorrelation *)h; }
+
+// ---- domain maps: the membership rule, the CPU twin of the kernel and the merge of parts (epv_dmaps.hpp), the
+// file of epievo_est_histories -D
+EPVH_API int epvh_domain_map_members(const uint64_t *x, uint64_t nbits, uint32_t L, uint64_t *out) {
+  try {
+    epv::domain_map_members(x, nbits, L, out);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// bits [N][ceil(cnt / 64)]; counts [N][K][cnt] receives + 1 per membership, edges [N][2][EW] this sample's records
+EPVH_API int epvh_domain_maps_part(uint32_t N, uint32_t K, const uint32_t *sizes, uint64_t cnt, const uint64_t *bits,
+                                   uint32_t *counts, uint64_t *edges) {
+  try {
+    epv::domain_maps_part(N, K, sizes, cnt, bits, counts, edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// cnts, counts, edges: n_parts entries each, parts in genome order ([N][K][cnt], [samples][N][2][EW]); out_cnt: the
+// sites of the union
+EPVH_API int epvh_domain_maps_merge(uint64_t n_parts, uint32_t N, uint32_t K, const uint32_t *sizes, uint64_t samples,
+                                    const uint64_t *cnts, const uint32_t *const *counts, const uint64_t *const *edges,
+                                    uint32_t *out_counts, uint64_t *out_edges, uint64_t *out_cnt) {
+  try {
+    const uint64_t n = epv::domain_maps_merge(n_parts, N, K, sizes, samples, cnts, counts, edges, out_counts, out_edges);
+    if (out_cnt) *out_cnt = n;
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// node_names: the N node names joined by '\n'; sums [N][K][ceil(n_sites / W)]
+EPVH_API int epvh_write_domain_maps(const char *file, const char *node_names, uint64_t n_samples, uint32_t state,
+                                    uint32_t K, const uint32_t *sizes, uint64_t n_sites, uint64_t W, const uint64_t *sums) {
+  try {
+    epv::write_domain_maps(file, split_names(node_names), n_samples, state, std::vector<uint32_t>(sizes, sizes + K),
+                           n_sites, W, sums);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_domain_maps(const char *file) {
+  try {
+    return new epv::DomainMaps(epv::read_domain_maps(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+// words: samples, sites, window, state, nodes, K, length of the joined names with its terminator
+EPVH_API void epvh_domain_maps_dims(void *h, uint64_t *words) {
+  const epv::DomainMaps *dm = (const epv::DomainMaps *)h;
+  words[0] = dm->n_samples;
+  words[1] = dm->n_sites;
+  words[2] = dm->window;
+  words[3] = dm->state;
+  words[4] = dm->node_names.size();
+  words[5] = dm->sizes.size();
+  words[6] = join_names(dm->node_names).size() + 1u;
+}
+EPVH_API void epvh_domain_maps_copy(void *h, char *names, int names_len, uint32_t *sizes, uint64_t *sums) {
+  const epv::DomainMaps *dm = (const epv::DomainMaps *)h;
+  put_text(join_names(dm->node_names), names, names_len);
+  std::copy(dm->sizes.begin(), dm->sizes.end(), sizes);
+  std::copy(dm->sums.begin(), dm->sums.end(), sums);
+}
+EPVH_API void epvh_domain_maps_free(void *h) { delete (epv::DomainMaps *)h; }
 
 // ---- epoch statistics: closing the difference form (epv_epochs.hpp), and the file of epievo_est_histories -E
 EPVH_API void epvh_epoch_edges(uint64_t fixT, uint32_t P, uint64_t *out) { epv::epoch_edges(fixT, P, out); }

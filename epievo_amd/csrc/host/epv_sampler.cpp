@@ -16,6 +16,7 @@
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
 #include "epv_corr.hpp"
+#include "epv_dmaps.hpp"
 #include "epievo_mi355x_comm.h"
 
 namespace epv {
@@ -440,6 +441,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (turnover_max_) set_domain_turnover(turnover_max_);
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
   if (mixing_lag_) enable_mixing(mixing_lag_);
+  if (!dmaps_sizes_.empty()) set_domain_maps(dmaps_sizes_, dmaps_state_, dmaps_max_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -456,6 +458,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (turnover_max_) set_domain_turnover(turnover_max_);
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
   if (mixing_lag_) enable_mixing(mixing_lag_);
+  if (!dmaps_sizes_.empty()) set_domain_maps(dmaps_sizes_, dmaps_state_, dmaps_max_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -995,6 +998,64 @@ void SingleSiteSampler::download_spatial_correlation(std::vector<uint64_t> &n11,
   std::vector<uint64_t> none(1, 0u);
   corr_part_close(n_rows, max_lag, n_samples, n_sites, n11.data(), edges.empty() ? none.data() : edges.data(),
                   left1.data(), right1.data());
+}
+
+void SingleSiteSampler::set_domain_maps(const std::vector<uint32_t> &sizes, uint32_t state, uint64_t max_samples) {
+  if (!sizes.empty()) check_domain_map_sizes((uint32_t)sizes.size(), sizes.data(), "set_domain_maps");
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || sizes.empty())
+    for (epv_ctx *c : contexts())
+      check_on(c, epv_set_domain_maps(c, (uint32_t)sizes.size(), sizes.data(), state, max_samples), "epv_set_domain_maps");
+  dmaps_sizes_ = sizes;
+  dmaps_state_ = state;
+  dmaps_max_ = sizes.empty() ? 0u : max_samples;
+}
+
+void SingleSiteSampler::reset_domain_maps() {
+  if (dmaps_sizes_.empty()) throw std::runtime_error("domain maps are off: set_domain_maps first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_domain_maps(c), "epv_reset_domain_maps");
+}
+
+void SingleSiteSampler::accumulate_domain_maps() {
+  if (dmaps_sizes_.empty()) throw std::runtime_error("domain maps are off: set_domain_maps first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_domain_maps(c), "epv_accumulate_domain_maps");
+}
+
+void SingleSiteSampler::download_domain_maps(std::vector<uint32_t> &counts, std::vector<uint64_t> &edges, uint32_t &n_nodes,
+                                             uint64_t &n_samples, uint64_t &n_sites) {
+  if (dmaps_sizes_.empty()) throw std::runtime_error("domain maps are off: set_domain_maps first");
+  const std::vector<epv_ctx *> cs = contexts();   // in genome order
+  const uint32_t K = (uint32_t)dmaps_sizes_.size(), EW = dmaps_edge_words(dmaps_sizes_.back());
+  std::vector<std::vector<uint32_t>> a(cs.size());
+  std::vector<std::vector<uint64_t>> e(cs.size());
+  std::vector<const uint32_t *> ap(cs.size());
+  std::vector<const uint64_t *> ep(cs.size());
+  std::vector<uint64_t> cnts(cs.size(), 0u);
+  n_nodes = 0;
+  n_samples = n_sites = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t N = 0, k = 0, state = 0, sizes[4] = {0, 0, 0, 0};
+    uint64_t first = 0, count = 0, chunk = 0, ns = 0;
+    check_on(cs[i], epv_domain_maps_layout(cs[i], &N, &k, sizes, &state, &first, &count, &chunk), "epv_domain_maps_layout");
+    check_on(cs[i], epv_domain_maps_samples(cs[i], &ns), "epv_domain_maps_samples");
+    if (k != K || !std::equal(dmaps_sizes_.begin(), dmaps_sizes_.end(), sizes) || state != dmaps_state_)
+      throw std::runtime_error("a context holds domain maps of other sizes or another state");
+    if (i == 0) { n_nodes = N; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of domain-map samples");
+    else if (N != n_nodes) throw std::runtime_error("the contexts hold domain maps of different trees");
+    cnts[i] = count;
+    n_sites += count;
+    a[i].assign(std::max<size_t>((size_t)N * K * count, 1u), 0u);
+    e[i].assign(std::max<size_t>((size_t)ns * N * 2u * EW, 1u), 0u);
+    check_on(cs[i], epv_get_domain_maps(cs[i], a[i].data(), e[i].data()), "epv_get_domain_maps");
+    ap[i] = a[i].data(); ep[i] = e[i].data();
+  }
+  counts.assign(std::max<size_t>((size_t)n_nodes * K * n_sites, 1u), 0u);
+  edges.assign(std::max<size_t>((size_t)n_samples * n_nodes * 2u * EW, 1u), 0u);
+  domain_maps_merge(cs.size(), n_nodes, K, dmaps_sizes_.data(), n_samples, cnts.data(), ap.data(), ep.data(), counts.data(),
+                    edges.data());
+  counts.resize((size_t)n_nodes * K * n_sites);
+  edges.resize((size_t)n_samples * n_nodes * 2u * EW);
 }
 
 void SingleSiteSampler::set_epoch_stats(uint32_t P) {

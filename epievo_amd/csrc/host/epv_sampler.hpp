@@ -196,6 +196,16 @@ public:
   void download_spatial_correlation(std::vector<uint64_t> &n11, std::vector<uint64_t> &left1,
                                     std::vector<uint64_t> &right1, uint32_t &n_rows, uint32_t &max_lag,
                                     uint64_t &n_samples);
+  // domain maps (epv_set_domain_maps) on every context, with the spatial correlations' samples and lifecycle; no
+  // sizes is off.  download_domain_maps: the parts of all slots and contexts of this process merged in genome order
+  // (epv::domain_maps_merge): counts [n_nodes][sizes][n_sites], edges [samples][n_nodes][2][EW].  Of one process of
+  // several it is that process's stretch: merge the processes' parts in genome order the same way
+  void set_domain_maps(const std::vector<uint32_t> &sizes, uint32_t state, uint64_t max_samples);
+  const std::vector<uint32_t> &domain_map_sizes() const { return dmaps_sizes_; }
+  void reset_domain_maps();
+  void accumulate_domain_maps();
+  void download_domain_maps(std::vector<uint32_t> &counts, std::vector<uint64_t> &edges, uint32_t &n_nodes,
+                            uint64_t &n_samples, uint64_t &n_sites);
   // change patterns (epv_set_change_patterns) on every context, with the branch events' samples and lifecycle.
   // n_rows = 12 + 2 (n_nodes-1) + internal non-root nodes.  download_change_patterns: rows[r * sites + site] over
   // the sites of this process in genome order; download_change_pattern_windows: sums[r * n_windows + w] over
@@ -321,6 +331,9 @@ private:
   uint64_t turnover_max_ = 0; // set_domain_turnover
   uint32_t corr_lag_ = 0;     // set_spatial_correlation
   uint64_t corr_max_ = 0;
+  std::vector<uint32_t> dmaps_sizes_;   // set_domain_maps
+  uint32_t dmaps_state_ = 1;
+  uint64_t dmaps_max_ = 0;
   bool patterns_ = false;     // set_change_patterns
   uint32_t mixing_lag_ = 0;   // enable_mixing
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)

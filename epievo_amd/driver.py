@@ -31,6 +31,7 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_turnover_part_sizes", "epvd_download_turnover_part", "epvd_download_turnover",
                   "epvd_set_corr", "epvd_reset_corr", "epvd_accumulate_corr",
                   "epvd_corr_part_sizes", "epvd_download_corr_part", "epvd_download_corr",
+                  "epvd_set_dmaps", "epvd_reset_dmaps", "epvd_accumulate_dmaps", "epvd_dmaps_sizes", "epvd_download_dmaps",
                   "epvd_set_change_patterns", "epvd_change_patterns_sizes", "epvd_download_change_patterns",
                   "epvd_download_change_pattern_windows",
                   "epvd_set_mixing", "epvd_mixing_sizes", "epvd_download_mixing"]
@@ -111,6 +112,11 @@ def lib():
         L.epvd_corr_part_sizes.argtypes = [vp, u32p, u32p, u64p, u64p]
         L.epvd_download_corr_part.argtypes = [vp, u64p, u64p]
         L.epvd_download_corr.argtypes = [vp, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p]
+        L.epvd_set_dmaps.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, C.c_uint64]
+        L.epvd_reset_dmaps.argtypes = [vp]
+        L.epvd_accumulate_dmaps.argtypes = [vp]
+        L.epvd_dmaps_sizes.argtypes = [vp, u32p, u32p, u64p, u64p]
+        L.epvd_download_dmaps.argtypes = [vp, u32p, u64p]
         _lib = L
     return _lib
 
@@ -494,6 +500,36 @@ class CppSampler:
         hist, len_sum, ns = np.zeros((R, 2, 2, 128), np.uint64), np.zeros((R, 2, 2), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_turnover(self.h, R, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
         return int(ns.value), hist, len_sum
+
+    def enable_domain_maps(self, sizes, state=1, max_samples=1 << 21):
+        """domain maps on every context (DeviceSampler.enable_domain_maps; an empty list: off)"""
+        z = host.domain_map_sizes(sizes) if np.size(sizes) else np.zeros(0, np.uint32)
+        self._ck(self.L.epvd_set_dmaps(self.h, len(z), _p(z if len(z) else np.zeros(1, np.uint32), C.c_uint32), int(state),
+                                       int(max_samples)))
+        self._dmaps_sizes = tuple(int(L) for L in z)
+
+    def reset_domain_maps(self):
+        self._ck(self.L.epvd_reset_dmaps(self.h))
+
+    def accumulate_domain_maps(self):
+        self._ck(self.L.epvd_accumulate_dmaps(self.h))
+
+    def domain_maps_part(self):
+        """-> (samples, sites, counts uint32 [N, K, sites], edges uint64 [samples, N, 2, EW]): the parts of this
+        process's slots and contexts merged in genome order"""
+        N, K, ns, cnt = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epvd_dmaps_sizes(self.h, C.byref(N), C.byref(K), C.byref(ns), C.byref(cnt)))
+        N, K, ns, cnt = int(N.value), int(K.value), int(ns.value), int(cnt.value)
+        EW = (2 * (self._dmaps_sizes[-1] - 1) + 63) // 64
+        counts = np.zeros(max(N * K * cnt, 1), np.uint32)
+        edges = np.zeros(max(ns * N * 2 * EW, 1), np.uint64)
+        self._ck(self.L.epvd_download_dmaps(self.h, _p(counts, C.c_uint32), _p(edges, C.c_uint64)))
+        return ns, cnt, counts[:N * K * cnt].reshape(N, K, cnt), edges[:ns * N * 2 * EW].reshape(ns, N, 2, EW)
+
+    def domain_maps(self, counts=False):
+        """-> (samples, maps [N, K, sites]) over the sites of this process (DeviceSampler.domain_maps)"""
+        ns, _, c, _ = self.domain_maps_part()
+        return ns, _per_sample(c, ns, counts)
 
     def enable_spatial_correlation(self, max_lag, max_samples):
         """spatial correlations on every context, lags 0 .. max_lag, for at most max_samples samples (max_lag = 0:

@@ -106,6 +106,21 @@ def lib():
         L.epvh_spatial_correlation_copy.restype = None
         L.epvh_spatial_correlation_free.argtypes = [C.c_void_p]
         L.epvh_spatial_correlation_free.restype = None
+        u32pp = C.POINTER(u32p)
+        L.epvh_domain_map_members.argtypes = [u64p, C.c_uint64, C.c_uint32, u64p]
+        L.epvh_domain_maps_part.argtypes = [C.c_uint32, C.c_uint32, u32p, C.c_uint64, u64p, u32p, u64p]
+        L.epvh_domain_maps_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, u32p, C.c_uint64, u64p, u32pp, u64pp,
+                                             u32p, u64p, u64p]
+        L.epvh_write_domain_maps.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, C.c_uint64,
+                                             C.c_uint64, u64p]
+        L.epvh_read_domain_maps.argtypes = [C.c_char_p]
+        L.epvh_read_domain_maps.restype = C.c_void_p
+        L.epvh_domain_maps_dims.argtypes = [C.c_void_p, u64p]
+        L.epvh_domain_maps_dims.restype = None
+        L.epvh_domain_maps_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, u32p, u64p]
+        L.epvh_domain_maps_copy.restype = None
+        L.epvh_domain_maps_free.argtypes = [C.c_void_p]
+        L.epvh_domain_maps_free.restype = None
         u64p_, u32 = C.POINTER(C.c_uint64), C.c_uint32
         L.epvh_epoch_edges.argtypes = [C.c_uint64, u32, u64p_]
         L.epvh_epoch_edges.restype = None
@@ -698,6 +713,165 @@ def read_spatial_correlation(path):
                     row_names=buf.value.decode().split("\n") if R else [], n11=arrs[0], left1=arrs[1], right1=arrs[2])
     finally:
         L_.epvh_spatial_correlation_free(h)
+
+
+# ---- domain maps (per node, size and site: the samples in which the site lies in a run of at least that size)
+DOMAIN_MAP_MAX_SIZE, DOMAIN_MAP_MAX_SIZES = 1024, 4
+
+
+def domain_map_sizes(sizes):
+    """-> uint32 [K]: 1 .. 4 strictly increasing sizes of 1 .. 1024, or ValueError"""
+    z = [int(L) for L in np.atleast_1d(sizes)]
+    if not 1 <= len(z) <= DOMAIN_MAP_MAX_SIZES:
+        raise ValueError("domain maps take 1 .. %d sizes" % DOMAIN_MAP_MAX_SIZES)
+    if any(L < 1 or L > DOMAIN_MAP_MAX_SIZE for L in z):
+        raise ValueError("a size of the domain maps is 1 .. %d" % DOMAIN_MAP_MAX_SIZE)
+    if any(b <= a for a, b in zip(z[:-1], z[1:])):
+        raise ValueError("the sizes of the domain maps are strictly increasing")
+    return np.array(z, np.uint32)
+
+
+def domain_map_edge_bits(sizes):
+    """E = 2 (L_K - 1): the bits of an edge record, and the fewest sites a part holds"""
+    return 2 * (int(domain_map_sizes(sizes)[-1]) - 1)
+
+
+def _pack_rows(x):
+    """0/1 [R, n] -> uint64 [R, ceil(n / 64)], bit j of a row in word j // 64 at position j % 64"""
+    x = np.ascontiguousarray(x, np.uint8)
+    R, n = x.shape
+    pad = np.zeros((R, (n + 63) // 64 * 64), np.uint8)
+    pad[:, :n] = x != 0
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little")).view("<u8").reshape(R, -1).astype(np.uint64)
+
+
+def domain_map_members(x, L):
+    """the opening of the 0/1 string x by L: uint8 [n], 1 where the site lies in a run of at least L ones"""
+    x = np.asarray(x, np.uint8).reshape(1, -1)
+    n = x.shape[1]
+    w = _pack_rows(x)[0] if n else np.zeros(1, np.uint64)
+    out = np.zeros(max((n + 63) // 64, 1), np.uint64)
+    if lib().epvh_domain_map_members(_p(w, C.c_uint64), n, int(L), _p(out, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return np.unpackbits(out.astype("<u8").view(np.uint8), bitorder="little")[:n]
+
+
+def domain_maps_part(x, sizes):
+    """one sample over a stretch of sites: x 0/1 [N, cnt], 1 where the node is in the state asked for -> the part
+    (cnt, counts uint32 [N, K, cnt], edges uint64 [1, N, 2, EW]) as the device counts it"""
+    x = np.asarray(x, np.uint8)
+    z = domain_map_sizes(sizes)
+    N, cnt = x.shape
+    EW = (domain_map_edge_bits(z) + 63) // 64
+    counts, edges = np.zeros((N, len(z), cnt), np.uint32), np.zeros((1, N, 2, EW), np.uint64)
+    one32, one64 = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    bits = _pack_rows(x)
+    if lib().epvh_domain_maps_part(N, len(z), _p(z, C.c_uint32), cnt, _p(bits if bits.size else one64, C.c_uint64),
+                                   _p(counts if counts.size else one32, C.c_uint32),
+                                   _p(edges if edges.size else one64, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return cnt, counts, edges
+
+
+def domain_maps_merge(sizes, parts):
+    """parts: [(sites, counts [N, K, sites], edges [samples, N, 2, EW])] of adjacent stretches of sites in genome
+    order, of the same samples, each of at least E = 2 (L_K - 1) sites -> the part of their union, (sites, counts,
+    edges)"""
+    if not parts:
+        raise ValueError("no parts")
+    z = domain_map_sizes(sizes)
+    EW = (domain_map_edge_bits(z) + 63) // 64
+    cnts = np.array([int(p[0]) for p in parts], np.uint64)
+    counts = [np.ascontiguousarray(p[1], np.uint32) for p in parts]
+    edges = [np.ascontiguousarray(p[2], np.uint64) for p in parts]
+    N, ns = counts[0].shape[0], edges[0].shape[0]
+    for n, a, e in zip(cnts, counts, edges):
+        if a.shape != (N, len(z), int(n)) or e.shape != (ns, N, 2, EW):
+            raise ValueError("a part is counts [N, K, sites] and edges [samples, N, 2, ceil((L_K - 1) / 32)] of the same "
+                             "nodes, sizes and samples")
+    out_c, out_e = np.zeros((N, len(z), int(cnts.sum())), np.uint32), np.zeros((ns, N, 2, EW), np.uint64)
+    one32, one64 = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    cp = (C.POINTER(C.c_uint32) * len(parts))(*[_p(a if a.size else one32, C.c_uint32) for a in counts])
+    total = C.c_uint64(0)
+    if lib().epvh_domain_maps_merge(len(parts), N, len(z), _p(z, C.c_uint32), ns, _p(cnts, C.c_uint64), cp,
+                                    _ptrs([e if e.size else one64 for e in edges]),
+                                    _p(out_c if out_c.size else one32, C.c_uint32),
+                                    _p(out_e if out_e.size else one64, C.c_uint64), C.byref(total)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return int(total.value), out_c, out_e
+
+
+def domain_map_windows(maps, W):
+    """maps [N, K, n] of integer counts -> uint64 [N, K, ceil(n / W)]: the sums over windows of W consecutive sites"""
+    maps = np.asarray(maps)
+    W = int(W)
+    if W < 1:
+        raise ValueError("a window holds at least one site")
+    if maps.ndim != 3 or not np.issubdtype(maps.dtype, np.integer):
+        raise ValueError("maps are integer counts [N, K, n]")
+    n = maps.shape[2]
+    if not n:
+        return np.zeros(maps.shape[:2] + (0,), np.uint64)
+    return np.add.reduceat(maps.astype(np.uint64), np.arange(0, n, W), axis=2)
+
+
+def domain_calls(samples, maps, size_index, support=0.5, min_sites=1):
+    """the located domains of every node: per node the list of (first site, last site, mean support) of the maximal
+    intervals of at least min_sites sites whose cells maps[v, size_index, p] / samples all reach `support`.  maps
+    are the integer counts [N, K, n] of `samples` samples"""
+    maps = np.asarray(maps)
+    if maps.ndim != 3 or not np.issubdtype(maps.dtype, np.integer):
+        raise ValueError("maps are integer counts [N, K, n]")
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError("domain calls need at least one sample")
+    if not 0.0 < float(support) <= 1.0:
+        raise ValueError("the support is in (0, 1]")
+    row = maps[:, int(size_index)].astype(np.int64)
+    calls = []
+    for v in range(row.shape[0]):
+        ok = np.concatenate([[0], (row[v] >= float(support) * samples).astype(np.int8), [0]])
+        d = np.diff(ok)
+        out = []
+        for a, b in zip(np.nonzero(d == 1)[0], np.nonzero(d == -1)[0]):     # sites a .. b - 1
+            if b - a >= int(min_sites):
+                out.append((int(a), int(b) - 1, float(row[v, a:b].sum()) / (float(samples) * float(b - a))))
+        calls.append(out)
+    return calls
+
+
+def write_domain_maps(path, node_names, samples, state, sizes, n_sites, W, sums):
+    """the file of epievo_est_histories -D: window sums [N, K, ceil(n_sites / W)] of the maps, integers only"""
+    z = domain_map_sizes(sizes)
+    sums = np.ascontiguousarray(sums, np.uint64)
+    if int(W) < 1:
+        raise ValueError("a window holds at least one site")
+    if sums.shape != (len(node_names), len(z), (int(n_sites) + int(W) - 1) // int(W)):
+        raise ValueError("sums are [nodes, sizes, ceil(n_sites / W)]")
+    if lib().epvh_write_domain_maps(path.encode(), "\n".join(node_names).encode(), int(samples), int(state), len(z),
+                                    _p(z, C.c_uint32), int(n_sites), int(W),
+                                    _p(sums if sums.size else np.zeros(1, np.uint64), C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_domain_maps(path):
+    """-> dict(samples, sites, window, state, sizes uint32 [K], node_names, sums uint64 [N, K, windows])"""
+    L_ = lib()
+    h = L_.epvh_read_domain_maps(path.encode())
+    if not h:
+        raise RuntimeError(L_.epvh_last_error().decode())
+    try:
+        w = np.zeros(7, np.uint64)
+        L_.epvh_domain_maps_dims(h, _p(w, C.c_uint64))
+        ns, n, W, state, N, K, ln = (int(v) for v in w)
+        buf = C.create_string_buffer(ln)
+        z, sums = np.zeros(K, np.uint32), np.zeros((N, K, (n + W - 1) // W), np.uint64)
+        L_.epvh_domain_maps_copy(h, buf, len(buf), _p(z, C.c_uint32),
+                                 _p(sums if sums.size else np.zeros(1, np.uint64), C.c_uint64))
+        return dict(samples=ns, sites=n, window=W, state=state, sizes=z,
+                    node_names=buf.value.decode().split("\n") if N else [], sums=sums)
+    finally:
+        L_.epvh_domain_maps_free(h)
 
 
 # ---- chain mixing diagnostics (does a site's history move, and how long does its jump count remember itself)

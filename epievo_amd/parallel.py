@@ -494,6 +494,27 @@ class ShardedSampler:
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
 
+    def domain_maps_part(self):
+        """-> (samples, sites, counts, edges): the part of the whole genome, identical on every rank: the sample counts
+        are compared first (a part's size depends on them), then the ranks' parts, each behind its number of sites
+        and with its counts padded to the sites of the widest rank, are all-gathered and merged in genome order"""
+        ns, cnt, counts, edges = self.dev.domain_maps_part()
+        if self.comm.world == 1:
+            return ns, cnt, counts, edges
+        sizes = self.dev.domain_maps_layout()[1]
+        widest = max(b - a for a, b in zip(self.cuts[:-1], self.cuts[1:]))
+        padded = np.zeros(counts.shape[:2] + (widest,), np.uint64)
+        padded[:, :, :cnt] = counts
+        return (ns,) + self._gather_parts(
+            ns, [np.array([cnt], np.uint64), padded, edges], NOUN["domain_maps"],
+            lambda parts: host.domain_maps_merge(
+                sizes, [(int(c[0]), a[:, :, :int(c[0])].astype(np.uint32), e) for c, a, e in parts]))
+
+    def domain_maps(self, counts=False):
+        """-> (samples, maps [N, K, n_global]) of the whole genome; every rank merges"""
+        ns, _, c, _ = self.domain_maps_part()
+        return ns, _per_sample(c, ns, counts)
+
     def mixing(self, counts=False):
         """-> DeviceSampler.mixing of the whole genome, identical on every rank: the ranks' rows are all-gathered
         (one collective) and concatenated in genome order (a 64-bit cell travels as two words); the ranks' pair
@@ -523,7 +544,7 @@ class ShardedSampler:
 forward_to_dev(ShardedSampler, LIFECYCLE + [
     "set_model", "scale_jump_times", "window_stats_scale_exps", "lineage_origins_layout", "lineage_origin_rows",
     "lineage_origins_scale_exp", "domain_stats_layout", "domain_turnover_layout", "spatial_correlation_layout",
-    "mixing_layout"])
+    "mixing_layout", "domain_maps_layout"])
 
 
 class LocalGroup:
@@ -713,6 +734,9 @@ class LocalGroup:
         if getattr(self, "_corr_lag", 0):
             # a shard that owns fewer than max_lag sites refuses here, before any shard's first sweep
             self._each(lambda j, s: s.spatial_correlation_layout())
+        if getattr(self, "_dmaps_on", False):
+            # likewise a shard that owns fewer sites than an edge record of the domain maps holds
+            self._each(lambda j, s: s.domain_maps_layout())
         res = self._each(lambda j, s: s.run_mcmc_counts(burn_in, batch, seed, sweep_base))
         for s in self.subs:
             self.capacity_events += s.capacity_events
@@ -935,6 +959,27 @@ class LocalGroup:
         """-> (samples, n11, left1, right1), each [R, L + 1], over the group's owned sites, closed"""
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
+
+    # domain maps: a shard's part is that of the sites it owns
+    def enable_domain_maps(self, sizes, state=1, max_samples=1 << 21):
+        self._dmaps_on = bool(np.size(sizes))
+        self._each_call("enable_domain_maps", sizes, state, max_samples)
+
+    def domain_maps_layout(self):
+        """(nodes N, sizes, state, first local site of the first shard, sites over all shards, sites per block)"""
+        lay = self._each_call("domain_maps_layout")
+        return lay[0][:4] + (sum(v[4] for v in lay),) + lay[0][5:]
+
+    def domain_maps_part(self):
+        """-> (samples, sites, counts, edges): the shards' parts merged in genome order"""
+        ns, parts = self._parts("domain_maps", "domain_maps_part")
+        sizes = self.subs[0].domain_maps_layout()[1]
+        return (ns,) + self._merged(parts, lambda ps: host.domain_maps_merge(sizes, ps))
+
+    def domain_maps(self, counts=False):
+        """-> (samples, maps [N, K, sites]) over the group's owned sites"""
+        ns, _, c, _ = self.domain_maps_part()
+        return ns, _per_sample(c, ns, counts)
 
     # chain mixing diagnostics: rows by site; the shards ran the same runs, so their pair counts agree
     def mixing_layout(self):

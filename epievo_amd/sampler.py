@@ -99,11 +99,12 @@ def _abi():
         "epv_get_spatial_correlation": [vp, u64p, u64p],
         "epv_mixing_layout": [vp, u64p, u64p, u32p], "epv_mixing_pairs": [vp, u64p],
         "epv_mixing_counts": [vp, u64, u64, u32p, u64p], "epv_mixing_windows": [vp, u64, u64, u64, u64p],
+        "epv_domain_maps_layout": [vp, u32p, u32p, u32p, u32p, u64p, u64p, u64p], "epv_get_domain_maps": [vp, u32p, u64p],
     }
     # epv_set_<stem>: what switches the summary on, after the context
     set_args = {"path_average": [u32], "branch_events": [i], "window_stats": [u64], "epoch_stats": [u32],
                 "lineage_origins": [i], "domain_stats": [u64], "change_patterns": [i], "domain_turnover": [u64],
-                "spatial_correlation": [u32, u64], "mixing": [u32]}
+                "spatial_correlation": [u32, u64], "mixing": [u32], "domain_maps": [u32, u32p, u32, u64]}
     for s in LAYERS:
         args["epv_set_" + s.stem] = [vp] + set_args[s.stem]
         args["epv_reset_" + s.stem] = args["epv_accumulate_" + s.stem] = [vp]
@@ -837,6 +838,49 @@ class DeviceSampler:
         ns, cnt, n11, edges = self.spatial_correlation_part()
         return (ns,) + host.corr_part_close(cnt, n11, edges)
 
+    # ---- domain maps (epv_set_domain_maps)
+    def enable_domain_maps(self, sizes, state=1, max_samples=1 << 21):
+        """count, per node, size and site, the samples in which the site lies in a run of `state` of at least that
+        size along the genome, after every batch sweep of run_mcmc, for at most max_samples samples: 1 .. 4 strictly
+        increasing sizes of 1 .. 1024 (an empty list: off)"""
+        z = np.array([int(L) for L in np.atleast_1d(sizes)], np.uint32) if np.size(sizes) else np.zeros(0, np.uint32)
+        if not len(z):
+            return self._ck(self.L.epv_set_domain_maps(self.h, 0, None, 0, 0))
+        z = host.domain_map_sizes(z)
+        if int(state) not in (0, 1):
+            raise ValueError("the state of the domain maps is 0 or 1")
+        self._ck(self.L.epv_set_domain_maps(self.h, len(z), _p(z, C.c_uint32), int(state), int(max_samples)))
+
+    def domain_maps_layout(self):
+        """(nodes N, sizes tuple, state, first local site, number of sites, sites per block of the membership kernel);
+        (0, (), 0, 0, 0, 0) when off"""
+        nn, nk, st = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        z = np.zeros(4, np.uint32)
+        a, k, cs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.epv_domain_maps_layout(self.h, C.byref(nn), C.byref(nk), _p(z, C.c_uint32), C.byref(st),
+                                               C.byref(a), C.byref(k), C.byref(cs)))
+        return (int(nn.value), tuple(int(L) for L in z[:int(nk.value)]), int(st.value), int(a.value), int(k.value),
+                int(cs.value))
+
+    def domain_maps_part(self):
+        """-> (samples, sites, counts uint32 [N, K, sites], edges uint64 [samples, N, 2, EW]): what this context's
+        stretch of sites contributes, unmerged (host.domain_maps_merge); EW = ceil((L_K - 1) / 32)"""
+        ns = self.domain_maps_samples()
+        N, z, _, _, cnt, _ = self.domain_maps_layout()
+        K = len(z)
+        EW = (2 * (z[-1] - 1) + 63) // 64 if K else 0
+        counts = np.zeros(max(N * K * cnt, 1), np.uint32)
+        edges = np.zeros(max(ns * N * 2 * EW, 1), np.uint64)
+        self._ck(self.L.epv_get_domain_maps(self.h, _p(counts, C.c_uint32), _p(edges, C.c_uint64)))
+        return ns, cnt, counts[:N * K * cnt].reshape(N, K, cnt), edges[:ns * N * 2 * EW].reshape(ns, N, 2, EW)
+
+    def domain_maps(self, counts=False):
+        """-> (samples, maps [N, K, sites]): maps[v, k, p] = the posterior probability that site p of node v lies in
+        a run of the state asked for of at least sizes[k] sites (over this context's sites); counts=True gives the
+        uint32 counts (host.domain_calls, host.domain_map_windows)"""
+        ns, _, c, _ = self.domain_maps_part()
+        return ns, _per_sample(c, ns, counts)
+
     # ---- epoch statistics (epv_set_epoch_stats)
     def enable_epoch_stats(self, P):
         """add J and D per branch and epoch (P epochs per branch) after every batch sweep of run_mcmc (0 = off)"""
@@ -1010,4 +1054,4 @@ forward_to_dev(SingleSiteSampler, LIFECYCLE + [
     "lineage_origin_windows", "domain_stats_layout", "domain_stats_part", "domain_stats", "change_patterns_layout",
     "change_patterns", "change_pattern_windows", "domain_turnover_layout", "domain_turnover_part", "domain_turnover",
     "spatial_correlation_layout", "spatial_correlation_part", "spatial_correlation", "mixing_layout", "mixing",
-    "mixing_windows"])
+    "mixing_windows", "domain_maps_layout", "domain_maps_part", "domain_maps"])

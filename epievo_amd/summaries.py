@@ -24,7 +24,12 @@ SUMMARIES = (
 DIAGNOSTICS = (
     Summary("mixing", "a", "mixing"),
 )
-LAYERS = SUMMARIES + DIAGNOSTICS
+# summaries that joined the chain after the diagnostics: after DIAGNOSTICS in kLayers, so that every order the two
+# tables above stand for stays what it was
+LATER_SUMMARIES = (
+    Summary("domain_maps", "a", "domain-map"),
+)
+LAYERS = SUMMARIES + DIAGNOSTICS + LATER_SUMMARIES
 NOUN = {s.stem: s.noun for s in LAYERS}
 # the four methods every sampler has for every summary and diagnostic
 LIFECYCLE = [fmt % s.stem for s in LAYERS for fmt in ("enable_%s", "reset_%s", "accumulate_%s", "%s_samples")]

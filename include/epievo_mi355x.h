@@ -790,6 +790,43 @@ int epv_mixing_pairs(epv_ctx *ctx, uint64_t *words);
 int epv_mixing_counts(epv_ctx *ctx, uint64_t first, uint64_t count, uint32_t *moved, uint64_t *sums);
 int epv_mixing_windows(epv_ctx *ctx, uint64_t W, uint64_t first_window, uint64_t n_windows, uint64_t *sums);
 
+/* ---- domain maps (new): WHERE the domains are.  Per node v, size L_k and site p of the sites the path average
+ * counts: counts[v][k][p] = the samples in which x_v[p] == state and p lies in a run of equal x_v of at least L_k
+ * sites (x_v as the domain size spectra define it, from the meta words alone; a run is clipped to the stretch, and
+ * at the two ends of the genome to the genome, as the spectra count them).  1 <= K <= 4 sizes, strictly increasing,
+ * 1 <= L_k <= 1024; one state per enable.  counts[v][k+1][p] <= counts[v][k][p] <= samples; with L_1 = 1 row 0 is
+ * the marginal of the node state.  The last layer of the chain.
+ * A context keeps a PART over its cnt sites:
+ *   counts[N][K][cnt] uint32, summed over the samples, runs clipped to the stretch
+ *   edge[sample][N][2][EW] uint64, E = 2 (L_K - 1), EW = ceil(E / 64): record 0 (head) bit j = (x_v[j] == state),
+ *     record 1 (tail) bit j = (x_v[cnt - E + j] == state); j < E, the bits beyond E in the last word are zero.  With
+ *     L_K = 1 there are no records
+ * Merge of a part A left of a part B (same samples, sizes and N, both of at least E sites): the counts concatenated;
+ * then per sample, node and size, with m(.) the opening by L_k (erode by L_k, dilate by L_k), the cells under A's
+ * tail receive m(tailA | headB) - m(tailA) and those under B's head m(tailA | headB) - m(headB), each 0 or 1 and
+ * zero but in the last L_k - 1 cells of A and the first L_k - 1 of B; the head is A's, the tail B's.  No close step:
+ * the part of the whole genome is the result (epvh_domain_maps_merge, epvh_domain_map_members in libepv_host.so).
+ * A context that counts fewer than E sites is EPV_ERR_ARG (the message gives both figures), when the layer is set
+ * or, for a range that changed since, before the first sweep of a run.
+ * Samples, sites and lifecycle are the spatial correlations'; a changed site range, number of nodes or first child
+ * of the root lays the part out again before the first sample and is EPV_ERR_STATE after it.  Off by default:
+ * nothing allocated, nothing launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_domain_maps: n_sizes sizes, state 0 or 1 and max_samples >= 1 (at most 2^21) allocate 4 N K cnt bytes of
+ *   counts, 8 N ceil(cnt / 64) bytes of scratch and 16 N EW max_samples bytes of edge records (checked against the
+ *   free device memory first; the message gives the figure) and zero them; n_sizes = 0 frees everything.  A sample
+ *   beyond max_samples is EPV_ERR_STATE, and so is a run whose batch would pass it, refused before its first sweep.
+ *   At most 2^32 - 1 sites per context.
+ * epv_domain_maps_layout: nodes N, K, sizes[4] (zeros beyond K), the state, the local sites first .. first+count-1
+ *   and the sites one block of the membership kernel covers (zeros when off).
+ * epv_get_domain_maps: the context's part, unmerged; edges holds [samples][N][2][EW]. */
+int epv_set_domain_maps(epv_ctx *ctx, uint32_t n_sizes, const uint32_t *sizes, uint32_t state, uint64_t max_samples);
+int epv_reset_domain_maps(epv_ctx *ctx);
+int epv_accumulate_domain_maps(epv_ctx *ctx);
+int epv_domain_maps_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_domain_maps_layout(epv_ctx *ctx, uint32_t *n_nodes, uint32_t *n_sizes, uint32_t *sizes, uint32_t *state,
+                           uint64_t *first, uint64_t *count, uint64_t *chunk_sites);
+int epv_get_domain_maps(epv_ctx *ctx, uint32_t *counts, uint64_t *edges);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

@@ -160,6 +160,17 @@ int epvd_download_corr_part(epvd_sampler *s, uint64_t *n11, uint64_t *edges);
 int epvd_download_corr(epvd_sampler *s, uint32_t n_rows, uint32_t max_lag, uint64_t *n11, uint64_t *left1,
                        uint64_t *right1, uint64_t *n_samples);
 
+/* domain maps (epv_set_domain_maps on every context; n_sizes = 0 is off; kept across epvd_reset, which starts them
+ * from zero).  The part of this process: the parts of its slots and contexts merged in genome order -- sizes first
+ * (nodes N, sizes K, samples S and the sites the part covers), then the copy of counts[N][K][sites] (uint32) and
+ * edges[S][N][2][ceil((L_K - 1) / 32)].  Of one process of several it is that process's stretch: merge the processes'
+ * parts in genome order (epvh_domain_maps_merge) */
+int epvd_set_dmaps(epvd_sampler *s, uint32_t n_sizes, const uint32_t *sizes, uint32_t state, uint64_t max_samples);
+int epvd_reset_dmaps(epvd_sampler *s);
+int epvd_accumulate_dmaps(epvd_sampler *s);
+int epvd_dmaps_sizes(epvd_sampler *s, uint32_t *n_nodes, uint32_t *n_sizes, uint64_t *n_samples, uint64_t *n_sites);
+int epvd_download_dmaps(epvd_sampler *s, uint32_t *counts, uint64_t *edges);
+
 /* change patterns (epv_set_change_patterns on every context; kept across epvd_reset, which starts the rows from
  * zero), and the rows over the sites of this process in genome order: sizes first (n_rows = 12 + 2 (n_nodes-1) +
  * internal non-root nodes, n_values = n_rows * sites), then the copy of rows[r * sites + site].
