@@ -2763,6 +2763,86 @@ EPV_API int epv_merge_kat(epv_ctx *c, uint32_t n, const uint32_t *heads, const d
   return EPV_OK;
 }
 
+// known-answer entry for the trial evaluator of the end-conditioned sampler: item i = one segment and a first
+// trial t0 (layout in include/epievo_mi355x.h).  One lane per item in waves of 64, so that the lanes of a wave
+// mix flips with keepers and t == 1 with t >= 2 as the grouped search's do.  Five evaluations, in the form the
+// fused bodies inline (plain multiplies, ONE first-draw block); the separate kernels' form is the parent's, and
+// its two first-draw arms do not compile next to each other in one lane's straight-line code here (the
+// compiler merges their tails and with them the scalar key chains of epv_philox.h):
+//   0  scan_trial1 at t0                    1  run_trial at t0 on the GIVEN first draw u0 (no shortcut bounds)
+//   2, 3, 4  scan_trials over W = 1, 4, 8 trials from t0
+// w_out[20 i + 4 e ..] = outcome, winning trial, jumps, M;  d_out[11 i ..] = first_draw(t0), then the first two
+// jump times of each evaluation.
+template <bool ASM_MUL>
+__device__ __forceinline__ void epv_trial_kat_form(uint32_t seed_lo, uint32_t seed_hi, const uint32_t *ci, const double *cd,
+                                                   uint32_t *w_out, double *d_out) {
+  const uint32_t site = ci[0], sweep = ci[1], node = ci[2], k = ci[3], t0 = ci[4], room = ci[5];
+  const uint32_t a0 = ci[6] & 1u, end = (ci[6] >> 1) & 1u;
+  const bool nielsen = (ci[6] >> 2) & 1u;
+  const double T = cd[0], r0 = cd[1], r1 = cd[2], trunc = cd[3], u0 = cd[4], start = cd[5];
+  d_out[0] = first_draw<ASM_MUL>(seed_lo, seed_hi, site, sweep, node, k, t0);
+  for (uint32_t e = 0; e < 5u; ++e) {
+    double jt[2] = {0.0, 0.0};
+    uint32_t nj = 0u, tw = 0u, mm = 0u;
+    int oc;
+    if (e == 0u) {
+      oc = scan_trial1<ASM_MUL>(seed_lo, seed_hi, site, sweep, node, k, t0, a0, end, T, r0, r1, trunc, room, jt, 1u, 2u, start,
+                                nj, nielsen, &mm);
+      tw = t0;
+    } else if (e == 1u) {
+      oc = run_trial<ASM_MUL>(seed_lo, seed_hi, site, sweep, node, k, t0, u0, a0, end, T, r0, r1, 0.0, 0.0, trunc, room, jt, 1u,
+                              2u, start, nj, nielsen);
+      tw = t0; mm = nj;
+    } else {
+      oc = scan_trials<ASM_MUL>(seed_lo, seed_hi, site, sweep, node, k, t0, e == 2u ? 1u : (e == 3u ? 4u : 8u), a0, end, T, r0,
+                                r1, trunc, room, jt, 1u, 2u, start, tw, nj, nielsen, &mm);
+    }
+    w_out[4u * e] = (uint32_t)oc; w_out[4u * e + 1u] = tw; w_out[4u * e + 2u] = nj; w_out[4u * e + 3u] = mm;
+    d_out[1u + 2u * e] = jt[0]; d_out[2u + 2u * e] = jt[1];
+  }
+}
+
+__global__ void __launch_bounds__(64) epv_trial_kat_kernel(uint32_t seed_lo, uint32_t seed_hi, uint32_t n, const uint32_t *ci,
+                                                           const double *cd, uint32_t *w_out, double *d_out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  epv_trial_kat_form<false>(seed_lo, seed_hi, ci + 8u * (size_t)i, cd + 6u * (size_t)i, w_out + 20u * (size_t)i, d_out + 11u * (size_t)i);
+}
+
+EPV_API int epv_trial_kat(epv_ctx *c, uint64_t seed, uint32_t n, const uint32_t *items, const double *reals, uint32_t *w_out,
+                          double *d_out) {
+  if (!c || !items || !reals || !w_out || !d_out || !n || n > (1u << 16)) return EPV_ERR_ARG;
+  for (uint32_t i = 0; i < n; ++i) {
+    // (a trial index of 0 is no trial, and a rate or a length that is not positive and finite would keep a
+    // lane in its hold-time loop)
+    const uint32_t *w = items + 8u * (size_t)i;
+    const double *r = reals + 6u * (size_t)i;
+    if (w[4] == 0u || w[4] > 0x7fffffffu - 8u || w[2] > 4095u || w[3] > 4095u || w[6] > 7u) return EPV_ERR_ARG;
+    if (!(r[0] > 0.0 && r[0] < EPV_INF && r[1] > 1e-3 && r[1] < EPV_INF && r[2] > 1e-3 && r[2] < EPV_INF)) return EPV_ERR_ARG;
+    if (!(r[0] * (r[1] > r[2] ? r[1] : r[2]) <= 64.0)) return EPV_ERR_ARG;       // (bounds the jumps of a trial)
+    if (!(r[3] >= 0.0 && r[3] < 1.0 && r[4] >= 0.0 && r[4] < 1.0 && std::fabs(r[5]) < EPV_INF)) return EPV_ERR_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one allocation: reals [6 n] | d_out [11 n] doubles, then items [8 n] | w_out [20 n] words
+  const size_t nd = (size_t)n * (6u + 11u), nw = (size_t)n * (8u + 20u);
+  double *d_buf = nullptr;
+  HIP_TRY(c, hipMalloc(&d_buf, nd * sizeof(double) + nw * sizeof(uint32_t)));
+  double *d_reals = d_buf, *d_d = d_buf + (size_t)n * 6u;
+  uint32_t *d_items = reinterpret_cast<uint32_t *>(d_buf + nd), *d_w = d_items + (size_t)n * 8u;
+  hipError_t e = hipMemcpyAsync(d_reals, reals, (size_t)n * 6u * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_items, items, (size_t)n * 8u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    epv_trial_kat_kernel<<<(n + 63u) / 64u, 64, 0, c->stream>>>((uint32_t)seed, (uint32_t)(seed >> 32), n, d_items, d_reals, d_w, d_d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_d, (size_t)n * 11u * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)n * 20u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_buf);
+  if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_trial_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
 EPV_API int epv_set_unobserved(epv_ctx *c, const uint8_t *unobserved) {
   if (!c) return EPV_ERR_ARG;
   if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_unobserved");

@@ -202,11 +202,11 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
   uint32_t tcur = 1u + sub, hist = 0u;      // hist: most jumps of this lane's failed trials so far
   for (uint32_t r = 0; r < rounds && __any(pend); ++r) {
     int oc = TRIAL_FAIL;
-    uint32_t cnt = 0u, tw = 0u, mm = 0u;
+    uint32_t cnt = 0u, mm = 0u;
     double jt[2] = {0.0, 0.0};
-    if (pend)
-      oc = scan_trials<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, tcur, 1u, prev, sampled, len, r0, r1, trunc, 0xffffffffu,
-                       jt, 1u, 2u, t.start, tw, cnt, nielsen, &mm);
+    if (pend)     // one trial per lane: the scan without its trial loop and pair cache
+      oc = scan_trial1<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, tcur, prev, sampled, len, r0, r1, trunc, 0xffffffffu,
+                                jt, 1u, 2u, t.start, cnt, nielsen, &mm);
     const unsigned long long hit = __ballot(pend && oc != TRIAL_FAIL);
     const uint32_t gh = (uint32_t)(hit >> gbase) & ((1u << G) - 1u);     // this group's hits (G <= 8)
     const uint32_t wsub = gh ? (uint32_t)__ffs((int)gh) - 1u : G;         // the group's lowest hit

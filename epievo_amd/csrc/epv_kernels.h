@@ -405,6 +405,8 @@ __device__ __forceinline__ int run_trial(uint32_t seed_lo, uint32_t seed_hi, uin
   epv_block2 blk;
   blk.d0 = 0.0; blk.d1 = 0.0;
   double u = u0;
+  // (Nielsen's arm and the loop stay two bodies: folded into one -- the first jump as iteration 0 of the
+  // loop -- the section shrinks by a quarter and the benchmark does not move)
   if (nielsen && a0 != end) {
     tau = -epv_log(1.0 - u0 * trunc) / (a0 ? r1 : r0);
     if (!(tau < T)) return TRIAL_FAIL;   // a draw within rounding of 1: redraw (oracle: same guard)
@@ -445,9 +447,17 @@ __device__ __forceinline__ double nojump_bound(double x) {
 template <bool ASM_MUL = true>
 __device__ __forceinline__ double first_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t gsite,
                                              uint32_t sweep, uint32_t node, uint32_t k, uint32_t t) {
-  if (t == 1u) return epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
+  // ONE block for every t: trial 1 reads (t = 0, blk = 0).d1 and trial t >= 2 reads (t >> 1, 255).d[t & 1], so
+  // the counter word is t >> 1 and the half is t & 1 for both; only the block index is a select.  (Lanes of
+  // one wave mix t == 1 with t >= 2 -- the grouped search gives lane `sub` of a group trial 1 + sub --, so a
+  // wave would execute both of two arms.)  The fused bodies (ASM_MUL = false) take this form.  The separate
+  // kernels keep the two arms: with the one block epv_mh_jumps_all_kernel gains 12 bytes of scratch and
+  // epv_seg_assemble_kernel loses a wave per SIMD (profiles/trial_body_static.txt).
+  if constexpr (ASM_MUL) {
+    if (t == 1u) return epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
+  }
   const epv_block2 fb = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t >> 1,
-                                        EPV_FIRST_DRAW_BLOCK);
+                                                 (!ASM_MUL && t == 1u) ? 0u : EPV_FIRST_DRAW_BLOCK);
   return (t & 1u) ? fb.d1 : fb.d0;
 }
 
@@ -485,12 +495,16 @@ __device__ __forceinline__ int scan_trials(uint32_t seed_lo, uint32_t seed_hi, u
     double u = 0.0;
     bool cand = false;
     for (; t < t_end; ++t) {
-      if (t == 1u) {
+      // the block of first_draw(), cached per counter word t >> 1: 0 belongs to trial 1 alone (its block
+      // index is 0), every other to the pair (2m, 2m+1) -- trials 1, 2, 3 read blocks (0, 0), (1, 255), (1, 255).
+      // ONE call site in the fused bodies; the separate kernels keep trial 1's own (see first_draw)
+      if (ASM_MUL && t == 1u) {
         u = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, 0u, 0u).d1;
       } else {
         if ((t >> 1) != fb_pair) {
           fb_pair = t >> 1;
-          fb = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, fb_pair, EPV_FIRST_DRAW_BLOCK);
+          fb = epv_keyed_block<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, fb_pair,
+                                        (!ASM_MUL && t == 1u) ? 0u : EPV_FIRST_DRAW_BLOCK);
         }
         u = (t & 1u) ? fb.d1 : fb.d0;
       }
@@ -509,6 +523,25 @@ __device__ __forceinline__ int scan_trials(uint32_t seed_lo, uint32_t seed_hi, u
     if (oc != TRIAL_FAIL) { t_out = t; return oc; }
     ++t;
   }
+}
+
+// scan_trials for ONE trial (W = 1, as the grouped search calls it): no trial loop and no pair cache.  The
+// scan's first level is run_trial's own test of the first draw against the no-jump bound, which for a
+// segment that does not flip settles the trial before any logarithm or further block: kept state -- success,
+// forward mode on a state change -- failure; so the bound goes in for both states.
+template <bool ASM_MUL = true>
+__device__ __forceinline__ int scan_trial1(uint32_t seed_lo, uint32_t seed_hi, uint32_t gsite, uint32_t sweep,
+                                           uint32_t node, uint32_t k, uint32_t t, uint32_t a0, uint32_t end, double T,
+                                           double r0, double r1, double trunc, uint32_t room, double *dst,
+                                           uint64_t stride, uint32_t max_store, double start_time, uint32_t &nj_out,
+                                           bool nielsen, uint32_t *maxm) {
+  const bool flip = nielsen && a0 != end;
+  const double bound = nojump_bound(T * ((flip ? end : a0) ? r1 : r0));
+  const double u = first_draw<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t);
+  const int oc = run_trial<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, t, u, a0, end, T, r0, r1, bound, bound, trunc,
+                                    room, dst, stride, max_store, start_time, nj_out, nielsen);
+  if (nj_out > *maxm) *maxm = nj_out;
+  return oc;
 }
 
 // ------------------------------------------------ LDS staging of constants

@@ -74,6 +74,7 @@ def _abi():
         "epv_phase_mode": [vp, u32p], "epv_phase_plan": [vp, u32p],
         "epv_philox_kat": [vp, u64, u32, u32p, dp], "epv_math_kat": [vp, u32, u32, u32, dp, dp],
         "epv_merge_kat": [vp, u32, u32p, dp, dp, u32p],
+        "epv_trial_kat": [vp, u64, u32, u32p, dp, u32p, dp],
         "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
         "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
         "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
@@ -306,6 +307,23 @@ class DeviceSampler:
         self._ck(self.L.epv_merge_kat(self.h, n, _p(heads, C.c_uint32), _p(times, C.c_double), _p(D, C.c_double),
                                       _p(J, C.c_uint32)))
         return D, J
+
+    def trial_kat(self, seed, items, reals):
+        """the trial evaluator of the end-conditioned sampler on known inputs (epv_trial_kat): items[i] = (site,
+        sweep, node, segment, first trial, room, start | end << 1 | nielsen << 2, 0), reals[i] = (length, rate 0,
+        rate 1, trunc, u0, start time).  Returns (W [i, 5, 4] uint32 = outcome, winning trial, jumps, M of the
+        single-trial scan, run_trial on u0, and scan_trials over 1, 4, 8 trials; first [i] = the first draw;
+        T [i, 5, 2] = the first two jump times)."""
+        it = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, 8)
+        re = np.ascontiguousarray(reals, dtype=np.float64).reshape(-1, 6)
+        n = it.shape[0]
+        if re.shape[0] != n:
+            raise ValueError("trial_kat: %d items, %d rows of reals" % (n, re.shape[0]))
+        W = np.zeros((n, 5, 4), np.uint32)
+        D = np.zeros((n, 11))
+        self._ck(self.L.epv_trial_kat(self.h, int(seed), n, _p(it, C.c_uint32), _p(re, C.c_double), _p(W, C.c_uint32),
+                                      _p(D, C.c_double)))
+        return W, D[:, 0].copy(), D[:, 1:].reshape(n, 5, 2).copy()
 
     def set_unobserved(self, mask):
         """missing leaf data (epv_set_unobserved): mask[b-1, s] != 0 -> the leaf end state of branch b at

@@ -202,6 +202,24 @@ int epv_math_kat(epv_ctx *ctx, uint32_t op, uint32_t where, uint32_t n, const do
  * establish. */
 int epv_merge_kat(epv_ctx *ctx, uint32_t n, const uint32_t *heads, const double *times, double *d_out, uint32_t *j_out);
 
+/* Known-answer entry for the trial evaluator of the end-conditioned sampler (first_draw, run_trial, scan_trials
+ * and the single-trial scan of epv_kernels.h), for tests: n <= 2^16 items, item i = one segment and a first trial.
+ *   items[8 i ..]  site, sweep, node (<= 4095), segment (<= 4095), first trial t0 >= 1, room (jump slots left),
+ *                  start state | end state << 1 | (Nielsen's method for a state change) << 2, 0
+ *   reals[6 i ..]  length T > 0, rate of state 0, rate of state 1 (each > 1e-3, T * rate <= 64),
+ *                  trunc = 1 - exp(-rate of the start state * T) as the caller computed it, u0 in [0, 1) = the
+ *                  first draw handed to evaluation 1, the segment's start time (added to every jump time)
+ * One lane per item, 64 items to a wave in the order given, so a wave's lanes mix whatever the caller puts side
+ * by side.  Five evaluations, in the form the fused colour phase inlines (plain Philox multiplies):
+ *   0  the single-trial scan of trial t0     1  run_trial of trial t0 on u0, no shortcut bounds
+ *   2, 3, 4  scan_trials over 1, 4, 8 trials from t0
+ * w_out[20 i + 4 e ..] = outcome (0 fail, 1 ok, 2 overflow), the winning trial (t0 for e < 2),
+ * its jumps, M = the most jumps of any trial evaluated;  d_out[11 i] = first_draw(t0), followed by the
+ * first two stored jump times of each evaluation (0 where there is none).  The key is `seed`.  Like the entries
+ * above this runs the functions in a kernel of their own, not a call site inside the MCMC kernels. */
+int epv_trial_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *items, const double *reals, uint32_t *w_out,
+                  double *d_out);
+
 /* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
  * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
  * instead of the indicator of the path's end state) instead of pinning it.  The node-major layout
