@@ -93,11 +93,15 @@ def nojump_sets():
 
 
 def model_rate_pairs():
-    """(r0, r1) of the four neighbour contexts of test.param and of the two dense models: rates[trip0], rates[trip0 | 2]"""
+    """(r0, r1) of the four neighbour contexts of test.param, of the two dense models and of the models of
+    model_cases.py: rates[trip0], rates[trip0 | 2]"""
     import dense_cases
+    import model_cases
     from common import ref_test_model
     out = []
-    for m in (ref_test_model(), dense_cases.model("weak"), dense_cases.model("flat")):
+    models = [ref_test_model(), dense_cases.model("weak"), dense_cases.model("flat")]
+    models += [model_cases.model(name) for name in model_cases.MODELS if name != "ref"]
+    for m in models:
         out += [(float(m.rates[t]), float(m.rates[t | 2])) for t in (0, 1, 4, 5)]
     return np.array(out)
 

@@ -33,6 +33,8 @@ Coverage (variant x options -> rows):
                                              branch, two and more words of proposal states, the fused phase at
                                              C = 31 with every branch heavy, the statistics kernels' merge rings
                                              and the accumulate kernels
+  models other than test.param, and models   test_model_space_gpu.py: every family above under the models and rows of
+  that did not generate the data             model_cases.py (rate T from 1e-12 to 2e5, rate ratios up to 5e9)
 """
 import json
 import os
