@@ -488,6 +488,10 @@ int plan_p2(epv_ctx *c) {
   const uint64_t phase_waves = (c->S.phase_cap + 63u) / 64u;
   const uint64_t f_seg_cap = 64ull * B * (2u * C + 1u), f_bt_cap = 64ull * B;
   const uint64_t f_bytes = (c->S.phase_cap + f_lanes - 1u) / f_lanes * (f_seg_cap * (sizeof(EpvSegTask) + sizeof(EpvSegOut)) + f_bt_cap * 12u);
+  // (The options are not consulted: they may change after the paths are planned.  Under EPV_OPT_DIRECT_SAMPLER
+  // phase_plan never launches the fused phase, yet the pool below is sized as if it did -- c->fused stays true
+  // next to the separate V2 kernels, and a tree near the LDS limit may go to the global pool or to V1 for a
+  // fused body that does not run.  Results do not depend on it; the cost is not measured.)
   bool fused = !c->knobs.propose_v1 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
                (c->knobs.fused_phase < 0 ? phase_waves <= FUSED_MAX_WAVES : c->knobs.fused_phase != 0);
   // heavy-segment records: 8 doubles, 10 when the segment-parallel jump kernels read them back
@@ -1922,10 +1926,11 @@ struct PhasePlan {
   bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
   bool evidence;         // a leaf cell carries evidence: V1 takes the template that reads the table
   uint32_t lanes_log2;   // fused: log2 of the sites per wave (2 .. 6)
+  bool direct;           // the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER)
   uint32_t word() const {
     return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
            p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16 |
-           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18 | lanes_log2 << 20;
+           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18 | lanes_log2 << 20 | (direct ? 1u : 0u) << 23;
   }
 };
 PhasePlan phase_plan(const epv_ctx *c) {
@@ -1942,7 +1947,9 @@ PhasePlan phase_plan(const epv_ctx *c) {
   const bool p3 = c->p3 && !P.refq && !P.unobs && !P.evidence;
   const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !P.evidence && !c->p2_gpool;
   P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
-  if (p2 && c->fused) {
+  // the direct sampler exists in the separate jump-time kernels only
+  P.direct = c->S.flags & EPV_FLAG_DIRECT_SAMPLER;
+  if (p2 && c->fused && !P.direct) {
     P.propose = EPV_PLAN_FUSED;
     P.small_nn = c->knobs.small_tree && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
     P.jumps = EPV_PLAN_JUMPS_FUSED;
@@ -1966,8 +1973,9 @@ PhasePlan phase_plan(const epv_ctx *c) {
   // The one-segment tasks (the first bucket: ~95 % on short branches) otherwise go to their own lean
   // kernel, epv_mh_jumps_all_kernel.  (Forward-rejection mode keeps the general kernel for
   // everything: a flip there can need 1e5 trials, which only the wave-wide search takes in reasonable time.)
+  // (The direct sampler has no lean one-segment body either: the general kernel's direct variant.)
   P.jumps = p2 && seg_jumps_on(c) ? EPV_PLAN_JUMPS_SEGMENTS
-          : !(c->S.flags & EPV_FLAG_FORWARD_REJECTION) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
+          : !(c->S.flags & (EPV_FLAG_FORWARD_REJECTION | EPV_FLAG_DIRECT_SAMPLER)) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
   // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
   const int acc_v3 = c->knobs.accept_v3;
   P.accept = (acc_v3 >= 0 ? acc_v3 != 0 : !P.meta_cache) ? EPV_PLAN_ACCEPT_V3
@@ -2080,6 +2088,15 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     // the device, the grids cover a quarter / an eighth of the capacity and stride over the rest
     const unsigned sx = (unsigned)std::min<uint64_t>(32u, std::max<uint64_t>(1u, (c->S.seg_cap / 4u + 255u) / 256u));
     const unsigned bx = (unsigned)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (c->S.btask_cap / 8u + 255u) / 256u));
+    if (P.direct) {
+      unsigned long long *giveups = c->d_counters + EPV_CNT_WORDS;
+      hipLaunchKernelGGL(epv_seg_search_direct_kernel, dim3(sx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
+                         c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, c->d_counters, giveups);
+      hipLaunchKernelGGL(epv_seg_assemble_direct_kernel, dim3(bx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
+                         c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, s0, c->d_counters);
+      hipLaunchKernelGGL(epv_mh_jumps_direct_kernel, dim3(1, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream, c->S,
+                         (uint32_t)seed, (uint32_t)(seed >> 32), sweep, 32u, s0, c->d_counters, giveups);
+    } else {
     hipLaunchKernelGGL(epv_seg_search_kernel, dim3(sx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
                        c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, c->d_counters);
     hipLaunchKernelGGL(epv_seg_assemble_kernel, dim3(bx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
@@ -2088,6 +2105,7 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     // and whatever did not fit the lists (normally nothing: it reads empty lists and leaves)
     hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3(1, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream, c->S,
                        (uint32_t)seed, (uint32_t)(seed >> 32), sweep, 32u, s0, 0.0, 0.0, c->d_counters);
+    }
   } else {
     // one lane per dirty (site, branch) pair; the count is only known on the device, so
     // launch a grid that covers the typical case and grid-stride over the rest
@@ -2104,6 +2122,11 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
       const uint64_t jgb = std::min<uint64_t>((max_tasks / 16u + 4u * tpw - 1u) / (4u * tpw) + 1u, 64u);
       hipLaunchKernelGGL(epv_mh_jumps_all_kernel, dim3(EPV_SHARDS, (unsigned)(jgb + j1b)), dim3(256), const_lds_bytes(c->S.N),
                          c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, c->d_counters, (uint32_t)jgb);
+    } else if (P.direct) {
+      const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);
+      hipLaunchKernelGGL(epv_mh_jumps_direct_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
+                         c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, c->d_counters,
+                         c->d_counters + EPV_CNT_WORDS);
     } else {
       const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);
       hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
@@ -2254,11 +2277,12 @@ EPV_API epv_ctx *epv_create(int device_id) {
   c->knobs = read_knobs();
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_model, sizeof(EpvModelConst)) != hipSuccess ||
-      hipMalloc(&c->d_counters, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess ||
+      // (one word behind the sharded counters: the direct sampler's give-ups, epv_direct_giveups)
+      hipMalloc(&c->d_counters, sizeof(unsigned long long) * (EPV_CNT_WORDS + 1u)) != hipSuccess ||
       hipHostMalloc(&c->h_counters, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess ||
       hipMalloc(&c->d_cnt_snap, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess ||
       hipHostMalloc(&c->h_cnt_snap, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess ||
-      hipMemset(c->d_counters, 0, sizeof(unsigned long long) * EPV_CNT_WORDS) != hipSuccess) {
+      hipMemset(c->d_counters, 0, sizeof(unsigned long long) * (EPV_CNT_WORDS + 1u)) != hipSuccess) {
     delete c;
     return nullptr;
   }
@@ -2559,8 +2583,12 @@ static int finish_mcmc(epv_ctx *c, uint64_t *n_accepted, uint64_t acc_base);
 
 EPV_API int epv_set_options(epv_ctx *c, uint32_t flags) {
   if (!c) return EPV_ERR_ARG;
-  if (flags & ~(uint32_t)(EPV_OPT_REFERENCE_PROPOSAL_RATIO | EPV_OPT_FORWARD_REJECTION | EPV_OPT_SAMPLE_ROOT))
+  if (flags & ~(uint32_t)(EPV_OPT_REFERENCE_PROPOSAL_RATIO | EPV_OPT_FORWARD_REJECTION | EPV_OPT_SAMPLE_ROOT |
+                          EPV_OPT_DIRECT_SAMPLER))
     return fail(c, EPV_ERR_ARG, "unknown option bits");
+  if ((flags & EPV_OPT_DIRECT_SAMPLER) && (flags & EPV_OPT_FORWARD_REJECTION))
+    return fail(c, EPV_ERR_ARG, "EPV_OPT_DIRECT_SAMPLER and EPV_OPT_FORWARD_REJECTION name two samplers: set one");
+  static_assert(EPV_OPT_DIRECT_SAMPLER == EPV_FLAG_DIRECT_SAMPLER, "option bits");
   static_assert(EPV_OPT_REFERENCE_PROPOSAL_RATIO == EPV_FLAG_REFERENCE_PROPOSAL_RATIO &&
                 EPV_OPT_FORWARD_REJECTION == EPV_FLAG_FORWARD_REJECTION && EPV_OPT_SAMPLE_ROOT == EPV_FLAG_SAMPLE_ROOT,
                 "option bits");
@@ -2840,6 +2868,69 @@ EPV_API int epv_trial_kat(epv_ctx *c, uint64_t seed, uint32_t n, const uint32_t 
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   dfree(d_buf);
   if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_trial_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
+// known-answer entry for the direct end-conditioned sampler (epv_direct.h): one lane per item in waves of 64; item
+// word 6 is the index of the segment's first draw (0 in every MCMC kernel), so that an item can cross trial words
+__global__ void __launch_bounds__(64) epv_direct_kat_kernel(uint32_t seed_lo, uint32_t seed_hi, uint32_t n, const uint32_t *ci,
+                                                            const double *cd, uint32_t *w_out, double *d_out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *w = ci + 8u * (size_t)i;
+  const double *r = cd + 4u * (size_t)i;
+  double jt[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  uint32_t nj = 0u, drawn = 0u, rounds = 0u;
+  const int oc = run_direct((uint32_t)seed_lo, seed_hi, w[0], w[1], w[2], w[3], w[5] & 1u, (w[5] >> 1) & 1u, r[0], r[1], r[2],
+                            w[4], jt, 1u, 8u, r[3], nj, drawn, rounds, w[6]);
+  uint32_t *wo = w_out + 4u * (size_t)i;
+  wo[0] = (uint32_t)oc; wo[1] = nj; wo[2] = drawn; wo[3] = rounds;
+  for (uint32_t q = 0; q < 8u; ++q) d_out[8u * (size_t)i + q] = jt[q];
+}
+
+EPV_API int epv_direct_kat(epv_ctx *c, uint64_t seed, uint32_t n, const uint32_t *items, const double *reals, uint32_t *w_out,
+                           double *d_out) {
+  if (!c || !items || !reals || !w_out || !d_out || !n || n > (1u << 16)) return EPV_ERR_ARG;
+  std::vector<uint32_t> it(items, items + 8u * (size_t)n);
+  for (uint32_t i = 0; i < n; ++i) {
+    // (the body returns whatever it is given; the checks keep an item what the restatement can follow)
+    uint32_t *w = it.data() + 8u * (size_t)i;
+    const double *r = reals + 4u * (size_t)i;
+    if (w[2] > 4095u || w[3] > 4095u || w[5] > 3u) return EPV_ERR_ARG;
+    // first draw index: 0, or the first half of a block (odd), far below the 32-bit trial word's end
+    if (w[6] != 0u && ((w[6] & 1u) == 0u || w[6] > (1u << 24))) return EPV_ERR_ARG;
+    if (!(r[0] > 0.0 && r[0] < EPV_INF && r[1] > 0.0 && r[1] < EPV_INF && r[2] > 0.0 && r[2] < EPV_INF && std::fabs(r[3]) < EPV_INF))
+      return EPV_ERR_ARG;
+    if (w[4] > 64u) w[4] = 64u;      // room: bounds the outer loop of a lane
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one allocation: reals [4 n] | d_out [8 n] doubles, then items [8 n] | w_out [4 n] words
+  const size_t nd = (size_t)n * (4u + 8u), nw = (size_t)n * (8u + 4u);
+  double *d_buf = nullptr;
+  HIP_TRY(c, hipMalloc(&d_buf, nd * sizeof(double) + nw * sizeof(uint32_t)));
+  double *d_reals = d_buf, *d_d = d_buf + (size_t)n * 4u;
+  uint32_t *d_items = reinterpret_cast<uint32_t *>(d_buf + nd), *d_w = d_items + (size_t)n * 8u;
+  hipError_t e = hipMemcpyAsync(d_reals, reals, (size_t)n * 4u * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_items, it.data(), (size_t)n * 8u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    epv_direct_kat_kernel<<<(n + 63u) / 64u, 64, 0, c->stream>>>((uint32_t)seed, (uint32_t)(seed >> 32), n, d_items, d_reals, d_w, d_d);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(d_out, d_d, (size_t)n * 8u * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(w_out, d_w, (size_t)n * 4u * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_buf);
+  if (e != hipSuccess) return fail(c, EPV_ERR_HIP, std::string("epv_direct_kat: ") + hipGetErrorString(e));
+  return EPV_OK;
+}
+
+EPV_API int epv_direct_giveups(epv_ctx *c, uint64_t *out) {
+  if (!c || !out) return EPV_ERR_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  unsigned long long v = 0ull;
+  HIP_TRY(c, hipMemcpyAsync(&v, c->d_counters + EPV_CNT_WORDS, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *out = v;
   return EPV_OK;
 }
 

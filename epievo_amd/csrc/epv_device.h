@@ -107,6 +107,7 @@ struct EpvIndepConst {
 // run-time options (epv_set_options; the same values as the public header)
 #define EPV_FLAG_REFERENCE_PROPOSAL_RATIO 1u  /* evaluate q(old)/q(new) with the reference's sums */
 #define EPV_FLAG_FORWARD_REJECTION 2u         /* state-changing segments by forward rejection too */
+#define EPV_FLAG_DIRECT_SAMPLER 8u            /* jump times by the direct end-conditioned sampler (epv_direct.h) */
 #define EPV_FLAG_SAMPLE_ROOT 4u               /* SingleSiteSampler::SAMPLE_ROOT: propose the root state too (reference arithmetic kernels) */
 
 // counters[] slots

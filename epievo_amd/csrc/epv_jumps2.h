@@ -250,7 +250,8 @@ __device__ __forceinline__ bool epv_seg_search_grouped(const EpvDev &S, const do
 // proposal; a capacity overflow flags the site (phase index tid).  The task word carries the
 // proposal's buffer and the branch's start state (bits 61, 60) so that the lane's chain does not
 // begin with two dependent loads (sel, then the meta word the proposal kernel wrote)
-template <bool ASM_MUL = true>
+// (DIRECT: the segments were sampled by run_direct -- tstar is 1 and M the count, and a replay is run_direct's)
+template <bool ASM_MUL = true, bool DIRECT = false>
 __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
                                                      const EpvSegOut *outs, unsigned long long bt, uint64_t first,
                                                      uint64_t s0, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
@@ -281,12 +282,18 @@ __device__ __forceinline__ void epv_seg_assemble_one(const EpvDev &S, const doub
       const uint32_t node = (uint32_t)(t.w0 >> 40) & 4095u, k = (uint32_t)(t.w0 >> 52);
       const uint32_t prev = (uint32_t)t.w3 & 1u, sampled = (uint32_t)(t.w3 >> 1) & 1u, trip0 = (uint32_t)(t.w3 >> 2) & 7u;
       const double r0 = s_rates[trip0], r1 = s_rates[trip0 | 2u];
-      double trunc = 0.0;
-      if (sampled != prev) trunc = 1.0 - epv_exp(-(prev ? r1 : r0) * t.len);
-      const double u0 = first_draw<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar);
-      uint32_t nj2 = 0;
-      run_trial<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar, u0, prev, sampled, t.len, r0, r1, 0.0, 0.0, trunc,
-                room, dst + (uint64_t)cnt * n, n, 0xffffffffu, t.start, nj2, nielsen);
+      if constexpr (DIRECT) {
+        uint32_t nj2 = 0, drawn, rounds;
+        run_direct(seed_lo, seed_hi, gsite, sweep, node, k, prev, sampled, t.len, r0, r1, room, dst + (uint64_t)cnt * n, n,
+                   0xffffffffu, t.start, nj2, drawn, rounds);
+      } else {
+        double trunc = 0.0;
+        if (sampled != prev) trunc = 1.0 - epv_exp(-(prev ? r1 : r0) * t.len);
+        const double u0 = first_draw<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar);
+        uint32_t nj2 = 0;
+        run_trial<ASM_MUL>(seed_lo, seed_hi, gsite, sweep, node, k, o.tstar, u0, prev, sampled, t.len, r0, r1, 0.0, 0.0, trunc,
+                  room, dst + (uint64_t)cnt * n, n, 0xffffffffu, t.start, nj2, nielsen);
+      }
     }
     cnt += o.cnt;
   }
@@ -317,6 +324,63 @@ __global__ __launch_bounds__(256) void epv_seg_assemble_kernel(EpvDev S, uint32_
     if (bt == ~0ull) continue;                      // blanked: the branch went to the sequential kernel
     epv_seg_assemble_one(S, s_rates, segs, outs, bt, S.bfirst[(uint64_t)shard * S.btask_cap + i], s0, seed_lo, seed_hi,
                          sweep, nielsen);
+  }
+}
+
+// ---- EPV_OPT_DIRECT_SAMPLER: the two kernels above with run_direct (epv_direct.h) for the trial search.  One
+// evaluation settles a segment, so the search has no cooperative windows and no LDS beyond the constants; the
+// room is the whole capacity there, and a segment that would pass it, or gives up, reports M beyond any room, so
+// the assembly rejects the proposal exactly where the sequential walk does.  (The give-up COUNT may differ from the
+// sequential kernel's: a segment that gives up here beyond the room the walk would have left it is an overflow
+// there and counted as one.  Both reject the proposal, so the paths agree; the event has probability <= 2^-64.)
+__global__ __launch_bounds__(256, EPV_SEARCH_WAVES) void epv_seg_search_direct_kernel(EpvDev S, uint32_t seed_lo,
+                                                                                      uint32_t seed_hi, uint32_t sweep,
+                                                                                      unsigned long long *counters,
+                                                                                      unsigned long long *giveups) {
+  extern __shared__ __attribute__((aligned(16))) double s_mem[];
+  stage_constants(S, s_mem);
+  const double *s_rates = s_mem;
+  const uint32_t shard = blockIdx.y;
+  const unsigned long long packed = counters[EPV_CNT_IDX(EPV_CNT_SEG, shard)];
+  const uint64_t n_seg = (packed & 0xffffffffull) < S.seg_cap ? (uint64_t)(packed & 0xffffffffull) : S.seg_cap;
+  const EpvSegTask *segs = S.segs + (uint64_t)shard * S.seg_cap;
+  EpvSegOut *outs = S.segout + (uint64_t)shard * S.seg_cap;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_seg; i += (uint64_t)gridDim.x * blockDim.x) {
+    const EpvSegTask t = segs[i];
+    EpvSegOut o;
+    o.cnt = 0u; o.tstar = 0u; o.maxm = 0u; o.pad = 0u; o.j0 = 0.0; o.j1 = 0.0;
+    if (t.len >= 0.0) {
+      const uint32_t gsite = (uint32_t)(S.g0 + (t.w0 & 0xffffffffffull));
+      const uint32_t node = (uint32_t)(t.w0 >> 40) & 4095u, k = (uint32_t)(t.w0 >> 52);
+      const uint32_t prev = (uint32_t)t.w3 & 1u, sampled = (uint32_t)(t.w3 >> 1) & 1u, trip0 = (uint32_t)(t.w3 >> 2) & 7u;
+      double jt[2] = {0.0, 0.0};
+      uint32_t cnt = 0u, drawn, rounds;
+      const int oc = run_direct(seed_lo, seed_hi, gsite, sweep, node, k, prev, sampled, t.len, s_rates[trip0],
+                                s_rates[trip0 | 2u], S.C, jt, 1u, 2u, t.start, cnt, drawn, rounds);
+      if (oc == TRIAL_GIVEUP) atomicAdd(giveups, 1ull);
+      o.cnt = cnt; o.tstar = 1u; o.maxm = oc == TRIAL_OK ? cnt : 0xffffffffu;
+      o.j0 = jt[0]; o.j1 = jt[1];
+    }
+    outs[i] = o;
+  }
+}
+
+__global__ __launch_bounds__(256) void epv_seg_assemble_direct_kernel(EpvDev S, uint32_t seed_lo, uint32_t seed_hi,
+                                                                      uint32_t sweep, uint64_t s0,
+                                                                      unsigned long long *counters) {
+  extern __shared__ __attribute__((aligned(16))) double s_mem[];
+  stage_constants(S, s_mem);
+  const double *s_rates = s_mem;
+  const uint32_t shard = blockIdx.y;
+  const unsigned long long packed = counters[EPV_CNT_IDX(EPV_CNT_SEG, shard)];
+  const uint64_t n_b = (packed >> 32) < S.btask_cap ? (uint64_t)(packed >> 32) : S.btask_cap;
+  const EpvSegTask *segs = S.segs + (uint64_t)shard * S.seg_cap;
+  const EpvSegOut *outs = S.segout + (uint64_t)shard * S.seg_cap;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_b; i += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long bt = S.btasks[(uint64_t)shard * S.btask_cap + i];
+    if (bt == ~0ull) continue;                      // blanked: the branch went to the sequential kernel
+    epv_seg_assemble_one<true, true>(S, s_rates, segs, outs, bt, S.bfirst[(uint64_t)shard * S.btask_cap + i], s0, seed_lo,
+                                     seed_hi, sweep, true);
   }
 }
 

@@ -960,12 +960,17 @@ __global__ __launch_bounds__(64, EPV_PROPOSE_WAVES) void epv_mh_propose_kernel(
 #ifndef EPV_JUMPS_WAVES
 #define EPV_JUMPS_WAVES 3   /* waves per SIMD the register allocation aims for: 3 = 168 VGPRs, no scratch since the Philox XOR3 (round 2: 26 registers spilled, 2 was as fast); 16-leaf tree -5..-8 % per phase, tree.nwk n = 3e6 -5 % */
 #endif
+#include "epv_direct.h"
+
 // (a device function with the block's place in its grid as arguments: epv_mh_jumps_all_kernel runs it in
 // the first blocks of a launch whose other blocks take the one-segment tasks)
+// DIRECT (compile time, epv_mh_jumps_direct_kernel alone): every segment by run_direct -- no trial search, so
+// the cooperative windows never open; a give-up is counted in *giveups and rejects the proposal like an overflow
+template <bool DIRECT = false>
 __device__ __forceinline__ void epv_jumps_body(const EpvDev &S, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep,
                                                uint32_t tasks_per_wave, uint64_t s0, double indep_r0, double indep_r1,
                                                unsigned long long *counters, uint32_t skip_single, uint32_t block_x,
-                                               uint32_t grid_x, uint32_t shard) {
+                                               uint32_t grid_x, uint32_t shard, unsigned long long *giveups = nullptr) {
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   // per-wave cooperative-search area: task slots by rank and per-lane trial results
   __shared__ double c_len_[4][64], c_r0_[4][64], c_r1_[4][64], c_trunc_[4][64], c_tj_[4][64 * EPV_TJ];
@@ -1062,7 +1067,16 @@ __device__ __forceinline__ void epv_jumps_body(const EpvDev &S, uint32_t seed_lo
         r1 = indep ? indep_r1 : s_rates[trip0 | 2u];
         // sample_trunc_exp's 1 - exp(-rate_a T) (EndCondSampling.cpp:577-580), state changes only
         if (sampled != prev) trunc = 1.0 - epv_exp(-(prev ? r1 : r0) * len);
-        if (!ovf) {
+        if constexpr (DIRECT) {
+          if (!ovf) {
+            uint32_t njt, drawn, rounds;
+            const int oc = run_direct(seed_lo, seed_hi, gsite, sweep, node, k, prev, sampled, len, r0, r1, C - cnt,
+                                      dst + (uint64_t)cnt * n, n, 0xffffffffu, time_passed, njt, drawn, rounds);
+            if (oc == TRIAL_OK) cnt += njt;
+            else ovf = true;
+            if (oc == TRIAL_GIVEUP) atomicAdd(giveups, 1ull);
+          }
+        } else if (!ovf) {
           uint32_t njt, tw;
           const int oc = scan_trials(seed_lo, seed_hi, gsite, sweep, node, k, 1u, EPV_INLINE_TRIALS, prev,
                                      sampled, len, r0, r1, trunc, C - cnt, dst + (uint64_t)cnt * n, n,
@@ -1080,7 +1094,8 @@ __device__ __forceinline__ void epv_jumps_body(const EpvDev &S, uint32_t seed_lo
       // G * EPV_COOP_WINDOW trials.  A leaf that forces a flip on a short branch needs ~1/P(a->b) trials
       // (hundreds for the slowest context); this turns that serial tail into a few
       // full-width rounds.  Identical to the sequential "first non-failing t" whatever P, G.
-      unsigned long long todo = __ballot(pend);
+      unsigned long long todo = 0ull;     // (DIRECT: nothing is ever pending)
+      if constexpr (!DIRECT) todo = __ballot(pend);
       while (todo) {
         const uint32_t P = (uint32_t)__popcll(todo);
         const uint32_t lg = 31u - (uint32_t)__clz((int)(64u / P));
@@ -1173,6 +1188,15 @@ __global__ __launch_bounds__(256, EPV_JUMPS_WAVES) void epv_mh_jumps_kernel(EpvD
                                                            unsigned long long *counters, uint32_t skip_single = 0u) {
   epv_jumps_body(S, seed_lo, seed_hi, sweep, tasks_per_wave, s0, indep_r0, indep_r1, counters, skip_single, blockIdx.x,
                  gridDim.x, blockIdx.y);
+}
+
+// the same kernel with every segment sampled directly (EPV_OPT_DIRECT_SAMPLER)
+__global__ __launch_bounds__(256, EPV_JUMPS_WAVES) void epv_mh_jumps_direct_kernel(EpvDev S, uint32_t seed_lo,
+                                                           uint32_t seed_hi, uint32_t sweep,
+                                                           uint32_t tasks_per_wave, uint64_t s0,
+                                                           unsigned long long *counters, unsigned long long *giveups) {
+  epv_jumps_body<true>(S, seed_lo, seed_hi, sweep, tasks_per_wave, s0, 0.0, 0.0, counters, 0u, blockIdx.x, gridDim.x,
+                       blockIdx.y, giveups);
 }
 
 // =========================================================================

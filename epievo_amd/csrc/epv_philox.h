@@ -19,6 +19,11 @@
 //   trial 1, first draw       : (b,k,t=0,blk=0).d1          (same block as the line above)
 //   trial t>=2, first draw    : (b,k,t>>1,blk=255).d[t&1]   (trials 2m, 2m+1 share a block)
 //   trial t>=1, draw d>=1     : (b,k,t,blk=(d-1)>>1).d[(d-1)&1]   (EndCondSampling.cpp:470-474)
+//   direct sampler, draw 0    : (b,k,t=0,blk=0).d1          (trial 1's first draw: the first decision of the segment)
+//   direct sampler, draw d>=1 : (b,k,t=1+(d-1)/508,blk=((d-1)%508)>>1).d[(d-1)&1]
+//                               (EPV_OPT_DIRECT_SAMPLER, epv_direct.h: a segment has no trials, its draws fill
+//                               blocks 0..253 of trial words 1, 2, ...; block 255 is never used and no address
+//                               is read twice in a segment)
 // Most trials end at their first draw (no jump inside the segment), so the common case
 // costs ONE Philox block per segment.
 #ifndef EPV_PHILOX_H

@@ -157,6 +157,7 @@ class CppSampler:
         if not self.h:
             raise DriverError(self.L.epvd_last_error(None).decode())
         self.B = self.n_global = self.pattern_rows = 0
+        self._options = 0          # the option word last handed to epvd_set_options
 
     def close(self):
         if getattr(self, "h", None):
@@ -211,9 +212,17 @@ class CppSampler:
                 "rccl": bool(rccl.value), "halo": halo.value}
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
-        """EPV_OPT_* of include/epievo_mi355x.h on every context, those of later resets included"""
-        self._ck(self.L.epvd_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
-                                         (4 if sample_root else 0)))
+        """EPV_OPT_* of include/epievo_mi355x.h on every context, those of later resets included.  These three bits;
+        EPV_OPT_DIRECT_SAMPLER stays as set_direct_sampler left it, so the order of the two calls does not matter"""
+        self._options = (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) | \
+            (4 if sample_root else 0) | (self._options & 8)
+        self._ck(self.L.epvd_set_options(self.h, self._options))
+
+    def set_direct_sampler(self, on=True):
+        """EPV_OPT_DIRECT_SAMPLER on every context, those of later resets included: this bit of the word set_options
+        last wrote, the others kept"""
+        self._options = (self._options | 8) if on else (self._options & ~8)
+        self._ck(self.L.epvd_set_options(self.h, self._options))
 
     def set_timing(self, every):
         self._ck(self.L.epvd_set_timing(self.h, int(every)))

@@ -163,11 +163,13 @@ class ShardedSampler:
     per-rank engine (the HIP DeviceSampler / LocalGroup in the product; the tests inject an
     oracle-backed double to check the sharding logic on CPU with gloo)."""
 
-    def __init__(self, comm, device=0, device_factory=None):
+    def __init__(self, comm, device=0, device_factory=None, direct_sampler=False):
         self.comm = comm
         if device_factory is None:
             device_factory = DeviceSampler
         self.dev = device_factory(device)
+        # EPV_OPT_DIRECT_SAMPLER on this rank's engine (every context of a LocalGroup), set with the paths in setup()
+        self.direct_sampler = bool(direct_sampler)
         # a capacity overflow widens this shard's jump slots and the run carries on (as the
         # reference's vectors would); refresh_halos() brings all shards to the same width
         # before columns travel
@@ -214,6 +216,8 @@ class ShardedSampler:
         self.dev.set_tree(tree)
         self.dev.set_model(model)
         self.dev.upload_paths(fp_loc, capacity, self.g0, n_global)
+        if self.direct_sampler:
+            self.dev.set_direct_sampler(True)
         self.dev.set_halo(left, right)
         self.refresh_halos()
 
@@ -1039,6 +1043,10 @@ class LocalGroup:
     def set_options(self, **kw):
         for s in self.subs:
             s.set_options(**kw)
+
+    def set_direct_sampler(self, on=True):
+        for s in self.subs:
+            s.set_direct_sampler(on)
 
     def phase_mode(self):
         """kernels of a colour phase (DeviceSampler.phase_mode) -- of the largest shard"""

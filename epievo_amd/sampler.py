@@ -75,6 +75,7 @@ def _abi():
         "epv_philox_kat": [vp, u64, u32, u32p, dp], "epv_math_kat": [vp, u32, u32, u32, dp, dp],
         "epv_merge_kat": [vp, u32, u32p, dp, dp, u32p],
         "epv_trial_kat": [vp, u64, u32, u32p, dp, u32p, dp],
+        "epv_direct_kat": [vp, u64, u32, u32p, dp, u32p, dp], "epv_direct_giveups": [vp, u64p],
         "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
         "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
         "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
@@ -231,9 +232,38 @@ class DeviceSampler:
         return self._u64(getattr(self.L, "epv_%s_samples" % s.stem))
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
-        """see EPV_OPT_* in include/epievo_mi355x.h"""
-        self._ck(self.L.epv_set_options(self.h, (1 if reference_proposal_ratio else 0) |
-                                        (2 if forward_rejection else 0) | (4 if sample_root else 0)))
+        """see EPV_OPT_* in include/epievo_mi355x.h.  These three bits; EPV_OPT_DIRECT_SAMPLER stays as
+        set_direct_sampler left it, so the order of the two calls does not matter (forward_rejection while the
+        direct sampler is on: EpvError)"""
+        flags = C.c_uint32(0)
+        self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
+        self._ck(self.L.epv_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
+                                        (4 if sample_root else 0) | (flags.value & 8)))
+
+    def set_direct_sampler(self, on=True):
+        """EPV_OPT_DIRECT_SAMPLER: jump times by the direct end-conditioned sampler, bounded work per segment (DESIGN
+        7.22).  Its own call because set_options keeps its three keywords: it changes this bit of the word and leaves
+        the others, as set_options leaves this one.  With forward_rejection: EpvError."""
+        flags = C.c_uint32(0)
+        self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
+        self._ck(self.L.epv_set_options(self.h, (flags.value | 8) if on else (flags.value & ~8)))
+
+    def direct_giveups(self):
+        """segments the direct sampler gave up on since the context was created (epv_direct_giveups)"""
+        return self._u64(self.L.epv_direct_giveups)
+
+    def direct_kat(self, seed, items, reals):
+        """the direct end-conditioned sampler on known segments (epv_direct_kat): items[i] = (site, sweep, node,
+        segment, room, start state | end state << 1, first draw index, 0), reals[i] = (T, r0, r1, start time).  Returns
+        (uint32 [i, 4] = outcome, jumps, uniforms consumed, longest run of rounds; float64 [i, 8] = the first times)."""
+        it = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, 8)
+        re = np.ascontiguousarray(reals, dtype=np.float64).reshape(-1, 4)
+        if len(it) != len(re):
+            raise ValueError("direct_kat: items and reals differ in length")
+        w, d = np.zeros((len(it), 4), np.uint32), np.zeros((len(it), 8))
+        self._ck(self.L.epv_direct_kat(self.h, int(seed), len(it), _p(it, C.c_uint32), _p(re, C.c_double),
+                                       _p(w, C.c_uint32), _p(d, C.c_double)))
+        return w, d
 
     PHASE_KERNELS = {
         0: "epv_mh_propose_kernel + epv_mh_jumps_kernel + epv_mh_accept_kernel",
@@ -244,7 +274,8 @@ class DeviceSampler:
     }
 
     def phase_mode(self):
-        """EPV_PHASE_* of include/epievo_mi355x.h: which kernels a colour phase launches"""
+        """EPV_PHASE_* of include/epievo_mi355x.h: which kernels a colour phase launches.  (With the direct sampler
+        on, the jump stage of the named family runs its direct variants; phase_plan()["direct"] says so.)"""
         v = C.c_uint32(0)
         self._ck(self.L.epv_phase_mode(self.h, C.byref(v)))
         return int(v.value)
@@ -261,7 +292,7 @@ class DeviceSampler:
         return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
                     small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
                     jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
-                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1),
+                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1), direct=bool(w >> 23 & 1),
                     fused_lanes=(1 << (w >> 20 & 7)) if (w & 3) == 3 else 0)
 
     def philox_kat(self, seed, counters):
@@ -999,11 +1030,13 @@ class SingleSiteSampler:
     stream is the counter-based (seed, sweep) pair, so the caller passes the seed and
     the index of the EM iteration (sweep numbers never repeat across iterations)."""
 
-    def __init__(self, n_burn_in, n_batch, device=0, capacity=0):
+    def __init__(self, n_burn_in, n_batch, device=0, capacity=0, direct_sampler=False):
         self.burn_in, self.batch = int(n_burn_in), int(n_batch)
         # hard-wired false in the reference (SingleSiteSampler.cpp:441) and set by none of its programs;
         # True = EPV_OPT_SAMPLE_ROOT: root states are proposed too (reference-arithmetic kernels)
         self.SAMPLE_ROOT = False
+        # True = EPV_OPT_DIRECT_SAMPLER: jump times in bounded work per segment (no reference counterpart)
+        self.direct_sampler = bool(direct_sampler)
         self.capacity = capacity
         self.dev = DeviceSampler(device)
         self.dev.auto_grow = True     # paths grow on demand, as the reference's vectors do
@@ -1015,6 +1048,7 @@ class SingleSiteSampler:
         flags = C.c_uint32(0)
         self.dev._ck(self.dev.L.epv_get_options(self.dev.h, C.byref(flags)))
         want = (flags.value | 4) if self.SAMPLE_ROOT else (flags.value & ~4)
+        want = (want | 8) if self.direct_sampler else (want & ~8)
         if want != flags.value:
             self.dev._ck(self.dev.L.epv_set_options(self.dev.h, want))
 

@@ -72,8 +72,21 @@ typedef struct {
  *     is no longer identically 1, so the kernels evaluate it as under
  *     EPV_OPT_REFERENCE_PROPOSAL_RATIO (the first-generation proposal kernel; about half the
  *     default throughput).  Pinned: oracle rung A with the field set == the linked reference bit
- *     for bit; the GPU == rung B bit for bit (tests/test_sample_root.py). */
-enum { EPV_OPT_REFERENCE_PROPOSAL_RATIO = 1, EPV_OPT_FORWARD_REJECTION = 2, EPV_OPT_SAMPLE_ROOT = 4 };
+ *     for bit; the GPU == rung B bit for bit (tests/test_sample_root.py).
+ * EPV_OPT_DIRECT_SAMPLER  draw every segment's jump times from the conditional law itself (DESIGN.md section
+ *     7.22, csrc/epv_direct.h) instead of searching forward trials for one that ends in the right state: a
+ *     kept state stops with probability exp(-ra s) / Paa(s) or draws its next jump by a rejection that succeeds
+ *     with probability >= 1/2 per round, a state change draws it by inversion from a two-arm mixture.  Work is
+ *     O(jumps drawn) and every loop is counted, so a colour phase returns whatever the rates -- the default
+ *     search needs about exp(rate T) trials where a state is left fast and re-entered slowly.  Same conditional
+ *     law, another use of the random stream (not bit-comparable with the other two samplers; the CPU oracle has
+ *     no such mode, tests/direct_ref.py restates it).  A colour phase then runs the separate jump-time kernels
+ *     in their direct variants (plan bit 23; never the fused phase).  A segment that exhausts its 64 rounds
+ *     gives up: the proposal is rejected through the overflow flag and counted (epv_direct_giveups).  Together
+ *     with EPV_OPT_FORWARD_REJECTION: EPV_ERR_ARG.  The initial paths of epv_init_paths_indep and
+ *     the site-independent updates keep the default sampler. */
+enum { EPV_OPT_REFERENCE_PROPOSAL_RATIO = 1, EPV_OPT_FORWARD_REJECTION = 2, EPV_OPT_SAMPLE_ROOT = 4,
+       EPV_OPT_DIRECT_SAMPLER = 8 };
 
 /* Create a context on HIP device `device_id`.  Returns NULL when the device cannot be
  * initialised (the product has no CPU fallback).  Replaces
@@ -126,6 +139,9 @@ int epv_get_options(epv_ctx *ctx, uint32_t *flags);
  *     the tree walked level by level, heavy branches one lane each, a lane per (site, triple) in the
  *     acceptance).  No reference counterpart. */
 enum { EPV_PHASE_V1 = 0, EPV_PHASE_V2 = 1, EPV_PHASE_V2_SEGMENTS = 2, EPV_PHASE_FUSED = 3, EPV_PHASE_V3 = 4 };
+/* (Under EPV_OPT_DIRECT_SAMPLER the mode names the proposal kernel's family as above, but the jump stage runs its
+ * direct variants: mode 1 launches epv_mh_jumps_direct_kernel, not epv_mh_jumps_all_kernel, mode 2 the direct search
+ * and assembly kernels, and mode 3 is never reported.  epv_phase_plan's bit 23 tells the two apart.) */
 int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
 
 /* The exact kernel variants a colour phase of the resident paths launches, as one word (the launch
@@ -149,7 +165,10 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *   bit  18    V1: the template that reads the table of leaf evidence (epv_set_leaf_evidence holds a cell;
  *              it forces V1 too, and the mask of bit 17 rides along for the cells without evidence)
  *   bits 20-22 fused: log2 of the sites per wave (2 .. 6 for 4, 8, 16, 32 or 64 sites: EPV_FUSED_LANES, or by
- *              launch size -- with (n + 2) / 3 + 1 lanes 64 above 65536, 32 above 32768, else 16) */
+ *              launch size -- with (n + 2) / 3 + 1 lanes 64 above 65536, 32 above 32768, else 16)
+ *   bit  23    the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER): epv_seg_search_direct_kernel +
+ *              epv_seg_assemble_direct_kernel + epv_mh_jumps_direct_kernel under _SEGMENTS, epv_mh_jumps_direct_kernel
+ *              under _GENERAL; never with the fused phase or _ALL */
 enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
 enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
@@ -219,6 +238,23 @@ int epv_merge_kat(epv_ctx *ctx, uint32_t n, const uint32_t *heads, const double 
  * above this runs the functions in a kernel of their own, not a call site inside the MCMC kernels. */
 int epv_trial_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *items, const double *reals, uint32_t *w_out,
                   double *d_out);
+
+/* Known-answer entry for the direct end-conditioned sampler (run_direct of csrc/epv_direct.h), for tests:
+ * n <= 2^16 items, item i = one segment.
+ *   items[8 i ..]  site, sweep, node (<= 4095), segment (<= 4095), room (jump slots left; the entry caps it at 64),
+ *                  start state | end state << 1, the index of the segment's first draw in its stream (0 as the
+ *                  kernels have it, or an odd index up to 2^24: the draws then begin in the middle of the stream,
+ *                  so that an item can cross from one trial word into the next), 0
+ *   reals[4 i ..]  length T, rate of state 0, rate of state 1 (each positive and finite), the segment's start
+ *                  time (finite; added to every jump time)
+ * One lane per item, 64 items to a wave in the order given.  w_out[4 i ..] = outcome (1 ok, 2 overflow, 3 gave
+ * up), jumps, the index after the last uniform consumed, the longest run of rounds for one jump;  d_out[8 i ..] = the first 8 jump
+ * times (0 where there is none).  The key is `seed`.  Like the entries above this runs the function in a kernel
+ * of its own, not a call site inside the MCMC kernels. */
+int epv_direct_kat(epv_ctx *ctx, uint64_t seed, uint32_t n, const uint32_t *items, const double *reals, uint32_t *w_out,
+                   double *d_out);
+/* Segments the direct sampler gave up on since the context was created (each rejected its proposal). */
+int epv_direct_giveups(epv_ctx *ctx, uint64_t *n_giveups);
 
 /* Missing leaf data.  unobserved[(b-1)*n_sites + s] != 0: the leaf end state of branch b at local
  * site s is not data -- the MCMC resamples it with the history (its Felsenstein vector is (1, 1)
