@@ -451,10 +451,18 @@ int plan_mh(epv_ctx *c) {
 // records (EPV_HREC doubles).  The pool covers the typical demand of 64 lanes with a margin (a wave that
 // needs more runs in rounds) and always one lane's worst case.
 // the fused phase's kernel for a tree of nn nodes: the small-tree body for 2 <= nn <= EPV_P2_SMALL_MAX,
-// else (and for nn = 0) the generic one
+// else (and for nn = 0) the generic one; direct: the bodies whose jump stage is run_direct (EPV_OPT_DIRECT_FUSED)
 using fused_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t,
                                 uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused);
-fused_kernel_t fused_kernel(uint32_t nn) {
+fused_kernel_t fused_kernel(uint32_t nn, bool direct = false) {
+  if (direct)
+    switch (nn) {
+      case 2: return epv_mh_propose2_kernel<true, true, 2, true>;
+      case 3: return epv_mh_propose2_kernel<true, true, 3, true>;
+      case 4: return epv_mh_propose2_kernel<true, true, 4, true>;
+      case 5: return epv_mh_propose2_kernel<true, true, 5, true>;
+      default: return epv_mh_propose2_kernel<true, true, 0, true>;
+    }
   switch (nn) {
     case 2: return epv_mh_propose2_kernel<true, true, 2>;
     case 3: return epv_mh_propose2_kernel<true, true, 3>;
@@ -489,9 +497,10 @@ int plan_p2(epv_ctx *c) {
   const uint64_t f_seg_cap = 64ull * B * (2u * C + 1u), f_bt_cap = 64ull * B;
   const uint64_t f_bytes = (c->S.phase_cap + f_lanes - 1u) / f_lanes * (f_seg_cap * (sizeof(EpvSegTask) + sizeof(EpvSegOut)) + f_bt_cap * 12u);
   // (The options are not consulted: they may change after the paths are planned.  Under EPV_OPT_DIRECT_SAMPLER
-  // phase_plan never launches the fused phase, yet the pool below is sized as if it did -- c->fused stays true
-  // next to the separate V2 kernels, and a tree near the LDS limit may go to the global pool or to V1 for a
-  // fused body that does not run.  Results do not depend on it; the cost is not measured.)
+  // without EPV_OPT_DIRECT_FUSED phase_plan never launches the fused phase, yet the pool below is sized as if it
+  // did -- c->fused stays true next to the separate V2 kernels, and a tree near the LDS limit may go to the global
+  // pool or to V1 for a fused body that does not run.  Results do not depend on it; the cost is not measured.
+  // With EPV_OPT_DIRECT_FUSED the fused direct bodies run in these very buffers.)
   bool fused = !c->knobs.propose_v1 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
                (c->knobs.fused_phase < 0 ? phase_waves <= FUSED_MAX_WAVES : c->knobs.fused_phase != 0);
   // heavy-segment records: 8 doubles, 10 when the segment-parallel jump kernels read them back
@@ -1947,9 +1956,10 @@ PhasePlan phase_plan(const epv_ctx *c) {
   const bool p3 = c->p3 && !P.refq && !P.unobs && !P.evidence;
   const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !P.evidence && !c->p2_gpool;
   P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
-  // the direct sampler exists in the separate jump-time kernels only
+  // the direct sampler: the separate jump-time kernels, and the fused phase's direct
+  // bodies only where EPV_OPT_DIRECT_FUSED asks for them
   P.direct = c->S.flags & EPV_FLAG_DIRECT_SAMPLER;
-  if (p2 && c->fused && !P.direct) {
+  if (p2 && c->fused && (!P.direct || (c->S.flags & EPV_FLAG_DIRECT_FUSED))) {
     P.propose = EPV_PLAN_FUSED;
     P.small_nn = c->knobs.small_tree && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
     P.jumps = EPV_PLAN_JUMPS_FUSED;
@@ -2025,7 +2035,8 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     F.topo = 0u;               // small-tree body: bit node = a leaf, bits 8 + 3 node .. = the parent
     for (uint32_t node = 1; node < P.small_nn; ++node)
       F.topo |= (c->subtree[node] == 1u ? 1u << node : 0u) | (c->parent[node] << (8u + 3u * node));
-    const auto kf = fused_kernel(P.small_nn);
+    F.giveups = c->d_counters + EPV_CNT_WORDS;
+    const auto kf = fused_kernel(P.small_nn, P.direct);
     hipLaunchKernelGGL(kf, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S,
                        (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,
                        c->p2_pool, 0u, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
@@ -2296,8 +2307,9 @@ EPV_API epv_ctx *epv_create(int device_id) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn)),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (int direct = 0; direct < 2; ++direct)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn, direct != 0)),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const void *v1[] = {
       reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_DATA>),
       reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_DATA>),
@@ -2584,11 +2596,14 @@ static int finish_mcmc(epv_ctx *c, uint64_t *n_accepted, uint64_t acc_base);
 EPV_API int epv_set_options(epv_ctx *c, uint32_t flags) {
   if (!c) return EPV_ERR_ARG;
   if (flags & ~(uint32_t)(EPV_OPT_REFERENCE_PROPOSAL_RATIO | EPV_OPT_FORWARD_REJECTION | EPV_OPT_SAMPLE_ROOT |
-                          EPV_OPT_DIRECT_SAMPLER))
+                          EPV_OPT_DIRECT_SAMPLER | EPV_OPT_DIRECT_FUSED))
     return fail(c, EPV_ERR_ARG, "unknown option bits");
+  if ((flags & EPV_OPT_DIRECT_FUSED) && !(flags & EPV_OPT_DIRECT_SAMPLER))
+    return fail(c, EPV_ERR_ARG, "EPV_OPT_DIRECT_FUSED selects the fused body of EPV_OPT_DIRECT_SAMPLER: set both");
   if ((flags & EPV_OPT_DIRECT_SAMPLER) && (flags & EPV_OPT_FORWARD_REJECTION))
     return fail(c, EPV_ERR_ARG, "EPV_OPT_DIRECT_SAMPLER and EPV_OPT_FORWARD_REJECTION name two samplers: set one");
-  static_assert(EPV_OPT_DIRECT_SAMPLER == EPV_FLAG_DIRECT_SAMPLER, "option bits");
+  static_assert(EPV_OPT_DIRECT_SAMPLER == EPV_FLAG_DIRECT_SAMPLER && EPV_OPT_DIRECT_FUSED == EPV_FLAG_DIRECT_FUSED,
+                "option bits");
   static_assert(EPV_OPT_REFERENCE_PROPOSAL_RATIO == EPV_FLAG_REFERENCE_PROPOSAL_RATIO &&
                 EPV_OPT_FORWARD_REJECTION == EPV_FLAG_FORWARD_REJECTION && EPV_OPT_SAMPLE_ROOT == EPV_FLAG_SAMPLE_ROOT,
                 "option bits");

@@ -108,6 +108,7 @@ struct EpvIndepConst {
 #define EPV_FLAG_REFERENCE_PROPOSAL_RATIO 1u  /* evaluate q(old)/q(new) with the reference's sums */
 #define EPV_FLAG_FORWARD_REJECTION 2u         /* state-changing segments by forward rejection too */
 #define EPV_FLAG_DIRECT_SAMPLER 8u            /* jump times by the direct end-conditioned sampler (epv_direct.h) */
+#define EPV_FLAG_DIRECT_FUSED 16u             /* ... in the fused phase too, where that is eligible (epv_propose2.h, DIRECT) */
 #define EPV_FLAG_SAMPLE_ROOT 4u               /* SingleSiteSampler::SAMPLE_ROOT: propose the root state too (reference arithmetic kernels) */
 
 // counters[] slots

@@ -333,6 +333,31 @@ __global__ __launch_bounds__(256) void epv_seg_assemble_kernel(EpvDev S, uint32_
 // the assembly rejects the proposal exactly where the sequential walk does.  (The give-up COUNT may differ from the
 // sequential kernel's: a segment that gives up here beyond the room the walk would have left it is an overflow
 // there and counted as one.  Both reject the proposal, so the paths agree; the event has probability <= 2^-64.)
+
+// one segment of a list by run_direct at the whole capacity, into its EpvSegOut (the loop body of
+// epv_seg_search_direct_kernel and of the fused phase's direct jump stage, epv_propose2.h); a segment that gives
+// up is counted in *giveups
+__device__ __forceinline__ void epv_seg_direct_one(const EpvDev &S, const double *s_rates, const EpvSegTask *segs,
+                                                   EpvSegOut *outs, uint64_t i, uint32_t seed_lo, uint32_t seed_hi,
+                                                   uint32_t sweep, unsigned long long *giveups) {
+  const EpvSegTask t = segs[i];
+  EpvSegOut o;
+  o.cnt = 0u; o.tstar = 0u; o.maxm = 0u; o.pad = 0u; o.j0 = 0.0; o.j1 = 0.0;
+  if (t.len >= 0.0) {
+    const uint32_t gsite = (uint32_t)(S.g0 + (t.w0 & 0xffffffffffull));
+    const uint32_t node = (uint32_t)(t.w0 >> 40) & 4095u, k = (uint32_t)(t.w0 >> 52);
+    const uint32_t prev = (uint32_t)t.w3 & 1u, sampled = (uint32_t)(t.w3 >> 1) & 1u, trip0 = (uint32_t)(t.w3 >> 2) & 7u;
+    double jt[2] = {0.0, 0.0};
+    uint32_t cnt = 0u, drawn, rounds;
+    const int oc = run_direct(seed_lo, seed_hi, gsite, sweep, node, k, prev, sampled, t.len, s_rates[trip0],
+                              s_rates[trip0 | 2u], S.C, jt, 1u, 2u, t.start, cnt, drawn, rounds);
+    if (oc == TRIAL_GIVEUP) atomicAdd(giveups, 1ull);
+    o.cnt = cnt; o.tstar = 1u; o.maxm = oc == TRIAL_OK ? cnt : 0xffffffffu;
+    o.j0 = jt[0]; o.j1 = jt[1];
+  }
+  outs[i] = o;
+}
+
 __global__ __launch_bounds__(256, EPV_SEARCH_WAVES) void epv_seg_search_direct_kernel(EpvDev S, uint32_t seed_lo,
                                                                                       uint32_t seed_hi, uint32_t sweep,
                                                                                       unsigned long long *counters,
@@ -345,24 +370,8 @@ __global__ __launch_bounds__(256, EPV_SEARCH_WAVES) void epv_seg_search_direct_k
   const uint64_t n_seg = (packed & 0xffffffffull) < S.seg_cap ? (uint64_t)(packed & 0xffffffffull) : S.seg_cap;
   const EpvSegTask *segs = S.segs + (uint64_t)shard * S.seg_cap;
   EpvSegOut *outs = S.segout + (uint64_t)shard * S.seg_cap;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_seg; i += (uint64_t)gridDim.x * blockDim.x) {
-    const EpvSegTask t = segs[i];
-    EpvSegOut o;
-    o.cnt = 0u; o.tstar = 0u; o.maxm = 0u; o.pad = 0u; o.j0 = 0.0; o.j1 = 0.0;
-    if (t.len >= 0.0) {
-      const uint32_t gsite = (uint32_t)(S.g0 + (t.w0 & 0xffffffffffull));
-      const uint32_t node = (uint32_t)(t.w0 >> 40) & 4095u, k = (uint32_t)(t.w0 >> 52);
-      const uint32_t prev = (uint32_t)t.w3 & 1u, sampled = (uint32_t)(t.w3 >> 1) & 1u, trip0 = (uint32_t)(t.w3 >> 2) & 7u;
-      double jt[2] = {0.0, 0.0};
-      uint32_t cnt = 0u, drawn, rounds;
-      const int oc = run_direct(seed_lo, seed_hi, gsite, sweep, node, k, prev, sampled, t.len, s_rates[trip0],
-                                s_rates[trip0 | 2u], S.C, jt, 1u, 2u, t.start, cnt, drawn, rounds);
-      if (oc == TRIAL_GIVEUP) atomicAdd(giveups, 1ull);
-      o.cnt = cnt; o.tstar = 1u; o.maxm = oc == TRIAL_OK ? cnt : 0xffffffffu;
-      o.j0 = jt[0]; o.j1 = jt[1];
-    }
-    outs[i] = o;
-  }
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_seg; i += (uint64_t)gridDim.x * blockDim.x)
+    epv_seg_direct_one(S, s_rates, segs, outs, i, seed_lo, seed_hi, sweep, giveups);
 }
 
 __global__ __launch_bounds__(256) void epv_seg_assemble_direct_kernel(EpvDev S, uint32_t seed_lo, uint32_t seed_hi,

@@ -160,6 +160,7 @@ struct EpvFused {
   uint32_t lanes;              // sites per wave
   uint32_t grouped_rounds;     // rounds of the grouped search of short segment lists (0 = off)
   uint32_t topo;               // small-tree body: the topology word (bit node: a leaf; bits 8 + 3 node ..: the parent)
+  unsigned long long *giveups; // DIRECT bodies: the direct sampler's give-up counter (epv_direct_giveups)
 };
 
 // NN > 0 (fused phase only): the node count as a compile-time constant, for trees of at most
@@ -169,13 +170,17 @@ struct EpvFused {
 // indexed by constants, and the topology is one scalar word read at the kernel's head.  The LDS copies
 // stay for what other lanes read (heavy-pair merges, the emission pass, the acceptance stage).  Same
 // operations in the same order: the results are the generic body's bit for bit.  NN = 0: S.N nodes.
+// DIRECT (fused phase only, EPV_OPT_DIRECT_FUSED): the jump stage samples every segment of the wave's list by
+// run_direct (epv_direct.h) instead of searching trials -- one counted loop over the list, then the assembly of
+// every branch; the searches and their cooperative LDS area are not compiled, so every loop of the kernel is counted.
 #define EPV_P2_SMALL_MAX 5
-template <bool SEG, bool FUSED, int NN = 0>
+template <bool SEG, bool FUSED, int NN = 0, bool DIRECT = false>
 __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,
     uint64_t last, uint64_t own_first, uint64_t own_last, uint32_t pool_dbl, uint32_t list_cap,
     uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab, EpvFused F) {
   static_assert(!FUSED || SEG, "the fused phase emits segments");
+  static_assert(!DIRECT || FUSED, "the direct body is the fused phase's");
   constexpr bool SMALL = NN > 0;
   static_assert(!SMALL || (FUSED && NN >= 2 && NN <= EPV_P2_SMALL_MAX), "the small-tree body is the fused phase's");
   constexpr int NNA = SMALL ? NN : 1;      // register array extents (1: unused by the generic body)
@@ -956,7 +961,24 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
     uint32_t f_nfin = 0u;      // branches the grouped search finished
-    if (f_nseg) {
+    if constexpr (DIRECT) {
+      if (f_nseg) {
+        // lane l samples segments l, l + 64, ... of the wave's list at the whole capacity (the body of
+        // epv_seg_search_direct_kernel); then every branch is assembled with run_direct for the replay
+        for (uint32_t i = (uint32_t)lane; i < f_nseg; i += 64u)
+          epv_seg_direct_one(S, s_rates, segs, outs, i, seed_lo, seed_hi, sweep, F.giveups);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        P2_MARK(7);
+        for (uint32_t i = (uint32_t)lane; i < f_nbt; i += 64u)
+          epv_seg_assemble_one<!FUSED, true>(S, s_rates, segs, outs, F.bt[f_wave * F.bt_cap + i], F.bfirst[f_wave * F.bt_cap + i],
+                                             s0, seed_lo, seed_hi, sweep, true, s_meta + 2u * B * 64u,
+                                             site - 3u * (uint64_t)lane, SMALL ? s_flag : nullptr);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        P2_MARK(8);
+      }
+    } else if (f_nseg) {
       EpvCoop W;
       W.len = pool; W.r0 = pool + 64; W.r1 = pool + 128; W.trunc = pool + 192; W.tj = pool + 256;
       uint32_t *u = reinterpret_cast<uint32_t *>(pool + 384);

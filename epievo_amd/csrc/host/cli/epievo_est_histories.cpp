@@ -74,7 +74,7 @@ static string strip_path(const string &full) {
 
 int main(int argc, const char **argv) {
   try {
-    bool VERBOSE = false, single_branch = false, direct_sampler = false;
+    bool VERBOSE = false, single_branch = false, direct_sampler = false, direct_fused = false;
     string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
@@ -94,6 +94,8 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("single_branch", 'T', "pairwise process (assumes no tree)", false, single_branch);
     opt_parse.add_opt("direct-sampler", 'j', "jump times by the direct end-conditioned sampler: bounded work per segment "
                       "whatever the rates", false, direct_sampler);
+    opt_parse.add_opt("direct-fused", 'F', "the direct sampler inside the fused colour phase where that is eligible "
+                      "(implies -j; same results)", false, direct_fused);
     opt_parse.add_opt("verbose", 'v', "print more run info", false, VERBOSE);
     opt_parse.add_opt("gpus", 'g', "GPUs to shard the sites over: all | 0,1,.. (default: EPV_DEVICES or 0)", false,
                       gpu_list);
@@ -228,7 +230,8 @@ int main(int argc, const char **argv) {
 
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
-    if (direct_sampler) mcmc.set_options((uint32_t)EPV_OPT_DIRECT_SAMPLER);   // (every context, later resets included)
+    if (direct_sampler || direct_fused)     // (every context, later resets included)
+      mcmc.set_options((uint32_t)EPV_OPT_DIRECT_SAMPLER | (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
     mcmc.reset(the_model, th, paths);

@@ -39,7 +39,7 @@ static string strip_path(const string &full) {
 
 int main(int argc, const char **argv) {
   try {
-    bool VERBOSE = false, single_branch = false, optimize_branches = false, direct_sampler = false;
+    bool VERBOSE = false, single_branch = false, optimize_branches = false, direct_sampler = false, direct_fused = false;
     string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file, leaf_probs_file;
     size_t iteration = 10, batch = 10, burnin = 10, paths_every = 1;
     size_t rng_seed = std::numeric_limits<size_t>::max();
@@ -58,6 +58,8 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("branch", 'b', "optimize branch lengths", false, optimize_branches);
     opt_parse.add_opt("direct-sampler", 'j', "jump times by the direct end-conditioned sampler: bounded work per segment "
                       "whatever the rates", false, direct_sampler);
+    opt_parse.add_opt("direct-fused", 'F', "the direct sampler inside the fused colour phase where that is eligible "
+                      "(implies -j; same results)", false, direct_fused);
     opt_parse.add_opt("verbose", 'v', "print more run info", false, VERBOSE);
     opt_parse.add_opt("gpus", 'g', "GPUs to shard the sites over: all | 0,1,.. (default: EPV_DEVICES or 0)", false,
                       gpu_list);
@@ -136,7 +138,8 @@ int main(int argc, const char **argv) {
     vector<double> out_branches;
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
-    if (direct_sampler) mcmc.set_options((uint32_t)EPV_OPT_DIRECT_SAMPLER);   // (every context, later resets included)
+    if (direct_sampler || direct_fused)     // (every context, later resets included)
+      mcmc.set_options((uint32_t)EPV_OPT_DIRECT_SAMPLER | (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
     // declared AFTER everything the thread references (and after the sampler): on an exception the

@@ -163,13 +163,15 @@ class ShardedSampler:
     per-rank engine (the HIP DeviceSampler / LocalGroup in the product; the tests inject an
     oracle-backed double to check the sharding logic on CPU with gloo)."""
 
-    def __init__(self, comm, device=0, device_factory=None, direct_sampler=False):
+    def __init__(self, comm, device=0, device_factory=None, direct_sampler=False, direct_fused=False):
         self.comm = comm
         if device_factory is None:
             device_factory = DeviceSampler
         self.dev = device_factory(device)
         # EPV_OPT_DIRECT_SAMPLER on this rank's engine (every context of a LocalGroup), set with the paths in setup()
         self.direct_sampler = bool(direct_sampler)
+        # with direct_sampler: EPV_OPT_DIRECT_FUSED as well (the fused phase's direct bodies where it is eligible)
+        self.direct_fused = bool(direct_fused)
         # a capacity overflow widens this shard's jump slots and the run carries on (as the
         # reference's vectors would); refresh_halos() brings all shards to the same width
         # before columns travel
@@ -216,7 +218,9 @@ class ShardedSampler:
         self.dev.set_tree(tree)
         self.dev.set_model(model)
         self.dev.upload_paths(fp_loc, capacity, self.g0, n_global)
-        if self.direct_sampler:
+        if self.direct_sampler and self.direct_fused:
+            self.dev.set_direct_sampler(True, fused=True)
+        elif self.direct_sampler:
             self.dev.set_direct_sampler(True)
         self.dev.set_halo(left, right)
         self.refresh_halos()
@@ -1044,9 +1048,9 @@ class LocalGroup:
         for s in self.subs:
             s.set_options(**kw)
 
-    def set_direct_sampler(self, on=True):
+    def set_direct_sampler(self, on=True, fused=False):
         for s in self.subs:
-            s.set_direct_sampler(on)
+            s.set_direct_sampler(on, fused=fused)
 
     def phase_mode(self):
         """kernels of a colour phase (DeviceSampler.phase_mode) -- of the largest shard"""

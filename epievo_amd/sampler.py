@@ -232,21 +232,23 @@ class DeviceSampler:
         return self._u64(getattr(self.L, "epv_%s_samples" % s.stem))
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
-        """see EPV_OPT_* in include/epievo_mi355x.h.  These three bits; EPV_OPT_DIRECT_SAMPLER stays as
-        set_direct_sampler left it, so the order of the two calls does not matter (forward_rejection while the
+        """see EPV_OPT_* in include/epievo_mi355x.h.  These three bits; EPV_OPT_DIRECT_SAMPLER and EPV_OPT_DIRECT_FUSED
+        stay as set_direct_sampler left them, so the order of the two calls does not matter (forward_rejection while the
         direct sampler is on: EpvError)"""
         flags = C.c_uint32(0)
         self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
         self._ck(self.L.epv_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
-                                        (4 if sample_root else 0) | (flags.value & 8)))
+                                        (4 if sample_root else 0) | (flags.value & 24)))
 
-    def set_direct_sampler(self, on=True):
+    def set_direct_sampler(self, on=True, fused=False):
         """EPV_OPT_DIRECT_SAMPLER: jump times by the direct end-conditioned sampler, bounded work per segment (DESIGN
-        7.22).  Its own call because set_options keeps its three keywords: it changes this bit of the word and leaves
-        the others, as set_options leaves this one.  With forward_rejection: EpvError."""
+        7.22).  Its own call because set_options keeps its three keywords: it changes its bits of the word and leaves
+        the others, as set_options leaves these.  With forward_rejection: EpvError.
+        fused=True adds EPV_OPT_DIRECT_FUSED: where the default mode would run the fused phase, the direct mode runs
+        the fused kernel's direct bodies (same results bit for bit, one launch per colour phase).  on=False clears both."""
         flags = C.c_uint32(0)
         self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
-        self._ck(self.L.epv_set_options(self.h, (flags.value | 8) if on else (flags.value & ~8)))
+        self._ck(self.L.epv_set_options(self.h, (flags.value & ~24) | ((8 | (16 if fused else 0)) if on else 0)))
 
     def direct_giveups(self):
         """segments the direct sampler gave up on since the context was created (epv_direct_giveups)"""
@@ -1030,13 +1032,15 @@ class SingleSiteSampler:
     stream is the counter-based (seed, sweep) pair, so the caller passes the seed and
     the index of the EM iteration (sweep numbers never repeat across iterations)."""
 
-    def __init__(self, n_burn_in, n_batch, device=0, capacity=0, direct_sampler=False):
+    def __init__(self, n_burn_in, n_batch, device=0, capacity=0, direct_sampler=False, direct_fused=False):
         self.burn_in, self.batch = int(n_burn_in), int(n_batch)
         # hard-wired false in the reference (SingleSiteSampler.cpp:441) and set by none of its programs;
         # True = EPV_OPT_SAMPLE_ROOT: root states are proposed too (reference-arithmetic kernels)
         self.SAMPLE_ROOT = False
         # True = EPV_OPT_DIRECT_SAMPLER: jump times in bounded work per segment (no reference counterpart)
         self.direct_sampler = bool(direct_sampler)
+        # with direct_sampler: EPV_OPT_DIRECT_FUSED, the fused phase's direct bodies where the fused phase is eligible
+        self.direct_fused = bool(direct_fused)
         self.capacity = capacity
         self.dev = DeviceSampler(device)
         self.dev.auto_grow = True     # paths grow on demand, as the reference's vectors do
@@ -1048,7 +1052,7 @@ class SingleSiteSampler:
         flags = C.c_uint32(0)
         self.dev._ck(self.dev.L.epv_get_options(self.dev.h, C.byref(flags)))
         want = (flags.value | 4) if self.SAMPLE_ROOT else (flags.value & ~4)
-        want = (want | 8) if self.direct_sampler else (want & ~8)
+        want = (want & ~24) | ((8 | (16 if self.direct_fused else 0)) if self.direct_sampler else 0)
         if want != flags.value:
             self.dev._ck(self.dev.L.epv_set_options(self.dev.h, want))
 

@@ -81,12 +81,18 @@ typedef struct {
  *     search needs about exp(rate T) trials where a state is left fast and re-entered slowly.  Same conditional
  *     law, another use of the random stream (not bit-comparable with the other two samplers; the CPU oracle has
  *     no such mode, tests/direct_ref.py restates it).  A colour phase then runs the separate jump-time kernels
- *     in their direct variants (plan bit 23; never the fused phase).  A segment that exhausts its 64 rounds
+ *     in their direct variants (plan bit 23; the fused phase only with EPV_OPT_DIRECT_FUSED).  A segment that exhausts its 64 rounds
  *     gives up: the proposal is rejected through the overflow flag and counted (epv_direct_giveups).  Together
  *     with EPV_OPT_FORWARD_REJECTION: EPV_ERR_ARG.  The initial paths of epv_init_paths_indep and
- *     the site-independent updates keep the default sampler. */
+ *     the site-independent updates keep the default sampler.
+ * EPV_OPT_DIRECT_FUSED  only together with EPV_OPT_DIRECT_SAMPLER (alone: EPV_ERR_ARG).  Wherever the default
+ *     mode would run the fused phase, the direct mode runs it too, in the kernel's direct bodies: the wave samples
+ *     its segment list by the same run_direct and assembles its branches itself, with no unbounded loop.  Same
+ *     paths, statistics and counters as without the bit, bit for bit; where the fused phase is not eligible
+ *     (a reference ratio, a sampled root, unobserved or evidence leaf cells, the large-tree kernel, a global
+ *     pool, launches above the fused limit) the plan is that of EPV_OPT_DIRECT_SAMPLER alone. */
 enum { EPV_OPT_REFERENCE_PROPOSAL_RATIO = 1, EPV_OPT_FORWARD_REJECTION = 2, EPV_OPT_SAMPLE_ROOT = 4,
-       EPV_OPT_DIRECT_SAMPLER = 8 };
+       EPV_OPT_DIRECT_SAMPLER = 8, EPV_OPT_DIRECT_FUSED = 16 };
 
 /* Create a context on HIP device `device_id`.  Returns NULL when the device cannot be
  * initialised (the product has no CPU fallback).  Replaces
@@ -141,7 +147,8 @@ int epv_get_options(epv_ctx *ctx, uint32_t *flags);
 enum { EPV_PHASE_V1 = 0, EPV_PHASE_V2 = 1, EPV_PHASE_V2_SEGMENTS = 2, EPV_PHASE_FUSED = 3, EPV_PHASE_V3 = 4 };
 /* (Under EPV_OPT_DIRECT_SAMPLER the mode names the proposal kernel's family as above, but the jump stage runs its
  * direct variants: mode 1 launches epv_mh_jumps_direct_kernel, not epv_mh_jumps_all_kernel, mode 2 the direct search
- * and assembly kernels, and mode 3 is never reported.  epv_phase_plan's bit 23 tells the two apart.) */
+ * and assembly kernels, and mode 3 is reported only with EPV_OPT_DIRECT_FUSED: the fused kernel's direct bodies.
+ * epv_phase_plan's bit 23 tells the two apart.) */
 int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
 
 /* The exact kernel variants a colour phase of the resident paths launches, as one word (the launch
@@ -168,7 +175,7 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *              launch size -- with (n + 2) / 3 + 1 lanes 64 above 65536, 32 above 32768, else 16)
  *   bit  23    the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER): epv_seg_search_direct_kernel +
  *              epv_seg_assemble_direct_kernel + epv_mh_jumps_direct_kernel under _SEGMENTS, epv_mh_jumps_direct_kernel
- *              under _GENERAL; never with the fused phase or _ALL */
+ *              under _GENERAL; with EPV_OPT_DIRECT_FUSED the fused kernel's direct bodies (_FUSED); never with _ALL */
 enum { EPV_PLAN_V1 = 0, EPV_PLAN_V2 = 1, EPV_PLAN_V3 = 2, EPV_PLAN_FUSED = 3 };
 enum { EPV_PLAN_JUMPS_FUSED = 0, EPV_PLAN_JUMPS_SEGMENTS = 1, EPV_PLAN_JUMPS_ALL = 2, EPV_PLAN_JUMPS_GENERAL = 3 };
 enum { EPV_PLAN_ACCEPT_FUSED = 0, EPV_PLAN_ACCEPT_V3 = 1, EPV_PLAN_ACCEPT_CACHE = 2, EPV_PLAN_ACCEPT_NO_CACHE = 3 };
