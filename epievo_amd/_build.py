@@ -87,6 +87,8 @@ def build_host(force=False):
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith((".cpp", ".hpp"))]
     srcs.append(os.path.join(CSRC, "epv_domain_bin.h"))   # (shared with the device code)
     srcs.append(os.path.join(CSRC, "epv_turnover_rec.h"))
+    srcs += [os.path.join(CSRC, "epv_plan.h"), os.path.join(CSRC, "epv_device.h"),   # (the colour phase's planner)
+             os.path.join(INCLUDE, "epievo_mi355x.h")]
     if not force and _newer(HOST_SO, srcs):
         return HOST_SO
     cmd = ["g++"] + HOST_FLAGS + ["-shared", "-I", HOST, "-I", INCLUDE, "-o", HOST_SO] + \

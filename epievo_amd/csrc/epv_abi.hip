@@ -15,6 +15,7 @@
 
 #include "epievo_mi355x.h"
 #include "epv_device.h"
+#include "epv_plan.h"     // the colour phase: knobs, launch shapes, kernel variants (host only)
 
 #define EPV_API extern "C" __attribute__((visibility("default")))
 
@@ -31,42 +32,6 @@
 #include "epv_corr.h"
 #include "epv_dmaps.h"
 #include "epv_patterns.h"
-
-// The library's knobs: environment variables that a context reads once, when epv_create makes it.
-// Each reaches a kernel path that the automatic choice would not take on a test's small input.  In
-// brackets, the tests that set it: P test_gpu_parity, M test_kernel_matrix, F test_fused_small_tree,
-// A test_path_average_gpu.
-//   EPV_PROPOSE_V1=1        the first proposal kernel everywhere [P M]
-//   EPV_PROPOSE_V3=0/1      the large-tree proposal kernel never / wherever the plan allows it; default:
-//                           where the second kernel's record pool does not fit LDS [P M]
-//   EPV_SEG_JUMPS=0/1       segment-parallel jump kernels off / on; default: kbar >= 0.25 [P M A]
-//   EPV_FUSED_PHASE=0/1     the fused colour phase off / on; default: phases of <= 3072 waves [P M F A]
-//   EPV_P2_SMALL_TREE=0     the fused phase's generic body also on trees of <= EPV_P2_SMALL_MAX nodes [F]
-//   EPV_FUSED_LANES=4/8/16/32/64   sites per wave of the fused phase (any other value: 64); default:
-//                           by launch size [F]
-//   EPV_FORCE_LDS_POOL      (set) the record pool in LDS wherever one lane's worst case fits [P M]
-//   EPV_FORCE_GLOBAL_POOL   (set) no LDS record pool: the first kernel's goes to global memory, and
-//                           the second kernel is not planned [M]
-//   EPV_P3_MIN_LIST         (set) the large-tree kernel's heavy list holds one lane's worst case only,
-//                           so that busy waves run in several rounds [P]
-//   EPV_P3_SLAB_POOL=0/1/2  the large-tree kernel's slabs: one per block / from a per-XCD pool when the
-//                           launch has more blocks than the pool has slabs (default) / always pooled [P M]
-//   EPV_ACCEPT_V3=0/1       the accept stage: the (no-)cache kernel / epv_mh_accept3_kernel; default:
-//                           accept3 where there is no meta cache [P]
-//   EPV_ACCEPT_NO_CACHE     (set) no LDS meta cache in the accept stage [P]
-struct EpvKnobs {
-  bool propose_v1 = false;
-  int propose_v3 = -1;         // -1: by the plan
-  int seg_jumps = -1;          // -1: by workload
-  int fused_phase = -1;        // -1: by launch size
-  bool small_tree = true;
-  uint32_t fused_lanes = 0;    // 0: by launch size
-  bool force_lds_pool = false, force_global_pool = false;
-  bool p3_min_list = false;
-  int p3_slab_pool = 1;
-  int accept_v3 = -1;          // -1: by the meta cache
-  bool accept_no_cache = false;
-};
 
 // ---- the state of the posterior summaries ("layers") of run_mcmc, one struct each.  Every member has a default:
 // a layer goes off by freeing its device buffers and taking a default-constructed struct (the *_off functions).
@@ -270,35 +235,19 @@ struct epv_ctx {
   uint64_t stage_cap = 0;
   hipEvent_t ev_copy[2] = {nullptr, nullptr};   // epv_copy_columns_async: "slot s of my staging buffer is packed"
   EpvIndepConst *d_indep = nullptr;  // [N] constants of the site-independent model
-  // launch shape of the MH kernel
-  uint32_t mh_threads = 64, pool_entries = 0;
-  bool mh_gpool = false;        // record pool of the propose kernel in global memory (large trees)
-  double *d_gpool = nullptr;
-  uint64_t gpool_cap = 0;       // doubles allocated
-  uint64_t gpool_need = 0, gpool3_need = 0;   // what the plans ask for; allocated when a launch first uses the slab
-  // second-generation proposal kernel (epv_propose2.h), one wave per block
-  uint32_t p2_pool = 0;          // LDS doubles per wave
-  bool p2_gpool = false;         // the pool does not fit LDS: the kernel is not planned
-  size_t p2_lds = 0;
-  double *d_gpool3 = nullptr;
-  uint64_t gpool3_cap = 0;
+  // launch shapes of the proposal kernels for the uploaded tree and paths (plan_kernels)
+  PhaseShapes shapes;
+  // global-memory slabs of the first and the third proposal kernel, allocated when a launch first takes the kernel
+  double *d_gpool = nullptr, *d_gpool3 = nullptr;
+  uint64_t gpool_cap = 0, gpool3_cap = 0;   // doubles allocated
   double *d_segtab = nullptr;    // [B][4][6] single-segment matrices, refreshed by epv_reset
-  // third proposal kernel (epv_propose3.h): large trees, where the record pool does not fit LDS
-  bool p3 = false;               // decided by plan_p3 for the uploaded tree and paths
-  uint32_t p3_list_cap = 0, p3_qrows = 0, p3_nup = 0, p3_depth = 0;
-  uint32_t p3_slots = 0;         // slabs per XCD handed out to resident blocks (0 = a slab per block of the launch)
   uint32_t *d_slabflags = nullptr;
-  size_t p3_lds = 0;
-  uint32_t *d_nodetab = nullptr; // node words and level lists of epv_mh_propose3_kernel (EPV_P3_*)
+  uint32_t *d_nodetab = nullptr; // shapes.v3.nodetab on the device
   uint32_t phase_parity = 0;     // accept lists are double-buffered by phase parity
-  // fused colour phase (epv_propose2.h, FUSED): one kernel per phase for launches of few waves
-  bool fused = false;            // decided by plan_p2 for the uploaded paths
-  uint32_t fused_lanes = 64;     // sites per wave of the fused phase (64 / 32 / 16 by launch size)
-  EpvFused F{};                  // per-wave lists, allocated on first use
+  EpvFused F{};                  // per-wave lists of the fused colour phase, allocated on first use
   uint64_t fused_waves = 0;      // waves the lists are allocated for
   double kbar = 0.0;  // mean jumps per (site, branch) of the uploaded paths
   double fwd_alloc_ms = 0.0, fwd_sim_ms = 0.0;   // epv_forward_simulate: device memory management / the simulation itself
-  size_t mh_lds = 0;
   // counters / timing
   uint64_t n_sweeps = 0, tot_overflow = 0, tot_coop = 0;
   bool timing = false;           // events around THIS launch (set per launch from timing_every)
@@ -331,30 +280,6 @@ struct epv_ctx {
 };
 
 namespace {
-
-// the knobs as the environment holds them now (epv_create)
-EpvKnobs read_knobs() {
-  EpvKnobs k;
-  auto has = [](const char *name) { return std::getenv(name) != nullptr; };
-  auto num = [](const char *name, int unset) { const char *e = std::getenv(name); return e ? std::atoi(e) : unset; };
-  k.propose_v1 = num("EPV_PROPOSE_V1", 0) != 0;
-  if (has("EPV_PROPOSE_V3")) k.propose_v3 = num("EPV_PROPOSE_V3", 0) != 0 ? 1 : 0;
-  if (has("EPV_SEG_JUMPS")) k.seg_jumps = num("EPV_SEG_JUMPS", 0) != 0 ? 1 : 0;
-  if (has("EPV_FUSED_PHASE")) k.fused_phase = num("EPV_FUSED_PHASE", 0) != 0 ? 1 : 0;
-  k.small_tree = num("EPV_P2_SMALL_TREE", 1) != 0;
-  if (has("EPV_FUSED_LANES")) {
-    const int v = num("EPV_FUSED_LANES", 0);
-    k.fused_lanes = (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) ? (uint32_t)v : 64u;
-  }
-  k.force_lds_pool = has("EPV_FORCE_LDS_POOL");
-  k.force_global_pool = has("EPV_FORCE_GLOBAL_POOL");
-  k.p3_min_list = has("EPV_P3_MIN_LIST");
-  k.p3_slab_pool = num("EPV_P3_SLAB_POOL", 1);
-  k.accept_v3 = num("EPV_ACCEPT_V3", -1);
-  k.accept_no_cache = has("EPV_ACCEPT_NO_CACHE");
-  return k;
-}
-
 
 int fail(epv_ctx *c, int code, const std::string &msg) {
   if (c) c->err = msg;
@@ -408,239 +333,33 @@ int ensure_stage(epv_ctx *c, uint64_t bytes) {
   return EPV_OK;
 }
 
-size_t const_lds_bytes(uint32_t N) { return (size_t)((20u + N + 1u) & ~1u) * 8u; }
-
-// choose the MH launch shape: one wave per block; the record pool is as large as fits
-// six blocks per CU, but never smaller than one lane's worst case
-int plan_mh(epv_ctx *c) {
-  const uint32_t B = c->S.B, C = c->S.C, N = c->S.N;
-  const uint64_t worst = (uint64_t)B * (2u * C + 2u);
-  // per wave: node table N*64 u32 (rounded to 16 B) + pool of 16-byte records
-  const size_t fixed = const_lds_bytes(N) + (((size_t)N * 64u * 4u + 15u) & ~(size_t)15u);
-  if (fixed > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the 160 KiB LDS node table");
-  // typical demand of 64 lanes: B * (2 kbar + 2) records each, with a 30 % margin
-  const uint64_t typical = (uint64_t)(64.0 * B * (2.0 * c->kbar + 2.0) * 1.3) + 32u;
-  const uint64_t max_fit = fixed + 16u < 160u * 1024u ? (160u * 1024u - fixed) / 16u : 0u;
-  const uint64_t want = std::max<uint64_t>(worst, typical);
-  c->mh_threads = 64;
-  // LDS pool while it leaves >= 8 waves per CU (2 per SIMD); otherwise a global-memory slab
-  // per block (the working set of the resident waves stays in L2 / Infinity Cache)
-  const bool lds_ok = want <= max_fit && (fixed + std::min(want, max_fit) * 16u) * 8u <= 160u * 1024u;
-  const bool use_lds = c->knobs.force_global_pool ? false : c->knobs.force_lds_pool ? want <= max_fit : lds_ok;
-  if (use_lds) {
-    const uint64_t pool = std::min(want, max_fit);
-    c->mh_gpool = false;
-    c->pool_entries = (uint32_t)pool;
-    c->mh_lds = fixed + (size_t)pool * 16u;
-    return EPV_OK;
-  }
-  // global slab: `worst` ROWS of 64 interleaved records per wave (a lane can always run)
-  const uint64_t pool = worst;
-  const uint64_t blocks = (c->S.phase_cap + 63u) / 64u;
-  c->gpool_need = blocks * pool * 128u;     // (allocated by ensure_slab when a launch takes this kernel)
-  c->mh_gpool = true;
-  c->pool_entries = (uint32_t)pool;
-  c->mh_lds = fixed;
-  return EPV_OK;
-}
-
-// the two ping-pong buffers of the canonical tree reduction, sized in DOUBLES for the launch
-// that uses them: level 0 holds one row per block, level 1 one row per 256 blocks
-// launch shape of epv_mh_propose2_kernel: per wave the constants, the matrix table, the node
-// table and a pool of doubles shared by the Felsenstein records (2 doubles) and the heavy-segment
-// records (EPV_HREC doubles).  The pool covers the typical demand of 64 lanes with a margin (a wave that
-// needs more runs in rounds) and always one lane's worst case.
-// the fused phase's kernel for a tree of nn nodes: the small-tree body for 2 <= nn <= EPV_P2_SMALL_MAX,
-// else (and for nn = 0) the generic one; direct: the bodies whose jump stage is run_direct (EPV_OPT_DIRECT_FUSED)
-using fused_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                                uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused);
-fused_kernel_t fused_kernel(uint32_t nn, bool direct = false) {
-  if (direct)
-    switch (nn) {
-      case 2: return epv_mh_propose2_kernel<true, true, 2, true>;
-      case 3: return epv_mh_propose2_kernel<true, true, 3, true>;
-      case 4: return epv_mh_propose2_kernel<true, true, 4, true>;
-      case 5: return epv_mh_propose2_kernel<true, true, 5, true>;
-      default: return epv_mh_propose2_kernel<true, true, 0, true>;
-    }
-  switch (nn) {
-    case 2: return epv_mh_propose2_kernel<true, true, 2>;
-    case 3: return epv_mh_propose2_kernel<true, true, 3>;
-    case 4: return epv_mh_propose2_kernel<true, true, 4>;
-    case 5: return epv_mh_propose2_kernel<true, true, 5>;
-    default: return epv_mh_propose2_kernel<true, true>;
-  }
-}
-bool seg_jumps_on(const epv_ctx *c) { return c->knobs.seg_jumps < 0 ? c->kbar >= 0.25 : c->knobs.seg_jumps != 0; }
-// LDS pool of the second kernel relative to the typical demand: 1.25 -> 1.15 with the 8-double records
-// gave one more wave per CU, ~4 % of the waves take a second round
-constexpr double P2_MARGIN = 1.15;
-// the fused phase pays while a phase has at most this many waves: measured on tree.nwk, +46 % at 520
-// waves, +20 % at 1700, +5 % at 2600, -4..-14 % at 5200 (tools/fused_scan.sh)
-constexpr uint64_t FUSED_MAX_WAVES = 3072u;
-int plan_p2(epv_ctx *c) {
-  const uint32_t B = c->S.B, C = c->S.C, N = c->S.N;
-  const size_t shared = const_lds_bytes(N) + (size_t)B * 4u * 6u * 8u;     // constants, matrix table: once per block
-  const size_t per_wave_fixed = ((((size_t)N * 64u + 1u) / 2u + 1u) & ~(size_t)1u) * 8u +
-                                ((3u * 64u + 2u) * (size_t)B * sizeof(epv_meta_t) + 15u) / 16u * 16u;   // node table, meta cache (+ 2 edge columns)
-  const size_t fixed = shared + per_wave_fixed;
-  // one lane's worst case: every branch with 2C+1 segments (records K+1, heavy K)
-  const uint64_t worst_rec = (uint64_t)B * (2u * C + 2u), worst_heavy = (uint64_t)B * (2u * C + 1u);
-  // the fused phase: few waves (a launch that leaves SIMDs idle pays one wave chain instead of
-  // three to five), at most 64 segments per branch (the hand-over's bit word), lists for the worst
-  // case of every wave within 4 GB
-  // sites per wave: halve while every SIMD could still get two waves
-  uint32_t f_lanes = c->knobs.fused_lanes ? c->knobs.fused_lanes : 64u;
-  if (!c->knobs.fused_lanes)
-    while (f_lanes > 16u && (c->S.phase_cap + f_lanes / 2u - 1u) / (f_lanes / 2u) <= 2048u) f_lanes /= 2u;
-  const uint64_t phase_waves = (c->S.phase_cap + 63u) / 64u;
-  const uint64_t f_seg_cap = 64ull * B * (2u * C + 1u), f_bt_cap = 64ull * B;
-  const uint64_t f_bytes = (c->S.phase_cap + f_lanes - 1u) / f_lanes * (f_seg_cap * (sizeof(EpvSegTask) + sizeof(EpvSegOut)) + f_bt_cap * 12u);
-  // (The options are not consulted: they may change after the paths are planned.  Under EPV_OPT_DIRECT_SAMPLER
-  // without EPV_OPT_DIRECT_FUSED phase_plan never launches the fused phase, yet the pool below is sized as if it
-  // did -- c->fused stays true next to the separate V2 kernels, and a tree near the LDS limit may go to the global
-  // pool or to V1 for a fused body that does not run.  Results do not depend on it; the cost is not measured.
-  // With EPV_OPT_DIRECT_FUSED the fused direct bodies run in these very buffers.)
-  bool fused = !c->knobs.propose_v1 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
-               (c->knobs.fused_phase < 0 ? phase_waves <= FUSED_MAX_WAVES : c->knobs.fused_phase != 0);
-  // heavy-segment records: 8 doubles, 10 when the segment-parallel jump kernels read them back
-  const uint64_t hrec = (fused || seg_jumps_on(c)) ? EPV_HREC : EPV_HREC_SHORT;
-  const uint64_t worst_dbl = 2u * worst_rec + hrec * worst_heavy;
-  // typical: K = 1 + Poisson(2 kbar) segments per branch; heavy segments E[K; K >= 2]
-  const double lam = 2.0 * c->kbar;
-  const double heavy_per_branch = (1.0 + lam) - std::exp(-lam);
-  uint32_t n_internal = 0;
-  for (uint32_t node = 1; node < N; ++node) n_internal += c->subtree[node] != 1u;
-  const double rec_per_lane = B * (1.0 + lam) + n_internal;     // K per branch, +1 for an internal node's q
-  const uint64_t typical_dbl = (uint64_t)(64.0 * (2.0 * rec_per_lane + (double)hrec * B * heavy_per_branch) * P2_MARGIN) + 64u;
-  const uint64_t max_fit = fixed + 64u < 160u * 1024u ? (160u * 1024u - fixed) / 8u : 0u;
-  uint64_t want = std::max(worst_dbl, typical_dbl);
-  // the fused phase reuses the pool for the search's cooperative area and then for the accept
-  // stage's task table, results, accumulators (992 doubles) and meta words (3 B columns of 64)
-  if (fused) want = std::max<uint64_t>(want, std::max<uint64_t>(EPV_COOP_BYTES / 8u, 992u + 48u * (uint64_t)B));
-  const bool lds_ok = want <= max_fit && (fixed + want * 8u) * 5u <= 160u * 1024u;   // >= 5 waves per CU
-  const bool use_lds = c->knobs.force_global_pool ? false : c->knobs.force_lds_pool ? want <= max_fit : lds_ok;
-  if (fixed > 150u * 1024u) return fail(c, EPV_ERR_ARG, "tree too large for the 160 KiB LDS node table");
-  c->fused = fused && use_lds;
-  c->fused_lanes = f_lanes;
-  c->p2_gpool = !use_lds;
-  c->p2_pool = use_lds ? (uint32_t)((want + 1u) & ~(uint64_t)1u) : 0u;
-  c->p2_lds = shared + per_wave_fixed + (size_t)c->p2_pool * 8u;
-  return EPV_OK;
-}
-
-// launch shape of epv_mh_propose3_kernel, for trees whose record pool does not fit LDS: per wave a
-// 16-bit word per (node, lane) and a stack of partial products in LDS, q rows of the internal nodes
-// and the heavy-segment records in a slab of global memory
-int plan_p3(epv_ctx *c) {
-  c->p3 = false;
-  const uint32_t B = c->S.B, C = c->S.C, N = c->S.N;
-  if (c->knobs.propose_v3 == 0 || c->knobs.propose_v1 || N > 128u || N < 2u) return EPV_OK;     // (node masks of one or two 64-bit words)
-  if (c->knobs.propose_v3 < 0 && !c->p2_gpool) return EPV_OK;     // the LDS pool is the better place while it fits
-  // per node: parent, children, depth; q rows for the internal nodes below the root
-  std::vector<uint32_t> depth(N, 0u), c1(N, 0u), c2(N, 0u), kids(N, 0u), qrow(N, 0u);
-  uint32_t qrows = 0, max_depth = 0;
-  for (uint32_t node = 1; node < N; ++node) {
-    const uint32_t par = c->parent[node];
-    if (par >= node) return EPV_OK;                      // (pre-order is what epv_set_tree checks; be safe)
-    depth[node] = depth[par] + 1u;
-    max_depth = std::max(max_depth, depth[node]);
-    if (kids[par] == 0u) c1[par] = node; else if (kids[par] == 1u) c2[par] = node;
-    ++kids[par];
-  }
-  for (uint32_t node = 1; node < N; ++node) {
-    if (kids[node] > 2u) return EPV_OK;                  // two child fields per node word
-    if (c->subtree[node] != 1u) qrow[node] = qrows++;
-  }
-  if (qrows > 63u) return EPV_OK;                        // (six bits in the node word; at N <= 128 only unary nodes reach it)
-  // tables: node words [N] | internal nodes deepest first [n_up] | their level starts [D + 2] |
-  //         all nodes but the root by depth [N - 1] | their level starts [D + 2]
-  std::vector<uint32_t> tab;
-  for (uint32_t node = 0; node < N; ++node)
-    tab.push_back(c->parent[node] | (c1[node] << 7) | (c2[node] << 14) | (qrow[node] << 21) |
-                  ((c->subtree[node] == 1u ? 1u : 0u) << 27));
-  std::vector<uint32_t> up, upstart(max_depth + 2u, 0u), dn, dnstart(max_depth + 2u, 0u);
-  for (uint32_t d = max_depth + 1u; d-- > 0u;) {        // upstart[d + 1] .. upstart[d] = internal nodes of depth d
-    if (d <= max_depth && d >= 1u)
-      for (uint32_t node = 1; node < N; ++node)
-        if (depth[node] == d && c->subtree[node] != 1u) up.push_back(node);
-    upstart[d] = (uint32_t)up.size();
-  }
-  upstart[max_depth + 1u] = 0u;
-  for (uint32_t d = 0; d <= max_depth; ++d) {           // dnstart[d] .. dnstart[d + 1] = nodes of depth d
-    dnstart[d] = (uint32_t)dn.size();
-    if (d >= 1u)
-      for (uint32_t node = 1; node < N; ++node)
-        if (depth[node] == d) dn.push_back(node);
-  }
-  dnstart[max_depth + 1u] = (uint32_t)dn.size();
-  const uint32_t n_up = (uint32_t)up.size();
-  tab.insert(tab.end(), up.begin(), up.end());
-  tab.insert(tab.end(), upstart.begin(), upstart.end());
-  tab.insert(tab.end(), dn.begin(), dn.end());
-  tab.insert(tab.end(), dnstart.begin(), dnstart.end());
-  for (uint32_t g = 0; g < max_depth; ++g) {            // pair groups: leaves, then internal nodes by depth
-    uint64_t m = 0, m2 = 0;      // nodes 0..63, 64..127
-    for (uint32_t node = 1; node < N; ++node) {
-      const bool leaf = c->subtree[node] == 1u;
-      if (g == 0u ? leaf : (!leaf && depth[node] == g)) (node < 64u ? m : m2) |= 1ull << (node & 63u);
-    }
-    tab.push_back((uint32_t)m);
-    tab.push_back((uint32_t)(m >> 32));
-    tab.push_back((uint32_t)m2);
-    tab.push_back((uint32_t)(m2 >> 32));
-  }
-  for (uint32_t node = 0; node < N; ++node) tab.push_back(depth[node]);
-  const double lam = 2.0 * c->kbar;
-  const double heavy_per_branch = (1.0 + lam) - std::exp(-lam);
-  const uint64_t worst_heavy = (uint64_t)B * (2u * C + 1u);
-  // EPV_P3_MIN_LIST=1 (tests): one lane's worst case only, so that busy waves run in several rounds
-  const uint64_t list_cap = c->knobs.p3_min_list ? worst_heavy : std::max<uint64_t>(worst_heavy, (uint64_t)(64.0 * B * heavy_per_branch * 1.5) + 64u);
-  if (list_cap >= (1ull << 20)) return EPV_OK;             // the pair word's record field
-  // a pool of slabs per XCD, claimed by resident blocks (EPV_P3_SLAB_POOL=0: one per block of the launch):
-  // 4 blocks of this kernel fit a CU (LDS) and an XCD of the MI355X has 32 CUs: 128 resident blocks at most,
-  // 160 slabs per XCD.  Used when the launch has more blocks than the pool has slabs (EPV_P3_SLAB_POOL=2: always)
-  const int pool_env = c->knobs.p3_slab_pool;
-  const uint64_t launch_waves = ((c->S.phase_cap + 255u) / 256u) * 4u;
-  const uint32_t slots = (pool_env == 2 || (pool_env && launch_waves > 8u * 160u * 4u)) ? 160u : 0u;
-  const uint64_t waves = slots ? 8ull * slots * 4u : launch_waves;
-  const uint64_t need = waves * ((uint64_t)qrows * 128u + list_cap * EPV_HREC_SHORT);
-  if (need * sizeof(double) > (24ull << 30)) return EPV_OK;
-  if (tab.size() > 2048u) return EPV_OK;
-  const size_t shared = const_lds_bytes(N) + (size_t)B * 4u * EPV_SEGTAB_DBL * 8u + (tab.size() + 1u) / 2u * 8u;
-  const size_t per_wave = ((size_t)EPV_P3_PCAP * 3u + EPV_P3_PCAP / 8u + (max_depth * 64u * 2u + 7u) / 8u + (max_depth + 3u) / 2u) * 8u;   // pair list, pair results, group offsets
-  const size_t lds = shared + 4u * per_wave;
-  if (lds > 120u * 1024u) return EPV_OK;      // (a very deep tree's group offsets: keep the first kernels)
-  // (every refusal above leaves the context as it was: from here on the plan is taken)
+// the launch shapes of every proposal kernel, for the current tree, paths and capacity: decided by plan_shapes
+// (epv_plan.h) and kept in the context; the node table of a taken V3 plan goes to the device
+int plan_kernels(epv_ctx *c) {
+  PhaseShapes shapes = plan_shapes({c->S.N, c->parent.data(), c->subtree.data(), c->S.C, c->S.n, c->kbar}, c->knobs);
+  if (shapes.error) return fail(c, EPV_ERR_ARG, shapes.error);
+  c->shapes = std::move(shapes);
+  PlanV3 &v3 = c->shapes.v3;
+  if (!v3.taken) return EPV_OK;
+  v3.taken = false;       // (until its table is on the device: a HIP error below leaves the first kernels planned)
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->d_nodetab) HIP_TRY(c, hipMalloc(&c->d_nodetab, 2048u * sizeof(uint32_t)));
   if (!c->d_slabflags) {
     HIP_TRY(c, hipMalloc(&c->d_slabflags, 8u * 256u * sizeof(uint32_t)));
     HIP_TRY(c, hipMemset(c->d_slabflags, 0, 8u * 256u * sizeof(uint32_t)));
   }
-  HIP_TRY(c, hipMemcpy(c->d_nodetab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  c->p3_slots = slots;
-  c->gpool3_need = need;
-  c->p3_lds = lds;
-  c->p3_list_cap = (uint32_t)list_cap;
-  c->p3_qrows = qrows;
-  c->p3_nup = n_up;
-  c->p3_depth = max_depth;
-  c->p3 = true;
+  HIP_TRY(c, hipMemcpy(c->d_nodetab, v3.nodetab.data(), v3.nodetab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  v3.taken = true;
   return EPV_OK;
 }
-
-// the launch shapes of every proposal kernel, for the current tree, paths and capacity
-int plan_kernels(epv_ctx *c) {
-  int rc = plan_mh(c);
-  if (!rc) rc = plan_p2(c);
-  return rc ? rc : plan_p3(c);
+PhasePlan phase_plan(const epv_ctx *c) {
+  return ::phase_plan(c->shapes, c->knobs, c->S.flags, c->unobs_cells, c->evidence_cells, c->S.B, c->kbar);
 }
 
 // per-wave lists of the fused phase, on first use
 int ensure_fused_buffers(epv_ctx *c) {
-  const uint64_t waves = (c->S.phase_cap + c->fused_lanes - 1u) / c->fused_lanes + 4u;
-  const uint64_t seg_cap = 64ull * c->S.B * (2u * c->S.C + 1u), bt_cap = 64ull * c->S.B;
+  const uint64_t waves = (c->S.phase_cap + c->shapes.v2.fused_lanes - 1u) / c->shapes.v2.fused_lanes + 4u;
+  const uint64_t seg_cap = epv_fused_seg_cap(c->S.B, c->S.C), bt_cap = epv_fused_bt_cap(c->S.B);
   if (c->F.segs && c->fused_waves >= waves && c->F.seg_cap == seg_cap && c->F.bt_cap == bt_cap) return EPV_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1919,100 +1638,205 @@ int ensure_slab(epv_ctx *c, double **slab, uint64_t *cap, uint64_t need) {
   return EPV_OK;
 }
 
-// the kernel variants of a colour phase (EPV_PLAN_* fields of include/epievo_mi355x.h): launch_phase
-// launches what this says, epv_phase_plan and epv_phase_mode report it
-struct PhasePlan {
-  uint32_t propose;      // EPV_PLAN_V1 / V2 / V3 / FUSED
-  bool gpool;            // V1: the record pool in global memory
-  bool refq;             // the proposal ratio is evaluated (V1 takes the reference template)
-  uint32_t small_nn;     // fused: the small-tree body's node count, 0 = generic body
-  uint32_t p3_words;     // V3: words per node mask
-  bool p3_slab_pool;     // V3: slabs from the per-XCD pool
-  uint32_t jumps;        // EPV_PLAN_JUMPS_*
-  uint32_t accept;       // EPV_PLAN_ACCEPT_*
-  bool listed;           // the accept stage reads the listed sites
-  bool meta_cache;       // (accept and fused kernels) the LDS meta cache
-  bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
-  bool evidence;         // a leaf cell carries evidence: V1 takes the template that reads the table
-  uint32_t lanes_log2;   // fused: log2 of the sites per wave (2 .. 6)
-  bool direct;           // the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER)
-  uint32_t word() const {
-    return propose | (gpool ? 1u : 0u) << 2 | (refq && propose == EPV_PLAN_V1 ? 1u : 0u) << 3 | small_nn << 4 |
-           p3_words << 8 | (p3_slab_pool ? 1u : 0u) << 10 | jumps << 12 | accept << 14 | (listed ? 1u : 0u) << 16 |
-           (unobs ? 1u : 0u) << 17 | (evidence ? 1u : 0u) << 18 | lanes_log2 << 20 | (direct ? 1u : 0u) << 23;
+// ---- the launch of a colour phase: phase_plan (epv_plan.h) decides, launch_phase and its stages launch.
+// Every template instantiation of a proposal kernel is named once, in the four tables below: the launches and the
+// dynamic-LDS limits that epv_create raises (proposal_kernel_lds) both go through them.
+using p2_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                             uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused);
+// the fused phase's kernel for a tree of nn nodes: the small-tree body for 2 <= nn <= EPV_P2_SMALL_MAX,
+// else (and for nn = 0) the generic one; direct: the bodies whose jump stage is run_direct (EPV_OPT_DIRECT_FUSED)
+template <bool DIRECT>
+p2_kernel_t fused_body(uint32_t nn) {
+  switch (nn) {
+    case 2: return epv_mh_propose2_kernel<true, true, 2, DIRECT>;
+    case 3: return epv_mh_propose2_kernel<true, true, 3, DIRECT>;
+    case 4: return epv_mh_propose2_kernel<true, true, 4, DIRECT>;
+    case 5: return epv_mh_propose2_kernel<true, true, 5, DIRECT>;
+    default: return epv_mh_propose2_kernel<true, true, 0, DIRECT>;
   }
+}
+p2_kernel_t fused_kernel(uint32_t nn, bool direct) { return direct ? fused_body<true>(nn) : fused_body<false>(nn); }
+// the second proposal kernel (seg: it lists the dirty segments for the segment-parallel jump kernels), and the third
+p2_kernel_t p2_kernel(bool seg) { return seg ? epv_mh_propose2_kernel<true, false> : epv_mh_propose2_kernel<false, false>; }
+auto p3_kernel(uint32_t words) { return words == 2u ? epv_mh_propose3_kernel<2> : epv_mh_propose3_kernel<1>; }
+// the first, by its trailing arguments: none (EPV_LEAF_DATA), the mask (_MASK), the evidence table and the mask (_EVIDENCE)
+using leaf_arg_t = const uint32_t *;
+template <class... Leaf>
+auto v1_kernel(bool gpool, bool refq) {
+  constexpr int LEAF = (int)sizeof...(Leaf);
+  return gpool ? (refq ? epv_mh_propose_kernel<true, true, LEAF, Leaf...> : epv_mh_propose_kernel<true, false, LEAF, Leaf...>)
+               : (refq ? epv_mh_propose_kernel<false, true, LEAF, Leaf...> : epv_mh_propose_kernel<false, false, LEAF, Leaf...>);
+}
+// the proposal kernels ask for more dynamic LDS than the 64 KiB default (epv_create)
+void proposal_kernel_lds() {
+  auto raise = [](int kib, auto... kernels) {
+    ((void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, kib * 1024), ...);
+  };
+  raise(128, p3_kernel(1u), p3_kernel(2u));   // (it has static LDS too)
+  raise(160, p2_kernel(false), p2_kernel(true));
+  for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn) raise(160, fused_kernel(nn, false), fused_kernel(nn, true));
+  for (int v = 0; v < 4; ++v)
+    raise(160, v1_kernel<>(v & 1, v & 2), v1_kernel<leaf_arg_t>(v & 1, v & 2), v1_kernel<leaf_arg_t, leaf_arg_t>(v & 1, v & 2));
+}
+
+// what the stages of one colour phase share
+struct PhaseArgs {
+  uint32_t colour, seed_lo, seed_hi, sweep;
+  uint64_t first, last, own_lo, own_hi;   // local sites the phase may update; those statistics and the accept counter cover
+  uint64_t s0;                            // first local site of this colour (the kernels derive the same value)
+  uint64_t threads, blocks;               // sites of this colour: a lane each; blocks of the first proposal kernel
 };
-PhasePlan phase_plan(const epv_ctx *c) {
-  PhasePlan P{};
-  // (root resampling changes the proposal's normalising constant with the path: the ratio must be evaluated)
-  P.refq = c->S.flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
-  // unobserved leaf cells: only the first kernel marginalises them
-  P.unobs = c->unobs_cells != 0u;
-  // leaf evidence: the same rule
-  P.evidence = c->evidence_cells != 0u;
-  // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
-  // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
-  // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us)
-  const bool p3 = c->p3 && !P.refq && !P.unobs && !P.evidence;
-  const bool p2 = !p3 && !c->knobs.propose_v1 && !P.refq && !P.unobs && !P.evidence && !c->p2_gpool;
-  P.meta_cache = c->S.B <= 8u && !c->knobs.accept_no_cache;
-  // the direct sampler: the separate jump-time kernels, and the fused phase's direct
-  // bodies only where EPV_OPT_DIRECT_FUSED asks for them
-  P.direct = c->S.flags & EPV_FLAG_DIRECT_SAMPLER;
-  if (p2 && c->fused && (!P.direct || (c->S.flags & EPV_FLAG_DIRECT_FUSED))) {
-    P.propose = EPV_PLAN_FUSED;
-    P.small_nn = c->knobs.small_tree && c->S.N >= 2u && c->S.N <= EPV_P2_SMALL_MAX ? c->S.N : 0u;
-    P.jumps = EPV_PLAN_JUMPS_FUSED;
-    P.accept = EPV_PLAN_ACCEPT_FUSED;
-    for (uint32_t l = c->fused_lanes; l > 1u; l >>= 1) ++P.lanes_log2;
-    return P;
-  }
-  if (p3) {
-    P.propose = EPV_PLAN_V3;
-    P.p3_words = c->S.N > 64u ? 2u : 1u;
-    P.p3_slab_pool = c->p3_slots != 0u;
-  } else if (p2) {
-    P.propose = EPV_PLAN_V2;
+
+// the whole phase in one kernel, one wave per fused_lanes sites (see epv_propose2.h)
+int launch_fused(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a) {
+  const PlanV2 &v = c->shapes.v2;
+  const int frc = ensure_fused_buffers(c);
+  if (frc) return frc;
+  const unsigned pb = (unsigned)((a.threads + v.fused_lanes - 1u) / v.fused_lanes);
+  if (pb > c->fused_waves) return fail(c, EPV_ERR_STATE, "fused phase: launch larger than its lists");
+  EpvFused F = c->F;
+  F.meta_cache = P.meta_cache ? 1u : 0u;
+  F.lanes = v.fused_lanes;
+  F.grouped_rounds = 4u;     // rounds of the grouped search of a short segment list
+  F.topo = 0u;               // small-tree body: bit node = a leaf, bits 8 + 3 node .. = the parent
+  for (uint32_t node = 1; node < P.small_nn; ++node)
+    F.topo |= (c->subtree[node] == 1u ? 1u << node : 0u) | (c->parent[node] << (8u + 3u * node));
+  F.giveups = c->d_counters + EPV_CNT_WORDS;
+  hipLaunchKernelGGL(fused_kernel(P.small_nn, P.direct), dim3(pb), dim3(64), v.lds, c->stream, c->S, a.colour, a.seed_lo,
+                     a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, 0u, c->d_counters, (double *)nullptr,
+                     c->d_segtab, F);
+  return EPV_OK;
+}
+
+template <class... Leaf>
+void launch_v1(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, Leaf... leaf) {
+  const PlanV1 &v = c->shapes.v1;
+  hipLaunchKernelGGL(v1_kernel<Leaf...>(P.gpool, P.refq), dim3((unsigned)a.blocks), dim3(v.threads), v.lds, c->stream, c->S,
+                     a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, v.pool_entries, c->d_counters,
+                     P.gpool ? c->d_gpool : (double *)nullptr, leaf...);
+}
+// the proposal stage.  list_mode: 0, or 1 + the phase parity that V2 and V3 file their listed sites under
+int launch_propose(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, uint32_t list_mode) {
+  if (P.propose == EPV_PLAN_V3) {
+    // large tree: a 16-bit word per (node, lane) in LDS, q rows and heavy records in a slab (epv_propose3.h)
+    const PlanV3 &v = c->shapes.v3;
+    const int rc = ensure_slab(c, &c->d_gpool3, &c->gpool3_cap, v.slab_need);
+    if (rc) return rc;
+    hipLaunchKernelGGL(p3_kernel(P.p3_words), dim3((unsigned)((a.threads + 255u) / 256u)), dim3(256), v.lds, c->stream, c->S,
+                       a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.list_cap, v.qrows,
+                       v.n_up, v.depth, list_mode - 1u, c->d_counters, c->d_gpool3, c->d_segtab, c->d_nodetab, c->d_slabflags,
+                       v.slots);
+    ++c->phase_parity;
+  } else if (P.propose == EPV_PLAN_V2) {
+    const PlanV2 &v = c->shapes.v2;
+    const bool seg = P.jumps == EPV_PLAN_JUMPS_SEGMENTS;
+    if (seg) { const int rc = ensure_seg_buffers(c); if (rc) return rc; }
+    hipLaunchKernelGGL(p2_kernel(seg), dim3((unsigned)((a.threads + 63u) / 64u)), dim3(64), v.lds, c->stream, c->S, a.colour,
+                       a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, list_mode - 1u,
+                       c->d_counters, (double *)nullptr, c->d_segtab, EpvFused{});
+    ++c->phase_parity;
   } else {
-    P.propose = EPV_PLAN_V1;
-    P.gpool = c->mh_gpool;
+    if (P.gpool) { const int rc = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->shapes.v1.slab_need); if (rc) return rc; }
+    // (under evidence the mask rides along where one is held: a cell without evidence follows it)
+    if (P.evidence) launch_v1(c, P, a, (leaf_arg_t)c->d_evidence, (leaf_arg_t)c->d_unobs);
+    else if (P.unobs) launch_v1(c, P, a, (leaf_arg_t)c->d_unobs);
+    else launch_v1(c, P, a);
   }
-  // segment-parallel jumps pay on long branches (single branch T = 1: +17 %, every segment is
-  // dirty and needs several trials) and cost on short ones (tree.nwk: -12 %, one dirty segment in
-  // fourteen branches does not repay the extra hand-over): profiles/r02_ab_seg_jumps.txt
-  // The one-segment tasks (the first bucket: ~95 % on short branches) otherwise go to their own lean
-  // kernel, epv_mh_jumps_all_kernel.  (Forward-rejection mode keeps the general kernel for
-  // everything: a flip there can need 1e5 trials, which only the wave-wide search takes in reasonable time.)
-  // (The direct sampler has no lean one-segment body either: the general kernel's direct variant.)
-  P.jumps = p2 && seg_jumps_on(c) ? EPV_PLAN_JUMPS_SEGMENTS
-          : !(c->S.flags & (EPV_FLAG_FORWARD_REJECTION | EPV_FLAG_DIRECT_SAMPLER)) ? EPV_PLAN_JUMPS_ALL : EPV_PLAN_JUMPS_GENERAL;
-  // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
-  const int acc_v3 = c->knobs.accept_v3;
-  P.accept = (acc_v3 >= 0 ? acc_v3 != 0 : !P.meta_cache) ? EPV_PLAN_ACCEPT_V3
-           : P.meta_cache ? EPV_PLAN_ACCEPT_CACHE : EPV_PLAN_ACCEPT_NO_CACHE;
-  P.listed = p2 || p3;
-  return P;
+  return EPV_OK;
+}
+
+// the jump stage: the jump times of every dirty (site, branch) pair of the proposals
+void launch_jumps(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a) {
+  const size_t lds = const_lds_bytes(c->S.N);
+  unsigned long long *giveups = c->d_counters + EPV_CNT_WORDS;   // (the direct sampler's)
+  // the sequential kernel -- under EPV_OPT_DIRECT_SAMPLER its direct variant -- on gx blocks per shard
+  auto general = [&](uint64_t gx, uint32_t tpw) {
+    if (P.direct)
+      hipLaunchKernelGGL(epv_mh_jumps_direct_kernel, dim3((unsigned)gx, EPV_SHARDS), dim3(256), lds, c->stream, c->S, a.seed_lo,
+                         a.seed_hi, a.sweep, tpw, a.s0, c->d_counters, giveups);
+    else
+      hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3((unsigned)gx, EPV_SHARDS), dim3(256), lds, c->stream, c->S, a.seed_lo,
+                         a.seed_hi, a.sweep, tpw, a.s0, 0.0, 0.0, c->d_counters, 0u);
+  };
+  if (P.jumps == EPV_PLAN_JUMPS_SEGMENTS) {
+    // dirty segments one lane each, then their branches one lane each; both lists are sized on
+    // the device, the grids cover a quarter / an eighth of the capacity and stride over the rest
+    const dim3 sg((unsigned)std::min<uint64_t>(32u, std::max<uint64_t>(1u, (c->S.seg_cap / 4u + 255u) / 256u)), EPV_SHARDS);
+    const dim3 bg((unsigned)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (c->S.btask_cap / 8u + 255u) / 256u)), EPV_SHARDS);
+    if (P.direct)
+      hipLaunchKernelGGL(epv_seg_search_direct_kernel, sg, dim3(256), lds, c->stream, c->S, a.seed_lo, a.seed_hi, a.sweep,
+                         c->d_counters, giveups);
+    else
+      hipLaunchKernelGGL(epv_seg_search_kernel, sg, dim3(256), lds, c->stream, c->S, a.seed_lo, a.seed_hi, a.sweep,
+                         c->d_counters);
+    hipLaunchKernelGGL(P.direct ? epv_seg_assemble_direct_kernel : epv_seg_assemble_kernel, bg, dim3(256), lds, c->stream, c->S,
+                       a.seed_lo, a.seed_hi, a.sweep, a.s0, c->d_counters);
+    // the sequential kernel behind them with a minimal grid: branches of more than 64 segments
+    // and whatever did not fit the lists (normally nothing: it reads empty lists and leaves)
+    return general(1u, 32u);
+  }
+  // one lane per dirty (site, branch) pair; the count is only known on the device, so
+  // launch a grid that covers the typical case and grid-stride over the rest
+  const uint64_t max_tasks = a.blocks / EPV_SHARDS * 64u * c->S.B + 64u * c->S.B;  // per shard
+  // lanes of a wave that own a task (the others only help in the cooperative search): full
+  // waves when there is work for every SIMD, fewer tasks per wave -- a shorter critical path --
+  // on a small genome (measured: DESIGN.md section 4.1)
+  const double est = (double)a.threads * c->S.B * std::min(1.0, 0.1 + c->kbar) / 2048.0;
+  const uint32_t tpw = est >= 64.0 ? 64u : est >= 32.0 ? 32u : est >= 16.0 ? 16u : 8u;
+  // the one-segment tasks in their own lean kernel (phase_plan), the general one then takes the rest
+  // with a grid sized for it; a block (4 waves) takes 4*tpw tasks per pass; size the grid for ~1/4 of the worst case
+  if (P.jumps != EPV_PLAN_JUMPS_ALL) return general(std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u), tpw);
+  const uint64_t j1b = std::min<uint64_t>((max_tasks / 4u + 255u) / 256u + 1u, 256u);
+  const uint64_t jgb = std::min<uint64_t>((max_tasks / 16u + 4u * tpw - 1u) / (4u * tpw) + 1u, 64u);
+  hipLaunchKernelGGL(epv_mh_jumps_all_kernel, dim3(EPV_SHARDS, (unsigned)(jgb + j1b)), dim3(256), lds, c->stream, c->S,
+                     a.seed_lo, a.seed_hi, a.sweep, tpw, a.s0, c->d_counters, (uint32_t)jgb);
+}
+
+// the accept stage, over the listed sites (list_mode != 0) or over every site of the colour
+void launch_accept(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, uint32_t list_mode) {
+  // the listed sites (proposal differs from the current path) per shard: typically ~30 % of the colour
+  const uint64_t per_shard = (a.threads + EPV_SHARDS - 1u) / EPV_SHARDS;
+  if (P.accept == EPV_PLAN_ACCEPT_V3) {
+    // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h);
+    // unlisted, every site of the colour in one row of blocks (reference proposal arithmetic on a large tree)
+    const uint64_t sites = list_mode ? per_shard : a.threads;
+    const unsigned ax3 = (unsigned)std::max<uint64_t>(1u, (sites + 4u * EPV_ACC3_SITES - 1u) / (4u * EPV_ACC3_SITES));
+    hipLaunchKernelGGL(epv_mh_accept3_kernel, dim3(ax3, list_mode ? EPV_SHARDS : 1u), dim3(256), const_lds_bytes(c->S.N),
+                       c->stream, c->S, a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi,
+                       c->d_counters, list_mode, list_mode ? (uint64_t)0 : a.threads);
+    return;
+  }
+  // meta cache of the accept kernel: 5 columns x B words per lane in LDS while that stays small
+  // (B <= 8: 20 KB per block next to the 24 KB of accumulators)
+  const uint32_t meta_cache = P.meta_cache ? 1u : 0u;
+  const size_t acc_lds = const_lds_bytes(c->S.N) + (meta_cache ? (size_t)5u * c->S.B * 256u * sizeof(epv_meta_t) : 0u);
+  // listed: the grid covers half of the worst case and strides over the rest
+  // (on a large tree nearly every site is listed -- one clean proposal in thirty branches is rare --
+  // and a block that strides twice runs two of the kernel's long dependent chains back to back)
+  const uint64_t covered = c->S.B > 8u ? per_shard : per_shard / 2u;
+  const dim3 grid = list_mode ? dim3((unsigned)std::max<uint64_t>(1u, (covered + 255u) / 256u), EPV_SHARDS)
+                              : dim3((unsigned)((a.threads + 255u) / 256u));
+  hipLaunchKernelGGL(epv_mh_accept_kernel, grid, dim3(256), acc_lds, c->stream, c->S, a.colour, a.seed_lo, a.seed_hi, a.sweep,
+                     a.first, a.last, a.own_lo, a.own_hi, c->d_counters, list_mode, meta_cache);
 }
 
 int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
-  uint64_t first = 0, last = 0, own_lo = 0, own_hi = 0;
-  int prc = phase_range(c, &first, &last);
+  PhaseArgs a{(uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep};
+  int prc = phase_range(c, &a.first, &a.last);
   if (prc) return prc;
-  owned_range(c, &own_lo, &own_hi);
-  const uint64_t span = last - first + 1u;
-  const uint64_t threads = (span + 2u) / 3u;
-  // first local site of this colour (the kernels derive the same value)
-  const uint64_t s0 = first + (((uint32_t)colour + 3u - (uint32_t)((c->S.g0 + first) % 3u)) % 3u);
-  const uint64_t blocks = (threads + c->mh_threads - 1u) / c->mh_threads;
-  if (blocks == 0) return EPV_OK;
+  owned_range(c, &a.own_lo, &a.own_hi);
+  const uint64_t span = a.last - a.first + 1u;
+  a.threads = (span + 2u) / 3u;
+  a.s0 = a.first + ((a.colour + 3u - (uint32_t)((c->S.g0 + a.first) % 3u)) % 3u);
+  a.blocks = (a.threads + c->shapes.v1.threads - 1u) / c->shapes.v1.threads;
+  if (a.blocks == 0) return EPV_OK;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   c->timing = c->timing_every && (c->timing_seen++ % c->timing_every) == 0u;
   if (c->timing) {
     if (c->ev_used == c->ev_pool.size()) {
-      hipEvent_t a, b;
-      HIP_TRY(c, hipEventCreate(&a));
-      HIP_TRY(c, hipEventCreate(&b));
-      c->ev_pool.emplace_back(a, b);
+      HIP_TRY(c, hipEventCreate(&e0));
+      HIP_TRY(c, hipEventCreate(&e1));
+      c->ev_pool.emplace_back(e0, e1);
     }
     e0 = c->ev_pool[c->ev_used].first;
     e1 = c->ev_pool[c->ev_used].second;
@@ -2020,161 +1844,12 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     HIP_TRY(c, hipEventRecord(e0, c->stream));
   }
   const PhasePlan P = phase_plan(c);
-  const uint32_t meta_cache = P.meta_cache ? 1u : 0u;
-  uint32_t list_mode = 0;
-  if (P.propose == EPV_PLAN_FUSED) {
-    // the whole phase in one kernel, one wave per 64 sites (see epv_propose2.h)
-    const int frc = ensure_fused_buffers(c);
-    if (frc) return frc;
-    const unsigned pb = (unsigned)((threads + c->fused_lanes - 1u) / c->fused_lanes);
-    if (pb > c->fused_waves) return fail(c, EPV_ERR_STATE, "fused phase: launch larger than its lists");
-    EpvFused F = c->F;
-    F.meta_cache = meta_cache;
-    F.lanes = c->fused_lanes;
-    F.grouped_rounds = 4u;     // rounds of the grouped search of a short segment list
-    F.topo = 0u;               // small-tree body: bit node = a leaf, bits 8 + 3 node .. = the parent
-    for (uint32_t node = 1; node < P.small_nn; ++node)
-      F.topo |= (c->subtree[node] == 1u ? 1u << node : 0u) | (c->parent[node] << (8u + 3u * node));
-    F.giveups = c->d_counters + EPV_CNT_WORDS;
-    const auto kf = fused_kernel(P.small_nn, P.direct);
-    hipLaunchKernelGGL(kf, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S,
-                       (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi,
-                       c->p2_pool, 0u, 0u, c->d_counters, (double *)nullptr, c->d_segtab, F);
-    if (c->timing) HIP_TRY(c, hipEventRecord(e1, c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (c->halo_mode) ++c->phases_used;
-    return EPV_OK;
-  }
-  const bool seg_mode = P.jumps == EPV_PLAN_JUMPS_SEGMENTS;
-  if (seg_mode) { const int src = ensure_seg_buffers(c); if (src) return src; }
-  if (P.propose == EPV_PLAN_V3) {
-    // large tree: a 16-bit word per (node, lane) in LDS, q rows and heavy records in a slab (epv_propose3.h)
-    list_mode = 1u + (c->phase_parity & 1u);
-    const unsigned pb = (unsigned)((threads + 255u) / 256u);
-    { const int rc3 = ensure_slab(c, &c->d_gpool3, &c->gpool3_cap, c->gpool3_need); if (rc3) return rc3; }
-    auto k3 = P.p3_words == 2u ? epv_mh_propose3_kernel<2> : epv_mh_propose3_kernel<1>;
-    hipLaunchKernelGGL(k3, dim3(pb), dim3(256), c->p3_lds, c->stream, c->S, (uint32_t)colour,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p3_list_cap,
-                       c->p3_qrows, c->p3_nup, c->p3_depth, c->phase_parity & 1u, c->d_counters, c->d_gpool3, c->d_segtab,
-                       c->d_nodetab, c->d_slabflags, c->p3_slots);
-    ++c->phase_parity;
-  } else if (P.propose == EPV_PLAN_V2) {
-    list_mode = 1u + (c->phase_parity & 1u);
-    const unsigned pb = (unsigned)((threads + 63u) / 64u);
-    auto kern = seg_mode ? epv_mh_propose2_kernel<true, false> : epv_mh_propose2_kernel<false, false>;
-    hipLaunchKernelGGL(kern, dim3(pb), dim3(64), c->p2_lds, c->stream, c->S, (uint32_t)colour, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->p2_pool, 0u,
-                       c->phase_parity & 1u, c->d_counters, (double *)nullptr, c->d_segtab, EpvFused{});
-    ++c->phase_parity;
-  } else {
-    if (P.gpool) { const int rc1 = ensure_slab(c, &c->d_gpool, &c->gpool_cap, c->gpool_need); if (rc1) return rc1; }
-    using M = const uint32_t *;
-    if (P.evidence) {
-      // (the mask rides along where one is held: a cell without evidence follows it)
-      constexpr int E = EPV_LEAF_EVIDENCE;
-      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, E, M, M> : epv_mh_propose_kernel<true, false, E, M, M>)
-                          : (P.refq ? epv_mh_propose_kernel<false, true, E, M, M> : epv_mh_propose_kernel<false, false, E, M, M>);
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
-                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
-                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr, (M)c->d_evidence,
-                         (M)c->d_unobs);
-    } else if (P.unobs) {
-      constexpr int U = EPV_LEAF_MASK;
-      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, U, M> : epv_mh_propose_kernel<true, false, U, M>)
-                          : (P.refq ? epv_mh_propose_kernel<false, true, U, M> : epv_mh_propose_kernel<false, false, U, M>);
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
-                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
-                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr, (M)c->d_unobs);
-    } else {
-      constexpr int D = EPV_LEAF_DATA;
-      auto kern = P.gpool ? (P.refq ? epv_mh_propose_kernel<true, true, D> : epv_mh_propose_kernel<true, false, D>)
-                          : (P.refq ? epv_mh_propose_kernel<false, true, D> : epv_mh_propose_kernel<false, false, D>);
-      hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(c->mh_threads), c->mh_lds, c->stream, c->S,
-                         (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last,
-                         c->pool_entries, c->d_counters, P.gpool ? c->d_gpool : (double *)nullptr);
-    }
-  }
-  if (seg_mode) {
-    // dirty segments one lane each, then their branches one lane each; both lists are sized on
-    // the device, the grids cover a quarter / an eighth of the capacity and stride over the rest
-    const unsigned sx = (unsigned)std::min<uint64_t>(32u, std::max<uint64_t>(1u, (c->S.seg_cap / 4u + 255u) / 256u));
-    const unsigned bx = (unsigned)std::min<uint64_t>(16u, std::max<uint64_t>(1u, (c->S.btask_cap / 8u + 255u) / 256u));
-    if (P.direct) {
-      unsigned long long *giveups = c->d_counters + EPV_CNT_WORDS;
-      hipLaunchKernelGGL(epv_seg_search_direct_kernel, dim3(sx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                         c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, c->d_counters, giveups);
-      hipLaunchKernelGGL(epv_seg_assemble_direct_kernel, dim3(bx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                         c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, s0, c->d_counters);
-      hipLaunchKernelGGL(epv_mh_jumps_direct_kernel, dim3(1, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream, c->S,
-                         (uint32_t)seed, (uint32_t)(seed >> 32), sweep, 32u, s0, c->d_counters, giveups);
-    } else {
-    hipLaunchKernelGGL(epv_seg_search_kernel, dim3(sx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                       c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, c->d_counters);
-    hipLaunchKernelGGL(epv_seg_assemble_kernel, dim3(bx, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                       c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, s0, c->d_counters);
-    // the sequential kernel behind them with a minimal grid: branches of more than 64 segments
-    // and whatever did not fit the lists (normally nothing: it reads empty lists and leaves)
-    hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3(1, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream, c->S,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), sweep, 32u, s0, 0.0, 0.0, c->d_counters);
-    }
-  } else {
-    // one lane per dirty (site, branch) pair; the count is only known on the device, so
-    // launch a grid that covers the typical case and grid-stride over the rest
-    const uint64_t max_tasks = blocks / EPV_SHARDS * 64u * c->S.B + 64u * c->S.B;  // per shard
-    // lanes of a wave that own a task (the others only help in the cooperative search): full
-    // waves when there is work for every SIMD, fewer tasks per wave -- a shorter critical path --
-    // on a small genome (measured: DESIGN.md section 4.1)
-    const double est = (double)threads * c->S.B * std::min(1.0, 0.1 + c->kbar) / 2048.0;
-    const uint32_t tpw = est >= 64.0 ? 64u : est >= 32.0 ? 32u : est >= 16.0 ? 16u : 8u;
-    // the one-segment tasks in their own lean kernel (phase_plan), the general one then takes the rest
-    // with a grid sized for it; a block (4 waves) takes 4*tpw tasks per pass; size the grid for ~1/4 of the worst case
-    if (P.jumps == EPV_PLAN_JUMPS_ALL) {
-      const uint64_t j1b = std::min<uint64_t>((max_tasks / 4u + 255u) / 256u + 1u, 256u);
-      const uint64_t jgb = std::min<uint64_t>((max_tasks / 16u + 4u * tpw - 1u) / (4u * tpw) + 1u, 64u);
-      hipLaunchKernelGGL(epv_mh_jumps_all_kernel, dim3(EPV_SHARDS, (unsigned)(jgb + j1b)), dim3(256), const_lds_bytes(c->S.N),
-                         c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, c->d_counters, (uint32_t)jgb);
-    } else if (P.direct) {
-      const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);
-      hipLaunchKernelGGL(epv_mh_jumps_direct_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
-                         c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, c->d_counters,
-                         c->d_counters + EPV_CNT_WORDS);
-    } else {
-      const uint64_t jb = std::min<uint64_t>((max_tasks / 4u + 4u * tpw - 1u) / (4u * tpw) + 1u, 256u);
-      hipLaunchKernelGGL(epv_mh_jumps_kernel, dim3((unsigned)jb, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N),
-                         c->stream, c->S, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, tpw, s0, 0.0, 0.0, c->d_counters, 0u);
-    }
-  }
-  // meta cache of the accept kernel: 5 columns x B words per lane in LDS while that stays small
-  // (B <= 8: 20 KB per block next to the 24 KB of accumulators)
-  const size_t acc_lds = const_lds_bytes(c->S.N) + (meta_cache ? (size_t)5u * c->S.B * 256u * sizeof(epv_meta_t) : 0u);
-  if (list_mode) {
-    // the listed sites (proposal differs from the current path) per shard: typically ~30 % of the
-    // colour; the grid covers half of the worst case and strides over the rest
-    // (on a large tree nearly every site is listed -- one clean proposal in thirty branches is rare --
-    // and a block that strides twice runs two of the kernel's long dependent chains back to back)
-    const uint64_t per_shard = (threads + EPV_SHARDS - 1u) / EPV_SHARDS;
-    const bool full = c->S.B > 8u;
-    const unsigned ax = (unsigned)std::max<uint64_t>(1u, ((full ? per_shard : per_shard / 2u) + 255u) / 256u);
-    // large trees (no room for the meta cache): a lane per (site, triple), branches in groups (epv_accept3.h)
-    if (P.accept == EPV_PLAN_ACCEPT_V3) {
-      const unsigned ax3 = (unsigned)std::max<uint64_t>(1u, (per_shard + 4u * EPV_ACC3_SITES - 1u) / (4u * EPV_ACC3_SITES));
-      hipLaunchKernelGGL(epv_mh_accept3_kernel, dim3(ax3, EPV_SHARDS), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                         c->S, (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo,
-                         own_hi, c->d_counters, list_mode, (uint64_t)0);
-    } else
-    hipLaunchKernelGGL(epv_mh_accept_kernel, dim3(ax, EPV_SHARDS), dim3(256), acc_lds, c->stream,
-                       c->S, (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo,
-                       own_hi, c->d_counters, list_mode, meta_cache);
-  } else if (P.accept == EPV_PLAN_ACCEPT_V3) {
-    // every site of the colour (reference proposal arithmetic on a large tree), a lane per (site, triple)
-    const unsigned ax3 = (unsigned)std::max<uint64_t>(1u, (threads + 4u * EPV_ACC3_SITES - 1u) / (4u * EPV_ACC3_SITES));
-    hipLaunchKernelGGL(epv_mh_accept3_kernel, dim3(ax3, 1), dim3(256), const_lds_bytes(c->S.N), c->stream,
-                       c->S, (uint32_t)colour, (uint32_t)seed, (uint32_t)(seed >> 32), sweep, first, last, own_lo,
-                       own_hi, c->d_counters, 0u, (uint64_t)threads);
-  } else {
-    hipLaunchKernelGGL(epv_mh_accept_kernel, dim3((unsigned)((threads + 255u) / 256u)), dim3(256),
-                       acc_lds, c->stream, c->S, (uint32_t)colour, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), sweep, first, last, own_lo, own_hi, c->d_counters, 0u, meta_cache);
+  const uint32_t list_mode = P.listed ? 1u + (c->phase_parity & 1u) : 0u;   // (never with the fused phase)
+  const int rc = P.propose == EPV_PLAN_FUSED ? launch_fused(c, P, a) : launch_propose(c, P, a, list_mode);
+  if (rc) return rc;
+  if (P.propose != EPV_PLAN_FUSED) {
+    launch_jumps(c, P, a);
+    launch_accept(c, P, a, list_mode);
   }
   if (c->timing) HIP_TRY(c, hipEventRecord(e1, c->stream));
   HIP_TRY(c, hipGetLastError());
@@ -2285,7 +1960,7 @@ EPV_API epv_ctx *epv_create(int device_id) {
   if (hipSetDevice(device_id) != hipSuccess) return nullptr;
   epv_ctx *c = new epv_ctx();
   c->device = device_id;
-  c->knobs = read_knobs();
+  c->knobs = read_knobs(std::getenv);
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&c->d_model, sizeof(EpvModelConst)) != hipSuccess ||
       // (one word behind the sharded counters: the direct sampler's give-ups, epv_direct_giveups)
@@ -2297,33 +1972,7 @@ EPV_API epv_ctx *epv_create(int device_id) {
     delete c;
     return nullptr;
   }
-  // the MH kernel asks for more dynamic LDS than the 64 KiB default
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose3_kernel<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);   // (it has static LDS too)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose3_kernel<2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(epv_mh_propose2_kernel<true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn)
-    for (int direct = 0; direct < 2; ++direct)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused_kernel(nn, direct != 0)),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const void *v1[] = {
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_DATA>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_DATA>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_DATA>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_DATA>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_MASK, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_MASK, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_MASK, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_MASK, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, false, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, false, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<false, true, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>),
-      reinterpret_cast<const void *>(epv_mh_propose_kernel<true, true, EPV_LEAF_EVIDENCE, const uint32_t *, const uint32_t *>)};
-  for (const void *k : v1) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  proposal_kernel_lds();
   return c;
 }
 
@@ -2435,13 +2084,13 @@ static int alloc_paths(epv_ctx *c, uint64_t n_sites, uint32_t capacity, uint64_t
   HIP_TRY(c, hipMalloc(&c->S.jumps, 2u * E * capacity * sizeof(double)));
   HIP_TRY(c, hipMalloc(&c->S.sel, n_sites));
   HIP_TRY(c, hipMalloc(&c->S.tri, n_sites * sizeof(double)));
-  c->S.phase_cap = (n_sites + 2u) / 3u + 1u;
+  c->S.phase_cap = epv_phase_cap(n_sites);
   HIP_TRY(c, hipMalloc(&c->S.prop_llr, c->S.phase_cap * sizeof(double)));
   HIP_TRY(c, hipMalloc(&c->S.prop_flag, c->S.phase_cap));
   c->S.W = (2u * capacity + 1u + 63u) / 64u;
   HIP_TRY(c, hipMalloc(&c->S.prop_states, B * c->S.phase_cap * c->S.W * sizeof(uint64_t)));
   // one task region per counter shard, sized for the worst case of the blocks that use it
-  c->S.task_cap = ((((n_sites + 2u) / 3u + 63u) / 64u + EPV_SHARDS - 1u) / EPV_SHARDS + 1u) * 64u * B;
+  c->S.task_cap = epv_task_cap(n_sites, B);
   HIP_TRY(c, hipMalloc(&c->S.tasks, c->S.task_cap * EPV_SHARDS * 2u * sizeof(unsigned long long)));
   // segment-parallel jump sampling: branch list as large as the task regions, segment list for
   // the expected number of dirty segments with a wide margin (what does not fit falls back to the
@@ -2449,7 +2098,7 @@ static int alloc_paths(epv_ctx *c, uint64_t n_sites, uint32_t capacity, uint64_t
   //   (allocated by ensure_seg_buffers when that path is first used)
   c->S.btask_cap = c->S.seg_cap = 0;
   // accept list: one region per counter shard, room for every site of the blocks that use it
-  c->S.alist_cap = ((((n_sites + 2u) / 3u + 63u) / 64u + EPV_SHARDS - 1u) / EPV_SHARDS + 1u) * 64u;
+  c->S.alist_cap = epv_task_cap(n_sites, 1u);
   HIP_TRY(c, hipMalloc(&c->S.alist, c->S.alist_cap * EPV_SHARDS * sizeof(uint32_t)));
   HIP_TRY(c, hipMemsetAsync(c->S.meta, 0, 2u * E * sizeof(epv_meta_t), c->stream));
   c->first = 1;

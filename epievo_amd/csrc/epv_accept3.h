@@ -76,7 +76,6 @@ __device__ __forceinline__ double triple_llh_grouped(const EpvDev &S, const doub
   return llh;
 }
 
-#define EPV_ACC3_SITES 21u   /* sites per wave: three lanes each, lane 63 idles */
 #ifndef EPV_ACC3_MINBLOCKS
 #define EPV_ACC3_MINBLOCKS 4
 #endif

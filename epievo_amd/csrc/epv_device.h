@@ -125,4 +125,15 @@ enum { EPV_CNT_ACCEPT = 0, EPV_CNT_OVERFLOW = 1, EPV_CNT_COOP = 2, EPV_CNT_TASKS
 #define EPV_CNT_WORDS (EPV_CNT_N * EPV_SHARDS * EPV_SHARD_STRIDE)
 #define EPV_CNT_IDX(kind, shard) (((kind) * EPV_SHARDS + (shard)) * EPV_SHARD_STRIDE)
 
+// sizes that the kernels and the host's plan of their launches (epv_plan.h) share
+// epv_propose2.h: the segment record EpvSegRec, as a heavy-segment record and as an entry of the matrix table
+#define EPV_SEGTAB_DBL 6u   /* table entry = the first six fields */
+#define EPV_HREC 10u        /* doubles per heavy-segment record: the eight fields, length, address word */
+#define EPV_HREC_SHORT 8u   /* ... when nothing reads length and address word after the dense evaluation
+                               (sequential jump kernel): they are parked in the slots of the two uniforms */
+#define EPV_P2_SMALL_MAX 5  /* most nodes of the fused phase's small-tree body */
+#define EPV_COOP_BYTES (64u * (6u * 8u + 7u * 4u))   /* epv_jumps2.h: a wave's cooperative-search area, EpvCoop */
+#define EPV_P3_PCAP 256u    /* epv_propose3.h: heavy (lane, node) pairs a wave lists per round (at least 64: one lane's worst case) */
+#define EPV_ACC3_SITES 21u  /* epv_accept3.h: sites per wave, three lanes each, lane 63 idles */
+
 #endif

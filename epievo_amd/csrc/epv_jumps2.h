@@ -42,7 +42,6 @@ struct EpvCoop {
   double *len, *r0, *r1, *trunc, *tj;     // [64] each, tj [128]
   uint32_t *misc, *gsite, *tbase, *nk, *res, *tw, *mm;   // [64] each
 };
-#define EPV_COOP_BYTES (64u * (6u * 8u + 7u * 4u))
 
 // the wave's share of a segment list: entries base_first + lane, + stride, ... below n_seg
 template <bool ASM_MUL = true>

@@ -38,10 +38,6 @@ struct EpvSegRec {      // one segment, everything the recursions need
   double len;           // segment length (kept for the jump tasks)
   uint64_t info;        // trip0 | owner lane << 3 | node << 9 | k << 21
 };
-#define EPV_SEGTAB_DBL 6u   /* table entry = the first six fields */
-#define EPV_HREC 10u        /* doubles per heavy-segment record: the eight fields, length, address word */
-#define EPV_HREC_SHORT 8u   /* ... when nothing reads length and address word after the dense evaluation
-                               (sequential jump kernel): they are parked in the slots of the two uniforms */
 
 // (host too, for epv_math_kat's host pass: the four matrix entries; the bounds are a device float exp)
 EPV_DEV void epv_seg_matrices(double len, double r0, double r1, double out[6]) {
@@ -173,7 +169,6 @@ struct EpvFused {
 // DIRECT (fused phase only, EPV_OPT_DIRECT_FUSED): the jump stage samples every segment of the wave's list by
 // run_direct (epv_direct.h) instead of searching trials -- one counted loop over the list, then the assembly of
 // every branch; the searches and their cooperative LDS area are not compiled, so every loop of the kernel is counted.
-#define EPV_P2_SMALL_MAX 5
 template <bool SEG, bool FUSED, int NN = 0, bool DIRECT = false>
 __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,

@@ -35,7 +35,6 @@
 // Preconditions (plan_p3, epv_abi.hip): N <= 128 (node masks of one or two 64-bit words: the kernel is a
 // template on the word count), every node but the root has at most two children.
 
-#define EPV_P3_PCAP 256u   /* heavy (lane, node) pairs a wave lists per round (at least 64: one lane's worst case) */
 
 // s_tree[node]: parent | first child << 7 | second child << 14 | q row << 21 | leaf << 27; s_dep[node]: depth
 #define EPV_P3_PARENT(w) ((w) & 127u)

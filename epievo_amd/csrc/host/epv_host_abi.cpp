@@ -18,6 +18,8 @@
 #include "epv_epochs.hpp"
 #include "epv_indep.hpp"
 #include "epv_forward.hpp"
+#include "epievo_mi355x.h"
+#include "../epv_plan.h"
 
 namespace {
 thread_local std::string g_err;
@@ -709,3 +711,39 @@ EPVH_API void epvh_epoch_stats_copy(void *h, char *names, int names_len, double 
   std::copy(es->factor.begin(), es->factor.end(), factor);
 }
 EPVH_API void epvh_epoch_stats_free(void *h) { delete (epv::EpochStats *)h; }
+
+// ---- the plan of a colour phase without a GPU: epv_plan.h, which the device library decides with.  The tree as
+// epv_set_tree takes it (checked by the same pre-order rules), the local sites, the jump capacity and the mean jumps
+// per (site, branch) as a context holds them, the option word as epv_set_options accepts it, the counts of
+// unobserved and evidence leaf cells, and the knobs as n_knobs strings NAME=VALUE in place of the environment.
+// *word: what epv_phase_plan reports for such a context
+EPVH_API int epvh_phase_plan(int n_nodes, const uint32_t *parent_ids, const uint32_t *subtree_sizes, uint64_t n_sites,
+                             uint32_t capacity, double kbar, uint32_t options, uint64_t unobs_cells,
+                             uint64_t evidence_cells, const char *const *knobs, int n_knobs, uint32_t *word) {
+  if (n_nodes < 2 || n_nodes > 4095 || !parent_ids || !subtree_sizes || !word || n_knobs < 0 || (n_knobs && !knobs)) {
+    g_err = "bad tree";
+    return 1;
+  }
+  for (int i = 1; i < n_nodes; ++i)
+    if (parent_ids[i] >= (uint32_t)i || subtree_sizes[i] < 1 || i + subtree_sizes[i] > (uint32_t)n_nodes) {
+      g_err = "tree arrays are not a valid pre-order tree";
+      return 1;
+    }
+  if (n_sites < 3 || capacity < 1 || capacity > EPV_MAX_CAP || !(kbar >= 0.0)) {
+    g_err = "bad paths: at least 3 sites, a capacity of 1 .. 2047, a mean jump count >= 0";
+    return 1;
+  }
+  const EpvKnobs k = read_knobs([&](const char *name) -> const char * {
+    const size_t len = std::strlen(name);
+    for (int i = 0; i < n_knobs; ++i)
+      if (knobs[i] && !std::strncmp(knobs[i], name, len) && knobs[i][len] == '=') return knobs[i] + len + 1;
+    return nullptr;
+  });
+  const PhaseShapes shapes = plan_shapes({(uint32_t)n_nodes, parent_ids, subtree_sizes, capacity, n_sites, kbar}, k);
+  if (shapes.error) {
+    g_err = shapes.error;
+    return 1;
+  }
+  *word = phase_plan(shapes, k, options, unobs_cells, evidence_cells, (uint32_t)n_nodes - 1u, kbar).word();
+  return 0;
+}

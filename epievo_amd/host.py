@@ -136,6 +136,8 @@ def lib():
         L.epvh_epoch_stats_copy.restype = None
         L.epvh_epoch_stats_free.argtypes = [C.c_void_p]
         L.epvh_epoch_stats_free.restype = None
+        L.epvh_phase_plan.argtypes = [C.c_int, u32p, u32p, C.c_uint64, u32, C.c_double, u32, C.c_uint64, C.c_uint64,
+                                      C.POINTER(C.c_char_p), C.c_int, C.POINTER(u32)]
         _lib = L
     return _lib
 
@@ -237,6 +239,35 @@ class FlatPaths:
         new_off[1:] = np.cumsum(cnt.reshape(-1))
         return FlatPaths(hi - lo, self.n_nodes, init.reshape(-1).copy(), new_off,
                          np.concatenate(pieces) if pieces else np.zeros(0))
+
+
+PLAN_PROPOSE = ("V1", "V2", "V3", "fused")
+PLAN_JUMPS = ("fused", "segments", "jumps_all", "jumps")
+PLAN_ACCEPT = ("fused", "accept3", "accept_cache", "accept_no_cache")
+
+
+def plan_fields(w):
+    """a plan word (EPV_PLAN_* of include/epievo_mi355x.h) as a dict of its fields"""
+    return dict(word=w, propose=PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
+                small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
+                jumps=PLAN_JUMPS[w >> 12 & 3], accept=PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
+                unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1), direct=bool(w >> 23 & 1),
+                fused_lanes=(1 << (w >> 20 & 7)) if (w & 3) == 3 else 0)
+
+
+def phase_plan(tree, n_sites, capacity, kbar, options=0, unobs_cells=0, evidence_cells=0, knobs={}):
+    """the kernel variants of a colour phase, decided without a GPU by the code the device library decides with
+    (csrc/epv_plan.h): what DeviceSampler.phase_plan() returns in a context with this tree, n_sites local sites of
+    jump capacity `capacity` and a mean of kbar jumps per (site, branch), the option word `options` (EPV_OPT_*),
+    so many unobserved and evidence leaf cells, and `knobs` (EPV_* names to values) as its environment"""
+    names = [("%s=%s" % kv).encode() for kv in knobs.items()]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    w = C.c_uint32(0)
+    if lib().epvh_phase_plan(tree.n_nodes, _p(tree.parent_ids, C.c_uint32), _p(tree.subtree_sizes, C.c_uint32),
+                             int(n_sites), int(capacity), float(kbar), int(options), int(unobs_cells),
+                             int(evidence_cells), arr, len(names), C.byref(w)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return plan_fields(int(w.value))
 
 
 def simulate(model, tree, n_sites, seed):

@@ -240,6 +240,12 @@ class DeviceSampler:
         self._ck(self.L.epv_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
                                         (4 if sample_root else 0) | (flags.value & 24)))
 
+    def options(self):
+        """the option word (EPV_OPT_* bits) as set_options and set_direct_sampler left it (epv_get_options)"""
+        flags = C.c_uint32(0)
+        self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
+        return int(flags.value)
+
     def set_direct_sampler(self, on=True, fused=False):
         """EPV_OPT_DIRECT_SAMPLER: jump times by the direct end-conditioned sampler, bounded work per segment (DESIGN
         7.22).  Its own call because set_options keeps its three keywords: it changes its bits of the word and leaves
@@ -282,20 +288,12 @@ class DeviceSampler:
         self._ck(self.L.epv_phase_mode(self.h, C.byref(v)))
         return int(v.value)
 
-    PLAN_PROPOSE = ("V1", "V2", "V3", "fused")
-    PLAN_JUMPS = ("fused", "segments", "jumps_all", "jumps")
-    PLAN_ACCEPT = ("fused", "accept3", "accept_cache", "accept_no_cache")
-
     def phase_plan(self):
-        """the kernel variants of a colour phase (epv_phase_plan, EPV_PLAN_* of include/epievo_mi355x.h)"""
+        """the kernel variants of a colour phase (epv_phase_plan, EPV_PLAN_* of include/epievo_mi355x.h); without a
+        GPU: host.phase_plan"""
         v = C.c_uint32(0)
         self._ck(self.L.epv_phase_plan(self.h, C.byref(v)))
-        w = int(v.value)
-        return dict(word=w, propose=self.PLAN_PROPOSE[w & 3], gpool=bool(w >> 2 & 1), refq=bool(w >> 3 & 1),
-                    small_nn=w >> 4 & 15, p3_words=w >> 8 & 3, p3_slab_pool=bool(w >> 10 & 1),
-                    jumps=self.PLAN_JUMPS[w >> 12 & 3], accept=self.PLAN_ACCEPT[w >> 14 & 3], listed=bool(w >> 16 & 1),
-                    unobs=bool(w >> 17 & 1), evidence=bool(w >> 18 & 1), direct=bool(w >> 23 & 1),
-                    fused_lanes=(1 << (w >> 20 & 7)) if (w & 3) == 3 else 0)
+        return host.plan_fields(int(v.value))
 
     def philox_kat(self, seed, counters):
         """the device's Philox blocks (epv_philox_kat): counters[i] = (site, sweep, branch, segment, trial,

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(_TESTS))
 sys.path.insert(0, _TESTS)
 
 from direct_gpu_child import _checked_run, _inputs, _replay, _sha      # noqa: E402
+from epievo_amd import host                                             # noqa: E402
 from epievo_amd.sampler import DeviceSampler                            # noqa: E402
 
 
@@ -77,6 +78,12 @@ def context(spec, model, tree, fp, cap):
     d.reset()
     plan = d.phase_plan()
     check_plan(plan, spec)
+    # the planner without a GPU, given what this context holds, decides the same word for word (bit 23 and the
+    # EPV_OPT_DIRECT_FUSED rule included)
+    kbar = fp.counts().sum() / (fp.n_sites * (tree.n_nodes - 1))
+    knobs = dict((k, v) for k, v in os.environ.items() if k.startswith("EPV_"))
+    assert host.phase_plan(tree, fp.n_sites, d.capacity(), kbar, d.options(), d.unobserved_cells(),
+                           d.leaf_evidence_cells(), knobs) == plan
     return d, plan
 
 

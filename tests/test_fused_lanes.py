@@ -1,7 +1,7 @@
 """The fused colour phase at 32 and 64 sites per wave (and once at 8), the launch tails of every colour-phase
 path, update ranges and the halo mode, each against the oracle's parallel rung B, bit for bit.
 
-A context chooses the sites per wave of its fused phase from its size (plan_p2 in epv_abi.hip: 16 up to a
+A context chooses the sites per wave of its fused phase from its size (plan_p2 in epv_plan.h: 16 up to a
 phase capacity of 32768 sites, 32 up to 65536, 64 above; phase capacity = (n + 2) // 3 + 1), so every other
 parity test of the suite, none above n = 40000, runs 16 sites per wave.  Here EPV_FUSED_LANES sets the width on
 genomes of a few hundred sites, whose per-colour site counts are chosen around one wave:
@@ -114,8 +114,8 @@ for _L in WIDTHS:
 # a width the library accepts and nothing else runs: 27 sites are 9, 8 and 8 of a colour
 TAILS.append(("tree-8", "tree", 5, [27], lanes_env(8), {}, fused(5, 8), 19))
 
-# the separate kernels, around one full block of their launches.  Block widths (launch_phase in epv_abi.hip): the
-# second proposal kernel 64 lanes; the first one mh_threads, which plan_mh sets to 64; both followed by
+# the separate kernels, around one full block of their launches.  Block widths (launch_propose and
+# launch_accept in epv_abi.hip): the second proposal kernel 64 lanes; the first one PlanV1's threads, 64; both followed by
 # epv_mh_accept_kernel in blocks of 256.  The large-tree kernel 256 lanes, followed by epv_mh_accept3_kernel in
 # blocks of 256 lanes = 84 sites (three lanes a site, 21 sites a wave)
 _V2 = dict(propose="V2", gpool=False, accept="accept_cache", listed=True, small_nn=0, p3_words=0, fused_lanes=0)

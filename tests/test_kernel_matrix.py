@@ -6,6 +6,9 @@ row runs in a fresh process with its knobs in the environment (a context reads t
 created): the plan is asserted after reset(), then run_mcmc is compared with the oracle's parallel
 rung B in the same mode -- J, D, the accept count, the paths and the cached triple likelihoods bit
 for bit.  Rows with the default options also run two sweeps at a capacity that overflows.
+Without a GPU, test_plan_without_a_gpu asserts every row's expected fields on host.phase_plan -- the device
+library's planner (csrc/epv_plan.h) through libepv_host.so; the GPU child asserts that the context's own plan
+equals it word for word.
 
 Coverage (variant x options -> rows):
   fused small-tree body NN = 2 / 3 / 4 / 5    forward rejection: fr-pair, fr-cherry, fr-star3, fr-tree;
@@ -137,6 +140,9 @@ d = DeviceSampler(0); d.set_tree(tree); d.set_model(model); d.upload_paths(fp, c
 plan = d.phase_plan()
 bad = dict((k, (v, plan[k])) for k, v in expect.items() if plan[k] != v)
 assert not bad, "plan differs (expected, got): %%r; plan %%r" %% (bad, plan)
+# the planner without a GPU, given what this context holds, decides the same word for word
+kbar = fp.counts().sum() / (spec["n"] * (tree.n_nodes - 1))
+assert host.phase_plan(tree, spec["n"], d.capacity(), kbar, d.options(), knobs=spec["env"]) == plan
 
 def oracle(c, seed):
     o = orc.Oracle(tree, model, fp, "B", cap=c, seed=seed)
@@ -250,12 +256,48 @@ ROWS = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("tree,nodes,n,env,opts,expect", [r[1:] for r in ROWS], ids=[r[0] for r in ROWS])
 def test_kernel_variant_matches_rung_b(tree, nodes, n, env, opts, expect):
-    spec = json.dumps(dict(tree=tree, nodes=nodes, n=n, opts=opts, expect=expect))
+    spec = json.dumps(dict(tree=tree, nodes=nodes, n=n, env=env, opts=opts, expect=expect))
     code = _CODE % dict(root=_ROOT, tests=_TESTS, spec=spec)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True,
                        timeout=900)
     print(r.stdout[-2000:])         # the plan that ran, fused_lanes included
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-3000:]
+
+
+OPTION_BITS = dict(reference_proposal_ratio=1, forward_rejection=2, sample_root=4)     # EPV_OPT_*
+
+
+@pytest.mark.parametrize("tree,nodes,n,env,opts,expect", [r[1:] for r in ROWS], ids=[r[0] for r in ROWS])
+def test_plan_without_a_gpu(tree, nodes, n, env, opts, expect):
+    """no GPU: the planner of the device library (csrc/epv_plan.h, through libepv_host.so) routes every row's tree,
+    capacity, mean jump count, knobs and options to the kernels the row expects -- the inputs built as the GPU
+    child builds them"""
+    from common import ref_test_model
+    from epievo_amd import host
+    model, t = ref_test_model(), make_tree(tree)
+    assert t.n_nodes == nodes
+    fp = host.simulate(model, t, n, 6)
+    cap = int(max(16, 2 * fp.counts().max() + 8))
+    kbar = fp.counts().sum() / (n * (t.n_nodes - 1))
+    options = sum(bit for name, bit in OPTION_BITS.items() if opts.get(name))
+    plan = host.phase_plan(t, n, cap, kbar, options, knobs=env)
+    bad = dict((k, (v, plan[k])) for k, v in expect.items() if plan[k] != v)
+    assert not bad, "plan differs (expected, got): %r; plan %r" % (bad, plan)
+
+
+def test_plan_without_a_gpu_checks_what_it_is_given():
+    """no GPU: arrays that are no pre-order tree and sizes no context can hold are refused, and a tree too large for the
+    LDS node table gets the device library's error text"""
+    from epievo_amd import host
+    with pytest.raises(RuntimeError, match="pre-order"):
+        host.phase_plan(host.Tree([3, 1, 1], [0, 2, 0], [0.0, 0.1, 0.1]), 400, 16, 0.05)      # a parent behind its child
+    with pytest.raises(RuntimeError, match="pre-order"):
+        host.phase_plan(host.Tree([3, 3, 1], [0, 0, 1], [0.0, 0.1, 0.1]), 400, 16, 0.05)      # a subtree past the end
+    for n, cap in [(2, 16), (400, 0), (400, 2048)]:
+        with pytest.raises(RuntimeError, match="bad paths"):
+            host.phase_plan(make_tree("tree"), n, cap, 0.05)
+    with pytest.raises(RuntimeError, match="tree too large for the 160 KiB LDS node table"):
+        host.phase_plan(host.Tree.balanced(400, 0.02), 400, 16, 0.05)
 
 
 def test_rows_cover_the_matrix():
