@@ -1659,8 +1659,23 @@ p2_kernel_t fused_kernel(uint32_t nn, bool direct) { return direct ? fused_body<
 // the second proposal kernel (seg: it lists the dirty segments for the segment-parallel jump kernels), and the third
 p2_kernel_t p2_kernel(bool seg) { return seg ? epv_mh_propose2_kernel<true, false> : epv_mh_propose2_kernel<false, false>; }
 auto p3_kernel(uint32_t words) { return words == 2u ? epv_mh_propose3_kernel<2> : epv_mh_propose3_kernel<1>; }
-// the first, by its trailing arguments: none (EPV_LEAF_DATA), the mask (_MASK), the evidence table and the mask (_EVIDENCE)
+// their leaf variants (EPV_OPT_LEAF_FAST with a held cell): the same arguments, then the evidence table and the mask
 using leaf_arg_t = const uint32_t *;
+using p2_leaf_kernel_t = void (*)(EpvDev, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                                  uint32_t, uint32_t, uint32_t, unsigned long long *, double *, const double *, EpvFused,
+                                  leaf_arg_t, leaf_arg_t);
+p2_leaf_kernel_t fused_leaf_kernel(uint32_t nn) {
+  switch (nn) {
+    case 2: return epv_mh_propose2_kernel<true, true, 2, false, leaf_arg_t, leaf_arg_t>;
+    case 3: return epv_mh_propose2_kernel<true, true, 3, false, leaf_arg_t, leaf_arg_t>;
+    case 4: return epv_mh_propose2_kernel<true, true, 4, false, leaf_arg_t, leaf_arg_t>;
+    case 5: return epv_mh_propose2_kernel<true, true, 5, false, leaf_arg_t, leaf_arg_t>;
+    default: return epv_mh_propose2_kernel<true, true, 0, false, leaf_arg_t, leaf_arg_t>;
+  }
+}
+p2_leaf_kernel_t p2_leaf_kernel(bool seg) { return seg ? epv_mh_propose2_kernel<true, false, 0, false, leaf_arg_t, leaf_arg_t> : epv_mh_propose2_kernel<false, false, 0, false, leaf_arg_t, leaf_arg_t>; }
+auto p3_leaf_kernel(uint32_t words) { return words == 2u ? epv_mh_propose3_kernel<2, leaf_arg_t, leaf_arg_t> : epv_mh_propose3_kernel<1, leaf_arg_t, leaf_arg_t>; }
+// the first, by its trailing arguments: none (EPV_LEAF_DATA), the mask (_MASK), the evidence table and the mask (_EVIDENCE)
 template <class... Leaf>
 auto v1_kernel(bool gpool, bool refq) {
   constexpr int LEAF = (int)sizeof...(Leaf);
@@ -1672,9 +1687,9 @@ void proposal_kernel_lds() {
   auto raise = [](int kib, auto... kernels) {
     ((void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, kib * 1024), ...);
   };
-  raise(128, p3_kernel(1u), p3_kernel(2u));   // (it has static LDS too)
-  raise(160, p2_kernel(false), p2_kernel(true));
-  for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn) raise(160, fused_kernel(nn, false), fused_kernel(nn, true));
+  raise(128, p3_kernel(1u), p3_kernel(2u), p3_leaf_kernel(1u), p3_leaf_kernel(2u));   // (it has static LDS too)
+  raise(160, p2_kernel(false), p2_kernel(true), p2_leaf_kernel(false), p2_leaf_kernel(true));
+  for (uint32_t nn = 0; nn <= EPV_P2_SMALL_MAX; ++nn) raise(160, fused_kernel(nn, false), fused_kernel(nn, true), fused_leaf_kernel(nn));
   for (int v = 0; v < 4; ++v)
     raise(160, v1_kernel<>(v & 1, v & 2), v1_kernel<leaf_arg_t>(v & 1, v & 2), v1_kernel<leaf_arg_t, leaf_arg_t>(v & 1, v & 2));
 }
@@ -1702,6 +1717,11 @@ int launch_fused(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a) {
   for (uint32_t node = 1; node < P.small_nn; ++node)
     F.topo |= (c->subtree[node] == 1u ? 1u << node : 0u) | (c->parent[node] << (8u + 3u * node));
   F.giveups = c->d_counters + EPV_CNT_WORDS;
+  if (P.unobs || P.evidence)    // (EPV_OPT_LEAF_FAST: the plan never pairs a held cell with the direct bodies)
+    hipLaunchKernelGGL(fused_leaf_kernel(P.small_nn), dim3(pb), dim3(64), v.lds, c->stream, c->S, a.colour, a.seed_lo,
+                       a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, 0u, c->d_counters, (double *)nullptr,
+                       c->d_segtab, F, (leaf_arg_t)c->d_evidence, (leaf_arg_t)c->d_unobs);
+  else
   hipLaunchKernelGGL(fused_kernel(P.small_nn, P.direct), dim3(pb), dim3(64), v.lds, c->stream, c->S, a.colour, a.seed_lo,
                      a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, 0u, c->d_counters, (double *)nullptr,
                      c->d_segtab, F);
@@ -1722,6 +1742,12 @@ int launch_propose(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, uint32_t 
     const PlanV3 &v = c->shapes.v3;
     const int rc = ensure_slab(c, &c->d_gpool3, &c->gpool3_cap, v.slab_need);
     if (rc) return rc;
+    if (P.unobs || P.evidence)
+      hipLaunchKernelGGL(p3_leaf_kernel(P.p3_words), dim3((unsigned)((a.threads + 255u) / 256u)), dim3(256), v.lds, c->stream,
+                         c->S, a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.list_cap, v.qrows,
+                         v.n_up, v.depth, list_mode - 1u, c->d_counters, c->d_gpool3, c->d_segtab, c->d_nodetab, c->d_slabflags,
+                         v.slots, (leaf_arg_t)c->d_evidence, (leaf_arg_t)c->d_unobs);
+    else
     hipLaunchKernelGGL(p3_kernel(P.p3_words), dim3((unsigned)((a.threads + 255u) / 256u)), dim3(256), v.lds, c->stream, c->S,
                        a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.list_cap, v.qrows,
                        v.n_up, v.depth, list_mode - 1u, c->d_counters, c->d_gpool3, c->d_segtab, c->d_nodetab, c->d_slabflags,
@@ -1731,6 +1757,12 @@ int launch_propose(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, uint32_t 
     const PlanV2 &v = c->shapes.v2;
     const bool seg = P.jumps == EPV_PLAN_JUMPS_SEGMENTS;
     if (seg) { const int rc = ensure_seg_buffers(c); if (rc) return rc; }
+    if (P.unobs || P.evidence)
+      hipLaunchKernelGGL(p2_leaf_kernel(seg), dim3((unsigned)((a.threads + 63u) / 64u)), dim3(64), v.lds, c->stream, c->S,
+                         a.colour, a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, list_mode - 1u,
+                         c->d_counters, (double *)nullptr, c->d_segtab, EpvFused{}, (leaf_arg_t)c->d_evidence,
+                         (leaf_arg_t)c->d_unobs);
+    else
     hipLaunchKernelGGL(p2_kernel(seg), dim3((unsigned)((a.threads + 63u) / 64u)), dim3(64), v.lds, c->stream, c->S, a.colour,
                        a.seed_lo, a.seed_hi, a.sweep, a.first, a.last, a.own_lo, a.own_hi, v.pool, 0u, list_mode - 1u,
                        c->d_counters, (double *)nullptr, c->d_segtab, EpvFused{});
@@ -2245,14 +2277,14 @@ static int finish_mcmc(epv_ctx *c, uint64_t *n_accepted, uint64_t acc_base);
 EPV_API int epv_set_options(epv_ctx *c, uint32_t flags) {
   if (!c) return EPV_ERR_ARG;
   if (flags & ~(uint32_t)(EPV_OPT_REFERENCE_PROPOSAL_RATIO | EPV_OPT_FORWARD_REJECTION | EPV_OPT_SAMPLE_ROOT |
-                          EPV_OPT_DIRECT_SAMPLER | EPV_OPT_DIRECT_FUSED))
+                          EPV_OPT_DIRECT_SAMPLER | EPV_OPT_DIRECT_FUSED | EPV_OPT_LEAF_FAST))
     return fail(c, EPV_ERR_ARG, "unknown option bits");
   if ((flags & EPV_OPT_DIRECT_FUSED) && !(flags & EPV_OPT_DIRECT_SAMPLER))
     return fail(c, EPV_ERR_ARG, "EPV_OPT_DIRECT_FUSED selects the fused body of EPV_OPT_DIRECT_SAMPLER: set both");
   if ((flags & EPV_OPT_DIRECT_SAMPLER) && (flags & EPV_OPT_FORWARD_REJECTION))
     return fail(c, EPV_ERR_ARG, "EPV_OPT_DIRECT_SAMPLER and EPV_OPT_FORWARD_REJECTION name two samplers: set one");
-  static_assert(EPV_OPT_DIRECT_SAMPLER == EPV_FLAG_DIRECT_SAMPLER && EPV_OPT_DIRECT_FUSED == EPV_FLAG_DIRECT_FUSED,
-                "option bits");
+  static_assert(EPV_OPT_DIRECT_SAMPLER == EPV_FLAG_DIRECT_SAMPLER && EPV_OPT_DIRECT_FUSED == EPV_FLAG_DIRECT_FUSED &&
+                EPV_OPT_LEAF_FAST == EPV_FLAG_LEAF_FAST, "option bits");
   static_assert(EPV_OPT_REFERENCE_PROPOSAL_RATIO == EPV_FLAG_REFERENCE_PROPOSAL_RATIO &&
                 EPV_OPT_FORWARD_REJECTION == EPV_FLAG_FORWARD_REJECTION && EPV_OPT_SAMPLE_ROOT == EPV_FLAG_SAMPLE_ROOT,
                 "option bits");

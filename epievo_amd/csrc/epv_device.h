@@ -110,6 +110,7 @@ struct EpvIndepConst {
 #define EPV_FLAG_DIRECT_SAMPLER 8u            /* jump times by the direct end-conditioned sampler (epv_direct.h) */
 #define EPV_FLAG_DIRECT_FUSED 16u             /* ... in the fused phase too, where that is eligible (epv_propose2.h, DIRECT) */
 #define EPV_FLAG_SAMPLE_ROOT 4u               /* SingleSiteSampler::SAMPLE_ROOT: propose the root state too (reference arithmetic kernels) */
+#define EPV_FLAG_LEAF_FAST 32u               /* held leaf cells keep the second / third / fused proposal kernels: their leaf variants */
 
 // counters[] slots
 enum { EPV_CNT_ACCEPT = 0, EPV_CNT_OVERFLOW = 1, EPV_CNT_COOP = 2, EPV_CNT_TASKS = 3, EPV_CNT_TASKS2 = 4,

@@ -597,6 +597,28 @@ __device__ __forceinline__ float epv_leaf_evidence(const uint32_t *table, uint32
 #define EPV_LEAF_EVIDENCE 2   /* ... or (1 - r, r) where the table holds r; (table, mask or nullptr) */
 template <class A, class... Rest> __device__ __forceinline__ A epv_first_arg(A a, Rest...) { return a; }
 template <class A, class Z> __device__ __forceinline__ Z epv_second_arg(A, Z z) { return z; }
+// The one leaf mode of the second and third proposal kernels and of the fused bodies (EPV_OPT_LEAF_FAST): the
+// table, the mask, either may be null (a wave-uniform test).  What a cell holds, one word a cell: the bits of a
+// non-NaN r, or one of two NaN words of ours -- the mask flags the cell / neither does.  The loads depend on node
+// and site alone, so a caller issues them (epv_leaf_word) ahead of whatever else it waits for and turns the word
+// into the vector (epv_leaf_q) where the leaf's state is known; the precedence is the first kernel's.
+struct EpvLeafSrc { const uint32_t *table, *mask; };
+#define EPV_LEAF_WORD_DATA 0x7fc00000u
+#define EPV_LEAF_WORD_UNOBS 0x7fc00001u
+__device__ __forceinline__ uint32_t epv_leaf_word(const EpvLeafSrc &L, uint32_t node, uint64_t site) {
+  float r = __uint_as_float(EPV_LEAF_WORD_DATA);
+  bool unobs = false;
+  if (L.table) r = epv_leaf_evidence(L.table, node, site);
+  if (L.mask) unobs = epv_unobserved(L.mask, node, site);
+  return r == r ? __float_as_uint(r) : unobs ? EPV_LEAF_WORD_UNOBS : EPV_LEAF_WORD_DATA;
+}
+__device__ __forceinline__ void epv_leaf_q(uint32_t word, uint32_t leaf_state, double &q0, double &q1) {
+  const float r = __uint_as_float(word);
+  q0 = leaf_state ? 0.0 : 1.0;
+  q1 = leaf_state ? 1.0 : 0.0;
+  if (r == r) { q1 = (double)r; q0 = 1.0 - (double)r; }
+  else if (word == EPV_LEAF_WORD_UNOBS) { q0 = 1.0; q1 = 1.0; }
+}
 
 // GPOOL = false: the record pool lives in LDS (short trees: ~13 KB per wave, 12 waves/CU).
 // GPOOL = true : the pool is a per-block slab in global memory with the very same indexing.

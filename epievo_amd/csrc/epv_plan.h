@@ -328,6 +328,7 @@ struct PhasePlan {
   bool meta_cache;       // (accept and fused kernels) the LDS meta cache
   bool unobs;            // a leaf cell is unobserved: V1 takes the template that marginalises it
   bool evidence;         // a leaf cell carries evidence: V1 takes the template that reads the table
+                         // (beside V2, V3 or FUSED, under EPV_OPT_LEAF_FAST: the leaf variant of that kernel)
   uint32_t lanes_log2;   // fused: log2 of the sites per wave (2 .. 6)
   bool direct;           // the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER)
   uint32_t word() const {
@@ -342,20 +343,25 @@ inline PhasePlan phase_plan(const PhaseShapes &shapes, const EpvKnobs &knobs, ui
   const uint32_t N = B + 1u;
   // (root resampling changes the proposal's normalising constant with the path: the ratio must be evaluated)
   P.refq = flags & (EPV_FLAG_REFERENCE_PROPOSAL_RATIO | EPV_FLAG_SAMPLE_ROOT);
-  // unobserved leaf cells: only the first kernel marginalises them
+  // unobserved leaf cells: the first kernel marginalises them
   P.unobs = unobs_cells != 0u;
   // leaf evidence: the same rule
   P.evidence = evidence_cells != 0u;
+  // ... unless EPV_OPT_LEAF_FAST is set: the plan is then what the context would get with no
+  // cell held, and bits 17 / 18 select the leaf variant of whichever kernel that is
+  const bool held = (P.unobs || P.evidence) && !(flags & EPV_FLAG_LEAF_FAST);
   // the reference-arithmetic mode keeps the first kernel, and so do trees whose record pool does
   // not fit LDS: with the pool in global memory the second kernel's extra passes over it cost
   // more than its dense evaluation saves (16-leaf tree: 830 vs 676 us)
-  const bool p3 = shapes.v3.taken && !P.refq && !P.unobs && !P.evidence;
-  const bool p2 = !p3 && !knobs.propose_v1 && !P.refq && !P.unobs && !P.evidence && shapes.v2.planned;
+  const bool p3 = shapes.v3.taken && !P.refq && !held;
+  const bool p2 = !p3 && !knobs.propose_v1 && !P.refq && !held && shapes.v2.planned;
   P.meta_cache = B <= 8u && !knobs.accept_no_cache;
   // the direct sampler: the separate jump-time kernels, and the fused phase's direct
   // bodies only where EPV_OPT_DIRECT_FUSED asks for them
   P.direct = flags & EPV_FLAG_DIRECT_SAMPLER;
-  if (p2 && shapes.v2.fused && (!P.direct || (flags & EPV_FLAG_DIRECT_FUSED))) {
+  // (the fused direct bodies have no leaf variant: with a held cell the plan is plain direct mode's)
+  const bool direct_fused = (flags & EPV_FLAG_DIRECT_FUSED) && !(P.unobs || P.evidence);
+  if (p2 && shapes.v2.fused && (!P.direct || direct_fused)) {
     P.propose = EPV_PLAN_FUSED;
     P.small_nn = knobs.small_tree && N >= 2u && N <= EPV_P2_SMALL_MAX ? N : 0u;
     P.jumps = EPV_PLAN_JUMPS_FUSED;

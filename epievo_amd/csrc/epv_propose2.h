@@ -169,13 +169,27 @@ struct EpvFused {
 // DIRECT (fused phase only, EPV_OPT_DIRECT_FUSED): the jump stage samples every segment of the wave's list by
 // run_direct (epv_direct.h) instead of searching trials -- one counted loop over the list, then the assembly of
 // every branch; the searches and their cooperative LDS area are not compiled, so every loop of the kernel is counted.
-template <bool SEG, bool FUSED, int NN = 0, bool DIRECT = false>
+// LEAF (EPV_OPT_LEAF_FAST): a leaf's q is the leaf vector of LS (epv_leaf_word: evidence, else
+// the mask, else the indicator) wherever the body would set it from the current path's end state.  Pruning loads the
+// cell's word at the head of the leaf's iteration and files the vector as the branch's record K, like an internal
+// node's q (so a leaf branch takes K + 1 records here, which one lane's worst case covers: plan_p2), and the downward
+// pass reads it back through the generic p[k + 1].  Nothing else reads the current path's end state: `ident` and the
+// clean-branch test compare the PROPOSAL's states with the path's start states and jump counts, and the hand-over's
+// end_b is the proposal's sampled end state.  The table and the mask (device layouts of epv_leaf_evidence and
+// epv_unobserved, either may be null) are the two trailing arguments only these instantiations take, as with the
+// first kernel's: the others keep their argument layout and their instruction streams.
+template <bool SEG, bool FUSED, int NN = 0, bool DIRECT = false, class... Leaf>
 __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,
     uint64_t last, uint64_t own_first, uint64_t own_last, uint32_t pool_dbl, uint32_t list_cap,
-    uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab, EpvFused F) {
+    uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab, EpvFused F, Leaf... leaf_args) {
+  constexpr bool LEAF = sizeof...(Leaf) != 0;
+  static_assert(sizeof...(Leaf) == (LEAF ? 2u : 0u), "the table and the mask come together");
+  [[maybe_unused]] EpvLeafSrc LS{nullptr, nullptr};
+  if constexpr (LEAF) { LS.table = epv_first_arg(leaf_args...); LS.mask = epv_second_arg(leaf_args...); }
   static_assert(!FUSED || SEG, "the fused phase emits segments");
   static_assert(!DIRECT || FUSED, "the direct body is the fused phase's");
+  static_assert(!LEAF || !DIRECT, "the fused direct bodies have no leaf variant");
   constexpr bool SMALL = NN > 0;
   static_assert(!SMALL || (FUSED && NN >= 2 && NN <= EPV_P2_SMALL_MAX), "the small-tree body is the fused phase's");
   constexpr int NNA = SMALL ? NN : 1;      // register array extents (1: unused by the generic body)
@@ -337,7 +351,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM[b];
       const uint32_t K = (mL[b] & EPV_NJ_MASK) + (mR[b] & EPV_NJ_MASK) + 1u;
       r_w[b] = (uint32_t)(epv_meta_t)mM[b] | (K << 16) | ((2u * (mL[b] >> EPV_INIT_SHIFT) + (mR[b] >> EPV_INIT_SHIFT)) << 24);
-      need_rec += K + (EPV_TOPO_LEAF(b + 1) ? 0u : 1u);
+      need_rec += K + (!LEAF && EPV_TOPO_LEAF(b + 1) ? 0u : 1u);
       if (K >= 2u) heavy += K;
     }
   } else if (!SMALL && valid) {
@@ -356,7 +370,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       s_meta[(1u * B + b) * 64u + lane] = (epv_meta_t)mR;
       s_meta[(2u * B + b) * 64u + lane] = (epv_meta_t)mM;
       const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
-      need_rec += K + (S.subtree[b + 1u] != 1u ? 1u : 0u);
+      need_rec += K + (LEAF || S.subtree[b + 1u] != 1u ? 1u : 0u);
       if (K >= 2u) heavy += K;
     }
   }
@@ -498,18 +512,28 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
 #pragma unroll 1
       for (uint32_t node = NNODE - 1u; node >= 1u; --node) {
         const uint32_t b = node - 1u;
+        // LEAF: the cell's word leaves first (its address is node and site), the LDS reads below behind it
+        [[maybe_unused]] uint32_t leaf_word = 0u;
+        if constexpr (LEAF) {
+          if (SMALL ? EPV_TOPO_LEAF(node) != 0u : S.subtree[node] == 1u) leaf_word = epv_leaf_word(LS, node, site);
+        }
         const uint32_t mL = s_meta[(0u * B + b) * 64u + lane], mR = s_meta[(1u * B + b) * 64u + lane];
         const uint32_t K = (mL & EPV_NJ_MASK) + (mR & EPV_NJ_MASK) + 1u;
         // SMALL: the tree's shape from the topology word -- no load on the chain.  (S.subtree[] is
         // wave-uniform, yet the compiler fetched it with a vector load and a full wait per node and child.)
         const uint32_t sub = SMALL ? 2u - EPV_TOPO_LEAF(node) : S.subtree[node];     // (SMALL: 1 = a leaf, that is all it says)
-        off -= K + (sub != 1u ? 1u : 0u);
+        off -= K + (LEAF || sub != 1u ? 1u : 0u);
         double n0 = 1.0, n1 = 1.0;
         if (sub == 1u) {
           const uint32_t mM = s_meta[(2u * B + b) * 64u + lane];
           const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
           n0 = leaf_state ? 0.0 : 1.0;
           n1 = leaf_state ? 1.0 : 0.0;
+          if constexpr (LEAF) {
+            epv_leaf_q(leaf_word, leaf_state, n0, n1);
+            double *recq = my + (size_t)(off + K) * RS;
+            recq[0] = n0; recq[1] = n1;
+          }
         } else {
           if constexpr (SMALL) {
             // the children are the later nodes whose parent this is, in ascending order: the order of
@@ -584,7 +608,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           for (uint32_t k = 0; k < K; ++k) {
             const bool last_seg = (k + 1u == K);
             double nxt0, nxt1;
-            if (last_seg && leaf) {          // q of a leaf: the observed state
+            if (!LEAF && last_seg && leaf) {          // q of a leaf: the observed state (LEAF: the record pruning filed)
               const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
               nxt0 = leaf_state ? 0.0 : 1.0;
               nxt1 = leaf_state ? 1.0 : 0.0;
@@ -648,7 +672,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         for (uint32_t k = 0; k < K; ++k) {
           const bool last_seg = (k + 1u == K);
           double nxt0, nxt1;
-          if (last_seg && leaf) {          // q of a leaf: the observed state
+          if (!LEAF && last_seg && leaf) {          // q of a leaf: the observed state (LEAF: the record pruning filed)
             const uint32_t leaf_state = (mM >> EPV_INIT_SHIFT) ^ (mM & 1u);
             nxt0 = leaf_state ? 0.0 : 1.0;
             nxt1 = leaf_state ? 1.0 : 0.0;

@@ -107,12 +107,22 @@ template <int W> __device__ __forceinline__ P3Mask<W> p3_shr1(const P3Mask<W> &m
 #ifndef EPV_P3_MINBLOCKS
 #define EPV_P3_MINBLOCKS 3   /* blocks of four waves per CU the register allocation aims for (<= 168 VGPRs) */
 #endif
-template <int W>
+// LEAF (EPV_OPT_LEAF_FAST): a leaf's q is the leaf vector of LS (epv_leaf_word) wherever the
+// body would set it from the current path's end state -- leaf_q of the two node passes, whose word travels in the
+// batch of the q-row loads, and the pair lanes of level 0 and of the long-branch walk, which reload the cell by node
+// and the OWNER's site: a soft cell's q is not the one bit the pair word carries (bit 62 stays, as the indicator's
+// state).  Nothing else reads the path's end state: `ident` compares start states and jump counts, the task word's
+// end state is the proposal's.  The table and the mask are the two trailing arguments only these instantiations take.
+template <int W, class... Leaf>
 __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
     EpvDev S, uint32_t colour, uint32_t seed_lo, uint32_t seed_hi, uint32_t sweep, uint64_t first,
     uint64_t last, uint64_t own_first, uint64_t own_last, uint32_t list_cap, uint32_t n_qrows, uint32_t n_up,
     uint32_t depth, uint32_t parity, unsigned long long *counters, double *gpool, const double *segtab,
-    const uint32_t *nodetab, uint32_t *slab_flags, uint32_t slab_slots) {
+    const uint32_t *nodetab, uint32_t *slab_flags, uint32_t slab_slots, Leaf... leaf_args) {
+  constexpr bool LEAF = sizeof...(Leaf) != 0;
+  static_assert(sizeof...(Leaf) == (LEAF ? 2u : 0u), "the table and the mask come together");
+  [[maybe_unused]] EpvLeafSrc LS{nullptr, nullptr};
+  if constexpr (LEAF) { LS.table = epv_first_arg(leaf_args...); LS.mask = epv_second_arg(leaf_args...); }
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
   constexpr uint32_t HREC = EPV_HREC_SHORT, LEN_AT = HREC - 2u, INFO_AT = HREC - 1u;
 #ifdef EPV_P2_PROFILE
@@ -399,6 +409,7 @@ __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
           const uint32_t leaf_state = (uint32_t)(pr >> 62) & 1u;
           q0 = leaf_state ? 0.0 : 1.0;
           q1 = leaf_state ? 1.0 : 0.0;
+          if constexpr (LEAF) epv_leaf_q(epv_leaf_word(LS, node, site_lane0 + 3u * (uint64_t)owner), leaf_state, q0, q1);
         } else {
           const double *qr = qrows + (size_t)EPV_P3_QROW(nw) * 128u + (size_t)owner * 2u;
           q0 = qr[0]; q1 = qr[1];
@@ -492,10 +503,13 @@ __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
       __builtin_amdgcn_wave_barrier();
     };
     // q of a leaf: the observed state (the end state of the site's current path)
+    // (LEAF: q0 arrives holding the cell's word, which the batch of q-row loads fetched)
     auto leaf_q = [&](uint32_t node, double &q0, double &q1) __attribute__((always_inline)) {
       const uint32_t leaf_state = p3_get(mM, node) ^ p3_get(mMp, node);
+      [[maybe_unused]] const uint32_t word = (uint32_t)epv_d2u(q0);
       q0 = leaf_state ? 0.0 : 1.0;
       q1 = leaf_state ? 1.0 : 0.0;
+      if constexpr (LEAF) epv_leaf_q(word, leaf_state, q0, q1);
     };
 
     // ---- 4. pruning (SingleSiteSampler.cpp:116-157), deepest level first.  A level: q of its internal
@@ -522,6 +536,9 @@ __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
                 if (!EPV_P3_LEAF(cw) && !p3_get(mH, c)) {
                   const double *qr = qrows + (size_t)EPV_P3_QROW(cw) * 128u + (size_t)lane * 2u;
                   cq[j][w][0] = qr[0]; cq[j][w][1] = qr[1];
+                }
+                if constexpr (LEAF) {
+                  if (EPV_P3_LEAF(cw) && !p3_get(mH, c)) cq[j][w][0] = epv_u2d((uint64_t)epv_leaf_word(LS, c, site));
                 }
               }
             }
@@ -585,6 +602,9 @@ __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
               if (!EPV_P3_LEAF(cw) && !p3_get(mH, c)) {
                 const double *qr = qrows + (size_t)EPV_P3_QROW(cw) * 128u + (size_t)lane * 2u;
                 cq[j][0] = qr[0]; cq[j][1] = qr[1];
+              }
+              if constexpr (LEAF) {
+                if (EPV_P3_LEAF(cw) && !p3_get(mH, c)) cq[j][0] = epv_u2d((uint64_t)epv_leaf_word(LS, c, site));
               }
             }
           }
@@ -665,6 +685,7 @@ __global__ __launch_bounds__(256, EPV_P3_MINBLOCKS) void epv_mh_propose3_kernel(
               const uint32_t leaf_state = (uint32_t)(pr >> 62) & 1u;
               q0 = leaf_state ? 0.0 : 1.0;
               q1 = leaf_state ? 1.0 : 0.0;
+              if constexpr (LEAF) epv_leaf_q(epv_leaf_word(LS, node, site_lane0 + 3u * (uint64_t)owner), leaf_state, q0, q1);
             } else {
               const double *qr = qrows + (size_t)EPV_P3_QROW(nw) * 128u + (size_t)owner * 2u;
               q0 = qr[0]; q1 = qr[1];

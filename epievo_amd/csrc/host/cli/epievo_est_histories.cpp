@@ -74,7 +74,7 @@ static string strip_path(const string &full) {
 
 int main(int argc, const char **argv) {
   try {
-    bool VERBOSE = false, single_branch = false, direct_sampler = false, direct_fused = false;
+    bool VERBOSE = false, single_branch = false, direct_sampler = false, direct_fused = false, leaf_fast = false;
     string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
@@ -96,6 +96,8 @@ int main(int argc, const char **argv) {
                       "whatever the rates", false, direct_sampler);
     opt_parse.add_opt("direct-fused", 'F', "the direct sampler inside the fused colour phase where that is eligible "
                       "(implies -j; same results)", false, direct_fused);
+    opt_parse.add_opt("leaf-fast", 'f', "with -m / -l: keep the fused, second or large-tree proposal kernel (their leaf "
+                      "variants) instead of the first (same results)", false, leaf_fast);
     opt_parse.add_opt("verbose", 'v', "print more run info", false, VERBOSE);
     opt_parse.add_opt("gpus", 'g', "GPUs to shard the sites over: all | 0,1,.. (default: EPV_DEVICES or 0)", false,
                       gpu_list);
@@ -208,11 +210,13 @@ int main(int argc, const char **argv) {
     if (!missing_file.empty() && !leaf_probs_file.empty())
       throw std::runtime_error("-m/--missing and -l/--leaf-probs cannot be given together (N in a -l file is a missing cell)");
     // missing leaf data, checked against the paths before any GPU call
+    uint64_t n_held_unobserved = 0, n_held_evidence = 0;   // (for -v: beside the proposal kernel the plan takes)
     vector<uint8_t> unobserved;
     if (!missing_file.empty()) {
       uint64_t n_unobserved = 0, n_leaf_cells = 0;
       unobserved = epv::unobserved_leaf_cells(missing_file, th, paths, n_unobserved, n_leaf_cells);
       if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
+      n_held_unobserved = n_unobserved;
     }
     // leaf evidence, likewise
     vector<float> evidence;
@@ -220,6 +224,7 @@ int main(int argc, const char **argv) {
       uint64_t n_evidence = 0, n_leaf_cells = 0;
       evidence = epv::leaf_evidence_cells(leaf_probs_file, th, paths, n_evidence, n_leaf_cells);
       if (VERBOSE) cerr << "[LEAF CELLS WITH EVIDENCE: " << n_evidence << " of " << n_leaf_cells << "]" << endl;
+      n_held_evidence = n_evidence;
     }
 
     if (rng_seed == std::numeric_limits<size_t>::max()) {
@@ -230,12 +235,20 @@ int main(int argc, const char **argv) {
 
     epv::SingleSiteSampler mcmc(burnin, batch,
                                 gpu_list.empty() ? epv::devices_from_env() : epv::parse_device_list(gpu_list));
-    if (direct_sampler || direct_fused)     // (every context, later resets included)
-      mcmc.set_options((uint32_t)EPV_OPT_DIRECT_SAMPLER | (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u));
+    // (every context, later resets included; -f is harmless without -m / -l: the plan is then the default's)
+    if (direct_sampler || direct_fused || leaf_fast)
+      mcmc.set_options((direct_sampler || direct_fused ? (uint32_t)EPV_OPT_DIRECT_SAMPLER : 0u) |
+                       (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u) | (leaf_fast ? (uint32_t)EPV_OPT_LEAF_FAST : 0u));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
     mcmc.reset(the_model, th, paths);
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
+    if (VERBOSE && (n_held_unobserved || n_held_evidence)) {
+      static const char *const kernel[] = {"first", "second", "second (segment lists)", "fused phase", "large-tree"};
+      const uint32_t mode = mcmc.phase_mode();
+      cerr << "[PROPOSAL KERNEL WITH " << n_held_unobserved << " UNOBSERVED AND " << n_held_evidence
+           << " EVIDENCE LEAF CELLS: " << kernel[mode < 5u ? mode : 0u] << (mode ? ", leaf variant" : "") << "]" << endl;
+    }
     if (!average_file.empty()) mcmc.set_path_average((uint32_t)n_points);
     if (!changes_file.empty()) mcmc.set_branch_events(true);
     if (!regional_file.empty()) mcmc.set_window_stats(window);

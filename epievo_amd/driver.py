@@ -213,16 +213,23 @@ class CppSampler:
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
         """EPV_OPT_* of include/epievo_mi355x.h on every context, those of later resets included.  These three bits;
-        EPV_OPT_DIRECT_SAMPLER and EPV_OPT_DIRECT_FUSED stay as set_direct_sampler left them, so the order of the two
-        calls does not matter"""
+        EPV_OPT_DIRECT_SAMPLER and EPV_OPT_DIRECT_FUSED stay as set_direct_sampler left them and EPV_OPT_LEAF_FAST as
+        set_leaf_fast did, so the order of the calls does not matter"""
         self._options = (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) | \
-            (4 if sample_root else 0) | (self._options & 24)
+            (4 if sample_root else 0) | (self._options & (24 | 32))
         self._ck(self.L.epvd_set_options(self.h, self._options))
 
     def set_direct_sampler(self, on=True, fused=False):
         """EPV_OPT_DIRECT_SAMPLER (fused=True: and EPV_OPT_DIRECT_FUSED) on every context, those of later resets
         included: these bits of the word set_options last wrote, the others kept; on=False clears both"""
         self._options = (self._options & ~24) | ((8 | (16 if fused else 0)) if on else 0)
+        self._ck(self.L.epvd_set_options(self.h, self._options))
+
+    def set_leaf_fast(self, on=True):
+        """EPV_OPT_LEAF_FAST on every context, those of later resets included: a held mask or table keeps the fused
+        phase, the second or the third proposal kernel (leaf variants) instead of the first; this bit of the word,
+        the others kept"""
+        self._options = (self._options & ~32) | (32 if on else 0)
         self._ck(self.L.epvd_set_options(self.h, self._options))
 
     def set_timing(self, every):

@@ -233,12 +233,12 @@ class DeviceSampler:
 
     def set_options(self, reference_proposal_ratio=False, forward_rejection=False, sample_root=False):
         """see EPV_OPT_* in include/epievo_mi355x.h.  These three bits; EPV_OPT_DIRECT_SAMPLER and EPV_OPT_DIRECT_FUSED
-        stay as set_direct_sampler left them, so the order of the two calls does not matter (forward_rejection while the
-        direct sampler is on: EpvError)"""
+        stay as set_direct_sampler left them and EPV_OPT_LEAF_FAST as set_leaf_fast did, so the order of the calls does
+        not matter (forward_rejection while the direct sampler is on: EpvError)"""
         flags = C.c_uint32(0)
         self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
         self._ck(self.L.epv_set_options(self.h, (1 if reference_proposal_ratio else 0) | (2 if forward_rejection else 0) |
-                                        (4 if sample_root else 0) | (flags.value & 24)))
+                                        (4 if sample_root else 0) | (flags.value & (24 | 32))))
 
     def options(self):
         """the option word (EPV_OPT_* bits) as set_options and set_direct_sampler left it (epv_get_options)"""
@@ -255,6 +255,15 @@ class DeviceSampler:
         flags = C.c_uint32(0)
         self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
         self._ck(self.L.epv_set_options(self.h, (flags.value & ~24) | ((8 | (16 if fused else 0)) if on else 0)))
+
+    def set_leaf_fast(self, on=True):
+        """EPV_OPT_LEAF_FAST: a held leaf cell (set_unobserved, set_leaf_evidence) keeps the fused phase, the second or
+        the third proposal kernel, in their leaf variants, instead of sending every colour phase to the first kernel
+        (DESIGN 7.23).  Same chain bit for bit; off by default.  Its own call, as set_direct_sampler is: it changes
+        this bit of the word and leaves the others, and set_options / set_direct_sampler leave this one."""
+        flags = C.c_uint32(0)
+        self._ck(self.L.epv_get_options(self.h, C.byref(flags)))
+        self._ck(self.L.epv_set_options(self.h, (flags.value & ~32) | (32 if on else 0)))
 
     def direct_giveups(self):
         """segments the direct sampler gave up on since the context was created (epv_direct_giveups)"""
@@ -1030,7 +1039,7 @@ class SingleSiteSampler:
     stream is the counter-based (seed, sweep) pair, so the caller passes the seed and
     the index of the EM iteration (sweep numbers never repeat across iterations)."""
 
-    def __init__(self, n_burn_in, n_batch, device=0, capacity=0, direct_sampler=False, direct_fused=False):
+    def __init__(self, n_burn_in, n_batch, device=0, capacity=0, direct_sampler=False, direct_fused=False, leaf_fast=False):
         self.burn_in, self.batch = int(n_burn_in), int(n_batch)
         # hard-wired false in the reference (SingleSiteSampler.cpp:441) and set by none of its programs;
         # True = EPV_OPT_SAMPLE_ROOT: root states are proposed too (reference-arithmetic kernels)
@@ -1039,6 +1048,8 @@ class SingleSiteSampler:
         self.direct_sampler = bool(direct_sampler)
         # with direct_sampler: EPV_OPT_DIRECT_FUSED, the fused phase's direct bodies where the fused phase is eligible
         self.direct_fused = bool(direct_fused)
+        # True = EPV_OPT_LEAF_FAST: held leaf cells keep the fused / second / third proposal kernels (leaf variants)
+        self.leaf_fast = bool(leaf_fast)
         self.capacity = capacity
         self.dev = DeviceSampler(device)
         self.dev.auto_grow = True     # paths grow on demand, as the reference's vectors do
@@ -1051,6 +1062,7 @@ class SingleSiteSampler:
         self.dev._ck(self.dev.L.epv_get_options(self.dev.h, C.byref(flags)))
         want = (flags.value | 4) if self.SAMPLE_ROOT else (flags.value & ~4)
         want = (want & ~24) | ((8 | (16 if self.direct_fused else 0)) if self.direct_sampler else 0)
+        want = (want & ~32) | (32 if self.leaf_fast else 0)
         if want != flags.value:
             self.dev._ck(self.dev.L.epv_set_options(self.dev.h, want))
 

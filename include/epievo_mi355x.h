@@ -89,10 +89,23 @@ typedef struct {
  *     mode would run the fused phase, the direct mode runs it too, in the kernel's direct bodies: the wave samples
  *     its segment list by the same run_direct and assembles its branches itself, with no unbounded loop.  Same
  *     paths, statistics and counters as without the bit, bit for bit; where the fused phase is not eligible
- *     (a reference ratio, a sampled root, unobserved or evidence leaf cells, the large-tree kernel, a global
- *     pool, launches above the fused limit) the plan is that of EPV_OPT_DIRECT_SAMPLER alone. */
+ *     (a reference ratio, a sampled root, the large-tree kernel, a global pool, launches above the fused limit)
+ *     the plan is that of EPV_OPT_DIRECT_SAMPLER alone.  So it is while a leaf cell is unobserved or carries
+ *     evidence: the first kernel then, or under EPV_OPT_LEAF_FAST the leaf variant of the second or third, and
+ *     the separate direct jump kernels either way (the fused direct bodies have no leaf variant).
+ * EPV_OPT_LEAF_FAST  off by default.  A held leaf cell (epv_set_unobserved, epv_set_leaf_evidence) no longer
+ *     sends the colour phases to the first proposal kernel: the plan is what the same context would get with no
+ *     cell held -- the fused phase (generic or small-tree body, same sites per wave), the second kernel with its
+ *     jump stage, or the third with its words and slab pool -- and plan bits 17 / 18, which stay set, select
+ *     that kernel's leaf variant: the same kernel with the leaf vector (evidence, else the mask, else the
+ *     indicator; the first kernel's precedence and device layouts) wherever it would take a leaf's observed
+ *     state.  The first kernel stays wherever it is chosen for another reason: a
+ *     reference ratio, EPV_OPT_SAMPLE_ROOT, EPV_PROPOSE_V1, a global pool without the third kernel, a tree the
+ *     third does not take.  Same chain: the GPU equals oracle rung B bit for bit with the bit on as with it off
+ *     (tests/test_leaf_fast_gpu.py).  With no cell held the plan word and every result are those of the bit
+ *     off.  Combines freely with EPV_OPT_FORWARD_REJECTION and EPV_OPT_DIRECT_SAMPLER. */
 enum { EPV_OPT_REFERENCE_PROPOSAL_RATIO = 1, EPV_OPT_FORWARD_REJECTION = 2, EPV_OPT_SAMPLE_ROOT = 4,
-       EPV_OPT_DIRECT_SAMPLER = 8, EPV_OPT_DIRECT_FUSED = 16 };
+       EPV_OPT_DIRECT_SAMPLER = 8, EPV_OPT_DIRECT_FUSED = 16, EPV_OPT_LEAF_FAST = 32 };
 
 /* Create a context on HIP device `device_id`.  Returns NULL when the device cannot be
  * initialised (the product has no CPU fallback).  Replaces
@@ -168,9 +181,12 @@ int epv_phase_mode(epv_ctx *ctx, uint32_t *mode);
  *              _CACHE (epv_mh_accept_kernel with its LDS meta cache), _NO_CACHE (epv_mh_accept_kernel without)
  *   bit  16    the accept stage reads the listed sites (proposal kernels V2 and V3; 0 = every site of the colour)
  *   bit  17    V1: the template that marginalises unobserved leaf cells (epv_set_unobserved holds a cell;
- *              it forces V1 like bit 3 does)
+ *              it forces V1 like bit 3 does, unless EPV_OPT_LEAF_FAST is set)
  *   bit  18    V1: the template that reads the table of leaf evidence (epv_set_leaf_evidence holds a cell;
- *              it forces V1 too, and the mask of bit 17 rides along for the cells without evidence)
+ *              it forces V1 too, unless EPV_OPT_LEAF_FAST is set, and the mask of bit 17 rides along for the
+ *              cells without evidence)
+ *              Beside _V2, _V3 or _FUSED (EPV_OPT_LEAF_FAST) either bit means the leaf variant of that kernel:
+ *              the instantiation that takes the table and the mask as trailing arguments.
  *   bits 20-22 fused: log2 of the sites per wave (2 .. 6 for 4, 8, 16, 32 or 64 sites: EPV_FUSED_LANES, or by
  *              launch size -- with (n + 2) / 3 + 1 lanes 64 above 65536, 32 above 32768, else 16)
  *   bit  23    the jump stage's direct variants (EPV_OPT_DIRECT_SAMPLER): epv_seg_search_direct_kernel +
@@ -273,7 +289,8 @@ int epv_direct_giveups(epv_ctx *ctx, uint64_t *n_giveups);
  * latent already); before paths are resident EPV_ERR_STATE.  The device holds one bit per (leaf,
  * site), and only while a cell is flagged.  epv_upload_paths, epv_init_paths_indep and
  * epv_forward_simulate clear the mask (new paths are new data); everything else keeps it.  While a
- * cell is flagged a colour phase takes the first proposal kernel (epv_phase_mode 0, plan bit 17).
+ * cell is flagged a colour phase takes the first proposal kernel (epv_phase_mode 0, plan bit 17), or, under
+ * EPV_OPT_LEAF_FAST, the leaf variant of the kernel it would take without the mask (plan bit 17 beside it).
  * epv_unobserved_cells: the number of flagged cells.  No reference counterpart. */
 int epv_set_unobserved(epv_ctx *ctx, const uint8_t *unobserved);
 int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
@@ -293,7 +310,8 @@ int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
  * one float32 per (leaf, site), and only while a cell is non-NaN.  What clears the mask clears the
  * table (epv_upload_paths, epv_init_paths_indep, epv_forward_simulate, another tree); everything
  * else keeps it.  While a cell holds evidence a colour phase takes the first proposal kernel
- * (epv_phase_mode 0, plan bit 18).  epv_leaf_evidence_cells: the number of non-NaN cells.  No
+ * (epv_phase_mode 0, plan bit 18), or, under EPV_OPT_LEAF_FAST, the leaf variant of the kernel it would take
+ * without the table (plan bit 18 beside it).  epv_leaf_evidence_cells: the number of non-NaN cells.  No
  * reference counterpart.
  * The two ratio modes.  The target of a site carries the leaf factor q[end state].  The default mode
  * needs nothing for it (the proposal carries the same factor and the ratio stays 1).  Under
