@@ -1709,6 +1709,9 @@ int launch_fused(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a) {
   if (frc) return frc;
   const unsigned pb = (unsigned)((a.threads + v.fused_lanes - 1u) / v.fused_lanes);
   if (pb > c->fused_waves) return fail(c, EPV_ERR_STATE, "fused phase: launch larger than its lists");
+  // (a lane whose worst case is beyond the pool would never run, and the kernel's round loop never end)
+  if (v.pool < p2_worst_dbl(c->S.B, c->S.C, p2_hrec(true, true)))
+    return fail(c, EPV_ERR_STATE, "fused phase: the record pool is below one lane's worst case");
   EpvFused F = c->F;
   F.meta_cache = P.meta_cache ? 1u : 0u;
   F.lanes = v.fused_lanes;
@@ -1756,6 +1759,9 @@ int launch_propose(epv_ctx *c, const PhasePlan &P, const PhaseArgs &a, uint32_t 
   } else if (P.propose == EPV_PLAN_V2) {
     const PlanV2 &v = c->shapes.v2;
     const bool seg = P.jumps == EPV_PLAN_JUMPS_SEGMENTS;
+    // (as in launch_fused: the pool may have been planned next to a fused body, whose records are shorter)
+    if (v.pool < p2_worst_dbl(c->S.B, c->S.C, p2_hrec(false, seg)))
+      return fail(c, EPV_ERR_STATE, "second proposal kernel: the record pool is below one lane's worst case");
     if (seg) { const int rc = ensure_seg_buffers(c); if (rc) return rc; }
     if (P.unobs || P.evidence)
       hipLaunchKernelGGL(p2_leaf_kernel(seg), dim3((unsigned)((a.threads + 63u) / 64u)), dim3(64), v.lds, c->stream, c->S,
@@ -3558,6 +3564,16 @@ EPV_API int epv_debug_p2_profile(unsigned long long *out) {
   for (size_t r = 0; r < EPV_P2_PROF_ROWS; ++r)
     for (int q = 0; q < 16; ++q) out[q] += rows[16u * r + q];
   return 0;
+}
+// what hipOccupancyMaxActiveBlocksPerMultiprocessor says for the fused kernel this context would launch, at the
+// launch's dynamic LDS: blocks (one wave each) per CU
+EPV_API int epv_debug_p2_occupancy(epv_ctx *c, int *blocks, unsigned long long *lds) {
+  if (!c || !blocks || !lds || !c->have_paths) return EPV_ERR_ARG;
+  const PhasePlan P = phase_plan(c);
+  if (P.propose != EPV_PLAN_FUSED) return EPV_ERR_STATE;
+  *lds = c->shapes.v2.lds;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, reinterpret_cast<const void *>(fused_kernel(P.small_nn, P.direct)), 64,
+                                                      c->shapes.v2.lds) == hipSuccess ? EPV_OK : EPV_ERR_HIP;
 }
 #endif
 

@@ -129,9 +129,13 @@ enum { EPV_CNT_ACCEPT = 0, EPV_CNT_OVERFLOW = 1, EPV_CNT_COOP = 2, EPV_CNT_TASKS
 // sizes that the kernels and the host's plan of their launches (epv_plan.h) share
 // epv_propose2.h: the segment record EpvSegRec, as a heavy-segment record and as an entry of the matrix table
 #define EPV_SEGTAB_DBL 6u   /* table entry = the first six fields */
-#define EPV_HREC 10u        /* doubles per heavy-segment record: the eight fields, length, address word */
-#define EPV_HREC_SHORT 8u   /* ... when nothing reads length and address word after the dense evaluation
-                               (sequential jump kernel): they are parked in the slots of the two uniforms */
+#define EPV_HREC 10u        /* doubles per heavy-segment record: the eight fields, length, address word -- the second
+                               proposal kernel when it lists segments for the segment-parallel jump kernels */
+#define EPV_HREC_SHORT 8u   /* ... where the ten are never alive together: length and address word sit in slots 6, 7.
+                               Second and third kernel before the sequential jump kernel: nothing reads them behind
+                               the dense evaluation, which puts the two uniforms there.  Fused bodies: they stay, and
+                               the eight fields come in two passes over slots 0..5 -- P00, P11 for pruning, then
+                               PT00, PT10, the bounds and the uniforms for the downward pass (epv_plan.h: p2_hrec) */
 #define EPV_P2_SMALL_MAX 5  /* most nodes of the fused phase's small-tree body */
 #define EPV_COOP_BYTES (64u * (6u * 8u + 7u * 4u))   /* epv_jumps2.h: a wave's cooperative-search area, EpvCoop */
 #define EPV_P3_PCAP 256u    /* epv_propose3.h: heavy (lane, node) pairs a wave lists per round (at least 64: one lane's worst case) */

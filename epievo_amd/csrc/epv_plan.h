@@ -162,9 +162,23 @@ inline bool plan_mh(const PlanInput &in, const EpvKnobs &knobs, PlanV1 &v) {
   return true;
 }
 
+// doubles of a heavy-segment record in a variant of epv_mh_propose2_kernel: 10 in the second kernel when it lists
+// segments for the segment-parallel jump kernels (they read the records back), 8 in every fused body and in the
+// second kernel otherwise
+inline uint32_t p2_hrec(bool fused_body, bool seg) { return !fused_body && seg ? EPV_HREC : EPV_HREC_SHORT; }
+// ... and the largest of any variant phase_plan can launch in one pool.  The options are not known when the pool is
+// planned, and under EPV_OPT_DIRECT_SAMPLER without EPV_OPT_DIRECT_FUSED the second kernel runs in a pool planned
+// next to a fused body; it lists segments exactly when seg_jumps_on says so for these knobs and this kbar.
+inline uint32_t p2_hrec_max(const EpvKnobs &knobs, double kbar) { return p2_hrec(false, seg_jumps_on(knobs, kbar)); }
+// one lane's worst case in pool doubles: every branch with 2C+1 segments (records K+1 of 2 doubles, heavy K).  A pool
+// below it for the launched variant never lets that lane run: launch_fused and launch_propose refuse such a launch.
+inline uint64_t p2_worst_dbl(uint32_t B, uint32_t C, uint32_t hrec) {
+  return 2u * (uint64_t)B * (2u * C + 2u) + (uint64_t)hrec * B * (2u * C + 1u);
+}
+
 // launch shape of epv_mh_propose2_kernel: per wave the constants, the matrix table, the node
 // table and a pool of doubles shared by the Felsenstein records (2 doubles) and the heavy-segment
-// records (EPV_HREC doubles).  The pool covers the typical demand of 64 lanes with a margin (a wave that
+// records (p2_hrec doubles).  The pool covers the typical demand of 64 lanes with a margin (a wave that
 // needs more runs in rounds) and always one lane's worst case.
 inline bool plan_p2(const PlanInput &in, const EpvKnobs &knobs, PlanV2 &v) {
   const uint32_t N = in.N, B = N - 1u, C = in.C;
@@ -173,8 +187,6 @@ inline bool plan_p2(const PlanInput &in, const EpvKnobs &knobs, PlanV2 &v) {
   const size_t per_wave_fixed = ((((size_t)N * 64u + 1u) / 2u + 1u) & ~(size_t)1u) * 8u +
                                 ((3u * 64u + 2u) * (size_t)B * sizeof(epv_meta_t) + 15u) / 16u * 16u;   // node table, meta cache (+ 2 edge columns)
   const size_t fixed = shared + per_wave_fixed;
-  // one lane's worst case: every branch with 2C+1 segments (records K+1, heavy K)
-  const uint64_t worst_rec = (uint64_t)B * (2u * C + 2u), worst_heavy = (uint64_t)B * (2u * C + 1u);
   // the fused phase: few waves (a launch that leaves SIMDs idle pays one wave chain instead of
   // three to five), at most 64 segments per branch (the hand-over's bit word), lists for the worst
   // case of every wave within 4 GB
@@ -192,9 +204,10 @@ inline bool plan_p2(const PlanInput &in, const EpvKnobs &knobs, PlanV2 &v) {
   // With EPV_OPT_DIRECT_FUSED the fused direct bodies run in these very buffers.)
   const bool fused = !knobs.propose_v1 && 2u * C + 1u <= 64u && f_bytes <= (4ull << 30) &&
                      (knobs.fused_phase < 0 ? phase_waves <= FUSED_MAX_WAVES : knobs.fused_phase != 0);
-  // heavy-segment records: 8 doubles, 10 when the segment-parallel jump kernels read them back
-  const uint64_t hrec = (fused || seg_jumps_on(knobs, in.kbar)) ? EPV_HREC : EPV_HREC_SHORT;
-  const uint64_t worst_dbl = 2u * worst_rec + hrec * worst_heavy;
+  // heavy-segment records: the largest of any kernel that phase_plan can launch in this pool under any option
+  // word (p2_hrec_max) -- a pool below one lane's worst case would leave the kernel's round loop without an end
+  const uint64_t hrec = p2_hrec_max(knobs, in.kbar);
+  const uint64_t worst_dbl = p2_worst_dbl(B, C, (uint32_t)hrec);
   const double lam = 2.0 * in.kbar;
   uint32_t n_internal = 0;
   for (uint32_t node = 1; node < N; ++node) n_internal += in.subtree[node] != 1u;

@@ -39,7 +39,32 @@ struct EpvSegRec {      // one segment, everything the recursions need
   uint64_t info;        // trip0 | owner lane << 3 | node << 9 | k << 21
 };
 
+// The two halves of a segment's evaluation, one exponential each.  The fused bodies run them as two passes over
+// their 8-double records (pruning reads the first half's values and is done with them before the downward pass
+// reads the second half's); everything else takes both through epv_seg_matrices.
+// the pruning form: P00, P11
+EPV_DEV void epv_seg_prune_matrix(double len, double r0, double r1, double out[2]) {
+  const double denom = r0 + r1;
+  const double h = 1.0 / epv_exp(len * (r0 + r1));     // ContinuousTimeMarkovModel.cpp:143-161
+  out[0] = (r0 * h + r1) / denom;
+  out[1] = (r0 + r1 * h) / denom;
+}
+// the downward pass's: PT00, PT10 and the no-jump bounds
+EPV_DEV void epv_seg_sample_matrices(double len, double r0, double r1, double out[4]) {
+  const double denom = r0 + r1;
+  const double h2 = epv_exp(-len * (r0 + r1));         // :116-125, shared by both start states
+  out[0] = gtp(r0, r1, h2, denom, 0u, 0u);
+  out[1] = gtp(r0, r1, h2, denom, 1u, 0u);
+#if defined(__HIP_DEVICE_COMPILE__)
+  out[2] = nojump_bound(len * r0);
+  out[3] = nojump_bound(len * r1);
+#else
+  out[2] = 0.0;
+  out[3] = 0.0;
+#endif
+}
 // (host too, for epv_math_kat's host pass: the four matrix entries; the bounds are a device float exp)
+// (both halves, written out: the separate kernels' instruction streams are the ones they had before the split)
 EPV_DEV void epv_seg_matrices(double len, double r0, double r1, double out[6]) {
   const double denom = r0 + r1;
   const double h = 1.0 / epv_exp(len * (r0 + r1));     // ContinuousTimeMarkovModel.cpp:143-161
@@ -199,7 +224,15 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
   // branches go to epv_mh_jumps_kernel's bucketed lists
   // pool_dbl: the LDS pool, doubles per wave (records and heavy list share it); list_cap and gpool are unused
   extern __shared__ __attribute__((aligned(16))) double s_mem[];
-  constexpr uint32_t HREC = SEG ? EPV_HREC : EPV_HREC_SHORT, LEN_AT = HREC - 2u, INFO_AT = HREC - 1u;
+  // heavy-segment records: 10 doubles only where the segment-parallel jump kernels' hand-over reads length and
+  // address word behind all eight fields.  FUSED: 8 -- length and address word keep slots 6 and 7 for the life of
+  // the record, and the eight fields come in two passes over slots 0..5 (pruning form, then the downward pass's)
+  constexpr uint32_t HREC = (SEG && !FUSED) ? EPV_HREC : EPV_HREC_SHORT, LEN_AT = HREC - 2u, INFO_AT = HREC - 1u;
+  // slots of the downward pass's fields: EpvSegRec's order in the separate kernels, pass 2's in the fused bodies
+  constexpr uint32_t F_PT = FUSED ? 0u : 2u, F_NB = FUSED ? 2u : 4u, F_UEND = FUSED ? 4u : 6u, F_UFIRST = FUSED ? 5u : 7u;
+  // ... and where the downward pass parks a dirty heavy branch's sampled states and its dirty-segment mask for
+  // the hand-over: the two uniforms' slots of the branch's first record, used by then
+  [[maybe_unused]] constexpr uint32_t F_W64 = F_UEND, F_DMASK = F_UFIRST;
 #ifdef EPV_P2_PROFILE
   unsigned long long t_acc_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_prev_ = __builtin_readcyclecounter();
@@ -484,20 +517,27 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     __builtin_amdgcn_wave_barrier();
 
     P2_MARK(2);
-    // ---- 2. evaluate them densely, one segment per lane
+    // ---- 2. evaluate them densely, one segment per lane (FUSED: pass 1 of two, what pruning reads)
     for (uint32_t i = (uint32_t)lane; i < totH; i += 64u) {
       double *rec = list + (size_t)i * HREC;
       const double len = rec[LEN_AT];
       const uint64_t info = epv_d2u(rec[INFO_AT]);
       const uint32_t trip0 = (uint32_t)info & 7u, owner = (uint32_t)(info >> 3) & 63u;
       const uint32_t node = (uint32_t)(info >> 9) & 4095u, k = (uint32_t)(info >> 21);
-      double m[6];
-      epv_seg_matrices(len, s_rates[trip0], s_rates[trip0 | 2u], m);
-      const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite_lane0 + 3u * owner, sweep, node, k, 0u, 0u);
+      if constexpr (FUSED) {
+        double m[2];
+        epv_seg_prune_matrix(len, s_rates[trip0], s_rates[trip0 | 2u], m);
+        rec[0] = m[0];
+        rec[1] = m[1];
+      } else {
+        double m[6];
+        epv_seg_matrices(len, s_rates[trip0], s_rates[trip0 | 2u], m);
+        const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite_lane0 + 3u * owner, sweep, node, k, 0u, 0u);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) rec[q] = m[q];
-      rec[6] = blk.d0;
-      rec[7] = blk.d1;
+        for (int q = 0; q < 6; ++q) rec[q] = m[q];
+        rec[6] = blk.d0;
+        rec[7] = blk.d1;
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -578,6 +618,31 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
     }
 
     P2_MARK(4);
+    if constexpr (FUSED) {
+      // ---- 3b. dense evaluation, pass 2: pruning has read P00 and P11 for the last time; the downward pass's
+      //      fields -- PT00, PT10, the no-jump bounds and the segment's Philox block -- take slots 0..5
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      for (uint32_t i = (uint32_t)lane; i < totH; i += 64u) {
+        double *rec = list + (size_t)i * HREC;
+        const double len = rec[LEN_AT];
+        const uint64_t info = epv_d2u(rec[INFO_AT]);
+        const uint32_t trip0 = (uint32_t)info & 7u, owner = (uint32_t)(info >> 3) & 63u;
+        const uint32_t node = (uint32_t)(info >> 9) & 4095u, k = (uint32_t)(info >> 21);
+        double m[4];
+        epv_seg_sample_matrices(len, s_rates[trip0], s_rates[trip0 | 2u], m);
+        const epv_block2 blk = epv_keyed_block<!FUSED>(seed_lo, seed_hi, gsite_lane0 + 3u * owner, sweep, node, k, 0u, 0u);
+        rec[F_PT] = m[0];
+        rec[F_PT + 1u] = m[1];
+        rec[F_NB] = m[2];
+        rec[F_NB + 1u] = m[3];
+        rec[F_UEND] = blk.d0;
+        rec[F_UFIRST] = blk.d1;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      P2_MARK(10);
+    }
     // ---- 4. downward sampling of the segment END STATES (:180-255); the jump times are drawn
     //         by epv_mh_jumps_kernel for the dirty branches only (see epv_kernels.h).  The node
     //         loop is wave-uniform: the task flush inside it is a wave-wide operation.
@@ -603,7 +668,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           const uint32_t mM = EPV_RW_META(r_w[b]);
           uint32_t prev = start_state;
           bool clean = true;
-          unsigned long long word = 0ull, w64 = 0ull;
+          unsigned long long word = 0ull, w64 = 0ull, dmask = 0ull;
           double pk0 = my[(size_t)off * RS], pk1 = my[(size_t)off * RS + 1u];
           for (uint32_t k = 0; k < K; ++k) {
             const bool last_seg = (k + 1u == K);
@@ -625,14 +690,15 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
               u_end = blk.d0; u_first = blk.d1;
             } else {
               const double *hr = list + (size_t)(hcur + k) * HREC;
-              PT0 = prev ? hr[3] : hr[2];
-              nb = prev ? hr[5] : hr[4];
-              u_end = hr[6]; u_first = hr[7];
+              PT0 = prev ? hr[F_PT + 1u] : hr[F_PT];
+              nb = prev ? hr[F_NB + 1u] : hr[F_NB];
+              u_end = hr[F_UEND]; u_first = hr[F_UFIRST];
             }
             const double p0 = PT0 * nxt0 / (prev ? pk1 : pk0);
             const uint32_t sampled = (u_end > p0) ? 1u : 0u;
             const bool seg_clean = (sampled == prev) && (1.0 - u_first < nb);
             clean = clean && seg_clean;
+            if (!seg_clean) dmask |= 1ull << (k & 63u);
             word |= (unsigned long long)sampled << (k & 63u);
             if (k < 64u) w64 = word;
             prev = sampled;
@@ -644,7 +710,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           // emission pass reads other lanes' rows, so the row goes to LDS as well
           r_node[node] = off | (prev << 31) | (clean ? 0u : 1u << 30) | (K >= 2u ? hrec0 << 14 : 0u);
           regA[node * 64u + lane] = r_node[node];
-          if (!clean && K >= 2u) list[(size_t)hrec0 * HREC + 6u] = epv_u2d(w64);
+          if (!clean && K >= 2u) {
+            list[(size_t)hrec0 * HREC + F_W64] = epv_u2d(w64);
+            list[(size_t)hrec0 * HREC + F_DMASK] = epv_u2d(dmask);
+          }
           s_meta[(2u * B + (uint32_t)b) * 64u + lane] = (epv_meta_t)(start_state << EPV_INIT_SHIFT);
           ident = ident && clean && mM == (start_state << EPV_INIT_SHIFT);
         }
@@ -654,7 +723,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
       const uint32_t b = node - 1u;
       // what the wave-wide hand-over below needs from this lane's branch
       uint32_t nds = 0, Kb = 0, st_b = 0, end_b = 0, hrec0 = 0, trip_b = 0;
-      unsigned long long w64 = 0ull;
+      unsigned long long w64 = 0ull, dmask = 0ull;     // (dmask, FUSED: the branch's dirty segments, for the hand-over)
       bool dirty_b = false;
       if (run) {
         const uint32_t mL = s_meta[(0u * B + b) * 64u + lane], mR = s_meta[(1u * B + b) * 64u + lane];
@@ -689,9 +758,9 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
             u_end = blk.d0; u_first = blk.d1;
           } else {
             const double *hr = list + (size_t)(hcur + k) * HREC;
-            PT0 = prev ? hr[3] : hr[2];
-            nb = prev ? hr[5] : hr[4];
-            u_end = hr[6]; u_first = hr[7];
+            PT0 = prev ? hr[F_PT + 1u] : hr[F_PT];
+            nb = prev ? hr[F_NB + 1u] : hr[F_NB];
+            u_end = hr[F_UEND]; u_first = hr[F_UFIRST];
           }
           const double p0 = PT0 * nxt0 / (prev ? pk1 : pk0);
           const uint32_t sampled = (u_end > p0) ? 1u : 0u;
@@ -700,6 +769,7 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
           const bool seg_clean = (sampled == prev) && (1.0 - u_first < nb);
           clean = clean && seg_clean;
           nds += seg_clean ? 0u : 1u;
+          if (FUSED && !seg_clean) dmask |= 1ull << (k & 63u);
           word |= (unsigned long long)sampled << (k & 63u);
           if (k < 64u) w64 = word;
           if (!FUSED && (k & 63u) == 63u) { states[k >> 6] = word; word = 0ull; }   // (the fused phase hands the states over in its segment tasks)
@@ -715,7 +785,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         // slot of its first record's end-state uniform, which has been used
         if (FUSED) {
           regA[node * 64u + lane] = off | (prev << 31) | (clean ? 0u : 1u << 30) | (K >= 2u ? hrec0 << 14 : 0u);
-          if (!clean && K >= 2u) list[(size_t)hrec0 * HREC + 6u] = epv_u2d(w64);
+          if (!clean && K >= 2u) {
+            list[(size_t)hrec0 * HREC + F_W64] = epv_u2d(w64);
+            list[(size_t)hrec0 * HREC + F_DMASK] = epv_u2d(dmask);
+          }
         } else
           regA[node * 64u + lane] = off | (prev << 31);  // proposal end state for the children
         // the proposal's meta word (start state, no jumps yet; the fused phase's assembly adds the
@@ -902,17 +975,10 @@ __global__ __launch_bounds__(256, EPV_PROPOSE2_WAVES) void epv_mh_propose2_kerne
         unsigned long long w64 = end_b, dmask = 1ull;
         uint32_t nds = act ? 1u : 0u;
         if (act && Kb >= 2u) {
-          w64 = epv_d2u(list[(size_t)hrec0 * HREC + 6u]);
-          dmask = 0ull;
-          nds = 0u;
-          uint32_t prev = st_b;
-          for (uint32_t k = 0; k < Kb; ++k) {
-            const double *hr = list + (size_t)(hrec0 + k) * HREC;
-            const uint32_t sampled = (uint32_t)(w64 >> k) & 1u;
-            const bool seg_clean = (sampled == prev) && (1.0 - hr[7] < (prev ? hr[5] : hr[4]));
-            if (!seg_clean) { dmask |= 1ull << k; ++nds; }
-            prev = sampled;
-          }
+          // (the downward pass left both in the branch's first record)
+          w64 = epv_d2u(list[(size_t)hrec0 * HREC + F_W64]);
+          dmask = epv_d2u(list[(size_t)hrec0 * HREC + F_DMASK]);
+          nds = (uint32_t)__popcll(dmask);
         }
         const uint32_t inclS = wave_incl_scan_u32(nds);
         const uint32_t totS = epv_bcast(inclS, 63);

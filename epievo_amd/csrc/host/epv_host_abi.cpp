@@ -717,9 +717,13 @@ EPVH_API void epvh_epoch_stats_free(void *h) { delete (epv::EpochStats *)h; }
 // per (site, branch) as a context holds them, the option word as epv_set_options accepts it, the counts of
 // unobserved and evidence leaf cells, and the knobs as n_knobs strings NAME=VALUE in place of the environment.
 // *word: what epv_phase_plan reports for such a context
-EPVH_API int epvh_phase_plan(int n_nodes, const uint32_t *parent_ids, const uint32_t *subtree_sizes, uint64_t n_sites,
-                             uint32_t capacity, double kbar, uint32_t options, uint64_t unobs_cells,
-                             uint64_t evidence_cells, const char *const *knobs, int n_knobs, uint32_t *word) {
+// *word: what epv_phase_plan reports for such a context.  p2 (may be null): the launch shape of the second proposal
+// kernel and of the fused phase in its buffers (plan_p2) -- planned, fused, pool doubles per wave, dynamic LDS bytes,
+// sites per fused wave
+EPVH_API int epvh_phase_plan2(int n_nodes, const uint32_t *parent_ids, const uint32_t *subtree_sizes, uint64_t n_sites,
+                              uint32_t capacity, double kbar, uint32_t options, uint64_t unobs_cells,
+                              uint64_t evidence_cells, const char *const *knobs, int n_knobs, uint32_t *word,
+                              uint64_t p2[5]) {
   if (n_nodes < 2 || n_nodes > 4095 || !parent_ids || !subtree_sizes || !word || n_knobs < 0 || (n_knobs && !knobs)) {
     g_err = "bad tree";
     return 1;
@@ -745,5 +749,15 @@ EPVH_API int epvh_phase_plan(int n_nodes, const uint32_t *parent_ids, const uint
     return 1;
   }
   *word = phase_plan(shapes, k, options, unobs_cells, evidence_cells, (uint32_t)n_nodes - 1u, kbar).word();
+  if (p2) {
+    const PlanV2 &v = shapes.v2;
+    p2[0] = v.planned ? 1u : 0u; p2[1] = v.fused ? 1u : 0u; p2[2] = v.pool; p2[3] = v.lds; p2[4] = v.fused_lanes;
+  }
   return 0;
+}
+EPVH_API int epvh_phase_plan(int n_nodes, const uint32_t *parent_ids, const uint32_t *subtree_sizes, uint64_t n_sites,
+                             uint32_t capacity, double kbar, uint32_t options, uint64_t unobs_cells,
+                             uint64_t evidence_cells, const char *const *knobs, int n_knobs, uint32_t *word) {
+  return epvh_phase_plan2(n_nodes, parent_ids, subtree_sizes, n_sites, capacity, kbar, options, unobs_cells, evidence_cells,
+                          knobs, n_knobs, word, nullptr);
 }

@@ -138,6 +138,7 @@ def lib():
         L.epvh_epoch_stats_free.restype = None
         L.epvh_phase_plan.argtypes = [C.c_int, u32p, u32p, C.c_uint64, u32, C.c_double, u32, C.c_uint64, C.c_uint64,
                                       C.POINTER(C.c_char_p), C.c_int, C.POINTER(u32)]
+        L.epvh_phase_plan2.argtypes = L.epvh_phase_plan.argtypes + [u64p_]
         _lib = L
     return _lib
 
@@ -260,14 +261,23 @@ def phase_plan(tree, n_sites, capacity, kbar, options=0, unobs_cells=0, evidence
     (csrc/epv_plan.h): what DeviceSampler.phase_plan() returns in a context with this tree, n_sites local sites of
     jump capacity `capacity` and a mean of kbar jumps per (site, branch), the option word `options` (EPV_OPT_*),
     so many unobserved and evidence leaf cells, and `knobs` (EPV_* names to values) as its environment"""
+    return phase_plan_p2(tree, n_sites, capacity, kbar, options, unobs_cells, evidence_cells, knobs)[0]
+
+
+def phase_plan_p2(tree, n_sites, capacity, kbar, options=0, unobs_cells=0, evidence_cells=0, knobs={}):
+    """phase_plan, and beside it the launch shape of the second proposal kernel and of the fused phase in its
+    buffers (plan_p2 of csrc/epv_plan.h): planned, fused, pool (LDS doubles per wave), lds (dynamic LDS bytes of
+    the launch), fused_lanes"""
     names = [("%s=%s" % kv).encode() for kv in knobs.items()]
     arr = (C.c_char_p * max(len(names), 1))(*names)
     w = C.c_uint32(0)
-    if lib().epvh_phase_plan(tree.n_nodes, _p(tree.parent_ids, C.c_uint32), _p(tree.subtree_sizes, C.c_uint32),
-                             int(n_sites), int(capacity), float(kbar), int(options), int(unobs_cells),
-                             int(evidence_cells), arr, len(names), C.byref(w)):
+    p2 = (C.c_uint64 * 5)()
+    if lib().epvh_phase_plan2(tree.n_nodes, _p(tree.parent_ids, C.c_uint32), _p(tree.subtree_sizes, C.c_uint32),
+                              int(n_sites), int(capacity), float(kbar), int(options), int(unobs_cells),
+                              int(evidence_cells), arr, len(names), C.byref(w), p2):
         raise RuntimeError(lib().epvh_last_error().decode())
-    return plan_fields(int(w.value))
+    return plan_fields(int(w.value)), dict(planned=bool(p2[0]), fused=bool(p2[1]), pool=int(p2[2]), lds=int(p2[3]),
+                                           fused_lanes=int(p2[4]))
 
 
 def simulate(model, tree, n_sites, seed):

@@ -2,7 +2,7 @@
 """The fused colour phase section by section in the compiled kernel, without a GPU (sibling of tools/head_static.py).
 For a directory made by tools/static_mix.sh with EPV_STATIC_MIX_KEEP and -DEPV_P2_PROFILE (pattern
 'epv_mh_propose2_kernel<true, true'), the disassembly of a fused body is cut at its s_memtime instructions -- the
-kernel's entry and P2_MARK(0) .. P2_MARK(9), in the order the compiler laid the code out, which is the order of the
+kernel's entry and P2_MARK(0) .. P2_MARK(9) (and P2_MARK(10) behind pruning), in the order the compiler laid the code out, which is the order of the
 source here -- and for every section of the body the tool counts
   instructions, global loads (16-bit ones, byte ones), vmcnt waits (full ones: vmcnt(0)), lgkmcnt waits, LDS instructions
 and, from the compiler's remarks, prints VGPRs, scratch, occupancy and spilled SGPRs of all fused bodies.
@@ -14,6 +14,8 @@ import sys
 
 SECTIONS = ["head", "scan/plan", "descriptor pass", "dense eval", "pruning", "downward", "hand-over", "search",
             "assembly", "acceptance"]
+# ... with the dense evaluation in two passes (8-double records): P2_MARK(10) sits behind pruning
+SECTIONS2 = SECTIONS[:5] + ["dense eval 2"] + SECTIONS[5:]
 
 
 def instructions(path):
@@ -46,7 +48,7 @@ def resources(d):
     """{NN: (VGPRs, scratch, occupancy, spilled SGPRs)} from remarks.txt"""
     out, nn = {}, None
     for line in open(os.path.join(d, "remarks.txt")):
-        m = re.search(r"Function Name: _Z22epv_mh_propose2_kernelILb1ELb1ELi(\d)EE", line)
+        m = re.search(r"Function Name: _Z22epv_mh_propose2_kernelILb1ELb1ELi(\d)E(?:Lb0EJE)?E", line)
         if "Function Name:" in line:
             nn = int(m.group(1)) if m else None
             if nn is not None:
@@ -68,18 +70,21 @@ if args and args[0] == "--nn":
     nn, args = int(args[1]), args[2:]
 for d in args:
     print("== %s, NN = %d" % (d, nn))
-    f = glob.glob(os.path.join(d, "_Z22epv_mh_propose2_kernelILb1ELb1ELi%dEE*.s" % nn))
+    # (the default body: not the direct one, no leaf arguments)
+    f = (glob.glob(os.path.join(d, "_Z22epv_mh_propose2_kernelILb1ELb1ELi%dELb0EJEE*.s" % nn)) or
+         glob.glob(os.path.join(d, "_Z22epv_mh_propose2_kernelILb1ELb1ELi%dEE*.s" % nn)))
     if not f:
         print("  (no disassembly: run tools/static_mix.sh with EPV_STATIC_MIX_KEEP=%s -DEPV_P2_PROFILE first)" % d)
         continue
     secs = sections(instructions(f[0]))
-    if len(secs) != len(SECTIONS):
-        print("  (%d sections, expected %d: not a -DEPV_P2_PROFILE build; registers only)" % (len(secs), len(SECTIONS)))
+    names = SECTIONS2 if len(secs) == len(SECTIONS2) else SECTIONS
+    if len(secs) != len(names):
+        print("  (%d sections, expected %d: not a -DEPV_P2_PROFILE build; registers only)" % (len(secs), len(SECTIONS2)))
         secs = []
     else:
         print("  %-16s %12s %12s %8s %7s %13s %18s %13s %5s" % ("section", "instructions", "global loads", "16-bit", "byte",
                                                               "global stores", "vmcnt waits / (0)", "lgkmcnt waits", "LDS"))
-    for name, sec in zip(SECTIONS, secs):
+    for name, sec in zip(names, secs):
         c = count(sec)
         print("  %-16s %12d %12d %8d %7d %13d %12d / %-3d %13d %5d" % (name, c["n"], c["gl"], c["gl16"], c["gl8"], c["gs"],
                                                                        c["vm"], c["vm0"], c["lgkm"], c["lds"]))

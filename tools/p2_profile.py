@@ -18,8 +18,11 @@ lib().epv_debug_p2_profile(out)
 tot = [out[i] - base[i] for i in range(16)]
 waves = tot[15]
 names = ["start..staged+meta", "scan/plan", "descriptor pass", "dense eval", "pruning", "downward", "hand-over",
-         "fused: search", "fused: assemble", "fused: accept"]
-s = sum(tot[:10])
+         "fused: search", "fused: assemble", "fused: accept", "fused: dense eval, pass 2"]
+s = sum(tot[:11])
+blocks, lds = C.c_int(0), C.c_ulonglong(0)
+if hasattr(lib(), "epv_debug_p2_occupancy") and lib().epv_debug_p2_occupancy(C.c_void_p(d.h), C.byref(blocks), C.byref(lds)) == 0:
+    print("occupancy of the fused launch: %d blocks per CU at %d B of dynamic LDS" % (blocks.value, lds.value))
 for n_, t in zip(names, tot):
     print("%-22s %8.0f ticks/wave  %5.1f %%" % (n_, t / waves, 100.0 * t / s))
 print("total %.0f ticks per wave (%d waves)" % (s / waves, waves))
