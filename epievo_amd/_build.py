@@ -29,7 +29,7 @@ HOST_SO = os.path.join(PKG, "libepv_host.so")
 DRIVER_SO = os.path.join(PKG, "libepv_driver.so")
 BIN_DIR = os.path.join(PKG, "bin")
 
-HOST_SOURCES = ["epv_model.cpp", "epv_sim.cpp", "epv_io.cpp", "epv_indep.cpp", "epv_forward.cpp", "epv_domains.cpp", "epv_turnover.cpp", "epv_corr.cpp", "epv_dmaps.cpp", "epv_epochs.cpp", "epv_host_abi.cpp"]
+HOST_SOURCES = ["epv_model.cpp", "epv_sim.cpp", "epv_io.cpp", "epv_indep.cpp", "epv_forward.cpp", "epv_domains.cpp", "epv_turnover.cpp", "epv_tracts.cpp", "epv_corr.cpp", "epv_dmaps.cpp", "epv_epochs.cpp", "epv_host_abi.cpp"]
 # the reference library is built -O3 without -march (no FMA contraction); match it
 HOST_FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden", "-Wall", "-pthread"]
 
@@ -87,6 +87,7 @@ def build_host(force=False):
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST) if f.endswith((".cpp", ".hpp"))]
     srcs.append(os.path.join(CSRC, "epv_domain_bin.h"))   # (shared with the device code)
     srcs.append(os.path.join(CSRC, "epv_turnover_rec.h"))
+    srcs.append(os.path.join(CSRC, "epv_tract_rec.h"))
     srcs += [os.path.join(CSRC, "epv_plan.h"), os.path.join(CSRC, "epv_device.h"),   # (the colour phase's planner)
              os.path.join(INCLUDE, "epievo_mi355x.h")]
     if not force and _newer(HOST_SO, srcs):
@@ -99,9 +100,10 @@ def build_host(force=False):
 
 def build_driver(force=False):
     srcs = [os.path.join(HOST, f) for f in ("epv_driver_abi.cpp", "epv_sampler.cpp", "epv_domains.cpp", "epv_turnover.cpp",
-                                              "epv_corr.cpp", "epv_dmaps.cpp", "epv_epochs.cpp")]
+                                              "epv_tracts.cpp", "epv_corr.cpp", "epv_dmaps.cpp", "epv_epochs.cpp")]
     deps = srcs + [os.path.join(HOST, "epv_dmaps.hpp"), os.path.join(HOST, "epv_sampler.hpp"), os.path.join(HOST, "epv_domains.hpp"),
                    os.path.join(HOST, "epv_turnover.hpp"), os.path.join(CSRC, "epv_turnover_rec.h"),
+                   os.path.join(HOST, "epv_tracts.hpp"), os.path.join(CSRC, "epv_tract_rec.h"),
                    os.path.join(HOST, "epv_corr.hpp"),
                    os.path.join(HOST, "epv_epochs.hpp"),
                    os.path.join(CSRC, "epv_domain_bin.h"), os.path.join(INCLUDE, "epievo_mi355x_driver.h"), HIP_SO, COMM_SO]
@@ -135,8 +137,8 @@ def build_cli(force=False):
     cli = os.path.join(HOST, "cli")
     os.makedirs(BIN_DIR, exist_ok=True)
     common = [os.path.join(HOST, f) for f in ("epv_model.cpp", "epv_sim.cpp", "epv_io.cpp", "epv_indep.cpp",
-                                              "epv_forward.cpp", "epv_domains.cpp", "epv_turnover.cpp", "epv_corr.cpp",
-                                              "epv_dmaps.cpp", "epv_epochs.cpp", "epv_sampler.cpp",
+                                              "epv_forward.cpp", "epv_domains.cpp", "epv_turnover.cpp", "epv_tracts.cpp",
+                                              "epv_corr.cpp", "epv_dmaps.cpp", "epv_epochs.cpp", "epv_sampler.cpp",
                                               "epv_options.cpp")]
     outs = []
     for f in sorted(os.listdir(cli)):

@@ -31,6 +31,7 @@
 #include "epv_turnover.h"
 #include "epv_corr.h"
 #include "epv_dmaps.h"
+#include "epv_tracts.h"
 #include "epv_patterns.h"
 
 // ---- the state of the posterior summaries ("layers") of run_mcmc, one struct each.  Every member has a default:
@@ -192,6 +193,20 @@ struct DmapsState {
   uint64_t samples = 0;
 };
 
+// change tracts (epv_tracts.h), off while !on
+struct TractsState {
+  bool on = false;
+  uint64_t max = 0;                       // samples the edge records are allocated for
+  unsigned long long *d_hist = nullptr;   // [B][27][128] tracts closed inside the counted stretch, over the samples
+  unsigned long long *d_len = nullptr;    // [B][27] their lengths
+  unsigned long long *d_edge = nullptr;   // [max][B][2] what a sample's stretch cannot close at its two ends
+  unsigned long long *d_bits = nullptr;   // [2 B][words] scratch: the turnover's rows of one sample, 64 sites a word
+  SiteLayout at;                          // (with B: the rows depend on nothing else of the tree)
+  uint64_t words = 0;
+  uint32_t B = 0;
+  uint64_t samples = 0;
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -269,6 +284,7 @@ struct epv_ctx {
   CorrState co;
   MixingState mx;
   DmapsState dp;
+  TractsState tr;
   // leaf cells whose end state is not data (epv_set_unobserved), allocated while unobs_cells > 0:
   // the layout of epv_unobserved (epv_kernels.h)
   uint32_t *d_unobs = nullptr;
@@ -554,7 +570,7 @@ struct Layer {
   const char *off_msg;                         // what an entry point that needs the layer says while it is off
   const char *name;                            // as the sites-changed failure calls it
 };
-extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr, kMixing, kDmaps;   // (each behind its functions)
+extern const Layer kPavg, kBevents, kWstat, kEpochs, kOrigins, kDomains, kPatterns, kTurnover, kCorr, kMixing, kDmaps, kTracts;   // (each behind its functions)
 
 int sites_changed(epv_ctx *c, const Layer &L, const char *setter) {
   return fail(c, EPV_ERR_STATE, std::string("the sites of this context changed after ") + L.name + " took samples: " +
@@ -1620,10 +1636,94 @@ int launch_dmaps(epv_ctx *c) {
 const Layer kDmaps = {dmaps_on, ensure_dmaps, dmaps_check_cap, launch_dmaps, dmaps_off, nullptr,
                       "domain maps are off: epv_set_domain_maps first", "the domain maps"};
 
+// ---- change tracts (epv_tracts.h): the sites of pavg_range, one row of tracts per branch; a context keeps its PART,
+// unclosed
+bool tracts_on(const epv_ctx *c) { return c->tr.on; }
+void tracts_off(epv_ctx *c) {
+  dfree(c->tr.d_hist); dfree(c->tr.d_len); dfree(c->tr.d_edge); dfree(c->tr.d_bits);
+  c->tr = TractsState{};
+}
+// (re)lay out the part for the current branches and site range; zeroes it
+int tracts_alloc(epv_ctx *c) {
+  const SiteLayout at = pavg_layout(c, true, true);
+  const uint64_t cnt = at.cnt;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dfree(c->tr.d_hist); dfree(c->tr.d_len); dfree(c->tr.d_edge); dfree(c->tr.d_bits);
+  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "change tracts take at most 2^32 - 1 sites per context");
+  const uint32_t B = c->S.B;
+  const uint64_t words = (cnt + 63u) / 64u;
+  const double need = 8.0 * B * (EPV_TRACT_CLASSES * (EPV_DOM_BINS + 1.0)) + 16.0 * B * (double)words + 16.0 * B * (double)c->tr.max;
+  bool fits = false;
+  double free_b = 0.0;
+  const int rc = device_room(c, need, &fits, &free_b);
+  if (rc) return rc;
+  if (!fits) {
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "change tracts need %.3g GB of device memory (16 B x %u branches x %llu samples of "
+                  "edge records, 16 B x %u branches x %llu words of row states); %.3g GB are free: ask for fewer samples "
+                  "(the change tracts are off)",
+                  need / 1e9, B, (unsigned long long)c->tr.max, B, (unsigned long long)words, free_b / 1e9);
+    return fail(c, EPV_ERR_ARG, buf);
+  }
+  const size_t hist_b = (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * B, len_b = (size_t)8u * EPV_TRACT_CLASSES * B,
+               edge_b = (size_t)16u * B * c->tr.max;
+  HIP_TRY(c, hipMalloc(&c->tr.d_hist, hist_b));
+  HIP_TRY(c, hipMalloc(&c->tr.d_len, len_b));
+  HIP_TRY(c, hipMalloc(&c->tr.d_edge, edge_b));
+  if (words) HIP_TRY(c, hipMalloc(&c->tr.d_bits, (size_t)16u * B * words));
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_hist, 0, hist_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_len, 0, len_b, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_edge, 0, edge_b, c->stream));
+  c->tr.at = at;
+  c->tr.words = words;
+  c->tr.B = B;
+  c->tr.samples = 0;
+  return EPV_OK;
+}
+// the part matches the current site range and number of branches (as the turnover's: a row is one branch's meta words)
+int ensure_tracts(epv_ctx *c) {
+  if (pavg_layout(c, true, true) == c->tr.at) return EPV_OK;
+  if (c->tr.samples) return sites_changed(c, kTracts, "epv_set_change_tracts");
+  return relayout(c, kTracts, tracts_alloc);
+}
+int tracts_check_cap(epv_ctx *c, uint64_t more) {
+  if (c->tr.samples + more > c->tr.max) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "change tracts hold %llu of the %llu samples their edge records were allocated "
+                  "for, and %llu more were asked: read them out and epv_reset_change_tracts, or "
+                  "epv_set_change_tracts with more", (unsigned long long)c->tr.samples, (unsigned long long)c->tr.max,
+                  (unsigned long long)more);
+    return fail(c, EPV_ERR_STATE, buf);
+  }
+  return EPV_OK;
+}
+// the resident paths as one sample (ensure_tracts first): pack the turnover's rows, then count the tracts
+int launch_tracts(epv_ctx *c) {
+  int rc = tracts_check_cap(c, 1u);
+  if (rc) return rc;
+  if (c->tr.at.cnt && c->tr.B) {
+    const uint64_t words = c->tr.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
+    hipLaunchKernelGGL(epv_turn_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->tr.at.lo,
+                       c->tr.at.cnt, words, c->tr.d_bits);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long *edge = c->tr.d_edge + c->tr.samples * 2u * c->tr.B;
+    for (uint32_t b0 = 0; b0 < c->tr.B; b0 += 65534u) {   // (a grid's y dimension takes 65535 rows)
+      const uint32_t nb = std::min<uint32_t>(65534u, c->tr.B - b0);
+      hipLaunchKernelGGL(epv_tract_runs_kernel, dim3((unsigned)chunks, nb), dim3(256), 0, c->stream,
+                         (const unsigned long long *)c->tr.d_bits, words, c->tr.at.cnt, b0, c->tr.d_hist, c->tr.d_len, edge);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  ++c->tr.samples;
+  return EPV_OK;
+}
+const Layer kTracts = {tracts_on, ensure_tracts, tracts_check_cap, launch_tracts, tracts_off, nullptr,
+                       "change tracts are off: epv_set_change_tracts first", "the change tracts"};
+
 // the layers in the order of the chain: run_mcmc ensures, caps and launches them in this order, so the first
 // that fails is the one reported, and their kernels enter the stream in this order after every batch sweep
 const Layer *const kLayers[] = {&kPavg, &kBevents, &kWstat, &kEpochs, &kOrigins, &kDomains, &kPatterns, &kTurnover, &kCorr,
-                                &kMixing, &kDmaps};
+                                &kMixing, &kDmaps, &kTracts};
 
 // the global-memory slab of a proposal kernel, allocated when a launch first takes that kernel (a
 // context on a large tree plans three kernels but runs one: 5 - 50 GB each at full size)
@@ -4227,6 +4327,68 @@ EPV_API int epv_get_domain_turnover(epv_ctx *c, uint64_t *hist, uint64_t *len_su
   HIP_TRY(c, hipMemcpy(len_sum, c->to.d_len, (size_t)32u * c->to.R, hipMemcpyDeviceToHost));
   if (c->to.samples)
     HIP_TRY(c, hipMemcpy(edges, c->to.d_edge, (size_t)16u * c->to.R * c->to.samples, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+// ---- change tracts (epv_tracts.h)
+EPV_API int epv_set_change_tracts(epv_ctx *c, uint64_t max_samples) {
+  if (!max_samples) return layer_set_off(c, kTracts);
+  if (max_samples > EPV_TRACT_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "change tracts take at most 2^21 samples");
+  const int rc = check_ready(c, false);
+  if (rc) return rc;
+  c->tr.on = true;
+  c->tr.max = max_samples;
+  return layer_set_on(c, kTracts, tracts_alloc);
+}
+
+EPV_API int epv_reset_change_tracts(epv_ctx *c) {
+  const int rc = layer_entry(c, kTracts);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_hist, 0, (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * c->tr.B, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_len, 0, (size_t)8u * EPV_TRACT_CLASSES * c->tr.B, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->tr.d_edge, 0, (size_t)16u * c->tr.B * c->tr.max, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->tr.samples = 0;
+  return EPV_OK;
+}
+
+EPV_API int epv_accumulate_change_tracts(epv_ctx *c) { return layer_accumulate(c, kTracts); }
+
+EPV_API int epv_change_tracts_samples(epv_ctx *c, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = c->tr.samples;   // (0 while the layer is off)
+  return EPV_OK;
+}
+
+EPV_API int epv_change_tracts_layout(epv_ctx *c, uint32_t *n_branches, uint32_t *n_classes, uint32_t *n_bins, uint64_t *first,
+                                     uint64_t *count, uint64_t *chunk_sites) {
+  if (!c || !n_branches || !n_classes || !n_bins || !first || !count || !chunk_sites) return EPV_ERR_ARG;
+  *n_branches = *n_classes = *n_bins = 0;
+  *first = *count = *chunk_sites = 0;
+  if (!c->tr.on) return EPV_OK;
+  if (c->have_tree && c->have_paths && !c->tr.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_tracts(c);
+    if (rc) return rc;
+  }
+  *n_branches = c->tr.B;
+  *n_classes = EPV_TRACT_CLASSES;
+  *n_bins = EPV_DOM_BINS;
+  *first = c->tr.at.lo;
+  *count = c->tr.at.cnt;
+  *chunk_sites = 64ull * EPV_DOM_CHUNK_WORDS;
+  return EPV_OK;
+}
+
+EPV_API int epv_get_change_tracts(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  const int rc = layer_entry(c, kTracts);
+  if (rc) return rc;
+  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(hist, c->tr.d_hist, (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * c->tr.B, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(len_sum, c->tr.d_len, (size_t)8u * EPV_TRACT_CLASSES * c->tr.B, hipMemcpyDeviceToHost));
+  if (c->tr.samples)
+    HIP_TRY(c, hipMemcpy(edges, c->tr.d_edge, (size_t)16u * c->tr.B * c->tr.samples, hipMemcpyDeviceToHost));
   return EPV_OK;
 }
 

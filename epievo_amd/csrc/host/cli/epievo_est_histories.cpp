@@ -49,6 +49,10 @@
 // (default 1) and the same -w/--window W: the domain maps of the B batch sweeps (epv_set_domain_maps with max_samples =
 // B: per node, size and site the samples in which the site lies in a run of state s of at least that size), summed
 // over windows of W sites, as integers (epv::write_domain_maps).  Changes nothing else the run writes.
+// New: -X/--tracts FILE: the change tracts of the B batch sweeps (epv_set_change_tracts with max_samples = B: per
+// branch the maximal runs of sites with a net change, by direction (gain, loss, mixed), by the state of the unchanged
+// site on each flank and by length -- domains born, grown, shrunk, split and died, and by how many sites -- closed
+// over the whole genome), as integers (epv::write_change_tracts).  Changes nothing else the run writes.
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -61,6 +65,7 @@
 #include "epv_model.hpp"
 #include "epv_options.hpp"
 #include "epv_sampler.hpp"
+#include "epv_tracts.hpp"
 
 using std::cerr;
 using std::endl;
@@ -75,7 +80,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false, direct_sampler = false, direct_fused = false, leaf_fast = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes;
+    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes, tracts_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
@@ -132,6 +137,8 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("sizes", 'z', "sizes of the domain maps: 1 to 4 increasing numbers of sites, at most 1024 (default "
                       "5,20)", false, maps_sizes);
     opt_parse.add_opt("state", 'S', "state whose domains the maps locate: 0 or 1 (default 1)", false, maps_state);
+    opt_parse.add_opt("tracts", 'X', "output file of the change tracts of the batch sweeps (integer counts per class and bin)",
+                      false, tracts_file);
     opt_parse.add_opt("nepochs", 'K', "epochs per branch of the epoch statistics (default 10, at most 256)", false, n_epochs);
     opt_parse.add_opt("window", 'w', "sites per window of the branch-event maps, regional statistics, origin maps, "
                       "change patterns, mixing diagnostics and domain maps (default 1)", false, window);
@@ -196,6 +203,8 @@ int main(int argc, const char **argv) {
     if (batch == 0) throw std::runtime_error("-B: at least one batch sweep");
     if (!turnover_file.empty() && batch > (1ull << 21))
       throw std::runtime_error("-R/--turnover: the domain turnover takes at most 2^21 batch sweeps (-B)");
+    if (!tracts_file.empty() && batch > (1ull << 21))
+      throw std::runtime_error("-X/--tracts: the change tracts take at most 2^21 batch sweeps (-B)");
     if (!corr_file.empty() && batch > (1ull << 21))
       throw std::runtime_error("-C/--correlation: the spatial correlations take at most 2^21 batch sweeps (-B)");
     const string param_file(leftover_args.front()), input_file(leftover_args.back());
@@ -260,6 +269,7 @@ int main(int argc, const char **argv) {
     if (!corr_file.empty()) mcmc.set_spatial_correlation((uint32_t)max_lag, batch);
     if (!mixing_file.empty()) mcmc.enable_mixing((uint32_t)mixing_lag);
     if (!maps_file.empty()) mcmc.set_domain_maps(map_sizes, (uint32_t)maps_state, batch);
+    if (!tracts_file.empty()) mcmc.set_change_tracts(batch);
     double acceptance_rate = 0.0;
     vector<vector<double>> J, D;
     mcmc.run_mcmc(rng_seed, 0, J, D, acceptance_rate);
@@ -370,6 +380,15 @@ int main(int argc, const char **argv) {
       epv::domain_map_windows(n_nodes, (uint32_t)map_sizes.size(), n_sites, counts.data(), window, sums.data());
       epv::write_domain_maps(maps_file, th.node_names, n_samples, (uint32_t)maps_state, map_sizes, n_sites, window,
                              sums.data());
+    }
+    if (!tracts_file.empty()) {
+      vector<uint64_t> hist, len_sum;
+      uint32_t n_branches = 0;
+      uint64_t n_samples = 0;
+      mcmc.download_change_tracts(hist, len_sum, n_branches, n_samples);
+      if (VERBOSE) cerr << "[WRITING CHANGE TRACTS OF " << n_samples << " SAMPLES: " << tracts_file << "]" << endl;
+      const vector<string> branch_names(th.node_names.begin() + 1, th.node_names.end());
+      epv::write_change_tracts(tracts_file, branch_names, n_samples, hist.data(), len_sum.data());
     }
   } catch (const std::exception &e) {
     cerr << e.what() << endl;

@@ -38,6 +38,8 @@ struct epvd_sampler {
   bool have_staged_domains = false;
   std::vector<uint64_t> staged_turn_hist, staged_turn_len, staged_turn_edges;   // between epvd_turnover_part_sizes and epvd_download_turnover_part
   bool have_staged_turnover = false;
+  std::vector<uint64_t> staged_tract_hist, staged_tract_len, staged_tract_edges;   // between epvd_tracts_part_sizes and epvd_download_tracts_part
+  bool have_staged_tracts = false;
   std::vector<uint64_t> staged_corr_n11, staged_corr_edges;   // between epvd_corr_part_sizes and epvd_download_corr_part
   bool have_staged_corr = false;
   std::vector<uint32_t> staged_dmaps_counts;   // between epvd_dmaps_sizes and epvd_download_dmaps
@@ -477,6 +479,47 @@ EPVD_API int epvd_download_turnover(epvd_sampler *h, uint32_t n_rows, uint64_t *
     uint64_t ns = 0;
     h->s->download_domain_turnover(hh, ll, R, ns);
     if (R != n_rows) throw std::runtime_error("epvd_download_turnover: n_rows must be twice the tree's number of branches");
+    std::copy(hh.begin(), hh.end(), hist);
+    std::copy(ll.begin(), ll.end(), len_sum);
+    if (n_samples) *n_samples = ns;
+  });
+}
+
+EPVD_API int epvd_set_tracts(epvd_sampler *h, uint64_t max_samples) {
+  return guarded(h, [&] { h->s->set_change_tracts(max_samples); });
+}
+EPVD_API int epvd_reset_tracts(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->reset_change_tracts(); });
+}
+EPVD_API int epvd_accumulate_tracts(epvd_sampler *h) {
+  return guarded(h, [&] { h->s->accumulate_change_tracts(); });
+}
+EPVD_API int epvd_tracts_part_sizes(epvd_sampler *h, uint32_t *n_branches, uint64_t *n_samples) {
+  return guarded(h, [&] {
+    h->s->download_change_tracts_part(h->staged_tract_hist, h->staged_tract_len, h->staged_tract_edges, *n_branches, *n_samples);
+    h->have_staged_tracts = true;
+  });
+}
+EPVD_API int epvd_download_tracts_part(epvd_sampler *h, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
+  return guarded(h, [&] {
+    if (!h->have_staged_tracts) throw std::runtime_error("epvd_tracts_part_sizes first");
+    std::copy(h->staged_tract_hist.begin(), h->staged_tract_hist.end(), hist);
+    std::copy(h->staged_tract_len.begin(), h->staged_tract_len.end(), len_sum);
+    std::copy(h->staged_tract_edges.begin(), h->staged_tract_edges.end(), edges);
+    h->staged_tract_hist.clear();
+    h->staged_tract_len.clear();
+    h->staged_tract_edges.clear();
+    h->have_staged_tracts = false;
+  });
+}
+EPVD_API int epvd_download_tracts(epvd_sampler *h, uint32_t n_branches, uint64_t *hist, uint64_t *len_sum,
+                                  uint64_t *n_samples) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> hh, ll;
+    uint32_t B = 0;
+    uint64_t ns = 0;
+    h->s->download_change_tracts(hh, ll, B, ns);
+    if (B != n_branches) throw std::runtime_error("epvd_download_tracts: n_branches must be the tree's number of branches");
     std::copy(hh.begin(), hh.end(), hist);
     std::copy(ll.begin(), ll.end(), len_sum);
     if (n_samples) *n_samples = ns;

@@ -13,6 +13,7 @@
 #include "epv_io.hpp"
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
+#include "epv_tracts.hpp"
 #include "epv_corr.hpp"
 #include "epv_dmaps.hpp"
 #include "epv_epochs.hpp"
@@ -533,6 +534,49 @@ EPVH_API void epvh_domain_turnover_copy(void *h, char *names, int names_len, uin
   std::copy(dt->len_sum.begin(), dt->len_sum.end(), len_sum);
 }
 EPVH_API void epvh_domain_turnover_free(void *h) { delete (epv::DomainTurnover *)h; }
+
+// ---- change tracts: merge and close of parts (epv_tracts.hpp), the file of epievo_est_histories -X
+// hists, len_sums, edges: n_parts pointers each, parts in genome order ([B][27][128], [B][27], [samples][B][2])
+EPVH_API int epvh_tract_parts_merge(uint64_t n_parts, uint32_t B, uint64_t samples, const uint64_t *const *hists,
+                                    const uint64_t *const *len_sums, const uint64_t *const *edges, uint64_t *out_hist,
+                                    uint64_t *out_len_sum, uint64_t *out_edges) {
+  try {
+    epv::tract_parts_merge(n_parts, B, samples, hists, len_sums, edges, out_hist, out_len_sum, out_edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API int epvh_tract_part_close(uint32_t B, uint64_t samples, uint64_t *hist, uint64_t *len_sum, const uint64_t *edges) {
+  try {
+    epv::tract_part_close(B, samples, hist, len_sum, edges);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+// branch_names: the child node's name of every branch joined by '\n'; hist [B][27][128], len_sum [B][27]: closed
+EPVH_API int epvh_write_change_tracts(const char *file, const char *branch_names, uint64_t n_samples, const uint64_t *hist,
+                                      const uint64_t *len_sum) {
+  try {
+    epv::write_change_tracts(file, split_names(branch_names), n_samples, hist, len_sum);
+    return 0;
+  } catch (const std::exception &e) { g_err = e.what(); return 1; }
+}
+EPVH_API void *epvh_read_change_tracts(const char *file) {
+  try {
+    return new epv::ChangeTracts(epv::read_change_tracts(file));
+  } catch (const std::exception &e) { g_err = e.what(); return nullptr; }
+}
+EPVH_API void epvh_change_tracts_dims(void *h, uint64_t *n_samples, uint64_t *n_branches, uint64_t *names_len) {
+  const epv::ChangeTracts *ct = (const epv::ChangeTracts *)h;
+  *n_samples = ct->n_samples;
+  *n_branches = ct->branch_names.size();
+  *names_len = join_names(ct->branch_names).size() + 1u;
+}
+EPVH_API void epvh_change_tracts_copy(void *h, char *names, int names_len, uint64_t *hist, uint64_t *len_sum) {
+  const epv::ChangeTracts *ct = (const epv::ChangeTracts *)h;
+  put_text(join_names(ct->branch_names), names, names_len);
+  std::copy(ct->hist.begin(), ct->hist.end(), hist);
+  std::copy(ct->len_sum.begin(), ct->len_sum.end(), len_sum);
+}
+EPVH_API void epvh_change_tracts_free(void *h) { delete (epv::ChangeTracts *)h; }
 
 // ---- spatial correlations: merge and close of parts (epv_corr.hpp), the file of epievo_est_histories -C
 // cnts, n11s, edges: n_parts entries each, parts in genome order ([R][L + 1], [samples][R][2][LW]); out_cnt: the

@@ -15,6 +15,7 @@
 #include "epievo_mi355x.h"
 #include "epv_domains.hpp"
 #include "epv_turnover.hpp"
+#include "epv_tracts.hpp"
 #include "epv_corr.hpp"
 #include "epv_dmaps.hpp"
 #include "epievo_mi355x_comm.h"
@@ -442,6 +443,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &p
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
   if (mixing_lag_) enable_mixing(mixing_lag_);
   if (!dmaps_sizes_.empty()) set_domain_maps(dmaps_sizes_, dmaps_state_, dmaps_max_);
+  if (tracts_max_) set_change_tracts(tracts_max_);
 }
 
 void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &owned, uint64_t n_global) {
@@ -459,6 +461,7 @@ void SingleSiteSampler::reset(const Model &m, const Tree &th, const FlatPaths &o
   if (corr_lag_) set_spatial_correlation(corr_lag_, corr_max_);
   if (mixing_lag_) enable_mixing(mixing_lag_);
   if (!dmaps_sizes_.empty()) set_domain_maps(dmaps_sizes_, dmaps_state_, dmaps_max_);
+  if (tracts_max_) set_change_tracts(tracts_max_);
 }
 
 void SingleSiteSampler::set_path_average(uint32_t n_points) {
@@ -928,6 +931,65 @@ void SingleSiteSampler::download_domain_turnover(std::vector<uint64_t> &hist, st
   std::vector<uint64_t> edges;
   download_domain_turnover_part(hist, len_sum, edges, n_rows, n_samples);
   turnover_part_close(n_rows, n_samples, hist.data(), len_sum.data(), edges.data());
+}
+
+void SingleSiteSampler::set_change_tracts(uint64_t max_samples) {
+  // (before the first reset(model, tree, paths): applied to the contexts that reset builds)
+  if (n_sites_ || !max_samples)
+    for (epv_ctx *c : contexts()) check_on(c, epv_set_change_tracts(c, max_samples), "epv_set_change_tracts");
+  tracts_max_ = max_samples;
+}
+
+void SingleSiteSampler::reset_change_tracts() {
+  if (!tracts_max_) throw std::runtime_error("change tracts are off: set_change_tracts first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_reset_change_tracts(c), "epv_reset_change_tracts");
+}
+
+void SingleSiteSampler::accumulate_change_tracts() {
+  if (!tracts_max_) throw std::runtime_error("change tracts are off: set_change_tracts first");
+  for (epv_ctx *c : contexts()) check_on(c, epv_accumulate_change_tracts(c), "epv_accumulate_change_tracts");
+}
+
+void SingleSiteSampler::download_change_tracts_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                                    std::vector<uint64_t> &edges, uint32_t &n_branches,
+                                                    uint64_t &n_samples) {
+  if (!tracts_max_) throw std::runtime_error("change tracts are off: set_change_tracts first");
+  const std::vector<epv_ctx *> cs = contexts();   // in genome order
+  std::vector<std::vector<uint64_t>> h(cs.size()), l(cs.size()), e(cs.size());
+  std::vector<const uint64_t *> hp(cs.size()), lp(cs.size()), ep(cs.size());
+  n_branches = 0;
+  n_samples = 0;
+  for (size_t i = 0; i < cs.size(); ++i) {
+    uint32_t B = 0, classes = 0, bins = 0;
+    uint64_t first = 0, count = 0, chunk = 0, ns = 0;
+    check_on(cs[i], epv_change_tracts_layout(cs[i], &B, &classes, &bins, &first, &count, &chunk), "epv_change_tracts_layout");
+    check_on(cs[i], epv_change_tracts_samples(cs[i], &ns), "epv_change_tracts_samples");
+    if (i == 0) { n_branches = B; n_samples = ns; }
+    else if (ns != n_samples) throw std::runtime_error("the contexts hold different numbers of change-tract samples");
+    else if (B != n_branches) throw std::runtime_error("the contexts hold change tracts of different trees");
+    h[i].assign((size_t)B * EPV_TRACT_CLASSES * EPV_DOM_BINS, 0u);
+    l[i].assign((size_t)B * EPV_TRACT_CLASSES, 0u);
+    e[i].assign(std::max<size_t>((size_t)ns * B * 2u, 1u), 0u);
+    check_on(cs[i], epv_get_change_tracts(cs[i], h[i].data(), l[i].data(), e[i].data()), "epv_get_change_tracts");
+    hp[i] = h[i].data(); lp[i] = l[i].data(); ep[i] = e[i].data();
+  }
+  hist.assign((size_t)n_branches * EPV_TRACT_CLASSES * EPV_DOM_BINS, 0u);
+  len_sum.assign((size_t)n_branches * EPV_TRACT_CLASSES, 0u);
+  edges.assign((size_t)n_samples * n_branches * 2u, 0u);
+  std::vector<uint64_t> none(1, 0u);
+  tract_parts_merge(cs.size(), n_branches, n_samples, hp.data(), lp.data(), ep.data(), hist.data(), len_sum.data(),
+                    edges.empty() ? none.data() : edges.data());
+}
+
+void SingleSiteSampler::download_change_tracts(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                               uint32_t &n_branches, uint64_t &n_samples) {
+  if (rank_mode_)
+    throw std::runtime_error("download_change_tracts: this process holds one slot's stretch of the genome, not the "
+                             "genome: merge the processes' download_change_tracts_part in genome order "
+                             "(epv::tract_parts_merge, epvh_tract_parts_merge), then close the merged part");
+  std::vector<uint64_t> edges;
+  download_change_tracts_part(hist, len_sum, edges, n_branches, n_samples);
+  tract_part_close(n_branches, n_samples, hist.data(), len_sum.data(), edges.data());
 }
 
 void SingleSiteSampler::set_spatial_correlation(uint32_t max_lag, uint64_t max_samples) {

@@ -181,6 +181,19 @@ public:
                                      std::vector<uint64_t> &edges, uint32_t &n_rows, uint64_t &n_samples);
   void download_domain_turnover(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_rows,
                                 uint64_t &n_samples);
+  // change tracts (epv_set_change_tracts) on every context, with the domain turnover's samples and lifecycle;
+  // max_samples = 0 is off.  n_branches = n_nodes-1.  download_change_tracts_part: the parts of all slots and
+  // contexts of this process merged in genome order (epv::tract_parts_merge), unclosed: hist [B][27][128], len_sum
+  // [B][27], edges [samples][B][2].  download_change_tracts: that part closed (epv::tract_part_close).  One slot
+  // per process: it throws, as download_domain_turnover does
+  void set_change_tracts(uint64_t max_samples);
+  uint64_t change_tracts_max() const { return tracts_max_; }
+  void reset_change_tracts();
+  void accumulate_change_tracts();
+  void download_change_tracts_part(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum,
+                                   std::vector<uint64_t> &edges, uint32_t &n_branches, uint64_t &n_samples);
+  void download_change_tracts(std::vector<uint64_t> &hist, std::vector<uint64_t> &len_sum, uint32_t &n_branches,
+                              uint64_t &n_samples);
   // spatial correlations (epv_set_spatial_correlation) on every context, with the domain turnover's samples and
   // lifecycle; max_lag = 0 is off.  n_rows = 2 n_nodes - 1.  download_spatial_correlation_part: the parts of all
   // slots and contexts of this process merged in genome order (epv::corr_parts_merge), unclosed: n11 [R][L + 1],
@@ -329,6 +342,7 @@ private:
   bool origins_ = false;      // set_lineage_origins
   uint64_t domains_max_ = 0; // set_domain_stats
   uint64_t turnover_max_ = 0; // set_domain_turnover
+  uint64_t tracts_max_ = 0;   // set_change_tracts
   uint32_t corr_lag_ = 0;     // set_spatial_correlation
   uint64_t corr_max_ = 0;
   std::vector<uint32_t> dmaps_sizes_;   // set_domain_maps

@@ -29,6 +29,8 @@ DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_des
                   "epvd_domain_part_sizes", "epvd_download_domain_part", "epvd_download_domain_stats",
                   "epvd_set_turnover", "epvd_reset_turnover", "epvd_accumulate_turnover",
                   "epvd_turnover_part_sizes", "epvd_download_turnover_part", "epvd_download_turnover",
+                  "epvd_set_tracts", "epvd_reset_tracts", "epvd_accumulate_tracts",
+                  "epvd_tracts_part_sizes", "epvd_download_tracts_part", "epvd_download_tracts",
                   "epvd_set_corr", "epvd_reset_corr", "epvd_accumulate_corr",
                   "epvd_corr_part_sizes", "epvd_download_corr_part", "epvd_download_corr",
                   "epvd_set_dmaps", "epvd_reset_dmaps", "epvd_accumulate_dmaps", "epvd_dmaps_sizes", "epvd_download_dmaps",
@@ -106,6 +108,12 @@ def lib():
         L.epvd_turnover_part_sizes.argtypes = [vp, u32p, u64p]
         L.epvd_download_turnover_part.argtypes = [vp, u64p, u64p, u64p]
         L.epvd_download_turnover.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
+        L.epvd_set_tracts.argtypes = [vp, C.c_uint64]
+        L.epvd_reset_tracts.argtypes = [vp]
+        L.epvd_accumulate_tracts.argtypes = [vp]
+        L.epvd_tracts_part_sizes.argtypes = [vp, u32p, u64p]
+        L.epvd_download_tracts_part.argtypes = [vp, u64p, u64p, u64p]
+        L.epvd_download_tracts.argtypes = [vp, C.c_uint32, u64p, u64p, u64p]
         L.epvd_set_corr.argtypes = [vp, C.c_uint32, C.c_uint64]
         L.epvd_reset_corr.argtypes = [vp]
         L.epvd_accumulate_corr.argtypes = [vp]
@@ -516,6 +524,36 @@ class CppSampler:
         R = 2 * self.B
         hist, len_sum, ns = np.zeros((R, 2, 2, 128), np.uint64), np.zeros((R, 2, 2), np.uint64), C.c_uint64(0)
         self._ck(self.L.epvd_download_turnover(self.h, R, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
+        return int(ns.value), hist, len_sum
+
+    def enable_change_tracts(self, max_samples):
+        """change tracts on every context, for at most max_samples samples (0 = off); kept across reset()"""
+        self._ck(self.L.epvd_set_tracts(self.h, int(max_samples)))
+
+    def reset_change_tracts(self):
+        self._ck(self.L.epvd_reset_tracts(self.h))
+
+    def accumulate_change_tracts(self):
+        self._ck(self.L.epvd_accumulate_tracts(self.h))
+
+    def change_tracts_part(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27], edges [samples, B, 2]), uint64: the parts of the slots and
+        contexts of this process merged in genome order, unclosed"""
+        B, ns = C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.L.epvd_tracts_part_sizes(self.h, C.byref(B), C.byref(ns)))
+        B, ns = int(B.value), int(ns.value)
+        hist, len_sum = np.zeros((max(B, 1), 27, 128), np.uint64), np.zeros((max(B, 1), 27), np.uint64)
+        edges = np.zeros((max(ns, 1), max(B, 1), 2), np.uint64)
+        self._ck(self.L.epvd_download_tracts_part(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64),
+                                                  _p(edges.reshape(-1)[:max(ns * B * 2, 1)], C.c_uint64)))
+        return ns, hist[:B], len_sum[:B], edges.reshape(-1)[:ns * B * 2].reshape(ns, B, 2)
+
+    def change_tracts(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27]): the closed result over the genome (one slot per process:
+        an error; merge the processes' change_tracts_part with host.tract_parts_merge, then host.tract_part_close)"""
+        B = self.B
+        hist, len_sum, ns = np.zeros((B, 27, 128), np.uint64), np.zeros((B, 27), np.uint64), C.c_uint64(0)
+        self._ck(self.L.epvd_download_tracts(self.h, B, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), C.byref(ns)))
         return int(ns.value), hist, len_sum
 
     def enable_domain_maps(self, sizes, state=1, max_samples=1 << 21):

@@ -93,6 +93,17 @@ def lib():
         L.epvh_domain_turnover_copy.restype = None
         L.epvh_domain_turnover_free.argtypes = [C.c_void_p]
         L.epvh_domain_turnover_free.restype = None
+        L.epvh_tract_parts_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, u64pp, u64pp, u64pp, u64p, u64p, u64p]
+        L.epvh_tract_part_close.argtypes = [C.c_uint32, C.c_uint64, u64p, u64p, u64p]
+        L.epvh_write_change_tracts.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, u64p, u64p]
+        L.epvh_read_change_tracts.argtypes = [C.c_char_p]
+        L.epvh_read_change_tracts.restype = C.c_void_p
+        L.epvh_change_tracts_dims.argtypes = [C.c_void_p, u64p, u64p, u64p]
+        L.epvh_change_tracts_dims.restype = None
+        L.epvh_change_tracts_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_int, u64p, u64p]
+        L.epvh_change_tracts_copy.restype = None
+        L.epvh_change_tracts_free.argtypes = [C.c_void_p]
+        L.epvh_change_tracts_free.restype = None
         L.epvh_corr_parts_merge.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64pp, u64pp, u64p, u64p,
                                             u64p]
         L.epvh_corr_part_close.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p]
@@ -652,6 +663,116 @@ def read_domain_turnover(path):
                     len_sum=len_sum)
     finally:
         L.epvh_domain_turnover_free(h)
+
+
+# ---- change tracts (per branch, the maximal runs of changed sites by direction and flanks)
+TRACT_CLASSES = 27     # EPV_TRACT_CLASSES: direction * 9 + left * 3 + right; direction gain, loss, mixed; flank 0, 1, none
+TRACT_DIRECTIONS = ("gain", "loss", "mixed")
+
+
+def tract_parts_merge(parts):
+    """parts: [(hist [B, 27, 128], len_sum [B, 27], edges [samples, B, 2])] of adjacent stretches of sites in genome
+    order, of the same samples -> the part of their union (uint64 arrays of the same shapes)"""
+    if not parts:
+        raise ValueError("no parts")
+    hists = [np.ascontiguousarray(p[0], np.uint64) for p in parts]
+    sums = [np.ascontiguousarray(p[1], np.uint64) for p in parts]
+    edges = [np.ascontiguousarray(p[2], np.uint64) for p in parts]
+    B, ns = hists[0].shape[0], edges[0].shape[0]
+    for h, l, e in zip(hists, sums, edges):
+        if h.shape != (B, TRACT_CLASSES, DOMAIN_BINS) or l.shape != (B, TRACT_CLASSES) or e.shape != (ns, B, 2):
+            raise ValueError("a part is hist [B, 27, 128], len_sum [B, 27], edges [samples, B, 2] of the same B and "
+                             "samples")
+    hist, len_sum = np.zeros((B, TRACT_CLASSES, DOMAIN_BINS), np.uint64), np.zeros((B, TRACT_CLASSES), np.uint64)
+    out = np.zeros((ns, B, 2), np.uint64)
+    o = out if out.size else np.zeros(1, np.uint64)
+    if lib().epvh_tract_parts_merge(len(parts), B, ns, _ptrs(hists), _ptrs(sums),
+                                    _ptrs([e if e.size else np.zeros(1, np.uint64) for e in edges]),
+                                    _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(o, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum, out
+
+
+def tract_part_close(hist, len_sum, edges):
+    """a part -> the result (hist [B, 27, 128], len_sum [B, 27]): the tracts still open at the two ends are binned
+    with flank 2 (none), a whole record once"""
+    hist, len_sum = np.array(hist, np.uint64), np.array(len_sum, np.uint64)
+    edges = np.ascontiguousarray(edges, np.uint64)
+    B, ns = hist.shape[0], edges.shape[0]
+    if hist.shape != (B, TRACT_CLASSES, DOMAIN_BINS) or len_sum.shape != (B, TRACT_CLASSES) or edges.shape != (ns, B, 2):
+        raise ValueError("a part is hist [B, 27, 128], len_sum [B, 27], edges [samples, B, 2]")
+    e = edges if edges.size else np.zeros(1, np.uint64)
+    h, l = (hist, len_sum) if B else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+    if lib().epvh_tract_part_close(B, ns, _p(h, C.c_uint64), _p(l, C.c_uint64), _p(e, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+    return hist, len_sum
+
+
+# the events of change_tract_summary: name -> (direction, left flank, right flank).  A gained tract left of a kept
+# domain (flanks 0 | 1) grew that domain at its left edge; a lost tract with flanks 0 | 1 took the left edge of the
+# domain to its right
+TRACT_EVENTS = {"born": (0, 0, 0), "filled": (0, 1, 1), "grew_left": (0, 0, 1), "grew_right": (0, 1, 0),
+                "died": (1, 0, 0), "split": (1, 1, 1), "shrank_left": (1, 0, 1), "shrank_right": (1, 1, 0)}
+
+
+def change_tract_summary(samples, hist, len_sum, tree):
+    """a closed result -> dict of float64 [B] arrays, per branch b (child node b + 1) and per sample: born, died,
+    filled, split (gain or loss between flanks 0 | 0 or 1 | 1), grew_left, grew_right, shrank_left, shrank_right (the
+    edge of the kept domain that moved), mixed (both directions in one tract, both flanks present) and open (a tract
+    at a genome end, any direction); <name>_size = the mean length of each (nan where there is none); and
+    net_edge_sites = the sites per sample that kept domains gained at their edges: grew sites - shrank sites"""
+    hist, len_sum = np.asarray(hist, np.uint64), np.asarray(len_sum, np.uint64)
+    B = tree.n_nodes - 1
+    if hist.shape != (B, TRACT_CLASSES, DOMAIN_BINS) or len_sum.shape != (B, TRACT_CLASSES):
+        raise ValueError("hist is [B, 27, 128], len_sum [B, 27] of the tree's B branches")
+    tracts = hist.sum(axis=2, dtype=np.uint64).astype(np.float64).reshape(B, 3, 3, 3)   # [b, direction, left, right]
+    sites = len_sum.astype(np.float64).reshape(B, 3, 3, 3)
+    ns = float(samples)
+    groups = {name: [key] for name, key in TRACT_EVENTS.items()}
+    groups["mixed"] = [(2, l, r) for l in (0, 1) for r in (0, 1)]
+    groups["open"] = [(d, l, r) for d in range(3) for l in range(3) for r in range(3) if l == 2 or r == 2]
+    out, total = {}, {}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for name, keys in groups.items():
+            count = sum(tracts[:, d, l, r] for d, l, r in keys)
+            total[name] = sum(sites[:, d, l, r] for d, l, r in keys)
+            out[name] = count / ns
+            out[name + "_size"] = total[name] / count
+        out["net_edge_sites"] = (total["grew_left"] + total["grew_right"] - total["shrank_left"] - total["shrank_right"]) / ns
+    return out
+
+
+def write_change_tracts(path, branch_names, samples, hist, len_sum):
+    """the file of epievo_est_histories -X: the closed result, integers only; branch_names = the child node's name
+    of every branch"""
+    hist, len_sum = np.ascontiguousarray(hist, np.uint64), np.ascontiguousarray(len_sum, np.uint64)
+    B = len(branch_names)
+    if hist.shape != (B, TRACT_CLASSES, DOMAIN_BINS) or len_sum.shape != (B, TRACT_CLASSES):
+        raise ValueError("hist is [branches, 27, 128], len_sum [branches, 27]")
+    a, b = (hist, len_sum) if B else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+    if lib().epvh_write_change_tracts(path.encode(), "\n".join(branch_names).encode(), int(samples),
+                                      _p(a, C.c_uint64), _p(b, C.c_uint64)):
+        raise RuntimeError(lib().epvh_last_error().decode())
+
+
+def read_change_tracts(path):
+    """-> dict(samples, branch_names, hist uint64 [B, 27, 128], len_sum uint64 [B, 27])"""
+    L = lib()
+    h = L.epvh_read_change_tracts(path.encode())
+    if not h:
+        raise RuntimeError(L.epvh_last_error().decode())
+    try:
+        ns, B, ln = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.epvh_change_tracts_dims(h, C.byref(ns), C.byref(B), C.byref(ln))
+        B = int(B.value)
+        buf = C.create_string_buffer(int(ln.value))
+        hist, len_sum = np.zeros((B, TRACT_CLASSES, DOMAIN_BINS), np.uint64), np.zeros((B, TRACT_CLASSES), np.uint64)
+        a, b = (hist, len_sum) if B else (np.zeros(1, np.uint64), np.zeros(1, np.uint64))
+        L.epvh_change_tracts_copy(h, buf, len(buf), _p(a, C.c_uint64), _p(b, C.c_uint64))
+        return dict(samples=int(ns.value), branch_names=buf.value.decode().split("\n") if B else [], hist=hist,
+                    len_sum=len_sum)
+    finally:
+        L.epvh_change_tracts_free(h)
 
 
 # ---- spatial correlations (two-point counts of node states and branch changes along the genome)

@@ -34,7 +34,7 @@ import numpy as np
 from . import host
 from .host import FlatPaths
 from .sampler import DeviceSampler, forward_to_dev
-from .summaries import LAYERS, LIFECYCLE, NOUN, _per_sample, _window_range, summary_method
+from .summaries import CHAIN, LIFECYCLE, NOUN, _per_sample, _window_range, summary_method
 
 BLOCK = 256      # sites per block: halo widths and shard_cuts' cut points are whole blocks
 TAIL = 1         # int64 words after a rank's counts in the all-gather: its accept count
@@ -523,6 +523,18 @@ class ShardedSampler:
         ns, _, c, _ = self.domain_maps_part()
         return ns, _per_sample(c, ns, counts)
 
+    def change_tracts_part(self):
+        """-> (samples, hist, len_sum, edges): the part of the whole genome, identical on every rank: the sample
+        counts are compared first (a part's size depends on them), then the ranks' parts are all-gathered and
+        merged in genome order"""
+        ns, *part = self.dev.change_tracts_part()
+        return (ns,) + self._gather_parts(ns, part, NOUN["change_tracts"], host.tract_parts_merge)
+
+    def change_tracts(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27]) of the whole genome, closed; every rank merges and closes"""
+        ns, hist, len_sum, edges = self.change_tracts_part()
+        return (ns,) + host.tract_part_close(hist, len_sum, edges)
+
     def mixing(self, counts=False):
         """-> DeviceSampler.mixing of the whole genome, identical on every rank: the ranks' rows are all-gathered
         (one collective) and concatenated in genome order (a 64-bit cell travels as two words); the ranks' pair
@@ -552,7 +564,7 @@ class ShardedSampler:
 forward_to_dev(ShardedSampler, LIFECYCLE + [
     "set_model", "scale_jump_times", "window_stats_scale_exps", "lineage_origins_layout", "lineage_origin_rows",
     "lineage_origins_scale_exp", "domain_stats_layout", "domain_turnover_layout", "spatial_correlation_layout",
-    "mixing_layout", "domain_maps_layout"])
+    "mixing_layout", "domain_maps_layout", "change_tracts_layout"])
 
 
 class LocalGroup:
@@ -989,6 +1001,22 @@ class LocalGroup:
         ns, _, c, _ = self.domain_maps_part()
         return ns, _per_sample(c, ns, counts)
 
+    # change tracts: a shard's part is that of the sites it owns
+    def change_tracts_layout(self):
+        """(branches B, classes, bins, first local site of the first shard, sites over all shards, sites per block)"""
+        lay = self._each_call("change_tracts_layout")
+        return lay[0][:4] + (sum(v[4] for v in lay),) + lay[0][5:]
+
+    def change_tracts_part(self):
+        """-> (samples, hist, len_sum, edges): the shards' parts merged in genome order, unclosed"""
+        ns, parts = self._parts("change_tracts", "change_tracts_part")
+        return (ns,) + self._merged(parts, host.tract_parts_merge)
+
+    def change_tracts(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27]) over the group's owned sites, closed"""
+        ns, hist, len_sum, edges = self.change_tracts_part()
+        return (ns,) + host.tract_part_close(hist, len_sum, edges)
+
     # chain mixing diagnostics: rows by site; the shards ran the same runs, so their pair counts agree
     def mixing_layout(self):
         """(first local site of the first shard, sites over all shards, max_lag)"""
@@ -1074,7 +1102,7 @@ def _enable_on_every_shard(name):
     return method
 
 
-for _s in LAYERS:
+for _s in CHAIN:
     if "enable_" + _s.stem not in vars(LocalGroup):
         setattr(LocalGroup, "enable_" + _s.stem, _enable_on_every_shard("enable_" + _s.stem))
     setattr(LocalGroup, "reset_" + _s.stem, summary_method(LocalGroup._reset_summary, _s, "reset_" + _s.stem))

@@ -14,7 +14,7 @@ import numpy as np
 from . import _build
 from . import host
 from .host import FlatPaths
-from .summaries import LAYERS, LIFECYCLE, _per_sample, _window_range, summary_method
+from .summaries import CHAIN, LIFECYCLE, _per_sample, _window_range, summary_method
 
 _lib = None
 
@@ -79,7 +79,7 @@ def _abi():
         "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
         "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
         "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
-        # the summaries: what is particular to each (the four lifecycle entry points of each follow from LAYERS)
+        # the summaries: what is particular to each (the four lifecycle entry points of each follow from CHAIN)
         "epv_get_path_average": [vp, u64, u64, u32p], "epv_path_average_layout": [vp, u32p, u64p, u64p],
         "epv_branch_events_set_samples": [vp, u64], "epv_branch_events_layout": [vp, u64p, u64p],
         "epv_get_branch_events": [vp, u64, u64, u32p], "epv_get_branch_event_windows": [vp, u64, u64, u64, u64p],
@@ -102,12 +102,13 @@ def _abi():
         "epv_mixing_layout": [vp, u64p, u64p, u32p], "epv_mixing_pairs": [vp, u64p],
         "epv_mixing_counts": [vp, u64, u64, u32p, u64p], "epv_mixing_windows": [vp, u64, u64, u64, u64p],
         "epv_domain_maps_layout": [vp, u32p, u32p, u32p, u32p, u64p, u64p, u64p], "epv_get_domain_maps": [vp, u32p, u64p],
+        "epv_change_tracts_layout": [vp, u32p, u32p, u32p, u64p, u64p, u64p], "epv_get_change_tracts": [vp, u64p, u64p, u64p],
     }
     # epv_set_<stem>: what switches the summary on, after the context
     set_args = {"path_average": [u32], "branch_events": [i], "window_stats": [u64], "epoch_stats": [u32],
                 "lineage_origins": [i], "domain_stats": [u64], "change_patterns": [i], "domain_turnover": [u64],
-                "spatial_correlation": [u32, u64], "mixing": [u32], "domain_maps": [u32, u32p, u32, u64]}
-    for s in LAYERS:
+                "spatial_correlation": [u32, u64], "mixing": [u32], "domain_maps": [u32, u32p, u32, u64], "change_tracts": [u64]}
+    for s in CHAIN:
         args["epv_set_" + s.stem] = [vp] + set_args[s.stem]
         args["epv_reset_" + s.stem] = args["epv_accumulate_" + s.stem] = [vp]
         args["epv_%s_samples" % s.stem] = [vp, u64p]
@@ -864,6 +865,40 @@ class DeviceSampler:
         ns, hist, len_sum, edges = self.domain_turnover_part()
         return (ns,) + host.turnover_part_close(hist, len_sum, edges)
 
+    # ---- change tracts (epv_set_change_tracts)
+    def enable_change_tracts(self, max_samples):
+        """count, per branch, the maximal runs of sites with a net change (tracts) by direction (gain, loss, mixed),
+        by the state of the unchanged site on each flank and by length, after every batch sweep of run_mcmc, for at
+        most max_samples samples (0 = off)"""
+        self._ck(self.L.epv_set_change_tracts(self.h, int(max_samples)))
+
+    def change_tracts_layout(self):
+        """(branches B, classes, bins, first local site, number of sites, sites per block of the tract kernel); zeros
+        when off"""
+        nb, nc, nbin, a, k, cs = (C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0),
+                                  C.c_uint64(0))
+        self._ck(self.L.epv_change_tracts_layout(self.h, C.byref(nb), C.byref(nc), C.byref(nbin), C.byref(a), C.byref(k),
+                                                 C.byref(cs)))
+        return int(nb.value), int(nc.value), int(nbin.value), int(a.value), int(k.value), int(cs.value)
+
+    def change_tracts_part(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27], edges [samples, B, 2]), uint64: what this context's
+        stretch of sites contributes, unclosed (host.tract_parts_merge, host.tract_part_close)"""
+        ns = self.change_tracts_samples()
+        B, nc, nb = self.change_tracts_layout()[:3]
+        nc = nc or host.TRACT_CLASSES
+        hist = np.zeros((max(B, 1), nc, max(nb, 1)), np.uint64)
+        len_sum = np.zeros((max(B, 1), nc), np.uint64)
+        edges = np.zeros((max(ns, 1), max(B, 1), 2), np.uint64)
+        self._ck(self.L.epv_get_change_tracts(self.h, _p(hist, C.c_uint64), _p(len_sum, C.c_uint64), _p(edges, C.c_uint64)))
+        return ns, hist[:B], len_sum[:B], edges[:ns, :B]
+
+    def change_tracts(self):
+        """-> (samples, hist [B, 27, 128], len_sum [B, 27]): the closed result over this context's sites; class =
+        direction * 9 + left * 3 + right (host.change_tract_summary)"""
+        ns, hist, len_sum, edges = self.change_tracts_part()
+        return (ns,) + host.tract_part_close(hist, len_sum, edges)
+
     # ---- spatial correlations (epv_set_spatial_correlation)
     def enable_spatial_correlation(self, max_lag, max_samples):
         """count, per node state row and branch change row, the site pairs (p, p + d) that are both 1 for every lag
@@ -1008,7 +1043,7 @@ class DeviceSampler:
         return int(words[0]), int(words[1]), out
 
 
-for _s in LAYERS:
+for _s in CHAIN:
     setattr(DeviceSampler, "reset_" + _s.stem, summary_method(DeviceSampler._reset_summary, _s, "reset_" + _s.stem))
     setattr(DeviceSampler, "accumulate_" + _s.stem,
             summary_method(DeviceSampler._accumulate_summary, _s, "accumulate_" + _s.stem,
@@ -1120,4 +1155,5 @@ forward_to_dev(SingleSiteSampler, LIFECYCLE + [
     "lineage_origin_windows", "domain_stats_layout", "domain_stats_part", "domain_stats", "change_patterns_layout",
     "change_patterns", "change_pattern_windows", "domain_turnover_layout", "domain_turnover_part", "domain_turnover",
     "spatial_correlation_layout", "spatial_correlation_part", "spatial_correlation", "mixing_layout", "mixing",
-    "mixing_windows", "domain_maps_layout", "domain_maps_part", "domain_maps"])
+    "mixing_windows", "domain_maps_layout", "domain_maps_part", "domain_maps", "change_tracts_layout",
+    "change_tracts_part", "change_tracts"])

@@ -30,9 +30,16 @@ LATER_SUMMARIES = (
     Summary("domain_maps", "a", "domain-map"),
 )
 LAYERS = SUMMARIES + DIAGNOSTICS + LATER_SUMMARIES
-NOUN = {s.stem: s.noun for s in LAYERS}
+# summaries that joined the chain after those: a fourth table, because the three above and their sum LAYERS are
+# what they were when tests recorded them.  CHAIN is every entry of kLayers in its order; what loops over "every
+# layer" loops over CHAIN
+TRACT_SUMMARIES = (
+    Summary("change_tracts", "a", "change-tract"),
+)
+CHAIN = LAYERS + TRACT_SUMMARIES
+NOUN = {s.stem: s.noun for s in CHAIN}
 # the four methods every sampler has for every summary and diagnostic
-LIFECYCLE = [fmt % s.stem for s in LAYERS for fmt in ("enable_%s", "reset_%s", "accumulate_%s", "%s_samples")]
+LIFECYCLE = [fmt % s.stem for s in CHAIN for fmt in ("enable_%s", "reset_%s", "accumulate_%s", "%s_samples")]
 
 
 def summary_method(helper, row, name, doc=None):

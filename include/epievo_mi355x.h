@@ -906,6 +906,45 @@ int epv_domain_maps_layout(epv_ctx *ctx, uint32_t *n_nodes, uint32_t *n_sizes, u
                            uint64_t *first, uint64_t *count, uint64_t *chunk_sites);
 int epv_get_domain_maps(epv_ctx *ctx, uint32_t *counts, uint64_t *edges);
 
+/* ---- change tracts (new): what the net changes on a branch did to the domains, and how many sites each event
+ * took.  Per branch b (child node b + 1) and counted site: c = k & 1 the net change, y = a XOR (k & 1) the end state
+ * (a = init state, k = jumps of the branch at the site; the start state is y ^ c).  A TRACT is a maximal run of
+ * sites with c = 1.  Its direction is 0 = gain (every y = 1), 1 = loss (every y = 0), 2 = mixed; its left and right
+ * flanks are y of the unchanged site before and after it, 2 = none where the tract touches the genome's first or
+ * last counted site.  class = direction * 9 + left * 3 + right (27 classes): a gain between flanks 0 | 0 is a domain
+ * born, between 0 | 1 or 1 | 0 a domain that grew by exactly that many sites at one edge, between 1 | 1 a gap
+ * filled; losses are death (0 | 0), shrinkage and a split (1 | 1).  The length goes to the bins of the domain
+ * statistics (csrc/epv_domain_bin.h).  Only the 16-bit meta words are read.
+ * A context keeps a PART over its cnt sites (the sites of the domain turnover):
+ *   hist[B][27][128], len_sum[B][27] uint64: the tracts with an unchanged site on both sides inside the stretch,
+ *     summed over the samples
+ *   edge[sample][B][2] uint64: record 0 for the stretch's first site, record 1 for its last; the bits are in
+ *     csrc/epv_tract_rec.h (length of the tract that holds the site, the site's y, has-gain, has-loss, the flank
+ *     inside the stretch, "whole" when every site changed).  An empty stretch has both records 0
+ * Merge of adjacent parts in genome order: tracts joined across a cut add their lengths and OR their direction bits,
+ * take the left flank of the leftmost piece and the right flank of the rightmost; a tract that ends at a cut takes the
+ * neighbour's boundary y as its flank.  Close: the tracts still open at the two ends are binned with flank 2
+ * (epvh_tract_parts_merge, epvh_tract_part_close in libepv_host.so).  After close, len_sum over the classes of a
+ * branch is the number of its changed sites over the samples.
+ * Samples, sites and lifecycle are the domain turnover's; a changed site range or number of branches lays the part
+ * out again before the first sample and is EPV_ERR_STATE after it.  Off by default: nothing allocated, nothing
+ * launched.  J, D, accept counts, paths, tri_llh and the plan word do not depend on it.
+ * epv_set_change_tracts: max_samples >= 1 (at most 2^21) allocates 8 B (27 x 128 + 27) bytes of counts,
+ *   8 x 2 B ceil(cnt / 64) bytes of scratch and 16 B max_samples bytes of edge records (checked against the free
+ *   device memory first; the message gives the figure) and zeroes them; 0 frees everything.  A sample beyond
+ *   max_samples is EPV_ERR_STATE, and so is a run whose batch would pass it, refused before its first sweep.  At most
+ *   2^32 - 1 sites per context.
+ * epv_change_tracts_layout: branches B, classes, bins, the local sites first .. first+count-1 and the sites one block
+ *   of the tract kernel covers (zeros when off).
+ * epv_get_change_tracts: the context's part, unclosed; edges holds [samples][B][2]. */
+int epv_set_change_tracts(epv_ctx *ctx, uint64_t max_samples);
+int epv_reset_change_tracts(epv_ctx *ctx);
+int epv_accumulate_change_tracts(epv_ctx *ctx);
+int epv_change_tracts_samples(epv_ctx *ctx, uint64_t *n_samples);
+int epv_change_tracts_layout(epv_ctx *ctx, uint32_t *n_branches, uint32_t *n_classes, uint32_t *n_bins, uint64_t *first,
+                             uint64_t *count, uint64_t *chunk_sites);
+int epv_get_change_tracts(epv_ctx *ctx, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+
 /* ---- epoch statistics (new): J and D per branch and epoch of the branch -- WHEN inside a branch the
  * changes happened, and in which neighbour context.  The direct posterior check of rates that are constant
  * over the tree.  epv_set_epoch_stats(ctx, P), 1 <= P <= EPV_EPOCH_MAX_P (0 = off and free), keeps J[8] and

@@ -146,6 +146,19 @@ int epvd_turnover_part_sizes(epvd_sampler *s, uint32_t *n_rows, uint64_t *n_samp
 int epvd_download_turnover_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
 int epvd_download_turnover(epvd_sampler *s, uint32_t n_rows, uint64_t *hist, uint64_t *len_sum, uint64_t *n_samples);
 
+/* the change tracts per branch (epv_set_change_tracts on every context; max_samples = 0 is off; kept across
+ * epvd_reset, which starts them from zero).  The part of this process: the parts of its slots and contexts merged in
+ * genome order, unclosed -- sizes first (branches B and samples S), then the copy of hist[B][27][128], len_sum[B][27]
+ * and edges[S][B][2].  epvd_download_tracts: that part closed, into hist[n_branches][27][128] and
+ * len_sum[n_branches][27] (n_branches = the tree's branches); one slot per process: an error that names the part and
+ * the merge function, because one process's stretch is not the genome */
+int epvd_set_tracts(epvd_sampler *s, uint64_t max_samples);
+int epvd_reset_tracts(epvd_sampler *s);
+int epvd_accumulate_tracts(epvd_sampler *s);
+int epvd_tracts_part_sizes(epvd_sampler *s, uint32_t *n_branches, uint64_t *n_samples);
+int epvd_download_tracts_part(epvd_sampler *s, uint64_t *hist, uint64_t *len_sum, uint64_t *edges);
+int epvd_download_tracts(epvd_sampler *s, uint32_t n_branches, uint64_t *hist, uint64_t *len_sum, uint64_t *n_samples);
+
 /* spatial correlations (epv_set_spatial_correlation on every context; max_lag = 0 is off; kept across epvd_reset,
  * which starts them from zero).  The part of this process: the parts of its slots and contexts merged in genome
  * order, unclosed -- sizes first (rows R = N + B, max_lag L, samples S and the sites the part covers), then the copy
