@@ -33,6 +33,7 @@
 #include "epv_dmaps.h"
 #include "epv_tracts.h"
 #include "epv_patterns.h"
+#include "epv_regions.h"   // fixed sites: the guards around a colour phase, the statistics correction
 
 // ---- the state of the posterior summaries ("layers") of run_mcmc, one struct each.  Every member has a default:
 // a layer goes off by freeing its device buffers and taking a default-constructed struct (the *_off functions).
@@ -207,6 +208,14 @@ struct TractsState {
   uint64_t samples = 0;
 };
 
+// fixed sites (epv_set_fixed_sites; epv_regions.h).  Everything is empty while no site is fixed: no launch, no buffer
+struct FixedState {
+  std::vector<uint8_t> mask;     // the mask as set, n local columns
+  uint64_t *d_sites = nullptr;   // the fixed local sites among 1 .. n - 2, colour by colour
+  uint64_t off[4] = {0, 0, 0, 0};  // colour k: d_sites[off[k] .. off[k + 1])
+  EpvFixedSave save{};           // what the guard keeps over a phase, one slot per listed site
+};
+
 struct epv_ctx {
   int device = 0;
   EpvKnobs knobs;
@@ -293,6 +302,7 @@ struct epv_ctx {
   // evidence_cells > 0: the layout of epv_leaf_evidence (epv_kernels.h)
   uint32_t *d_evidence = nullptr;
   uint64_t evidence_cells = 0;
+  FixedState fx;
 };
 
 namespace {
@@ -325,6 +335,11 @@ struct DevTmp {
   T *release() { T *q = p; p = nullptr; return q; }
 };
 
+void fixed_off(epv_ctx *c) {
+  dfree(c->fx.d_sites); dfree(c->fx.save.sel); dfree(c->fx.save.tri);
+  c->fx = FixedState();
+}
+
 void free_paths(epv_ctx *c) {
   dfree(c->S.meta); dfree(c->S.jumps); dfree(c->S.sel); dfree(c->S.tri);
   dfree(c->S.prop_llr); dfree(c->S.prop_flag); dfree(c->S.prop_states); dfree(c->S.tasks); dfree(c->S.alist);
@@ -337,6 +352,7 @@ void free_paths(epv_ctx *c) {
   c->unobs_cells = 0;
   dfree(c->d_evidence);
   c->evidence_cells = 0;
+  fixed_off(c);
   c->have_paths = c->have_reset = false;
 }
 
@@ -544,6 +560,15 @@ int finish_stats(epv_ctx *c, uint64_t batch, int average, double *J, double *D) 
   return EPV_OK;
 }
 
+// the triples centred at fixed sites of the owned range, taken off the integer words at `tot` ([B][16]): a fixed site
+// is no centre (epv_regions.h).  Nothing is launched while no site is fixed
+void launch_fixed_unstat(epv_ctx *c, uint64_t own_lo, uint64_t own_hi, unsigned long long *tot) {
+  const uint64_t count = c->fx.off[3];
+  if (!count) return;
+  hipLaunchKernelGGL(epv_fixed_unstat_kernel, dim3((unsigned)((count * c->S.B + 63u) / 64u)), dim3(64), 0, c->stream, c->S,
+                     c->fx.d_sites, count, own_lo, own_hi, c->d_statscale, tot);
+}
+
 // integer J/D of the current paths over the owned range into d_sweep_tot[slot]
 int launch_suffstats(epv_ctx *c, uint64_t slot) {
   int rc = ensure_partials(c);
@@ -554,7 +579,9 @@ int launch_suffstats(epv_ctx *c, uint64_t slot) {
   owned_range(c, &own_lo, &own_hi);
   hipLaunchKernelGGL(epv_suffstat_kernel, dim3((unsigned)nb, (c->S.B + EPV_STAT_BCH - 1u) / EPV_STAT_BCH), dim3(256), 0,
                      c->stream, c->S, own_lo, own_hi, (uint64_t)0, c->d_statscale, (unsigned long long *)c->d_partial[0]);
-  return reduce_blocks_to_tot(c, c->d_partial[0], nb, 1u, slot);
+  if ((rc = reduce_blocks_to_tot(c, c->d_partial[0], nb, 1u, slot))) return rc;
+  launch_fixed_unstat(c, own_lo, own_hi, c->d_sweep_tot + slot * c->S.B * 16u);
+  return EPV_OK;
 }
 
 // ---- the posterior summaries of run_mcmc ("layers").  What the chain, the destructor and
@@ -1968,6 +1995,9 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
   a.s0 = a.first + ((a.colour + 3u - (uint32_t)((c->S.g0 + a.first) % 3u)) % 3u);
   a.blocks = (a.threads + c->shapes.v1.threads - 1u) / c->shapes.v1.threads;
   if (a.blocks == 0) return EPV_OK;
+  // the guard of the fixed sites of this colour (epv_regions.h): kept before the phase, put back after it
+  const uint64_t *fx_sites = c->fx.d_sites + c->fx.off[colour];
+  const uint64_t fx_count = c->fx.off[colour + 1] - c->fx.off[colour];
   hipEvent_t e0 = nullptr, e1 = nullptr;
   c->timing = c->timing_every && (c->timing_seen++ % c->timing_every) == 0u;
   if (c->timing) {
@@ -1982,6 +2012,11 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     HIP_TRY(c, hipEventRecord(e0, c->stream));
   }
   const PhasePlan P = phase_plan(c);
+  // (the second and third proposal kernel and the fused phase count a proposal equal to the current path themselves)
+  const uint32_t fx_ident = P.propose == EPV_PLAN_FUSED || P.propose == EPV_PLAN_V2 || P.propose == EPV_PLAN_V3 ? 1u : 0u;
+  if (fx_count)
+    hipLaunchKernelGGL(epv_fixed_save_kernel, dim3((unsigned)((fx_count + 63u) / 64u)), dim3(64), 0, c->stream, c->S,
+                       fx_sites, fx_count, c->fx.save, fx_ident);
   const uint32_t list_mode = P.listed ? 1u + (c->phase_parity & 1u) : 0u;   // (never with the fused phase)
   const int rc = P.propose == EPV_PLAN_FUSED ? launch_fused(c, P, a) : launch_propose(c, P, a, list_mode);
   if (rc) return rc;
@@ -1990,6 +2025,9 @@ int launch_phase(epv_ctx *c, int colour, uint64_t seed, uint32_t sweep) {
     launch_accept(c, P, a, list_mode);
   }
   if (c->timing) HIP_TRY(c, hipEventRecord(e1, c->stream));
+  if (fx_count)
+    hipLaunchKernelGGL(epv_fixed_restore_kernel, dim3((unsigned)((fx_count + 63u) / 64u)), dim3(64), 0, c->stream, c->S,
+                       fx_sites, fx_count, c->fx.save, a.first, a.last, a.own_lo, a.own_hi, fx_ident, c->d_counters);
   HIP_TRY(c, hipGetLastError());
   if (c->halo_mode) ++c->phases_used;
   return EPV_OK;
@@ -2041,6 +2079,25 @@ int layer_set_off(epv_ctx *c, const Layer &L) {
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   L.off(c);
+  return EPV_OK;
+}
+// ---- fixed sites and the layers.  Seven layers count triples or runs across neighbouring sites and are not cut at
+// fixed sites yet: they and the fixed sites refuse each other, each naming the other
+struct SpanningLayer {
+  const Layer *L;
+  const char *setter;
+};
+const SpanningLayer kSpanning[] = {{&kWstat, "epv_set_window_stats"},         {&kEpochs, "epv_set_epoch_stats"},
+                                   {&kDomains, "epv_set_domain_stats"},       {&kTurnover, "epv_set_domain_turnover"},
+                                   {&kTracts, "epv_set_change_tracts"},       {&kCorr, "epv_set_spatial_correlation"},
+                                   {&kDmaps, "epv_set_domain_maps"}};
+// what a spanning layer's setter begins with when it is told to switch the layer on
+int refuse_fixed(epv_ctx *c, const Layer &L) {
+  if (!c || c->fx.mask.empty()) return EPV_OK;
+  for (const SpanningLayer &sp : kSpanning)
+    if (sp.L == &L)
+      return fail(c, EPV_ERR_STATE, std::string(sp.setter) + ": fixed sites are held (epv_set_fixed_sites) and " + L.name +
+                                    " would count across them: clear the fixed sites first");
   return EPV_OK;
 }
 // a setter that has taken its arguments into the layer's state: lay out for the context as it is now
@@ -2788,6 +2845,61 @@ EPV_API int epv_unobserved_cells(epv_ctx *c, uint64_t *n_cells) {
   return EPV_OK;
 }
 
+// fixed sites (epv_regions.h): a byte per local column.  The lists of the guard are built
+// here, colour by colour ((g0 + site) % 3, as launch_phase colours the sites); columns 0 and n - 1 of a context are
+// never updated and centre no triple, so they are kept in the mask and left out of the lists
+EPV_API int epv_set_fixed_sites(epv_ctx *c, const uint8_t *mask) {
+  if (!c) return EPV_ERR_ARG;
+  if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_fixed_sites");
+  const uint64_t n = c->S.n;
+  bool any = false;
+  for (uint64_t s = 0; mask && s < n && !any; ++s) any = mask[s] != 0;
+  if (any)
+    for (const SpanningLayer &sp : kSpanning)
+      if (sp.L->on(c))
+        return fail(c, EPV_ERR_STATE, std::string("epv_set_fixed_sites: ") + sp.L->name + " would count across fixed sites: " +
+                                      "switch that layer off (" + sp.setter + " with 0) first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  fixed_off(c);
+  if (!any) return EPV_OK;   // nothing fixed: today's launches, no allocation
+  std::vector<uint64_t> sites;
+  uint64_t off[4] = {0, 0, 0, 0}, widest = 0;
+  for (uint32_t colour = 0; colour < 3; ++colour) {
+    for (uint64_t s = 1; s + 1 < n; ++s)
+      if (mask[s] && (c->S.g0 + s) % 3u == colour) sites.push_back(s);
+    off[colour + 1] = sites.size();
+    widest = std::max<uint64_t>(widest, off[colour + 1] - off[colour]);
+  }
+  DevTmp<uint64_t> d_sites;
+  DevTmp<uint32_t> d_sel;
+  DevTmp<double> d_tri;
+  if (!sites.empty()) {
+    HIP_TRY(c, d_sites.alloc(sites.size()));
+    HIP_TRY(c, d_sel.alloc(widest));
+    HIP_TRY(c, d_tri.alloc(3u * widest));
+    HIP_TRY(c, hipMemcpy(d_sites.p, sites.data(), sites.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  }
+  c->fx.mask.assign(mask, mask + n);
+  c->fx.d_sites = d_sites.release();
+  c->fx.save.sel = d_sel.release();
+  c->fx.save.tri = d_tri.release();
+  c->fx.save.cap = widest;
+  for (int k = 0; k < 4; ++k) c->fx.off[k] = off[k];
+  return EPV_OK;
+}
+
+// the fixed sites inside the owned range: what to take off the number of owned sites for an acceptance rate
+EPV_API int epv_fixed_sites(epv_ctx *c, uint64_t *n_fixed_updatable) {
+  if (!c || !n_fixed_updatable) return EPV_ERR_ARG;
+  *n_fixed_updatable = 0;
+  if (c->fx.mask.empty()) return EPV_OK;
+  uint64_t lo = 0, hi = 0;
+  owned_range(c, &lo, &hi);
+  for (uint64_t s = lo; s <= hi && s < c->fx.mask.size(); ++s) *n_fixed_updatable += c->fx.mask[s] != 0;
+  return EPV_OK;
+}
+
 EPV_API int epv_set_leaf_evidence(epv_ctx *c, const float *p_state1) {
   if (!c) return EPV_ERR_ARG;
   if (!c->have_paths) return fail(c, EPV_ERR_STATE, "paths must be resident before epv_set_leaf_evidence");
@@ -3379,6 +3491,7 @@ EPV_API int epv_run_mcmc_counts(epv_ctx *c, uint64_t burn_in, uint64_t batch, ui
   rc = run_chain(c, burn_in, batch, seed, sweep_base, [&](uint64_t w) {
     hipLaunchKernelGGL(epv_suffstat_wave_kernel, dim3((unsigned)(n_own * 4u), (c->S.B + EPV_STATW_BCH - 1u) / EPV_STATW_BCH),
                        dim3(64), 0, c->stream, c->S, own_lo, own_hi, blk_lo, c->d_statscale, rows + w * n_rows * V, n_rows);
+    launch_fixed_unstat(c, own_lo, own_hi, rows + w * n_rows * V);   // (off row 0 of the sweep: the rows are summed)
     return EPV_OK;
   });
   if (rc) return rc;
@@ -3978,6 +4091,7 @@ EPV_API int epv_get_change_pattern_windows(epv_ctx *c, uint64_t W, uint64_t firs
 // ---- regional sufficient statistics (epv_wstat.h)
 EPV_API int epv_set_window_stats(epv_ctx *c, uint64_t W) {
   if (!W) return layer_set_off(c, kWstat);
+  if (const int frc = refuse_fixed(c, kWstat)) return frc;
   const int rc = check_ready(c, false);
   if (rc) return rc;
   c->ws.W_asked = W;
@@ -4211,6 +4325,7 @@ EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t firs
 // ---- domain size spectra (epv_domains.h)
 EPV_API int epv_set_domain_stats(epv_ctx *c, uint64_t max_samples) {
   if (!max_samples) return layer_set_off(c, kDomains);
+  if (const int frc = refuse_fixed(c, kDomains)) return frc;
   if (max_samples > EPV_DOM_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^21 samples");
   const int rc = check_ready(c, false);
   if (rc) return rc;
@@ -4272,6 +4387,7 @@ EPV_API int epv_get_domain_stats(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, 
 // ---- domain turnover (epv_turnover.h)
 EPV_API int epv_set_domain_turnover(epv_ctx *c, uint64_t max_samples) {
   if (!max_samples) return layer_set_off(c, kTurnover);
+  if (const int frc = refuse_fixed(c, kTurnover)) return frc;
   if (max_samples > EPV_TURN_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "domain turnover takes at most 2^21 samples");
   const int rc = check_ready(c, false);
   if (rc) return rc;
@@ -4333,6 +4449,7 @@ EPV_API int epv_get_domain_turnover(epv_ctx *c, uint64_t *hist, uint64_t *len_su
 // ---- change tracts (epv_tracts.h)
 EPV_API int epv_set_change_tracts(epv_ctx *c, uint64_t max_samples) {
   if (!max_samples) return layer_set_off(c, kTracts);
+  if (const int frc = refuse_fixed(c, kTracts)) return frc;
   if (max_samples > EPV_TRACT_MAX_SAMPLES) return fail(c, EPV_ERR_ARG, "change tracts take at most 2^21 samples");
   const int rc = check_ready(c, false);
   if (rc) return rc;
@@ -4395,6 +4512,7 @@ EPV_API int epv_get_change_tracts(epv_ctx *c, uint64_t *hist, uint64_t *len_sum,
 // ---- spatial correlations (epv_corr.h)
 EPV_API int epv_set_spatial_correlation(epv_ctx *c, uint32_t max_lag, uint64_t max_samples) {
   if (!max_lag) return layer_set_off(c, kCorr);
+  if (const int frc = refuse_fixed(c, kCorr)) return frc;
   if (!c) return EPV_ERR_ARG;
   if (max_lag > EPV_CORR_MAX_LAG) return fail(c, EPV_ERR_ARG, "spatial correlations take lags up to 1024");
   if (!max_samples) return fail(c, EPV_ERR_ARG, "spatial correlations: max_samples is at least 1");
@@ -4457,6 +4575,7 @@ EPV_API int epv_get_spatial_correlation(epv_ctx *c, uint64_t *n11, uint64_t *edg
 // ---- domain maps (epv_dmaps.h)
 EPV_API int epv_set_domain_maps(epv_ctx *c, uint32_t n_sizes, const uint32_t *sizes, uint32_t state, uint64_t max_samples) {
   if (!n_sizes) return layer_set_off(c, kDmaps);
+  if (const int frc = refuse_fixed(c, kDmaps)) return frc;
   if (!c) return EPV_ERR_ARG;
   if (!sizes) return fail(c, EPV_ERR_ARG, "null sizes");
   if (n_sizes > EPV_DMAPS_MAX_SIZES) return fail(c, EPV_ERR_ARG, "domain maps take at most 4 sizes");
@@ -4554,6 +4673,7 @@ EPV_API int epv_window_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64
 // ---- epoch statistics (epv_epochs.h)
 EPV_API int epv_set_epoch_stats(epv_ctx *c, uint32_t P) {
   if (!P) return layer_set_off(c, kEpochs);
+  if (const int frc = refuse_fixed(c, kEpochs)) return frc;
   if (P > EPV_EPOCH_MAX_P) return fail(c, EPV_ERR_ARG, "epoch statistics take at most EPV_EPOCH_MAX_P = 256 epochs");
   if (!c) return EPV_ERR_ARG;
   if (!c->have_tree) return fail(c, EPV_ERR_STATE, "epv_set_tree must come first");

@@ -11,6 +11,10 @@
 // New: -l/--leaf-probs FILE: a file of the same shape with P(state 1) per leaf cell (N = 0.5): cells with a
 // probability strictly between 0 and 1 carry evidence (SingleSiteSampler::set_leaf_evidence) and are resampled;
 // 0 and 1 are data and must agree with the paths.  Not together with -m.
+// New: -G/--regions FILE: the chromosomes or gap-free stretches of the genome, `name n_sites` per line in the order of
+// the paths (epv::read_regions): their end sites are held fixed, so no update and no counted triple spans a break
+// (SingleSiteSampler::set_regions).  Not together with -r, -E, -d, -R, -X, -C or -D: those summaries count across
+// neighbouring sites and are not cut at breaks yet, and the library refuses them by name.
 // New: -c/--changes FILE with -w/--window W (default 1): the posterior branch-event maps of the B batch sweeps
 // (epv_set_branch_events: end state, net gain / loss, any change, gains, losses per branch and site), summed
 // over windows of W sites, as integers (epv::write_branch_events).  Changes nothing else the run writes.
@@ -80,7 +84,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false, direct_sampler = false, direct_fused = false, leaf_fast = false;
-    string outfile, tree_file, gpu_list, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes, tracts_file;
+    string outfile, tree_file, gpu_list, regions_file, average_file, missing_file, leaf_probs_file, changes_file, regional_file, origins_file, domains_file, epochs_file, patterns_file, turnover_file, corr_file, mixing_file, maps_file, maps_sizes, tracts_file;
     size_t batch = 10, burnin = 10, n_points = 100;
     const size_t no_epochs = std::numeric_limits<size_t>::max();
     size_t n_epochs = no_epochs;
@@ -110,6 +114,9 @@ int main(int argc, const char **argv) {
     opt_parse.add_opt("npoints", 'n', "number of time points per branch of the average", false, n_points);
     opt_parse.add_opt("missing", 'm', "states file whose N cells are missing leaf data: resampled, not pinned", false,
                       missing_file);
+    opt_parse.add_opt("regions", 'G', "regions file (name n_sites per line, in the order of the paths): the first and last "
+                      "site of every region are held fixed, no update and no counted triple spans a break", false,
+                      regions_file);
     opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell (N = 0.5): evidence, resampled; 0 and 1 are data",
                       false, leaf_probs_file);
     opt_parse.add_opt("changes", 'c', "output file of the branch-event maps of the batch sweeps (integer window sums)",
@@ -227,6 +234,12 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
       n_held_unobserved = n_unobserved;
     }
+    // genomic regions, likewise
+    vector<uint64_t> regions;
+    if (!regions_file.empty()) {
+      regions = epv::read_regions(regions_file, paths.n_sites);
+      if (VERBOSE) cerr << "[REGIONS: " << regions.size() << " OVER " << paths.n_sites << " SITES]" << endl;
+    }
     // leaf evidence, likewise
     vector<float> evidence;
     if (!leaf_probs_file.empty()) {
@@ -250,6 +263,7 @@ int main(int argc, const char **argv) {
                        (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u) | (leaf_fast ? (uint32_t)EPV_OPT_LEAF_FAST : 0u));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
+    if (!regions.empty()) mcmc.set_regions(std::move(regions));
     mcmc.reset(the_model, th, paths);
     if (VERBOSE) cerr << "[GPU LAYOUT: " << mcmc.layout() << "]" << endl;
     if (VERBOSE && (n_held_unobserved || n_held_evidence)) {

@@ -11,6 +11,9 @@
 // E-step instead of pinned (SingleSiteSampler::set_unobserved; kept across the iterations).
 // And: -l/--leaf-probs FILE -- P(state 1) per leaf cell in a file of the same shape (N = 0.5); cells strictly
 // between 0 and 1 carry evidence in every E-step (SingleSiteSampler::set_leaf_evidence).  Not together with -m.
+// And: -G/--regions FILE -- the chromosomes or gap-free stretches of the genome, `name n_sites` per line in the order
+// of the paths (epv::read_regions): their end sites are held fixed in every E-step, so no update and no counted
+// triple spans a break (SingleSiteSampler::set_regions; kept across the iterations).
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -40,7 +43,7 @@ static string strip_path(const string &full) {
 int main(int argc, const char **argv) {
   try {
     bool VERBOSE = false, single_branch = false, optimize_branches = false, direct_sampler = false, direct_fused = false, leaf_fast = false;
-    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file, leaf_probs_file;
+    string outfile, param_file_updated, tree_file, treefile_updated, gpu_list, missing_file, leaf_probs_file, regions_file;
     size_t iteration = 10, batch = 10, burnin = 10, paths_every = 1;
     size_t rng_seed = std::numeric_limits<size_t>::max();
     static const double param_tol = 1e-10;
@@ -72,6 +75,9 @@ int main(int argc, const char **argv) {
                       missing_file);
     opt_parse.add_opt("leaf-probs", 'l', "file of P(state 1) per leaf cell (N = 0.5): evidence, resampled; 0 and 1 are data",
                       false, leaf_probs_file);
+    opt_parse.add_opt("regions", 'G', "regions file (name n_sites per line, in the order of the paths): the first and last "
+                      "site of every region are held fixed, no update and no counted triple spans a break", false,
+                      regions_file);
     opt_parse.add_opt("paths-every", 'e', "write the paths file every k-th iteration and after the last (default 1: "
                       "every iteration, as the reference does)", false, paths_every);
     vector<string> leftover_args;
@@ -114,6 +120,12 @@ int main(int argc, const char **argv) {
       if (VERBOSE) cerr << "[UNOBSERVED LEAF CELLS: " << n_unobserved << " of " << n_leaf_cells << "]" << endl;
       n_held_unobserved = n_unobserved;
     }
+    // genomic regions, likewise
+    vector<uint64_t> regions;
+    if (!regions_file.empty()) {
+      regions = epv::read_regions(regions_file, paths.n_sites);
+      if (VERBOSE) cerr << "[REGIONS: " << regions.size() << " OVER " << paths.n_sites << " SITES]" << endl;
+    }
     // leaf evidence, likewise
     vector<float> evidence;
     if (!leaf_probs_file.empty()) {
@@ -149,6 +161,7 @@ int main(int argc, const char **argv) {
                        (direct_fused ? (uint32_t)EPV_OPT_DIRECT_FUSED : 0u) | (leaf_fast ? (uint32_t)EPV_OPT_LEAF_FAST : 0u));
     if (!unobserved.empty()) mcmc.set_unobserved(std::move(unobserved));   // (applied by the first reset)
     if (!evidence.empty()) mcmc.set_leaf_evidence(std::move(evidence));
+    if (!regions.empty()) mcmc.set_regions(std::move(regions));   // (kept across the iterations)
     // declared AFTER everything the thread references (and after the sampler): on an exception the
     // join runs first, while out_paths, out_branches and writer_error are still alive, and the file
     // of the last completed iteration is written out in full, as the synchronous reference leaves it

@@ -188,6 +188,14 @@ EPVD_API int epvd_set_unobserved(epvd_sampler *h, uint64_t n_sites, int n_nodes,
   });
 }
 
+EPVD_API int epvd_set_regions(epvd_sampler *h, uint64_t n_regions, const uint64_t *lengths) {
+  return guarded(h, [&] {
+    std::vector<uint64_t> m;
+    if (lengths) m.assign(lengths, lengths + n_regions);
+    h->s->set_regions(std::move(m));
+  });
+}
+
 EPVD_API int epvd_set_leaf_evidence(epvd_sampler *h, uint64_t n_sites, int n_nodes, const float *p_state1) {
   return guarded(h, [&] {
     std::vector<float> r;

@@ -504,6 +504,46 @@ void read_states_file_missing(const std::string &states_file, std::vector<std::s
   }
 }
 
+std::vector<uint64_t> read_regions(const std::string &regions_file, uint64_t n_sites) {
+  std::ifstream in(regions_file);
+  if (!in) throw std::runtime_error("cannot read regions file: " + regions_file);
+  std::vector<uint64_t> lengths;
+  uint64_t total = 0, line_no = 0, last = 0;
+  std::string line;
+  while (std::getline(in, line)) {
+    ++line_no;
+    std::istringstream is(line);
+    std::vector<std::string> fields;
+    for (std::string f; is >> f;) fields.push_back(f);
+    if (fields.empty() || fields[0][0] == '#') continue;
+    const std::string where = regions_file + ", line " + std::to_string(line_no) + ": ";
+    if (fields.size() != 2)
+      throw std::runtime_error(where + "a region is `name n_sites`, found " + std::to_string(fields.size()) + " fields");
+    long long m = 0;
+    size_t used = 0;
+    try {
+      m = std::stoll(fields[1], &used);
+    } catch (const std::exception &) {
+      used = 0;
+    }
+    if (used != fields[1].size() || used == 0)
+      throw std::runtime_error(where + "the number of sites of region " + fields[0] + " is not an integer: " + fields[1]);
+    if (m < 3)
+      throw std::runtime_error(where + "region " + fields[0] + " holds " + std::to_string(m) +
+                               " sites, a region holds at least 3");
+    total += (uint64_t)m;
+    if (total > n_sites)
+      throw std::runtime_error(where + "the regions up to " + fields[0] + " hold " + std::to_string(total) +
+                               " sites, the paths hold " + std::to_string(n_sites));
+    lengths.push_back((uint64_t)m);
+    last = line_no;
+  }
+  if (total != n_sites)
+    throw std::runtime_error(regions_file + ", line " + std::to_string(last) + ": the regions hold " + std::to_string(total) +
+                             " sites in all, the paths hold " + std::to_string(n_sites));
+  return lengths;
+}
+
 std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const Tree &th, const FlatPaths &paths,
                                            uint64_t &n_unobserved, uint64_t &n_leaf_cells) {
   std::vector<std::string> names;

@@ -212,6 +212,11 @@ void read_states_file_missing(const std::string &states_file, std::vector<std::s
 // site.  Throws, naming leaf and site, where an observed cell differs from the paths' leaf end state.
 std::vector<uint8_t> unobserved_leaf_cells(const std::string &states_file, const Tree &th, const FlatPaths &paths,
                                            uint64_t &n_unobserved, uint64_t &n_leaf_cells);
+// The regions file of a genome (-G; the chrom.sizes shape): one line per region, `name <whitespace> n_sites`, in
+// the order of the paths file; a line that starts with # is a comment, an empty line is skipped.  Every region
+// holds at least 3 sites and the lengths sum to n_sites.  -> the lengths (SingleSiteSampler::set_regions).  A
+// violation throws naming the line
+std::vector<uint64_t> read_regions(const std::string &regions_file, uint64_t n_sites);
 // a file of the same shape whose tokens are probabilities of state 1: a real number in [0, 1], or `N`/`n` for
 // no information (0.5).  probs[seq][site]; any other token is stored as +infinity
 void read_leaf_probs_file(const std::string &probs_file, std::vector<std::string> &names,

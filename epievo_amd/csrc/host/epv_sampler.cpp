@@ -1202,6 +1202,44 @@ void SingleSiteSampler::apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi) {
   check_on(c, epv_set_unobserved(c, win.data()), "epv_set_unobserved");
 }
 
+void SingleSiteSampler::set_regions(std::vector<uint64_t> lengths) {
+  regions_ = std::move(lengths);
+  if (!n_sites_) return;   // no paths yet: the reset that uploads them applies it
+  build_fixed(n_sites_);
+  if (!sharded()) {
+    apply_fixed(ctx_, 0, n_sites_);
+    return;
+  }
+  for (const Part &p : parts_) apply_fixed(p.ctx, p.lo, p.hi);
+}
+
+void SingleSiteSampler::build_fixed(uint64_t n) {
+  fixed_.clear();
+  n_fixed_ = 0;
+  if (regions_.empty()) return;
+  uint64_t total = 0;
+  for (size_t k = 0; k < regions_.size(); ++k) {
+    if (regions_[k] < 3)
+      throw std::runtime_error("region " + std::to_string(k) + " holds " + std::to_string(regions_[k]) +
+                               " sites, a region holds at least 3");
+    total += regions_[k];
+  }
+  if (total != n)
+    throw std::runtime_error("the regions hold " + std::to_string(total) + " sites in all, the paths hold " + std::to_string(n));
+  fixed_.assign(n, 0);
+  uint64_t a = 0;
+  for (uint64_t m : regions_) {
+    fixed_[a] = fixed_[a + m - 1] = 1;
+    a += m;
+  }
+  for (uint64_t s = 1; s + 1 < n; ++s) n_fixed_ += fixed_[s];
+}
+
+void SingleSiteSampler::apply_fixed(epv_ctx *c, uint64_t lo, uint64_t hi) {
+  check_on(c, epv_set_fixed_sites(c, fixed_.empty() ? nullptr : fixed_.data() + lo), "epv_set_fixed_sites");
+  (void)hi;
+}
+
 void SingleSiteSampler::set_leaf_evidence(std::vector<float> whole_genome) {
   bool any = false;
   for (float r : whole_genome) any = any || r == r;
@@ -1237,6 +1275,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
   if (!unobs_.empty() && unobs_.size() != (uint64_t)(th.n_nodes() - 1) * n)
     throw std::runtime_error("mask of unobserved cells: " + std::to_string(unobs_.size()) + " entries for " +
                              std::to_string(th.n_nodes() - 1) + " branches x " + std::to_string(n) + " sites");
+  build_fixed(n);   // (throws when the regions do not sum to this genome)
   n_nodes_ = th.n_nodes();
   n_sites_ = n;
   drop_parts();
@@ -1273,6 +1312,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
                            paths.jumps.data(), capacity_, 0), "epv_upload_paths");
     if (!unobs_.empty()) apply_unobserved(ctx_, 0, n);
     if (!evidence_.empty()) apply_leaf_evidence(ctx_, 0, n);
+    if (!fixed_.empty()) apply_fixed(ctx_, 0, n);
     return;
   }
   uint32_t cap = capacity_;
@@ -1327,6 +1367,7 @@ void SingleSiteSampler::build(const Tree &th, const FlatPaths &paths, uint64_t n
                                  part.jumps.empty() ? &dummy : part.jumps.data(), cap, q.lo), "epv_upload_paths");
     if (!unobs_.empty()) apply_unobserved(c, q.lo, q.hi);   // (its window of the genome, halos included)
     if (!evidence_.empty()) apply_leaf_evidence(c, q.lo, q.hi);
+    if (!fixed_.empty()) apply_fixed(c, q.lo, q.hi);
     check_on(c, epv_set_global_length(c, n), "epv_set_global_length");
   }
   if (rank_mode) {
@@ -1478,7 +1519,7 @@ void SingleSiteSampler::run_mcmc(uint64_t seed, uint64_t em_iteration,
     J[b].assign(Jf.begin() + (b - 1) * 8, Jf.begin() + b * 8);
     D[b].assign(Df.begin() + (b - 1) * 8, Df.begin() + b * 8);
   }
-  acceptance_rate = static_cast<double>(n_acc) / (batch * (n_sites_ - 2));
+  acceptance_rate = static_cast<double>(n_acc) / (batch * (n_sites_ - 2 - n_fixed_));
 }
 
 size_t SingleSiteSampler::sweeps(size_t n, uint64_t seed, uint32_t sweep_base) {

@@ -252,6 +252,14 @@ public:
   // genome site s is 1 | that cell's observation), NaN = none.  Stored, sliced, re-applied and length-checked
   // exactly as set_unobserved's mask; empty or all NaN = clear.
   void set_leaf_evidence(std::vector<float> whole_genome);
+  // genomic regions (chromosomes, gap-free stretches; epv_set_fixed_sites): their numbers of
+  // sites in the order of the genome, each at least 3, summing to the genome.  The first and the last site of every
+  // region are held fixed on every context -- each gets its window of the genome's mask, halos included -- so no
+  // update and no counted triple spans a break.  Kept, windowed and re-applied as set_unobserved's mask is (a
+  // reset(model, tree, paths) throws when the lengths do not sum to its genome); run_mcmc's acceptance rate is over
+  // the sites that can be updated.  Empty = clear.  The seven summaries that count across neighbouring sites
+  // refuse while regions are held, and regions refuse while one of them is on, with the library's message
+  void set_regions(std::vector<uint64_t> lengths);
   void set_timing(int every);
   void kernel_time_ms(double &avg_ms, uint64_t &n_launches);
   uint32_t phase_mode();
@@ -316,6 +324,8 @@ private:
   void refresh_parts();       // equal capacities, halo columns of every inner edge, fresh halo marks
   void apply_sample_root();
   void apply_unobserved(epv_ctx *c, uint64_t lo, uint64_t hi);   // unobs_ columns [lo, hi) of the genome
+  void build_fixed(uint64_t n);                                  // fixed_ of regions_ over a genome of n sites
+  void apply_fixed(epv_ctx *c, uint64_t lo, uint64_t hi);        // fixed_ columns [lo, hi) of the genome
   void apply_leaf_evidence(epv_ctx *c, uint64_t lo, uint64_t hi);   // evidence_ columns [lo, hi) of the genome
   void build(const Tree &th, const FlatPaths &paths, uint64_t n_global, bool rank_mode);
   std::vector<epv_ctx *> contexts() const;
@@ -352,6 +362,9 @@ private:
   uint32_t mixing_lag_ = 0;   // enable_mixing
   uint32_t options_ = 0;      // set_options: the word every context gets (its SAMPLE_ROOT bit follows SAMPLE_ROOT)
   std::vector<uint8_t> unobs_;   // set_unobserved: whole-genome mask of unobserved leaf cells, empty = none
+  std::vector<uint64_t> regions_;   // set_regions: the lengths, empty = one region
+  std::vector<uint8_t> fixed_;      // their end sites over the genome (built when the genome's length is known)
+  uint64_t n_fixed_ = 0;            // the fixed sites among 1 .. n - 2: not counted in the acceptance rate
   std::vector<float> evidence_;  // set_leaf_evidence: whole-genome table of leaf evidence, empty = none
   int n_nodes_ = 0;
   uint64_t n_sites_ = 0;      // genome length (all slots)

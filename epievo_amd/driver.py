@@ -17,7 +17,7 @@ vp, dp, u8p, u32p, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8
 DRIVER_SYMBOLS = ["epvd_create", "epvd_unique_id", "epvd_create_rank", "epvd_destroy", "epvd_last_error", "epvd_shard_cuts",
                   "epvd_reset", "epvd_reset_model", "epvd_run_mcmc", "epvd_scale_jump_times", "epvd_download_sizes",
                   "epvd_download", "epvd_layout", "epvd_set_options", "epvd_set_timing", "epvd_kernel_time_ms",
-                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average",
+                  "epvd_phase_mode", "epvd_set_unobserved", "epvd_set_leaf_evidence", "epvd_set_regions", "epvd_set_path_average", "epvd_path_average_sizes", "epvd_download_path_average",
                   "epvd_set_branch_events", "epvd_branch_events_sizes", "epvd_download_branch_events",
                   "epvd_download_branch_event_windows",
                   "epvd_set_window_stats", "epvd_window_stats_sizes", "epvd_download_window_stats",
@@ -67,6 +67,7 @@ def lib():
         L.epvd_phase_mode.argtypes = [vp, u32p]
         L.epvd_set_unobserved.argtypes = [vp, C.c_uint64, C.c_int, u8p]
         L.epvd_set_leaf_evidence.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_float)]
+        L.epvd_set_regions.argtypes = [vp, C.c_uint64, u64p]
         L.epvd_set_path_average.argtypes = [vp, C.c_uint32]
         L.epvd_path_average_sizes.argtypes = [vp, u64p, u32p, u64p]
         L.epvd_download_path_average.argtypes = [vp, u32p]
@@ -284,6 +285,17 @@ class CppSampler:
             r = r.reshape(self.B, -1)
         r = np.ascontiguousarray(r)
         self._ck(self.L.epvd_set_leaf_evidence(self.h, r.shape[1], r.shape[0] + 1, _p(r, C.c_float)))
+
+    def set_regions(self, lengths):
+        """genomic regions of the whole genome (epvd_set_regions): their numbers of sites in its order, each at least
+        3, summing to it (host.read_regions reads them from a file).  Their end sites are held fixed on every
+        context, and run_mcmc's acceptance rate is over the sites that can be updated.  Kept and applied as
+        set_unobserved's mask is; None clears."""
+        if lengths is None:
+            self._ck(self.L.epvd_set_regions(self.h, 0, None))
+            return
+        m = np.ascontiguousarray([int(x) for x in lengths], np.uint64)
+        self._ck(self.L.epvd_set_regions(self.h, len(m), _p(m, C.c_uint64)))
 
     def enable_path_average(self, n_points):
         """the average history of the sampled paths on every context (0 = off); kept across reset()"""

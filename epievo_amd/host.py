@@ -319,6 +319,55 @@ def write_paths(path_file, node_names, tot_times, fp):
         raise RuntimeError(lib().epvh_last_error().decode())
 
 
+def read_regions(path, n_sites):
+    """the regions file of a genome (the chrom.sizes shape): one line per region, `name <whitespace> n_sites`, in the
+    order of the paths file; a line that starts with # is a comment, an empty line is skipped.  Every region holds at
+    least 3 sites and the lengths sum to n_sites.  -> the list of lengths.  A violation raises ValueError naming the
+    line (the regions are the chromosomes, or the gap-free stretches of them, of SingleSiteSampler.set_regions)"""
+    lengths, total, last = [], 0, 0
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            fields = line.split()
+            if not fields or fields[0].startswith("#"):
+                continue
+            where = "%s, line %d" % (path, no)
+            if len(fields) != 2:
+                raise ValueError("%s: a region is `name n_sites`, found %d fields" % (where, len(fields)))
+            try:
+                m = int(fields[1])
+            except ValueError:
+                raise ValueError("%s: the number of sites of region %s is not an integer: %s"
+                                 % (where, fields[0], fields[1])) from None
+            if m < 3:
+                raise ValueError("%s: region %s holds %d sites, a region holds at least 3" % (where, fields[0], m))
+            total += m
+            if total > n_sites:
+                raise ValueError("%s: the regions up to %s hold %d sites, the paths hold %d"
+                                 % (where, fields[0], total, n_sites))
+            lengths.append(m)
+            last = no
+    if total != n_sites:
+        raise ValueError("%s, line %d: the regions hold %d sites in all, the paths hold %d"
+                         % (path, last, total, n_sites))
+    return lengths
+
+
+def region_fixed_mask(n_sites, lengths):
+    """uint8 [n_sites]: 1 at the first and the last site of every region (DeviceSampler.set_fixed_sites).  A region
+    of 3 sites has one site that is updated; two adjacent regions put two fixed sites side by side"""
+    lengths = [int(m) for m in lengths]
+    for k, m in enumerate(lengths):
+        if m < 3:
+            raise ValueError("region %d holds %d sites, a region holds at least 3" % (k, m))
+    if sum(lengths) != int(n_sites):
+        raise ValueError("the regions hold %d sites in all, the paths hold %d" % (sum(lengths), int(n_sites)))
+    mask = np.zeros(int(n_sites), np.uint8)
+    ends = np.cumsum(lengths)
+    mask[ends - np.asarray(lengths)] = 1
+    mask[ends - 1] = 1
+    return mask
+
+
 def m_step(model, tree_branches, J, D, optimize_branches=False):
     """The EM driver's M-step (est_params_histories.cpp:253-263).  Returns
     (new Model, new branches, llh, param-file text)."""

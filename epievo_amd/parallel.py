@@ -181,6 +181,21 @@ class ShardedSampler:
         self._halo_bufs, self._halo_bytes = None, 0
         self._piece = self._gathered = None
         self._piece_batch = 0
+        self._regions, self._n_fixed = None, 0
+
+    def set_regions(self, lengths):
+        """genomic regions of the whole genome (SingleSiteSampler.set_regions), the same on every rank: this rank's
+        engine gets the slice of the genome's mask of fixed sites for its local columns, halos included.  Kept and
+        applied again by setup(); None clears.  run_mcmc's acceptance rate counts the sites that can be updated"""
+        self._regions = None if lengths is None else [int(m) for m in lengths]
+        if not getattr(self, "n_loc", 0):
+            return
+        if self._regions is None:
+            self._n_fixed = 0
+            return self.dev.set_fixed_sites(None)
+        whole = host.region_fixed_mask(self.n_global, self._regions)
+        self._n_fixed = int(whole[1:-1].sum())
+        self.dev.set_fixed_sites(whole[self.g0:self.g0 + self.n_loc])
 
     def owned_sites(self):
         return self.n_own - (1 if self.comm.rank == 0 else 0) - \
@@ -223,6 +238,8 @@ class ShardedSampler:
         elif self.direct_sampler:
             self.dev.set_direct_sampler(True)
         self.dev.set_halo(left, right)
+        if getattr(self, "_regions", None) is not None:
+            self.set_regions(self._regions)
         self.refresh_halos()
 
     def _agree_on_capacity(self):
@@ -305,7 +322,7 @@ class ShardedSampler:
         pieces = self.dev.read(self._gathered, 0, words * self.comm.world, np.int64).reshape(self.comm.world, words)
         total = pieces.sum(axis=0, dtype=np.int64)
         J, D = self.dev.counts_to_stats(total[:-TAIL].reshape(batch, -1), batch, True)
-        return J, D, float(total[-TAIL]) / float(batch * (self.n_global - 2))
+        return J, D, float(total[-TAIL]) / float(batch * (self.n_global - 2 - getattr(self, "_n_fixed", 0)))
 
     # ---- the posterior summaries: every rank counts its owned columns, and a read-out of
     # the whole genome, identical on every rank, has one of three shapes across ranks: _gather_sites, _gather_sums,
@@ -654,6 +671,38 @@ class LocalGroup:
         self.n_sites = n
         self.halo_mode = False
         self.outer = (0, 0)     # the halos are set by set_halo() (ShardedSampler) or by reset()
+        self._g0, self._n_global = int(global_site_offset), int(n_global)
+        if getattr(self, "_regions", None) is not None:     # (new paths cleared the shards' masks)
+            self.set_regions(self._regions)
+
+    # ---- fixed sites and regions: every shard gets the slice of the mask for its local columns, halos included,
+    # so a halo column that its owner holds fixed is held fixed in the copy too
+    def set_fixed_sites(self, mask):
+        """as DeviceSampler.set_fixed_sites over the group's columns; None clears"""
+        if mask is None:
+            for s in self.subs:
+                s.set_fixed_sites(None)
+            return
+        m = (np.ascontiguousarray(mask).reshape(-1) != 0).astype(np.uint8)
+        if m.size != self.n_sites:
+            raise ValueError("mask of fixed sites: %d entries for %d sites" % (m.size, self.n_sites))
+        for j, s in enumerate(self.subs):
+            s.set_fixed_sites(m if len(self.subs) == 1 else m[self.lo[j]:self.hi[j]])
+
+    def fixed_sites(self):
+        """the fixed sites among those whose acceptances are counted: the shards' numbers added"""
+        return sum(s.fixed_sites() for s in self.subs)
+
+    def set_regions(self, lengths):
+        """genomic regions of the whole genome (SingleSiteSampler.set_regions): their end sites are held fixed.  Kept
+        and re-applied to new paths; None clears"""
+        self._regions = None if lengths is None else [int(m) for m in lengths]
+        if not self.n_sites:
+            return
+        if self._regions is None:
+            return self.set_fixed_sites(None)
+        whole = host.region_fixed_mask(self._n_global, self._regions)
+        self.set_fixed_sites(whole[self._g0:self._g0 + self.n_sites])
 
     # ---- halos
     def set_halo(self, left, right):

@@ -78,6 +78,7 @@ def _abi():
         "epv_direct_kat": [vp, u64, u32, u32p, dp, u32p, dp], "epv_direct_giveups": [vp, u64p],
         "epv_set_unobserved": [vp, u8p], "epv_unobserved_cells": [vp, u64p],
         "epv_set_leaf_evidence": [vp, fp], "epv_leaf_evidence_cells": [vp, u64p],
+        "epv_set_fixed_sites": [vp, u8p], "epv_fixed_sites": [vp, u64p],
         "epv_forward_simulate": [vp, u64, u8p, u64, u32, u64p], "epv_forward_last_ms": [vp, dp, dp],
         # the summaries: what is particular to each (the four lifecycle entry points of each follow from CHAIN)
         "epv_get_path_average": [vp, u64, u64, u32p], "epv_path_average_layout": [vp, u32p, u64p, u64p],
@@ -403,6 +404,24 @@ class DeviceSampler:
     def leaf_evidence_cells(self):
         """the number of leaf cells that hold evidence (epv_leaf_evidence_cells)"""
         return self._u64(self.L.epv_leaf_evidence_cells)
+
+    def set_fixed_sites(self, mask):
+        """fixed sites (epv_set_fixed_sites): mask[s] != 0 -> local site s is never changed by a colour phase, stays
+        context for its neighbours, centres no counted triple and is not counted in n_accepted.  One entry per local
+        column, halo columns included; None clears.  Regions are made of these (host.region_fixed_mask).  Uploading
+        paths clears the mask; the seven summaries that count across neighbouring sites and the mask refuse each other."""
+        if mask is None:
+            self._ck(self.L.epv_set_fixed_sites(self.h, None))
+            return
+        m = np.ascontiguousarray(mask).reshape(-1)
+        if m.size != self.n_sites:
+            raise ValueError("mask of fixed sites: %d entries for %d sites" % (m.size, self.n_sites))
+        m = (m != 0).astype(np.uint8)
+        self._ck(self.L.epv_set_fixed_sites(self.h, _p(m, C.c_uint8)))
+
+    def fixed_sites(self):
+        """the number of fixed sites among those whose acceptances are counted (epv_fixed_sites)"""
+        return self._u64(self.L.epv_fixed_sites)
 
     def capacity(self):
         v = C.c_uint32(0)
@@ -1091,6 +1110,7 @@ class SingleSiteSampler:
         self._uploaded = False
         self._unobserved = None       # the mask of unobserved leaf cells, re-applied after every upload
         self._leaf_evidence = None    # the table of leaf evidence, likewise
+        self._regions = None          # the lengths of the genomic regions, likewise (their end sites are held fixed)
 
     def _apply_sample_root(self):
         flags = C.c_uint32(0)
@@ -1111,6 +1131,8 @@ class SingleSiteSampler:
                 self.dev.set_unobserved(self._unobserved)
             if self._leaf_evidence is not None:
                 self.dev.set_leaf_evidence(self._leaf_evidence)
+            if self._regions is not None:
+                self.dev.set_fixed_sites(host.region_fixed_mask(paths.n_sites, self._regions))
         if not self._uploaded:
             raise EpvError(EPV_ERR_STATE, "reset() needs paths the first time")
         self._apply_sample_root()
@@ -1136,11 +1158,23 @@ class SingleSiteSampler:
         if self._uploaded:
             self.dev.set_leaf_evidence(self._leaf_evidence)
 
+    def set_regions(self, lengths):
+        """genomic regions (chromosomes, gap-free stretches): their numbers of sites in the order of the paths, each
+        at least 3, summing to the number of sites (host.read_regions reads them from a file).  The first and the
+        last site of every region are held fixed (DeviceSampler.set_fixed_sites), so no triple and no update spans a
+        break: the regions are sampled and counted independently given their end columns.  Kept across resets,
+        re-applied to new paths.  None clears."""
+        self._regions = None if lengths is None else [int(m) for m in lengths]
+        if self._uploaded:
+            self.dev.set_fixed_sites(None if self._regions is None
+                                     else host.region_fixed_mask(self.dev.n_sites, self._regions))
+
     def run_mcmc(self, seed, em_iter=0):
         self._apply_sample_root()
         base = em_iter * (self.burn_in + self.batch)
         J, D, nacc = self.dev.run_mcmc(self.burn_in, self.batch, seed, base)
-        acc_rate = nacc / float(self.batch * (self.dev.n_sites - 2))
+        updatable = self.dev.n_sites - 2 - (self.dev.fixed_sites() if self._regions is not None else 0)
+        acc_rate = nacc / float(self.batch * updatable)
         return J, D, acc_rate
 
     def sweeps(self, n, seed, sweep_base=0):

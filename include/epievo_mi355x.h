@@ -295,6 +295,30 @@ int epv_direct_giveups(epv_ctx *ctx, uint64_t *n_giveups);
 int epv_set_unobserved(epv_ctx *ctx, const uint8_t *unobserved);
 int epv_unobserved_cells(epv_ctx *ctx, uint64_t *n_cells);
 
+/* Fixed sites: what genomic regions are made of (the first and the last site of every chromosome or gap-free
+ * stretch).  mask[s] != 0, one byte per local column, halos included: site s is
+ *   1. never changed by a colour phase -- its path, its buffer bit and the cached triple likelihoods around it are
+ *      after the phase what they were before it;
+ *   2. context for its neighbours like any other column;
+ *   3. no centre: its triple is left out of the integer J and D of epv_run_mcmc_sums, epv_run_mcmc_counts and
+ *      epv_get_sufficient_statistics;
+ *   4. not counted in n_accepted.
+ * The colour-phase kernels are the ones of a context without a mask: a small guard launch before and after a
+ * phase keeps and restores the fixed sites of its colour, and one small launch per statistics pass takes their
+ * triples off the totals.  NULL, or no nonzero entry, clears the mask: then not one launch differs from a context
+ * that never had one.  A proposal is still made for a fixed site; one that overflows the capacity raises the
+ * overflow counter and EPV_ERR_CAPACITY although nothing was lost (repeat with a larger capacity: same results).
+ * Seven summaries count triples or runs across neighbouring sites and are not cut at fixed sites yet: window
+ * statistics, epoch statistics, domain statistics, domain turnover, change tracts, spatial correlations and domain
+ * maps.  While one of them is on epv_set_fixed_sites returns EPV_ERR_STATE naming it, and while a mask is held
+ * their epv_set_* return EPV_ERR_STATE naming epv_set_fixed_sites.  Before paths are resident EPV_ERR_STATE.
+ * What clears the mask of epv_set_unobserved clears this one (new paths); everything else keeps it
+ * (epv_set_capacity, epv_set_model, epv_scale_jump_times, epv_reset, epv_put_columns, epv_set_halo).
+ * epv_fixed_sites: the number of fixed sites inside the range whose acceptances n_accepted counts (the owned
+ * range) -- an acceptance rate is n_accepted / (sweeps * (owned sites - that number)).  No reference counterpart. */
+int epv_set_fixed_sites(epv_ctx *ctx, const uint8_t *mask /* n local columns, NULL clears */);
+int epv_fixed_sites(epv_ctx *ctx, uint64_t *n_fixed_updatable);
+
 /* Leaf evidence.  p_state1[(b-1)*n_sites + s] = r, a float32: the probability that the leaf end
  * state of branch b at local site s is 1 given that cell's observation alone, under a flat prior;
  * NaN = the cell has none.  The MCMC then starts Felsenstein pruning at that leaf from

@@ -62,6 +62,11 @@ int epvd_set_unobserved(epvd_sampler *s, uint64_t n_sites, int n_nodes, const ui
 /* leaf evidence: epv_set_leaf_evidence over the whole genome, p_state1[(b-1)*n_sites + s] (NaN = none), kept
  * and applied exactly as epvd_set_unobserved's mask is; NULL clears */
 int epvd_set_leaf_evidence(epvd_sampler *s, uint64_t n_sites, int n_nodes, const float *p_state1);
+/* genomic regions: the numbers of sites of the chromosomes or gap-free stretches of the whole genome, in its order,
+ * each at least 3, summing to it; their end sites are held fixed (epv_set_fixed_sites, every context its window),
+ * and the acceptance rate of epvd_run_mcmc is over the sites that can be updated.  Kept and applied as
+ * epvd_set_unobserved's mask is; NULL or n_regions = 0 clears */
+int epvd_set_regions(epvd_sampler *s, uint64_t n_regions, const uint64_t *lengths);
 
 /* the average history of the sampled paths (epv_set_path_average on every context; 0 = off; kept
  * across epvd_reset, which starts the counts from zero), and its counts over the sites of this process
