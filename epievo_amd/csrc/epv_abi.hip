@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "epievo_mi355x.h"
 #include "epv_device.h"
 #include "epv_plan.h"     // the colour phase: knobs, launch shapes, kernel variants (host only)
+#include "epv_part.h"     // the parts of the summaries that are joint along the genome: every byte size (host only)
 
 #define EPV_API extern "C" __attribute__((visibility("default")))
 
@@ -106,19 +108,22 @@ struct OriginsState {
   unsigned long long *d_out = nullptr;    // window read-out staging
   uint64_t out_cap = 0;                   // bytes
 };
-// domain size spectra (epv_domains.h), off while !on
-struct DomainsState {
-  bool on = false;
+// What the five summaries that are joint along the genome keep (epv_part.h): a context counts a PART, the host
+// merges the parts.  The sizes are those of the shape the part was laid out with; nothing computes them again
+struct PartState {
   uint64_t max = 0;                       // samples the edge records are allocated for
-  unsigned long long *d_hist = nullptr;   // [N][2][128] runs closed inside the counted stretch, over the samples
-  unsigned long long *d_len = nullptr;    // [N][2] their lengths
-  unsigned long long *d_edge = nullptr;   // [max][N][2] the two runs a sample's stretch cannot close
-  unsigned long long *d_bits = nullptr;   // [N][words] scratch: the node states of one sample, 64 sites a word
-  SiteLayout at;                          // (without B: the tree is compared itself)
-  uint64_t words = 0;
-  uint32_t N = 0, child0 = 0;             // nodes, and the root's lowest-numbered child
   uint64_t samples = 0;
-  std::vector<uint32_t> parent;           // the tree they were laid out for
+  SiteLayout at;                          // (with B only where the rows depend on nothing else of the tree)
+  PartShape shape;                        // rows, words and every byte size below
+  std::vector<uint32_t> tree;             // what of the tree the rows depend on (the layer's describe function)
+  unsigned long long *d_bits = nullptr;   // [rows][words] scratch: the rows of one sample, 64 sites a word
+  unsigned long long *d_edge = nullptr;   // [max] edge records of shape.edge_b bytes: what a sample's stretch cannot close
+  void *d_acc[2] = {nullptr, nullptr};    // shape.acc_b bytes each: what the stretch closes, over the samples
+};
+// domain size spectra (epv_domains.h), off while !on: acc = hist [N][2][128], len [N][2]; edge [max][N][2]
+struct DomainsState : PartState {
+  bool on = false;
+  uint32_t child0 = 0;                    // the root's lowest-numbered child
 };
 
 // change patterns (epv_patterns.h), off while !on
@@ -133,32 +138,15 @@ struct PatternsState {
   uint64_t out_cap = 0;                   // bytes
 };
 
-// domain turnover (epv_turnover.h), off while !on
-struct TurnoverState {
+// domain turnover (epv_turnover.h), off while !on: R = 2 B rows; acc = hist [R][2][2][128], len [R][2][2]; edge [max][R][2]
+struct TurnoverState : PartState {
   bool on = false;
-  uint64_t max = 0;                       // samples the edge records are allocated for
-  unsigned long long *d_hist = nullptr;   // [R][2][2][128] runs closed inside the counted stretch, over the samples
-  unsigned long long *d_len = nullptr;    // [R][2][2] their lengths
-  unsigned long long *d_edge = nullptr;   // [max][R][2] the two runs a sample's stretch cannot close
-  unsigned long long *d_bits = nullptr;   // [R][words] scratch: the rows of one sample, 64 sites a word
-  SiteLayout at;                          // (with B: the rows depend on nothing else of the tree)
-  uint64_t words = 0;
-  uint32_t R = 0;                         // rows: two per branch
-  uint64_t samples = 0;
 };
 
-// spatial correlations (epv_corr.h), off while L == 0
-struct CorrState {
+// spatial correlations (epv_corr.h), off while L == 0: R = N + B rows; acc = n11 [R][L + 1]; edge [max][R][2][LW]
+struct CorrState : PartState {
   uint32_t L = 0;                         // max_lag
-  uint64_t max = 0;                       // samples the edge records are allocated for
-  unsigned long long *d_n11 = nullptr;    // [R][L + 1] pairs of ones inside the counted stretch, over the samples
-  unsigned long long *d_edge = nullptr;   // [max][R][2][LW] the first and the last L bits of every sample's rows
-  unsigned long long *d_bits = nullptr;   // [R][words] scratch: the rows of one sample, 64 sites a word
-  SiteLayout at;                          // (with B)
-  uint64_t words = 0;
-  uint32_t R = 0, LW = 0;                 // rows N + B, words of an edge record
-  uint32_t N = 0, child0 = 0;             // nodes, and the root's lowest-numbered child: what row 0 depends on
-  uint64_t samples = 0;
+  uint32_t child0 = 0;                    // the root's lowest-numbered child: what row 0 depends on
 };
 
 // chain mixing diagnostics (epv_mixing.h), off while K == 0.  The one layer that is joint across samples: it keeps
@@ -180,32 +168,17 @@ struct MixingState {
   uint64_t out_cap = 0;                   // bytes
 };
 
-// domain maps (epv_dmaps.h), off while Z.K == 0
-struct DmapsState {
+// domain maps (epv_dmaps.h), off while Z.K == 0: N rows; acc = counts uint32 [N][K][at.cnt]; edge [max][N][2][EW]
+struct DmapsState : PartState {
   EpvDmapSizes Z{};                       // the sizes
   uint32_t state = 1;                     // the state whose runs are located
-  uint64_t max = 0;                       // samples the edge records are allocated for
-  uint32_t *d_counts = nullptr;           // [N][K][at.cnt] memberships inside the counted stretch, over the samples
-  unsigned long long *d_edge = nullptr;   // [max][N][2][EW] the first and the last E bits of every sample's rows
-  unsigned long long *d_bits = nullptr;   // [N][words] scratch: the rows of one sample, 64 sites a word
-  SiteLayout at;                          // (without B: the tree is compared itself)
-  uint64_t words = 0;
-  uint32_t N = 0, child0 = 0, EW = 0;     // nodes, the root's lowest-numbered child, words of an edge record
-  uint64_t samples = 0;
+  uint32_t child0 = 0;                    // the root's lowest-numbered child
 };
 
-// change tracts (epv_tracts.h), off while !on
-struct TractsState {
+// change tracts (epv_tracts.h), off while !on: the turnover's 2 B rows; acc = hist [B][27][128], len [B][27];
+// edge [max][B][2]
+struct TractsState : PartState {
   bool on = false;
-  uint64_t max = 0;                       // samples the edge records are allocated for
-  unsigned long long *d_hist = nullptr;   // [B][27][128] tracts closed inside the counted stretch, over the samples
-  unsigned long long *d_len = nullptr;    // [B][27] their lengths
-  unsigned long long *d_edge = nullptr;   // [max][B][2] what a sample's stretch cannot close at its two ends
-  unsigned long long *d_bits = nullptr;   // [2 B][words] scratch: the turnover's rows of one sample, 64 sites a word
-  SiteLayout at;                          // (with B: the rows depend on nothing else of the tree)
-  uint64_t words = 0;
-  uint32_t B = 0;
-  uint64_t samples = 0;
 };
 
 // fixed sites (epv_set_fixed_sites; epv_regions.h).  Everything is empty while no site is fixed: no launch, no buffer
@@ -1012,277 +985,217 @@ int launch_origins(epv_ctx *c) {
 const Layer kOrigins = {origins_on, ensure_origins, origins_check_cap, launch_origins, origins_off, nullptr,
                         "lineage origins are off: epv_set_lineage_origins first", "the lineage origins"};
 
-// ---- domain size spectra (epv_domains.h): the sites of pavg_range; a context keeps its PART, unclosed
-bool domains_on(const epv_ctx *c) { return c->dm.on; }
-void domains_off(epv_ctx *c) {
-  dfree(c->dm.d_hist); dfree(c->dm.d_len); dfree(c->dm.d_edge); dfree(c->dm.d_bits);
-  c->dm = DomainsState{};
+// ---- the summaries that are joint along the genome: the sites of pavg_range; a context
+// keeps its PART (PartState), unclosed.  What the five share is here once; a layer adds its describe function, its
+// launch and what its entry points take and give
+struct PartDesc {
+  PartShape shape;              // every size of the part (epv_part.h)
+  std::vector<uint32_t> tree;   // what of the tree the rows depend on beyond B: a change of it after samples is refused
+  std::string terms;            // the factors of the shape's sizes, for the device-room text
+  std::string refusal;          // (not empty) the stretch is too short for the layer: why
+};
+struct PartKind {
+  const Layer &layer;
+  const char *noun, *setter, *reset;   // as the texts call the layer, and the entry points they tell to call
+  const char *advice;                  // what to do when the part does not fit the device
+  bool with_B;                         // the site layout holds B: the rows depend on nothing else of the tree
+  PartDesc (*describe)(const epv_ctx *, uint64_t cnt);   // the part of cnt counted sites for the context as it is now
+};
+std::string text(const char *format, ...) __attribute__((format(printf, 1, 2)));
+std::string text(const char *format, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, format);
+  std::vsnprintf(buf, sizeof buf, format, ap);
+  va_end(ap);
+  return buf;
 }
-// (re)lay out the part for the current tree and site range; zeroes it
-int domains_alloc(epv_ctx *c) {
-  const SiteLayout at = pavg_layout(c, true, false);
-  const uint64_t cnt = at.cnt;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->dm.d_hist); dfree(c->dm.d_len); dfree(c->dm.d_edge); dfree(c->dm.d_bits);
-  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain statistics take at most 2^32 - 1 sites per context");
-  const uint32_t N = c->S.N;
-  const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 8.0 * N * (2.0 * EPV_DOM_BINS + 2.0) + 8.0 * N * (double)words + 16.0 * N * (double)c->dm.max;
-  bool fits = false;
-  double free_b = 0.0;
-  const int rc = device_room(c, need, &fits, &free_b);
-  if (rc) return rc;
-  if (!fits) {
-    char buf[320];
-    std::snprintf(buf, sizeof buf, "domain statistics need %.3g GB of device memory (16 B x %u nodes x %llu samples of "
-                  "edge records, 8 B x %u nodes x %llu words of node states); %.3g GB are free: ask for fewer samples "
-                  "(the statistics are off)",
-                  need / 1e9, N, (unsigned long long)c->dm.max, N, (unsigned long long)words, free_b / 1e9);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  uint32_t child0 = 0;
-  for (uint32_t v = 1; v < N && !child0; ++v) if (c->parent[v] == 0u) child0 = v;
-  const size_t hist_b = (size_t)16u * EPV_DOM_BINS * N, len_b = (size_t)16u * N, edge_b = (size_t)16u * N * c->dm.max;
-  HIP_TRY(c, hipMalloc(&c->dm.d_hist, hist_b));
-  HIP_TRY(c, hipMalloc(&c->dm.d_len, len_b));
-  HIP_TRY(c, hipMalloc(&c->dm.d_edge, edge_b));
-  if (words) HIP_TRY(c, hipMalloc(&c->dm.d_bits, (size_t)8u * N * words));
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_hist, 0, hist_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_len, 0, len_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_edge, 0, edge_b, c->stream));
-  c->dm.at = at;
-  c->dm.words = words;
-  c->dm.N = N;
-  c->dm.child0 = child0;
-  c->dm.samples = 0;
-  c->dm.parent = c->parent;
-  return EPV_OK;
-}
-// the part matches the current site range and tree (branch lengths do not matter: no jump time is read)
-int ensure_domains(epv_ctx *c) {
-  const bool sites = !(pavg_layout(c, true, false) == c->dm.at);
-  const bool tree = c->S.N != c->dm.N || c->parent != c->dm.parent;
-  if (!sites && !tree) return EPV_OK;
-  if (c->dm.samples) {
-    if (sites) return sites_changed(c, kDomains, "epv_set_domain_stats");
-    return fail(c, EPV_ERR_STATE, "the tree changed after the domain statistics took samples: read them out and "
-                                  "epv_reset_domain_stats");
-  }
-  return relayout(c, kDomains, domains_alloc);
-}
-int domains_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->dm.samples + more > c->dm.max) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "domain statistics hold %llu of the %llu samples their edge records were allocated "
-                  "for, and %llu more were asked: read them out and epv_reset_domain_stats, or epv_set_domain_stats "
-                  "with more", (unsigned long long)c->dm.samples, (unsigned long long)c->dm.max, (unsigned long long)more);
-    return fail(c, EPV_ERR_STATE, buf);
-  }
-  return EPV_OK;
-}
-// the resident paths as one sample (ensure_domains first): pack the node states, then count the runs
-int launch_domains(epv_ctx *c) {
-  int rc = domains_check_cap(c, 1u);
-  if (rc) return rc;
-  if (c->dm.at.cnt) {
-    const uint64_t words = c->dm.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
-    hipLaunchKernelGGL(epv_dom_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->dm.at.lo,
-                       c->dm.at.cnt, words, c->dm.child0, c->dm.d_bits);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long *edge = c->dm.d_edge + c->dm.samples * 2u * c->dm.N;
-    for (uint32_t v0 = 0; v0 < c->dm.N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
-      const uint32_t nv = std::min<uint32_t>(65535u, c->dm.N - v0);
-      hipLaunchKernelGGL(epv_dom_runs_kernel, dim3((unsigned)chunks, nv), dim3(256), 0, c->stream,
-                         (const unsigned long long *)c->dm.d_bits, words, c->dm.at.cnt, v0, c->dm.d_hist, c->dm.d_len, edge);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  ++c->dm.samples;
-  return EPV_OK;
-}
-const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off, nullptr,
-                        "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
-
-// ---- domain turnover (epv_turnover.h): the sites of pavg_range, R = 2 B rows; a context keeps its PART, unclosed
-bool turnover_on(const epv_ctx *c) { return c->to.on; }
-void turnover_off(epv_ctx *c) {
-  dfree(c->to.d_hist); dfree(c->to.d_len); dfree(c->to.d_edge); dfree(c->to.d_bits);
-  c->to = TurnoverState{};
-}
-// (re)lay out the part for the current branches and site range; zeroes it
-int turnover_alloc(epv_ctx *c) {
-  const SiteLayout at = pavg_layout(c, true, true);
-  const uint64_t cnt = at.cnt;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->to.d_hist); dfree(c->to.d_len); dfree(c->to.d_edge); dfree(c->to.d_bits);
-  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain turnover takes at most 2^32 - 1 sites per context");
-  const uint32_t R = 2u * c->S.B;
-  const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 8.0 * R * (4.0 * EPV_DOM_BINS + 4.0) + 8.0 * R * (double)words + 16.0 * R * (double)c->to.max;
-  bool fits = false;
-  double free_b = 0.0;
-  const int rc = device_room(c, need, &fits, &free_b);
-  if (rc) return rc;
-  if (!fits) {
-    char buf[320];
-    std::snprintf(buf, sizeof buf, "domain turnover needs %.3g GB of device memory (16 B x %u rows x %llu samples of "
-                  "edge records, 8 B x %u rows x %llu words of row states); %.3g GB are free: ask for fewer samples "
-                  "(the turnover is off)",
-                  need / 1e9, R, (unsigned long long)c->to.max, R, (unsigned long long)words, free_b / 1e9);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const size_t hist_b = (size_t)32u * EPV_DOM_BINS * R, len_b = (size_t)32u * R, edge_b = (size_t)16u * R * c->to.max;
-  HIP_TRY(c, hipMalloc(&c->to.d_hist, hist_b));
-  HIP_TRY(c, hipMalloc(&c->to.d_len, len_b));
-  HIP_TRY(c, hipMalloc(&c->to.d_edge, edge_b));
-  if (words) HIP_TRY(c, hipMalloc(&c->to.d_bits, (size_t)8u * R * words));
-  HIP_TRY(c, hipMemsetAsync(c->to.d_hist, 0, hist_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->to.d_len, 0, len_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->to.d_edge, 0, edge_b, c->stream));
-  c->to.at = at;
-  c->to.words = words;
-  c->to.R = R;
-  c->to.samples = 0;
-  return EPV_OK;
-}
-// the part matches the current site range and number of branches (neither the tree's shape nor its branch lengths
-// matter: a row is one branch's meta words)
-int ensure_turnover(epv_ctx *c) {
-  if (pavg_layout(c, true, true) == c->to.at) return EPV_OK;
-  if (c->to.samples) return sites_changed(c, kTurnover, "epv_set_domain_turnover");
-  return relayout(c, kTurnover, turnover_alloc);
-}
-int turnover_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->to.samples + more > c->to.max) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "domain turnover holds %llu of the %llu samples its edge records were allocated "
-                  "for, and %llu more were asked: read them out and epv_reset_domain_turnover, or "
-                  "epv_set_domain_turnover with more", (unsigned long long)c->to.samples, (unsigned long long)c->to.max,
-                  (unsigned long long)more);
-    return fail(c, EPV_ERR_STATE, buf);
-  }
-  return EPV_OK;
-}
-// the resident paths as one sample (ensure_turnover first): pack the rows, then count the runs
-int launch_turnover(epv_ctx *c) {
-  int rc = turnover_check_cap(c, 1u);
-  if (rc) return rc;
-  if (c->to.at.cnt && c->to.R) {
-    const uint64_t words = c->to.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
-    hipLaunchKernelGGL(epv_turn_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->to.at.lo,
-                       c->to.at.cnt, words, c->to.d_bits);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long *edge = c->to.d_edge + c->to.samples * 2u * c->to.R;
-    for (uint32_t r0 = 0; r0 < c->to.R; r0 += 65534u) {   // (a grid's y dimension takes 65535 rows)
-      const uint32_t nr = std::min<uint32_t>(65534u, c->to.R - r0);
-      hipLaunchKernelGGL(epv_turn_runs_kernel, dim3((unsigned)chunks, nr), dim3(256), 0, c->stream,
-                         (const unsigned long long *)c->to.d_bits, words, c->to.at.cnt, r0, c->to.d_hist, c->to.d_len, edge);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  ++c->to.samples;
-  return EPV_OK;
-}
-const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off, nullptr,
-                         "domain turnover is off: epv_set_domain_turnover first", "the domain turnover"};
-
-// ---- spatial correlations (epv_corr.h): the sites of pavg_range, R = N + B rows; a context keeps its PART, unclosed
-bool corr_on(const epv_ctx *c) { return c->co.L != 0u; }
-void corr_off(epv_ctx *c) {
-  dfree(c->co.d_n11); dfree(c->co.d_edge); dfree(c->co.d_bits);
-  c->co = CorrState{};
-}
+// the root's lowest-numbered child: what the root's row is read from
 uint32_t corr_child0(const epv_ctx *c) {
   for (uint32_t v = 1; v < c->S.N; ++v) if (c->parent[v] == 0u) return v;
   return 0u;
 }
+void part_free(PartState &p) { dfree(p.d_acc[0]); dfree(p.d_acc[1]); dfree(p.d_edge); dfree(p.d_bits); }
+template <class State>
+void part_off(State &s) {
+  part_free(s);
+  s = State{};
+}
+// no samples: the accumulators and the edge records zeroed (the scratch is written before it is read)
+int part_zero(epv_ctx *c, PartState &p) {
+  for (int i = 0; i < 2; ++i)
+    if (p.shape.acc_b[i]) HIP_TRY(c, hipMemsetAsync(p.d_acc[i], 0, p.shape.acc_b[i], c->stream));
+  if (p.shape.edges_b) HIP_TRY(c, hipMemsetAsync(p.d_edge, 0, p.shape.edges_b, c->stream));
+  p.samples = 0;
+  return EPV_OK;
+}
 // (re)lay out the part for the current tree and site range; zeroes it
-int corr_alloc(epv_ctx *c) {
-  const SiteLayout at = pavg_layout(c, true, true);
-  const uint64_t cnt = at.cnt;
+int part_alloc(epv_ctx *c, const PartKind &K, PartState &p) {
+  const SiteLayout at = pavg_layout(c, true, K.with_B);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->co.d_n11); dfree(c->co.d_edge); dfree(c->co.d_bits);
-  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "spatial correlations take at most 2^32 - 1 sites per context");
-  const uint32_t L = c->co.L;
-  if (cnt < L) {   // (a pair may span two parts, never three)
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "spatial correlations: this context counts %llu sites, fewer than max_lag = %u: "
-                  "a context's stretch holds at least max_lag sites (the correlations are off)",
-                  (unsigned long long)cnt, L);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const uint32_t N = c->S.N, R = N + c->S.B, LW = (L + 63u) / 64u;
-  const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 8.0 * R * (L + 1.0) + 8.0 * R * (double)words + 16.0 * R * LW * (double)c->co.max;
+  part_free(p);
+  if (at.cnt >> 32) return fail(c, EPV_ERR_ARG, std::string(K.noun) + ": at most 2^32 - 1 sites per context");
+  PartDesc d = K.describe(c, at.cnt);
+  if (!d.refusal.empty()) return fail(c, EPV_ERR_ARG, d.refusal);
+  const PartShape &sh = d.shape;
+  const double need = (double)sh.total();
   bool fits = false;
   double free_b = 0.0;
   const int rc = device_room(c, need, &fits, &free_b);
   if (rc) return rc;
-  if (!fits) {
-    char buf[360];
-    std::snprintf(buf, sizeof buf, "spatial correlations need %.3g GB of device memory (16 B x %u rows x %u words x %llu "
-                  "samples of edge records, 8 B x %u rows x %llu words of row states, 8 B x %u rows x %u lags of "
-                  "counts); %.3g GB are free: ask for fewer samples (the correlations are off)",
-                  need / 1e9, R, LW, (unsigned long long)c->co.max, R, (unsigned long long)words, R, L + 1u, free_b / 1e9);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const size_t n11_b = (size_t)8u * R * (L + 1u), edge_b = (size_t)16u * R * LW * c->co.max;
-  HIP_TRY(c, hipMalloc(&c->co.d_n11, n11_b));
-  HIP_TRY(c, hipMalloc(&c->co.d_edge, edge_b));
-  HIP_TRY(c, hipMalloc(&c->co.d_bits, (size_t)8u * R * words));
-  HIP_TRY(c, hipMemsetAsync(c->co.d_n11, 0, n11_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->co.d_edge, 0, edge_b, c->stream));
-  c->co.at = at;
-  c->co.words = words;
-  c->co.R = R;
-  c->co.LW = LW;
-  c->co.N = N;
-  c->co.child0 = corr_child0(c);
-  c->co.samples = 0;
-  return EPV_OK;
+  if (!fits)
+    return fail(c, EPV_ERR_ARG, text("%s: %.3g GB of device memory are needed (%s); %.3g GB are free: %s", K.noun,
+                                     need / 1e9, d.terms.c_str(), free_b / 1e9, K.advice));
+  if (sh.bits_b) HIP_TRY(c, hipMalloc(&p.d_bits, sh.bits_b));
+  if (sh.edges_b) HIP_TRY(c, hipMalloc(&p.d_edge, sh.edges_b));
+  for (int i = 0; i < 2; ++i)
+    if (sh.acc_b[i]) HIP_TRY(c, hipMalloc(&p.d_acc[i], sh.acc_b[i]));
+  p.at = at;
+  p.shape = sh;
+  p.tree.swap(d.tree);
+  return part_zero(c, p);
 }
-// the part matches the current site range, number of nodes and branches and the root's first child (nothing else
-// of the tree matters: a row is one branch's meta words, and no jump time is read)
-int ensure_corr(epv_ctx *c) {
-  const bool sites = !(pavg_layout(c, true, true) == c->co.at);
-  const bool tree = c->S.N != c->co.N || corr_child0(c) != c->co.child0;
-  if (!sites && !tree) return EPV_OK;
-  if (c->co.samples) {
-    if (sites) return sites_changed(c, kCorr, "epv_set_spatial_correlation");
-    return fail(c, EPV_ERR_STATE, "the tree changed after the spatial correlations took samples: read them out and "
-                                  "epv_reset_spatial_correlation");
+// the part matches the current site range and what its rows depend on of the tree (branch lengths never matter: no
+// jump time is read)
+int part_ensure(epv_ctx *c, const PartKind &K, const PartState &p, int (*alloc)(epv_ctx *)) {
+  const SiteLayout at = pavg_layout(c, true, K.with_B);
+  const bool sites = !(at == p.at);
+  if (!sites && K.describe(c, at.cnt).tree == p.tree) return EPV_OK;
+  if (p.samples) {
+    if (sites) return sites_changed(c, K.layer, K.setter);
+    return fail(c, EPV_ERR_STATE, std::string("the tree changed after ") + K.layer.name + " took samples: read them out and " +
+                                  K.reset);
   }
-  return relayout(c, kCorr, corr_alloc);
+  return relayout(c, K.layer, alloc);
 }
-int corr_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->co.samples + more > c->co.max) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "spatial correlations hold %llu of the %llu samples their edge records were "
-                  "allocated for, and %llu more were asked: read them out and epv_reset_spatial_correlation, or "
-                  "epv_set_spatial_correlation with more", (unsigned long long)c->co.samples,
-                  (unsigned long long)c->co.max, (unsigned long long)more);
-    return fail(c, EPV_ERR_STATE, buf);
-  }
-  return EPV_OK;
+// `more` further samples fit the edge records
+int part_check_cap(epv_ctx *c, const PartKind &K, const PartState &p, uint64_t more) {
+  if (p.samples + more <= p.max) return EPV_OK;
+  return fail(c, EPV_ERR_STATE, text("%s: %llu of the %llu samples the edge records were allocated for are held, and "
+                                     "%llu more were asked: read them out and %s, or %s with more", K.noun,
+                                     (unsigned long long)p.samples, (unsigned long long)p.max, (unsigned long long)more,
+                                     K.reset, K.setter));
 }
-// the resident paths as one sample (ensure_corr first): pack the rows, then count the pairs of every lag
-int launch_corr(epv_ctx *c) {
-  int rc = corr_check_cap(c, 1u);
+// the resident paths as one sample (the layer's ensure first).  While `counts`: the rows ROWS of epv_rows.h into the
+// part's scratch, then one(r0, nr, bits, words, edge) launches the layer's kernel over rows r0 .. r0 + nr - 1 of
+// `rows`, at most `slice` at a time (a grid's y dimension takes 65535 rows); edge = this sample's records
+template <uint32_t ROWS, class One>
+int part_sample(epv_ctx *c, const PartKind &K, PartState &p, bool counts, uint32_t child0, uint32_t state, uint32_t rows,
+                uint32_t slice, One one) {
+  const int rc = K.layer.check_cap(c, 1u);
   if (rc) return rc;
-  const uint64_t words = c->co.words, chunks = (words + EPV_CORR_CHUNK_WORDS - 1u) / EPV_CORR_CHUNK_WORDS;
-  hipLaunchKernelGGL(epv_corr_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->co.at.lo,
-                     c->co.at.cnt, words, c->co.child0, c->co.d_bits);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long *edge = c->co.d_edge + c->co.samples * 2u * c->co.R * c->co.LW;
-  const unsigned threads = std::min<unsigned>(256u, (c->co.L + 1u + 63u) / 64u * 64u);   // (a thread owns lags)
-  for (uint32_t r0 = 0; r0 < c->co.R; r0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
-    const uint32_t nr = std::min<uint32_t>(65535u, c->co.R - r0);
-    hipLaunchKernelGGL(epv_corr_count_kernel, dim3((unsigned)chunks, nr), dim3(threads), 0, c->stream,
-                       (const unsigned long long *)c->co.d_bits, words, c->co.at.cnt, r0, c->co.L, c->co.d_n11, edge);
+  if (counts) {
+    const uint64_t words = p.shape.words;
+    hipLaunchKernelGGL(epv_rows_pack_kernel<ROWS>, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, p.at.lo,
+                       p.at.cnt, words, child0, state, p.d_bits);
     HIP_TRY(c, hipGetLastError());
+    unsigned long long *edge = p.d_edge + p.samples * (p.shape.edge_b / 8u);
+    for (uint32_t r0 = 0; r0 < rows; r0 += slice) {
+      one(r0, std::min<uint32_t>(slice, rows - r0), (const unsigned long long *)p.d_bits, words, edge);
+      HIP_TRY(c, hipGetLastError());
+    }
   }
-  ++c->co.samples;
+  ++p.samples;
   return EPV_OK;
+}
+// blocks along a row of `words` words, chunk words a block
+unsigned part_chunks(uint64_t words, uint32_t chunk) { return (unsigned)((words + chunk - 1u) / chunk); }
+
+// ---- domain size spectra (epv_domains.h): N node rows; the part depends on the whole tree
+PartDesc domains_part(const epv_ctx *c, uint64_t cnt) {
+  PartDesc d;
+  d.shape = domains_shape(c->S.N, cnt, c->dm.max);
+  d.tree = c->parent;
+  d.terms = text("16 B x %u nodes x %llu samples of edge records, 8 B x %u nodes x %llu words of node states", c->S.N,
+                 (unsigned long long)c->dm.max, c->S.N, (unsigned long long)d.shape.words);
+  return d;
+}
+const PartKind kDomainsPart = {kDomains, "domain statistics", "epv_set_domain_stats", "epv_reset_domain_stats",
+                               "ask for fewer samples (the statistics are off)", false, domains_part};
+bool domains_on(const epv_ctx *c) { return c->dm.on; }
+void domains_off(epv_ctx *c) { part_off(c->dm); }
+int domains_alloc(epv_ctx *c) {
+  const int rc = part_alloc(c, kDomainsPart, c->dm);
+  if (!rc) c->dm.child0 = corr_child0(c);
+  return rc;
+}
+int ensure_domains(epv_ctx *c) { return part_ensure(c, kDomainsPart, c->dm, domains_alloc); }
+int domains_check_cap(epv_ctx *c, uint64_t more) { return part_check_cap(c, kDomainsPart, c->dm, more); }
+// pack the node states, then count the runs
+int launch_domains(epv_ctx *c) {
+  DomainsState &p = c->dm;
+  return part_sample<EPV_ROWS_NODE>(c, kDomainsPart, p, p.at.cnt != 0u, p.child0, 1u, p.shape.rows, 65535u,
+    [&](uint32_t v0, uint32_t nv, const unsigned long long *bits, uint64_t words, unsigned long long *edge) {
+      hipLaunchKernelGGL(epv_dom_runs_kernel, dim3(part_chunks(words, EPV_DOM_CHUNK_WORDS), nv), dim3(256), 0, c->stream, bits,
+                         words, p.at.cnt, v0, (unsigned long long *)p.d_acc[0], (unsigned long long *)p.d_acc[1], edge);
+    });
+}
+const Layer kDomains = {domains_on, ensure_domains, domains_check_cap, launch_domains, domains_off, nullptr,
+                        "domain statistics are off: epv_set_domain_stats first", "the domain statistics"};
+
+// ---- domain turnover (epv_turnover.h): R = 2 B end rows; neither the tree's shape nor its branch lengths matter
+PartDesc turnover_part(const epv_ctx *c, uint64_t cnt) {
+  PartDesc d;
+  d.shape = turnover_shape(c->S.B, cnt, c->to.max);
+  d.terms = text("16 B x %u rows x %llu samples of edge records, 8 B x %u rows x %llu words of row states", d.shape.rows,
+                 (unsigned long long)c->to.max, d.shape.rows, (unsigned long long)d.shape.words);
+  return d;
+}
+const PartKind kTurnoverPart = {kTurnover, "domain turnover", "epv_set_domain_turnover", "epv_reset_domain_turnover",
+                                "ask for fewer samples (the turnover is off)", true, turnover_part};
+bool turnover_on(const epv_ctx *c) { return c->to.on; }
+void turnover_off(epv_ctx *c) { part_off(c->to); }
+int turnover_alloc(epv_ctx *c) { return part_alloc(c, kTurnoverPart, c->to); }
+int ensure_turnover(epv_ctx *c) { return part_ensure(c, kTurnoverPart, c->to, turnover_alloc); }
+int turnover_check_cap(epv_ctx *c, uint64_t more) { return part_check_cap(c, kTurnoverPart, c->to, more); }
+// pack the rows, then count the runs (slices of an even number of rows: a row's partner is in its slice)
+int launch_turnover(epv_ctx *c) {
+  TurnoverState &p = c->to;
+  return part_sample<EPV_ROWS_ENDS>(c, kTurnoverPart, p, p.at.cnt && p.shape.rows, 0u, 1u, p.shape.rows, 65534u,
+    [&](uint32_t r0, uint32_t nr, const unsigned long long *bits, uint64_t words, unsigned long long *edge) {
+      hipLaunchKernelGGL(epv_turn_runs_kernel, dim3(part_chunks(words, EPV_DOM_CHUNK_WORDS), nr), dim3(256), 0, c->stream, bits,
+                         words, p.at.cnt, r0, (unsigned long long *)p.d_acc[0], (unsigned long long *)p.d_acc[1], edge);
+    });
+}
+const Layer kTurnover = {turnover_on, ensure_turnover, turnover_check_cap, launch_turnover, turnover_off, nullptr,
+                         "domain turnover is off: epv_set_domain_turnover first", "the domain turnover"};
+
+// ---- spatial correlations (epv_corr.h): R = N + B rows, the node rows and the change rows; of the tree the number
+// of nodes and the root's first child matter
+PartDesc corr_part(const epv_ctx *c, uint64_t cnt) {
+  PartDesc d;
+  const uint32_t L = c->co.L, LW = (L + 63u) / 64u;
+  d.shape = corr_shape(c->S.N, c->S.B, L, cnt, c->co.max);
+  d.tree = {c->S.N, corr_child0(c)};
+  d.terms = text("16 B x %u rows x %u words x %llu samples of edge records, 8 B x %u rows x %llu words of row states, "
+                 "8 B x %u rows x %u lags of counts", d.shape.rows, LW, (unsigned long long)c->co.max, d.shape.rows,
+                 (unsigned long long)d.shape.words, d.shape.rows, L + 1u);
+  if (cnt < L)   // (a pair may span two parts, never three)
+    d.refusal = text("spatial correlations: this context counts %llu sites, fewer than max_lag = %u: a context's stretch "
+                     "holds at least max_lag sites (the correlations are off)", (unsigned long long)cnt, L);
+  return d;
+}
+const PartKind kCorrPart = {kCorr, "spatial correlations", "epv_set_spatial_correlation", "epv_reset_spatial_correlation",
+                            "ask for fewer samples (the correlations are off)", true, corr_part};
+bool corr_on(const epv_ctx *c) { return c->co.L != 0u; }
+void corr_off(epv_ctx *c) { part_off(c->co); }
+int corr_alloc(epv_ctx *c) {
+  const int rc = part_alloc(c, kCorrPart, c->co);
+  if (!rc) c->co.child0 = corr_child0(c);
+  return rc;
+}
+int ensure_corr(epv_ctx *c) { return part_ensure(c, kCorrPart, c->co, corr_alloc); }
+int corr_check_cap(epv_ctx *c, uint64_t more) { return part_check_cap(c, kCorrPart, c->co, more); }
+// pack the rows, then count the pairs of every lag (no guard: a stretch holds at least max_lag >= 1 sites, and a tree
+// at least one branch)
+int launch_corr(epv_ctx *c) {
+  CorrState &p = c->co;
+  const unsigned threads = std::min<unsigned>(256u, (p.L + 1u + 63u) / 64u * 64u);   // (a thread owns lags)
+  return part_sample<EPV_ROWS_CORR>(c, kCorrPart, p, true, p.child0, 1u, p.shape.rows, 65535u,
+    [&](uint32_t r0, uint32_t nr, const unsigned long long *bits, uint64_t words, unsigned long long *edge) {
+      hipLaunchKernelGGL(epv_corr_count_kernel, dim3(part_chunks(words, EPV_CORR_CHUNK_WORDS), nr), dim3(threads), 0, c->stream,
+                         bits, words, p.at.cnt, r0, p.L, (unsigned long long *)p.d_acc[0], edge);
+    });
 }
 const Layer kCorr = {corr_on, ensure_corr, corr_check_cap, launch_corr, corr_off, nullptr,
                      "spatial correlations are off: epv_set_spatial_correlation first", "the spatial correlations"};
@@ -1562,187 +1475,73 @@ int launch_mixing(epv_ctx *c) {
 const Layer kMixing = {mixing_on, ensure_mixing, mixing_check_cap, launch_mixing, mixing_off, begin_mixing,
                        "mixing diagnostics are off: epv_set_mixing first", "the mixing diagnostics"};
 
-// ---- domain maps (epv_dmaps.h): the sites of pavg_range, N rows; a context keeps its PART
+// ---- domain maps (epv_dmaps.h): N node rows of the state to indicate; of the tree the number of nodes and the
+// root's first child matter
+PartDesc dmaps_part(const epv_ctx *c, uint64_t cnt) {
+  PartDesc d;
+  const uint32_t N = c->S.N, K = c->dp.Z.K, LK = c->dp.Z.L[K - 1u], E = dmaps_edge_bits(LK), EW = (E + 63u) / 64u;
+  d.shape = dmaps_shape(N, K, LK, cnt, c->dp.max);
+  d.tree = {N, corr_child0(c)};
+  d.terms = text("4 B x %u nodes x %u sizes x %llu sites of counts, 16 B x %u nodes x %u words x %llu samples of edge "
+                 "records, 8 B x %u nodes x %llu words of node states", N, K, (unsigned long long)cnt, N, EW,
+                 (unsigned long long)c->dp.max, N, (unsigned long long)d.shape.words);
+  if (cnt < E)   // (a run's membership is decided inside two adjacent parts, never three)
+    d.refusal = text("domain maps: this context counts %llu sites, fewer than the %u of an edge record (twice the largest "
+                     "size %u less one): a context's stretch holds at least those (the maps are off)",
+                     (unsigned long long)cnt, E, LK);
+  return d;
+}
+const PartKind kDmapsPart = {kDmaps, "domain maps", "epv_set_domain_maps", "epv_reset_domain_maps",
+                             "ask for fewer sizes or samples, or use more GPUs (the maps are off)", false, dmaps_part};
 bool dmaps_on(const epv_ctx *c) { return c->dp.Z.K != 0u; }
-void dmaps_off(epv_ctx *c) {
-  dfree(c->dp.d_counts); dfree(c->dp.d_edge); dfree(c->dp.d_bits);
-  c->dp = DmapsState{};
-}
-// (re)lay out the part for the current tree and site range; zeroes it
+void dmaps_off(epv_ctx *c) { part_off(c->dp); }
 int dmaps_alloc(epv_ctx *c) {
-  const SiteLayout at = pavg_layout(c, true, false);
-  const uint64_t cnt = at.cnt;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->dp.d_counts); dfree(c->dp.d_edge); dfree(c->dp.d_bits);
-  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "domain maps take at most 2^32 - 1 sites per context");
-  const uint32_t K = c->dp.Z.K, LK = c->dp.Z.L[K - 1u], E = 2u * (LK - 1u), EW = (E + 63u) / 64u;
-  if (cnt < E) {   // (a run's membership is decided inside two adjacent parts, never three)
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "domain maps: this context counts %llu sites, fewer than the %u of an edge record "
-                  "(twice the largest size %u less one): a context's stretch holds at least those (the maps are off)",
-                  (unsigned long long)cnt, E, LK);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const uint32_t N = c->S.N;
-  const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 4.0 * N * K * (double)cnt + 8.0 * N * (double)words + 16.0 * N * EW * (double)c->dp.max;
-  bool fits = false;
-  double free_b = 0.0;
-  const int rc = device_room(c, need, &fits, &free_b);
-  if (rc) return rc;
-  if (!fits) {
-    char buf[400];
-    std::snprintf(buf, sizeof buf, "domain maps need %.3g GB of device memory (4 B x %u nodes x %u sizes x %llu sites of "
-                  "counts, 16 B x %u nodes x %u words x %llu samples of edge records, 8 B x %u nodes x %llu words of node "
-                  "states); %.3g GB are free: ask for fewer sizes or samples, or use more GPUs (the maps are off)",
-                  need / 1e9, N, K, (unsigned long long)cnt, N, EW, (unsigned long long)c->dp.max, N,
-                  (unsigned long long)words, free_b / 1e9);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const size_t counts_b = (size_t)4u * N * K * cnt, edge_b = (size_t)16u * N * EW * c->dp.max;
-  if (counts_b) {
-    HIP_TRY(c, hipMalloc(&c->dp.d_counts, counts_b));
-    HIP_TRY(c, hipMemsetAsync(c->dp.d_counts, 0, counts_b, c->stream));
-    HIP_TRY(c, hipMalloc(&c->dp.d_bits, (size_t)8u * N * words));
-  }
-  if (edge_b) {
-    HIP_TRY(c, hipMalloc(&c->dp.d_edge, edge_b));
-    HIP_TRY(c, hipMemsetAsync(c->dp.d_edge, 0, edge_b, c->stream));
-  }
-  c->dp.at = at;
-  c->dp.words = words;
-  c->dp.N = N;
-  c->dp.child0 = corr_child0(c);
-  c->dp.EW = EW;
-  c->dp.samples = 0;
-  return EPV_OK;
+  const int rc = part_alloc(c, kDmapsPart, c->dp);
+  if (!rc) c->dp.child0 = corr_child0(c);
+  return rc;
 }
-// the part matches the current site range, number of nodes and the root's first child (nothing else of the tree
-// matters: a row is one branch's meta words, and no jump time is read)
-int ensure_dmaps(epv_ctx *c) {
-  const bool sites = !(pavg_layout(c, true, false) == c->dp.at);
-  const bool tree = c->S.N != c->dp.N || corr_child0(c) != c->dp.child0;
-  if (!sites && !tree) return EPV_OK;
-  if (c->dp.samples) {
-    if (sites) return sites_changed(c, kDmaps, "epv_set_domain_maps");
-    return fail(c, EPV_ERR_STATE, "the tree changed after the domain maps took samples: read them out and "
-                                  "epv_reset_domain_maps");
-  }
-  return relayout(c, kDmaps, dmaps_alloc);
-}
+int ensure_dmaps(epv_ctx *c) { return part_ensure(c, kDmapsPart, c->dp, dmaps_alloc); }
+// the edge records, and the 32-bit counts: a site adds at most one per sample
 int dmaps_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->dp.samples + more > c->dp.max) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "domain maps hold %llu of the %llu samples their edge records were allocated for, "
-                  "and %llu more were asked: read them out and epv_reset_domain_maps, or epv_set_domain_maps with more",
-                  (unsigned long long)c->dp.samples, (unsigned long long)c->dp.max, (unsigned long long)more);
-    return fail(c, EPV_ERR_STATE, buf);
-  }
-  return check_cap32(c, c->dp.samples, more, "domain maps", "epv_reset_domain_maps");
+  const int rc = part_check_cap(c, kDmapsPart, c->dp, more);
+  return rc ? rc : check_cap32(c, c->dp.samples, more, "domain maps", "epv_reset_domain_maps");
 }
-// the resident paths as one sample (ensure_dmaps first): pack the rows, then add every site's memberships
+// pack the rows, then add every site's memberships (the edge records are never read while a record has no words)
 int launch_dmaps(epv_ctx *c) {
-  int rc = dmaps_check_cap(c, 1u);
-  if (rc) return rc;
-  if (c->dp.at.cnt) {
-    const uint64_t words = c->dp.words, chunks = (words + EPV_DMAPS_CHUNK_WORDS - 1u) / EPV_DMAPS_CHUNK_WORDS;
-    hipLaunchKernelGGL(epv_dmaps_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S,
-                       c->dp.at.lo, c->dp.at.cnt, words, c->dp.child0, c->dp.state, c->dp.d_bits);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long *edge = c->dp.d_edge + c->dp.samples * 2u * c->dp.N * c->dp.EW;   // (never read while EW == 0)
-    for (uint32_t v0 = 0; v0 < c->dp.N; v0 += 65535u) {   // (a grid's y dimension takes 65535 rows)
-      const uint32_t nv = std::min<uint32_t>(65535u, c->dp.N - v0);
-      hipLaunchKernelGGL(epv_dmaps_member_kernel, dim3((unsigned)chunks, nv), dim3(256), 0, c->stream,
-                         (const unsigned long long *)c->dp.d_bits, words, c->dp.at.cnt, v0, c->dp.Z, c->dp.d_counts, edge);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  ++c->dp.samples;
-  return EPV_OK;
+  DmapsState &p = c->dp;
+  return part_sample<EPV_ROWS_NODE>(c, kDmapsPart, p, p.at.cnt != 0u, p.child0, p.state, p.shape.rows, 65535u,
+    [&](uint32_t v0, uint32_t nv, const unsigned long long *bits, uint64_t words, unsigned long long *edge) {
+      hipLaunchKernelGGL(epv_dmaps_member_kernel, dim3(part_chunks(words, EPV_DMAPS_CHUNK_WORDS), nv), dim3(256), 0, c->stream,
+                         bits, words, p.at.cnt, v0, p.Z, (uint32_t *)p.d_acc[0], edge);
+    });
 }
 const Layer kDmaps = {dmaps_on, ensure_dmaps, dmaps_check_cap, launch_dmaps, dmaps_off, nullptr,
                       "domain maps are off: epv_set_domain_maps first", "the domain maps"};
 
-// ---- change tracts (epv_tracts.h): the sites of pavg_range, one row of tracts per branch; a context keeps its PART,
-// unclosed
+// ---- change tracts (epv_tracts.h): the turnover's 2 B end rows, one row of tracts per branch
+PartDesc tracts_part(const epv_ctx *c, uint64_t cnt) {
+  PartDesc d;
+  d.shape = tracts_shape(c->S.B, cnt, c->tr.max);
+  d.terms = text("16 B x %u branches x %llu samples of edge records, 16 B x %u branches x %llu words of row states", c->S.B,
+                 (unsigned long long)c->tr.max, c->S.B, (unsigned long long)d.shape.words);
+  return d;
+}
+const PartKind kTractsPart = {kTracts, "change tracts", "epv_set_change_tracts", "epv_reset_change_tracts",
+                              "ask for fewer samples (the change tracts are off)", true, tracts_part};
 bool tracts_on(const epv_ctx *c) { return c->tr.on; }
-void tracts_off(epv_ctx *c) {
-  dfree(c->tr.d_hist); dfree(c->tr.d_len); dfree(c->tr.d_edge); dfree(c->tr.d_bits);
-  c->tr = TractsState{};
-}
-// (re)lay out the part for the current branches and site range; zeroes it
-int tracts_alloc(epv_ctx *c) {
-  const SiteLayout at = pavg_layout(c, true, true);
-  const uint64_t cnt = at.cnt;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  dfree(c->tr.d_hist); dfree(c->tr.d_len); dfree(c->tr.d_edge); dfree(c->tr.d_bits);
-  if (cnt >> 32) return fail(c, EPV_ERR_ARG, "change tracts take at most 2^32 - 1 sites per context");
-  const uint32_t B = c->S.B;
-  const uint64_t words = (cnt + 63u) / 64u;
-  const double need = 8.0 * B * (EPV_TRACT_CLASSES * (EPV_DOM_BINS + 1.0)) + 16.0 * B * (double)words + 16.0 * B * (double)c->tr.max;
-  bool fits = false;
-  double free_b = 0.0;
-  const int rc = device_room(c, need, &fits, &free_b);
-  if (rc) return rc;
-  if (!fits) {
-    char buf[320];
-    std::snprintf(buf, sizeof buf, "change tracts need %.3g GB of device memory (16 B x %u branches x %llu samples of "
-                  "edge records, 16 B x %u branches x %llu words of row states); %.3g GB are free: ask for fewer samples "
-                  "(the change tracts are off)",
-                  need / 1e9, B, (unsigned long long)c->tr.max, B, (unsigned long long)words, free_b / 1e9);
-    return fail(c, EPV_ERR_ARG, buf);
-  }
-  const size_t hist_b = (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * B, len_b = (size_t)8u * EPV_TRACT_CLASSES * B,
-               edge_b = (size_t)16u * B * c->tr.max;
-  HIP_TRY(c, hipMalloc(&c->tr.d_hist, hist_b));
-  HIP_TRY(c, hipMalloc(&c->tr.d_len, len_b));
-  HIP_TRY(c, hipMalloc(&c->tr.d_edge, edge_b));
-  if (words) HIP_TRY(c, hipMalloc(&c->tr.d_bits, (size_t)16u * B * words));
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_hist, 0, hist_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_len, 0, len_b, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_edge, 0, edge_b, c->stream));
-  c->tr.at = at;
-  c->tr.words = words;
-  c->tr.B = B;
-  c->tr.samples = 0;
-  return EPV_OK;
-}
-// the part matches the current site range and number of branches (as the turnover's: a row is one branch's meta words)
-int ensure_tracts(epv_ctx *c) {
-  if (pavg_layout(c, true, true) == c->tr.at) return EPV_OK;
-  if (c->tr.samples) return sites_changed(c, kTracts, "epv_set_change_tracts");
-  return relayout(c, kTracts, tracts_alloc);
-}
-int tracts_check_cap(epv_ctx *c, uint64_t more) {
-  if (c->tr.samples + more > c->tr.max) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "change tracts hold %llu of the %llu samples their edge records were allocated "
-                  "for, and %llu more were asked: read them out and epv_reset_change_tracts, or "
-                  "epv_set_change_tracts with more", (unsigned long long)c->tr.samples, (unsigned long long)c->tr.max,
-                  (unsigned long long)more);
-    return fail(c, EPV_ERR_STATE, buf);
-  }
-  return EPV_OK;
-}
-// the resident paths as one sample (ensure_tracts first): pack the turnover's rows, then count the tracts
+void tracts_off(epv_ctx *c) { part_off(c->tr); }
+int tracts_alloc(epv_ctx *c) { return part_alloc(c, kTractsPart, c->tr); }
+int ensure_tracts(epv_ctx *c) { return part_ensure(c, kTractsPart, c->tr, tracts_alloc); }
+int tracts_check_cap(epv_ctx *c, uint64_t more) { return part_check_cap(c, kTractsPart, c->tr, more); }
+// pack the turnover's rows, then count the tracts, a row of them per branch
 int launch_tracts(epv_ctx *c) {
-  int rc = tracts_check_cap(c, 1u);
-  if (rc) return rc;
-  if (c->tr.at.cnt && c->tr.B) {
-    const uint64_t words = c->tr.words, chunks = (words + EPV_DOM_CHUNK_WORDS - 1u) / EPV_DOM_CHUNK_WORDS;
-    hipLaunchKernelGGL(epv_turn_pack_kernel, dim3((unsigned)((words + 3u) / 4u)), dim3(256), 0, c->stream, c->S, c->tr.at.lo,
-                       c->tr.at.cnt, words, c->tr.d_bits);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long *edge = c->tr.d_edge + c->tr.samples * 2u * c->tr.B;
-    for (uint32_t b0 = 0; b0 < c->tr.B; b0 += 65534u) {   // (a grid's y dimension takes 65535 rows)
-      const uint32_t nb = std::min<uint32_t>(65534u, c->tr.B - b0);
-      hipLaunchKernelGGL(epv_tract_runs_kernel, dim3((unsigned)chunks, nb), dim3(256), 0, c->stream,
-                         (const unsigned long long *)c->tr.d_bits, words, c->tr.at.cnt, b0, c->tr.d_hist, c->tr.d_len, edge);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  ++c->tr.samples;
-  return EPV_OK;
+  TractsState &p = c->tr;
+  const uint32_t B = p.shape.rows / 2u;
+  return part_sample<EPV_ROWS_ENDS>(c, kTractsPart, p, p.at.cnt && B, 0u, 1u, B, 65534u,
+    [&](uint32_t b0, uint32_t nb, const unsigned long long *bits, uint64_t words, unsigned long long *edge) {
+      hipLaunchKernelGGL(epv_tract_runs_kernel, dim3(part_chunks(words, EPV_DOM_CHUNK_WORDS), nb), dim3(256), 0, c->stream, bits,
+                         words, p.at.cnt, b0, (unsigned long long *)p.d_acc[0], (unsigned long long *)p.d_acc[1], edge);
+    });
 }
 const Layer kTracts = {tracts_on, ensure_tracts, tracts_check_cap, launch_tracts, tracts_off, nullptr,
                        "change tracts are off: epv_set_change_tracts first", "the change tracts"};
@@ -4322,6 +4121,40 @@ EPV_API int epv_get_lineage_origin_windows(epv_ctx *c, uint64_t W, uint64_t firs
   return EPV_OK;
 }
 
+// ---- the entry points of the summaries that are joint along the genome
+// what epv_*_layout begins with while the layer is on: no samples yet, so lay out for the tree and sites as they are now
+static int part_layout_entry(epv_ctx *c, const PartKind &K, const PartState &p) {
+  if (!c->have_tree || !c->have_paths || p.samples) return EPV_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return K.layer.ensure(c);
+}
+// epv_*_samples (0 while the layer is off)
+static int part_samples(const epv_ctx *c, const PartState *p, uint64_t *n) {
+  if (!c || !n) return EPV_ERR_ARG;
+  *n = p->samples;
+  return EPV_OK;
+}
+// epv_reset_*
+static int part_reset(epv_ctx *c, const PartKind &K, PartState &p) {
+  int rc = layer_entry(c, K.layer);
+  if (rc || (rc = part_zero(c, p))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return EPV_OK;
+}
+// epv_get_*: the accumulators whole, the edge records of the samples held
+static int part_get(epv_ctx *c, const PartKind &K, const PartState &p, void *acc0, void *acc1, uint64_t *edges) {
+  const int rc = layer_entry(c, K.layer);
+  if (rc) return rc;
+  void *const acc[2] = {acc0, acc1};
+  if (!edges || !acc0 || (p.shape.acc_b[1] && !acc1)) return fail(c, EPV_ERR_ARG, "null output");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 2; ++i)
+    if (p.shape.acc_b[i]) HIP_TRY(c, hipMemcpy(acc[i], p.d_acc[i], p.shape.acc_b[i], hipMemcpyDeviceToHost));
+  if (p.shape.edge_b * p.samples) HIP_TRY(c, hipMemcpy(edges, p.d_edge, p.shape.edge_b * p.samples, hipMemcpyDeviceToHost));
+  return EPV_OK;
+}
+
+
 // ---- domain size spectra (epv_domains.h)
 EPV_API int epv_set_domain_stats(epv_ctx *c, uint64_t max_samples) {
   if (!max_samples) return layer_set_off(c, kDomains);
@@ -4334,24 +4167,11 @@ EPV_API int epv_set_domain_stats(epv_ctx *c, uint64_t max_samples) {
   return layer_set_on(c, kDomains, domains_alloc);
 }
 
-EPV_API int epv_reset_domain_stats(epv_ctx *c) {
-  const int rc = layer_entry(c, kDomains);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_hist, 0, (size_t)16u * EPV_DOM_BINS * c->dm.N, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_len, 0, (size_t)16u * c->dm.N, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->dm.d_edge, 0, (size_t)16u * c->dm.N * c->dm.max, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->dm.samples = 0;
-  return EPV_OK;
-}
+EPV_API int epv_reset_domain_stats(epv_ctx *c) { return c ? part_reset(c, kDomainsPart, c->dm) : EPV_ERR_ARG; }
 
 EPV_API int epv_accumulate_domain_stats(epv_ctx *c) { return layer_accumulate(c, kDomains); }
 
-EPV_API int epv_domain_stats_samples(epv_ctx *c, uint64_t *n) {
-  if (!c || !n) return EPV_ERR_ARG;
-  *n = c->dm.samples;   // (0 while the layer is off)
-  return EPV_OK;
-}
+EPV_API int epv_domain_stats_samples(epv_ctx *c, uint64_t *n) { return part_samples(c, c ? &c->dm : nullptr, n); }
 
 EPV_API int epv_domain_stats_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_bins, uint64_t *first, uint64_t *count,
                                     uint64_t *chunk_sites) {
@@ -4359,12 +4179,9 @@ EPV_API int epv_domain_stats_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_b
   *n_nodes = *n_bins = 0;
   *first = *count = *chunk_sites = 0;
   if (!c->dm.on) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->dm.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_domains(c);
-    if (rc) return rc;
-  }
-  *n_nodes = c->dm.N;
+  const int rc = part_layout_entry(c, kDomainsPart, c->dm);
+  if (rc) return rc;
+  *n_nodes = c->dm.shape.rows;
   *n_bins = EPV_DOM_BINS;
   *first = c->dm.at.lo;
   *count = c->dm.at.cnt;
@@ -4373,15 +4190,7 @@ EPV_API int epv_domain_stats_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_b
 }
 
 EPV_API int epv_get_domain_stats(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
-  const int rc = layer_entry(c, kDomains);
-  if (rc) return rc;
-  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(hist, c->dm.d_hist, (size_t)16u * EPV_DOM_BINS * c->dm.N, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(len_sum, c->dm.d_len, (size_t)16u * c->dm.N, hipMemcpyDeviceToHost));
-  if (c->dm.samples)
-    HIP_TRY(c, hipMemcpy(edges, c->dm.d_edge, (size_t)16u * c->dm.N * c->dm.samples, hipMemcpyDeviceToHost));
-  return EPV_OK;
+  return c ? part_get(c, kDomainsPart, c->dm, hist, len_sum, edges) : EPV_ERR_ARG;
 }
 
 // ---- domain turnover (epv_turnover.h)
@@ -4396,24 +4205,11 @@ EPV_API int epv_set_domain_turnover(epv_ctx *c, uint64_t max_samples) {
   return layer_set_on(c, kTurnover, turnover_alloc);
 }
 
-EPV_API int epv_reset_domain_turnover(epv_ctx *c) {
-  const int rc = layer_entry(c, kTurnover);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->to.d_hist, 0, (size_t)32u * EPV_DOM_BINS * c->to.R, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->to.d_len, 0, (size_t)32u * c->to.R, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->to.d_edge, 0, (size_t)16u * c->to.R * c->to.max, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->to.samples = 0;
-  return EPV_OK;
-}
+EPV_API int epv_reset_domain_turnover(epv_ctx *c) { return c ? part_reset(c, kTurnoverPart, c->to) : EPV_ERR_ARG; }
 
 EPV_API int epv_accumulate_domain_turnover(epv_ctx *c) { return layer_accumulate(c, kTurnover); }
 
-EPV_API int epv_domain_turnover_samples(epv_ctx *c, uint64_t *n) {
-  if (!c || !n) return EPV_ERR_ARG;
-  *n = c->to.samples;   // (0 while the layer is off)
-  return EPV_OK;
-}
+EPV_API int epv_domain_turnover_samples(epv_ctx *c, uint64_t *n) { return part_samples(c, c ? &c->to : nullptr, n); }
 
 EPV_API int epv_domain_turnover_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *n_bins, uint64_t *first, uint64_t *count,
                                        uint64_t *chunk_sites) {
@@ -4421,12 +4217,9 @@ EPV_API int epv_domain_turnover_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *n
   *n_rows = *n_bins = 0;
   *first = *count = *chunk_sites = 0;
   if (!c->to.on) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->to.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_turnover(c);
-    if (rc) return rc;
-  }
-  *n_rows = c->to.R;
+  const int rc = part_layout_entry(c, kTurnoverPart, c->to);
+  if (rc) return rc;
+  *n_rows = c->to.shape.rows;
   *n_bins = EPV_DOM_BINS;
   *first = c->to.at.lo;
   *count = c->to.at.cnt;
@@ -4435,15 +4228,7 @@ EPV_API int epv_domain_turnover_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *n
 }
 
 EPV_API int epv_get_domain_turnover(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
-  const int rc = layer_entry(c, kTurnover);
-  if (rc) return rc;
-  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(hist, c->to.d_hist, (size_t)32u * EPV_DOM_BINS * c->to.R, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(len_sum, c->to.d_len, (size_t)32u * c->to.R, hipMemcpyDeviceToHost));
-  if (c->to.samples)
-    HIP_TRY(c, hipMemcpy(edges, c->to.d_edge, (size_t)16u * c->to.R * c->to.samples, hipMemcpyDeviceToHost));
-  return EPV_OK;
+  return c ? part_get(c, kTurnoverPart, c->to, hist, len_sum, edges) : EPV_ERR_ARG;
 }
 
 // ---- change tracts (epv_tracts.h)
@@ -4458,24 +4243,11 @@ EPV_API int epv_set_change_tracts(epv_ctx *c, uint64_t max_samples) {
   return layer_set_on(c, kTracts, tracts_alloc);
 }
 
-EPV_API int epv_reset_change_tracts(epv_ctx *c) {
-  const int rc = layer_entry(c, kTracts);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_hist, 0, (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * c->tr.B, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_len, 0, (size_t)8u * EPV_TRACT_CLASSES * c->tr.B, c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->tr.d_edge, 0, (size_t)16u * c->tr.B * c->tr.max, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->tr.samples = 0;
-  return EPV_OK;
-}
+EPV_API int epv_reset_change_tracts(epv_ctx *c) { return c ? part_reset(c, kTractsPart, c->tr) : EPV_ERR_ARG; }
 
 EPV_API int epv_accumulate_change_tracts(epv_ctx *c) { return layer_accumulate(c, kTracts); }
 
-EPV_API int epv_change_tracts_samples(epv_ctx *c, uint64_t *n) {
-  if (!c || !n) return EPV_ERR_ARG;
-  *n = c->tr.samples;   // (0 while the layer is off)
-  return EPV_OK;
-}
+EPV_API int epv_change_tracts_samples(epv_ctx *c, uint64_t *n) { return part_samples(c, c ? &c->tr : nullptr, n); }
 
 EPV_API int epv_change_tracts_layout(epv_ctx *c, uint32_t *n_branches, uint32_t *n_classes, uint32_t *n_bins, uint64_t *first,
                                      uint64_t *count, uint64_t *chunk_sites) {
@@ -4483,12 +4255,9 @@ EPV_API int epv_change_tracts_layout(epv_ctx *c, uint32_t *n_branches, uint32_t 
   *n_branches = *n_classes = *n_bins = 0;
   *first = *count = *chunk_sites = 0;
   if (!c->tr.on) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->tr.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_tracts(c);
-    if (rc) return rc;
-  }
-  *n_branches = c->tr.B;
+  const int rc = part_layout_entry(c, kTractsPart, c->tr);
+  if (rc) return rc;
+  *n_branches = c->tr.shape.rows / 2u;
   *n_classes = EPV_TRACT_CLASSES;
   *n_bins = EPV_DOM_BINS;
   *first = c->tr.at.lo;
@@ -4498,15 +4267,7 @@ EPV_API int epv_change_tracts_layout(epv_ctx *c, uint32_t *n_branches, uint32_t 
 }
 
 EPV_API int epv_get_change_tracts(epv_ctx *c, uint64_t *hist, uint64_t *len_sum, uint64_t *edges) {
-  const int rc = layer_entry(c, kTracts);
-  if (rc) return rc;
-  if (!hist || !len_sum || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(hist, c->tr.d_hist, (size_t)8u * EPV_TRACT_CLASSES * EPV_DOM_BINS * c->tr.B, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(len_sum, c->tr.d_len, (size_t)8u * EPV_TRACT_CLASSES * c->tr.B, hipMemcpyDeviceToHost));
-  if (c->tr.samples)
-    HIP_TRY(c, hipMemcpy(edges, c->tr.d_edge, (size_t)16u * c->tr.B * c->tr.samples, hipMemcpyDeviceToHost));
-  return EPV_OK;
+  return c ? part_get(c, kTractsPart, c->tr, hist, len_sum, edges) : EPV_ERR_ARG;
 }
 
 // ---- spatial correlations (epv_corr.h)
@@ -4524,23 +4285,11 @@ EPV_API int epv_set_spatial_correlation(epv_ctx *c, uint32_t max_lag, uint64_t m
   return layer_set_on(c, kCorr, corr_alloc);
 }
 
-EPV_API int epv_reset_spatial_correlation(epv_ctx *c) {
-  const int rc = layer_entry(c, kCorr);
-  if (rc) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->co.d_n11, 0, (size_t)8u * c->co.R * (c->co.L + 1u), c->stream));
-  HIP_TRY(c, hipMemsetAsync(c->co.d_edge, 0, (size_t)16u * c->co.R * c->co.LW * c->co.max, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->co.samples = 0;
-  return EPV_OK;
-}
+EPV_API int epv_reset_spatial_correlation(epv_ctx *c) { return c ? part_reset(c, kCorrPart, c->co) : EPV_ERR_ARG; }
 
 EPV_API int epv_accumulate_spatial_correlation(epv_ctx *c) { return layer_accumulate(c, kCorr); }
 
-EPV_API int epv_spatial_correlation_samples(epv_ctx *c, uint64_t *n) {
-  if (!c || !n) return EPV_ERR_ARG;
-  *n = c->co.samples;   // (0 while the layer is off)
-  return EPV_OK;
-}
+EPV_API int epv_spatial_correlation_samples(epv_ctx *c, uint64_t *n) { return part_samples(c, c ? &c->co : nullptr, n); }
 
 EPV_API int epv_spatial_correlation_layout(epv_ctx *c, uint32_t *n_rows, uint32_t *max_lag, uint64_t *first,
                                            uint64_t *count, uint64_t *chunk_sites) {
@@ -4548,12 +4297,9 @@ EPV_API int epv_spatial_correlation_layout(epv_ctx *c, uint32_t *n_rows, uint32_
   *n_rows = *max_lag = 0;
   *first = *count = *chunk_sites = 0;
   if (!corr_on(c)) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->co.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_corr(c);
-    if (rc) return rc;
-  }
-  *n_rows = c->co.R;
+  const int rc = part_layout_entry(c, kCorrPart, c->co);
+  if (rc) return rc;
+  *n_rows = c->co.shape.rows;
   *max_lag = c->co.L;
   *first = c->co.at.lo;
   *count = c->co.at.cnt;
@@ -4562,14 +4308,7 @@ EPV_API int epv_spatial_correlation_layout(epv_ctx *c, uint32_t *n_rows, uint32_
 }
 
 EPV_API int epv_get_spatial_correlation(epv_ctx *c, uint64_t *n11, uint64_t *edges) {
-  const int rc = layer_entry(c, kCorr);
-  if (rc) return rc;
-  if (!n11 || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(n11, c->co.d_n11, (size_t)8u * c->co.R * (c->co.L + 1u), hipMemcpyDeviceToHost));
-  if (c->co.samples)
-    HIP_TRY(c, hipMemcpy(edges, c->co.d_edge, (size_t)16u * c->co.R * c->co.LW * c->co.samples, hipMemcpyDeviceToHost));
-  return EPV_OK;
+  return c ? part_get(c, kCorrPart, c->co, n11, nullptr, edges) : EPV_ERR_ARG;
 }
 
 // ---- domain maps (epv_dmaps.h)
@@ -4596,24 +4335,11 @@ EPV_API int epv_set_domain_maps(epv_ctx *c, uint32_t n_sizes, const uint32_t *si
   return layer_set_on(c, kDmaps, dmaps_alloc);
 }
 
-EPV_API int epv_reset_domain_maps(epv_ctx *c) {
-  const int rc = layer_entry(c, kDmaps);
-  if (rc) return rc;
-  const size_t counts_b = (size_t)4u * c->dp.N * c->dp.Z.K * c->dp.at.cnt, edge_b = (size_t)16u * c->dp.N * c->dp.EW * c->dp.max;
-  if (counts_b) HIP_TRY(c, hipMemsetAsync(c->dp.d_counts, 0, counts_b, c->stream));
-  if (edge_b) HIP_TRY(c, hipMemsetAsync(c->dp.d_edge, 0, edge_b, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->dp.samples = 0;
-  return EPV_OK;
-}
+EPV_API int epv_reset_domain_maps(epv_ctx *c) { return c ? part_reset(c, kDmapsPart, c->dp) : EPV_ERR_ARG; }
 
 EPV_API int epv_accumulate_domain_maps(epv_ctx *c) { return layer_accumulate(c, kDmaps); }
 
-EPV_API int epv_domain_maps_samples(epv_ctx *c, uint64_t *n) {
-  if (!c || !n) return EPV_ERR_ARG;
-  *n = c->dp.samples;   // (0 while the layer is off)
-  return EPV_OK;
-}
+EPV_API int epv_domain_maps_samples(epv_ctx *c, uint64_t *n) { return part_samples(c, c ? &c->dp : nullptr, n); }
 
 EPV_API int epv_domain_maps_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_sizes, uint32_t *sizes, uint32_t *state,
                                    uint64_t *first, uint64_t *count, uint64_t *chunk_sites) {
@@ -4622,12 +4348,9 @@ EPV_API int epv_domain_maps_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_si
   for (uint32_t k = 0; k < EPV_DMAPS_MAX_SIZES; ++k) sizes[k] = 0;
   *first = *count = *chunk_sites = 0;
   if (!dmaps_on(c)) return EPV_OK;
-  if (c->have_tree && c->have_paths && !c->dp.samples) {   // (no samples yet: lay out for the tree and sites as they are now)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_dmaps(c);
-    if (rc) return rc;
-  }
-  *n_nodes = c->dp.N;
+  const int rc = part_layout_entry(c, kDmapsPart, c->dp);
+  if (rc) return rc;
+  *n_nodes = c->dp.shape.rows;
   *n_sizes = c->dp.Z.K;
   for (uint32_t k = 0; k < c->dp.Z.K; ++k) sizes[k] = c->dp.Z.L[k];
   *state = c->dp.state;
@@ -4638,15 +4361,7 @@ EPV_API int epv_domain_maps_layout(epv_ctx *c, uint32_t *n_nodes, uint32_t *n_si
 }
 
 EPV_API int epv_get_domain_maps(epv_ctx *c, uint32_t *counts, uint64_t *edges) {
-  const int rc = layer_entry(c, kDmaps);
-  if (rc) return rc;
-  if (!counts || !edges) return fail(c, EPV_ERR_ARG, "null output");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const size_t counts_b = (size_t)4u * c->dp.N * c->dp.Z.K * c->dp.at.cnt;
-  const size_t edge_b = (size_t)16u * c->dp.N * c->dp.EW * c->dp.samples;
-  if (counts_b) HIP_TRY(c, hipMemcpy(counts, c->dp.d_counts, counts_b, hipMemcpyDeviceToHost));
-  if (edge_b) HIP_TRY(c, hipMemcpy(edges, c->dp.d_edge, edge_b, hipMemcpyDeviceToHost));
-  return EPV_OK;
+  return c ? part_get(c, kDmapsPart, c->dp, counts, nullptr, edges) : EPV_ERR_ARG;
 }
 
 EPV_API int epv_window_counts_to_stats(epv_ctx *c, const int64_t *counts, uint64_t n_windows, uint64_t samples,

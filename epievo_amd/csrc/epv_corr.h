@@ -10,7 +10,7 @@
 // child, x_v = a XOR (k & 1)); row N + b is the net change of branch b, k & 1.
 //
 // Two launches per sample:
-//   epv_corr_pack_kernel    one wave per tile of 64 consecutive counted sites -> bits[r][tile] (64-bit words)
+//   epv_rows_pack_kernel    the node rows of state 1, then the change rows (epv_rows.h) -> bits[r][tile]
 //   epv_corr_count_kernel   one block per chunk of EPV_CORR_CHUNK_WORDS words of one row: the chunk and the words
 //                           a pair that starts in it can reach are staged in LDS; a thread owns lags and walks the
 //                           chunk's words with a shifted AND and a popcount.  The first and the last chunk's block
@@ -27,6 +27,7 @@
 
 #include "epv_device.h"
 #include "epv_domains.h"
+#include "epv_rows.h"
 
 #define EPV_CORR_MAX_LAG 1024u
 #define EPV_CORR_MAX_LW (EPV_CORR_MAX_LAG / 64u)
@@ -35,39 +36,6 @@
  * row, 558 over the 9 rows of a 5-node tree, for 256 CUs (1024 words would leave 16 per row) */
 #define EPV_CORR_CHUNK_WORDS 256u
 #define EPV_CORR_STAGE_WORDS (EPV_CORR_CHUNK_WORDS + EPV_CORR_MAX_LW + 1u)
-
-// bits[r * words + tile]: bit j of a word = X_r[lo + 64 tile + j], zero beyond cnt.  Tiles start at lo, not at a
-// multiple of 64.  sel once, then the current buffer's meta words of all branches, EPV_DOM_BCH loads at a time.
-// child0 = the lowest-numbered child of the root.  blockDim = 256: four tiles per block.
-__global__ __launch_bounds__(256) void epv_corr_pack_kernel(EpvDev S, uint64_t lo, uint64_t cnt, uint64_t words,
-                                                            uint32_t child0, unsigned long long *bits) {
-  const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (tile >= words) return;   // (wave-uniform)
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t s = tile * 64u + lane, n = S.n;
-  const bool in = s < cnt;
-  const uint64_t site = lo + (in ? s : cnt - 1u);   // (a lane beyond the range reads the last site and counts as 0)
-  const uint32_t B = S.B, N = S.N;
-  const epv_meta_t *m = S.meta + (S.sel[site] ? (uint64_t)B * n : 0ull) + site;
-  for (uint32_t b0 = 0; b0 < B; b0 += EPV_DOM_BCH) {
-    uint32_t w[EPV_DOM_BCH];
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) w[i] = b0 + i < B ? (uint32_t)m[(uint64_t)(b0 + i) * n] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) {
-      if (b0 + i >= B) break;   // (uniform)
-      const uint32_t a = w[i] >> EPV_INIT_SHIFT, k = w[i] & EPV_NJ_MASK;
-      const unsigned long long x = __ballot(in && ((a ^ k) & 1u));
-      const unsigned long long r = __ballot(in && (a & 1u));
-      const unsigned long long ch = __ballot(in && (k & 1u));
-      if (lane == 0u) {
-        bits[(uint64_t)(b0 + i + 1u) * words + tile] = x;
-        if (b0 + i + 1u == child0) bits[tile] = r;
-        bits[(uint64_t)(N + b0 + i) * words + tile] = ch;
-      }
-    }
-  }
-}
 
 // bits s .. s + 63 of the 128-bit string (a low, b high), 0 <= s < 64; no shift by 64 is formed
 __device__ __forceinline__ unsigned long long epv_corr_window(unsigned long long a, unsigned long long b, uint32_t s) {

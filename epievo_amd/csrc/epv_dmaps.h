@@ -10,8 +10,7 @@
 // dilate by L (every site of such a run).
 //
 // Two launches per sample:
-//   epv_dmaps_pack_kernel     one wave per tile of 64 consecutive counted sites -> bits[v][tile] (64-bit words); the
-//                             twin of epv_dom_pack_kernel with the state to indicate
+//   epv_rows_pack_kernel      the node rows of the state to indicate (epv_rows.h) -> bits[v][tile]
 //   epv_dmaps_member_kernel   one block per chunk of EPV_DMAPS_CHUNK_WORDS words of one node's row: the chunk and a
 //                             halo on either side are held a word (or two) per thread and exchanged through LDS for
 //                             every shifted AND / OR; spans double, and the erosion of a size continues that of the
@@ -29,6 +28,7 @@
 
 #include "epv_device.h"
 #include "epv_domains.h"
+#include "epv_rows.h"
 
 #define EPV_DMAPS_MAX_SIZE 1024u
 #define EPV_DMAPS_MAX_SIZES 4u
@@ -44,36 +44,6 @@ struct EpvDmapSizes {
   uint32_t K;                          // 1 .. EPV_DMAPS_MAX_SIZES
   uint32_t L[EPV_DMAPS_MAX_SIZES];     // strictly increasing, 1 .. EPV_DMAPS_MAX_SIZE
 };
-
-// bits[v * words + tile]: bit j of a word = (x_v[lo + 64 tile + j] == state), zero beyond cnt.  Otherwise as
-// epv_dom_pack_kernel: tiles start at lo, sel once, EPV_DOM_BCH meta loads at a time, four tiles per block.
-__global__ __launch_bounds__(256) void epv_dmaps_pack_kernel(EpvDev S, uint64_t lo, uint64_t cnt, uint64_t words,
-                                                             uint32_t child0, uint32_t state, unsigned long long *bits) {
-  const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (tile >= words) return;   // (wave-uniform)
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t s = tile * 64u + lane, n = S.n;
-  const bool in = s < cnt;
-  const uint64_t site = lo + (in ? s : cnt - 1u);   // (a lane beyond the range reads the last site and counts as 0)
-  const uint32_t B = S.B;
-  const epv_meta_t *m = S.meta + (S.sel[site] ? (uint64_t)B * n : 0ull) + site;
-  for (uint32_t b0 = 0; b0 < B; b0 += EPV_DOM_BCH) {
-    uint32_t w[EPV_DOM_BCH];
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) w[i] = b0 + i < B ? (uint32_t)m[(uint64_t)(b0 + i) * n] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) {
-      if (b0 + i >= B) break;   // (uniform)
-      const uint32_t a = w[i] >> EPV_INIT_SHIFT, k = w[i] & EPV_NJ_MASK;
-      const unsigned long long x = __ballot(in && ((a ^ k) & 1u) == state);
-      const unsigned long long r = __ballot(in && (a & 1u) == state);
-      if (lane == 0u) {
-        bits[(uint64_t)(b0 + i + 1u) * words + tile] = x;
-        if (b0 + i + 1u == child0) bits[tile] = r;
-      }
-    }
-  }
-}
 
 // word i of the staged string, zero outside it
 __device__ __forceinline__ unsigned long long epv_dmaps_at(const unsigned long long *w, uint32_t total, int32_t i) {

@@ -10,7 +10,7 @@
 // x[p] != x[p + 1]; the run that ends there has length p - p' (p' = the previous end) and state x[p].
 //
 // Two launches per sample:
-//   epv_dom_pack_kernel   one wave per tile of 64 consecutive counted sites -> bits[v][tile] (64-bit words)
+//   epv_rows_pack_kernel  the node rows of state 1 (epv_rows.h) -> bits[v][tile] (64-bit words)
 //   epv_dom_runs_kernel   one block per chunk of EPV_DOM_CHUNK_WORDS words of one node's row: end masks, the
 //                         position of the last end before each thread's words (a cooperative look-back for the
 //                         chunk, a prefix maximum inside it), run lengths binned in LDS
@@ -24,41 +24,10 @@
 
 #include "epv_device.h"
 #include "epv_domain_bin.h"
+#include "epv_rows.h"
 
-#define EPV_DOM_BCH 8u                /* branches whose meta loads are in flight together */
 #define EPV_DOM_CHUNK_WORDS 1024u     /* words of a node's row per block of the runs kernel: 65 536 sites */
 #define EPV_DOM_WPT (EPV_DOM_CHUNK_WORDS / 256u)   /* consecutive words per thread */
-
-// bits[v * words + tile]: bit j of a word = x_v[lo + 64 tile + j], zero beyond cnt.  Tiles start at lo, not at a
-// multiple of 64.  sel once, then the current buffer's meta words of all branches, EPV_DOM_BCH loads at a time.
-// child0 = the lowest-numbered child of the root.  blockDim = 256: four tiles per block.
-__global__ __launch_bounds__(256) void epv_dom_pack_kernel(EpvDev S, uint64_t lo, uint64_t cnt, uint64_t words,
-                                                           uint32_t child0, unsigned long long *bits) {
-  const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (tile >= words) return;   // (wave-uniform)
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t s = tile * 64u + lane, n = S.n;
-  const bool in = s < cnt;
-  const uint64_t site = lo + (in ? s : cnt - 1u);   // (a lane beyond the range reads the last site and counts as 0)
-  const uint32_t B = S.B;
-  const epv_meta_t *m = S.meta + (S.sel[site] ? (uint64_t)B * n : 0ull) + site;
-  for (uint32_t b0 = 0; b0 < B; b0 += EPV_DOM_BCH) {
-    uint32_t w[EPV_DOM_BCH];
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) w[i] = b0 + i < B ? (uint32_t)m[(uint64_t)(b0 + i) * n] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) {
-      if (b0 + i >= B) break;   // (uniform)
-      const uint32_t a = w[i] >> EPV_INIT_SHIFT, k = w[i] & EPV_NJ_MASK;
-      const unsigned long long x = __ballot(in && ((a ^ k) & 1u));
-      const unsigned long long r = __ballot(in && a);
-      if (lane == 0u) {
-        bits[(uint64_t)(b0 + i + 1u) * words + tile] = x;
-        if (b0 + i + 1u == child0) bits[tile] = r;
-      }
-    }
-  }
-}
 
 // the end mask of word i of a row: bit j set where x[64 i + j] != x[64 i + j + 1] and 64 i + j + 1 < cnt
 __device__ __forceinline__ unsigned long long epv_dom_ends(unsigned long long w, unsigned long long next, uint64_t i,

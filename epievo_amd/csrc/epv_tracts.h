@@ -11,7 +11,7 @@
 // and p + 1 < cnt; a tract that holds the stretch's first or last site goes to an edge record (epv_tract_rec.h).
 //
 // Two launches per sample:
-//   epv_turn_pack_kernel    the turnover's, unchanged, into this layer's own scratch
+//   epv_rows_pack_kernel    the end rows (epv_rows.h), as the turnover packs them, into this layer's own scratch
 //   epv_tract_runs_kernel   one block per chunk of EPV_DOM_CHUNK_WORDS words of one branch: the scan carries the last
 //                           start, the flank before it and the directions met since
 // No block waits for another.  Integer adds commute and every edge record has one writer: the result depends on
@@ -24,6 +24,7 @@
 
 #include "epv_device.h"
 #include "epv_domains.h"
+#include "epv_rows.h"
 #include "epv_tract_rec.h"
 
 // the classes a block can close: 3 directions x 2 left flanks x 2 right flanks (a flank "none" goes to a record)

@@ -10,7 +10,7 @@
 // is kept iff K has a bit inside it.
 //
 // Two launches per sample:
-//   epv_turn_pack_kernel   one wave per tile of 64 consecutive counted sites -> bits[r][tile]
+//   epv_rows_pack_kernel   the end rows (epv_rows.h) -> bits[r][tile]
 //   epv_turn_runs_kernel   one block per chunk of EPV_DOM_CHUNK_WORDS words of one row: the runs kernel of the
 //                          domain size spectra, with a pair (last end, OR of K after it) where that one carries
 //                          the last end alone
@@ -24,37 +24,8 @@
 
 #include "epv_device.h"
 #include "epv_domains.h"
+#include "epv_rows.h"
 #include "epv_turnover_rec.h"
-
-// bits[r * words + tile]: bit j of a word = X_r[lo + 64 tile + j], zero beyond cnt.  blockDim = 256: four tiles
-// per block.
-__global__ __launch_bounds__(256) void epv_turn_pack_kernel(EpvDev S, uint64_t lo, uint64_t cnt, uint64_t words,
-                                                            unsigned long long *bits) {
-  const uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (tile >= words) return;   // (wave-uniform)
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t s = tile * 64u + lane, n = S.n;
-  const bool in = s < cnt;
-  const uint64_t site = lo + (in ? s : cnt - 1u);   // (a lane beyond the range reads the last site and counts as 0)
-  const uint32_t B = S.B;
-  const epv_meta_t *m = S.meta + (S.sel[site] ? (uint64_t)B * n : 0ull) + site;
-  for (uint32_t b0 = 0; b0 < B; b0 += EPV_DOM_BCH) {
-    uint32_t w[EPV_DOM_BCH];
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) w[i] = b0 + i < B ? (uint32_t)m[(uint64_t)(b0 + i) * n] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < EPV_DOM_BCH; ++i) {
-      if (b0 + i >= B) break;   // (uniform)
-      const uint32_t a = w[i] >> EPV_INIT_SHIFT, k = w[i] & EPV_NJ_MASK;
-      const unsigned long long xa = __ballot(in && (a & 1u));
-      const unsigned long long xe = __ballot(in && ((a ^ k) & 1u));
-      if (lane == 0u) {
-        bits[(uint64_t)(2u * (b0 + i)) * words + tile] = xa;
-        bits[(uint64_t)(2u * (b0 + i) + 1u) * words + tile] = xe;
-      }
-    }
-  }
-}
 
 // the keep word of word i of a row x and its partner y: bit j set where x and y agree and 64 i + j < cnt
 __device__ __forceinline__ unsigned long long epv_turn_keep(unsigned long long x, unsigned long long y, uint64_t i,
